@@ -10,12 +10,13 @@ figure and the one-GPU basis of the same 8M workload travel as secondary keys of
 ONE pass defines the line: a "step" is one complete BLOCKING pricing --
 `MonteCarloPricer.price(S, K, T, r, sigma, "call", seed=..., return_error=True)` at N = 1 (one path kernel with its
 fused reduction, result on the host), and at N > 1 the same thing sharded: this rank's kernel on its block of the
-global paths -> the all-reduce -> result on the host of every rank.  After W untimed warm-up steps a pass times EXACTLY
-K steps between barrier + synchronise fences (max over ranks); passes repeat until >= 1.5 s are covered, and
+global paths -> the all-reduce -> result on the host of every rank.  After W untimed warm-up steps the K seeds run once
+with HIP events attached to every dispatch, then ONE pass times EXACTLY K steps of the same seeds between barrier +
+synchronise fences (max over ranks), and
 
-    value                  = global paths x 252 x K / median pass time
-    ms_per_step            = median pass time / K
-    roofline.avg_kernel_ms = HIP events attached to the dispatches of those very calls
+    value                  = global paths x 252 x K / pass time
+    ms_per_step            = pass time / K
+    roofline.avg_kernel_ms = HIP events attached to the dispatches of the first run of those calls
 
 so `avg_kernel_ms <= ms_per_step` by construction.  `roofline.frac` is an issue-cycle fraction: VALU issue cycles the
 kernel's instruction stream needs per launch (rocprofv3 PMC, collected LIVE by a child pass of this script before the
@@ -25,6 +26,9 @@ stdout carries ONE JSON line of <= 3 KB (`compact_line`): the contract keys, `ro
 {value, ms, frac} entries for configs[2] (`c3`), [3] (`c4`), [4] (`c5`).  Everything else -- issue tables, instruction
 mixes, per-pass seconds, probes -- goes to the sidecar file the line names in `detail` (bench_detail.json next to this
 script; copies of record live under profiles/).
+
+`--dump-outputs DIR` writes what the last timed step returned to its caller (price, std_error, n_paths; one float64 .npy
+each).  That step's seed is SEED + K - 1, so runs with equal arguments price identical inputs.
 
 torch is plumbing here (device result slots, stream handle, process group); the compute is libolmc.so through its
 C ABI.  With N > 1 and no launcher in the environment (WORLD_SIZE unset) this script starts its own N ranks as a child
@@ -534,6 +538,14 @@ def write_detail(full):
         return None
 
 
+def dump_outputs(out_dir, result):
+    """--dump-outputs: the (price, std_error, n_paths) the last timed step handed its caller, one float64 .npy per field."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, x in zip(("price", "std_error", "n_paths"), result):
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(x, dtype=np.float64))
+
+
 # ------------------------------------------------------------------------------------------------ launcher (N > 1, no torchrun around)
 def launch_ranks(args):
     """`python3 bench.py --gpus N` on its own: this process never touches a GPU; it starts the N ranks as ONE child process
@@ -581,9 +593,8 @@ def main():
     ap.add_argument("--pmc-keep", default=None, help="directory to keep the rocprofv3 CSVs of the live passes in")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--single-process-child", action="store_true", help=argparse.SUPPRESS)
-    ap.add_argument("--min-seconds", type=float, default=1.5,
-                    help="timed passes repeat until the plain ones alone cover this much wall time (as many instrumented ones ride along: the GPU "
-                         "is busy for about twice this, which an outside utilisation sampler can see)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned (price, std_error, n_paths) to DIR/<name>.npy as float64")
     ap.add_argument("--paths-per-gpu", type=int, default=0,
                     help="default: 1,000,000 at --gpus 1 (BASELINE configs[1]), 8,000,000 at --gpus N > 1 (configs[4]'s per-GPU shard)")
     args = ap.parse_args()
@@ -705,16 +716,18 @@ def worker(args):
             return price, se, int(n)
         return step
 
-    def timed_passes(step, n_global, steps, warm, min_total_s=1.5, max_passes=1000, seed0=0):
+    def timed_passes(step, n_global, steps, warm, min_total_s=1.5, max_passes=1000, seed0=0, min_passes=3):
         """warm untimed steps, then passes of EXACTLY `steps` blocking steps, each between fences; max over ranks per pass.
-        Passes ALTERNATE plain / instrumented: an instrumented pass is the same loop with a HIP event pair attached to
+        Passes ALTERNATE instrumented / plain: an instrumented pass is the same loop with a HIP event pair attached to
         every dispatch (the kernel's own begin / end timestamps).  Attaching the pair puts a marker packet in front of the
         kernel, which costs a blocking call several microseconds, so the events ride on every other pass instead of
         on all of them: `value` comes from the plain passes, the kernel duration from the instrumented ones, and both
-        pass times are reported.  Passes repeat until the plain ones alone cover `min_total_s` (at least 3, at most `max_passes`
-        of each kind).  Returns (plain pass times, instrumented pass times, per-call times of
-        the plain passes on this rank, avg kernel seconds, launches timed, worst |price - BS| / se, prices of the first pass)."""
-        worst, calls, first = 0.0, [], []
+        pass times are reported.  An instrumented pass goes first, so every plain pass follows `steps` steps of the same load
+        (a first pass straight after the event pool's creation runs ~3 % slow at 20 steps).  Passes repeat until the plain
+        ones alone cover `min_total_s` (at least `min_passes`, at most `max_passes` of each kind).  Returns (plain pass times, instrumented pass times, per-call times of
+        the plain passes on this rank, avg kernel seconds, launches timed, worst |price - BS| / se, prices of the first pass,
+        the (price, std_error, n) of the last plain step)."""
+        worst, calls, first, last = 0.0, [], [], None
 
         def check(res):
             nonlocal worst
@@ -728,8 +741,8 @@ def worker(args):
         _hip.profile_reset()
         passes, inst_passes = [], []
         # every rank sees the same max-reduced pass times, so every rank stops after the same pass
-        while len(inst_passes) < len(passes) or len(passes) < 3 or (sum(passes) < min_total_s and len(passes) < max_passes):
-            instrumented = len(passes) > len(inst_passes)          # plain, instrumented, plain, ...
+        while len(passes) < len(inst_passes) or len(passes) < min_passes or (sum(passes) < min_total_s and len(passes) < max_passes):
+            instrumented = len(inst_passes) == len(passes)         # instrumented, plain, instrumented, ...
             _hip.profile_enable(instrumented)
             base = seed0 + (len(passes if not instrumented else inst_passes) * steps) % 1_000_000     # both kinds walk the same seeds
             results, stamps, pc = [], [], time.perf_counter
@@ -745,6 +758,7 @@ def worker(args):
                 check(res)
             if not instrumented:
                 calls.extend(b - a for a, b in zip([t0] + stamps[:-1], stamps))
+                last = results[-1]
             if not passes and not instrumented:
                 first.extend(res[0] for res in results)
             (inst_passes if instrumented else passes).append(dt)
@@ -753,7 +767,7 @@ def worker(args):
         launches, kernel_ms = _hip.kernel_time()
         _hip.profile_enable(False)
         avg_kernel_s = kernel_ms / 1e3 / launches if launches else None
-        return passes, inst_passes, calls, avg_kernel_s, launches, worst, first
+        return passes, inst_passes, calls, avg_kernel_s, launches, worst, first, last
 
     # Before anything is timed the device gets ~150 ms of the same work (untimed, `pre_warm_ms`): an idle MI355X needs tens
     # of milliseconds of load to reach its sustained clocks.  A FIXED count, not a clock: every rank enters the same
@@ -774,9 +788,12 @@ def worker(args):
         dist.all_reduce(ones, op=dist.ReduceOp.SUM)
         ranks_seen = int(ones.item())
 
-    passes, inst_passes, calls, avg_kernel_s, launches, worst, first_prices = timed_passes(step_main, n_global, K_steps, W,
-                                                                                           min_total_s=args.min_seconds)     # THE measured passes
+    # THE measured pass: exactly K timed steps, behind one run of the same K seeds with events attached (the kernel time)
+    passes, inst_passes, calls, avg_kernel_s, launches, worst, first_prices, last = timed_passes(step_main, n_global, K_steps, W,
+                                                                                                 min_total_s=0.0, min_passes=1)
     assert worst <= 5.5, f"a step's price is {worst:.2f} sigma from Black-Scholes"     # max of up to ~50,000 draws of |N(0,1)|: P(> 5.5) ~ 2e-3
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
     pass_s = statistics.median(passes)
     path_steps = n_global * N_STEPS
     value = path_steps * K_steps / pass_s
@@ -832,10 +849,10 @@ def worker(args):
                        "paths_per_gpu": paths_per_gpu, "n_steps": N_STEPS, "global_paths": n_global,
                        "parallelism": f"path-sharded x{world}" + (", 1 RCCL all-reduce of (sum,sumsq,n) per step" if world > 1 else "")
                                       + (" [REHEARSAL: all ranks on one GPU, gloo]" if rehearsal else "")},
-            "passes": {"n": len(passes), "seconds": passes, "what": f"each = exactly {K_steps} blocking steps between fences, max over ranks; "
-                                                                    "value and ms_per_step use the median pass"},
+            "passes": {"n": len(passes), "seconds": passes, "what": f"exactly {K_steps} blocking steps between fences, max over ranks; "
+                                                                    "value and ms_per_step use this pass"},
             "instrumented_passes": {"n": len(inst_passes), "ms_per_step": statistics.median(inst_passes) / K_steps * 1e3,
-                                    "what": "the same loop, same seeds, interleaved with the plain passes, with a HIP event pair attached to every "
+                                    "what": "the same loop, same seeds, run before the plain pass, with a HIP event pair attached to every "
                                             "dispatch -> roofline.avg_kernel_ms. The pair's start marker is an extra packet in front of the kernel: "
                                             "the difference to ms_per_step is its price, which is why `value` is not taken from these passes"},
             "per_call": {"median_ms": statistics.median(calls) * 1e3, "min_ms": min(calls) * 1e3, "p90_ms": sorted(calls)[int(0.9 * (len(calls) - 1))] * 1e3,
@@ -890,7 +907,7 @@ def worker(args):
     def side(n_glob, steps, what, sharded=None, key=None, min_total_s=0.1):
         """A secondary workload through the same timed_passes: {value, ms_per_step, avg_kernel_ms, roofline, ...}."""
         step = make_step(n_glob, sharded)
-        ps, _ips, cs, ks, ln, wst, _first = timed_passes(step, n_glob, steps, 2, min_total_s=min_total_s, max_passes=12, seed0=7_000_000)
+        ps, _ips, cs, ks, ln, wst, _first, _last = timed_passes(step, n_glob, steps, 2, min_total_s=min_total_s, max_passes=12, seed0=7_000_000)
         med = statistics.median(ps)
         per_gpu = n_glob // world if (use_dist if sharded is None else sharded) else n_glob
         d = {"value": n_glob * N_STEPS * steps / med, "unit": "path-steps/s", "ms_per_step": med / steps * 1e3, "steps": steps, "passes": len(ps),

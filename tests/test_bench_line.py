@@ -186,3 +186,14 @@ def test_round_4_record_keeps_every_section_within_the_budget(bench):
     assert all(v[0] > 0 and 0 < v[1] <= 1 for k, v in line["f"].items() if k != "american_lsm") and set(line["f"]["american_lsm"]) == {"50000x50", "1000000x50"}
     assert line["c2_f64_normals"]["x_product_kernel"] > 3 and line["c5"]["single_process"]["n_gpus"] == 1
     assert {"c3", "c4", "pipelined"} <= set(line)
+
+
+def test_dump_outputs_writes_the_last_steps_result_as_float64_arrays(bench, tmp_path):
+    """--dump-outputs DIR: what the last timed step handed its caller (price, std_error, n_paths), one float64 .npy per field."""
+    import numpy as np
+    out = tmp_path / "dump"
+    bench.dump_outputs(str(out), (10.452156943040634, 0.010411613038905873, 2_000_000))
+    assert sorted(p.name for p in out.iterdir()) == ["n_paths.npy", "price.npy", "std_error.npy"]
+    got = {n: np.load(out / f"{n}.npy") for n in ("price", "std_error", "n_paths")}
+    assert all(a.dtype == np.float64 and a.shape == () for a in got.values())
+    assert got["price"] == 10.452156943040634 and got["std_error"] == 0.010411613038905873 and got["n_paths"] == 2_000_000
