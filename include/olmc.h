@@ -257,7 +257,12 @@ int olmc_asian_greeks_fd(double S, double K, double T, double r, double sigma, d
  * LookbackOption.price (:359-401) on ExoticOptionBase._generate_paths (:40-67): the
  * running max / min of ln S_t live in registers, no path matrix.  barrier_kind:
  * OLMC_BARRIER_*; fixed_strike: 0 = floating (call S_T - S_min, put S_max - S_T),
- * 1 = fixed (call max(S_max - K, 0), put max(K - S_min, 0)). */
+ * 1 = fixed (call max(S_max - K, 0), put max(K - S_min, 0)).
+ * t = 0 is decided in log space: the running extrema start at ln(S_0/S_0) = 0 and are compared with
+ * ln(barrier / S), so a barrier equal to the spot counts as crossed (up: 0 >= 0, down: 0 <= 0).  The
+ * reference monitors np.exp(np.log(S)), a few ulps off S for some spots; BarrierOption and the fused
+ * Greeks pass a level nudged by those ulps where the two rules disagree (optionslab_amd/exotic.py
+ * reference_barrier_level), tied per seed to the reference's payoff in tests/test_gpu_exotics_reference_tie.py. */
 enum { OLMC_BARRIER_UP_OUT = 0, OLMC_BARRIER_UP_IN = 1, OLMC_BARRIER_DOWN_OUT = 2, OLMC_BARRIER_DOWN_IN = 3 };
 int olmc_barrier(double S, double K, double T, double r, double sigma, double q, int is_call,
                  double barrier, int barrier_kind, int64_t path_offset, int64_t n_local,
@@ -280,6 +285,10 @@ int olmc_extrema_greeks_fd(double S, double K, double T, double r, double sigma,
  * olmc_autocallable replaces AutocallableOption.price (src/pricing_models/exotic_options.py:404-491):
  * barriers are relative to spot; out->price = mean of the per-path DISCOUNTED payoffs (the reference
  * discounts each redemption at its own date), fraction of notional.
+ * Observation dates t = f, 2f, ... <= n_steps; observation_freq > n_steps (no observation date) is refused
+ * with OLMC_ERR_ARG.  The reference prices that case (range(f, M + 1, f) is empty: every path runs to
+ * maturity); AutocallableOption reproduces it with an autocall level no path reaches.  The knock-in minimum includes t = 0 (log space,
+ * as for the barrier); that cannot move a price: a loss needs S_T/S_0 < 1, and the minimum is at most S_T/S_0.
  * olmc_cliquet replaces CliquetOption.price (:494-554): n_periods resets of n_steps // n_periods steps. */
 int olmc_autocallable(double S, double T, double r, double sigma, double q, double autocall_barrier,
                       double coupon_barrier, double coupon_rate, double ki_barrier,
@@ -301,10 +310,14 @@ int olmc_cliquet(double S, double T, double r, double sigma, double q, double lo
  * in-the-money side under the model's own law), which keeps the normal equations well conditioned where the
  * reference relies on lstsq's SVD.  Where the moment matrix is numerically singular all the same (few distinct
  * in-the-money prices: a pivot below 1e-11 of its diagonal entry) that monomial is left out of the date's fit; the
- * reference's lstsq returns the minimum-norm solution there.  PARITY with the reference is therefore STATISTICAL for
- * this entry point, per-seed parity unpinned: other normals (Philox, not PCG64) AND, in degenerate regressions, another
- * choice among the equally good fits -- gated by 3-sigma tests against the reference's own algorithm over 24 seeds and on
- * ill-conditioned cases (tests/test_gpu_exotics.py), bit-level only against the build's own checker.
+ * reference's lstsq returns the minimum-norm solution there.  Per seed, on this entry point's own paths, the price is
+ * PINNED to the reference's algorithm (oracle/numpy_reference.py american_from_paths, SVD lstsq on raw powers) to 1e-9 for
+ * degrees 1-3 on well-conditioned cases, puts and calls (tests/test_gpu_exotics_reference_tie.py): no exercise decision
+ * differs.  Degree 4 is tied to 1e-3 only: there the reference's raw-power design matrix has condition 1e11-1e13 and its
+ * own fit flips decisions against an exact one.  Against the reference's own draw (its normals, not Philox) parity is STATISTICAL,
+ * and in degenerate regressions another choice among the equally good fits is made -- gated by 3-sigma tests against the
+ * reference's algorithm over 24 seeds and on ill-conditioned cases (tests/test_gpu_exotics.py), bit-level against the
+ * build's own checker.
  * out->price = mean of the time-0 cash flows; single device. */
 int olmc_american_lsm(double S, double K, double T, double r, double sigma, double q, int is_call,
                       int64_t n_paths, int32_t n_steps, int32_t poly_degree, uint64_t seed,

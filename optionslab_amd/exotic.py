@@ -59,9 +59,33 @@ class AsianOption:
         return self.K * disc * _ncdf(-d2) - self.S * grow * _ncdf(-d1)
 
 
+def reference_barrier_level(S: float, barrier: float, barrier_type: str) -> float:
+    """The level to pass to the C ABI so that its decision at t = 0 is the reference's.
+
+    The ABI decides t = 0 in log space: ln(S_0/S_0) = 0 against ln(B/S), so a barrier at the spot counts as crossed
+    (include/olmc.h).  The reference monitors its path matrix, whose column 0 is np.exp(np.log(S)) (exotic_options.py:64-67):
+    a few ulps above S for some spots (100, 110), below it for others (80, 120), S itself for the rest (90, 95).  Where the
+    two rules disagree the level moves one ulp at a time until they agree; a later date reaches within those ulps of the level
+    only on a set of measure zero.  NumPy's exponential and libm's differ on some spots, so this is decided here, on the
+    reference's own arithmetic, and not in the C host."""
+    if not (S > 0.0 and barrier > 0.0):
+        return barrier                                                  # invalid inputs are the ABI's to judge
+    up = barrier_type.startswith("up")                                  # exotic_options.py:201-204
+    s0 = float(np.exp(np.array([np.log(S)]))[0])                        # the reference's column 0
+    wanted = (s0 >= barrier) if up else (s0 <= barrier)
+    level = float(barrier)
+    toward = math.inf if up != wanted else 0.0                          # up: a higher level crosses less; down: more
+    for _ in range(16):
+        if ((level / S <= 1.0) if up else (level / S >= 1.0)) == wanted:   # sign of ln(level/S) <= or >= the start at 0
+            return level
+        level = math.nextafter(level, toward)
+    raise AssertionError(f"no level near {barrier} reproduces the reference's t = 0 decision at S = {S}")
+
+
 @dataclass
 class BarrierOption:
-    """exotic_options.py:163-224: knock-in / knock-out on discrete monitoring dates t = 0..M."""
+    """exotic_options.py:163-224: knock-in / knock-out on discrete monitoring dates t = 0..M; at t = 0 the reference's
+    np.exp(np.log(S)) is monitored (reference_barrier_level)."""
 
     S: float
     K: float
@@ -82,7 +106,8 @@ class BarrierOption:
         # the reference dispatches on startswith("up") / endswith("out") (:201-212)
         kind = (0 if barrier_type.startswith("up") else 2) + (0 if barrier_type.endswith("out") else 1)
         seed = self.seed if self.seed is not None else int(np.random.default_rng().integers(0, 2**31))
-        st = _hip.barrier(self.S, self.K, self.T, self.r, self.sigma, self.q, option_type == "call", self.barrier, kind,
+        level = reference_barrier_level(self.S, self.barrier, barrier_type)
+        st = _hip.barrier(self.S, self.K, self.T, self.r, self.sigma, self.q, option_type == "call", level, kind,
                           n_paths, n_steps, seed, antithetic)
         return (np.float64(st.price), float(st.std_error)) if return_error else np.float64(st.price)
 
@@ -148,7 +173,11 @@ def price_american(S: float, K: float, T: float, r: float, sigma: float, option_
 
 @dataclass
 class AutocallableOption:
-    """exotic_options.py:404-491 (snowball note; barriers relative to spot; result = fraction of notional)."""
+    """exotic_options.py:404-491 (snowball note; barriers relative to spot; result = fraction of notional).  observation_freq >
+    n_steps leaves no observation date (the reference's range(f, M + 1, f) is empty) and every path runs to maturity; the C ABI
+    refuses that case, so it is priced with one observation date, on the last step, at a level no path reaches.  The knock-in minimum includes t = 0 in log space, where the reference
+    sees np.exp(np.log(S)) / S; that cannot move a price (a loss needs S_T/S < 1, and the minimum is at most S_T/S), so no level
+    is adjusted here."""
 
     S: float
     K: float
@@ -167,7 +196,10 @@ class AutocallableOption:
         if n_paths < 1 or n_steps < 1:
             raise ValueError("n_paths and n_steps must be >= 1")
         seed = self.seed if self.seed is not None else int(np.random.default_rng().integers(0, 2**31))
-        st = _hip.autocallable(self.S, self.T, self.r, self.sigma, self.q, self.autocall_barrier, self.coupon_barrier,
+        autocall_barrier = self.autocall_barrier
+        if observation_freq > n_steps:                  # no observation date: nothing redeems early (exotic_options.py:442, 448)
+            observation_freq, autocall_barrier = n_steps, math.inf
+        st = _hip.autocallable(self.S, self.T, self.r, self.sigma, self.q, autocall_barrier, self.coupon_barrier,
                                self.coupon_rate, self.ki_barrier, observation_freq, n_paths, n_steps, seed, antithetic)
         return (np.float64(st.price), float(st.std_error)) if return_error else np.float64(st.price)
 

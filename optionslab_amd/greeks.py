@@ -84,6 +84,9 @@ class ExoticAdapter:
             vals, _ = _hip.asian_greeks_fd(S, K, T, r, sigma, q, is_call, self.n_paths, self.n_steps, ex.seed, anti, include_second_order, want_evals=False,
                                            geometric=payoff == 1)
         else:
+            if payoff <= 3:     # a barrier: the mid contract's t = 0 decision is the reference's (the bumped spots are h_S away from it)
+                from .exotic import reference_barrier_level
+                level = reference_barrier_level(S, level, kw.get("barrier_type", "up-and-out"))
             vals, _ = _hip.extrema_greeks_fd(S, K, T, r, sigma, q, is_call, payoff, level, self.n_paths, self.n_steps, ex.seed, anti, include_second_order,
                                              want_evals=False)
         ex.S, ex.K, ex.T, ex.r, ex.sigma, ex.q = S, K, T, r, sigma, q

@@ -258,16 +258,25 @@ def asian_price(S, K, T, r, sigma, q=0.0, seed=None, n_paths=100000, n_steps=252
     """exotic_options.py:97-131 -- average over t=1..M (t=0 excluded).  `return_error=True` adds what the reference does not
     return: the standard error of the SAME payoffs, disc * std(x, ddof=0) / sqrt(n) as monte_carlo.py:147-149 takes it."""
     paths = asian_paths(S, T, r, sigma, q, n_paths, n_steps, seed)
+    price, x = asian_from_paths(paths, K, T, r, avg_type, option_type, return_payoffs=True)
+    if return_error:
+        return price, np.exp(-r * T) * np.std(x) / np.sqrt(n_paths)
+    return price
+
+
+# The payoffs below on a given (n_paths, n_steps + 1) path matrix, column 0 = the reference's exp(log S).  Each
+# *_price above is asian_paths followed by its *_from_paths, same operations in the same order.  return_payoffs=True
+# returns (price, x) with x the per-path values whose mean the price is (undiscounted, except where the reference
+# discounts path by path: autocallable, american).
+def asian_from_paths(paths, K, T, r, avg_type="arithmetic", option_type="call", return_payoffs=False):
+    """exotic_options.py:117-131"""
     if avg_type == "arithmetic":  # :119-120
         avg = np.mean(paths[:, 1:], axis=1)
     else:  # :121-122
         avg = np.exp(np.mean(np.log(paths[:, 1:]), axis=1))
-    del paths
     x = np.maximum(avg - K, 0) if option_type == "call" else np.maximum(K - avg, 0)  # :125-128
     price = np.exp(-r * T) * np.mean(x)  # :131  (np.float64)
-    if return_error:
-        return price, np.exp(-r * T) * np.std(x) / np.sqrt(n_paths)
-    return price
+    return (price, x) if return_payoffs else price
 
 
 def barrier_price(S, K, T, r, sigma, barrier, q=0.0, seed=None, n_paths=100000, n_steps=252,
@@ -276,28 +285,46 @@ def barrier_price(S, K, T, r, sigma, barrier, q=0.0, seed=None, n_paths=100000, 
     if barrier <= 0:  # :195-196
         raise ValueError("Barrier must be positive")
     paths = asian_paths(S, T, r, sigma, q, n_paths, n_steps, seed)
+    return barrier_from_paths(paths, K, T, r, barrier, barrier_type, option_type)
+
+
+def barrier_from_paths(paths, K, T, r, barrier, barrier_type="up-and-out", option_type="call", return_payoffs=False):
+    """exotic_options.py:200-223 -- every column is monitored, t = 0 included."""
     crossed = np.any(paths >= barrier, axis=1) if barrier_type.startswith("up") else np.any(paths <= barrier, axis=1)
     active = ~crossed if barrier_type.endswith("out") else crossed  # :207-212
     st = paths[:, -1]
     x = np.maximum(st - K, 0) if option_type == "call" else np.maximum(K - st, 0)
-    return np.exp(-r * T) * np.mean(x * active)  # :221-223
+    price = np.exp(-r * T) * np.mean(x * active)  # :221-223
+    return (price, x * active) if return_payoffs else price
 
 
 def lookback_price(S, K, T, r, sigma, q=0.0, seed=None, n_paths=100000, n_steps=252, lookback_type="floating",
                    option_type="call"):
     """exotic_options.py:359-401"""
     paths = asian_paths(S, T, r, sigma, q, n_paths, n_steps, seed)
+    return lookback_from_paths(paths, K, T, r, lookback_type, option_type)
+
+
+def lookback_from_paths(paths, K, T, r, lookback_type="floating", option_type="call", return_payoffs=False):
+    """exotic_options.py:379-401 -- extrema over every column, t = 0 included."""
     st, hi, lo = paths[:, -1], np.max(paths, axis=1), np.min(paths, axis=1)
     if lookback_type == "floating":
         x = st - lo if option_type == "call" else hi - st
     else:
         x = np.maximum(hi - K, 0) if option_type == "call" else np.maximum(K - lo, 0)
-    return np.exp(-r * T) * np.mean(x)
+    price = np.exp(-r * T) * np.mean(x)
+    return (price, x) if return_payoffs else price
 
 
 def american_price(S, K, T, r, sigma, q=0.0, seed=None, n_paths=50000, n_steps=50, option_type="put", poly_degree=3):
     """exotic_options.py:237-305 Longstaff-Schwartz."""
     paths = asian_paths(S, T, r, sigma, q, n_paths, n_steps, seed)
+    return american_from_paths(paths, K, T, r, option_type, poly_degree)
+
+
+def american_from_paths(paths, K, T, r, option_type="put", poly_degree=3, return_payoffs=False):
+    """exotic_options.py:262-305 -- n_steps = paths.shape[1] - 1; x = the discounted time-0 cash flows."""
+    n_steps = paths.shape[1] - 1
     dt = T / n_steps
     discount = np.exp(-r * dt)
     intrinsic = np.maximum(paths - K, 0) if option_type == "call" else np.maximum(K - paths, 0)
@@ -313,7 +340,8 @@ def american_price(S, K, T, r, sigma, q=0.0, seed=None, n_paths=50000, n_steps=5
             ex = intrinsic[itm, t] > cont
             idx = np.where(itm)[0][ex]
             cf[idx] = intrinsic[idx, t]
-    return np.mean(cf * discount)
+    price = np.mean(cf * discount)
+    return (price, cf * discount) if return_payoffs else price
 
 
 def exercise_boundary_from_paths(paths, K, option_type="put"):
@@ -339,6 +367,13 @@ def autocallable_price(S, T, r, sigma, q=0.0, seed=None, n_paths=100000, n_steps
                        autocall_barrier=1.0, coupon_barrier=0.8, coupon_rate=0.10, ki_barrier=0.6):
     """exotic_options.py:404-491"""
     paths = asian_paths(S, T, r, sigma, q, n_paths, n_steps, seed)
+    return autocallable_from_paths(paths, S, T, r, observation_freq, autocall_barrier, coupon_barrier, coupon_rate, ki_barrier)
+
+
+def autocallable_from_paths(paths, S, T, r, observation_freq=21, autocall_barrier=1.0, coupon_barrier=0.8, coupon_rate=0.10,
+                            ki_barrier=0.6, return_payoffs=False):
+    """exotic_options.py:438-491 -- x = the per-path payoffs, each discounted at its own date."""
+    n_paths, n_steps = paths.shape[0], paths.shape[1] - 1
     dt = T / n_steps
     obs = list(range(observation_freq, n_steps + 1, observation_freq))
     pay = np.zeros(n_paths)
@@ -356,20 +391,30 @@ def autocallable_price(S, T, r, sigma, q=0.0, seed=None, n_paths=100000, n_steps
     loss = knocked_in[still] & (rel < 1.0)  # :481-483
     fin[loss] = rel[loss]
     pay[still] = fin * np.exp(-r * T)
-    return np.mean(pay)
+    price = np.mean(pay)
+    return (price, pay) if return_payoffs else price
 
 
 def cliquet_price(S, T, r, sigma, q=0.0, seed=None, n_paths=100000, n_steps=252, n_periods=12, local_cap=0.05,
                   local_floor=-0.05, global_cap=0.30, global_floor=0.0):
     """exotic_options.py:494-554"""
     paths = asian_paths(S, T, r, sigma, q, n_paths, n_steps, seed)
+    return cliquet_from_paths(paths, S, T, r, n_periods, local_cap, local_floor, global_cap, global_floor)
+
+
+def cliquet_from_paths(paths, S, T, r, n_periods=12, local_cap=0.05, local_floor=-0.05, global_cap=0.30, global_floor=0.0,
+                       return_payoffs=False):
+    """exotic_options.py:526-554 -- periods of n_steps // n_periods steps from t = 0; trailing steps never enter one."""
+    n_paths, n_steps = paths.shape[0], paths.shape[1] - 1
     spp = n_steps // n_periods
     total = np.zeros(n_paths)
     for p_ in range(n_periods):
         a, b = paths[:, p_ * spp], paths[:, (p_ + 1) * spp]
         total += np.clip((b - a) / a, local_floor, local_cap)
     total = np.clip(total, global_floor, global_cap)
-    return np.exp(-r * T) * np.mean(np.maximum(total, 0) * S)
+    x = np.maximum(total, 0) * S
+    price = np.exp(-r * T) * np.mean(x)
+    return (price, x) if return_payoffs else price
 
 
 def asian_geometric_closed_form(S, K, T, r, sigma, q=0.0, option_type="call"):

@@ -385,3 +385,25 @@ def test_contract_set_layout_of_the_greeks_sets_and_of_random_sets():
         opts = [(100.0 + float(rng.normal(0, 3)), float(rng.uniform(80, 120)), 1.0, 0.05 + float(rng.normal(0, 0.01)), vols[int(rng.integers(0, len(vols)))], 0.0,
                  bool(rng.integers(0, 2))) for _ in range(k)]
         _layout_invariants(opts, int(rng.integers(1, 300)))
+
+
+def test_reference_barrier_level_reproduces_the_reference_t0_decision():
+    """BarrierOption passes the C ABI a level whose log-space t = 0 decision (0 against ln(level/S): a level at the spot is crossed)
+    is the reference's on its column 0, np.exp(np.log(S)); the level stays within a few ulps of the contract's."""
+    import numpy as np
+    from optionslab_amd.exotic import reference_barrier_level
+
+    spots = [100.0, 80.0, 95.0, 110.0, 120.0, 3.0, 50.0] + list(np.random.default_rng(5).uniform(1.0, 500.0, 300))
+    moved = 0
+    for S in spots:
+        s0 = np.exp(np.full(3, np.log(S)))[0]
+        for B in (S, np.nextafter(S, 0.0), np.nextafter(S, np.inf), 0.9 * S, 1.1 * S):
+            for kind in ("up-and-out", "up-and-in", "down-and-out", "down-and-in"):
+                up = kind.startswith("up")
+                level = reference_barrier_level(S, B, kind)
+                assert ((level / S <= 1.0) if up else (level / S >= 1.0)) == ((s0 >= B) if up else (s0 <= B)), (S, B, kind)
+                assert abs(level - B) <= 8 * np.spacing(B) and (level == B or abs(B - S) <= 4 * np.spacing(S))
+                moved += level != B
+    assert moved > 0                                                    # 100 and 80 need a nudge (100: down; 80: up)
+    assert reference_barrier_level(95.0, 95.0, "down-and-out") == 95.0
+    assert reference_barrier_level(100.0, 100.0, "down-and-out") < 100.0 and reference_barrier_level(80.0, 80.0, "up-and-out") > 80.0
