@@ -57,7 +57,8 @@ extern "C" {
                               * 5: additions only -- olmc_multi_gpu_european_qmc, olmc_multi_gpu_spans, tune knobs 10, 11 (OLMC_TUNE_MULTI_LAUNCH, OLMC_TUNE_STAGED_COPY); the multi-GPU
                               *    entry points launch their ranks from one launcher thread per device; the grid reduction's consumer side is an
                               *    agent-scope acquire again (numbers unchanged) 
-                              * 6: additions only -- olmc_multi_gpu_european_qmc_greeks_fd, olmc_multi_gpu_european_qmc_cv; OLMC_TUNE_QMC_BLOCK takes 2 */
+                              * 6: additions only -- olmc_multi_gpu_european_qmc_greeks_fd, olmc_multi_gpu_european_qmc_cv; OLMC_TUNE_QMC_BLOCK takes 2;
+                              *    later additions within v6: olmc_asian_qmc, olmc_extrema_qmc (Sobol paths for the path payoffs) */
 
 enum {
     OLMC_OK = 0,
@@ -400,6 +401,33 @@ int olmc_european_qmc_terminal(double S, double T, double r, double sigma, doubl
                                int64_t point_offset, int64_t n_paths, int32_t dims,
                                const uint32_t* sv, const uint32_t* shift, int32_t bits,
                                int antithetic, double* out_host /* [n_paths * (1 + antithetic)] */);
+
+/* ---- quasi-Monte Carlo path payoffs: Asian, barrier, lookback ---------------
+ * The pseudo-random olmc_asian / olmc_barrier / olmc_lookback payoffs on scrambled-Sobol paths.  Point k of
+ * scipy.stats.qmc.Sobol(d=n_steps, scramble=True, seed) (sv / shift / bits as olmc_european_qmc, dims = n_steps) drives one path:
+ *   z_t = Phi^-1(clip(u_t, 1e-10, 1 - 1e-10)), t = 0 .. n-1 (n = n_steps; the inverse normal of olmc_european_qmc);
+ *   OLMC_QMC_SEQUENTIAL  W_j = z_0 + ... + z_{j-1}: dimension t drives date t + 1 (gbm_qmc.py's convention), n <= 21201;
+ *   OLMC_QMC_BRIDGE      the Brownian bridge in breadth-first order, n <= OLMC_QMC_BRIDGE_MAX_STEPS (the kernel keeps a point's
+ *                        W_0 .. W_n in LDS):
+ *                          W_0 = 0, W_n = sqrt(n) z_0, k = 1; queue = [(0, n)];
+ *                          while queue: (a, b) = pop_front; if b - a < 2: continue; m = (a + b) / 2 (integer);
+ *                            W_m = ((b - m) W_a + (m - a) W_b) / (b - a) + sqrt((m - a)(b - m) / (b - a)) z_k; k += 1;
+ *                            push_back (a, m), (m, b)
+ *   ln S_j = ln S + j drift + vol W_j, j = 1 .. n, drift = (r - q - sigma^2 / 2) dt, vol = sigma sqrt(dt), dt = T / n; date 0 is S.
+ * Payoffs as the pseudo-random calls: avg_kind OLMC_AVG_ARITHMETIC (one fp64 exponential per date) or OLMC_AVG_GEOMETRIC (the fast
+ * fp32 form is refused); payoff OLMC_BARRIER_* (`barrier` = the level, decided in log space with t = 0 included, as olmc_barrier) or
+ * OLMC_LOOKBACK_FLOATING / OLMC_LOOKBACK_FIXED (`barrier` ignored).  antithetic != 0 also prices the mirrored point -z: 2 n_points
+ * payoffs.  Points [point_offset, point_offset + n_points) of the sequence: shards of one sequence add up (olmc_combine_stats).
+ * out->std_error is the naive per-path standard error of the payoffs: for Sobol points it is NOT a confidence interval (it
+ * overstates the error).  The payoffs are reduced in index order: equal arguments give equal bits. */
+enum { OLMC_QMC_SEQUENTIAL = 0, OLMC_QMC_BRIDGE = 1 };
+#define OLMC_QMC_BRIDGE_MAX_STEPS 1024
+int olmc_asian_qmc(double S, double K, double T, double r, double sigma, double q, int is_call, int avg_kind, int construction,
+                   int64_t point_offset, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift, int32_t bits,
+                   int antithetic, olmc_stats* out);
+int olmc_extrema_qmc(double S, double K, double T, double r, double sigma, double q, int is_call, int payoff, double barrier,
+                     int construction, int64_t point_offset, int64_t n_points, int32_t n_steps, const uint32_t* sv,
+                     const uint32_t* shift, int32_t bits, int antithetic, olmc_stats* out);
 
 /* ---- multi-GPU, single process ------------------------------------------
  * n_paths split into n_gpus contiguous global path ranges (rank d = device d, [d N / P, (d + 1) N / P)).  Per list of devices the

@@ -77,6 +77,8 @@ PROTOTYPES = {
     "olmc_european_qmc_greeks_fd": (_I, _SIX + [_I, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, _I, C.POINTER(_D), C.POINTER(Stats)]),
     "olmc_european_qmc_terminal": (_I, [_D] * 5 + [_I64, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, _I, C.POINTER(_D)]),
     "olmc_asian": (_I, _SIX + [_I, _I, _I64, _I64, _I32, _U64T, _I, C.POINTER(Stats)]),
+    "olmc_asian_qmc": (_I, _SIX + [_I, _I, _I, _I64, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, _I, C.POINTER(Stats)]),
+    "olmc_extrema_qmc": (_I, _SIX + [_I, _I, _D, _I, _I64, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, _I, C.POINTER(Stats)]),
     "olmc_asian_greeks_fd": (_I, _SIX + [_I, _I, _I64, _I32, _U64T, _I, _I, C.POINTER(_D), C.POINTER(Stats)]),
     "olmc_extrema_greeks_fd": (_I, _SIX + [_I, _I, _D, _I64, _I32, _U64T, _I, _I, C.POINTER(_D), C.POINTER(Stats)]),
     "olmc_barrier": (_I, _SIX + [_I, _D, _I, _I64, _I64, _I32, _U64T, _I, C.POINTER(Stats)]),
@@ -456,6 +458,31 @@ def asian_greeks_fd(S, K, T, r, sigma, q, is_call: bool, n_paths: int, n_steps: 
 
 
 LOOKBACK_FLOATING, LOOKBACK_FIXED = 4, 5
+QMC_SEQUENTIAL, QMC_BRIDGE = 0, 1
+QMC_BRIDGE_MAX_STEPS = 1024          # OLMC_QMC_BRIDGE_MAX_STEPS
+
+
+def asian_qmc(S, K, T, r, sigma, q, is_call: bool, geometric: bool, n_points: int, sv: np.ndarray, shift: np.ndarray, bridge: bool = True,
+              antithetic: bool = False, point_offset: int = 0) -> Stats:
+    """The Asian option on scrambled-Sobol paths (olmc_asian_qmc): n_steps = sv.shape[0] dates, bridge or sequential construction."""
+    sv, psv, shift, psh = _sobol_args(sv, shift, point_offset, n_points)
+    out = Stats()
+    _check(lib().olmc_asian_qmc(S, K, T, r, sigma, q, int(is_call), AVG_GEOMETRIC if geometric else AVG_ARITHMETIC,
+                                QMC_BRIDGE if bridge else QMC_SEQUENTIAL, int(point_offset), int(n_points), int(sv.shape[0]), psv, psh,
+                                int(sv.shape[1]), int(antithetic), C.byref(out)))
+    return out
+
+
+def extrema_qmc(S, K, T, r, sigma, q, is_call: bool, payoff: int, level: float, n_points: int, sv: np.ndarray, shift: np.ndarray,
+                bridge: bool = True, antithetic: bool = False, point_offset: int = 0) -> Stats:
+    """A barrier (payoff = BARRIER_KINDS value, `level` from reference_barrier_level) or lookback (LOOKBACK_FLOATING / LOOKBACK_FIXED)
+    option on scrambled-Sobol paths (olmc_extrema_qmc)."""
+    sv, psv, shift, psh = _sobol_args(sv, shift, point_offset, n_points)
+    out = Stats()
+    _check(lib().olmc_extrema_qmc(S, K, T, r, sigma, q, int(is_call), int(payoff), float(level), QMC_BRIDGE if bridge else QMC_SEQUENTIAL,
+                                  int(point_offset), int(n_points), int(sv.shape[0]), psv, psh, int(sv.shape[1]), int(antithetic),
+                                  C.byref(out)))
+    return out
 
 
 def extrema_greeks_fd(S, K, T, r, sigma, q, is_call: bool, payoff: int, barrier: float, n_paths: int, n_steps: int, seed: int, antithetic: bool,

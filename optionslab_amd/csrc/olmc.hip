@@ -114,6 +114,10 @@ struct DeviceCtx {
     uint32_t* d_sobol = nullptr;     // [dims x 30 direction numbers | dims shifts]
     size_t sobol_words = 0;          // capacity
     std::vector<uint32_t> sobol_host;   // what d_sobol holds (compared word for word with the caller's table)
+    // the Brownian-bridge plan of the last bridge-constructed QMC path call (qmc_bridge_plan): it depends on n_steps alone
+    void* d_bridge = nullptr;        // [n uint32 a | b << 16][3 x n doubles ca, cb, sd]
+    int32_t bridge_n = 0;            // n of the plan d_bridge holds (0: none)
+    std::vector<unsigned char> bridge_host;   // the plan as uploaded (kept alive for the asynchronous copy)
     bool busy = false;                  // leased (guarded by the pool's mutex)
     // profiling
     std::vector<EventPair> ev_free, ev_pending;
@@ -171,6 +175,7 @@ void ctx_release(DeviceCtx* c) {
     if (c->d_multi) (void)hipFree(c->d_multi);
     if (c->h_multi) (void)hipHostFree(c->h_multi);
     if (c->d_sobol) (void)hipFree(c->d_sobol);
+    if (c->d_bridge) (void)hipFree(c->d_bridge);
     for (auto& sl : c->slots) {
         if (sl.block_rows) (void)hipFree(sl.block_rows);
         if (sl.group_rows) (void)hipFree(sl.group_rows);
@@ -1951,6 +1956,141 @@ extern "C" int olmc_european_qmc_terminal(double S, double T, double r, double s
                                           int32_t bits, int antithetic, double* out_host) {
     if (!out_host) return fail(OLMC_ERR_ARG, "null pointer");
     return run_qmc(S, 0.0, T, r, sigma, q, 1, point_offset, n_paths, dims, sv, shift, bits, nullptr, out_host, antithetic);
+}
+
+// ============================================================ QMC path payoffs ====
+namespace {
+// The breadth-first Brownian-bridge plan of n dates (include/olmc.h): node k >= 1 is the midpoint m = (a + b) / 2 of the k-th interval
+// of length >= 2 taken from the queue that starts with (0, n), with W_m = ca W_a + cb W_b + sd z_k.  Built here once per n and kept on
+// the context's device; the kernel reads node k from lane k of a trip (qmc_path_kernel).
+int qmc_bridge_plan(DeviceCtx* c, int32_t n, QmcBridgePlan* plan) {
+    const size_t ab_bytes = (sizeof(uint32_t) * static_cast<size_t>(n) + 7) & ~size_t(7), bytes = ab_bytes + sizeof(double) * 3 * n;
+    if (c->bridge_n != n) {
+        std::vector<unsigned char> host(bytes, 0);
+        uint32_t* ab = reinterpret_cast<uint32_t*>(host.data());
+        double* coef = reinterpret_cast<double*>(host.data() + ab_bytes);
+        std::vector<std::pair<int32_t, int32_t>> queue{{0, n}};
+        int32_t k = 1;
+        for (size_t head = 0; head < queue.size(); ++head) {
+            const int32_t a = queue[head].first, b = queue[head].second;
+            if (b - a < 2) continue;
+            const int32_t m = (a + b) / 2;
+            if (k >= n) return fail(OLMC_ERR_ARG, "bridge plan overflow");
+            ab[k] = static_cast<uint32_t>(a) | (static_cast<uint32_t>(b) << 16);
+            coef[k] = static_cast<double>(b - m) / (b - a);
+            coef[n + k] = static_cast<double>(m - a) / (b - a);
+            coef[2 * n + k] = std::sqrt(static_cast<double>((m - a) * (b - m)) / (b - a));
+            ++k;
+            queue.emplace_back(a, m);
+            queue.emplace_back(m, b);
+        }
+        if (k != n) return fail(OLMC_ERR_ARG, "bridge plan is incomplete");
+        c->bridge_n = 0;
+        if (c->d_bridge) {
+            HIP_TRY(hipStreamSynchronize(c->stream));            // a launch of the previous plan may still read it
+            HIP_TRY(hipFree(c->d_bridge));
+            c->d_bridge = nullptr;
+        }
+        HIP_TRY(hipMalloc(&c->d_bridge, bytes));
+        c->bridge_host.swap(host);
+        HIP_TRY(hipMemcpyAsync(c->d_bridge, c->bridge_host.data(), bytes, hipMemcpyHostToDevice, c->stream));
+        c->bridge_n = n;
+    }
+    plan->ab = static_cast<const uint32_t*>(c->d_bridge);
+    plan->coef = reinterpret_cast<const double*>(static_cast<const unsigned char*>(c->d_bridge) + ab_bytes);
+    return OLMC_OK;
+}
+
+template <int FAMILY>
+void launch_qmc_path(bool bridge, bool anti, int32_t grid, hipStream_t s, const EventPair* timed, const QmcRange& qr, const ExtremaContract& ec,
+                     double inv_steps, const uint32_t* d_sv, const uint32_t* d_shift, const QmcBridgePlan& plan, const ReduceWs& ws) {
+    if (bridge && anti) launch_timed(qmc_path_kernel<FAMILY, true, true>, dim3(grid), dim3(kBlock), s, timed, qr, ec, inv_steps, d_sv, d_shift, plan, ws);
+    else if (bridge) launch_timed(qmc_path_kernel<FAMILY, true, false>, dim3(grid), dim3(kBlock), s, timed, qr, ec, inv_steps, d_sv, d_shift, plan, ws);
+    else if (anti) launch_timed(qmc_path_kernel<FAMILY, false, true>, dim3(grid), dim3(kBlock), s, timed, qr, ec, inv_steps, d_sv, d_shift, plan, ws);
+    else launch_timed(qmc_path_kernel<FAMILY, false, false>, dim3(grid), dim3(kBlock), s, timed, qr, ec, inv_steps, d_sv, d_shift, plan, ws);
+}
+
+// Workgroups of a QMC path launch: four points in flight per workgroup, grid-striding beyond kQmcPathMaxGrid.
+constexpr int64_t kQmcPathMaxGrid = 8192;
+
+// family: kQmcAsianArithmetic / kQmcAsianGeometric (payoff ignored) or kQmcExtrema (payoff = kBarrier* / kLookback*, `barrier` its level).
+int run_qmc_path(int family, int payoff, double S, double K, double T, double r, double sigma, double q, int is_call, double barrier,
+                 int construction, int64_t point_offset, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift,
+                 int32_t bits, int antithetic, olmc_stats* out) {
+    if (!out) return fail(OLMC_ERR_ARG, "null pointer");
+    if (construction != OLMC_QMC_SEQUENTIAL && construction != OLMC_QMC_BRIDGE) return fail(OLMC_ERR_ARG, "bad construction");
+    if (construction == OLMC_QMC_BRIDGE && n_steps > OLMC_QMC_BRIDGE_MAX_STEPS)
+        return fail(OLMC_ERR_ARG, "the Brownian-bridge construction takes at most OLMC_QMC_BRIDGE_MAX_STEPS (1024) dates");
+    static_assert(OLMC_QMC_BRIDGE_MAX_STEPS == kQmcBridgeMaxSteps, "the header's cap is the kernel's LDS size");
+    int rc = qmc_check(sv, shift, bits, n_steps, point_offset, n_points);
+    if (rc) return rc;
+    CtxLease lease;
+    rc = ctx_lease(&lease);
+    if (rc) return rc;
+    DeviceCtx* const c = lease.c;
+    rc = qmc_table(c, sv, shift, n_steps);
+    if (rc) return rc;
+    const uint32_t* d_sv = c->d_sobol;
+    const uint32_t* d_shift = d_sv + static_cast<size_t>(n_steps) * kSobolBits;
+    QmcBridgePlan plan{nullptr, nullptr};
+    const bool bridge = construction == OLMC_QMC_BRIDGE;
+    if (bridge) {
+        rc = qmc_bridge_plan(c, n_steps, &plan);
+        if (rc) return rc;
+    }
+    ExtremaContract ec;
+    const double dt = T / n_steps;                               // exotic_options.py:54-56
+    ec.s0 = S;
+    ec.log_barrier_rel = family == kQmcExtrema && payoff <= kBarrierDownIn ? std::log(barrier / S) : 0.0;
+    ec.drift = (r - q - 0.5 * sigma * sigma) * dt;
+    ec.vol = sigma * std::sqrt(dt);
+    ec.strike = K;
+    ec.sign = is_call ? 1.0 : -1.0;
+    ec.payoff = family == kQmcExtrema ? payoff : 0;
+    ec.pad = 0;
+    QmcRange qr;
+    qr.first = static_cast<uint64_t>(point_offset);
+    qr.count = n_points;
+    qr.dims = n_steps;
+    qr.mirror = antithetic ? 1 : 0;
+    const int32_t grid = static_cast<int32_t>(std::min<int64_t>((n_points + kWavesPerBlock - 1) / kWavesPerBlock, kQmcPathMaxGrid));
+    ReduceWs ws;
+    rc = make_ws(c, c->stream, grid, 2, c->d_result, -1.0, &ws);
+    if (rc) return rc;
+    EventPair ep{};
+    const EventPair* timed = nullptr;
+    rc = prof_pair(c, &ep, &timed);
+    if (rc) return rc;
+    const bool anti = antithetic != 0;
+    const double inv_steps = 1.0 / n_steps;
+    if (family == kQmcAsianArithmetic) launch_qmc_path<kQmcAsianArithmetic>(bridge, anti, grid, c->stream, timed, qr, ec, inv_steps, d_sv, d_shift, plan, ws);
+    else if (family == kQmcAsianGeometric) launch_qmc_path<kQmcAsianGeometric>(bridge, anti, grid, c->stream, timed, qr, ec, inv_steps, d_sv, d_shift, plan, ws);
+    else launch_qmc_path<kQmcExtrema>(bridge, anti, grid, c->stream, timed, qr, ec, inv_steps, d_sv, d_shift, plan, ws);
+    rc = after_launch(c, c->stream);
+    if (rc) return rc;
+    rc = sync_or_recover(c, c->stream);
+    if (rc) return rc;
+    finish_stats(c->h_result[0], c->h_result[1], n_points * (anti ? 2 : 1), r, T, out);
+    if (poisoned(S, K, T, r, sigma, q) || std::isnan(barrier)) nan_stats(out->n, out);
+    return OLMC_OK;
+}
+}  // namespace
+
+extern "C" int olmc_asian_qmc(double S, double K, double T, double r, double sigma, double q, int is_call, int avg_kind, int construction,
+                              int64_t point_offset, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift, int32_t bits,
+                              int antithetic, olmc_stats* out) {
+    if (avg_kind != OLMC_AVG_ARITHMETIC && avg_kind != OLMC_AVG_GEOMETRIC) return fail(OLMC_ERR_ARG, "bad avg_kind (arithmetic or geometric)");
+    return run_qmc_path(avg_kind == OLMC_AVG_GEOMETRIC ? kQmcAsianGeometric : kQmcAsianArithmetic, 0, S, K, T, r, sigma, q, is_call, 0.0,
+                        construction, point_offset, n_points, n_steps, sv, shift, bits, antithetic, out);
+}
+
+extern "C" int olmc_extrema_qmc(double S, double K, double T, double r, double sigma, double q, int is_call, int payoff, double barrier,
+                                int construction, int64_t point_offset, int64_t n_points, int32_t n_steps, const uint32_t* sv,
+                                const uint32_t* shift, int32_t bits, int antithetic, olmc_stats* out) {
+    if (payoff < OLMC_BARRIER_UP_OUT || payoff > OLMC_LOOKBACK_FIXED) return fail(OLMC_ERR_ARG, "bad payoff");
+    if (payoff <= OLMC_BARRIER_DOWN_IN && !(barrier > 0.0)) return fail(OLMC_ERR_ARG, "Barrier must be positive");
+    return run_qmc_path(kQmcExtrema, payoff, S, K, T, r, sigma, q, is_call, payoff <= OLMC_BARRIER_DOWN_IN ? barrier : 0.0, construction,
+                        point_offset, n_points, n_steps, sv, shift, bits, antithetic, out);
 }
 
 namespace {

@@ -2987,6 +2987,173 @@ __global__ void publish_kernel(const double* __restrict__ src, int32_t n, double
     if (threadIdx.x == 0) __hip_atomic_store(done_flag, done_value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// ----------------------------------------------- QMC path payoffs (Asian, barrier, lookback) ----
+// Scrambled-Sobol paths for the path-dependent payoffs.  Point k of scipy.stats.qmc.Sobol(d = n, scramble=True, seed) drives ONE
+// path of n dates: z_t = Phi^-1(clip(u_t, 1e-10, 1 - 1e-10)) (the Sobol uniform and inverse normal of european_qmc_kernel), then
+//   SEQUENTIAL  dimension t drives date t + 1:  W_j = z_0 + ... + z_{j-1}               (gbm_qmc.py's convention)
+//   BRIDGE      the Brownian bridge in breadth-first order (include/olmc.h): W_n = sqrt(n) z_0, then midpoint m of (a, b) takes
+//               W_m = ca W_a + cb W_b + sd z_k,  ca = (b - m) / (b - a), cb = (m - a) / (b - a), sd = sqrt((m - a)(b - m) / (b - a))
+// and ln(S_j / S) = j drift + vol W_j for j = 1..n (date 0 is S).  The antithetic mirror is the point -z: W -> -W, the same walk.
+//
+// LANES OVER DATES.  A wave owns one point at a time and walks its dimensions 64 at a time, lane l taking dimension c0 + l: the
+// Gray-code fold of the point's index is wave-uniform (a branch on uniform bits, one direction number per set bit), the inverse
+// normal runs on 64 dimensions at once, and the point's payoff is lane 0's after a butterfly over the wave.  One point per THREAD
+// would leave 2^14 points as 64 workgroups.
+//   sequential  an inclusive scan of z across the wave (six DPP-free shuffles) plus the carry of the trips before: W_j in the lane
+//               of date j, nothing stored, any n up to 21201.
+//   bridge      the point's W lives in LDS (n + 1 doubles per wave, n <= kQmcBridgeMaxSteps).  The midpoints of one breadth-first
+//               level are independent and level L holds nodes k = 2^L .. 2^(L+1) - 1, so trip 0 (nodes 0 .. 63) runs levels 0..5
+//               one after the other and every later trip is a single level: lane l of trip c fills node 64 c + l from two nodes
+//               of earlier levels.  The host's plan (qmc_bridge_plan) gives each node its a, b and three coefficients.  Then a
+//               second walk reads W_j with lanes over dates.
+// Payoffs: Asian arithmetic = S mean_j exp(ln(S_j / S)) by one fp64 exponential per date (exp2_f64, the exponent carried in log2
+// units as asian_exp64_kernel does); geometric = S exp(mean_j ln(S_j / S)); barrier / lookback = extrema_payoff on the running max
+// / min of ln(S_j / S), t = 0 included.  The per-point payoffs meet in block_then_grid_reduce: index order, equal inputs, equal bits.
+constexpr int kQmcBridgeMaxSteps = 1024;
+enum QmcPathFamily { kQmcAsianArithmetic = 0, kQmcAsianGeometric = 1, kQmcExtrema = 2 };
+
+struct QmcBridgePlan {
+    const uint32_t* ab;      // [n]: node k's a | b << 16 (node 0: unused -- W_n = sqrt(n) z_0)
+    const double* coef;      // [3][n]: ca, cb, sd of node k
+};
+
+// LDS writes of one lane reach the wave's other lanes: everything issued has landed, and the compiler keeps its order.
+__device__ __forceinline__ void wave_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+
+// Dimension t of point `gray` (wave-uniform Gray code) as a standard normal.
+__device__ __forceinline__ double qmc_normal(const uint32_t* __restrict__ sv, const uint32_t* __restrict__ shift, int32_t t, uint32_t gray) {
+    const uint32_t* __restrict__ row = sv + static_cast<size_t>(t) * kSobolBits;
+    uint32_t x = shift[t];
+    for (uint32_t g = gray; g != 0u; g &= g - 1u) x ^= row[__builtin_ctz(g)];          // uniform trip count: no divergence
+    return ndtri_w_add(0.0, sobol_uniform(x), opaque_zero());
+}
+
+__device__ __forceinline__ double wave_allsum(double v) {
+#pragma unroll
+    for (int off = 1; off < kWave; off <<= 1) v += __shfl_xor(v, off, kWave);
+    return v;
+}
+__device__ __forceinline__ double wave_allmax(double v) {
+#pragma unroll
+    for (int off = 1; off < kWave; off <<= 1) v = max_f64(v, __shfl_xor(v, off, kWave));
+    return v;
+}
+__device__ __forceinline__ double wave_allmin(double v) {
+#pragma unroll
+    for (int off = 1; off < kWave; off <<= 1) v = min_f64(v, __shfl_xor(v, off, kWave));
+    return v;
+}
+
+// Per-leg state of one path while its dates stream past: the sum of exp / of ln(S_j / S) (Asian), or the running extrema.
+struct QmcLeg {
+    double a = 0.0, mx = 0.0, mn = 0.0;      // t = 0: ln(S_0 / S_0) = 0 is an extremum candidate
+};
+
+template <int FAMILY>
+__device__ __forceinline__ void qmc_leg_add(QmcLeg& g, double y /* ln(S_j/S), log2 units for the arithmetic Asian */) {
+    if constexpr (FAMILY == kQmcAsianArithmetic) g.a += exp2_f64(y);
+    else if constexpr (FAMILY == kQmcAsianGeometric) g.a += y;
+    else { g.mx = max_f64(g.mx, y); g.mn = min_f64(g.mn, y); }
+}
+
+// The payoff of one leg, in every lane (butterflies); y_n = ln(S_n / S) in natural units.
+template <int FAMILY>
+__device__ __forceinline__ double qmc_leg_payoff(const ExtremaContract& c, double inv_steps, const QmcLeg& g, double y_n) {
+    if constexpr (FAMILY == kQmcExtrema) return extrema_payoff(c, y_n, wave_allmax(g.mx), wave_allmin(g.mn));
+    const double s = wave_allsum(g.a);
+    const double avg = FAMILY == kQmcAsianArithmetic ? c.s0 * (s * inv_steps) : c.s0 * exp(s * inv_steps);
+    return fmax(c.sign * (avg - c.strike), 0.0);
+}
+
+template <int FAMILY, bool BRIDGE, bool ANTI>
+__global__ __launch_bounds__(kBlock) void qmc_path_kernel(QmcRange qr, ExtremaContract c, double inv_steps, const uint32_t* __restrict__ sv,
+                                                          const uint32_t* __restrict__ shift, QmcBridgePlan plan, ReduceWs ws) {
+    constexpr double kLog2e = 1.4426950408889634;
+    constexpr double kUnit = FAMILY == kQmcAsianArithmetic ? kLog2e : 1.0;
+    const int lane = static_cast<int>(threadIdx.x) & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) / kWave);
+    const int32_t n = qr.dims;
+    const double drift = c.drift * kUnit, vol = c.vol * kUnit;
+    double acc[2] = {0.0, 0.0};
+    [[maybe_unused]] double* W = nullptr;
+    if constexpr (BRIDGE) {
+        __shared__ double w_lds[kWavesPerBlock][kQmcBridgeMaxSteps + 1];
+        W = w_lds[wave];
+    }
+    const int64_t stride = static_cast<int64_t>(gridDim.x) * kWavesPerBlock;
+    for (int64_t i = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave; i < qr.count; i += stride) {
+        const uint64_t k = qr.first + static_cast<uint64_t>(i);
+        const uint32_t gray = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(k ^ (k >> 1))));
+        QmcLeg up, dn;
+        double w_n;
+        if constexpr (BRIDGE) {
+            // fill W: trip 0 = levels 0 .. 5 in turn, every later trip one level (node k reads only nodes of earlier levels)
+            wave_lds_sync();                                         // the previous point's reads are done
+            for (int32_t c0 = 0; c0 < n; c0 += kWave) {
+                const int32_t node = c0 + lane;
+                const bool live = node < n;
+                const double z = qmc_normal(sv, shift, live ? node : n - 1, gray);
+                uint32_t ab = 0u;
+                double ca = 0.0, cb = 0.0, sd = 0.0;
+                if (live && node > 0) {
+                    ab = plan.ab[node];
+                    ca = plan.coef[node]; cb = plan.coef[n + node]; sd = plan.coef[2 * n + node];
+                }
+                const int32_t a = static_cast<int32_t>(ab & 0xffffu), b = static_cast<int32_t>(ab >> 16), m = (a + b) >> 1;
+                if (c0 == 0) {
+                    if (lane == 0) { W[0] = 0.0; W[n] = sqrt(static_cast<double>(n)) * z; }
+                    wave_lds_sync();
+#pragma unroll 1
+                    for (int lvl = 0; lvl < 6 && (1 << lvl) < n; ++lvl) {
+                        if (live && node >= (1 << lvl) && node < (2 << lvl)) W[m] = __builtin_fma(ca, W[a], __builtin_fma(cb, W[b], sd * z));
+                        wave_lds_sync();
+                    }
+                } else {
+                    if (live) W[m] = __builtin_fma(ca, W[a], __builtin_fma(cb, W[b], sd * z));
+                    wave_lds_sync();
+                }
+            }
+            // walk the dates: lane l of trip c0 takes date j = c0 + l + 1
+            for (int32_t c0 = 0; c0 < n; c0 += kWave) {
+                const int32_t j = c0 + lane + 1;
+                if (j <= n) {
+                    const double wj = W[j], jd = static_cast<double>(j) * drift;
+                    qmc_leg_add<FAMILY>(up, __builtin_fma(vol, wj, jd));
+                    if constexpr (ANTI) qmc_leg_add<FAMILY>(dn, __builtin_fma(-vol, wj, jd));
+                }
+            }
+            w_n = W[n];
+        } else {
+            double carry = 0.0;
+            for (int32_t c0 = 0; c0 < n; c0 += kWave) {
+                const int32_t t = c0 + lane;
+                double s = t < n ? qmc_normal(sv, shift, t, gray) : 0.0;
+#pragma unroll
+                for (int off = 1; off < kWave; off <<= 1) {          // inclusive scan over the lanes
+                    const double o = __shfl_up(s, off, kWave);
+                    if (lane >= off) s += o;
+                }
+                const double wj = carry + s;
+                carry += __shfl(s, kWave - 1, kWave);
+                if (t < n) {
+                    const double jd = static_cast<double>(t + 1) * drift;
+                    qmc_leg_add<FAMILY>(up, __builtin_fma(vol, wj, jd));
+                    if constexpr (ANTI) qmc_leg_add<FAMILY>(dn, __builtin_fma(-vol, wj, jd));
+                }
+            }
+            w_n = carry;
+        }
+        const double nd = static_cast<double>(n) * c.drift;
+        const double xu = qmc_leg_payoff<FAMILY>(c, inv_steps, up, __builtin_fma(c.vol, w_n, nd));
+        if (lane == 0) { acc[0] += xu; acc[1] += xu * xu; }
+        if constexpr (ANTI) {
+            const double xd = qmc_leg_payoff<FAMILY>(c, inv_steps, dn, __builtin_fma(-c.vol, w_n, nd));
+            if (lane == 0) { acc[0] += xd; acc[1] += xd * xd; }
+        }
+    }
+    block_then_grid_reduce<2>(acc, ws);
+}
+
 // ------------------------------------------------------- validation taps ----
 __global__ void philox_words_kernel(uint64_t first, int64_t n_paths, int32_t block0, int32_t n_blocks,
                                     uint32_t tag, uint32_t k0, uint32_t k1, uint32_t* __restrict__ out) {

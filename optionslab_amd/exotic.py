@@ -5,6 +5,9 @@ Same dataclass fields and ``price(n_paths, n_steps, avg_type, option_type)``
 signature; the running average lives in registers, no (n_paths, n_steps) matrix
 exists.  Like the reference there is no antithetic mirror unless asked for, and
 the return value is a ``numpy.float64``.
+
+Additive: ``method="qmc"`` prices the Asian, barrier and lookback payoffs on scrambled-Sobol paths (_qmc_tables, include/olmc.h
+"quasi-Monte Carlo path payoffs"), by default with the Brownian-bridge construction.
 """
 from __future__ import annotations
 
@@ -16,6 +19,28 @@ import numpy as np
 
 from . import _hip
 from .black_scholes import _ncdf
+
+
+def _qmc_tables(method: str, path_construction: str, n_paths: int, n_steps: int, seed: Optional[int]):
+    """(sv, shift, bridge) for method="qmc", None for "pseudo"; every refusal is a ValueError raised before the device is touched."""
+    if method not in ("pseudo", "qmc"):
+        raise ValueError("method must be 'pseudo' or 'qmc'")
+    if path_construction not in ("bridge", "sequential"):
+        raise ValueError("path_construction must be 'bridge' or 'sequential'")
+    if method == "pseudo":
+        return None
+    from .monte_carlo import SOBOL_MAX_DIM, sobol_tables
+
+    if n_steps > SOBOL_MAX_DIM:
+        raise ValueError(f"method='qmc' takes at most {SOBOL_MAX_DIM} steps (Sobol dimensions)")
+    bridge = path_construction == "bridge"
+    if bridge and n_steps > _hip.QMC_BRIDGE_MAX_STEPS:
+        raise ValueError(f"path_construction='bridge' takes at most {_hip.QMC_BRIDGE_MAX_STEPS} steps; use 'sequential'")
+    if n_paths > 1 << 30:
+        raise ValueError("method='qmc' takes at most 2**30 paths (Sobol points)")
+    seed = seed if seed is not None else int(np.random.default_rng().integers(0, 2**31))
+    sv, shift = sobol_tables(n_steps, seed, n_paths)
+    return sv, shift, bridge
 
 
 @dataclass
@@ -31,14 +56,33 @@ class AsianOption:
     def price(self, n_paths: int = 100000, n_steps: int = 252,
               avg_type: Literal["arithmetic", "geometric"] = "arithmetic",
               option_type: Literal["call", "put"] = "call", antithetic: bool = False,
-              return_error: bool = False, precision: Literal["fp64", "fp32"] = "fp64"):
+              return_error: bool = False, precision: Literal["fp64", "fp32"] = "fp64",
+              method: Literal["pseudo", "qmc"] = "pseudo", path_construction: Literal["bridge", "sequential"] = "bridge"):
         """precision (additive, arithmetic average only): "fp64" = the reference's arithmetic (fp64 cumulative
         log-return, one fp64 exponential per monitoring date, :62-67); "fp32" = the opt-in fast kernel (one
-        hardware fp32 exponential per date: ~2e-6 on the price, 1.6x faster)."""
+        hardware fp32 exponential per date: ~2e-6 on the price, 1.6x faster).
+
+        method (additive): "pseudo" (default) = the Philox paths of the pseudo-random kernels; "qmc" = scrambled-Sobol paths: the
+        option's seed is the scramble seed of scipy.stats.qmc.Sobol(d=n_steps, scramble=True, seed=seed) (None draws one), point k drives
+        path k through z = norm.ppf(clip(u, 1e-10, 1 - 1e-10)).  fp64 only; n_steps <= 21201.
+        path_construction (read only with method="qmc"): "bridge" (default) = the Brownian bridge in breadth-first order (dimension 0 sets
+        the terminal value, the next ones the midpoints: include/olmc.h), at most 1024 dates; "sequential" = dimension t drives date t + 1.
+        With method="qmc", antithetic=True also prices the mirrored point -z, and return_error's standard error is the naive per-path
+        one: for Sobol points it is not a confidence interval (it overstates the error).
+        Refused (ValueError, before the device is touched): an unknown method or path_construction, method="qmc" with
+        precision="fp32", n_steps > 21201 with method="qmc", n_steps > 1024 with the bridge."""
         if n_paths < 1 or n_steps < 1:
             raise ValueError("n_paths and n_steps must be >= 1")
         if precision not in ("fp64", "fp32"):
             raise ValueError("precision must be 'fp64' or 'fp32'")
+        if method == "qmc" and precision != "fp64":
+            raise ValueError("method='qmc' prices in fp64 only")
+        qmc = _qmc_tables(method, path_construction, n_paths, n_steps, self.seed)
+        if qmc is not None:
+            sv, shift, bridge = qmc
+            st = _hip.asian_qmc(self.S, self.K, self.T, self.r, self.sigma, self.q, option_type == "call", avg_type != "arithmetic",
+                                n_paths, sv, shift, bridge, antithetic)
+            return (np.float64(st.price), float(st.std_error)) if return_error else np.float64(st.price)
         # seed=None: the reference leaves the global RandomState unseeded (:51-52) => fresh draw
         seed = self.seed if self.seed is not None else int(np.random.default_rng().integers(0, 2**31))
         st = _hip.asian(self.S, self.K, self.T, self.r, self.sigma, self.q, option_type == "call",
@@ -98,15 +142,23 @@ class BarrierOption:
 
     def price(self, n_paths: int = 100000, n_steps: int = 252,
               barrier_type: Literal["up-and-out", "up-and-in", "down-and-out", "down-and-in"] = "up-and-out",
-              option_type: Literal["call", "put"] = "call", antithetic: bool = False, return_error: bool = False):
+              option_type: Literal["call", "put"] = "call", antithetic: bool = False, return_error: bool = False,
+              method: Literal["pseudo", "qmc"] = "pseudo", path_construction: Literal["bridge", "sequential"] = "bridge"):
+        """method, path_construction (additive): scrambled-Sobol paths, as AsianOption.price."""
         if self.barrier <= 0:                       # :195-196
             raise ValueError("Barrier must be positive")
         if n_paths < 1 or n_steps < 1:
             raise ValueError("n_paths and n_steps must be >= 1")
         # the reference dispatches on startswith("up") / endswith("out") (:201-212)
         kind = (0 if barrier_type.startswith("up") else 2) + (0 if barrier_type.endswith("out") else 1)
-        seed = self.seed if self.seed is not None else int(np.random.default_rng().integers(0, 2**31))
+        qmc = _qmc_tables(method, path_construction, n_paths, n_steps, self.seed)
         level = reference_barrier_level(self.S, self.barrier, barrier_type)
+        if qmc is not None:
+            sv, shift, bridge = qmc
+            st = _hip.extrema_qmc(self.S, self.K, self.T, self.r, self.sigma, self.q, option_type == "call", kind, level, n_paths, sv, shift,
+                                  bridge, antithetic)
+            return (np.float64(st.price), float(st.std_error)) if return_error else np.float64(st.price)
+        seed = self.seed if self.seed is not None else int(np.random.default_rng().integers(0, 2**31))
         st = _hip.barrier(self.S, self.K, self.T, self.r, self.sigma, self.q, option_type == "call", level, kind,
                           n_paths, n_steps, seed, antithetic)
         return (np.float64(st.price), float(st.std_error)) if return_error else np.float64(st.price)
@@ -125,9 +177,18 @@ class LookbackOption:
     seed: Optional[int] = None
 
     def price(self, n_paths: int = 100000, n_steps: int = 252, lookback_type: Literal["floating", "fixed"] = "floating",
-              option_type: Literal["call", "put"] = "call", antithetic: bool = False, return_error: bool = False):
+              option_type: Literal["call", "put"] = "call", antithetic: bool = False, return_error: bool = False,
+              method: Literal["pseudo", "qmc"] = "pseudo", path_construction: Literal["bridge", "sequential"] = "bridge"):
+        """method, path_construction (additive): scrambled-Sobol paths, as AsianOption.price."""
         if n_paths < 1 or n_steps < 1:
             raise ValueError("n_paths and n_steps must be >= 1")
+        qmc = _qmc_tables(method, path_construction, n_paths, n_steps, self.seed)
+        if qmc is not None:
+            sv, shift, bridge = qmc
+            st = _hip.extrema_qmc(self.S, self.K, self.T, self.r, self.sigma, self.q, option_type == "call",
+                                  _hip.LOOKBACK_FIXED if lookback_type != "floating" else _hip.LOOKBACK_FLOATING, 0.0, n_paths, sv, shift,
+                                  bridge, antithetic)
+            return (np.float64(st.price), float(st.std_error)) if return_error else np.float64(st.price)
         seed = self.seed if self.seed is not None else int(np.random.default_rng().integers(0, 2**31))
         st = _hip.lookback(self.S, self.K, self.T, self.r, self.sigma, self.q, option_type == "call",
                            lookback_type != "floating", n_paths, n_steps, seed, antithetic)

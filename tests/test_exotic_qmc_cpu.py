@@ -1,0 +1,104 @@
+"""method="qmc" on the exotic options without a device: every refusal comes before the device is touched, a missing GPU is loud,
+and the pinned Brownian-bridge construction (include/olmc.h) is Brownian motion."""
+import collections
+import math
+import os
+
+import numpy as np
+import pytest
+
+import optionslab_amd as ol
+from optionslab_amd import _hip
+from optionslab_amd.exceptions import AccelerationError
+
+S, K, T, R, SIG = 100.0, 100.0, 1.0, 0.05, 0.2
+
+
+def _options():
+    return [
+        (ol.AsianOption(S, K, T, R, SIG, seed=3), {}),
+        (ol.BarrierOption(S, K, T, R, SIG, seed=3, barrier=120.0), {}),
+        (ol.LookbackOption(S, K, T, R, SIG, seed=3), {}),
+    ]
+
+
+@pytest.fixture
+def no_device(monkeypatch):
+    """Any attempt to reach the library (hence the device) fails the test."""
+    def touched(*a, **k):
+        raise AssertionError("the device was touched")
+
+    for name in ("lib", "asian_qmc", "extrema_qmc", "asian", "barrier", "lookback"):
+        monkeypatch.setattr(_hip, name, touched)
+
+
+@pytest.mark.parametrize("kwargs,match", [
+    (dict(method="sobol"), "method"),
+    (dict(method="QMC"), "method"),
+    (dict(method="qmc", path_construction="pca"), "path_construction"),
+    (dict(method="pseudo", path_construction="brownian"), "path_construction"),
+    (dict(method="qmc", n_steps=21202, path_construction="sequential"), "21201"),
+    (dict(method="qmc", n_steps=1025), "1024"),
+    (dict(method="qmc", n_steps=2000, path_construction="bridge"), "1024"),
+])
+def test_refusals_come_before_the_device(no_device, kwargs, match):
+    for opt, _ in _options():
+        kw = dict(n_paths=100, n_steps=8)
+        kw.update(kwargs)
+        with pytest.raises(ValueError, match=match):
+            opt.price(**kw)
+
+
+def test_qmc_refuses_fp32(no_device):
+    with pytest.raises(ValueError, match="fp64"):
+        ol.AsianOption(S, K, T, R, SIG, seed=3).price(100, 8, method="qmc", precision="fp32")
+
+
+def test_the_sequential_construction_takes_more_than_1024_dates_up_to_the_sobol_cap(no_device):
+    # the cap of the bridge is not the sequential construction's: the call goes on to the device (here: the stub)
+    with pytest.raises(AssertionError, match="touched"):
+        ol.LookbackOption(S, K, T, R, SIG, seed=3).price(4, 21201, method="qmc", path_construction="sequential")
+
+
+@pytest.mark.skipif(os.path.exists("/dev/kfd"), reason="GPU present: loud-failure path not reachable")
+def test_qmc_without_a_gpu_is_an_acceleration_error():
+    for opt, _ in _options():
+        for construction in ("bridge", "sequential"):
+            with pytest.raises(AccelerationError):
+                opt.price(n_paths=64, n_steps=16, method="qmc", path_construction=construction)
+
+
+def test_the_abi_declares_the_qmc_path_entry_points():
+    for name in ("olmc_asian_qmc", "olmc_extrema_qmc"):
+        assert name in _hip.PROTOTYPES
+    with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "olmc.h")) as f:
+        header = f.read()
+    assert "#define OLMC_QMC_BRIDGE_MAX_STEPS 1024" in header and _hip.QMC_BRIDGE_MAX_STEPS == 1024
+
+
+def bridge_weights(n):
+    """The pinned bridge (include/olmc.h) as a linear map: W = z @ B, B (n, n + 1)."""
+    B = np.zeros((n, n + 1))
+    B[0, n] = math.sqrt(n)
+    k = 1
+    queue = collections.deque([(0, n)])
+    while queue:
+        a, b = queue.popleft()
+        if b - a < 2:
+            continue
+        m = (a + b) // 2
+        B[:, m] = ((b - m) * B[:, a] + (m - a) * B[:, b]) / (b - a)
+        B[k, m] += math.sqrt((m - a) * (b - m) / (b - a))
+        k += 1
+        queue.append((a, m))
+        queue.append((m, b))
+    assert k == n                                   # every dimension is used exactly once
+    return B
+
+
+@pytest.mark.parametrize("n", [1, 2, 3, 7, 252])
+def test_the_pinned_bridge_is_brownian_motion(n):
+    B = bridge_weights(n)
+    cov = B.T @ B                                   # Cov(W_i, W_j) for independent standard normal z
+    i = np.arange(n + 1)
+    assert np.max(np.abs(cov - np.minimum.outer(i, i))) <= 1e-12
