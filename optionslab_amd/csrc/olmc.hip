@@ -624,18 +624,24 @@ PathRange make_range(int64_t path_offset, int64_t n_local, int32_t n_steps, uint
 // `timed` != nullptr: the dispatch itself carries the event pair (hipExtLaunchKernelGGL): the events take the
 // kernel's own begin / end timestamps, as rocprofv3 reads them.  hipEventRecord brackets around a launch also
 // time the marker packets on either side (+7..10 us at these durations: 119 vs 109 us in one and the same run).
-template <typename Kernel, int NSETS>
-void launch_one(Kernel kernel, int32_t grid, hipStream_t s, const EventPair* timed, const PathRange& pr, const ContractSet<NSETS>& cs,
-                const ReduceWs& ws, double* terminal) {
-    if (timed) hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, s, timed->start, timed->stop, 0, pr, cs, ws, terminal);
-    else hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, s, pr, cs, ws, terminal);
-}
-
-// The same for any kernel and any launch shape.
 template <typename Kernel, typename... Args>
-void launch_timed(Kernel kernel, dim3 grid, dim3 block, hipStream_t s, const EventPair* timed, Args... args) {
+void launch_timed(Kernel kernel, dim3 grid, dim3 block, hipStream_t s, const EventPair* timed, const Args&... args) {
     if (timed) hipExtLaunchKernelGGL(kernel, grid, block, 0, s, timed->start, timed->stop, 0, args...);
     else hipLaunchKernelGGL(kernel, grid, block, 0, s, args...);
+}
+
+// Compile-time dispatch on a runtime flag: f(std::true_type{}) or f(std::false_type{}), so that one generic lambda names the
+// kernel instantiation of either value (kernel<B> with `auto B`).
+template <typename F>
+void with_bool(bool b, F&& f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+
+// The same over a fused set's width and the antithetic flag: f(integral_constant<int, 8 or 16>, integral_constant<bool, anti>).
+template <typename F>
+void with_set_anti(int nsets, bool anti, F&& f) {
+    with_bool(nsets == 8, [&](auto eight) { with_bool(anti, [&](auto a) { f(std::integral_constant<int, eight ? 8 : 16>{}, a); }); });
 }
 
 // Profiling on: take an event pair for the launch that follows and queue it for prof_drain.
@@ -653,17 +659,66 @@ template <int NSETS, int MODE>
 void launch_european(bool anti, int32_t grid, hipStream_t s, const PathRange& pr, const ContractSet<NSETS>& cs,
                      const ReduceWs& ws, double* terminal, const EventPair* timed = nullptr) {
     const bool strided = static_cast<int64_t>(grid) * kBlock < pr.count;      // the grid does not cover every path
-    if (strided) {
-        if (anti) launch_one(european_path_kernel<NSETS, true, MODE, true>, grid, s, timed, pr, cs, ws, terminal);
-        else launch_one(european_path_kernel<NSETS, false, MODE, true>, grid, s, timed, pr, cs, ws, terminal);
-    } else {
-        if (anti) launch_one(european_path_kernel<NSETS, true, MODE, false>, grid, s, timed, pr, cs, ws, terminal);
-        else launch_one(european_path_kernel<NSETS, false, MODE, false>, grid, s, timed, pr, cs, ws, terminal);
+    with_bool(strided, [&](auto strided_c) {
+        with_bool(anti, [&](auto a) {
+            launch_timed(european_path_kernel<NSETS, a, MODE, strided_c>, dim3(grid), dim3(kBlock), s, timed, pr, cs, ws, terminal);
+        });
+    });
+}
+
+// Waits for the launch just made on stream s (defined with the poll below).
+int sync_or_recover(DeviceCtx* c, hipStream_t s);
+
+// ONE reducing launch on a leased context: the workspace of `grid` workgroups x nv values, whose last workgroup writes the sums to
+// d_out (and `tail` behind them when tail >= 0), an event pair when profiling is on (unless !profiled), launch(grid, s, timed, ws),
+// the launch check.  The launch that writes into the context's pinned buffer (d_out == c->d_result) BLOCKS: on OLMC_OK the sums
+// are in c->h_result.  Any other d_out is a shard's device buffer, and its launch is left queued on `s`.
+template <typename Launch>
+int launch_reduce(DeviceCtx* c, hipStream_t s, double* d_out, double tail, int nv, int32_t grid, Launch&& launch, bool profiled = true) {
+    ReduceWs ws;
+    int rc = make_ws(c, s, grid, nv, d_out, tail, &ws);
+    if (rc) return rc;
+    EventPair ep{};
+    const EventPair* timed = nullptr;
+    if (profiled) {
+        rc = prof_pair(c, &ep, &timed);
+        if (rc) return rc;
+    }
+    launch(grid, s, timed, ws);
+    rc = after_launch(c, s);
+    if (rc || d_out != c->d_result) return rc;
+    return sync_or_recover(c, s);
+}
+
+// The stats of one contract from {sum, sumsq} at h; poisoned inputs (`bad`) answer NaN (nan_stats overwrites every field).
+void finish_one(const double* h, int64_t n, double r_disc, double T, bool bad, olmc_stats* out) {
+    if (bad) nan_stats(n, out);
+    else finish_stats(h[0], h[1], n, r_disc, T, out);
+}
+
+// The stats of k contracts from one launch's sums: contract i's pair sits at slot pos[i] (pos == nullptr: slot i); a lean launch
+// left one sum per slot and no sum of squares.  Poisoned contracts, or all of them when extra_bad, answer NaN.
+void finish_set(const double* h, const int* pos, int64_t n, const olmc_option* opts, int64_t k, bool extra_bad, bool lean, olmc_stats* st) {
+    for (int64_t i = 0; i < k; ++i) {
+        const int64_t slot = pos ? pos[i] : i;
+        const olmc_option& o = opts[i];
+        if (extra_bad || poisoned(o.S, o.K, o.T, o.r, o.sigma, o.q)) nan_stats(n, &st[i]);
+        else if (lean) finish_stats(h[slot], std::nan(""), n, o.r, o.T, &st[i]);      // the price is exact, the standard error was not asked for
+        else finish_stats(h[2 * slot], h[2 * slot + 1], n, o.r, o.T, &st[i]);
     }
 }
 
+// The per-step constants of a GBM path recursion (exotic_options.py:54-56, gbm_numpy.py:106-108, gbm_qmc.py:38-44).
+struct GbmStep {
+    double dt, drift, vol;
+};
+GbmStep gbm_step(double T, int32_t n_steps, double r, double q, double sigma) {
+    const double dt = T / n_steps;
+    return {dt, (r - q - 0.5 * sigma * sigma) * dt, sigma * std::sqrt(dt)};
+}
+
 // ONE launch on stream `s` for k contracts: leaves {sum, sumsq} x k in d_out[0 .. 2k)
-// (padded to the kernel's NSETS) and, when tail >= 0, `tail` in d_out[2 * nsets].
+// (padded to the kernel's NSETS) and, when tail >= 0, `tail` in d_out[2 * nsets].  Blocks when d_out is c->d_result (launch_reduce).
 int run_batch_device(DeviceCtx* c, hipStream_t s, const olmc_option* opts, int32_t k, int64_t path_offset,
                      int64_t n_local, int32_t n_steps, uint64_t seed, int antithetic, double* d_out, double tail,
                      int* pos /* [k]: slot of contract i in d_out, may be NULL when k == 1 */, bool* sums_only = nullptr
@@ -677,35 +732,25 @@ int run_batch_device(DeviceCtx* c, hipStream_t s, const olmc_option* opts, int32
     // where the launch covers every path
     const bool lean = sums_only && *sums_only && nsets > 1 && static_cast<int64_t>(grid) * kBlock >= n_local;
     if (sums_only) *sums_only = lean;
-    ReduceWs ws;
-    int rc = make_ws(c, s, grid, lean ? nsets : 2 * nsets, d_out, tail, &ws);
-    if (rc) return rc;
-    EventPair ep{};
-    const EventPair* timed = nullptr;
-    rc = prof_pair(c, &ep, &timed);
-    if (rc) return rc;
-    if (nsets == 1) {
-        ContractSet<1> cs;
-        cs.c[0] = make_contract(opts[0], n_steps);
-        cs.base_mask = 1u; cs.upper_continues_slot0 = 0;
-        if (pos) pos[0] = 0;
-        launch_european<1, kReduce>(anti, grid, s, pr, cs, ws, nullptr, timed);
-    } else if (nsets == 8) {
-        ContractSet<8> cs;
-        group_contracts<8>(opts, k, n_steps, &cs, pos);
-        if (!lean) launch_european<8, kReduce>(anti, grid, s, pr, cs, ws, nullptr, timed);
-        else if (anti) launch_one(european_path_kernel<8, true, kSumOnly, false>, grid, s, timed, pr, cs, ws, nullptr);
-        else launch_one(european_path_kernel<8, false, kSumOnly, false>, grid, s, timed, pr, cs, ws, nullptr);
-    } else {
-        ContractSet<16> cs;
-        group_contracts<16>(opts, k, n_steps, &cs, pos);
-        if (!lean) launch_european<16, kReduce>(anti, grid, s, pr, cs, ws, nullptr, timed);
-        else if (anti) launch_one(european_path_kernel<16, true, kSumOnly, false>, grid, s, timed, pr, cs, ws, nullptr);
-        else launch_one(european_path_kernel<16, false, kSumOnly, false>, grid, s, timed, pr, cs, ws, nullptr);
-    }
-    rc = after_launch(c, s);
-    if (rc) return rc;
-    return OLMC_OK;
+    return launch_reduce(c, s, d_out, tail, lean ? nsets : 2 * nsets, grid, [&](int32_t g, hipStream_t st, const EventPair* timed, const ReduceWs& ws) {
+        auto fused = [&](auto width) {
+            ContractSet<width> cs;
+            group_contracts<width>(opts, k, n_steps, &cs, pos);
+            if (!lean) launch_european<width, kReduce>(anti, g, st, pr, cs, ws, nullptr, timed);
+            else with_bool(anti, [&](auto a) { launch_timed(european_path_kernel<width, a, kSumOnly, false>, dim3(g), dim3(kBlock), st, timed, pr, cs, ws, nullptr); });
+        };
+        if (nsets == 1) {
+            ContractSet<1> cs;
+            cs.c[0] = make_contract(opts[0], n_steps);
+            cs.base_mask = 1u; cs.upper_continues_slot0 = 0;
+            if (pos) pos[0] = 0;
+            launch_european<1, kReduce>(anti, g, st, pr, cs, ws, nullptr, timed);
+        } else if (nsets == 8) {
+            fused(std::integral_constant<int, 8>{});
+        } else {
+            fused(std::integral_constant<int, 16>{});
+        }
+    });
 }
 
 // Waits for the launch just made on stream s.  If it was armed (make_ws), the host polls the flag word in pinned memory:
@@ -797,18 +842,7 @@ int run_batch(const olmc_option* opts, int32_t k, int64_t path_offset, int64_t n
     bool lean = prices_only;
     rc = run_batch_device(c, c->stream, opts, k, path_offset, n_local, n_steps, seed, antithetic, c->d_result, -1.0, pos, &lean);
     if (rc) return rc;
-    rc = sync_or_recover(c, c->stream);
-    if (rc) return rc;
-    const int64_t n = n_local * (antithetic ? 2 : 1);
-    for (int i = 0; i < k; ++i) {
-        if (poisoned(opts[i].S, opts[i].K, opts[i].T, opts[i].r, opts[i].sigma, opts[i].q)) {
-            nan_stats(n, &out[i]);
-        } else if (lean) {                           // one sum per slot: the price is exact, the standard error was not asked for
-            finish_stats(c->h_result[pos[i]], std::nan(""), n, opts[i].r, opts[i].T, &out[i]);
-        } else {
-            finish_stats(c->h_result[2 * pos[i]], c->h_result[2 * pos[i] + 1], n, opts[i].r, opts[i].T, &out[i]);
-        }
-    }
+    finish_set(c->h_result, pos, n_local * (antithetic ? 2 : 1), opts, k, false, lean, out);
     return OLMC_OK;
 }
 
@@ -1029,8 +1063,7 @@ extern "C" int olmc_european_multi(const olmc_option* opts, const uint32_t* tags
     if (g_profile) { rc = prof_begin(c, c->stream, &ep); if (rc) return rc; }
     for (int64_t base_opt = 0; base_opt < n_options; base_opt += 65535) {
         const unsigned ny = static_cast<unsigned>(std::min<int64_t>(65535, n_options - base_opt));
-        if (antithetic) hipLaunchKernelGGL((european_multi_kernel<true>), dim3(bpo, ny), dim3(kBlock), 0, c->stream, pr, d_opts, base_opt, d_rows, d_cnt, d_out, md);
-        else hipLaunchKernelGGL((european_multi_kernel<false>), dim3(bpo, ny), dim3(kBlock), 0, c->stream, pr, d_opts, base_opt, d_rows, d_cnt, d_out, md);
+        with_bool(antithetic != 0, [&](auto a) { launch_timed(european_multi_kernel<a>, dim3(bpo, ny), dim3(kBlock), c->stream, nullptr, pr, d_opts, base_opt, d_rows, d_cnt, d_out, md); });
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) {
             multi_recover(c);
@@ -1040,11 +1073,7 @@ extern "C" int olmc_european_multi(const olmc_option* opts, const uint32_t* tags
     if (g_profile) { rc = prof_end(c, c->stream, ep); if (rc) { multi_recover(c); return rc; } }
     rc = wait_armed(c, c->stream);
     if (rc) { multi_recover(c); return rc; }
-    const int64_t n = n_paths * (antithetic ? 2 : 1);
-    for (int64_t j = 0; j < n_options; ++j) {
-        if (poisoned(opts[j].S, opts[j].K, opts[j].T, opts[j].r, opts[j].sigma, opts[j].q)) nan_stats(n, &out[j]);
-        else finish_stats(h_out[2 * j], h_out[2 * j + 1], n, opts[j].r, opts[j].T, &out[j]);
-    }
+    finish_set(h_out, nullptr, n_paths * (antithetic ? 2 : 1), opts, n_options, false, false, out);
     return OLMC_OK;
 }
 
@@ -1111,6 +1140,21 @@ extern "C" int olmc_european_terminal(double S, double T, double r, double sigma
 }
 
 // =========================================================== control variate ====
+namespace {
+// ONE launch of the five control-variate moments (of the UNdiscounted payoff) of contract o, then `tail`, at d_out (launch_reduce).
+int cv_device(DeviceCtx* c, hipStream_t s, const olmc_option& o, int64_t path_offset, int64_t n_local, int32_t n_steps, uint64_t seed,
+              int antithetic, double* d_out, double tail, bool profiled) {
+    PathRange pr = make_range(path_offset, n_local, n_steps, seed);
+    const int32_t grid = european_launch_shape(c, &pr, european_occupancy<1, kControlVariate>(antithetic != 0));
+    ContractSet<1> cs;
+    cs.c[0] = make_contract(o, n_steps);
+    cs.base_mask = 1u; cs.upper_continues_slot0 = 0;
+    return launch_reduce(c, s, d_out, tail, 5, grid, [&](int32_t g, hipStream_t st, const EventPair* timed, const ReduceWs& ws) {
+        launch_european<1, kControlVariate>(antithetic != 0, g, st, pr, cs, ws, nullptr, timed);
+    }, profiled);
+}
+}  // namespace
+
 extern "C" int olmc_european_cv_shard(double S, double K, double T, double r, double sigma, double q, int is_call,
                                       int64_t path_offset, int64_t n_local, int32_t n_steps, uint64_t seed, int antithetic,
                                       olmc_cv_moments* out) {
@@ -1121,22 +1165,7 @@ extern "C" int olmc_european_cv_shard(double S, double K, double T, double r, do
     rc = ctx_lease(&lease);
     if (rc) return rc;
     DeviceCtx* const c = lease.c;
-    PathRange pr = make_range(path_offset, n_local, n_steps, seed);
-    const int32_t grid = european_launch_shape(c, &pr, european_occupancy<1, kControlVariate>(antithetic != 0));
-    ContractSet<1> cs;
-    cs.c[0] = make_contract(make_option(S, K, T, r, sigma, q, is_call), n_steps);
-    cs.base_mask = 1u; cs.upper_continues_slot0 = 0;
-    ReduceWs ws;
-    rc = make_ws(c, c->stream, grid, 5, c->d_result, -1.0, &ws);
-    if (rc) return rc;
-    EventPair ep{};
-    const EventPair* timed = nullptr;
-    rc = prof_pair(c, &ep, &timed);
-    if (rc) return rc;
-    launch_european<1, kControlVariate>(antithetic != 0, grid, c->stream, pr, cs, ws, nullptr, timed);
-    rc = after_launch(c, c->stream);
-    if (rc) return rc;
-    rc = sync_or_recover(c, c->stream);
+    rc = cv_device(c, c->stream, make_option(S, K, T, r, sigma, q, is_call), path_offset, n_local, n_steps, seed, antithetic, c->d_result, -1.0, true);
     if (rc) return rc;
     cv_from_device(c->h_result, n_local * (antithetic ? 2 : 1), S, T, r, q, out);       // d = disc * x (monte_carlo.py:175)
     if (poisoned(S, K, T, r, sigma, q)) out->value = std::nan("");
@@ -1156,13 +1185,14 @@ extern "C" int olmc_combine_cv(const olmc_cv_moments* parts, int32_t n_parts, do
     return OLMC_OK;
 }
 
-// ===================================================================== Asian ====
-extern "C" int olmc_asian(double S, double K, double T, double r, double sigma, double q, int is_call, int avg_kind,
-                          int64_t path_offset, int64_t n_local, int32_t n_steps, uint64_t seed, int antithetic,
-                          olmc_stats* out) {
+// ======================================================= single-contract exotics ====
+namespace {
+// One reducing launch of a one-contract path kernel on a leased context, grid_for(n_local) workgroups, then its stats (discounted
+// at r_for_discount; NaN when poisoned_inputs).  launch(grid, stream, timed, pr, ws) queues the kernel.
+template <typename Launch>
+int run_structured(int64_t path_offset, int64_t n_local, int32_t n_steps, uint64_t seed, int antithetic, double r_for_discount,
+                   double T, bool poisoned_inputs, olmc_stats* out, Launch launch, int nv = 2, double* raw_sums = nullptr) {
     if (!out) return fail(OLMC_ERR_ARG, "null pointer");
-    if (avg_kind != OLMC_AVG_ARITHMETIC && avg_kind != OLMC_AVG_GEOMETRIC && avg_kind != OLMC_AVG_ARITHMETIC_FAST)
-        return fail(OLMC_ERR_ARG, "bad avg_kind");
     int rc = check_paths(path_offset, n_local, n_steps);
     if (rc) return rc;
     CtxLease lease;
@@ -1170,37 +1200,39 @@ extern "C" int olmc_asian(double S, double K, double T, double r, double sigma, 
     if (rc) return rc;
     DeviceCtx* const c = lease.c;
     const PathRange pr = make_range(path_offset, n_local, n_steps, seed);
-    const int32_t grid = grid_for(n_local);
+    rc = launch_reduce(c, c->stream, c->d_result, -1.0, nv, grid_for(n_local),
+                       [&](int32_t grid, hipStream_t st, const EventPair* timed, const ReduceWs& ws) { launch(grid, st, timed, pr, ws); });
+    if (rc) return rc;
+    finish_one(c->h_result, n_local * (antithetic ? 2 : 1), r_for_discount, T, poisoned_inputs, out);
+    if (raw_sums) for (int m = 0; m < nv; ++m) raw_sums[m] = c->h_result[m];     // the context is still leased
+    return OLMC_OK;
+}
+}  // namespace
+
+// ===================================================================== Asian ====
+extern "C" int olmc_asian(double S, double K, double T, double r, double sigma, double q, int is_call, int avg_kind,
+                          int64_t path_offset, int64_t n_local, int32_t n_steps, uint64_t seed, int antithetic,
+                          olmc_stats* out) {
+    if (!out) return fail(OLMC_ERR_ARG, "null pointer");
+    if (avg_kind != OLMC_AVG_ARITHMETIC && avg_kind != OLMC_AVG_GEOMETRIC && avg_kind != OLMC_AVG_ARITHMETIC_FAST)
+        return fail(OLMC_ERR_ARG, "bad avg_kind");
     AsianContract ac;
-    const double dt = T / n_steps;                               // exotic_options.py:54-56
+    const GbmStep g = gbm_step(T, n_steps, r, q, sigma);          // exotic_options.py:54-56
     ac.log_s0 = std::log(S);
     ac.s0 = S;
-    ac.drift = (r - q - 0.5 * sigma * sigma) * dt;
-    ac.vol = sigma * std::sqrt(dt);
+    ac.drift = g.drift;
+    ac.vol = g.vol;
     ac.strike = K;
     ac.sign = is_call ? 1.0 : -1.0;
     ac.inv_steps = 1.0 / n_steps;
-    ReduceWs ws;
-    rc = make_ws(c, c->stream, grid, 2, c->d_result, -1.0, &ws);
-    if (rc) return rc;
-    EventPair ep{};
-    const EventPair* timed = nullptr;
-    rc = prof_pair(c, &ep, &timed);
-    if (rc) return rc;
     const bool anti = antithetic != 0, geo = avg_kind == OLMC_AVG_GEOMETRIC, fast = avg_kind == OLMC_AVG_ARITHMETIC_FAST;
-    if (anti && geo) launch_timed(asian_kernel<true, true>, dim3(grid), dim3(kBlock), c->stream, timed, pr, ac, ws);
-    else if (geo) launch_timed(asian_kernel<false, true>, dim3(grid), dim3(kBlock), c->stream, timed, pr, ac, ws);
-    else if (anti && fast) launch_timed(asian_kernel<true, false>, dim3(grid), dim3(kBlock), c->stream, timed, pr, ac, ws);
-    else if (fast) launch_timed(asian_kernel<false, false>, dim3(grid), dim3(kBlock), c->stream, timed, pr, ac, ws);
-    else if (anti) launch_timed(asian_exp64_kernel<true>, dim3(grid), dim3(kBlock), c->stream, timed, pr, ac, ws);      // reference precision
-    else launch_timed(asian_exp64_kernel<false>, dim3(grid), dim3(kBlock), c->stream, timed, pr, ac, ws);
-    rc = after_launch(c, c->stream);
-    if (rc) return rc;
-    rc = sync_or_recover(c, c->stream);
-    if (rc) return rc;
-    finish_stats(c->h_result[0], c->h_result[1], n_local * (antithetic ? 2 : 1), r, T, out);
-    if (poisoned(S, K, T, r, sigma, q)) nan_stats(out->n, out);
-    return OLMC_OK;
+    return run_structured(path_offset, n_local, n_steps, seed, antithetic, r, T, poisoned(S, K, T, r, sigma, q), out,
+                          [&](int32_t grid, hipStream_t st, const EventPair* timed, const PathRange& pr, const ReduceWs& ws) {
+                              auto go = [&](auto kernel) { launch_timed(kernel, dim3(grid), dim3(kBlock), st, timed, pr, ac, ws); };
+                              if (geo) with_bool(anti, [&](auto a) { go(asian_kernel<a, true>); });
+                              else if (fast) with_bool(anti, [&](auto a) { go(asian_kernel<a, false>); });
+                              else with_bool(anti, [&](auto a) { go(asian_exp64_kernel<a>); });      // reference precision
+                          });
 }
 
 // The 8 / 14 contracts of compute_greeks_unified over an arithmetic Asian (ExoticAdapter, unified_greeks.py:177-227) in one launch.
@@ -1225,77 +1257,45 @@ extern "C" int olmc_asian_greeks_fd(double S, double K, double T, double r, doub
     if (n_paths > static_cast<int64_t>(kMaxGrid) * kBlock) return fail(OLMC_ERR_ARG, "n_paths beyond one launch of the fused Asian Greeks kernel (2^26)");
     const PathRange pr = make_range(0, n_paths, n_steps, seed);
     const int32_t grid = static_cast<int32_t>((n_paths + kBlock - 1) / kBlock);      // the grid covers every path
-    const int nsets = gs.k <= 8 ? 8 : 16;
-    ReduceWs ws;
-    rc = make_ws(c, c->stream, grid, 2 * nsets, c->d_result, -1.0, &ws);
-    if (rc) return rc;
-    EventPair ep{};
-    const EventPair* timed = nullptr;
-    rc = prof_pair(c, &ep, &timed);
-    if (rc) return rc;
+    const int nsets = gs.nsets();
     const bool anti = antithetic != 0;
-    if (geo) {
-        if (nsets == 8 && anti) launch_timed(asian_geometric_greeks_kernel<true, 8>, dim3(grid), dim3(kBlock), c->stream, timed, pr, as, ws);
-        else if (nsets == 8) launch_timed(asian_geometric_greeks_kernel<false, 8>, dim3(grid), dim3(kBlock), c->stream, timed, pr, as, ws);
-        else if (anti) launch_timed(asian_geometric_greeks_kernel<true, 16>, dim3(grid), dim3(kBlock), c->stream, timed, pr, as, ws);
-        else launch_timed(asian_geometric_greeks_kernel<false, 16>, dim3(grid), dim3(kBlock), c->stream, timed, pr, as, ws);
-    } else if (nsets == 8 && anti) launch_timed(asian_exp64_greeks_kernel<true, 8>, dim3(grid), dim3(kBlock), c->stream, timed, pr, as, ws);
-    else if (nsets == 8) launch_timed(asian_exp64_greeks_kernel<false, 8>, dim3(grid), dim3(kBlock), c->stream, timed, pr, as, ws);
-    else if (anti) launch_timed(asian_exp64_greeks_kernel<true, 16>, dim3(grid), dim3(kBlock), c->stream, timed, pr, as, ws);
-    else launch_timed(asian_exp64_greeks_kernel<false, 16>, dim3(grid), dim3(kBlock), c->stream, timed, pr, as, ws);
-    rc = after_launch(c, c->stream);
+    rc = launch_reduce(c, c->stream, c->d_result, -1.0, 2 * nsets, grid, [&](int32_t g, hipStream_t st, const EventPair* timed, const ReduceWs& ws) {
+        auto go = [&](auto kernel) { launch_timed(kernel, dim3(g), dim3(kBlock), st, timed, pr, as, ws); };
+        if (geo) with_set_anti(nsets, anti, [&](auto width, auto a) { go(asian_geometric_greeks_kernel<a, width>); });
+        else with_set_anti(nsets, anti, [&](auto width, auto a) { go(asian_exp64_greeks_kernel<a, width>); });
+    });
     if (rc) return rc;
-    rc = sync_or_recover(c, c->stream);
-    if (rc) return rc;
-    const int64_t n = n_paths * (anti ? 2 : 1);
     olmc_stats st[OLMC_MAX_BATCH];
-    for (int i = 0; i < gs.k; ++i) {
-        finish_stats(c->h_result[2 * i], c->h_result[2 * i + 1], n, gs.o[i].r, gs.o[i].T, &st[i]);
-        if (poisoned(gs.o[i].S, gs.o[i].K, gs.o[i].T, gs.o[i].r, gs.o[i].sigma, gs.o[i].q)) nan_stats(n, &st[i]);
-    }
+    finish_set(c->h_result, nullptr, n_paths * (anti ? 2 : 1), gs.o, gs.k, false, false, st);
     gs.finish(st, T, out9, evals);
     return OLMC_OK;
 }
 
 // ========================================================== barrier / lookback ====
 namespace {
-int run_extrema(double S, double K, double T, double r, double sigma, double q, int is_call, int payoff, double barrier,
-                int64_t path_offset, int64_t n_local, int32_t n_steps, uint64_t seed, int antithetic, olmc_stats* out) {
-    if (!out) return fail(OLMC_ERR_ARG, "null pointer");
-    int rc = check_paths(path_offset, n_local, n_steps);
-    if (rc) return rc;
-    CtxLease lease;
-    rc = ctx_lease(&lease);
-    if (rc) return rc;
-    DeviceCtx* const c = lease.c;
-    const PathRange pr = make_range(path_offset, n_local, n_steps, seed);
-    const int32_t grid = grid_for(n_local);
+// The contract of a barrier / lookback path (extrema_kernel, qmc_path_kernel).  `barrier` is the level of a barrier kind (> 0: the
+// entry points refuse any other) and 0 where there is none (lookbacks, the Asian payoffs of qmc_path_kernel): log_barrier_rel is then 0.
+ExtremaContract make_extrema(double S, double K, double T, double r, double sigma, double q, int is_call, int payoff, double barrier, int32_t n_steps) {
+    const GbmStep g = gbm_step(T, n_steps, r, q, sigma);          // exotic_options.py:54-56
     ExtremaContract ec;
-    const double dt = T / n_steps;                               // exotic_options.py:54-56
     ec.s0 = S;
-    ec.log_barrier_rel = payoff <= kBarrierDownIn ? std::log(barrier / S) : 0.0;
-    ec.drift = (r - q - 0.5 * sigma * sigma) * dt;
-    ec.vol = sigma * std::sqrt(dt);
+    ec.log_barrier_rel = barrier > 0.0 ? std::log(barrier / S) : 0.0;
+    ec.drift = g.drift;
+    ec.vol = g.vol;
     ec.strike = K;
     ec.sign = is_call ? 1.0 : -1.0;
     ec.payoff = payoff;
     ec.pad = 0;
-    ReduceWs ws;
-    rc = make_ws(c, c->stream, grid, 2, c->d_result, -1.0, &ws);
-    if (rc) return rc;
-    EventPair ep{};
-    const EventPair* timed = nullptr;
-    rc = prof_pair(c, &ep, &timed);
-    if (rc) return rc;
-    if (antithetic) launch_timed(extrema_kernel<true>, dim3(grid), dim3(kBlock), c->stream, timed, pr, ec, ws);
-    else launch_timed(extrema_kernel<false>, dim3(grid), dim3(kBlock), c->stream, timed, pr, ec, ws);
-    rc = after_launch(c, c->stream);
-    if (rc) return rc;
-    rc = sync_or_recover(c, c->stream);
-    if (rc) return rc;
-    finish_stats(c->h_result[0], c->h_result[1], n_local * (antithetic ? 2 : 1), r, T, out);
-    if (poisoned(S, K, T, r, sigma, q) || std::isnan(barrier)) nan_stats(out->n, out);
-    return OLMC_OK;
+    return ec;
+}
+
+int run_extrema(double S, double K, double T, double r, double sigma, double q, int is_call, int payoff, double barrier,
+                int64_t path_offset, int64_t n_local, int32_t n_steps, uint64_t seed, int antithetic, olmc_stats* out) {
+    const ExtremaContract ec = make_extrema(S, K, T, r, sigma, q, is_call, payoff, barrier, n_steps);
+    return run_structured(path_offset, n_local, n_steps, seed, antithetic, r, T, poisoned(S, K, T, r, sigma, q) || std::isnan(barrier), out,
+                          [&](int32_t grid, hipStream_t st, const EventPair* timed, const PathRange& pr, const ReduceWs& ws) {
+                              with_bool(antithetic != 0, [&](auto a) { launch_timed(extrema_kernel<a>, dim3(grid), dim3(kBlock), st, timed, pr, ec, ws); });
+                          });
 }
 }  // namespace
 
@@ -1335,66 +1335,19 @@ extern "C" int olmc_extrema_greeks_fd(double S, double K, double T, double r, do
     DeviceCtx* const c = lease.c;
     const PathRange pr = make_range(0, n_paths, n_steps, seed);
     const int32_t grid = static_cast<int32_t>((n_paths + kBlock - 1) / kBlock);      // the grid covers every path
-    const int nsets = gs.k <= 8 ? 8 : 16;
-    ReduceWs ws;
-    rc = make_ws(c, c->stream, grid, 2 * nsets, c->d_result, -1.0, &ws);
-    if (rc) return rc;
-    EventPair ep{};
-    const EventPair* timed = nullptr;
-    rc = prof_pair(c, &ep, &timed);
-    if (rc) return rc;
+    const int nsets = gs.nsets();
     const bool anti = antithetic != 0;
-    if (nsets == 8 && anti) launch_timed(extrema_greeks_kernel<true, 8>, dim3(grid), dim3(kBlock), c->stream, timed, pr, es, ws);
-    else if (nsets == 8) launch_timed(extrema_greeks_kernel<false, 8>, dim3(grid), dim3(kBlock), c->stream, timed, pr, es, ws);
-    else if (anti) launch_timed(extrema_greeks_kernel<true, 16>, dim3(grid), dim3(kBlock), c->stream, timed, pr, es, ws);
-    else launch_timed(extrema_greeks_kernel<false, 16>, dim3(grid), dim3(kBlock), c->stream, timed, pr, es, ws);
-    rc = after_launch(c, c->stream);
+    rc = launch_reduce(c, c->stream, c->d_result, -1.0, 2 * nsets, grid, [&](int32_t g, hipStream_t st, const EventPair* timed, const ReduceWs& ws) {
+        with_set_anti(nsets, anti, [&](auto width, auto a) { launch_timed(extrema_greeks_kernel<a, width>, dim3(g), dim3(kBlock), st, timed, pr, es, ws); });
+    });
     if (rc) return rc;
-    rc = sync_or_recover(c, c->stream);
-    if (rc) return rc;
-    const int64_t n = n_paths * (anti ? 2 : 1);
     olmc_stats st[OLMC_MAX_BATCH];
-    for (int i = 0; i < gs.k; ++i) {
-        finish_stats(c->h_result[2 * i], c->h_result[2 * i + 1], n, gs.o[i].r, gs.o[i].T, &st[i]);
-        if (poisoned(gs.o[i].S, gs.o[i].K, gs.o[i].T, gs.o[i].r, gs.o[i].sigma, gs.o[i].q) || std::isnan(barrier)) nan_stats(n, &st[i]);
-    }
+    finish_set(c->h_result, nullptr, n_paths * (anti ? 2 : 1), gs.o, gs.k, std::isnan(barrier), false, st);
     gs.finish(st, T, out9, evals);
     return OLMC_OK;
 }
 
 // ======================================================= autocallable / cliquet ====
-namespace {
-template <typename Launch>
-int run_structured(int64_t path_offset, int64_t n_local, int32_t n_steps, uint64_t seed, int antithetic, double r_for_discount,
-                   double T, bool poisoned_inputs, olmc_stats* out, Launch launch, int nv = 2, double* raw_sums = nullptr) {
-    if (!out) return fail(OLMC_ERR_ARG, "null pointer");
-    int rc = check_paths(path_offset, n_local, n_steps);
-    if (rc) return rc;
-    CtxLease lease;
-    rc = ctx_lease(&lease);
-    if (rc) return rc;
-    DeviceCtx* const c = lease.c;
-    const PathRange pr = make_range(path_offset, n_local, n_steps, seed);
-    const int32_t grid = grid_for(n_local);
-    ReduceWs ws;
-    rc = make_ws(c, c->stream, grid, nv, c->d_result, -1.0, &ws);
-    if (rc) return rc;
-    EventPair ep{};
-    const EventPair* timed = nullptr;
-    rc = prof_pair(c, &ep, &timed);
-    if (rc) return rc;
-    launch(grid, c->stream, timed, pr, ws);
-    rc = after_launch(c, c->stream);
-    if (rc) return rc;
-    rc = sync_or_recover(c, c->stream);
-    if (rc) return rc;
-    finish_stats(c->h_result[0], c->h_result[1], n_local * (antithetic ? 2 : 1), r_for_discount, T, out);
-    if (raw_sums) for (int m = 0; m < nv; ++m) raw_sums[m] = c->h_result[m];     // the context is still leased
-    if (poisoned_inputs) nan_stats(out->n, out);
-    return OLMC_OK;
-}
-}  // namespace
-
 extern "C" int olmc_autocallable(double S, double T, double r, double sigma, double q, double autocall_barrier,
                                  double coupon_barrier, double coupon_rate, double ki_barrier, int32_t observation_freq,
                                  int64_t path_offset, int64_t n_local, int32_t n_steps, uint64_t seed, int antithetic,
@@ -1402,9 +1355,9 @@ extern "C" int olmc_autocallable(double S, double T, double r, double sigma, dou
     if (observation_freq < 1) return fail(OLMC_ERR_ARG, "observation_freq must be >= 1");
     if (n_steps >= 1 && n_steps / observation_freq < 1) return fail(OLMC_ERR_ARG, "no observation date: observation_freq > n_steps");
     AutocallContract ac;
-    const double dt = T / n_steps;
-    ac.drift = (r - q - 0.5 * sigma * sigma) * dt;
-    ac.vol = sigma * std::sqrt(dt);
+    const GbmStep g = gbm_step(T, n_steps, r, q, sigma);
+    ac.drift = g.drift;
+    ac.vol = g.vol;
     ac.log_autocall = log_level(autocall_barrier);
     ac.log_coupon = log_level(coupon_barrier);
     ac.log_ki = log_level(ki_barrier);
@@ -1412,14 +1365,13 @@ extern "C" int olmc_autocallable(double S, double T, double r, double sigma, dou
     ac.n_obs = n_steps / observation_freq;                      // len(range(f, M + 1, f))
     ac.coupon_unit = coupon_rate * T / ac.n_obs;                // coupon_rate * ((i+1)/n_obs) * T, accrued per observation (:459-460)
     ac.final_coupon = coupon_rate * T;
-    ac.obs_df = std::exp(-r * dt * observation_freq);           // exp(-r t dt) at t = k f, built up by products (:461)
+    ac.obs_df = std::exp(-r * g.dt * observation_freq);          // exp(-r t dt) at t = k f, built up by products (:461)
     ac.final_df = std::exp(-r * T);
     const bool bad = poisoned(S, 1.0, T, r, sigma, q) || std::isnan(autocall_barrier + coupon_barrier + coupon_rate + ki_barrier);
     // payoffs are already discounted path by path (exotic_options.py:463, 489): no outer discount
     return run_structured(path_offset, n_local, n_steps, seed, antithetic, 0.0, T, bad, out,
                           [&](int32_t grid, hipStream_t st, const EventPair* timed, const PathRange& pr, const ReduceWs& ws) {
-                              if (antithetic) launch_timed(autocall_kernel<true>, dim3(grid), dim3(kBlock), st, timed, pr, ac, ws);
-                              else launch_timed(autocall_kernel<false>, dim3(grid), dim3(kBlock), st, timed, pr, ac, ws);
+                              with_bool(antithetic != 0, [&](auto a) { launch_timed(autocall_kernel<a>, dim3(grid), dim3(kBlock), st, timed, pr, ac, ws); });
                           });
 }
 
@@ -1428,45 +1380,53 @@ extern "C" int olmc_cliquet(double S, double T, double r, double sigma, double q
                             int64_t n_local, int32_t n_steps, uint64_t seed, int antithetic, olmc_stats* out) {
     if (n_periods < 1 || (n_steps >= 1 && n_steps / n_periods < 1)) return fail(OLMC_ERR_ARG, "n_periods must be in [1, n_steps]");
     CliquetContract cc;
-    const double dt = T / n_steps;
+    const GbmStep g = gbm_step(T, n_steps, r, q, sigma);
     cc.s0 = S;
-    cc.drift = (r - q - 0.5 * sigma * sigma) * dt;
-    cc.vol = sigma * std::sqrt(dt);
+    cc.drift = g.drift;
+    cc.vol = g.vol;
     cc.local_cap = local_cap; cc.local_floor = local_floor; cc.global_cap = global_cap; cc.global_floor = global_floor;
     cc.steps_per_period = n_steps / n_periods;                  // exotic_options.py:532
     cc.n_periods = n_periods;
     const bool bad = poisoned(S, 1.0, T, r, sigma, q) || std::isnan(local_cap + local_floor + global_cap + global_floor);
     return run_structured(path_offset, n_local, n_steps, seed, antithetic, r, T, bad, out,
                           [&](int32_t grid, hipStream_t st, const EventPair* timed, const PathRange& pr, const ReduceWs& ws) {
-                              if (antithetic) launch_timed(cliquet_kernel<true>, dim3(grid), dim3(kBlock), st, timed, pr, cc, ws);
-                              else launch_timed(cliquet_kernel<false>, dim3(grid), dim3(kBlock), st, timed, pr, cc, ws);
+                              with_bool(antithetic != 0, [&](auto a) { launch_timed(cliquet_kernel<a>, dim3(grid), dim3(kBlock), st, timed, pr, cc, ws); });
                           });
 }
 
 // ================================================================== full paths ====
+namespace {
+// The prologue of a path-matrix export: the argument checks, the cap on the `bytes` it keeps on the device (refused with `too_big`),
+// a lease and, when `reserve`, a bulk buffer of `bytes`.
+int matrix_prologue(int64_t n_paths, int32_t n_steps, double bytes, const char* too_big, CtxLease* lease, bool reserve = true) {
+    int rc = check_paths(0, n_paths, n_steps);
+    if (rc) return rc;
+    if (bytes > 64e9) return fail(OLMC_ERR_ARG, too_big);
+    rc = ctx_lease(lease);
+    if (rc || !reserve) return rc;
+    return bulk_reserve(lease->c, static_cast<size_t>(bytes));
+}
+}  // namespace
+
 extern "C" int olmc_gbm_paths(double S, double T, double r, double sigma, double q, int64_t n_paths, int32_t n_steps,
                               uint64_t seed, int path_major, double* out_host) {
     if (!out_host) return fail(OLMC_ERR_ARG, "null pointer");
-    int rc = check_paths(0, n_paths, n_steps);
-    if (rc) return rc;
     const double bytes = 8.0 * static_cast<double>(n_paths) * (n_steps + 1.0);
-    if (bytes > 64e9) return fail(OLMC_ERR_ARG, "path matrix would exceed 64 GB");
     CtxLease lease;
-    rc = ctx_lease(&lease);
+    const int rc = matrix_prologue(n_paths, n_steps, bytes, "path matrix would exceed 64 GB", &lease);
     if (rc) return rc;
     DeviceCtx* const c = lease.c;
-    rc = bulk_reserve(c, static_cast<size_t>(bytes));
-    if (rc) return rc;
     LsmContract lc{};
-    const double dt = T / n_steps;                      // gbm_numpy.py:106-108
+    const GbmStep g = gbm_step(T, n_steps, r, q, sigma);          // gbm_numpy.py:106-108
     lc.log_s0 = std::log(S);
     lc.s_first = S;
-    lc.drift = (r - q - 0.5 * sigma * sigma) * dt;
-    lc.vol = sigma * std::sqrt(dt);
+    lc.drift = g.drift;
+    lc.vol = g.vol;
     lc.n_steps = n_steps;
     const PathRange pr = make_range(0, n_paths, n_steps, seed);
-    if (path_major) hipLaunchKernelGGL((lsm_paths_kernel<true>), dim3(grid_for(n_paths)), dim3(kBlock), 0, c->stream, pr, lc, static_cast<double*>(c->d_bulk));
-    else hipLaunchKernelGGL((lsm_paths_kernel<false>), dim3(grid_for(n_paths)), dim3(kBlock), 0, c->stream, pr, lc, static_cast<double*>(c->d_bulk));
+    with_bool(path_major != 0, [&](auto pm) {
+        launch_timed(lsm_paths_kernel<pm>, dim3(grid_for(n_paths)), dim3(kBlock), c->stream, nullptr, pr, lc, static_cast<double*>(c->d_bulk));
+    });
     HIP_TRY(hipGetLastError());
     return copy_to_host(c, out_host, c->d_bulk, static_cast<size_t>(bytes));
 }
@@ -1474,12 +1434,9 @@ extern "C" int olmc_gbm_paths(double S, double T, double r, double sigma, double
 extern "C" int olmc_exercise_boundary(double S, double K, double T, double r, double sigma, double q, int is_call,
                                       int64_t n_paths, int32_t n_steps, uint64_t seed, double* boundary_host) {
     if (!boundary_host) return fail(OLMC_ERR_ARG, "null pointer");
-    int rc = check_paths(0, n_paths, n_steps);
-    if (rc) return rc;
     const double bytes = 8.0 * static_cast<double>(n_paths) * (n_steps + 1.0);
-    if (bytes > 64e9) return fail(OLMC_ERR_ARG, "path matrix would exceed 64 GB");
     CtxLease lease;
-    rc = ctx_lease(&lease);
+    int rc = matrix_prologue(n_paths, n_steps, bytes, "path matrix would exceed 64 GB", &lease, false);
     if (rc) return rc;
     DeviceCtx* const c = lease.c;
     const size_t rows = static_cast<size_t>(n_steps) + 1;
@@ -1489,11 +1446,11 @@ extern "C" int olmc_exercise_boundary(double S, double K, double T, double r, do
     double* d_paths = static_cast<double*>(c->d_bulk);
     double* d_boundary = reinterpret_cast<double*>(static_cast<char*>(c->d_bulk) + path_bytes);
     LsmContract lc{};
-    const double dt = T / n_steps;                      // exotic_options.py:54-56
+    const GbmStep g = gbm_step(T, n_steps, r, q, sigma);          // exotic_options.py:54-56
     lc.log_s0 = std::log(S);
     lc.s_first = std::exp(lc.log_s0);                   // :59-65: column 0 is exp(log S)
-    lc.drift = (r - q - 0.5 * sigma * sigma) * dt;
-    lc.vol = sigma * std::sqrt(dt);
+    lc.drift = g.drift;
+    lc.vol = g.vol;
     lc.n_steps = n_steps;
     const PathRange pr = make_range(0, n_paths, n_steps, seed);
     hipLaunchKernelGGL((lsm_paths_kernel<false>), dim3(grid_for(n_paths)), dim3(kBlock), 0, c->stream, pr, lc, d_paths);
@@ -1535,25 +1492,21 @@ extern "C" int olmc_american_lsm(double S, double K, double T, double r, double 
                                  int64_t n_paths, int32_t n_steps, int32_t poly_degree, uint64_t seed, olmc_stats* out) {
     if (!out) return fail(OLMC_ERR_ARG, "null pointer");
     if (poly_degree < 1 || poly_degree > kLsmMaxDegree) return fail(OLMC_ERR_ARG, "poly_degree must be in [1, 4]");
-    int rc = check_paths(0, n_paths, n_steps);
-    if (rc) return rc;
     const double path_bytes = 8.0 * static_cast<double>(n_paths) * (n_steps + 2.0) + 8.0 * 2 * 1024 * kLsmNV;   // + two buffers of <= 1024 workgroup rows
-    if (path_bytes > 64e9) return fail(OLMC_ERR_ARG, "path matrix would exceed 64 GB: lower n_paths or n_steps");
     CtxLease lease;
-    rc = ctx_lease(&lease);
+    int rc = matrix_prologue(n_paths, n_steps, path_bytes, "path matrix would exceed 64 GB: lower n_paths or n_steps", &lease);
     if (rc) return rc;
     DeviceCtx* const c = lease.c;
-    rc = bulk_reserve(c, static_cast<size_t>(path_bytes));
-    if (rc) return rc;
     double* d_paths = static_cast<double*>(c->d_bulk);                                  // [n_steps + 1][n_paths]
     double* d_cash = d_paths + static_cast<size_t>(n_steps + 1) * n_paths;              // [n_paths]
     double* d_rows = d_cash + n_paths;                                                  // [2][grid][kLsmNV]: the regression sums a date hands to the next launch
     LsmContract lc;
-    const double dt = T / n_steps;                      // exotic_options.py:54-56, 260-261
+    const GbmStep g = gbm_step(T, n_steps, r, q, sigma);          // exotic_options.py:54-56, 260-261
+    const double dt = g.dt;
     lc.log_s0 = std::log(S);
     lc.s_first = std::exp(lc.log_s0);
-    lc.drift = (r - q - 0.5 * sigma * sigma) * dt;
-    lc.vol = sigma * std::sqrt(dt);
+    lc.drift = g.drift;
+    lc.vol = g.vol;
     lc.strike = K;
     lc.inv_strike = 1.0 / K;
     lc.sign = is_call ? 1.0 : -1.0;
@@ -1607,8 +1560,7 @@ extern "C" int olmc_american_lsm(double S, double K, double T, double r, double 
     if (rc) return rc;
     if (g_profile) { rc = prof_end(c, c->stream, ep); if (rc) return rc; }
     // the time-0 cash flows are already discounted step by step (:302-304): no outer factor
-    finish_stats(c->h_result[0], c->h_result[1], n_paths, 0.0, T, out);
-    if (poisoned(S, K, T, r, sigma, q)) nan_stats(n_paths, out);
+    finish_one(c->h_result, n_paths, 0.0, T, poisoned(S, K, T, r, sigma, q), out);
     return OLMC_OK;
 }
 
@@ -1639,22 +1591,18 @@ extern "C" int olmc_heston_paths(double S, double T, double r, double q, double 
                                  double* var_host) {
     if (!spot_host || !var_host) return fail(OLMC_ERR_ARG, "null pointer");
     if (!(rho >= -1.0 && rho <= 1.0)) return fail(OLMC_ERR_ARG, "rho must be in [-1, 1]");
-    int rc = check_paths(0, n_paths, n_steps);
-    if (rc) return rc;
     const double bytes = 8.0 * static_cast<double>(n_paths) * (n_steps + 1.0);
-    if (2 * bytes > 64e9) return fail(OLMC_ERR_ARG, "path matrices would exceed 64 GB");
     CtxLease lease;
-    rc = ctx_lease(&lease);
+    int rc = matrix_prologue(n_paths, n_steps, 2 * bytes, "path matrices would exceed 64 GB", &lease);
     if (rc) return rc;
     DeviceCtx* const c = lease.c;
-    rc = bulk_reserve(c, 2 * static_cast<size_t>(bytes));
-    if (rc) return rc;
     double* d_spot = static_cast<double*>(c->d_bulk);
     double* d_var = d_spot + static_cast<size_t>(n_paths) * (n_steps + 1);
     const HestonContract hc = make_heston(S, 0.0, T, r, q, 1, kappa, theta, sigma_v, rho, v0, n_steps);
     const PathRange pr = make_range(0, n_paths, n_steps, seed);
-    if (path_major) hipLaunchKernelGGL((heston_paths_kernel<true>), dim3(grid_for(n_paths)), dim3(kBlock), 0, c->stream, pr, hc, S, d_spot, d_var);
-    else hipLaunchKernelGGL((heston_paths_kernel<false>), dim3(grid_for(n_paths)), dim3(kBlock), 0, c->stream, pr, hc, S, d_spot, d_var);
+    with_bool(path_major != 0, [&](auto pm) {
+        launch_timed(heston_paths_kernel<pm>, dim3(grid_for(n_paths)), dim3(kBlock), c->stream, nullptr, pr, hc, S, d_spot, d_var);
+    });
     HIP_TRY(hipGetLastError());
     rc = copy_to_host(c, spot_host, d_spot, static_cast<size_t>(bytes));
     if (rc) return rc;
@@ -1666,31 +1614,12 @@ extern "C" int olmc_heston(double S, double K, double T, double r, double q, int
                            uint64_t seed, int antithetic, olmc_stats* out) {
     if (!out) return fail(OLMC_ERR_ARG, "null pointer");
     if (!(rho >= -1.0 && rho <= 1.0)) return fail(OLMC_ERR_ARG, "rho must be in [-1, 1]");
-    int rc = check_paths(path_offset, n_local, n_steps);
-    if (rc) return rc;
-    CtxLease lease;
-    rc = ctx_lease(&lease);
-    if (rc) return rc;
-    DeviceCtx* const c = lease.c;
-    const PathRange pr = make_range(path_offset, n_local, n_steps, seed);
-    const int32_t grid = grid_for(n_local);
     const HestonContract hc = make_heston(S, K, T, r, q, is_call, kappa, theta, sigma_v, rho, v0, n_steps);
-    ReduceWs ws;
-    rc = make_ws(c, c->stream, grid, 2, c->d_result, -1.0, &ws);
-    if (rc) return rc;
-    EventPair ep{};
-    const EventPair* timed = nullptr;
-    rc = prof_pair(c, &ep, &timed);
-    if (rc) return rc;
-    if (antithetic) launch_timed(heston_kernel<true>, dim3(grid), dim3(kBlock), c->stream, timed, pr, hc, ws);
-    else launch_timed(heston_kernel<false>, dim3(grid), dim3(kBlock), c->stream, timed, pr, hc, ws);
-    rc = after_launch(c, c->stream);
-    if (rc) return rc;
-    rc = sync_or_recover(c, c->stream);
-    if (rc) return rc;
-    finish_stats(c->h_result[0], c->h_result[1], n_local * (antithetic ? 2 : 1), r, T, out);
-    if (poisoned(S, K, T, r, 0.0, q) || std::isnan(kappa + theta + sigma_v + rho + v0)) nan_stats(out->n, out);
-    return OLMC_OK;
+    const bool bad = poisoned(S, K, T, r, 0.0, q) || std::isnan(kappa + theta + sigma_v + rho + v0);
+    return run_structured(path_offset, n_local, n_steps, seed, antithetic, r, T, bad, out,
+                          [&](int32_t grid, hipStream_t st, const EventPair* timed, const PathRange& pr, const ReduceWs& ws) {
+                              with_bool(antithetic != 0, [&](auto a) { launch_timed(heston_kernel<a>, dim3(grid), dim3(kBlock), st, timed, pr, hc, ws); });
+                          });
 }
 
 // ============================================================== jump diffusion ====
@@ -1750,21 +1679,15 @@ extern "C" int olmc_jump_paths(double S, double T, double r, double sigma, doubl
     JumpContract jc;
     int rc = make_jump(S, 0.0, T, r, sigma, q, 1, model, lambda_j, a1, a2, a3, n_steps, &jc);
     if (rc) return rc;
-    rc = check_paths(0, n_paths, n_steps);
-    if (rc) return rc;
     const double bytes = 8.0 * static_cast<double>(n_paths) * (n_steps + 1.0);
-    if (bytes > 64e9) return fail(OLMC_ERR_ARG, "path matrix would exceed 64 GB");
     CtxLease lease;
-    rc = ctx_lease(&lease);
+    rc = matrix_prologue(n_paths, n_steps, bytes, "path matrix would exceed 64 GB", &lease);
     if (rc) return rc;
     DeviceCtx* const c = lease.c;
-    rc = bulk_reserve(c, static_cast<size_t>(bytes));
-    if (rc) return rc;
     const PathRange pr = make_range(0, n_paths, n_steps, seed);
-    if (path_major) hipLaunchKernelGGL((jump_paths_kernel<true>), dim3(grid_for(n_paths)), dim3(kBlock), 0, c->stream, pr, jc, S,
-                                       static_cast<double*>(c->d_bulk));
-    else hipLaunchKernelGGL((jump_paths_kernel<false>), dim3(grid_for(n_paths)), dim3(kBlock), 0, c->stream, pr, jc, S,
-                            static_cast<double*>(c->d_bulk));
+    with_bool(path_major != 0, [&](auto pm) {
+        launch_timed(jump_paths_kernel<pm>, dim3(grid_for(n_paths)), dim3(kBlock), c->stream, nullptr, pr, jc, S, static_cast<double*>(c->d_bulk));
+    });
     HIP_TRY(hipGetLastError());
     return copy_to_host(c, out_host, c->d_bulk, static_cast<size_t>(bytes));
 }
@@ -1838,6 +1761,30 @@ QmcShape qmc_shape(int64_t point_offset, int64_t n_paths, int32_t dims) {
     return sh;
 }
 
+// The Sobol shape ladder of the European kernels (qmc_shape), MODE kReduce / kControlVariate / kTerminal.
+template <int MODE>
+void launch_qmc_european(const QmcShape& sh, int32_t grid, hipStream_t s, const EventPair* timed, const QmcRange& qr, const Contract& ct,
+                         const uint32_t* d_sv, const uint32_t* d_shift, const ReduceWs& ws, double* terminal) {
+    auto go = [&](auto kernel) { launch_timed(kernel, dim3(grid), dim3(kBlock), s, timed, qr, ct, d_sv, d_shift, ws, terminal); };
+    if (sh.blocks && sh.aligned8) go(european_qmc_block_kernel<MODE, true>);
+    else if (sh.blocks) go(european_qmc_block_kernel<MODE, false>);
+    else if (sh.split && sh.aligned) go(european_qmc_kernel<MODE, true, true>);
+    else if (sh.split) go(european_qmc_kernel<MODE, true, false>);
+    else go(european_qmc_kernel<MODE, false, false>);
+}
+
+// The same for the fused batch kernel.
+template <int NSETS>
+void launch_qmc_batch(const QmcShape& sh, int32_t grid, hipStream_t s, const EventPair* timed, const QmcRange& qr, const ContractSet<NSETS>& cs,
+                      const uint32_t* d_sv, const uint32_t* d_shift, const ReduceWs& ws) {
+    auto go = [&](auto kernel) { launch_timed(kernel, dim3(grid), dim3(kBlock), s, timed, qr, cs, d_sv, d_shift, ws); };
+    if (sh.blocks && sh.aligned8) go(european_qmc_batch_kernel<NSETS, true, false, true>);
+    else if (sh.blocks) go(european_qmc_batch_kernel<NSETS, true, false>);
+    else if (sh.split && sh.aligned) go(european_qmc_batch_kernel<NSETS, false, true, true>);
+    else if (sh.split) go(european_qmc_batch_kernel<NSETS, false, true>);
+    else go(european_qmc_batch_kernel<NSETS, false, false>);
+}
+
 int run_qmc(double S, double K, double T, double r, double sigma, double q, int is_call, int64_t point_offset,
             int64_t n_paths, int32_t dims, const uint32_t* sv, const uint32_t* shift, int32_t bits,
             olmc_stats* out, double* terminal_host, int mirror = 0, olmc_cv_moments* cv = nullptr,
@@ -1862,13 +1809,11 @@ int run_qmc(double S, double K, double T, double r, double sigma, double q, int 
     uint32_t* d_sv = c->d_sobol;
     uint32_t* d_shift = d_sv + sv_words;
     double* d_term = terminal_host ? static_cast<double*>(c->d_bulk) : nullptr;
-    // gbm_qmc.py:38-44
-    const double dt = T / dims;
-    const double drift = (r - q - 0.5 * sigma * sigma) * dt;
+    const GbmStep g = gbm_step(T, dims, r, q, sigma);              // gbm_qmc.py:38-44
     Contract ct;
-    ct.vol = sigma * std::sqrt(dt);
+    ct.vol = g.vol;
     // gbm_qmc.py:44 (drift * steps) vs :70 (the antithetic variant multiplies the rate by T directly)
-    ct.a = mirror ? std::log(S) + (r - q - 0.5 * sigma * sigma) * T : std::log(S) + drift * dims;
+    ct.a = mirror ? std::log(S) + (r - q - 0.5 * sigma * sigma) * T : std::log(S) + g.drift * dims;
     ct.strike = K;
     ct.sign = is_call ? 1.0 : -1.0;
     ct.scale = 1.0;
@@ -1880,60 +1825,27 @@ int run_qmc(double S, double K, double T, double r, double sigma, double q, int 
     qr.dims = dims;
     qr.mirror = mirror ? 1 : 0;
     const QmcShape sh = qmc_shape(point_offset, n_paths, dims);
-    const bool blocks = sh.blocks;
-    const int32_t grid = sh.grid;
-    ReduceWs ws{};
-    EventPair ep{};
-    const EventPair* timed = nullptr;
-    double* const no_terminal = nullptr;
-    if (cv || (d_triple && shard_cv)) {
-        hipStream_t s = d_triple ? shard_stream : c->stream;
-        rc = make_ws(c, s, grid, 5, d_triple ? d_triple : c->d_result, d_triple ? static_cast<double>(n_paths) : -1.0, &ws);
-        if (rc) return rc;
-        rc = prof_pair(c, &ep, &timed);
-        if (rc) return rc;
-        if (blocks && sh.aligned8) launch_timed(european_qmc_block_kernel<kControlVariate, true>, dim3(grid), dim3(kBlock), s, timed, qr, ct, d_sv, d_shift, ws, no_terminal);
-        else if (blocks) launch_timed(european_qmc_block_kernel<kControlVariate, false>, dim3(grid), dim3(kBlock), s, timed, qr, ct, d_sv, d_shift, ws, no_terminal);
-        else if (sh.split && sh.aligned) launch_timed(european_qmc_kernel<kControlVariate, true, true>, dim3(grid), dim3(kBlock), s, timed, qr, ct, d_sv, d_shift, ws, no_terminal);
-        else if (sh.split) launch_timed(european_qmc_kernel<kControlVariate, true>, dim3(grid), dim3(kBlock), s, timed, qr, ct, d_sv, d_shift, ws, no_terminal);
-        else launch_timed(european_qmc_kernel<kControlVariate, false>, dim3(grid), dim3(kBlock), s, timed, qr, ct, d_sv, d_shift, ws, no_terminal);
-        if (d_triple) return after_launch(c, s);
-    } else if (!terminal_host) {
-        hipStream_t s = d_triple ? shard_stream : c->stream;
-        rc = make_ws(c, s, grid, 2, d_triple ? d_triple : c->d_result, d_triple ? static_cast<double>(n_paths) : -1.0, &ws);
-        if (rc) return rc;
-        rc = prof_pair(c, &ep, &timed);
-        if (rc) return rc;
-        if (blocks && sh.aligned8) launch_timed(european_qmc_block_kernel<kReduce, true>, dim3(grid), dim3(kBlock), s, timed, qr, ct, d_sv, d_shift, ws, no_terminal);
-        else if (blocks) launch_timed(european_qmc_block_kernel<kReduce, false>, dim3(grid), dim3(kBlock), s, timed, qr, ct, d_sv, d_shift, ws, no_terminal);
-        else if (sh.split && sh.aligned) launch_timed(european_qmc_kernel<kReduce, true, true>, dim3(grid), dim3(kBlock), s, timed, qr, ct, d_sv, d_shift, ws, no_terminal);
-        else if (sh.split) launch_timed(european_qmc_kernel<kReduce, true, false>, dim3(grid), dim3(kBlock), s, timed, qr, ct, d_sv, d_shift, ws, no_terminal);
-        else launch_timed(european_qmc_kernel<kReduce, false, false>, dim3(grid), dim3(kBlock), s, timed, qr, ct, d_sv, d_shift, ws, no_terminal);
-        if (d_triple) return after_launch(c, s);
-    } else {
-        if (blocks && sh.aligned8) hipLaunchKernelGGL((european_qmc_block_kernel<kTerminal, true>), dim3(grid), dim3(kBlock), 0, c->stream, qr, ct, d_sv, d_shift, ws, d_term);
-        else if (blocks) hipLaunchKernelGGL((european_qmc_block_kernel<kTerminal, false>), dim3(grid), dim3(kBlock), 0, c->stream, qr, ct, d_sv, d_shift, ws, d_term);
-        else if (sh.split && sh.aligned) hipLaunchKernelGGL((european_qmc_kernel<kTerminal, true, true>), dim3(grid), dim3(kBlock), 0, c->stream, qr, ct, d_sv, d_shift, ws, d_term);
-        else if (sh.split) hipLaunchKernelGGL((european_qmc_kernel<kTerminal, true>), dim3(grid), dim3(kBlock), 0, c->stream, qr, ct, d_sv, d_shift, ws, d_term);
-        else hipLaunchKernelGGL((european_qmc_kernel<kTerminal, false>), dim3(grid), dim3(kBlock), 0, c->stream, qr, ct, d_sv, d_shift, ws, d_term);
-    }
-    if (terminal_host) {            // no reduction workspace was handed out: only the launch status matters
-        HIP_TRY(hipGetLastError());
-        c->armed = 0;
-        return copy_to_host(c, terminal_host, d_term, term_bytes);
-    }
-    rc = after_launch(c, c->stream);
-    if (rc) return rc;
-    rc = sync_or_recover(c, c->stream);
-    if (rc) return rc;
-    if (cv) {       // device moments are of the UNdiscounted payoff x; d = disc * x (monte_carlo.py:175)
-        cv_from_device(c->h_result, n_paths, S, T, r, q, cv);
-        if (poisoned(S, K, T, r, sigma, q)) cv->value = std::nan("");
+    if (!terminal_host) {
+        const bool five = cv || (d_triple && shard_cv);
+        rc = launch_reduce(c, d_triple ? shard_stream : c->stream, d_triple ? d_triple : c->d_result, d_triple ? static_cast<double>(n_paths) : -1.0,
+                           five ? 5 : 2, sh.grid, [&](int32_t grid, hipStream_t s, const EventPair* timed, const ReduceWs& ws) {
+            if (five) launch_qmc_european<kControlVariate>(sh, grid, s, timed, qr, ct, d_sv, d_shift, ws, nullptr);
+            else launch_qmc_european<kReduce>(sh, grid, s, timed, qr, ct, d_sv, d_shift, ws, nullptr);
+        });
+        if (rc || d_triple) return rc;
+        if (cv) {       // device moments are of the UNdiscounted payoff x; d = disc * x (monte_carlo.py:175)
+            cv_from_device(c->h_result, n_paths, S, T, r, q, cv);
+            if (poisoned(S, K, T, r, sigma, q)) cv->value = std::nan("");
+            return OLMC_OK;
+        }
+        finish_one(c->h_result, n_paths, r, T, poisoned(S, K, T, r, sigma, q), out);
         return OLMC_OK;
     }
-    finish_stats(c->h_result[0], c->h_result[1], n_paths, r, T, out);
-    if (poisoned(S, K, T, r, sigma, q)) nan_stats(n_paths, out);
-    return OLMC_OK;
+    // no reduction workspace is handed out: only the launch status matters
+    launch_qmc_european<kTerminal>(sh, sh.grid, c->stream, nullptr, qr, ct, d_sv, d_shift, ReduceWs{}, d_term);
+    HIP_TRY(hipGetLastError());
+    c->armed = 0;
+    return copy_to_host(c, terminal_host, d_term, term_bytes);
 }
 }  // namespace
 
@@ -2004,10 +1916,9 @@ int qmc_bridge_plan(DeviceCtx* c, int32_t n, QmcBridgePlan* plan) {
 template <int FAMILY>
 void launch_qmc_path(bool bridge, bool anti, int32_t grid, hipStream_t s, const EventPair* timed, const QmcRange& qr, const ExtremaContract& ec,
                      double inv_steps, const uint32_t* d_sv, const uint32_t* d_shift, const QmcBridgePlan& plan, const ReduceWs& ws) {
-    if (bridge && anti) launch_timed(qmc_path_kernel<FAMILY, true, true>, dim3(grid), dim3(kBlock), s, timed, qr, ec, inv_steps, d_sv, d_shift, plan, ws);
-    else if (bridge) launch_timed(qmc_path_kernel<FAMILY, true, false>, dim3(grid), dim3(kBlock), s, timed, qr, ec, inv_steps, d_sv, d_shift, plan, ws);
-    else if (anti) launch_timed(qmc_path_kernel<FAMILY, false, true>, dim3(grid), dim3(kBlock), s, timed, qr, ec, inv_steps, d_sv, d_shift, plan, ws);
-    else launch_timed(qmc_path_kernel<FAMILY, false, false>, dim3(grid), dim3(kBlock), s, timed, qr, ec, inv_steps, d_sv, d_shift, plan, ws);
+    with_bool(bridge, [&](auto b) {
+        with_bool(anti, [&](auto a) { launch_timed(qmc_path_kernel<FAMILY, b, a>, dim3(grid), dim3(kBlock), s, timed, qr, ec, inv_steps, d_sv, d_shift, plan, ws); });
+    });
 }
 
 // Workgroups of a QMC path launch: four points in flight per workgroup, grid-striding beyond kQmcPathMaxGrid.
@@ -2038,40 +1949,22 @@ int run_qmc_path(int family, int payoff, double S, double K, double T, double r,
         rc = qmc_bridge_plan(c, n_steps, &plan);
         if (rc) return rc;
     }
-    ExtremaContract ec;
-    const double dt = T / n_steps;                               // exotic_options.py:54-56
-    ec.s0 = S;
-    ec.log_barrier_rel = family == kQmcExtrema && payoff <= kBarrierDownIn ? std::log(barrier / S) : 0.0;
-    ec.drift = (r - q - 0.5 * sigma * sigma) * dt;
-    ec.vol = sigma * std::sqrt(dt);
-    ec.strike = K;
-    ec.sign = is_call ? 1.0 : -1.0;
-    ec.payoff = family == kQmcExtrema ? payoff : 0;
-    ec.pad = 0;
+    const ExtremaContract ec = make_extrema(S, K, T, r, sigma, q, is_call, family == kQmcExtrema ? payoff : 0, barrier, n_steps);
     QmcRange qr;
     qr.first = static_cast<uint64_t>(point_offset);
     qr.count = n_points;
     qr.dims = n_steps;
     qr.mirror = antithetic ? 1 : 0;
     const int32_t grid = static_cast<int32_t>(std::min<int64_t>((n_points + kWavesPerBlock - 1) / kWavesPerBlock, kQmcPathMaxGrid));
-    ReduceWs ws;
-    rc = make_ws(c, c->stream, grid, 2, c->d_result, -1.0, &ws);
-    if (rc) return rc;
-    EventPair ep{};
-    const EventPair* timed = nullptr;
-    rc = prof_pair(c, &ep, &timed);
-    if (rc) return rc;
     const bool anti = antithetic != 0;
     const double inv_steps = 1.0 / n_steps;
-    if (family == kQmcAsianArithmetic) launch_qmc_path<kQmcAsianArithmetic>(bridge, anti, grid, c->stream, timed, qr, ec, inv_steps, d_sv, d_shift, plan, ws);
-    else if (family == kQmcAsianGeometric) launch_qmc_path<kQmcAsianGeometric>(bridge, anti, grid, c->stream, timed, qr, ec, inv_steps, d_sv, d_shift, plan, ws);
-    else launch_qmc_path<kQmcExtrema>(bridge, anti, grid, c->stream, timed, qr, ec, inv_steps, d_sv, d_shift, plan, ws);
-    rc = after_launch(c, c->stream);
+    rc = launch_reduce(c, c->stream, c->d_result, -1.0, 2, grid, [&](int32_t g, hipStream_t s, const EventPair* timed, const ReduceWs& ws) {
+        if (family == kQmcAsianArithmetic) launch_qmc_path<kQmcAsianArithmetic>(bridge, anti, g, s, timed, qr, ec, inv_steps, d_sv, d_shift, plan, ws);
+        else if (family == kQmcAsianGeometric) launch_qmc_path<kQmcAsianGeometric>(bridge, anti, g, s, timed, qr, ec, inv_steps, d_sv, d_shift, plan, ws);
+        else launch_qmc_path<kQmcExtrema>(bridge, anti, g, s, timed, qr, ec, inv_steps, d_sv, d_shift, plan, ws);
+    });
     if (rc) return rc;
-    rc = sync_or_recover(c, c->stream);
-    if (rc) return rc;
-    finish_stats(c->h_result[0], c->h_result[1], n_points * (anti ? 2 : 1), r, T, out);
-    if (poisoned(S, K, T, r, sigma, q) || std::isnan(barrier)) nan_stats(out->n, out);
+    finish_one(c->h_result, n_points * (anti ? 2 : 1), r, T, poisoned(S, K, T, r, sigma, q) || std::isnan(barrier), out);
     return OLMC_OK;
 }
 }  // namespace
@@ -2105,7 +1998,6 @@ int run_qmc_batch(const olmc_option* opts, int32_t k, int64_t point_offset, int6
     int rc = qmc_check(sv, shift, bits, dims, point_offset, n_paths);
     if (rc) return rc;
     const QmcShape sh = qmc_shape(point_offset, n_paths, dims);
-    const bool blocks = sh.blocks;
     const int64_t units = sh.units;
     if (d_sums && (k < 2 || (units + kBlock - 1) / kBlock > kMaxGrid))
         return fail(OLMC_ERR_ARG, "a shard of fused Sobol contracts needs 2 .. 16 contracts and points one grid covers");
@@ -2136,44 +2028,23 @@ int run_qmc_batch(const olmc_option* opts, int32_t k, int64_t point_offset, int6
     qr.mirror = 0;
     const int32_t grid = sh.split ? sh.grid : static_cast<int32_t>((units + kBlock - 1) / kBlock);     // the grid covers every point / block
     const int nsets = k <= 8 ? 8 : 16;
-    ReduceWs ws;
-    rc = make_ws(c, st, grid, 2 * nsets, d_sums ? d_sums : c->d_result, d_sums ? static_cast<double>(n_paths) : -1.0, &ws);
-    if (rc) return rc;
-    EventPair ep{};
-    const EventPair* timed = nullptr;
-    rc = prof_pair(c, &ep, &timed);
-    if (rc) return rc;
     int pos[OLMC_MAX_BATCH];
-    // make_contract(o, dims) IS gbm_qmc.py:38-44: dt = T / dims, drift * dims, sigma sqrt(dt)
-    if (nsets == 8) {
-        ContractSet<8> cs;
-        group_contracts<8>(opts, k, dims, &cs, pos);
-        if (blocks && sh.aligned8) launch_timed(european_qmc_batch_kernel<8, true, false, true>, dim3(grid), dim3(kBlock), st, timed, qr, cs, d_sv, d_shift, ws);
-        else if (blocks) launch_timed(european_qmc_batch_kernel<8, true, false>, dim3(grid), dim3(kBlock), st, timed, qr, cs, d_sv, d_shift, ws);
-        else if (sh.split && sh.aligned) launch_timed(european_qmc_batch_kernel<8, false, true, true>, dim3(grid), dim3(kBlock), st, timed, qr, cs, d_sv, d_shift, ws);
-        else if (sh.split) launch_timed(european_qmc_batch_kernel<8, false, true>, dim3(grid), dim3(kBlock), st, timed, qr, cs, d_sv, d_shift, ws);
-        else launch_timed(european_qmc_batch_kernel<8, false, false>, dim3(grid), dim3(kBlock), st, timed, qr, cs, d_sv, d_shift, ws);
-    } else {
-        ContractSet<16> cs;
-        group_contracts<16>(opts, k, dims, &cs, pos);
-        if (blocks && sh.aligned8) launch_timed(european_qmc_batch_kernel<16, true, false, true>, dim3(grid), dim3(kBlock), st, timed, qr, cs, d_sv, d_shift, ws);
-        else if (blocks) launch_timed(european_qmc_batch_kernel<16, true, false>, dim3(grid), dim3(kBlock), st, timed, qr, cs, d_sv, d_shift, ws);
-        else if (sh.split && sh.aligned) launch_timed(european_qmc_batch_kernel<16, false, true, true>, dim3(grid), dim3(kBlock), st, timed, qr, cs, d_sv, d_shift, ws);
-        else if (sh.split) launch_timed(european_qmc_batch_kernel<16, false, true>, dim3(grid), dim3(kBlock), st, timed, qr, cs, d_sv, d_shift, ws);
-        else launch_timed(european_qmc_batch_kernel<16, false, false>, dim3(grid), dim3(kBlock), st, timed, qr, cs, d_sv, d_shift, ws);
-    }
-    if (d_sums) {
-        if (pos_out) std::copy(pos, pos + k, pos_out);
-        return after_launch(c, st);
-    }
-    rc = after_launch(c, c->stream);
-    if (rc) return rc;
-    rc = sync_or_recover(c, c->stream);
-    if (rc) return rc;
-    for (int i = 0; i < k; ++i) {
-        if (poisoned(opts[i].S, opts[i].K, opts[i].T, opts[i].r, opts[i].sigma, opts[i].q)) nan_stats(n_paths, &out[i]);
-        else finish_stats(c->h_result[2 * pos[i]], c->h_result[2 * pos[i] + 1], n_paths, opts[i].r, opts[i].T, &out[i]);
-    }
+    rc = launch_reduce(c, st, d_sums ? d_sums : c->d_result, d_sums ? static_cast<double>(n_paths) : -1.0, 2 * nsets, grid,
+                       [&](int32_t g, hipStream_t s, const EventPair* timed, const ReduceWs& ws) {
+        // make_contract(o, dims) IS gbm_qmc.py:38-44: dt = T / dims, drift * dims, sigma sqrt(dt)
+        if (nsets == 8) {
+            ContractSet<8> cs;
+            group_contracts<8>(opts, k, dims, &cs, pos);
+            launch_qmc_batch<8>(sh, g, s, timed, qr, cs, d_sv, d_shift, ws);
+        } else {
+            ContractSet<16> cs;
+            group_contracts<16>(opts, k, dims, &cs, pos);
+            launch_qmc_batch<16>(sh, g, s, timed, qr, cs, d_sv, d_shift, ws);
+        }
+    });
+    if (d_sums && pos_out) std::copy(pos, pos + k, pos_out);
+    if (rc || d_sums) return rc;
+    finish_set(c->h_result, pos, n_paths, opts, k, false, false, out);
     return OLMC_OK;
 }
 }  // namespace
@@ -2656,17 +2527,7 @@ int cv_shard_dev(const olmc_option& o, int64_t path_offset, int64_t n_local, int
     CtxLease lease;
     int rc = ctx_lease(&lease);
     if (rc) return rc;
-    DeviceCtx* const c = lease.c;
-    PathRange pr = make_range(path_offset, n_local, n_steps, seed);
-    const int32_t grid = european_launch_shape(c, &pr, european_occupancy<1, kControlVariate>(antithetic != 0));
-    ContractSet<1> cs;
-    cs.c[0] = make_contract(o, n_steps);
-    cs.base_mask = 1u; cs.upper_continues_slot0 = 0;
-    ReduceWs ws;
-    rc = make_ws(c, s, grid, 5, d_out, static_cast<double>(n_local * (antithetic ? 2 : 1)), &ws);
-    if (rc) return rc;
-    launch_european<1, kControlVariate>(antithetic != 0, grid, s, pr, cs, ws, nullptr);
-    return after_launch(c, s);
+    return cv_device(lease.c, s, o, path_offset, n_local, n_steps, seed, antithetic, d_out, static_cast<double>(n_local * (antithetic ? 2 : 1)), false);
 }
 }  // namespace
 
@@ -2679,8 +2540,7 @@ extern "C" int olmc_multi_gpu_european(double S, double K, double T, double r, d
         return olmc_european_shard_dev(S, K, T, r, sigma, q, is_call, lo, n_local, n_steps, seed, antithetic, d_send, s);
     }, host);
     if (rc) return rc;
-    finish_stats(host[0], host[1], static_cast<int64_t>(host[2]), r, T, out);
-    if (poisoned(S, K, T, r, sigma, q)) nan_stats(out->n, out);
+    finish_one(host, static_cast<int64_t>(host[2]), r, T, poisoned(S, K, T, r, sigma, q), out);
     return OLMC_OK;
 }
 
@@ -2698,12 +2558,8 @@ extern "C" int olmc_multi_gpu_greeks_fd(double S, double K, double T, double r, 
         return batch_shard_dev(gs.o, gs.k, lo, n_local, n_steps, seed, 1, d_send, s, rank == 0 ? pos : other);      // layout is the one kept
     }, host);
     if (rc) return rc;
-    const int64_t n = static_cast<int64_t>(host[2 * nsets]);
     olmc_stats st[OLMC_MAX_BATCH];
-    for (int i = 0; i < gs.k; ++i) {
-        finish_stats(host[2 * pos[i]], host[2 * pos[i] + 1], n, gs.o[i].r, gs.o[i].T, &st[i]);
-        if (poisoned(gs.o[i].S, gs.o[i].K, gs.o[i].T, gs.o[i].r, gs.o[i].sigma, gs.o[i].q)) nan_stats(n, &st[i]);
-    }
+    finish_set(host, pos, static_cast<int64_t>(host[2 * nsets]), gs.o, gs.k, false, false, st);
     gs.finish(st, T, out9, evals);
     return OLMC_OK;
 }
@@ -2718,14 +2574,7 @@ extern "C" int olmc_multi_gpu_european_cv(double S, double K, double T, double r
         return cv_shard_dev(o, lo, n_local, n_steps, seed, antithetic, d_send, s);
     }, host);
     if (rc) return rc;
-    const double disc = std::exp(-r * T);          // device moments are of the UNdiscounted payoff x; d = disc * x (monte_carlo.py:175)
-    out->sum_d = disc * host[0];
-    out->sum_s = host[1];
-    out->sum_dd = disc * disc * host[2];
-    out->sum_ss = host[3];
-    out->sum_ds = disc * host[4];
-    out->n = static_cast<int64_t>(host[5]);
-    cv_finish(S, T, r, q, out);
+    cv_from_device(host, static_cast<int64_t>(host[5]), S, T, r, q, out);       // d = disc * x (monte_carlo.py:175)
     if (poisoned(S, K, T, r, sigma, q)) out->value = std::nan("");
     return OLMC_OK;
 }
@@ -2745,8 +2594,7 @@ extern "C" int olmc_multi_gpu_european_qmc(double S, double K, double T, double 
         return run_qmc(S, K, T, r, sigma, q, is_call, lo, n_local, dims, sv, shift, bits, nullptr, nullptr, 0, nullptr, d_send, s);
     }, host, true);
     if (rc) return rc;
-    finish_stats(host[0], host[1], static_cast<int64_t>(host[2]), r, T, out);
-    if (poisoned(S, K, T, r, sigma, q)) nan_stats(out->n, out);
+    finish_one(host, static_cast<int64_t>(host[2]), r, T, poisoned(S, K, T, r, sigma, q), out);
     return OLMC_OK;
 }
 
@@ -2769,12 +2617,8 @@ extern "C" int olmc_multi_gpu_european_qmc_greeks_fd(double S, double K, double 
         return run_qmc_batch(gs.o, gs.k, lo, n_local, dims, sv, shift, bits, nullptr, d_send, s, rank == 0 ? pos : other);      // layout is the one kept
     }, host, true);
     if (rc) return rc;
-    const int64_t n = static_cast<int64_t>(host[2 * nsets]);
     olmc_stats st[OLMC_MAX_BATCH];
-    for (int i = 0; i < gs.k; ++i) {
-        finish_stats(host[2 * pos[i]], host[2 * pos[i] + 1], n, gs.o[i].r, gs.o[i].T, &st[i]);
-        if (poisoned(gs.o[i].S, gs.o[i].K, gs.o[i].T, gs.o[i].r, gs.o[i].sigma, gs.o[i].q)) nan_stats(n, &st[i]);
-    }
+    finish_set(host, pos, static_cast<int64_t>(host[2 * nsets]), gs.o, gs.k, false, false, st);
     gs.finish(st, T, out9, evals);
     return OLMC_OK;
 }

@@ -186,3 +186,151 @@ def test_the_kernels_refuse_a_finite_math_build():
                         "-I" + os.path.join(ROOT, "optionslab_amd", "csrc"), os.path.join(ROOT, "optionslab_amd", "csrc", "olmc.hip")],
                        capture_output=True, text=True)
     assert r.returncode != 0 and "do not build with -ffinite-math-only" in r.stderr
+
+
+# One row per argument refusal of the pricing entry points that happens before a device is touched: (entry point, arguments,
+# exact olmc_last_error() message).  Every row returns OLMC_ERR_ARG with or without a GPU.
+def _ST():
+    return C.byref(_hip.Stats())
+
+
+def _CV():
+    return C.byref(_hip.CvMoments())
+
+
+_G = (100.0, 100.0, 1.0, 0.05, 0.2, 0.0, 1)                       # S K T r sigma q is_call
+_GT0 = (100.0, 100.0, 0.0, 0.05, 0.2, 0.0, 1)                     # T = 0
+_MKT = (100.0, 1.0, 0.05, 0.2, 0.0)                               # S T r sigma q
+_HES = (0.05, 0.0, 2.0, 0.04, 0.3)                                # r q kappa theta sigma_v (rho, v0 follow)
+
+
+def _opts(k):
+    return (_hip.Option * 16)(*[_hip.Option(100.0, 90.0 + i, 1.0, 0.05, 0.2, 0.0, 1, 0) for i in range(k)])
+
+
+def _sobol(dims):
+    return (C.c_uint32 * (30 * max(dims, 1)))(*range(1, 30 * max(dims, 1) + 1)), (C.c_uint32 * max(dims, 1))()
+
+
+def _out9():
+    return (C.c_double * 9)()
+
+
+_REFUSALS = [
+    ("olmc_european", lambda: (*_G, 0, 4, 1, 1, _ST()), "n_paths must be >= 1"),
+    ("olmc_european", lambda: (*_G, 100, 0, 1, 1, _ST()), "n_steps must be >= 1"),
+    ("olmc_european", lambda: (*_G, 100, 4, 1, 1, None), "null pointer"),
+    ("olmc_european_shard", lambda: (*_G, -1, 100, 4, 1, 1, _ST()), "path_offset must be >= 0"),
+    ("olmc_european_shard_dev", lambda: (*_G, 0, 100, 4, 1, 1, None, None), "null pointer"),
+    ("olmc_european_shard_dev", lambda: (*_G, 0, 0, 4, 1, 1, C.c_void_p(8), None), "n_paths must be >= 1"),
+    ("olmc_european_batch", lambda: (_opts(2), 0, 0, 100, 4, 1, 1, (_hip.Stats * 16)()), "batch size must be in [1, OLMC_MAX_BATCH]"),
+    ("olmc_european_batch", lambda: (_opts(2), 17, 0, 100, 4, 1, 1, (_hip.Stats * 16)()), "batch size must be in [1, OLMC_MAX_BATCH]"),
+    ("olmc_european_batch", lambda: (None, 2, 0, 100, 4, 1, 1, (_hip.Stats * 16)()), "null pointer"),
+    ("olmc_european_batch", lambda: (_opts(2), 2, 0, 100, 0, 1, 1, (_hip.Stats * 16)()), "n_steps must be >= 1"),
+    ("olmc_european_multi", lambda: (_opts(2), None, 0, 100, 4, 1, 1, (_hip.Stats * 16)()), "n_options must be >= 1"),
+    ("olmc_european_multi", lambda: (_opts(2), None, 2, 0, 4, 1, 1, (_hip.Stats * 16)()), "n_paths must be >= 1"),
+    ("olmc_european_greeks_fd", lambda: (*_GT0, 100, 4, 1, 0, _out9(), None), "T must be > 0 (price() returns intrinsic value without simulating)"),
+    ("olmc_european_greeks_fd", lambda: (*_G, 0, 4, 1, 0, _out9(), None), "n_paths must be >= 1"),
+    ("olmc_european_terminal", lambda: (*_MKT, 100, 4, 1, 1, None), "null pointer"),
+    ("olmc_european_terminal", lambda: (*_MKT, 100, 0, 1, 1, (C.c_double * 4)()), "n_steps must be >= 1"),
+    ("olmc_european_cv", lambda: (*_G, 0, 4, 1, 1, _CV()), "n_paths must be >= 1"),
+    ("olmc_european_cv_shard", lambda: (*_G, -5, 100, 4, 1, 1, _CV()), "path_offset must be >= 0"),
+    ("olmc_european_cv_shard", lambda: (*_G, 0, 100, 4, 1, 1, None), "null pointer"),
+    ("olmc_asian", lambda: (*_G, 7, 0, 100, 4, 1, 1, _ST()), "bad avg_kind"),
+    ("olmc_asian", lambda: (*_G, 0, 0, 100, 4, 1, 1, None), "null pointer"),
+    ("olmc_asian", lambda: (*_G, 2, 0, 100, 0, 1, 1, _ST()), "n_steps must be >= 1"),
+    ("olmc_asian_greeks_fd", lambda: (*_GT0, 0, 100, 4, 1, 1, 0, _out9(), None), "T must be > 0"),
+    ("olmc_asian_greeks_fd", lambda: (*_G, 2, 100, 4, 1, 1, 0, _out9(), None),
+     "avg_kind must be OLMC_AVG_ARITHMETIC or OLMC_AVG_GEOMETRIC (the fp32-exponent form has no fused Greeks)"),
+    ("olmc_asian_greeks_fd", lambda: (*_G, 0, 0, 4, 1, 1, 0, _out9(), None), "n_paths must be >= 1"),
+    ("olmc_asian_greeks_fd", lambda: (*_G, 0, 100, 4, 1, 1, 0, None, None), "null pointer"),
+    ("olmc_barrier", lambda: (*_G, -1.0, 0, 0, 100, 4, 1, 1, _ST()), "Barrier must be positive"),
+    ("olmc_barrier", lambda: (*_G, 120.0, 4, 0, 100, 4, 1, 1, _ST()), "bad barrier_kind"),
+    ("olmc_barrier", lambda: (*_G, 120.0, 0, 0, 100, 4, 1, 1, None), "null pointer"),
+    ("olmc_barrier", lambda: (*_G, 120.0, 0, 0, 100, 0, 1, 1, _ST()), "n_steps must be >= 1"),
+    ("olmc_lookback", lambda: (*_G, 1, -1, 100, 4, 1, 1, _ST()), "path_offset must be >= 0"),
+    ("olmc_lookback", lambda: (*_G, 1, 0, 100, 4, 1, 1, None), "null pointer"),
+    ("olmc_extrema_greeks_fd", lambda: (*_GT0, 0, 120.0, 100, 4, 1, 1, 0, _out9(), None), "T must be > 0"),
+    ("olmc_extrema_greeks_fd", lambda: (*_G, 6, 120.0, 100, 4, 1, 1, 0, _out9(), None),
+     "payoff must be a barrier kind (0..3) or OLMC_LOOKBACK_FLOATING / _FIXED (4, 5)"),
+    ("olmc_extrema_greeks_fd", lambda: (*_G, 2, 0.0, 100, 4, 1, 1, 0, _out9(), None), "Barrier must be positive"),
+    ("olmc_extrema_greeks_fd", lambda: (*_G, 4, 0.0, 0, 4, 1, 1, 0, _out9(), None), "n_paths must be >= 1"),
+    ("olmc_extrema_greeks_fd", lambda: (*_G, 4, 0.0, (1 << 26) + 1, 4, 1, 1, 0, _out9(), None),
+     "n_paths beyond one launch of the fused Greeks kernel (2^26)"),
+    ("olmc_autocallable", lambda: (*_MKT, 1.0, 0.8, 0.05, 0.6, 0, 0, 100, 4, 1, 1, _ST()), "observation_freq must be >= 1"),
+    ("olmc_autocallable", lambda: (*_MKT, 1.0, 0.8, 0.05, 0.6, 5, 0, 100, 4, 1, 1, _ST()), "no observation date: observation_freq > n_steps"),
+    ("olmc_autocallable", lambda: (*_MKT, 1.0, 0.8, 0.05, 0.6, 1, 0, 100, 4, 1, 1, None), "null pointer"),
+    ("olmc_autocallable", lambda: (*_MKT, 1.0, 0.8, 0.05, 0.6, 1, 0, 0, 4, 1, 1, _ST()), "n_paths must be >= 1"),
+    ("olmc_cliquet", lambda: (*_MKT, 0.05, 0.0, 0.5, 0.0, 0, 0, 100, 4, 1, 1, _ST()), "n_periods must be in [1, n_steps]"),
+    ("olmc_cliquet", lambda: (*_MKT, 0.05, 0.0, 0.5, 0.0, 5, 0, 100, 4, 1, 1, _ST()), "n_periods must be in [1, n_steps]"),
+    ("olmc_cliquet", lambda: (*_MKT, 0.05, 0.0, 0.5, 0.0, 2, -1, 100, 4, 1, 1, _ST()), "path_offset must be >= 0"),
+    ("olmc_gbm_paths", lambda: (*_MKT, 100, 4, 1, 0, None), "null pointer"),
+    ("olmc_gbm_paths", lambda: (*_MKT, 10 ** 9, 10, 1, 0, (C.c_double * 4)()), "path matrix would exceed 64 GB"),
+    ("olmc_gbm_paths", lambda: (*_MKT, 0, 10, 1, 0, (C.c_double * 4)()), "n_paths must be >= 1"),
+    ("olmc_exercise_boundary", lambda: (*_G, 100, 4, 1, None), "null pointer"),
+    ("olmc_exercise_boundary", lambda: (*_G, 10 ** 9, 10, 1, (C.c_double * 4)()), "path matrix would exceed 64 GB"),
+    ("olmc_heston_paths", lambda: (100.0, 1.0, *_HES, 1.5, 0.04, 100, 4, 1, 0, (C.c_double * 4)(), (C.c_double * 4)()), "rho must be in [-1, 1]"),
+    ("olmc_heston_paths", lambda: (100.0, 1.0, *_HES, -0.5, 0.04, 100, 4, 1, 0, (C.c_double * 4)(), None), "null pointer"),
+    ("olmc_heston_paths", lambda: (100.0, 1.0, *_HES, -0.5, 0.04, 5 * 10 ** 8, 10, 1, 0, (C.c_double * 4)(), (C.c_double * 4)()),
+     "path matrices would exceed 64 GB"),
+    ("olmc_heston", lambda: (100.0, 100.0, 1.0, 0.05, 0.0, 1, 2.0, 0.04, 0.3, -1.5, 0.04, 0, 100, 4, 1, 1, _ST()), "rho must be in [-1, 1]"),
+    ("olmc_heston", lambda: (100.0, 100.0, 1.0, 0.05, 0.0, 1, 2.0, 0.04, 0.3, -0.5, 0.04, 0, 100, 4, 1, 1, None), "null pointer"),
+    ("olmc_heston", lambda: (100.0, 100.0, 1.0, 0.05, 0.0, 1, 2.0, 0.04, 0.3, -0.5, 0.04, 0, 100, 0, 1, 1, _ST()), "n_steps must be >= 1"),
+    ("olmc_jump_diffusion", lambda: (*_G, 2, 1.0, -0.1, 0.2, 0.0, 0, 100, 4, 1, _ST()), "bad jump model"),
+    ("olmc_jump_diffusion", lambda: (*_G, 0, -1.0, -0.1, 0.2, 0.0, 0, 100, 4, 1, _ST()), "lambda_j must be non-negative"),
+    ("olmc_jump_diffusion", lambda: (*_G, 0, 100.0, -0.1, 0.2, 0.0, 0, 100, 4, 1, _ST()),
+     "lambda_j * T / n_steps must be <= 20 jumps per step: raise n_steps"),
+    ("olmc_jump_diffusion", lambda: (*_G, 0, 1.0, -0.1, 0.2, 0.0, 0, 100, 4, 1, None), "null pointer"),
+    ("olmc_jump_paths", lambda: (*_MKT, 0, 1.0, -0.1, 0.2, 0.0, 100, 4, 1, 0, None), "null pointer"),
+    ("olmc_jump_paths", lambda: (*_MKT, 0, 1.0, -0.1, 0.2, 0.0, 100, 0, 1, 0, (C.c_double * 4)()), "n_steps must be >= 1"),
+    ("olmc_jump_paths", lambda: (*_MKT, 0, 1.0, -0.1, 0.2, 0.0, 10 ** 9, 10, 1, 0, (C.c_double * 4)()), "path matrix would exceed 64 GB"),
+    ("olmc_american_lsm", lambda: (*_G, 100, 4, 0, 1, _ST()), "poly_degree must be in [1, 4]"),
+    ("olmc_american_lsm", lambda: (*_G, 10 ** 9, 10, 2, 1, _ST()), "path matrix would exceed 64 GB: lower n_paths or n_steps"),
+    ("olmc_european_qmc", lambda: (*_G, 0, 64, 4, *_sobol(4), 30, None), "null pointer"),
+    ("olmc_european_qmc", lambda: (*_G, 0, 64, 4, None, None, 30, _ST()), "null pointer"),
+    ("olmc_european_qmc", lambda: (*_G, 0, 64, 4, *_sobol(4), 32, _ST()), "only 30-bit Sobol tables (SciPy's default) are supported"),
+    ("olmc_european_qmc", lambda: (*_G, 0, 64, 0, *_sobol(1), 30, _ST()), "dims must be in [1, 21201]"),
+    ("olmc_european_qmc", lambda: (*_G, 1 << 30, 1, 1, *_sobol(1), 30, _ST()), "at most 2**30 Sobol points"),
+    ("olmc_european_qmc", lambda: (*_G, 0, 0, 4, *_sobol(4), 30, _ST()), "n_paths must be >= 1"),
+    ("olmc_european_qmc_cv", lambda: (*_G, 0, 64, 4, *_sobol(4), 30, None), "null pointer"),
+    ("olmc_european_qmc_cv", lambda: (*_G, -64, 64, 4, *_sobol(4), 30, _CV()), "path_offset must be >= 0"),
+    ("olmc_european_qmc_terminal", lambda: (*_MKT, 0, 64, 4, *_sobol(4), 30, 0, None), "null pointer"),
+    ("olmc_european_qmc_terminal", lambda: (*_MKT, 0, 64, 4, *_sobol(4), 29, 0, (C.c_double * 64)()), "only 30-bit Sobol tables (SciPy's default) are supported"),
+    ("olmc_european_qmc_batch", lambda: (_opts(2), 0, 0, 64, 4, *_sobol(4), 30, (_hip.Stats * 16)()), "batch size must be in [1, OLMC_MAX_BATCH]"),
+    ("olmc_european_qmc_batch", lambda: (_opts(2), 2, 0, 64, 4, *_sobol(4), 30, None), "null pointer"),
+    ("olmc_european_qmc_batch", lambda: (_opts(2), 2, 0, 64, 22000, *_sobol(4), 30, (_hip.Stats * 16)()), "dims must be in [1, 21201]"),
+    ("olmc_european_qmc_greeks_fd", lambda: (*_GT0, 64, 4, *_sobol(4), 30, 0, _out9(), None), "T must be > 0 (price() returns intrinsic value without simulating)"),
+    ("olmc_european_qmc_greeks_fd", lambda: (*_G, 64, 4, *_sobol(4), 30, 0, None, None), "null pointer"),
+    ("olmc_european_qmc_greeks_fd", lambda: (*_G, 0, 4, *_sobol(4), 30, 0, _out9(), None), "n_paths must be >= 1"),
+    ("olmc_asian_qmc", lambda: (*_G, 2, 0, 0, 64, 4, *_sobol(4), 30, 0, _ST()), "bad avg_kind (arithmetic or geometric)"),
+    ("olmc_asian_qmc", lambda: (*_G, 0, 2, 0, 64, 4, *_sobol(4), 30, 0, _ST()), "bad construction"),
+    ("olmc_asian_qmc", lambda: (*_G, 0, 1, 0, 64, 1025, *_sobol(1025), 30, 0, _ST()),
+     "the Brownian-bridge construction takes at most OLMC_QMC_BRIDGE_MAX_STEPS (1024) dates"),
+    ("olmc_asian_qmc", lambda: (*_G, 0, 0, 0, 64, 4, *_sobol(4), 30, 0, None), "null pointer"),
+    ("olmc_asian_qmc", lambda: (*_G, 1, 0, 0, 64, 4, *_sobol(4), 31, 0, _ST()), "only 30-bit Sobol tables (SciPy's default) are supported"),
+    ("olmc_extrema_qmc", lambda: (*_G, 6, 120.0, 0, 0, 64, 4, *_sobol(4), 30, 0, _ST()), "bad payoff"),
+    ("olmc_extrema_qmc", lambda: (*_G, 1, -2.0, 0, 0, 64, 4, *_sobol(4), 30, 0, _ST()), "Barrier must be positive"),
+    ("olmc_extrema_qmc", lambda: (*_G, 4, 0.0, 3, 0, 64, 4, *_sobol(4), 30, 0, _ST()), "bad construction"),
+    ("olmc_extrema_qmc", lambda: (*_G, 5, 0.0, 0, 0, 0, 4, *_sobol(4), 30, 0, _ST()), "n_paths must be >= 1"),
+    ("olmc_multi_gpu_european", lambda: (*_G, 100, 4, 1, 1, 1, None), "null pointer"),
+    ("olmc_multi_gpu_european", lambda: (*_G, 100, 4, 1, 1, 0, _ST()), "n_gpus out of range"),
+    ("olmc_multi_gpu_european", lambda: (*_G, 100, 0, 1, 1, 1, _ST()), "n_steps must be >= 1"),
+    ("olmc_multi_gpu_european", lambda: (*_G, 3, 4, 1, 1, 4, _ST()), "fewer paths than GPUs"),
+    ("olmc_multi_gpu_greeks_fd", lambda: (*_GT0, 100, 4, 1, 0, 1, _out9(), None), "T must be > 0 (price() returns intrinsic value without simulating)"),
+    ("olmc_multi_gpu_greeks_fd", lambda: (*_G, 100, 4, 1, 0, 17, _out9(), None), "n_gpus out of range"),
+    ("olmc_multi_gpu_european_cv", lambda: (*_G, 100, 4, 1, 1, 1, None), "null pointer"),
+    ("olmc_multi_gpu_european_qmc", lambda: (*_G, 64, 4, *_sobol(4), 30, 1, None), "null pointer"),
+    ("olmc_multi_gpu_european_qmc", lambda: (*_G, 64, 4, *_sobol(4), 16, 1, _ST()), "only 30-bit Sobol tables (SciPy's default) are supported"),
+    ("olmc_multi_gpu_european_qmc_greeks_fd", lambda: (*_GT0, 64, 4, *_sobol(4), 30, 0, 1, _out9(), None),
+     "T must be > 0 (price() returns intrinsic value without simulating)"),
+    ("olmc_multi_gpu_european_qmc_greeks_fd", lambda: (*_G, 64, 4, *_sobol(4), 30, 0, 0, _out9(), None), "n_gpus out of range"),
+    ("olmc_multi_gpu_european_qmc_cv", lambda: (*_G, 64, 0, *_sobol(1), 30, 1, _CV()), "dims must be in [1, 21201]"),
+]
+
+
+@pytest.mark.parametrize("name,args,message", _REFUSALS, ids=[f"{n}-{i}" for i, (n, _a, _m) in enumerate(_REFUSALS)])
+def test_entry_points_refuse_bad_arguments_before_touching_a_device(library, name, args, message):
+    """Each refusal answers OLMC_ERR_ARG (1) with its exact message, ahead of any device work (no device is initialised here)."""
+    rc = getattr(library, name)(*args())
+    assert rc == 1
+    assert library.olmc_last_error().decode() == message
