@@ -762,6 +762,73 @@ struct PathRange {
                           // there); INT32_MAX = none.  Other kernels ignore it.
 };
 
+// Local path i as Philox counter words 0 and 1 (its global index).
+struct PathWords {
+    uint32_t lo, hi;
+};
+__device__ __forceinline__ PathWords path_words(const PathRange& pr, int64_t i) {
+    const uint64_t gp = pr.first + static_cast<uint64_t>(i);
+    return {static_cast<uint32_t>(gp), static_cast<uint32_t>(gp >> 32)};
+}
+
+// The grid-stride path loop: body(i, g_lo, g_hi) for every local path i of this thread.
+template <typename Body>
+__device__ __forceinline__ void for_each_path(const PathRange& pr, Body body) {
+    const int64_t stride = static_cast<int64_t>(gridDim.x) * kBlock;
+    for (int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; i < pr.count; i += stride) {
+        const PathWords p = path_words(pr, i);
+        body(i, p.lo, p.hi);
+    }
+}
+
+// A path's dates as Philox blocks of four: `full` whole blocks, then one block of which the first `rem` dates are used.
+// Launch-uniform: computed once per kernel, before the path loop.
+struct BlockWalk {
+    int32_t full, rem;
+};
+__device__ __forceinline__ BlockWalk block_walk(int32_t n_steps) { return {n_steps >> 2, n_steps & 3}; }
+
+// Blocks [b0, b1), all four dates live: normals(b, z) fills z, then body(z, std::integral_constant<int, 4>).
+template <typename Normals, typename Body>
+__device__ __forceinline__ void full_blocks(int32_t b0, int32_t b1, Normals normals, Body body) {
+    float z[4];
+    for (int32_t b = b0; b < b1; ++b) {                 // branch-free body
+        normals(b, z);
+        body(z, std::integral_constant<int, 4>{});
+    }
+}
+
+// The trailing block, if any: body(z, std::integral_constant<int, rem>).
+template <typename Normals, typename Body>
+__device__ __forceinline__ void tail_block(BlockWalk w, Normals normals, Body body) {
+    if (w.rem) {
+        float z[4];
+        normals(w.full, z);
+        if (w.rem == 1) body(z, std::integral_constant<int, 1>{});
+        else if (w.rem == 2) body(z, std::integral_constant<int, 2>{});
+        else body(z, std::integral_constant<int, 3>{});
+    }
+}
+
+template <typename Normals, typename Body>
+__device__ __forceinline__ void walk_blocks(BlockWalk w, Normals normals, Body body) {
+    full_blocks(0, w.full, normals, body);
+    tail_block(w, normals, body);
+}
+
+// v[g] for a launch-uniform g: a ladder of selects, so that v stays in registers.  Each v[k] is read into a value of its own
+// first: a select between two reads of v becomes one read at a selected address, which puts v in scratch or LDS.
+template <int G>
+__device__ __forceinline__ double pick_recursion(int32_t g, const double (&v)[G]) {
+    double r = v[0];
+#pragma unroll
+    for (int k = 1; k < G; ++k) {
+        const double vk = v[k];
+        r = g == k ? vk : r;
+    }
+    return r;
+}
+
 enum Mode : int { kReduce = 0, kTerminal = 1, kControlVariate = 2, kSumOnly = 3 };   // kSumOnly: sum x per contract, no sum x^2 (prices only)
 
 template <int MODE>
@@ -1181,10 +1248,7 @@ __global__ __launch_bounds__(kBlock) void asian_exp64_kernel(PathRange pr, Asian
     const double vol = c.vol * kZScale * kUnit;         // applied to RAW normals
     const int32_t full = pr.n_steps >> 2, rem = pr.n_steps & 3;
     const RoundKeys rk = pin_round_keys(pr.key0, pr.key1);       // A/B at 1M x 1024: 965 -> 940 us (antithetic 1478 -> 1467)
-    const int64_t stride = static_cast<int64_t>(gridDim.x) * kBlock;
-    for (int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; i < pr.count; i += stride) {
-        const uint64_t gp = pr.first + static_cast<uint64_t>(i);
-        const uint32_t g_lo = static_cast<uint32_t>(gp), g_hi = static_cast<uint32_t>(gp >> 32);
+    for_each_path(pr, [&](int64_t, uint32_t g_lo, uint32_t g_hi) {
         double cum_u = 0.0, cum_d = 0.0, run_u = 0.0, run_d = 0.0;
         float z[4];
         for (int32_t b = 0; b < full; ++b) {            // branch-free body
@@ -1203,7 +1267,7 @@ __global__ __launch_bounds__(kBlock) void asian_exp64_kernel(PathRange pr, Asian
             const double x = fmax(c.sign * (avg - c.strike), 0.0);
             acc[0] += x; acc[1] += x * x;
         }
-    }
+    });
     block_then_grid_reduce<2>(acc, ws);
 }
 
@@ -1229,8 +1293,7 @@ __global__ __launch_bounds__(kBlock) void asian_exp64_greeks_kernel(PathRange pr
     {
         const double* __restrict__ drift = gs.drift;    // already in exponent units (host: the two multiplications of asian_exp64_kernel)
         const double* __restrict__ vol = gs.vol;
-        const uint64_t gp = pr.first + static_cast<uint64_t>(i < pr.count ? i : 0);
-        const uint32_t g_lo = static_cast<uint32_t>(gp), g_hi = static_cast<uint32_t>(gp >> 32);
+        const PathWords pw = path_words(pr, i < pr.count ? i : 0);
         double cum[LEGS][R], run[LEGS][G];
 #pragma unroll
         for (int leg = 0; leg < LEGS; ++leg) {
@@ -1280,25 +1343,18 @@ __global__ __launch_bounds__(kBlock) void asian_exp64_greeks_kernel(PathRange pr
                 }
             }
         };
-        const int32_t full = pr.n_steps >> 2, rem = pr.n_steps & 3;
-        float z[4];
-        for (int32_t b0 = 0; b0 < full; b0 += kRefreshBlocks) {
+        auto normals = [&](int32_t b, float (&z)[4]) { raw_normals4_pinned(pw.lo, pw.hi, static_cast<uint32_t>(b), 0u, rk, z); };
+        const BlockWalk w = block_walk(pr.n_steps);
+        for (int32_t b0 = 0; b0 < w.full; b0 += kRefreshBlocks) {
 #pragma unroll
             for (int d = 0; d < D; ++d) growth[d] = expm1(gs.rate_step[d] * static_cast<double>(4 * b0));
-            const int32_t b1 = min(b0 + kRefreshBlocks, full);
-            for (int32_t b = b0; b < b1; ++b) {                 // branch-free body
-                raw_normals4_pinned(g_lo, g_hi, static_cast<uint32_t>(b), 0u, rk, z);
-                dates(z, std::integral_constant<int, 4>{});
-            }
+            full_blocks(b0, min(b0 + kRefreshBlocks, w.full), normals, dates);
         }
-        if (rem) {
+        if (w.rem) {
 #pragma unroll
-            for (int d = 0; d < D; ++d) growth[d] = expm1(gs.rate_step[d] * static_cast<double>(4 * full));
-            raw_normals4_pinned(g_lo, g_hi, static_cast<uint32_t>(full), 0u, rk, z);
-            if (rem == 1) dates(z, std::integral_constant<int, 1>{});
-            else if (rem == 2) dates(z, std::integral_constant<int, 2>{});
-            else dates(z, std::integral_constant<int, 3>{});
+            for (int d = 0; d < D; ++d) growth[d] = expm1(gs.rate_step[d] * static_cast<double>(4 * w.full));
         }
+        tail_block(w, normals, dates);
         const bool alive = i < pr.count;
 #pragma unroll
         for (int leg = 0; leg < LEGS; ++leg)
@@ -1310,9 +1366,7 @@ __global__ __launch_bounds__(kBlock) void asian_exp64_greeks_kernel(PathRange pr
             acc[2 * s] = acc[2 * s + 1] = 0.0;
 #pragma unroll
             for (int leg = 0; leg < LEGS; ++leg) {
-                double r = run[leg][0];
-#pragma unroll
-                for (int k = 1; k < G; ++k) r = g == k ? run[leg][k] : r;
+                const double r = pick_recursion(g, run[leg]);
                 const double avg = gs.s0[s] * (r * gs.inv_steps);
                 const double x = alive ? fmax(gs.sign * (avg - gs.strike), 0.0) : 0.0;
                 acc[2 * s] += x;
@@ -1334,8 +1388,7 @@ __global__ __launch_bounds__(kBlock) void asian_geometric_greeks_kernel(PathRang
     double acc[NV];                                     // the grid covers every path (host guarantee): born after the date loop
     const RoundKeys rk = pin_round_keys(pr.key0, pr.key1);
     const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
-    const uint64_t gp = pr.first + static_cast<uint64_t>(i < pr.count ? i : 0);
-    const uint32_t g_lo = static_cast<uint32_t>(gp), g_hi = static_cast<uint32_t>(gp >> 32);
+    const PathWords pw = path_words(pr, i < pr.count ? i : 0);
     double base[LEGS][G], run[LEGS][G];
 #pragma unroll
     for (int leg = 0; leg < LEGS; ++leg)
@@ -1366,7 +1419,7 @@ __global__ __launch_bounds__(kBlock) void asian_geometric_greeks_kernel(PathRang
     for (; b + kAsianGroupBlocks <= full; b += kAsianGroupBlocks) {
 #pragma unroll
         for (int k = 0; k < kAsianGroupBlocks; ++k) {
-            raw_normals4_pinned(g_lo, g_hi, static_cast<uint32_t>(b + k), 0u, rk, z);
+            raw_normals4_pinned(pw.lo, pw.hi, static_cast<uint32_t>(b + k), 0u, rk, z);
             dates(z, std::integral_constant<int, 4>{});
         }
         close_group(4 * kAsianGroupBlocks);
@@ -1375,10 +1428,10 @@ __global__ __launch_bounds__(kBlock) void asian_geometric_greeks_kernel(PathRang
 #pragma unroll
     for (int k = 0; k < kAsianGroupBlocks; ++k) {
         if (k < tail_blocks) {
-            raw_normals4_pinned(g_lo, g_hi, static_cast<uint32_t>(b + k), 0u, rk, z);
+            raw_normals4_pinned(pw.lo, pw.hi, static_cast<uint32_t>(b + k), 0u, rk, z);
             dates(z, std::integral_constant<int, 4>{});
         } else if (k == tail_blocks && rem) {
-            raw_normals4_pinned(g_lo, g_hi, static_cast<uint32_t>(full), 0u, rk, z);
+            raw_normals4_pinned(pw.lo, pw.hi, static_cast<uint32_t>(full), 0u, rk, z);
             if (rem == 1) dates(z, std::integral_constant<int, 1>{});
             else if (rem == 2) dates(z, std::integral_constant<int, 2>{});
             else dates(z, std::integral_constant<int, 3>{});
@@ -1393,9 +1446,7 @@ __global__ __launch_bounds__(kBlock) void asian_geometric_greeks_kernel(PathRang
         double sum = 0.0, sumsq = 0.0;
 #pragma unroll
         for (int leg = 0; leg < LEGS; ++leg) {
-            double r = run[leg][0];
-#pragma unroll
-            for (int k = 1; k < G; ++k) r = g == k ? run[leg][k] : r;
+            const double r = pick_recursion(g, run[leg]);
             const double avg = exp(gs.log_s0[s] + r * gs.inv_steps);
             const double x = alive ? fmax(gs.sign * (avg - gs.strike), 0.0) : 0.0;
             sum += x;
@@ -1455,52 +1506,36 @@ __device__ __forceinline__ double min_f64(double a, double b) {
     return r;
 }
 
-template <bool ANTI, int LIVE>
-__device__ __forceinline__ void extrema_block(const float (&z)[4], double drift, double vol, double& cum_u, double& mx_u,
-                                              double& mn_u, double& cum_d, double& mx_d, double& mn_d) {
-#pragma unroll
-    for (int j = 0; j < LIVE; ++j) {
-        const double zj = static_cast<double>(z[j]);
-        cum_u += __builtin_fma(vol, zj, drift);
-        mx_u = max_f64(mx_u, cum_u);
-        mn_u = min_f64(mn_u, cum_u);
-        if constexpr (ANTI) {
-            cum_d += __builtin_fma(-vol, zj, drift);
-            mx_d = max_f64(mx_d, cum_d);
-            mn_d = min_f64(mn_d, cum_d);
-        }
-    }
-}
-
 template <bool ANTI>
 __global__ __launch_bounds__(kBlock) void extrema_kernel(PathRange pr, ExtremaContract c, ReduceWs ws) {
     const RoundKeys rk = pin_round_keys(pr.key0, pr.key1);
     double acc[2] = {0.0, 0.0};
     const double vol = c.vol * kZScale;             // applied to RAW normals
-    const int32_t full = pr.n_steps >> 2, rem = pr.n_steps & 3;
-    const int64_t stride = static_cast<int64_t>(gridDim.x) * kBlock;
-    for (int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; i < pr.count; i += stride) {
-        const uint64_t g = pr.first + static_cast<uint64_t>(i);
-        const uint32_t g_lo = static_cast<uint32_t>(g), g_hi = static_cast<uint32_t>(g >> 32);
+    const BlockWalk w = block_walk(pr.n_steps);
+    for_each_path(pr, [&](int64_t, uint32_t g_lo, uint32_t g_hi) {
         double cum_u = 0.0, mx_u = 0.0, mn_u = 0.0, cum_d = 0.0, mx_d = 0.0, mn_d = 0.0;   // t = 0: ln(S_0/S_0) = 0
-        float z[4];
-        for (int32_t b = 0; b < full; ++b) {           // branch-free body
-            raw_normals4_pinned(g_lo, g_hi, static_cast<uint32_t>(b), 0u, rk, z);
-            extrema_block<ANTI, 4>(z, c.drift, vol, cum_u, mx_u, mn_u, cum_d, mx_d, mn_d);
-        }
-        if (rem) {
-            raw_normals4_pinned(g_lo, g_hi, static_cast<uint32_t>(full), 0u, rk, z);
-            if (rem == 1) extrema_block<ANTI, 1>(z, c.drift, vol, cum_u, mx_u, mn_u, cum_d, mx_d, mn_d);
-            else if (rem == 2) extrema_block<ANTI, 2>(z, c.drift, vol, cum_u, mx_u, mn_u, cum_d, mx_d, mn_d);
-            else extrema_block<ANTI, 3>(z, c.drift, vol, cum_u, mx_u, mn_u, cum_d, mx_d, mn_d);
-        }
+        auto dates = [&](const float (&z)[4], auto live) {
+#pragma unroll
+            for (int j = 0; j < decltype(live)::value; ++j) {
+                const double zj = static_cast<double>(z[j]);
+                cum_u += __builtin_fma(vol, zj, c.drift);
+                mx_u = max_f64(mx_u, cum_u);
+                mn_u = min_f64(mn_u, cum_u);
+                if constexpr (ANTI) {
+                    cum_d += __builtin_fma(-vol, zj, c.drift);
+                    mx_d = max_f64(mx_d, cum_d);
+                    mn_d = min_f64(mn_d, cum_d);
+                }
+            }
+        };
+        walk_blocks(w, [&](int32_t b, float (&z)[4]) { raw_normals4_pinned(g_lo, g_hi, static_cast<uint32_t>(b), 0u, rk, z); }, dates);
         const double xu = extrema_payoff(c, cum_u, mx_u, mn_u);
         acc[0] += xu; acc[1] += xu * xu;
         if constexpr (ANTI) {
             const double xd = extrema_payoff(c, cum_d, mx_d, mn_d);
             acc[0] += xd; acc[1] += xd * xd;
         }
-    }
+    });
     block_then_grid_reduce<2>(acc, ws);
 }
 
@@ -1510,13 +1545,17 @@ __global__ __launch_bounds__(kBlock) void extrema_kernel(PathRange pr, ExtremaCo
 // six recursions of (cumulative log-return, its running max, its running min); spot, strike and the barrier's level relative to the
 // spot act in the epilogue.  Each recursion is extrema_kernel's own arithmetic, each payoff extrema_payoff's.
 
+// Contract slot s of the set (the per-step drift and vol are not used by extrema_payoff).
+__device__ __forceinline__ ExtremaContract extrema_slot(const ExtremaGreeksSet& gs, int s) {
+    return {gs.s0[s], gs.log_barrier_rel[s], 0.0, 0.0, gs.strike, gs.sign, gs.payoff, 0};
+}
+
 template <bool ANTI, int NSETS>
 __global__ __launch_bounds__(kBlock) void extrema_greeks_kernel(PathRange pr, ExtremaGreeksSet gs, ReduceWs ws) {
     constexpr int NV = 2 * NSETS, G = kAsianGroups, LEGS = ANTI ? 2 : 1;
     const RoundKeys rk = pin_round_keys(pr.key0, pr.key1);
     const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;       // the grid covers every path (host guarantee)
-    const uint64_t gp = pr.first + static_cast<uint64_t>(i < pr.count ? i : 0);
-    const uint32_t g_lo = static_cast<uint32_t>(gp), g_hi = static_cast<uint32_t>(gp >> 32);
+    const PathWords pw = path_words(pr, i < pr.count ? i : 0);
     double cum[LEGS][G], mx[LEGS][G], mn[LEGS][G];
 #pragma unroll
     for (int leg = 0; leg < LEGS; ++leg)
@@ -1540,16 +1579,14 @@ __global__ __launch_bounds__(kBlock) void extrema_greeks_kernel(PathRange pr, Ex
             if constexpr (ANTI) __builtin_amdgcn_sched_barrier(0);       // a date at a time: twelve chains already fill the pipeline, and
         }                                                                  // four dates in flight at once cost 40 more registers
     };
-    const int32_t full = pr.n_steps >> 2, rem = pr.n_steps & 3;
-    float z[4];
-    for (int32_t b = 0; b < full; ++b) {                // branch-free body
-        raw_normals4_pinned(g_lo, g_hi, static_cast<uint32_t>(b), 0u, rk, z);
-        dates(z, std::integral_constant<int, 4>{});
-    }
-    if (rem) {                                          // the last one to three dates: ONE copy of the date body in a real loop (three
-        raw_normals4_pinned(g_lo, g_hi, static_cast<uint32_t>(full), 0u, rk, z);       // unrolled variants were where the register count peaked)
+    auto normals = [&](int32_t b, float (&z)[4]) { raw_normals4_pinned(pw.lo, pw.hi, static_cast<uint32_t>(b), 0u, rk, z); };
+    const BlockWalk w = block_walk(pr.n_steps);
+    full_blocks(0, w.full, normals, dates);
+    if (w.rem) {                                        // the last one to three dates: ONE copy of the date body in a real loop (three
+        float z[4];                                     // unrolled variants were where the register count peaked)
+        normals(w.full, z);
 #pragma unroll 1
-        for (int32_t j = 0; j < rem; ++j) {
+        for (int32_t j = 0; j < w.rem; ++j) {
             const float one[4] = {j == 0 ? z[0] : (j == 1 ? z[1] : z[2]), 0.f, 0.f, 0.f};
             dates(one, std::integral_constant<int, 1>{});
         }
@@ -1564,9 +1601,7 @@ __global__ __launch_bounds__(kBlock) void extrema_greeks_kernel(PathRange pr, Ex
 #pragma unroll 1
     for (int s = 0; s < NSETS; ++s) {                   // a real loop: the payoff holds up to three library exponentials
         const int32_t g = gs.group[s];                  // launch-uniform
-        ExtremaContract c;
-        c.s0 = gs.s0[s]; c.log_barrier_rel = gs.log_barrier_rel[s]; c.drift = 0.0; c.vol = 0.0; c.strike = gs.strike; c.sign = gs.sign;
-        c.payoff = gs.payoff; c.pad = 0;
+        const ExtremaContract c = extrema_slot(gs, s);
         double sum = 0.0, sumsq = 0.0;
 #pragma unroll
         for (int leg = 0; leg < LEGS; ++leg) {
@@ -1702,10 +1737,7 @@ __global__ __launch_bounds__(kBlock) void cliquet_kernel(PathRange pr, CliquetCo
     constexpr int LEGS = ANTI ? 2 : 1;
     const int32_t used_steps = c.steps_per_period * c.n_periods;      // trailing steps never enter a period
     const double period_drift = c.steps_per_period * c.drift;
-    const int64_t stride = static_cast<int64_t>(gridDim.x) * kBlock;
-    for (int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; i < pr.count; i += stride) {
-        const uint64_t g = pr.first + static_cast<uint64_t>(i);
-        const uint32_t g_lo = static_cast<uint32_t>(g), g_hi = static_cast<uint32_t>(g >> 32);
+    for_each_path(pr, [&](int64_t, uint32_t g_lo, uint32_t g_hi) {
         double total[2] = {0.0, 0.0};
         double psum = 0.0;            // RAW normal sum of the period in flight (fp64 part)
         float part = 0.0f;            // ... and the blocks not yet folded into it
@@ -1747,7 +1779,7 @@ __global__ __launch_bounds__(kBlock) void cliquet_kernel(PathRange pr, CliquetCo
             const double x = fmax(clipped, 0.0) * c.s0;
             acc[0] += x; acc[1] += x * x;
         }
-    }
+    });
     block_then_grid_reduce<2>(acc, ws);
 }
 
@@ -1793,10 +1825,7 @@ __device__ __forceinline__ size_t path_at(int64_t i, int32_t t, int64_t count, i
 template <bool PATH_MAJOR = false>
 __global__ __launch_bounds__(kBlock) void lsm_paths_kernel(PathRange pr, LsmContract c, double* __restrict__ paths) {
     const double vol = c.vol * kZScale;
-    const int64_t stride = static_cast<int64_t>(gridDim.x) * kBlock;
-    for (int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; i < pr.count; i += stride) {
-        const uint64_t g = pr.first + static_cast<uint64_t>(i);
-        const uint32_t g_lo = static_cast<uint32_t>(g), g_hi = static_cast<uint32_t>(g >> 32);
+    for_each_path(pr, [&](int64_t i, uint32_t g_lo, uint32_t g_hi) {
         double cum = 0.0;
         paths[path_at<PATH_MAJOR>(i, 0, pr.count, pr.n_steps)] = c.s_first;
         const int32_t blocks = (pr.n_steps + 3) >> 2;
@@ -1812,7 +1841,7 @@ __global__ __launch_bounds__(kBlock) void lsm_paths_kernel(PathRange pr, LsmCont
                 }
             }
         }
-    }
+    });
 }
 
 // AmericanOption.early_exercise_boundary (exotic_options.py:309-345): for every date t the 10th (put) /
@@ -2210,10 +2239,7 @@ __global__ __launch_bounds__(kBlock) void heston_paths_kernel(PathRange pr, Hest
     const HestonStep hs(c);
     double v_start;
     const bool skip0 = heston_start(c, v_start);
-    const int64_t stride = static_cast<int64_t>(gridDim.x) * kBlock;
-    for (int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; i < pr.count; i += stride) {
-        const uint64_t g = pr.first + static_cast<uint64_t>(i);
-        const uint32_t g_lo = static_cast<uint32_t>(g), g_hi = static_cast<uint32_t>(g >> 32);
+    for_each_path(pr, [&](int64_t i, uint32_t g_lo, uint32_t g_hi) {
         double ls = c.log_s0, v = v_start;       // ls WITHOUT the (r - q) dt terms: added per date below
         spot[path_at<PATH_MAJOR>(i, 0, pr.count, pr.n_steps)] = s_first;
         var[path_at<PATH_MAJOR>(i, 0, pr.count, pr.n_steps)] = c.v0;
@@ -2235,7 +2261,7 @@ __global__ __launch_bounds__(kBlock) void heston_paths_kernel(PathRange pr, Hest
                 }
             }
         }
-    }
+    });
 }
 
 // Jump diffusion (src/pricing_models/jump_diffusion.py:160-225 Merton, :325-372 Kou): per step one
@@ -2309,15 +2335,12 @@ __global__ __launch_bounds__(kBlock) void jump_kernel(PathRange pr, JumpContract
     double acc[2] = {0.0, 0.0};
     const double vol = c.vol * kZScale;
     const int32_t blocks = (pr.n_steps + 1) >> 1;
-    const int64_t stride = static_cast<int64_t>(gridDim.x) * kBlock;
-    for (int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; i < pr.count; i += stride) {
-        const uint64_t g = pr.first + static_cast<uint64_t>(i);
-        const uint32_t g_lo = static_cast<uint32_t>(g), g_hi = static_cast<uint32_t>(g >> 32);
+    for_each_path(pr, [&](int64_t, uint32_t g_lo, uint32_t g_hi) {
         double ls = c.log_s0;
         for (int32_t b = 0; b < blocks; ++b) jump_block(pr, c, vol, g_lo, g_hi, b, ls, [](int32_t, double) {});
         const double x = fmax(c.sign * (exp(ls) - c.strike), 0.0);
         acc[0] += x; acc[1] += x * x;
-    }
+    });
     block_then_grid_reduce<2>(acc, ws);
 }
 
@@ -2327,16 +2350,13 @@ template <bool PATH_MAJOR>
 __global__ __launch_bounds__(kBlock) void jump_paths_kernel(PathRange pr, JumpContract c, double s_first, double* __restrict__ out) {
     const double vol = c.vol * kZScale;
     const int32_t blocks = (pr.n_steps + 1) >> 1;
-    const int64_t stride = static_cast<int64_t>(gridDim.x) * kBlock;
-    for (int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; i < pr.count; i += stride) {
-        const uint64_t g = pr.first + static_cast<uint64_t>(i);
-        const uint32_t g_lo = static_cast<uint32_t>(g), g_hi = static_cast<uint32_t>(g >> 32);
+    for_each_path(pr, [&](int64_t i, uint32_t g_lo, uint32_t g_hi) {
         double ls = c.log_s0;
         out[path_at<PATH_MAJOR>(i, 0, pr.count, pr.n_steps)] = s_first;
         for (int32_t b = 0; b < blocks; ++b)
             jump_block(pr, c, vol, g_lo, g_hi, b, ls,
                        [&](int32_t t, double l) { out[path_at<PATH_MAJOR>(i, t + 1, pr.count, pr.n_steps)] = exp(l); });
-    }
+    });
 }
 
 // ------------------------------------------------------------------ QMC ----
