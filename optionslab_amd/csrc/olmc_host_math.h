@@ -49,6 +49,7 @@ struct ContractSet {
 };
 
 constexpr double kZScale = 1.1774100225154747;     // sqrt(2 ln 2): raw Box-Muller normals are in units of it (olmc_kernels.h)
+constexpr double kPairZScale = 1.6651092223153954; // 2 sqrt(ln 2) = kZScale * sqrt(2): the unit of a path_normal_quarters sum (pair sums)
 constexpr int kExp2Entries = 256;                  // entries of the exp2 table = workgroup size (olmc_kernels.h: exp2_f64_tab)
 
 // Fused exotic Greeks: the 8 / 14 contracts are at most six path recursions (see the kernels in olmc_kernels.h).

@@ -110,7 +110,20 @@ __device__ __forceinline__ Words4 philox4x32_10_pinned(uint32_t c0, uint32_t c1,
 // kZScale = sqrt(2 ln 2) once per path (to sum z') or once per thread (to vol): two
 // multiplies fewer per pair, and the negation is a free source modifier of v_sqrt_f32.
 // kZScale = sqrt(2 ln 2): olmc_host_math.h
+//
+// Pair sums.  A kernel that needs only the SUM of a path's normals (the European family, the
+// cliquet's period sums) never needs the two normals of a pair apart, and
+//     cos t + sin t = sqrt(2) * sin(t + 1/8 turn)   (exact)
+// makes each pair one v_sin_f32 instead of v_sin_f32 + v_cos_f32 + v_add_f32.  The eighth of a
+// turn is an integer add of 2^20 to the angle word BEFORE the mantissa mask: modulo 2^23 it is
+// exact, and it maps the 2^23-point angle lattice onto itself, so the distribution of every pair
+// sum is exactly what it was (and the Philox words are untouched); only fp32 rounding moves.
+// The sum then comes out in units of (z'_cos + z'_sin) / sqrt(2): pair_sum_raw below, and
+// kPairZScale = kZScale * sqrt(2) = 2 sqrt(ln 2) (olmc_host_math.h) scales it to true normals.
 constexpr float kZScaleF = 1.17741002f;
+constexpr uint32_t kEighthTurn = 0x00100000u;      // 2^20 = 1/8 of the 2^23-point angle lattice
+constexpr float kInvSqrt2F = 0.707106769f;         // fp32(1 / sqrt(2)): an odd leftover normal in pair-sum units
+constexpr double kSqrt2 = 1.4142135623730951;      // pair-sum units -> RAW normal units (the cliquet's group folds)
 
 __device__ __forceinline__ void box_muller_raw(uint32_t xa, uint32_t xb, float& z_cos, float& z_sin) {
     constexpr float kTwoM32 = 2.3283064365386963e-10f;   // 2^-32
@@ -137,22 +150,21 @@ __device__ __forceinline__ void raw_normals4_pinned(uint32_t g_lo, uint32_t g_hi
     box_muller_raw(w.x2, w.x3, z[2], z[3]);
 }
 
-// acc + (sum of the four RAW normals of one Philox block), factored as
-//   fma(rad_b, cos_b + sin_b, fma(rad_a, cos_a + sin_a, acc)):
-// two adds and two fmas per block INCLUDING the accumulation (the packed-math form needed
-// register-pair moves: 5.25 instructions per block against 4).
-__device__ __forceinline__ float raw_block_sum_of_words(float acc, const Words4& w) {
+// acc + (z'_cos + z'_sin) / sqrt(2) of the pair (xa, xb) = acc + rad * sin(turns + 1/8): one fma.
+__device__ __forceinline__ float pair_sum_raw(float acc, uint32_t xa, uint32_t xb) {
     constexpr float kTwoM32 = 2.3283064365386963e-10f;   // 2^-32
     constexpr float kTwoM33 = 1.1641532182693481e-10f;   // 2^-33
-    const float ua = __builtin_fmaf(static_cast<float>(w.x0), kTwoM32, kTwoM33);
-    const float ub = __builtin_fmaf(static_cast<float>(w.x2), kTwoM32, kTwoM33);
-    const float ta = __uint_as_float((w.x1 & 0x007FFFFFu) | 0x3F800000u);
-    const float tb = __uint_as_float((w.x3 & 0x007FFFFFu) | 0x3F800000u);
-    const float rad_a = __builtin_amdgcn_sqrtf(-__builtin_amdgcn_logf(ua));
-    const float rad_b = __builtin_amdgcn_sqrtf(-__builtin_amdgcn_logf(ub));
-    const float sum_a = __builtin_amdgcn_cosf(ta) + __builtin_amdgcn_sinf(ta);
-    const float sum_b = __builtin_amdgcn_cosf(tb) + __builtin_amdgcn_sinf(tb);
-    return __builtin_fmaf(rad_b, sum_b, __builtin_fmaf(rad_a, sum_a, acc));
+    const float ua = __builtin_fmaf(static_cast<float>(xa), kTwoM32, kTwoM33);
+    const float turns = __uint_as_float(((xb + kEighthTurn) & 0x007FFFFFu) | 0x3F800000u);
+    const float rad = __builtin_amdgcn_sqrtf(-__builtin_amdgcn_logf(ua));
+    return __builtin_fmaf(rad, __builtin_amdgcn_sinf(turns), acc);
+}
+
+// acc + (sum of the four RAW normals of one Philox block) / sqrt(2), in pair-sum units (see Box-Muller above):
+//   fma(rad_b, sin(tb + 1/8), fma(rad_a, sin(ta + 1/8), acc)).
+// One fma per pair INCLUDING the accumulation; the one canonical association every evaluator of a path's sum shares.
+__device__ __forceinline__ float raw_block_sum_of_words(float acc, const Words4& w) {
+    return pair_sum_raw(pair_sum_raw(acc, w.x0, w.x1), w.x2, w.x3);
 }
 
 __device__ __forceinline__ float raw_block_accumulate(float acc, uint32_t g_lo, uint32_t g_hi, uint32_t block, uint32_t tag,
@@ -162,7 +174,9 @@ __device__ __forceinline__ float raw_block_accumulate(float acc, uint32_t g_lo, 
 
 // sum_t Z_t (true normals) of one path.  Block b covers steps 4b..4b+3; fp32 within a group of
 // kGroup blocks (16 normals, interleaved by hipcc for ILP), fp64 across groups; a trailing
-// partial block contributes its first n_steps % 4 normals.
+// partial block contributes its first n_steps % 4 normals.  Everything is in pair-sum units
+// (kPairZScale): whole pairs natively, and in the partial block a first pair (n_steps % 4 >= 2)
+// by the same identity, an odd leftover normal rad * cos(turns) times 1 / sqrt(2).
 //
 // The fp64 sum over groups has ONE canonical association, whoever computes it:
 //     sum = ((Q0 + Q1) + Q2) + Q3,    Q_w = the full groups [w gq, (w+1) gq) added in order, gq = ceil(#full groups / 4),
@@ -173,7 +187,7 @@ __device__ __forceinline__ float raw_block_accumulate(float acc, uint32_t g_lo, 
 // ~5e-7, about one path in ten million -- but "equal seeds give equal bits" must not depend on the launch shape.)
 constexpr int kGroup = 4;   // measured: 2 is 2 % slower, 8 no faster
 
-// Quarters [w0, w1) of one path's canonical sum, UNSCALED (multiply by kZScale once all four are in).  w0 = 0, w1 = 4 is the
+// Quarters [w0, w1) of one path's canonical sum, UNSCALED (multiply by kPairZScale once all four are in).  w0 = 0, w1 = 4 is the
 // whole path: ((0 + Q0) + Q1) + Q2, then + Q3.  A single quarter w returns 0 + Q_w = Q_w exactly.  One loop nest serves both.
 __device__ __forceinline__ double path_normal_quarters(uint32_t g_lo, uint32_t g_hi, int32_t n_steps, int32_t w0, int32_t w1, uint32_t k0,
                                                        uint32_t k1, uint32_t tag = 0u) {
@@ -202,14 +216,15 @@ __device__ __forceinline__ double path_normal_quarters(uint32_t g_lo, uint32_t g
             q += static_cast<double>(s);
         }
         const int32_t rem = n_steps & 3;
-        if (rem) {
-            float z[4];
+        if (rem) {                                     // pair-sum units: steps 0, 1 as a pair, a last odd step alone / sqrt(2)
             const Words4 wd = philox4x32_10_pinned(g_lo, g_hi, static_cast<uint32_t>(full), tag, rk);
-            box_muller_raw(wd.x0, wd.x1, z[0], z[1]);
-            box_muller_raw(wd.x2, wd.x3, z[2], z[3]);
-            float s = z[0];
-            if (rem > 1) s += z[1];
-            if (rem > 2) s += z[2];
+            float s = 0.0f;
+            if (rem > 1) s = pair_sum_raw(0.0f, wd.x0, wd.x1);
+            if (rem & 1) {
+                float z_cos, z_sin;
+                box_muller_raw(rem == 1 ? wd.x0 : wd.x2, rem == 1 ? wd.x1 : wd.x3, z_cos, z_sin);
+                s = __builtin_fmaf(z_cos, kInvSqrt2F, s);
+            }
             q += static_cast<double>(s);
         }
         acc += q;
@@ -219,7 +234,7 @@ __device__ __forceinline__ double path_normal_quarters(uint32_t g_lo, uint32_t g
 
 __device__ __forceinline__ double path_normal_sum(uint32_t g_lo, uint32_t g_hi, int32_t n_steps, uint32_t k0, uint32_t k1,
                                                   uint32_t tag = 0u) {
-    return path_normal_quarters(g_lo, g_hi, n_steps, 0, 4, k0, k1, tag) * kZScale;
+    return path_normal_quarters(g_lo, g_hi, n_steps, 0, 4, k0, k1, tag) * kPairZScale;
 }
 
 // ------------------------------------------------------------ reductions ----
@@ -990,7 +1005,7 @@ __global__ __launch_bounds__(kBlock) void european_path_kernel(PathRange pr, Con
             __syncthreads();
             zsum = ((quarter_sum[0][lane] + quarter_sum[1][lane]) + quarter_sum[2][lane]) + quarter_sum[3][lane];
         }
-        zsum *= kZScale;
+        zsum *= kPairZScale;
         const bool payer = !split || wave == 0;         // waves 1..3 of a split workgroup carry no path through the payoffs (wave-uniform)
         if constexpr ((MODE == kReduce || MODE == kSumOnly) && NSETS > 1) {
             constexpr int KEPT = NV / 2;                // born after the step loop, and only half of the NV sums (folded first exchange)
@@ -1740,7 +1755,7 @@ __global__ __launch_bounds__(kBlock) void cliquet_kernel(PathRange pr, CliquetCo
     for_each_path(pr, [&](int64_t, uint32_t g_lo, uint32_t g_hi) {
         double total[2] = {0.0, 0.0};
         double psum = 0.0;            // RAW normal sum of the period in flight (fp64 part)
-        float part = 0.0f;            // ... and the blocks not yet folded into it
+        float part = 0.0f;            // ... and the blocks not yet folded into it, in pair-sum units (x sqrt(2) at the fold)
         int32_t part_blocks = 0;
         int32_t until_reset = c.steps_per_period;
         const int32_t blocks = (used_steps + 3) >> 2;
@@ -1749,10 +1764,10 @@ __global__ __launch_bounds__(kBlock) void cliquet_kernel(PathRange pr, CliquetCo
                 asm volatile("; olmc_fast_trip");       // (tools/isa_mix.py: the fast path of this loop)
                 until_reset -= 4;
                 part = raw_block_sum_of_words(part, philox4x32_10_pinned(g_lo, g_hi, static_cast<uint32_t>(b), 0u, rk));
-                if (++part_blocks == kGroup) { psum += static_cast<double>(part); part = 0.0f; part_blocks = 0; }
+                if (++part_blocks == kGroup) { psum += kSqrt2 * static_cast<double>(part); part = 0.0f; part_blocks = 0; }
                 continue;
             }
-            psum += static_cast<double>(part);
+            psum += kSqrt2 * static_cast<double>(part);
             part = 0.0f;
             part_blocks = 0;
             float z[4];

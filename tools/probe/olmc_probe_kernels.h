@@ -76,7 +76,7 @@ __global__ __launch_bounds__(kBlock) void european_stamp_kernel(PathRange pr, Co
         __syncthreads();
         zsum = ((quarter_sum[0][lane] + quarter_sum[1][lane]) + quarter_sum[2][lane]) + quarter_sum[3][lane];
     }
-    zsum *= kZScale;
+    zsum *= kPairZScale;
     asm volatile("s_nop 0" ::"v"(zsum));                 // the stamp below must follow the loop's last result
     const uint64_t t_loop = __builtin_amdgcn_s_memrealtime();
     double acc[2] = {0.0, 0.0};
