@@ -431,12 +431,14 @@ int olmc_extrema_qmc(double S, double K, double T, double r, double sigma, doubl
 
 /* ---- multi-GPU, single process ------------------------------------------
  * n_paths split into n_gpus contiguous global path ranges (rank d = device d, [d N / P, (d + 1) N / P)).  Per list of devices the
- * library keeps an engine: a stream, a send / receive buffer and a LAUNCHER THREAD per rank (bound to the rank's device once, at
- * birth; parked on a futex between calls) and the list's RCCL communicators (ncclCommInitAll).  A call posts the launch to the
- * launchers -- every rank's path kernel is queued at the same time --, then the calling thread queues ONE grouped RCCL all-reduce
- * over xGMI (only after every rank has launched: a failed rank leaves no peer inside a collective; the group is closed on every
- * error path), and the reduced sums are handed to the host by rank 0's polled completion word (as olmc_fetch_dev) while the
- * launchers drain the other ranks, which hold the same sums.  Identical finalisation on every rank.  On any error
+ * library keeps an engine: per rank a context of its own for the engine's lifetime (stream, reduction workspaces, pinned landing
+ * buffer and completion word, Sobol table; outside the pool of the Threading note, so no other call ever leases it), a send /
+ * receive buffer and a LAUNCHER THREAD (bound to the rank's device once, at birth; parked on a futex between calls), and the
+ * list's RCCL communicators (ncclCommInitAll).  A rank's table upload, path kernel, collective and fetch share its context's stream.
+ * A call posts the launch to the launchers -- every rank's path kernel is queued at the same time --, then the calling thread
+ * queues ONE grouped RCCL all-reduce over xGMI (only after every rank has launched: a failed rank leaves no peer inside a
+ * collective; the group is closed on every error path), and the reduced sums are handed to the host by rank 0's polled completion
+ * word (as olmc_fetch_dev) while the launchers drain the other ranks, which hold the same sums.  Identical finalisation on every rank.  On any error
  * return the thread's device and the streams already launched on are restored / drained.  Calls on lists that share no device run
  * concurrently; lists that share a device take turns.  Payload of the all-reduce:
  *   olmc_multi_gpu_european      {sum, sumsq, n}                                   count = 3
@@ -503,8 +505,8 @@ int olmc_normals(uint64_t seed, int64_t path_offset, int64_t n_paths, int32_t n_
  * (hipExtLaunchKernelGGL): they take the kernel's own begin / end timestamps on the stream it runs on, the
  * figures rocprofv3 reports.  (hipEventRecord brackets around a launch also time the marker packets on either
  * side: +7..10 us at these durations.)  Multi-launch entry points (olmc_american_lsm, olmc_european_multi with
- * more than 65535 contracts) are bracketed as a whole.  olmc_kernel_time returns the number of launches timed
- * and their total milliseconds since the last reset. */
+ * more than 65535 contracts) are bracketed as a whole.  The ranks' launches of the multi-GPU entry points are not
+ * timed.  olmc_kernel_time returns the number of launches timed and their total milliseconds since the last reset. */
 int olmc_profile_enable(int on);
 /* Tuning knob for A/B measurements (results never change, only the launch shape):
  *   OLMC_TUNE_GRID_CAP   max workgroups per launch, 0 = default (larger jobs grid-stride)

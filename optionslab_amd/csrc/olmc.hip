@@ -224,7 +224,7 @@ struct CtxLease {
             c->busy = false;
         }
         // notify_all: the pool's one condition variable has two kinds of waiter (a lease, in ctx_lease_on; "every context idle", in
-        // pool_forget_stream / with_all_contexts) -- notify_one could hand the only wake-up to a waiter whose predicate is still false
+        // with_all_contexts) -- notify_one could hand the only wake-up to a waiter whose predicate is still false
         pool->idle.notify_all();
         c = nullptr;
     }
@@ -669,9 +669,9 @@ void launch_european(bool anti, int32_t grid, hipStream_t s, const PathRange& pr
 // Waits for the launch just made on stream s (defined with the poll below).
 int sync_or_recover(DeviceCtx* c, hipStream_t s);
 
-// ONE reducing launch on a leased context: the workspace of `grid` workgroups x nv values, whose last workgroup writes the sums to
-// d_out (and `tail` behind them when tail >= 0), an event pair when profiling is on (unless !profiled), launch(grid, s, timed, ws),
-// the launch check.  The launch that writes into the context's pinned buffer (d_out == c->d_result) BLOCKS: on OLMC_OK the sums
+// ONE reducing launch on a context the caller holds (a lease, or a multi-GPU rank's own): the workspace of `grid` workgroups x nv
+// values, whose last workgroup writes the sums to d_out (and `tail` behind them when tail >= 0), an event pair when profiling is on
+// (unless !profiled), launch(grid, s, timed, ws), the launch check.  The launch that writes into the context's pinned buffer (d_out == c->d_result) BLOCKS: on OLMC_OK the sums
 // are in c->h_result.  Any other d_out is a shard's device buffer, and its launch is left queued on `s`.
 template <typename Launch>
 int launch_reduce(DeviceCtx* c, hipStream_t s, double* d_out, double tail, int nv, int32_t grid, Launch&& launch, bool profiled = true) {
@@ -721,7 +721,7 @@ GbmStep gbm_step(double T, int32_t n_steps, double r, double q, double sigma) {
 // (padded to the kernel's NSETS) and, when tail >= 0, `tail` in d_out[2 * nsets].  Blocks when d_out is c->d_result (launch_reduce).
 int run_batch_device(DeviceCtx* c, hipStream_t s, const olmc_option* opts, int32_t k, int64_t path_offset,
                      int64_t n_local, int32_t n_steps, uint64_t seed, int antithetic, double* d_out, double tail,
-                     int* pos /* [k]: slot of contract i in d_out, may be NULL when k == 1 */, bool* sums_only = nullptr
+                     int* pos /* [k]: slot of contract i in d_out, may be NULL when k == 1 */, bool profiled, bool* sums_only = nullptr
                      /* in: the caller needs no sums of squares; out: the launch made left ONE sum per slot (d_out[slot]) */) {
     PathRange pr = make_range(path_offset, n_local, n_steps, seed);
     const bool anti = antithetic != 0;
@@ -750,7 +750,7 @@ int run_batch_device(DeviceCtx* c, hipStream_t s, const olmc_option* opts, int32
         } else {
             fused(std::integral_constant<int, 16>{});
         }
-    });
+    }, profiled);
 }
 
 // Waits for the launch just made on stream s.  If it was armed (make_ws), the host polls the flag word in pinned memory:
@@ -840,7 +840,7 @@ int run_batch(const olmc_option* opts, int32_t k, int64_t path_offset, int64_t n
     DeviceCtx* const c = lease.c;
     int pos[OLMC_MAX_BATCH];
     bool lean = prices_only;
-    rc = run_batch_device(c, c->stream, opts, k, path_offset, n_local, n_steps, seed, antithetic, c->d_result, -1.0, pos, &lean);
+    rc = run_batch_device(c, c->stream, opts, k, path_offset, n_local, n_steps, seed, antithetic, c->d_result, -1.0, pos, true, &lean);
     if (rc) return rc;
     finish_set(c->h_result, pos, n_local * (antithetic ? 2 : 1), opts, k, false, lean, out);
     return OLMC_OK;
@@ -954,34 +954,39 @@ extern "C" int olmc_european_shard_dev(double S, double K, double T, double r, d
     const olmc_option o = make_option(S, K, T, r, sigma, q, is_call);
     const double n = static_cast<double>(n_local * (antithetic ? 2 : 1));
     // the path kernel's last workgroup writes {sum, sumsq, n} straight into the caller's buffer
-    return run_batch_device(c, s, &o, 1, path_offset, n_local, n_steps, seed, antithetic, d_triple, n, nullptr);
+    return run_batch_device(c, s, &o, 1, path_offset, n_local, n_steps, seed, antithetic, d_triple, n, nullptr, true);
 }
 
-// Blocking fetch of n (<= 33) doubles that work already queued on `hip_stream` leaves at d_src (e.g. the triple after the caller's
-// RCCL all-reduce): a one-wave kernel behind that work copies them into the pinned buffer and raises the completion word, the host
-// polls it -- the same hand-over as a blocking pricing, instead of hipMemcpyAsync + hipStreamSynchronize (8 us -> 3 us per step).
-extern "C" int olmc_fetch_dev(const double* d_src, int32_t n, void* hip_stream, double* out_host) {
-    if (!d_src || !out_host) return fail(OLMC_ERR_ARG, "null pointer");
-    if (n < 1 || n > kMaxNV + 1) return fail(OLMC_ERR_ARG, "n must be in [1, 33]");
-    CtxLease lease;
-    int rc = ctx_lease(&lease);
-    if (rc) return rc;
-    DeviceCtx* const c = lease.c;
-    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+// Blocking fetch of n (<= 33) doubles that work already queued on stream s leaves at d_src (e.g. the triple after an all-reduce):
+// a one-wave kernel behind that work copies them into c's pinned buffer and raises c's completion word, the host polls it -- the
+// same hand-over as a blocking pricing, instead of hipMemcpyAsync + hipStreamSynchronize (8 us -> 3 us per step).
+namespace {
+int fetch_dev(DeviceCtx* c, const double* d_src, int32_t n, hipStream_t s, double* out_host) {
     const uint64_t want = ++c->seq;
     hipLaunchKernelGGL(publish_kernel, dim3(1), dim3(kWave), 0, s, d_src, n, c->d_result, c->d_flag, want);
     HIP_TRY(hipGetLastError());
+    int rc = OLMC_OK;
     if (g_poll >= 0) {
         c->armed = want;
         rc = wait_armed(c, s);
     } else {
-        rc = OLMC_OK;
         hipError_t e = hipStreamSynchronize(s);
         if (e != hipSuccess) rc = fail(OLMC_ERR_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
     }
     if (rc) return rc;
     for (int32_t i = 0; i < n; ++i) out_host[i] = c->h_result[i];
     return OLMC_OK;
+}
+}  // namespace
+
+// The fetch on the caller's stream (one process per GPU: the triple after the caller's RCCL all-reduce), through a leased context.
+extern "C" int olmc_fetch_dev(const double* d_src, int32_t n, void* hip_stream, double* out_host) {
+    if (!d_src || !out_host) return fail(OLMC_ERR_ARG, "null pointer");
+    if (n < 1 || n > kMaxNV + 1) return fail(OLMC_ERR_ARG, "n must be in [1, 33]");
+    CtxLease lease;
+    int rc = ctx_lease(&lease);
+    if (rc) return rc;
+    return fetch_dev(lease.c, d_src, n, static_cast<hipStream_t>(hip_stream), out_host);
 }
 
 extern "C" int olmc_european_batch(const olmc_option* opts, int32_t k, int64_t path_offset, int64_t n_local,
@@ -1694,11 +1699,12 @@ extern "C" int olmc_jump_paths(double S, double T, double r, double sigma, doubl
 
 // ======================================================================= QMC ====
 namespace {
-// The scrambled direction matrix and digital shift on the device: [dims x 30 | dims] words.  The table travels only when it
-// differs from the one already there (compared word for word: 31 KB at 252 dims, ~1 us, against two pageable uploads): the
-// 8 / 14 pricings of literal FD Greeks and every repeated pricing share one upload.  The caller holds the context's lease.
-int qmc_table(DeviceCtx* c, const uint32_t* sv, const uint32_t* shift, int32_t dims, bool* uploaded = nullptr) {
-    if (uploaded) *uploaded = false;
+// The scrambled direction matrix and digital shift on the device: [dims x 30 | dims] words, uploaded on c's own stream -- the stream
+// every launch that reads them is queued on, so no launch sees a table half travelled or one another caller put there.  The table
+// travels only when it differs from the one already there (compared word for word: 31 KB at 252 dims, ~1 us, against two pageable
+// uploads): the 8 / 14 pricings of literal FD Greeks and every repeated pricing share one upload.  The caller owns c (a lease, or
+// a multi-GPU rank's own context).
+int qmc_table(DeviceCtx* c, const uint32_t* sv, const uint32_t* shift, int32_t dims) {
     const size_t sv_words = static_cast<size_t>(dims) * kSobolBits, table_words = sv_words + dims;
     const bool same = c->sobol_host.size() == table_words && std::memcmp(c->sobol_host.data(), sv, sizeof(uint32_t) * sv_words) == 0 &&
                       std::memcmp(c->sobol_host.data() + sv_words, shift, sizeof(uint32_t) * dims) == 0;
@@ -1716,7 +1722,6 @@ int qmc_table(DeviceCtx* c, const uint32_t* sv, const uint32_t* shift, int32_t d
     HIP_TRY(hipMemcpyAsync(c->d_sobol + sv_words, shift, sizeof(uint32_t) * dims, hipMemcpyHostToDevice, c->stream));
     c->sobol_host.assign(sv, sv + sv_words);
     c->sobol_host.insert(c->sobol_host.end(), shift, shift + dims);
-    if (uploaded) *uploaded = true;
     return OLMC_OK;
 }
 
@@ -1785,31 +1790,9 @@ void launch_qmc_batch(const QmcShape& sh, int32_t grid, hipStream_t s, const Eve
     else go(european_qmc_batch_kernel<NSETS, false, false>);
 }
 
-int run_qmc(double S, double K, double T, double r, double sigma, double q, int is_call, int64_t point_offset,
-            int64_t n_paths, int32_t dims, const uint32_t* sv, const uint32_t* shift, int32_t bits,
-            olmc_stats* out, double* terminal_host, int mirror = 0, olmc_cv_moments* cv = nullptr,
-            double* d_triple = nullptr /* a shard of a multi-GPU call: {sum, sumsq, n} are LEFT here, on `shard_stream`, nothing is waited for */,
-            hipStream_t shard_stream = nullptr, bool shard_cv = false /* with d_triple: the five control-variate moments and n instead */) {
-    int rc = qmc_check(sv, shift, bits, dims, point_offset, n_paths);
-    if (rc) return rc;
-    CtxLease lease;
-    rc = ctx_lease(&lease);
-    if (rc) return rc;
-    DeviceCtx* const c = lease.c;
-    const size_t sv_words = static_cast<size_t>(dims) * kSobolBits;
-    const size_t term_bytes = terminal_host ? sizeof(double) * static_cast<size_t>(n_paths) * (mirror ? 2 : 1) : 0;
-    if (term_bytes) {
-        rc = bulk_reserve(c, term_bytes);
-        if (rc) return rc;
-    }
-    bool uploaded = false;
-    rc = qmc_table(c, sv, shift, dims, &uploaded);
-    if (rc) return rc;
-    if (d_triple && uploaded) HIP_TRY(hipStreamSynchronize(c->stream));      // the table travelled on the context's stream, the kernel runs on the rank's
-    uint32_t* d_sv = c->d_sobol;
-    uint32_t* d_shift = d_sv + sv_words;
-    double* d_term = terminal_host ? static_cast<double*>(c->d_bulk) : nullptr;
-    const GbmStep g = gbm_step(T, dims, r, q, sigma);              // gbm_qmc.py:38-44
+// gbm_qmc.py:38-44 on `dims` dates (mirror: the antithetic variant, :70).
+Contract qmc_contract(double S, double K, double T, double r, double sigma, double q, int is_call, int32_t dims, bool mirror) {
+    const GbmStep g = gbm_step(T, dims, r, q, sigma);
     Contract ct;
     ct.vol = g.vol;
     // gbm_qmc.py:44 (drift * steps) vs :70 (the antithetic variant multiplies the rate by T directly)
@@ -1819,20 +1802,39 @@ int run_qmc(double S, double K, double T, double r, double sigma, double q, int 
     ct.scale = 1.0;
     ct.neg_sign_strike = -ct.sign * K;
     ct.sign_scale = ct.sign;
-    QmcRange qr;
-    qr.first = static_cast<uint64_t>(point_offset);
-    qr.count = n_paths;
-    qr.dims = dims;
-    qr.mirror = mirror ? 1 : 0;
+    return ct;
+}
+
+// ONE reducing Sobol launch of contract ct over points [point_offset, point_offset + n_paths), queued on c's own stream behind the
+// table: {sum, sumsq} -- the five control-variate moments when `five` -- then `tail` at d_out (launch_reduce: blocks when d_out is
+// c->d_result).
+int qmc_device(DeviceCtx* c, const Contract& ct, int64_t point_offset, int64_t n_paths, int32_t dims, const uint32_t* sv,
+               const uint32_t* shift, bool five, double* d_out, double tail, bool profiled) {
+    int rc = qmc_table(c, sv, shift, dims);
+    if (rc) return rc;
+    const uint32_t* d_sv = c->d_sobol;
+    const uint32_t* d_shift = d_sv + static_cast<size_t>(dims) * kSobolBits;
+    const QmcRange qr{static_cast<uint64_t>(point_offset), n_paths, dims, 0};
     const QmcShape sh = qmc_shape(point_offset, n_paths, dims);
+    return launch_reduce(c, c->stream, d_out, tail, five ? 5 : 2, sh.grid, [&](int32_t grid, hipStream_t s, const EventPair* timed, const ReduceWs& ws) {
+        if (five) launch_qmc_european<kControlVariate>(sh, grid, s, timed, qr, ct, d_sv, d_shift, ws, nullptr);
+        else launch_qmc_european<kReduce>(sh, grid, s, timed, qr, ct, d_sv, d_shift, ws, nullptr);
+    }, profiled);
+}
+
+int run_qmc(double S, double K, double T, double r, double sigma, double q, int is_call, int64_t point_offset,
+            int64_t n_paths, int32_t dims, const uint32_t* sv, const uint32_t* shift, int32_t bits,
+            olmc_stats* out, double* terminal_host, int mirror = 0, olmc_cv_moments* cv = nullptr) {
+    int rc = qmc_check(sv, shift, bits, dims, point_offset, n_paths);
+    if (rc) return rc;
+    CtxLease lease;
+    rc = ctx_lease(&lease);
+    if (rc) return rc;
+    DeviceCtx* const c = lease.c;
+    const Contract ct = qmc_contract(S, K, T, r, sigma, q, is_call, dims, mirror != 0);
     if (!terminal_host) {
-        const bool five = cv || (d_triple && shard_cv);
-        rc = launch_reduce(c, d_triple ? shard_stream : c->stream, d_triple ? d_triple : c->d_result, d_triple ? static_cast<double>(n_paths) : -1.0,
-                           five ? 5 : 2, sh.grid, [&](int32_t grid, hipStream_t s, const EventPair* timed, const ReduceWs& ws) {
-            if (five) launch_qmc_european<kControlVariate>(sh, grid, s, timed, qr, ct, d_sv, d_shift, ws, nullptr);
-            else launch_qmc_european<kReduce>(sh, grid, s, timed, qr, ct, d_sv, d_shift, ws, nullptr);
-        });
-        if (rc || d_triple) return rc;
+        rc = qmc_device(c, ct, point_offset, n_paths, dims, sv, shift, cv != nullptr, c->d_result, -1.0, true);
+        if (rc) return rc;
         if (cv) {       // device moments are of the UNdiscounted payoff x; d = disc * x (monte_carlo.py:175)
             cv_from_device(c->h_result, n_paths, S, T, r, q, cv);
             if (poisoned(S, K, T, r, sigma, q)) cv->value = std::nan("");
@@ -1841,8 +1843,17 @@ int run_qmc(double S, double K, double T, double r, double sigma, double q, int 
         finish_one(c->h_result, n_paths, r, T, poisoned(S, K, T, r, sigma, q), out);
         return OLMC_OK;
     }
+    const size_t term_bytes = sizeof(double) * static_cast<size_t>(n_paths) * (mirror ? 2 : 1);
+    rc = bulk_reserve(c, term_bytes);
+    if (rc) return rc;
+    rc = qmc_table(c, sv, shift, dims);
+    if (rc) return rc;
+    double* d_term = static_cast<double*>(c->d_bulk);
+    const QmcShape sh = qmc_shape(point_offset, n_paths, dims);
+    const QmcRange qr{static_cast<uint64_t>(point_offset), n_paths, dims, mirror ? 1 : 0};
     // no reduction workspace is handed out: only the launch status matters
-    launch_qmc_european<kTerminal>(sh, sh.grid, c->stream, nullptr, qr, ct, d_sv, d_shift, ReduceWs{}, d_term);
+    launch_qmc_european<kTerminal>(sh, sh.grid, c->stream, nullptr, qr, ct, c->d_sobol, c->d_sobol + static_cast<size_t>(dims) * kSobolBits,
+                                   ReduceWs{}, d_term);
     HIP_TRY(hipGetLastError());
     c->armed = 0;
     return copy_to_host(c, terminal_host, d_term, term_bytes);
@@ -1987,20 +1998,44 @@ extern "C" int olmc_extrema_qmc(double S, double K, double T, double r, double s
 }
 
 namespace {
-// k contracts on the same Sobol points, ONE launch (european_qmc_batch_kernel); falls back to k launches beyond the size one
-// grid covers.  out[i] = stats of opts[i].
+// k (2 .. 16) contracts on points [point_offset, point_offset + n_paths), ONE launch (european_qmc_batch_kernel) whose grid covers
+// them all, queued on c's own stream behind the table: the 2 nsets sums then `tail` at d_out, contract i's pair at slot pos[i]
+// (launch_reduce: blocks when d_out is c->d_result).
+int qmc_batch_device(DeviceCtx* c, const olmc_option* opts, int32_t k, int64_t point_offset, int64_t n_paths, int32_t dims,
+                     const uint32_t* sv, const uint32_t* shift, double* d_out, double tail, int* pos, bool profiled) {
+    const QmcShape sh = qmc_shape(point_offset, n_paths, dims);
+    if (k < 2 || (sh.units + kBlock - 1) / kBlock > kMaxGrid)
+        return fail(OLMC_ERR_ARG, "a shard of fused Sobol contracts needs 2 .. 16 contracts and points one grid covers");
+    int rc = qmc_table(c, sv, shift, dims);
+    if (rc) return rc;
+    const uint32_t* d_sv = c->d_sobol;
+    const uint32_t* d_shift = d_sv + static_cast<size_t>(dims) * kSobolBits;
+    const QmcRange qr{static_cast<uint64_t>(point_offset), n_paths, dims, 0};
+    const int32_t grid = sh.split ? sh.grid : static_cast<int32_t>((sh.units + kBlock - 1) / kBlock);     // the grid covers every point / block
+    const int nsets = k <= 8 ? 8 : 16;
+    return launch_reduce(c, c->stream, d_out, tail, 2 * nsets, grid, [&](int32_t g, hipStream_t s, const EventPair* timed, const ReduceWs& ws) {
+        // make_contract(o, dims) IS gbm_qmc.py:38-44: dt = T / dims, drift * dims, sigma sqrt(dt)
+        if (nsets == 8) {
+            ContractSet<8> cs;
+            group_contracts<8>(opts, k, dims, &cs, pos);
+            launch_qmc_batch<8>(sh, g, s, timed, qr, cs, d_sv, d_shift, ws);
+        } else {
+            ContractSet<16> cs;
+            group_contracts<16>(opts, k, dims, &cs, pos);
+            launch_qmc_batch<16>(sh, g, s, timed, qr, cs, d_sv, d_shift, ws);
+        }
+    }, profiled);
+}
+
+// k contracts on the same Sobol points, ONE launch (qmc_batch_device); falls back to k launches beyond the size one grid covers.
+// out[i] = stats of opts[i].
 int run_qmc_batch(const olmc_option* opts, int32_t k, int64_t point_offset, int64_t n_paths, int32_t dims, const uint32_t* sv,
-                  const uint32_t* shift, int32_t bits, olmc_stats* out,
-                  double* d_sums = nullptr /* a shard of a multi-GPU call: the 2 nsets sums and n are LEFT here, on `shard_stream`, nothing is waited for */,
-                  hipStream_t shard_stream = nullptr, int* pos_out = nullptr /* with d_sums: slot of contract i */) {
-    if (!opts || (!out && !d_sums)) return fail(OLMC_ERR_ARG, "null pointer");
+                  const uint32_t* shift, int32_t bits, olmc_stats* out) {
+    if (!opts || !out) return fail(OLMC_ERR_ARG, "null pointer");
     if (k < 1 || k > OLMC_MAX_BATCH) return fail(OLMC_ERR_ARG, "batch size must be in [1, OLMC_MAX_BATCH]");
     int rc = qmc_check(sv, shift, bits, dims, point_offset, n_paths);
     if (rc) return rc;
-    const QmcShape sh = qmc_shape(point_offset, n_paths, dims);
-    const int64_t units = sh.units;
-    if (d_sums && (k < 2 || (units + kBlock - 1) / kBlock > kMaxGrid))
-        return fail(OLMC_ERR_ARG, "a shard of fused Sobol contracts needs 2 .. 16 contracts and points one grid covers");
+    const int64_t units = qmc_shape(point_offset, n_paths, dims).units;
     if (k == 1 || (units + kBlock - 1) / kBlock > kMaxGrid) {             // one contract, or more points than a grid covers: literal launches
         for (int i = 0; i < k; ++i) {
             rc = run_qmc(opts[i].S, opts[i].K, opts[i].T, opts[i].r, opts[i].sigma, opts[i].q, opts[i].is_call, point_offset, n_paths, dims, sv, shift,
@@ -2013,37 +2048,9 @@ int run_qmc_batch(const olmc_option* opts, int32_t k, int64_t point_offset, int6
     rc = ctx_lease(&lease);
     if (rc) return rc;
     DeviceCtx* const c = lease.c;
-    bool uploaded = false;
-    rc = qmc_table(c, sv, shift, dims, &uploaded);
-    if (rc) return rc;
-    if (d_sums && uploaded) HIP_TRY(hipStreamSynchronize(c->stream));        // the table travelled on the context's stream, the kernel runs on the rank's
-    hipStream_t const st = d_sums ? shard_stream : c->stream;
-    const size_t sv_words = static_cast<size_t>(dims) * kSobolBits;
-    uint32_t* d_sv = c->d_sobol;
-    uint32_t* d_shift = d_sv + sv_words;
-    QmcRange qr;
-    qr.first = static_cast<uint64_t>(point_offset);
-    qr.count = n_paths;
-    qr.dims = dims;
-    qr.mirror = 0;
-    const int32_t grid = sh.split ? sh.grid : static_cast<int32_t>((units + kBlock - 1) / kBlock);     // the grid covers every point / block
-    const int nsets = k <= 8 ? 8 : 16;
     int pos[OLMC_MAX_BATCH];
-    rc = launch_reduce(c, st, d_sums ? d_sums : c->d_result, d_sums ? static_cast<double>(n_paths) : -1.0, 2 * nsets, grid,
-                       [&](int32_t g, hipStream_t s, const EventPair* timed, const ReduceWs& ws) {
-        // make_contract(o, dims) IS gbm_qmc.py:38-44: dt = T / dims, drift * dims, sigma sqrt(dt)
-        if (nsets == 8) {
-            ContractSet<8> cs;
-            group_contracts<8>(opts, k, dims, &cs, pos);
-            launch_qmc_batch<8>(sh, g, s, timed, qr, cs, d_sv, d_shift, ws);
-        } else {
-            ContractSet<16> cs;
-            group_contracts<16>(opts, k, dims, &cs, pos);
-            launch_qmc_batch<16>(sh, g, s, timed, qr, cs, d_sv, d_shift, ws);
-        }
-    });
-    if (d_sums && pos_out) std::copy(pos, pos + k, pos_out);
-    if (rc || d_sums) return rc;
+    rc = qmc_batch_device(c, opts, k, point_offset, n_paths, dims, sv, shift, c->d_result, -1.0, pos, true);
+    if (rc) return rc;
     finish_set(c->h_result, pos, n_paths, opts, k, false, false, out);
     return OLMC_OK;
 }
@@ -2071,17 +2078,17 @@ extern "C" int olmc_european_qmc_greeks_fd(double S, double K, double T, double 
 // librccl is resolved lazily (dlopen) so single-GPU users never load it; the TYPES and ENUM VALUES come from
 // <rccl/rccl.h> at compile time, so a header / library mismatch is a build-time matter, not a guessed constant.
 //
-// One process, n ranks (rank d = device d).  An ENGINE exists per list of devices: per rank a stream, a send / receive buffer and a
-// LAUNCHER THREAD bound to the rank's device at birth (one hipSetDevice, ever -- SURVEY §8e: "one host thread per device +
-// ncclCommInitAll"), plus the list's communicators.  Never a pricing context: a shard launch leases one like any other call and uses
-// the rank's stream as a caller stream.  A call
+// One process, n ranks (rank d = device d).  An ENGINE exists per list of devices: per rank a context of its own (ctx_create: stream,
+// workspaces, Sobol table; in no pool, so nobody else ever leases it), a send / receive buffer and a LAUNCHER THREAD bound to the
+// rank's device at birth (one hipSetDevice, ever -- SURVEY §8e: "one host thread per device + ncclCommInitAll"), plus the list's
+// communicators.  A rank's table upload, path kernel, collective and fetch all run on its context's stream.  A call
 //   1. posts the launch job: every launcher queues its rank's path kernel at once (round 4 queued them one after the other from the
 //      calling thread: rank 7's kernel started seven enqueues late);
 //   2. queues ONE grouped all-reduce of `count` doubles from the calling thread (3 for a price, 2 nsets + 1 for finite-difference
 //      Greeks, 6 for the control variate: SURVEY §8e) -- only after every rank has launched, so a rank that failed leaves no peer
 //      waiting inside a collective;
 //   3. posts the drain job (launchers 1 .. n-1 wait for their streams) and meanwhile takes the reduced values home through rank 0's
-//      polled completion word (olmc_fetch_dev); every rank holds the same values.
+//      polled completion word (fetch_dev); every rank holds the same values.
 // Calls on device lists that share no device run concurrently; lists that share one queue behind that device's mutex (two
 // communicators driven at once on one device may deadlock inside RCCL).  OLMC_TUNE_MULTI_LAUNCH = -1 keeps round 4's serial form
 // (everything from the calling thread) for A/B; both forms give the same bits.
@@ -2135,7 +2142,7 @@ struct MultiEngine;
 
 struct MultiRank {
     int device = -1;
-    hipStream_t stream = nullptr;
+    DeviceCtx* ctx = nullptr;                       // the rank's own: its stream is the rank stream
     double* d_send = nullptr;                       // [kMultiValues] this rank's sums (written by its path kernel's last workgroup)
     double* d_recv = nullptr;                       // [kMultiValues] the reduced sums
     hipEvent_t queued = nullptr;                    // rehearsal only: the rank's path kernel is queued behind this
@@ -2182,36 +2189,6 @@ int engine_wait(MultiEngine* e) {
     return OLMC_OK;
 }
 
-// A rank stream is about to be destroyed: the workspace slots it claimed in the contexts of its device are handed back (a later
-// stream may get the same handle value; and a slot whose owner is gone would otherwise stay taken for good -- the host fault of round 4,
-// with every slot claimed by a dead stream, the next caller stream went down the slot-sharing path, which drained the
-// slot's "owner" with hipStreamSynchronize on a destroyed handle).
-void pool_forget_stream(int dev, hipStream_t stream) {
-    DevicePool* pool = g_pool[dev].load(std::memory_order_acquire);
-    if (!pool) return;
-    // context by context: each is taken out of circulation for the moment its slots are looked at (a wait bounded by one call's
-    // duration).  Waiting for ALL contexts to be idle at once could starve behind two busy callers that never pause together.
-    for (size_t i = 0;; ++i) {
-        DeviceCtx* c = nullptr;
-        {
-            std::unique_lock<std::mutex> lock(pool->mu);
-            if (i >= pool->all.size()) break;
-            c = pool->all[i];
-            pool->idle.wait(lock, [&] { return !c->busy; });
-            c->busy = true;
-        }
-        for (int k = 0; k < DeviceCtx::kSlots; ++k) {
-            DeviceCtx::WsSlot& sl = c->slots[k];
-            if (sl.claimed && !sl.shared && sl.owner == stream) { sl.claimed = false; sl.owner = nullptr; sl.used = false; }
-        }
-        {
-            std::lock_guard<std::mutex> lock(pool->mu);
-            c->busy = false;
-        }
-        pool->idle.notify_all();                    // lease waiters share the condition variable with this wait
-    }
-}
-
 void engine_destroy(MultiEngine* e) {
     if (std::any_of(e->ranks.begin(), e->ranks.end(), [](const MultiRank& rk) { return rk.launcher.joinable(); })) {
         engine_post(e, nullptr, 0);                 // work == nullptr: leave
@@ -2222,7 +2199,7 @@ void engine_destroy(MultiEngine* e) {
         if (cm && g_rccl.CommDestroy) g_rccl.CommDestroy(cm);
     for (MultiRank& rk : e->ranks) {
         if (rk.device < 0 || hipSetDevice(rk.device) != hipSuccess) continue;
-        if (rk.stream) { (void)hipStreamSynchronize(rk.stream); pool_forget_stream(rk.device, rk.stream); (void)hipStreamDestroy(rk.stream); }
+        if (rk.ctx) ctx_release(rk.ctx);
         if (rk.d_send) (void)hipFree(rk.d_send);
         if (rk.queued) (void)hipEventDestroy(rk.queued);
     }
@@ -2240,7 +2217,7 @@ void multi_gpu_release() {
     for (MultiEngine* e : all) engine_destroy(e);
 }
 
-// Streams, buffers, launchers and communicators for exactly this list of devices.  Called with the devices' mutexes held.
+// Contexts, buffers, launchers and communicators for exactly this list of devices.  Called with the devices' mutexes held.
 int engine_build(const std::vector<int>& devs, bool rehearsal, MultiEngine** out) {
     MultiEngine* e = new MultiEngine();
     e->rehearsal = rehearsal;
@@ -2249,11 +2226,12 @@ int engine_build(const std::vector<int>& devs, bool rehearsal, MultiEngine** out
     auto bail = [&](int rc) { engine_destroy(e); return rc; };
     for (size_t d = 0; d < devs.size(); ++d) {
         MultiRank& rk = e->ranks[d];
-        hipError_t err = hipSetDevice(devs[d]);
-        if (err == hipSuccess) { rk.device = devs[d]; err = hipStreamCreateWithFlags(&rk.stream, hipStreamNonBlocking); }
+        const int rc = ctx_create(devs[d], &rk.ctx);      // leaves devs[d] the current device
+        if (rc) return bail(fail(rc, "multi-GPU engine, rank " + std::to_string(d) + ": " + t_error));
+        rk.device = devs[d];
         constexpr int kStride = 64;                  // doubles: the receive buffer starts on its own 512-byte boundary (the collective's vector accesses)
         static_assert(kStride >= kMultiValues, "rank buffers hold the widest payload");
-        if (err == hipSuccess) err = hipMalloc(&rk.d_send, sizeof(double) * 2 * kStride);
+        hipError_t err = hipMalloc(&rk.d_send, sizeof(double) * 2 * kStride);
         if (err == hipSuccess) { rk.d_recv = rk.d_send + kStride; err = hipEventCreateWithFlags(&rk.queued, hipEventDisableTiming); }
         if (err != hipSuccess) return bail(fail(OLMC_ERR_HIP, std::string("multi-GPU engine, rank ") + std::to_string(d) + ": " + hipGetErrorString(err)));
     }
@@ -2298,7 +2276,7 @@ int engine_for(const std::vector<int>& devs, bool rehearsal, MultiEngine** out) 
             g_engines.erase(g_engines.begin() + static_cast<std::ptrdiff_t>(i));
         }
     }
-    for (MultiEngine* old : evicted) engine_destroy(old);      // joins its launchers, hands its streams' workspace slots back, destroys them
+    for (MultiEngine* old : evicted) engine_destroy(old);      // joins its launchers, frees its rank contexts
     MultiEngine* e = nullptr;
     const int rc = engine_build(devs, rehearsal, &e);      // the devices' mutexes are held: nobody else builds this list meanwhile
     if (rc) return rc;
@@ -2306,14 +2284,6 @@ int engine_for(const std::vector<int>& devs, bool rehearsal, MultiEngine** out) 
     g_engines.push_back(e);
     *out = e;
     return OLMC_OK;
-}
-
-// After a stream of a failed call could not be drained: the self-resetting counters of that device's workspaces may be dirty.
-void pool_recover(int dev) {
-    DevicePool* pool = g_pool[dev].load(std::memory_order_acquire);
-    if (!pool) return;
-    std::lock_guard<std::mutex> lock(pool->mu);
-    for (DeviceCtx* c : pool->all) ws_recover(c);
 }
 
 // Whatever way a multi-GPU call leaves (any of its error returns included), the calling thread gets back the library device and
@@ -2335,7 +2305,7 @@ struct MultiGpuScope {
         if (engine)
             for (int d : launched) {
                 const MultiRank& rk = engine->ranks[d];
-                if (hipSetDevice(rk.device) == hipSuccess && hipStreamSynchronize(rk.stream) != hipSuccess) pool_recover(rk.device);
+                if (hipSetDevice(rk.device) == hipSuccess && hipStreamSynchronize(rk.ctx->stream) != hipSuccess) ws_recover(rk.ctx);
             }
         for (auto it = locked.rbegin(); it != locked.rend(); ++it) g_multi_dev_mu[*it].unlock();
         t_device = saved_lib_device;
@@ -2351,7 +2321,7 @@ int grouped_allreduce(MultiEngine* e, int count) {
     ncclResult_t bad = ncclSuccess;
     for (size_t d = 0; d < e->ranks.size() && bad == ncclSuccess; ++d) {
         const MultiRank& rk = e->ranks[d];
-        bad = g_rccl.AllReduce(rk.d_send, rk.d_recv, static_cast<size_t>(count), ncclFloat64, ncclSum, e->comms[d], rk.stream);
+        bad = g_rccl.AllReduce(rk.d_send, rk.d_recv, static_cast<size_t>(count), ncclFloat64, ncclSum, e->comms[d], rk.ctx->stream);
     }
     const ncclResult_t end = g_rccl.GroupEnd();
     if (bad != ncclSuccess) return fail(OLMC_ERR_RCCL, rccl_message("ncclAllReduce", bad));
@@ -2378,21 +2348,22 @@ int rehearsal_allreduce(MultiEngine* e, int count) {
     RankBuffers in{};
     for (int d = 0; d < n; ++d) {
         in.send[d] = e->ranks[d].d_send;
-        HIP_TRY(hipEventRecord(e->ranks[d].queued, e->ranks[d].stream));
+        HIP_TRY(hipEventRecord(e->ranks[d].queued, e->ranks[d].ctx->stream));
     }
     for (int d = 0; d < n; ++d) {
         for (int o = 0; o < n; ++o)
-            if (o != d) HIP_TRY(hipStreamWaitEvent(e->ranks[d].stream, e->ranks[o].queued, 0));
-        hipLaunchKernelGGL(rehearsal_allreduce_kernel, dim3(1), dim3(kWave), 0, e->ranks[d].stream, in, n, count, e->ranks[d].d_recv);
+            if (o != d) HIP_TRY(hipStreamWaitEvent(e->ranks[d].ctx->stream, e->ranks[o].queued, 0));
+        hipLaunchKernelGGL(rehearsal_allreduce_kernel, dim3(1), dim3(kWave), 0, e->ranks[d].ctx->stream, in, n, count, e->ranks[d].d_recv);
         HIP_TRY(hipGetLastError());
     }
     return OLMC_OK;
 }
 #endif
 
-// The skeleton every multi-GPU entry point shares.  launch(rank, lo, n_local, stream, d_send) queues rank's path kernel on ITS
-// stream (the thread it runs on has the rank's device as its library device) and must leave `count` doubles at d_send; host
-// receives their sums.  `launch` runs on the launcher threads, one rank each, at the same time: it must not write shared state.
+// The skeleton every multi-GPU entry point shares.  launch(rank, lo, n_local, c, d_send) queues rank's path kernel on the stream of
+// the rank's own context c, unprofiled (no olmc_kernel_time drains c's events: c is in no pool), and must leave `count` doubles at
+// d_send; host receives their sums.  `launch` runs on the launcher threads, one rank each, at the same time: it must not write
+// shared state.
 template <typename Launch>
 int multi_gpu_run(int n_gpus, int64_t n_paths, int32_t n_steps, int count, Launch launch, double* host, bool sobol_points = false) {
     if (n_gpus < 1 || n_gpus > kMaxDevices) return fail(OLMC_ERR_ARG, "n_gpus out of range");
@@ -2432,7 +2403,7 @@ int multi_gpu_run(int n_gpus, int64_t n_paths, int32_t n_steps, int count, Launc
 #ifdef OLMC_WITH_PROBES
         if (g_fault_shard == d + 1) return fail(OLMC_ERR_HIP, "injected shard failure (OLMC_PROBE_TUNE_FAULT_SHARD)");
 #endif
-        return launch(d, lo, n_local, rk.stream, rk.d_send);
+        return launch(d, lo, n_local, rk.ctx, rk.d_send);
     };
     if (threaded) {
         for (int d = 0; d < n_gpus; ++d) scope.launched.push_back(d);       // any of them may have queued work by the time one fails
@@ -2473,10 +2444,10 @@ int multi_gpu_run(int n_gpus, int64_t n_paths, int32_t n_steps, int count, Launc
     }
     const auto t2 = clock::now();
     // 3. The sums come home the way every blocking pricing's result does: a one-wave kernel behind the all-reduce on rank 0 writes
-    // them into a pinned buffer and raises the completion word the host polls (olmc_fetch_dev); the other ranks hold the same sums
+    // them into a pinned buffer and raises the completion word the host polls (fetch_dev); the other ranks hold the same sums
     // and finish with the same collective -- their launchers wait for their streams meanwhile.
     const std::function<int(int)> drain_rank = [&](int d) -> int {
-        const hipError_t err = hipStreamSynchronize(eng->ranks[d].stream);
+        const hipError_t err = hipStreamSynchronize(eng->ranks[d].ctx->stream);
         return err == hipSuccess ? OLMC_OK : fail(OLMC_ERR_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(err));
     };
     const MultiRank& first = eng->ranks[0];
@@ -2484,7 +2455,7 @@ int multi_gpu_run(int n_gpus, int64_t n_paths, int32_t n_steps, int count, Launc
     t_device = first.device;
     // from the post to the wait below NOTHING may return: the job refers to this frame
     if (threaded) engine_post(eng, &drain_rank, 0);     // rank 0's launcher too: every launcher ends the call awake, and spins for the next
-    rc = olmc_fetch_dev(first.d_recv, count, first.stream, host);
+    rc = fetch_dev(first.ctx, first.d_recv, count, first.ctx->stream, host);
     const auto t3 = clock::now();
     if (threaded) {
         const int rc_drain = engine_wait(eng);          // always: the job refers to this frame
@@ -2512,32 +2483,17 @@ int multi_gpu_run(int n_gpus, int64_t n_paths, int32_t n_steps, int count, Launc
     return OLMC_OK;
 }
 
-// k contracts on this rank's block of the common normals, queued on the rank's stream: {sum, sumsq} x nsets then n at d_out.
-int batch_shard_dev(const olmc_option* opts, int32_t k, int64_t path_offset, int64_t n_local, int32_t n_steps, uint64_t seed, int antithetic,
-                    double* d_out, hipStream_t s, int* pos) {
-    CtxLease lease;
-    int rc = ctx_lease(&lease);
-    if (rc) return rc;
-    const double n = static_cast<double>(n_local * (antithetic ? 2 : 1));
-    return run_batch_device(lease.c, s, opts, k, path_offset, n_local, n_steps, seed, antithetic, d_out, n, pos);
-}
-
-// The five control-variate moments of this rank's block (of the UNdiscounted payoff) then n at d_out.
-int cv_shard_dev(const olmc_option& o, int64_t path_offset, int64_t n_local, int32_t n_steps, uint64_t seed, int antithetic, double* d_out, hipStream_t s) {
-    CtxLease lease;
-    int rc = ctx_lease(&lease);
-    if (rc) return rc;
-    return cv_device(lease.c, s, o, path_offset, n_local, n_steps, seed, antithetic, d_out, static_cast<double>(n_local * (antithetic ? 2 : 1)), false);
-}
 }  // namespace
 
 extern "C" int olmc_multi_gpu_european(double S, double K, double T, double r, double sigma, double q, int is_call,
                                        int64_t n_paths, int32_t n_steps, uint64_t seed, int antithetic, int n_gpus,
                                        olmc_stats* out) {
     if (!out) return fail(OLMC_ERR_ARG, "null pointer");
+    const olmc_option o = make_option(S, K, T, r, sigma, q, is_call);
     double host[3] = {0, 0, 0};
-    const int rc = multi_gpu_run(n_gpus, n_paths, n_steps, 3, [&](int, int64_t lo, int64_t n_local, hipStream_t s, double* d_send) {
-        return olmc_european_shard_dev(S, K, T, r, sigma, q, is_call, lo, n_local, n_steps, seed, antithetic, d_send, s);
+    const int rc = multi_gpu_run(n_gpus, n_paths, n_steps, 3, [&](int, int64_t lo, int64_t n_local, DeviceCtx* c, double* d_send) {
+        const double n = static_cast<double>(n_local * (antithetic ? 2 : 1));      // {sum, sumsq, n}
+        return run_batch_device(c, c->stream, &o, 1, lo, n_local, n_steps, seed, antithetic, d_send, n, nullptr, false);
     }, host);
     if (rc) return rc;
     finish_one(host, static_cast<int64_t>(host[2]), r, T, poisoned(S, K, T, r, sigma, q), out);
@@ -2553,9 +2509,10 @@ extern "C" int olmc_multi_gpu_greeks_fd(double S, double K, double T, double r, 
     const int nsets = gs.k <= 8 ? 8 : 16;
     int pos[OLMC_MAX_BATCH] = {};
     double host[kMultiValues] = {};
-    const int rc = multi_gpu_run(n_gpus, n_paths, n_steps, 2 * nsets + 1, [&](int rank, int64_t lo, int64_t n_local, hipStream_t s, double* d_send) {
+    const int rc = multi_gpu_run(n_gpus, n_paths, n_steps, 2 * nsets + 1, [&](int rank, int64_t lo, int64_t n_local, DeviceCtx* c, double* d_send) {
         int other[OLMC_MAX_BATCH];                                                               // every rank lays the set out alike: rank 0's
-        return batch_shard_dev(gs.o, gs.k, lo, n_local, n_steps, seed, 1, d_send, s, rank == 0 ? pos : other);      // layout is the one kept
+        return run_batch_device(c, c->stream, gs.o, gs.k, lo, n_local, n_steps, seed, 1, d_send, static_cast<double>(2 * n_local),
+                                rank == 0 ? pos : other, false);                                 // layout is the one kept
     }, host);
     if (rc) return rc;
     olmc_stats st[OLMC_MAX_BATCH];
@@ -2570,8 +2527,8 @@ extern "C" int olmc_multi_gpu_european_cv(double S, double K, double T, double r
     if (!out) return fail(OLMC_ERR_ARG, "null pointer");
     const olmc_option o = make_option(S, K, T, r, sigma, q, is_call);
     double host[6] = {};
-    const int rc = multi_gpu_run(n_gpus, n_paths, n_steps, 6, [&](int, int64_t lo, int64_t n_local, hipStream_t s, double* d_send) {
-        return cv_shard_dev(o, lo, n_local, n_steps, seed, antithetic, d_send, s);
+    const int rc = multi_gpu_run(n_gpus, n_paths, n_steps, 6, [&](int, int64_t lo, int64_t n_local, DeviceCtx* c, double* d_send) {
+        return cv_device(c, c->stream, o, lo, n_local, n_steps, seed, antithetic, d_send, static_cast<double>(n_local * (antithetic ? 2 : 1)), false);
     }, host);
     if (rc) return rc;
     cv_from_device(host, static_cast<int64_t>(host[5]), S, T, r, q, out);       // d = disc * x (monte_carlo.py:175)
@@ -2589,9 +2546,10 @@ extern "C" int olmc_multi_gpu_european_qmc(double S, double K, double T, double 
     if (!out) return fail(OLMC_ERR_ARG, "null pointer");
     int rc = qmc_check(sv, shift, bits, dims, 0, n_paths);
     if (rc) return rc;
+    const Contract ct = qmc_contract(S, K, T, r, sigma, q, is_call, dims, false);
     double host[3] = {0, 0, 0};
-    rc = multi_gpu_run(n_gpus, n_paths, dims, 3, [&](int, int64_t lo, int64_t n_local, hipStream_t s, double* d_send) {
-        return run_qmc(S, K, T, r, sigma, q, is_call, lo, n_local, dims, sv, shift, bits, nullptr, nullptr, 0, nullptr, d_send, s);
+    rc = multi_gpu_run(n_gpus, n_paths, dims, 3, [&](int, int64_t lo, int64_t n_local, DeviceCtx* c, double* d_send) {
+        return qmc_device(c, ct, lo, n_local, dims, sv, shift, false, d_send, static_cast<double>(n_local), false);
     }, host, true);
     if (rc) return rc;
     finish_one(host, static_cast<int64_t>(host[2]), r, T, poisoned(S, K, T, r, sigma, q), out);
@@ -2612,9 +2570,9 @@ extern "C" int olmc_multi_gpu_european_qmc_greeks_fd(double S, double K, double 
     const int nsets = gs.k <= 8 ? 8 : 16;
     int pos[OLMC_MAX_BATCH] = {};
     double host[kMultiValues] = {};
-    rc = multi_gpu_run(n_gpus, n_paths, dims, 2 * nsets + 1, [&](int rank, int64_t lo, int64_t n_local, hipStream_t s, double* d_send) {
+    rc = multi_gpu_run(n_gpus, n_paths, dims, 2 * nsets + 1, [&](int rank, int64_t lo, int64_t n_local, DeviceCtx* c, double* d_send) {
         int other[OLMC_MAX_BATCH];                                                               // every rank lays the set out alike: rank 0's
-        return run_qmc_batch(gs.o, gs.k, lo, n_local, dims, sv, shift, bits, nullptr, d_send, s, rank == 0 ? pos : other);      // layout is the one kept
+        return qmc_batch_device(c, gs.o, gs.k, lo, n_local, dims, sv, shift, d_send, static_cast<double>(n_local), rank == 0 ? pos : other, false);
     }, host, true);
     if (rc) return rc;
     olmc_stats st[OLMC_MAX_BATCH];
@@ -2631,9 +2589,10 @@ extern "C" int olmc_multi_gpu_european_qmc_cv(double S, double K, double T, doub
     if (!out) return fail(OLMC_ERR_ARG, "null pointer");
     int rc = qmc_check(sv, shift, bits, dims, 0, n_paths);
     if (rc) return rc;
+    const Contract ct = qmc_contract(S, K, T, r, sigma, q, is_call, dims, false);
     double host[6] = {};
-    rc = multi_gpu_run(n_gpus, n_paths, dims, 6, [&](int, int64_t lo, int64_t n_local, hipStream_t s, double* d_send) {
-        return run_qmc(S, K, T, r, sigma, q, is_call, lo, n_local, dims, sv, shift, bits, nullptr, nullptr, 0, nullptr, d_send, s, true);
+    rc = multi_gpu_run(n_gpus, n_paths, dims, 6, [&](int, int64_t lo, int64_t n_local, DeviceCtx* c, double* d_send) {
+        return qmc_device(c, ct, lo, n_local, dims, sv, shift, true, d_send, static_cast<double>(n_local), false);
     }, host, true);
     if (rc) return rc;
     cv_from_device(host, static_cast<int64_t>(host[5]), S, T, r, q, out);

@@ -8,6 +8,7 @@ binding bound to that library, so `probe.hip.european(...)` runs the same code `
   * the exp2, inverse-normal and normal-moment taps.
 """
 import math
+import threading
 
 import numpy as np
 import pytest
@@ -50,7 +51,7 @@ def test_n_rank_price_equals_the_rank_ordered_sum_of_its_shards(rehearsal, n_ran
     """olmc_multi_gpu_european with n ranks (each its own stream and buffers on this one device, the all-reduce emulated by a
     rank-ordered sum behind every rank's kernel): the triple must be EXACTLY what olmc_combine_stats makes of the n shard triples
     priced one by one -- same partition [d N / P, (d + 1) N / P), same paths, same association -- and the call itself checks that
-    ranks 1..n-1 ended with rank 0's bits.  11 ranks share the 8 workspace slots a context has for caller streams."""
+    ranks 1..n-1 ended with rank 0's bits.  11 ranks: more ranks than a pool context has workspace slots for caller streams."""
     S, K, T, r, v = ATM
     N, M, seed = 1_000_003, 40, 9
     got = hip.multi_gpu_european(S, K, T, r, v, 0.0, True, N, M, seed, True, n_ranks)
@@ -225,10 +226,11 @@ def test_engines_come_and_go_without_touching_dead_streams(rehearsal):
     rebuilt whenever the rank count changed, which DESTROYED the old rank streams while the workspace slots they had claimed in the
     device's contexts still named them as owners; once all eight slots of a context belonged to dead streams, the next rank stream
     went down the slot-sharing path, which drained the slot's owner with hipStreamSynchronize(dead handle) -- a use-after-free inside
-    the HIP runtime, not an error code.  Fixed in b0df7f4: slots are handed back before a rank stream dies (pool_forget_stream), and a
-    shared slot's previous owner is drained with hipDeviceSynchronize, never through its handle.  This test walks that road on
-    purpose: more rank counts than the engine cache keeps (engines are evicted and their streams destroyed), more ranks than a
-    context has slots, twice over; every price must stay the one-device price."""
+    the HIP runtime, not an error code.  Fixed in b0df7f4: slots were handed back before a rank stream died, and a shared slot's
+    previous owner is drained with hipDeviceSynchronize, never through its handle.  Today every rank owns a context of its own,
+    whose stream is the rank stream, so rank streams claim no slots in pool contexts at all.  This test still walks that road: more
+    rank counts than the engine cache keeps (engines are evicted and their rank contexts freed), more ranks than a context has
+    slots, twice over; every price must stay the one-device price."""
     S, K, T, r, v = ATM
     N, M, seed = 200_003, 12, 3
     whole = hip.european(S, K, T, r, v, 0.0, True, N, M, seed, True)
@@ -239,6 +241,57 @@ def test_engines_come_and_go_without_touching_dead_streams(rehearsal):
             g, _ = hip.multi_gpu_greeks_fd(S, K, T, r, v, 0.0, True, N, M, seed, bool(n_ranks & 1), n_ranks, want_evals=False)
             assert g[0] == pytest.approx(whole.price, rel=1e-12)
     assert hip.device_info()["device"] == 0
+
+
+def test_single_device_sobol_pricing_on_another_thread_leaves_a_multi_gpu_sobol_call_alone(rehearsal):
+    """when a rank leased a pool context for its launch only, its Sobol kernel, still queued on the rank stream,
+    read that context's table after the lease came back; a single-device caller on another thread could lease the same context and
+    overwrite the table meanwhile.  Every rank now owns its context.  Table B has other dimensions than table A, so an upload of B
+    into a context that held A reallocates the table.  A background thread prices on B while the main thread makes multi-GPU Sobol
+    calls on A with 4 ranks: every result must keep its bits."""
+    S, K, T, r, v = ATM
+    n_a, n_b = 1 << 20, 1 << 16
+    sv_a, sh_a = ol.monte_carlo.sobol_tables(252, 42, n_a)
+    sv_b, sh_b = ol.monte_carlo.sobol_tables(64, 7, n_b)
+    one_q = hip.european_qmc(S, K, T, r, v, 0.0, True, n_a, sv_a, sh_a)
+    one_g, _ = hip.european_qmc_greeks_fd(S, K, T, r, v, 0.01, True, n_a, sv_a, sh_a, False, want_evals=False)
+    one_c = hip.european_qmc_cv(S, K, T, r, v, 0.01, False, n_a, sv_a, sh_a)
+    b = hip.european_qmc(S, K, T, r, v, 0.0, True, n_b, sv_b, sh_b)
+    stop, seen, errors = threading.Event(), [], []
+
+    def background():
+        try:
+            for _ in range(50_000):
+                if stop.is_set():
+                    break
+                st = hip.european_qmc(S, K, T, r, v, 0.0, True, n_b, sv_b, sh_b)
+                seen.append((st.sum, st.sumsq, st.n))
+        except Exception as exc:            # reported by the main thread
+            errors.append(exc)
+
+    th = threading.Thread(target=background, daemon=True)
+    th.start()
+    runs = []
+    try:
+        for _ in range(10):
+            q = hip.multi_gpu_european_qmc(S, K, T, r, v, 0.0, True, n_a, sv_a, sh_a, 4)
+            g, _ = hip.multi_gpu_european_qmc_greeks_fd(S, K, T, r, v, 0.01, True, n_a, sv_a, sh_a, False, 4, want_evals=False)
+            c = hip.multi_gpu_european_qmc_cv(S, K, T, r, v, 0.01, False, n_a, sv_a, sh_a, 4)
+            runs.append(((q.sum, q.sumsq, q.n), tuple(g), (c.sum_d, c.sum_s, c.sum_dd, c.sum_ss, c.sum_ds, c.n)))
+    finally:
+        stop.set()
+        th.join(timeout=60)
+    assert not th.is_alive() and not errors, errors
+    assert seen and all(x == (b.sum, b.sumsq, b.n) for x in seen)
+    assert all(run == runs[0] for run in runs)
+    (q_sum, q_sumsq, q_n), g, (c_d, c_s, c_dd, c_ss, c_ds, c_n) = runs[0]
+    assert q_n == one_q.n and q_sum == pytest.approx(one_q.sum, rel=1e-13) and q_sumsq == pytest.approx(one_q.sumsq, rel=1e-13)
+    assert g[0] == pytest.approx(one_g[0], rel=1e-13)
+    for a, x in zip(one_g[1:], g[1:]):
+        assert x == pytest.approx(a, rel=1e-7, abs=1e-7)
+    assert c_n == one_c.n
+    for f, x in zip(("sum_d", "sum_s", "sum_dd", "sum_ss", "sum_ds"), (c_d, c_s, c_dd, c_ss, c_ds)):
+        assert x == pytest.approx(getattr(one_c, f), rel=1e-13), f
 
 
 def test_a_failing_rank_in_the_middle_leaves_the_thread_and_the_library_usable(rehearsal):
