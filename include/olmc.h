@@ -58,7 +58,8 @@ extern "C" {
                               *    entry points launch their ranks from one launcher thread per device; the grid reduction's consumer side is an
                               *    agent-scope acquire again (numbers unchanged) 
                               * 6: additions only -- olmc_multi_gpu_european_qmc_greeks_fd, olmc_multi_gpu_european_qmc_cv; OLMC_TUNE_QMC_BLOCK takes 2;
-                              *    later additions within v6: olmc_asian_qmc, olmc_extrema_qmc (Sobol paths for the path payoffs) */
+                              *    later additions within v6: olmc_asian_qmc, olmc_extrema_qmc (Sobol paths for the path payoffs),
+                              *    olmc_asian_qmc_greeks_fd, olmc_extrema_qmc_greeks_fd (their finite-difference Greeks in one launch) */
 
 enum {
     OLMC_OK = 0,
@@ -428,6 +429,19 @@ int olmc_asian_qmc(double S, double K, double T, double r, double sigma, double 
 int olmc_extrema_qmc(double S, double K, double T, double r, double sigma, double q, int is_call, int payoff, double barrier,
                      int construction, int64_t point_offset, int64_t n_points, int32_t n_steps, const uint32_t* sv,
                      const uint32_t* shift, int32_t bits, int antithetic, olmc_stats* out);
+/* Finite-difference Greeks of those payoffs on Sobol points [0, n_points): the 8 / 14 bumped contracts of olmc_european_greeks_fd
+ * (out9 and evals[14] or NULL mean what they mean there, in the reference's call order) priced on the SAME points in ONE launch.
+ * evals[i] is what olmc_asian_qmc / olmc_extrema_qmc return for contract i alone up to the association of the sums (barrier /
+ * lookback payoffs are those bits per point).  `barrier` is one level for every contract (the caller applies its t = 0 rule at the
+ * mid spot).  Refused (OLMC_ERR_ARG, before any device work): T <= 0, avg_kind other than OLMC_AVG_ARITHMETIC / _GEOMETRIC, a bad
+ * payoff or a barrier kind with barrier <= 0, a bad construction, the bridge beyond OLMC_QMC_BRIDGE_MAX_STEPS dates, bits != 30,
+ * n_points outside [1, 2^30], n_steps outside [1, 21201]. */
+int olmc_asian_qmc_greeks_fd(double S, double K, double T, double r, double sigma, double q, int is_call, int avg_kind,
+                             int construction, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift,
+                             int32_t bits, int antithetic, int second_order, double* out9, olmc_stats* evals /* [14] or NULL */);
+int olmc_extrema_qmc_greeks_fd(double S, double K, double T, double r, double sigma, double q, int is_call, int payoff, double barrier,
+                               int construction, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift,
+                               int32_t bits, int antithetic, int second_order, double* out9, olmc_stats* evals /* [14] or NULL */);
 
 /* ---- multi-GPU, single process ------------------------------------------
  * n_paths split into n_gpus contiguous global path ranges (rank d = device d, [d N / P, (d + 1) N / P)).  Per list of devices the

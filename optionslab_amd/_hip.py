@@ -79,6 +79,9 @@ PROTOTYPES = {
     "olmc_asian": (_I, _SIX + [_I, _I, _I64, _I64, _I32, _U64T, _I, C.POINTER(Stats)]),
     "olmc_asian_qmc": (_I, _SIX + [_I, _I, _I, _I64, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, _I, C.POINTER(Stats)]),
     "olmc_extrema_qmc": (_I, _SIX + [_I, _I, _D, _I, _I64, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, _I, C.POINTER(Stats)]),
+    "olmc_asian_qmc_greeks_fd": (_I, _SIX + [_I, _I, _I, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, _I, _I, C.POINTER(_D), C.POINTER(Stats)]),
+    "olmc_extrema_qmc_greeks_fd": (_I, _SIX + [_I, _I, _D, _I, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, _I, _I, C.POINTER(_D),
+                                              C.POINTER(Stats)]),
     "olmc_asian_greeks_fd": (_I, _SIX + [_I, _I, _I64, _I32, _U64T, _I, _I, C.POINTER(_D), C.POINTER(Stats)]),
     "olmc_extrema_greeks_fd": (_I, _SIX + [_I, _I, _D, _I64, _I32, _U64T, _I, _I, C.POINTER(_D), C.POINTER(Stats)]),
     "olmc_barrier": (_I, _SIX + [_I, _D, _I, _I64, _I64, _I32, _U64T, _I, C.POINTER(Stats)]),
@@ -483,6 +486,30 @@ def extrema_qmc(S, K, T, r, sigma, q, is_call: bool, payoff: int, level: float, 
                                   int(point_offset), int(n_points), int(sv.shape[0]), psv, psh, int(sv.shape[1]), int(antithetic),
                                   C.byref(out)))
     return out
+
+
+def asian_qmc_greeks_fd(S, K, T, r, sigma, q, is_call: bool, geometric: bool, n_points: int, sv: np.ndarray, shift: np.ndarray, bridge: bool,
+                        antithetic: bool, second_order: bool, want_evals: bool = True) -> Tuple[List[float], List[Stats]]:
+    """As asian_greeks_fd on the Sobol points of asian_qmc: the 8 / 14 bumped contracts in ONE launch (olmc_asian_qmc_greeks_fd)."""
+    sv, psv, shift, psh = _sobol_args(sv, shift, 0, n_points)
+    out9 = (C.c_double * 9)()
+    evals = (Stats * 14)() if want_evals else None
+    _check(lib().olmc_asian_qmc_greeks_fd(S, K, T, r, sigma, q, int(is_call), AVG_GEOMETRIC if geometric else AVG_ARITHMETIC,
+                                          QMC_BRIDGE if bridge else QMC_SEQUENTIAL, int(n_points), int(sv.shape[0]), psv, psh, int(sv.shape[1]),
+                                          int(antithetic), int(second_order), out9, evals))
+    return list(out9), (list(evals) if want_evals else [])
+
+
+def extrema_qmc_greeks_fd(S, K, T, r, sigma, q, is_call: bool, payoff: int, level: float, n_points: int, sv: np.ndarray, shift: np.ndarray,
+                          bridge: bool, antithetic: bool, second_order: bool, want_evals: bool = True) -> Tuple[List[float], List[Stats]]:
+    """As extrema_greeks_fd on the Sobol points of extrema_qmc: ONE launch (olmc_extrema_qmc_greeks_fd); `level` is every contract's."""
+    sv, psv, shift, psh = _sobol_args(sv, shift, 0, n_points)
+    out9 = (C.c_double * 9)()
+    evals = (Stats * 14)() if want_evals else None
+    _check(lib().olmc_extrema_qmc_greeks_fd(S, K, T, r, sigma, q, int(is_call), int(payoff), float(level), QMC_BRIDGE if bridge else QMC_SEQUENTIAL,
+                                            int(n_points), int(sv.shape[0]), psv, psh, int(sv.shape[1]), int(antithetic), int(second_order),
+                                            out9, evals))
+    return list(out9), (list(evals) if want_evals else [])
 
 
 def extrema_greeks_fd(S, K, T, r, sigma, q, is_call: bool, payoff: int, barrier: float, n_paths: int, n_steps: int, seed: int, antithetic: bool,

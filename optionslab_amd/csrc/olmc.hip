@@ -1932,50 +1932,119 @@ void launch_qmc_path(bool bridge, bool anti, int32_t grid, hipStream_t s, const 
     });
 }
 
+// The same for the fused Greeks kernel (8 or 16 contract slots).
+template <int FAMILY>
+void launch_qmc_path_greeks(bool bridge, bool anti, int nsets, int32_t grid, hipStream_t s, const EventPair* timed, const QmcRange& qr,
+                            const ExtremaGreeksSet& es, double inv_steps, const uint32_t* d_sv, const uint32_t* d_shift, const QmcBridgePlan& plan,
+                            const ReduceWs& ws) {
+    with_bool(bridge, [&](auto b) {
+        with_set_anti(nsets, anti, [&](auto width, auto a) {
+            launch_timed(qmc_path_greeks_kernel<FAMILY, b, a, width>, dim3(grid), dim3(kBlock), s, timed, qr, es, inv_steps, d_sv, d_shift, plan, ws);
+        });
+    });
+}
+
 // Workgroups of a QMC path launch: four points in flight per workgroup, grid-striding beyond kQmcPathMaxGrid.
 constexpr int64_t kQmcPathMaxGrid = 8192;
+
+// The argument checks of a Sobol path call, before any context is leased.
+int qmc_path_check(int construction, int64_t point_offset, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift, int32_t bits) {
+    if (construction != OLMC_QMC_SEQUENTIAL && construction != OLMC_QMC_BRIDGE) return fail(OLMC_ERR_ARG, "bad construction");
+    if (construction == OLMC_QMC_BRIDGE && n_steps > OLMC_QMC_BRIDGE_MAX_STEPS)
+        return fail(OLMC_ERR_ARG, "the Brownian-bridge construction takes at most OLMC_QMC_BRIDGE_MAX_STEPS (1024) dates");
+    static_assert(OLMC_QMC_BRIDGE_MAX_STEPS == kQmcBridgeMaxSteps, "the header's cap is the kernel's LDS size");
+    return qmc_check(sv, shift, bits, n_steps, point_offset, n_points);
+}
+
+// A Sobol path launch on a context the caller holds: the tables (and the bridge plan) on its device, the points, the grid.
+struct QmcPathLaunch {
+    const uint32_t* d_sv;
+    const uint32_t* d_shift;
+    QmcBridgePlan plan;
+    QmcRange qr;
+    int32_t grid;
+    bool bridge, anti;
+    double inv_steps;
+};
+int qmc_path_setup(DeviceCtx* c, int construction, int64_t point_offset, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift,
+                   int antithetic, QmcPathLaunch* pl) {
+    int rc = qmc_table(c, sv, shift, n_steps);
+    if (rc) return rc;
+    pl->d_sv = c->d_sobol;
+    pl->d_shift = pl->d_sv + static_cast<size_t>(n_steps) * kSobolBits;
+    pl->plan = QmcBridgePlan{nullptr, nullptr};
+    pl->bridge = construction == OLMC_QMC_BRIDGE;
+    if (pl->bridge) {
+        rc = qmc_bridge_plan(c, n_steps, &pl->plan);
+        if (rc) return rc;
+    }
+    pl->qr.first = static_cast<uint64_t>(point_offset);
+    pl->qr.count = n_points;
+    pl->qr.dims = n_steps;
+    pl->qr.mirror = antithetic ? 1 : 0;
+    pl->grid = static_cast<int32_t>(std::min<int64_t>((n_points + kWavesPerBlock - 1) / kWavesPerBlock, kQmcPathMaxGrid));
+    pl->anti = antithetic != 0;
+    pl->inv_steps = 1.0 / n_steps;
+    return OLMC_OK;
+}
 
 // family: kQmcAsianArithmetic / kQmcAsianGeometric (payoff ignored) or kQmcExtrema (payoff = kBarrier* / kLookback*, `barrier` its level).
 int run_qmc_path(int family, int payoff, double S, double K, double T, double r, double sigma, double q, int is_call, double barrier,
                  int construction, int64_t point_offset, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift,
                  int32_t bits, int antithetic, olmc_stats* out) {
     if (!out) return fail(OLMC_ERR_ARG, "null pointer");
-    if (construction != OLMC_QMC_SEQUENTIAL && construction != OLMC_QMC_BRIDGE) return fail(OLMC_ERR_ARG, "bad construction");
-    if (construction == OLMC_QMC_BRIDGE && n_steps > OLMC_QMC_BRIDGE_MAX_STEPS)
-        return fail(OLMC_ERR_ARG, "the Brownian-bridge construction takes at most OLMC_QMC_BRIDGE_MAX_STEPS (1024) dates");
-    static_assert(OLMC_QMC_BRIDGE_MAX_STEPS == kQmcBridgeMaxSteps, "the header's cap is the kernel's LDS size");
-    int rc = qmc_check(sv, shift, bits, n_steps, point_offset, n_points);
+    int rc = qmc_path_check(construction, point_offset, n_points, n_steps, sv, shift, bits);
     if (rc) return rc;
     CtxLease lease;
     rc = ctx_lease(&lease);
     if (rc) return rc;
     DeviceCtx* const c = lease.c;
-    rc = qmc_table(c, sv, shift, n_steps);
+    QmcPathLaunch pl;
+    rc = qmc_path_setup(c, construction, point_offset, n_points, n_steps, sv, shift, antithetic, &pl);
     if (rc) return rc;
-    const uint32_t* d_sv = c->d_sobol;
-    const uint32_t* d_shift = d_sv + static_cast<size_t>(n_steps) * kSobolBits;
-    QmcBridgePlan plan{nullptr, nullptr};
-    const bool bridge = construction == OLMC_QMC_BRIDGE;
-    if (bridge) {
-        rc = qmc_bridge_plan(c, n_steps, &plan);
-        if (rc) return rc;
-    }
     const ExtremaContract ec = make_extrema(S, K, T, r, sigma, q, is_call, family == kQmcExtrema ? payoff : 0, barrier, n_steps);
-    QmcRange qr;
-    qr.first = static_cast<uint64_t>(point_offset);
-    qr.count = n_points;
-    qr.dims = n_steps;
-    qr.mirror = antithetic ? 1 : 0;
-    const int32_t grid = static_cast<int32_t>(std::min<int64_t>((n_points + kWavesPerBlock - 1) / kWavesPerBlock, kQmcPathMaxGrid));
-    const bool anti = antithetic != 0;
-    const double inv_steps = 1.0 / n_steps;
-    rc = launch_reduce(c, c->stream, c->d_result, -1.0, 2, grid, [&](int32_t g, hipStream_t s, const EventPair* timed, const ReduceWs& ws) {
-        if (family == kQmcAsianArithmetic) launch_qmc_path<kQmcAsianArithmetic>(bridge, anti, g, s, timed, qr, ec, inv_steps, d_sv, d_shift, plan, ws);
-        else if (family == kQmcAsianGeometric) launch_qmc_path<kQmcAsianGeometric>(bridge, anti, g, s, timed, qr, ec, inv_steps, d_sv, d_shift, plan, ws);
-        else launch_qmc_path<kQmcExtrema>(bridge, anti, g, s, timed, qr, ec, inv_steps, d_sv, d_shift, plan, ws);
+    rc = launch_reduce(c, c->stream, c->d_result, -1.0, 2, pl.grid, [&](int32_t g, hipStream_t s, const EventPair* timed, const ReduceWs& ws) {
+        if (family == kQmcAsianArithmetic) launch_qmc_path<kQmcAsianArithmetic>(pl.bridge, pl.anti, g, s, timed, pl.qr, ec, pl.inv_steps, pl.d_sv, pl.d_shift, pl.plan, ws);
+        else if (family == kQmcAsianGeometric) launch_qmc_path<kQmcAsianGeometric>(pl.bridge, pl.anti, g, s, timed, pl.qr, ec, pl.inv_steps, pl.d_sv, pl.d_shift, pl.plan, ws);
+        else launch_qmc_path<kQmcExtrema>(pl.bridge, pl.anti, g, s, timed, pl.qr, ec, pl.inv_steps, pl.d_sv, pl.d_shift, pl.plan, ws);
     });
     if (rc) return rc;
-    finish_one(c->h_result, n_points * (anti ? 2 : 1), r, T, poisoned(S, K, T, r, sigma, q) || std::isnan(barrier), out);
+    finish_one(c->h_result, n_points * (pl.anti ? 2 : 1), r, T, poisoned(S, K, T, r, sigma, q) || std::isnan(barrier), out);
+    return OLMC_OK;
+}
+
+// The 8 / 14 contracts of compute_greeks_unified over a Sobol-path option (ExoticAdapter, method="qmc") on points [0, n_points), ONE
+// launch of qmc_path_greeks_kernel.  Every family is grouped by extrema_greeks_layout in the Sobol normal's unit (1); the Asian
+// families have no level (payoff 0, barrier 0: log_barrier_rel 0, unread).
+int run_qmc_path_greeks(int family, int payoff, double S, double K, double T, double r, double sigma, double q, int is_call, double barrier,
+                        int construction, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift, int32_t bits,
+                        int antithetic, int second_order, double* out9, olmc_stats* evals) {
+    if (!out9) return fail(OLMC_ERR_ARG, "null pointer");
+    if (!(T > 0.0)) return fail(OLMC_ERR_ARG, "T must be > 0");
+    int rc = qmc_path_check(construction, 0, n_points, n_steps, sv, shift, bits);
+    if (rc) return rc;
+    const GreeksSet gs(S, K, T, r, sigma, q, is_call, second_order);
+    ExtremaGreeksSet es;
+    if (const char* bad = extrema_greeks_layout(gs, n_steps, payoff, barrier, K, is_call, &es, 1.0)) return fail(OLMC_ERR_STATE, bad);
+    CtxLease lease;
+    rc = ctx_lease(&lease);
+    if (rc) return rc;
+    DeviceCtx* const c = lease.c;
+    QmcPathLaunch pl;
+    rc = qmc_path_setup(c, construction, 0, n_points, n_steps, sv, shift, antithetic, &pl);
+    if (rc) return rc;
+    const int nsets = gs.nsets();
+    rc = launch_reduce(c, c->stream, c->d_result, -1.0, 2 * nsets, pl.grid, [&](int32_t g, hipStream_t s, const EventPair* timed, const ReduceWs& ws) {
+        if (family == kQmcAsianArithmetic)
+            launch_qmc_path_greeks<kQmcAsianArithmetic>(pl.bridge, pl.anti, nsets, g, s, timed, pl.qr, es, pl.inv_steps, pl.d_sv, pl.d_shift, pl.plan, ws);
+        else if (family == kQmcAsianGeometric)
+            launch_qmc_path_greeks<kQmcAsianGeometric>(pl.bridge, pl.anti, nsets, g, s, timed, pl.qr, es, pl.inv_steps, pl.d_sv, pl.d_shift, pl.plan, ws);
+        else launch_qmc_path_greeks<kQmcExtrema>(pl.bridge, pl.anti, nsets, g, s, timed, pl.qr, es, pl.inv_steps, pl.d_sv, pl.d_shift, pl.plan, ws);
+    });
+    if (rc) return rc;
+    olmc_stats st[OLMC_MAX_BATCH];
+    finish_set(c->h_result, nullptr, n_points * (pl.anti ? 2 : 1), gs.o, gs.k, false, false, st);
+    gs.finish(st, T, out9, evals);
     return OLMC_OK;
 }
 }  // namespace
@@ -1995,6 +2064,24 @@ extern "C" int olmc_extrema_qmc(double S, double K, double T, double r, double s
     if (payoff <= OLMC_BARRIER_DOWN_IN && !(barrier > 0.0)) return fail(OLMC_ERR_ARG, "Barrier must be positive");
     return run_qmc_path(kQmcExtrema, payoff, S, K, T, r, sigma, q, is_call, payoff <= OLMC_BARRIER_DOWN_IN ? barrier : 0.0, construction,
                         point_offset, n_points, n_steps, sv, shift, bits, antithetic, out);
+}
+
+extern "C" int olmc_asian_qmc_greeks_fd(double S, double K, double T, double r, double sigma, double q, int is_call, int avg_kind,
+                                        int construction, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift,
+                                        int32_t bits, int antithetic, int second_order, double* out9, olmc_stats* evals) {
+    if (avg_kind != OLMC_AVG_ARITHMETIC && avg_kind != OLMC_AVG_GEOMETRIC)
+        return fail(OLMC_ERR_ARG, "bad avg_kind (arithmetic or geometric: the fp32-exponent form has no Sobol path)");
+    return run_qmc_path_greeks(avg_kind == OLMC_AVG_GEOMETRIC ? kQmcAsianGeometric : kQmcAsianArithmetic, 0, S, K, T, r, sigma, q, is_call, 0.0,
+                               construction, n_points, n_steps, sv, shift, bits, antithetic, second_order, out9, evals);
+}
+
+extern "C" int olmc_extrema_qmc_greeks_fd(double S, double K, double T, double r, double sigma, double q, int is_call, int payoff, double barrier,
+                                          int construction, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift,
+                                          int32_t bits, int antithetic, int second_order, double* out9, olmc_stats* evals) {
+    if (payoff < OLMC_BARRIER_UP_OUT || payoff > OLMC_LOOKBACK_FIXED) return fail(OLMC_ERR_ARG, "bad payoff");
+    if (payoff <= OLMC_BARRIER_DOWN_IN && !(barrier > 0.0)) return fail(OLMC_ERR_ARG, "Barrier must be positive");
+    return run_qmc_path_greeks(kQmcExtrema, payoff, S, K, T, r, sigma, q, is_call, payoff <= OLMC_BARRIER_DOWN_IN ? barrier : 0.0, construction,
+                               n_points, n_steps, sv, shift, bits, antithetic, second_order, out9, evals);
 }
 
 namespace {

@@ -333,16 +333,18 @@ inline void contract_layout(const olmc_option* opts, int32_t k, int32_t n_steps,
 
 // ---------------------------------------------------- fused exotic Greeks sets ----
 // Barrier / lookback: a contract enters the step loop only through (drift, vol) per step (exotic_options.py:54-56): the 8 / 14
-// contracts of a GreeksSet are at most kAsianGroups recursions.  Returns nullptr, or what is wrong.
+// contracts of a GreeksSet are at most kAsianGroups recursions.  Returns nullptr, or what is wrong.  `z_scale` = the unit of the
+// normals the kernel reads: kZScale for raw Philox normals (extrema_kernel's product), 1 for Sobol normals (qmc_path_greeks_kernel,
+// which groups the Asian payoffs on Sobol paths this way too: it forms their exponent units on the device, as qmc_path_kernel does).
 inline const char* extrema_greeks_layout(const GreeksSet& gs, int32_t n_steps, int payoff, double barrier, double K, int is_call,
-                                         ExtremaGreeksSet* es) {
+                                         ExtremaGreeksSet* es, double z_scale = kZScale) {
     std::memset(es, 0, sizeof *es);
     const bool is_barrier = payoff <= kBarrierDownIn;
     int n_groups = 0;
     for (int i = 0; i < gs.k; ++i) {
         const olmc_option& o = gs.o[i];
         const double dt = o.T / n_steps;                             // exotic_options.py:54-56, as run_extrema
-        const double drift = (o.r - o.q - 0.5 * o.sigma * o.sigma) * dt, vol = o.sigma * std::sqrt(dt) * kZScale;
+        const double drift = (o.r - o.q - 0.5 * o.sigma * o.sigma) * dt, vol = o.sigma * std::sqrt(dt) * z_scale;
         int g = 0;
         while (g < n_groups && !(same_bits(es->drift[g], drift) && same_bits(es->vol[g], vol))) ++g;
         if (g == n_groups) {
@@ -353,7 +355,7 @@ inline const char* extrema_greeks_layout(const GreeksSet& gs, int32_t n_steps, i
         }
         es->group[i] = g;
         es->s0[i] = o.S;
-        es->log_barrier_rel[i] = is_barrier ? std::log(barrier / o.S) : 0.0;
+        es->log_barrier_rel[i] = is_barrier && barrier > 0.0 ? std::log(barrier / o.S) : 0.0;     // no level (0): as make_extrema
     }
     for (int g = n_groups; g < kAsianGroups; ++g) { es->drift[g] = es->drift[0]; es->vol[g] = es->vol[0]; }
     es->strike = K;

@@ -530,46 +530,51 @@ __device__ __forceinline__ double dbl_of(uint32_t lo, uint32_t hi) {
     return __longlong_as_double(static_cast<long long>((static_cast<uint64_t>(hi) << 32) | lo));
 }
 
-// a' + b' after swapping the upper (OFF = 32: lanes 32..63; OFF = 16: rows 1 and 3) part of a with the lower part of b:
-// lanes with bit OFF clear get a(own) + a(partner), lanes with it set get b(partner) + b(own).
-template <int OFF>
+// The combining operation of a transpose-reduce: a sum here, a running max / min for the Sobol path Greeks (MaxOp / MinOp).
+struct SumOp {
+    __device__ __forceinline__ double operator()(double a, double b) const { return a + b; }
+};
+
+// a' op b' after swapping the upper (OFF = 32: lanes 32..63; OFF = 16: rows 1 and 3) part of a with the lower part of b:
+// lanes with bit OFF clear get a(own) op a(partner), lanes with it set get b(partner) op b(own).
+template <int OFF, typename Op = SumOp>
 __device__ __forceinline__ double swap_add(double a, double b) {
     static_assert(OFF == 32 || OFF == 16, "permlane swaps exist for half-waves and rows");
     if constexpr (OFF == 32) {
         const auto lo = __builtin_amdgcn_permlane32_swap(dbl_lo(a), dbl_lo(b), false, false);
         const auto hi = __builtin_amdgcn_permlane32_swap(dbl_hi(a), dbl_hi(b), false, false);
-        return dbl_of(lo[0], hi[0]) + dbl_of(lo[1], hi[1]);
+        return Op()(dbl_of(lo[0], hi[0]), dbl_of(lo[1], hi[1]));
     } else {
         const auto lo = __builtin_amdgcn_permlane16_swap(dbl_lo(a), dbl_lo(b), false, false);
         const auto hi = __builtin_amdgcn_permlane16_swap(dbl_hi(a), dbl_hi(b), false, false);
-        return dbl_of(lo[0], hi[0]) + dbl_of(lo[1], hi[1]);
+        return Op()(dbl_of(lo[0], hi[0]), dbl_of(lo[1], hi[1]));
     }
 }
 
-template <int P, int OFF = kWave / 2>
+template <int P, int OFF = kWave / 2, typename Op = SumOp>
 __device__ __forceinline__ void wave_transpose_reduce(double (&v)[P]) {
     if constexpr (P > 1) {
         constexpr int H = P / 2;
         double kept[H];
         if constexpr (OFF >= 16) {
 #pragma unroll
-            for (int k = 0; k < H; ++k) kept[k] = swap_add<OFF>(v[k], v[k + H]);
+            for (int k = 0; k < H; ++k) kept[k] = swap_add<OFF, Op>(v[k], v[k + H]);
         } else {
             const bool upper = (threadIdx.x & OFF) != 0;
 #pragma unroll
             for (int k = 0; k < H; ++k) {
                 const double send = upper ? v[k] : v[k + H];
                 const double mine = upper ? v[k + H] : v[k];
-                kept[k] = mine + __shfl_xor(send, OFF, kWave);
+                kept[k] = Op()(mine, __shfl_xor(send, OFF, kWave));
             }
         }
-        wave_transpose_reduce<H, OFF / 2>(kept);
+        wave_transpose_reduce<H, OFF / 2, Op>(kept);
         v[0] = kept[0];
     } else if constexpr (OFF >= 1) {
         double one[1];
-        if constexpr (OFF >= 16) one[0] = swap_add<OFF>(v[0], v[0]);        // own + partner in every lane
-        else one[0] = v[0] + __shfl_xor(v[0], OFF, kWave);
-        wave_transpose_reduce<1, OFF / 2>(one);
+        if constexpr (OFF >= 16) one[0] = swap_add<OFF, Op>(v[0], v[0]);        // own op partner in every lane
+        else one[0] = Op()(v[0], __shfl_xor(v[0], OFF, kWave));
+        wave_transpose_reduce<1, OFF / 2, Op>(one);
         v[0] = one[0];
     }
 }
@@ -1520,6 +1525,12 @@ __device__ __forceinline__ double min_f64(double a, double b) {
     asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
     return r;
 }
+struct MaxOp {
+    __device__ __forceinline__ double operator()(double a, double b) const { return max_f64(a, b); }
+};
+struct MinOp {
+    __device__ __forceinline__ double operator()(double a, double b) const { return min_f64(a, b); }
+};
 
 template <bool ANTI>
 __global__ __launch_bounds__(kBlock) void extrema_kernel(PathRange pr, ExtremaContract c, ReduceWs ws) {
@@ -3091,13 +3102,82 @@ __device__ __forceinline__ void qmc_leg_add(QmcLeg& g, double y /* ln(S_j/S), lo
     else { g.mx = max_f64(g.mx, y); g.mn = min_f64(g.mn, y); }
 }
 
-// The payoff of one leg, in every lane (butterflies); y_n = ln(S_n / S) in natural units.
+// The payoff of one path given its leg totals: a = the sum over the dates (Asian), mx / mn = the extrema (barrier / lookback), y_n =
+// ln(S_n / S) in natural units.
+template <int FAMILY>
+__device__ __forceinline__ double qmc_payoff(const ExtremaContract& c, double inv_steps, double a, double mx, double mn, double y_n) {
+    if constexpr (FAMILY == kQmcExtrema) return extrema_payoff(c, y_n, mx, mn);
+    const double avg = FAMILY == kQmcAsianArithmetic ? c.s0 * (a * inv_steps) : c.s0 * exp(a * inv_steps);
+    return fmax(c.sign * (avg - c.strike), 0.0);
+}
+
+// The payoff of one leg, in every lane (butterflies).
 template <int FAMILY>
 __device__ __forceinline__ double qmc_leg_payoff(const ExtremaContract& c, double inv_steps, const QmcLeg& g, double y_n) {
-    if constexpr (FAMILY == kQmcExtrema) return extrema_payoff(c, y_n, wave_allmax(g.mx), wave_allmin(g.mn));
-    const double s = wave_allsum(g.a);
-    const double avg = FAMILY == kQmcAsianArithmetic ? c.s0 * (s * inv_steps) : c.s0 * exp(s * inv_steps);
-    return fmax(c.sign * (avg - c.strike), 0.0);
+    if constexpr (FAMILY == kQmcExtrema) return qmc_payoff<FAMILY>(c, inv_steps, 0.0, wave_allmax(g.mx), wave_allmin(g.mn), y_n);
+    return qmc_payoff<FAMILY>(c, inv_steps, wave_allsum(g.a), 0.0, 0.0, y_n);
+}
+
+// W_1 .. W_n of point `gray` into the wave's LDS row W (W_0 = 0): trip 0 = levels 0 .. 5 in turn, every later trip one level (node k
+// reads only nodes of earlier levels).  One Gray fold and one inverse normal per dimension.
+__device__ __forceinline__ void qmc_bridge_fill(const uint32_t* __restrict__ sv, const uint32_t* __restrict__ shift, const QmcBridgePlan& plan,
+                                                double* W, int32_t n, int lane, uint32_t gray) {
+    wave_lds_sync();                                         // the previous point's reads are done
+    for (int32_t c0 = 0; c0 < n; c0 += kWave) {
+        const int32_t node = c0 + lane;
+        const bool live = node < n;
+        const double z = qmc_normal(sv, shift, live ? node : n - 1, gray);
+        uint32_t ab = 0u;
+        double ca = 0.0, cb = 0.0, sd = 0.0;
+        if (live && node > 0) {
+            ab = plan.ab[node];
+            ca = plan.coef[node]; cb = plan.coef[n + node]; sd = plan.coef[2 * n + node];
+        }
+        const int32_t a = static_cast<int32_t>(ab & 0xffffu), b = static_cast<int32_t>(ab >> 16), m = (a + b) >> 1;
+        if (c0 == 0) {
+            if (lane == 0) { W[0] = 0.0; W[n] = sqrt(static_cast<double>(n)) * z; }
+            wave_lds_sync();
+#pragma unroll 1
+            for (int lvl = 0; lvl < 6 && (1 << lvl) < n; ++lvl) {
+                if (live && node >= (1 << lvl) && node < (2 << lvl)) W[m] = __builtin_fma(ca, W[a], __builtin_fma(cb, W[b], sd * z));
+                wave_lds_sync();
+            }
+        } else {
+            if (live) W[m] = __builtin_fma(ca, W[a], __builtin_fma(cb, W[b], sd * z));
+            wave_lds_sync();
+        }
+    }
+}
+
+// One point's dates, expanded once: body(j, W_j) for every date j = 1 .. n in the lane that owns it (lane l of trip c0 takes j = c0 +
+// l + 1).  Bridge: the fill above, then a walk over the LDS row; sequential: W_j as an inclusive scan of the normals over the lanes,
+// carried from trip to trip.  Returns W_n (wave-uniform).  W: the wave's LDS row (bridge only).
+template <bool BRIDGE, typename Body>
+__device__ __forceinline__ double qmc_point_walk(const uint32_t* __restrict__ sv, const uint32_t* __restrict__ shift, const QmcBridgePlan& plan,
+                                                 double* W, int32_t n, int lane, uint32_t gray, Body body) {
+    if constexpr (BRIDGE) {
+        qmc_bridge_fill(sv, shift, plan, W, n, lane, gray);
+        for (int32_t c0 = 0; c0 < n; c0 += kWave) {
+            const int32_t j = c0 + lane + 1;
+            if (j <= n) body(j, W[j]);
+        }
+        return W[n];
+    } else {
+        double carry = 0.0;
+        for (int32_t c0 = 0; c0 < n; c0 += kWave) {
+            const int32_t t = c0 + lane;
+            double s = t < n ? qmc_normal(sv, shift, t, gray) : 0.0;
+#pragma unroll
+            for (int off = 1; off < kWave; off <<= 1) {          // inclusive scan over the lanes
+                const double o = __shfl_up(s, off, kWave);
+                if (lane >= off) s += o;
+            }
+            const double wj = carry + s;
+            carry += __shfl(s, kWave - 1, kWave);
+            if (t < n) body(t + 1, wj);
+        }
+        return carry;
+    }
 }
 
 template <int FAMILY, bool BRIDGE, bool ANTI>
@@ -3120,64 +3200,11 @@ __global__ __launch_bounds__(kBlock) void qmc_path_kernel(QmcRange qr, ExtremaCo
         const uint64_t k = qr.first + static_cast<uint64_t>(i);
         const uint32_t gray = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(k ^ (k >> 1))));
         QmcLeg up, dn;
-        double w_n;
-        if constexpr (BRIDGE) {
-            // fill W: trip 0 = levels 0 .. 5 in turn, every later trip one level (node k reads only nodes of earlier levels)
-            wave_lds_sync();                                         // the previous point's reads are done
-            for (int32_t c0 = 0; c0 < n; c0 += kWave) {
-                const int32_t node = c0 + lane;
-                const bool live = node < n;
-                const double z = qmc_normal(sv, shift, live ? node : n - 1, gray);
-                uint32_t ab = 0u;
-                double ca = 0.0, cb = 0.0, sd = 0.0;
-                if (live && node > 0) {
-                    ab = plan.ab[node];
-                    ca = plan.coef[node]; cb = plan.coef[n + node]; sd = plan.coef[2 * n + node];
-                }
-                const int32_t a = static_cast<int32_t>(ab & 0xffffu), b = static_cast<int32_t>(ab >> 16), m = (a + b) >> 1;
-                if (c0 == 0) {
-                    if (lane == 0) { W[0] = 0.0; W[n] = sqrt(static_cast<double>(n)) * z; }
-                    wave_lds_sync();
-#pragma unroll 1
-                    for (int lvl = 0; lvl < 6 && (1 << lvl) < n; ++lvl) {
-                        if (live && node >= (1 << lvl) && node < (2 << lvl)) W[m] = __builtin_fma(ca, W[a], __builtin_fma(cb, W[b], sd * z));
-                        wave_lds_sync();
-                    }
-                } else {
-                    if (live) W[m] = __builtin_fma(ca, W[a], __builtin_fma(cb, W[b], sd * z));
-                    wave_lds_sync();
-                }
-            }
-            // walk the dates: lane l of trip c0 takes date j = c0 + l + 1
-            for (int32_t c0 = 0; c0 < n; c0 += kWave) {
-                const int32_t j = c0 + lane + 1;
-                if (j <= n) {
-                    const double wj = W[j], jd = static_cast<double>(j) * drift;
-                    qmc_leg_add<FAMILY>(up, __builtin_fma(vol, wj, jd));
-                    if constexpr (ANTI) qmc_leg_add<FAMILY>(dn, __builtin_fma(-vol, wj, jd));
-                }
-            }
-            w_n = W[n];
-        } else {
-            double carry = 0.0;
-            for (int32_t c0 = 0; c0 < n; c0 += kWave) {
-                const int32_t t = c0 + lane;
-                double s = t < n ? qmc_normal(sv, shift, t, gray) : 0.0;
-#pragma unroll
-                for (int off = 1; off < kWave; off <<= 1) {          // inclusive scan over the lanes
-                    const double o = __shfl_up(s, off, kWave);
-                    if (lane >= off) s += o;
-                }
-                const double wj = carry + s;
-                carry += __shfl(s, kWave - 1, kWave);
-                if (t < n) {
-                    const double jd = static_cast<double>(t + 1) * drift;
-                    qmc_leg_add<FAMILY>(up, __builtin_fma(vol, wj, jd));
-                    if constexpr (ANTI) qmc_leg_add<FAMILY>(dn, __builtin_fma(-vol, wj, jd));
-                }
-            }
-            w_n = carry;
-        }
+        const double w_n = qmc_point_walk<BRIDGE>(sv, shift, plan, W, n, lane, gray, [&](int32_t j, double wj) {
+            const double jd = static_cast<double>(j) * drift;
+            qmc_leg_add<FAMILY>(up, __builtin_fma(vol, wj, jd));
+            if constexpr (ANTI) qmc_leg_add<FAMILY>(dn, __builtin_fma(-vol, wj, jd));
+        });
         const double nd = static_cast<double>(n) * c.drift;
         const double xu = qmc_leg_payoff<FAMILY>(c, inv_steps, up, __builtin_fma(c.vol, w_n, nd));
         if (lane == 0) { acc[0] += xu; acc[1] += xu * xu; }
@@ -3187,6 +3214,117 @@ __global__ __launch_bounds__(kBlock) void qmc_path_kernel(QmcRange qr, ExtremaCo
         }
     }
     block_then_grid_reduce<2>(acc, ws);
+}
+
+// Finite-difference Greeks on Sobol paths in ONE launch: the 8 / 14 contracts of compute_greeks_unified over an Asian, barrier or
+// lookback option (ExoticAdapter, method="qmc").  As in extrema_greeks_kernel a contract enters the date loop only through its drift and
+// vol per step, so the set is at most kAsianGroups = 6 recursions ({mid, S+-}, sigma+, sigma-, T-, r+, r-; extrema_greeks_layout with
+// the Sobol normal's unit 1), and W_j of either construction depends on the point alone.  So a wave expands its point ONCE
+// (qmc_point_walk: one Gray fold and one inverse normal per dimension, one bridge fill) and runs the six recursions on every W_j: y =
+// fma(vol_g, W_j, j drift_g) per leg, qmc_path_kernel's arithmetic for that contract (drift and vol times the same kUnit, the same
+// exp2_f64 / max_f64 / min_f64).  No rider: the r bumps are recursions of their own, so every evaluation is its own launch's up to
+// the association of sums.
+// Per point, the 6 x LEGS leg totals (Asian: a sum each; extrema: a max and a min each) meet in ONE transpose-reduce per operation
+// (12 values: 15 exchanges where butterflies take 72) that leaves recursion g, leg l in lanes (l G + g) << SHIFT; lane s < NSETS
+// then reads its contract's recursion and evaluates contract s (its spot, barrier and y_n): the payoffs run lane-parallel.  The
+// extrema are exact whatever the order, so barrier / lookback payoffs are bitwise those of qmc_path_kernel; an Asian sum is
+// associated from lane ^ 32 down where wave_allsum goes from lane ^ 1 up (a rounding of the average).  Lane s keeps contract s's
+// {sum, sumsq} over the wave's points (the points of qmc_path_kernel's wave: same grid), staged per wave and added in wave order,
+// then grid_reduce_workgroup<2 NSETS> (index order: equal arguments, equal bits).
+// Resources (tools/kernel_meta.sh, gfx950; no scratch, no spills): VGPRs arithmetic Asian 79 / 77 (sequential / bridge), 93 / 91
+// antithetic; geometric 75 / 70, 70 / 66; extrema 92 / 84, 116 / 104.  LDS 2.5 KB (8 slots) / 3.0 KB (16), + 32.8 KB with the bridge.
+template <int FAMILY, bool BRIDGE, bool ANTI, int NSETS>
+__global__ __launch_bounds__(kBlock) void qmc_path_greeks_kernel(QmcRange qr, ExtremaGreeksSet gs, double inv_steps, const uint32_t* __restrict__ sv,
+                                                                 const uint32_t* __restrict__ shift, QmcBridgePlan plan, ReduceWs ws) {
+    constexpr double kLog2e = 1.4426950408889634;
+    constexpr double kUnit = FAMILY == kQmcAsianArithmetic ? kLog2e : 1.0;
+    constexpr int G = kAsianGroups, LEGS = ANTI ? 2 : 1, NV = 2 * NSETS;
+    constexpr int P = pow2_ceil(LEGS * G), SHIFT = 6 - log2_of(P);      // leg totals per point, padded; lanes that share one after the reduce
+    static_assert(NSETS <= kWave, "one lane per contract");
+    const int lane = static_cast<int>(threadIdx.x) & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) / kWave);
+    const int32_t n = qr.dims;
+    double drift[G], vol[G];                                  // in the exponent's units, as qmc_path_kernel forms them
+#pragma unroll
+    for (int g = 0; g < G; ++g) { drift[g] = gs.drift[g] * kUnit; vol[g] = gs.vol[g] * kUnit; }
+    // lane s evaluates contract s (lanes >= NSETS repeat contract 0 and keep nothing): its slot and recursion, fixed for the launch
+    const int s = lane < NSETS ? lane : 0;
+    int32_t grp = gs.group[0];
+#pragma unroll
+    for (int k = 1; k < NSETS; ++k) {
+        const int32_t gk = gs.group[k];
+        grp = s == k ? gk : grp;
+    }
+    ExtremaContract c;
+    c.s0 = pick_recursion(s, gs.s0);
+    c.log_barrier_rel = pick_recursion(s, gs.log_barrier_rel);
+    c.drift = pick_recursion(grp, gs.drift);                  // natural units: y_n
+    c.vol = pick_recursion(grp, gs.vol);
+    c.strike = gs.strike;
+    c.sign = gs.sign;
+    c.payoff = gs.payoff;
+    c.pad = 0;
+    const int src_up = grp << SHIFT, src_dn = (G + grp) << SHIFT;
+    double acc[2] = {0.0, 0.0};
+    [[maybe_unused]] double* W = nullptr;
+    if constexpr (BRIDGE) {
+        __shared__ double w_lds[kWavesPerBlock][kQmcBridgeMaxSteps + 1];
+        W = w_lds[wave];
+    }
+    const int64_t stride = static_cast<int64_t>(gridDim.x) * kWavesPerBlock;
+    for (int64_t i = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave; i < qr.count; i += stride) {
+        const uint64_t k = qr.first + static_cast<uint64_t>(i);
+        const uint32_t gray = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(k ^ (k >> 1))));
+        QmcLeg leg[LEGS][G];
+        const double w_n = qmc_point_walk<BRIDGE>(sv, shift, plan, W, n, lane, gray, [&](int32_t j, double wj) {
+            const double jj = static_cast<double>(j);
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                const double jd = jj * drift[g];
+                qmc_leg_add<FAMILY>(leg[0][g], __builtin_fma(vol[g], wj, jd));
+                if constexpr (ANTI) qmc_leg_add<FAMILY>(leg[1][g], __builtin_fma(-vol[g], wj, jd));
+            }
+        });
+        // the leg totals, value l G + g = recursion g of leg l
+        double a_up = 0.0, a_dn = 0.0, mx_up = 0.0, mx_dn = 0.0, mn_up = 0.0, mn_dn = 0.0;
+        if constexpr (FAMILY == kQmcExtrema) {
+            double vmx[P], vmn[P];
+#pragma unroll
+            for (int v = 0; v < P; ++v) {
+                vmx[v] = v < LEGS * G ? leg[v / G][v % G].mx : 0.0;
+                vmn[v] = v < LEGS * G ? leg[v / G][v % G].mn : 0.0;
+            }
+            wave_transpose_reduce<P, kWave / 2, MaxOp>(vmx);
+            wave_transpose_reduce<P, kWave / 2, MinOp>(vmn);
+            mx_up = __shfl(vmx[0], src_up, kWave);
+            mn_up = __shfl(vmn[0], src_up, kWave);
+            if constexpr (ANTI) { mx_dn = __shfl(vmx[0], src_dn, kWave); mn_dn = __shfl(vmn[0], src_dn, kWave); }
+        } else {
+            double va[P];
+#pragma unroll
+            for (int v = 0; v < P; ++v) va[v] = v < LEGS * G ? leg[v / G][v % G].a : 0.0;
+            wave_transpose_reduce<P>(va);
+            a_up = __shfl(va[0], src_up, kWave);
+            if constexpr (ANTI) a_dn = __shfl(va[0], src_dn, kWave);
+        }
+        const double nd = static_cast<double>(n) * c.drift;
+        const double xu = qmc_payoff<FAMILY>(c, inv_steps, a_up, mx_up, mn_up, __builtin_fma(c.vol, w_n, nd));
+        acc[0] += xu; acc[1] += xu * xu;
+        if constexpr (ANTI) {
+            const double xd = qmc_payoff<FAMILY>(c, inv_steps, a_dn, mx_dn, mn_dn, __builtin_fma(-c.vol, w_n, nd));
+            acc[0] += xd; acc[1] += xd * xd;
+        }
+    }
+    __shared__ double stage[kWavesPerBlock][NV];
+    if (lane < NSETS) { stage[wave][2 * lane] = acc[0]; stage[wave][2 * lane + 1] = acc[1]; }
+    __syncthreads();
+    double row = 0.0;
+    if (threadIdx.x < NV) {
+        row = stage[0][threadIdx.x];
+#pragma unroll
+        for (int w = 1; w < kWavesPerBlock; ++w) row += stage[w][threadIdx.x];
+    }
+    grid_reduce_workgroup<NV>(row, ws);
 }
 
 // ------------------------------------------------------- validation taps ----

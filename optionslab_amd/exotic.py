@@ -21,6 +21,12 @@ from . import _hip
 from .black_scholes import _ncdf
 
 
+def _qmc_precision(method: str, precision: str) -> None:
+    """The Sobol path kernels price in fp64 only (AsianOption.price, and its fused Greeks)."""
+    if method == "qmc" and precision != "fp64":
+        raise ValueError("method='qmc' prices in fp64 only")
+
+
 def _qmc_tables(method: str, path_construction: str, n_paths: int, n_steps: int, seed: Optional[int]):
     """(sv, shift, bridge) for method="qmc", None for "pseudo"; every refusal is a ValueError raised before the device is touched."""
     if method not in ("pseudo", "qmc"):
@@ -75,8 +81,7 @@ class AsianOption:
             raise ValueError("n_paths and n_steps must be >= 1")
         if precision not in ("fp64", "fp32"):
             raise ValueError("precision must be 'fp64' or 'fp32'")
-        if method == "qmc" and precision != "fp64":
-            raise ValueError("method='qmc' prices in fp64 only")
+        _qmc_precision(method, precision)
         qmc = _qmc_tables(method, path_construction, n_paths, n_steps, self.seed)
         if qmc is not None:
             sv, shift, bridge = qmc

@@ -4,8 +4,9 @@ option_type, q=0.0, **kw)`` -- the reference's ``compute_greeks_unified``
 parameter tuple, the same OrderedDict and the same GreeksError wrapping.
 
 For the device pricer the 8 / 14 evaluations are fused into one launch
-(olmc_european_greeks_fd); ``fused=False`` forces the literal one-launch-per-
-evaluation form, which gives the same numbers.
+(olmc_european_greeks_fd), and so are those of a seeded Asian, barrier or lookback
+option through ExoticAdapter, on Philox or Sobol paths; ``fused=False`` forces the
+literal one-launch-per-evaluation form, which gives the same numbers.
 """
 from __future__ import annotations
 
@@ -47,27 +48,34 @@ class ExoticAdapter:
 
     # -- additive: the 8 / 14 evaluations of compute_greeks_unified in ONE launch where the device has a fused kernel for the payoff --
     #    the Asian (arithmetic at the reference's precision, or geometric), barrier and lookback options (the payoffs streamlit_app/pages/
-    #    7_Exotic_Options.py:266-284 asks Greeks of) -- and the option has a fixed seed (an unseeded one draws fresh normals per
-    #    evaluation, as the reference's does: nothing to share).  Same bumps, same formulas, same normals as the 8 / 14 price() calls.
+    #    7_Exotic_Options.py:266-284 asks Greeks of), on Philox paths or on Sobol paths (method="qmc") -- and the option has a fixed seed
+    #    (an unseeded one draws fresh normals / a fresh scramble per evaluation, as the reference's does: nothing to share).  Same bumps,
+    #    same formulas, same paths as the 8 / 14 price() calls.
     def _fused_plan(self):
-        """(kind, payoff code, barrier level) of the fused kernel that prices this adapter's option, or None."""
+        """(kind, payoff code, barrier level, qmc) of the fused kernel that prices this adapter's option, or None; qmc = method="qmc"."""
         from .exotic import AsianOption, BarrierOption, LookbackOption
         ex, kw = self.exotic, self.exotic_kwargs
-        if ex.seed is None or not (1 <= self.n_paths <= 1 << 26) or self.n_steps < 1:
+        qmc = kw.get("method", "pseudo") == "qmc"
+        if "method" in kw and not qmc:
+            return None
+        sobol = {"method", "path_construction"} if qmc else set()
+        if ex.seed is None or self.n_steps < 1 or not (1 <= self.n_paths <= (1 << 30 if qmc else 1 << 26)):
             return None
         if type(ex) is AsianOption:
             geometric = kw.get("avg_type", "arithmetic") != "arithmetic"             # AsianOption.price: anything but "arithmetic" is geometric
-            ok = set(kw) <= {"avg_type", "antithetic", "precision", "option_type"} and kw.get("precision", "fp64") in (("fp64", "fp32") if geometric else ("fp64",))
-            return ("asian", 1 if geometric else 0, 0.0) if ok else None
+            # method="qmc" with precision="fp32" is taken, to be refused as the literal form refuses it (_fused_greeks)
+            precisions = ("fp64", "fp32") if geometric or qmc else ("fp64",)
+            ok = set(kw) <= {"avg_type", "antithetic", "precision", "option_type"} | sobol and kw.get("precision", "fp64") in precisions
+            return ("asian", 1 if geometric else 0, 0.0, qmc) if ok else None
         if type(ex) is BarrierOption:
             kind = kw.get("barrier_type", "up-and-out")
-            if not (set(kw) <= {"barrier_type", "antithetic", "option_type"} and isinstance(kind, str) and ex.barrier > 0):
+            if not (set(kw) <= {"barrier_type", "antithetic", "option_type"} | sobol and isinstance(kind, str) and ex.barrier > 0):
                 return None
-            return ("extrema", (0 if kind.startswith("up") else 2) + (0 if kind.endswith("out") else 1), float(ex.barrier))      # exotic_options.py:201-212
+            return ("extrema", (0 if kind.startswith("up") else 2) + (0 if kind.endswith("out") else 1), float(ex.barrier), qmc)      # exotic_options.py:201-212
         if type(ex) is LookbackOption:
-            if not set(kw) <= {"lookback_type", "antithetic", "option_type"}:
+            if not set(kw) <= {"lookback_type", "antithetic", "option_type"} | sobol:
                 return None
-            return ("extrema", 4 if kw.get("lookback_type", "floating") == "floating" else 5, 0.0)
+            return ("extrema", 4 if kw.get("lookback_type", "floating") == "floating" else 5, 0.0, qmc)
         return None
 
     def _can_fuse(self, pricer_kwargs) -> bool:
@@ -78,15 +86,25 @@ class ExoticAdapter:
 
         from . import _hip
         ex, kw = self.exotic, self.exotic_kwargs
-        kind, payoff, level = self._fused_plan()
+        kind, payoff, level, qmc = self._fused_plan()
         is_call, anti = kw.get("option_type", option_type) == "call", bool(kw.get("antithetic", False))
-        if kind == "asian":
+        if qmc:         # the literal form's refusals and tables (exotic.py: AsianOption.price, _qmc_tables)
+            from .exotic import _qmc_precision, _qmc_tables
+            _qmc_precision("qmc", kw.get("precision", "fp64"))
+            sv, shift, bridge = _qmc_tables("qmc", kw.get("path_construction", "bridge"), self.n_paths, self.n_steps, ex.seed)
+        if kind != "asian" and payoff <= 3:     # a barrier: the mid contract's t = 0 decision is the reference's (the bumped spots are h_S away from it)
+            from .exotic import reference_barrier_level
+            level = reference_barrier_level(S, level, kw.get("barrier_type", "up-and-out"))
+        if kind == "asian" and qmc:
+            vals, _ = _hip.asian_qmc_greeks_fd(S, K, T, r, sigma, q, is_call, payoff == 1, self.n_paths, sv, shift, bridge, anti, include_second_order,
+                                               want_evals=False)
+        elif kind == "asian":
             vals, _ = _hip.asian_greeks_fd(S, K, T, r, sigma, q, is_call, self.n_paths, self.n_steps, ex.seed, anti, include_second_order, want_evals=False,
                                            geometric=payoff == 1)
+        elif qmc:
+            vals, _ = _hip.extrema_qmc_greeks_fd(S, K, T, r, sigma, q, is_call, payoff, level, self.n_paths, sv, shift, bridge, anti, include_second_order,
+                                                 want_evals=False)
         else:
-            if payoff <= 3:     # a barrier: the mid contract's t = 0 decision is the reference's (the bumped spots are h_S away from it)
-                from .exotic import reference_barrier_level
-                level = reference_barrier_level(S, level, kw.get("barrier_type", "up-and-out"))
             vals, _ = _hip.extrema_greeks_fd(S, K, T, r, sigma, q, is_call, payoff, level, self.n_paths, self.n_steps, ex.seed, anti, include_second_order,
                                              want_evals=False)
         ex.S, ex.K, ex.T, ex.r, ex.sigma, ex.q = S, K, T, r, sigma, q
