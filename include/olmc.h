@@ -59,7 +59,8 @@ extern "C" {
                               *    agent-scope acquire again (numbers unchanged) 
                               * 6: additions only -- olmc_multi_gpu_european_qmc_greeks_fd, olmc_multi_gpu_european_qmc_cv; OLMC_TUNE_QMC_BLOCK takes 2;
                               *    later additions within v6: olmc_asian_qmc, olmc_extrema_qmc (Sobol paths for the path payoffs),
-                              *    olmc_asian_qmc_greeks_fd, olmc_extrema_qmc_greeks_fd (their finite-difference Greeks in one launch) */
+                              *    olmc_asian_qmc_greeks_fd, olmc_extrema_qmc_greeks_fd (their finite-difference Greeks in one launch),
+                              *    olmc_american_lsm_qmc, olmc_exercise_boundary_qmc, olmc_gbm_qmc_paths (the American and its path matrix on Sobol paths) */
 
 enum {
     OLMC_OK = 0,
@@ -442,6 +443,32 @@ int olmc_asian_qmc_greeks_fd(double S, double K, double T, double r, double sigm
 int olmc_extrema_qmc_greeks_fd(double S, double K, double T, double r, double sigma, double q, int is_call, int payoff, double barrier,
                                int construction, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift,
                                int32_t bits, int antithetic, int second_order, double* out9, olmc_stats* evals /* [14] or NULL */);
+
+/* ---- quasi-Monte Carlo path matrix: the American option (LSM) and its exercise boundary ---------------
+ * olmc_american_lsm / olmc_exercise_boundary / olmc_gbm_paths on scrambled-Sobol paths: point k of
+ * scipy.stats.qmc.Sobol(d=n_steps, scramble=True, seed) (sv / shift / bits as olmc_european_qmc) drives path k, k in [0, n_points),
+ * with the z, the constructions and the bridge of the QMC path payoffs above, and
+ *   ln S_j = ln S + fma(vol, W_j, j drift), S_j = exp(ln S_j) in fp64, j = 1 .. n (drift, vol per step as there).
+ * OLMC_QMC_SEQUENTIAL sums W_j = W_{j-1} + z_{j-1} one date after another, left to right (np.cumsum's association; the wave scan of
+ * olmc_asian_qmc / olmc_extrema_qmc associates the same sum differently, a few ulps apart).  The bridge fills W in the plan's node order.
+ * Column 0 is exp(ln S) in the matrix the LSM chain and the boundary read (exotic_options.py:64-67, as olmc_exercise_boundary), S
+ * itself in the export (as olmc_gbm_paths); dates 1 .. n_steps have the same bits in every layout and every entry point.
+ *   olmc_american_lsm_qmc       the step chain of olmc_american_lsm (same regression, decisions and out) on the Sobol matrix;
+ *   olmc_exercise_boundary_qmc  the percentiles of olmc_exercise_boundary on it, boundary_host[n_steps + 1];
+ *   olmc_gbm_qmc_paths          the matrix itself to HOST memory: path_major != 0 -> out_host[i * (n_steps + 1) + t] (the reference's C
+ *                               order, written so by the kernel), path_major == 0 -> out_host[t * n_points + i] (the time-major layout the
+ *                               LSM chain reads).
+ * No antithetic mirror, no point offset (LSM regresses on the whole set).  Refused (OLMC_ERR_ARG, before any device work): a bad
+ * construction, the bridge beyond OLMC_QMC_BRIDGE_MAX_STEPS dates, bits != 30, n_points outside [1, 2^30], n_steps outside [1, 21201],
+ * poly_degree outside [1, 4], a device matrix over 64 GB (for the LSM the cash flows and the regression rows count towards it). */
+int olmc_american_lsm_qmc(double S, double K, double T, double r, double sigma, double q, int is_call, int construction,
+                          int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift, int32_t bits,
+                          int32_t poly_degree, olmc_stats* out);
+int olmc_exercise_boundary_qmc(double S, double K, double T, double r, double sigma, double q, int is_call, int construction,
+                               int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift, int32_t bits,
+                               double* boundary_host);
+int olmc_gbm_qmc_paths(double S, double T, double r, double sigma, double q, int construction, int64_t n_points, int32_t n_steps,
+                       const uint32_t* sv, const uint32_t* shift, int32_t bits, int path_major, double* out_host);
 
 /* ---- multi-GPU, single process ------------------------------------------
  * n_paths split into n_gpus contiguous global path ranges (rank d = device d, [d N / P, (d + 1) N / P)).  Per list of devices the

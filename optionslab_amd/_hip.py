@@ -92,6 +92,9 @@ PROTOTYPES = {
     "olmc_heston_paths": (_I, [_D] * 9 + [_I64, _I32, _U64T, _I, C.POINTER(_D), C.POINTER(_D)]),
     "olmc_jump_paths": (_I, [_D] * 5 + [_I, _D, _D, _D, _D, _I64, _I32, _U64T, _I, C.POINTER(_D)]),
     "olmc_american_lsm": (_I, _SIX + [_I, _I64, _I32, _I32, _U64T, C.POINTER(Stats)]),
+    "olmc_american_lsm_qmc": (_I, _SIX + [_I, _I, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, _I32, C.POINTER(Stats)]),
+    "olmc_exercise_boundary_qmc": (_I, _SIX + [_I, _I, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, C.POINTER(_D)]),
+    "olmc_gbm_qmc_paths": (_I, [_D] * 5 + [_I, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, _I, C.POINTER(_D)]),
     "olmc_jump_diffusion": (_I, _SIX + [_I, _I, _D, _D, _D, _D, _I64, _I64, _I32, _U64T, C.POINTER(Stats)]),
     "olmc_heston": (_I, [_D] * 5 + [_I] + [_D] * 5 + [_I64, _I64, _I32, _U64T, _I, C.POINTER(Stats)]),
     "olmc_multi_gpu_european": (_I, _SIX + [_I, _I64, _I32, _U64T, _I, _I, C.POINTER(Stats)]),
@@ -562,6 +565,33 @@ def american_lsm(S, K, T, r, sigma, q, is_call: bool, n_paths: int, n_steps: int
     out = Stats()
     _check(lib().olmc_american_lsm(S, K, T, r, sigma, q, int(is_call), int(n_paths), int(n_steps), int(poly_degree),
                                    seed64(seed), C.byref(out)))
+    return out
+
+
+def american_lsm_qmc(S, K, T, r, sigma, q, is_call: bool, n_points: int, sv: np.ndarray, shift: np.ndarray, bridge: bool, poly_degree: int) -> Stats:
+    """The American option (LSM) on scrambled-Sobol paths (olmc_american_lsm_qmc): n_steps = sv.shape[0] dates, points [0, n_points)."""
+    sv, psv, shift, psh = _sobol_args(sv, shift, 0, n_points)
+    out = Stats()
+    _check(lib().olmc_american_lsm_qmc(S, K, T, r, sigma, q, int(is_call), QMC_BRIDGE if bridge else QMC_SEQUENTIAL, int(n_points), int(sv.shape[0]),
+                                       psv, psh, int(sv.shape[1]), int(poly_degree), C.byref(out)))
+    return out
+
+
+def exercise_boundary_qmc(S, K, T, r, sigma, q, is_call: bool, n_points: int, sv: np.ndarray, shift: np.ndarray, bridge: bool) -> np.ndarray:
+    """exercise_boundary on the Sobol matrix of american_lsm_qmc (olmc_exercise_boundary_qmc)."""
+    sv, psv, shift, psh = _sobol_args(sv, shift, 0, n_points)
+    out = np.empty(int(sv.shape[0]) + 1, dtype=np.float64)
+    _check(lib().olmc_exercise_boundary_qmc(S, K, T, r, sigma, q, int(is_call), QMC_BRIDGE if bridge else QMC_SEQUENTIAL, int(n_points),
+                                            int(sv.shape[0]), psv, psh, int(sv.shape[1]), out.ctypes.data_as(C.POINTER(C.c_double))))
+    return out
+
+
+def gbm_qmc_paths(S, T, r, sigma, q, n_points: int, sv: np.ndarray, shift: np.ndarray, bridge: bool = True, path_major: bool = False) -> np.ndarray:
+    """Sobol-path prices at dates 0 .. n_steps = sv.shape[0] (date 0 = spot), layouts as gbm_paths (olmc_gbm_qmc_paths)."""
+    sv, psv, shift, psh = _sobol_args(sv, shift, 0, n_points)
+    out = _path_matrix(n_points, sv.shape[0], path_major)
+    _check(lib().olmc_gbm_qmc_paths(S, T, r, sigma, q, QMC_BRIDGE if bridge else QMC_SEQUENTIAL, int(n_points), int(sv.shape[0]), psv, psh,
+                                    int(sv.shape[1]), int(path_major), out.ctypes.data_as(C.POINTER(C.c_double))))
     return out
 
 

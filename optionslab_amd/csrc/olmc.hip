@@ -1491,23 +1491,11 @@ void lsm_regressor_scale(double S, double K, double r, double q, double sigma, d
     *centre = mean / K;
     *inv_width = K / width;
 }
-}  // namespace
 
-extern "C" int olmc_american_lsm(double S, double K, double T, double r, double sigma, double q, int is_call,
-                                 int64_t n_paths, int32_t n_steps, int32_t poly_degree, uint64_t seed, olmc_stats* out) {
-    if (!out) return fail(OLMC_ERR_ARG, "null pointer");
-    if (poly_degree < 1 || poly_degree > kLsmMaxDegree) return fail(OLMC_ERR_ARG, "poly_degree must be in [1, 4]");
-    const double path_bytes = 8.0 * static_cast<double>(n_paths) * (n_steps + 2.0) + 8.0 * 2 * 1024 * kLsmNV;   // + two buffers of <= 1024 workgroup rows
-    CtxLease lease;
-    int rc = matrix_prologue(n_paths, n_steps, path_bytes, "path matrix would exceed 64 GB: lower n_paths or n_steps", &lease);
-    if (rc) return rc;
-    DeviceCtx* const c = lease.c;
-    double* d_paths = static_cast<double*>(c->d_bulk);                                  // [n_steps + 1][n_paths]
-    double* d_cash = d_paths + static_cast<size_t>(n_steps + 1) * n_paths;              // [n_paths]
-    double* d_rows = d_cash + n_paths;                                                  // [2][grid][kLsmNV]: the regression sums a date hands to the next launch
+// The contract of an LSM pricing on paths of T / n_steps steps (exotic_options.py:54-56, 260-261); column 0 is exp(ln S) (:59-65).
+LsmContract lsm_contract(double S, double K, double T, double r, double sigma, double q, int is_call, int32_t n_steps, int32_t poly_degree) {
     LsmContract lc;
-    const GbmStep g = gbm_step(T, n_steps, r, q, sigma);          // exotic_options.py:54-56, 260-261
-    const double dt = g.dt;
+    const GbmStep g = gbm_step(T, n_steps, r, q, sigma);
     lc.log_s0 = std::log(S);
     lc.s_first = std::exp(lc.log_s0);
     lc.drift = g.drift;
@@ -1515,29 +1503,37 @@ extern "C" int olmc_american_lsm(double S, double K, double T, double r, double 
     lc.strike = K;
     lc.inv_strike = 1.0 / K;
     lc.sign = is_call ? 1.0 : -1.0;
-    lc.discount = std::exp(-r * dt);
+    lc.discount = std::exp(-r * g.dt);
     lc.degree = poly_degree;
     lc.n_steps = n_steps;
-    const PathRange pr = make_range(0, n_paths, n_steps, seed);
-    const int32_t path_grid = grid_for(n_paths);
+    return lc;
+}
+
+// Bytes of an LSM pricing's device buffers: the path matrix and the cash flows, + two buffers of <= 1024 workgroup rows.
+double lsm_bytes(int64_t n_paths, int32_t n_steps) { return 8.0 * static_cast<double>(n_paths) * (n_steps + 2.0) + 8.0 * 2 * 1024 * kLsmNV; }
+
+// The step chain of an LSM pricing over the time-major path matrix d_paths [n_steps + 1][n_paths] that a launch queued before it on
+// c's stream writes; d_cash [n_paths] and d_rows [2][1024][kLsmNV] follow it in c's bulk buffer.  Leaves the moments of the time-0
+// cash flows in c->h_result once the host has waited for them.
+int lsm_chain(DeviceCtx* c, double S, double K, double T, double r, double sigma, double q, int is_call, const LsmContract& lc,
+              int64_t n_paths, int32_t n_steps, double* d_paths) {
+    double* d_cash = d_paths + static_cast<size_t>(n_steps + 1) * n_paths;              // [n_paths]
+    double* d_rows = d_cash + n_paths;                                                  // [2][grid][kLsmNV]: the regression sums a date hands to the next launch
+    const double dt = T / n_steps;
     // The per-date launches move 32 bytes per path and hand 16 sums per workgroup to the next launch, EVERY workgroup of which sums all
     // the rows: at most ONE workgroup per compute unit (<= 256 rows: one round trip), each thread taking its paths U at a time with all
     // 3 U loads in flight.  With one wave per SIMD the register count buys nothing, so U follows the paths a thread has (1, 2, 4, 8:
     // 98 ... 170 VGPRs).  Measured per call, 51 launches (profiles/r04_lsm_ab.jsonl): 1M x 50 -- 898 us at U = 1, 771 / 658 / 628 / 662 at
     // 2 / 4 / 8 / 16; two workgroups per CU 792 / 717 / 674 (U = 1 / 2 / 4), four 978 / 971 / 952 (a workgroup re-reads every row);
     // 200k x 50 -- 366 / 343 / 328 / 345 at U = 1 / 2 / 4 / 8; 50k x 50, where a thread has one path, 275 - 300 whatever U.
-    const int32_t grid = std::min<int32_t>(path_grid, std::min<int32_t>(c->cus, 1024));
+    const int32_t grid = std::min<int32_t>(grid_for(n_paths), std::min<int32_t>(c->cus, 1024));
     const int64_t per_thread = (n_paths + static_cast<int64_t>(grid) * kBlock - 1) / (static_cast<int64_t>(grid) * kBlock);
     const int lsm_unroll = per_thread <= 1 ? 1 : per_thread <= 2 ? 2 : per_thread <= 4 ? 4 : 8;
-    EventPair ep{};
-    if (g_profile) { rc = prof_begin(c, c->stream, &ep); if (rc) return rc; }
-    hipLaunchKernelGGL((lsm_paths_kernel<false>), dim3(path_grid), dim3(kBlock), 0, c->stream, pr, lc, d_paths);
-    HIP_TRY(hipGetLastError());
     // every launch sums the rows the launch before it stored, fits the later date from them and stores its own rows: stream order is
     // the only synchronisation, the host waits once at the end.  Only the LAST launch (t_fit == 0: the moments of the time-0 cash
     // flow) goes through the grid reduction and writes into the pinned host buffer.
     ReduceWs ws;
-    rc = make_ws(c, c->stream, grid, kLsmNV, c->d_result, -1.0, &ws);          // arms the completion word for the launch that writes d_result
+    int rc = make_ws(c, c->stream, grid, kLsmNV, c->d_result, -1.0, &ws);          // arms the completion word for the launch that writes d_result
     if (rc) return rc;
     std::vector<double> centre(static_cast<size_t>(n_steps) + 1, 1.0), inv_width(static_cast<size_t>(n_steps) + 1, 1.0);   // while the path kernel runs
     for (int32_t t = 1; t < n_steps; ++t) lsm_regressor_scale(S, K, r, q, sigma, dt, t, is_call != 0, &centre[t], &inv_width[t]);
@@ -1561,7 +1557,26 @@ extern "C" int olmc_american_lsm(double S, double K, double T, double r, double 
         if (rc) return rc;
         init = 0;
     }
-    rc = sync_or_recover(c, c->stream);
+    return sync_or_recover(c, c->stream);
+}
+}  // namespace
+
+extern "C" int olmc_american_lsm(double S, double K, double T, double r, double sigma, double q, int is_call,
+                                 int64_t n_paths, int32_t n_steps, int32_t poly_degree, uint64_t seed, olmc_stats* out) {
+    if (!out) return fail(OLMC_ERR_ARG, "null pointer");
+    if (poly_degree < 1 || poly_degree > kLsmMaxDegree) return fail(OLMC_ERR_ARG, "poly_degree must be in [1, 4]");
+    CtxLease lease;
+    int rc = matrix_prologue(n_paths, n_steps, lsm_bytes(n_paths, n_steps), "path matrix would exceed 64 GB: lower n_paths or n_steps", &lease);
+    if (rc) return rc;
+    DeviceCtx* const c = lease.c;
+    double* d_paths = static_cast<double*>(c->d_bulk);                                  // [n_steps + 1][n_paths]
+    const LsmContract lc = lsm_contract(S, K, T, r, sigma, q, is_call, n_steps, poly_degree);
+    const PathRange pr = make_range(0, n_paths, n_steps, seed);
+    EventPair ep{};
+    if (g_profile) { rc = prof_begin(c, c->stream, &ep); if (rc) return rc; }
+    hipLaunchKernelGGL((lsm_paths_kernel<false>), dim3(grid_for(n_paths)), dim3(kBlock), 0, c->stream, pr, lc, d_paths);
+    HIP_TRY(hipGetLastError());
+    rc = lsm_chain(c, S, K, T, r, sigma, q, is_call, lc, n_paths, n_steps, d_paths);
     if (rc) return rc;
     if (g_profile) { rc = prof_end(c, c->stream, ep); if (rc) return rc; }
     // the time-0 cash flows are already discounted step by step (:302-304): no outer factor
@@ -2082,6 +2097,97 @@ extern "C" int olmc_extrema_qmc_greeks_fd(double S, double K, double T, double r
     if (payoff <= OLMC_BARRIER_DOWN_IN && !(barrier > 0.0)) return fail(OLMC_ERR_ARG, "Barrier must be positive");
     return run_qmc_path_greeks(kQmcExtrema, payoff, S, K, T, r, sigma, q, is_call, payoff <= OLMC_BARRIER_DOWN_IN ? barrier : 0.0, construction,
                                n_points, n_steps, sv, shift, bits, antithetic, second_order, out9, evals);
+}
+
+// ================================================================ QMC path matrix ====
+namespace {
+// The argument checks and the lease of a Sobol path-matrix call: qmc_path_check, then matrix_prologue with the call's `bytes` (reserved
+// when `reserve`) -- every refusal before any device work.
+int qmc_matrix_prologue(int construction, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift, int32_t bits,
+                        double bytes, CtxLease* lease, bool reserve = true) {
+    const int rc = qmc_path_check(construction, 0, n_points, n_steps, sv, shift, bits);
+    return rc ? rc : matrix_prologue(n_points, n_steps, bytes, "path matrix would exceed 64 GB: lower n_paths or n_steps", lease, reserve);
+}
+
+// Sobol points [0, n_points) as the path matrix d_paths (lsm_qmc_paths_kernel), queued on c's stream behind the tables and the plan.
+int qmc_matrix(DeviceCtx* c, int construction, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift, const LsmContract& lc,
+               bool path_major, double* d_paths) {
+    QmcPathLaunch pl;
+    const int rc = qmc_path_setup(c, construction, 0, n_points, n_steps, sv, shift, 0, &pl);
+    if (rc) return rc;
+    const int64_t blocks = (n_points + kWave - 1) / kWave;               // one wave per 64 points, grid-striding beyond kQmcPathMaxGrid
+    const int32_t grid = static_cast<int32_t>(std::min<int64_t>((blocks + kWavesPerBlock - 1) / kWavesPerBlock, kQmcPathMaxGrid));
+    with_bool(pl.bridge, [&](auto b) {
+        with_bool(path_major, [&](auto pm) {
+            launch_timed(lsm_qmc_paths_kernel<b, pm>, dim3(grid), dim3(kBlock), c->stream, nullptr, pl.qr, lc, pl.d_sv, pl.d_shift, pl.plan, d_paths);
+        });
+    });
+    HIP_TRY(hipGetLastError());
+    return OLMC_OK;
+}
+}  // namespace
+
+extern "C" int olmc_american_lsm_qmc(double S, double K, double T, double r, double sigma, double q, int is_call, int construction,
+                                     int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift, int32_t bits,
+                                     int32_t poly_degree, olmc_stats* out) {
+    if (!out) return fail(OLMC_ERR_ARG, "null pointer");
+    if (poly_degree < 1 || poly_degree > kLsmMaxDegree) return fail(OLMC_ERR_ARG, "poly_degree must be in [1, 4]");
+    CtxLease lease;
+    int rc = qmc_matrix_prologue(construction, n_points, n_steps, sv, shift, bits, lsm_bytes(n_points, n_steps), &lease);
+    if (rc) return rc;
+    DeviceCtx* const c = lease.c;
+    double* d_paths = static_cast<double*>(c->d_bulk);                                  // [n_steps + 1][n_points], then olmc_american_lsm's buffers
+    const LsmContract lc = lsm_contract(S, K, T, r, sigma, q, is_call, n_steps, poly_degree);
+    EventPair ep{};
+    if (g_profile) { rc = prof_begin(c, c->stream, &ep); if (rc) return rc; }
+    rc = qmc_matrix(c, construction, n_points, n_steps, sv, shift, lc, false, d_paths);
+    if (rc) return rc;
+    rc = lsm_chain(c, S, K, T, r, sigma, q, is_call, lc, n_points, n_steps, d_paths);
+    if (rc) return rc;
+    if (g_profile) { rc = prof_end(c, c->stream, ep); if (rc) return rc; }
+    finish_one(c->h_result, n_points, 0.0, T, poisoned(S, K, T, r, sigma, q), out);
+    return OLMC_OK;
+}
+
+extern "C" int olmc_exercise_boundary_qmc(double S, double K, double T, double r, double sigma, double q, int is_call, int construction,
+                                          int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift, int32_t bits,
+                                          double* boundary_host) {
+    if (!boundary_host) return fail(OLMC_ERR_ARG, "null pointer");
+    const size_t rows = static_cast<size_t>(n_steps) + 1;
+    const double bytes = 8.0 * static_cast<double>(n_points) * (n_steps + 1.0);
+    CtxLease lease;
+    int rc = qmc_matrix_prologue(construction, n_points, n_steps, sv, shift, bits, bytes, &lease, false);
+    if (rc) return rc;
+    DeviceCtx* const c = lease.c;
+    const size_t path_bytes = (static_cast<size_t>(bytes) + 255) / 256 * 256;
+    rc = bulk_reserve(c, path_bytes + rows * sizeof(double));
+    if (rc) return rc;
+    double* d_paths = static_cast<double*>(c->d_bulk);
+    double* d_boundary = reinterpret_cast<double*>(static_cast<char*>(c->d_bulk) + path_bytes);
+    rc = qmc_matrix(c, construction, n_points, n_steps, sv, shift, lsm_contract(S, K, T, r, sigma, q, is_call, n_steps, 1), false, d_paths);
+    if (rc) return rc;
+    // as olmc_exercise_boundary: np.percentile(x, 10) for a put, 90 for a call (exotic_options.py:337-341)
+    hipLaunchKernelGGL(exercise_boundary_kernel, dim3(static_cast<uint32_t>(rows)), dim3(kBoundaryThreads), 0, c->stream, d_paths, n_points, K,
+                       is_call ? 1.0 : -1.0, (is_call ? 90.0 : 10.0) / 100.0, d_boundary);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(boundary_host, d_boundary, rows * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return OLMC_OK;
+}
+
+extern "C" int olmc_gbm_qmc_paths(double S, double T, double r, double sigma, double q, int construction, int64_t n_points, int32_t n_steps,
+                                  const uint32_t* sv, const uint32_t* shift, int32_t bits, int path_major, double* out_host) {
+    if (!out_host) return fail(OLMC_ERR_ARG, "null pointer");
+    const double bytes = 8.0 * static_cast<double>(n_points) * (n_steps + 1.0);
+    CtxLease lease;
+    int rc = qmc_matrix_prologue(construction, n_points, n_steps, sv, shift, bits, bytes, &lease);
+    if (rc) return rc;
+    DeviceCtx* const c = lease.c;
+    LsmContract lc = lsm_contract(S, S, T, r, sigma, q, 0, n_steps, 1);            // no strike: only the path fields are read
+    lc.s_first = S;                                                     // the export's column 0 is S itself, as olmc_gbm_paths'
+    rc = qmc_matrix(c, construction, n_points, n_steps, sv, shift, lc, path_major != 0, static_cast<double*>(c->d_bulk));
+    if (rc) return rc;
+    return copy_to_host(c, out_host, c->d_bulk, static_cast<size_t>(bytes));
 }
 
 namespace {

@@ -3327,6 +3327,88 @@ __global__ __launch_bounds__(kBlock) void qmc_path_greeks_kernel(QmcRange qr, Ex
     grid_reduce_workgroup<NV>(row, ws);
 }
 
+// ------------------------------------------------------------- QMC path matrix (American, LSM) ----
+// The Sobol-path matrix of olmc_american_lsm_qmc / olmc_exercise_boundary_qmc / olmc_gbm_qmc_paths: S_j of points [0, count) at
+// dates j = 0 .. n (PATH_MAJOR as path_at), with qmc_path_kernel's z, bridge plan and ln S_j = ln S + fma(vol, W_j, j drift),
+// S_j = exp(ln S_j) in fp64, column 0 = c.s_first.
+//
+// LANES OVER POINTS (where qmc_path_kernel runs lanes over dates): the 64 lanes of a wave hold the 64 consecutive points of an aligned
+// block, so a time-major store of one date is 512 contiguous bytes.  Bits 6 .. 29 of the block's Gray codes are the same in every lane
+// (qmc_point_sum<true>): per 64 dimensions lane l folds them -- and the digital shift -- into one word for dimension c0 + l, and the
+// dimension loop broadcasts that word (ds_bpermute) and adds the lane's own six low rows.  Lanes past `count` in the last block fold
+// and broadcast with the others and touch no memory.
+//   SEQUENTIAL  W_j = W_{j-1} + z_{j-1}: a running sum per lane, one store per date (the wave scan of qmc_point_walk associates the
+//               same sum otherwise: a few ulps apart).
+//   BRIDGE      node k of the plan (a, b, m and the coefficients wave-uniform) fills W_m = fma(ca, W_a, fma(cb, W_b, sd z_k)) INTO the
+//               lane's own column of the output (W_0 = 0 is not stored; W_n = sqrt(n) z_0), in plan order: W_a and W_b are the lane's
+//               own earlier stores.  A second sweep turns W_j into S_j in place.  No LDS, any n <= kQmcBridgeMaxSteps.
+// Resources (-Rpass-analysis=kernel-resource-usage, gfx950): 70-72 VGPRs, no LDS, no scratch (the inverse normal's coefficients spill
+// SGPRs to VGPR lanes only, as in the other Sobol kernels), 7 waves per SIMD.  Measured (profiles/r08_lsm_qmc_timing.jsonl): 2^20 x 50
+// 0.19 ms sequential, 0.37 bridge (lsm_paths_kernel 0.095); the bridge's nodes read back the lane's own earlier stores (latency).
+template <bool BRIDGE, bool PATH_MAJOR>
+__global__ __launch_bounds__(kBlock) void lsm_qmc_paths_kernel(QmcRange qr, LsmContract c, const uint32_t* __restrict__ sv,
+                                                               const uint32_t* __restrict__ shift, QmcBridgePlan plan, double* paths) {
+    const int lane = static_cast<int>(threadIdx.x) & (kWave - 1);
+    const int32_t n = qr.dims;
+    const int64_t count = qr.count;
+    const int64_t n_blocks = (count + kWave - 1) / kWave;
+    const int64_t stride = static_cast<int64_t>(gridDim.x) * kWavesPerBlock;
+    const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) / kWave);
+    for (int64_t blk = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave; blk < n_blocks; blk += stride) {
+        const int64_t i = blk * kWave + lane;
+        const bool live = i < count;
+        const uint32_t k = static_cast<uint32_t>(i);                               // < 2^30: the host refuses more points
+        const uint32_t gray = k ^ (k >> 1);
+        const uint32_t gray_hi = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(gray))) & ~63u;
+        uint32_t mask[6];
+#pragma unroll
+        for (int b = 0; b < 6; ++b) mask[b] = 0u - ((gray >> b) & 1u);
+        auto at = [&](int32_t t) { return path_at<PATH_MAJOR>(i, t, count, n); };
+        if (live) paths[at(0)] = c.s_first;
+        double w = 0.0;                                                            // sequential: W_j
+        for (int32_t c0 = 0; c0 < n; c0 += kWave) {
+            const int32_t tl = c0 + lane < n ? c0 + lane : n - 1;
+            const uint32_t* __restrict__ mine = sv + static_cast<size_t>(tl) * kSobolBits;
+            uint32_t fold = shift[tl];
+#pragma unroll
+            for (int b = 6; b < kSobolBits; ++b) fold ^= mine[b] & (0u - ((gray_hi >> b) & 1u));
+            const int32_t cn = n - c0 < kWave ? n - c0 : kWave;
+            for (int32_t d = 0; d < cn; ++d) {
+                const int32_t t = c0 + d;                                          // dimension t = date t + 1 / bridge node t
+                const uint32_t* __restrict__ row = sv + static_cast<size_t>(t) * kSobolBits;
+                uint32_t x = static_cast<uint32_t>(__shfl(static_cast<int>(fold), d, kWave));
+#pragma unroll
+                for (int b = 0; b < 6; ++b) x = __builtin_amdgcn_bitop3_b32(x, row[b], mask[b], 0x78);   // x ^ (row & mask)
+                const double z = ndtri_w_add(0.0, sobol_uniform(x), opaque_zero());
+                if constexpr (BRIDGE) {
+                    if (t == 0) {
+                        if (live) paths[at(n)] = sqrt(static_cast<double>(n)) * z;
+                    } else {
+                        const uint32_t ab = plan.ab[t];
+                        const int32_t a = static_cast<int32_t>(ab & 0xffffu), b = static_cast<int32_t>(ab >> 16), m = (a + b) >> 1;
+                        const double ca = plan.coef[t], cb = plan.coef[n + t], sd = plan.coef[2 * n + t];
+                        if (live) {
+                            const double wa = a == 0 ? 0.0 : paths[at(a)];
+                            paths[at(m)] = __builtin_fma(ca, wa, __builtin_fma(cb, paths[at(b)], sd * z));
+                        }
+                    }
+                } else {
+                    w += z;
+                    if (live) paths[at(t + 1)] = exp(c.log_s0 + __builtin_fma(c.vol, w, static_cast<double>(t + 1) * c.drift));
+                }
+            }
+        }
+        if constexpr (BRIDGE) {
+            if (live) {
+                for (int32_t j = 1; j <= n; ++j) {
+                    const size_t p = at(j);
+                    paths[p] = exp(c.log_s0 + __builtin_fma(c.vol, paths[p], static_cast<double>(j) * c.drift));
+                }
+            }
+        }
+    }
+}
+
 // ------------------------------------------------------- validation taps ----
 __global__ void philox_words_kernel(uint64_t first, int64_t n_paths, int32_t block0, int32_t n_blocks,
                                     uint32_t tag, uint32_t k0, uint32_t k1, uint32_t* __restrict__ out) {

@@ -6,8 +6,8 @@ signature; the running average lives in registers, no (n_paths, n_steps) matrix
 exists.  Like the reference there is no antithetic mirror unless asked for, and
 the return value is a ``numpy.float64``.
 
-Additive: ``method="qmc"`` prices the Asian, barrier and lookback payoffs on scrambled-Sobol paths (_qmc_tables, include/olmc.h
-"quasi-Monte Carlo path payoffs"), by default with the Brownian-bridge construction.
+Additive: ``method="qmc"`` prices the Asian, barrier, lookback and American (LSM) options on scrambled-Sobol paths (_qmc_tables,
+include/olmc.h "quasi-Monte Carlo path payoffs" and "quasi-Monte Carlo path matrix"), by default with the Brownian-bridge construction.
 """
 from __future__ import annotations
 
@@ -213,19 +213,37 @@ class AmericanOption:
     seed: Optional[int] = None
 
     def price(self, n_paths: int = 50000, n_steps: int = 50, option_type: Literal["call", "put"] = "put",
-              poly_degree: int = 3, return_error: bool = False):
+              poly_degree: int = 3, return_error: bool = False,
+              method: Literal["pseudo", "qmc"] = "pseudo", path_construction: Literal["bridge", "sequential"] = "bridge"):
+        """method, path_construction (additive): "qmc" prices on scrambled-Sobol paths, as AsianOption.price (the seed is the scramble
+        seed; the standard error is the naive per-path one), with the same regression as the Philox paths (include/olmc.h "quasi-Monte
+        Carlo path matrix").  Refused (ValueError, before the device is touched) as there."""
         if n_paths < 1 or n_steps < 1:
             raise ValueError("n_paths and n_steps must be >= 1")
+        qmc = _qmc_tables(method, path_construction, n_paths, n_steps, self.seed)
+        if qmc is not None:
+            sv, shift, bridge = qmc
+            st = _hip.american_lsm_qmc(self.S, self.K, self.T, self.r, self.sigma, self.q, option_type == "call", n_paths, sv, shift, bridge,
+                                       poly_degree)
+            return (np.float64(st.price), float(st.std_error)) if return_error else np.float64(st.price)
         seed = self.seed if self.seed is not None else int(np.random.default_rng().integers(0, 2**31))
         st = _hip.american_lsm(self.S, self.K, self.T, self.r, self.sigma, self.q, option_type == "call", n_paths, n_steps,
                                poly_degree, seed)
         return (np.float64(st.price), float(st.std_error)) if return_error else np.float64(st.price)
 
-    def early_exercise_boundary(self, n_paths: int = 10000, n_steps: int = 50, option_type: Literal["call", "put"] = "put"):
+    def early_exercise_boundary(self, n_paths: int = 10000, n_steps: int = 50, option_type: Literal["call", "put"] = "put",
+                                method: Literal["pseudo", "qmc"] = "pseudo", path_construction: Literal["bridge", "sequential"] = "bridge"):
         """exotic_options.py:309-345: (times, boundary): per date the 10th (put) / 90th (call) percentile of the
-        in-the-money simulated prices, NaN where none is; selected on the device from the LSM path set."""
+        in-the-money simulated prices, NaN where none is; selected on the device from the LSM path set.
+        method, path_construction (additive): the Sobol path set of price(method="qmc")."""
         if n_paths < 1 or n_steps < 1:
             raise ValueError("n_paths and n_steps must be >= 1")
+        qmc = _qmc_tables(method, path_construction, n_paths, n_steps, self.seed)
+        if qmc is not None:
+            sv, shift, bridge = qmc
+            boundary = _hip.exercise_boundary_qmc(self.S, self.K, self.T, self.r, self.sigma, self.q, option_type == "call", n_paths, sv, shift,
+                                                  bridge)
+            return np.linspace(0, self.T, n_steps + 1), boundary
         seed = self.seed if self.seed is not None else int(np.random.default_rng().integers(0, 2**31))
         boundary = _hip.exercise_boundary(self.S, self.K, self.T, self.r, self.sigma, self.q, option_type == "call", n_paths, n_steps, seed)
         return np.linspace(0, self.T, n_steps + 1), boundary

@@ -7,7 +7,7 @@ import numpy as np
 from . import _hip
 
 __all__ = ["simulate_gbm_hip", "simulate_gbm_hip_fast", "simulate_gbm_paths_hip", "simulate_gbm_qmc_hip",
-           "simulate_gbm_qmc_antithetic_hip", "hip_available"]
+           "simulate_gbm_qmc_antithetic_hip", "simulate_gbm_qmc_paths_hip", "hip_available"]
 
 hip_available = _hip.hip_available
 
@@ -52,3 +52,16 @@ def simulate_gbm_qmc_antithetic_hip(S: float, T: float, r: float, sigma: float, 
 
     sv, shift = sobol_tables(n_steps, seed, n_paths)
     return _hip.european_qmc_terminal(S, T, r, sigma, q, n_paths, sv, shift, antithetic=True)
+
+
+def simulate_gbm_qmc_paths_hip(S: float, T: float, r: float, sigma: float, q: float, n_paths: int, n_steps: int, seed: int,
+                               path_construction: str = "bridge") -> np.ndarray:
+    """Full scrambled-Sobol paths, shape (n_paths, n_steps + 1), column 0 = S: point k of Sobol(d=n_steps, scramble=True, seed) drives
+    path k by the bridge or the sequential construction -- the path set of AmericanOption.price(method="qmc") (include/olmc.h).
+    Refused (ValueError, before the device is touched) as AsianOption.price(method="qmc")."""
+    from .exotic import _qmc_tables
+
+    if n_paths < 1 or n_steps < 1:
+        raise ValueError("n_paths and n_steps must be >= 1")
+    sv, shift, bridge = _qmc_tables("qmc", path_construction, n_paths, n_steps, seed)
+    return _hip.gbm_qmc_paths(S, T, r, sigma, q, n_paths, sv, shift, bridge, path_major=True)
