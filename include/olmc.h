@@ -60,7 +60,8 @@ extern "C" {
                               * 6: additions only -- olmc_multi_gpu_european_qmc_greeks_fd, olmc_multi_gpu_european_qmc_cv; OLMC_TUNE_QMC_BLOCK takes 2;
                               *    later additions within v6: olmc_asian_qmc, olmc_extrema_qmc (Sobol paths for the path payoffs),
                               *    olmc_asian_qmc_greeks_fd, olmc_extrema_qmc_greeks_fd (their finite-difference Greeks in one launch),
-                              *    olmc_american_lsm_qmc, olmc_exercise_boundary_qmc, olmc_gbm_qmc_paths (the American and its path matrix on Sobol paths) */
+                              *    olmc_american_lsm_qmc, olmc_exercise_boundary_qmc, olmc_gbm_qmc_paths (the American and its path matrix on Sobol paths),
+                              *    olmc_autocallable_qmc, olmc_cliquet_qmc (the structured products on Sobol paths) */
 
 enum {
     OLMC_OK = 0,
@@ -443,6 +444,27 @@ int olmc_asian_qmc_greeks_fd(double S, double K, double T, double r, double sigm
 int olmc_extrema_qmc_greeks_fd(double S, double K, double T, double r, double sigma, double q, int is_call, int payoff, double barrier,
                                int construction, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift,
                                int32_t bits, int antithetic, int second_order, double* out9, olmc_stats* evals /* [14] or NULL */);
+
+/* ---- quasi-Monte Carlo structured products: autocallable, cliquet ---------------
+ * olmc_autocallable / olmc_cliquet on the scrambled-Sobol paths of the "quasi-Monte Carlo path payoffs" section above: the same sv /
+ * shift / bits, the same z_t, the same two constructions (and the bridge's cap), the same ln S_j = ln S + j drift + vol W_j; point k
+ * drives path k, antithetic != 0 also prices the mirrored point -z (2 n_points payoffs), points [point_offset, point_offset +
+ * n_points) are a shard of one sequence (olmc_combine_stats).  The contracts mean what they mean in the pseudo-random calls:
+ *   olmc_autocallable_qmc  observations at t = f, 2f, ... <= n_steps, levels relative to spot and decided in log space, the knock-in
+ *                          minimum with t = 0; each payoff discounted at its own date, out->price = their mean (no outer discount);
+ *   olmc_cliquet_qmc       n_periods resets of n_steps / n_periods (integer) dates from t = 0; dates after the last reset never enter
+ *                          (the sequential construction does not draw their dimensions); out->price = exp(-r T) mean.
+ * out->std_error is the naive per-path one (for Sobol points not a confidence interval).  Payoffs are reduced in index order: equal
+ * arguments give equal bits.  A NaN input gives NaN results, as in the pseudo-random calls.  Refused (OLMC_ERR_ARG, before any device
+ * work): observation_freq < 1 or > n_steps, n_periods outside [1, n_steps], a bad construction, the bridge beyond
+ * OLMC_QMC_BRIDGE_MAX_STEPS dates, bits != 30, n_points outside [1, 2^30], n_steps outside [1, 21201], a null pointer. */
+int olmc_autocallable_qmc(double S, double T, double r, double sigma, double q, double autocall_barrier, double coupon_barrier,
+                          double coupon_rate, double ki_barrier, int32_t observation_freq, int construction,
+                          int64_t point_offset, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift,
+                          int32_t bits, int antithetic, olmc_stats* out);
+int olmc_cliquet_qmc(double S, double T, double r, double sigma, double q, double local_cap, double local_floor, double global_cap,
+                     double global_floor, int32_t n_periods, int construction, int64_t point_offset, int64_t n_points,
+                     int32_t n_steps, const uint32_t* sv, const uint32_t* shift, int32_t bits, int antithetic, olmc_stats* out);
 
 /* ---- quasi-Monte Carlo path matrix: the American option (LSM) and its exercise boundary ---------------
  * olmc_american_lsm / olmc_exercise_boundary / olmc_gbm_paths on scrambled-Sobol paths: point k of

@@ -92,6 +92,8 @@ PROTOTYPES = {
     "olmc_heston_paths": (_I, [_D] * 9 + [_I64, _I32, _U64T, _I, C.POINTER(_D), C.POINTER(_D)]),
     "olmc_jump_paths": (_I, [_D] * 5 + [_I, _D, _D, _D, _D, _I64, _I32, _U64T, _I, C.POINTER(_D)]),
     "olmc_american_lsm": (_I, _SIX + [_I, _I64, _I32, _I32, _U64T, C.POINTER(Stats)]),
+    "olmc_autocallable_qmc": (_I, [_D] * 9 + [_I32, _I, _I64, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, _I, C.POINTER(Stats)]),
+    "olmc_cliquet_qmc": (_I, [_D] * 9 + [_I32, _I, _I64, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, _I, C.POINTER(Stats)]),
     "olmc_american_lsm_qmc": (_I, _SIX + [_I, _I, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, _I32, C.POINTER(Stats)]),
     "olmc_exercise_boundary_qmc": (_I, _SIX + [_I, _I, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, C.POINTER(_D)]),
     "olmc_gbm_qmc_paths": (_I, [_D] * 5 + [_I, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, _I, C.POINTER(_D)]),
@@ -558,6 +560,28 @@ def cliquet(S, T, r, sigma, q, local_cap, local_floor, global_cap, global_floor,
     out = Stats()
     _check(lib().olmc_cliquet(S, T, r, sigma, q, local_cap, local_floor, global_cap, global_floor, int(n_periods),
                               int(path_offset), int(n_paths), int(n_steps), seed64(seed), int(antithetic), C.byref(out)))
+    return out
+
+
+def autocallable_qmc(S, T, r, sigma, q, autocall_barrier, coupon_barrier, coupon_rate, ki_barrier, observation_freq: int, n_points: int,
+                     sv: np.ndarray, shift: np.ndarray, bridge: bool = True, antithetic: bool = False, point_offset: int = 0) -> Stats:
+    """The autocallable on scrambled-Sobol paths (olmc_autocallable_qmc): n_steps = sv.shape[0] dates, bridge or sequential construction."""
+    sv, psv, shift, psh = _sobol_args(sv, shift, point_offset, n_points)
+    out = Stats()
+    _check(lib().olmc_autocallable_qmc(S, T, r, sigma, q, autocall_barrier, coupon_barrier, coupon_rate, ki_barrier, int(observation_freq),
+                                       QMC_BRIDGE if bridge else QMC_SEQUENTIAL, int(point_offset), int(n_points), int(sv.shape[0]), psv, psh,
+                                       int(sv.shape[1]), int(antithetic), C.byref(out)))
+    return out
+
+
+def cliquet_qmc(S, T, r, sigma, q, local_cap, local_floor, global_cap, global_floor, n_periods: int, n_points: int, sv: np.ndarray,
+                shift: np.ndarray, bridge: bool = True, antithetic: bool = False, point_offset: int = 0) -> Stats:
+    """The cliquet on scrambled-Sobol paths (olmc_cliquet_qmc): n_steps = sv.shape[0] dates, bridge or sequential construction."""
+    sv, psv, shift, psh = _sobol_args(sv, shift, point_offset, n_points)
+    out = Stats()
+    _check(lib().olmc_cliquet_qmc(S, T, r, sigma, q, local_cap, local_floor, global_cap, global_floor, int(n_periods),
+                                  QMC_BRIDGE if bridge else QMC_SEQUENTIAL, int(point_offset), int(n_points), int(sv.shape[0]), psv, psh,
+                                  int(sv.shape[1]), int(antithetic), C.byref(out)))
     return out
 
 

@@ -1353,13 +1353,23 @@ extern "C" int olmc_extrema_greeks_fd(double S, double K, double T, double r, do
 }
 
 // ======================================================= autocallable / cliquet ====
-extern "C" int olmc_autocallable(double S, double T, double r, double sigma, double q, double autocall_barrier,
-                                 double coupon_barrier, double coupon_rate, double ki_barrier, int32_t observation_freq,
-                                 int64_t path_offset, int64_t n_local, int32_t n_steps, uint64_t seed, int antithetic,
-                                 olmc_stats* out) {
+namespace {
+// The checks and the contract of an autocallable, shared by the Philox and the Sobol entry points.
+int autocall_check(int32_t observation_freq, int32_t n_steps) {
     if (observation_freq < 1) return fail(OLMC_ERR_ARG, "observation_freq must be >= 1");
     if (n_steps >= 1 && n_steps / observation_freq < 1) return fail(OLMC_ERR_ARG, "no observation date: observation_freq > n_steps");
+    return OLMC_OK;
+}
+
+struct AutocallSetup {
     AutocallContract ac;
+    double obs_rate;       // -r dt f: ln of ac.obs_df (qmc_autocall_kernel takes its redemption discount by one exponential)
+    bool bad;              // a NaN input: the result is NaN (poisoned)
+};
+AutocallSetup make_autocall(double S, double T, double r, double sigma, double q, double autocall_barrier, double coupon_barrier,
+                            double coupon_rate, double ki_barrier, int32_t observation_freq, int32_t n_steps) {
+    AutocallSetup a;
+    AutocallContract& ac = a.ac;
     const GbmStep g = gbm_step(T, n_steps, r, q, sigma);
     ac.drift = g.drift;
     ac.vol = g.vol;
@@ -1370,20 +1380,20 @@ extern "C" int olmc_autocallable(double S, double T, double r, double sigma, dou
     ac.n_obs = n_steps / observation_freq;                      // len(range(f, M + 1, f))
     ac.coupon_unit = coupon_rate * T / ac.n_obs;                // coupon_rate * ((i+1)/n_obs) * T, accrued per observation (:459-460)
     ac.final_coupon = coupon_rate * T;
-    ac.obs_df = std::exp(-r * g.dt * observation_freq);          // exp(-r t dt) at t = k f, built up by products (:461)
+    a.obs_rate = -r * g.dt * observation_freq;
+    ac.obs_df = std::exp(a.obs_rate);                           // exp(-r t dt) at t = k f, built up by products (:461)
     ac.final_df = std::exp(-r * T);
-    const bool bad = poisoned(S, 1.0, T, r, sigma, q) || std::isnan(autocall_barrier + coupon_barrier + coupon_rate + ki_barrier);
-    // payoffs are already discounted path by path (exotic_options.py:463, 489): no outer discount
-    return run_structured(path_offset, n_local, n_steps, seed, antithetic, 0.0, T, bad, out,
-                          [&](int32_t grid, hipStream_t st, const EventPair* timed, const PathRange& pr, const ReduceWs& ws) {
-                              with_bool(antithetic != 0, [&](auto a) { launch_timed(autocall_kernel<a>, dim3(grid), dim3(kBlock), st, timed, pr, ac, ws); });
-                          });
+    a.bad = poisoned(S, 1.0, T, r, sigma, q) || std::isnan(autocall_barrier + coupon_barrier + coupon_rate + ki_barrier);
+    return a;
 }
 
-extern "C" int olmc_cliquet(double S, double T, double r, double sigma, double q, double local_cap, double local_floor,
-                            double global_cap, double global_floor, int32_t n_periods, int64_t path_offset,
-                            int64_t n_local, int32_t n_steps, uint64_t seed, int antithetic, olmc_stats* out) {
+int cliquet_check(int32_t n_periods, int32_t n_steps) {
     if (n_periods < 1 || (n_steps >= 1 && n_steps / n_periods < 1)) return fail(OLMC_ERR_ARG, "n_periods must be in [1, n_steps]");
+    return OLMC_OK;
+}
+
+CliquetContract make_cliquet(double S, double T, double r, double sigma, double q, double local_cap, double local_floor, double global_cap,
+                             double global_floor, int32_t n_periods, int32_t n_steps) {
     CliquetContract cc;
     const GbmStep g = gbm_step(T, n_steps, r, q, sigma);
     cc.s0 = S;
@@ -1392,7 +1402,34 @@ extern "C" int olmc_cliquet(double S, double T, double r, double sigma, double q
     cc.local_cap = local_cap; cc.local_floor = local_floor; cc.global_cap = global_cap; cc.global_floor = global_floor;
     cc.steps_per_period = n_steps / n_periods;                  // exotic_options.py:532
     cc.n_periods = n_periods;
-    const bool bad = poisoned(S, 1.0, T, r, sigma, q) || std::isnan(local_cap + local_floor + global_cap + global_floor);
+    return cc;
+}
+
+bool cliquet_poisoned(double S, double T, double r, double sigma, double q, double local_cap, double local_floor, double global_cap, double global_floor) {
+    return poisoned(S, 1.0, T, r, sigma, q) || std::isnan(local_cap + local_floor + global_cap + global_floor);
+}
+}  // namespace
+
+extern "C" int olmc_autocallable(double S, double T, double r, double sigma, double q, double autocall_barrier,
+                                 double coupon_barrier, double coupon_rate, double ki_barrier, int32_t observation_freq,
+                                 int64_t path_offset, int64_t n_local, int32_t n_steps, uint64_t seed, int antithetic,
+                                 olmc_stats* out) {
+    if (const int rc = autocall_check(observation_freq, n_steps)) return rc;
+    const AutocallSetup a = make_autocall(S, T, r, sigma, q, autocall_barrier, coupon_barrier, coupon_rate, ki_barrier, observation_freq, n_steps);
+    const AutocallContract& ac = a.ac;
+    // payoffs are already discounted path by path (exotic_options.py:463, 489): no outer discount
+    return run_structured(path_offset, n_local, n_steps, seed, antithetic, 0.0, T, a.bad, out,
+                          [&](int32_t grid, hipStream_t st, const EventPair* timed, const PathRange& pr, const ReduceWs& ws) {
+                              with_bool(antithetic != 0, [&](auto a_) { launch_timed(autocall_kernel<a_>, dim3(grid), dim3(kBlock), st, timed, pr, ac, ws); });
+                          });
+}
+
+extern "C" int olmc_cliquet(double S, double T, double r, double sigma, double q, double local_cap, double local_floor,
+                            double global_cap, double global_floor, int32_t n_periods, int64_t path_offset,
+                            int64_t n_local, int32_t n_steps, uint64_t seed, int antithetic, olmc_stats* out) {
+    if (const int rc = cliquet_check(n_periods, n_steps)) return rc;
+    const CliquetContract cc = make_cliquet(S, T, r, sigma, q, local_cap, local_floor, global_cap, global_floor, n_periods, n_steps);
+    const bool bad = cliquet_poisoned(S, T, r, sigma, q, local_cap, local_floor, global_cap, global_floor);
     return run_structured(path_offset, n_local, n_steps, seed, antithetic, r, T, bad, out,
                           [&](int32_t grid, hipStream_t st, const EventPair* timed, const PathRange& pr, const ReduceWs& ws) {
                               with_bool(antithetic != 0, [&](auto a) { launch_timed(cliquet_kernel<a>, dim3(grid), dim3(kBlock), st, timed, pr, cc, ws); });
@@ -2003,29 +2040,40 @@ int qmc_path_setup(DeviceCtx* c, int construction, int64_t point_offset, int64_t
     return OLMC_OK;
 }
 
-// family: kQmcAsianArithmetic / kQmcAsianGeometric (payoff ignored) or kQmcExtrema (payoff = kBarrier* / kLookback*, `barrier` its level).
-int run_qmc_path(int family, int payoff, double S, double K, double T, double r, double sigma, double q, int is_call, double barrier,
-                 int construction, int64_t point_offset, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift,
-                 int32_t bits, int antithetic, olmc_stats* out) {
-    if (!out) return fail(OLMC_ERR_ARG, "null pointer");
-    int rc = qmc_path_check(construction, point_offset, n_points, n_steps, sv, shift, bits);
-    if (rc) return rc;
+// One Sobol path pricing once its arguments are checked: the lease, the tables (and the plan), launch(grid, stream, timed, pl, ws) -- the
+// payoff's kernel -- under the grid reduction, the statistics; r_for_discount as run_structured.
+template <typename Launch>
+int run_qmc_payoff(int construction, int64_t point_offset, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift,
+                   int antithetic, double r_for_discount, double T, bool poisoned_inputs, olmc_stats* out, Launch launch) {
     CtxLease lease;
-    rc = ctx_lease(&lease);
+    int rc = ctx_lease(&lease);
     if (rc) return rc;
     DeviceCtx* const c = lease.c;
     QmcPathLaunch pl;
     rc = qmc_path_setup(c, construction, point_offset, n_points, n_steps, sv, shift, antithetic, &pl);
     if (rc) return rc;
+    rc = launch_reduce(c, c->stream, c->d_result, -1.0, 2, pl.grid,
+                       [&](int32_t g, hipStream_t s, const EventPair* timed, const ReduceWs& ws) { launch(g, s, timed, pl, ws); });
+    if (rc) return rc;
+    finish_one(c->h_result, n_points * (pl.anti ? 2 : 1), r_for_discount, T, poisoned_inputs, out);
+    return OLMC_OK;
+}
+
+// family: kQmcAsianArithmetic / kQmcAsianGeometric (payoff ignored) or kQmcExtrema (payoff = kBarrier* / kLookback*, `barrier` its level).
+int run_qmc_path(int family, int payoff, double S, double K, double T, double r, double sigma, double q, int is_call, double barrier,
+                 int construction, int64_t point_offset, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift,
+                 int32_t bits, int antithetic, olmc_stats* out) {
+    if (!out) return fail(OLMC_ERR_ARG, "null pointer");
+    const int rc = qmc_path_check(construction, point_offset, n_points, n_steps, sv, shift, bits);
+    if (rc) return rc;
     const ExtremaContract ec = make_extrema(S, K, T, r, sigma, q, is_call, family == kQmcExtrema ? payoff : 0, barrier, n_steps);
-    rc = launch_reduce(c, c->stream, c->d_result, -1.0, 2, pl.grid, [&](int32_t g, hipStream_t s, const EventPair* timed, const ReduceWs& ws) {
+    const bool bad = poisoned(S, K, T, r, sigma, q) || std::isnan(barrier);
+    return run_qmc_payoff(construction, point_offset, n_points, n_steps, sv, shift, antithetic, r, T, bad, out,
+                          [&](int32_t g, hipStream_t s, const EventPair* timed, const QmcPathLaunch& pl, const ReduceWs& ws) {
         if (family == kQmcAsianArithmetic) launch_qmc_path<kQmcAsianArithmetic>(pl.bridge, pl.anti, g, s, timed, pl.qr, ec, pl.inv_steps, pl.d_sv, pl.d_shift, pl.plan, ws);
         else if (family == kQmcAsianGeometric) launch_qmc_path<kQmcAsianGeometric>(pl.bridge, pl.anti, g, s, timed, pl.qr, ec, pl.inv_steps, pl.d_sv, pl.d_shift, pl.plan, ws);
         else launch_qmc_path<kQmcExtrema>(pl.bridge, pl.anti, g, s, timed, pl.qr, ec, pl.inv_steps, pl.d_sv, pl.d_shift, pl.plan, ws);
     });
-    if (rc) return rc;
-    finish_one(c->h_result, n_points * (pl.anti ? 2 : 1), r, T, poisoned(S, K, T, r, sigma, q) || std::isnan(barrier), out);
-    return OLMC_OK;
 }
 
 // The 8 / 14 contracts of compute_greeks_unified over a Sobol-path option (ExoticAdapter, method="qmc") on points [0, n_points), ONE
@@ -2097,6 +2145,58 @@ extern "C" int olmc_extrema_qmc_greeks_fd(double S, double K, double T, double r
     if (payoff <= OLMC_BARRIER_DOWN_IN && !(barrier > 0.0)) return fail(OLMC_ERR_ARG, "Barrier must be positive");
     return run_qmc_path_greeks(kQmcExtrema, payoff, S, K, T, r, sigma, q, is_call, payoff <= OLMC_BARRIER_DOWN_IN ? barrier : 0.0, construction,
                                n_points, n_steps, sv, shift, bits, antithetic, second_order, out9, evals);
+}
+
+// The autocallable and the cliquet on the Sobol paths of run_qmc_path (include/olmc.h "quasi-Monte Carlo structured products"): the
+// contracts of olmc_autocallable / olmc_cliquet, the checks of both sides before any device work.
+namespace {
+// m with j / d == (2 j m) >> 32 for 0 <= j, d < 2^15 (qmc_date_quotient in olmc_kernels.h has the proof).
+uint32_t qmc_date_magic(int32_t d) { return static_cast<uint32_t>((uint64_t(1) << 31) / static_cast<uint64_t>(d)) + 1u; }
+}  // namespace
+
+extern "C" int olmc_autocallable_qmc(double S, double T, double r, double sigma, double q, double autocall_barrier, double coupon_barrier,
+                                     double coupon_rate, double ki_barrier, int32_t observation_freq, int construction,
+                                     int64_t point_offset, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift,
+                                     int32_t bits, int antithetic, olmc_stats* out) {
+    if (!out) return fail(OLMC_ERR_ARG, "null pointer");
+    int rc = qmc_path_check(construction, point_offset, n_points, n_steps, sv, shift, bits);
+    if (rc) return rc;
+    rc = autocall_check(observation_freq, n_steps);
+    if (rc) return rc;
+    const AutocallSetup a = make_autocall(S, T, r, sigma, q, autocall_barrier, coupon_barrier, coupon_rate, ki_barrier, observation_freq, n_steps);
+    const uint32_t magic = qmc_date_magic(observation_freq);
+    // payoffs are already discounted path by path, as olmc_autocallable's: no outer discount
+    return run_qmc_payoff(construction, point_offset, n_points, n_steps, sv, shift, antithetic, 0.0, T, a.bad, out,
+                          [&](int32_t g, hipStream_t s, const EventPair* timed, const QmcPathLaunch& pl, const ReduceWs& ws) {
+                              with_bool(pl.bridge, [&](auto b) {
+                                  with_bool(pl.anti, [&](auto m) {
+                                      launch_timed(qmc_autocall_kernel<b, m>, dim3(g), dim3(kBlock), s, timed, pl.qr, a.ac, a.obs_rate, magic, pl.d_sv,
+                                                   pl.d_shift, pl.plan, ws);
+                                  });
+                              });
+                          });
+}
+
+extern "C" int olmc_cliquet_qmc(double S, double T, double r, double sigma, double q, double local_cap, double local_floor, double global_cap,
+                                double global_floor, int32_t n_periods, int construction, int64_t point_offset, int64_t n_points,
+                                int32_t n_steps, const uint32_t* sv, const uint32_t* shift, int32_t bits, int antithetic, olmc_stats* out) {
+    if (!out) return fail(OLMC_ERR_ARG, "null pointer");
+    int rc = qmc_path_check(construction, point_offset, n_points, n_steps, sv, shift, bits);
+    if (rc) return rc;
+    rc = cliquet_check(n_periods, n_steps);
+    if (rc) return rc;
+    const CliquetContract cc = make_cliquet(S, T, r, sigma, q, local_cap, local_floor, global_cap, global_floor, n_periods, n_steps);
+    const uint32_t magic = qmc_date_magic(cc.steps_per_period);
+    const bool bad = cliquet_poisoned(S, T, r, sigma, q, local_cap, local_floor, global_cap, global_floor);
+    return run_qmc_payoff(construction, point_offset, n_points, n_steps, sv, shift, antithetic, r, T, bad, out,
+                          [&](int32_t g, hipStream_t s, const EventPair* timed, const QmcPathLaunch& pl, const ReduceWs& ws) {
+                              with_bool(pl.bridge, [&](auto b) {
+                                  with_bool(pl.anti, [&](auto m) {
+                                      launch_timed(qmc_cliquet_kernel<b, m>, dim3(g), dim3(kBlock), s, timed, pl.qr, cc, magic, pl.d_sv, pl.d_shift,
+                                                   pl.plan, ws);
+                                  });
+                              });
+                          });
 }
 
 // ================================================================ QMC path matrix ====

@@ -3216,6 +3216,153 @@ __global__ __launch_bounds__(kBlock) void qmc_path_kernel(QmcRange qr, ExtremaCo
     block_then_grid_reduce<2>(acc, ws);
 }
 
+// ---------------------------------------------- QMC path payoffs (autocallable, cliquet) ----
+// The structured products of autocall_kernel / cliquet_kernel on the Sobol paths above: one point per wave, lanes over dates, the
+// same z, constructions and ln(S_j / S) = fma(vol, W_j, j drift) as qmc_path_kernel, the mirror -z as a second leg of the same walk.
+// Both ask "is date j a multiple of d" (d = the observation frequency, the period length) of every date: d is wave-uniform and j, d <=
+// 21201 < 2^15, so j / d is one v_mul_hi_u32 by the host's m = floor(2^31 / d) + 1 (qmc_date_magic): m d = 2^31 + e with 0 < e <= d,
+// so floor(j m / 2^31) = floor(j / d + j e / (d 2^31)) = floor(j / d) as long as j e < 2^31, and j e < 2^30.  No division in the loop.
+__device__ __forceinline__ uint32_t qmc_date_quotient(int32_t j, uint32_t magic) { return __umulhi(2u * static_cast<uint32_t>(j), magic); }
+
+__device__ __forceinline__ int32_t wave_allmin_i32(int32_t v) {
+#pragma unroll
+    for (int off = 1; off < kWave; off <<= 1) v = min(v, __shfl_xor(v, off, kWave));
+    return v;
+}
+
+// The autocallable's payoff from the leg totals (wave-uniform values): first = the smallest observation index k = 1 .. n_obs whose
+// date saw ln(S_kf / S) >= log_autocall (beyond n_obs: none), mn = the path minimum of ln(S_j / S) with t = 0, y_n = ln(S_n / S).
+// obs_rate = -r dt f: the redemption discount exp(-r k f dt) is one exponential per point and leg (autocall_kernel builds it by
+// products along its step loop, where an exponential per path and date would cost).
+__device__ __forceinline__ double qmc_autocall_payoff(const AutocallContract& c, double obs_rate, int32_t first, double mn, double y_n) {
+    if (first <= c.n_obs) {
+        const double k = static_cast<double>(first);
+        return (1.0 + c.coupon_unit * k) * exp(obs_rate * k);
+    }
+    double fin = 1.0;
+    if (y_n >= c.log_coupon) fin += c.final_coupon;
+    if (mn <= c.log_ki && y_n < 0.0) fin = exp(y_n);
+    return fin * c.final_df;
+}
+
+// Autocallable (exotic_options.py:404-491) on Sobol paths.  Per date and leg: one fma, one min, one compare and a select of the
+// observation index; per date: the quotient above, a multiply and a compare.  The payoff carries its own discount.
+// Resources (tools/kernel_meta.sh, gfx950; no scratch, no spills): VGPRs 67 / 76 (sequential / bridge), 72 / 75 antithetic; LDS 64 B
+// (the reduction), + 32.8 KB with the bridge.
+template <bool BRIDGE, bool ANTI>
+__global__ __launch_bounds__(kBlock) void qmc_autocall_kernel(QmcRange qr, AutocallContract c, double obs_rate, uint32_t obs_magic,
+                                                              const uint32_t* __restrict__ sv, const uint32_t* __restrict__ shift,
+                                                              QmcBridgePlan plan, ReduceWs ws) {
+    constexpr int LEGS = ANTI ? 2 : 1;
+    constexpr int32_t kNever = 0x7fffffff;
+    const int lane = static_cast<int>(threadIdx.x) & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) / kWave);
+    const int32_t n = qr.dims;
+    const uint32_t f = static_cast<uint32_t>(c.obs_freq);
+    double acc[2] = {0.0, 0.0};
+    [[maybe_unused]] double* W = nullptr;
+    if constexpr (BRIDGE) {
+        __shared__ double w_lds[kWavesPerBlock][kQmcBridgeMaxSteps + 1];
+        W = w_lds[wave];
+    }
+    const int64_t stride = static_cast<int64_t>(gridDim.x) * kWavesPerBlock;
+    for (int64_t i = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave; i < qr.count; i += stride) {
+        const uint64_t k = qr.first + static_cast<uint64_t>(i);
+        const uint32_t gray = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(k ^ (k >> 1))));
+        double mn[LEGS];                       // t = 0: ln(S_0 / S_0) = 0 is a candidate (include/olmc.h: it cannot move a price)
+        int32_t first[LEGS];
+#pragma unroll
+        for (int leg = 0; leg < LEGS; ++leg) { mn[leg] = 0.0; first[leg] = kNever; }
+        const double w_n = qmc_point_walk<BRIDGE>(sv, shift, plan, W, n, lane, gray, [&](int32_t j, double wj) {
+            const double jd = static_cast<double>(j) * c.drift;
+            const uint32_t obs = qmc_date_quotient(j, obs_magic);                     // j / f: date j is observation `obs` when f divides j
+            const bool observed = obs * f == static_cast<uint32_t>(j);                // (obs <= n_obs = n / f then, as j <= n)
+#pragma unroll
+            for (int leg = 0; leg < LEGS; ++leg) {
+                const double y = __builtin_fma(leg ? -c.vol : c.vol, wj, jd);
+                mn[leg] = min_f64(mn[leg], y);
+                first[leg] = (observed && y >= c.log_autocall) ? min(first[leg], static_cast<int32_t>(obs)) : first[leg];
+            }
+        });
+        const double nd = static_cast<double>(n) * c.drift;
+#pragma unroll
+        for (int leg = 0; leg < LEGS; ++leg) {
+            const double x = qmc_autocall_payoff(c, obs_rate, wave_allmin_i32(first[leg]), wave_allmin(mn[leg]),
+                                                 __builtin_fma(leg ? -c.vol : c.vol, w_n, nd));
+            if (lane == 0) { acc[0] += x; acc[1] += x * x; }
+        }
+    }
+    block_then_grid_reduce<2>(acc, ws);
+}
+
+// Cliquet (exotic_options.py:494-554) on Sobol paths.  Only the reset dates p spp (spp = steps_per_period, p = 1 .. n_periods) enter:
+// period p returns exp(spp drift + vol (W_{p spp} - W_{(p-1) spp})) - 1, clipped locally, summed over the wave, clipped globally.
+//   bridge      after the fill the whole W is in the wave's LDS row, so the lanes run over PERIODS, not dates: lane l takes periods l,
+//               l + 64, ... and reads its two ends.  One exponential per leg for 64 periods; the dates in between are never read.
+//   sequential  W_j exists only in the lane of date j while its trip is live, so the walk stops at the last reset date (the
+//               trailing dimensions are never drawn) and the lane of a reset date j takes W_{j - spp} from lane l - spp of the same
+//               trip (one shuffle) when spp <= l, else from w_reset, the wave-uniform W of the last reset date of earlier trips (W_0 = 0
+//               before the first).  A trip evaluates its exponential only if it holds a reset date.
+// Resources (tools/kernel_meta.sh, gfx950; no scratch, no spills): VGPRs 67 / 86 (sequential / bridge), 52 / 66 antithetic; LDS 64 B
+// (the reduction), + 32.8 KB with the bridge.
+template <bool BRIDGE, bool ANTI>
+__global__ __launch_bounds__(kBlock) void qmc_cliquet_kernel(QmcRange qr, CliquetContract c, uint32_t period_magic,
+                                                             const uint32_t* __restrict__ sv, const uint32_t* __restrict__ shift,
+                                                             QmcBridgePlan plan, ReduceWs ws) {
+    constexpr int LEGS = ANTI ? 2 : 1;
+    const int lane = static_cast<int>(threadIdx.x) & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) / kWave);
+    const int32_t n = qr.dims, spp = c.steps_per_period;
+    [[maybe_unused]] const int32_t used = spp * c.n_periods;                  // <= n: trailing dates never enter a period
+    const double period_drift = spp * c.drift;
+    double acc[2] = {0.0, 0.0};
+    [[maybe_unused]] double* W = nullptr;
+    if constexpr (BRIDGE) {
+        __shared__ double w_lds[kWavesPerBlock][kQmcBridgeMaxSteps + 1];
+        W = w_lds[wave];
+    }
+    const int64_t stride = static_cast<int64_t>(gridDim.x) * kWavesPerBlock;
+    for (int64_t i = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave; i < qr.count; i += stride) {
+        const uint64_t k = qr.first + static_cast<uint64_t>(i);
+        const uint32_t gray = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(k ^ (k >> 1))));
+        double total[LEGS];
+#pragma unroll
+        for (int leg = 0; leg < LEGS; ++leg) total[leg] = 0.0;
+        auto add_period = [&](double dw /* W_end - W_start */) {
+#pragma unroll
+            for (int leg = 0; leg < LEGS; ++leg) {
+                const double local = exp(__builtin_fma(leg ? -c.vol : c.vol, dw, period_drift)) - 1.0;      // (S_end - S_start) / S_start
+                total[leg] += fmin(fmax(local, c.local_floor), c.local_cap);
+            }
+        };
+        if constexpr (BRIDGE) {
+            qmc_bridge_fill(sv, shift, plan, W, n, lane, gray);
+            for (int32_t p0 = 0; p0 < c.n_periods; p0 += kWave) {
+                const int32_t p = p0 + lane;                                  // period p: dates p spp .. (p + 1) spp <= used <= n
+                if (p < c.n_periods) add_period(W[(p + 1) * spp] - W[p * spp]);
+            }
+        } else {
+            double w_reset = 0.0;
+            qmc_point_walk<false>(sv, shift, plan, W, used, lane, gray, [&](int32_t j, double wj) {
+                // every lane here has j <= used, and the lanes this one reads (an earlier date of the trip) are live with it
+                const int32_t c0 = __builtin_amdgcn_readfirstlane(j - lane - 1);                            // the trip holds dates c0 + 1 .. c0 + 64
+                const double w_before = __shfl_up(wj, static_cast<unsigned int>(spp), kWave);               // W_{j - spp} where spp <= lane
+                const double w_start = lane >= spp ? w_before : w_reset;
+                if (qmc_date_quotient(j, period_magic) * static_cast<uint32_t>(spp) == static_cast<uint32_t>(j)) add_period(wj - w_start);
+                const int32_t last = static_cast<int32_t>(qmc_date_quotient(min(c0 + kWave, used), period_magic)) * spp;   // the trip's last reset date, if > c0
+                if (last > c0) w_reset = __shfl(wj, last - c0 - 1, kWave);
+            });
+        }
+#pragma unroll
+        for (int leg = 0; leg < LEGS; ++leg) {
+            const double clipped = fmin(fmax(wave_allsum(total[leg]), c.global_floor), c.global_cap);
+            const double x = fmax(clipped, 0.0) * c.s0;
+            if (lane == 0) { acc[0] += x; acc[1] += x * x; }
+        }
+    }
+    block_then_grid_reduce<2>(acc, ws);
+}
+
 // Finite-difference Greeks on Sobol paths in ONE launch: the 8 / 14 contracts of compute_greeks_unified over an Asian, barrier or
 // lookback option (ExoticAdapter, method="qmc").  As in extrema_greeks_kernel a contract enters the date loop only through its drift and
 // vol per step, so the set is at most kAsianGroups = 6 recursions ({mid, S+-}, sigma+, sigma-, T-, r+, r-; extrema_greeks_layout with

@@ -6,8 +6,9 @@ signature; the running average lives in registers, no (n_paths, n_steps) matrix
 exists.  Like the reference there is no antithetic mirror unless asked for, and
 the return value is a ``numpy.float64``.
 
-Additive: ``method="qmc"`` prices the Asian, barrier, lookback and American (LSM) options on scrambled-Sobol paths (_qmc_tables,
-include/olmc.h "quasi-Monte Carlo path payoffs" and "quasi-Monte Carlo path matrix"), by default with the Brownian-bridge construction.
+Additive: ``method="qmc"`` prices every option here (Asian, barrier, lookback, American (LSM), autocallable, cliquet) on scrambled-Sobol
+paths (_qmc_tables, include/olmc.h "quasi-Monte Carlo path payoffs", "... structured products" and "... path matrix"), by default with
+the Brownian-bridge construction.
 """
 from __future__ import annotations
 
@@ -276,13 +277,22 @@ class AutocallableOption:
     ki_barrier: float = 0.6
 
     def price(self, n_paths: int = 100000, n_steps: int = 252, observation_freq: int = 21, antithetic: bool = False,
-              return_error: bool = False, **kwargs):
+              return_error: bool = False, method: Literal["pseudo", "qmc"] = "pseudo",
+              path_construction: Literal["bridge", "sequential"] = "bridge", **kwargs):
+        """method, path_construction (additive): scrambled-Sobol paths, as AsianOption.price (the seed is the scramble seed, the
+        standard error the naive per-path one; refusals as there).  **kwargs: the ExoticAdapter's option_type, unread."""
         if n_paths < 1 or n_steps < 1:
             raise ValueError("n_paths and n_steps must be >= 1")
-        seed = self.seed if self.seed is not None else int(np.random.default_rng().integers(0, 2**31))
+        qmc = _qmc_tables(method, path_construction, n_paths, n_steps, self.seed)
         autocall_barrier = self.autocall_barrier
         if observation_freq > n_steps:                  # no observation date: nothing redeems early (exotic_options.py:442, 448)
             observation_freq, autocall_barrier = n_steps, math.inf
+        if qmc is not None:
+            sv, shift, bridge = qmc
+            st = _hip.autocallable_qmc(self.S, self.T, self.r, self.sigma, self.q, autocall_barrier, self.coupon_barrier, self.coupon_rate,
+                                       self.ki_barrier, observation_freq, n_paths, sv, shift, bridge, antithetic)
+            return (np.float64(st.price), float(st.std_error)) if return_error else np.float64(st.price)
+        seed = self.seed if self.seed is not None else int(np.random.default_rng().integers(0, 2**31))
         st = _hip.autocallable(self.S, self.T, self.r, self.sigma, self.q, autocall_barrier, self.coupon_barrier,
                                self.coupon_rate, self.ki_barrier, observation_freq, n_paths, n_steps, seed, antithetic)
         return (np.float64(st.price), float(st.std_error)) if return_error else np.float64(st.price)
@@ -305,9 +315,18 @@ class CliquetOption:
     global_floor: float = 0.0
 
     def price(self, n_paths: int = 100000, n_steps: int = 252, n_periods: int = 12, antithetic: bool = False,
-              return_error: bool = False, **kwargs):
+              return_error: bool = False, method: Literal["pseudo", "qmc"] = "pseudo",
+              path_construction: Literal["bridge", "sequential"] = "bridge", **kwargs):
+        """method, path_construction (additive): scrambled-Sobol paths, as AsianOption.price (the seed is the scramble seed, the
+        standard error the naive per-path one; refusals as there).  **kwargs: the ExoticAdapter's option_type, unread."""
         if n_paths < 1 or n_steps < 1:
             raise ValueError("n_paths and n_steps must be >= 1")
+        qmc = _qmc_tables(method, path_construction, n_paths, n_steps, self.seed)
+        if qmc is not None:
+            sv, shift, bridge = qmc
+            st = _hip.cliquet_qmc(self.S, self.T, self.r, self.sigma, self.q, self.local_cap, self.local_floor, self.global_cap,
+                                  self.global_floor, n_periods, n_paths, sv, shift, bridge, antithetic)
+            return (np.float64(st.price), float(st.std_error)) if return_error else np.float64(st.price)
         seed = self.seed if self.seed is not None else int(np.random.default_rng().integers(0, 2**31))
         st = _hip.cliquet(self.S, self.T, self.r, self.sigma, self.q, self.local_cap, self.local_floor, self.global_cap,
                           self.global_floor, n_periods, n_paths, n_steps, seed, antithetic)
