@@ -61,7 +61,8 @@ extern "C" {
                               *    later additions within v6: olmc_asian_qmc, olmc_extrema_qmc (Sobol paths for the path payoffs),
                               *    olmc_asian_qmc_greeks_fd, olmc_extrema_qmc_greeks_fd (their finite-difference Greeks in one launch),
                               *    olmc_american_lsm_qmc, olmc_exercise_boundary_qmc, olmc_gbm_qmc_paths (the American and its path matrix on Sobol paths),
-                              *    olmc_autocallable_qmc, olmc_cliquet_qmc (the structured products on Sobol paths) */
+                              *    olmc_autocallable_qmc, olmc_cliquet_qmc (the structured products on Sobol paths),
+                              *    olmc_heston_qmc, olmc_heston_qmc_paths (Heston on Sobol paths, two dimensions per step) */
 
 enum {
     OLMC_OK = 0,
@@ -491,6 +492,35 @@ int olmc_exercise_boundary_qmc(double S, double K, double T, double r, double si
                                double* boundary_host);
 int olmc_gbm_qmc_paths(double S, double T, double r, double sigma, double q, int construction, int64_t n_points, int32_t n_steps,
                        const uint32_t* sv, const uint32_t* shift, int32_t bits, int path_major, double* out_host);
+
+/* ---- quasi-Monte Carlo Heston ---------------
+ * olmc_heston / olmc_heston_paths on scrambled-Sobol points.  A step has two noise factors, so n = n_steps steps take d = 2 n
+ * dimensions: point k of scipy.stats.qmc.Sobol(d=2 n_steps, scramble=True, seed) (sv / shift / bits as olmc_european_qmc with dims = 2
+ * n_steps, so n_steps <= 10600) drives path k through z_i = Phi^-1(clip(u_i, 1e-10, 1 - 1e-10)), i = 0 .. 2 n - 1, and
+ *   OLMC_QMC_SEQUENTIAL  step t takes Z1 = z_{2t} and the independent Z2' = z_{2t+1} (the reference's draw order, heston.py:232-233);
+ *   OLMC_QMC_BRIDGE      TWO Brownian bridges W1, W2 on the breadth-first plan of the "quasi-Monte Carlo path payoffs" section for n
+ *                        dates (n <= OLMC_QMC_BRIDGE_MAX_STEPS): bridge normal k of W1 is z_{2k} and bridge normal k of W2 is z_{2k+1}, so
+ *                        dimensions 0 and 1 carry the two terminal values W1_n = sqrt(n) z_0, W2_n = sqrt(n) z_1, dimensions 2 and 3 the
+ *                        two midpoints, and so on; step t takes Z1 = W1_{t+1} - W1_t and Z2' = W2_{t+1} - W2_t (W_0 = 0).
+ * The recursion is heston.py:230-244 -- Z2 = rho Z1 + sqrt(1 - rho^2) Z2', v+ = max(v, 0), ln S += (r - q - v+/2) dt + sqrt(v+ dt) Z1,
+ * v = max(v + kappa (theta - v+) dt + sigma_v sqrt(v+ dt) Z2, 0) -- in the folded form of olmc_heston's kernel; v0 < 0 means what it
+ * means there (the first step sees v+ = 0 and is deterministic).
+ *   olmc_heston_qmc        the payoff max(+-(S_n - K), 0) of points [point_offset, point_offset + n_points): a shard of one sequence
+ *                          (olmc_combine_stats); antithetic != 0 also prices the mirrored point -z (2 n_points payoffs);
+ *                          out->price = exp(-r T) mean; out->std_error is the naive per-path one (for Sobol points not a confidence
+ *                          interval).  The bridge keeps a point's 2 n values of W in device memory the library owns: one slab per wave of
+ *                          the launch, at most 1 GiB per context, kept until olmc_shutdown.
+ *   olmc_heston_qmc_paths  spot and variance of points [0, n_points) at dates 0 .. n_steps to HOST memory, date 0 = (S, v0), layouts as
+ *                          olmc_heston_paths: the states of olmc_heston_qmc's recursion for the same tables (non-mirrored leg).
+ * A NaN input gives NaN results, as olmc_heston.  Refused (OLMC_ERR_ARG, before any device work): rho outside [-1, 1], a bad
+ * construction, the bridge beyond OLMC_QMC_BRIDGE_MAX_STEPS dates, n_steps outside [1, 10600], bits != 30, n_points outside [1, 2^30], a
+ * null pointer, path matrices over 64 GB. */
+int olmc_heston_qmc(double S, double K, double T, double r, double q, int is_call, double kappa, double theta, double sigma_v,
+                    double rho, double v0, int construction, int64_t point_offset, int64_t n_points, int32_t n_steps,
+                    const uint32_t* sv, const uint32_t* shift, int32_t bits, int antithetic, olmc_stats* out);
+int olmc_heston_qmc_paths(double S, double T, double r, double q, double kappa, double theta, double sigma_v, double rho, double v0,
+                          int construction, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift,
+                          int32_t bits, int path_major, double* spot_host, double* var_host);
 
 /* ---- multi-GPU, single process ------------------------------------------
  * n_paths split into n_gpus contiguous global path ranges (rank d = device d, [d N / P, (d + 1) N / P)).  Per list of devices the

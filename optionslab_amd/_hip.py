@@ -99,6 +99,8 @@ PROTOTYPES = {
     "olmc_gbm_qmc_paths": (_I, [_D] * 5 + [_I, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, _I, C.POINTER(_D)]),
     "olmc_jump_diffusion": (_I, _SIX + [_I, _I, _D, _D, _D, _D, _I64, _I64, _I32, _U64T, C.POINTER(Stats)]),
     "olmc_heston": (_I, [_D] * 5 + [_I] + [_D] * 5 + [_I64, _I64, _I32, _U64T, _I, C.POINTER(Stats)]),
+    "olmc_heston_qmc": (_I, [_D] * 5 + [_I] + [_D] * 5 + [_I, _I64, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, _I, C.POINTER(Stats)]),
+    "olmc_heston_qmc_paths": (_I, [_D] * 9 + [_I, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, _I, C.POINTER(_D), C.POINTER(_D)]),
     "olmc_multi_gpu_european": (_I, _SIX + [_I, _I64, _I32, _U64T, _I, _I, C.POINTER(Stats)]),
     "olmc_multi_gpu_greeks_fd": (_I, _SIX + [_I, _I64, _I32, _U64T, _I, _I, C.POINTER(_D), C.POINTER(Stats)]),
     "olmc_multi_gpu_european_cv": (_I, _SIX + [_I, _I64, _I32, _U64T, _I, _I, C.POINTER(CvMoments)]),
@@ -634,6 +636,36 @@ def heston(S, K, T, r, q, is_call: bool, kappa, theta, sigma_v, rho, v0, n_paths
     _check(lib().olmc_heston(S, K, T, r, q, int(is_call), kappa, theta, sigma_v, rho, v0, int(path_offset), int(n_paths),
                              int(n_steps), seed64(seed), int(antithetic), C.byref(out)))
     return out
+
+
+def _heston_steps(sv) -> int:
+    if sv.shape[0] % 2:
+        raise ValueError("Heston takes two Sobol dimensions per step: the tables must hold an even number of dimensions")
+    return int(sv.shape[0]) // 2
+
+
+def heston_qmc(S, K, T, r, q, is_call: bool, kappa, theta, sigma_v, rho, v0, n_points: int, sv: np.ndarray, shift: np.ndarray,
+               bridge: bool = True, antithetic: bool = False, point_offset: int = 0) -> Stats:
+    """Heston on scrambled-Sobol paths (olmc_heston_qmc): n_steps = sv.shape[0] / 2 steps, bridge or sequential construction."""
+    sv, psv, shift, psh = _sobol_args(sv, shift, point_offset, n_points)
+    n_steps = _heston_steps(sv)
+    out = Stats()
+    _check(lib().olmc_heston_qmc(S, K, T, r, q, int(is_call), kappa, theta, sigma_v, rho, v0, QMC_BRIDGE if bridge else QMC_SEQUENTIAL,
+                                 int(point_offset), int(n_points), n_steps, psv, psh, int(sv.shape[1]), int(antithetic), C.byref(out)))
+    return out
+
+
+def heston_qmc_paths(S, T, r, q, kappa, theta, sigma_v, rho, v0, n_points: int, sv: np.ndarray, shift: np.ndarray, bridge: bool = True,
+                     path_major: bool = False):
+    """Spot and variance of the Sobol paths at dates 0 .. n_steps = sv.shape[0] / 2, layouts as heston_paths (olmc_heston_qmc_paths)."""
+    sv, psv, shift, psh = _sobol_args(sv, shift, 0, n_points)
+    n_steps = _heston_steps(sv)
+    spot = _path_matrix(n_points, n_steps, path_major)
+    var = np.empty_like(spot)
+    _check(lib().olmc_heston_qmc_paths(S, T, r, q, kappa, theta, sigma_v, rho, v0, QMC_BRIDGE if bridge else QMC_SEQUENTIAL, int(n_points),
+                                       n_steps, psv, psh, int(sv.shape[1]), int(path_major), spot.ctypes.data_as(C.POINTER(C.c_double)),
+                                       var.ctypes.data_as(C.POINTER(C.c_double))))
+    return spot, var
 
 
 def multi_gpu_european(S, K, T, r, sigma, q, is_call: bool, n_paths: int, n_steps: int, seed: int, antithetic: bool,

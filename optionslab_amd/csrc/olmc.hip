@@ -118,6 +118,9 @@ struct DeviceCtx {
     void* d_bridge = nullptr;        // [n uint32 a | b << 16][3 x n doubles ca, cb, sd]
     int32_t bridge_n = 0;            // n of the plan d_bridge holds (0: none)
     std::vector<unsigned char> bridge_host;   // the plan as uploaded (kept alive for the asynchronous copy)
+    // the bridge slabs of heston_qmc_kernel: [waves of the grid][2 n][64] doubles, grown on demand (heston_slabs)
+    double* d_heston_w = nullptr;
+    size_t heston_w_bytes = 0;
     bool busy = false;                  // leased (guarded by the pool's mutex)
     // profiling
     std::vector<EventPair> ev_free, ev_pending;
@@ -176,6 +179,7 @@ void ctx_release(DeviceCtx* c) {
     if (c->h_multi) (void)hipHostFree(c->h_multi);
     if (c->d_sobol) (void)hipFree(c->d_sobol);
     if (c->d_bridge) (void)hipFree(c->d_bridge);
+    if (c->d_heston_w) (void)hipFree(c->d_heston_w);
     for (auto& sl : c->slots) {
         if (sl.block_rows) (void)hipFree(sl.block_rows);
         if (sl.group_rows) (void)hipFree(sl.group_rows);
@@ -1641,24 +1645,38 @@ HestonContract make_heston(double S, double K, double T, double r, double q, int
     hc.sign = is_call ? 1.0 : -1.0;
     return hc;
 }
+
+// The model checks every Heston entry point makes (Philox and Sobol), and the inputs that answer NaN.
+int heston_check(double rho) {
+    if (!(rho >= -1.0 && rho <= 1.0)) return fail(OLMC_ERR_ARG, "rho must be in [-1, 1]");
+    return OLMC_OK;
+}
+bool heston_poisoned(double S, double K, double T, double r, double q, double kappa, double theta, double sigma_v, double rho, double v0) {
+    return poisoned(S, K, T, r, 0.0, q) || std::isnan(kappa + theta + sigma_v + rho + v0);
+}
 }  // namespace
 
 extern "C" int olmc_heston_paths(double S, double T, double r, double q, double kappa, double theta, double sigma_v, double rho,
                                  double v0, int64_t n_paths, int32_t n_steps, uint64_t seed, int path_major, double* spot_host,
                                  double* var_host) {
     if (!spot_host || !var_host) return fail(OLMC_ERR_ARG, "null pointer");
-    if (!(rho >= -1.0 && rho <= 1.0)) return fail(OLMC_ERR_ARG, "rho must be in [-1, 1]");
+    int rc = heston_check(rho);
+    if (rc) return rc;
     const double bytes = 8.0 * static_cast<double>(n_paths) * (n_steps + 1.0);
     CtxLease lease;
-    int rc = matrix_prologue(n_paths, n_steps, 2 * bytes, "path matrices would exceed 64 GB", &lease);
+    rc = matrix_prologue(n_paths, n_steps, 2 * bytes, "path matrices would exceed 64 GB", &lease);
     if (rc) return rc;
     DeviceCtx* const c = lease.c;
     double* d_spot = static_cast<double*>(c->d_bulk);
     double* d_var = d_spot + static_cast<size_t>(n_paths) * (n_steps + 1);
     const HestonContract hc = make_heston(S, 0.0, T, r, q, 1, kappa, theta, sigma_v, rho, v0, n_steps);
     const PathRange pr = make_range(0, n_paths, n_steps, seed);
+    EventPair ep{};
+    const EventPair* timed = nullptr;                  // profiling on: the path kernel counts in olmc_kernel_time
+    rc = prof_pair(c, &ep, &timed);
+    if (rc) return rc;
     with_bool(path_major != 0, [&](auto pm) {
-        launch_timed(heston_paths_kernel<pm>, dim3(grid_for(n_paths)), dim3(kBlock), c->stream, nullptr, pr, hc, S, d_spot, d_var);
+        launch_timed(heston_paths_kernel<pm>, dim3(grid_for(n_paths)), dim3(kBlock), c->stream, timed, pr, hc, S, d_spot, d_var);
     });
     HIP_TRY(hipGetLastError());
     rc = copy_to_host(c, spot_host, d_spot, static_cast<size_t>(bytes));
@@ -1670,9 +1688,10 @@ extern "C" int olmc_heston(double S, double K, double T, double r, double q, int
                            double sigma_v, double rho, double v0, int64_t path_offset, int64_t n_local, int32_t n_steps,
                            uint64_t seed, int antithetic, olmc_stats* out) {
     if (!out) return fail(OLMC_ERR_ARG, "null pointer");
-    if (!(rho >= -1.0 && rho <= 1.0)) return fail(OLMC_ERR_ARG, "rho must be in [-1, 1]");
+    const int rc = heston_check(rho);
+    if (rc) return rc;
     const HestonContract hc = make_heston(S, K, T, r, q, is_call, kappa, theta, sigma_v, rho, v0, n_steps);
-    const bool bad = poisoned(S, K, T, r, 0.0, q) || std::isnan(kappa + theta + sigma_v + rho + v0);
+    const bool bad = heston_poisoned(S, K, T, r, q, kappa, theta, sigma_v, rho, v0);
     return run_structured(path_offset, n_local, n_steps, seed, antithetic, r, T, bad, out,
                           [&](int32_t grid, hipStream_t st, const EventPair* timed, const PathRange& pr, const ReduceWs& ws) {
                               with_bool(antithetic != 0, [&](auto a) { launch_timed(heston_kernel<a>, dim3(grid), dim3(kBlock), st, timed, pr, hc, ws); });
@@ -1999,13 +2018,17 @@ void launch_qmc_path_greeks(bool bridge, bool anti, int nsets, int32_t grid, hip
 // Workgroups of a QMC path launch: four points in flight per workgroup, grid-striding beyond kQmcPathMaxGrid.
 constexpr int64_t kQmcPathMaxGrid = 8192;
 
-// The argument checks of a Sobol path call, before any context is leased.
-int qmc_path_check(int construction, int64_t point_offset, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift, int32_t bits) {
+// The argument checks of a Sobol path call, before any context is leased.  A step takes dims_per_step dimensions of the table (1: the GBM
+// paths, 2: Heston's two factors).
+int qmc_path_check(int construction, int64_t point_offset, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift, int32_t bits,
+                   int32_t dims_per_step = 1) {
     if (construction != OLMC_QMC_SEQUENTIAL && construction != OLMC_QMC_BRIDGE) return fail(OLMC_ERR_ARG, "bad construction");
     if (construction == OLMC_QMC_BRIDGE && n_steps > OLMC_QMC_BRIDGE_MAX_STEPS)
         return fail(OLMC_ERR_ARG, "the Brownian-bridge construction takes at most OLMC_QMC_BRIDGE_MAX_STEPS (1024) dates");
     static_assert(OLMC_QMC_BRIDGE_MAX_STEPS == kQmcBridgeMaxSteps, "the header's cap is the kernel's LDS size");
-    return qmc_check(sv, shift, bits, n_steps, point_offset, n_points);
+    if (dims_per_step == 2 && (n_steps < 1 || n_steps > 10600))
+        return fail(OLMC_ERR_ARG, "n_steps must be in [1, 10600]: a step takes two of the 21201 Sobol dimensions");
+    return qmc_check(sv, shift, bits, n_steps * dims_per_step, point_offset, n_points);
 }
 
 // A Sobol path launch on a context the caller holds: the tables (and the bridge plan) on its device, the points, the grid.
@@ -2017,13 +2040,15 @@ struct QmcPathLaunch {
     int32_t grid;
     bool bridge, anti;
     double inv_steps;
+    double* slabs = nullptr;     // heston_qmc_kernel's bridge slabs (heston_slabs)
 };
 int qmc_path_setup(DeviceCtx* c, int construction, int64_t point_offset, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift,
-                   int antithetic, QmcPathLaunch* pl) {
-    int rc = qmc_table(c, sv, shift, n_steps);
+                   int antithetic, QmcPathLaunch* pl, int32_t dims_per_step = 1) {
+    const int32_t dims = n_steps * dims_per_step;                        // the table's; the plan and qr.dims count steps
+    int rc = qmc_table(c, sv, shift, dims);
     if (rc) return rc;
     pl->d_sv = c->d_sobol;
-    pl->d_shift = pl->d_sv + static_cast<size_t>(n_steps) * kSobolBits;
+    pl->d_shift = pl->d_sv + static_cast<size_t>(dims) * kSobolBits;
     pl->plan = QmcBridgePlan{nullptr, nullptr};
     pl->bridge = construction == OLMC_QMC_BRIDGE;
     if (pl->bridge) {
@@ -2041,22 +2066,32 @@ int qmc_path_setup(DeviceCtx* c, int construction, int64_t point_offset, int64_t
 }
 
 // One Sobol path pricing once its arguments are checked: the lease, the tables (and the plan), launch(grid, stream, timed, pl, ws) -- the
-// payoff's kernel -- under the grid reduction, the statistics; r_for_discount as run_structured.
-template <typename Launch>
+// payoff's kernel -- under the grid reduction, the statistics; r_for_discount as run_structured.  shape(c, &pl) may give the launch a
+// grid of its own and reserve what it needs on the context.
+template <typename Launch, typename Shape>
 int run_qmc_payoff(int construction, int64_t point_offset, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift,
-                   int antithetic, double r_for_discount, double T, bool poisoned_inputs, olmc_stats* out, Launch launch) {
+                   int antithetic, double r_for_discount, double T, bool poisoned_inputs, olmc_stats* out, Launch launch, int32_t dims_per_step,
+                   Shape shape) {
     CtxLease lease;
     int rc = ctx_lease(&lease);
     if (rc) return rc;
     DeviceCtx* const c = lease.c;
     QmcPathLaunch pl;
-    rc = qmc_path_setup(c, construction, point_offset, n_points, n_steps, sv, shift, antithetic, &pl);
+    rc = qmc_path_setup(c, construction, point_offset, n_points, n_steps, sv, shift, antithetic, &pl, dims_per_step);
+    if (rc) return rc;
+    rc = shape(c, &pl);
     if (rc) return rc;
     rc = launch_reduce(c, c->stream, c->d_result, -1.0, 2, pl.grid,
                        [&](int32_t g, hipStream_t s, const EventPair* timed, const ReduceWs& ws) { launch(g, s, timed, pl, ws); });
     if (rc) return rc;
     finish_one(c->h_result, n_points * (pl.anti ? 2 : 1), r_for_discount, T, poisoned_inputs, out);
     return OLMC_OK;
+}
+template <typename Launch>
+int run_qmc_payoff(int construction, int64_t point_offset, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift,
+                   int antithetic, double r_for_discount, double T, bool poisoned_inputs, olmc_stats* out, Launch launch) {
+    return run_qmc_payoff(construction, point_offset, n_points, n_steps, sv, shift, antithetic, r_for_discount, T, poisoned_inputs, out, launch, 1,
+                          [](DeviceCtx*, QmcPathLaunch*) { return OLMC_OK; });
 }
 
 // family: kQmcAsianArithmetic / kQmcAsianGeometric (payoff ignored) or kQmcExtrema (payoff = kBarrier* / kLookback*, `barrier` its level).
@@ -2204,9 +2239,14 @@ namespace {
 // The argument checks and the lease of a Sobol path-matrix call: qmc_path_check, then matrix_prologue with the call's `bytes` (reserved
 // when `reserve`) -- every refusal before any device work.
 int qmc_matrix_prologue(int construction, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift, int32_t bits,
-                        double bytes, CtxLease* lease, bool reserve = true) {
-    const int rc = qmc_path_check(construction, 0, n_points, n_steps, sv, shift, bits);
+                        double bytes, CtxLease* lease, bool reserve = true, int32_t dims_per_step = 1) {
+    const int rc = qmc_path_check(construction, 0, n_points, n_steps, sv, shift, bits, dims_per_step);
     return rc ? rc : matrix_prologue(n_points, n_steps, bytes, "path matrix would exceed 64 GB: lower n_paths or n_steps", lease, reserve);
+}
+
+// Workgroups of a lanes-over-points launch: one wave per aligned block of 64 points, grid-striding beyond kQmcPathMaxGrid.
+int32_t qmc_block_grid(int64_t blocks) {
+    return static_cast<int32_t>(std::min<int64_t>((blocks + kWavesPerBlock - 1) / kWavesPerBlock, kQmcPathMaxGrid));
 }
 
 // Sobol points [0, n_points) as the path matrix d_paths (lsm_qmc_paths_kernel), queued on c's stream behind the tables and the plan.
@@ -2215,8 +2255,7 @@ int qmc_matrix(DeviceCtx* c, int construction, int64_t n_points, int32_t n_steps
     QmcPathLaunch pl;
     const int rc = qmc_path_setup(c, construction, 0, n_points, n_steps, sv, shift, 0, &pl);
     if (rc) return rc;
-    const int64_t blocks = (n_points + kWave - 1) / kWave;               // one wave per 64 points, grid-striding beyond kQmcPathMaxGrid
-    const int32_t grid = static_cast<int32_t>(std::min<int64_t>((blocks + kWavesPerBlock - 1) / kWavesPerBlock, kQmcPathMaxGrid));
+    const int32_t grid = qmc_block_grid((n_points + kWave - 1) / kWave);
     with_bool(pl.bridge, [&](auto b) {
         with_bool(path_major, [&](auto pm) {
             launch_timed(lsm_qmc_paths_kernel<b, pm>, dim3(grid), dim3(kBlock), c->stream, nullptr, pl.qr, lc, pl.d_sv, pl.d_shift, pl.plan, d_paths);
@@ -2288,6 +2327,99 @@ extern "C" int olmc_gbm_qmc_paths(double S, double T, double r, double sigma, do
     rc = qmc_matrix(c, construction, n_points, n_steps, sv, shift, lc, path_major != 0, static_cast<double*>(c->d_bulk));
     if (rc) return rc;
     return copy_to_host(c, out_host, c->d_bulk, static_cast<size_t>(bytes));
+}
+
+// ================================================================ Heston on Sobol paths ====
+// olmc_heston / olmc_heston_paths on scrambled-Sobol points (include/olmc.h "quasi-Monte Carlo Heston"): their contract and model
+// checks, the table / construction / point-range checks of the other Sobol path calls with two dimensions per step.
+namespace {
+// The bridge slabs of heston_qmc_kernel on c: one [2 n][64] slab per RESIDENT wave.  The grid is cut to the workgroups the device holds
+// at once (kHestonBridgeBlocksPerCu per CU = two waves per SIMD, of the four its 109-117 VGPRs allow) and strides over the blocks beyond, and
+// the slabs of a launch stay under kHestonSlabCap (the grid shrinks further): the buffer follows the device and n, not the number of
+// points -- 0.5 GiB at 252 steps and 1 GiB from 504 steps on with 256 CUs, kept with the context.
+constexpr size_t kHestonSlabCap = size_t(1) << 30;
+constexpr int32_t kHestonBridgeBlocksPerCu = 2;
+int heston_slabs(DeviceCtx* c, int32_t n_steps, int32_t* grid) {
+    const size_t slab = 2 * static_cast<size_t>(n_steps) * kWave * sizeof(double);          // <= 1 MiB (n <= 1024)
+    const int32_t fit = static_cast<int32_t>(std::max<size_t>(kHestonSlabCap / (slab * kWavesPerBlock), 1));
+    *grid = std::min(*grid, std::min(fit, std::max(c->cus, 1) * kHestonBridgeBlocksPerCu));
+    const size_t bytes = slab * kWavesPerBlock * static_cast<size_t>(*grid);
+    if (bytes <= c->heston_w_bytes) return OLMC_OK;
+    if (c->d_heston_w) {
+        HIP_TRY(hipStreamSynchronize(c->stream));                // a launch may still walk the old slabs
+        HIP_TRY(hipFree(c->d_heston_w));
+        c->d_heston_w = nullptr;
+        c->heston_w_bytes = 0;
+    }
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_heston_w), bytes));
+    c->heston_w_bytes = bytes;
+    return OLMC_OK;
+}
+}  // namespace
+
+extern "C" int olmc_heston_qmc(double S, double K, double T, double r, double q, int is_call, double kappa, double theta, double sigma_v,
+                               double rho, double v0, int construction, int64_t point_offset, int64_t n_points, int32_t n_steps,
+                               const uint32_t* sv, const uint32_t* shift, int32_t bits, int antithetic, olmc_stats* out) {
+    if (!out) return fail(OLMC_ERR_ARG, "null pointer");
+    int rc = heston_check(rho);
+    if (rc) return rc;
+    rc = qmc_path_check(construction, point_offset, n_points, n_steps, sv, shift, bits, 2);
+    if (rc) return rc;
+    const HestonContract hc = make_heston(S, K, T, r, q, is_call, kappa, theta, sigma_v, rho, v0, n_steps);
+    const bool bad = heston_poisoned(S, K, T, r, q, kappa, theta, sigma_v, rho, v0);
+    return run_qmc_payoff(construction, point_offset, n_points, n_steps, sv, shift, antithetic, r, T, bad, out,
+                          [&](int32_t g, hipStream_t s, const EventPair* timed, const QmcPathLaunch& pl, const ReduceWs& ws) {
+                              with_bool(pl.bridge, [&](auto b) {
+                                  with_bool(pl.anti, [&](auto m) {
+                                      launch_timed(heston_qmc_kernel<b, m>, dim3(g), dim3(kBlock), s, timed, pl.qr, hc, pl.d_sv, pl.d_shift, pl.plan,
+                                                   pl.slabs, ws);
+                                  });
+                              });
+                          },
+                          2, [&](DeviceCtx* c, QmcPathLaunch* pl) {
+                              // the kernel's blocks are aligned in the absolute point index
+                              const int64_t first_block = point_offset / kWave, last_block = (point_offset + n_points - 1) / kWave;
+                              pl->grid = qmc_block_grid(last_block - first_block + 1);
+                              pl->slabs = nullptr;
+                              if (!pl->bridge) return static_cast<int>(OLMC_OK);
+                              const int rc2 = heston_slabs(c, n_steps, &pl->grid);
+                              pl->slabs = c->d_heston_w;
+                              return rc2;
+                          });
+}
+
+extern "C" int olmc_heston_qmc_paths(double S, double T, double r, double q, double kappa, double theta, double sigma_v, double rho, double v0,
+                                     int construction, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift,
+                                     int32_t bits, int path_major, double* spot_host, double* var_host) {
+    if (!spot_host || !var_host) return fail(OLMC_ERR_ARG, "null pointer");
+    int rc = heston_check(rho);
+    if (rc) return rc;
+    const double bytes = 8.0 * static_cast<double>(n_points) * (n_steps + 1.0);
+    CtxLease lease;
+    rc = qmc_matrix_prologue(construction, n_points, n_steps, sv, shift, bits, 2 * bytes, &lease, true, 2);
+    if (rc) return rc;
+    DeviceCtx* const c = lease.c;
+    double* d_spot = static_cast<double*>(c->d_bulk);
+    double* d_var = d_spot + static_cast<size_t>(n_points) * (n_steps + 1);
+    const HestonContract hc = make_heston(S, 0.0, T, r, q, 1, kappa, theta, sigma_v, rho, v0, n_steps);
+    QmcPathLaunch pl;
+    rc = qmc_path_setup(c, construction, 0, n_points, n_steps, sv, shift, 0, &pl, 2);
+    if (rc) return rc;
+    const int32_t grid = qmc_block_grid((n_points + kWave - 1) / kWave);
+    EventPair ep{};
+    const EventPair* timed = nullptr;                  // profiling on: the path kernel counts in olmc_kernel_time, as olmc_heston_paths'
+    rc = prof_pair(c, &ep, &timed);
+    if (rc) return rc;
+    with_bool(pl.bridge, [&](auto b) {
+        with_bool(path_major != 0, [&](auto pm) {
+            launch_timed(heston_qmc_paths_kernel<b, pm>, dim3(grid), dim3(kBlock), c->stream, timed, pl.qr, hc, S, pl.d_sv, pl.d_shift, pl.plan,
+                         d_spot, d_var);
+        });
+    });
+    HIP_TRY(hipGetLastError());
+    rc = copy_to_host(c, spot_host, d_spot, static_cast<size_t>(bytes));
+    if (rc) return rc;
+    return copy_to_host(c, var_host, d_var, static_cast<size_t>(bytes));
 }
 
 namespace {

@@ -2198,9 +2198,10 @@ __device__ __forceinline__ double sqrt_nonneg(double x) {
 struct HestonStep {
     double neg_half_dt, one_minus_kdt, kdt_theta;
     double zs, a, b;                 // RAW normal -> u = zs z1;  w = a z1 + b z2
-    __device__ __forceinline__ explicit HestonStep(const HestonContract& c)
+    // z_unit: what one unit of the normals handed to u / w is worth (kZScale for the RAW Philox normals, 1 for the Sobol kernels' true ones)
+    __device__ __forceinline__ explicit HestonStep(const HestonContract& c, double z_unit = kZScale)
         : neg_half_dt(-0.5 * c.dt), one_minus_kdt(1.0 - c.kappa_dt), kdt_theta(c.kappa_dt * c.theta),
-          zs(kZScale * c.sqrt_dt), a(c.sigma_v * c.rho * (kZScale * c.sqrt_dt)), b(c.sigma_v * c.rho_c * (kZScale * c.sqrt_dt)) {}
+          zs(z_unit * c.sqrt_dt), a(c.sigma_v * c.rho * (z_unit * c.sqrt_dt)), b(c.sigma_v * c.rho_c * (z_unit * c.sqrt_dt)) {}
     // SIGN = +1 / -1: the antithetic leg flips both normals (free source modifiers)
     template <int SIGN>
     __device__ __forceinline__ void advance(double u, double w, double& ls, double& v) const {
@@ -3553,6 +3554,201 @@ __global__ __launch_bounds__(kBlock) void lsm_qmc_paths_kernel(QmcRange qr, LsmC
                 }
             }
         }
+    }
+}
+
+// ------------------------------------------------------------------ Heston on Sobol paths ----
+// heston_kernel / heston_paths_kernel on scrambled-Sobol points (include/olmc.h "quasi-Monte Carlo Heston"): point k of
+// scipy.stats.qmc.Sobol(d = 2 n, scramble=True, seed) drives one path of n steps through the inverse normal of the other Sobol
+// kernels and HestonStep's folded recursion with TRUE normals (z_unit = 1).
+//   SEQUENTIAL  dimension 2 t is Z1 of step t and dimension 2 t + 1 its independent Z2' (the reference's draw order).
+//   BRIDGE      two Brownian bridges W1, W2 on the breadth-first plan for n dates: node k of W1 takes dimension 2 k, node k of W2
+//               dimension 2 k + 1 (the two terminal values sit on dimensions 0 and 1); step t then takes Z1 = W1_{t+1} - W1_t and
+//               Z2' = W2_{t+1} - W2_t.
+// LANES OVER POINTS, as lsm_qmc_paths_kernel: the variance recursion is serial in time, so a lane keeps (ln S, v) of its point (and
+// of the mirror -z) in fp64 registers and the wave walks the 2 n dimensions together -- one fold of the block's common Gray bits per
+// 64 dimensions (32 steps), then per dimension a broadcast plus the lane's six low rows, two inverse normals per step.  Blocks are
+// aligned in the ABSOLUTE point index, so a shard [first, first + count) that starts anywhere shares the high Gray bits per wave;
+// lanes outside the shard fold and broadcast with the others, touch no memory and add nothing.
+// The bridge needs all 2 n normals of a point before step 0: the nodes fill W1_j, W2_j (j = 1 .. n; W_0 = 0 is not stored) in plan
+// order into memory the lane owns, reading back its own earlier stores, and a sweep then reads W_{t+1} four dates at a time.
+//   heston_qmc_paths_kernel  fills them in place in the two output matrices; the sweep reads a batch of W before it stores (S, v) there.
+//   heston_qmc_kernel        fills a library-owned slab of [2 n][64] doubles per wave of the GRID (time-major: a date is 512 contiguous
+//                            bytes), reused by every block the wave strides over; the mirror leg reads the same W (-z gives -W).
+// The sequential price kernel reads nothing but the tables and stores nothing but the reduction.
+constexpr int kHestonQmcBatch = 4;       // dates whose W the sweep has in flight
+
+// A lane's point in an aligned block of 64: the Gray bits every lane shares, and masks of its own six low ones.
+struct QmcLanePoint {
+    uint32_t gray_hi;
+    uint32_t mask[6];
+    __device__ __forceinline__ explicit QmcLanePoint(uint32_t k /* < 2^30 + 64 */) {
+        const uint32_t gray = k ^ (k >> 1);
+        gray_hi = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(gray))) & ~63u;
+#pragma unroll
+        for (int b = 0; b < 6; ++b) mask[b] = 0u - ((gray >> b) & 1u);
+    }
+};
+
+// body(t, z_{2t}, z_{2t+1}) for t = 0 .. n - 1 in every lane: the two normals of step t (sequential) / of node t (bridge).
+template <typename Body>
+__device__ __forceinline__ void heston_qmc_normals(const uint32_t* __restrict__ sv, const uint32_t* __restrict__ shift, int32_t n, int lane,
+                                                   const QmcLanePoint& lp, Body body) {
+    const int32_t dims = 2 * n;
+    for (int32_t c0 = 0; c0 < dims; c0 += kWave) {
+        const int32_t tl = c0 + lane < dims ? c0 + lane : dims - 1;
+        const uint32_t* __restrict__ mine = sv + static_cast<size_t>(tl) * kSobolBits;
+        uint32_t fold = shift[tl];
+#pragma unroll
+        for (int b = 6; b < kSobolBits; ++b) fold ^= mine[b] & (0u - ((lp.gray_hi >> b) & 1u));
+        const int32_t cn = dims - c0 < kWave ? dims - c0 : kWave;            // even: dims and kWave are
+        for (int32_t d = 0; d < cn; d += 2) {
+            double z[2];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const uint32_t* __restrict__ row = sv + static_cast<size_t>(c0 + d + h) * kSobolBits;
+                uint32_t x = static_cast<uint32_t>(__shfl(static_cast<int>(fold), d + h, kWave));
+#pragma unroll
+                for (int b = 0; b < 6; ++b) x = __builtin_amdgcn_bitop3_b32(x, row[b], lp.mask[b], 0x78);   // x ^ (row & mask)
+                z[h] = ndtri_w_add(0.0, sobol_uniform(x), opaque_zero());
+            }
+            body((c0 + d) >> 1, z[0], z[1]);
+        }
+    }
+}
+
+// W1_j, W2_j (j = 1 .. n) of the lane's point at w1[at(j)], w2[at(j)], in plan order (the plan's a, b, m and coefficients are
+// wave-uniform); every lane walks the dimensions, only `live` ones touch memory.
+template <typename At>
+__device__ __forceinline__ void heston_qmc_bridge_fill(const uint32_t* __restrict__ sv, const uint32_t* __restrict__ shift, const QmcBridgePlan& plan,
+                                                       int32_t n, int lane, const QmcLanePoint& lp, bool live, double* w1, double* w2, At at) {
+    heston_qmc_normals(sv, shift, n, lane, lp, [&](int32_t k, double z1, double z2) {
+        if (k == 0) {
+            const double sq = sqrt(static_cast<double>(n));
+            if (live) { w1[at(n)] = sq * z1; w2[at(n)] = sq * z2; }
+        } else {
+            const uint32_t ab = plan.ab[k];
+            const int32_t a = static_cast<int32_t>(ab & 0xffffu), b = static_cast<int32_t>(ab >> 16), m = (a + b) >> 1;
+            const double ca = plan.coef[k], cb = plan.coef[n + k], sd = plan.coef[2 * n + k];
+            if (live) {
+                const double a1 = a == 0 ? 0.0 : w1[at(a)], a2 = a == 0 ? 0.0 : w2[at(a)];
+                const double b1 = w1[at(b)], b2 = w2[at(b)];
+                w1[at(m)] = __builtin_fma(ca, a1, __builtin_fma(cb, b1, sd * z1));
+                w2[at(m)] = __builtin_fma(ca, a2, __builtin_fma(cb, b2, sd * z2));
+            }
+        }
+    });
+}
+
+// step(t, W1_{t+1} - W1_t, W2_{t+1} - W2_t) for t = 0 .. n - 1: a batch of W is read before its steps run, so step may overwrite
+// w1[at(t + 1)] and w2[at(t + 1)].
+template <typename At, typename Step>
+__device__ __forceinline__ void heston_qmc_bridge_sweep(int32_t n, const double* w1, const double* w2, At at, Step step) {
+    double p1 = 0.0, p2 = 0.0;
+    for (int32_t t0 = 0; t0 < n; t0 += kHestonQmcBatch) {
+        double q1[kHestonQmcBatch], q2[kHestonQmcBatch];
+#pragma unroll
+        for (int j = 0; j < kHestonQmcBatch; ++j) {
+            const int32_t jj = t0 + j + 1 <= n ? t0 + j + 1 : n;
+            q1[j] = w1[at(jj)];
+            q2[j] = w2[at(jj)];
+        }
+#pragma unroll
+        for (int j = 0; j < kHestonQmcBatch; ++j) {
+            if (t0 + j < n) {
+                step(t0 + j, q1[j] - p1, q2[j] - p2);
+                p1 = q1[j]; p2 = q2[j];
+            }
+        }
+    }
+}
+
+// Resources (tools/kernel_meta.sh, gfx950; no scratch, no spills): VGPRs 88 / 78 (sequential: plain / antithetic), 117 / 109 (bridge); LDS
+// 64 B (the reduction); the bridge's slabs are global memory of the library (olmc.hip: heston_slabs).
+template <bool BRIDGE, bool ANTI>
+__global__ __launch_bounds__(kBlock) void heston_qmc_kernel(QmcRange qr, HestonContract c, const uint32_t* __restrict__ sv,
+                                                            const uint32_t* __restrict__ shift, QmcBridgePlan plan, double* slabs, ReduceWs ws) {
+    const int lane = static_cast<int>(threadIdx.x) & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) / kWave);
+    const int32_t n = qr.dims;                                               // steps: the tables hold 2 n dimensions
+    const HestonStep hs(c, 1.0);
+    double v_start;
+    const bool skip0 = heston_start(c, v_start);
+    const double ls_start = c.log_s0 + n * c.mu_dt;                          // the drift (r - q) dt of every step, once
+    const uint64_t base = qr.first & ~static_cast<uint64_t>(kWave - 1);      // blocks aligned in the absolute index
+    const uint64_t end = qr.first + static_cast<uint64_t>(qr.count);
+    const int64_t n_blocks = static_cast<int64_t>((end - base + kWave - 1) / kWave);
+    const int64_t stride = static_cast<int64_t>(gridDim.x) * kWavesPerBlock;
+    const int64_t slot = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave;
+    double acc[2] = {0.0, 0.0};
+    for (int64_t blk = slot; blk < n_blocks; blk += stride) {
+        const uint64_t k = base + static_cast<uint64_t>(blk) * kWave + lane;
+        const bool live = k >= qr.first && k < end;
+        const QmcLanePoint lp(static_cast<uint32_t>(k));
+        double ls[2] = {ls_start, ls_start}, v[2] = {v_start, v_start};
+        auto step = [&](int32_t t, double z1, double z2) {
+            if (skip0 && t == 0) return;
+            const double u = hs.zs * z1;
+            const double w = __builtin_fma(hs.b, z2, hs.a * z1);
+            hs.advance<1>(u, w, ls[0], v[0]);
+            if constexpr (ANTI) hs.advance<-1>(u, w, ls[1], v[1]);
+        };
+        if constexpr (BRIDGE) {
+            double* w1 = slabs + static_cast<size_t>(slot) * (2 * static_cast<size_t>(n) * kWave);
+            double* w2 = w1 + static_cast<size_t>(n) * kWave;
+            auto at = [&](int32_t j) { return static_cast<size_t>(j - 1) * kWave + lane; };
+            heston_qmc_bridge_fill(sv, shift, plan, n, lane, lp, live, w1, w2, at);
+            if (live) heston_qmc_bridge_sweep(n, w1, w2, at, step);
+        } else {
+            heston_qmc_normals(sv, shift, n, lane, lp, step);
+        }
+        if (live) {
+#pragma unroll
+            for (int leg = 0; leg < (ANTI ? 2 : 1); ++leg) {
+                const double x = fmax(c.sign * (exp(ls[leg]) - c.strike), 0.0);
+                acc[0] += x; acc[1] += x * x;
+            }
+        }
+    }
+    block_then_grid_reduce<2>(acc, ws);
+}
+
+// Spot and variance of points [0, count) at dates 0 .. n (layouts: path_at), date 0 = (S, v0) as given, as heston_paths_kernel.
+// Resources (tools/kernel_meta.sh, gfx950; no scratch, no spills, no LDS): VGPRs 82 / 94 (sequential: time-major / path-major), 115 / 101
+// (bridge).
+template <bool BRIDGE, bool PATH_MAJOR>
+__global__ __launch_bounds__(kBlock) void heston_qmc_paths_kernel(QmcRange qr, HestonContract c, double s_first, const uint32_t* __restrict__ sv,
+                                                                  const uint32_t* __restrict__ shift, QmcBridgePlan plan, double* spot, double* var) {
+    const int lane = static_cast<int>(threadIdx.x) & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) / kWave);
+    const int32_t n = qr.dims;
+    const int64_t count = qr.count;
+    const HestonStep hs(c, 1.0);
+    double v_start;
+    const bool skip0 = heston_start(c, v_start);
+    const int64_t n_blocks = (count + kWave - 1) / kWave;
+    const int64_t stride = static_cast<int64_t>(gridDim.x) * kWavesPerBlock;
+    for (int64_t blk = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave; blk < n_blocks; blk += stride) {
+        const int64_t i = blk * kWave + lane;
+        const bool live = i < count;
+        const QmcLanePoint lp(static_cast<uint32_t>(i));
+        auto at = [&](int32_t t) { return path_at<PATH_MAJOR>(i, t, count, n); };
+        double ls = c.log_s0, v = v_start;                                   // ls WITHOUT the (r - q) dt terms: added per date below
+        auto step = [&](int32_t t, double z1, double z2) {
+            if (!(skip0 && t == 0)) hs.advance<1>(hs.zs * z1, __builtin_fma(hs.b, z2, hs.a * z1), ls, v);
+            if (live) {
+                const size_t p = at(t + 1);
+                spot[p] = exp(__builtin_fma(static_cast<double>(t + 1), c.mu_dt, ls));
+                var[p] = v;
+            }
+        };
+        if constexpr (BRIDGE) {
+            heston_qmc_bridge_fill(sv, shift, plan, n, lane, lp, live, spot, var, at);
+            if (live) heston_qmc_bridge_sweep(n, spot, var, at, step);
+        } else {
+            heston_qmc_normals(sv, shift, n, lane, lp, step);
+        }
+        if (live) { spot[at(0)] = s_first; var[at(0)] = c.v0; }
     }
 }
 

@@ -28,8 +28,9 @@ def _qmc_precision(method: str, precision: str) -> None:
         raise ValueError("method='qmc' prices in fp64 only")
 
 
-def _qmc_tables(method: str, path_construction: str, n_paths: int, n_steps: int, seed: Optional[int]):
-    """(sv, shift, bridge) for method="qmc", None for "pseudo"; every refusal is a ValueError raised before the device is touched."""
+def _qmc_tables(method: str, path_construction: str, n_paths: int, n_steps: int, seed: Optional[int], dims_per_step: int = 1):
+    """(sv, shift, bridge) for method="qmc", None for "pseudo"; every refusal is a ValueError raised before the device is touched.
+    dims_per_step: the Sobol dimensions one step takes (2 for Heston's two factors): the tables hold n_steps * dims_per_step."""
     if method not in ("pseudo", "qmc"):
         raise ValueError("method must be 'pseudo' or 'qmc'")
     if path_construction not in ("bridge", "sequential"):
@@ -38,15 +39,16 @@ def _qmc_tables(method: str, path_construction: str, n_paths: int, n_steps: int,
         return None
     from .monte_carlo import SOBOL_MAX_DIM, sobol_tables
 
-    if n_steps > SOBOL_MAX_DIM:
-        raise ValueError(f"method='qmc' takes at most {SOBOL_MAX_DIM} steps (Sobol dimensions)")
+    if n_steps > SOBOL_MAX_DIM // dims_per_step:
+        what = "Sobol dimensions" if dims_per_step == 1 else f"{dims_per_step} Sobol dimensions per step"
+        raise ValueError(f"method='qmc' takes at most {SOBOL_MAX_DIM // dims_per_step} steps ({what})")
     bridge = path_construction == "bridge"
     if bridge and n_steps > _hip.QMC_BRIDGE_MAX_STEPS:
         raise ValueError(f"path_construction='bridge' takes at most {_hip.QMC_BRIDGE_MAX_STEPS} steps; use 'sequential'")
     if n_paths > 1 << 30:
         raise ValueError("method='qmc' takes at most 2**30 paths (Sobol points)")
     seed = seed if seed is not None else int(np.random.default_rng().integers(0, 2**31))
-    sv, shift = sobol_tables(n_steps, seed, n_paths)
+    sv, shift = sobol_tables(n_steps * dims_per_step, seed, n_paths)
     return sv, shift, bridge
 
 

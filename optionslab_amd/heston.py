@@ -4,6 +4,9 @@
 (ln S, v) in fp64 registers.  `price_european` (:131-182) is the reference's semi-analytic
 Lewis/Gatheral quadrature -- scalar host arithmetic, kept so `HestonAdapter`-style callers and
 accuracy checks have the same oracle the reference has; it is not a Monte Carlo path.
+
+Additive: ``method="qmc"`` runs `price_monte_carlo` and `simulate_paths` on scrambled-Sobol points, two dimensions per step
+(_qmc_tables below, include/olmc.h "quasi-Monte Carlo Heston"), by default with two Brownian bridges.
 """
 from __future__ import annotations
 
@@ -14,6 +17,13 @@ from typing import Tuple, Literal, Optional
 import numpy as np
 
 from . import _hip
+
+
+def _qmc_tables(method: str, path_construction: str, n_paths: int, n_steps: int, seed: Optional[int]):
+    """exotic._qmc_tables with two Sobol dimensions per step: tables of Sobol(d=2 n_steps), at most 10600 steps."""
+    from .exotic import _qmc_tables as tables
+
+    return tables(method, path_construction, n_paths, n_steps, seed, dims_per_step=2)
 
 
 @dataclass
@@ -73,9 +83,26 @@ class HestonPricer:
 
     def price_monte_carlo(self, S: float, K: float, T: float, r: float, q: float = 0.0,
                           option_type: Literal["call", "put"] = "call", n_paths: int = 100000, n_steps: int = 252,
-                          seed: Optional[int] = None, antithetic: bool = False, return_error: bool = False):
+                          seed: Optional[int] = None, antithetic: bool = False, return_error: bool = False, *,
+                          method: Literal["pseudo", "qmc"] = "pseudo", path_construction: Literal["bridge", "sequential"] = "bridge"):
+        """method (additive): "pseudo" (default) = the Philox paths; "qmc" = scrambled-Sobol paths: `seed` is the scramble seed of
+        scipy.stats.qmc.Sobol(d=2 n_steps, scramble=True, seed=seed) (None draws one), point k drives path k through
+        z = norm.ppf(clip(u, 1e-10, 1 - 1e-10)); n_paths <= 2**30, n_steps <= 10600.
+        path_construction (read only with method="qmc"): "bridge" (default) = two Brownian bridges in breadth-first order, W1 on the
+        even and W2 on the odd dimensions (dimensions 0 and 1 set the two terminal values: include/olmc.h), step t taking their
+        increments as Z1 and Z2', at most 1024 steps; "sequential" = dimensions 2t, 2t + 1 are Z1, Z2' of step t.
+        With method="qmc", antithetic=True also prices the mirrored point -z (2 n_paths samples), and return_error's standard error is
+        the naive per-path one: for Sobol points it is not a confidence interval (it overstates the error).
+        Refused (ValueError, before the device is touched): an unknown method or path_construction, and with method="qmc"
+        n_steps > 10600, n_steps > 1024 with the bridge, n_paths > 2**30."""
         if n_paths < 1 or n_steps < 1:
             raise ValueError("n_paths and n_steps must be >= 1")
+        qmc = _qmc_tables(method, path_construction, n_paths, n_steps, seed)
+        if qmc is not None:
+            sv, shift, bridge = qmc
+            st = _hip.heston_qmc(S, K, T, r, q, option_type == "call", self.kappa, self.theta, self.sigma_v, self.rho, self.v0, n_paths,
+                                 sv, shift, bridge, antithetic)
+            return (np.float64(st.price), float(st.std_error)) if return_error else np.float64(st.price)
         s = seed if seed is not None else int(np.random.default_rng().integers(0, 2**31))
         st = _hip.heston(S, K, T, r, q, option_type == "call", self.kappa, self.theta, self.sigma_v, self.rho, self.v0,
                          n_paths, n_steps, s, antithetic)
@@ -83,11 +110,17 @@ class HestonPricer:
 
 
     def simulate_paths(self, S: float, T: float, r: float, q: float = 0.0, n_paths: int = 1000, n_steps: int = 252,
-                       seed: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+                       seed: Optional[int] = None, *, method: Literal["pseudo", "qmc"] = "pseudo",
+                       path_construction: Literal["bridge", "sequential"] = "bridge") -> Tuple[np.ndarray, np.ndarray]:
         """heston.py:257-305: (spot_paths, variance_paths), each (n_paths, n_steps + 1), column 0 = (S, v0).
-        The states of price_monte_carlo's recursion for the same seed."""
+        The states of price_monte_carlo's recursion for the same seed, method and path_construction (additive, as there)."""
         if n_paths < 1 or n_steps < 1:
             raise ValueError("n_paths and n_steps must be >= 1")
+        qmc = _qmc_tables(method, path_construction, n_paths, n_steps, seed)
+        if qmc is not None:
+            sv, shift, bridge = qmc
+            return _hip.heston_qmc_paths(S, T, r, q, self.kappa, self.theta, self.sigma_v, self.rho, self.v0, n_paths, sv, shift, bridge,
+                                         path_major=True)
         s = seed if seed is not None else int(np.random.default_rng().integers(0, 2**31))
         return _hip.heston_paths(S, T, r, q, self.kappa, self.theta, self.sigma_v, self.rho, self.v0, n_paths, n_steps, s, path_major=True)
 
