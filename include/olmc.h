@@ -62,7 +62,8 @@ extern "C" {
                               *    olmc_asian_qmc_greeks_fd, olmc_extrema_qmc_greeks_fd (their finite-difference Greeks in one launch),
                               *    olmc_american_lsm_qmc, olmc_exercise_boundary_qmc, olmc_gbm_qmc_paths (the American and its path matrix on Sobol paths),
                               *    olmc_autocallable_qmc, olmc_cliquet_qmc (the structured products on Sobol paths),
-                              *    olmc_heston_qmc, olmc_heston_qmc_paths (Heston on Sobol paths, two dimensions per step) */
+                              *    olmc_heston_qmc, olmc_heston_qmc_paths (Heston on Sobol paths, two dimensions per step),
+                              *    olmc_heston_path_payoff, olmc_heston_qmc_path_payoff (Asian, barrier and lookback payoffs under Heston) */
 
 enum {
     OLMC_OK = 0,
@@ -521,6 +522,34 @@ int olmc_heston_qmc(double S, double K, double T, double r, double q, int is_cal
 int olmc_heston_qmc_paths(double S, double T, double r, double q, double kappa, double theta, double sigma_v, double rho, double v0,
                           int construction, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift,
                           int32_t bits, int path_major, double* spot_host, double* var_host);
+
+/* ---- path payoffs under Heston ---------------
+ * Asian, barrier and lookback options on olmc_heston's paths (Philox) and olmc_heston_qmc's (scrambled Sobol, both constructions): ONE
+ * launch per call, the running statistics of a path in registers, only (sum x, sum x^2) left in memory.  The payoff of path i is what
+ * the reference's AsianOption / BarrierOption / LookbackOption.price (src/pricing_models/exotic_options.py:97-131, 174-224, 347-401)
+ * computes from row i of the spot matrix of olmc_heston_paths / olmc_heston_qmc_paths for the same seed or tables: the same recursion on
+ * the same normals, dimension assignment and bridge plan as in "quasi-Monte Carlo Heston".
+ *   payoff   OLMC_BARRIER_* (`barrier` = the level, > 0), OLMC_LOOKBACK_FLOATING / OLMC_LOOKBACK_FIXED or OLMC_PATH_ASIAN_ARITHMETIC /
+ *            OLMC_PATH_ASIAN_GEOMETRIC (`barrier` ignored).
+ *   dates    date 0 is the spot S itself (heston.py:285).  Barriers and lookback extrema monitor dates 0 .. n_steps: the date-0 decision is
+ *            the plain comparison S >= barrier (up) / S <= barrier (down), later dates compare ln(S_t / S) with ln(barrier / S).  The Asian
+ *            average runs over dates 1 .. n_steps (the arithmetic mean by one fp64 exponential per date).
+ *   payoffs  Asian max(+-(A - K), 0); barrier max(+-(S_n - K), 0) where active; lookback as olmc_lookback.
+ * out->price = exp(-r T) mean, out->std_error the naive per-path one (for Sobol points not a confidence interval).  antithetic != 0 also
+ * prices the mirrored leg -- both normals of every step flipped (Philox), the whole point z -> -z (Sobol) -- 2 n payoffs.  A call prices
+ * paths [path_offset, path_offset + n_local) of the stream / points [point_offset, point_offset + n_points) of the sequence: shards add
+ * up (olmc_combine_stats).  v0 < 0 means what it means in olmc_heston.  A NaN input (`barrier` of a barrier kind included) gives NaN
+ * results.  Refused (OLMC_ERR_ARG, before any device work): a null pointer, rho outside [-1, 1], an unknown payoff, a barrier kind with
+ * barrier <= 0, and what olmc_heston / olmc_heston_qmc refuse of counts, steps, construction and tables.  The bridge uses olmc_heston_qmc's
+ * slabs. */
+enum { OLMC_PATH_ASIAN_ARITHMETIC = 6, OLMC_PATH_ASIAN_GEOMETRIC = 7 };   /* continue OLMC_BARRIER_* (0-3), OLMC_LOOKBACK_* (4-5) */
+int olmc_heston_path_payoff(double S, double K, double T, double r, double q, int is_call, double kappa, double theta, double sigma_v,
+                            double rho, double v0, int payoff, double barrier, int64_t path_offset, int64_t n_local, int32_t n_steps,
+                            uint64_t seed, int antithetic, olmc_stats* out);
+int olmc_heston_qmc_path_payoff(double S, double K, double T, double r, double q, int is_call, double kappa, double theta, double sigma_v,
+                                double rho, double v0, int payoff, double barrier, int construction, int64_t point_offset,
+                                int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift, int32_t bits,
+                                int antithetic, olmc_stats* out);
 
 /* ---- multi-GPU, single process ------------------------------------------
  * n_paths split into n_gpus contiguous global path ranges (rank d = device d, [d N / P, (d + 1) N / P)).  Per list of devices the

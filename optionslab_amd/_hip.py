@@ -101,6 +101,9 @@ PROTOTYPES = {
     "olmc_heston": (_I, [_D] * 5 + [_I] + [_D] * 5 + [_I64, _I64, _I32, _U64T, _I, C.POINTER(Stats)]),
     "olmc_heston_qmc": (_I, [_D] * 5 + [_I] + [_D] * 5 + [_I, _I64, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, _I, C.POINTER(Stats)]),
     "olmc_heston_qmc_paths": (_I, [_D] * 9 + [_I, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, _I, C.POINTER(_D), C.POINTER(_D)]),
+    "olmc_heston_path_payoff": (_I, [_D] * 5 + [_I] + [_D] * 5 + [_I, _D, _I64, _I64, _I32, _U64T, _I, C.POINTER(Stats)]),
+    "olmc_heston_qmc_path_payoff": (_I, [_D] * 5 + [_I] + [_D] * 5 + [_I, _D, _I, _I64, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, _I,
+                                         C.POINTER(Stats)]),
     "olmc_multi_gpu_european": (_I, _SIX + [_I, _I64, _I32, _U64T, _I, _I, C.POINTER(Stats)]),
     "olmc_multi_gpu_greeks_fd": (_I, _SIX + [_I, _I64, _I32, _U64T, _I, _I, C.POINTER(_D), C.POINTER(Stats)]),
     "olmc_multi_gpu_european_cv": (_I, _SIX + [_I, _I64, _I32, _U64T, _I, _I, C.POINTER(CvMoments)]),
@@ -468,6 +471,7 @@ def asian_greeks_fd(S, K, T, r, sigma, q, is_call: bool, n_paths: int, n_steps: 
 
 
 LOOKBACK_FLOATING, LOOKBACK_FIXED = 4, 5
+PATH_ASIAN_ARITHMETIC, PATH_ASIAN_GEOMETRIC = 6, 7          # OLMC_PATH_ASIAN_*: continue BARRIER_KINDS (0-3) and LOOKBACK_* (4-5)
 QMC_SEQUENTIAL, QMC_BRIDGE = 0, 1
 QMC_BRIDGE_MAX_STEPS = 1024          # OLMC_QMC_BRIDGE_MAX_STEPS
 
@@ -666,6 +670,28 @@ def heston_qmc_paths(S, T, r, q, kappa, theta, sigma_v, rho, v0, n_points: int, 
                                        n_steps, psv, psh, int(sv.shape[1]), int(path_major), spot.ctypes.data_as(C.POINTER(C.c_double)),
                                        var.ctypes.data_as(C.POINTER(C.c_double))))
     return spot, var
+
+
+def heston_path_payoff(S, K, T, r, q, is_call: bool, kappa, theta, sigma_v, rho, v0, payoff: int, barrier: float, n_paths: int, n_steps: int,
+                       seed: int, antithetic: bool = False, path_offset: int = 0) -> Stats:
+    """An Asian (PATH_ASIAN_*), barrier (BARRIER_KINDS value, `barrier` = the level) or lookback (LOOKBACK_*) option on heston()'s paths, one
+    launch (olmc_heston_path_payoff); `barrier` is ignored by the other payoffs."""
+    out = Stats()
+    _check(lib().olmc_heston_path_payoff(S, K, T, r, q, int(is_call), kappa, theta, sigma_v, rho, v0, int(payoff), float(barrier),
+                                         int(path_offset), int(n_paths), int(n_steps), seed64(seed), int(antithetic), C.byref(out)))
+    return out
+
+
+def heston_qmc_path_payoff(S, K, T, r, q, is_call: bool, kappa, theta, sigma_v, rho, v0, payoff: int, barrier: float, n_points: int,
+                           sv: np.ndarray, shift: np.ndarray, bridge: bool = True, antithetic: bool = False, point_offset: int = 0) -> Stats:
+    """heston_path_payoff on heston_qmc()'s scrambled-Sobol paths (olmc_heston_qmc_path_payoff): n_steps = sv.shape[0] / 2."""
+    sv, psv, shift, psh = _sobol_args(sv, shift, point_offset, n_points)
+    n_steps = _heston_steps(sv)
+    out = Stats()
+    _check(lib().olmc_heston_qmc_path_payoff(S, K, T, r, q, int(is_call), kappa, theta, sigma_v, rho, v0, int(payoff), float(barrier),
+                                             QMC_BRIDGE if bridge else QMC_SEQUENTIAL, int(point_offset), int(n_points), n_steps, psv, psh,
+                                             int(sv.shape[1]), int(antithetic), C.byref(out)))
+    return out
 
 
 def multi_gpu_european(S, K, T, r, sigma, q, is_call: bool, n_paths: int, n_steps: int, seed: int, antithetic: bool,

@@ -25,6 +25,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <limits>
 #include <mutex>
 #include <string>
 #include <system_error>
@@ -2333,8 +2334,9 @@ extern "C" int olmc_gbm_qmc_paths(double S, double T, double r, double sigma, do
 // olmc_heston / olmc_heston_paths on scrambled-Sobol points (include/olmc.h "quasi-Monte Carlo Heston"): their contract and model
 // checks, the table / construction / point-range checks of the other Sobol path calls with two dimensions per step.
 namespace {
-// The bridge slabs of heston_qmc_kernel on c: one [2 n][64] slab per RESIDENT wave.  The grid is cut to the workgroups the device holds
-// at once (kHestonBridgeBlocksPerCu per CU = two waves per SIMD, of the four its 109-117 VGPRs allow) and strides over the blocks beyond, and
+// The bridge slabs of heston_qmc_kernel / heston_qmc_path_kernel on c: one [2 n][64] slab per RESIDENT wave.  The grid is cut to the workgroups the device holds
+// at once (kHestonBridgeBlocksPerCu per CU = two waves per SIMD, of the four its 109-117 VGPRs allow; heston_qmc_path_kernel's 113-131 allow
+// three or four) and strides over the blocks beyond, and
 // the slabs of a launch stay under kHestonSlabCap (the grid shrinks further): the buffer follows the device and n, not the number of
 // points -- 0.5 GiB at 252 steps and 1 GiB from 504 steps on with 256 CUs, kept with the context.
 constexpr size_t kHestonSlabCap = size_t(1) << 30;
@@ -2354,6 +2356,20 @@ int heston_slabs(DeviceCtx* c, int32_t n_steps, int32_t* grid) {
     HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_heston_w), bytes));
     c->heston_w_bytes = bytes;
     return OLMC_OK;
+}
+
+// run_qmc_payoff's shape of a Heston price launch (heston_qmc_kernel, heston_qmc_path_kernel): the grid over the blocks of 64 points,
+// aligned in the absolute point index, and for the bridge its slabs.
+auto heston_qmc_shape(int64_t point_offset, int64_t n_points, int32_t n_steps) {
+    return [=](DeviceCtx* c, QmcPathLaunch* pl) {
+        const int64_t first_block = point_offset / kWave, last_block = (point_offset + n_points - 1) / kWave;
+        pl->grid = qmc_block_grid(last_block - first_block + 1);
+        pl->slabs = nullptr;
+        if (!pl->bridge) return static_cast<int>(OLMC_OK);
+        const int rc2 = heston_slabs(c, n_steps, &pl->grid);
+        pl->slabs = c->d_heston_w;
+        return rc2;
+    };
 }
 }  // namespace
 
@@ -2376,16 +2392,7 @@ extern "C" int olmc_heston_qmc(double S, double K, double T, double r, double q,
                                   });
                               });
                           },
-                          2, [&](DeviceCtx* c, QmcPathLaunch* pl) {
-                              // the kernel's blocks are aligned in the absolute point index
-                              const int64_t first_block = point_offset / kWave, last_block = (point_offset + n_points - 1) / kWave;
-                              pl->grid = qmc_block_grid(last_block - first_block + 1);
-                              pl->slabs = nullptr;
-                              if (!pl->bridge) return static_cast<int>(OLMC_OK);
-                              const int rc2 = heston_slabs(c, n_steps, &pl->grid);
-                              pl->slabs = c->d_heston_w;
-                              return rc2;
-                          });
+                          2, heston_qmc_shape(point_offset, n_points, n_steps));
 }
 
 extern "C" int olmc_heston_qmc_paths(double S, double T, double r, double q, double kappa, double theta, double sigma_v, double rho, double v0,
@@ -2420,6 +2427,104 @@ extern "C" int olmc_heston_qmc_paths(double S, double T, double r, double q, dou
     rc = copy_to_host(c, spot_host, d_spot, static_cast<size_t>(bytes));
     if (rc) return rc;
     return copy_to_host(c, var_host, d_var, static_cast<size_t>(bytes));
+}
+
+// ============================================================ path payoffs under Heston ====
+// Asian, barrier and lookback payoffs on olmc_heston's and olmc_heston_qmc's paths (include/olmc.h "path payoffs under Heston"): their
+// contract, model and range checks, one launch of heston_path_kernel / heston_qmc_path_kernel.
+namespace {
+bool heston_path_is_barrier(int payoff) { return payoff <= OLMC_BARRIER_DOWN_IN; }
+int heston_path_check(int payoff, double barrier) {
+    if (payoff < OLMC_BARRIER_UP_OUT || payoff > OLMC_PATH_ASIAN_GEOMETRIC) return fail(OLMC_ERR_ARG, "bad payoff");
+    if (heston_path_is_barrier(payoff) && barrier <= 0.0) return fail(OLMC_ERR_ARG, "Barrier must be positive");
+    return OLMC_OK;
+}
+int heston_path_family(int payoff) {
+    return payoff == OLMC_PATH_ASIAN_ARITHMETIC ? kQmcAsianArithmetic : payoff == OLMC_PATH_ASIAN_GEOMETRIC ? kQmcAsianGeometric : kQmcExtrema;
+}
+
+// What the payoff reads of an ExtremaContract (no drift, no vol: the model is the HestonContract's).  Date 0 of the reference's matrix is
+// the spot S itself, so a barrier's date-0 decision is the plain comparison S >= B (up) / S <= B (down), made here: a barrier hit at date
+// 0 becomes a level every running extremum meets, and one not hit a level strictly beyond the running extrema's start (ln(S_0 / S) = 0),
+// also where ln(B / S) rounds to 0.  Later dates compare ln(S_t / S) with ln(B / S).
+ExtremaContract heston_path_contract(double S, double K, int is_call, int payoff, double barrier) {
+    ExtremaContract ec;
+    ec.s0 = S;
+    ec.log_barrier_rel = 0.0;
+    if (heston_path_is_barrier(payoff)) {
+        const bool up = payoff <= OLMC_BARRIER_UP_IN;
+        const double inf = std::numeric_limits<double>::infinity(), tiny = std::numeric_limits<double>::min();
+        const double lb = std::log(barrier / S);
+        if (up) ec.log_barrier_rel = S >= barrier ? -inf : (lb > 0.0 ? lb : tiny);
+        else ec.log_barrier_rel = S <= barrier ? inf : (lb < 0.0 ? lb : -tiny);
+    }
+    ec.drift = 0.0;
+    ec.vol = 0.0;
+    ec.strike = K;
+    ec.sign = is_call ? 1.0 : -1.0;
+    ec.payoff = heston_path_family(payoff) == kQmcExtrema ? payoff : 0;
+    ec.pad = 0;
+    return ec;
+}
+
+// f(integral_constant<int, family>) for the family of a checked payoff code.
+template <typename F>
+void with_heston_path_family(int payoff, F&& f) {
+    const int family = heston_path_family(payoff);
+    if (family == kQmcAsianArithmetic) f(std::integral_constant<int, kQmcAsianArithmetic>{});
+    else if (family == kQmcAsianGeometric) f(std::integral_constant<int, kQmcAsianGeometric>{});
+    else f(std::integral_constant<int, kQmcExtrema>{});
+}
+}  // namespace
+
+extern "C" int olmc_heston_path_payoff(double S, double K, double T, double r, double q, int is_call, double kappa, double theta, double sigma_v,
+                                       double rho, double v0, int payoff, double barrier, int64_t path_offset, int64_t n_local, int32_t n_steps,
+                                       uint64_t seed, int antithetic, olmc_stats* out) {
+    if (!out) return fail(OLMC_ERR_ARG, "null pointer");
+    int rc = heston_check(rho);
+    if (rc) return rc;
+    rc = heston_path_check(payoff, barrier);
+    if (rc) return rc;
+    const HestonContract hc = make_heston(S, K, T, r, q, is_call, kappa, theta, sigma_v, rho, v0, n_steps);
+    const ExtremaContract ec = heston_path_contract(S, K, is_call, payoff, barrier);
+    const bool bad = heston_poisoned(S, K, T, r, q, kappa, theta, sigma_v, rho, v0) || (heston_path_is_barrier(payoff) && std::isnan(barrier));
+    const double inv_steps = 1.0 / n_steps;                  // n_steps < 1 is refused by run_structured before any launch
+    return run_structured(path_offset, n_local, n_steps, seed, antithetic, r, T, bad, out,
+                          [&](int32_t grid, hipStream_t st, const EventPair* timed, const PathRange& pr, const ReduceWs& ws) {
+                              with_heston_path_family(payoff, [&](auto f) {
+                                  with_bool(antithetic != 0, [&](auto a) {
+                                      launch_timed(heston_path_kernel<f, a>, dim3(grid), dim3(kBlock), st, timed, pr, hc, ec, inv_steps, ws);
+                                  });
+                              });
+                          });
+}
+
+extern "C" int olmc_heston_qmc_path_payoff(double S, double K, double T, double r, double q, int is_call, double kappa, double theta, double sigma_v,
+                                           double rho, double v0, int payoff, double barrier, int construction, int64_t point_offset,
+                                           int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift, int32_t bits,
+                                           int antithetic, olmc_stats* out) {
+    if (!out) return fail(OLMC_ERR_ARG, "null pointer");
+    int rc = heston_check(rho);
+    if (rc) return rc;
+    rc = heston_path_check(payoff, barrier);
+    if (rc) return rc;
+    rc = qmc_path_check(construction, point_offset, n_points, n_steps, sv, shift, bits, 2);
+    if (rc) return rc;
+    const HestonContract hc = make_heston(S, K, T, r, q, is_call, kappa, theta, sigma_v, rho, v0, n_steps);
+    const ExtremaContract ec = heston_path_contract(S, K, is_call, payoff, barrier);
+    const bool bad = heston_poisoned(S, K, T, r, q, kappa, theta, sigma_v, rho, v0) || (heston_path_is_barrier(payoff) && std::isnan(barrier));
+    return run_qmc_payoff(construction, point_offset, n_points, n_steps, sv, shift, antithetic, r, T, bad, out,
+                          [&](int32_t g, hipStream_t s, const EventPair* timed, const QmcPathLaunch& pl, const ReduceWs& ws) {
+                              with_heston_path_family(payoff, [&](auto f) {
+                                  with_bool(pl.bridge, [&](auto b) {
+                                      with_bool(pl.anti, [&](auto m) {
+                                          launch_timed(heston_qmc_path_kernel<f, b, m>, dim3(g), dim3(kBlock), s, timed, pl.qr, hc, ec, pl.inv_steps,
+                                                       pl.d_sv, pl.d_shift, pl.plan, pl.slabs, ws);
+                                      });
+                                  });
+                              });
+                          },
+                          2, heston_qmc_shape(point_offset, n_points, n_steps));
 }
 
 namespace {

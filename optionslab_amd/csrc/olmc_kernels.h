@@ -3752,6 +3752,125 @@ __global__ __launch_bounds__(kBlock) void heston_qmc_paths_kernel(QmcRange qr, H
     }
 }
 
+// ------------------------------------------------------ path payoffs under Heston ----
+// Asian, barrier and lookback payoffs on the paths of heston_kernel (Philox) and heston_qmc_kernel (Sobol): the payoff of a path is what
+// AsianOption / BarrierOption / LookbackOption.price (exotic_options.py:97-131, 174-224, 347-401) computes from its row of
+// HestonPricer.simulate_paths' spot matrix -- same stream or points, same HestonStep recursion, the date's log-spot formed as
+// heston_paths_kernel forms it, fma(t + 1, mu_dt, ls).  ls is carried RELATIVE to ln S (it starts at 0), so date 0 is the spot S itself
+// (heston.py:285), as ExtremaContract's payoffs assume: extrema over dates 0 .. n (QmcLeg starts them at ln(S_0 / S) = 0), the Asian mean
+// over dates 1 .. n.  A lane owns a path, so a leg's totals are qmc_payoff's arguments as they stand (no butterflies); the extrema
+// family's payoff code acts in the epilogue only.  ExtremaContract's drift and vol are not read; its log_barrier_rel carries the host's
+// date-0 decision (olmc.hip: heston_path_contract).
+// The arithmetic Asian takes one exp2_f64 per date and leg, so its ln S side runs in log2 units: the two constants of HestonStep that
+// feed ln S (and mu_dt) are scaled once; the variance recursion is untouched and keeps simulate_paths' bits.
+template <int FAMILY, bool ANTI>
+struct HestonPathLegs {
+    static constexpr double kUnit = FAMILY == kQmcAsianArithmetic ? 1.4426950408889634 : 1.0;
+    HestonStep hs;
+    double mu_unit;
+    double ls[2], v[2];
+    QmcLeg leg[2];
+    __device__ __forceinline__ HestonPathLegs(const HestonContract& c, double z_unit) : hs(c, z_unit), mu_unit(c.mu_dt * kUnit) {
+        hs.neg_half_dt *= kUnit;
+        hs.zs *= kUnit;
+    }
+    __device__ __forceinline__ void start(double v_start) {
+#pragma unroll
+        for (int l = 0; l < 2; ++l) { ls[l] = 0.0; v[l] = v_start; leg[l] = QmcLeg(); }
+    }
+    // step t (normals z1, z2 in the unit hs was built for), then date t + 1 into every leg; advance = false: heston_start took the step
+    __device__ __forceinline__ void date(int32_t t, double z1, double z2, bool advance) {
+        if (advance) {
+            const double u = hs.zs * z1;
+            const double w = __builtin_fma(hs.b, z2, hs.a * z1);
+            hs.advance<1>(u, w, ls[0], v[0]);
+            if constexpr (ANTI) hs.advance<-1>(u, w, ls[1], v[1]);
+        }
+        const double td = static_cast<double>(t + 1);
+#pragma unroll
+        for (int l = 0; l < (ANTI ? 2 : 1); ++l) qmc_leg_add<FAMILY>(leg[l], __builtin_fma(td, mu_unit, ls[l]));
+    }
+    __device__ __forceinline__ void payoffs(const ExtremaContract& ec, double inv_steps, int32_t n, double (&acc)[2]) const {
+#pragma unroll
+        for (int l = 0; l < (ANTI ? 2 : 1); ++l) {
+            // y_n is read by the extrema family only, whose unit is 1
+            const double x = qmc_payoff<FAMILY>(ec, inv_steps, leg[l].a, leg[l].mx, leg[l].mn, __builtin_fma(static_cast<double>(n), mu_unit, ls[l]));
+            acc[0] += x; acc[1] += x * x;
+        }
+    }
+};
+
+// Philox: lane per path, heston_kernel's stream (tag kTagHeston, one block for two steps).
+// Resources (tools/kernel_meta.sh, gfx950; no scratch, no spills; LDS 64 B, the reduction), VGPRs plain / antithetic: arithmetic 98 / 78,
+// geometric 98 / 86, extrema 100 / 114 (heston_kernel: 96 / 76).
+template <int FAMILY, bool ANTI>
+__global__ __launch_bounds__(kBlock) void heston_path_kernel(PathRange pr, HestonContract c, ExtremaContract ec, double inv_steps, ReduceWs ws) {
+    const RoundKeys rk = pin_round_keys(pr.key0, pr.key1);
+    double acc[2] = {0.0, 0.0};
+    HestonPathLegs<FAMILY, ANTI> p(c, kZScale);
+    double v_start;
+    const bool skip0 = heston_start(c, v_start);
+    const int32_t blocks = (pr.n_steps + 1) >> 1;
+    for_each_path(pr, [&](int64_t, uint32_t g_lo, uint32_t g_hi) {
+        p.start(v_start);
+        for (int32_t b = 0; b < blocks; ++b) {
+            float z[4];
+            raw_normals4_pinned(g_lo, g_hi, static_cast<uint32_t>(b), kTagHeston, rk, z);
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int32_t t = 2 * b + h;
+                if (t < pr.n_steps) p.date(t, static_cast<double>(z[2 * h]), static_cast<double>(z[2 * h + 1]), !(skip0 && t == 0));
+            }
+        }
+        p.payoffs(ec, inv_steps, pr.n_steps, acc);
+    });
+    block_then_grid_reduce<2>(acc, ws);
+}
+
+// Sobol: heston_qmc_kernel's skeleton (aligned blocks in the absolute point index, lanes over points, the bridge's library-owned slabs),
+// the per-date accumulation inside the step functor.
+// Resources (tools/kernel_meta.sh, gfx950; no scratch, no spills; LDS 64 B, the reduction), VGPRs plain / antithetic:
+//   sequential  arithmetic 94 / 80, geometric 88 / 76, extrema 92 / 100      (heston_qmc_kernel: 88 / 78)
+//   bridge      arithmetic 121 / 117, geometric 117 / 113, extrema 115 / 131  (heston_qmc_kernel: 117 / 109)
+// The antithetic extrema bridge (two legs of ln S, v, max, min) is the one instantiation past 128: its 136 allocated registers admit
+// three waves per SIMD where the others admit four.  The bridge launch holds two (olmc.hip: kHestonBridgeBlocksPerCu = 2 workgroups of
+// four waves per CU, to bound the slabs), so no instantiation runs at a lower occupancy than heston_qmc_kernel's bridge does.
+template <int FAMILY, bool BRIDGE, bool ANTI>
+__global__ __launch_bounds__(kBlock) void heston_qmc_path_kernel(QmcRange qr, HestonContract c, ExtremaContract ec, double inv_steps,
+                                                                 const uint32_t* __restrict__ sv, const uint32_t* __restrict__ shift, QmcBridgePlan plan,
+                                                                 double* slabs, ReduceWs ws) {
+    const int lane = static_cast<int>(threadIdx.x) & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) / kWave);
+    const int32_t n = qr.dims;                                               // steps: the tables hold 2 n dimensions
+    HestonPathLegs<FAMILY, ANTI> p(c, 1.0);
+    double v_start;
+    const bool skip0 = heston_start(c, v_start);
+    const uint64_t base = qr.first & ~static_cast<uint64_t>(kWave - 1);      // blocks aligned in the absolute index
+    const uint64_t end = qr.first + static_cast<uint64_t>(qr.count);
+    const int64_t n_blocks = static_cast<int64_t>((end - base + kWave - 1) / kWave);
+    const int64_t stride = static_cast<int64_t>(gridDim.x) * kWavesPerBlock;
+    const int64_t slot = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave;
+    double acc[2] = {0.0, 0.0};
+    for (int64_t blk = slot; blk < n_blocks; blk += stride) {
+        const uint64_t k = base + static_cast<uint64_t>(blk) * kWave + lane;
+        const bool live = k >= qr.first && k < end;
+        const QmcLanePoint lp(static_cast<uint32_t>(k));
+        p.start(v_start);
+        auto step = [&](int32_t t, double z1, double z2) { p.date(t, z1, z2, !(skip0 && t == 0)); };
+        if constexpr (BRIDGE) {
+            double* w1 = slabs + static_cast<size_t>(slot) * (2 * static_cast<size_t>(n) * kWave);
+            double* w2 = w1 + static_cast<size_t>(n) * kWave;
+            auto at = [&](int32_t j) { return static_cast<size_t>(j - 1) * kWave + lane; };
+            heston_qmc_bridge_fill(sv, shift, plan, n, lane, lp, live, w1, w2, at);
+            if (live) heston_qmc_bridge_sweep(n, w1, w2, at, step);
+        } else {
+            heston_qmc_normals(sv, shift, n, lane, lp, step);
+        }
+        if (live) p.payoffs(ec, inv_steps, n, acc);
+    }
+    block_then_grid_reduce<2>(acc, ws);
+}
+
 // ------------------------------------------------------- validation taps ----
 __global__ void philox_words_kernel(uint64_t first, int64_t n_paths, int32_t block0, int32_t n_blocks,
                                     uint32_t tag, uint32_t k0, uint32_t k1, uint32_t* __restrict__ out) {

@@ -124,6 +124,66 @@ class HestonPricer:
         s = seed if seed is not None else int(np.random.default_rng().integers(0, 2**31))
         return _hip.heston_paths(S, T, r, q, self.kappa, self.theta, self.sigma_v, self.rho, self.v0, n_paths, n_steps, s, path_major=True)
 
+    def _price_path_payoff(self, payoff: int, barrier: float, S, K, T, r, q, option_type, n_paths, n_steps, seed, antithetic, return_error,
+                           method, path_construction):
+        """One launch of the path-payoff kernels (include/olmc.h "path payoffs under Heston") under price_monte_carlo's conventions."""
+        if n_paths < 1 or n_steps < 1:
+            raise ValueError("n_paths and n_steps must be >= 1")
+        model = (self.kappa, self.theta, self.sigma_v, self.rho, self.v0)
+        qmc = _qmc_tables(method, path_construction, n_paths, n_steps, seed)
+        if qmc is not None:
+            sv, shift, bridge = qmc
+            st = _hip.heston_qmc_path_payoff(S, K, T, r, q, option_type == "call", *model, payoff, barrier, n_paths, sv, shift, bridge, antithetic)
+        else:
+            s = seed if seed is not None else int(np.random.default_rng().integers(0, 2**31))
+            st = _hip.heston_path_payoff(S, K, T, r, q, option_type == "call", *model, payoff, barrier, n_paths, n_steps, s, antithetic)
+        return (np.float64(st.price), float(st.std_error)) if return_error else np.float64(st.price)
+
+    def price_asian(self, S: float, K: float, T: float, r: float, q: float = 0.0, option_type: Literal["call", "put"] = "call",
+                    avg_type: Literal["arithmetic", "geometric"] = "arithmetic", n_paths: int = 100000, n_steps: int = 252,
+                    seed: Optional[int] = None, antithetic: bool = False, return_error: bool = False, *,
+                    method: Literal["pseudo", "qmc"] = "pseudo", path_construction: Literal["bridge", "sequential"] = "bridge"):
+        """The Asian option max(+-(A - K), 0) under this model, A the arithmetic or geometric mean of the spot over dates 1 .. n_steps: what
+        AsianOption.price (exotic_options.py:97-131) computes from simulate_paths' spot matrix for the same seed, method and
+        path_construction, in one launch that stores no path.  seed, antithetic, return_error, method and path_construction as
+        price_monte_carlo: with method="qmc" the standard error is the naive per-path one, not a confidence interval (it overstates the
+        error).  Refused (ValueError, before the device is touched): an unknown avg_type, and what price_monte_carlo refuses."""
+        if avg_type not in ("arithmetic", "geometric"):
+            raise ValueError("avg_type must be 'arithmetic' or 'geometric'")
+        payoff = _hip.PATH_ASIAN_GEOMETRIC if avg_type == "geometric" else _hip.PATH_ASIAN_ARITHMETIC
+        return self._price_path_payoff(payoff, 0.0, S, K, T, r, q, option_type, n_paths, n_steps, seed, antithetic, return_error, method,
+                                       path_construction)
+
+    def price_barrier(self, S: float, K: float, T: float, r: float, barrier: float, q: float = 0.0,
+                      option_type: Literal["call", "put"] = "call",
+                      barrier_type: Literal["up-and-out", "up-and-in", "down-and-out", "down-and-in"] = "up-and-out", n_paths: int = 100000,
+                      n_steps: int = 252, seed: Optional[int] = None, antithetic: bool = False, return_error: bool = False, *,
+                      method: Literal["pseudo", "qmc"] = "pseudo", path_construction: Literal["bridge", "sequential"] = "bridge"):
+        """The barrier option under this model: max(+-(S_n - K), 0) where the barrier, monitored at dates 0 .. n_steps of simulate_paths' spot
+        matrix (date 0 is S itself: S >= barrier for an up barrier, S <= barrier for a down one), leaves it active -- what
+        BarrierOption.price (exotic_options.py:174-224) computes from that matrix, in one launch that stores no path.  barrier_type is read
+        as the reference's class reads it: startswith("up") and endswith("out").  After date 0 the kernel decides in log space, ln(S_t / S)
+        against ln(barrier / S), where the matrix route compares exp(ln S_t) with the barrier: the two agree except for a path within
+        rounding (about 1e-16 relative) of the level, which can decide differently.  The rest as price_asian; also refused: barrier <= 0."""
+        if barrier <= 0:
+            raise ValueError("Barrier must be positive")
+        kind = ("up" if barrier_type.startswith("up") else "down") + ("-and-out" if barrier_type.endswith("out") else "-and-in")
+        return self._price_path_payoff(_hip.BARRIER_KINDS[kind], barrier, S, K, T, r, q, option_type, n_paths, n_steps, seed, antithetic,
+                                       return_error, method, path_construction)
+
+    def price_lookback(self, S: float, K: float, T: float, r: float, q: float = 0.0, option_type: Literal["call", "put"] = "call",
+                       lookback_type: Literal["floating", "fixed"] = "floating", n_paths: int = 100000, n_steps: int = 252,
+                       seed: Optional[int] = None, antithetic: bool = False, return_error: bool = False, *,
+                       method: Literal["pseudo", "qmc"] = "pseudo", path_construction: Literal["bridge", "sequential"] = "bridge"):
+        """The lookback option under this model on the extrema of simulate_paths' spot matrix over dates 0 .. n_steps: floating call S_n -
+        S_min, floating put S_max - S_n, fixed call max(S_max - K, 0), fixed put max(K - S_min, 0) (LookbackOption.price,
+        exotic_options.py:347-401), in one launch that stores no path.  The rest as price_asian; also refused: an unknown lookback_type."""
+        if lookback_type not in ("floating", "fixed"):
+            raise ValueError("lookback_type must be 'floating' or 'fixed'")
+        payoff = _hip.LOOKBACK_FIXED if lookback_type == "fixed" else _hip.LOOKBACK_FLOATING
+        return self._price_path_payoff(payoff, 0.0, S, K, T, r, q, option_type, n_paths, n_steps, seed, antithetic, return_error, method,
+                                       path_construction)
+
 
 class HestonAdapter:
     """unified_greeks.py:74-104: sigma -> v0 = sigma^2, prices with the semi-analytic formula."""

@@ -1,0 +1,148 @@
+"""Oracles of the Heston path-payoff tests (not a test module).
+
+Payoffs: oracle/numpy_reference.py's restatements of AsianOption / BarrierOption / LookbackOption.price, applied as they are to a spot
+matrix (n_paths, n_steps + 1).  Paths: the literal recursion of src/pricing_models/heston.py:291-303 on given normals, and the Sobol
+construction pinned in include/olmc.h ("quasi-Monte Carlo Heston"): SciPy's Sobol(d=2n, scramble=True, seed).random(N), the clip and
+norm.ppf of src/simulation/gbm_qmc.py:32-38, sequential = dimensions 2t, 2t + 1 are Z1, Z2' of step t, bridge = W1 on the even and W2
+on the odd dimensions of the breadth-first plan, step t taking their increments; the mirror leg is the same on -z.
+"""
+import collections
+import math
+import warnings
+
+import numpy as np
+
+from oracle import numpy_reference as orc
+
+S, K, T, R, Q = 100.0, 100.0, 1.0, 0.05, 0.01
+UP, DOWN = 120.0, 85.0
+# kappa theta sigma_v rho v0
+USUAL = (2.0, 0.04, 0.3, -0.7, 0.04)
+FELLER_VIOLATING = (3.0, 0.02, 0.8, 0.3, 0.05)              # the variance is truncated at 0
+CALM = (2.0, 0.09, 0.1, -0.7, 0.09)                         # the variance stays away from 0: the normals can be recovered from the states
+
+BARRIER_KINDS = ("up-and-out", "up-and-in", "down-and-out", "down-and-in")
+# (name, family, kind): the eight payoffs
+PAYOFFS = ([("asian-" + k, "asian", k) for k in ("arithmetic", "geometric")] + [("barrier-" + k, "barrier", k) for k in BARRIER_KINDS]
+           + [("lookback-" + k, "lookback", k) for k in ("floating", "fixed")])
+
+
+def barrier_level(kind):
+    return UP if kind.startswith("up") else DOWN
+
+
+def payoff_code(family, kind):
+    """(payoff, barrier) of the C ABI."""
+    from optionslab_amd import _hip
+
+    if family == "asian":
+        return (_hip.PATH_ASIAN_GEOMETRIC if kind == "geometric" else _hip.PATH_ASIAN_ARITHMETIC), 0.0
+    if family == "barrier":
+        return _hip.BARRIER_KINDS[kind], barrier_level(kind)
+    return (_hip.LOOKBACK_FIXED if kind == "fixed" else _hip.LOOKBACK_FLOATING), 0.0
+
+
+def payoffs(spot, family, kind, option_type):
+    """The undiscounted payoff of every row of the spot matrix."""
+    if family == "asian":
+        return orc.asian_from_paths(spot, K, T, R, kind, option_type, return_payoffs=True)[1]
+    if family == "barrier":
+        return orc.barrier_from_paths(spot, K, T, R, barrier_level(kind), kind, option_type, return_payoffs=True)[1]
+    return orc.lookback_from_paths(spot, K, T, R, kind, option_type, return_payoffs=True)[1]
+
+
+def price_method(pricer, family, kind, option_type, **kw):
+    """HestonPricer.price_asian / price_barrier / price_lookback of the payoff."""
+    if family == "asian":
+        return pricer.price_asian(S, K, T, R, Q, option_type, kind, **kw)
+    if family == "barrier":
+        return pricer.price_barrier(S, K, T, R, barrier_level(kind), Q, option_type, kind, **kw)
+    return pricer.price_lookback(S, K, T, R, Q, option_type, kind, **kw)
+
+
+def barrier_clearance(spot):
+    """The closest relative approach of any path's maximum or minimum to the barrier it could cross."""
+    return min(float(np.min(np.abs(np.max(spot, axis=1) / UP - 1.0))), float(np.min(np.abs(np.min(spot, axis=1) / DOWN - 1.0))))
+
+
+def literal_recursion(z1, z2p, model, n):
+    """heston.py:291-303 with the given normals (each (m, n)): spot and variance, each (m, n + 1)."""
+    kappa, theta, sigma_v, rho, v0 = model
+    dt = T / n
+    sqrt_dt = np.sqrt(dt)
+    rho_sqrt = np.sqrt(1 - rho**2)
+    m = z1.shape[0]
+    spot, var = np.zeros((m, n + 1)), np.zeros((m, n + 1))
+    spot[:, 0], var[:, 0] = S, v0
+    log_S = np.log(S) * np.ones(m)
+    v = v0 * np.ones(m)
+    for t in range(1, n + 1):
+        Z1 = z1[:, t - 1]
+        Z2 = rho * Z1 + rho_sqrt * z2p[:, t - 1]
+        v_pos = np.maximum(v, 0)
+        sqrt_v = np.sqrt(v_pos)
+        log_S += (R - Q - 0.5 * v_pos) * dt + sqrt_v * sqrt_dt * Z1
+        v += kappa * (theta - v_pos) * dt + sigma_v * sqrt_v * sqrt_dt * Z2
+        v = np.maximum(v, 0)
+        spot[:, t] = np.exp(log_S)
+        var[:, t] = v
+    return spot, var
+
+
+def recovered_normals(spot, var, model):
+    """(Z1, Z2') of every step from the states of a path whose variance never touched 0: the recursion solved for its normals."""
+    kappa, theta, sigma_v, rho, _v0 = model
+    n = spot.shape[1] - 1
+    dt = T / n
+    v = var[:, :-1]
+    sd = np.sqrt(v * dt)
+    z1 = (np.diff(np.log(spot), axis=1) - (R - Q - 0.5 * v) * dt) / sd
+    z2 = (np.diff(var, axis=1) - kappa * (theta - v) * dt) / (sigma_v * sd)
+    return z1, (z2 - rho * z1) / np.sqrt(1 - rho**2)
+
+
+def bridge_walk(z):
+    """The pinned breadth-first Brownian bridge (include/olmc.h), over the rows of z (N, n): W (N, n + 1)."""
+    n = z.shape[1]
+    W = np.zeros((z.shape[0], n + 1))
+    W[:, n] = math.sqrt(n) * z[:, 0]
+    k = 1
+    queue = collections.deque([(0, n)])
+    while queue:
+        a, b = queue.popleft()
+        if b - a < 2:
+            continue
+        m = (a + b) // 2
+        W[:, m] = ((b - m) * W[:, a] + (m - a) * W[:, b]) / (b - a) + math.sqrt((m - a) * (b - m) / (b - a)) * z[:, k]
+        k += 1
+        queue.append((a, m))
+        queue.append((m, b))
+    return W
+
+
+def step_normals(z, construction):
+    """(Z1, Z2') of every step, each (m, n), from the point's 2n normals."""
+    if construction == "sequential":
+        return z[:, 0::2], z[:, 1::2]
+    return np.diff(bridge_walk(z[:, 0::2]), axis=1), np.diff(bridge_walk(z[:, 1::2]), axis=1)
+
+
+def sobol_spots(n, n_points, seed, model, constructions, chunk=1024):
+    """{(construction, leg): spot matrix} over Sobol points [0, n_points); leg 1 is the mirror -z."""
+    from scipy.stats import norm, qmc
+
+    eng = qmc.Sobol(d=2 * n, scramble=True, seed=seed)
+    parts = collections.defaultdict(list)
+    done = 0
+    while done < n_points:
+        m = min(chunk, n_points - done)
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", UserWarning)
+            u = eng.random(m)
+        z = norm.ppf(np.clip(u, 1e-10, 1 - 1e-10))
+        for construction in constructions:
+            z1, z2p = step_normals(z, construction)
+            for leg, sign in enumerate((1.0, -1.0)):
+                parts[(construction, leg)].append(literal_recursion(sign * z1, sign * z2p, model, n)[0])
+        done += m
+    return {key: np.concatenate(v) for key, v in parts.items()}

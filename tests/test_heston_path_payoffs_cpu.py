@@ -1,0 +1,217 @@
+"""HestonPricer.price_asian / price_barrier / price_lookback without a device: the ABI declares, binds and exports the two entry points,
+they refuse bad arguments with exact messages before any device work, the Python refusals come before the library is loaded, the
+methods reach the bindings with the payoff codes of the header, and the reference fixture is whole."""
+import ctypes as C
+import json
+import math
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import optionslab_amd as ol
+from optionslab_amd import _hip
+from optionslab_amd.build import LIBRARY, PROBE_LIBRARY, build_library, build_probe_library
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+S, K, T, R, Q = 100.0, 100.0, 1.0, 0.05, 0.01
+MODEL = (2.0, 0.04, 0.3, -0.7, 0.04)                      # kappa theta sigma_v rho v0
+NAMES = ("olmc_heston_path_payoff", "olmc_heston_qmc_path_payoff")
+
+
+def _pricer():
+    return ol.HestonPricer(*MODEL)
+
+
+def _calls(p):
+    """The three public calls as functions of their keywords."""
+    return [lambda **kw: p.price_asian(S, K, T, R, Q, "call", **kw), lambda **kw: p.price_barrier(S, K, T, R, 120.0, Q, "call", **kw),
+            lambda **kw: p.price_lookback(S, K, T, R, Q, "put", **kw)]
+
+
+# ------------------------------------------------------------------------------------------------------------ the ABI ----
+@pytest.fixture(scope="module")
+def library():
+    build_library()
+    return _hip.load_library()
+
+
+def _exported(path):
+    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
+    return set(re.findall(r"\bT (olmc_[a-z0-9_]+)", out))
+
+
+def test_the_header_declares_the_bindings_bind_and_both_libraries_export_the_entry_points(library):
+    with open(os.path.join(ROOT, "include", "olmc.h")) as f:
+        header = f.read()
+    build_probe_library()
+    for name in NAMES:
+        assert f"int {name}(" in header
+        assert name in _hip.PROTOTYPES and hasattr(library, name)
+        assert name in _exported(LIBRARY) and name in _exported(PROBE_LIBRARY)
+    assert "enum { OLMC_PATH_ASIAN_ARITHMETIC = 6, OLMC_PATH_ASIAN_GEOMETRIC = 7 };" in header
+    assert (_hip.PATH_ASIAN_ARITHMETIC, _hip.PATH_ASIAN_GEOMETRIC) == (6, 7)
+    assert "#define OLMC_ABI_VERSION 6 " in header
+    assert library.olmc_abi_version() == 6
+
+
+def _ST():
+    return C.byref(_hip.Stats())
+
+
+def _sobol(dims):
+    return (C.c_uint32 * (30 * dims))(*range(1, 30 * dims + 1)), (C.c_uint32 * dims)()
+
+
+_PRICE = (S, K, T, R, Q, 1, *MODEL)                               # S K T r q is_call kappa theta sigma_v rho v0
+_BAD_RHO = (S, K, T, R, Q, 1, 2.0, 0.04, 0.3, -1.5, 0.04)
+_BRIDGE_CAP = "the Brownian-bridge construction takes at most OLMC_QMC_BRIDGE_MAX_STEPS (1024) dates"
+_BITS = "only 30-bit Sobol tables (SciPy's default) are supported"
+_STEPS = "n_steps must be in [1, 10600]: a step takes two of the 21201 Sobol dimensions"
+_P, _Q = "olmc_heston_path_payoff", "olmc_heston_qmc_path_payoff"
+
+# olmc_heston_path_payoff: contract, payoff, barrier, path_offset, n_local, n_steps, seed, antithetic, out
+# olmc_heston_qmc_path_payoff: contract, payoff, barrier, construction, point_offset, n_points, n_steps, sv, shift, bits, antithetic, out
+_REFUSALS = [
+    (_P, lambda: (*_PRICE, 8, 0.0, 0, 64, 8, 1, 0, _ST()), "bad payoff"),
+    (_P, lambda: (*_PRICE, -1, 0.0, 0, 64, 8, 1, 0, _ST()), "bad payoff"),
+    (_P, lambda: (*_PRICE, 0, 0.0, 0, 64, 8, 1, 0, _ST()), "Barrier must be positive"),
+    (_P, lambda: (*_PRICE, 3, -120.0, 0, 64, 8, 1, 0, _ST()), "Barrier must be positive"),
+    (_P, lambda: (*_BAD_RHO, 6, 0.0, 0, 64, 8, 1, 0, _ST()), "rho must be in [-1, 1]"),
+    (_P, lambda: (*_PRICE, 6, 0.0, 0, 64, 8, 1, 0, None), "null pointer"),
+    (_P, lambda: (*_PRICE, 6, 0.0, 0, 0, 8, 1, 0, _ST()), "n_paths must be >= 1"),
+    (_P, lambda: (*_PRICE, 7, 0.0, 0, 64, 0, 1, 0, _ST()), "n_steps must be >= 1"),
+    (_P, lambda: (*_PRICE, 4, 0.0, -1, 64, 8, 1, 0, _ST()), "path_offset must be >= 0"),
+    (_Q, lambda: (*_PRICE, 8, 0.0, 1, 0, 64, 8, *_sobol(16), 30, 0, _ST()), "bad payoff"),
+    (_Q, lambda: (*_PRICE, 2, 0.0, 1, 0, 64, 8, *_sobol(16), 30, 0, _ST()), "Barrier must be positive"),
+    (_Q, lambda: (*_PRICE, 1, -1.0, 0, 0, 64, 8, *_sobol(16), 30, 0, _ST()), "Barrier must be positive"),
+    (_Q, lambda: (*_BAD_RHO, 6, 0.0, 0, 0, 64, 8, *_sobol(16), 30, 0, _ST()), "rho must be in [-1, 1]"),
+    (_Q, lambda: (*_PRICE, 6, 0.0, 1, 0, 64, 1025, *_sobol(2), 30, 0, _ST()), _BRIDGE_CAP),
+    (_Q, lambda: (*_PRICE, 5, 0.0, 0, 0, 64, 10601, *_sobol(2), 30, 0, _ST()), _STEPS),
+    (_Q, lambda: (*_PRICE, 5, 0.0, 0, 0, 64, 0, *_sobol(2), 30, 0, _ST()), _STEPS),
+    (_Q, lambda: (*_PRICE, 6, 0.0, 1, 0, 64, 8, *_sobol(16), 29, 0, _ST()), _BITS),
+    (_Q, lambda: (*_PRICE, 6, 0.0, 2, 0, 64, 8, *_sobol(16), 30, 0, _ST()), "bad construction"),
+    (_Q, lambda: (*_PRICE, 6, 0.0, 1, 0, 64, 8, None, _sobol(16)[1], 30, 0, _ST()), "null pointer"),
+    (_Q, lambda: (*_PRICE, 6, 0.0, 1, 0, 64, 8, _sobol(16)[0], None, 30, 0, _ST()), "null pointer"),
+    (_Q, lambda: (*_PRICE, 6, 0.0, 1, 0, 64, 8, *_sobol(16), 30, 0, None), "null pointer"),
+    (_Q, lambda: (*_PRICE, 7, 0.0, 0, 0, 0, 8, *_sobol(16), 30, 0, _ST()), "n_paths must be >= 1"),
+    (_Q, lambda: (*_PRICE, 7, 0.0, 0, 1, 1 << 30, 8, *_sobol(16), 30, 0, _ST()), "at most 2**30 Sobol points"),
+]
+
+
+@pytest.mark.parametrize("name,args,message", _REFUSALS, ids=[f"{n}-{i}" for i, (n, _a, _m) in enumerate(_REFUSALS)])
+def test_entry_points_refuse_bad_arguments_before_touching_a_device(library, name, args, message):
+    """Each refusal answers OLMC_ERR_ARG (1) with its exact message, ahead of any device work (no device is initialised here)."""
+    rc = getattr(library, name)(*args())
+    assert rc == 1
+    assert library.olmc_last_error().decode() == message
+
+
+# --------------------------------------------------------------------------------------------------------- the methods ----
+@pytest.fixture
+def no_library(monkeypatch):
+    """Any attempt to load the library (hence to reach the device) fails the test."""
+    def touched(*a, **k):
+        raise AssertionError("the library was loaded")
+
+    monkeypatch.setattr(_hip, "lib", touched)
+
+
+@pytest.mark.parametrize("kwargs,match", [
+    (dict(method="sobol"), "method"),
+    (dict(method="qmc", path_construction="pca"), "path_construction"),
+    (dict(method="pseudo", path_construction="brownian"), "path_construction"),
+    (dict(method="qmc", n_steps=1025), "1024"),
+    (dict(method="qmc", n_steps=10601, path_construction="sequential"), "10600"),
+    (dict(method="qmc", n_paths=(1 << 30) + 1), r"2\*\*30"),
+    (dict(n_paths=0), "n_paths"),
+    (dict(method="qmc", n_steps=0), "n_steps"),
+])
+def test_refusals_come_before_the_device(no_library, kwargs, match):
+    for call in _calls(_pricer()):
+        kw = dict(n_paths=100, n_steps=8)
+        kw.update(kwargs)
+        with pytest.raises(ValueError, match=match):
+            call(**kw)
+
+
+def test_the_payoff_keywords_are_checked_before_the_device(no_library):
+    p = _pricer()
+    with pytest.raises(ValueError, match="avg_type"):
+        p.price_asian(S, K, T, R, Q, "call", "harmonic", 100, 8, 1)
+    with pytest.raises(ValueError, match="lookback_type"):
+        p.price_lookback(S, K, T, R, Q, "call", "partial", 100, 8, 1, method="qmc")
+    for barrier in (0.0, -120.0):
+        with pytest.raises(ValueError, match="^Barrier must be positive$"):
+            p.price_barrier(S, K, T, R, barrier, Q, "call", "up-and-out", 100, 8, 1)
+    with pytest.raises(TypeError):                                                  # method and path_construction are keyword-only
+        p.price_asian(S, K, T, R, Q, "call", "arithmetic", 100, 8, 3, False, False, "qmc")
+    with pytest.raises(TypeError):
+        p.price_barrier(S, K, T, R, 120.0, Q, "call", "up-and-out", 100, 8, 3, False, False, "qmc")
+    with pytest.raises(TypeError):
+        p.price_lookback(S, K, T, R, Q, "call", "floating", 100, 8, 3, False, False, "qmc")
+
+
+def test_the_methods_reach_the_bindings_with_the_headers_payoff_codes(no_library, monkeypatch):
+    calls = []
+
+    def recorder(name):
+        def call(*a, **k):
+            calls.append((name, a, k))
+            st = _hip.Stats()
+            st.price, st.std_error = 1.25, 0.5
+            return st
+        return call
+
+    for name in ("heston_path_payoff", "heston_qmc_path_payoff"):
+        monkeypatch.setattr(_hip, name, recorder(name))
+    p = _pricer()
+    head = (S, K, T, R, Q)
+    got = p.price_asian(*head, "put", "geometric", 100, 8, 3, True)
+    assert isinstance(got, np.float64) and got == 1.25
+    assert p.price_asian(*head, n_paths=100, n_steps=8, seed=3, return_error=True) == (1.25, 0.5)
+    p.price_lookback(*head, "call", "fixed", 100, 8, 3)
+    p.price_lookback(*head, "call", "floating", 100, 8, 3)
+    for kind, code in (("up-and-out", 0), ("up-and-in", 1), ("down-and-out", 2), ("down-and-in", 3), ("up-or-out", 0), ("down-then-in", 3)):
+        p.price_barrier(S, K, T, R, 120.0, Q, "call", kind, 100, 8, 3)
+        assert calls[-1] == ("heston_path_payoff", (*head, True, *MODEL, code, 120.0, 100, 8, 3, False), {})
+    assert calls[:4] == [
+        ("heston_path_payoff", (*head, False, *MODEL, 7, 0.0, 100, 8, 3, True), {}),
+        ("heston_path_payoff", (*head, True, *MODEL, 6, 0.0, 100, 8, 3, False), {}),
+        ("heston_path_payoff", (*head, True, *MODEL, 5, 0.0, 100, 8, 3, False), {}),
+        ("heston_path_payoff", (*head, True, *MODEL, 4, 0.0, 100, 8, 3, False), {}),
+    ]
+    from optionslab_amd.monte_carlo import sobol_tables
+
+    sv, shift = sobol_tables(16, 3, 100)                                            # d = 2 n; the seed is the scramble seed
+    for construction, bridge in (("bridge", True), ("sequential", False)):
+        p.price_barrier(S, K, T, R, 85.0, Q, "put", "down-and-in", 100, 8, 3, True, method="qmc", path_construction=construction)
+        name, a, k = calls[-1]
+        assert name == "heston_qmc_path_payoff" and not k
+        assert a[:14] == (*head, False, *MODEL, 3, 85.0, 100) and a[16:] == (bridge, True)
+        assert np.array_equal(a[14], sv) and np.array_equal(a[15], shift)
+    p.price_asian(*head, n_paths=100, n_steps=8, seed=3, method="qmc")
+    assert calls[-1][1][16] is True                                                 # the default construction is the bridge
+
+
+def test_the_bindings_refuse_tables_with_an_odd_number_of_dimensions(no_library):
+    sv, shift = np.ones((7, 30), np.uint32), np.zeros(7, np.uint32)
+    with pytest.raises(ValueError, match="even"):
+        _hip.heston_qmc_path_payoff(S, K, T, R, Q, True, *MODEL, 6, 0.0, 64, sv, shift)
+
+
+# --------------------------------------------------------------------------------------------------------- the fixture ----
+def test_the_reference_fixture_holds_32_finite_prices_with_positive_standard_errors():
+    with open(os.path.join(ROOT, "tests", "golden", "heston_path_payoffs.json")) as f:
+        doc = json.load(f)
+    rows = doc["prices"]
+    assert len(rows) == 32
+    assert len({(r["model"], r["payoff"], r["option_type"]) for r in rows}) == 32
+    assert {r["model"] for r in rows} == set(doc["models"]) and len(doc["models"]) == 2
+    assert len({r["payoff"] for r in rows}) == 8 and {r["option_type"] for r in rows} == {"call", "put"}
+    for r in rows:
+        assert math.isfinite(r["price"]) and r["price"] > 0.0
+        assert math.isfinite(r["std_error"]) and r["std_error"] > 0.0
+    assert doc["inputs"]["n_paths"] == 100_000 and doc["inputs"]["n_steps"] == 64
