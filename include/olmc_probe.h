@@ -4,7 +4,7 @@
  * test seams switched in, plus the kernels and entry points below; it also exports everything include/olmc.h declares (so a test
  * can price through it), with contexts of its own.  libolmc.so exports NONE of the symbols declared here and contains no
  * fault-injection branch.  Same conventions as olmc.h: int status, 0 = ok, olmc_last_error() of the SAME library for the text.
- * Who loads it: tests/ (device-guard, failing-shard, multi-rank rehearsal, exp2 and moment taps), tools/ (phase stamps, issue
+ * Who loads it: tests/ (device-guard, failing-shard, multi-rank rehearsal, exp2, inverse-normal, Box-Muller, square-root and moment taps), tools/ (phase stamps, issue
  * probes), bench.py (clock and issue-cost calibration of the roofline) -- through tools/probe/binding.py. */
 #ifndef OLMC_PROBE_H
 #define OLMC_PROBE_H
@@ -26,6 +26,15 @@ int olmc_exp2_probe_form(const double* x_host, int64_t n, double* y_host, int fo
  * 2 = two in lockstep, 3 = eight in lockstep: the four must agree bit for bit (the Sobol kernels' sums do not depend on the launch
  * shape because of it). */
 int olmc_ndtri_probe(const double* p_host, int64_t n, double* z_host, int form);
+/* The normal generator under every Philox kernel, on CHOSEN words (host arrays of n): z_cos[i], z_sin[i] = box_muller_raw(xa[i],
+ * xb[i]) and pair[i] = pair_sum_raw(0, xa[i], xb[i]) of olmc_kernels.h -- RAW normals, in units of 1 / sqrt(2 ln 2) (the pair sum in
+ * units of (z_cos + z_sin) / sqrt(2)), as the kernels carry them before kZScale / kPairZScale.  Reaches the words a seeded stream
+ * meets once in 2^25 draws: a radius that rounds to 1, the deep tail, the zeros of the hardware sine / cosine, the wrap of the
+ * eighth-turn shift. */
+int olmc_box_muller_probe(const uint32_t* xa, const uint32_t* xb, int64_t n, float* z_cos, float* z_sin, float* pair);
+/* The Heston kernels' square root (sqrt_nonneg, olmc_kernels.h): y[i] = sqrt_nonneg(x[i]), host arrays.  A negative or non-finite
+ * x[i] is an argument error (the kernels only ever hand it a truncated variance). */
+int olmc_sqrt_nonneg_probe(const double* x, int64_t n, double* y);
 /* Power sums of the normal stream: out4[m-1] = sum over paths and steps of z^m, m = 1..4 (fp64). */
 int olmc_normal_moments(uint64_t seed, int64_t path_offset, int64_t n_paths, int32_t n_steps, double* out4);
 

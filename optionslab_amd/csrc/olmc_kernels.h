@@ -2179,9 +2179,11 @@ struct HestonContract {
 };
 
 // sqrt of a non-negative finite fp64 from an fp32 v_rsq_f32 seed (2^-22) and one coupled Newton/Goldschmidt
-// round plus a residual correction: 1 ulp (checked against sqrt over [1e-12, 10]), 10 instructions against
+// round plus a residual correction: 1 ulp against sqrt over [1e-12, 10], 10 instructions against
 // the 17 + v_rsq_f64 of the library expansion (which also handles inf / NaN / subnormals: not needed for a
 // truncated variance).  x = 0 gives 0; x below 1e-30 loses accuracy (sqrt < 1e-15: immaterial here).
+// Pinned point by point through olmc_sqrt_nonneg_probe by tests/test_gpu_box_muller.py
+// (test_sqrt_nonneg_*): the ulp bound, exact squares, x = 0, and 2^-40 relative out to 1e-30 / 1e30.
 __device__ __forceinline__ double sqrt_nonneg(double x) {
     const double r = static_cast<double>(__builtin_amdgcn_rsqf(fmaxf(static_cast<float>(x), 1e-30f)));
     double g = x * r, h = 0.5 * r;

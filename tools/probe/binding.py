@@ -37,6 +37,8 @@ def _second_binding():
         "olmc_exp2_probe": (_I, [C.POINTER(_D), _I64, C.POINTER(_D)]),
         "olmc_exp2_probe_form": (_I, [C.POINTER(_D), _I64, C.POINTER(_D), _I]),
         "olmc_ndtri_probe": (_I, [C.POINTER(_D), _I64, C.POINTER(_D), _I]),
+        "olmc_box_muller_probe": (_I, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I64] + [C.POINTER(C.c_float)] * 3),
+        "olmc_sqrt_nonneg_probe": (_I, [C.POINTER(_D), _I64, C.POINTER(_D)]),
         "olmc_normal_moments": (_I, [_U64T, _I64, _I64, _I32, C.POINTER(_D)]),
         "olmc_phase_stamps": (_I, [_I64, _I32, _U64T, _I32, C.POINTER(C.c_uint64), _I64, C.POINTER(_I64)]),
         "olmc_clock_probe": (_I, [_I64, _I32, _U64T, C.POINTER(_D)]),
@@ -49,8 +51,9 @@ def _second_binding():
 
 
 hip = _second_binding()
-PROBE_PROTOTYPES = ("olmc_exp2_probe", "olmc_exp2_probe_form", "olmc_ndtri_probe", "olmc_normal_moments", "olmc_phase_stamps", "olmc_clock_probe",
-                    "olmc_issue_probe", "olmc_probe_tune", "olmc_european_f64_normals", "olmc_launch_gap_probe")
+PROBE_PROTOTYPES = ("olmc_exp2_probe", "olmc_exp2_probe_form", "olmc_ndtri_probe", "olmc_box_muller_probe", "olmc_sqrt_nonneg_probe",
+                    "olmc_normal_moments", "olmc_phase_stamps", "olmc_clock_probe", "olmc_issue_probe", "olmc_probe_tune",
+                    "olmc_european_f64_normals", "olmc_launch_gap_probe")
 _check, lib, seed64 = hip._check, hip.lib, hip.seed64
 
 TUNE_FAULT_SHARD = 5
@@ -81,6 +84,28 @@ def ndtri_probe(p: np.ndarray, form: int = 0) -> np.ndarray:
     z = np.empty_like(p)
     _check(lib().olmc_ndtri_probe(p.ctypes.data_as(C.POINTER(C.c_double)), p.size, z.ctypes.data_as(C.POINTER(C.c_double)), int(form)))
     return z
+
+
+def box_muller_probe(xa: np.ndarray, xb: np.ndarray, chunk: int = 1 << 22):
+    """(z_cos, z_sin, pair) in fp32 RAW units: box_muller_raw(xa, xb) and pair_sum_raw(0, xa, xb) of olmc_kernels.h on chosen words
+    (uint32 arrays of one shape), at most `chunk` words per call of the tap."""
+    xa, xb = np.ascontiguousarray(xa, dtype=np.uint32).ravel(), np.ascontiguousarray(xb, dtype=np.uint32).ravel()
+    if xa.size != xb.size:
+        raise ValueError("xa and xb must have one size")
+    out = [np.empty(xa.size, dtype=np.float32) for _ in range(3)]
+    u32, f32 = C.POINTER(C.c_uint32), C.POINTER(C.c_float)
+    for lo in range(0, xa.size, int(chunk)):
+        n = min(int(chunk), xa.size - lo)
+        _check(lib().olmc_box_muller_probe(xa[lo:].ctypes.data_as(u32), xb[lo:].ctypes.data_as(u32), n, *(o[lo:].ctypes.data_as(f32) for o in out)))
+    return tuple(out)
+
+
+def sqrt_nonneg_probe(x: np.ndarray) -> np.ndarray:
+    """sqrt_nonneg (the Heston kernels' square root, olmc_kernels.h) on non-negative finite doubles."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    y = np.empty_like(x)
+    _check(lib().olmc_sqrt_nonneg_probe(x.ctypes.data_as(C.POINTER(C.c_double)), x.size, y.ctypes.data_as(C.POINTER(C.c_double))))
+    return y
 
 
 def normal_moments(seed: int, n_paths: int, n_steps: int, path_offset: int = 0):

@@ -60,6 +60,57 @@ extern "C" int olmc_ndtri_probe(const double* p_host, int64_t n, double* z_host,
     return OLMC_OK;
 }
 
+// box_muller_raw / pair_sum_raw on chosen words (box_muller_probe_kernel): bulk buffer = [xa | xb | z_cos | z_sin | pair], n words each.
+extern "C" int olmc_box_muller_probe(const uint32_t* xa_host, const uint32_t* xb_host, int64_t n, float* z_cos_host, float* z_sin_host,
+                                     float* pair_host) {
+    if (!xa_host || !xb_host || !z_cos_host || !z_sin_host || !pair_host || n < 1) return fail(OLMC_ERR_ARG, "bad arguments");
+    CtxLease lease;
+    int rc = ctx_lease(&lease);
+    if (rc) return rc;
+    DeviceCtx* const c = lease.c;
+    const size_t bytes = sizeof(uint32_t) * static_cast<size_t>(n);
+    static_assert(sizeof(uint32_t) == sizeof(float), "one stride for words and normals");
+    rc = bulk_reserve(c, 5 * bytes);
+    if (rc) return rc;
+    uint32_t* d_xa = static_cast<uint32_t*>(c->d_bulk);
+    uint32_t* d_xb = d_xa + n;
+    float* d_cos = reinterpret_cast<float*>(d_xb + n);
+    float* d_sin = d_cos + n;
+    float* d_pair = d_sin + n;
+    HIP_TRY(hipMemcpyAsync(d_xa, xa_host, bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_xb, xb_host, bytes, hipMemcpyHostToDevice, c->stream));
+    const int grid = static_cast<int>(std::min<int64_t>((n + 255) / 256, 4096));
+    hipLaunchKernelGGL(box_muller_probe_kernel, dim3(grid), dim3(256), 0, c->stream, d_xa, d_xb, n, d_cos, d_sin, d_pair);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(z_cos_host, d_cos, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(z_sin_host, d_sin, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(pair_host, d_pair, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return OLMC_OK;
+}
+
+extern "C" int olmc_sqrt_nonneg_probe(const double* x_host, int64_t n, double* y_host) {
+    if (!x_host || !y_host || n < 1) return fail(OLMC_ERR_ARG, "bad arguments");
+    for (int64_t i = 0; i < n; ++i)
+        if (!(x_host[i] >= 0.0 && x_host[i] <= std::numeric_limits<double>::max())) return fail(OLMC_ERR_ARG, "an argument that is negative or not finite");
+    CtxLease lease;
+    int rc = ctx_lease(&lease);
+    if (rc) return rc;
+    DeviceCtx* const c = lease.c;
+    const size_t bytes = sizeof(double) * static_cast<size_t>(n);
+    rc = bulk_reserve(c, 2 * bytes);
+    if (rc) return rc;
+    double* d_x = static_cast<double*>(c->d_bulk);
+    double* d_y = d_x + n;
+    HIP_TRY(hipMemcpyAsync(d_x, x_host, bytes, hipMemcpyHostToDevice, c->stream));
+    const int grid = static_cast<int>(std::min<int64_t>((n + 255) / 256, 4096));
+    hipLaunchKernelGGL(sqrt_nonneg_probe_kernel, dim3(grid), dim3(256), 0, c->stream, d_x, n, d_y);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(y_host, d_y, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return OLMC_OK;
+}
+
 extern "C" int olmc_normal_moments(uint64_t seed, int64_t path_offset, int64_t n_paths, int32_t n_steps, double* out4) {
     if (!out4) return fail(OLMC_ERR_ARG, "null pointer");
     olmc_stats dummy;

@@ -288,6 +288,25 @@ __global__ void ndtri_probe_kernel(const double* __restrict__ p, int64_t n, doub
     }
 }
 
+// The normal generator under every Philox kernel on chosen words: box_muller_raw and pair_sum_raw (olmc_kernels.h) themselves, RAW
+// units (no kZScale).  z_cos[i], z_sin[i] = the pair of (xa[i], xb[i]); pair[i] = 0 + (z_cos + z_sin) / sqrt(2) by the one-sine form.
+__global__ void box_muller_probe_kernel(const uint32_t* __restrict__ xa, const uint32_t* __restrict__ xb, int64_t n, float* __restrict__ z_cos,
+                                        float* __restrict__ z_sin, float* __restrict__ pair) {
+    for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+        float c, s;
+        box_muller_raw(xa[i], xb[i], c, s);
+        z_cos[i] = c;
+        z_sin[i] = s;
+        pair[i] = pair_sum_raw(0.0f, xa[i], xb[i]);
+    }
+}
+
+// The Heston kernels' square root (sqrt_nonneg, olmc_kernels.h) on an array of non-negative finite doubles.
+__global__ void sqrt_nonneg_probe_kernel(const double* __restrict__ x, int64_t n, double* __restrict__ y) {
+    for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += static_cast<int64_t>(gridDim.x) * blockDim.x)
+        y[i] = sqrt_nonneg(x[i]);
+}
+
 // ---------------------------------------------------------------- the price of the reference's own width (round 4) ----
 // The European step loop with fp64 NORMALS, as NumPy draws them (gbm_numpy.py:32-33: standard_normal of a PCG64 Generator, fp64):
 // the same Philox4x32-10 counter stream, but one block now yields TWO normals -- its four words make two 53-bit uniforms
