@@ -4,7 +4,8 @@
  * test seams switched in, plus the kernels and entry points below; it also exports everything include/olmc.h declares (so a test
  * can price through it), with contexts of its own.  libolmc.so exports NONE of the symbols declared here and contains no
  * fault-injection branch.  Same conventions as olmc.h: int status, 0 = ok, olmc_last_error() of the SAME library for the text.
- * Who loads it: tests/ (device-guard, failing-shard, multi-rank rehearsal, exp2, inverse-normal, Box-Muller, square-root and moment taps), tools/ (phase stamps, issue
+ * Who loads it: tests/ (device-guard, failing-shard, multi-rank rehearsal, exp2, inverse-normal, Box-Muller, square-root and moment taps, and the three taps of the
+ * fused grid reduction: olmc_reduce_probe, olmc_rows_sum_probe, olmc_wave_reduce_probe), tools/ (phase stamps, issue
  * probes), bench.py (clock and issue-cost calibration of the roofline) -- through tools/probe/binding.py. */
 #ifndef OLMC_PROBE_H
 #define OLMC_PROBE_H
@@ -37,6 +38,26 @@ int olmc_box_muller_probe(const uint32_t* xa, const uint32_t* xb, int64_t n, flo
 int olmc_sqrt_nonneg_probe(const double* x, int64_t n, double* y);
 /* Power sums of the normal stream: out4[m-1] = sum over paths and steps of z^m, m = 1..4 (fp64). */
 int olmc_normal_moments(uint64_t seed, int64_t path_offset, int64_t n_paths, int32_t n_steps, double* out4);
+/* The fused grid reduction (olmc_kernels.h) on SYNTHETIC per-thread values with an exact answer.  `launches` launches, launch j on
+ * ceil(n_threads[j] / 256) workgroups of 256 threads (at most 2^18 workgroups), through the product's own launch plumbing and
+ * workspace; thread t of workgroup b contributes H(b, c, salt[j]) + K(t, c, salt[j]) to component c when 256 b + t < n_threads[j],
+ * else 0.0 -- H a 24-bit, K a 16-bit odd integer hash (written out in tools/probe/olmc_probe_kernels.h and restated by
+ * tests/reduction_reference.py), so every partial sum is exact in fp64 and the totals must EQUAL integers.  values 0 = those
+ * integers, 1 = double(H + K) / 3.0 (sums round).  nv in {2, 5, 8, 16, 32}.  form 0 = block_then_grid_reduce<nv>, 1 =
+ * block_then_grid_reduce_from<nv, 1> with the first exchange made by the producer (nv 8, 16, 32 only), 2 = block_row_sum<nv> then
+ * grid_reduce<nv> (nv = 2) / grid_reduce_workgroup<nv> called directly.  blocking 1 = each launch writes the context's pinned result
+ * and completes through the polled flag; 0 = all launches queued back to back on one stream with no host wait between them, each into
+ * its own slot of a device buffer, one synchronise and one copy at the end.  out[launches][nv + 1] (host): the nv totals, then the
+ * workspace's tail (= n_threads[j]).  Where a launch refuses to store (the device-side row-capacity guard) the totals are NaN and the
+ * tail is -1 (blocking) or NaN. */
+int olmc_reduce_probe(int nv, int form, int values, int blocking, int32_t launches, const int64_t* n_threads, const uint64_t* salt,
+                      double* out);
+/* The row summers on a host matrix rows_host[rows][nv] (rows in [1, 2^20]): out_nv[c] = sum of column c by wave_rows_sum<nv>
+ * (whole_workgroup 0: one wave, nv 2 or 5) or workgroup_rows_sum<nv> (whole_workgroup 1: 256 threads, nv 5, 8, 16 or 32). */
+int olmc_rows_sum_probe(int nv, int whole_workgroup, const double* rows_host, int32_t rows, double* out_nv);
+/* wave_transpose_reduce<p, 32, op> on one wave, p in {1, 2, 4, 8, 16, 32}, op 0 = sum, 1 = max, 2 = min: lane l starts from
+ * v_host[l][0 .. p); out[l] = its v[0] afterwards, the result of value index l >> (6 - log2 p). */
+int olmc_wave_reduce_probe(int p, int op, const double* v_host, double* out);
 
 /* ---- where a launch spends its time --------------------------------------- */
 /* One launch of the headline kernel (European call, antithetic, n_paths x n_steps, production launch shape): wave 0 of every

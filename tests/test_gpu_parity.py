@@ -773,10 +773,24 @@ def test_one_seed_gives_one_pair_of_sums_thousands_of_times_under_load():
     gate.  So: the same pricing thousands of times (the headline 1M x 252: 3,907 rows in two levels; 8M x 252: 31,250 rows; the
     14-contract Greeks: 32-wide rows summed by a whole workgroup; 10k x 50: one level), while seven other threads keep seven other
     contexts of the device busy with launches of other sizes -- ONE distinct (sum, sumsq) each.  OLMC_REPRO_SCALE multiplies the counts
-    (10 = the 20,000 pricings VERDICT r4 asked for)."""
+    (10 = the 20,000 pricings VERDICT r4 asked for).
+
+    The calls ALTERNATE two seeds, 42 and 43.  The row a late reader would find stale is the one the launch before left in the same
+    slot of the workspace; with one seed that row has the very bits of the fresh one and the failure this test exists for would leave
+    it green.  With two seeds the row left over belongs to the other seed and changes the sum.  Each seed must show exactly one
+    (sum, sumsq), and it must be the pair computed for that seed before the load threads start."""
     import threading
     scale = float(os.environ.get("OLMC_REPRO_SCALE", "1"))
     stop, errs = threading.Event(), []
+    SEEDS = (42, 43)
+    cases = (
+        ("1M x 252", int(2000 * scale), lambda seed: (lambda st: (st.sum, st.sumsq))(_hip.european(*ATM, 0.0, True, 1_000_000, 252, seed, True))),
+        ("8M x 252", int(150 * scale), lambda seed: (lambda st: (st.sum, st.sumsq))(_hip.european(*ATM, 0.0, True, 8_000_000, 252, seed, True))),
+        ("10k x 50", int(3000 * scale), lambda seed: (lambda st: (st.sum, st.sumsq))(_hip.european(*ATM, 0.0, True, 10_000, 50, seed, True))),
+        ("greeks14 1M x 64", int(500 * scale), lambda seed: tuple(_hip.european_greeks_fd(*ATM, 0.0, True, 1_000_000, 64, seed, True, want_evals=False)[0])))
+    quiet = {what: {seed: fn(seed) for seed in SEEDS} for what, _reps, fn in cases}      # on an otherwise idle device
+    for what, pair in quiet.items():
+        assert pair[42] != pair[43], (what, "the two seeds must differ in bits, or a stale row could not show")
 
     def load(k):
         try:
@@ -794,13 +808,14 @@ def test_one_seed_gives_one_pair_of_sums_thousands_of_times_under_load():
     ts = [threading.Thread(target=load, args=(k,)) for k in range(7)]
     [t.start() for t in ts]
     try:
-        for what, reps, fn in (
-                ("1M x 252", int(2000 * scale), lambda: (lambda st: (st.sum, st.sumsq))(_hip.european(*ATM, 0.0, True, 1_000_000, 252, 42, True))),
-                ("8M x 252", int(150 * scale), lambda: (lambda st: (st.sum, st.sumsq))(_hip.european(*ATM, 0.0, True, 8_000_000, 252, 42, True))),
-                ("10k x 50", int(3000 * scale), lambda: (lambda st: (st.sum, st.sumsq))(_hip.european(*ATM, 0.0, True, 10_000, 50, 42, True))),
-                ("greeks14 1M x 64", int(500 * scale), lambda: tuple(_hip.european_greeks_fd(*ATM, 0.0, True, 1_000_000, 64, 42, True, want_evals=False)[0]))):
-            seen = {fn() for _ in range(reps)}
-            assert len(seen) == 1, (what, len(seen), sorted(seen)[:3])
+        for what, reps, fn in cases:                        # the same number of pricings as with one seed
+            seen = {seed: set() for seed in SEEDS}
+            for i in range(reps):
+                seed = SEEDS[i & 1]
+                seen[seed].add(fn(seed))
+            for seed in SEEDS:
+                assert len(seen[seed]) == 1, (what, seed, len(seen[seed]), sorted(seen[seed])[:3])
+                assert seen[seed] == {quiet[what][seed]}, (what, seed, "other bits under load than on the idle device")
     finally:
         stop.set()
         [t.join() for t in ts]

@@ -40,6 +40,9 @@ def _second_binding():
         "olmc_box_muller_probe": (_I, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I64] + [C.POINTER(C.c_float)] * 3),
         "olmc_sqrt_nonneg_probe": (_I, [C.POINTER(_D), _I64, C.POINTER(_D)]),
         "olmc_normal_moments": (_I, [_U64T, _I64, _I64, _I32, C.POINTER(_D)]),
+        "olmc_reduce_probe": (_I, [_I, _I, _I, _I, _I32, C.POINTER(_I64), C.POINTER(_U64T), C.POINTER(_D)]),
+        "olmc_rows_sum_probe": (_I, [_I, _I, C.POINTER(_D), _I32, C.POINTER(_D)]),
+        "olmc_wave_reduce_probe": (_I, [_I, _I, C.POINTER(_D), C.POINTER(_D)]),
         "olmc_phase_stamps": (_I, [_I64, _I32, _U64T, _I32, C.POINTER(C.c_uint64), _I64, C.POINTER(_I64)]),
         "olmc_clock_probe": (_I, [_I64, _I32, _U64T, C.POINTER(_D)]),
         "olmc_issue_probe": (_I, [_I, _I, C.POINTER(_D)]),
@@ -52,7 +55,7 @@ def _second_binding():
 
 hip = _second_binding()
 PROBE_PROTOTYPES = ("olmc_exp2_probe", "olmc_exp2_probe_form", "olmc_ndtri_probe", "olmc_box_muller_probe", "olmc_sqrt_nonneg_probe",
-                    "olmc_normal_moments", "olmc_phase_stamps", "olmc_clock_probe", "olmc_issue_probe", "olmc_probe_tune",
+                    "olmc_normal_moments", "olmc_reduce_probe", "olmc_rows_sum_probe", "olmc_wave_reduce_probe", "olmc_phase_stamps", "olmc_clock_probe", "olmc_issue_probe", "olmc_probe_tune",
                     "olmc_european_f64_normals", "olmc_launch_gap_probe")
 _check, lib, seed64 = hip._check, hip.lib, hip.seed64
 
@@ -113,6 +116,42 @@ def normal_moments(seed: int, n_paths: int, n_steps: int, path_offset: int = 0):
     out = (C.c_double * 4)()
     _check(lib().olmc_normal_moments(seed64(seed), int(path_offset), int(n_paths), int(n_steps), out))
     return tuple(out)
+
+
+def reduce_probe(nv: int, form: int, n_threads, salts, values: int = 0, blocking: bool = True) -> np.ndarray:
+    """out[launches, nv + 1] of olmc_reduce_probe: the fused grid reduction (form 0 block_then_grid_reduce, 1 the folded first
+    exchange, 2 block_row_sum + grid_reduce[_workgroup]) on the synthetic values of tests/reduction_reference.py, one launch per entry
+    of n_threads / salts; the last column is the workspace's tail (= n_threads).  blocking=False queues every launch back to back."""
+    n = np.ascontiguousarray(n_threads, dtype=np.int64).ravel()
+    s = np.ascontiguousarray(salts, dtype=np.uint64).ravel()
+    if n.size != s.size:
+        raise ValueError("n_threads and salts must have one size")
+    out = np.full((n.size, int(nv) + 1), np.nan, dtype=np.float64)
+    _check(lib().olmc_reduce_probe(int(nv), int(form), int(values), int(bool(blocking)), n.size, n.ctypes.data_as(C.POINTER(C.c_int64)),
+                                   s.ctypes.data_as(C.POINTER(C.c_uint64)), out.ctypes.data_as(C.POINTER(C.c_double))))
+    return out
+
+
+def rows_sum_probe(rows: np.ndarray, whole_workgroup: bool) -> np.ndarray:
+    """Column sums of rows[n, nv] by wave_rows_sum<nv> (one wave) or workgroup_rows_sum<nv> (whole_workgroup)."""
+    rows = np.ascontiguousarray(rows, dtype=np.float64)
+    out = np.full(rows.shape[1], np.nan, dtype=np.float64)
+    _check(lib().olmc_rows_sum_probe(rows.shape[1], int(bool(whole_workgroup)), rows.ctypes.data_as(C.POINTER(C.c_double)), rows.shape[0],
+                                     out.ctypes.data_as(C.POINTER(C.c_double))))
+    return out
+
+
+WAVE_OPS = {"sum": 0, "max": 1, "min": 2}
+
+
+def wave_reduce_probe(v: np.ndarray, op: str = "sum") -> np.ndarray:
+    """out[64]: every lane's v[0] after wave_transpose_reduce<p, 32, op> on v[64, p] (lane l: value index l >> (6 - log2 p))."""
+    v = np.ascontiguousarray(v, dtype=np.float64)
+    if v.ndim != 2 or v.shape[0] != 64:
+        raise ValueError("v must be [64, p]")
+    out = np.full(64, np.nan, dtype=np.float64)
+    _check(lib().olmc_wave_reduce_probe(v.shape[1], WAVE_OPS[op], v.ctypes.data_as(C.POINTER(C.c_double)), out.ctypes.data_as(C.POINTER(C.c_double))))
+    return out
 
 
 def phase_stamps(n_paths: int = 1_000_000, n_steps: int = 252, seed: int = 42, lead_launches: int = 20):

@@ -111,6 +111,156 @@ extern "C" int olmc_sqrt_nonneg_probe(const double* x_host, int64_t n, double* y
     return OLMC_OK;
 }
 
+// ---- the fused grid reduction on synthetic values (reduce_probe_kernel) ----
+namespace {
+template <int NV>
+void launch_reduce_probe(int form, int32_t grid, hipStream_t st, const EventPair* timed, int64_t n, uint64_t salt, int values, const ReduceWs& ws) {
+    if (form == 0) launch_timed(reduce_probe_kernel<NV, 0>, dim3(grid), dim3(kBlock), st, timed, n, salt, values, ws);
+    else if (form == 2) launch_timed(reduce_probe_kernel<NV, 2>, dim3(grid), dim3(kBlock), st, timed, n, salt, values, ws);
+    else if constexpr (NV >= 8) launch_timed(reduce_probe_kernel<NV, 1>, dim3(grid), dim3(kBlock), st, timed, n, salt, values, ws);
+}
+
+// f(integral_constant<int, NV>) for the row widths the product instantiates; false for any other nv.
+template <typename F>
+bool with_reduce_width(int nv, F&& f) {
+    switch (nv) {
+        case 2: f(std::integral_constant<int, 2>{}); return true;
+        case 5: f(std::integral_constant<int, 5>{}); return true;
+        case 8: f(std::integral_constant<int, 8>{}); return true;
+        case 16: f(std::integral_constant<int, 16>{}); return true;
+        case 32: f(std::integral_constant<int, 32>{}); return true;
+        default: return false;
+    }
+}
+}  // namespace
+
+// `launches` launches of reduce_probe_kernel<nv, form> through launch_reduce / make_ws, launch j on ceil(n_threads[j] / 256)
+// workgroups with ws.tail = n_threads[j]; out[j] = {the nv totals, the tail}.  blocking = 1: every launch writes the context's pinned
+// result and completes through the polled flag, as a blocking pricing does.  blocking = 0: all launches are queued back to back on
+// the context's stream with no host wait in between, each into its own slot of a device buffer; one copy and one synchronise follow.
+extern "C" int olmc_reduce_probe(int nv, int form, int values, int blocking, int32_t launches, const int64_t* n_threads, const uint64_t* salt,
+                                 double* out) {
+    if (!n_threads || !salt || !out) return fail(OLMC_ERR_ARG, "null pointer");
+    if (nv != 2 && nv != 5 && nv != 8 && nv != 16 && nv != 32) return fail(OLMC_ERR_ARG, "nv must be 2, 5, 8, 16 or 32");
+    if (form < 0 || form > 2) return fail(OLMC_ERR_ARG, "form must be 0, 1 or 2");
+    if (form == 1 && nv < 8) return fail(OLMC_ERR_ARG, "form 1 (the folded first exchange) exists for nv 8, 16 and 32");
+    if ((values != 0 && values != 1) || (blocking != 0 && blocking != 1)) return fail(OLMC_ERR_ARG, "values and blocking must be 0 or 1");
+    if (launches < 1 || launches > 4096) return fail(OLMC_ERR_ARG, "launches must be in [1, 4096]");
+    int64_t most = 0;
+    for (int32_t j = 0; j < launches; ++j) {
+        if (n_threads[j] < 1) return fail(OLMC_ERR_ARG, "n_threads must be >= 1");
+        if (n_threads[j] > static_cast<int64_t>(kMaxGrid) * kBlock) return fail(OLMC_ERR_ARG, "n_threads beyond one launch of 2^18 workgroups");
+        most = std::max(most, n_threads[j]);
+    }
+    CtxLease lease;
+    int rc = ctx_lease(&lease);
+    if (rc) return rc;
+    DeviceCtx* const c = lease.c;
+    const int row = nv + 1;
+    auto grid_of = [](int64_t n) { return static_cast<int32_t>((n + kBlock - 1) / kBlock); };
+    auto one = [&](int32_t j, double* d_out) {
+        const int64_t n = n_threads[j];
+        const uint64_t s = salt[j];
+        return launch_reduce(c, c->stream, d_out, static_cast<double>(n), nv, grid_of(n),
+                             [&](int32_t grid, hipStream_t st, const EventPair* timed, const ReduceWs& ws) {
+                                 with_reduce_width(nv, [&](auto width) { launch_reduce_probe<width>(form, grid, st, timed, n, s, values, ws); });
+                             });
+    };
+    if (blocking) {
+        for (int32_t j = 0; j < launches; ++j) {
+            c->h_result[nv] = -1.0;                         // a launch that writes no tail must not show the one before it
+            rc = one(j, c->d_result);
+            if (rc) return rc;
+            for (int m = 0; m < row; ++m) out[static_cast<size_t>(j) * row + m] = c->h_result[m];
+        }
+        return OLMC_OK;
+    }
+    const size_t bytes = sizeof(double) * static_cast<size_t>(launches) * row;
+    rc = bulk_reserve(c, bytes);
+    if (rc) return rc;
+    double* const d_out = static_cast<double*>(c->d_bulk);
+    ReduceWs widest;                                         // the workspace grows (and waits for the stream) here, not between the launches
+    rc = make_ws(c, c->stream, grid_of(most), nv, d_out, -1.0, &widest);
+    if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(d_out, 0xFF, bytes, c->stream));  // NaN wherever a launch writes nothing
+    for (int32_t j = 0; j < launches; ++j) {
+        rc = one(j, d_out + static_cast<size_t>(j) * row);
+        if (rc) return rc;
+    }
+    hipError_t e = hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) { ws_recover(c); return fail(OLMC_ERR_HIP, std::string("reduce probe: ") + hipGetErrorString(e)); }
+    return OLMC_OK;
+}
+
+// wave_rows_sum<nv> (whole_workgroup = 0: nv 2 or 5, one wave) or workgroup_rows_sum<nv> (1: nv 5, 8, 16 or 32, 256 threads) on a host
+// matrix [rows][nv]: out_nv[c] = the sum of column c.  Bulk buffer = [matrix | out].
+extern "C" int olmc_rows_sum_probe(int nv, int whole_workgroup, const double* rows_host, int32_t rows, double* out_nv) {
+    if (!rows_host || !out_nv) return fail(OLMC_ERR_ARG, "null pointer");
+    if (whole_workgroup != 0 && whole_workgroup != 1) return fail(OLMC_ERR_ARG, "whole_workgroup must be 0 or 1");
+    if (whole_workgroup ? (nv != 5 && nv != 8 && nv != 16 && nv != 32) : (nv != 2 && nv != 5))
+        return fail(OLMC_ERR_ARG, "nv must be 2 or 5 for one wave, 5, 8, 16 or 32 for the whole workgroup");
+    if (rows < 1 || rows > (1 << 20)) return fail(OLMC_ERR_ARG, "rows must be in [1, 2^20]");
+    CtxLease lease;
+    int rc = ctx_lease(&lease);
+    if (rc) return rc;
+    DeviceCtx* const c = lease.c;
+    const size_t count = static_cast<size_t>(rows) * nv;
+    rc = bulk_reserve(c, sizeof(double) * (count + nv));
+    if (rc) return rc;
+    double* d_rows = static_cast<double*>(c->d_bulk);
+    double* d_out = d_rows + count;
+    HIP_TRY(hipMemcpyAsync(d_rows, rows_host, sizeof(double) * count, hipMemcpyHostToDevice, c->stream));
+    with_reduce_width(nv, [&](auto width) {
+        if (whole_workgroup) {
+            if constexpr (width > 2) hipLaunchKernelGGL((rows_sum_probe_kernel<width, true>), dim3(1), dim3(kBlock), 0, c->stream, d_rows, rows, d_out);
+        } else {
+            if constexpr (width <= 5) hipLaunchKernelGGL((rows_sum_probe_kernel<width, false>), dim3(1), dim3(kWave), 0, c->stream, d_rows, rows, d_out);
+        }
+    });
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out_nv, d_out, sizeof(double) * nv, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return OLMC_OK;
+}
+
+// wave_transpose_reduce<p, 32, op> on one wave (op 0 = sum, 1 = max, 2 = min): lane l starts from v_host[l][0 .. p), out[l] = its
+// v[0] afterwards.  Bulk buffer = [v | out].
+extern "C" int olmc_wave_reduce_probe(int p, int op, const double* v_host, double* out) {
+    if (!v_host || !out) return fail(OLMC_ERR_ARG, "null pointer");
+    if (p != 1 && p != 2 && p != 4 && p != 8 && p != 16 && p != 32) return fail(OLMC_ERR_ARG, "p must be 1, 2, 4, 8, 16 or 32");
+    if (op < 0 || op > 2) return fail(OLMC_ERR_ARG, "op must be 0 (sum), 1 (max) or 2 (min)");
+    CtxLease lease;
+    int rc = ctx_lease(&lease);
+    if (rc) return rc;
+    DeviceCtx* const c = lease.c;
+    const size_t count = static_cast<size_t>(kWave) * p;
+    rc = bulk_reserve(c, sizeof(double) * (count + kWave));
+    if (rc) return rc;
+    double* d_v = static_cast<double*>(c->d_bulk);
+    double* d_out = d_v + count;
+    HIP_TRY(hipMemcpyAsync(d_v, v_host, sizeof(double) * count, hipMemcpyHostToDevice, c->stream));
+    auto with_p = [&](auto f) {
+        switch (p) {
+            case 1: f(std::integral_constant<int, 1>{}); break;
+            case 2: f(std::integral_constant<int, 2>{}); break;
+            case 4: f(std::integral_constant<int, 4>{}); break;
+            case 8: f(std::integral_constant<int, 8>{}); break;
+            case 16: f(std::integral_constant<int, 16>{}); break;
+            default: f(std::integral_constant<int, 32>{}); break;
+        }
+    };
+    with_p([&](auto width) {
+        if (op == 0) hipLaunchKernelGGL((wave_reduce_probe_kernel<width, SumOp>), dim3(1), dim3(kWave), 0, c->stream, d_v, d_out);
+        else if (op == 1) hipLaunchKernelGGL((wave_reduce_probe_kernel<width, MaxOp>), dim3(1), dim3(kWave), 0, c->stream, d_v, d_out);
+        else hipLaunchKernelGGL((wave_reduce_probe_kernel<width, MinOp>), dim3(1), dim3(kWave), 0, c->stream, d_v, d_out);
+    });
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, d_out, sizeof(double) * kWave, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return OLMC_OK;
+}
+
 extern "C" int olmc_normal_moments(uint64_t seed, int64_t path_offset, int64_t n_paths, int32_t n_steps, double* out4) {
     if (!out4) return fail(OLMC_ERR_ARG, "null pointer");
     olmc_stats dummy;

@@ -307,6 +307,90 @@ __global__ void sqrt_nonneg_probe_kernel(const double* __restrict__ x, int64_t n
         y[i] = sqrt_nonneg(x[i]);
 }
 
+// ---------------------------------------------------------------- the fused grid reduction on synthetic values ----
+// Validation taps of the reduction family of olmc_kernels.h (wave_transpose_reduce, block_then_grid_reduce[_from], block_row_sum,
+// grid_reduce[_workgroup], wave_rows_sum, workgroup_rows_sum): the product's own device functions on values whose sum has an exact
+// answer.  Thread t of workgroup b contributes to component c
+//     v = H(b, c, salt) + K(t, c, salt)        when 256 b + t < n_threads, else 0.0
+// with two 32-bit integer hashes (all arithmetic mod 2^32; tests/reduction_reference.py restates them in NumPy):
+//     mix32(x):  x ^= x >> 16;  x *= 0x7FEB352D;  x ^= x >> 15;  x *= 0x846CA68B;  x ^= x >> 16
+//     seed     = mix32(lo32(salt) ^ mix32(hi32(salt) ^ 0x9E3779B9))
+//     H        = (mix32( seed + b * 0x9E3779B1 + c * 0x85EBCA6B) >>  8) | 1         24 bits, odd
+//     K        = (mix32(~seed + t * 0xC2B2AE35 + c * 0x27D4EB2F) >> 16) | 1         16 bits, odd
+// values = 0: v is that integer -- at most 2^26 threads x (2^24 + 2^16) < 2^51, so every partial sum is exact in fp64 whatever the
+// order, and the total must EQUAL the integer  sum_b live(b) H + sum_t count(t) K  (separable: NumPy has it in milliseconds).
+// values = 1: v = double(H + K) / 3.0 (one correctly rounded fp64 division): sums round, order matters.
+__host__ __device__ inline uint32_t probe_mix32(uint32_t x) {
+    x ^= x >> 16; x *= 0x7FEB352Du; x ^= x >> 15; x *= 0x846CA68Bu; x ^= x >> 16;
+    return x;
+}
+__host__ __device__ inline uint32_t probe_seed(uint64_t salt) {
+    return probe_mix32(static_cast<uint32_t>(salt) ^ probe_mix32(static_cast<uint32_t>(salt >> 32) ^ 0x9E3779B9u));
+}
+__device__ __forceinline__ double reduce_probe_value(uint32_t seed, uint32_t b, uint32_t t, uint32_t c, bool live, int values) {
+    const uint32_t h = (probe_mix32(seed + b * 0x9E3779B1u + c * 0x85EBCA6Bu) >> 8) | 1u;
+    const uint32_t k = (probe_mix32(~seed + t * 0xC2B2AE35u + c * 0x27D4EB2Fu) >> 16) | 1u;
+    const double v = static_cast<double>(h + k);
+    return live ? (values ? v / 3.0 : v) : 0.0;
+}
+
+// FORM 0 = block_then_grid_reduce<NV>;  1 = block_then_grid_reduce_from<NV, 1>, the lane ^ 32 exchange made by the producer as in
+// european_payoffs_folded (value k meets value k + P / 2);  2 = block_row_sum<NV>, then grid_reduce<NV> (NV = 2, wave 0 only) or
+// grid_reduce_workgroup<NV> called directly, as extrema_greeks_kernel and qmc_path_greeks_kernel enter.
+template <int NV, int FORM>
+__global__ __launch_bounds__(kBlock) void reduce_probe_kernel(int64_t n_threads, uint64_t salt, int values, ReduceWs ws) {
+    const uint32_t seed = probe_seed(salt);
+    const bool live = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x < n_threads;
+    auto value = [&](int c) { return reduce_probe_value(seed, blockIdx.x, threadIdx.x, static_cast<uint32_t>(c), live, values); };
+    if constexpr (FORM == 1) {
+        constexpr int P = pow2_ceil(NV), H = P / 2;
+        double kept[H];
+#pragma unroll
+        for (int k = 0; k < H; ++k) kept[k] = swap_add<32>(k < NV ? value(k) : 0.0, k + H < NV ? value(k + H) : 0.0);
+        block_then_grid_reduce_from<NV, 1>(kept, ws);
+    } else {
+        double acc[NV];
+#pragma unroll
+        for (int k = 0; k < NV; ++k) acc[k] = value(k);
+        if constexpr (FORM == 0) {
+            block_then_grid_reduce<NV>(acc, ws);
+        } else {
+            const double row = block_row_sum<NV>(acc);
+            if constexpr (NV <= 2) {
+                if (threadIdx.x >= kWave) return;
+                grid_reduce<NV>(row, ws);
+            } else {
+                grid_reduce_workgroup<NV>(row, ws);
+            }
+        }
+    }
+}
+
+// wave_rows_sum<NV> (one wave) or workgroup_rows_sum<NV> (kBlock threads) on a [rows][NV] matrix: out[c] = column c's sum.
+template <int NV, bool WORKGROUP>
+__global__ __launch_bounds__(kBlock) void rows_sum_probe_kernel(const double* __restrict__ src, int32_t rows, double* __restrict__ out) {
+    acquire_rows();
+    double total;
+    if constexpr (WORKGROUP) {
+        __shared__ double part[kBlock];
+        total = workgroup_rows_sum<NV>(src, rows, part);
+    } else {
+        total = wave_rows_sum<NV>(src, rows);
+    }
+    if (threadIdx.x < NV) out[threadIdx.x] = total;
+}
+
+// wave_transpose_reduce<P, 32, Op> on one wave: lane l holds v[l][0 .. P), out[l] = its v[0] afterwards (an ordinary per-lane
+// store) -- by the contract of olmc_kernels.h the result of value index l >> (6 - log2 P).
+template <int P, typename Op>
+__global__ __launch_bounds__(kWave) void wave_reduce_probe_kernel(const double* __restrict__ v_in, double* __restrict__ out) {
+    double v[P];
+#pragma unroll
+    for (int k = 0; k < P; ++k) v[k] = v_in[threadIdx.x * P + k];
+    wave_transpose_reduce<P, kWave / 2, Op>(v);
+    out[threadIdx.x] = v[0];
+}
+
 // ---------------------------------------------------------------- the price of the reference's own width (round 4) ----
 // The European step loop with fp64 NORMALS, as NumPy draws them (gbm_numpy.py:32-33: standard_normal of a PCG64 Generator, fp64):
 // the same Philox4x32-10 counter stream, but one block now yields TWO normals -- its four words make two 53-bit uniforms
