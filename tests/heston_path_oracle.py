@@ -13,6 +13,7 @@ import warnings
 import numpy as np
 
 from oracle import numpy_reference as orc
+from tests.sobol_reference import bridge_walk, normal_chunks
 
 S, K, T, R, Q = 100.0, 100.0, 1.0, 0.05, 0.01
 UP, DOWN = 120.0, 85.0
@@ -101,25 +102,6 @@ def recovered_normals(spot, var, model):
     return z1, (z2 - rho * z1) / np.sqrt(1 - rho**2)
 
 
-def bridge_walk(z):
-    """The pinned breadth-first Brownian bridge (include/olmc.h), over the rows of z (N, n): W (N, n + 1)."""
-    n = z.shape[1]
-    W = np.zeros((z.shape[0], n + 1))
-    W[:, n] = math.sqrt(n) * z[:, 0]
-    k = 1
-    queue = collections.deque([(0, n)])
-    while queue:
-        a, b = queue.popleft()
-        if b - a < 2:
-            continue
-        m = (a + b) // 2
-        W[:, m] = ((b - m) * W[:, a] + (m - a) * W[:, b]) / (b - a) + math.sqrt((m - a) * (b - m) / (b - a)) * z[:, k]
-        k += 1
-        queue.append((a, m))
-        queue.append((m, b))
-    return W
-
-
 def step_normals(z, construction):
     """(Z1, Z2') of every step, each (m, n), from the point's 2n normals."""
     if construction == "sequential":
@@ -127,22 +109,13 @@ def step_normals(z, construction):
     return np.diff(bridge_walk(z[:, 0::2]), axis=1), np.diff(bridge_walk(z[:, 1::2]), axis=1)
 
 
-def sobol_spots(n, n_points, seed, model, constructions, chunk=1024):
-    """{(construction, leg): spot matrix} over Sobol points [0, n_points); leg 1 is the mirror -z."""
-    from scipy.stats import norm, qmc
-
-    eng = qmc.Sobol(d=2 * n, scramble=True, seed=seed)
+def sobol_spots(n, n_points, seed, model, constructions, chunk=1024, z=None):
+    """{(construction, leg): spot matrix} over Sobol points [0, n_points); leg 1 is the mirror -z.  With z (n_points, 2n) given, over
+    the points whose normals are its rows."""
     parts = collections.defaultdict(list)
-    done = 0
-    while done < n_points:
-        m = min(chunk, n_points - done)
-        with warnings.catch_warnings():
-            warnings.simplefilter("ignore", UserWarning)
-            u = eng.random(m)
-        z = norm.ppf(np.clip(u, 1e-10, 1 - 1e-10))
+    for z in normal_chunks(2 * n, n_points, seed, chunk, z):
         for construction in constructions:
             z1, z2p = step_normals(z, construction)
             for leg, sign in enumerate((1.0, -1.0)):
                 parts[(construction, leg)].append(literal_recursion(sign * z1, sign * z2p, model, n)[0])
-        done += m
     return {key: np.concatenate(v) for key, v in parts.items()}

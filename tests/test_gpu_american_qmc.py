@@ -19,6 +19,7 @@ from optionslab_amd.exceptions import AccelerationError
 from optionslab_amd.greeks import ExoticAdapter, compute_greeks_unified
 from optionslab_amd.monte_carlo import sobol_tables
 from oracle import numpy_reference as orc
+from tests.sobol_reference import bridge_walk, normal_chunks
 
 pytestmark = pytest.mark.gpu
 
@@ -26,39 +27,14 @@ T, R = 1.0, 0.05
 
 
 # ----------------------------------------------------------------------------------------------------------- oracle ----
-def bridge_walk(z):
-    """The pinned breadth-first Brownian bridge (include/olmc.h), over the rows of z (N, n): W (N, n + 1)."""
-    n = z.shape[1]
-    W = np.zeros((z.shape[0], n + 1))
-    W[:, n] = math.sqrt(n) * z[:, 0]
-    k = 1
-    queue = collections.deque([(0, n)])
-    while queue:
-        a, b = queue.popleft()
-        if b - a < 2:
-            continue
-        m = (a + b) // 2
-        W[:, m] = ((b - m) * W[:, a] + (m - a) * W[:, b]) / (b - a) + math.sqrt((m - a) * (b - m) / (b - a)) * z[:, k]
-        k += 1
-        queue.append((a, m))
-        queue.append((m, b))
-    return W
-
-
-def oracle_paths(S, T_, r, sigma, q, n, n_points, seed, bridge, chunk=4096):
-    """Yields (row0, prices (m, n + 1)) over Sobol points [0, n_points) in chunks; column 0 = S."""
-    from scipy.stats import norm, qmc
-
-    eng = qmc.Sobol(d=n, scramble=True, seed=seed)
+def oracle_paths(S, T_, r, sigma, q, n, n_points, seed, bridge, chunk=4096, z=None):
+    """Yields (row0, prices (m, n + 1)) over Sobol points [0, n_points) in chunks; column 0 = S.  With z (n_points, n) given, over the
+    points whose normals are its rows."""
     dt = T_ / n
     drift, vol = (r - q - 0.5 * sigma**2) * dt, sigma * math.sqrt(dt)
     done = 0
-    while done < n_points:
-        m = min(chunk, n_points - done)
-        with warnings.catch_warnings():
-            warnings.simplefilter("ignore", UserWarning)
-            u = eng.random(m)
-        z = norm.ppf(np.clip(u, 1e-10, 1 - 1e-10))
+    for z in normal_chunks(n, n_points, seed, chunk, z):
+        m = z.shape[0]
         if bridge:
             W = bridge_walk(z)
         else:

@@ -18,6 +18,7 @@ from optionslab_amd import _hip
 from optionslab_amd.exotic import reference_barrier_level
 from optionslab_amd.greeks import ExoticAdapter, compute_greeks_unified
 from optionslab_amd.monte_carlo import sobol_tables
+from tests.sobol_reference import bridge_walk, normal_chunks
 
 pytestmark = pytest.mark.gpu
 
@@ -28,40 +29,14 @@ KINDS = [("asian", "arithmetic"), ("asian", "geometric"), ("barrier", "up-and-ou
 
 
 # ----------------------------------------------------------------------------------------------------------- oracle ----
-def bridge_walk(z):
-    """The pinned breadth-first Brownian bridge (include/olmc.h), over the rows of z (N, n): W (N, n + 1)."""
-    n = z.shape[1]
-    W = np.zeros((z.shape[0], n + 1))
-    W[:, n] = math.sqrt(n) * z[:, 0]
-    k = 1
-    queue = collections.deque([(0, n)])
-    while queue:
-        a, b = queue.popleft()
-        if b - a < 2:
-            continue
-        m = (a + b) // 2
-        W[:, m] = ((b - m) * W[:, a] + (m - a) * W[:, b]) / (b - a) + math.sqrt((m - a) * (b - m) / (b - a)) * z[:, k]
-        k += 1
-        queue.append((a, m))
-        queue.append((m, b))
-    return W
-
-
-def oracle_payoffs(n, n_points, seed, bridge, mirror=False, S=S, T=T, r=R, sigma=SIG, q=Q, chunk=2048):
-    """{(kind, sub, option_type): payoff vector} for Sobol points [0, n_points) (and their mirrors -z after them)."""
-    from scipy.stats import norm, qmc
-
-    eng = qmc.Sobol(d=n, scramble=True, seed=seed)
+def oracle_payoffs(n, n_points, seed, bridge, mirror=False, S=S, T=T, r=R, sigma=SIG, q=Q, chunk=2048, z=None):
+    """{(kind, sub, option_type): payoff vector} for Sobol points [0, n_points) (and their mirrors -z after them); with z (n_points, n)
+    given, for the points whose normals are its rows."""
     dt = T / n
     drift, vol = (r - q - 0.5 * sigma**2) * dt, sigma * math.sqrt(dt)
     out = collections.defaultdict(list)
-    done = 0
-    while done < n_points:
-        m = min(chunk, n_points - done)
-        with warnings.catch_warnings():
-            warnings.simplefilter("ignore", UserWarning)
-            u = eng.random(m)
-        z = norm.ppf(np.clip(u, 1e-10, 1 - 1e-10))
+    for z in normal_chunks(n, n_points, seed, chunk, z):
+        m = z.shape[0]
         for zz in ([z, -z] if mirror else [z]):
             if bridge:
                 W = bridge_walk(zz)
@@ -88,7 +63,6 @@ def oracle_payoffs(n, n_points, seed, bridge, mirror=False, S=S, T=T, r=R, sigma
                 out[("barrier", "down-and-in", ot)].append(vanilla * down_crossed)
                 out[("lookback", "floating", ot)].append(S_T - smin if ot == "call" else smax - S_T)
                 out[("lookback", "fixed", ot)].append(np.maximum(smax - K, 0) if ot == "call" else np.maximum(K - smin, 0))
-        done += m
     return {key: np.concatenate(v) for key, v in out.items()}
 
 

@@ -19,6 +19,7 @@ import pytest
 import optionslab_amd as ol
 from optionslab_amd import _hip
 from optionslab_amd.monte_carlo import sobol_tables
+from tests.sobol_reference import bridge_walk, normal_chunks
 
 pytestmark = pytest.mark.gpu
 
@@ -42,25 +43,6 @@ def pricer(model):
 
 
 # ----------------------------------------------------------------------------------------------------------- oracle ----
-def bridge_walk(z):
-    """The pinned breadth-first Brownian bridge (include/olmc.h), over the rows of z (N, n): W (N, n + 1)."""
-    n = z.shape[1]
-    W = np.zeros((z.shape[0], n + 1))
-    W[:, n] = math.sqrt(n) * z[:, 0]
-    k = 1
-    queue = collections.deque([(0, n)])
-    while queue:
-        a, b = queue.popleft()
-        if b - a < 2:
-            continue
-        m = (a + b) // 2
-        W[:, m] = ((b - m) * W[:, a] + (m - a) * W[:, b]) / (b - a) + math.sqrt((m - a) * (b - m) / (b - a)) * z[:, k]
-        k += 1
-        queue.append((a, m))
-        queue.append((m, b))
-    return W
-
-
 def step_normals(z, construction):
     """(Z1, Z2') of every step, each (m, n), from the point's 2n normals."""
     if construction == "sequential":
@@ -92,24 +74,15 @@ def literal_recursion(z1, z2p, model, n, S_=S, T_=T, r=R, q=Q):
     return spot, var
 
 
-def oracle_paths(n, n_points, seed, model, chunk=2048):
-    """{(construction, leg): (spot, var)} over Sobol points [0, n_points); leg 1 is the mirror -z."""
-    from scipy.stats import norm, qmc
-
-    eng = qmc.Sobol(d=2 * n, scramble=True, seed=seed)
+def oracle_paths(n, n_points, seed, model, chunk=2048, z=None):
+    """{(construction, leg): (spot, var)} over Sobol points [0, n_points); leg 1 is the mirror -z.  With z (n_points, 2n) given, over
+    the points whose normals are its rows."""
     parts = collections.defaultdict(list)
-    done = 0
-    while done < n_points:
-        m = min(chunk, n_points - done)
-        with warnings.catch_warnings():
-            warnings.simplefilter("ignore", UserWarning)
-            u = eng.random(m)
-        z = norm.ppf(np.clip(u, 1e-10, 1 - 1e-10))
+    for z in normal_chunks(2 * n, n_points, seed, chunk, z):
         for construction in constructions(n):
             z1, z2p = step_normals(z, construction)
             for leg, sign in enumerate((1.0, -1.0)):
                 parts[(construction, leg)].append(literal_recursion(sign * z1, sign * z2p, model, n))
-        done += m
     return {key: (np.concatenate([p[0] for p in v]), np.concatenate([p[1] for p in v])) for key, v in parts.items()}
 
 

@@ -22,6 +22,7 @@ from optionslab_amd import _hip
 from optionslab_amd.greeks import ExoticAdapter, compute_greeks_unified
 from optionslab_amd.monte_carlo import sobol_tables
 from oracle import numpy_reference as ref
+from tests.sobol_reference import bridge_walk, normal_chunks
 
 pytestmark = pytest.mark.gpu
 
@@ -60,39 +61,13 @@ def constructions(n):
 
 
 # ----------------------------------------------------------------------------------------------------------- oracle ----
-def bridge_walk(z):
-    """The pinned breadth-first Brownian bridge (include/olmc.h), over the rows of z (N, n): W (N, n + 1)."""
-    n = z.shape[1]
-    W = np.zeros((z.shape[0], n + 1))
-    W[:, n] = math.sqrt(n) * z[:, 0]
-    k = 1
-    queue = collections.deque([(0, n)])
-    while queue:
-        a, b = queue.popleft()
-        if b - a < 2:
-            continue
-        m = (a + b) // 2
-        W[:, m] = ((b - m) * W[:, a] + (m - a) * W[:, b]) / (b - a) + math.sqrt((m - a) * (b - m) / (b - a)) * z[:, k]
-        k += 1
-        queue.append((a, m))
-        queue.append((m, b))
-    return W
-
-
-def oracle_paths(n, n_points, seed, S=S, T=T, r=R, sigma=SIG, q=Q, chunk=2048):
-    """Yields {(construction, leg): price matrix (m, n + 1)} for consecutive chunks of Sobol points [0, n_points); leg 1 is the mirror -z."""
-    from scipy.stats import norm, qmc
-
-    eng = qmc.Sobol(d=n, scramble=True, seed=seed)
+def oracle_paths(n, n_points, seed, S=S, T=T, r=R, sigma=SIG, q=Q, chunk=2048, z=None):
+    """Yields {(construction, leg): price matrix (m, n + 1)} for consecutive chunks of Sobol points [0, n_points); leg 1 is the mirror -z.
+    With z (n_points, n) given, for the points whose normals are its rows."""
     dt = T / n
     drift, vol = (r - q - 0.5 * sigma**2) * dt, sigma * math.sqrt(dt)
-    done = 0
-    while done < n_points:
-        m = min(chunk, n_points - done)
-        with warnings.catch_warnings():
-            warnings.simplefilter("ignore", UserWarning)
-            u = eng.random(m)
-        z = norm.ppf(np.clip(u, 1e-10, 1 - 1e-10))
+    for z in normal_chunks(n, n_points, seed, chunk, z):
+        m = z.shape[0]
         out = {}
         for construction in constructions(n):
             for leg, zz in enumerate((z, -z)):
@@ -106,7 +81,6 @@ def oracle_paths(n, n_points, seed, S=S, T=T, r=R, sigma=SIG, q=Q, chunk=2048):
                 log_S[:, 1:] = np.log(S) + np.arange(1, n + 1) * drift + vol * W[:, 1:]
                 out[(construction, leg)] = np.exp(log_S)
         yield out
-        done += m
 
 
 def auto_payoffs(paths, f, over, S_=S, T_=T, r=R):
@@ -118,7 +92,8 @@ def cliq_payoffs(paths, periods, over, S_=S, T_=T, r=R):
 
 
 def oracle_vectors(n, n_points, seed, jobs, **market):
-    """{(job index, construction, leg): payoff vector over points [0, n_points)}; a job is (payoff function, parameter, overrides)."""
+    """{(job index, construction, leg): payoff vector over points [0, n_points)}; a job is (payoff function, parameter, overrides).
+    z=(n_points, n) normals among the keywords: the points whose normals are its rows."""
     parts = collections.defaultdict(list)
     p = {k_: market[k_] for k_ in ("S", "T", "r") if k_ in market}
     kw = dict(S_=p.get("S", S), T_=p.get("T", T), r=p.get("r", R))
