@@ -63,7 +63,8 @@ extern "C" {
                               *    olmc_american_lsm_qmc, olmc_exercise_boundary_qmc, olmc_gbm_qmc_paths (the American and its path matrix on Sobol paths),
                               *    olmc_autocallable_qmc, olmc_cliquet_qmc (the structured products on Sobol paths),
                               *    olmc_heston_qmc, olmc_heston_qmc_paths (Heston on Sobol paths, two dimensions per step),
-                              *    olmc_heston_path_payoff, olmc_heston_qmc_path_payoff (Asian, barrier and lookback payoffs under Heston) */
+                              *    olmc_heston_path_payoff, olmc_heston_qmc_path_payoff (Asian, barrier and lookback payoffs under Heston),
+                              *    olmc_heston_surface, olmc_heston_qmc_surface (a strike x maturity grid of European options on one set of Heston paths) */
 
 enum {
     OLMC_OK = 0,
@@ -550,6 +551,29 @@ int olmc_heston_qmc_path_payoff(double S, double K, double T, double r, double q
                                 double rho, double v0, int payoff, double barrier, int construction, int64_t point_offset,
                                 int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift, int32_t bits,
                                 int antithetic, olmc_stats* out);
+
+/* ---- a Heston option surface -----------------
+ * European options at k <= OLMC_MAX_BATCH cells (strikes[i], steps[i]) on ONE set of olmc_heston's paths (Philox) or olmc_heston_qmc's
+ * (scrambled Sobol, both constructions), in ONE launch: the (ln S, v) recursion of a path depends on neither strike nor maturity, so a
+ * cell is a read-out of the paths at its date.  T and n_steps define the time grid, dt = T / n_steps as in olmc_heston; cell i matures
+ * at date steps[i] of it (1 <= steps[i] <= n_steps) and its payoff on path j is max(+-(S_j[steps[i]] - strikes[i]), 0), S_j the row of
+ * the spot matrix of olmc_heston_paths / olmc_heston_qmc_paths for the same T, n_steps and seed or tables.  The step loop ends at the
+ * largest step of the list.  For the Sobol paths the tables (and the bridge) are those of the full n_steps horizon: a cell at an
+ * intermediate date reads the full-horizon construction, not the one olmc_heston_qmc would build for n_steps = steps[i].
+ * out[i] answers cell i in the caller's order (cells may come in any order and repeat): .sum and .sumsq undiscounted, so shards add up
+ * (olmc_combine_stats with T = steps[i] dt), .price = exp(-r steps[i] dt) mean, .std_error the naive per-path one.  A cell's sums do
+ * not depend on the other cells of the call or on its place in the list.  is_call, antithetic, path_offset / point_offset and v0 < 0
+ * as in olmc_heston / olmc_heston_qmc.  A NaN in S, T, r, q or the model gives NaN in every cell, a NaN strike in its own cell only.
+ * Refused (OLMC_ERR_ARG, before any device work): a null pointer, k outside [1, OLMC_MAX_BATCH], a step outside [1, n_steps], and what
+ * olmc_heston / olmc_heston_qmc_path_payoff refuse of rho, counts, steps, construction and tables.  With profiling on the launch counts
+ * once in olmc_kernel_time. */
+int olmc_heston_surface(double S, double T, double r, double q, int is_call, double kappa, double theta, double sigma_v, double rho,
+                        double v0, const double* strikes, const int32_t* steps, int32_t k, int64_t path_offset, int64_t n_local,
+                        int32_t n_steps, uint64_t seed, int antithetic, olmc_stats* out /* [k], in the caller's cell order */);
+int olmc_heston_qmc_surface(double S, double T, double r, double q, int is_call, double kappa, double theta, double sigma_v, double rho,
+                            double v0, const double* strikes, const int32_t* steps, int32_t k, int construction, int64_t point_offset,
+                            int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift, int32_t bits, int antithetic,
+                            olmc_stats* out /* [k] */);
 
 /* ---- multi-GPU, single process ------------------------------------------
  * n_paths split into n_gpus contiguous global path ranges (rank d = device d, [d N / P, (d + 1) N / P)).  Per list of devices the

@@ -104,7 +104,10 @@ PROTOTYPES = {
     "olmc_heston_path_payoff": (_I, [_D] * 5 + [_I] + [_D] * 5 + [_I, _D, _I64, _I64, _I32, _U64T, _I, C.POINTER(Stats)]),
     "olmc_heston_qmc_path_payoff": (_I, [_D] * 5 + [_I] + [_D] * 5 + [_I, _D, _I, _I64, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, _I,
                                          C.POINTER(Stats)]),
-    "olmc_multi_gpu_european": (_I, _SIX + [_I, _I64, _I32, _U64T, _I, _I, C.POINTER(Stats)]),
+    "olmc_heston_surface": (_I, [_D] * 4 + [_I] + [_D] * 5 + [C.POINTER(_D), C.POINTER(_I32), _I32, _I64, _I64, _I32, _U64T, _I, C.POINTER(Stats)]),
+    "olmc_heston_qmc_surface": (_I, [_D] * 4 + [_I] + [_D] * 5 + [C.POINTER(_D), C.POINTER(_I32), _I32, _I, _I64, _I64, _I32, C.POINTER(C.c_uint32),
+                                     C.POINTER(C.c_uint32), _I32, _I, C.POINTER(Stats)]),
+    "olmc_multi_gpu_european":(_I, _SIX + [_I, _I64, _I32, _U64T, _I, _I, C.POINTER(Stats)]),
     "olmc_multi_gpu_greeks_fd": (_I, _SIX + [_I, _I64, _I32, _U64T, _I, _I, C.POINTER(_D), C.POINTER(Stats)]),
     "olmc_multi_gpu_european_cv": (_I, _SIX + [_I, _I64, _I32, _U64T, _I, _I, C.POINTER(CvMoments)]),
     "olmc_multi_gpu_european_qmc": (_I, _SIX + [_I, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, _I, C.POINTER(Stats)]),
@@ -692,6 +695,36 @@ def heston_qmc_path_payoff(S, K, T, r, q, is_call: bool, kappa, theta, sigma_v, 
                                              QMC_BRIDGE if bridge else QMC_SEQUENTIAL, int(point_offset), int(n_points), n_steps, psv, psh,
                                              int(sv.shape[1]), int(antithetic), C.byref(out)))
     return out
+
+
+def _surface_cells(strikes, steps):
+    strikes = np.ascontiguousarray(strikes, dtype=np.float64)
+    steps = np.ascontiguousarray(steps, dtype=np.int32)
+    if strikes.ndim != 1 or strikes.shape != steps.shape:
+        raise ValueError("strikes and steps must be two lists of one length: cell i is (strikes[i], steps[i])")
+    return strikes, steps, strikes.ctypes.data_as(C.POINTER(C.c_double)), steps.ctypes.data_as(C.POINTER(C.c_int32)), (Stats * max(len(strikes), 1))()
+
+
+def heston_surface(S, T, r, q, is_call: bool, kappa, theta, sigma_v, rho, v0, strikes, steps, n_paths: int, n_steps: int, seed: int,
+                   antithetic: bool = False, path_offset: int = 0) -> List[Stats]:
+    """European options at the cells (strikes[i], steps[i]) of the time grid dt = T / n_steps on heston()'s paths, one launch
+    (olmc_heston_surface): at most 16 cells, in any order; the answers come in the same order."""
+    strikes, steps, pk, ps, out = _surface_cells(strikes, steps)
+    _check(lib().olmc_heston_surface(S, T, r, q, int(is_call), kappa, theta, sigma_v, rho, v0, pk, ps, len(strikes), int(path_offset),
+                                     int(n_paths), int(n_steps), seed64(seed), int(antithetic), out))
+    return list(out)[:len(strikes)]
+
+
+def heston_qmc_surface(S, T, r, q, is_call: bool, kappa, theta, sigma_v, rho, v0, strikes, steps, n_points: int, sv: np.ndarray,
+                       shift: np.ndarray, bridge: bool = True, antithetic: bool = False, point_offset: int = 0) -> List[Stats]:
+    """heston_surface on heston_qmc()'s scrambled-Sobol paths (olmc_heston_qmc_surface): n_steps = sv.shape[0] / 2 steps to T."""
+    sv, psv, shift, psh = _sobol_args(sv, shift, point_offset, n_points)
+    n_steps = _heston_steps(sv)
+    strikes, steps, pk, ps, out = _surface_cells(strikes, steps)
+    _check(lib().olmc_heston_qmc_surface(S, T, r, q, int(is_call), kappa, theta, sigma_v, rho, v0, pk, ps, len(strikes),
+                                         QMC_BRIDGE if bridge else QMC_SEQUENTIAL, int(point_offset), int(n_points), n_steps, psv, psh,
+                                         int(sv.shape[1]), int(antithetic), out))
+    return list(out)[:len(strikes)]
 
 
 def multi_gpu_european(S, K, T, r, sigma, q, is_call: bool, n_paths: int, n_steps: int, seed: int, antithetic: bool,

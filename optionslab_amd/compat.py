@@ -18,6 +18,7 @@ import sys
 import types
 
 from .black_scholes import black_scholes as _black_scholes
+from .black_scholes import implied_volatility as _implied_volatility
 from . import exceptions as _exc
 from . import exotic as _exotic
 from . import greeks as _greeks
@@ -35,7 +36,8 @@ _MISSING = object()
 # (src/pricing_models/__init__.py:23-66, src/greeks/__init__.py:11-23, src/exceptions/__init__.py).
 _PACKAGE_EXPORTS = {
     "src.pricing_models": ["src.pricing_models.monte_carlo", "src.pricing_models.monte_carlo_unified", "src.pricing_models.black_scholes",
-                           "src.pricing_models.exotic_options", "src.pricing_models.heston", "src.pricing_models.jump_diffusion"],
+                           "src.pricing_models.exotic_options", "src.pricing_models.heston", "src.pricing_models.jump_diffusion",
+                           "src.pricing_models.iv_solver"],
     "src.greeks": ["src.greeks.unified_greeks"],
     "src.exceptions": ["src.exceptions.montecarlo_exceptions", "src.exceptions.greek_exceptions"],
 }
@@ -74,7 +76,8 @@ def _targets() -> dict:
                                                      AmericanOption=_exotic.AmericanOption, AutocallableOption=_exotic.AutocallableOption,
                                                      CliquetOption=_exotic.CliquetOption, price_asian=_exotic.price_asian,
                                                      price_barrier=_exotic.price_barrier, price_american=_exotic.price_american),
-        "src.pricing_models.heston": _module("src.pricing_models.heston", HestonPricer=_heston.HestonPricer),
+        "src.pricing_models.heston": _module("src.pricing_models.heston", HestonPricer=_heston.HestonPricer, calibrate_heston=_heston.calibrate_heston),
+        "src.pricing_models.iv_solver": _module("src.pricing_models.iv_solver", implied_volatility=_implied_volatility),
         "src.pricing_models.jump_diffusion": _module("src.pricing_models.jump_diffusion", MertonJumpDiffusion=_jump.MertonJumpDiffusion,
                                                      KouJumpDiffusion=_jump.KouJumpDiffusion),
         "src.simulation": sim,

@@ -2527,6 +2527,113 @@ extern "C" int olmc_heston_qmc_path_payoff(double S, double K, double T, double 
                           2, heston_qmc_shape(point_offset, n_points, n_steps));
 }
 
+// ====================================================== a Heston option surface ====
+// European payoffs at k (strike, step) cells on the paths of olmc_heston / olmc_heston_qmc (include/olmc.h "a Heston option surface"):
+// one launch of heston_surface_kernel / heston_qmc_surface_kernel, the cells sorted by step for the kernel and answered in the caller's
+// order.
+namespace {
+static_assert(kSurfaceCells == OLMC_MAX_BATCH && 2 * kSurfaceCells <= kMaxNV, "a surface launch's row is OLMC_MAX_BATCH pairs wide");
+
+struct SurfaceOrder {
+    HestonSurfaceCells cells;
+    int32_t slot_of[OLMC_MAX_BATCH];     // caller's cell i sits at the kernel's slot slot_of[i]
+};
+
+// The checks of the cell list (after n_steps is known to be >= 1), then the cells by ascending step; equal steps keep the caller's order.
+int surface_cells(const double* strikes, const int32_t* steps, int32_t k, int32_t n_steps, SurfaceOrder* so) {
+    if (k < 1 || k > OLMC_MAX_BATCH) return fail(OLMC_ERR_ARG, "the number of cells must be in [1, OLMC_MAX_BATCH]");
+    for (int32_t i = 0; i < k; ++i)
+        if (steps[i] < 1 || steps[i] > n_steps) return fail(OLMC_ERR_ARG, "a cell's step must be in [1, n_steps]");
+    int32_t order[OLMC_MAX_BATCH];
+    for (int32_t i = 0; i < k; ++i) order[i] = i;
+    std::stable_sort(order, order + k, [&](int32_t a, int32_t b) { return steps[a] < steps[b]; });
+    for (int32_t j = 0; j < kSurfaceCells; ++j) {
+        so->cells.strike[j] = j < k ? strikes[order[j]] : 0.0;
+        so->cells.step[j] = j < k ? steps[order[j]] : INT32_MAX;
+        if (j < k) so->slot_of[order[j]] = j;
+    }
+    so->cells.k = k;
+    so->cells.last = steps[order[k - 1]];
+    return OLMC_OK;
+}
+
+// Cell i's stats from the launch's sums: discounted at the grid's time of its step; a NaN strike poisons its own cell, `bad` all of them.
+void surface_finish(const double* h, const SurfaceOrder& so, const double* strikes, const int32_t* steps, int32_t k, int64_t n, double r,
+                    double dt, bool bad, olmc_stats* out) {
+    for (int32_t i = 0; i < k; ++i) {
+        const int32_t j = so.slot_of[i];
+        if (bad || std::isnan(strikes[i])) nan_stats(n, &out[i]);
+        else finish_stats(h[2 * j], h[2 * j + 1], n, r, steps[i] * dt, &out[i]);
+    }
+}
+}  // namespace
+
+extern "C" int olmc_heston_surface(double S, double T, double r, double q, int is_call, double kappa, double theta, double sigma_v, double rho,
+                                   double v0, const double* strikes, const int32_t* steps, int32_t k, int64_t path_offset, int64_t n_local,
+                                   int32_t n_steps, uint64_t seed, int antithetic, olmc_stats* out) {
+    if (!strikes || !steps || !out) return fail(OLMC_ERR_ARG, "null pointer");
+    int rc = heston_check(rho);
+    if (rc) return rc;
+    rc = check_paths(path_offset, n_local, n_steps);
+    if (rc) return rc;
+    SurfaceOrder so;
+    rc = surface_cells(strikes, steps, k, n_steps, &so);
+    if (rc) return rc;
+    const HestonContract hc = make_heston(S, 0.0, T, r, q, is_call, kappa, theta, sigma_v, rho, v0, n_steps);
+    const bool bad = heston_poisoned(S, 0.0, T, r, q, kappa, theta, sigma_v, rho, v0);
+    CtxLease lease;
+    rc = ctx_lease(&lease);
+    if (rc) return rc;
+    DeviceCtx* const c = lease.c;
+    const PathRange pr = make_range(path_offset, n_local, n_steps, seed);
+    rc = launch_reduce(c, c->stream, c->d_result, -1.0, 2 * kSurfaceCells, grid_for(n_local),
+                       [&](int32_t grid, hipStream_t st, const EventPair* timed, const ReduceWs& ws) {
+                           with_bool(antithetic != 0, [&](auto a) {
+                               launch_timed(heston_surface_kernel<a>, dim3(grid), dim3(kBlock), st, timed, pr, hc, so.cells, ws);
+                           });
+                       });
+    if (rc) return rc;
+    surface_finish(c->h_result, so, strikes, steps, k, n_local * (antithetic ? 2 : 1), r, hc.dt, bad, out);
+    return OLMC_OK;
+}
+
+extern "C" int olmc_heston_qmc_surface(double S, double T, double r, double q, int is_call, double kappa, double theta, double sigma_v,
+                                       double rho, double v0, const double* strikes, const int32_t* steps, int32_t k, int construction,
+                                       int64_t point_offset, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift,
+                                       int32_t bits, int antithetic, olmc_stats* out) {
+    if (!strikes || !steps || !out) return fail(OLMC_ERR_ARG, "null pointer");
+    int rc = heston_check(rho);
+    if (rc) return rc;
+    rc = qmc_path_check(construction, point_offset, n_points, n_steps, sv, shift, bits, 2);
+    if (rc) return rc;
+    SurfaceOrder so;
+    rc = surface_cells(strikes, steps, k, n_steps, &so);
+    if (rc) return rc;
+    const HestonContract hc = make_heston(S, 0.0, T, r, q, is_call, kappa, theta, sigma_v, rho, v0, n_steps);
+    const bool bad = heston_poisoned(S, 0.0, T, r, q, kappa, theta, sigma_v, rho, v0);
+    CtxLease lease;
+    rc = ctx_lease(&lease);
+    if (rc) return rc;
+    DeviceCtx* const c = lease.c;
+    QmcPathLaunch pl;
+    rc = qmc_path_setup(c, construction, point_offset, n_points, n_steps, sv, shift, antithetic, &pl, 2);
+    if (rc) return rc;
+    rc = heston_qmc_shape(point_offset, n_points, n_steps)(c, &pl);
+    if (rc) return rc;
+    rc = launch_reduce(c, c->stream, c->d_result, -1.0, 2 * kSurfaceCells, pl.grid,
+                       [&](int32_t g, hipStream_t s, const EventPair* timed, const ReduceWs& ws) {
+                           with_bool(pl.bridge, [&](auto b) {
+                               with_bool(pl.anti, [&](auto m) {
+                                   launch_timed(heston_qmc_surface_kernel<b, m>, dim3(g), dim3(kBlock), s, timed, pl.qr, hc, so.cells, pl.d_sv,
+                                                pl.d_shift, pl.plan, pl.slabs, ws);
+                               });
+                           });
+                       });
+    if (rc) return rc;
+    surface_finish(c->h_result, so, strikes, steps, k, n_points * (pl.anti ? 2 : 1), r, hc.dt, bad, out);
+    return OLMC_OK;
+}
+
 namespace {
 // k (2 .. 16) contracts on points [point_offset, point_offset + n_paths), ONE launch (european_qmc_batch_kernel) whose grid covers
 // them all, queued on c's own stream behind the table: the 2 nsets sums then `tail` at d_out, contract i's pair at slot pos[i]

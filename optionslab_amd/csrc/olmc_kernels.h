@@ -3873,6 +3873,183 @@ __global__ __launch_bounds__(kBlock) void heston_qmc_path_kernel(QmcRange qr, He
     block_then_grid_reduce<2>(acc, ws);
 }
 
+// ------------------------------------------------- a strike x maturity surface under Heston ----
+// European payoffs at up to kSurfaceCells (strike, step) cells on ONE set of paths (include/olmc.h "a Heston option surface"): the
+// (ln S, v) recursion of a path knows neither strike nor maturity, so a cell is a read-out of the paths at its date -- the payoff of
+// column `step` of HestonPricer.simulate_paths' spot matrix for the same stream or points.  The cells are launch-uniform and sorted by
+// step on the host; when the step loop has just finished date t + 1 and that is the step of the next pending cell (a scalar compare),
+// the date's log-spot is formed as heston_paths_kernel forms it, fma(t + 1, mu_dt, ls) with ls carried WITHOUT the (r - q) dt terms,
+// exponentiated once per leg, and every cell of that date takes x = max(sign (s - strike), 0) per leg.  The loop ends at the last
+// cell's step.
+// No per-thread accumulators (16 cells x {sum, sumsq} would be 64 VGPRs beside the recursion's): as in extrema_greeks_kernel a cell's
+// two values are folded over the wave as soon as they exist (wave_sum: fixed order) and lane 0 adds them into the wave's LDS row; the
+// workgroup row is the four waves' rows added in wave order, then grid_reduce_workgroup.  The row is kSurfaceCells pairs wide whatever
+// the number of cells (unused ones stay 0): a cell's sums depend neither on the cells that share its launch nor on its place in the
+// list.  The fold needs all 64 lanes, so the path loops here are WAVE-uniform: a lane outside the range runs the recursion of a
+// defined path (path 0 / the Sobol point of its index) with its payoff masked to 0, and nothing folds inside a divergent region.
+constexpr int kSurfaceCells = 16;        // OLMC_MAX_BATCH (olmc.hip asserts it)
+
+struct HestonSurfaceCells {
+    double strike[kSurfaceCells];
+    int32_t step[kSurfaceCells];         // ascending, each in [1, n_steps]
+    int32_t k;                           // cells in use; step[j] = INT32_MAX for j >= k
+    int32_t last;                        // step[k - 1]: where the step loop ends
+};
+
+// The wave's partial sums of a launch: row[2 j], row[2 j + 1] = (sum x, sum x^2) of cell j over the paths this wave has walked.
+struct SurfaceRows {
+    double (*stage)[2 * kSurfaceCells];  // LDS [kWavesPerBlock][2 kSurfaceCells]
+    double* strike;                      // LDS [kSurfaceCells]: the cells, out of the scalar registers the step loop is short of (a runtime
+    int32_t* step;                       // LDS [kSurfaceCells]  index into the argument itself would move it to scratch)
+    int lane, wave;
+    __device__ __forceinline__ void clear(const HestonSurfaceCells& cells) const {
+        if (lane < 2 * kSurfaceCells) stage[wave][lane] = 0.0;
+        if (threadIdx.x == 0) {
+#pragma unroll
+            for (int j = 0; j < kSurfaceCells; ++j) { strike[j] = cells.strike[j]; step[j] = cells.step[j]; }
+        }
+        __syncthreads();
+    }
+    // Date `date` (1-based) of a block of 64 paths is done: read out the cells pending at it.  Call with all 64 lanes; next (the first
+    // cell not yet read out) and pending (its step) are wave-uniform, so a date without a cell costs one scalar compare.
+    template <int LEGS>
+    __device__ __forceinline__ void read_out(int32_t& next, int32_t& pending, int32_t date, double mu_dt,
+                                             double sign, const double (&ls)[2], bool live) const {
+        if (date != pending) return;
+        double s[LEGS];
+#pragma unroll
+        for (int leg = 0; leg < LEGS; ++leg) s[leg] = exp(__builtin_fma(static_cast<double>(date), mu_dt, ls[leg]));
+        int32_t nx = __builtin_amdgcn_readfirstlane(next);
+        do {
+            const double strike_nx = strike[nx];
+            double sum = 0.0, sumsq = 0.0;
+#pragma unroll
+            for (int leg = 0; leg < LEGS; ++leg) {
+                const double x = live ? fmax(sign * (s[leg] - strike_nx), 0.0) : 0.0;
+                sum += x;
+                sumsq += x * x;
+            }
+            const double wave_total = wave_sum(sum), wave_total_sq = wave_sum(sumsq);       // valid in lane 0
+            if (lane == 0) { stage[wave][2 * nx] += wave_total; stage[wave][2 * nx + 1] += wave_total_sq; }
+            nx = __builtin_amdgcn_readfirstlane(nx + 1);
+            pending = __builtin_amdgcn_readfirstlane(nx < kSurfaceCells ? step[nx] : INT32_MAX);       // an unused cell's step is INT32_MAX
+        } while (pending == date);
+        next = nx;
+    }
+    // The workgroup's row into the grid reduction (all waves).
+    __device__ __forceinline__ void reduce(const ReduceWs& ws) const {
+        __syncthreads();
+        double row = 0.0;
+        if (threadIdx.x < 2 * kSurfaceCells) {
+            row = stage[0][threadIdx.x];
+#pragma unroll
+            for (int k = 1; k < kWavesPerBlock; ++k) row += stage[k][threadIdx.x];
+        }
+        grid_reduce_workgroup<2 * kSurfaceCells>(row, ws);
+    }
+};
+
+// Philox: lane per path, heston_kernel's stream (tag kTagHeston, one block for two steps: a cell's date may fall inside a block).
+// Resources (tools/kernel_meta.sh, gfx950; no scratch, no spills; LDS 3.2 KiB: the wave rows, the cells and the workgroup
+// reduction), VGPRs plain / antithetic: 92 / 82 (heston_kernel: 96 / 76).  Plain stays in heston_kernel's row (96 allocated, five waves
+// per SIMD); the antithetic form allocates 88 where heston_kernel allocates 80 (five waves against six): the read-out keeps both legs'
+// spots and the pair of sums live next to the two recursions, and the path loop carries the lane's `live` flag and the wave's base.
+template <bool ANTI>
+__global__ __launch_bounds__(kBlock) void heston_surface_kernel(PathRange pr, HestonContract c, HestonSurfaceCells cells, ReduceWs ws) {
+    constexpr int LEGS = ANTI ? 2 : 1;
+    __shared__ double stage[kWavesPerBlock][2 * kSurfaceCells], cell_strike[kSurfaceCells];
+    __shared__ int32_t cell_step[kSurfaceCells];
+    const SurfaceRows rows{stage, cell_strike, cell_step, static_cast<int>(threadIdx.x) & (kWave - 1),
+                           __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) / kWave)};
+    rows.clear(cells);
+    const RoundKeys rk = pin_round_keys(pr.key0, pr.key1);
+    const HestonStep hs(c);
+    double v_start;
+    const bool skip0 = heston_start(c, v_start);
+    const int32_t blocks = (cells.last + 1) >> 1;
+    const int64_t stride = static_cast<int64_t>(gridDim.x) * kBlock;
+    for (int64_t w0 = static_cast<int64_t>(blockIdx.x) * kBlock + rows.wave * kWave; w0 < pr.count; w0 += stride) {      // wave-uniform
+        const int64_t i = w0 + rows.lane;
+        const bool live = i < pr.count;
+        const PathWords pw = path_words(pr, live ? i : 0);
+        double ls[2] = {c.log_s0, c.log_s0}, v[2] = {v_start, v_start};       // ls WITHOUT the (r - q) dt terms: added per read-out
+        int32_t next = 0, pending = cells.step[0];
+        for (int32_t b = 0; b < blocks; ++b) {
+            float z[4];
+            raw_normals4_pinned(pw.lo, pw.hi, static_cast<uint32_t>(b), kTagHeston, rk, z);
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int32_t t = 2 * b + h;
+                if (t < cells.last) {
+                    if (!(skip0 && t == 0)) {
+                        const double z1 = static_cast<double>(z[2 * h]);
+                        const double u = hs.zs * z1;
+                        const double w = __builtin_fma(hs.b, static_cast<double>(z[2 * h + 1]), hs.a * z1);
+                        hs.advance<1>(u, w, ls[0], v[0]);
+                        if constexpr (ANTI) hs.advance<-1>(u, w, ls[1], v[1]);
+                    }
+                    rows.read_out<LEGS>(next, pending, t + 1, c.mu_dt, c.sign, ls, live);
+                }
+            }
+        }
+    }
+    rows.reduce(ws);
+}
+
+// Sobol: heston_qmc_kernel's skeleton, slabs and grid.  The tables and the bridge plan are those of the full n = qr.dims steps (a cell
+// at an intermediate date reads the full-horizon construction); the sequential walk and the bridge's sweep stop at the last cell's
+// step.  Every lane fills and sweeps its own column of the wave's slab, inside the shard or not.
+// Resources (tools/kernel_meta.sh, gfx950; no scratch, no spills; LDS 3.2 KiB), VGPRs plain / antithetic: 88 / 74 (sequential), 97 / 87 (bridge)
+// (heston_qmc_kernel: 88 / 78 and 117 / 109): the sequential forms sit in heston_qmc_kernel's rows (five and six waves per SIMD), the
+// bridge forms need fewer registers than its (no divergent sweep to keep a mask for) and run at the two waves per SIMD its launch holds.
+template <bool BRIDGE, bool ANTI>
+__global__ __launch_bounds__(kBlock) void heston_qmc_surface_kernel(QmcRange qr, HestonContract c, HestonSurfaceCells cells,
+                                                                    const uint32_t* __restrict__ sv, const uint32_t* __restrict__ shift,
+                                                                    QmcBridgePlan plan, double* slabs, ReduceWs ws) {
+    constexpr int LEGS = ANTI ? 2 : 1;
+    __shared__ double stage[kWavesPerBlock][2 * kSurfaceCells], cell_strike[kSurfaceCells];
+    __shared__ int32_t cell_step[kSurfaceCells];
+    const SurfaceRows rows{stage, cell_strike, cell_step, static_cast<int>(threadIdx.x) & (kWave - 1),
+                           __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) / kWave)};
+    rows.clear(cells);
+    const int lane = rows.lane;
+    const int32_t n = qr.dims;                                               // steps of the grid: the tables hold 2 n dimensions
+    const HestonStep hs(c, 1.0);
+    double v_start;
+    const bool skip0 = heston_start(c, v_start);
+    const uint64_t base = qr.first & ~static_cast<uint64_t>(kWave - 1);      // blocks aligned in the absolute index
+    const uint64_t end = qr.first + static_cast<uint64_t>(qr.count);
+    const int64_t n_blocks = static_cast<int64_t>((end - base + kWave - 1) / kWave);
+    const int64_t stride = static_cast<int64_t>(gridDim.x) * kWavesPerBlock;
+    const int64_t slot = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + rows.wave;
+    for (int64_t blk = slot; blk < n_blocks; blk += stride) {                // wave-uniform
+        const uint64_t k = base + static_cast<uint64_t>(blk) * kWave + lane;
+        const bool live = k >= qr.first && k < end;
+        const QmcLanePoint lp(static_cast<uint32_t>(k));
+        double ls[2] = {c.log_s0, c.log_s0}, v[2] = {v_start, v_start};       // ls WITHOUT the (r - q) dt terms
+        int32_t next = 0, pending = cells.step[0];
+        auto step = [&](int32_t t, double z1, double z2) {
+            if (!(skip0 && t == 0)) {
+                const double u = hs.zs * z1;
+                const double w = __builtin_fma(hs.b, z2, hs.a * z1);
+                hs.advance<1>(u, w, ls[0], v[0]);
+                if constexpr (ANTI) hs.advance<-1>(u, w, ls[1], v[1]);
+            }
+            rows.read_out<LEGS>(next, pending, t + 1, c.mu_dt, c.sign, ls, live);
+        };
+        if constexpr (BRIDGE) {
+            double* w1 = slabs + static_cast<size_t>(slot) * (2 * static_cast<size_t>(n) * kWave);
+            double* w2 = w1 + static_cast<size_t>(n) * kWave;
+            auto at = [&](int32_t j) { return static_cast<size_t>(j - 1) * kWave + lane; };
+            heston_qmc_bridge_fill(sv, shift, plan, n, lane, lp, true, w1, w2, at);
+            heston_qmc_bridge_sweep(cells.last, w1, w2, at, step);
+        } else {
+            heston_qmc_normals(sv, shift, cells.last, lane, lp, step);
+        }
+    }
+    rows.reduce(ws);
+}
+
 // ------------------------------------------------------- validation taps ----
 __global__ void philox_words_kernel(uint64_t first, int64_t n_paths, int32_t block0, int32_t n_blocks,
                                     uint32_t tag, uint32_t k0, uint32_t k1, uint32_t* __restrict__ out) {

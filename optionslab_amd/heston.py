@@ -18,12 +18,58 @@ import numpy as np
 
 from . import _hip
 
+_SURFACE_CELLS = 16          # cells of one launch (OLMC_MAX_BATCH)
+
 
 def _qmc_tables(method: str, path_construction: str, n_paths: int, n_steps: int, seed: Optional[int]):
     """exotic._qmc_tables with two Sobol dimensions per step: tables of Sobol(d=2 n_steps), at most 10600 steps."""
     from .exotic import _qmc_tables as tables
 
     return tables(method, path_construction, n_paths, n_steps, seed, dims_per_step=2)
+
+
+def _surface_steps(maturities, n_steps: int) -> Tuple[float, list]:
+    """(T, the grid step of every maturity): T = max(maturities), dt = T / n_steps, maturity T_j sits at step m = round(T_j / dt) and
+    must lie on the grid (m >= 1, |m dt - T_j| <= 1e-9 T).  ValueError names the maturity that does not."""
+    mats = [float(t) for t in np.asarray(maturities, dtype=np.float64).ravel()]
+    if not mats:
+        raise ValueError("maturities must not be empty")
+    for t in mats:
+        if not t > 0.0:                                   # NaN included
+            raise ValueError(f"maturity {t!r} must be > 0")
+    if n_steps < 1:
+        raise ValueError("n_paths and n_steps must be >= 1")
+    T = max(mats)
+    dt = T / n_steps
+    steps = []
+    for t in mats:
+        m = int(round(t / dt))
+        if m < 1 or m > n_steps or abs(m * dt - t) > 1e-9 * T:
+            raise ValueError(f"maturity {t!r} is not on the grid of {n_steps} steps to T = {T!r} (dt = {dt!r})")
+        steps.append(m)
+    return T, steps
+
+
+def _surface_launches(steps, n_strikes: int):
+    """The cells (i, j) = (strike index, maturity index) of a surface cut into launches: sorted by step (then maturity index, then
+    strike index), at most 16 cells each -- every cell once; a launch's step loop ends at its own last step."""
+    cells = sorted(((steps[j], j, i) for j in range(len(steps)) for i in range(n_strikes)))
+    return [[(i, j) for _m, j, i in cells[a:a + _SURFACE_CELLS]] for a in range(0, len(cells), _SURFACE_CELLS)]
+
+
+def _grid_steps(maturities, per_year: int = 64, cap: int = 1024) -> int:
+    """The smallest n_steps <= cap with at least per_year steps per year to the longest maturity on whose grid every maturity lies."""
+    mats = [float(t) for t in np.asarray(maturities, dtype=np.float64).ravel()]
+    if not mats or not all(t > 0.0 for t in mats):
+        raise ValueError("maturities must be a non-empty list of positive times")
+    T = max(mats)
+    for n in range(max(1, int(np.ceil(per_year * T - 1e-9))), cap + 1):
+        try:
+            _surface_steps(mats, n)
+        except ValueError:
+            continue
+        return n
+    raise ValueError(f"no grid of at most {cap} steps to T = {T!r} holds every maturity of {mats!r}: pass n_steps, or move the maturities")
 
 
 @dataclass
@@ -108,6 +154,53 @@ class HestonPricer:
                          n_paths, n_steps, s, antithetic)
         return (np.float64(st.price), float(st.std_error)) if return_error else np.float64(st.price)
 
+
+    def price_surface(self, S: float, strikes, maturities, r: float, q: float = 0.0, option_type: Literal["call", "put"] = "call",
+                      n_paths: int = 100000, n_steps: int = 252, seed: Optional[int] = None, antithetic: bool = False,
+                      return_error: bool = False, *, method: Literal["pseudo", "qmc"] = "pseudo",
+                      path_construction: Literal["bridge", "sequential"] = "bridge"):
+        """European prices on a strike x maturity grid from ONE set of paths: a float64 array (len(strikes), len(maturities)), the
+        orientation of calibrate_heston's market_ivs[i, j]; with return_error, (prices, std_errors) of that shape.
+        n_steps is the number of steps to the LONGEST maturity T = max(maturities), dt = T / n_steps; every maturity must lie on that
+        grid: m = round(T_j / dt) with m >= 1 and |m dt - T_j| <= 1e-9 T, else ValueError naming the maturity, before the device is
+        touched.  Maturities may come in any order and may repeat.  More than 16 cells are cut into launches of at most 16, sorted by
+        step; each launch stops at its own last step and passes the same T, n_steps, seed and tables, and a cell's bits do not depend
+        on the cells it shares a launch with.
+        Ties: cell (K, T_j) is exp(-r T_j) mean(max(+-(spot[:, m_j] - K), 0)) over column m_j of
+        simulate_paths(S, T, r, q, n_paths, n_steps, seed, method=..., path_construction=...)[0] (and of the mirrored paths with
+        antithetic=True), its error exp(-r T_j) std / sqrt(samples) of the same payoffs -- which is what the reference's
+        price_monte_carlo(S, K, T m/n, ..., n_paths, m, seed) computes cell by cell from one NumPy stream, its draws being per step.
+        With method="pseudo" a cell on a grid where T m / n_steps is exact, e.g. T = 1 and n_steps = 64, has the sums of
+        price_monte_carlo(S, K, T_j, ..., n_steps=m_j, seed=seed); the cell (K, T) always has those of price_monte_carlo(S, K, T, ...,
+        n_steps, seed) for either method.
+        With method="qmc" a cell at an INTERMEDIATE maturity is a read-out of the full-horizon construction (the Sobol dimensions and,
+        for the bridge, the plan of n_steps dates): it is not the price price_monte_carlo(T_j, n_steps=m_j, method="qmc") would give,
+        whose construction ends at T_j.  What the full-horizon construction buys at an intermediate date (the price scatter over
+        scrambles against Philox seeds) has NOT been measured on the device yet: tools/heston_surface_timing.py measures it.
+        seed=None, antithetic, method, path_construction, the standard error's meaning and the refusals as price_monte_carlo; also
+        refused: empty strikes or maturities, a maturity <= 0."""
+        ks = [float(k) for k in np.asarray(strikes, dtype=np.float64).ravel()]
+        if not ks:
+            raise ValueError("strikes must not be empty")
+        if n_paths < 1 or n_steps < 1:
+            raise ValueError("n_paths and n_steps must be >= 1")
+        T, steps = _surface_steps(maturities, n_steps)
+        qmc = _qmc_tables(method, path_construction, n_paths, n_steps, seed)
+        model = (self.kappa, self.theta, self.sigma_v, self.rho, self.v0)
+        if qmc is None:
+            s = seed if seed is not None else int(np.random.default_rng().integers(0, 2**31))
+        prices = np.empty((len(ks), len(steps)), dtype=np.float64)
+        errors = np.empty_like(prices)
+        for launch in _surface_launches(steps, len(ks)):
+            cell_k, cell_m = [ks[i] for i, _j in launch], [steps[j] for _i, j in launch]
+            if qmc is not None:
+                sv, shift, bridge = qmc
+                sts = _hip.heston_qmc_surface(S, T, r, q, option_type == "call", *model, cell_k, cell_m, n_paths, sv, shift, bridge, antithetic)
+            else:
+                sts = _hip.heston_surface(S, T, r, q, option_type == "call", *model, cell_k, cell_m, n_paths, n_steps, s, antithetic)
+            for (i, j), st in zip(launch, sts):
+                prices[i, j], errors[i, j] = st.price, st.std_error
+        return (prices, errors) if return_error else prices
 
     def simulate_paths(self, S: float, T: float, r: float, q: float = 0.0, n_paths: int = 1000, n_steps: int = 252,
                        seed: Optional[int] = None, *, method: Literal["pseudo", "qmc"] = "pseudo",
@@ -205,3 +298,99 @@ def greeks_heston(heston_pricer, S: float, K: float, T: float, r: float, sigma: 
     from .greeks import compute_greeks_unified
 
     return compute_greeks_unified(HestonAdapter(heston_pricer), S, K, T, r, sigma, option_type, q)
+
+
+def calibration_objective(market_data: dict, *, n_paths: int = 1 << 14, n_steps: Optional[int] = None, seed: int = 0,
+                          method: Literal["pseudo", "qmc"] = "qmc", path_construction: Literal["bridge", "sequential"] = "bridge",
+                          antithetic: bool = False):
+    """calibrate_heston's objective as a function of (kappa, theta, sigma_v, rho, v0): checks market_data and the settings as
+    calibrate_heston does (before the device is touched) and returns the callable; its attribute `evals` counts the surfaces priced."""
+    from .black_scholes import implied_volatility
+
+    missing = [key for key in ("spot", "strikes", "maturities", "market_ivs", "r") if key not in market_data]
+    if missing:
+        raise ValueError(f"market_data lacks {missing}")
+    spot = float(market_data["spot"])
+    strikes = np.asarray(market_data["strikes"], dtype=np.float64).ravel()
+    maturities = np.asarray(market_data["maturities"], dtype=np.float64).ravel()
+    market_ivs = np.asarray(market_data["market_ivs"], dtype=np.float64)
+    r_rate = float(market_data["r"])
+    q_yield = float(market_data.get("q", 0.0))
+    if strikes.size == 0:
+        raise ValueError("strikes must not be empty")
+    if n_steps is None:
+        n_steps = _grid_steps(maturities)
+    _surface_steps(maturities, n_steps)
+    if market_ivs.shape != (strikes.size, maturities.size):
+        raise ValueError(f"market_ivs must have shape (len(strikes), len(maturities)) = {(strikes.size, maturities.size)}")
+    if n_paths < 1:
+        raise ValueError("n_paths and n_steps must be >= 1")
+    if seed is None:
+        raise ValueError("calibration needs a fixed seed: every objective evaluation must see the same random numbers")
+    _qmc_tables(method, path_construction, n_paths, n_steps, seed)         # price_surface's refusals, once and ahead of the optimiser
+    quoted = ~np.isnan(market_ivs)
+
+    def objective(params):
+        kappa, theta, sigma_v, rho, v0 = (float(p) for p in params)
+        if kappa <= 0 or theta <= 0 or sigma_v <= 0 or v0 <= 0:
+            return 1e10
+        if not -0.99 <= rho <= 0.99:
+            return 1e10
+        try:
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore", UserWarning)        # Feller, at every trial point
+                pricer = HestonPricer(kappa, theta, sigma_v, rho, v0)
+        except ValueError:
+            return 1e10
+        objective.evals += 1
+        prices = pricer.price_surface(spot, strikes, maturities, r_rate, q_yield, "call", n_paths, n_steps, seed, antithetic,
+                                      method=method, path_construction=path_construction)
+        total, count = 0.0, 0
+        for i, K in enumerate(strikes):
+            for j, T in enumerate(maturities):
+                if not quoted[i, j]:
+                    continue
+                try:
+                    total += (implied_volatility(float(prices[i, j]), spot, float(K), float(T), r_rate, "call", q_yield) - market_ivs[i, j]) ** 2
+                except ValueError:
+                    total += 1.0                                    # heston.py:383-385
+                count += 1
+        return total / max(count, 1)
+
+    objective.evals = 0
+    return objective
+
+
+def calibrate_heston(market_data: dict, initial_params: Optional[dict] = None, *, n_paths: int = 1 << 14, n_steps: Optional[int] = None,
+                     seed: int = 0, method: Literal["pseudo", "qmc"] = "qmc", path_construction: Literal["bridge", "sequential"] = "bridge",
+                     antithetic: bool = False, maxiter: int = 200) -> HestonPricer:
+    """heston.py:312-414 on the device's own Monte Carlo prices: fit (kappa, theta, sigma_v, rho, v0) to an implied-volatility surface.
+
+    market_data: spot, strikes, maturities, market_ivs[i, j] (strike i, maturity j; NaN = no quote), r and optionally q.  As in the
+    reference: the default start (2.0, 0.04, 0.3, -0.5, 0.04), L-BFGS-B with its bounds and maxiter=200, the objective = the mean squared
+    difference of model and market implied volatility over the quoted cells, 1e10 outside the bounds, +1.0 for a cell whose model
+    implied volatility cannot be found.  Unlike the reference, whose objective prices with the semi-analytic price_european, the model
+    prices here come from ONE price_surface per objective evaluation (calls, the given n_paths, method, path_construction, antithetic)
+    at a FIXED seed: every evaluation sees the same random numbers, so the objective is a deterministic function of the five parameters,
+    and the model is calibrated to the pricer price_monte_carlo and price_surface are.
+    n_steps=None picks the smallest grid with at least 64 steps per year to the longest maturity on which every maturity lies
+    (ValueError if none of at most 1024 steps exists).  Returns the calibrated HestonPricer with the final objective value and the number
+    of surfaces priced (objective evaluations inside the bounds) attached as `calibration_error` and `calibration_evals`.  maxiter
+    (additive) caps L-BFGS-B's iterations; the default is the reference's 200.
+    Refused (ValueError, before the device is touched): a missing market_data key, market_ivs of another shape than
+    (len(strikes), len(maturities)), seed=None, and what price_surface refuses."""
+    from scipy.optimize import minimize
+
+    objective = calibration_objective(market_data, n_paths=n_paths, n_steps=n_steps, seed=seed, method=method,
+                                      path_construction=path_construction, antithetic=antithetic)
+    if initial_params is None:
+        initial_params = {"kappa": 2.0, "theta": 0.04, "sigma_v": 0.3, "rho": -0.5, "v0": 0.04}
+    x0 = [initial_params[key] for key in ("kappa", "theta", "sigma_v", "rho", "v0")]
+    bounds = [(0.01, 10.0), (0.001, 1.0), (0.01, 2.0), (-0.99, 0.99), (0.001, 1.0)]
+    result = minimize(objective, x0, method="L-BFGS-B", bounds=bounds, options={"maxiter": maxiter})
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", UserWarning)
+        pricer = HestonPricer(*(float(p) for p in result.x))
+    pricer.calibration_error = float(result.fun)
+    pricer.calibration_evals = objective.evals
+    return pricer
