@@ -64,7 +64,9 @@ extern "C" {
                               *    olmc_autocallable_qmc, olmc_cliquet_qmc (the structured products on Sobol paths),
                               *    olmc_heston_qmc, olmc_heston_qmc_paths (Heston on Sobol paths, two dimensions per step),
                               *    olmc_heston_path_payoff, olmc_heston_qmc_path_payoff (Asian, barrier and lookback payoffs under Heston),
-                              *    olmc_heston_surface, olmc_heston_qmc_surface (a strike x maturity grid of European options on one set of Heston paths) */
+                              *    olmc_heston_surface, olmc_heston_qmc_surface (a strike x maturity grid of European options on one set of Heston paths),
+                              *    olmc_heston_qe_surface, olmc_heston_qe_qmc_surface, olmc_heston_qe_paths, olmc_heston_qe_qmc_paths (Heston by the
+                              *    quadratic-exponential scheme: surfaces and path matrices) */
 
 enum {
     OLMC_OK = 0,
@@ -75,6 +77,7 @@ enum {
 };
 
 enum { OLMC_STREAM_GBM = 0, OLMC_STREAM_HESTON = 1, OLMC_STREAM_JUMP = 2, OLMC_STREAM_KOU = 3 };   /* counter word 3 (stream_tag); batches use tag = contract index */
+enum { OLMC_STREAM_HESTON_QE = 0x48514500 };     /* the QE scheme's own tag, out of reach of Kou's size tags (3, 4, ...: one per two jumps of a step) */
 enum { OLMC_AVG_ARITHMETIC = 0, OLMC_AVG_GEOMETRIC = 1, OLMC_AVG_ARITHMETIC_FAST = 2 };
 #define OLMC_MAX_BATCH 16                        /* parameter sets per fused launch      */
 
@@ -574,6 +577,40 @@ int olmc_heston_qmc_surface(double S, double T, double r, double q, int is_call,
                             double v0, const double* strikes, const int32_t* steps, int32_t k, int construction, int64_t point_offset,
                             int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift, int32_t bits, int antithetic,
                             olmc_stats* out /* [k] */);
+
+/* ---- Heston, quadratic-exponential scheme ---
+ * olmc_heston_surface / olmc_heston_paths and their Sobol forms with Andersen's QE discretisation ("Efficient simulation of the Heston
+ * stochastic volatility model", 2008) in place of the full-truncation Euler one: central weights gamma1 = gamma2 = 1/2, psi_c = 1.5, no
+ * martingale correction.  dt = T / n_steps, E = exp(-kappa dt); one step from (ln S, v), v >= 0:
+ *   m = theta + (v - theta) E,   s^2 = v sigma_v^2 E (1 - E) / kappa + theta sigma_v^2 (1 - E)^2 / (2 kappa),   psi = s^2 / m^2
+ *   psi <= 1.5 (quadratic)    b^2 = 2/psi - 1 + sqrt(2/psi) sqrt(2/psi - 1),  a = m / (1 + b^2),  v' = a (b + Z_v)^2
+ *   psi >  1.5 (exponential)  p = (psi - 1) / (psi + 1),  beta = (1 - p) / m,  v' = 0 if U_v <= p, else ln((1 - p) / (1 - U_v)) / beta
+ *   ln S' = ln S + (r - q) dt + K0 + K1 v + K2 v' + sqrt(K3 v + K4 v') Z_s,
+ *   K0 = -rho kappa theta dt / sigma_v,  K1 = dt/2 (kappa rho / sigma_v - 1/2) - rho / sigma_v,  K2 = the same + rho / sigma_v,
+ *   K3 = K4 = dt/2 (1 - rho^2).
+ * v' matches the exact conditional mean m and variance s^2 of the variance process in both branches; v = 0 is a legal state.
+ * THE DRAWS of step t (t = 0 .. n_steps - 1); psi depends on the previous state alone, so only the branch taken reads its draw:
+ *   Philox  ONE block per step, counter (path_lo, path_hi, t, OLMC_STREAM_HESTON_QE), key = the seed's: words (x0, x1) give the pair
+ *           (Z_v, Z_s) by the library's Box-Muller (cosine, sine), U_v = (x2 + 1/2) 2^-32, x3 is unused.
+ *   Sobol   OLMC_QMC_SEQUENTIAL only, d = 2 n_steps dimensions: dimension 2 t gives U_v = clip(u, 1e-10, 1 - 1e-10) and Z_v = Phi^-1 of
+ *           that same value (inverse-transform sampling of v' from one uniform), dimension 2 t + 1 gives Z_s = Phi^-1(clip(u)).
+ *   antithetic  the mirror leg takes -Z_v, -Z_s and 1 - U_v (Philox: exactly (~x2 + 1/2) 2^-32); its branches are its own.
+ * Argument lists, cells, read-out, sums, shards (path_offset / point_offset), layouts, date 0 = (S, v0), NaN inputs and profiling as in
+ * olmc_heston_surface, olmc_heston_qmc_surface, olmc_heston_paths and olmc_heston_qmc_paths; a single cell at step n_steps is the
+ * European price.  Refused (OLMC_ERR_ARG, before any device work): what those refuse, and kappa <= 0, theta <= 0, sigma_v <= 0, v0 < 0
+ * (the formulas divide by kappa, sigma_v and m) and construction = OLMC_QMC_BRIDGE (U_v is a uniform, not a Brownian increment). */
+int olmc_heston_qe_surface(double S, double T, double r, double q, int is_call, double kappa, double theta, double sigma_v, double rho,
+                           double v0, const double* strikes, const int32_t* steps, int32_t k, int64_t path_offset, int64_t n_local,
+                           int32_t n_steps, uint64_t seed, int antithetic, olmc_stats* out /* [k], in the caller's cell order */);
+int olmc_heston_qe_qmc_surface(double S, double T, double r, double q, int is_call, double kappa, double theta, double sigma_v, double rho,
+                               double v0, const double* strikes, const int32_t* steps, int32_t k, int construction, int64_t point_offset,
+                               int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift, int32_t bits, int antithetic,
+                               olmc_stats* out /* [k] */);
+int olmc_heston_qe_paths(double S, double T, double r, double q, double kappa, double theta, double sigma_v, double rho, double v0,
+                         int64_t n_paths, int32_t n_steps, uint64_t seed, int path_major, double* spot_host, double* var_host);
+int olmc_heston_qe_qmc_paths(double S, double T, double r, double q, double kappa, double theta, double sigma_v, double rho, double v0,
+                             int construction, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift, int32_t bits,
+                             int path_major, double* spot_host, double* var_host);
 
 /* ---- multi-GPU, single process ------------------------------------------
  * n_paths split into n_gpus contiguous global path ranges (rank d = device d, [d N / P, (d + 1) N / P)).  Per list of devices the

@@ -107,6 +107,11 @@ PROTOTYPES = {
     "olmc_heston_surface": (_I, [_D] * 4 + [_I] + [_D] * 5 + [C.POINTER(_D), C.POINTER(_I32), _I32, _I64, _I64, _I32, _U64T, _I, C.POINTER(Stats)]),
     "olmc_heston_qmc_surface": (_I, [_D] * 4 + [_I] + [_D] * 5 + [C.POINTER(_D), C.POINTER(_I32), _I32, _I, _I64, _I64, _I32, C.POINTER(C.c_uint32),
                                      C.POINTER(C.c_uint32), _I32, _I, C.POINTER(Stats)]),
+    "olmc_heston_qe_surface": (_I, [_D] * 4 + [_I] + [_D] * 5 + [C.POINTER(_D), C.POINTER(_I32), _I32, _I64, _I64, _I32, _U64T, _I, C.POINTER(Stats)]),
+    "olmc_heston_qe_qmc_surface": (_I, [_D] * 4 + [_I] + [_D] * 5 + [C.POINTER(_D), C.POINTER(_I32), _I32, _I, _I64, _I64, _I32, C.POINTER(C.c_uint32),
+                                        C.POINTER(C.c_uint32), _I32, _I, C.POINTER(Stats)]),
+    "olmc_heston_qe_paths": (_I, [_D] * 9 + [_I64, _I32, _U64T, _I, C.POINTER(_D), C.POINTER(_D)]),
+    "olmc_heston_qe_qmc_paths": (_I, [_D] * 9 + [_I, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, _I, C.POINTER(_D), C.POINTER(_D)]),
     "olmc_multi_gpu_european":(_I, _SIX + [_I, _I64, _I32, _U64T, _I, _I, C.POINTER(Stats)]),
     "olmc_multi_gpu_greeks_fd": (_I, _SIX + [_I, _I64, _I32, _U64T, _I, _I, C.POINTER(_D), C.POINTER(Stats)]),
     "olmc_multi_gpu_european_cv": (_I, _SIX + [_I, _I64, _I32, _U64T, _I, _I, C.POINTER(CvMoments)]),
@@ -725,6 +730,53 @@ def heston_qmc_surface(S, T, r, q, is_call: bool, kappa, theta, sigma_v, rho, v0
                                          QMC_BRIDGE if bridge else QMC_SEQUENTIAL, int(point_offset), int(n_points), n_steps, psv, psh,
                                          int(sv.shape[1]), int(antithetic), out))
     return list(out)[:len(strikes)]
+
+
+STREAM_HESTON_QE = 0x48514500      # OLMC_STREAM_HESTON_QE: counter word 3 of the QE scheme's Philox blocks
+
+
+def heston_qe_surface(S, T, r, q, is_call: bool, kappa, theta, sigma_v, rho, v0, strikes, steps, n_paths: int, n_steps: int, seed: int,
+                      antithetic: bool = False, path_offset: int = 0) -> List[Stats]:
+    """heston_surface by the quadratic-exponential scheme (olmc_heston_qe_surface): one Philox block per step, at most 16 cells."""
+    strikes, steps, pk, ps, out = _surface_cells(strikes, steps)
+    _check(lib().olmc_heston_qe_surface(S, T, r, q, int(is_call), kappa, theta, sigma_v, rho, v0, pk, ps, len(strikes), int(path_offset),
+                                        int(n_paths), int(n_steps), seed64(seed), int(antithetic), out))
+    return list(out)[:len(strikes)]
+
+
+def heston_qe_qmc_surface(S, T, r, q, is_call: bool, kappa, theta, sigma_v, rho, v0, strikes, steps, n_points: int, sv: np.ndarray,
+                          shift: np.ndarray, bridge: bool = False, antithetic: bool = False, point_offset: int = 0) -> List[Stats]:
+    """heston_qe_surface on scrambled-Sobol points (olmc_heston_qe_qmc_surface): n_steps = sv.shape[0] / 2, sequential construction only
+    (bridge=True is passed on and refused by the library)."""
+    sv, psv, shift, psh = _sobol_args(sv, shift, point_offset, n_points)
+    n_steps = _heston_steps(sv)
+    strikes, steps, pk, ps, out = _surface_cells(strikes, steps)
+    _check(lib().olmc_heston_qe_qmc_surface(S, T, r, q, int(is_call), kappa, theta, sigma_v, rho, v0, pk, ps, len(strikes),
+                                            QMC_BRIDGE if bridge else QMC_SEQUENTIAL, int(point_offset), int(n_points), n_steps, psv, psh,
+                                            int(sv.shape[1]), int(antithetic), out))
+    return list(out)[:len(strikes)]
+
+
+def heston_qe_paths(S, T, r, q, kappa, theta, sigma_v, rho, v0, n_paths: int, n_steps: int, seed: int, path_major: bool = False):
+    """Spot and variance of heston_qe_surface's paths at dates 0 .. n_steps (date 0 = (S, v0)); layouts as gbm_paths."""
+    spot = _path_matrix(n_paths, n_steps, path_major)
+    var = np.empty_like(spot)
+    _check(lib().olmc_heston_qe_paths(S, T, r, q, kappa, theta, sigma_v, rho, v0, int(n_paths), int(n_steps), seed64(seed), int(path_major),
+                                      spot.ctypes.data_as(C.POINTER(C.c_double)), var.ctypes.data_as(C.POINTER(C.c_double))))
+    return spot, var
+
+
+def heston_qe_qmc_paths(S, T, r, q, kappa, theta, sigma_v, rho, v0, n_points: int, sv: np.ndarray, shift: np.ndarray, bridge: bool = False,
+                        path_major: bool = False):
+    """Spot and variance of heston_qe_qmc_surface's paths at dates 0 .. n_steps = sv.shape[0] / 2 (olmc_heston_qe_qmc_paths)."""
+    sv, psv, shift, psh = _sobol_args(sv, shift, 0, n_points)
+    n_steps = _heston_steps(sv)
+    spot = _path_matrix(n_points, n_steps, path_major)
+    var = np.empty_like(spot)
+    _check(lib().olmc_heston_qe_qmc_paths(S, T, r, q, kappa, theta, sigma_v, rho, v0, QMC_BRIDGE if bridge else QMC_SEQUENTIAL, int(n_points),
+                                          n_steps, psv, psh, int(sv.shape[1]), int(path_major), spot.ctypes.data_as(C.POINTER(C.c_double)),
+                                          var.ctypes.data_as(C.POINTER(C.c_double))))
+    return spot, var
 
 
 def multi_gpu_european(S, K, T, r, sigma, q, is_call: bool, n_paths: int, n_steps: int, seed: int, antithetic: bool,

@@ -2634,6 +2634,175 @@ extern "C" int olmc_heston_qmc_surface(double S, double T, double r, double q, i
     return OLMC_OK;
 }
 
+// ====================================================== Heston, quadratic-exponential scheme ====
+// olmc_heston_surface / olmc_heston_paths and their Sobol forms with Andersen's QE step in place of the Euler one (include/olmc.h
+// "Heston, quadratic-exponential scheme"): the same checks, ranges, cells and read-out, one launch of the heston_qe_* kernels.
+namespace {
+// The scheme divides by kappa, sigma_v and the conditional mean m = v E + theta (1 - E), and starts from v0 itself.
+int heston_qe_check(double kappa, double theta, double sigma_v, double rho, double v0) {
+    const int rc = heston_check(rho);
+    if (rc) return rc;
+    if (kappa <= 0.0) return fail(OLMC_ERR_ARG, "kappa must be positive for the QE scheme");
+    if (theta <= 0.0) return fail(OLMC_ERR_ARG, "theta must be positive for the QE scheme");
+    if (sigma_v <= 0.0) return fail(OLMC_ERR_ARG, "sigma_v must be positive for the QE scheme");
+    if (v0 < 0.0) return fail(OLMC_ERR_ARG, "v0 must be non-negative for the QE scheme");
+    return OLMC_OK;
+}
+
+int heston_qe_sequential(int construction) {
+    if (construction == OLMC_QMC_BRIDGE)
+        return fail(OLMC_ERR_ARG, "the QE scheme takes OLMC_QMC_SEQUENTIAL only: its variance draw is a uniform, not a Brownian increment");
+    return OLMC_OK;
+}
+
+// The launch constants, every one folded here in fp64 (olmc_kernels.h "Heston, quadratic-exponential scheme").
+HestonQeContract make_heston_qe(double S, double T, double r, double q, int is_call, double kappa, double theta, double sigma_v, double rho,
+                                double v0, int32_t n_steps) {
+    HestonQeContract hc;
+    const double dt = T / n_steps;
+    const double e = std::exp(-kappa * dt), one_minus_e = -std::expm1(-kappa * dt);
+    const double g = 0.5 * dt * (kappa * rho / sigma_v - 0.5);
+    hc.log_s0 = std::log(S);
+    hc.v0 = v0;
+    hc.drift_dt = (r - q) * dt + -rho * kappa * theta * dt / sigma_v;                // (r - q) dt + K0
+    hc.e = e;
+    hc.theta_1me = theta * one_minus_e;
+    hc.c1 = sigma_v * sigma_v * e * one_minus_e / kappa;
+    hc.c2 = theta * sigma_v * sigma_v * one_minus_e * one_minus_e / (2.0 * kappa);
+    hc.k1 = g - rho / sigma_v;
+    hc.k2 = g + rho / sigma_v;
+    hc.k3 = 0.5 * dt * (1.0 - rho * rho);                                            // K4 = K3
+    hc.sign = is_call ? 1.0 : -1.0;
+    return hc;
+}
+}  // namespace
+
+extern "C" int olmc_heston_qe_surface(double S, double T, double r, double q, int is_call, double kappa, double theta, double sigma_v, double rho,
+                                      double v0, const double* strikes, const int32_t* steps, int32_t k, int64_t path_offset, int64_t n_local,
+                                      int32_t n_steps, uint64_t seed, int antithetic, olmc_stats* out) {
+    if (!strikes || !steps || !out) return fail(OLMC_ERR_ARG, "null pointer");
+    int rc = heston_qe_check(kappa, theta, sigma_v, rho, v0);
+    if (rc) return rc;
+    rc = check_paths(path_offset, n_local, n_steps);
+    if (rc) return rc;
+    SurfaceOrder so;
+    rc = surface_cells(strikes, steps, k, n_steps, &so);
+    if (rc) return rc;
+    const HestonQeContract hc = make_heston_qe(S, T, r, q, is_call, kappa, theta, sigma_v, rho, v0, n_steps);
+    const bool bad = heston_poisoned(S, 0.0, T, r, q, kappa, theta, sigma_v, rho, v0);
+    CtxLease lease;
+    rc = ctx_lease(&lease);
+    if (rc) return rc;
+    DeviceCtx* const c = lease.c;
+    const PathRange pr = make_range(path_offset, n_local, n_steps, seed);
+    rc = launch_reduce(c, c->stream, c->d_result, -1.0, 2 * kSurfaceCells, grid_for(n_local),
+                       [&](int32_t grid, hipStream_t st, const EventPair* timed, const ReduceWs& ws) {
+                           with_bool(antithetic != 0, [&](auto a) {
+                               launch_timed(heston_qe_surface_kernel<a>, dim3(grid), dim3(kBlock), st, timed, pr, hc, so.cells, ws);
+                           });
+                       });
+    if (rc) return rc;
+    surface_finish(c->h_result, so, strikes, steps, k, n_local * (antithetic ? 2 : 1), r, T / n_steps, bad, out);
+    return OLMC_OK;
+}
+
+extern "C" int olmc_heston_qe_qmc_surface(double S, double T, double r, double q, int is_call, double kappa, double theta, double sigma_v,
+                                          double rho, double v0, const double* strikes, const int32_t* steps, int32_t k, int construction,
+                                          int64_t point_offset, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift,
+                                          int32_t bits, int antithetic, olmc_stats* out) {
+    if (!strikes || !steps || !out) return fail(OLMC_ERR_ARG, "null pointer");
+    int rc = heston_qe_check(kappa, theta, sigma_v, rho, v0);
+    if (rc) return rc;
+    rc = heston_qe_sequential(construction);
+    if (rc) return rc;
+    rc = qmc_path_check(construction, point_offset, n_points, n_steps, sv, shift, bits, 2);
+    if (rc) return rc;
+    SurfaceOrder so;
+    rc = surface_cells(strikes, steps, k, n_steps, &so);
+    if (rc) return rc;
+    const HestonQeContract hc = make_heston_qe(S, T, r, q, is_call, kappa, theta, sigma_v, rho, v0, n_steps);
+    const bool bad = heston_poisoned(S, 0.0, T, r, q, kappa, theta, sigma_v, rho, v0);
+    CtxLease lease;
+    rc = ctx_lease(&lease);
+    if (rc) return rc;
+    DeviceCtx* const c = lease.c;
+    QmcPathLaunch pl;
+    rc = qmc_path_setup(c, construction, point_offset, n_points, n_steps, sv, shift, antithetic, &pl, 2);
+    if (rc) return rc;
+    rc = heston_qmc_shape(point_offset, n_points, n_steps)(c, &pl);                  // sequential: the grid over the aligned blocks, no slabs
+    if (rc) return rc;
+    rc = launch_reduce(c, c->stream, c->d_result, -1.0, 2 * kSurfaceCells, pl.grid,
+                       [&](int32_t g, hipStream_t s, const EventPair* timed, const ReduceWs& ws) {
+                           with_bool(pl.anti, [&](auto m) {
+                               launch_timed(heston_qe_qmc_surface_kernel<m>, dim3(g), dim3(kBlock), s, timed, pl.qr, hc, so.cells, pl.d_sv, pl.d_shift,
+                                            ws);
+                           });
+                       });
+    if (rc) return rc;
+    surface_finish(c->h_result, so, strikes, steps, k, n_points * (pl.anti ? 2 : 1), r, T / n_steps, bad, out);
+    return OLMC_OK;
+}
+
+extern "C" int olmc_heston_qe_paths(double S, double T, double r, double q, double kappa, double theta, double sigma_v, double rho, double v0,
+                                    int64_t n_paths, int32_t n_steps, uint64_t seed, int path_major, double* spot_host, double* var_host) {
+    if (!spot_host || !var_host) return fail(OLMC_ERR_ARG, "null pointer");
+    int rc = heston_qe_check(kappa, theta, sigma_v, rho, v0);
+    if (rc) return rc;
+    const double bytes = 8.0 * static_cast<double>(n_paths) * (n_steps + 1.0);
+    CtxLease lease;
+    rc = matrix_prologue(n_paths, n_steps, 2 * bytes, "path matrices would exceed 64 GB", &lease);
+    if (rc) return rc;
+    DeviceCtx* const c = lease.c;
+    double* d_spot = static_cast<double*>(c->d_bulk);
+    double* d_var = d_spot + static_cast<size_t>(n_paths) * (n_steps + 1);
+    const HestonQeContract hc = make_heston_qe(S, T, r, q, 1, kappa, theta, sigma_v, rho, v0, n_steps);
+    const PathRange pr = make_range(0, n_paths, n_steps, seed);
+    EventPair ep{};
+    const EventPair* timed = nullptr;                  // profiling on: the path kernel counts in olmc_kernel_time, as olmc_heston_paths'
+    rc = prof_pair(c, &ep, &timed);
+    if (rc) return rc;
+    with_bool(path_major != 0, [&](auto pm) {
+        launch_timed(heston_qe_paths_kernel<pm>, dim3(grid_for(n_paths)), dim3(kBlock), c->stream, timed, pr, hc, S, d_spot, d_var);
+    });
+    HIP_TRY(hipGetLastError());
+    rc = copy_to_host(c, spot_host, d_spot, static_cast<size_t>(bytes));
+    if (rc) return rc;
+    return copy_to_host(c, var_host, d_var, static_cast<size_t>(bytes));
+}
+
+extern "C" int olmc_heston_qe_qmc_paths(double S, double T, double r, double q, double kappa, double theta, double sigma_v, double rho, double v0,
+                                        int construction, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift,
+                                        int32_t bits, int path_major, double* spot_host, double* var_host) {
+    if (!spot_host || !var_host) return fail(OLMC_ERR_ARG, "null pointer");
+    int rc = heston_qe_check(kappa, theta, sigma_v, rho, v0);
+    if (rc) return rc;
+    rc = heston_qe_sequential(construction);
+    if (rc) return rc;
+    const double bytes = 8.0 * static_cast<double>(n_points) * (n_steps + 1.0);
+    CtxLease lease;
+    rc = qmc_matrix_prologue(construction, n_points, n_steps, sv, shift, bits, 2 * bytes, &lease, true, 2);
+    if (rc) return rc;
+    DeviceCtx* const c = lease.c;
+    double* d_spot = static_cast<double*>(c->d_bulk);
+    double* d_var = d_spot + static_cast<size_t>(n_points) * (n_steps + 1);
+    const HestonQeContract hc = make_heston_qe(S, T, r, q, 1, kappa, theta, sigma_v, rho, v0, n_steps);
+    QmcPathLaunch pl;
+    rc = qmc_path_setup(c, construction, 0, n_points, n_steps, sv, shift, 0, &pl, 2);
+    if (rc) return rc;
+    const int32_t grid = qmc_block_grid((n_points + kWave - 1) / kWave);
+    EventPair ep{};
+    const EventPair* timed = nullptr;
+    rc = prof_pair(c, &ep, &timed);
+    if (rc) return rc;
+    with_bool(path_major != 0, [&](auto pm) {
+        launch_timed(heston_qe_qmc_paths_kernel<pm>, dim3(grid), dim3(kBlock), c->stream, timed, pl.qr, hc, S, pl.d_sv, pl.d_shift, d_spot, d_var);
+    });
+    HIP_TRY(hipGetLastError());
+    rc = copy_to_host(c, spot_host, d_spot, static_cast<size_t>(bytes));
+    if (rc) return rc;
+    return copy_to_host(c, var_host, d_var, static_cast<size_t>(bytes));
+}
+
 namespace {
 // k (2 .. 16) contracts on points [point_offset, point_offset + n_paths), ONE launch (european_qmc_batch_kernel) whose grid covers
 // them all, queued on c's own stream behind the table: the 2 nsets sums then `tail` at d_out, contract i's pair at slot pos[i]

@@ -4050,6 +4050,275 @@ __global__ __launch_bounds__(kBlock) void heston_qmc_surface_kernel(QmcRange qr,
     rows.reduce(ws);
 }
 
+// ------------------------------------------------- Heston, quadratic-exponential scheme ----
+// Andersen's QE (2008; include/olmc.h "Heston, quadratic-exponential scheme"): central weights gamma1 = gamma2 = 1/2, psi_c = 1.5, no
+// martingale correction.  The variance of the next date is drawn from a distribution matched to the exact conditional mean m and
+// variance s^2 of the CIR process given v >= 0,
+//   m = v E + theta (1 - E),   s^2 = v c1 + c2,   E = exp(-kappa dt),   c1 = sigma_v^2 E (1 - E) / kappa,
+//   c2 = theta sigma_v^2 (1 - E)^2 / (2 kappa),   psi = s^2 / m^2                       (m > 0 and s^2 > 0 also at v = 0),
+//   psi <= 1.5  QUADRATIC    x = 2 / psi,  b^2 = x - 1 + sqrt(x) sqrt(x - 1),  a = m / (1 + b^2),  v' = a (b + Z_v)^2
+//   psi >  1.5  EXPONENTIAL  p = (psi - 1) / (psi + 1),  beta = (1 - p) / m,  v' = 0 if U_v <= p, else ln((1 - p) / (1 - U_v)) / beta
+// and the log-spot follows with the trapezoidal weights
+//   ln S' = ln S + (r - q) dt + K0 + K1 v + K2 v' + sqrt(K3 (v + v')) Z_s                                        (K4 = K3).
+// The launch constants are folded on the host in fp64 (olmc.hip: make_heston_qe); (r - q) dt + K0 is one constant, added per date as
+// the Euler kernels add (r - q) dt.  psi depends on v alone, so the branch is known before any draw is read: only the branch taken
+// reads its draw (Z_v or U_v), and the Sobol kernels evaluate the inverse normal of the variance dimension only where a leg is
+// quadratic.  The mirror leg takes -Z_v, -Z_s and 1 - U_v; its variance is its own, so the two legs branch independently.
+// fp64 cost of a step beside the draws: the branch test is s^2 <= 1.5 m^2 (no division); quadratic = two reciprocals (x, a) and two
+// square roots (of x (x - 1) and of b^2); exponential = two reciprocals (p, 1 / (1 - p)) and one logarithm; the spot one square root.
+// Square roots are the plain fp64 sqrt: x is unbounded above and K3 (v + v') reaches 0, outside what sqrt_nonneg is pinned on.
+constexpr uint32_t kTagHestonQe = 0x48514500u;   // OLMC_STREAM_HESTON_QE: far from Kou's size tags, which grow upward from 3
+
+struct HestonQeContract {
+    double log_s0, v0;
+    double drift_dt;       // (r - q) dt + K0
+    double e, theta_1me;   // E, theta (1 - E)
+    double c1, c2;
+    double k1, k2, k3;
+    double sign;
+};
+
+// n / d for finite d > 0 away from the subnormals: a v_rcp_f64 seed, one Newton round and a residual correction of the quotient, as
+// neg_log_quad divides (within an ulp of n / d).
+__device__ __forceinline__ double qe_div(double n, double d) {
+    double r = __builtin_amdgcn_rcp(d);
+    r = __builtin_fma(__builtin_fma(-d, r, 1.0), r, r);
+    const double q = n * r;
+    return __builtin_fma(__builtin_fma(-d, q, n), r, q);
+}
+
+// The variance draw of a leg: U_v and 1 - U_v, formed only on the exponential branch.
+struct QeWordUniform {          // Philox: U_v = unit_open64(x2); 1 - U_v = unit_open64(~x2) exactly
+    uint32_t x;
+    template <int SIGN>
+    __device__ __forceinline__ void get(double& u, double& one_minus_u) const {
+        u = unit_open64(SIGN > 0 ? x : ~x);
+        one_minus_u = unit_open64(SIGN > 0 ? ~x : x);
+    }
+};
+struct QeSobolUniform {         // Sobol: sobol_uniform's clipped value
+    double u0;
+    template <int SIGN>
+    __device__ __forceinline__ void get(double& u, double& one_minus_u) const {
+        u = SIGN > 0 ? u0 : 1.0 - u0;
+        one_minus_u = SIGN > 0 ? 1.0 - u0 : u0;
+    }
+};
+
+struct HestonQeStep {
+    double e, theta_1me, c1, c2, k1, k2, k3z, z_unit;
+    // z_unit as in HestonStep: kZScale for the RAW Philox normals, 1 for the Sobol kernels' true ones
+    __device__ __forceinline__ HestonQeStep(const HestonQeContract& c, double unit)
+        : e(c.e), theta_1me(c.theta_1me), c1(c.c1), c2(c.c2), k1(c.k1), k2(c.k2), k3z(c.k3 * (unit * unit)), z_unit(unit) {}
+    struct Moments {
+        double m, s2, m2;
+        bool quadratic;
+    };
+    __device__ __forceinline__ Moments moments(double v) const {
+        Moments mo;
+        mo.m = __builtin_fma(v, e, theta_1me);
+        mo.s2 = __builtin_fma(v, c1, c2);
+        mo.m2 = mo.m * mo.m;
+        mo.quadratic = mo.s2 <= 1.5 * mo.m2;
+        return mo;
+    }
+    // SIGN = +1 / -1: the mirror leg.  z_v, z_s in units of z_unit; z_v is read on the quadratic branch only, the uniform on the other.
+    template <int SIGN, typename Uniform>
+    __device__ __forceinline__ void advance(const Moments& mo, const Uniform& draw, double z_v, double z_s, double& ls, double& v) const {
+        double vn;
+        if (mo.quadratic) {
+            const double x = qe_div(2.0 * mo.m2, mo.s2);                    // 2 / psi >= 4/3
+            const double b2 = (x - 1.0) + sqrt(x * (x - 1.0));
+            const double a = qe_div(mo.m, 1.0 + b2);
+            const double w = __builtin_fma(SIGN > 0 ? z_unit : -z_unit, z_v, sqrt(b2));
+            vn = a * (w * w);
+        } else {
+            const double p = qe_div(mo.s2 - mo.m2, mo.s2 + mo.m2);          // in (1/5, 1)
+            double u, one_minus_u;
+            draw.template get<SIGN>(u, one_minus_u);
+            vn = 0.0;
+            if (u > p) {
+                const double one_minus_p = 1.0 - p;
+                double r = __builtin_amdgcn_rcp(one_minus_p);                // two Newton rounds: 1 / (1 - p) to an ulp
+                r = __builtin_fma(__builtin_fma(-one_minus_p, r, 1.0), r, r);
+                r = __builtin_fma(__builtin_fma(-one_minus_p, r, 1.0), r, r);
+                // (1 - U) / (1 - p) <= 1 up to rounding: the fmax keeps v' >= 0 when U sits an ulp above p
+                vn = fmax(-log(one_minus_u * r) * (mo.m * r), 0.0);
+            }
+        }
+        const double sd = sqrt(k3z * (v + vn));
+        ls = __builtin_fma(sd, SIGN > 0 ? z_s : -z_s, __builtin_fma(k2, vn, __builtin_fma(k1, v, ls)));
+        v = vn;
+    }
+};
+
+// Philox: lane per path, ONE block per step -- counter (path_lo, path_hi, t, kTagHestonQe): (x0, x1) -> box_muller_raw -> (Z_v, Z_s),
+// x2 -> U_v, x3 unused.  heston_surface_kernel's skeleton, cell rows and read-out; a single-cell launch at step n is the European price.
+// Resources (tools/kernel_meta.sh, gfx950; no scratch, no spills; LDS 3.2 KiB), VGPRs plain / antithetic: 92 / 82 (heston_surface_kernel: 92 / 82).
+template <bool ANTI>
+__global__ __launch_bounds__(kBlock) void heston_qe_surface_kernel(PathRange pr, HestonQeContract c, HestonSurfaceCells cells, ReduceWs ws) {
+    constexpr int LEGS = ANTI ? 2 : 1;
+    __shared__ double stage[kWavesPerBlock][2 * kSurfaceCells], cell_strike[kSurfaceCells];
+    __shared__ int32_t cell_step[kSurfaceCells];
+    const SurfaceRows rows{stage, cell_strike, cell_step, static_cast<int>(threadIdx.x) & (kWave - 1),
+                           __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) / kWave)};
+    rows.clear(cells);
+    const RoundKeys rk = pin_round_keys(pr.key0, pr.key1);
+    const HestonQeStep hs(c, kZScale);
+    const int64_t stride = static_cast<int64_t>(gridDim.x) * kBlock;
+    for (int64_t w0 = static_cast<int64_t>(blockIdx.x) * kBlock + rows.wave * kWave; w0 < pr.count; w0 += stride) {      // wave-uniform
+        const int64_t i = w0 + rows.lane;
+        const bool live = i < pr.count;
+        const PathWords pw = path_words(pr, live ? i : 0);
+        double ls[2] = {c.log_s0, c.log_s0}, v[2] = {c.v0, c.v0};             // ls WITHOUT the drift_dt terms: added per read-out
+        int32_t next = 0, pending = cells.step[0];
+        for (int32_t t = 0; t < cells.last; ++t) {
+            const Words4 w = philox4x32_10_pinned(pw.lo, pw.hi, static_cast<uint32_t>(t), kTagHestonQe, rk);
+            float z_v, z_s;
+            box_muller_raw(w.x0, w.x1, z_v, z_s);
+            const QeWordUniform draw{w.x2};
+            hs.advance<1>(hs.moments(v[0]), draw, static_cast<double>(z_v), static_cast<double>(z_s), ls[0], v[0]);
+            if constexpr (ANTI) hs.advance<-1>(hs.moments(v[1]), draw, static_cast<double>(z_v), static_cast<double>(z_s), ls[1], v[1]);
+            rows.read_out<LEGS>(next, pending, t + 1, c.drift_dt, c.sign, ls, live);
+        }
+    }
+    rows.reduce(ws);
+}
+
+// Every (S, v) state of heston_qe_surface_kernel's paths (layouts: path_at), date 0 = (S, v0) as given, as heston_paths_kernel.
+// Resources (tools/kernel_meta.sh, gfx950; no scratch, no spills, no LDS), VGPRs time-major / path-major: 77 / 83 (heston_paths_kernel: 82 / 80).
+template <bool PATH_MAJOR>
+__global__ __launch_bounds__(kBlock) void heston_qe_paths_kernel(PathRange pr, HestonQeContract c, double s_first,
+                                                                 double* __restrict__ spot, double* __restrict__ var) {
+    const HestonQeStep hs(c, kZScale);
+    for_each_path(pr, [&](int64_t i, uint32_t g_lo, uint32_t g_hi) {
+        double ls = c.log_s0, v = c.v0;          // ls WITHOUT the drift_dt terms: added per date below
+        spot[path_at<PATH_MAJOR>(i, 0, pr.count, pr.n_steps)] = s_first;
+        var[path_at<PATH_MAJOR>(i, 0, pr.count, pr.n_steps)] = c.v0;
+        for (int32_t t = 0; t < pr.n_steps; ++t) {
+            const Words4 w = philox4x32_10(g_lo, g_hi, static_cast<uint32_t>(t), kTagHestonQe, pr.key0, pr.key1);
+            float z_v, z_s;
+            box_muller_raw(w.x0, w.x1, z_v, z_s);
+            hs.advance<1>(hs.moments(v), QeWordUniform{w.x2}, static_cast<double>(z_v), static_cast<double>(z_s), ls, v);
+            const size_t at = path_at<PATH_MAJOR>(i, t + 1, pr.count, pr.n_steps);
+            spot[at] = exp(__builtin_fma(static_cast<double>(t + 1), c.drift_dt, ls));
+            var[at] = v;
+        }
+    });
+}
+
+// Sobol, sequential only: dimension 2 t is U_v of step t (sobol_uniform's clipped value; Z_v = its inverse normal, evaluated only
+// where a leg is quadratic -- inverse-transform sampling of v' from ONE uniform), dimension 2 t + 1 gives Z_s.
+// body(t, u_{2t}, z_{2t+1}) for t = 0 .. n - 1 in every lane: heston_qmc_normals' walk (one fold of the common Gray bits per 64
+// dimensions, a broadcast plus the lane's six low rows per dimension) with the even dimension left a uniform.
+template <typename Body>
+__device__ __forceinline__ void heston_qe_qmc_draws(const uint32_t* __restrict__ sv, const uint32_t* __restrict__ shift, int32_t n, int lane,
+                                                    const QmcLanePoint& lp, Body body) {
+    const int32_t dims = 2 * n;
+    for (int32_t c0 = 0; c0 < dims; c0 += kWave) {
+        const int32_t tl = c0 + lane < dims ? c0 + lane : dims - 1;
+        const uint32_t* __restrict__ mine = sv + static_cast<size_t>(tl) * kSobolBits;
+        uint32_t fold = shift[tl];
+#pragma unroll
+        for (int b = 6; b < kSobolBits; ++b) fold ^= mine[b] & (0u - ((lp.gray_hi >> b) & 1u));
+        const int32_t cn = dims - c0 < kWave ? dims - c0 : kWave;            // even: dims and kWave are
+        for (int32_t d = 0; d < cn; d += 2) {
+            double p[2];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const uint32_t* __restrict__ row = sv + static_cast<size_t>(c0 + d + h) * kSobolBits;
+                uint32_t x = static_cast<uint32_t>(__shfl(static_cast<int>(fold), d + h, kWave));
+#pragma unroll
+                for (int b = 0; b < 6; ++b) x = __builtin_amdgcn_bitop3_b32(x, row[b], lp.mask[b], 0x78);   // x ^ (row & mask)
+                p[h] = sobol_uniform(x);
+            }
+            body((c0 + d) >> 1, p[0], ndtri_w_add(0.0, p[1], opaque_zero()));
+        }
+    }
+}
+
+// One step of both legs on Sobol draws: the inverse normal of the variance dimension behind the legs' branch.
+template <bool ANTI>
+__device__ __forceinline__ void heston_qe_qmc_step(const HestonQeStep& hs, double u_v, double z_s, double (&ls)[2], double (&v)[2]) {
+    const HestonQeStep::Moments m0 = hs.moments(v[0]);
+    HestonQeStep::Moments m1 = m0;
+    if constexpr (ANTI) m1 = hs.moments(v[1]);
+    double z_v = 0.0;
+    if (m0.quadratic || (ANTI && m1.quadratic)) z_v = ndtri_w_add(0.0, u_v, opaque_zero());
+    const QeSobolUniform draw{u_v};
+    hs.advance<1>(m0, draw, z_v, z_s, ls[0], v[0]);
+    if constexpr (ANTI) hs.advance<-1>(m1, draw, z_v, z_s, ls[1], v[1]);
+}
+
+// The sequential heston_qmc_surface_kernel's skeleton (aligned blocks in the absolute point index, lanes over points, wave-uniform
+// loops), cell rows and read-out; the walk stops at the last cell's step.
+// Resources (tools/kernel_meta.sh, gfx950; no scratch, no spills; LDS 3.2 KiB), VGPRs plain / antithetic: 94 / 87 (heston_qmc_surface_kernel,
+// sequential: 88 / 74).
+template <bool ANTI>
+__global__ __launch_bounds__(kBlock) void heston_qe_qmc_surface_kernel(QmcRange qr, HestonQeContract c, HestonSurfaceCells cells,
+                                                                       const uint32_t* __restrict__ sv, const uint32_t* __restrict__ shift,
+                                                                       ReduceWs ws) {
+    constexpr int LEGS = ANTI ? 2 : 1;
+    __shared__ double stage[kWavesPerBlock][2 * kSurfaceCells], cell_strike[kSurfaceCells];
+    __shared__ int32_t cell_step[kSurfaceCells];
+    const SurfaceRows rows{stage, cell_strike, cell_step, static_cast<int>(threadIdx.x) & (kWave - 1),
+                           __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) / kWave)};
+    rows.clear(cells);
+    const int lane = rows.lane;
+    const HestonQeStep hs(c, 1.0);
+    const uint64_t base = qr.first & ~static_cast<uint64_t>(kWave - 1);      // blocks aligned in the absolute index
+    const uint64_t end = qr.first + static_cast<uint64_t>(qr.count);
+    const int64_t n_blocks = static_cast<int64_t>((end - base + kWave - 1) / kWave);
+    const int64_t stride = static_cast<int64_t>(gridDim.x) * kWavesPerBlock;
+    for (int64_t blk = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + rows.wave; blk < n_blocks; blk += stride) {      // wave-uniform
+        const uint64_t k = base + static_cast<uint64_t>(blk) * kWave + lane;
+        const bool live = k >= qr.first && k < end;
+        const QmcLanePoint lp(static_cast<uint32_t>(k));
+        double ls[2] = {c.log_s0, c.log_s0}, v[2] = {c.v0, c.v0};             // ls WITHOUT the drift_dt terms
+        int32_t next = 0, pending = cells.step[0];
+        heston_qe_qmc_draws(sv, shift, cells.last, lane, lp, [&](int32_t t, double u_v, double z_s) {
+            heston_qe_qmc_step<ANTI>(hs, u_v, z_s, ls, v);
+            rows.read_out<LEGS>(next, pending, t + 1, c.drift_dt, c.sign, ls, live);
+        });
+    }
+    rows.reduce(ws);
+}
+
+// Spot and variance of points [0, count) at dates 0 .. n (layouts: path_at), date 0 = (S, v0) as given: the sequential
+// heston_qmc_paths_kernel with the QE step.
+// Resources (tools/kernel_meta.sh, gfx950; no scratch, no spills, no LDS), VGPRs time-major / path-major: 90 / 102
+// (heston_qmc_paths_kernel, sequential: 82 / 94).
+template <bool PATH_MAJOR>
+__global__ __launch_bounds__(kBlock) void heston_qe_qmc_paths_kernel(QmcRange qr, HestonQeContract c, double s_first,
+                                                                     const uint32_t* __restrict__ sv, const uint32_t* __restrict__ shift,
+                                                                     double* spot, double* var) {
+    const int lane = static_cast<int>(threadIdx.x) & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) / kWave);
+    const int32_t n = qr.dims;
+    const int64_t count = qr.count;
+    const HestonQeStep hs(c, 1.0);
+    const int64_t n_blocks = (count + kWave - 1) / kWave;
+    const int64_t stride = static_cast<int64_t>(gridDim.x) * kWavesPerBlock;
+    for (int64_t blk = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave; blk < n_blocks; blk += stride) {
+        const int64_t i = blk * kWave + lane;
+        const bool live = i < count;
+        const QmcLanePoint lp(static_cast<uint32_t>(i));
+        double ls[2] = {c.log_s0, c.log_s0}, v[2] = {c.v0, c.v0};             // leg 0 only; ls WITHOUT the drift_dt terms
+        heston_qe_qmc_draws(sv, shift, n, lane, lp, [&](int32_t t, double u_v, double z_s) {
+            heston_qe_qmc_step<false>(hs, u_v, z_s, ls, v);
+            if (live) {
+                const size_t p = path_at<PATH_MAJOR>(i, t + 1, count, n);
+                spot[p] = exp(__builtin_fma(static_cast<double>(t + 1), c.drift_dt, ls[0]));
+                var[p] = v[0];
+            }
+        });
+        if (live) {
+            spot[path_at<PATH_MAJOR>(i, 0, count, n)] = s_first;
+            var[path_at<PATH_MAJOR>(i, 0, count, n)] = c.v0;
+        }
+    }
+}
+
 // ------------------------------------------------------- validation taps ----
 __global__ void philox_words_kernel(uint64_t first, int64_t n_paths, int32_t block0, int32_t n_blocks,
                                     uint32_t tag, uint32_t k0, uint32_t k1, uint32_t* __restrict__ out) {

@@ -7,6 +7,9 @@ accuracy checks have the same oracle the reference has; it is not a Monte Carlo 
 
 Additive: ``method="qmc"`` runs `price_monte_carlo` and `simulate_paths` on scrambled-Sobol points, two dimensions per step
 (_qmc_tables below, include/olmc.h "quasi-Monte Carlo Heston"), by default with two Brownian bridges.
+Additive: ``scheme="qe"`` (keyword-only; "euler" is the default and today's code path) discretises with Andersen's quadratic-exponential
+scheme (include/olmc.h "Heston, quadratic-exponential scheme") in `price_monte_carlo`, `simulate_paths`, `price_surface`,
+`calibration_objective` and `calibrate_heston`; the path payoffs (`price_asian`, `price_barrier`, `price_lookback`) stay on Euler.
 """
 from __future__ import annotations
 
@@ -19,6 +22,7 @@ import numpy as np
 from . import _hip
 
 _SURFACE_CELLS = 16          # cells of one launch (OLMC_MAX_BATCH)
+_STEPS_PER_YEAR = {"euler": 64, "qe": 16}      # calibrate_heston's grid when n_steps is None
 
 
 def _qmc_tables(method: str, path_construction: str, n_paths: int, n_steps: int, seed: Optional[int]):
@@ -26,6 +30,16 @@ def _qmc_tables(method: str, path_construction: str, n_paths: int, n_steps: int,
     from .exotic import _qmc_tables as tables
 
     return tables(method, path_construction, n_paths, n_steps, seed, dims_per_step=2)
+
+
+def _check_scheme(scheme: str, method: str, path_construction: str) -> bool:
+    """True for scheme="qe"; ValueError (before the device is touched) for an unknown scheme and for QE on bridged Sobol points."""
+    if scheme not in ("euler", "qe"):
+        raise ValueError("scheme must be 'euler' or 'qe'")
+    if scheme == "qe" and method == "qmc" and path_construction == "bridge":
+        raise ValueError("scheme='qe' with method='qmc' takes path_construction='sequential': pass path_construction='sequential' "
+                         "(QE's variance draw is a uniform, not a Brownian increment, so there is nothing for a bridge to build)")
+    return scheme == "qe"
 
 
 def _surface_steps(maturities, n_steps: int) -> Tuple[float, list]:
@@ -130,7 +144,8 @@ class HestonPricer:
     def price_monte_carlo(self, S: float, K: float, T: float, r: float, q: float = 0.0,
                           option_type: Literal["call", "put"] = "call", n_paths: int = 100000, n_steps: int = 252,
                           seed: Optional[int] = None, antithetic: bool = False, return_error: bool = False, *,
-                          method: Literal["pseudo", "qmc"] = "pseudo", path_construction: Literal["bridge", "sequential"] = "bridge"):
+                          method: Literal["pseudo", "qmc"] = "pseudo", path_construction: Literal["bridge", "sequential"] = "bridge",
+                          scheme: Literal["euler", "qe"] = "euler"):
         """method (additive): "pseudo" (default) = the Philox paths; "qmc" = scrambled-Sobol paths: `seed` is the scramble seed of
         scipy.stats.qmc.Sobol(d=2 n_steps, scramble=True, seed=seed) (None draws one), point k drives path k through
         z = norm.ppf(clip(u, 1e-10, 1 - 1e-10)); n_paths <= 2**30, n_steps <= 10600.
@@ -140,9 +155,20 @@ class HestonPricer:
         With method="qmc", antithetic=True also prices the mirrored point -z (2 n_paths samples), and return_error's standard error is
         the naive per-path one: for Sobol points it is not a confidence interval (it overstates the error).
         Refused (ValueError, before the device is touched): an unknown method or path_construction, and with method="qmc"
-        n_steps > 10600, n_steps > 1024 with the bridge, n_paths > 2**30."""
+        n_steps > 10600, n_steps > 1024 with the bridge, n_paths > 2**30.
+        scheme (additive): "euler" (default) = the reference's full-truncation Euler step; "qe" = Andersen's quadratic-exponential
+        scheme (include/olmc.h "Heston, quadratic-exponential scheme"), priced as the one-cell surface (K, T) of price_surface(...,
+        scheme="qe") -- the same bits.  QE samples the variance from a distribution matched to its exact conditional mean and variance
+        and needs 4-16 steps per year where Euler needs hundreds when the Feller condition fails; its Philox stream (one block per
+        step, its own tag) and its Sobol draws (dimension 2t = the variance's uniform, 2t + 1 = the spot's normal) are not Euler's, so
+        equal seeds give other paths.  With method="qmc" it takes path_construction="sequential" only: the default "bridge" is refused
+        (ValueError, before the device is touched), as is an unknown scheme."""
         if n_paths < 1 or n_steps < 1:
             raise ValueError("n_paths and n_steps must be >= 1")
+        if _check_scheme(scheme, method, path_construction):
+            prices, errors = self.price_surface(S, [K], [T], r, q, option_type, n_paths, n_steps, seed, antithetic, return_error=True,
+                                                method=method, path_construction=path_construction, scheme="qe")
+            return (np.float64(prices[0, 0]), float(errors[0, 0])) if return_error else np.float64(prices[0, 0])
         qmc = _qmc_tables(method, path_construction, n_paths, n_steps, seed)
         if qmc is not None:
             sv, shift, bridge = qmc
@@ -158,7 +184,7 @@ class HestonPricer:
     def price_surface(self, S: float, strikes, maturities, r: float, q: float = 0.0, option_type: Literal["call", "put"] = "call",
                       n_paths: int = 100000, n_steps: int = 252, seed: Optional[int] = None, antithetic: bool = False,
                       return_error: bool = False, *, method: Literal["pseudo", "qmc"] = "pseudo",
-                      path_construction: Literal["bridge", "sequential"] = "bridge"):
+                      path_construction: Literal["bridge", "sequential"] = "bridge", scheme: Literal["euler", "qe"] = "euler"):
         """European prices on a strike x maturity grid from ONE set of paths: a float64 array (len(strikes), len(maturities)), the
         orientation of calibrate_heston's market_ivs[i, j]; with return_error, (prices, std_errors) of that shape.
         n_steps is the number of steps to the LONGEST maturity T = max(maturities), dt = T / n_steps; every maturity must lie on that
@@ -178,7 +204,10 @@ class HestonPricer:
         whose construction ends at T_j.  What the full-horizon construction buys at an intermediate date (the price scatter over
         scrambles against Philox seeds) has NOT been measured on the device yet: tools/heston_surface_timing.py measures it.
         seed=None, antithetic, method, path_construction, the standard error's meaning and the refusals as price_monte_carlo; also
-        refused: empty strikes or maturities, a maturity <= 0."""
+        refused: empty strikes or maturities, a maturity <= 0.
+        scheme as price_monte_carlo: with "qe" the cells are read-outs of simulate_paths(..., scheme="qe")'s columns in the same way
+        (the launches, the ties to the matrix, the independence of the cells and the shards' sums all hold as above)."""
+        qe = _check_scheme(scheme, method, path_construction)
         ks = [float(k) for k in np.asarray(strikes, dtype=np.float64).ravel()]
         if not ks:
             raise ValueError("strikes must not be empty")
@@ -193,7 +222,12 @@ class HestonPricer:
         errors = np.empty_like(prices)
         for launch in _surface_launches(steps, len(ks)):
             cell_k, cell_m = [ks[i] for i, _j in launch], [steps[j] for _i, j in launch]
-            if qmc is not None:
+            if qe and qmc is not None:
+                sv, shift, _bridge = qmc
+                sts = _hip.heston_qe_qmc_surface(S, T, r, q, option_type == "call", *model, cell_k, cell_m, n_paths, sv, shift, False, antithetic)
+            elif qe:
+                sts = _hip.heston_qe_surface(S, T, r, q, option_type == "call", *model, cell_k, cell_m, n_paths, n_steps, s, antithetic)
+            elif qmc is not None:
                 sv, shift, bridge = qmc
                 sts = _hip.heston_qmc_surface(S, T, r, q, option_type == "call", *model, cell_k, cell_m, n_paths, sv, shift, bridge, antithetic)
             else:
@@ -204,12 +238,21 @@ class HestonPricer:
 
     def simulate_paths(self, S: float, T: float, r: float, q: float = 0.0, n_paths: int = 1000, n_steps: int = 252,
                        seed: Optional[int] = None, *, method: Literal["pseudo", "qmc"] = "pseudo",
-                       path_construction: Literal["bridge", "sequential"] = "bridge") -> Tuple[np.ndarray, np.ndarray]:
+                       path_construction: Literal["bridge", "sequential"] = "bridge",
+                       scheme: Literal["euler", "qe"] = "euler") -> Tuple[np.ndarray, np.ndarray]:
         """heston.py:257-305: (spot_paths, variance_paths), each (n_paths, n_steps + 1), column 0 = (S, v0).
-        The states of price_monte_carlo's recursion for the same seed, method and path_construction (additive, as there)."""
+        The states of price_monte_carlo's recursion for the same seed, method, path_construction and scheme (additive, as there)."""
         if n_paths < 1 or n_steps < 1:
             raise ValueError("n_paths and n_steps must be >= 1")
+        qe = _check_scheme(scheme, method, path_construction)
         qmc = _qmc_tables(method, path_construction, n_paths, n_steps, seed)
+        model = (self.kappa, self.theta, self.sigma_v, self.rho, self.v0)
+        if qe and qmc is not None:
+            sv, shift, _bridge = qmc
+            return _hip.heston_qe_qmc_paths(S, T, r, q, *model, n_paths, sv, shift, False, path_major=True)
+        if qe:
+            s = seed if seed is not None else int(np.random.default_rng().integers(0, 2**31))
+            return _hip.heston_qe_paths(S, T, r, q, *model, n_paths, n_steps, s, path_major=True)
         if qmc is not None:
             sv, shift, bridge = qmc
             return _hip.heston_qmc_paths(S, T, r, q, self.kappa, self.theta, self.sigma_v, self.rho, self.v0, n_paths, sv, shift, bridge,
@@ -302,9 +345,10 @@ def greeks_heston(heston_pricer, S: float, K: float, T: float, r: float, sigma: 
 
 def calibration_objective(market_data: dict, *, n_paths: int = 1 << 14, n_steps: Optional[int] = None, seed: int = 0,
                           method: Literal["pseudo", "qmc"] = "qmc", path_construction: Literal["bridge", "sequential"] = "bridge",
-                          antithetic: bool = False):
+                          antithetic: bool = False, scheme: Literal["euler", "qe"] = "euler"):
     """calibrate_heston's objective as a function of (kappa, theta, sigma_v, rho, v0): checks market_data and the settings as
-    calibrate_heston does (before the device is touched) and returns the callable; its attribute `evals` counts the surfaces priced."""
+    calibrate_heston does (before the device is touched) and returns the callable; its attribute `evals` counts the surfaces priced.
+    scheme as HestonPricer.price_surface; n_steps=None picks the grid as calibrate_heston does for the scheme."""
     from .black_scholes import implied_volatility
 
     missing = [key for key in ("spot", "strikes", "maturities", "market_ivs", "r") if key not in market_data]
@@ -318,8 +362,9 @@ def calibration_objective(market_data: dict, *, n_paths: int = 1 << 14, n_steps:
     q_yield = float(market_data.get("q", 0.0))
     if strikes.size == 0:
         raise ValueError("strikes must not be empty")
+    _check_scheme(scheme, method, path_construction)
     if n_steps is None:
-        n_steps = _grid_steps(maturities)
+        n_steps = _grid_steps(maturities, _STEPS_PER_YEAR[scheme])
     _surface_steps(maturities, n_steps)
     if market_ivs.shape != (strikes.size, maturities.size):
         raise ValueError(f"market_ivs must have shape (len(strikes), len(maturities)) = {(strikes.size, maturities.size)}")
@@ -344,7 +389,7 @@ def calibration_objective(market_data: dict, *, n_paths: int = 1 << 14, n_steps:
             return 1e10
         objective.evals += 1
         prices = pricer.price_surface(spot, strikes, maturities, r_rate, q_yield, "call", n_paths, n_steps, seed, antithetic,
-                                      method=method, path_construction=path_construction)
+                                      method=method, path_construction=path_construction, scheme=scheme)
         total, count = 0.0, 0
         for i, K in enumerate(strikes):
             for j, T in enumerate(maturities):
@@ -363,7 +408,7 @@ def calibration_objective(market_data: dict, *, n_paths: int = 1 << 14, n_steps:
 
 def calibrate_heston(market_data: dict, initial_params: Optional[dict] = None, *, n_paths: int = 1 << 14, n_steps: Optional[int] = None,
                      seed: int = 0, method: Literal["pseudo", "qmc"] = "qmc", path_construction: Literal["bridge", "sequential"] = "bridge",
-                     antithetic: bool = False, maxiter: int = 200) -> HestonPricer:
+                     antithetic: bool = False, maxiter: int = 200, scheme: Literal["euler", "qe"] = "euler") -> HestonPricer:
     """heston.py:312-414 on the device's own Monte Carlo prices: fit (kappa, theta, sigma_v, rho, v0) to an implied-volatility surface.
 
     market_data: spot, strikes, maturities, market_ivs[i, j] (strike i, maturity j; NaN = no quote), r and optionally q.  As in the
@@ -377,12 +422,17 @@ def calibrate_heston(market_data: dict, initial_params: Optional[dict] = None, *
     (ValueError if none of at most 1024 steps exists).  Returns the calibrated HestonPricer with the final objective value and the number
     of surfaces priced (objective evaluations inside the bounds) attached as `calibration_error` and `calibration_evals`.  maxiter
     (additive) caps L-BFGS-B's iterations; the default is the reference's 200.
+    scheme (additive) as HestonPricer.price_surface: "qe" calibrates on the quadratic-exponential scheme's surfaces, with
+    method="qmc" (the default here) on path_construction="sequential" only -- the default "bridge" is refused; n_steps=None then picks
+    at least 16 steps per year instead of 64.  At a model that violates the Feller condition Euler's bias at 16-64 steps per year is
+    tens of standard errors (DESIGN.md "Heston: the quadratic-exponential scheme"), so Euler's objective at the parameters that
+    generated a surface is far from 0 and QE's is not.
     Refused (ValueError, before the device is touched): a missing market_data key, market_ivs of another shape than
     (len(strikes), len(maturities)), seed=None, and what price_surface refuses."""
     from scipy.optimize import minimize
 
     objective = calibration_objective(market_data, n_paths=n_paths, n_steps=n_steps, seed=seed, method=method,
-                                      path_construction=path_construction, antithetic=antithetic)
+                                      path_construction=path_construction, antithetic=antithetic, scheme=scheme)
     if initial_params is None:
         initial_params = {"kappa": 2.0, "theta": 0.04, "sigma_v": 0.3, "rho": -0.5, "v0": 0.04}
     x0 = [initial_params[key] for key in ("kappa", "theta", "sigma_v", "rho", "v0")]

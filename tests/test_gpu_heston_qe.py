@@ -1,0 +1,324 @@
+"""Heston's quadratic-exponential scheme on the device (include/olmc.h "Heston, quadratic-exponential scheme"; scheme="qe" of
+HestonPricer.price_monte_carlo / simulate_paths / price_surface, calibration_objective).
+
+The reference is tests/heston_qe_reference.py, the NumPy restatement of the step, fed the draws the header pins.  The bars: TIE (rel
+1e-10, abs 1e-12) for per-path ties, rel 1e-10 / 1e-6 for a cell's price / error, rel 1e-12 for sums that must add up, standard errors
+for the accuracy.  QE's variance map jumps where psi crosses 1.5 (the two branches match two moments, not each other), so a path with a
+step whose psi lies within 1e-9 of 1.5 may take the other branch on the device and is set aside: at most 1 path in 1000.
+
+1. Per-path tie on Sobol points: SciPy's points, norm.ppf.
+2. Per-path tie on Philox blocks: the oracle's words, the instrumented build's Box-Muller tap.
+3. The surface is a read-out of the path matrix: both methods, both legs; independence, shards, price_monte_carlo's cell, determinism.
+4. Accuracy with power: QE within 4 standard errors of the characteristic-function price where Euler is more than 20 away.
+5. The calibration objective at the parameters that made the quotes.
+6. Refusals and NaN at the C ABI.
+"""
+import functools
+import math
+import warnings
+
+import numpy as np
+import pytest
+
+import optionslab_amd as ol
+from optionslab_amd import _hip
+from optionslab_amd.black_scholes import implied_volatility
+from optionslab_amd.exceptions import AccelerationError
+from optionslab_amd.heston import calibration_objective
+from optionslab_amd.monte_carlo import sobol_tables
+from oracle import philox_oracle
+from tests import heston_qe_reference as qe
+
+pytestmark = pytest.mark.gpu
+
+TIE = dict(rel=1e-10, abs=1e-12)
+S, R, Q, T = 100.0, 0.05, 0.0, 1.0
+MODEL_NAMES = ("feller_violated", "steep", "usual")
+SEQUENTIAL = dict(method="qmc", path_construction="sequential", scheme="qe")
+PHILOX_SEED = 3
+WORST = {}                                              # the worst deviations seen, printed by every tie
+
+
+def pricer(model):
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", UserWarning)                               # Feller
+        return ol.HestonPricer(*model)
+
+
+@functools.lru_cache(maxsize=None)
+def sobol_draws(n, count, seed):
+    return qe.sobol_draws(n, count, seed)
+
+
+@functools.lru_cache(maxsize=None)
+def philox_draws(n, count, seed, path_offset):
+    from tools.probe import binding as probe
+
+    words = philox_oracle.philox_words(seed, path_offset, count, 0, n, qe.STREAM_HESTON_QE)
+    return qe.philox_draws(words, probe.box_muller_probe)
+
+
+def close(got, want):
+    return np.abs(got - want) <= np.maximum(TIE["rel"] * np.abs(want), TIE["abs"])
+
+
+def check_paths(label, model, got_spot, got_var, want):
+    """The device's matrices against the restatement's, path by path."""
+    spot, var, quadratic, psi = want
+    count, n = quadratic.shape
+    assert got_spot.shape == got_var.shape == (count, n + 1)
+    assert np.all(got_spot[:, 0] == S) and np.all(got_var[:, 0] == model[4])
+    aside = np.any(np.abs(psi - qe.PSI_C) < 1e-9, axis=1)
+    assert int(aside.sum()) <= count // 1000, (label, int(aside.sum()))
+    keep = ~aside
+    # the branch the device took, from its own states: psi of the variance it stored
+    got_quadratic = qe.moments(got_var[:, :-1], qe.constants(model, R, Q, T, n))[2] <= qe.PSI_C
+    assert np.array_equal(got_quadratic[keep], quadratic[keep]), label
+    assert np.all(got_var >= 0.0)
+    dev_spot = float(np.max(np.abs(got_spot[keep] / spot[keep] - 1.0)))
+    dev_var = float(np.max(np.abs(got_var[keep] - var[keep]) / np.maximum(np.abs(var[keep]), 1e-2)))
+    WORST[label[0]] = max(WORST.get(label[0], 0.0), dev_spot, dev_var)
+    print(label, "set aside", int(aside.sum()), "worst spot rel", dev_spot, "worst var (rel, floor 1e-2)", dev_var, "exponential steps",
+          float(1.0 - quadratic.mean()), "zeros", int((var[:, 1:] == 0.0).sum()), int((got_var[:, 1:] == 0.0).sum()), "worst so far", WORST)
+    assert np.all(close(got_spot[keep], spot[keep])), label
+    assert np.all(close(got_var[keep], var[keep])), label
+    return quadratic, (var[:, 1:] == 0.0), (got_var[:, 1:] == 0.0)
+
+
+def check_branches(name, n, quadratic, zero_want, zero_got):
+    if name == "usual":
+        assert quadratic.all() and not zero_want.any() and not zero_got.any()
+    elif n >= 7:
+        assert quadratic.any() and not quadratic.all()                              # both branches occur
+        assert zero_want.any() and zero_got.any()                                   # some v' = 0 exactly, on both sides
+        assert np.mean(zero_want != zero_got) <= 1e-3
+
+
+# ------------------------------------------------------------------------------------------ 1. per-path tie, Sobol ----
+@pytest.mark.parametrize("seed", (0, 5))
+@pytest.mark.parametrize("name", MODEL_NAMES)
+@pytest.mark.parametrize("N,n", [(1000, 1), (1000, 7), (4133, 16), (200, 33)])     # 33 steps = 66 dimensions: across the 64-dimension fold
+def test_sobol_paths_tie_to_the_restatement_on_scipys_points(N, n, name, seed):
+    model = qe.MODELS[name]
+    got_spot, got_var = pricer(model).simulate_paths(S, T, R, Q, N, n, seed, **SEQUENTIAL)
+    want = qe.paths(S, model, R, Q, T, n, *sobol_draws(n, N, seed))
+    check_branches(name, n, *check_paths(("sobol", N, n, name, seed), model, got_spot, got_var, want))
+
+
+def test_sobol_time_major_layout_holds_the_same_states():
+    model, N, n, seed = qe.FELLER_VIOLATED, 1000, 7, 5
+    sv, shift = sobol_tables(2 * n, seed, N)
+    a_spot, a_var = _hip.heston_qe_qmc_paths(S, T, R, Q, *model, N, sv, shift, path_major=True)
+    b_spot, b_var = _hip.heston_qe_qmc_paths(S, T, R, Q, *model, N, sv, shift, path_major=False)
+    assert np.array_equal(a_spot, b_spot.T) and np.array_equal(a_var, b_var.T)
+    c_spot, c_var = _hip.heston_qe_paths(S, T, R, Q, *model, N, n, seed, path_major=True)
+    d_spot, d_var = _hip.heston_qe_paths(S, T, R, Q, *model, N, n, seed, path_major=False)
+    assert np.array_equal(c_spot, d_spot.T) and np.array_equal(c_var, d_var.T)
+
+
+# ----------------------------------------------------------------------------------------- 2. per-path tie, Philox ----
+@pytest.mark.parametrize("name", MODEL_NAMES)
+@pytest.mark.parametrize("N,n", [(1000, 1), (1000, 7), (4133, 16)])
+def test_philox_paths_tie_to_the_restatement_on_the_oracles_words(N, n, name):
+    model = qe.MODELS[name]
+    got_spot, got_var = pricer(model).simulate_paths(S, T, R, Q, N, n, PHILOX_SEED, scheme="qe")
+    want = qe.paths(S, model, R, Q, T, n, *philox_draws(n, N, PHILOX_SEED, 0))
+    check_branches(name, n, *check_paths(("philox", N, n, name), model, got_spot, got_var, want))
+
+
+@pytest.mark.parametrize("name", MODEL_NAMES)
+@pytest.mark.parametrize("N,n", [(1000, 1), (1000, 7), (4133, 16)])
+def test_philox_paths_beyond_2_to_the_32_tie_to_the_restatement(N, n, name):
+    """The path matrix has no offset (as olmc_heston_paths has none), so paths [2^32 + 5, 2^32 + 5 + N) are reached through the surface's
+    path_offset.  A call of strike 0 pays the spot itself: single-path launches give the spot of a path at every date (here 24 paths
+    spread over the range), and a launch over the whole range gives the column sums of all N."""
+    model, offset = qe.MODELS[name], (1 << 32) + 5
+    spot, var, quadratic, psi = qe.paths(S, model, R, Q, T, n, *philox_draws(n, N, PHILOX_SEED, offset))
+    aside = np.any(np.abs(psi - qe.PSI_C) < 1e-9, axis=1)
+    assert int(aside.sum()) <= N // 1000
+    dates = list(range(1, n + 1))
+    worst = 0.0
+    for i in np.linspace(0, N - 1, 24).astype(int):
+        if aside[i]:
+            continue
+        got = _hip.heston_qe_surface(S, T, R, Q, True, *model, [0.0] * n, dates, 1, n, PHILOX_SEED, False, offset + int(i))
+        for st, t in zip(got, dates):
+            assert st.n == 1 and st.sum == pytest.approx(spot[i, t], **TIE), (name, N, n, i, t)
+            worst = max(worst, abs(st.sum / spot[i, t] - 1.0))
+    got = _hip.heston_qe_surface(S, T, R, Q, True, *model, [0.0] * n, dates, N, n, PHILOX_SEED, False, offset)
+    for st, t in zip(got, dates):
+        if aside.any():                                                             # the column sums need every path
+            print("column sums not compared: a path was set aside")
+            break
+        assert st.n == N and st.sum == pytest.approx(float(np.sum(spot[:, t])), **TIE)
+        assert st.sumsq == pytest.approx(float(np.sum(spot[:, t] ** 2)), **TIE)
+        worst = max(worst, abs(st.sum / float(np.sum(spot[:, t])) - 1.0))
+    print(("philox", N, n, name, "offset 2^32 + 5"), "worst rel", worst)
+    if name != "usual" and n >= 7:
+        assert quadratic.any() and not quadratic.all() and (var[:, 1:] == 0.0).any()
+
+
+# -------------------------------------------------------------------------------------------- 3. the surface read-out ----
+SURFACE_N, SURFACE_STEPS, SURFACE_SEED = 4133, 16, PHILOX_SEED
+# 17 maturities on a 16-step grid: unsorted, with repeats -- 17 cells, two launches
+MATURITIES_17 = tuple(m / 16 for m in (8, 16, 1, 4, 16, 12, 2, 3, 8, 15, 5, 6, 7, 9, 10, 11, 13))
+SURFACES = ((((95.0,), MATURITIES_17)), ((80.0, 100.0, 120.0), (0.5, 0.25, 1.0, 0.25, 0.0625, 0.75)))
+
+
+def payoff(spot, strike, step, option_type):
+    return np.maximum((1.0 if option_type == "call" else -1.0) * (spot[:, step] - strike), 0)
+
+
+@pytest.mark.parametrize("method", ("pseudo", "qmc"))
+@pytest.mark.parametrize("name", ("feller_violated", "steep"))
+def test_every_cell_is_a_read_out_of_the_path_matrix(name, method):
+    model, N, n, seed = qe.MODELS[name], SURFACE_N, SURFACE_STEPS, SURFACE_SEED
+    kw = SEQUENTIAL if method == "qmc" else dict(scheme="qe")
+    p = pricer(model)
+    spot, _var = p.simulate_paths(S, T, R, Q, N, n, seed, **kw)
+    draws = sobol_draws(n, N, seed) if method == "qmc" else philox_draws(n, N, seed, 0)
+    mirror, _v, _q, mirror_psi = qe.paths(S, model, R, Q, T, n, *draws, mirror=True)
+    assert not np.any(np.abs(mirror_psi - qe.PSI_C) < 1e-9)                         # the mirror leg's sums need every path
+    for strikes, maturities in SURFACES:
+        for option_type in ("call", "put"):
+            for antithetic in (False, True):
+                prices, errors = p.price_surface(S, strikes, maturities, R, Q, option_type, N, n, seed, antithetic, True, **kw)
+                assert prices.shape == errors.shape == (len(strikes), len(maturities))
+                for i, strike in enumerate(strikes):
+                    for j, t_j in enumerate(maturities):
+                        step = round(t_j * n)
+                        x = payoff(spot, strike, step, option_type)
+                        if antithetic:
+                            x = np.concatenate([x, payoff(mirror, strike, step, option_type)])
+                        disc = math.exp(-R * t_j)
+                        assert prices[i, j] == pytest.approx(disc * float(np.mean(x)), rel=1e-10, abs=1e-14), (strike, t_j, option_type, antithetic)
+                        assert errors[i, j] == pytest.approx(disc * float(np.std(x)) / math.sqrt(len(x)), rel=1e-6, abs=1e-14), (strike, t_j)
+                if len(maturities) == 17:
+                    assert prices[0, 1] == prices[0, 4] and prices[0, 0] == prices[0, 8]                  # the repeats
+
+
+def launchers(model, N, n, seed, is_call, antithetic):
+    sv, shift = sobol_tables(2 * n, seed, N)
+    return (lambda ks, ms, cnt=N, off=0: _hip.heston_qe_surface(S, T, R, Q, is_call, *model, ks, ms, cnt, n, seed, antithetic, off),
+            lambda ks, ms, cnt=N, off=0: _hip.heston_qe_qmc_surface(S, T, R, Q, is_call, *model, ks, ms, cnt, sv, shift, False, antithetic, off))
+
+
+def test_a_cells_bits_do_not_depend_on_its_neighbours():
+    N, n, seed = SURFACE_N, SURFACE_STEPS, 31
+    cells = [(80.0 + 2.5 * i, m) for i, m in enumerate((16, 1, 8, 8, 3, 16, 12, 5, 2, 9, 16, 7, 4, 11, 13, 15))]
+    for launch in launchers(qe.FELLER_VIOLATED, N, n, seed, False, True):
+        full = launch([k for k, _m in cells], [m for _k, m in cells])
+        backwards = launch([k for k, _m in cells[::-1]], [m for _k, m in cells[::-1]])[::-1]
+        others = launch([k if i == 6 else k + 1.0 for i, (k, _m) in enumerate(cells)], [m if i == 6 else 16 for i, (_k, m) in enumerate(cells)])
+        for i, (strike, step) in enumerate(cells):
+            alone = launch([strike], [step])[0]
+            for other in (alone, backwards[i]):
+                assert (other.sum, other.sumsq, other.price, other.std_error) == (full[i].sum, full[i].sumsq, full[i].price, full[i].std_error)
+        assert (others[6].sum, others[6].sumsq) == (full[6].sum, full[6].sumsq)
+
+
+def test_shards_of_one_stream_or_sequence_add_up():
+    N, n, a, seed = SURFACE_N, SURFACE_STEPS, 1000, 9                                # a is no multiple of 64
+    cells = [(100.0, 16), (80.0, 1), (120.0, 16), (100.0, 8), (90.0, 5)]
+    ks, ms = [k for k, _m in cells], [m for _k, m in cells]
+    for model, is_call, antithetic in ((qe.FELLER_VIOLATED, True, False), (qe.STEEP, False, True)):
+        for launch in launchers(model, N, n, seed, is_call, antithetic):
+            for whole, lo, hi in zip(launch(ks, ms), launch(ks, ms, a, 0), launch(ks, ms, N - a, a)):
+                assert whole.n == lo.n + hi.n == N * (2 if antithetic else 1)
+                assert whole.sum == pytest.approx(lo.sum + hi.sum, rel=1e-12)
+                assert whole.sumsq == pytest.approx(lo.sumsq + hi.sumsq, rel=1e-12)
+
+
+def test_price_monte_carlo_is_the_terminal_cell_and_equal_seeds_give_equal_bits():
+    p = pricer(qe.FELLER_VIOLATED)
+    N, n = SURFACE_N, SURFACE_STEPS
+    strikes, maturities = (80.0, 100.0, 120.0), (0.5, 1.0)
+    for kw in (dict(scheme="qe"), SEQUENTIAL):
+        surface = lambda seed, steps=n: p.price_surface(S, strikes, maturities, R, Q, "put", N, steps, seed, True, True, **kw)
+        first, other = surface(11), surface(12)
+        surface(12, 32)                                                             # other tables in between
+        again = surface(11)
+        assert np.array_equal(again[0], first[0]) and np.array_equal(again[1], first[1]) and not np.array_equal(first[0], other[0])
+        for i, strike in enumerate(strikes):
+            price, error = p.price_monte_carlo(S, strike, T, R, Q, "put", N, n, 11, True, True, **kw)
+            assert (price, error) == (first[0][i, 1], first[1][i, 1])
+        # the QE stream is its own: Euler at the same seed walks other paths
+        euler = {k: v for k, v in kw.items() if k != "scheme"}
+        assert p.price_monte_carlo(S, 100.0, T, R, Q, "put", N, n, 11, True, **euler) != first[0][1, 1]
+
+
+# ------------------------------------------------------------------------------------------ 4. accuracy with power ----
+def test_qe_is_unbiased_where_euler_is_tens_of_standard_errors_away():
+    """Feller violated, 16 steps to T = 1, 2^20 Philox paths, seed 7, against the characteristic-function call (tests/heston_qe_reference.py
+    heston_call: the published P1 / P2 form).  NumPy prototype of both schemes at these settings: QE -0.0 and +0.1 standard errors at
+    K = 100 and 120, Euler +64 and +82."""
+    p = pricer(qe.FELLER_VIOLATED)
+    for strike in (100.0, 120.0):
+        anchor = qe.heston_call(S, strike, T, R, Q, qe.FELLER_VIOLATED)
+        bias = {}
+        for scheme in ("qe", "euler"):
+            price, error = p.price_monte_carlo(S, strike, T, R, Q, "call", 1 << 20, 16, 7, return_error=True, scheme=scheme)
+            bias[scheme] = (price - anchor) / error
+            print("strike", strike, scheme, "price", price, "anchor", anchor, "standard error", error, "bias / standard error", bias[scheme])
+        assert abs(bias["qe"]) <= 4.0
+        assert abs(bias["euler"]) > 20.0                                            # the first assertion has power
+
+
+# ------------------------------------------------------------------------ 5. the calibration objective at the truth ----
+def test_the_calibration_objective_at_the_true_parameters():
+    """Quotes from the characteristic function through the package's implied_volatility on the 3 x 3 grid; 2^14 Sobol points, 16 steps,
+    sequential, seed 0.  NumPy prototype over seeds 0-3: QE 0.8e-6 .. 2.6e-6, Euler 280 .. 850 times that."""
+    model = qe.FELLER_VIOLATED
+    strikes, maturities = (90.0, 100.0, 110.0), (0.25, 0.5, 1.0)
+    ivs = [[implied_volatility(qe.heston_call(S, k, t, R, Q, model), S, k, t, R, "call", Q) for t in maturities] for k in strikes]
+    market = dict(spot=S, strikes=strikes, maturities=maturities, market_ivs=ivs, r=R, q=Q)
+    settings = dict(n_paths=1 << 14, n_steps=16, method="qmc", path_construction="sequential", seed=0)
+    value = {scheme: calibration_objective(market, scheme=scheme, **settings)(model) for scheme in ("qe", "euler")}
+    print("objective at the truth", value, "ratio", value["euler"] / value["qe"])
+    assert value["qe"] <= 1e-5
+    assert value["euler"] >= 50.0 * value["qe"]
+
+
+# ------------------------------------------------------------------------------------------- 6. refusals and NaN ----
+def test_refusals_at_the_c_abi():
+    N, n = 128, 4
+    sv, shift = sobol_tables(2 * n, 1, N)
+    good = qe.USUAL
+    bad_models = ((0.0, *good[1:]), (-2.0, *good[1:]), (good[0], 0.0, *good[2:]), (*good[:2], 0.0, *good[3:]), (*good[:2], -0.3, *good[3:]),
+                  (*good[:4], -0.01))
+    for model in bad_models:
+        for call in (lambda m: _hip.heston_qe_surface(S, T, R, Q, True, *m, [100.0], [n], N, n, 1),
+                     lambda m: _hip.heston_qe_qmc_surface(S, T, R, Q, True, *m, [100.0], [n], N, sv, shift),
+                     lambda m: _hip.heston_qe_paths(S, T, R, Q, *m, N, n, 1),
+                     lambda m: _hip.heston_qe_qmc_paths(S, T, R, Q, *m, N, sv, shift)):
+            with pytest.raises(AccelerationError, match="for the QE scheme"):
+                call(model)
+    with pytest.raises(AccelerationError, match="OLMC_QMC_SEQUENTIAL only"):
+        _hip.heston_qe_qmc_surface(S, T, R, Q, True, *good, [100.0], [n], N, sv, shift, bridge=True)
+    with pytest.raises(AccelerationError, match="OLMC_QMC_SEQUENTIAL only"):
+        _hip.heston_qe_qmc_paths(S, T, R, Q, *good, N, sv, shift, bridge=True)
+    for k in (17,):                                                                 # k = 0: tests/test_heston_qe_cpu.py, on real arrays
+        with pytest.raises(AccelerationError, match="number of cells"):
+            _hip.heston_qe_surface(S, T, R, Q, True, *good, [100.0] * k, [n] * k, N, n, 1)
+        with pytest.raises(AccelerationError, match="number of cells"):
+            _hip.heston_qe_qmc_surface(S, T, R, Q, True, *good, [100.0] * k, [n] * k, N, sv, shift)
+    # v0 = 0 is a legal start
+    spot, var = _hip.heston_qe_paths(S, T, R, Q, *good[:4], 0.0, N, n, 1, path_major=True)
+    assert np.all(var[:, 0] == 0.0) and np.all(var[:, 1:] >= 0.0) and np.all(np.isfinite(spot))
+
+
+def test_nan_inputs_answer_nan_cell_by_cell():
+    N, n, seed = 1000, 8, 3
+    sv, shift = sobol_tables(2 * n, seed, N)
+    nan = float("nan")
+    model, steps = qe.FELLER_VIOLATED, [8, 5, 5]
+    clean = _hip.heston_qe_surface(S, T, R, Q, True, *model, [80.0, 100.0, 120.0], steps, N, n, seed)
+    for got in (_hip.heston_qe_surface(S, T, R, Q, True, *model, [80.0, nan, 120.0], steps, N, n, seed),
+                _hip.heston_qe_qmc_surface(S, T, R, Q, True, *model, [80.0, nan, 120.0], steps, N, sv, shift)):
+        assert math.isnan(got[1].price) and math.isnan(got[1].std_error) and math.isfinite(got[0].price) and math.isfinite(got[2].price)
+    got = _hip.heston_qe_surface(S, T, R, Q, True, *model, [80.0, nan, 120.0], steps, N, n, seed)
+    assert (got[0].price, got[2].price) == (clean[0].price, clean[2].price)
+    for args in ((nan, T, R, Q, True, *model), (S, nan, R, Q, True, *model), (S, T, nan, Q, True, *model), (S, T, R, nan, True, *model),
+                 (S, T, R, Q, True, nan, *model[1:]), (S, T, R, Q, True, *model[:2], nan, *model[3:]), (S, T, R, Q, True, *model[:4], nan)):
+        assert all(math.isnan(st.price) for st in _hip.heston_qe_surface(*args, [80.0, 100.0, 120.0], steps, N, n, seed))
+        assert all(math.isnan(st.price) for st in _hip.heston_qe_qmc_surface(*args, [80.0, 100.0, 120.0], steps, N, sv, shift))
