@@ -66,7 +66,9 @@ extern "C" {
                               *    olmc_heston_path_payoff, olmc_heston_qmc_path_payoff (Asian, barrier and lookback payoffs under Heston),
                               *    olmc_heston_surface, olmc_heston_qmc_surface (a strike x maturity grid of European options on one set of Heston paths),
                               *    olmc_heston_qe_surface, olmc_heston_qe_qmc_surface, olmc_heston_qe_paths, olmc_heston_qe_qmc_paths (Heston by the
-                              *    quadratic-exponential scheme: surfaces and path matrices) */
+                              *    quadratic-exponential scheme: surfaces and path matrices),
+                              *    olmc_heston_autocallable, olmc_heston_autocallable_qmc, olmc_heston_cliquet, olmc_heston_cliquet_qmc (the structured
+                              *    products under Heston, by either scheme) */
 
 enum {
     OLMC_OK = 0,
@@ -611,6 +613,48 @@ int olmc_heston_qe_paths(double S, double T, double r, double q, double kappa, d
 int olmc_heston_qe_qmc_paths(double S, double T, double r, double q, double kappa, double theta, double sigma_v, double rho, double v0,
                              int construction, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift, int32_t bits,
                              int path_major, double* spot_host, double* var_host);
+
+/* ---- structured products under Heston -------
+ * The autocallable and the cliquet of olmc_autocallable / olmc_cliquet on Heston paths, ONE launch per call that stores no path: the
+ * payoff of path i is what the reference's AutocallableOption / CliquetOption.price (src/pricing_models/exotic_options.py:438-491,
+ * 526-554) computes from row i of the spot matrix of the scheme's own path-matrix call for the same seed or tables --
+ *   scheme = OLMC_HESTON_EULER  olmc_heston_paths (Philox: stream OLMC_STREAM_HESTON, one block per two steps) / olmc_heston_qmc_paths
+ *                               (Sobol: both constructions, the dimension assignment, bridge plan and slabs of "quasi-Monte Carlo Heston");
+ *   scheme = OLMC_HESTON_QE     olmc_heston_qe_paths (Philox: stream OLMC_STREAM_HESTON_QE, one block per step) / olmc_heston_qe_qmc_paths
+ *                               (Sobol: OLMC_QMC_SEQUENTIAL only, the draws of "Heston, quadratic-exponential scheme").
+ * Date 0 is the spot S itself.  Levels are decided in log space, ln(S_t / S) against ln(level), where the matrix route compares prices:
+ * the two agree except for a path within rounding (about 1e-16 relative) of a level.
+ *   autocallable  levels relative to S; observation dates f, 2f, ... <= n_steps (f = observation_freq); a path not yet redeemed with
+ *                 S_t / S >= autocall_barrier at observation k redeems (1 + coupon_rate T k / n_obs) exp(-r k f dt); at maturity the rest
+ *                 get 1 (+ coupon_rate T if S_n / S >= coupon_barrier), or S_n / S if the minimum over dates 0 .. n_steps touched
+ *                 ki_barrier and S_n < S; times exp(-r T).  .sum / .sumsq carry each payoff's own discount and .price is the plain mean
+ *                 (a fraction of notional), as olmc_autocallable's.
+ *   cliquet       n_periods periods of n_steps / n_periods (integer division) steps from date 0; trailing dates never enter a period and
+ *                 are not simulated (the QE and sequential Sobol forms do not draw their dimensions).  x = max(clip(sum_p clip(S_end /
+ *                 S_start - 1, local_floor, local_cap), global_floor, global_cap), 0) S; .sum / .sumsq undiscounted, .price = exp(-r T)
+ *                 mean, as olmc_cliquet's.
+ * .std_error is the naive per-path one (for Sobol points not a confidence interval).  antithetic != 0 also prices the mirrored leg of
+ * the scheme (2 n payoffs).  A call prices paths [path_offset, path_offset + n_local) / points [point_offset, point_offset + n_points):
+ * shards add up (olmc_combine_stats).  A NaN input gives NaN results.  v0 < 0 means under Euler what it means in olmc_heston.
+ * Refused (OLMC_ERR_ARG, before any device work): a null pointer, an unknown scheme, rho outside [-1, 1], observation_freq < 1 or
+ * > n_steps, n_periods outside [1, n_steps], what olmc_heston / olmc_heston_qmc refuse of counts, steps, construction, tables and the
+ * bridge's cap, and for OLMC_HESTON_QE what olmc_heston_qe_qmc_surface refuses: kappa, theta or sigma_v <= 0, v0 < 0, OLMC_QMC_BRIDGE. */
+enum { OLMC_HESTON_EULER = 0, OLMC_HESTON_QE = 1 };
+int olmc_heston_autocallable(double S, double T, double r, double q, double kappa, double theta, double sigma_v, double rho, double v0,
+                             double autocall_barrier, double coupon_barrier, double coupon_rate, double ki_barrier, int32_t observation_freq,
+                             int scheme, int64_t path_offset, int64_t n_local, int32_t n_steps, uint64_t seed, int antithetic,
+                             olmc_stats* out);
+int olmc_heston_autocallable_qmc(double S, double T, double r, double q, double kappa, double theta, double sigma_v, double rho, double v0,
+                                 double autocall_barrier, double coupon_barrier, double coupon_rate, double ki_barrier,
+                                 int32_t observation_freq, int scheme, int construction, int64_t point_offset, int64_t n_points,
+                                 int32_t n_steps, const uint32_t* sv, const uint32_t* shift, int32_t bits, int antithetic, olmc_stats* out);
+int olmc_heston_cliquet(double S, double T, double r, double q, double kappa, double theta, double sigma_v, double rho, double v0,
+                        double local_cap, double local_floor, double global_cap, double global_floor, int32_t n_periods, int scheme,
+                        int64_t path_offset, int64_t n_local, int32_t n_steps, uint64_t seed, int antithetic, olmc_stats* out);
+int olmc_heston_cliquet_qmc(double S, double T, double r, double q, double kappa, double theta, double sigma_v, double rho, double v0,
+                            double local_cap, double local_floor, double global_cap, double global_floor, int32_t n_periods, int scheme,
+                            int construction, int64_t point_offset, int64_t n_points, int32_t n_steps, const uint32_t* sv,
+                            const uint32_t* shift, int32_t bits, int antithetic, olmc_stats* out);
 
 /* ---- multi-GPU, single process ------------------------------------------
  * n_paths split into n_gpus contiguous global path ranges (rank d = device d, [d N / P, (d + 1) N / P)).  Per list of devices the

@@ -112,6 +112,12 @@ PROTOTYPES = {
                                         C.POINTER(C.c_uint32), _I32, _I, C.POINTER(Stats)]),
     "olmc_heston_qe_paths": (_I, [_D] * 9 + [_I64, _I32, _U64T, _I, C.POINTER(_D), C.POINTER(_D)]),
     "olmc_heston_qe_qmc_paths": (_I, [_D] * 9 + [_I, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, _I, C.POINTER(_D), C.POINTER(_D)]),
+    "olmc_heston_autocallable": (_I, [_D] * 13 + [_I32, _I, _I64, _I64, _I32, _U64T, _I, C.POINTER(Stats)]),
+    "olmc_heston_autocallable_qmc": (_I, [_D] * 13 + [_I32, _I, _I, _I64, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, _I,
+                                          C.POINTER(Stats)]),
+    "olmc_heston_cliquet": (_I, [_D] * 13 + [_I32, _I, _I64, _I64, _I32, _U64T, _I, C.POINTER(Stats)]),
+    "olmc_heston_cliquet_qmc": (_I, [_D] * 13 + [_I32, _I, _I, _I64, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, _I,
+                                     C.POINTER(Stats)]),
     "olmc_multi_gpu_european":(_I, _SIX + [_I, _I64, _I32, _U64T, _I, _I, C.POINTER(Stats)]),
     "olmc_multi_gpu_greeks_fd": (_I, _SIX + [_I, _I64, _I32, _U64T, _I, _I, C.POINTER(_D), C.POINTER(Stats)]),
     "olmc_multi_gpu_european_cv": (_I, _SIX + [_I, _I64, _I32, _U64T, _I, _I, C.POINTER(CvMoments)]),
@@ -755,6 +761,58 @@ def heston_qe_qmc_surface(S, T, r, q, is_call: bool, kappa, theta, sigma_v, rho,
                                             QMC_BRIDGE if bridge else QMC_SEQUENTIAL, int(point_offset), int(n_points), n_steps, psv, psh,
                                             int(sv.shape[1]), int(antithetic), out))
     return list(out)[:len(strikes)]
+
+
+HESTON_EULER, HESTON_QE = 0, 1      # olmc.h: OLMC_HESTON_EULER / OLMC_HESTON_QE
+
+
+def heston_autocallable(S, T, r, q, kappa, theta, sigma_v, rho, v0, autocall_barrier, coupon_barrier, coupon_rate, ki_barrier,
+                        observation_freq: int, n_paths: int, n_steps: int, seed: int, antithetic: bool = False, path_offset: int = 0,
+                        qe: bool = False) -> Stats:
+    """The autocallable on heston()'s paths (qe: on heston_qe_surface()'s), one launch (olmc_heston_autocallable)."""
+    out = Stats()
+    _check(lib().olmc_heston_autocallable(S, T, r, q, kappa, theta, sigma_v, rho, v0, autocall_barrier, coupon_barrier, coupon_rate, ki_barrier,
+                                          int(observation_freq), HESTON_QE if qe else HESTON_EULER, int(path_offset), int(n_paths), int(n_steps),
+                                          seed64(seed), int(antithetic), C.byref(out)))
+    return out
+
+
+def heston_autocallable_qmc(S, T, r, q, kappa, theta, sigma_v, rho, v0, autocall_barrier, coupon_barrier, coupon_rate, ki_barrier,
+                            observation_freq: int, n_points: int, sv: np.ndarray, shift: np.ndarray, bridge: bool = True,
+                            antithetic: bool = False, point_offset: int = 0, qe: bool = False) -> Stats:
+    """heston_autocallable on scrambled-Sobol points (olmc_heston_autocallable_qmc): n_steps = sv.shape[0] / 2; qe takes bridge=False only."""
+    sv, psv, shift, psh = _sobol_args(sv, shift, point_offset, n_points)
+    n_steps = _heston_steps(sv)
+    out = Stats()
+    _check(lib().olmc_heston_autocallable_qmc(S, T, r, q, kappa, theta, sigma_v, rho, v0, autocall_barrier, coupon_barrier, coupon_rate,
+                                              ki_barrier, int(observation_freq), HESTON_QE if qe else HESTON_EULER,
+                                              QMC_BRIDGE if bridge else QMC_SEQUENTIAL, int(point_offset), int(n_points), n_steps, psv, psh,
+                                              int(sv.shape[1]), int(antithetic), C.byref(out)))
+    return out
+
+
+def heston_cliquet(S, T, r, q, kappa, theta, sigma_v, rho, v0, local_cap, local_floor, global_cap, global_floor, n_periods: int,
+                   n_paths: int, n_steps: int, seed: int, antithetic: bool = False, path_offset: int = 0, qe: bool = False) -> Stats:
+    """The cliquet on heston()'s paths (qe: on heston_qe_surface()'s), one launch (olmc_heston_cliquet)."""
+    out = Stats()
+    _check(lib().olmc_heston_cliquet(S, T, r, q, kappa, theta, sigma_v, rho, v0, local_cap, local_floor, global_cap, global_floor,
+                                     int(n_periods), HESTON_QE if qe else HESTON_EULER, int(path_offset), int(n_paths), int(n_steps),
+                                     seed64(seed), int(antithetic), C.byref(out)))
+    return out
+
+
+def heston_cliquet_qmc(S, T, r, q, kappa, theta, sigma_v, rho, v0, local_cap, local_floor, global_cap, global_floor, n_periods: int,
+                       n_points: int, sv: np.ndarray, shift: np.ndarray, bridge: bool = True, antithetic: bool = False,
+                       point_offset: int = 0, qe: bool = False) -> Stats:
+    """heston_cliquet on scrambled-Sobol points (olmc_heston_cliquet_qmc): n_steps = sv.shape[0] / 2; qe takes bridge=False only."""
+    sv, psv, shift, psh = _sobol_args(sv, shift, point_offset, n_points)
+    n_steps = _heston_steps(sv)
+    out = Stats()
+    _check(lib().olmc_heston_cliquet_qmc(S, T, r, q, kappa, theta, sigma_v, rho, v0, local_cap, local_floor, global_cap, global_floor,
+                                         int(n_periods), HESTON_QE if qe else HESTON_EULER, QMC_BRIDGE if bridge else QMC_SEQUENTIAL,
+                                         int(point_offset), int(n_points), n_steps, psv, psh, int(sv.shape[1]), int(antithetic),
+                                         C.byref(out)))
+    return out
 
 
 def heston_qe_paths(S, T, r, q, kappa, theta, sigma_v, rho, v0, n_paths: int, n_steps: int, seed: int, path_major: bool = False):

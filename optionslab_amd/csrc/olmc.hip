@@ -2803,6 +2803,149 @@ extern "C" int olmc_heston_qe_qmc_paths(double S, double T, double r, double q, 
     return copy_to_host(c, var_host, d_var, static_cast<size_t>(bytes));
 }
 
+// ====================================================== structured products under Heston ====
+// olmc_autocallable / olmc_cliquet and their Sobol forms on Heston paths, by either scheme (include/olmc.h "structured products under
+// Heston"): the contracts of make_autocall / make_cliquet (their GBM drift and vol are not read), the model and range checks of the
+// scheme's own entry points, one launch of heston_product_kernel, heston_qmc_product_kernel, heston_qe_product_kernel or
+// heston_qe_qmc_product_kernel with the product as the policy.
+namespace {
+int heston_scheme_check(int scheme, double kappa, double theta, double sigma_v, double rho, double v0) {
+    if (scheme == OLMC_HESTON_EULER) return heston_check(rho);
+    if (scheme == OLMC_HESTON_QE) return heston_qe_check(kappa, theta, sigma_v, rho, v0);
+    return fail(OLMC_ERR_ARG, "bad scheme (OLMC_HESTON_EULER or OLMC_HESTON_QE)");
+}
+
+struct HestonModel {
+    double kappa, theta, sigma_v, rho, v0;
+    bool nan() const { return std::isnan(kappa + theta + sigma_v + rho + v0); }
+};
+
+// Philox: paths [path_offset, path_offset + n_local) of olmc_heston's stream (Euler) / olmc_heston_qe_surface's (QE).
+template <template <bool> class Product>
+int run_heston_product(double S, double T, double r, double q, const HestonModel& m, int scheme, const typename Product<false>::Contract& pc,
+                       double r_for_discount, bool bad, int64_t path_offset, int64_t n_local, int32_t n_steps, uint64_t seed, int antithetic,
+                       olmc_stats* out) {
+    if (scheme == OLMC_HESTON_QE) {
+        const HestonQeContract hc = make_heston_qe(S, T, r, q, 1, m.kappa, m.theta, m.sigma_v, m.rho, m.v0, n_steps);
+        return run_structured(path_offset, n_local, n_steps, seed, antithetic, r_for_discount, T, bad, out,
+                              [&](int32_t grid, hipStream_t st, const EventPair* timed, const PathRange& pr, const ReduceWs& ws) {
+                                  with_bool(antithetic != 0, [&](auto a) {
+                                      launch_timed(heston_qe_product_kernel<Product, a>, dim3(grid), dim3(kBlock), st, timed, pr, hc, pc, ws);
+                                  });
+                              });
+    }
+    const HestonContract hc = make_heston(S, 0.0, T, r, q, 1, m.kappa, m.theta, m.sigma_v, m.rho, m.v0, n_steps);
+    return run_structured(path_offset, n_local, n_steps, seed, antithetic, r_for_discount, T, bad, out,
+                          [&](int32_t grid, hipStream_t st, const EventPair* timed, const PathRange& pr, const ReduceWs& ws) {
+                              with_bool(antithetic != 0, [&](auto a) {
+                                  launch_timed(heston_product_kernel<Product, a>, dim3(grid), dim3(kBlock), st, timed, pr, hc, pc, ws);
+                              });
+                          });
+}
+
+// The checks of a Sobol call that do not depend on the product, in the order of olmc_heston_qe_qmc_surface.
+int heston_qmc_product_check(int scheme, const HestonModel& m, int construction, int64_t point_offset, int64_t n_points, int32_t n_steps,
+                             const uint32_t* sv, const uint32_t* shift, int32_t bits) {
+    int rc = heston_scheme_check(scheme, m.kappa, m.theta, m.sigma_v, m.rho, m.v0);
+    if (rc) return rc;
+    if (scheme == OLMC_HESTON_QE) {
+        rc = heston_qe_sequential(construction);
+        if (rc) return rc;
+    }
+    return qmc_path_check(construction, point_offset, n_points, n_steps, sv, shift, bits, 2);
+}
+
+// Sobol: points [point_offset, point_offset + n_points) of olmc_heston_qmc's construction (Euler) / olmc_heston_qe_qmc_surface's (QE).
+template <template <bool> class Product>
+int run_heston_qmc_product(double S, double T, double r, double q, const HestonModel& m, int scheme, const typename Product<false>::Contract& pc,
+                           double r_for_discount, bool bad, int construction, int64_t point_offset, int64_t n_points, int32_t n_steps,
+                           const uint32_t* sv, const uint32_t* shift, int antithetic, olmc_stats* out) {
+    if (scheme == OLMC_HESTON_QE) {
+        const HestonQeContract hc = make_heston_qe(S, T, r, q, 1, m.kappa, m.theta, m.sigma_v, m.rho, m.v0, n_steps);
+        return run_qmc_payoff(construction, point_offset, n_points, n_steps, sv, shift, antithetic, r_for_discount, T, bad, out,
+                              [&](int32_t g, hipStream_t s, const EventPair* timed, const QmcPathLaunch& pl, const ReduceWs& ws) {
+                                  with_bool(pl.anti, [&](auto a) {
+                                      launch_timed(heston_qe_qmc_product_kernel<Product, a>, dim3(g), dim3(kBlock), s, timed, pl.qr, hc, pc, pl.d_sv,
+                                                   pl.d_shift, ws);
+                                  });
+                              },
+                              2, heston_qmc_shape(point_offset, n_points, n_steps));      // sequential: the grid over the aligned blocks, no slabs
+    }
+    const HestonContract hc = make_heston(S, 0.0, T, r, q, 1, m.kappa, m.theta, m.sigma_v, m.rho, m.v0, n_steps);
+    return run_qmc_payoff(construction, point_offset, n_points, n_steps, sv, shift, antithetic, r_for_discount, T, bad, out,
+                          [&](int32_t g, hipStream_t s, const EventPair* timed, const QmcPathLaunch& pl, const ReduceWs& ws) {
+                              with_bool(pl.bridge, [&](auto b) {
+                                  with_bool(pl.anti, [&](auto a) {
+                                      launch_timed(heston_qmc_product_kernel<Product, b, a>, dim3(g), dim3(kBlock), s, timed, pl.qr, hc, pc, pl.d_sv,
+                                                   pl.d_shift, pl.plan, pl.slabs, ws);
+                                  });
+                              });
+                          },
+                          2, heston_qmc_shape(point_offset, n_points, n_steps));
+}
+}  // namespace
+
+extern "C" int olmc_heston_autocallable(double S, double T, double r, double q, double kappa, double theta, double sigma_v, double rho, double v0,
+                                        double autocall_barrier, double coupon_barrier, double coupon_rate, double ki_barrier,
+                                        int32_t observation_freq, int scheme, int64_t path_offset, int64_t n_local, int32_t n_steps,
+                                        uint64_t seed, int antithetic, olmc_stats* out) {
+    if (!out) return fail(OLMC_ERR_ARG, "null pointer");
+    int rc = heston_scheme_check(scheme, kappa, theta, sigma_v, rho, v0);
+    if (rc) return rc;
+    rc = autocall_check(observation_freq, n_steps);
+    if (rc) return rc;
+    const HestonModel m{kappa, theta, sigma_v, rho, v0};
+    const AutocallSetup a = make_autocall(S, T, r, 0.0, q, autocall_barrier, coupon_barrier, coupon_rate, ki_barrier, observation_freq, n_steps);
+    // payoffs are already discounted path by path, as olmc_autocallable's: no outer discount
+    return run_heston_product<HestonAutocall>(S, T, r, q, m, scheme, a.ac, 0.0, a.bad || m.nan(), path_offset, n_local, n_steps, seed, antithetic, out);
+}
+
+extern "C" int olmc_heston_autocallable_qmc(double S, double T, double r, double q, double kappa, double theta, double sigma_v, double rho,
+                                            double v0, double autocall_barrier, double coupon_barrier, double coupon_rate, double ki_barrier,
+                                            int32_t observation_freq, int scheme, int construction, int64_t point_offset, int64_t n_points,
+                                            int32_t n_steps, const uint32_t* sv, const uint32_t* shift, int32_t bits, int antithetic,
+                                            olmc_stats* out) {
+    if (!out) return fail(OLMC_ERR_ARG, "null pointer");
+    const HestonModel m{kappa, theta, sigma_v, rho, v0};
+    int rc = heston_qmc_product_check(scheme, m, construction, point_offset, n_points, n_steps, sv, shift, bits);
+    if (rc) return rc;
+    rc = autocall_check(observation_freq, n_steps);
+    if (rc) return rc;
+    const AutocallSetup a = make_autocall(S, T, r, 0.0, q, autocall_barrier, coupon_barrier, coupon_rate, ki_barrier, observation_freq, n_steps);
+    return run_heston_qmc_product<HestonAutocall>(S, T, r, q, m, scheme, a.ac, 0.0, a.bad || m.nan(), construction, point_offset, n_points, n_steps,
+                                                  sv, shift, antithetic, out);
+}
+
+extern "C" int olmc_heston_cliquet(double S, double T, double r, double q, double kappa, double theta, double sigma_v, double rho, double v0,
+                                   double local_cap, double local_floor, double global_cap, double global_floor, int32_t n_periods, int scheme,
+                                   int64_t path_offset, int64_t n_local, int32_t n_steps, uint64_t seed, int antithetic, olmc_stats* out) {
+    if (!out) return fail(OLMC_ERR_ARG, "null pointer");
+    int rc = heston_scheme_check(scheme, kappa, theta, sigma_v, rho, v0);
+    if (rc) return rc;
+    rc = cliquet_check(n_periods, n_steps);
+    if (rc) return rc;
+    const HestonModel m{kappa, theta, sigma_v, rho, v0};
+    const CliquetContract cc = make_cliquet(S, T, r, 0.0, q, local_cap, local_floor, global_cap, global_floor, n_periods, n_steps);
+    const bool bad = cliquet_poisoned(S, T, r, 0.0, q, local_cap, local_floor, global_cap, global_floor) || m.nan();
+    return run_heston_product<HestonCliquet>(S, T, r, q, m, scheme, cc, r, bad, path_offset, n_local, n_steps, seed, antithetic, out);
+}
+
+extern "C" int olmc_heston_cliquet_qmc(double S, double T, double r, double q, double kappa, double theta, double sigma_v, double rho, double v0,
+                                       double local_cap, double local_floor, double global_cap, double global_floor, int32_t n_periods,
+                                       int scheme, int construction, int64_t point_offset, int64_t n_points, int32_t n_steps,
+                                       const uint32_t* sv, const uint32_t* shift, int32_t bits, int antithetic, olmc_stats* out) {
+    if (!out) return fail(OLMC_ERR_ARG, "null pointer");
+    const HestonModel m{kappa, theta, sigma_v, rho, v0};
+    int rc = heston_qmc_product_check(scheme, m, construction, point_offset, n_points, n_steps, sv, shift, bits);
+    if (rc) return rc;
+    rc = cliquet_check(n_periods, n_steps);
+    if (rc) return rc;
+    const CliquetContract cc = make_cliquet(S, T, r, 0.0, q, local_cap, local_floor, global_cap, global_floor, n_periods, n_steps);
+    const bool bad = cliquet_poisoned(S, T, r, 0.0, q, local_cap, local_floor, global_cap, global_floor) || m.nan();
+    return run_heston_qmc_product<HestonCliquet>(S, T, r, q, m, scheme, cc, r, bad, construction, point_offset, n_points, n_steps, sv, shift,
+                                                 antithetic, out);
+}
+
 namespace {
 // k (2 .. 16) contracts on points [point_offset, point_offset + n_paths), ONE launch (european_qmc_batch_kernel) whose grid covers
 // them all, queued on c's own stream behind the table: the 2 nsets sums then `tail` at d_out, contract i's pair at slot pos[i]

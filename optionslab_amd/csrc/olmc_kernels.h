@@ -4319,6 +4319,298 @@ __global__ __launch_bounds__(kBlock) void heston_qe_qmc_paths_kernel(QmcRange qr
     }
 }
 
+// ------------------------------------------------- structured products under Heston ----
+// The autocallable and the cliquet of autocall_kernel / cliquet_kernel on Heston paths, Euler or QE, Philox or Sobol (include/olmc.h
+// "structured products under Heston"): the payoff of a path is what the reference's AutocallableOption / CliquetOption.price
+// (exotic_options.py:438-491, 526-554) computes from its row of HestonPricer.simulate_paths' spot matrix for the same scheme, stream or
+// points.  A lane owns a path (and its mirror), both legs in fp64 registers, as in heston_path_kernel and the QE surface kernels; the
+// recursions are HestonStep / HestonQeStep as they stand, so the variance keeps simulate_paths' bits.  A product is a per-date POLICY on
+// x_t = ln(S_t / S): ls is carried relative to ln S (it starts at 0, date 0 is S itself), and the date's value is formed as the path
+// kernels form it, fma(t + 1, drift_dt, ls).  The four skeletons below take the policy as a template argument:
+//   Product::last(pc, n)        the date the step loop ends at (the cliquet's trailing dates never enter a period)
+//   p.start(pc)                 a new path; date 0 contributes x_0 = 0
+//   p.date(pc, x)               date t + 1 of both legs, dates in order
+//   p.payoffs(pc, x_last, acc)  the legs' payoffs into (sum, sum of squares)
+// AutocallContract and CliquetContract are the GBM kernels'; their drift and vol are not read.
+template <bool ANTI>
+struct HestonAutocall {
+    using Contract = AutocallContract;
+    static constexpr int LEGS = ANTI ? 2 : 1;
+    int32_t until_obs;               // wave-uniform, as autocall_kernel's
+    double coupon, df;               // wave-uniform running values of the redemption amount (1 + coupon_k) df_k
+    double mn[2], pay[2];
+    bool redeemed[2];
+    __device__ __forceinline__ static int32_t last(const Contract&, int32_t n) { return n; }
+    __device__ __forceinline__ void start(const Contract& c) {
+        until_obs = c.obs_freq;
+        coupon = 0.0; df = 1.0;
+#pragma unroll
+        for (int l = 0; l < 2; ++l) { mn[l] = 0.0; pay[l] = 0.0; redeemed[l] = false; }      // the knock-in minimum includes date 0
+    }
+    __device__ __forceinline__ void date(const Contract& c, const double (&x)[2]) {
+        const bool observe = (--until_obs == 0);
+        double redemption = 0.0;
+        if (observe) {
+            until_obs = c.obs_freq;
+            coupon += c.coupon_unit;
+            df *= c.obs_df;
+            redemption = (1.0 + coupon) * df;
+        }
+#pragma unroll
+        for (int l = 0; l < LEGS; ++l) {
+            mn[l] = min_f64(mn[l], x[l]);
+            const bool call_now = observe && !redeemed[l] && x[l] >= c.log_autocall;
+            pay[l] = call_now ? redemption : pay[l];
+            redeemed[l] = redeemed[l] || call_now;
+        }
+    }
+    __device__ __forceinline__ void payoffs(const Contract& c, const double (&x)[2], double (&acc)[2]) const {
+#pragma unroll
+        for (int l = 0; l < LEGS; ++l) {
+            double y = pay[l];
+            if (!redeemed[l]) {
+                double fin = 1.0;
+                if (x[l] >= c.log_coupon) fin += c.final_coupon;
+                if (mn[l] <= c.log_ki && x[l] < 0.0) fin = exp(x[l]);      // the one exponential of a leg: the loss branch
+                y = fin * c.final_df;
+            }
+            acc[0] += y; acc[1] += y * y;
+        }
+    }
+};
+
+template <bool ANTI>
+struct HestonCliquet {
+    using Contract = CliquetContract;
+    static constexpr int LEGS = ANTI ? 2 : 1;
+    int32_t until_reset;             // wave-uniform
+    double at_reset[2], total[2];    // ln(S / S_0) at the last reset; the sum of the clipped period returns
+    __device__ __forceinline__ static int32_t last(const Contract& c, int32_t) { return c.steps_per_period * c.n_periods; }
+    __device__ __forceinline__ void start(const Contract& c) {
+        until_reset = c.steps_per_period;
+#pragma unroll
+        for (int l = 0; l < 2; ++l) { at_reset[l] = 0.0; total[l] = 0.0; }
+    }
+    __device__ __forceinline__ void date(const Contract& c, const double (&x)[2]) {
+        if (--until_reset != 0) return;
+        until_reset = c.steps_per_period;
+#pragma unroll
+        for (int l = 0; l < LEGS; ++l) {
+            const double local = exp(x[l] - at_reset[l]) - 1.0;              // (S_end - S_start) / S_start
+            total[l] += fmin(fmax(local, c.local_floor), c.local_cap);
+            at_reset[l] = x[l];
+        }
+    }
+    __device__ __forceinline__ void payoffs(const Contract& c, const double (&)[2], double (&acc)[2]) const {
+#pragma unroll
+        for (int l = 0; l < LEGS; ++l) {
+            const double clipped = fmin(fmax(total[l], c.global_floor), c.global_cap);
+            const double y = fmax(clipped, 0.0) * c.s0;
+            acc[0] += y; acc[1] += y * y;
+        }
+    }
+};
+
+// The two legs of a path under a product.  Euler: heston_path_kernel's date (HestonPathLegs, unit 1); QE: the surface kernels' step.
+template <typename Product, bool ANTI>
+struct HestonProductLegs {
+    static constexpr int LEGS = ANTI ? 2 : 1;
+    HestonStep hs;
+    double mu_dt;
+    double ls[2], v[2];
+    Product p;
+    __device__ __forceinline__ HestonProductLegs(const HestonContract& c, double z_unit) : hs(c, z_unit), mu_dt(c.mu_dt) {}
+    __device__ __forceinline__ void start(const typename Product::Contract& pc, double v_start) {
+#pragma unroll
+        for (int l = 0; l < 2; ++l) { ls[l] = 0.0; v[l] = v_start; }
+        p.start(pc);
+    }
+    __device__ __forceinline__ void log_spots(int32_t date, double (&x)[2]) const {
+        const double td = static_cast<double>(date);
+        x[1] = 0.0;
+#pragma unroll
+        for (int l = 0; l < LEGS; ++l) x[l] = __builtin_fma(td, mu_dt, ls[l]);
+    }
+    // step t (normals z1, z2 in the unit hs was built for), then date t + 1; advance = false: heston_start took the step
+    __device__ __forceinline__ void date(const typename Product::Contract& pc, int32_t t, double z1, double z2, bool advance) {
+        if (advance) {
+            const double u = hs.zs * z1;
+            const double w = __builtin_fma(hs.b, z2, hs.a * z1);
+            hs.advance<1>(u, w, ls[0], v[0]);
+            if constexpr (ANTI) hs.advance<-1>(u, w, ls[1], v[1]);
+        }
+        double x[2];
+        log_spots(t + 1, x);
+        p.date(pc, x);
+    }
+    __device__ __forceinline__ void payoffs(const typename Product::Contract& pc, int32_t last, double (&acc)[2]) const {
+        double x[2];
+        log_spots(last, x);
+        p.payoffs(pc, x, acc);
+    }
+};
+
+template <typename Product, bool ANTI>
+struct HestonQeProductLegs {
+    static constexpr int LEGS = ANTI ? 2 : 1;
+    HestonQeStep hs;
+    double drift_dt;
+    double ls[2], v[2];
+    Product p;
+    __device__ __forceinline__ HestonQeProductLegs(const HestonQeContract& c, double z_unit) : hs(c, z_unit), drift_dt(c.drift_dt) {}
+    __device__ __forceinline__ void start(const typename Product::Contract& pc, double v0) {
+#pragma unroll
+        for (int l = 0; l < 2; ++l) { ls[l] = 0.0; v[l] = v0; }
+        p.start(pc);
+    }
+    __device__ __forceinline__ void log_spots(int32_t date, double (&x)[2]) const {
+        const double td = static_cast<double>(date);
+        x[1] = 0.0;
+#pragma unroll
+        for (int l = 0; l < LEGS; ++l) x[l] = __builtin_fma(td, drift_dt, ls[l]);
+    }
+    // after step t has advanced ls and v: date t + 1
+    __device__ __forceinline__ void date(const typename Product::Contract& pc, int32_t t) {
+        double x[2];
+        log_spots(t + 1, x);
+        p.date(pc, x);
+    }
+    __device__ __forceinline__ void payoffs(const typename Product::Contract& pc, int32_t last, double (&acc)[2]) const {
+        double x[2];
+        log_spots(last, x);
+        p.payoffs(pc, x, acc);
+    }
+};
+
+// Euler on Philox: heston_kernel's stream (tag kTagHeston, one block for two steps), heston_path_kernel's skeleton.
+// Resources (tools/kernel_meta.sh, gfx950; no scratch, no spills; LDS 64 B, the reduction), VGPRs plain / antithetic:
+// autocallable 116 / 124, cliquet 104 / 98 (heston_path_kernel, extrema: 100 / 114).
+template <template <bool> class Product, bool ANTI>
+__global__ __launch_bounds__(kBlock) void heston_product_kernel(PathRange pr, HestonContract c, typename Product<ANTI>::Contract pc, ReduceWs ws) {
+    const RoundKeys rk = pin_round_keys(pr.key0, pr.key1);
+    double acc[2] = {0.0, 0.0};
+    HestonProductLegs<Product<ANTI>, ANTI> p(c, kZScale);
+    double v_start;
+    const bool skip0 = heston_start(c, v_start);
+    const int32_t last = Product<ANTI>::last(pc, pr.n_steps);
+    const int32_t blocks = (last + 1) >> 1;
+    for_each_path(pr, [&](int64_t, uint32_t g_lo, uint32_t g_hi) {
+        p.start(pc, v_start);
+        for (int32_t b = 0; b < blocks; ++b) {
+            float z[4];
+            raw_normals4_pinned(g_lo, g_hi, static_cast<uint32_t>(b), kTagHeston, rk, z);
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int32_t t = 2 * b + h;
+                if (t < last) p.date(pc, t, static_cast<double>(z[2 * h]), static_cast<double>(z[2 * h + 1]), !(skip0 && t == 0));
+            }
+        }
+        p.payoffs(pc, last, acc);
+    });
+    block_then_grid_reduce<2>(acc, ws);
+}
+
+// Euler on Sobol: heston_qmc_path_kernel's skeleton, dimension assignment, bridge plan and slabs.  The sequential walk stops at the
+// product's last date (the trailing dimensions are not drawn); the bridge fills all n dates of the plan and sweeps to the last.
+// Resources (tools/kernel_meta.sh, gfx950; no scratch, no spills; LDS 64 B, the reduction), VGPRs plain / antithetic:
+//   sequential  autocallable 98 / 106, cliquet 92 / 83       (heston_qmc_path_kernel, extrema: 92 / 100)
+//   bridge      autocallable 127 / 135, cliquet 121 / 115    (heston_qmc_path_kernel, extrema: 115 / 131)
+// The antithetic autocallable bridge (two legs of ln S, v, minimum and redemption) allocates 136 registers, as heston_qmc_path_kernel's
+// antithetic extrema bridge does: three waves per SIMD, above the two the bridge launch holds (olmc.hip: kHestonBridgeBlocksPerCu).
+template <template <bool> class Product, bool BRIDGE, bool ANTI>
+__global__ __launch_bounds__(kBlock) void heston_qmc_product_kernel(QmcRange qr, HestonContract c, typename Product<ANTI>::Contract pc,
+                                                                    const uint32_t* __restrict__ sv, const uint32_t* __restrict__ shift,
+                                                                    QmcBridgePlan plan, double* slabs, ReduceWs ws) {
+    const int lane = static_cast<int>(threadIdx.x) & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) / kWave);
+    const int32_t n = qr.dims;                                               // steps: the tables hold 2 n dimensions
+    HestonProductLegs<Product<ANTI>, ANTI> p(c, 1.0);
+    double v_start;
+    const bool skip0 = heston_start(c, v_start);
+    const int32_t last = Product<ANTI>::last(pc, n);
+    const uint64_t base = qr.first & ~static_cast<uint64_t>(kWave - 1);      // blocks aligned in the absolute index
+    const uint64_t end = qr.first + static_cast<uint64_t>(qr.count);
+    const int64_t n_blocks = static_cast<int64_t>((end - base + kWave - 1) / kWave);
+    const int64_t stride = static_cast<int64_t>(gridDim.x) * kWavesPerBlock;
+    const int64_t slot = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave;
+    double acc[2] = {0.0, 0.0};
+    for (int64_t blk = slot; blk < n_blocks; blk += stride) {
+        const uint64_t k = base + static_cast<uint64_t>(blk) * kWave + lane;
+        const bool live = k >= qr.first && k < end;
+        const QmcLanePoint lp(static_cast<uint32_t>(k));
+        p.start(pc, v_start);
+        auto step = [&](int32_t t, double z1, double z2) { p.date(pc, t, z1, z2, !(skip0 && t == 0)); };
+        if constexpr (BRIDGE) {
+            double* w1 = slabs + static_cast<size_t>(slot) * (2 * static_cast<size_t>(n) * kWave);
+            double* w2 = w1 + static_cast<size_t>(n) * kWave;
+            auto at = [&](int32_t j) { return static_cast<size_t>(j - 1) * kWave + lane; };
+            heston_qmc_bridge_fill(sv, shift, plan, n, lane, lp, live, w1, w2, at);
+            if (live) heston_qmc_bridge_sweep(last, w1, w2, at, step);
+        } else {
+            heston_qmc_normals(sv, shift, last, lane, lp, step);
+        }
+        if (live) p.payoffs(pc, last, acc);
+    }
+    block_then_grid_reduce<2>(acc, ws);
+}
+
+// QE on Philox: heston_qe_surface_kernel's draws -- ONE block per step, counter (path_lo, path_hi, t, kTagHestonQe): (x0, x1) ->
+// box_muller_raw -> (Z_v, Z_s), x2 -> U_v.
+// Resources (tools/kernel_meta.sh, gfx950; no scratch, no spills; LDS 64 B, the reduction), VGPRs plain / antithetic:
+// autocallable 109 / 120, cliquet 101 / 95 (heston_qe_surface_kernel: 92 / 82).
+template <template <bool> class Product, bool ANTI>
+__global__ __launch_bounds__(kBlock) void heston_qe_product_kernel(PathRange pr, HestonQeContract c, typename Product<ANTI>::Contract pc, ReduceWs ws) {
+    const RoundKeys rk = pin_round_keys(pr.key0, pr.key1);
+    double acc[2] = {0.0, 0.0};
+    HestonQeProductLegs<Product<ANTI>, ANTI> p(c, kZScale);
+    const int32_t last = Product<ANTI>::last(pc, pr.n_steps);
+    for_each_path(pr, [&](int64_t, uint32_t g_lo, uint32_t g_hi) {
+        p.start(pc, c.v0);
+        for (int32_t t = 0; t < last; ++t) {
+            const Words4 w = philox4x32_10_pinned(g_lo, g_hi, static_cast<uint32_t>(t), kTagHestonQe, rk);
+            float z_v, z_s;
+            box_muller_raw(w.x0, w.x1, z_v, z_s);
+            const QeWordUniform draw{w.x2};
+            p.hs.template advance<1>(p.hs.moments(p.v[0]), draw, static_cast<double>(z_v), static_cast<double>(z_s), p.ls[0], p.v[0]);
+            if constexpr (ANTI) p.hs.template advance<-1>(p.hs.moments(p.v[1]), draw, static_cast<double>(z_v), static_cast<double>(z_s), p.ls[1], p.v[1]);
+            p.date(pc, t);
+        }
+        p.payoffs(pc, last, acc);
+    });
+    block_then_grid_reduce<2>(acc, ws);
+}
+
+// QE on Sobol, sequential only: heston_qe_qmc_draws (the inverse normal of the variance dimension only where a leg is quadratic) to the
+// product's last date, the aligned blocks of heston_qe_qmc_surface_kernel.
+// Resources (tools/kernel_meta.sh, gfx950; no scratch, no spills; LDS 64 B, the reduction), VGPRs plain / antithetic:
+// autocallable 106 / 121, cliquet 98 / 94 (heston_qe_qmc_surface_kernel: 94 / 87).
+template <template <bool> class Product, bool ANTI>
+__global__ __launch_bounds__(kBlock) void heston_qe_qmc_product_kernel(QmcRange qr, HestonQeContract c, typename Product<ANTI>::Contract pc,
+                                                                       const uint32_t* __restrict__ sv, const uint32_t* __restrict__ shift,
+                                                                       ReduceWs ws) {
+    const int lane = static_cast<int>(threadIdx.x) & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) / kWave);
+    HestonQeProductLegs<Product<ANTI>, ANTI> p(c, 1.0);
+    const int32_t last = Product<ANTI>::last(pc, qr.dims);
+    const uint64_t base = qr.first & ~static_cast<uint64_t>(kWave - 1);      // blocks aligned in the absolute index
+    const uint64_t end = qr.first + static_cast<uint64_t>(qr.count);
+    const int64_t n_blocks = static_cast<int64_t>((end - base + kWave - 1) / kWave);
+    const int64_t stride = static_cast<int64_t>(gridDim.x) * kWavesPerBlock;
+    double acc[2] = {0.0, 0.0};
+    for (int64_t blk = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave; blk < n_blocks; blk += stride) {
+        const uint64_t k = base + static_cast<uint64_t>(blk) * kWave + lane;
+        const bool live = k >= qr.first && k < end;
+        const QmcLanePoint lp(static_cast<uint32_t>(k));
+        p.start(pc, c.v0);
+        heston_qe_qmc_draws(sv, shift, last, lane, lp, [&](int32_t t, double u_v, double z_s) {
+            heston_qe_qmc_step<ANTI>(p.hs, u_v, z_s, p.ls, p.v);
+            p.date(pc, t);
+        });
+        if (live) p.payoffs(pc, last, acc);
+    }
+    block_then_grid_reduce<2>(acc, ws);
+}
+
 // ------------------------------------------------------- validation taps ----
 __global__ void philox_words_kernel(uint64_t first, int64_t n_paths, int32_t block0, int32_t n_blocks,
                                     uint32_t tag, uint32_t k0, uint32_t k1, uint32_t* __restrict__ out) {

@@ -320,6 +320,66 @@ class HestonPricer:
         return self._price_path_payoff(payoff, 0.0, S, K, T, r, q, option_type, n_paths, n_steps, seed, antithetic, return_error, method,
                                        path_construction)
 
+    def _price_structured(self, philox, sobol, contract, S, T, r, q, n_paths, n_steps, seed, antithetic, return_error, method,
+                          path_construction, scheme):
+        """One launch of the structured-product kernels (include/olmc.h "structured products under Heston") under price_monte_carlo's
+        conventions: `philox` / `sobol` are the product's two bindings, `contract` its arguments between the model and the counts."""
+        qe = _check_scheme(scheme, method, path_construction)
+        model = (self.kappa, self.theta, self.sigma_v, self.rho, self.v0)
+        qmc = _qmc_tables(method, path_construction, n_paths, n_steps, seed)
+        if qmc is not None:
+            sv, shift, bridge = qmc
+            st = sobol(S, T, r, q, *model, *contract, n_paths, sv, shift, bridge, antithetic, qe=qe)
+        else:
+            s = seed if seed is not None else int(np.random.default_rng().integers(0, 2**31))
+            st = philox(S, T, r, q, *model, *contract, n_paths, n_steps, s, antithetic, qe=qe)
+        return (np.float64(st.price), float(st.std_error)) if return_error else np.float64(st.price)
+
+    def price_autocallable(self, S: float, T: float, r: float, q: float = 0.0, autocall_barrier: float = 1.0, coupon_barrier: float = 0.8,
+                           coupon_rate: float = 0.10, ki_barrier: float = 0.6, observation_freq: int = 21, n_paths: int = 100000,
+                           n_steps: int = 252, seed: Optional[int] = None, antithetic: bool = False, return_error: bool = False, *,
+                           method: Literal["pseudo", "qmc"] = "pseudo", path_construction: Literal["bridge", "sequential"] = "bridge",
+                           scheme: Literal["euler", "qe"] = "euler"):
+        """The autocallable note under this model, a fraction of notional: what AutocallableOption.price (exotic_options.py:438-491) computes
+        from the spot matrix of simulate_paths(S, T, r, q, n_paths, n_steps, seed, method=..., path_construction=..., scheme=...), in one
+        launch that stores no path.  The levels are relative to S; the observation dates are observation_freq, 2 observation_freq, ...
+        <= n_steps; a payoff is discounted at its own date, so the price is the plain mean; the knock-in minimum includes date 0.
+        observation_freq > n_steps leaves no observation date and every path runs to maturity: it is priced, as AutocallableOption prices
+        it, with one observation on the last step at a level no path reaches.  The kernel decides in log space, ln(S_t / S) against
+        ln(level): a path within rounding (about 1e-16 relative) of a level can decide differently from the matrix route.
+        seed=None, antithetic, return_error, method, path_construction, scheme and the standard error's meaning as price_monte_carlo;
+        scheme="qe" with method="qmc" takes path_construction="sequential" only.  A structured product's own grid (12 monthly resets, 4
+        quarterly observations) is where "qe" matters: Euler on such a grid is biased by tens of standard errors (DESIGN.md "Structured
+        products under Heston").  Refused (ValueError, before the device is touched): what price_monte_carlo refuses, and
+        observation_freq < 1."""
+        if n_paths < 1 or n_steps < 1:
+            raise ValueError("n_paths and n_steps must be >= 1")
+        if observation_freq < 1:
+            raise ValueError("observation_freq must be >= 1")
+        if observation_freq > n_steps:                  # no observation date: nothing redeems early (exotic_options.py:442, 448)
+            observation_freq, autocall_barrier = n_steps, float("inf")
+        contract = (autocall_barrier, coupon_barrier, coupon_rate, ki_barrier, observation_freq)
+        return self._price_structured(_hip.heston_autocallable, _hip.heston_autocallable_qmc, contract, S, T, r, q, n_paths, n_steps, seed,
+                                      antithetic, return_error, method, path_construction, scheme)
+
+    def price_cliquet(self, S: float, T: float, r: float, q: float = 0.0, local_cap: float = 0.05, local_floor: float = -0.05,
+                      global_cap: float = 0.30, global_floor: float = 0.0, n_periods: int = 12, n_paths: int = 100000, n_steps: int = 252,
+                      seed: Optional[int] = None, antithetic: bool = False, return_error: bool = False, *,
+                      method: Literal["pseudo", "qmc"] = "pseudo", path_construction: Literal["bridge", "sequential"] = "bridge",
+                      scheme: Literal["euler", "qe"] = "euler"):
+        """The cliquet under this model: exp(-r T) mean(max(clip(sum of clip(period return, local_floor, local_cap), global_floor,
+        global_cap), 0) S) over n_periods periods of n_steps // n_periods steps from date 0 (trailing dates never enter a period) -- what
+        CliquetOption.price (exotic_options.py:526-554) computes from simulate_paths' spot matrix for the same seed, method,
+        path_construction and scheme, in one launch that stores no path.  The rest as price_autocallable; also refused: n_periods outside
+        [1, n_steps]."""
+        if n_paths < 1 or n_steps < 1:
+            raise ValueError("n_paths and n_steps must be >= 1")
+        if n_periods < 1 or n_periods > n_steps:
+            raise ValueError("n_periods must be in [1, n_steps]")
+        contract = (local_cap, local_floor, global_cap, global_floor, n_periods)
+        return self._price_structured(_hip.heston_cliquet, _hip.heston_cliquet_qmc, contract, S, T, r, q, n_paths, n_steps, seed, antithetic,
+                                      return_error, method, path_construction, scheme)
+
 
 class HestonAdapter:
     """unified_greeks.py:74-104: sigma -> v0 = sigma^2, prices with the semi-analytic formula."""

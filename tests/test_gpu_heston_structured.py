@@ -1,0 +1,479 @@
+"""The autocallable and the cliquet under Heston on the device (include/olmc.h "structured products under Heston";
+HestonPricer.price_autocallable / price_cliquet), Euler and QE, Philox and Sobol.
+
+The payoff of a path is what oracle/numpy_reference.py's autocallable_from_paths / cliquet_from_paths compute from its row of
+simulate_paths' spot matrix.  The bars: TIE (rel 1e-10, abs 1e-12) for sums against per-path payoffs, rel 1e-12 for shards, combined
+standard errors at workload level.  The kernel decides in log space, so every tie first asserts that no path sits within 1e-9 relative
+of a level (observed spots against the autocall level, the terminal spot against the coupon level and S, the path minimum against the
+knock-in level) and, against the QE restatement, that no step's psi sits within 1e-9 of 1.5; sums need every path, so a seed that breaks
+a precondition is to be changed, not the rule.
+
+1. Philox, both schemes, leg 0: the device's own simulate_paths matrix.
+2. Philox, the mirror leg: Euler on recovered normals (CALM), QE on the oracle's words and the Box-Muller tap.
+3. Sobol: Euler on both constructions against hpo.sobol_spots, QE sequential against qe.sobol_draws + qe.paths; both legs.
+4. Agreement of entry points.
+5. Shards, determinism, a path_offset beyond 2^32, the existing entry points' bits.
+6. Workload level against tests/golden/heston_structured.json, with power, and the Black-Scholes limit.
+7. Refusals, NaN and v0 < 0 at the C ABI.
+"""
+import functools
+import json
+import math
+import os
+import warnings
+
+import numpy as np
+import pytest
+
+import optionslab_amd as ol
+from optionslab_amd import _hip
+from optionslab_amd.exceptions import AccelerationError
+from optionslab_amd.monte_carlo import sobol_tables
+from oracle import numpy_reference as orc
+from oracle import philox_oracle
+from tests import heston_path_oracle as hpo
+from tests import heston_qe_reference as qe
+
+pytestmark = pytest.mark.gpu
+
+TIE = dict(rel=1e-10, abs=1e-12)
+S, T, R, Q = 100.0, 1.0, 0.05, 0.01                       # hpo's S, T, R, Q
+AUTOCALL = (1.0, 0.9, 0.10, 0.8)                          # autocall level, coupon level, coupon rate, knock-in level
+CLIQUET = (0.05, -0.05, 0.30, 0.0)                        # local cap, local floor, global cap, global floor
+# (n_steps, observation_freq, n_periods): (13, 4, 4) and (64, 21, 12) leave a trailing step and a non-dividing period, (33, 11, 3)
+# crosses the 64-dimension fold
+SHAPES = ((1, 1, 1), (2, 1, 2), (12, 3, 12), (12, 3, 4), (13, 4, 4), (64, 21, 12), (33, 11, 3))
+COUNTS = (1, 63, 65, 1000, 4097)
+SHAPE_IDS = [f"n{n}-f{f}-p{p}" for n, f, p in SHAPES]
+EULER_MODELS = (hpo.USUAL, hpo.FELLER_VIOLATING)
+QE_MODELS = (qe.FELLER_VIOLATED, qe.STEEP, qe.USUAL)
+
+
+def pricer(model):
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", UserWarning)                               # Feller
+        return ol.HestonPricer(*model)
+
+
+def autocall_payoffs(spot, f, contract=AUTOCALL):
+    """Per-path payoffs, each discounted at its own date."""
+    return orc.autocallable_from_paths(spot, S, T, R, f, contract[0], contract[1], contract[2], contract[3], return_payoffs=True)[1]
+
+
+def cliquet_payoffs(spot, periods, contract=CLIQUET):
+    """Per-path payoffs, undiscounted."""
+    return orc.cliquet_from_paths(spot, S, T, R, periods, *contract, return_payoffs=True)[1]
+
+
+def assert_clear_of_the_levels(spot, f, label, contract=AUTOCALL):
+    n = spot.shape[1] - 1
+    rel = spot / S
+    obs = list(range(f, n + 1, f))
+    gaps = dict(autocall=float(np.min(np.abs(rel[:, obs] / contract[0] - 1.0))) if obs else math.inf,
+                coupon=float(np.min(np.abs(rel[:, -1] / contract[1] - 1.0))), spot=float(np.min(np.abs(rel[:, -1] - 1.0))),
+                knock_in=float(np.min(np.abs(np.min(rel, axis=1) / contract[3] - 1.0))))
+    print(label, "closest approaches", gaps)
+    assert min(gaps.values()) > 1e-9, (label, gaps)
+
+
+def assert_clear_of_the_branch(psi, label):
+    gap = float(np.min(np.abs(psi - qe.PSI_C))) if psi.size else math.inf
+    assert gap > 1e-9, (label, gap)
+
+
+def branch_mix(spot, f):
+    """Fractions (redeemed early, to maturity above the coupon level, knock-in loss) of the default autocallable."""
+    n = spot.shape[1] - 1
+    rel = spot / S
+    obs = list(range(f, n + 1, f))
+    early = np.any(rel[:, obs] >= AUTOCALL[0], axis=1)
+    loss = ~early & (np.min(rel, axis=1) <= AUTOCALL[3]) & (rel[:, -1] < 1.0)
+    coupon = ~early & ~loss & (rel[:, -1] >= AUTOCALL[1])
+    return float(early.mean()), float(coupon.mean()), float(loss.mean())
+
+
+def check_sums(st, x, label):
+    want, want2 = float(np.sum(x)), float(np.sum(x * x))
+    print(label, "sum", st.sum, "oracle", want, "sumsq", st.sumsq, "oracle", want2)
+    assert st.n == len(x), label
+    assert st.sum == pytest.approx(want, **TIE), label
+    assert st.sumsq == pytest.approx(want2, **TIE), label
+
+
+def philox_autocall(model, f, N, n, seed, qe_scheme, antithetic=False, path_offset=0, contract=AUTOCALL):
+    return _hip.heston_autocallable(S, T, R, Q, *model, *contract, f, N, n, seed, antithetic, path_offset, qe=qe_scheme)
+
+
+def philox_cliquet(model, periods, N, n, seed, qe_scheme, antithetic=False, path_offset=0, contract=CLIQUET):
+    return _hip.heston_cliquet(S, T, R, Q, *model, *contract, periods, N, n, seed, antithetic, path_offset, qe=qe_scheme)
+
+
+@functools.lru_cache(maxsize=None)
+def tables(n, seed, count):
+    return sobol_tables(2 * n, seed, count)
+
+
+def sobol_autocall(model, f, N, n, seed, construction, qe_scheme, antithetic=False, point_offset=0):
+    sv, shift = tables(n, seed, point_offset + N)
+    return _hip.heston_autocallable_qmc(S, T, R, Q, *model, *AUTOCALL, f, N, sv, shift, construction == "bridge", antithetic, point_offset,
+                                        qe=qe_scheme)
+
+
+def sobol_cliquet(model, periods, N, n, seed, construction, qe_scheme, antithetic=False, point_offset=0):
+    sv, shift = tables(n, seed, point_offset + N)
+    return _hip.heston_cliquet_qmc(S, T, R, Q, *model, *CLIQUET, periods, N, sv, shift, construction == "bridge", antithetic, point_offset,
+                                   qe=qe_scheme)
+
+
+def check_both_products(label, spots, f, periods, autocall_stats, cliquet_stats):
+    """spots: the legs' matrices in the order the sums take them."""
+    for leg, spot in enumerate(spots):
+        assert_clear_of_the_levels(spot, f, (label, "leg", leg))
+    check_sums(autocall_stats, np.concatenate([autocall_payoffs(spot, f) for spot in spots]), (label, "autocallable"))
+    check_sums(cliquet_stats, np.concatenate([cliquet_payoffs(spot, periods) for spot in spots]), (label, "cliquet"))
+
+
+# ------------------------------------------------------------------------------ 1. Philox: tie to the device's own matrix ----
+@pytest.mark.parametrize("scheme", ("euler", "qe"))
+@pytest.mark.parametrize("n,f,periods", SHAPES, ids=SHAPE_IDS)
+def test_philox_sums_match_the_payoffs_of_the_devices_own_path_matrix(n, f, periods, scheme):
+    is_qe = scheme == "qe"
+    for mi, model in enumerate((qe.FELLER_VIOLATED, qe.STEEP) if is_qe else EULER_MODELS):
+        p = pricer(model)
+        for N in COUNTS:
+            seed = 1000 * n + 10 * N + mi
+            spot, _var = p.simulate_paths(S, T, R, Q, N, n, seed, scheme=scheme)
+            label = (scheme, mi, n, f, periods, N, seed)
+            check_both_products(label, [spot], f, periods, philox_autocall(model, f, N, n, seed, is_qe),
+                                philox_cliquet(model, periods, N, n, seed, is_qe))
+            if N == 1000 and n >= 12:
+                early, coupon, loss = branch_mix(spot, f)
+                print(label, "early", early, "coupon", coupon, "loss", loss)
+                assert early > 0.3 and coupon > 0.01 and loss > 0.01                # each branch of the payoff is exercised
+                # the public methods: the discounted mean and its naive standard error
+                x = autocall_payoffs(spot, f)
+                price, error = p.price_autocallable(S, T, R, Q, *AUTOCALL, f, N, n, seed, False, True, scheme=scheme)
+                assert price == pytest.approx(float(np.mean(x)), rel=1e-10) and error == pytest.approx(float(np.std(x)) / math.sqrt(N), rel=1e-6)
+                x = cliquet_payoffs(spot, periods)
+                price, error = p.price_cliquet(S, T, R, Q, *CLIQUET, periods, N, n, seed, False, True, scheme=scheme)
+                disc = math.exp(-R * T)
+                assert price == pytest.approx(disc * float(np.mean(x)), rel=1e-10)
+                assert error == pytest.approx(disc * float(np.std(x)) / math.sqrt(N), rel=1e-6)
+                assert isinstance(price, np.float64) and isinstance(error, float)
+
+
+def test_an_observation_frequency_beyond_the_steps_prices_every_path_at_maturity():
+    """observation_freq > n_steps: the reference's list of observation dates is empty."""
+    N, n, seed = 1000, 12, 77
+    for scheme, model in (("euler", hpo.FELLER_VIOLATING), ("qe", qe.FELLER_VIOLATED)):
+        p = pricer(model)
+        spot, _var = p.simulate_paths(S, T, R, Q, N, n, seed, scheme=scheme)
+        assert_clear_of_the_levels(spot, 13, (scheme, "no observation"))
+        x = autocall_payoffs(spot, 13)
+        assert len(set(np.round(x / math.exp(-R * T), 12))) > 2                      # 1, 1 + coupon, and the losses
+        price = p.price_autocallable(S, T, R, Q, *AUTOCALL, 13, N, n, seed, scheme=scheme)
+        assert price == pytest.approx(float(np.mean(x)), rel=1e-10)
+
+
+# --------------------------------------------------------------------------------------------- 2. Philox: the mirror leg ----
+@pytest.mark.parametrize("n,f,periods", SHAPES, ids=SHAPE_IDS)
+def test_the_euler_mirror_leg_is_the_recursion_on_the_negated_normals(n, f, periods):
+    model = hpo.CALM
+    for N in COUNTS:
+        seed = 17 + n + N
+        spot, var = pricer(model).simulate_paths(S, T, R, Q, N, n, seed)
+        # a step's normals can be solved for when the variance it starts from is positive.  The variance of the LAST date starts no step:
+        # truncated there (one step of dt = 1 does that to a path in 700), only that step's Z2' is lost, which no spot reads.  The mirror's
+        # own variance may touch 0 anywhere: the literal recursion truncates as the device does.
+        assert float(var[:, :-1].min()) > 0.0
+        z1, z2p = hpo.recovered_normals(spot, var, model)
+        again, _ = hpo.literal_recursion(z1, z2p, model, n)
+        assert float(np.max(np.abs(again / spot - 1.0))) < 1e-12                    # the recovery is sound
+        mirror, _mirror_var = hpo.literal_recursion(-z1, -z2p, model, n)
+        check_both_products(("euler mirror", n, f, periods, N), [spot, mirror], f, periods,
+                            philox_autocall(model, f, N, n, seed, False, antithetic=True),
+                            philox_cliquet(model, periods, N, n, seed, False, antithetic=True))
+
+
+@functools.lru_cache(maxsize=None)
+def qe_philox_draws(n, count, seed, path_offset):
+    from tools.probe import binding as probe
+
+    words = philox_oracle.philox_words(seed, path_offset, count, 0, n, qe.STREAM_HESTON_QE)
+    return qe.philox_draws(words, probe.box_muller_probe)
+
+
+def qe_legs(model, n, draws, label):
+    """[leg 0, mirror] of the restatement, the branch precondition asserted on both."""
+    legs = []
+    for mirror in (False, True):
+        spot, _var, _quadratic, psi = qe.paths(S, model, R, Q, T, n, *draws, mirror=mirror)
+        assert_clear_of_the_branch(psi, (label, "mirror" if mirror else "leg 0"))
+        legs.append(spot)
+    return legs
+
+
+@pytest.mark.parametrize("n,f,periods", SHAPES, ids=SHAPE_IDS)
+def test_the_qe_legs_tie_to_the_restatement_on_the_oracles_words(n, f, periods):
+    seed = 3
+    for mi, model in enumerate((qe.FELLER_VIOLATED, qe.STEEP)):
+        for N in COUNTS:
+            legs = qe_legs(model, n, qe_philox_draws(n, N, seed, 0), ("qe philox", mi, n, N))
+            label = ("qe philox", mi, n, f, periods, N)
+            check_both_products(label, legs, f, periods, philox_autocall(model, f, N, n, seed, True, antithetic=True),
+                                philox_cliquet(model, periods, N, n, seed, True, antithetic=True))
+            check_both_products(label, legs[:1], f, periods, philox_autocall(model, f, N, n, seed, True),
+                                philox_cliquet(model, periods, N, n, seed, True))
+
+
+# ----------------------------------------------------------------------------------- 3. Sobol: per-path tie to the oracle ----
+EULER_SOBOL_CASES = [(n, f, p, N) for n, f, p in SHAPES for N in COUNTS]
+EULER_SOBOL_IDS = [f"n{c[0]}-f{c[1]}-p{c[2]}-N{c[3]}" for c in EULER_SOBOL_CASES]
+
+
+def check_euler_sobol(n, f, periods, N, model, seed, constructions):
+    spots = hpo.sobol_spots(n, N, seed, model, constructions)
+    for construction in constructions:
+        label = ("euler sobol", construction, n, f, periods, N)
+        legs = [spots[(construction, 0)], spots[(construction, 1)]]
+        check_both_products(label, legs[:1], f, periods, sobol_autocall(model, f, N, n, seed, construction, False),
+                            sobol_cliquet(model, periods, N, n, seed, construction, False))
+        check_both_products(label, legs, f, periods, sobol_autocall(model, f, N, n, seed, construction, False, antithetic=True),
+                            sobol_cliquet(model, periods, N, n, seed, construction, False, antithetic=True))
+    return spots
+
+
+@pytest.mark.parametrize("n,f,periods,N", EULER_SOBOL_CASES, ids=EULER_SOBOL_IDS)
+def test_euler_sobol_sums_match_the_numpy_oracle(n, f, periods, N):
+    for model in EULER_MODELS:
+        check_euler_sobol(n, f, periods, N, model, 3, ("bridge", "sequential"))
+
+
+def test_euler_bridge_at_252_steps_matches_the_numpy_oracle():
+    spots = check_euler_sobol(252, 21, 12, 1000, hpo.USUAL, 3, ("bridge",))
+    early, coupon, loss = branch_mix(spots[("bridge", 0)], 21)
+    assert early > 0.3 and coupon > 0.0 and loss > 0.0                            # 87 %, 1.2 %, 11 % by the oracle
+
+
+@pytest.mark.parametrize("seed", (0, 5))
+@pytest.mark.parametrize("n,f,periods", SHAPES, ids=SHAPE_IDS)
+def test_qe_sobol_sums_match_the_restatement_on_scipys_points(n, f, periods, seed):
+    for mi, model in enumerate(QE_MODELS):
+        for N in COUNTS:
+            legs = qe_legs(model, n, qe.sobol_draws(n, N, seed), ("qe sobol", mi, n, N, seed))
+            label = ("qe sobol", mi, n, f, periods, N, seed)
+            check_both_products(label, legs[:1], f, periods, sobol_autocall(model, f, N, n, seed, "sequential", True),
+                                sobol_cliquet(model, periods, N, n, seed, "sequential", True))
+            check_both_products(label, legs, f, periods, sobol_autocall(model, f, N, n, seed, "sequential", True, antithetic=True),
+                                sobol_cliquet(model, periods, N, n, seed, "sequential", True, antithetic=True))
+
+
+# ------------------------------------------------------------------------------------------ 4. agreement of entry points ----
+@pytest.mark.parametrize("kw", (dict(scheme="euler"), dict(scheme="qe"), dict(scheme="euler", method="qmc"),
+                                dict(scheme="qe", method="qmc", path_construction="sequential")), ids=lambda kw: "-".join(kw.values()))
+def test_an_uncapped_one_period_cliquet_is_the_at_the_money_call(kw):
+    inf = math.inf
+    for model in (hpo.FELLER_VIOLATING, qe.STEEP):
+        p = pricer(model)
+        for antithetic in (False, True):
+            for N, n in ((1000, 12), (4097, 13)):
+                call = p.price_monte_carlo(S, S, T, R, Q, "call", N, n, 11, antithetic, True, **kw)
+                cliquet = p.price_cliquet(S, T, R, Q, inf, -1.0, inf, 0.0, 1, N, n, 11, antithetic, True, **kw)
+                print(kw, model, antithetic, N, n, call, cliquet)
+                assert cliquet[0] == pytest.approx(call[0], rel=1e-10) and cliquet[1] == pytest.approx(call[1], rel=1e-6)
+                assert call[0] > 1.0
+
+
+@pytest.mark.parametrize("kw", (dict(scheme="euler"), dict(scheme="qe"), dict(scheme="euler", method="qmc"),
+                                dict(scheme="qe", method="qmc", path_construction="sequential")), ids=lambda kw: "-".join(kw.values()))
+def test_an_autocallable_that_can_neither_redeem_nor_lose_nor_pay_a_coupon_is_the_discount_factor(kw):
+    """No observation date, coupon 0, knock-in level 0: every path pays 1 at maturity.  64 paths are one wave: its butterfly sums equal
+    values pairwise, so every partial sum is a power of two times exp(-r T) and the mean is exact."""
+    p = pricer(qe.FELLER_VIOLATED)
+    price, error = p.price_autocallable(S, T, R, Q, 1.0, 0.9, 0.0, 0.0, 13, 64, 12, 5, False, True, **kw)
+    assert price == math.exp(-R * T) and error == 0.0
+    price = p.price_autocallable(S, T, R, Q, 1.0, 0.9, 0.0, 0.0, 13, 1000, 12, 5, True, **kw)
+    assert price == pytest.approx(math.exp(-R * T), rel=1e-14)
+
+
+# ---------------------------------------------------------------------------------------------- 5. shards and invariants ----
+def stats_calls(N, n, f, periods, seed, antithetic):
+    """{label: call(count, offset)} over every product, scheme and method."""
+    calls = {}
+    for is_qe, model in ((False, hpo.FELLER_VIOLATING), (True, qe.FELLER_VIOLATED)):
+        calls[("autocallable", "philox", is_qe)] = lambda c, o, m=model, s=is_qe: philox_autocall(m, f, c, n, seed, s, antithetic, o)
+        calls[("cliquet", "philox", is_qe)] = lambda c, o, m=model, s=is_qe: philox_cliquet(m, periods, c, n, seed, s, antithetic, o)
+        for construction in ("sequential",) if is_qe else ("sequential", "bridge"):
+            sv, shift = sobol_tables(2 * n, seed, N)
+            calls[("autocallable", construction, is_qe)] = lambda c, o, m=model, s=is_qe, b=construction == "bridge", sv=sv, shift=shift: \
+                _hip.heston_autocallable_qmc(S, T, R, Q, *m, *AUTOCALL, f, c, sv, shift, b, antithetic, o, qe=s)
+            calls[("cliquet", construction, is_qe)] = lambda c, o, m=model, s=is_qe, b=construction == "bridge", sv=sv, shift=shift: \
+                _hip.heston_cliquet_qmc(S, T, R, Q, *m, *CLIQUET, periods, c, sv, shift, b, antithetic, o, qe=s)
+    return calls
+
+
+@pytest.mark.parametrize("antithetic", (False, True))
+def test_shards_of_one_stream_or_sequence_add_up(antithetic):
+    N, a, n, f, periods, seed = 4133, 1000, 13, 4, 4, 9                              # a is no multiple of 64
+    for label, call in stats_calls(N, n, f, periods, seed, antithetic).items():
+        whole, lo, hi = call(N, 0), call(a, 0), call(N - a, a)
+        assert whole.n == lo.n + hi.n == N * (2 if antithetic else 1), label
+        assert whole.sum == pytest.approx(lo.sum + hi.sum, rel=1e-12), label
+        assert whole.sumsq == pytest.approx(lo.sumsq + hi.sumsq, rel=1e-12), label
+
+
+def test_equal_arguments_give_equal_bits_and_the_existing_entry_points_give_the_bits_they_gave():
+    N, n, f, periods = 4133, 13, 4, 4
+    p = pricer(qe.FELLER_VIOLATED)
+    before = (p.price_monte_carlo(S, S, T, R, Q, "call", N, n, 11, True, True), p.price_monte_carlo(S, S, T, R, Q, "put", N, n, 11, True, True, scheme="qe"),
+              p.price_lookback(S, S, T, R, Q, "call", "floating", N, n, 11, method="qmc"))
+    first = {label: call(N, 0) for label, call in stats_calls(N, n, f, periods, 11, True).items()}
+    other = {label: call(N, 0) for label, call in stats_calls(N, n, f, periods, 12, True).items()}
+    stats_calls(N, 32, 8, 8, 12, False)[("autocallable", "bridge", False)](N, 0)     # other tables, another plan in between
+    again = {label: call(N, 0) for label, call in stats_calls(N, n, f, periods, 11, True).items()}
+    for label in first:
+        assert (first[label].sum, first[label].sumsq, first[label].price, first[label].std_error) == \
+               (again[label].sum, again[label].sumsq, again[label].price, again[label].std_error), label
+        assert first[label].sum != other[label].sum, label
+    after = (p.price_monte_carlo(S, S, T, R, Q, "call", N, n, 11, True, True), p.price_monte_carlo(S, S, T, R, Q, "put", N, n, 11, True, True, scheme="qe"),
+             p.price_lookback(S, S, T, R, Q, "call", "floating", N, n, 11, method="qmc"))
+    assert before == after
+
+
+def test_paths_beyond_2_to_the_32_tie_to_the_restatement():
+    n, f, periods, N, seed, offset = 12, 3, 12, 1000, 3, (1 << 32) + 5
+    for mi, model in enumerate((qe.FELLER_VIOLATED, qe.STEEP)):
+        legs = qe_legs(model, n, qe_philox_draws(n, N, seed, offset), ("offset", mi))
+        assert not np.array_equal(legs[0], qe_legs(model, n, qe_philox_draws(n, N, seed, 0), ("offset 0", mi))[0])
+        check_both_products(("offset 2^32 + 5", mi), legs, f, periods, philox_autocall(model, f, N, n, seed, True, True, offset),
+                            philox_cliquet(model, periods, N, n, seed, True, True, offset))
+    # Euler: shards on both sides of 2^32 add up to the launch across it
+    model, lo = hpo.USUAL, (1 << 32) - 300
+    for call in (lambda c, o: philox_autocall(model, f, c, n, seed, False, True, o), lambda c, o: philox_cliquet(model, periods, c, n, seed, False, True, o)):
+        whole, a, b = call(N, lo), call(300, lo), call(N - 300, 1 << 32)
+        assert whole.sum == pytest.approx(a.sum + b.sum, rel=1e-12) and whole.sumsq == pytest.approx(a.sumsq + b.sumsq, rel=1e-12)
+        assert b.sum != call(N - 300, 0).sum                                        # the high word of the path index is read
+
+
+# ------------------------------------------------------------------------------------------------------ 6. workload level ----
+WORKLOAD_N, WORKLOAD_STEPS, WORKLOAD_SEED = 1 << 18, 12, 42      # the seed was fixed before the first run
+
+
+@functools.lru_cache(maxsize=None)
+def golden():
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "heston_structured.json")) as f:
+        doc = json.load(f)
+    assert doc["inputs"]["n_steps"] == WORKLOAD_STEPS and (doc["inputs"]["S"], doc["inputs"]["T"], doc["inputs"]["r"], doc["inputs"]["q"]) == (S, T, R, Q)
+    return doc
+
+
+def device_price(model, payoff, scheme, doc):
+    p = pricer(model)
+    if payoff == "cliquet":
+        c = doc["cliquet"]
+        return p.price_cliquet(S, T, R, Q, c["local_cap"], c["local_floor"], c["global_cap"], c["global_floor"], c["n_periods"], WORKLOAD_N,
+                               WORKLOAD_STEPS, WORKLOAD_SEED, False, True, scheme=scheme)
+    a = doc["autocallable"]
+    return p.price_autocallable(S, T, R, Q, a["autocall_barrier"], a["coupon_barrier"], a["coupon_rate"], a["ki_barrier"], a["observation_freq"],
+                                WORKLOAD_N, WORKLOAD_STEPS, WORKLOAD_SEED, False, True, scheme=scheme)
+
+
+def test_prices_agree_with_the_golden_values_at_workload_level():
+    doc = golden()
+    assert len(doc["prices"]) == 6
+    for entry in doc["prices"]:
+        model = tuple(doc["models"][entry["model"]])
+        price, error = device_price(model, entry["payoff"], entry["scheme"], doc)
+        combined = math.hypot(error, entry["std_error"])
+        print(entry, "device", price, error, "deviation / combined standard error", (price - entry["price"]) / combined)
+        assert abs(price - entry["price"]) <= 4.0 * combined, entry
+
+
+def test_euler_on_the_products_own_grid_is_far_from_qe_where_feller_fails():
+    """The power of the test above: the device's Euler cliquet on 12 steps against the QE golden.  NumPy prototype at 2^19 paths: 60 and 127
+    combined standard errors under FELLER_VIOLATED and STEEP, hence about 42 and 90 at 2^18."""
+    doc = golden()
+    for entry in doc["prices"]:
+        if entry["scheme"] == "qe" and entry["payoff"] == "cliquet":
+            model = tuple(doc["models"][entry["model"]])
+            price, error = device_price(model, "cliquet", "euler", doc)
+            deviation = (price - entry["price"]) / math.hypot(error, entry["std_error"])
+            print(entry["model"], "euler", price, "qe golden", entry["price"], "deviation / combined standard error", deviation)
+            assert abs(deviation) > 10.0
+
+
+@pytest.mark.parametrize("scheme", ("euler", "qe"))
+def test_a_vanishing_vol_of_vol_agrees_with_the_flat_vol_kernels(scheme):
+    """sigma_v = 1e-4, v0 = theta = 0.04: the variance stays at 0.04 and both schemes price what olmc_autocallable / olmc_cliquet price at
+    sigma = 0.2 (independent streams, equal N: 4 combined standard errors).  kappa = 0.1 keeps QE's O((kappa dt)^2) factor on the
+    spot's share of the variance noise (tests/test_heston_qe_cpu.py, the Black-Scholes limit) far below a standard error."""
+    model, N, n, seed = (0.1, 0.04, 1e-4, -0.7, 0.04), WORKLOAD_N, WORKLOAD_STEPS, WORKLOAD_SEED
+    p = pricer(model)
+    got = p.price_autocallable(S, T, R, Q, *AUTOCALL, 3, N, n, seed, False, True, scheme=scheme)
+    flat = _hip.autocallable(S, T, R, 0.2, Q, *AUTOCALL, 3, N, n, seed + 1)
+    print(scheme, "autocallable", got, flat.price, flat.std_error)
+    assert abs(got[0] - flat.price) <= 4.0 * math.hypot(got[1], flat.std_error)
+    got = p.price_cliquet(S, T, R, Q, *CLIQUET, 12, N, n, seed, False, True, scheme=scheme)
+    flat = _hip.cliquet(S, T, R, 0.2, Q, *CLIQUET, 12, N, n, seed + 1)
+    print(scheme, "cliquet", got, flat.price, flat.std_error)
+    assert abs(got[0] - flat.price) <= 4.0 * math.hypot(got[1], flat.std_error)
+    assert flat.std_error > 0.0 and got[1] == pytest.approx(flat.std_error, rel=0.05)
+
+
+# ----------------------------------------------------------------------------------------- 7. refusals, NaN and v0 < 0 ----
+def test_refusals_at_the_c_abi():
+    N, n = 128, 12
+    sv, shift = sobol_tables(2 * n, 1, N)
+    good = qe.USUAL
+    philox = (lambda m, count=3, **kw: _hip.heston_autocallable(S, T, R, Q, *m, *AUTOCALL, count, N, n, 1, **kw),
+              lambda m, count=3, **kw: _hip.heston_cliquet(S, T, R, Q, *m, *CLIQUET, count, N, n, 1, **kw))
+    sobol = (lambda m, count=3, **kw: _hip.heston_autocallable_qmc(S, T, R, Q, *m, *AUTOCALL, count, N, sv, shift, False, **kw),
+             lambda m, count=3, **kw: _hip.heston_cliquet_qmc(S, T, R, Q, *m, *CLIQUET, count, N, sv, shift, False, **kw))
+    bad_models = ((0.0, *good[1:]), (good[0], 0.0, *good[2:]), (*good[:2], -0.3, *good[3:]), (*good[:4], -0.01))
+    for call in philox + sobol:
+        for model in bad_models:
+            with pytest.raises(AccelerationError, match="for the QE scheme"):
+                call(model, qe=True)
+        for is_qe in (False, True):
+            with pytest.raises(AccelerationError, match="rho must be in"):
+                call((*good[:3], 1.01, good[4]), qe=is_qe)
+            for count in (0, 13):
+                with pytest.raises(AccelerationError, match="observation_freq|n_periods"):
+                    call(good, count, qe=is_qe)
+            assert math.isfinite(call(good, 12, qe=is_qe).price) and math.isfinite(call(good, 1, qe=is_qe).price)
+    with pytest.raises(AccelerationError, match="OLMC_QMC_SEQUENTIAL only"):
+        _hip.heston_autocallable_qmc(S, T, R, Q, *good, *AUTOCALL, 3, N, sv, shift, True, qe=True)
+    with pytest.raises(AccelerationError, match="OLMC_QMC_SEQUENTIAL only"):
+        _hip.heston_cliquet_qmc(S, T, R, Q, *good, *CLIQUET, 3, N, sv, shift, True, qe=True)
+    # v0 = 0 is a legal start of QE
+    assert math.isfinite(_hip.heston_cliquet(S, T, R, Q, *good[:4], 0.0, *CLIQUET, 3, N, n, 1, qe=True).price)
+
+
+def test_nan_inputs_answer_nan():
+    N, n, seed = 1000, 12, 3
+    sv, shift = sobol_tables(2 * n, seed, N)
+    nan = float("nan")
+    model = qe.FELLER_VIOLATED
+    for is_qe in (False, True):
+        for i in (0, 1, 2, 3, 4, 5, 6, 8, 9, 10, 11, 12):                           # S, T, r, q, kappa, theta, sigma_v, v0, the contract (rho: refused)
+            for contract, philox, sobol in ((AUTOCALL, _hip.heston_autocallable, _hip.heston_autocallable_qmc),
+                                            (CLIQUET, _hip.heston_cliquet, _hip.heston_cliquet_qmc)):
+                args = [S, T, R, Q, *model, *contract]
+                assert math.isfinite(philox(*args, 3, N, n, seed, qe=is_qe).price)
+                args[i] = nan
+                for st in (philox(*args, 3, N, n, seed, qe=is_qe), sobol(*args, 3, N, sv, shift, False, qe=is_qe)):
+                    assert math.isnan(st.price) and math.isnan(st.std_error), (is_qe, i)
+
+
+def test_a_negative_start_variance_means_under_euler_what_it_means_in_olmc_heston():
+    model, N, n, f, periods, seed = (2.0, 0.04, 0.3, -0.7, -0.01), 1000, 13, 4, 4, 3
+    spot, var = _hip.heston_paths(S, T, R, Q, *model, N, n, seed, path_major=True)
+    assert np.all(var[:, 0] == -0.01) and np.all(spot[:, 1] == spot[0, 1])         # the first step is deterministic
+    check_both_products("v0 < 0", [spot], f, periods, philox_autocall(model, f, N, n, seed, False), philox_cliquet(model, periods, N, n, seed, False))
+    sv, shift = sobol_tables(2 * n, seed, N)
+    for construction in ("bridge", "sequential"):
+        qspot, _ = _hip.heston_qmc_paths(S, T, R, Q, *model, N, sv, shift, construction == "bridge", path_major=True)
+        check_both_products(("v0 < 0", construction), [qspot], f, periods, sobol_autocall(model, f, N, n, seed, construction, False),
+                            sobol_cliquet(model, periods, N, n, seed, construction, False))
+    with pytest.raises(AccelerationError, match="v0 must be non-negative for the QE scheme"):
+        philox_autocall(model, f, N, n, seed, True)

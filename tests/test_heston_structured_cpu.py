@@ -1,0 +1,306 @@
+"""The autocallable and the cliquet under Heston without a GPU (include/olmc.h "structured products under Heston";
+HestonPricer.price_autocallable / price_cliquet): signatures, the Python refusals before the device, the routing of every (method, scheme)
+to its binding, the observation_freq > n_steps mapping, the C ABI's symbols and its refusals before any device work, and the golden
+file's generator.
+"""
+import ctypes as C
+import inspect
+import json
+import math
+import os
+import warnings
+
+import numpy as np
+import pytest
+
+import optionslab_amd as ol
+from optionslab_amd import _hip
+from tests import heston_qe_reference as qe
+
+S, R, Q, T = 100.0, 0.05, 0.01, 1.0
+NAMES = ("olmc_heston_autocallable", "olmc_heston_autocallable_qmc", "olmc_heston_cliquet", "olmc_heston_cliquet_qmc")
+BINDINGS = ("heston_autocallable", "heston_autocallable_qmc", "heston_cliquet", "heston_cliquet_qmc")
+AUTOCALL = (1.0, 0.9, 0.10, 0.8)          # autocall, coupon, rate, knock-in
+CLIQUET = (0.05, -0.05, 0.30, 0.0)
+
+
+def pricer(model):
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", UserWarning)                               # Feller
+        return ol.HestonPricer(*model)
+
+
+@pytest.fixture
+def no_library(monkeypatch):
+    """Any attempt to load the library (hence to reach the device) fails the test."""
+    def touched(*a, **k):
+        raise AssertionError("the library was loaded")
+
+    monkeypatch.setattr(_hip, "lib", touched)
+
+
+# ---------------------------------------------------------------------------------------------------- the signatures ----
+def test_the_signatures_are_the_issues():
+    auto = inspect.signature(ol.HestonPricer.price_autocallable).parameters
+    assert list(auto) == ["self", "S", "T", "r", "q", "autocall_barrier", "coupon_barrier", "coupon_rate", "ki_barrier", "observation_freq",
+                          "n_paths", "n_steps", "seed", "antithetic", "return_error", "method", "path_construction", "scheme"]
+    assert [auto[k].default for k in list(auto)[4:]] == [0.0, 1.0, 0.8, 0.10, 0.6, 21, 100000, 252, None, False, False, "pseudo", "bridge",
+                                                        "euler"]
+    cliq = inspect.signature(ol.HestonPricer.price_cliquet).parameters
+    assert list(cliq) == ["self", "S", "T", "r", "q", "local_cap", "local_floor", "global_cap", "global_floor", "n_periods", "n_paths",
+                          "n_steps", "seed", "antithetic", "return_error", "method", "path_construction", "scheme"]
+    assert [cliq[k].default for k in list(cliq)[4:]] == [0.0, 0.05, -0.05, 0.30, 0.0, 12, 100000, 252, None, False, False, "pseudo", "bridge",
+                                                        "euler"]
+    for parameters in (auto, cliq):
+        for name in ("method", "path_construction", "scheme"):
+            assert parameters[name].kind is inspect.Parameter.KEYWORD_ONLY
+        assert parameters["return_error"].kind is inspect.Parameter.POSITIONAL_OR_KEYWORD
+    # the path payoffs stay as they are
+    for f in (ol.HestonPricer.price_asian, ol.HestonPricer.price_barrier, ol.HestonPricer.price_lookback):
+        assert "scheme" not in inspect.signature(f).parameters
+
+
+# ------------------------------------------------------------------------------------------------- the Python refusals ----
+def test_the_refusals_come_before_the_device(no_library):
+    p = pricer(qe.FELLER_VIOLATED)
+    calls = {
+        "price_autocallable": lambda n_paths=100, n_steps=12, **kw: p.price_autocallable(S, T, R, Q, *AUTOCALL, 3, n_paths, n_steps, 1, **kw),
+        "price_cliquet": lambda n_paths=100, n_steps=12, **kw: p.price_cliquet(S, T, R, Q, *CLIQUET, 12, n_paths, n_steps, 1, **kw),
+    }
+    for name, call in calls.items():
+        with pytest.raises(ValueError, match="scheme must be"):
+            call(scheme="milstein")
+        with pytest.raises(ValueError, match="pass path_construction='sequential'"):
+            call(scheme="qe", method="qmc")                                         # the default construction is the bridge
+        with pytest.raises(ValueError, match="pass path_construction='sequential'"):
+            call(scheme="qe", method="qmc", path_construction="bridge")
+        for scheme in ("euler", "qe"):
+            with pytest.raises(ValueError, match="method"):
+                call(scheme=scheme, method="sobol")
+            with pytest.raises(ValueError, match="path_construction"):
+                call(scheme=scheme, method="qmc", path_construction="pca")
+            with pytest.raises(ValueError, match=">= 1"):
+                call(n_paths=0, scheme=scheme)
+            with pytest.raises(ValueError, match=">= 1"):
+                call(n_steps=0, scheme=scheme)
+        with pytest.raises(ValueError):
+            call(n_paths=(1 << 30) + 1, method="qmc")                               # what price_monte_carlo refuses of Sobol counts
+        with pytest.raises(ValueError):
+            call(n_steps=1025, method="qmc")                                        # the bridge's cap
+        with pytest.raises(ValueError):
+            call(n_steps=10601, method="qmc", path_construction="sequential")
+    for freq in (0, -3):
+        with pytest.raises(ValueError, match="observation_freq must be >= 1"):
+            p.price_autocallable(S, T, R, Q, *AUTOCALL, freq, 100, 12, 1)
+    for periods in (0, -1, 13):
+        with pytest.raises(ValueError, match=r"n_periods must be in \[1, n_steps\]"):
+            p.price_cliquet(S, T, R, Q, *CLIQUET, periods, 100, 12, 1)
+
+
+# ---------------------------------------------------------------------------------------------------------- the routing ----
+@pytest.fixture
+def recorded(no_library, monkeypatch):
+    """The four bindings replaced by recorders that answer in a binding's shape."""
+    calls = []
+
+    def recorder(name):
+        def call(*args, **kw):
+            calls.append((name, args, kw))
+            st = _hip.Stats()
+            st.price, st.std_error = 7.0, 0.5
+            return st
+        return call
+
+    for name in BINDINGS:
+        monkeypatch.setattr(_hip, name, recorder(name))
+    return calls
+
+
+@pytest.mark.parametrize("scheme", ("euler", "qe"))
+def test_every_method_and_scheme_reaches_its_own_binding(recorded, scheme):
+    model = qe.FELLER_VIOLATED
+    p = pricer(model)
+    qe_flag = scheme == "qe"
+    extras = (dict(), dict(scheme="euler")) if scheme == "euler" else (dict(scheme="qe"),)
+    for extra in extras:
+        recorded.clear()
+        # Philox
+        assert p.price_autocallable(S, T, R, Q, *AUTOCALL, 3, 1000, 12, 5, True, **extra) == 7.0
+        assert p.price_cliquet(S, T, R, Q, *CLIQUET, 4, 1000, 12, 5, False, True, **extra) == (7.0, 0.5)
+        (n0, a0, k0), (n1, a1, k1) = recorded
+        assert n0 == "heston_autocallable" and a0 == (S, T, R, Q, *model, *AUTOCALL, 3, 1000, 12, 5, True) and k0 == dict(qe=qe_flag)
+        assert n1 == "heston_cliquet" and a1 == (S, T, R, Q, *model, *CLIQUET, 4, 1000, 12, 5, False) and k1 == dict(qe=qe_flag)
+        assert isinstance(p.price_cliquet(S, T, R, Q, *CLIQUET, 4, 1000, 12, 5, **extra), np.float64)
+        recorded.clear()
+        # Sobol: the sequential construction for both schemes, the bridge (the default) for Euler only
+        constructions = [("sequential", False)] + ([("bridge", True)] if scheme == "euler" else [])
+        for construction, bridge in constructions:
+            recorded.clear()
+            kw = dict(method="qmc", path_construction=construction, **extra)
+            p.price_autocallable(S, T, R, Q, *AUTOCALL, 3, 128, 12, 5, True, **kw)
+            p.price_cliquet(S, T, R, Q, *CLIQUET, 4, 128, 12, 5, **kw)
+            (n0, a0, k0), (n1, a1, k1) = recorded
+            assert n0 == "heston_autocallable_qmc" and a0[:14] == (S, T, R, Q, *model, *AUTOCALL, 3) and a0[14] == 128
+            assert a0[15].shape == (24, 30) and a0[16].shape == (24,) and a0[17:] == (bridge, True) and k0 == dict(qe=qe_flag)
+            assert n1 == "heston_cliquet_qmc" and a1[:14] == (S, T, R, Q, *model, *CLIQUET, 4) and a1[14] == 128
+            assert a1[15].shape == (24, 30) and a1[17:] == (bridge, False) and k1 == dict(qe=qe_flag)
+    if scheme == "euler":
+        recorded.clear()
+        p.price_autocallable(S, T, R, Q, *AUTOCALL, 3, 128, 12, 5, method="qmc")
+        assert recorded[0][1][17] is True                                           # the default construction is the bridge
+
+
+def test_seed_none_draws_a_seed_and_the_tables(recorded):
+    p = pricer(qe.USUAL)
+    p.price_cliquet(S, T, R, Q, n_paths=100, n_steps=12)
+    p.price_autocallable(S, T, R, Q, n_paths=100, n_steps=12, observation_freq=3, method="qmc")
+    (_n0, a0, _k0), (_n1, a1, _k1) = recorded
+    assert isinstance(a0[16], int) and 0 <= a0[16] < 2**31                        # n_paths, n_steps, seed, antithetic
+    assert a1[15].shape == (24, 30)
+
+
+def test_an_observation_frequency_beyond_the_steps_is_one_unreachable_observation_on_the_last_step(recorded):
+    p = pricer(qe.USUAL)
+    p.price_autocallable(S, T, R, Q, *AUTOCALL, 13, 1000, 12, 5)
+    p.price_autocallable(S, T, R, Q, *AUTOCALL, 12, 1000, 12, 5)
+    p.price_autocallable(S, T, R, Q, *AUTOCALL, 300, 128, 12, 5, method="qmc", path_construction="sequential", scheme="qe")
+    (_n0, a0, _k0), (_n1, a1, _k1), (_n2, a2, _k2) = recorded
+    assert a0[9:14] == (math.inf, *AUTOCALL[1:], 12)
+    assert a1[9:14] == (*AUTOCALL, 12)                                              # observation_freq = n_steps is an observation like any
+    assert a2[9:14] == (math.inf, *AUTOCALL[1:], 12)
+
+
+# ---------------------------------------------------------------------------------------------------------- the C ABI ----
+@pytest.fixture(scope="module")
+def library():
+    from optionslab_amd.build import build_library
+
+    build_library()
+    return _hip.load_library()
+
+
+def test_the_entry_points_are_declared_bound_and_exported(library):
+    from tests.test_abi_cpu import declared_symbols, exported_symbols
+
+    exported = exported_symbols(_hip.LIBRARY_PATH)
+    for name, binding in zip(NAMES, BINDINGS):
+        assert name in declared_symbols() and name in _hip.PROTOTYPES and hasattr(library, name) and name in exported
+        assert callable(getattr(_hip, binding))
+    assert (_hip.HESTON_EULER, _hip.HESTON_QE) == (0, 1)
+    header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "olmc.h")).read()
+    assert "enum { OLMC_HESTON_EULER = 0, OLMC_HESTON_QE = 1 };" in header and "structured products under Heston" in header
+    assert library.olmc_abi_version() == 6
+
+
+def _st():
+    return _hip.Stats()
+
+
+def _sobol(dims):
+    return (C.c_uint32 * (30 * dims))(*range(1, 30 * dims + 1)), (C.c_uint32 * dims)()
+
+
+_M = (2.0, 0.04, 0.3, -0.7, 0.04)
+_MKT = (100.0, 1.0, 0.05, 0.01)
+
+
+def _model(**over):
+    m = dict(zip(("kappa", "theta", "sigma_v", "rho", "v0"), _M))
+    m.update(over)
+    return tuple(m.values())
+
+
+def _philox(product, model=_M, count=4, scheme=0, offset=0, n_local=100, n_steps=12, out=True):
+    """count = observation_freq or n_periods."""
+    contract = AUTOCALL if product == "autocallable" else CLIQUET
+    return lambda: (*_MKT, *model, *contract, count, scheme, offset, n_local, n_steps, 1, 0, C.byref(_st()) if out else None)
+
+
+def _qmc(product, model=_M, count=4, scheme=0, construction=0, offset=0, n_points=64, n_steps=12, bits=30, tables=True, out=True):
+    contract = AUTOCALL if product == "autocallable" else CLIQUET
+    sv, shift = _sobol(2 * max(n_steps, 1)) if tables else (None, None)
+    return lambda: (*_MKT, *model, *contract, count, scheme, construction, offset, n_points, n_steps, sv, shift, bits, 0,
+                    C.byref(_st()) if out else None)
+
+
+_BRIDGE = "the QE scheme takes OLMC_QMC_SEQUENTIAL only: its variance draw is a uniform, not a Brownian increment"
+_SCHEME = "bad scheme (OLMC_HESTON_EULER or OLMC_HESTON_QE)"
+_COUNT = {"autocallable": ("observation_freq must be >= 1", "no observation date: observation_freq > n_steps"),
+          "cliquet": ("n_periods must be in [1, n_steps]", "n_periods must be in [1, n_steps]")}
+_REFUSALS = []
+for _product, _names in (("autocallable", NAMES[:2]), ("cliquet", NAMES[2:])):
+    for _name, _make in zip(_names, (_philox, _qmc)):
+        _below, _above = _COUNT[_product]
+        _REFUSALS += [
+            (_name, _make(_product, out=False), "null pointer"),
+            (_name, _make(_product, scheme=2), _SCHEME),
+            (_name, _make(_product, scheme=-1), _SCHEME),
+            (_name, _make(_product, _model(rho=1.5)), "rho must be in [-1, 1]"),
+            (_name, _make(_product, _model(rho=-1.5), scheme=1), "rho must be in [-1, 1]"),
+            (_name, _make(_product, count=0), _below),
+            (_name, _make(_product, count=-2, scheme=1), _below),
+            (_name, _make(_product, count=13), _above),
+            (_name, _make(_product, count=13, scheme=1), _above),
+            (_name, _make(_product, n_steps=0), "n_steps must be in [1, 10600]: a step takes two of the 21201 Sobol dimensions"
+             if _make is _qmc else "n_steps must be >= 1"),
+            (_name, _make(_product, offset=-1), "path_offset must be >= 0"),
+            (_name, _make(_product, _model(kappa=0.0), scheme=1), "kappa must be positive for the QE scheme"),
+            (_name, _make(_product, _model(theta=-0.04), scheme=1), "theta must be positive for the QE scheme"),
+            (_name, _make(_product, _model(sigma_v=0.0), scheme=1), "sigma_v must be positive for the QE scheme"),
+            (_name, _make(_product, _model(v0=-1e-9), scheme=1), "v0 must be non-negative for the QE scheme"),
+        ]
+    _REFUSALS += [
+        (_names[0], _philox(_product, n_local=0), "n_paths must be >= 1"),
+        (_names[1], _qmc(_product, n_points=0), "n_paths must be >= 1"),
+        (_names[1], _qmc(_product, n_points=(1 << 30) + 1), "at most 2**30 Sobol points"),
+        (_names[1], _qmc(_product, construction=1, scheme=1), _BRIDGE),
+        (_names[1], _qmc(_product, construction=2), "bad construction"),
+        (_names[1], _qmc(_product, construction=7, scheme=1), "bad construction"),
+        (_names[1], _qmc(_product, bits=32), "only 30-bit Sobol tables (SciPy's default) are supported"),
+        (_names[1], _qmc(_product, tables=False), "null pointer"),
+        (_names[1], _qmc(_product, construction=1, n_steps=1025),
+         "the Brownian-bridge construction takes at most OLMC_QMC_BRIDGE_MAX_STEPS (1024) dates"),
+        (_names[1], _qmc(_product, n_steps=10601, tables=False), "n_steps must be in [1, 10600]: a step takes two of the 21201 Sobol dimensions"),
+    ]
+
+
+@pytest.mark.parametrize("name,args,message", _REFUSALS, ids=[f"{n}-{i}" for i, (n, _a, _m) in enumerate(_REFUSALS)])
+def test_the_entry_points_refuse_bad_arguments_before_touching_a_device(library, name, args, message):
+    rc = getattr(library, name)(*args())
+    assert rc == 1
+    assert library.olmc_last_error().decode() == message
+
+
+def test_a_negative_start_variance_is_eulers_to_take_and_qes_to_refuse(library):
+    """v0 < 0 means under Euler what it means in olmc_heston: it passes the argument checks (the next refusal shows it did)."""
+    rc = library.olmc_heston_autocallable(*_philox("autocallable", _model(v0=-0.01), n_local=0)())
+    assert rc == 1 and library.olmc_last_error().decode() == "n_paths must be >= 1"
+    rc = library.olmc_heston_cliquet(*_philox("cliquet", _model(v0=-0.01), scheme=1, n_local=0)())
+    assert rc == 1 and library.olmc_last_error().decode() == "v0 must be non-negative for the QE scheme"
+
+
+# ------------------------------------------------------------------------------------------------- the golden file ----
+def test_the_generator_reproduces_the_first_golden_entry_at_a_reduced_n():
+    """The first entry (QE, Feller violated, cliquet) needs nothing but this repository.  At N = 2^16 the generator's own function must
+    give a value within 4 combined standard errors of the stored one (other draws of the same law: the first 2^16 paths of the stored
+    run's stream are not its first chunk's), a standard error that scales as 1 / sqrt(N) (within 5 %: the relative error of a
+    standard deviation estimated from 2^16 payoffs is about 1 / sqrt(2 N) = 0.3 %), and the same numbers when run twice."""
+    from tests.golden import make_heston_structured as gen
+
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "heston_structured.json")) as f:
+        doc = json.load(f)
+    first = doc["prices"][0]
+    assert (first["scheme"], first["model"], first["payoff"]) == ("qe", "feller_violated", "cliquet")
+    assert doc["inputs"] == dict(S=gen.S, T=gen.T, r=gen.R, q=gen.Q, n_paths=gen.N, n_steps=gen.STEPS, numpy_seed=gen.SEED, chunk=gen.CHUNK)
+    assert doc["autocallable"] == gen.AUTOCALLABLE and doc["cliquet"] == gen.CLIQUET
+    assert [(e["scheme"], e["model"], e["payoff"]) for e in doc["prices"]] == [
+        ("qe", "feller_violated", "cliquet"), ("qe", "feller_violated", "autocallable"), ("qe", "steep", "cliquet"),
+        ("qe", "steep", "autocallable"), ("euler", "usual", "cliquet"), ("euler", "usual", "autocallable")]
+    n = 1 << 16
+    got, auto = gen.qe_entries("feller_violated", n)
+    again, _ = gen.qe_entries("feller_violated", n)
+    assert got == again and got["payoff"] == "cliquet" and auto["payoff"] == "autocallable"
+    combined = math.hypot(got["std_error"], first["std_error"])
+    print("golden", first, "at 2^16", got, "deviation / combined standard error", (got["price"] - first["price"]) / combined)
+    assert abs(got["price"] - first["price"]) <= 4.0 * combined
+    assert got["std_error"] == pytest.approx(first["std_error"] * math.sqrt(gen.N / n), rel=0.05)
