@@ -1628,12 +1628,18 @@ extern "C" int olmc_american_lsm(double S, double K, double T, double r, double 
 
 // ===================================================================== Heston ====
 namespace {
-HestonContract make_heston(double S, double K, double T, double r, double q, int is_call, double kappa, double theta,
-                           double sigma_v, double rho, double v0, int32_t n_steps) {
+// The model, as every olmc_heston* entry point hands it inward.
+struct HestonModel {
+    double kappa, theta, sigma_v, rho, v0;
+    bool nan() const { return std::isnan(kappa + theta + sigma_v + rho + v0); }
+};
+
+HestonContract make_heston(double S, double K, double T, double r, double q, int is_call, const HestonModel& m, int32_t n_steps) {
+    const double kappa = m.kappa, theta = m.theta, sigma_v = m.sigma_v, rho = m.rho;
     HestonContract hc;
     const double dt = T / n_steps;                     // heston.py:218-219
     hc.log_s0 = std::log(S);
-    hc.v0 = v0;
+    hc.v0 = m.v0;
     hc.mu_dt = (r - q) * dt;
     hc.dt = dt;
     hc.sqrt_dt = std::sqrt(dt);
@@ -1648,51 +1654,141 @@ HestonContract make_heston(double S, double K, double T, double r, double q, int
 }
 
 // The model checks every Heston entry point makes (Philox and Sobol), and the inputs that answer NaN.
-int heston_check(double rho) {
-    if (!(rho >= -1.0 && rho <= 1.0)) return fail(OLMC_ERR_ARG, "rho must be in [-1, 1]");
+int heston_check(const HestonModel& m) {
+    if (!(m.rho >= -1.0 && m.rho <= 1.0)) return fail(OLMC_ERR_ARG, "rho must be in [-1, 1]");
     return OLMC_OK;
 }
-bool heston_poisoned(double S, double K, double T, double r, double q, double kappa, double theta, double sigma_v, double rho, double v0) {
-    return poisoned(S, K, T, r, 0.0, q) || std::isnan(kappa + theta + sigma_v + rho + v0);
-}
-}  // namespace
+bool heston_poisoned(double S, double K, double T, double r, double q, const HestonModel& m) { return poisoned(S, K, T, r, 0.0, q) || m.nan(); }
 
-extern "C" int olmc_heston_paths(double S, double T, double r, double q, double kappa, double theta, double sigma_v, double rho,
-                                 double v0, int64_t n_paths, int32_t n_steps, uint64_t seed, int path_major, double* spot_host,
-                                 double* var_host) {
+// The scheme divides by kappa, sigma_v and the conditional mean m = v E + theta (1 - E), and starts from v0 itself.
+int heston_qe_check(const HestonModel& m) {
+    const int rc = heston_check(m);
+    if (rc) return rc;
+    if (m.kappa <= 0.0) return fail(OLMC_ERR_ARG, "kappa must be positive for the QE scheme");
+    if (m.theta <= 0.0) return fail(OLMC_ERR_ARG, "theta must be positive for the QE scheme");
+    if (m.sigma_v <= 0.0) return fail(OLMC_ERR_ARG, "sigma_v must be positive for the QE scheme");
+    if (m.v0 < 0.0) return fail(OLMC_ERR_ARG, "v0 must be non-negative for the QE scheme");
+    return OLMC_OK;
+}
+
+int heston_qe_sequential(int construction) {
+    if (construction == OLMC_QMC_BRIDGE)
+        return fail(OLMC_ERR_ARG, "the QE scheme takes OLMC_QMC_SEQUENTIAL only: its variance draw is a uniform, not a Brownian increment");
+    return OLMC_OK;
+}
+
+// The launch constants, every one folded here in fp64 (olmc_kernels.h "Heston, quadratic-exponential scheme").
+HestonQeContract make_heston_qe(double S, double T, double r, double q, int is_call, const HestonModel& m, int32_t n_steps) {
+    const double kappa = m.kappa, theta = m.theta, sigma_v = m.sigma_v, rho = m.rho;
+    HestonQeContract hc;
+    const double dt = T / n_steps;
+    const double e = std::exp(-kappa * dt), one_minus_e = -std::expm1(-kappa * dt);
+    const double g = 0.5 * dt * (kappa * rho / sigma_v - 0.5);
+    hc.log_s0 = std::log(S);
+    hc.v0 = m.v0;
+    hc.drift_dt = (r - q) * dt + -rho * kappa * theta * dt / sigma_v;                // (r - q) dt + K0
+    hc.e = e;
+    hc.theta_1me = theta * one_minus_e;
+    hc.c1 = sigma_v * sigma_v * e * one_minus_e / kappa;
+    hc.c2 = theta * sigma_v * sigma_v * one_minus_e * one_minus_e / (2.0 * kappa);
+    hc.k1 = g - rho / sigma_v;
+    hc.k2 = g + rho / sigma_v;
+    hc.k3 = 0.5 * dt * (1.0 - rho * rho);                                            // K4 = K3
+    hc.sign = is_call ? 1.0 : -1.0;
+    return hc;
+}
+
+// A discretisation scheme as the entry points that serve both take it: its launch contract and how to make it, the model checks of its
+// calls, whether its Sobol form takes the Brownian bridge, and its Philox kernels (the Sobol ones differ in their arguments by kBridge).
+struct HestonEuler {
+    using Contract = HestonContract;
+    static constexpr bool kBridge = true;
+    static int check(const HestonModel& m) { return heston_check(m); }
+    static Contract make(double S, double T, double r, double q, int is_call, const HestonModel& m, int32_t n_steps) {
+        return make_heston(S, 0.0, T, r, q, is_call, m, n_steps);
+    }
+    template <bool PM> static constexpr auto paths_kernel() { return heston_paths_kernel<PM>; }
+    template <bool A> static constexpr auto surface_kernel() { return heston_surface_kernel<A>; }
+    template <template <bool> class Product, bool A> static constexpr auto product_kernel() { return heston_product_kernel<Product, A>; }
+};
+struct HestonQe {
+    using Contract = HestonQeContract;
+    static constexpr bool kBridge = false;
+    static int check(const HestonModel& m) { return heston_qe_check(m); }
+    static Contract make(double S, double T, double r, double q, int is_call, const HestonModel& m, int32_t n_steps) {
+        return make_heston_qe(S, T, r, q, is_call, m, n_steps);
+    }
+    template <bool PM> static constexpr auto paths_kernel() { return heston_qe_paths_kernel<PM>; }
+    template <bool A> static constexpr auto surface_kernel() { return heston_qe_surface_kernel<A>; }
+    template <template <bool> class Product, bool A> static constexpr auto product_kernel() { return heston_qe_product_kernel<Product, A>; }
+};
+template <typename F>
+int with_heston_scheme(int scheme, F&& f) {
+    return scheme == OLMC_HESTON_QE ? f(HestonQe{}) : f(HestonEuler{});
+}
+// The model checks of a Sobol call of the scheme, up to the construction it takes.
+template <typename Scheme>
+int heston_qmc_scheme_check(const HestonModel& m, int construction) {
+    const int rc = Scheme::check(m);
+    if (rc || Scheme::kBridge) return rc;
+    return heston_qe_sequential(construction);
+}
+
+// The two device matrices of a path call (spot, then variance, [n + 1] dates each) in the context's bulk buffer, to the host after `launch`.
+template <typename Launch>
+int heston_path_matrices(DeviceCtx* c, int64_t n_paths, int32_t n_steps, double* spot_host, double* var_host, Launch&& launch) {
+    const size_t bytes = sizeof(double) * static_cast<size_t>(n_paths) * (static_cast<size_t>(n_steps) + 1);
+    double* d_spot = static_cast<double*>(c->d_bulk);
+    double* d_var = d_spot + static_cast<size_t>(n_paths) * (n_steps + 1);
+    EventPair ep{};
+    const EventPair* timed = nullptr;                  // profiling on: the path kernel counts in olmc_kernel_time
+    int rc = prof_pair(c, &ep, &timed);
+    if (rc) return rc;
+    launch(timed, d_spot, d_var);
+    HIP_TRY(hipGetLastError());
+    rc = copy_to_host(c, spot_host, d_spot, bytes);
+    if (rc) return rc;
+    return copy_to_host(c, var_host, d_var, bytes);
+}
+
+// Philox: every (S, v) state of paths [0, n_paths) of the scheme's stream.
+template <typename Scheme>
+int run_heston_paths(double S, double T, double r, double q, const HestonModel& m, int64_t n_paths, int32_t n_steps, uint64_t seed, int path_major,
+                     double* spot_host, double* var_host) {
     if (!spot_host || !var_host) return fail(OLMC_ERR_ARG, "null pointer");
-    int rc = heston_check(rho);
+    int rc = Scheme::check(m);
     if (rc) return rc;
     const double bytes = 8.0 * static_cast<double>(n_paths) * (n_steps + 1.0);
     CtxLease lease;
     rc = matrix_prologue(n_paths, n_steps, 2 * bytes, "path matrices would exceed 64 GB", &lease);
     if (rc) return rc;
     DeviceCtx* const c = lease.c;
-    double* d_spot = static_cast<double*>(c->d_bulk);
-    double* d_var = d_spot + static_cast<size_t>(n_paths) * (n_steps + 1);
-    const HestonContract hc = make_heston(S, 0.0, T, r, q, 1, kappa, theta, sigma_v, rho, v0, n_steps);
+    const auto hc = Scheme::make(S, T, r, q, 1, m, n_steps);
     const PathRange pr = make_range(0, n_paths, n_steps, seed);
-    EventPair ep{};
-    const EventPair* timed = nullptr;                  // profiling on: the path kernel counts in olmc_kernel_time
-    rc = prof_pair(c, &ep, &timed);
-    if (rc) return rc;
-    with_bool(path_major != 0, [&](auto pm) {
-        launch_timed(heston_paths_kernel<pm>, dim3(grid_for(n_paths)), dim3(kBlock), c->stream, timed, pr, hc, S, d_spot, d_var);
+    return heston_path_matrices(c, n_paths, n_steps, spot_host, var_host, [&](const EventPair* timed, double* d_spot, double* d_var) {
+        with_bool(path_major != 0, [&](auto pm) {
+            launch_timed(Scheme::template paths_kernel<decltype(pm)::value>(), dim3(grid_for(n_paths)), dim3(kBlock), c->stream, timed, pr, hc, S, d_spot,
+                         d_var);
+        });
     });
-    HIP_TRY(hipGetLastError());
-    rc = copy_to_host(c, spot_host, d_spot, static_cast<size_t>(bytes));
-    if (rc) return rc;
-    return copy_to_host(c, var_host, d_var, static_cast<size_t>(bytes));
+}
+}  // namespace
+
+extern "C" int olmc_heston_paths(double S, double T, double r, double q, double kappa, double theta, double sigma_v, double rho,
+                                 double v0, int64_t n_paths, int32_t n_steps, uint64_t seed, int path_major, double* spot_host,
+                                 double* var_host) {
+    return run_heston_paths<HestonEuler>(S, T, r, q, {kappa, theta, sigma_v, rho, v0}, n_paths, n_steps, seed, path_major, spot_host, var_host);
 }
 
 extern "C" int olmc_heston(double S, double K, double T, double r, double q, int is_call, double kappa, double theta,
                            double sigma_v, double rho, double v0, int64_t path_offset, int64_t n_local, int32_t n_steps,
                            uint64_t seed, int antithetic, olmc_stats* out) {
     if (!out) return fail(OLMC_ERR_ARG, "null pointer");
-    const int rc = heston_check(rho);
+    const HestonModel m{kappa, theta, sigma_v, rho, v0};
+    const int rc = heston_check(m);
     if (rc) return rc;
-    const HestonContract hc = make_heston(S, K, T, r, q, is_call, kappa, theta, sigma_v, rho, v0, n_steps);
-    const bool bad = heston_poisoned(S, K, T, r, q, kappa, theta, sigma_v, rho, v0);
+    const HestonContract hc = make_heston(S, K, T, r, q, is_call, m, n_steps);
+    const bool bad = heston_poisoned(S, K, T, r, q, m);
     return run_structured(path_offset, n_local, n_steps, seed, antithetic, r, T, bad, out,
                           [&](int32_t grid, hipStream_t st, const EventPair* timed, const PathRange& pr, const ReduceWs& ws) {
                               with_bool(antithetic != 0, [&](auto a) { launch_timed(heston_kernel<a>, dim3(grid), dim3(kBlock), st, timed, pr, hc, ws); });
@@ -2371,18 +2467,50 @@ auto heston_qmc_shape(int64_t point_offset, int64_t n_points, int32_t n_steps) {
         return rc2;
     };
 }
+
+// Sobol: every (S, v) state of points [0, n_points) of the scheme's construction.
+template <typename Scheme>
+int run_heston_qmc_paths(double S, double T, double r, double q, const HestonModel& m, int construction, int64_t n_points, int32_t n_steps,
+                         const uint32_t* sv, const uint32_t* shift, int32_t bits, int path_major, double* spot_host, double* var_host) {
+    if (!spot_host || !var_host) return fail(OLMC_ERR_ARG, "null pointer");
+    int rc = heston_qmc_scheme_check<Scheme>(m, construction);
+    if (rc) return rc;
+    const double bytes = 8.0 * static_cast<double>(n_points) * (n_steps + 1.0);
+    CtxLease lease;
+    rc = qmc_matrix_prologue(construction, n_points, n_steps, sv, shift, bits, 2 * bytes, &lease, true, 2);
+    if (rc) return rc;
+    DeviceCtx* const c = lease.c;
+    const auto hc = Scheme::make(S, T, r, q, 1, m, n_steps);
+    QmcPathLaunch pl;
+    rc = qmc_path_setup(c, construction, 0, n_points, n_steps, sv, shift, 0, &pl, 2);
+    if (rc) return rc;
+    const int32_t grid = qmc_block_grid((n_points + kWave - 1) / kWave);
+    return heston_path_matrices(c, n_points, n_steps, spot_host, var_host, [&](const EventPair* timed, double* d_spot, double* d_var) {
+        with_bool(path_major != 0, [&](auto pm) {
+            if constexpr (Scheme::kBridge) {
+                with_bool(pl.bridge, [&](auto b) {
+                    launch_timed(heston_qmc_paths_kernel<b, pm>, dim3(grid), dim3(kBlock), c->stream, timed, pl.qr, hc, S, pl.d_sv, pl.d_shift, pl.plan,
+                                 d_spot, d_var);
+                });
+            } else {
+                launch_timed(heston_qe_qmc_paths_kernel<pm>, dim3(grid), dim3(kBlock), c->stream, timed, pl.qr, hc, S, pl.d_sv, pl.d_shift, d_spot, d_var);
+            }
+        });
+    });
+}
 }  // namespace
 
 extern "C" int olmc_heston_qmc(double S, double K, double T, double r, double q, int is_call, double kappa, double theta, double sigma_v,
                                double rho, double v0, int construction, int64_t point_offset, int64_t n_points, int32_t n_steps,
                                const uint32_t* sv, const uint32_t* shift, int32_t bits, int antithetic, olmc_stats* out) {
     if (!out) return fail(OLMC_ERR_ARG, "null pointer");
-    int rc = heston_check(rho);
+    const HestonModel hm{kappa, theta, sigma_v, rho, v0};
+    int rc = heston_check(hm);
     if (rc) return rc;
     rc = qmc_path_check(construction, point_offset, n_points, n_steps, sv, shift, bits, 2);
     if (rc) return rc;
-    const HestonContract hc = make_heston(S, K, T, r, q, is_call, kappa, theta, sigma_v, rho, v0, n_steps);
-    const bool bad = heston_poisoned(S, K, T, r, q, kappa, theta, sigma_v, rho, v0);
+    const HestonContract hc = make_heston(S, K, T, r, q, is_call, hm, n_steps);
+    const bool bad = heston_poisoned(S, K, T, r, q, hm);
     return run_qmc_payoff(construction, point_offset, n_points, n_steps, sv, shift, antithetic, r, T, bad, out,
                           [&](int32_t g, hipStream_t s, const EventPair* timed, const QmcPathLaunch& pl, const ReduceWs& ws) {
                               with_bool(pl.bridge, [&](auto b) {
@@ -2398,35 +2526,8 @@ extern "C" int olmc_heston_qmc(double S, double K, double T, double r, double q,
 extern "C" int olmc_heston_qmc_paths(double S, double T, double r, double q, double kappa, double theta, double sigma_v, double rho, double v0,
                                      int construction, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift,
                                      int32_t bits, int path_major, double* spot_host, double* var_host) {
-    if (!spot_host || !var_host) return fail(OLMC_ERR_ARG, "null pointer");
-    int rc = heston_check(rho);
-    if (rc) return rc;
-    const double bytes = 8.0 * static_cast<double>(n_points) * (n_steps + 1.0);
-    CtxLease lease;
-    rc = qmc_matrix_prologue(construction, n_points, n_steps, sv, shift, bits, 2 * bytes, &lease, true, 2);
-    if (rc) return rc;
-    DeviceCtx* const c = lease.c;
-    double* d_spot = static_cast<double*>(c->d_bulk);
-    double* d_var = d_spot + static_cast<size_t>(n_points) * (n_steps + 1);
-    const HestonContract hc = make_heston(S, 0.0, T, r, q, 1, kappa, theta, sigma_v, rho, v0, n_steps);
-    QmcPathLaunch pl;
-    rc = qmc_path_setup(c, construction, 0, n_points, n_steps, sv, shift, 0, &pl, 2);
-    if (rc) return rc;
-    const int32_t grid = qmc_block_grid((n_points + kWave - 1) / kWave);
-    EventPair ep{};
-    const EventPair* timed = nullptr;                  // profiling on: the path kernel counts in olmc_kernel_time, as olmc_heston_paths'
-    rc = prof_pair(c, &ep, &timed);
-    if (rc) return rc;
-    with_bool(pl.bridge, [&](auto b) {
-        with_bool(path_major != 0, [&](auto pm) {
-            launch_timed(heston_qmc_paths_kernel<b, pm>, dim3(grid), dim3(kBlock), c->stream, timed, pl.qr, hc, S, pl.d_sv, pl.d_shift, pl.plan,
-                         d_spot, d_var);
-        });
-    });
-    HIP_TRY(hipGetLastError());
-    rc = copy_to_host(c, spot_host, d_spot, static_cast<size_t>(bytes));
-    if (rc) return rc;
-    return copy_to_host(c, var_host, d_var, static_cast<size_t>(bytes));
+    return run_heston_qmc_paths<HestonEuler>(S, T, r, q, {kappa, theta, sigma_v, rho, v0}, construction, n_points, n_steps, sv, shift, bits, path_major,
+                                             spot_host, var_host);
 }
 
 // ============================================================ path payoffs under Heston ====
@@ -2481,13 +2582,14 @@ extern "C" int olmc_heston_path_payoff(double S, double K, double T, double r, d
                                        double rho, double v0, int payoff, double barrier, int64_t path_offset, int64_t n_local, int32_t n_steps,
                                        uint64_t seed, int antithetic, olmc_stats* out) {
     if (!out) return fail(OLMC_ERR_ARG, "null pointer");
-    int rc = heston_check(rho);
+    const HestonModel hm{kappa, theta, sigma_v, rho, v0};
+    int rc = heston_check(hm);
     if (rc) return rc;
     rc = heston_path_check(payoff, barrier);
     if (rc) return rc;
-    const HestonContract hc = make_heston(S, K, T, r, q, is_call, kappa, theta, sigma_v, rho, v0, n_steps);
+    const HestonContract hc = make_heston(S, K, T, r, q, is_call, hm, n_steps);
     const ExtremaContract ec = heston_path_contract(S, K, is_call, payoff, barrier);
-    const bool bad = heston_poisoned(S, K, T, r, q, kappa, theta, sigma_v, rho, v0) || (heston_path_is_barrier(payoff) && std::isnan(barrier));
+    const bool bad = heston_poisoned(S, K, T, r, q, hm) || (heston_path_is_barrier(payoff) && std::isnan(barrier));
     const double inv_steps = 1.0 / n_steps;                  // n_steps < 1 is refused by run_structured before any launch
     return run_structured(path_offset, n_local, n_steps, seed, antithetic, r, T, bad, out,
                           [&](int32_t grid, hipStream_t st, const EventPair* timed, const PathRange& pr, const ReduceWs& ws) {
@@ -2504,15 +2606,16 @@ extern "C" int olmc_heston_qmc_path_payoff(double S, double K, double T, double 
                                            int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift, int32_t bits,
                                            int antithetic, olmc_stats* out) {
     if (!out) return fail(OLMC_ERR_ARG, "null pointer");
-    int rc = heston_check(rho);
+    const HestonModel hm{kappa, theta, sigma_v, rho, v0};
+    int rc = heston_check(hm);
     if (rc) return rc;
     rc = heston_path_check(payoff, barrier);
     if (rc) return rc;
     rc = qmc_path_check(construction, point_offset, n_points, n_steps, sv, shift, bits, 2);
     if (rc) return rc;
-    const HestonContract hc = make_heston(S, K, T, r, q, is_call, kappa, theta, sigma_v, rho, v0, n_steps);
+    const HestonContract hc = make_heston(S, K, T, r, q, is_call, hm, n_steps);
     const ExtremaContract ec = heston_path_contract(S, K, is_call, payoff, barrier);
-    const bool bad = heston_poisoned(S, K, T, r, q, kappa, theta, sigma_v, rho, v0) || (heston_path_is_barrier(payoff) && std::isnan(barrier));
+    const bool bad = heston_poisoned(S, K, T, r, q, hm) || (heston_path_is_barrier(payoff) && std::isnan(barrier));
     return run_qmc_payoff(construction, point_offset, n_points, n_steps, sv, shift, antithetic, r, T, bad, out,
                           [&](int32_t g, hipStream_t s, const EventPair* timed, const QmcPathLaunch& pl, const ReduceWs& ws) {
                               with_heston_path_family(payoff, [&](auto f) {
@@ -2566,21 +2669,21 @@ void surface_finish(const double* h, const SurfaceOrder& so, const double* strik
         else finish_stats(h[2 * j], h[2 * j + 1], n, r, steps[i] * dt, &out[i]);
     }
 }
-}  // namespace
 
-extern "C" int olmc_heston_surface(double S, double T, double r, double q, int is_call, double kappa, double theta, double sigma_v, double rho,
-                                   double v0, const double* strikes, const int32_t* steps, int32_t k, int64_t path_offset, int64_t n_local,
-                                   int32_t n_steps, uint64_t seed, int antithetic, olmc_stats* out) {
+// Philox: the cells on paths [path_offset, path_offset + n_local) of the scheme's stream, one launch of its surface kernel.
+template <typename Scheme>
+int run_heston_surface(double S, double T, double r, double q, int is_call, const HestonModel& m, const double* strikes, const int32_t* steps,
+                       int32_t k, int64_t path_offset, int64_t n_local, int32_t n_steps, uint64_t seed, int antithetic, olmc_stats* out) {
     if (!strikes || !steps || !out) return fail(OLMC_ERR_ARG, "null pointer");
-    int rc = heston_check(rho);
+    int rc = Scheme::check(m);
     if (rc) return rc;
     rc = check_paths(path_offset, n_local, n_steps);
     if (rc) return rc;
     SurfaceOrder so;
     rc = surface_cells(strikes, steps, k, n_steps, &so);
     if (rc) return rc;
-    const HestonContract hc = make_heston(S, 0.0, T, r, q, is_call, kappa, theta, sigma_v, rho, v0, n_steps);
-    const bool bad = heston_poisoned(S, 0.0, T, r, q, kappa, theta, sigma_v, rho, v0);
+    const auto hc = Scheme::make(S, T, r, q, is_call, m, n_steps);
+    const bool bad = heston_poisoned(S, 0.0, T, r, q, m);
     CtxLease lease;
     rc = ctx_lease(&lease);
     if (rc) return rc;
@@ -2589,28 +2692,30 @@ extern "C" int olmc_heston_surface(double S, double T, double r, double q, int i
     rc = launch_reduce(c, c->stream, c->d_result, -1.0, 2 * kSurfaceCells, grid_for(n_local),
                        [&](int32_t grid, hipStream_t st, const EventPair* timed, const ReduceWs& ws) {
                            with_bool(antithetic != 0, [&](auto a) {
-                               launch_timed(heston_surface_kernel<a>, dim3(grid), dim3(kBlock), st, timed, pr, hc, so.cells, ws);
+                               launch_timed(Scheme::template surface_kernel<decltype(a)::value>(), dim3(grid), dim3(kBlock), st, timed, pr, hc, so.cells, ws);
                            });
                        });
     if (rc) return rc;
-    surface_finish(c->h_result, so, strikes, steps, k, n_local * (antithetic ? 2 : 1), r, hc.dt, bad, out);
+    surface_finish(c->h_result, so, strikes, steps, k, n_local * (antithetic ? 2 : 1), r, T / n_steps, bad, out);
     return OLMC_OK;
 }
 
-extern "C" int olmc_heston_qmc_surface(double S, double T, double r, double q, int is_call, double kappa, double theta, double sigma_v,
-                                       double rho, double v0, const double* strikes, const int32_t* steps, int32_t k, int construction,
-                                       int64_t point_offset, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift,
-                                       int32_t bits, int antithetic, olmc_stats* out) {
+// Sobol: the cells on points [point_offset, point_offset + n_points) of the scheme's construction; the shape of a Heston price launch
+// (without the bridge: the grid over the aligned blocks, no slabs).
+template <typename Scheme>
+int run_heston_qmc_surface(double S, double T, double r, double q, int is_call, const HestonModel& m, const double* strikes, const int32_t* steps,
+                           int32_t k, int construction, int64_t point_offset, int64_t n_points, int32_t n_steps, const uint32_t* sv,
+                           const uint32_t* shift, int32_t bits, int antithetic, olmc_stats* out) {
     if (!strikes || !steps || !out) return fail(OLMC_ERR_ARG, "null pointer");
-    int rc = heston_check(rho);
+    int rc = heston_qmc_scheme_check<Scheme>(m, construction);
     if (rc) return rc;
     rc = qmc_path_check(construction, point_offset, n_points, n_steps, sv, shift, bits, 2);
     if (rc) return rc;
     SurfaceOrder so;
     rc = surface_cells(strikes, steps, k, n_steps, &so);
     if (rc) return rc;
-    const HestonContract hc = make_heston(S, 0.0, T, r, q, is_call, kappa, theta, sigma_v, rho, v0, n_steps);
-    const bool bad = heston_poisoned(S, 0.0, T, r, q, kappa, theta, sigma_v, rho, v0);
+    const auto hc = Scheme::make(S, T, r, q, is_call, m, n_steps);
+    const bool bad = heston_poisoned(S, 0.0, T, r, q, m);
     CtxLease lease;
     rc = ctx_lease(&lease);
     if (rc) return rc;
@@ -2622,185 +2727,68 @@ extern "C" int olmc_heston_qmc_surface(double S, double T, double r, double q, i
     if (rc) return rc;
     rc = launch_reduce(c, c->stream, c->d_result, -1.0, 2 * kSurfaceCells, pl.grid,
                        [&](int32_t g, hipStream_t s, const EventPair* timed, const ReduceWs& ws) {
-                           with_bool(pl.bridge, [&](auto b) {
-                               with_bool(pl.anti, [&](auto m) {
-                                   launch_timed(heston_qmc_surface_kernel<b, m>, dim3(g), dim3(kBlock), s, timed, pl.qr, hc, so.cells, pl.d_sv,
-                                                pl.d_shift, pl.plan, pl.slabs, ws);
-                               });
-                           });
-                       });
-    if (rc) return rc;
-    surface_finish(c->h_result, so, strikes, steps, k, n_points * (pl.anti ? 2 : 1), r, hc.dt, bad, out);
-    return OLMC_OK;
-}
-
-// ====================================================== Heston, quadratic-exponential scheme ====
-// olmc_heston_surface / olmc_heston_paths and their Sobol forms with Andersen's QE step in place of the Euler one (include/olmc.h
-// "Heston, quadratic-exponential scheme"): the same checks, ranges, cells and read-out, one launch of the heston_qe_* kernels.
-namespace {
-// The scheme divides by kappa, sigma_v and the conditional mean m = v E + theta (1 - E), and starts from v0 itself.
-int heston_qe_check(double kappa, double theta, double sigma_v, double rho, double v0) {
-    const int rc = heston_check(rho);
-    if (rc) return rc;
-    if (kappa <= 0.0) return fail(OLMC_ERR_ARG, "kappa must be positive for the QE scheme");
-    if (theta <= 0.0) return fail(OLMC_ERR_ARG, "theta must be positive for the QE scheme");
-    if (sigma_v <= 0.0) return fail(OLMC_ERR_ARG, "sigma_v must be positive for the QE scheme");
-    if (v0 < 0.0) return fail(OLMC_ERR_ARG, "v0 must be non-negative for the QE scheme");
-    return OLMC_OK;
-}
-
-int heston_qe_sequential(int construction) {
-    if (construction == OLMC_QMC_BRIDGE)
-        return fail(OLMC_ERR_ARG, "the QE scheme takes OLMC_QMC_SEQUENTIAL only: its variance draw is a uniform, not a Brownian increment");
-    return OLMC_OK;
-}
-
-// The launch constants, every one folded here in fp64 (olmc_kernels.h "Heston, quadratic-exponential scheme").
-HestonQeContract make_heston_qe(double S, double T, double r, double q, int is_call, double kappa, double theta, double sigma_v, double rho,
-                                double v0, int32_t n_steps) {
-    HestonQeContract hc;
-    const double dt = T / n_steps;
-    const double e = std::exp(-kappa * dt), one_minus_e = -std::expm1(-kappa * dt);
-    const double g = 0.5 * dt * (kappa * rho / sigma_v - 0.5);
-    hc.log_s0 = std::log(S);
-    hc.v0 = v0;
-    hc.drift_dt = (r - q) * dt + -rho * kappa * theta * dt / sigma_v;                // (r - q) dt + K0
-    hc.e = e;
-    hc.theta_1me = theta * one_minus_e;
-    hc.c1 = sigma_v * sigma_v * e * one_minus_e / kappa;
-    hc.c2 = theta * sigma_v * sigma_v * one_minus_e * one_minus_e / (2.0 * kappa);
-    hc.k1 = g - rho / sigma_v;
-    hc.k2 = g + rho / sigma_v;
-    hc.k3 = 0.5 * dt * (1.0 - rho * rho);                                            // K4 = K3
-    hc.sign = is_call ? 1.0 : -1.0;
-    return hc;
-}
-}  // namespace
-
-extern "C" int olmc_heston_qe_surface(double S, double T, double r, double q, int is_call, double kappa, double theta, double sigma_v, double rho,
-                                      double v0, const double* strikes, const int32_t* steps, int32_t k, int64_t path_offset, int64_t n_local,
-                                      int32_t n_steps, uint64_t seed, int antithetic, olmc_stats* out) {
-    if (!strikes || !steps || !out) return fail(OLMC_ERR_ARG, "null pointer");
-    int rc = heston_qe_check(kappa, theta, sigma_v, rho, v0);
-    if (rc) return rc;
-    rc = check_paths(path_offset, n_local, n_steps);
-    if (rc) return rc;
-    SurfaceOrder so;
-    rc = surface_cells(strikes, steps, k, n_steps, &so);
-    if (rc) return rc;
-    const HestonQeContract hc = make_heston_qe(S, T, r, q, is_call, kappa, theta, sigma_v, rho, v0, n_steps);
-    const bool bad = heston_poisoned(S, 0.0, T, r, q, kappa, theta, sigma_v, rho, v0);
-    CtxLease lease;
-    rc = ctx_lease(&lease);
-    if (rc) return rc;
-    DeviceCtx* const c = lease.c;
-    const PathRange pr = make_range(path_offset, n_local, n_steps, seed);
-    rc = launch_reduce(c, c->stream, c->d_result, -1.0, 2 * kSurfaceCells, grid_for(n_local),
-                       [&](int32_t grid, hipStream_t st, const EventPair* timed, const ReduceWs& ws) {
-                           with_bool(antithetic != 0, [&](auto a) {
-                               launch_timed(heston_qe_surface_kernel<a>, dim3(grid), dim3(kBlock), st, timed, pr, hc, so.cells, ws);
-                           });
-                       });
-    if (rc) return rc;
-    surface_finish(c->h_result, so, strikes, steps, k, n_local * (antithetic ? 2 : 1), r, T / n_steps, bad, out);
-    return OLMC_OK;
-}
-
-extern "C" int olmc_heston_qe_qmc_surface(double S, double T, double r, double q, int is_call, double kappa, double theta, double sigma_v,
-                                          double rho, double v0, const double* strikes, const int32_t* steps, int32_t k, int construction,
-                                          int64_t point_offset, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift,
-                                          int32_t bits, int antithetic, olmc_stats* out) {
-    if (!strikes || !steps || !out) return fail(OLMC_ERR_ARG, "null pointer");
-    int rc = heston_qe_check(kappa, theta, sigma_v, rho, v0);
-    if (rc) return rc;
-    rc = heston_qe_sequential(construction);
-    if (rc) return rc;
-    rc = qmc_path_check(construction, point_offset, n_points, n_steps, sv, shift, bits, 2);
-    if (rc) return rc;
-    SurfaceOrder so;
-    rc = surface_cells(strikes, steps, k, n_steps, &so);
-    if (rc) return rc;
-    const HestonQeContract hc = make_heston_qe(S, T, r, q, is_call, kappa, theta, sigma_v, rho, v0, n_steps);
-    const bool bad = heston_poisoned(S, 0.0, T, r, q, kappa, theta, sigma_v, rho, v0);
-    CtxLease lease;
-    rc = ctx_lease(&lease);
-    if (rc) return rc;
-    DeviceCtx* const c = lease.c;
-    QmcPathLaunch pl;
-    rc = qmc_path_setup(c, construction, point_offset, n_points, n_steps, sv, shift, antithetic, &pl, 2);
-    if (rc) return rc;
-    rc = heston_qmc_shape(point_offset, n_points, n_steps)(c, &pl);                  // sequential: the grid over the aligned blocks, no slabs
-    if (rc) return rc;
-    rc = launch_reduce(c, c->stream, c->d_result, -1.0, 2 * kSurfaceCells, pl.grid,
-                       [&](int32_t g, hipStream_t s, const EventPair* timed, const ReduceWs& ws) {
-                           with_bool(pl.anti, [&](auto m) {
-                               launch_timed(heston_qe_qmc_surface_kernel<m>, dim3(g), dim3(kBlock), s, timed, pl.qr, hc, so.cells, pl.d_sv, pl.d_shift,
-                                            ws);
+                           with_bool(pl.anti, [&](auto a) {
+                               if constexpr (Scheme::kBridge) {
+                                   with_bool(pl.bridge, [&](auto b) {
+                                       launch_timed(heston_qmc_surface_kernel<b, a>, dim3(g), dim3(kBlock), s, timed, pl.qr, hc, so.cells, pl.d_sv,
+                                                    pl.d_shift, pl.plan, pl.slabs, ws);
+                                   });
+                               } else {
+                                   launch_timed(heston_qe_qmc_surface_kernel<a>, dim3(g), dim3(kBlock), s, timed, pl.qr, hc, so.cells, pl.d_sv, pl.d_shift,
+                                                ws);
+                               }
                            });
                        });
     if (rc) return rc;
     surface_finish(c->h_result, so, strikes, steps, k, n_points * (pl.anti ? 2 : 1), r, T / n_steps, bad, out);
     return OLMC_OK;
 }
+}  // namespace
+
+extern "C" int olmc_heston_surface(double S, double T, double r, double q, int is_call, double kappa, double theta, double sigma_v, double rho,
+                                   double v0, const double* strikes, const int32_t* steps, int32_t k, int64_t path_offset, int64_t n_local,
+                                   int32_t n_steps, uint64_t seed, int antithetic, olmc_stats* out) {
+    return run_heston_surface<HestonEuler>(S, T, r, q, is_call, {kappa, theta, sigma_v, rho, v0}, strikes, steps, k, path_offset, n_local, n_steps,
+                                           seed, antithetic, out);
+}
+
+extern "C" int olmc_heston_qmc_surface(double S, double T, double r, double q, int is_call, double kappa, double theta, double sigma_v,
+                                       double rho, double v0, const double* strikes, const int32_t* steps, int32_t k, int construction,
+                                       int64_t point_offset, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift,
+                                       int32_t bits, int antithetic, olmc_stats* out) {
+    return run_heston_qmc_surface<HestonEuler>(S, T, r, q, is_call, {kappa, theta, sigma_v, rho, v0}, strikes, steps, k, construction, point_offset,
+                                               n_points, n_steps, sv, shift, bits, antithetic, out);
+}
+
+// ====================================================== Heston, quadratic-exponential scheme ====
+// olmc_heston_surface / olmc_heston_paths and their Sobol forms with Andersen's QE step in place of the Euler one (include/olmc.h
+// "Heston, quadratic-exponential scheme"): the same checks, ranges, cells and read-out (HestonQe), one launch of the heston_qe_* kernels.
+
+extern "C" int olmc_heston_qe_surface(double S, double T, double r, double q, int is_call, double kappa, double theta, double sigma_v, double rho,
+                                      double v0, const double* strikes, const int32_t* steps, int32_t k, int64_t path_offset, int64_t n_local,
+                                      int32_t n_steps, uint64_t seed, int antithetic, olmc_stats* out) {
+    return run_heston_surface<HestonQe>(S, T, r, q, is_call, {kappa, theta, sigma_v, rho, v0}, strikes, steps, k, path_offset, n_local, n_steps, seed,
+                                        antithetic, out);
+}
+
+extern "C" int olmc_heston_qe_qmc_surface(double S, double T, double r, double q, int is_call, double kappa, double theta, double sigma_v,
+                                          double rho, double v0, const double* strikes, const int32_t* steps, int32_t k, int construction,
+                                          int64_t point_offset, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift,
+                                          int32_t bits, int antithetic, olmc_stats* out) {
+    return run_heston_qmc_surface<HestonQe>(S, T, r, q, is_call, {kappa, theta, sigma_v, rho, v0}, strikes, steps, k, construction, point_offset,
+                                            n_points, n_steps, sv, shift, bits, antithetic, out);
+}
 
 extern "C" int olmc_heston_qe_paths(double S, double T, double r, double q, double kappa, double theta, double sigma_v, double rho, double v0,
                                     int64_t n_paths, int32_t n_steps, uint64_t seed, int path_major, double* spot_host, double* var_host) {
-    if (!spot_host || !var_host) return fail(OLMC_ERR_ARG, "null pointer");
-    int rc = heston_qe_check(kappa, theta, sigma_v, rho, v0);
-    if (rc) return rc;
-    const double bytes = 8.0 * static_cast<double>(n_paths) * (n_steps + 1.0);
-    CtxLease lease;
-    rc = matrix_prologue(n_paths, n_steps, 2 * bytes, "path matrices would exceed 64 GB", &lease);
-    if (rc) return rc;
-    DeviceCtx* const c = lease.c;
-    double* d_spot = static_cast<double*>(c->d_bulk);
-    double* d_var = d_spot + static_cast<size_t>(n_paths) * (n_steps + 1);
-    const HestonQeContract hc = make_heston_qe(S, T, r, q, 1, kappa, theta, sigma_v, rho, v0, n_steps);
-    const PathRange pr = make_range(0, n_paths, n_steps, seed);
-    EventPair ep{};
-    const EventPair* timed = nullptr;                  // profiling on: the path kernel counts in olmc_kernel_time, as olmc_heston_paths'
-    rc = prof_pair(c, &ep, &timed);
-    if (rc) return rc;
-    with_bool(path_major != 0, [&](auto pm) {
-        launch_timed(heston_qe_paths_kernel<pm>, dim3(grid_for(n_paths)), dim3(kBlock), c->stream, timed, pr, hc, S, d_spot, d_var);
-    });
-    HIP_TRY(hipGetLastError());
-    rc = copy_to_host(c, spot_host, d_spot, static_cast<size_t>(bytes));
-    if (rc) return rc;
-    return copy_to_host(c, var_host, d_var, static_cast<size_t>(bytes));
+    return run_heston_paths<HestonQe>(S, T, r, q, {kappa, theta, sigma_v, rho, v0}, n_paths, n_steps, seed, path_major, spot_host, var_host);
 }
 
 extern "C" int olmc_heston_qe_qmc_paths(double S, double T, double r, double q, double kappa, double theta, double sigma_v, double rho, double v0,
                                         int construction, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift,
                                         int32_t bits, int path_major, double* spot_host, double* var_host) {
-    if (!spot_host || !var_host) return fail(OLMC_ERR_ARG, "null pointer");
-    int rc = heston_qe_check(kappa, theta, sigma_v, rho, v0);
-    if (rc) return rc;
-    rc = heston_qe_sequential(construction);
-    if (rc) return rc;
-    const double bytes = 8.0 * static_cast<double>(n_points) * (n_steps + 1.0);
-    CtxLease lease;
-    rc = qmc_matrix_prologue(construction, n_points, n_steps, sv, shift, bits, 2 * bytes, &lease, true, 2);
-    if (rc) return rc;
-    DeviceCtx* const c = lease.c;
-    double* d_spot = static_cast<double*>(c->d_bulk);
-    double* d_var = d_spot + static_cast<size_t>(n_points) * (n_steps + 1);
-    const HestonQeContract hc = make_heston_qe(S, T, r, q, 1, kappa, theta, sigma_v, rho, v0, n_steps);
-    QmcPathLaunch pl;
-    rc = qmc_path_setup(c, construction, 0, n_points, n_steps, sv, shift, 0, &pl, 2);
-    if (rc) return rc;
-    const int32_t grid = qmc_block_grid((n_points + kWave - 1) / kWave);
-    EventPair ep{};
-    const EventPair* timed = nullptr;
-    rc = prof_pair(c, &ep, &timed);
-    if (rc) return rc;
-    with_bool(path_major != 0, [&](auto pm) {
-        launch_timed(heston_qe_qmc_paths_kernel<pm>, dim3(grid), dim3(kBlock), c->stream, timed, pl.qr, hc, S, pl.d_sv, pl.d_shift, d_spot, d_var);
-    });
-    HIP_TRY(hipGetLastError());
-    rc = copy_to_host(c, spot_host, d_spot, static_cast<size_t>(bytes));
-    if (rc) return rc;
-    return copy_to_host(c, var_host, d_var, static_cast<size_t>(bytes));
+    return run_heston_qmc_paths<HestonQe>(S, T, r, q, {kappa, theta, sigma_v, rho, v0}, construction, n_points, n_steps, sv, shift, bits, path_major,
+                                          spot_host, var_host);
 }
 
 // ====================================================== structured products under Heston ====
@@ -2809,44 +2797,33 @@ extern "C" int olmc_heston_qe_qmc_paths(double S, double T, double r, double q, 
 // scheme's own entry points, one launch of heston_product_kernel, heston_qmc_product_kernel, heston_qe_product_kernel or
 // heston_qe_qmc_product_kernel with the product as the policy.
 namespace {
-int heston_scheme_check(int scheme, double kappa, double theta, double sigma_v, double rho, double v0) {
-    if (scheme == OLMC_HESTON_EULER) return heston_check(rho);
-    if (scheme == OLMC_HESTON_QE) return heston_qe_check(kappa, theta, sigma_v, rho, v0);
-    return fail(OLMC_ERR_ARG, "bad scheme (OLMC_HESTON_EULER or OLMC_HESTON_QE)");
+int heston_scheme_check(int scheme, const HestonModel& m) {
+    if (scheme != OLMC_HESTON_EULER && scheme != OLMC_HESTON_QE) return fail(OLMC_ERR_ARG, "bad scheme (OLMC_HESTON_EULER or OLMC_HESTON_QE)");
+    return with_heston_scheme(scheme, [&](auto s) { return decltype(s)::check(m); });
 }
-
-struct HestonModel {
-    double kappa, theta, sigma_v, rho, v0;
-    bool nan() const { return std::isnan(kappa + theta + sigma_v + rho + v0); }
-};
 
 // Philox: paths [path_offset, path_offset + n_local) of olmc_heston's stream (Euler) / olmc_heston_qe_surface's (QE).
 template <template <bool> class Product>
 int run_heston_product(double S, double T, double r, double q, const HestonModel& m, int scheme, const typename Product<false>::Contract& pc,
                        double r_for_discount, bool bad, int64_t path_offset, int64_t n_local, int32_t n_steps, uint64_t seed, int antithetic,
                        olmc_stats* out) {
-    if (scheme == OLMC_HESTON_QE) {
-        const HestonQeContract hc = make_heston_qe(S, T, r, q, 1, m.kappa, m.theta, m.sigma_v, m.rho, m.v0, n_steps);
+    return with_heston_scheme(scheme, [&](auto s) {
+        using Scheme = decltype(s);
+        const auto hc = Scheme::make(S, T, r, q, 1, m, n_steps);
         return run_structured(path_offset, n_local, n_steps, seed, antithetic, r_for_discount, T, bad, out,
                               [&](int32_t grid, hipStream_t st, const EventPair* timed, const PathRange& pr, const ReduceWs& ws) {
                                   with_bool(antithetic != 0, [&](auto a) {
-                                      launch_timed(heston_qe_product_kernel<Product, a>, dim3(grid), dim3(kBlock), st, timed, pr, hc, pc, ws);
+                                      launch_timed(Scheme::template product_kernel<Product, decltype(a)::value>(), dim3(grid), dim3(kBlock), st, timed, pr,
+                                                   hc, pc, ws);
                                   });
                               });
-    }
-    const HestonContract hc = make_heston(S, 0.0, T, r, q, 1, m.kappa, m.theta, m.sigma_v, m.rho, m.v0, n_steps);
-    return run_structured(path_offset, n_local, n_steps, seed, antithetic, r_for_discount, T, bad, out,
-                          [&](int32_t grid, hipStream_t st, const EventPair* timed, const PathRange& pr, const ReduceWs& ws) {
-                              with_bool(antithetic != 0, [&](auto a) {
-                                  launch_timed(heston_product_kernel<Product, a>, dim3(grid), dim3(kBlock), st, timed, pr, hc, pc, ws);
-                              });
-                          });
+    });
 }
 
 // The checks of a Sobol call that do not depend on the product, in the order of olmc_heston_qe_qmc_surface.
 int heston_qmc_product_check(int scheme, const HestonModel& m, int construction, int64_t point_offset, int64_t n_points, int32_t n_steps,
                              const uint32_t* sv, const uint32_t* shift, int32_t bits) {
-    int rc = heston_scheme_check(scheme, m.kappa, m.theta, m.sigma_v, m.rho, m.v0);
+    int rc = heston_scheme_check(scheme, m);
     if (rc) return rc;
     if (scheme == OLMC_HESTON_QE) {
         rc = heston_qe_sequential(construction);
@@ -2855,33 +2832,31 @@ int heston_qmc_product_check(int scheme, const HestonModel& m, int construction,
     return qmc_path_check(construction, point_offset, n_points, n_steps, sv, shift, bits, 2);
 }
 
-// Sobol: points [point_offset, point_offset + n_points) of olmc_heston_qmc's construction (Euler) / olmc_heston_qe_qmc_surface's (QE).
+// Sobol: points [point_offset, point_offset + n_points) of olmc_heston_qmc's construction (Euler) / olmc_heston_qe_qmc_surface's (QE:
+// sequential, the grid over the aligned blocks, no slabs).
 template <template <bool> class Product>
 int run_heston_qmc_product(double S, double T, double r, double q, const HestonModel& m, int scheme, const typename Product<false>::Contract& pc,
                            double r_for_discount, bool bad, int construction, int64_t point_offset, int64_t n_points, int32_t n_steps,
                            const uint32_t* sv, const uint32_t* shift, int antithetic, olmc_stats* out) {
-    if (scheme == OLMC_HESTON_QE) {
-        const HestonQeContract hc = make_heston_qe(S, T, r, q, 1, m.kappa, m.theta, m.sigma_v, m.rho, m.v0, n_steps);
+    return with_heston_scheme(scheme, [&](auto s) {
+        using Scheme = decltype(s);
+        const auto hc = Scheme::make(S, T, r, q, 1, m, n_steps);
         return run_qmc_payoff(construction, point_offset, n_points, n_steps, sv, shift, antithetic, r_for_discount, T, bad, out,
-                              [&](int32_t g, hipStream_t s, const EventPair* timed, const QmcPathLaunch& pl, const ReduceWs& ws) {
+                              [&](int32_t g, hipStream_t st, const EventPair* timed, const QmcPathLaunch& pl, const ReduceWs& ws) {
                                   with_bool(pl.anti, [&](auto a) {
-                                      launch_timed(heston_qe_qmc_product_kernel<Product, a>, dim3(g), dim3(kBlock), s, timed, pl.qr, hc, pc, pl.d_sv,
-                                                   pl.d_shift, ws);
+                                      if constexpr (Scheme::kBridge) {
+                                          with_bool(pl.bridge, [&](auto b) {
+                                              launch_timed(heston_qmc_product_kernel<Product, b, a>, dim3(g), dim3(kBlock), st, timed, pl.qr, hc, pc,
+                                                           pl.d_sv, pl.d_shift, pl.plan, pl.slabs, ws);
+                                          });
+                                      } else {
+                                          launch_timed(heston_qe_qmc_product_kernel<Product, a>, dim3(g), dim3(kBlock), st, timed, pl.qr, hc, pc, pl.d_sv,
+                                                       pl.d_shift, ws);
+                                      }
                                   });
                               },
-                              2, heston_qmc_shape(point_offset, n_points, n_steps));      // sequential: the grid over the aligned blocks, no slabs
-    }
-    const HestonContract hc = make_heston(S, 0.0, T, r, q, 1, m.kappa, m.theta, m.sigma_v, m.rho, m.v0, n_steps);
-    return run_qmc_payoff(construction, point_offset, n_points, n_steps, sv, shift, antithetic, r_for_discount, T, bad, out,
-                          [&](int32_t g, hipStream_t s, const EventPair* timed, const QmcPathLaunch& pl, const ReduceWs& ws) {
-                              with_bool(pl.bridge, [&](auto b) {
-                                  with_bool(pl.anti, [&](auto a) {
-                                      launch_timed(heston_qmc_product_kernel<Product, b, a>, dim3(g), dim3(kBlock), s, timed, pl.qr, hc, pc, pl.d_sv,
-                                                   pl.d_shift, pl.plan, pl.slabs, ws);
-                                  });
-                              });
-                          },
-                          2, heston_qmc_shape(point_offset, n_points, n_steps));
+                              2, heston_qmc_shape(point_offset, n_points, n_steps));
+    });
 }
 }  // namespace
 
@@ -2890,11 +2865,11 @@ extern "C" int olmc_heston_autocallable(double S, double T, double r, double q, 
                                         int32_t observation_freq, int scheme, int64_t path_offset, int64_t n_local, int32_t n_steps,
                                         uint64_t seed, int antithetic, olmc_stats* out) {
     if (!out) return fail(OLMC_ERR_ARG, "null pointer");
-    int rc = heston_scheme_check(scheme, kappa, theta, sigma_v, rho, v0);
+    const HestonModel m{kappa, theta, sigma_v, rho, v0};
+    int rc = heston_scheme_check(scheme, m);
     if (rc) return rc;
     rc = autocall_check(observation_freq, n_steps);
     if (rc) return rc;
-    const HestonModel m{kappa, theta, sigma_v, rho, v0};
     const AutocallSetup a = make_autocall(S, T, r, 0.0, q, autocall_barrier, coupon_barrier, coupon_rate, ki_barrier, observation_freq, n_steps);
     // payoffs are already discounted path by path, as olmc_autocallable's: no outer discount
     return run_heston_product<HestonAutocall>(S, T, r, q, m, scheme, a.ac, 0.0, a.bad || m.nan(), path_offset, n_local, n_steps, seed, antithetic, out);
@@ -2920,11 +2895,11 @@ extern "C" int olmc_heston_cliquet(double S, double T, double r, double q, doubl
                                    double local_cap, double local_floor, double global_cap, double global_floor, int32_t n_periods, int scheme,
                                    int64_t path_offset, int64_t n_local, int32_t n_steps, uint64_t seed, int antithetic, olmc_stats* out) {
     if (!out) return fail(OLMC_ERR_ARG, "null pointer");
-    int rc = heston_scheme_check(scheme, kappa, theta, sigma_v, rho, v0);
+    const HestonModel m{kappa, theta, sigma_v, rho, v0};
+    int rc = heston_scheme_check(scheme, m);
     if (rc) return rc;
     rc = cliquet_check(n_periods, n_steps);
     if (rc) return rc;
-    const HestonModel m{kappa, theta, sigma_v, rho, v0};
     const CliquetContract cc = make_cliquet(S, T, r, 0.0, q, local_cap, local_floor, global_cap, global_floor, n_periods, n_steps);
     const bool bad = cliquet_poisoned(S, T, r, 0.0, q, local_cap, local_floor, global_cap, global_floor) || m.nan();
     return run_heston_product<HestonCliquet>(S, T, r, q, m, scheme, cc, r, bad, path_offset, n_local, n_steps, seed, antithetic, out);

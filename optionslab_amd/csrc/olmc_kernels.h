@@ -2211,6 +2211,14 @@ struct HestonStep {
         ls = __builtin_fma(sv, SIGN > 0 ? u : -u, __builtin_fma(neg_half_dt, v, ls));
         v = fmax(__builtin_fma(sv, SIGN > 0 ? w : -w, __builtin_fma(v, one_minus_kdt, kdt_theta)), 0.0);
     }
+    // One step of a path and (ANTI) its mirror from the step's two normals, in the unit this was built for; leg 1 is untouched without ANTI.
+    template <bool ANTI>
+    __device__ __forceinline__ void legs(double z1, double z2, double (&ls)[2], double (&v)[2]) const {
+        const double u = zs * z1;
+        const double w = __builtin_fma(b, z2, a * z1);
+        advance<1>(u, w, ls[0], v[0]);
+        if constexpr (ANTI) advance<-1>(u, w, ls[1], v[1]);
+    }
 };
 
 // v0 < 0 never comes through HestonPricer (heston.py:71-72 rejects it); at the C ABI the reference's recursion
@@ -2220,6 +2228,36 @@ __device__ __forceinline__ bool heston_start(const HestonContract& c, double& v)
     if (c.v0 >= 0.0) { v = c.v0; return false; }
     v = fmax(c.v0 + c.kappa_dt * c.theta, 0.0);
     return true;
+}
+
+// A Philox block of a Heston stream under the launch's keys: pinned in VGPRs (RoundKeys), or the launch's scalars where the
+// kernel is bound by its stores (the path-matrix kernels).
+struct LaunchKeys {
+    uint32_t k0, k1;
+};
+__device__ __forceinline__ Words4 heston_words(uint32_t g_lo, uint32_t g_hi, int32_t block, uint32_t tag, const RoundKeys& rk) {
+    return philox4x32_10_pinned(g_lo, g_hi, static_cast<uint32_t>(block), tag, rk);
+}
+__device__ __forceinline__ Words4 heston_words(uint32_t g_lo, uint32_t g_hi, int32_t block, uint32_t tag, const LaunchKeys& k) {
+    return philox4x32_10(g_lo, g_hi, static_cast<uint32_t>(block), tag, k.k0, k.k1);
+}
+
+// Steps t = 0 .. last - 1 of a path on the Euler stream, one block for two steps: body(t, z1, z2, advance) with the step's RAW
+// normals; advance = false where heston_start took the step.
+template <typename Keys, typename Body>
+__device__ __forceinline__ void heston_philox_walk(uint32_t g_lo, uint32_t g_hi, const Keys& keys, int32_t last, bool skip0, Body body) {
+    const int32_t blocks = (last + 1) >> 1;
+    for (int32_t b = 0; b < blocks; ++b) {
+        const Words4 w = heston_words(g_lo, g_hi, b, kTagHeston, keys);
+        float z[4];
+        box_muller_raw(w.x0, w.x1, z[0], z[1]);
+        box_muller_raw(w.x2, w.x3, z[2], z[3]);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int32_t t = 2 * b + h;
+            if (t < last) body(t, static_cast<double>(z[2 * h]), static_cast<double>(z[2 * h + 1]), !(skip0 && t == 0));
+        }
+    }
 }
 
 template <bool ANTI>
@@ -2242,13 +2280,7 @@ __global__ __launch_bounds__(kBlock) void heston_kernel(PathRange pr, HestonCont
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 const int32_t t = 2 * b + h;
-                if (t < pr.n_steps && !(skip0 && t == 0)) {
-                    const double z1 = static_cast<double>(z[2 * h]);
-                    const double u = hs.zs * z1;
-                    const double w = __builtin_fma(hs.b, static_cast<double>(z[2 * h + 1]), hs.a * z1);
-                    hs.advance<1>(u, w, ls[0], v[0]);
-                    if constexpr (ANTI) hs.advance<-1>(u, w, ls[1], v[1]);
-                }
+                if (t < pr.n_steps && !(skip0 && t == 0)) hs.legs<ANTI>(static_cast<double>(z[2 * h]), static_cast<double>(z[2 * h + 1]), ls, v);
             }
         }
 #pragma unroll
@@ -2269,27 +2301,15 @@ __global__ __launch_bounds__(kBlock) void heston_paths_kernel(PathRange pr, Hest
     double v_start;
     const bool skip0 = heston_start(c, v_start);
     for_each_path(pr, [&](int64_t i, uint32_t g_lo, uint32_t g_hi) {
-        double ls = c.log_s0, v = v_start;       // ls WITHOUT the (r - q) dt terms: added per date below
+        double ls[2] = {c.log_s0, c.log_s0}, v[2] = {v_start, v_start};       // leg 0 only; ls WITHOUT the (r - q) dt terms: added per date below
         spot[path_at<PATH_MAJOR>(i, 0, pr.count, pr.n_steps)] = s_first;
         var[path_at<PATH_MAJOR>(i, 0, pr.count, pr.n_steps)] = c.v0;
-        const int32_t blocks = (pr.n_steps + 1) >> 1;
-        for (int32_t b = 0; b < blocks; ++b) {
-            float z[4];
-            raw_normals4(g_lo, g_hi, static_cast<uint32_t>(b), kTagHeston, pr.key0, pr.key1, z);
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int32_t t = 2 * b + h;
-                if (t < pr.n_steps) {
-                    if (!(skip0 && t == 0)) {
-                        const double z1 = static_cast<double>(z[2 * h]);
-                        hs.advance<1>(hs.zs * z1, __builtin_fma(hs.b, static_cast<double>(z[2 * h + 1]), hs.a * z1), ls, v);
-                    }
-                    const size_t at = path_at<PATH_MAJOR>(i, t + 1, pr.count, pr.n_steps);
-                    spot[at] = exp(__builtin_fma(static_cast<double>(t + 1), c.mu_dt, ls));
-                    var[at] = v;
-                }
-            }
-        }
+        heston_philox_walk(g_lo, g_hi, LaunchKeys{pr.key0, pr.key1}, pr.n_steps, skip0, [&](int32_t t, double z1, double z2, bool advance) {
+            if (advance) hs.legs<false>(z1, z2, ls, v);
+            const size_t at = path_at<PATH_MAJOR>(i, t + 1, pr.count, pr.n_steps);
+            spot[at] = exp(__builtin_fma(static_cast<double>(t + 1), c.mu_dt, ls[0]));
+            var[at] = v[0];
+        });
     });
 }
 
@@ -3592,10 +3612,12 @@ struct QmcLanePoint {
     }
 };
 
-// body(t, z_{2t}, z_{2t+1}) for t = 0 .. n - 1 in every lane: the two normals of step t (sequential) / of node t (bridge).
-template <typename Body>
-__device__ __forceinline__ void heston_qmc_normals(const uint32_t* __restrict__ sv, const uint32_t* __restrict__ shift, int32_t n, int lane,
-                                                   const QmcLanePoint& lp, Body body) {
+// body(t, p_{2t}, z_{2t+1}) for t = 0 .. n - 1 in every lane, one fold of the block's common Gray bits per 64 dimensions, a broadcast
+// plus the lane's six low rows per dimension.  EVEN_NORMAL: p is the normal z_{2t} -- with z_{2t+1} the two normals of step t
+// (sequential) / of node t (bridge); else the even dimension is left a uniform (sobol_uniform's clipped value: the QE kernels).
+template <bool EVEN_NORMAL, typename Body>
+__device__ __forceinline__ void heston_qmc_draws(const uint32_t* __restrict__ sv, const uint32_t* __restrict__ shift, int32_t n, int lane,
+                                                 const QmcLanePoint& lp, Body body) {
     const int32_t dims = 2 * n;
     for (int32_t c0 = 0; c0 < dims; c0 += kWave) {
         const int32_t tl = c0 + lane < dims ? c0 + lane : dims - 1;
@@ -3605,16 +3627,17 @@ __device__ __forceinline__ void heston_qmc_normals(const uint32_t* __restrict__ 
         for (int b = 6; b < kSobolBits; ++b) fold ^= mine[b] & (0u - ((lp.gray_hi >> b) & 1u));
         const int32_t cn = dims - c0 < kWave ? dims - c0 : kWave;            // even: dims and kWave are
         for (int32_t d = 0; d < cn; d += 2) {
-            double z[2];
+            double p[2];
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 const uint32_t* __restrict__ row = sv + static_cast<size_t>(c0 + d + h) * kSobolBits;
                 uint32_t x = static_cast<uint32_t>(__shfl(static_cast<int>(fold), d + h, kWave));
 #pragma unroll
                 for (int b = 0; b < 6; ++b) x = __builtin_amdgcn_bitop3_b32(x, row[b], lp.mask[b], 0x78);   // x ^ (row & mask)
-                z[h] = ndtri_w_add(0.0, sobol_uniform(x), opaque_zero());
+                p[h] = sobol_uniform(x);
+                if (EVEN_NORMAL || h == 1) p[h] = ndtri_w_add(0.0, p[h], opaque_zero());
             }
-            body((c0 + d) >> 1, z[0], z[1]);
+            body((c0 + d) >> 1, p[0], p[1]);
         }
     }
 }
@@ -3624,7 +3647,7 @@ __device__ __forceinline__ void heston_qmc_normals(const uint32_t* __restrict__ 
 template <typename At>
 __device__ __forceinline__ void heston_qmc_bridge_fill(const uint32_t* __restrict__ sv, const uint32_t* __restrict__ shift, const QmcBridgePlan& plan,
                                                        int32_t n, int lane, const QmcLanePoint& lp, bool live, double* w1, double* w2, At at) {
-    heston_qmc_normals(sv, shift, n, lane, lp, [&](int32_t k, double z1, double z2) {
+    heston_qmc_draws<true>(sv, shift, n, lane, lp, [&](int32_t k, double z1, double z2) {
         if (k == 0) {
             const double sq = sqrt(static_cast<double>(n));
             if (live) { w1[at(n)] = sq * z1; w2[at(n)] = sq * z2; }
@@ -3665,6 +3688,23 @@ __device__ __forceinline__ void heston_qmc_bridge_sweep(int32_t n, const double*
     }
 }
 
+// The wave's blocks of 64 points, aligned in the ABSOLUTE point index: body(slot, lane, k, live, lp) per block with the lane's point k,
+// whether the shard holds it, and its Gray bits.  slot is the wave's place in the grid (its bridge slab).  Wave-uniform.
+template <typename Body>
+__device__ __forceinline__ void heston_point_blocks(const QmcRange& qr, Body body) {
+    const int lane = static_cast<int>(threadIdx.x) & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) / kWave);
+    const uint64_t base = qr.first & ~static_cast<uint64_t>(kWave - 1);
+    const uint64_t end = qr.first + static_cast<uint64_t>(qr.count);
+    const int64_t n_blocks = static_cast<int64_t>((end - base + kWave - 1) / kWave);
+    const int64_t stride = static_cast<int64_t>(gridDim.x) * kWavesPerBlock;
+    const int64_t slot = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave;
+    for (int64_t blk = slot; blk < n_blocks; blk += stride) {
+        const uint64_t k = base + static_cast<uint64_t>(blk) * kWave + lane;
+        body(slot, lane, k, k >= qr.first && k < end, QmcLanePoint(static_cast<uint32_t>(k)));
+    }
+}
+
 // Resources (tools/kernel_meta.sh, gfx950; no scratch, no spills): VGPRs 88 / 78 (sequential: plain / antithetic), 117 / 109 (bridge); LDS
 // 64 B (the reduction); the bridge's slabs are global memory of the library (olmc.hip: heston_slabs).
 template <bool BRIDGE, bool ANTI>
@@ -3689,11 +3729,7 @@ __global__ __launch_bounds__(kBlock) void heston_qmc_kernel(QmcRange qr, HestonC
         const QmcLanePoint lp(static_cast<uint32_t>(k));
         double ls[2] = {ls_start, ls_start}, v[2] = {v_start, v_start};
         auto step = [&](int32_t t, double z1, double z2) {
-            if (skip0 && t == 0) return;
-            const double u = hs.zs * z1;
-            const double w = __builtin_fma(hs.b, z2, hs.a * z1);
-            hs.advance<1>(u, w, ls[0], v[0]);
-            if constexpr (ANTI) hs.advance<-1>(u, w, ls[1], v[1]);
+            if (!(skip0 && t == 0)) hs.legs<ANTI>(z1, z2, ls, v);
         };
         if constexpr (BRIDGE) {
             double* w1 = slabs + static_cast<size_t>(slot) * (2 * static_cast<size_t>(n) * kWave);
@@ -3702,7 +3738,7 @@ __global__ __launch_bounds__(kBlock) void heston_qmc_kernel(QmcRange qr, HestonC
             heston_qmc_bridge_fill(sv, shift, plan, n, lane, lp, live, w1, w2, at);
             if (live) heston_qmc_bridge_sweep(n, w1, w2, at, step);
         } else {
-            heston_qmc_normals(sv, shift, n, lane, lp, step);
+            heston_qmc_draws<true>(sv, shift, n, lane, lp, step);
         }
         if (live) {
 #pragma unroll
@@ -3735,20 +3771,20 @@ __global__ __launch_bounds__(kBlock) void heston_qmc_paths_kernel(QmcRange qr, H
         const bool live = i < count;
         const QmcLanePoint lp(static_cast<uint32_t>(i));
         auto at = [&](int32_t t) { return path_at<PATH_MAJOR>(i, t, count, n); };
-        double ls = c.log_s0, v = v_start;                                   // ls WITHOUT the (r - q) dt terms: added per date below
+        double ls[2] = {c.log_s0, c.log_s0}, v[2] = {v_start, v_start};       // leg 0 only; ls WITHOUT the (r - q) dt terms: added per date below
         auto step = [&](int32_t t, double z1, double z2) {
-            if (!(skip0 && t == 0)) hs.advance<1>(hs.zs * z1, __builtin_fma(hs.b, z2, hs.a * z1), ls, v);
+            if (!(skip0 && t == 0)) hs.legs<false>(z1, z2, ls, v);
             if (live) {
                 const size_t p = at(t + 1);
-                spot[p] = exp(__builtin_fma(static_cast<double>(t + 1), c.mu_dt, ls));
-                var[p] = v;
+                spot[p] = exp(__builtin_fma(static_cast<double>(t + 1), c.mu_dt, ls[0]));
+                var[p] = v[0];
             }
         };
         if constexpr (BRIDGE) {
             heston_qmc_bridge_fill(sv, shift, plan, n, lane, lp, live, spot, var, at);
             if (live) heston_qmc_bridge_sweep(n, spot, var, at, step);
         } else {
-            heston_qmc_normals(sv, shift, n, lane, lp, step);
+            heston_qmc_draws<true>(sv, shift, n, lane, lp, step);
         }
         if (live) { spot[at(0)] = s_first; var[at(0)] = c.v0; }
     }
@@ -3782,12 +3818,7 @@ struct HestonPathLegs {
     }
     // step t (normals z1, z2 in the unit hs was built for), then date t + 1 into every leg; advance = false: heston_start took the step
     __device__ __forceinline__ void date(int32_t t, double z1, double z2, bool advance) {
-        if (advance) {
-            const double u = hs.zs * z1;
-            const double w = __builtin_fma(hs.b, z2, hs.a * z1);
-            hs.advance<1>(u, w, ls[0], v[0]);
-            if constexpr (ANTI) hs.advance<-1>(u, w, ls[1], v[1]);
-        }
+        if (advance) hs.template legs<ANTI>(z1, z2, ls, v);
         const double td = static_cast<double>(t + 1);
 #pragma unroll
         for (int l = 0; l < (ANTI ? 2 : 1); ++l) qmc_leg_add<FAMILY>(leg[l], __builtin_fma(td, mu_unit, ls[l]));
@@ -3866,7 +3897,7 @@ __global__ __launch_bounds__(kBlock) void heston_qmc_path_kernel(QmcRange qr, He
             heston_qmc_bridge_fill(sv, shift, plan, n, lane, lp, live, w1, w2, at);
             if (live) heston_qmc_bridge_sweep(n, w1, w2, at, step);
         } else {
-            heston_qmc_normals(sv, shift, n, lane, lp, step);
+            heston_qmc_draws<true>(sv, shift, n, lane, lp, step);
         }
         if (live) p.payoffs(ec, inv_steps, n, acc);
     }
@@ -3982,11 +4013,7 @@ __global__ __launch_bounds__(kBlock) void heston_surface_kernel(PathRange pr, He
                 const int32_t t = 2 * b + h;
                 if (t < cells.last) {
                     if (!(skip0 && t == 0)) {
-                        const double z1 = static_cast<double>(z[2 * h]);
-                        const double u = hs.zs * z1;
-                        const double w = __builtin_fma(hs.b, static_cast<double>(z[2 * h + 1]), hs.a * z1);
-                        hs.advance<1>(u, w, ls[0], v[0]);
-                        if constexpr (ANTI) hs.advance<-1>(u, w, ls[1], v[1]);
+                        hs.legs<ANTI>(static_cast<double>(z[2 * h]), static_cast<double>(z[2 * h + 1]), ls, v);
                     }
                     rows.read_out<LEGS>(next, pending, t + 1, c.mu_dt, c.sign, ls, live);
                 }
@@ -4029,12 +4056,7 @@ __global__ __launch_bounds__(kBlock) void heston_qmc_surface_kernel(QmcRange qr,
         double ls[2] = {c.log_s0, c.log_s0}, v[2] = {v_start, v_start};       // ls WITHOUT the (r - q) dt terms
         int32_t next = 0, pending = cells.step[0];
         auto step = [&](int32_t t, double z1, double z2) {
-            if (!(skip0 && t == 0)) {
-                const double u = hs.zs * z1;
-                const double w = __builtin_fma(hs.b, z2, hs.a * z1);
-                hs.advance<1>(u, w, ls[0], v[0]);
-                if constexpr (ANTI) hs.advance<-1>(u, w, ls[1], v[1]);
-            }
+            if (!(skip0 && t == 0)) hs.legs<ANTI>(z1, z2, ls, v);
             rows.read_out<LEGS>(next, pending, t + 1, c.mu_dt, c.sign, ls, live);
         };
         if constexpr (BRIDGE) {
@@ -4044,7 +4066,7 @@ __global__ __launch_bounds__(kBlock) void heston_qmc_surface_kernel(QmcRange qr,
             heston_qmc_bridge_fill(sv, shift, plan, n, lane, lp, true, w1, w2, at);
             heston_qmc_bridge_sweep(cells.last, w1, w2, at, step);
         } else {
-            heston_qmc_normals(sv, shift, cells.last, lane, lp, step);
+            heston_qmc_draws<true>(sv, shift, cells.last, lane, lp, step);
         }
     }
     rows.reduce(ws);
@@ -4150,10 +4172,27 @@ struct HestonQeStep {
         ls = __builtin_fma(sd, SIGN > 0 ? z_s : -z_s, __builtin_fma(k2, vn, __builtin_fma(k1, v, ls)));
         v = vn;
     }
+    // One step of a path and (ANTI) its mirror from draws that are all at hand (Philox); leg 1 is untouched without ANTI.
+    template <bool ANTI, typename Uniform>
+    __device__ __forceinline__ void legs(const Uniform& draw, double z_v, double z_s, double (&ls)[2], double (&v)[2]) const {
+        advance<1>(moments(v[0]), draw, z_v, z_s, ls[0], v[0]);
+        if constexpr (ANTI) advance<-1>(moments(v[1]), draw, z_v, z_s, ls[1], v[1]);
+    }
 };
 
-// Philox: lane per path, ONE block per step -- counter (path_lo, path_hi, t, kTagHestonQe): (x0, x1) -> box_muller_raw -> (Z_v, Z_s),
-// x2 -> U_v, x3 unused.  heston_surface_kernel's skeleton, cell rows and read-out; a single-cell launch at step n is the European price.
+// The draws of step t of a path on the QE stream, ONE block per step -- counter (path_lo, path_hi, t, kTagHestonQe): (x0, x1) ->
+// box_muller_raw -> (Z_v, Z_s) RAW, x2 -> U_v, x3 unused.
+template <typename Keys>
+__device__ __forceinline__ QeWordUniform heston_qe_philox_draw(uint32_t g_lo, uint32_t g_hi, int32_t t, const Keys& keys, double& z_v, double& z_s) {
+    const Words4 w = heston_words(g_lo, g_hi, t, kTagHestonQe, keys);
+    float zf_v, zf_s;
+    box_muller_raw(w.x0, w.x1, zf_v, zf_s);
+    z_v = static_cast<double>(zf_v);
+    z_s = static_cast<double>(zf_s);
+    return QeWordUniform{w.x2};
+}
+
+// Philox: lane per path, heston_qe_philox_draw per step.  heston_surface_kernel's skeleton, cell rows and read-out; a single-cell launch at step n is the European price.
 // Resources (tools/kernel_meta.sh, gfx950; no scratch, no spills; LDS 3.2 KiB), VGPRs plain / antithetic: 92 / 82 (heston_surface_kernel: 92 / 82).
 template <bool ANTI>
 __global__ __launch_bounds__(kBlock) void heston_qe_surface_kernel(PathRange pr, HestonQeContract c, HestonSurfaceCells cells, ReduceWs ws) {
@@ -4173,12 +4212,9 @@ __global__ __launch_bounds__(kBlock) void heston_qe_surface_kernel(PathRange pr,
         double ls[2] = {c.log_s0, c.log_s0}, v[2] = {c.v0, c.v0};             // ls WITHOUT the drift_dt terms: added per read-out
         int32_t next = 0, pending = cells.step[0];
         for (int32_t t = 0; t < cells.last; ++t) {
-            const Words4 w = philox4x32_10_pinned(pw.lo, pw.hi, static_cast<uint32_t>(t), kTagHestonQe, rk);
-            float z_v, z_s;
-            box_muller_raw(w.x0, w.x1, z_v, z_s);
-            const QeWordUniform draw{w.x2};
-            hs.advance<1>(hs.moments(v[0]), draw, static_cast<double>(z_v), static_cast<double>(z_s), ls[0], v[0]);
-            if constexpr (ANTI) hs.advance<-1>(hs.moments(v[1]), draw, static_cast<double>(z_v), static_cast<double>(z_s), ls[1], v[1]);
+            double z_v, z_s;
+            const QeWordUniform draw = heston_qe_philox_draw(pw.lo, pw.hi, t, rk, z_v, z_s);
+            hs.legs<ANTI>(draw, z_v, z_s, ls, v);
             rows.read_out<LEGS>(next, pending, t + 1, c.drift_dt, c.sign, ls, live);
         }
     }
@@ -4196,10 +4232,9 @@ __global__ __launch_bounds__(kBlock) void heston_qe_paths_kernel(PathRange pr, H
         spot[path_at<PATH_MAJOR>(i, 0, pr.count, pr.n_steps)] = s_first;
         var[path_at<PATH_MAJOR>(i, 0, pr.count, pr.n_steps)] = c.v0;
         for (int32_t t = 0; t < pr.n_steps; ++t) {
-            const Words4 w = philox4x32_10(g_lo, g_hi, static_cast<uint32_t>(t), kTagHestonQe, pr.key0, pr.key1);
-            float z_v, z_s;
-            box_muller_raw(w.x0, w.x1, z_v, z_s);
-            hs.advance<1>(hs.moments(v), QeWordUniform{w.x2}, static_cast<double>(z_v), static_cast<double>(z_s), ls, v);
+            double z_v, z_s;
+            const QeWordUniform draw = heston_qe_philox_draw(g_lo, g_hi, t, LaunchKeys{pr.key0, pr.key1}, z_v, z_s);
+            hs.advance<1>(hs.moments(v), draw, z_v, z_s, ls, v);
             const size_t at = path_at<PATH_MAJOR>(i, t + 1, pr.count, pr.n_steps);
             spot[at] = exp(__builtin_fma(static_cast<double>(t + 1), c.drift_dt, ls));
             var[at] = v;
@@ -4208,9 +4243,10 @@ __global__ __launch_bounds__(kBlock) void heston_qe_paths_kernel(PathRange pr, H
 }
 
 // Sobol, sequential only: dimension 2 t is U_v of step t (sobol_uniform's clipped value; Z_v = its inverse normal, evaluated only
-// where a leg is quadratic -- inverse-transform sampling of v' from ONE uniform), dimension 2 t + 1 gives Z_s.
-// body(t, u_{2t}, z_{2t+1}) for t = 0 .. n - 1 in every lane: heston_qmc_normals' walk (one fold of the common Gray bits per 64
-// dimensions, a broadcast plus the lane's six low rows per dimension) with the even dimension left a uniform.
+// where a leg is quadratic -- inverse-transform sampling of v' from ONE uniform), dimension 2 t + 1 gives Z_s: heston_qmc_draws<false>.
+
+// heston_qmc_draws<false> with the even dimension's hand-over written out, for heston_qe_qmc_product_kernel alone (through the merged walk
+// its antithetic instantiations compile to other code).
 template <typename Body>
 __device__ __forceinline__ void heston_qe_qmc_draws(const uint32_t* __restrict__ sv, const uint32_t* __restrict__ shift, int32_t n, int lane,
                                                     const QmcLanePoint& lp, Body body) {
@@ -4264,23 +4300,15 @@ __global__ __launch_bounds__(kBlock) void heston_qe_qmc_surface_kernel(QmcRange 
     const SurfaceRows rows{stage, cell_strike, cell_step, static_cast<int>(threadIdx.x) & (kWave - 1),
                            __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) / kWave)};
     rows.clear(cells);
-    const int lane = rows.lane;
     const HestonQeStep hs(c, 1.0);
-    const uint64_t base = qr.first & ~static_cast<uint64_t>(kWave - 1);      // blocks aligned in the absolute index
-    const uint64_t end = qr.first + static_cast<uint64_t>(qr.count);
-    const int64_t n_blocks = static_cast<int64_t>((end - base + kWave - 1) / kWave);
-    const int64_t stride = static_cast<int64_t>(gridDim.x) * kWavesPerBlock;
-    for (int64_t blk = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + rows.wave; blk < n_blocks; blk += stride) {      // wave-uniform
-        const uint64_t k = base + static_cast<uint64_t>(blk) * kWave + lane;
-        const bool live = k >= qr.first && k < end;
-        const QmcLanePoint lp(static_cast<uint32_t>(k));
+    heston_point_blocks(qr, [&](int64_t, int lane, uint64_t, bool live, const QmcLanePoint& lp) {
         double ls[2] = {c.log_s0, c.log_s0}, v[2] = {c.v0, c.v0};             // ls WITHOUT the drift_dt terms
         int32_t next = 0, pending = cells.step[0];
-        heston_qe_qmc_draws(sv, shift, cells.last, lane, lp, [&](int32_t t, double u_v, double z_s) {
+        heston_qmc_draws<false>(sv, shift, cells.last, lane, lp, [&](int32_t t, double u_v, double z_s) {
             heston_qe_qmc_step<ANTI>(hs, u_v, z_s, ls, v);
             rows.read_out<LEGS>(next, pending, t + 1, c.drift_dt, c.sign, ls, live);
         });
-    }
+    });
     rows.reduce(ws);
 }
 
@@ -4304,7 +4332,7 @@ __global__ __launch_bounds__(kBlock) void heston_qe_qmc_paths_kernel(QmcRange qr
         const bool live = i < count;
         const QmcLanePoint lp(static_cast<uint32_t>(i));
         double ls[2] = {c.log_s0, c.log_s0}, v[2] = {c.v0, c.v0};             // leg 0 only; ls WITHOUT the drift_dt terms
-        heston_qe_qmc_draws(sv, shift, n, lane, lp, [&](int32_t t, double u_v, double z_s) {
+        heston_qmc_draws<false>(sv, shift, n, lane, lp, [&](int32_t t, double u_v, double z_s) {
             heston_qe_qmc_step<false>(hs, u_v, z_s, ls, v);
             if (live) {
                 const size_t p = path_at<PATH_MAJOR>(i, t + 1, count, n);
@@ -4411,15 +4439,15 @@ struct HestonCliquet {
     }
 };
 
-// The two legs of a path under a product.  Euler: heston_path_kernel's date (HestonPathLegs, unit 1); QE: the surface kernels' step.
+// The two legs of a path under a product: ls relative to ln S, v, and the policy.  drift_dt is the scheme's per-date constant ((r - q) dt
+// under Euler, (r - q) dt + K0 under QE); the scheme's step advances ls and v from outside.
 template <typename Product, bool ANTI>
-struct HestonProductLegs {
+struct ProductLegs {
     static constexpr int LEGS = ANTI ? 2 : 1;
-    HestonStep hs;
-    double mu_dt;
+    double drift_dt;
     double ls[2], v[2];
     Product p;
-    __device__ __forceinline__ HestonProductLegs(const HestonContract& c, double z_unit) : hs(c, z_unit), mu_dt(c.mu_dt) {}
+    __device__ __forceinline__ explicit ProductLegs(double drift) : drift_dt(drift) {}
     __device__ __forceinline__ void start(const typename Product::Contract& pc, double v_start) {
 #pragma unroll
         for (int l = 0; l < 2; ++l) { ls[l] = 0.0; v[l] = v_start; }
@@ -4429,16 +4457,10 @@ struct HestonProductLegs {
         const double td = static_cast<double>(date);
         x[1] = 0.0;
 #pragma unroll
-        for (int l = 0; l < LEGS; ++l) x[l] = __builtin_fma(td, mu_dt, ls[l]);
+        for (int l = 0; l < LEGS; ++l) x[l] = __builtin_fma(td, drift_dt, ls[l]);
     }
-    // step t (normals z1, z2 in the unit hs was built for), then date t + 1; advance = false: heston_start took the step
-    __device__ __forceinline__ void date(const typename Product::Contract& pc, int32_t t, double z1, double z2, bool advance) {
-        if (advance) {
-            const double u = hs.zs * z1;
-            const double w = __builtin_fma(hs.b, z2, hs.a * z1);
-            hs.advance<1>(u, w, ls[0], v[0]);
-            if constexpr (ANTI) hs.advance<-1>(u, w, ls[1], v[1]);
-        }
+    // after step t has advanced ls and v (or heston_start has taken it): date t + 1
+    __device__ __forceinline__ void date(const typename Product::Contract& pc, int32_t t) {
         double x[2];
         log_spots(t + 1, x);
         p.date(pc, x);
@@ -4450,6 +4472,7 @@ struct HestonProductLegs {
     }
 };
 
+// The QE product kernels' legs, with the step inside (through ProductLegs these kernels compile to other, slower code).
 template <typename Product, bool ANTI>
 struct HestonQeProductLegs {
     static constexpr int LEGS = ANTI ? 2 : 1;
@@ -4489,22 +4512,17 @@ template <template <bool> class Product, bool ANTI>
 __global__ __launch_bounds__(kBlock) void heston_product_kernel(PathRange pr, HestonContract c, typename Product<ANTI>::Contract pc, ReduceWs ws) {
     const RoundKeys rk = pin_round_keys(pr.key0, pr.key1);
     double acc[2] = {0.0, 0.0};
-    HestonProductLegs<Product<ANTI>, ANTI> p(c, kZScale);
+    const HestonStep hs(c);
+    ProductLegs<Product<ANTI>, ANTI> p(c.mu_dt);
     double v_start;
     const bool skip0 = heston_start(c, v_start);
     const int32_t last = Product<ANTI>::last(pc, pr.n_steps);
-    const int32_t blocks = (last + 1) >> 1;
     for_each_path(pr, [&](int64_t, uint32_t g_lo, uint32_t g_hi) {
         p.start(pc, v_start);
-        for (int32_t b = 0; b < blocks; ++b) {
-            float z[4];
-            raw_normals4_pinned(g_lo, g_hi, static_cast<uint32_t>(b), kTagHeston, rk, z);
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int32_t t = 2 * b + h;
-                if (t < last) p.date(pc, t, static_cast<double>(z[2 * h]), static_cast<double>(z[2 * h + 1]), !(skip0 && t == 0));
-            }
-        }
+        heston_philox_walk(g_lo, g_hi, rk, last, skip0, [&](int32_t t, double z1, double z2, bool advance) {
+            if (advance) hs.legs<ANTI>(z1, z2, p.ls, p.v);
+            p.date(pc, t);
+        });
         p.payoffs(pc, last, acc);
     });
     block_then_grid_reduce<2>(acc, ws);
@@ -4521,25 +4539,19 @@ template <template <bool> class Product, bool BRIDGE, bool ANTI>
 __global__ __launch_bounds__(kBlock) void heston_qmc_product_kernel(QmcRange qr, HestonContract c, typename Product<ANTI>::Contract pc,
                                                                     const uint32_t* __restrict__ sv, const uint32_t* __restrict__ shift,
                                                                     QmcBridgePlan plan, double* slabs, ReduceWs ws) {
-    const int lane = static_cast<int>(threadIdx.x) & (kWave - 1);
-    const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) / kWave);
     const int32_t n = qr.dims;                                               // steps: the tables hold 2 n dimensions
-    HestonProductLegs<Product<ANTI>, ANTI> p(c, 1.0);
+    const HestonStep hs(c, 1.0);
+    ProductLegs<Product<ANTI>, ANTI> p(c.mu_dt);
     double v_start;
     const bool skip0 = heston_start(c, v_start);
     const int32_t last = Product<ANTI>::last(pc, n);
-    const uint64_t base = qr.first & ~static_cast<uint64_t>(kWave - 1);      // blocks aligned in the absolute index
-    const uint64_t end = qr.first + static_cast<uint64_t>(qr.count);
-    const int64_t n_blocks = static_cast<int64_t>((end - base + kWave - 1) / kWave);
-    const int64_t stride = static_cast<int64_t>(gridDim.x) * kWavesPerBlock;
-    const int64_t slot = static_cast<int64_t>(blockIdx.x) * kWavesPerBlock + wave;
     double acc[2] = {0.0, 0.0};
-    for (int64_t blk = slot; blk < n_blocks; blk += stride) {
-        const uint64_t k = base + static_cast<uint64_t>(blk) * kWave + lane;
-        const bool live = k >= qr.first && k < end;
-        const QmcLanePoint lp(static_cast<uint32_t>(k));
+    heston_point_blocks(qr, [&](int64_t slot, int lane, uint64_t, bool live, const QmcLanePoint& lp) {
         p.start(pc, v_start);
-        auto step = [&](int32_t t, double z1, double z2) { p.date(pc, t, z1, z2, !(skip0 && t == 0)); };
+        auto step = [&](int32_t t, double z1, double z2) {
+            if (!(skip0 && t == 0)) hs.legs<ANTI>(z1, z2, p.ls, p.v);
+            p.date(pc, t);
+        };
         if constexpr (BRIDGE) {
             double* w1 = slabs + static_cast<size_t>(slot) * (2 * static_cast<size_t>(n) * kWave);
             double* w2 = w1 + static_cast<size_t>(n) * kWave;
@@ -4547,15 +4559,15 @@ __global__ __launch_bounds__(kBlock) void heston_qmc_product_kernel(QmcRange qr,
             heston_qmc_bridge_fill(sv, shift, plan, n, lane, lp, live, w1, w2, at);
             if (live) heston_qmc_bridge_sweep(last, w1, w2, at, step);
         } else {
-            heston_qmc_normals(sv, shift, last, lane, lp, step);
+            heston_qmc_draws<true>(sv, shift, last, lane, lp, step);
         }
         if (live) p.payoffs(pc, last, acc);
-    }
+    });
     block_then_grid_reduce<2>(acc, ws);
 }
 
 // QE on Philox: heston_qe_surface_kernel's draws -- ONE block per step, counter (path_lo, path_hi, t, kTagHestonQe): (x0, x1) ->
-// box_muller_raw -> (Z_v, Z_s), x2 -> U_v.
+// box_muller_raw -> (Z_v, Z_s), x2 -> U_v (drawn in place: with heston_qe_philox_draw the antithetic instantiations compile to other code).
 // Resources (tools/kernel_meta.sh, gfx950; no scratch, no spills; LDS 64 B, the reduction), VGPRs plain / antithetic:
 // autocallable 109 / 120, cliquet 101 / 95 (heston_qe_surface_kernel: 92 / 82).
 template <template <bool> class Product, bool ANTI>

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Interleaved A/B of whole libolmc builds: one subprocess per (library, round), each timing the
-European path kernel with HIP events (olmc_kernel_time).  Usage (GPU box):
-    python tools/ab_libs.py libA.so libB.so ... [--n 1000000] [--m 252] [--rounds 7] [--case european|greeks8|greeks14|greeks8_lean|greeks14_lean|asian|asian_fast|asian_fast_anti|asian_anti|asian_geo|barrier|heston|merton|kou|autocall[_anti]|cliquet[_anti]|american|{barrier,lookback}_greeks{8,14}[_anti]|asian_greeks8|asian_greeks14[_rho]|qmc|qmc_cv|qmc_greeks8|qmc_greeks14]"""
+European path kernel with HIP events (olmc_kernel_time).  --case takes one name or a comma-separated list (measured one after the other in the
+same subprocess, which is ended after --timeout seconds); --out appends one JSON line per (case, library).  Usage (GPU box):
+    python tools/ab_libs.py libA.so libB.so ... [--n 1000000] [--m 252] [--rounds 7] [--timeout 300] [--out FILE.jsonl] [--case european|heston_*|greeks8|greeks14|greeks8_lean|greeks14_lean|asian|asian_fast|asian_fast_anti|asian_anti|asian_geo|barrier|heston|merton|kou|autocall[_anti]|cliquet[_anti]|american|{barrier,lookback}_greeks{8,14}[_anti]|asian_greeks8|asian_greeks14[_rho]|qmc|qmc_cv|qmc_greeks8|qmc_greeks14]"""
 import argparse
 import json
 import os
@@ -56,22 +57,55 @@ if sys.argv[3].startswith("qmc"):
     CASES["qmc_cv"] = lambda s: (lambda m: type("R", (), dict(price=m.value, sum=m.sum_d))())(_hip.european_qmc_cv(*P, True, N, SV, SH))
     CASES["qmc_greeks8"] = lambda s: _hip.european_qmc_greeks_fd(*P, True, N, SV, SH, False)[1][0]
     CASES["qmc_greeks14"] = lambda s: _hip.european_qmc_greeks_fd(*P, True, N, SV, SH, True)[1][0]
-run = CASES[sys.argv[3]]
+# the Heston family: M steps (Sobol: 2 M dimensions, seed 42), the usual model for Euler and a Feller-violating one (both branches) for QE
+HM, HQ = (2.0, 0.04, 0.3, -0.7, 0.04), (1.0, 0.09, 1.0, -0.3, 0.09)
+HA, HC = (1.0, 0.9, 0.10, 0.8, 21), (0.05, -0.05, 0.30, 0.0, 12)
+if "heston_" in sys.argv[3]:
+    from optionslab_amd.monte_carlo import sobol_tables
+    HSV, HSH = sobol_tables(2 * M, 42, N) if "qmc" in sys.argv[3] else (None, None)
+    one = lambda cells: type("R", (), dict(price=cells[0].price, sum=cells[0].sum))()
+    head = lambda mats: type("R", (), dict(price=float(mats[0][-1].mean()), sum=float(mats[1][-1].sum())))()
+    for _a, _sa in ((False, ""), (True, "_anti")):
+        CASES["heston" + _sa] = lambda s, a=_a: _hip.heston(100.0, 100.0, 1.0, 0.05, 0.0, True, *HM, N, M, s, a)
+        CASES["heston_surface" + _sa] = lambda s, a=_a: one(_hip.heston_surface(100.0, 1.0, 0.05, 0.0, True, *HM, [100.0], [M], N, M, s, a))
+        CASES["heston_qe_surface" + _sa] = lambda s, a=_a: one(_hip.heston_qe_surface(100.0, 1.0, 0.05, 0.0, True, *HQ, [100.0], [M], N, M, s, a))
+        CASES["heston_qe_qmc_surface" + _sa] = lambda s, a=_a: one(_hip.heston_qe_qmc_surface(100.0, 1.0, 0.05, 0.0, True, *HQ, [100.0], [M], N, HSV, HSH, False, a))
+        for _q, _sq, _m in ((False, "", HM), (True, "_qe", HQ)):
+            CASES["heston_autocall" + _sq + _sa] = lambda s, a=_a, q=_q, m=_m: _hip.heston_autocallable(100.0, 1.0, 0.05, 0.0, *m, *HA, N, M, s, a, 0, q)
+            CASES["heston_cliquet" + _sq + _sa] = lambda s, a=_a, q=_q, m=_m: _hip.heston_cliquet(100.0, 1.0, 0.05, 0.0, *m, *HC, N, M, s, a, 0, q)
+            for _b, _sb in ((False, "_seq"), (True, "_bridge")):
+                if _q and _b:
+                    continue
+                CASES["heston_qmc_autocall" + _sq + _sb + _sa] = lambda s, a=_a, q=_q, m=_m, b=_b: _hip.heston_autocallable_qmc(100.0, 1.0, 0.05, 0.0, *m, *HA, N, HSV, HSH, b, a, 0, q)
+                CASES["heston_qmc_cliquet" + _sq + _sb + _sa] = lambda s, a=_a, q=_q, m=_m, b=_b: _hip.heston_cliquet_qmc(100.0, 1.0, 0.05, 0.0, *m, *HC, N, HSV, HSH, b, a, 0, q)
+        for _b, _sb in ((False, "_seq"), (True, "_bridge")):
+            CASES["heston_qmc" + _sb + _sa] = lambda s, a=_a, b=_b: _hip.heston_qmc(100.0, 100.0, 1.0, 0.05, 0.0, True, *HM, N, HSV, HSH, b, a)
+            CASES["heston_qmc_surface" + _sb + _sa] = lambda s, a=_a, b=_b: one(_hip.heston_qmc_surface(100.0, 1.0, 0.05, 0.0, True, *HM, [100.0], [M], N, HSV, HSH, b, a))
+            for _f, _payoff in (("asian", _hip.PATH_ASIAN_ARITHMETIC), ("asian_geo", _hip.PATH_ASIAN_GEOMETRIC), ("lookback", _hip.LOOKBACK_FLOATING)):
+                if not _b:
+                    CASES["heston_" + _f + _sa] = lambda s, a=_a, p=_payoff: _hip.heston_path_payoff(100.0, 100.0, 1.0, 0.05, 0.0, True, *HM, p, 0.0, N, M, s, a)
+                CASES["heston_qmc_" + _f + _sb + _sa] = lambda s, a=_a, b=_b, p=_payoff: _hip.heston_qmc_path_payoff(100.0, 100.0, 1.0, 0.05, 0.0, True, *HM, p, 0.0, N, HSV, HSH, b, a)
+    for _pm, _sp in ((False, ""), (True, "_pm")):          # the path matrices: N x (M + 1) doubles twice to the host per call
+        CASES["heston_paths" + _sp] = lambda s, pm=_pm: head(_hip.heston_paths(100.0, 1.0, 0.05, 0.0, *HM, N, M, s, pm))
+        CASES["heston_qe_paths" + _sp] = lambda s, pm=_pm: head(_hip.heston_qe_paths(100.0, 1.0, 0.05, 0.0, *HQ, N, M, s, pm))
 import os, time
 if os.environ.get("OLMC_AB_TUNE"):                      # "knob=value,knob=value" applied before anything runs
     for kv in os.environ["OLMC_AB_TUNE"].split(","):
         k, v = kv.split("=")
         _hip.tune(int(k), int(v))
-_hip.profile_enable(False)
-for i in range(400): run(1 + i)                          # clocks up (an idle device needs tens of ms of load)
-t0 = time.perf_counter()
-for i in range(100): st = run(42 + i)
-wall = (time.perf_counter() - t0) / 100
-_hip.profile_enable(True)
-_hip.profile_reset()
-for i in range(60): st = run(42 + i)
-n, ms = _hip.kernel_time()
-print(json.dumps({"us": (ms / n * 1e3) if n else wall * 1e6, "wall_us": wall * 1e6, "price": st.price, "sum": st.sum}))
+for k, case in enumerate(sys.argv[3].split(",")):
+    run = CASES[case]
+    _hip.profile_enable(False)
+    if k == 0:
+        for i in range(400): run(1 + i)                      # clocks up (an idle device needs tens of ms of load)
+    t0 = time.perf_counter()
+    for i in range(100): st = run(42 + i)
+    wall = (time.perf_counter() - t0) / 100
+    _hip.profile_enable(True)
+    _hip.profile_reset()
+    for i in range(60): st = run(42 + i)
+    n, ms = _hip.kernel_time()
+    print(json.dumps({"case": case, "us": (ms / n * 1e3) if n else wall * 1e6, "wall_us": wall * 1e6, "price": st.price, "sum": st.sum}), flush=True)
 """ % ROOT
 
 ap = argparse.ArgumentParser()
@@ -80,10 +114,13 @@ ap.add_argument("--n", type=int, default=1_000_000)
 ap.add_argument("--m", type=int, default=252)
 ap.add_argument("--rounds", type=int, default=7)
 ap.add_argument("--case", default="european")
+ap.add_argument("--out", default=None)
+ap.add_argument("--timeout", type=float, default=300.0)
 a = ap.parse_args()
+cases = a.case.split(",")
 # a library may carry a tuning suffix: "libolmc.so@7=-1" runs it with olmc_tune(7, -1) (e.g. split workgroups off)
-res = {l: [] for l in a.libs}
-wall = {l: [] for l in a.libs}
+res = {(c, l): [] for c in cases for l in a.libs}
+wall = {(c, l): [] for c in cases for l in a.libs}
 price = {}
 for r in range(a.rounds):
     for l in a.libs:
@@ -91,14 +128,18 @@ for r in range(a.rounds):
         env = dict(os.environ, OLMC_LIBRARY=os.path.abspath(path))
         if tune:
             env["OLMC_AB_TUNE"] = tune
-        out = subprocess.run([sys.executable, "-c", CHILD, str(a.n), str(a.m), a.case], env=env, capture_output=True, text=True)
+        out = subprocess.run([sys.executable, "-c", CHILD, str(a.n), str(a.m), a.case], env=env, capture_output=True, text=True, timeout=a.timeout)
         if out.returncode != 0:
             raise SystemExit(f"{l}: child failed (rc {out.returncode}): {out.stderr[-600:]}")
-        d = json.loads(out.stdout.strip().splitlines()[-1])
-        res[l].append(d["us"])
-        wall[l].append(d["wall_us"])
-        price[l] = (d["price"], d["sum"])
-for l in a.libs:
-    v, w = res[l], wall[l]
-    print(f"{os.path.basename(l):34s} kernel median {statistics.median(v):8.2f} us  min {min(v):8.2f}  max {max(v):8.2f} | blocking call median "
-          f"{statistics.median(w):8.2f} us | price {price[l][0]:.12f} sum {price[l][1]!r}", flush=True)
+        for d in map(json.loads, out.stdout.strip().splitlines()[-len(cases):]):
+            res[d["case"], l].append(d["us"])
+            wall[d["case"], l].append(d["wall_us"])
+            price[d["case"], l] = (d["price"], d["sum"])
+for c, l in res:
+    v, w = res[c, l], wall[c, l]
+    if a.out:
+        with open(a.out, "a") as f:
+            f.write(json.dumps(dict(case=c, lib=l, n=a.n, m=a.m, us=v, us_median=statistics.median(v), us_min=min(v), us_max=max(v),
+                                    wall_us_median=statistics.median(w), price=price[c, l][0], sum=price[c, l][1])) + "\n")
+    print(f"{c + ' ' if len(cases) > 1 else ''}{os.path.basename(l):34s} kernel median {statistics.median(v):8.2f} us  min {min(v):8.2f}  max {max(v):8.2f} | blocking call median "
+          f"{statistics.median(w):8.2f} us | price {price[c, l][0]:.12f} sum {price[c, l][1]!r}", flush=True)
