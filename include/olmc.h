@@ -755,9 +755,13 @@ int olmc_profile_enable(int on);
  *                        (default), -1 = one hipMemcpyAsync into the caller's pageable buffer (round 4's form).  Same bytes either way
  *   OLMC_TUNE_MULTI_LAUNCH multi-GPU entry points: 0 = one launcher thread per device queues the ranks' kernels in parallel
  *                        (default), -1 = the calling thread queues them one after the other (round 4's form)
+ *   OLMC_TUNE_PHILOX_TABLE European launches (prices, fused Greeks, control variate, terminal array): 1 = a launch whose grid covers
+ *                        every path, whose paths have at most 64 Philox blocks (256 steps) and share the high word of the path index
+ *                        carries the words of Philox rounds 1-2 that all its paths share as a table the host builds per launch
+ *                        (default), 0 = never: every thread runs all ten rounds.  Same bits either way
  */
 enum { OLMC_TUNE_GRID_CAP = 2, OLMC_TUNE_QMC_BLOCK = 4, OLMC_TUNE_SPLIT_TAIL = 7, OLMC_TUNE_POLL = 8, OLMC_TUNE_SPLIT_SAT = 9,
-       OLMC_TUNE_MULTI_LAUNCH = 10, OLMC_TUNE_STAGED_COPY = 11 };
+       OLMC_TUNE_MULTI_LAUNCH = 10, OLMC_TUNE_STAGED_COPY = 11, OLMC_TUNE_PHILOX_TABLE = 12 };
 int olmc_tune(int knob, int value);
 /* The behavioural knobs can also be switched off from the environment, read once by the first olmc_init:
  * OLMC_POLL=0 (as OLMC_TUNE_POLL = -1), OLMC_SPLIT_TAIL=0 (as OLMC_TUNE_SPLIT_TAIL = -1), OLMC_MULTI_LAUNCH=serial (as

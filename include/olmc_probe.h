@@ -111,8 +111,11 @@ int olmc_launch_gap_probe(int32_t n, double* us_per_launch);
  *                                    0's completion word, the drain of the ranks and the restoration of the thread's device run
  *                                    exactly as with n devices (except that n launchers then queue on ONE device's runtime locks: the
  *                                    launch phase is no faster than the serial form's there); the call also checks that every rank
- *                                    ended with rank 0's bits. */
-enum { OLMC_PROBE_TUNE_FAULT_SHARD = 5, OLMC_PROBE_TUNE_FORCE_NV = 6, OLMC_PROBE_TUNE_MULTI_REHEARSAL = 11 };
+ *                                    ended with rank 0's bits.
+ *   OLMC_PROBE_TUNE_EXPECT_TABLE     1 / -1: every European launch from now on is expected to carry a / no Philox prefix table
+ *                                    (OLMC_TUNE_PHILOX_TABLE); the launches run either way.  Setting the knob again (to any value)
+ *                                    answers OLMC_ERR_STATE if a launch since the last setting did otherwise, and clears the count. */
+enum { OLMC_PROBE_TUNE_FAULT_SHARD = 5, OLMC_PROBE_TUNE_FORCE_NV = 6, OLMC_PROBE_TUNE_MULTI_REHEARSAL = 11, OLMC_PROBE_TUNE_EXPECT_TABLE = 12 };
 int olmc_probe_tune(int knob, int value);
 
 #ifdef __cplusplus

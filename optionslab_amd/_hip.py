@@ -929,6 +929,7 @@ TUNE_POLL = 8
 TUNE_SPLIT_SAT = 9
 TUNE_MULTI_LAUNCH = 10
 TUNE_STAGED_COPY = 11
+TUNE_PHILOX_TABLE = 12
 
 
 def tune(knob: int, value: int) -> None:

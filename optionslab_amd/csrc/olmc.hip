@@ -388,12 +388,15 @@ int g_grid_cap = 0;          // OLMC_TUNE_GRID_CAP: max workgroups per launch (0
 int g_qmc_block = 0;         // OLMC_TUNE_QMC_BLOCK: 0 = by size, 1 = always eight points per thread, -1 = never (and never split), 2 = always split
 int g_poll = 0;              // OLMC_TUNE_POLL: 0 = blocking calls poll a host-mapped flag for completion (default), -1 = hipStreamSynchronize
 int g_split_tail = 0;        // OLMC_TUNE_SPLIT_TAIL: 0 = split workgroups for the remainder of a European launch (default), -1 = never
+int g_philox_table = 1;      // OLMC_TUNE_PHILOX_TABLE: 1 = European launches carry the Philox prefix table where one applies (default), 0 = never
 int g_split_sat = 0;         // OLMC_TUNE_SPLIT_SAT: k > 0: a last round of fewer than k whole workgroups per CU is split too; 0 = never (default:
                              // measured, no gain -- see european_launch_shape)
 #ifdef OLMC_WITH_PROBES      // the instrumented build (tools/probe/olmc_probe.hip -> libolmc_probe.so) only: test seams, see include/olmc_probe.h
 int g_fault_shard = 0;       // OLMC_PROBE_TUNE_FAULT_SHARD: k > 0 makes rank k - 1 of a multi-GPU call fail before it launches
 int g_force_nv = 0;          // OLMC_PROBE_TUNE_FORCE_NV: > 0 makes workspaces REPORT room for this many values per row (test of the device guard)
 int g_multi_rehearsal = 0;   // OLMC_PROBE_TUNE_MULTI_REHEARSAL: != 0 runs the n ranks of a multi-GPU call on the caller's ONE device
+int g_expect_table = 0;      // OLMC_PROBE_TUNE_EXPECT_TABLE: 1 / -1 = every European launch is expected to carry a / no Philox prefix table ...
+std::atomic<int> g_expect_table_misses{0};   // ... and this counts the launches that did otherwise (reported and cleared when the knob is set again)
 #endif
 
 // Launch geometry: one workgroup per 256 paths, handed out by the hardware dispatcher
@@ -660,15 +663,32 @@ int prof_pair(DeviceCtx* c, EventPair* ep, const EventPair** timed) {
     return OLMC_OK;
 }
 
+// The Philox prefix table of a European launch (PhiloxPrefix, olmc_host_math.h), or none (n_blocks = 0: the kernel's own ten rounds).
+// A table needs a grid that covers every path (the strided form walks several paths per thread and keeps its loop), room for every
+// block of a path, the trailing partial one included, and ONE high path word for the whole launch.
+PhiloxPrefix european_prefix(const PathRange& pr, bool strided) {
+    PhiloxPrefix pp;
+    const int32_t blocks = (pr.n_steps + 3) / 4;
+    const uint64_t last = pr.first + static_cast<uint64_t>(pr.count) - 1;
+    const bool table = g_philox_table != 0 && !strided && blocks <= kPrefixBlocks && (last >> 32) == (pr.first >> 32);
+    philox_prefix(static_cast<uint64_t>(pr.key0) | static_cast<uint64_t>(pr.key1) << 32, static_cast<uint32_t>(pr.first >> 32), 0u, table ? blocks : 0, &pp);
+    return pp;
+}
+
 template <int NSETS, int MODE>
 void launch_european(bool anti, int32_t grid, hipStream_t s, const PathRange& pr, const ContractSet<NSETS>& cs,
                      const ReduceWs& ws, double* terminal, const EventPair* timed = nullptr) {
     const bool strided = static_cast<int64_t>(grid) * kBlock < pr.count;      // the grid does not cover every path
-    with_bool(strided, [&](auto strided_c) {
-        with_bool(anti, [&](auto a) {
-            launch_timed(european_path_kernel<NSETS, a, MODE, strided_c>, dim3(grid), dim3(kBlock), s, timed, pr, cs, ws, terminal);
-        });
-    });
+    const PhiloxPrefix pp = european_prefix(pr, strided);
+#ifdef OLMC_WITH_PROBES
+    if (g_expect_table != 0 && (g_expect_table > 0) != (pp.n_blocks != 0)) g_expect_table_misses.fetch_add(1, std::memory_order_relaxed);
+#endif
+    auto launch = [&](auto strided_c, auto a) {
+        launch_timed(european_path_kernel<NSETS, a, MODE, strided_c>, dim3(grid), dim3(kBlock), s, timed, pr, cs, ws, terminal, pp);
+    };
+    // kSumOnly exists only where the grid covers every path (run_batch_device asks for it nowhere else)
+    if constexpr (MODE == kSumOnly) with_bool(anti, [&](auto a) { launch(std::false_type{}, a); });
+    else with_bool(strided, [&](auto strided_c) { with_bool(anti, [&](auto a) { launch(strided_c, a); }); });
 }
 
 // Waits for the launch just made on stream s (defined with the poll below).
@@ -742,7 +762,7 @@ int run_batch_device(DeviceCtx* c, hipStream_t s, const olmc_option* opts, int32
             ContractSet<width> cs;
             group_contracts<width>(opts, k, n_steps, &cs, pos);
             if (!lean) launch_european<width, kReduce>(anti, g, st, pr, cs, ws, nullptr, timed);
-            else with_bool(anti, [&](auto a) { launch_timed(european_path_kernel<width, a, kSumOnly, false>, dim3(g), dim3(kBlock), st, timed, pr, cs, ws, nullptr); });
+            else launch_european<width, kSumOnly>(anti, g, st, pr, cs, ws, nullptr, timed);
         };
         if (nsets == 1) {
             ContractSet<1> cs;
@@ -3584,6 +3604,7 @@ extern "C" int olmc_tune(int knob, int value) {
     if (knob == OLMC_TUNE_SPLIT_SAT && value >= 0 && value <= 16) { g_split_sat = value; return OLMC_OK; }
     if (knob == OLMC_TUNE_MULTI_LAUNCH && value >= -1 && value <= 0) { g_multi_launch = value; return OLMC_OK; }
     if (knob == OLMC_TUNE_STAGED_COPY && value >= -1 && value <= 0) { g_staged_copy = value; return OLMC_OK; }
+    if (knob == OLMC_TUNE_PHILOX_TABLE && value >= 0 && value <= 1) { g_philox_table = value; return OLMC_OK; }
     return fail(OLMC_ERR_ARG, "unknown tuning knob or value");
 }
 

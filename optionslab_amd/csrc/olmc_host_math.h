@@ -52,6 +52,43 @@ constexpr double kZScale = 1.1774100225154747;     // sqrt(2 ln 2): raw Box-Mull
 constexpr double kPairZScale = 1.6651092223153954; // 2 sqrt(ln 2) = kZScale * sqrt(2): the unit of a path_normal_quarters sum (pair sums)
 constexpr int kExp2Entries = 256;                  // entries of the exp2 table = workgroup size (olmc_kernels.h: exp2_f64_tab)
 
+// ------------------------------------------------------ Philox prefix table ----
+// Philox4x32-10 multipliers and key increments (Salmon et al., SC'11).
+constexpr uint32_t kPhiloxM0 = 0xD2511F53u;
+constexpr uint32_t kPhiloxM1 = 0xCD9E8D57u;
+constexpr uint32_t kPhiloxW0 = 0x9E3779B9u;
+constexpr uint32_t kPhiloxW1 = 0xBB67AE85u;
+
+// The step loops draw block b of path g as philox4x32_10((g_lo, g_hi, b, tag), key).  After two rounds the state is
+//     c0 = [hi(M1 c2') ^ k0 + W0] ^ lo(M1 b)         c1 = lo(M1 c2')
+//     c2 = [lo(M0 g_lo) ^ k1 + W1] ^ hi(M0 c0')      c3 = lo(M0 c0')
+// with c0' = hi(M1 b) ^ g_hi ^ k0 and c2' = hi(M0 g_lo) ^ tag ^ k1: the bracketed words and c1 belong to the path, and
+// w[b] = {lo(M1 b), hi(M0 c0'), lo(M0 c0'), 0} to the whole launch, as long as all its paths share g_hi.  The host builds w[] once
+// per launch (two multiplies per block) and the table travels BY VALUE in the kernel arguments: it changes with every seed, nothing
+// is cached.  n_blocks = 0: no table, the kernel runs all ten rounds itself.
+constexpr int kPrefixBlocks = 64;                  // 252 steps are 63 blocks; a launch with more blocks per path carries no table
+struct alignas(16) PhiloxPrefix {
+    uint32_t w[kPrefixBlocks][4];
+    int32_t n_blocks;
+    int32_t pad[3];
+};
+
+// The table of blocks 0 .. n_blocks - 1 for key = seed, counter word 1 = g_hi.  Counter word 3 (`tag`) and the key's high word reach
+// the state after two rounds only through the path's own words (c2' above), so no table word depends on them.
+inline void philox_prefix(uint64_t seed, uint32_t g_hi, uint32_t tag, int32_t n_blocks, PhiloxPrefix* out) {
+    (void)tag;
+    std::memset(out, 0, sizeof *out);
+    const uint32_t k0 = static_cast<uint32_t>(seed);
+    out->n_blocks = std::min(std::max(n_blocks, 0), kPrefixBlocks);
+    for (int32_t b = 0; b < out->n_blocks; ++b) {
+        const uint64_t p1 = static_cast<uint64_t>(kPhiloxM1) * static_cast<uint32_t>(b);
+        const uint64_t p0 = static_cast<uint64_t>(kPhiloxM0) * (static_cast<uint32_t>(p1 >> 32) ^ g_hi ^ k0);
+        out->w[b][0] = static_cast<uint32_t>(p1);
+        out->w[b][1] = static_cast<uint32_t>(p0 >> 32);
+        out->w[b][2] = static_cast<uint32_t>(p0);
+    }
+}
+
 // Fused exotic Greeks: the 8 / 14 contracts are at most six path recursions (see the kernels in olmc_kernels.h).
 constexpr int kAsianGroups = 6;
 constexpr int kAsianRealGroups = 4;                     // arithmetic kernel: slots 0..3 are recursions of their own, 4..5 ride on slot 0

@@ -6,7 +6,8 @@
 // src/simulation/gbm_numpy.py:43-51).  Normals are produced in registers by
 // Philox4x32-10 + Box-Muller; HBM sees only per-block partial sums (or, in the
 // array-returning mode, the terminal prices).  The step loop is VALU-bound:
-// no LDS, no global loads, MFMA unused (there is no contraction to feed it).
+// no global loads, MFMA unused (there is no contraction to feed it); the only
+// LDS traffic is the European loop's read of its launch's Philox prefix table.
 #pragma once
 #include <type_traits>
 #include <hip/hip_runtime.h>
@@ -21,10 +22,7 @@ constexpr int kWave = 64;
 constexpr int kWavesPerBlock = kBlock / kWave;
 
 // ---------------------------------------------------------------- Philox ----
-constexpr uint32_t kPhiloxM0 = 0xD2511F53u;
-constexpr uint32_t kPhiloxM1 = 0xCD9E8D57u;
-constexpr uint32_t kPhiloxW0 = 0x9E3779B9u;
-constexpr uint32_t kPhiloxW1 = 0xBB67AE85u;
+// kPhiloxM0, kPhiloxM1, kPhiloxW0, kPhiloxW1: olmc_host_math.h (the host builds the prefix table of a launch from them)
 
 struct Words4 {
     uint32_t x0, x1, x2, x3;
@@ -84,9 +82,11 @@ __device__ __forceinline__ RoundKeys pin_round_keys(uint32_t k0, uint32_t k1) {
     return rk;
 }
 
+// Rounds FIRST .. 9 (counted from 0) on the state after round FIRST - 1; FIRST = 0 is the whole generator.
+template <int FIRST = 0>
 __device__ __forceinline__ Words4 philox4x32_10_pinned(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, const RoundKeys& rk) {
 #pragma unroll
-    for (int round = 0; round < 10; ++round) {
+    for (int round = FIRST; round < 10; ++round) {
         const uint64_t p0 = static_cast<uint64_t>(kPhiloxM0) * c0;
         const uint64_t p1 = static_cast<uint64_t>(kPhiloxM1) * c2;
         const uint32_t n0 = xor3(static_cast<uint32_t>(p1 >> 32), c1, rk.k[2 * round]);
@@ -187,23 +187,53 @@ __device__ __forceinline__ float raw_block_accumulate(float acc, uint32_t g_lo, 
 // ~5e-7, about one path in ten million -- but "equal seeds give equal bits" must not depend on the launch shape.)
 constexpr int kGroup = 4;   // measured: 2 is 2 % slower, 8 no faster
 
+// The Philox prefix table of a launch (PhiloxPrefix, olmc_host_math.h).  In the step loop the counter is (g_lo, g_hi, block, tag): of
+// the state after two rounds, three words per block depend on (seed, g_hi, block) alone -- the same for every path of the launch --
+//     t.x = lo(M1 b),   t.y = hi(M0 c0'),   t.z = lo(M0 c0'),   c0' = hi(M1 b) ^ g_hi ^ k0,
+// and the rest on the path alone (PrefixLane, once per thread).  The host computes the three words per block once per launch; the
+// workgroup copies them from the kernel arguments into LDS, and the loop reads them at a uniform address: an LDS read lands in
+// VGPRs (a wave-uniform value the compiler computes itself lands in SGPRs, and an SGPR operand costs an XOR two more issue cycles,
+// see RoundKeys), and the LDS pipe has nothing else to do here.  Per block that leaves rounds 3-10 and two 2-input XORs:
+// 16 v_mad_u64_u32 instead of 17.
+struct PrefixLane {
+    uint32_t a, b, c;      // hi(M1 c2') ^ k0'', lo(M0 g_lo) ^ k1'', lo(M1 c2'), c2' = hi(M0 g_lo) ^ tag ^ k1 (k'' = the second round's keys)
+};
+
+__device__ __forceinline__ PrefixLane prefix_lane(uint32_t g_lo, uint32_t tag, const RoundKeys& rk) {
+    const uint64_t p0 = static_cast<uint64_t>(kPhiloxM0) * g_lo;
+    const uint64_t p1 = static_cast<uint64_t>(kPhiloxM1) * xor3(static_cast<uint32_t>(p0 >> 32), tag, rk.k[1]);
+    return {static_cast<uint32_t>(p1 >> 32) ^ rk.k[2], static_cast<uint32_t>(p0) ^ rk.k[3], static_cast<uint32_t>(p1)};
+}
+
+__device__ __forceinline__ Words4 philox_from_prefix(const uint4& t, const PrefixLane& pl, const RoundKeys& rk) {
+    return philox4x32_10_pinned<2>(pl.a ^ t.x, pl.c, pl.b ^ t.y, t.z, rk);
+}
+
 // Quarters [w0, w1) of one path's canonical sum, UNSCALED (multiply by kPairZScale once all four are in).  w0 = 0, w1 = 4 is the
 // whole path: ((0 + Q0) + Q1) + Q2, then + Q3.  A single quarter w returns 0 + Q_w = Q_w exactly.  One loop nest serves both.
-__device__ __forceinline__ double path_normal_quarters(uint32_t g_lo, uint32_t g_hi, int32_t n_steps, int32_t w0, int32_t w1, uint32_t k0,
-                                                       uint32_t k1, uint32_t tag = 0u) {
+// TABLE: the words of block b come from tab[b] (the launch's prefix table in LDS) -- the same words, hence the same sums.
+template <bool TABLE>
+__device__ __forceinline__ double path_normal_quarters_walk(uint32_t g_lo, uint32_t g_hi, int32_t n_steps, int32_t w0, int32_t w1, const RoundKeys& rk,
+                                                            uint32_t tag, const uint4* tab) {
     const int32_t full = n_steps >> 2;                 // blocks whose four steps all count
     const int32_t n_groups = full / kGroup;            // full groups
     const int32_t gq = (n_groups + 3) >> 2;            // groups per quarter
-    const RoundKeys rk = pin_round_keys(k0, k1);
+    PrefixLane pl{};
+    if constexpr (TABLE) pl = prefix_lane(g_lo, tag, rk);
+    auto words = [&](int32_t b) {
+        if constexpr (TABLE) return philox_from_prefix(tab[b], pl, rk);
+        else return philox4x32_10_pinned(g_lo, g_hi, static_cast<uint32_t>(b), tag, rk);
+    };
     double acc = 0.0, q = 0.0;
 #pragma unroll 1
     for (int32_t w = w0; w < w1; ++w) {
         q = 0.0;
         const int32_t b1 = min((w + 1) * gq, n_groups) * kGroup;
         for (int32_t b = min(w * gq, n_groups) * kGroup; b < b1; b += kGroup) {
+            if constexpr (TABLE) asm volatile("; olmc_table_trip");       // no instruction: by this label tools/isa_mix.py tells the two step loops apart
             float s = 0.0f;
 #pragma unroll
-            for (int j = 0; j < kGroup; ++j) s = raw_block_sum_of_words(s, philox4x32_10_pinned(g_lo, g_hi, static_cast<uint32_t>(b + j), tag, rk));
+            for (int j = 0; j < kGroup; ++j) s = raw_block_sum_of_words(s, words(b + j));
             q += static_cast<double>(s);
         }
         if (w < 3) acc += q;
@@ -212,12 +242,12 @@ __device__ __forceinline__ double path_normal_quarters(uint32_t g_lo, uint32_t g
         int32_t b = n_groups * kGroup;
         if (b < full) {
             float s = 0.0f;
-            for (; b < full; ++b) s = raw_block_sum_of_words(s, philox4x32_10_pinned(g_lo, g_hi, static_cast<uint32_t>(b), tag, rk));
+            for (; b < full; ++b) s = raw_block_sum_of_words(s, words(b));
             q += static_cast<double>(s);
         }
         const int32_t rem = n_steps & 3;
         if (rem) {                                     // pair-sum units: steps 0, 1 as a pair, a last odd step alone / sqrt(2)
-            const Words4 wd = philox4x32_10_pinned(g_lo, g_hi, static_cast<uint32_t>(full), tag, rk);
+            const Words4 wd = words(full);
             float s = 0.0f;
             if (rem > 1) s = pair_sum_raw(0.0f, wd.x0, wd.x1);
             if (rem & 1) {
@@ -230,6 +260,14 @@ __device__ __forceinline__ double path_normal_quarters(uint32_t g_lo, uint32_t g
         acc += q;
     }
     return acc;
+}
+
+// tab != nullptr (launch-uniform): the launch carries a prefix table that covers every block of the path, g_hi included.
+__device__ __forceinline__ double path_normal_quarters(uint32_t g_lo, uint32_t g_hi, int32_t n_steps, int32_t w0, int32_t w1, uint32_t k0,
+                                                       uint32_t k1, uint32_t tag = 0u, const uint4* tab = nullptr) {
+    const RoundKeys rk = pin_round_keys(k0, k1);
+    if (tab) return path_normal_quarters_walk<true>(g_lo, g_hi, n_steps, w0, w1, rk, tag, tab);
+    return path_normal_quarters_walk<false>(g_lo, g_hi, n_steps, w0, w1, rk, tag, nullptr);
 }
 
 __device__ __forceinline__ double path_normal_sum(uint32_t g_lo, uint32_t g_hi, int32_t n_steps, uint32_t k0, uint32_t k1,
@@ -979,7 +1017,7 @@ __device__ __forceinline__ void european_payoffs_folded(const ContractSet<NSETS>
 
 template <int NSETS, bool ANTI, int MODE, bool STRIDED>
 __global__ __launch_bounds__(kBlock) void european_path_kernel(PathRange pr, ContractSet<NSETS> cs, ReduceWs ws,
-                                                               double* __restrict__ terminal) {
+                                                               double* __restrict__ terminal, PhiloxPrefix pp) {
     constexpr int NV = (MODE == kControlVariate) ? 5 : (MODE == kSumOnly ? NSETS : 2 * NSETS);
     static_assert(MODE != kSumOnly || (!STRIDED && NSETS > 1), "kSumOnly exists for the fused sets on launches that cover every path");
     if constexpr (STRIDED) {
@@ -995,6 +1033,12 @@ __global__ __launch_bounds__(kBlock) void european_path_kernel(PathRange pr, Con
         if constexpr (MODE != kTerminal) block_then_grid_reduce<NV>(acc, ws);
     } else {
         __shared__ double quarter_sum[kWavesPerBlock][kWave];
+        __shared__ uint4 prefix[kPrefixBlocks];
+        const bool tabled = pp.n_blocks != 0;           // launch-uniform: the host built the launch's prefix table (see PhiloxPrefix)
+        if (tabled) {
+            if (static_cast<int32_t>(threadIdx.x) < pp.n_blocks) prefix[threadIdx.x] = make_uint4(pp.w[threadIdx.x][0], pp.w[threadIdx.x][1], pp.w[threadIdx.x][2], pp.w[threadIdx.x][3]);
+            __syncthreads();
+        }
         // readfirstlane: the wave index is uniform, and the compiler must KNOW it -- the Philox block counter derives from it in
         // a split workgroup, and a counter in SGPRs keeps the first round's multiply on the scalar unit (17 instead of 18
         // v_mad_u64_u32 per block)
@@ -1004,7 +1048,7 @@ __global__ __launch_bounds__(kBlock) void european_path_kernel(PathRange pr, Con
                                 : static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
         const uint64_t g = pr.first + static_cast<uint64_t>(i);
         double zsum = path_normal_quarters(static_cast<uint32_t>(g), static_cast<uint32_t>(g >> 32), pr.n_steps, split ? wave : 0,
-                                           split ? wave + 1 : 4, pr.key0, pr.key1);
+                                           split ? wave + 1 : 4, pr.key0, pr.key1, 0u, tabled ? prefix : nullptr);
         if (split) {
             quarter_sum[wave][lane] = zsum;
             __syncthreads();

@@ -62,6 +62,7 @@ _check, lib, seed64 = hip._check, hip.lib, hip.seed64
 TUNE_FAULT_SHARD = 5
 TUNE_FORCE_NV = 6
 TUNE_MULTI_REHEARSAL = 11
+TUNE_EXPECT_TABLE = 12
 
 
 def tune(knob: int, value: int) -> None:

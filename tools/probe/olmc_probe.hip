@@ -448,5 +448,10 @@ extern "C" int olmc_probe_tune(int knob, int value) {
     if (knob == OLMC_PROBE_TUNE_FAULT_SHARD && value >= 0 && value <= kMaxDevices) { g_fault_shard = value; return OLMC_OK; }
     if (knob == OLMC_PROBE_TUNE_FORCE_NV && value >= 0 && value <= kMaxNV) { g_force_nv = value; return OLMC_OK; }
     if (knob == OLMC_PROBE_TUNE_MULTI_REHEARSAL && value >= 0 && value <= 1) { g_multi_rehearsal = value; return OLMC_OK; }
+    if (knob == OLMC_PROBE_TUNE_EXPECT_TABLE && value >= -1 && value <= 1) {
+        g_expect_table = value;
+        const int misses = g_expect_table_misses.exchange(0);
+        return misses ? fail(OLMC_ERR_STATE, std::to_string(misses) + " European launches did not meet OLMC_PROBE_TUNE_EXPECT_TABLE") : OLMC_OK;
+    }
     return fail(OLMC_ERR_ARG, "unknown probe knob or value");
 }
