@@ -68,7 +68,9 @@ extern "C" {
                               *    olmc_heston_qe_surface, olmc_heston_qe_qmc_surface, olmc_heston_qe_paths, olmc_heston_qe_qmc_paths (Heston by the
                               *    quadratic-exponential scheme: surfaces and path matrices),
                               *    olmc_heston_autocallable, olmc_heston_autocallable_qmc, olmc_heston_cliquet, olmc_heston_cliquet_qmc (the structured
-                              *    products under Heston, by either scheme) */
+                              *    products under Heston, by either scheme),
+                              *    olmc_heston_scenario_layout, olmc_heston_scenarios, olmc_heston_qmc_scenarios, olmc_heston_greeks_fd,
+                              *    olmc_heston_qmc_greeks_fd (Heston scenario sets and finite-difference Greeks in one launch) */
 
 enum {
     OLMC_OK = 0,
@@ -579,6 +581,55 @@ int olmc_heston_qmc_surface(double S, double T, double r, double q, int is_call,
                             double v0, const double* strikes, const int32_t* steps, int32_t k, int construction, int64_t point_offset,
                             int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift, int32_t bits, int antithetic,
                             olmc_stats* out /* [k] */);
+
+/* ---- Heston scenario sets and finite-difference Greeks ---
+ * European options under k <= OLMC_MAX_BATCH parameter sets ("scenarios": spot, strike, maturity, rates, call / put AND the model) on
+ * ONE set of olmc_heston's draws (Philox) or olmc_heston_qmc's (scrambled Sobol, both constructions), in ONE launch: common random
+ * numbers for what-if scenarios, model-parameter bumps and finite-difference Greeks of the Monte Carlo price.
+ * The folded recursion of a path carries (ln S - drift, v) and depends on (dt, kappa, theta, sigma_v, rho, v0) alone; spot, strike, r,
+ * q and call / put act after the step loop.  Two scenarios SHARE A RECURSION exactly when their (T, kappa, theta, sigma_v, rho, v0)
+ * are equal as doubles (bit for bit: 0.04 and 0.2 * 0.2 are two recursions); recursions are numbered in order of first appearance and
+ * a launch carries at most OLMC_HESTON_MAX_RECURSIONS of them.  Every recursion walks the same n_steps steps on the same normals --
+ * the draws are in units of standard normals, a recursion with another T only scales them by its own sqrt(T / n_steps) -- so scenario
+ * i is the contract olmc_heston / olmc_heston_qmc would price with its parameters, the same n_steps and the same seed or tables: its
+ * payoff on a path is max(+-(exp(ln S_i + n_steps (r_i - q_i) dt_i + x) - K_i), 0), x the recursion's log-spot without ln S and
+ * without the drift, which the one-contract kernels carry inside their sum (the sums agree to rounding, not to the bit).
+ * olmc_heston_scenario_layout reports the grouping (host arithmetic only; no device needed): n_recursions and group[i], the
+ * recursion of scenario i.
+ * out[i] answers scenario i in the caller's order: .sum and .sumsq undiscounted, so shards add up (olmc_combine_stats with the
+ * scenario's own r and T), .price = exp(-r_i T_i) mean, .std_error the naive per-path one.  A scenario's sums depend neither on the
+ * other scenarios of the call, nor on its place in the list, nor on which recursion slot its recursion takes or how many are in use.
+ * antithetic, path_offset / point_offset and v0 < 0 (per recursion) as in olmc_heston / olmc_heston_qmc.  A NaN in a scenario gives
+ * NaN in that scenario only (but a NaN rho, which is no rho in [-1, 1] and is refused as olmc_heston refuses it).
+ * Refused (OLMC_ERR_ARG, before any device work): a null pointer, k outside [1, OLMC_MAX_BATCH], more than
+ * OLMC_HESTON_MAX_RECURSIONS recursions, a T <= 0, a rho outside [-1, 1], and what olmc_heston / olmc_heston_qmc refuse of counts,
+ * steps, construction and tables.  With profiling on a call counts as one launch in olmc_kernel_time.
+ * THE GREEKS.  olmc_heston_greeks_fd / olmc_heston_qmc_greeks_fd are olmc_european_greeks_fd's contracts -- the bumps, the call order
+ * and the differences of compute_greeks_unified (unified_greeks.py:274-277, 295-358); 7 / 8 contracts first order (without / with the
+ * T bump, taken when T > 1/365), 11 / 14 with second_order -- priced under the model with sigma -> v0 = sigma^2 (HestonAdapter's
+ * convention, unified_greeks.py:74-104) as ONE scenario launch on paths / points [0, n): the 14 contracts are four recursions (mid,
+ * which also serves the S and r bumps; sigma + h; sigma - h; T - h_T).  out9 = price, delta, gamma, vega, theta, rho, vanna, charm,
+ * vomma (the last three only with second_order); evals (NULL, or 14 olmc_stats) receives the contracts' statistics in the call order,
+ * zero-filled beyond the contracts in use.  Also refused: T <= 0. */
+typedef struct olmc_heston_scenario {
+    double  S, K, T, r, q, kappa, theta, sigma_v, rho, v0;
+    int32_t is_call;
+    int32_t pad;
+} olmc_heston_scenario;
+#define OLMC_HESTON_MAX_RECURSIONS 6
+int olmc_heston_scenario_layout(const olmc_heston_scenario* sc, int32_t k, int32_t* n_recursions, int32_t* group /* [k] */);
+int olmc_heston_scenarios(const olmc_heston_scenario* sc, int32_t k, int64_t path_offset, int64_t n_local, int32_t n_steps, uint64_t seed,
+                          int antithetic, olmc_stats* out /* [k], in the caller's order */);
+int olmc_heston_qmc_scenarios(const olmc_heston_scenario* sc, int32_t k, int construction, int64_t point_offset, int64_t n_points,
+                              int32_t n_steps, const uint32_t* sv, const uint32_t* shift, int32_t bits, int antithetic,
+                              olmc_stats* out /* [k] */);
+int olmc_heston_greeks_fd(double S, double K, double T, double r, double sigma, double q, int is_call, double kappa, double theta,
+                          double sigma_v, double rho, int64_t n_paths, int32_t n_steps, uint64_t seed, int antithetic, int second_order,
+                          double* out9, olmc_stats* evals /* [14] or NULL */);
+int olmc_heston_qmc_greeks_fd(double S, double K, double T, double r, double sigma, double q, int is_call, double kappa, double theta,
+                              double sigma_v, double rho, int construction, int64_t n_points, int32_t n_steps, const uint32_t* sv,
+                              const uint32_t* shift, int32_t bits, int antithetic, int second_order, double* out9,
+                              olmc_stats* evals /* [14] or NULL */);
 
 /* ---- Heston, quadratic-exponential scheme ---
  * olmc_heston_surface / olmc_heston_paths and their Sobol forms with Andersen's QE discretisation ("Efficient simulation of the Heston

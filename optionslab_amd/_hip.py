@@ -35,6 +35,12 @@ class Option(C.Structure):
                 ("sigma", C.c_double), ("q", C.c_double), ("is_call", C.c_int32), ("reserved", C.c_int32)]
 
 
+class HestonScenario(C.Structure):
+    _fields_ = [("S", C.c_double), ("K", C.c_double), ("T", C.c_double), ("r", C.c_double), ("q", C.c_double),
+                ("kappa", C.c_double), ("theta", C.c_double), ("sigma_v", C.c_double), ("rho", C.c_double), ("v0", C.c_double),
+                ("is_call", C.c_int32), ("pad", C.c_int32)]
+
+
 class CvMoments(C.Structure):
     _fields_ = [("sum_d", C.c_double), ("sum_s", C.c_double), ("sum_dd", C.c_double), ("sum_ss", C.c_double),
                 ("sum_ds", C.c_double), ("n", C.c_int64), ("value", C.c_double)]
@@ -107,6 +113,13 @@ PROTOTYPES = {
     "olmc_heston_surface": (_I, [_D] * 4 + [_I] + [_D] * 5 + [C.POINTER(_D), C.POINTER(_I32), _I32, _I64, _I64, _I32, _U64T, _I, C.POINTER(Stats)]),
     "olmc_heston_qmc_surface": (_I, [_D] * 4 + [_I] + [_D] * 5 + [C.POINTER(_D), C.POINTER(_I32), _I32, _I, _I64, _I64, _I32, C.POINTER(C.c_uint32),
                                      C.POINTER(C.c_uint32), _I32, _I, C.POINTER(Stats)]),
+    "olmc_heston_scenario_layout": (_I, [C.POINTER(HestonScenario), _I32, C.POINTER(_I32), C.POINTER(_I32)]),
+    "olmc_heston_scenarios": (_I, [C.POINTER(HestonScenario), _I32, _I64, _I64, _I32, _U64T, _I, C.POINTER(Stats)]),
+    "olmc_heston_qmc_scenarios": (_I, [C.POINTER(HestonScenario), _I32, _I, _I64, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, _I,
+                                       C.POINTER(Stats)]),
+    "olmc_heston_greeks_fd": (_I, _SIX + [_I] + [_D] * 4 + [_I64, _I32, _U64T, _I, _I, C.POINTER(_D), C.POINTER(Stats)]),
+    "olmc_heston_qmc_greeks_fd": (_I, _SIX + [_I] + [_D] * 4 + [_I, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, _I, _I, C.POINTER(_D),
+                                                             C.POINTER(Stats)]),
     "olmc_heston_qe_surface": (_I, [_D] * 4 + [_I] + [_D] * 5 + [C.POINTER(_D), C.POINTER(_I32), _I32, _I64, _I64, _I32, _U64T, _I, C.POINTER(Stats)]),
     "olmc_heston_qe_qmc_surface": (_I, [_D] * 4 + [_I] + [_D] * 5 + [C.POINTER(_D), C.POINTER(_I32), _I32, _I, _I64, _I64, _I32, C.POINTER(C.c_uint32),
                                         C.POINTER(C.c_uint32), _I32, _I, C.POINTER(Stats)]),
@@ -736,6 +749,71 @@ def heston_qmc_surface(S, T, r, q, is_call: bool, kappa, theta, sigma_v, rho, v0
                                          QMC_BRIDGE if bridge else QMC_SEQUENTIAL, int(point_offset), int(n_points), n_steps, psv, psh,
                                          int(sv.shape[1]), int(antithetic), out))
     return list(out)[:len(strikes)]
+
+
+HESTON_MAX_RECURSIONS = 6          # OLMC_HESTON_MAX_RECURSIONS
+
+
+def _scenarios(scenarios):
+    """(S, K, T, r, q, is_call, kappa, theta, sigma_v, rho, v0) tuples as the C array."""
+    k = len(scenarios)
+    return (HestonScenario * max(k, 1))(*[HestonScenario(S, K, T, r, q, kappa, theta, sigma_v, rho, v0, int(bool(c)), 0)
+                                          for (S, K, T, r, q, c, kappa, theta, sigma_v, rho, v0) in scenarios]), k
+
+
+def heston_scenario_layout(scenarios) -> Tuple[int, List[int]]:
+    """(n_recursions, group[k]) of a list of scenarios (S, K, T, r, q, is_call, kappa, theta, sigma_v, rho, v0): two share a recursion
+    exactly when their (T, kappa, theta, sigma_v, rho, v0) are equal as doubles, numbered by first appearance
+    (olmc_heston_scenario_layout; pure host function: loads the library, not the GPU)."""
+    arr, k = _scenarios(scenarios)
+    n_rec, group = C.c_int32(0), (C.c_int32 * max(k, 1))()
+    _check(load_library().olmc_heston_scenario_layout(arr, k, C.byref(n_rec), group))
+    return n_rec.value, list(group)[:k]
+
+
+def heston_scenarios(scenarios, n_paths: int, n_steps: int, seed: int, antithetic: bool = False, path_offset: int = 0) -> List[Stats]:
+    """European options under k <= 16 scenarios (S, K, T, r, q, is_call, kappa, theta, sigma_v, rho, v0) of at most 6 recursions on ONE
+    walk over heston()'s Philox draws, one launch (olmc_heston_scenarios); the answers come in the caller's order."""
+    arr, k = _scenarios(scenarios)
+    out = (Stats * max(k, 1))()
+    _check(lib().olmc_heston_scenarios(arr, k, int(path_offset), int(n_paths), int(n_steps), seed64(seed), int(antithetic), out))
+    return list(out)[:k]
+
+
+def heston_qmc_scenarios(scenarios, n_points: int, sv: np.ndarray, shift: np.ndarray, bridge: bool = True, antithetic: bool = False,
+                         point_offset: int = 0) -> List[Stats]:
+    """heston_scenarios on heston_qmc()'s scrambled-Sobol points (olmc_heston_qmc_scenarios): n_steps = sv.shape[0] / 2; one fill of the
+    two bridges serves every recursion."""
+    sv, psv, shift, psh = _sobol_args(sv, shift, point_offset, n_points)
+    n_steps = _heston_steps(sv)
+    arr, k = _scenarios(scenarios)
+    out = (Stats * max(k, 1))()
+    _check(lib().olmc_heston_qmc_scenarios(arr, k, QMC_BRIDGE if bridge else QMC_SEQUENTIAL, int(point_offset), int(n_points), n_steps, psv, psh,
+                                           int(sv.shape[1]), int(antithetic), out))
+    return list(out)[:k]
+
+
+def heston_greeks_fd(S, K, T, r, sigma, q, is_call: bool, kappa, theta, sigma_v, rho, n_paths: int, n_steps: int, seed: int, antithetic: bool,
+                     second_order: bool, want_evals: bool = True) -> Tuple[List[float], List[Stats]]:
+    """As european_greeks_fd under the Heston model with sigma -> v0 = sigma^2: the 7 / 8 / 11 / 14 bumped contracts as ONE scenario launch
+    of four recursions (olmc_heston_greeks_fd)."""
+    out9 = (C.c_double * 9)()
+    evals = (Stats * 14)() if want_evals else None
+    _check(lib().olmc_heston_greeks_fd(S, K, T, r, sigma, q, int(is_call), kappa, theta, sigma_v, rho, int(n_paths), int(n_steps), seed64(seed),
+                                       int(antithetic), int(second_order), out9, evals))
+    return list(out9), (list(evals) if want_evals else [])
+
+
+def heston_qmc_greeks_fd(S, K, T, r, sigma, q, is_call: bool, kappa, theta, sigma_v, rho, n_points: int, sv: np.ndarray, shift: np.ndarray,
+                         bridge: bool, antithetic: bool, second_order: bool, want_evals: bool = True) -> Tuple[List[float], List[Stats]]:
+    """heston_greeks_fd on the Sobol points of heston_qmc (olmc_heston_qmc_greeks_fd)."""
+    sv, psv, shift, psh = _sobol_args(sv, shift, 0, n_points)
+    n_steps = _heston_steps(sv)
+    out9 = (C.c_double * 9)()
+    evals = (Stats * 14)() if want_evals else None
+    _check(lib().olmc_heston_qmc_greeks_fd(S, K, T, r, sigma, q, int(is_call), kappa, theta, sigma_v, rho, QMC_BRIDGE if bridge else QMC_SEQUENTIAL,
+                                           int(n_points), n_steps, psv, psh, int(sv.shape[1]), int(antithetic), int(second_order), out9, evals))
+    return list(out9), (list(evals) if want_evals else [])
 
 
 STREAM_HESTON_QE = 0x48514500      # OLMC_STREAM_HESTON_QE: counter word 3 of the QE scheme's Philox blocks

@@ -2780,6 +2780,147 @@ extern "C" int olmc_heston_qmc_surface(double S, double T, double r, double q, i
                                                n_points, n_steps, sv, shift, bits, antithetic, out);
 }
 
+// ====================================================== Heston scenario sets and fused Greeks ====
+// k scenarios on one set of olmc_heston's / olmc_heston_qmc's draws (include/olmc.h "Heston scenario sets and finite-difference
+// Greeks"): the grouping and the kernel's argument are host arithmetic (olmc_host_math.h: heston_scenario_set), the launch is the
+// surface's -- the same runners, ranges, grids and slabs, one launch of heston_scenarios_kernel / heston_qmc_scenarios_kernel.
+namespace {
+static_assert(kHestonRecursions == kAsianGroups && sizeof(HestonScenarioSet) <= 2048, "the scenario set travels by value in the kernel arguments");
+
+// The checks of a scenario list that need no device, in the order olmc.h lists them.
+int scenario_check(const olmc_heston_scenario* sc, int32_t k, const olmc_stats* out) {
+    if (!sc || !out) return fail(OLMC_ERR_ARG, "null pointer");
+    if (k < 1 || k > OLMC_MAX_BATCH) return fail(OLMC_ERR_ARG, "the number of scenarios must be in [1, OLMC_MAX_BATCH]");
+    for (int32_t i = 0; i < k; ++i) {
+        if (sc[i].T <= 0.0) return fail(OLMC_ERR_ARG, "T must be > 0 in every scenario");
+        const int rc = heston_check({sc[i].kappa, sc[i].theta, sc[i].sigma_v, sc[i].rho, sc[i].v0});
+        if (rc) return rc;
+    }
+    int32_t n_rec, group[OLMC_MAX_BATCH];
+    if (const char* bad = heston_scenario_groups(sc, k, &n_rec, group)) return fail(OLMC_ERR_ARG, bad);
+    return OLMC_OK;
+}
+
+// Scenario i's stats from the launch's sums, discounted at its own r and T; a poisoned scenario answers NaN, alone.
+void scenario_finish(const double* h, const int32_t* slot_of, const olmc_heston_scenario* sc, int32_t k, int64_t n, olmc_stats* out) {
+    for (int32_t i = 0; i < k; ++i) {
+        const int32_t j = slot_of[i];
+        if (heston_scenario_poisoned(sc[i])) nan_stats(n, &out[i]);
+        else finish_stats(h[2 * j], h[2 * j + 1], n, sc[i].r, sc[i].T, &out[i]);
+    }
+}
+
+// Philox: the scenarios on paths [path_offset, path_offset + n_local) of olmc_heston's stream.
+int run_heston_scenarios(const olmc_heston_scenario* sc, int32_t k, int64_t path_offset, int64_t n_local, int32_t n_steps, uint64_t seed,
+                         int antithetic, olmc_stats* out) {
+    int rc = scenario_check(sc, k, out);
+    if (rc) return rc;
+    rc = check_paths(path_offset, n_local, n_steps);
+    if (rc) return rc;
+    HestonScenarioSet set;
+    int32_t slot_of[OLMC_MAX_BATCH];
+    if (const char* bad = heston_scenario_set(sc, k, n_steps, kZScale, &set, slot_of)) return fail(OLMC_ERR_ARG, bad);
+    CtxLease lease;
+    rc = ctx_lease(&lease);
+    if (rc) return rc;
+    DeviceCtx* const c = lease.c;
+    const PathRange pr = make_range(path_offset, n_local, n_steps, seed);
+    rc = launch_reduce(c, c->stream, c->d_result, -1.0, 2 * kSurfaceCells, grid_for(n_local),
+                       [&](int32_t grid, hipStream_t st, const EventPair* timed, const ReduceWs& ws) {
+                           with_bool(antithetic != 0, [&](auto a) {
+                               launch_timed(heston_scenarios_kernel<a>, dim3(grid), dim3(kBlock), st, timed, set, pr, ws);
+                           });
+                       });
+    if (rc) return rc;
+    scenario_finish(c->h_result, slot_of, sc, k, n_local * (antithetic ? 2 : 1), out);
+    return OLMC_OK;
+}
+
+// Sobol: the scenarios on points [point_offset, point_offset + n_points) of olmc_heston_qmc's construction; the shape of a Heston price launch.
+int run_heston_qmc_scenarios(const olmc_heston_scenario* sc, int32_t k, int construction, int64_t point_offset, int64_t n_points, int32_t n_steps,
+                             const uint32_t* sv, const uint32_t* shift, int32_t bits, int antithetic, olmc_stats* out) {
+    int rc = scenario_check(sc, k, out);
+    if (rc) return rc;
+    rc = qmc_path_check(construction, point_offset, n_points, n_steps, sv, shift, bits, 2);
+    if (rc) return rc;
+    HestonScenarioSet set;
+    int32_t slot_of[OLMC_MAX_BATCH];
+    if (const char* bad = heston_scenario_set(sc, k, n_steps, 1.0, &set, slot_of)) return fail(OLMC_ERR_ARG, bad);
+    CtxLease lease;
+    rc = ctx_lease(&lease);
+    if (rc) return rc;
+    DeviceCtx* const c = lease.c;
+    QmcPathLaunch pl;
+    rc = qmc_path_setup(c, construction, point_offset, n_points, n_steps, sv, shift, antithetic, &pl, 2);
+    if (rc) return rc;
+    rc = heston_qmc_shape(point_offset, n_points, n_steps)(c, &pl);
+    if (rc) return rc;
+    rc = launch_reduce(c, c->stream, c->d_result, -1.0, 2 * kSurfaceCells, pl.grid,
+                       [&](int32_t g, hipStream_t s, const EventPair* timed, const ReduceWs& ws) {
+                           with_bool(pl.anti, [&](auto a) {
+                               with_bool(pl.bridge, [&](auto b) {
+                                   launch_timed(heston_qmc_scenarios_kernel<b, a>, dim3(g), dim3(kBlock), s, timed, set, pl.qr, pl.d_sv, pl.d_shift,
+                                                pl.plan, pl.slabs, ws);
+                               });
+                           });
+                       });
+    if (rc) return rc;
+    scenario_finish(c->h_result, slot_of, sc, k, n_points * (pl.anti ? 2 : 1), out);
+    return OLMC_OK;
+}
+}  // namespace
+
+// The grouping of a scenario list (pure host arithmetic: needs no device).
+extern "C" int olmc_heston_scenario_layout(const olmc_heston_scenario* sc, int32_t k, int32_t* n_recursions, int32_t* group) {
+    if (!sc || !n_recursions || !group) return fail(OLMC_ERR_ARG, "null pointer");
+    if (const char* bad = heston_scenario_groups(sc, k, n_recursions, group)) return fail(OLMC_ERR_ARG, bad);
+    return OLMC_OK;
+}
+
+extern "C" int olmc_heston_scenarios(const olmc_heston_scenario* sc, int32_t k, int64_t path_offset, int64_t n_local, int32_t n_steps,
+                                     uint64_t seed, int antithetic, olmc_stats* out) {
+    return run_heston_scenarios(sc, k, path_offset, n_local, n_steps, seed, antithetic, out);
+}
+
+extern "C" int olmc_heston_qmc_scenarios(const olmc_heston_scenario* sc, int32_t k, int construction, int64_t point_offset, int64_t n_points,
+                                         int32_t n_steps, const uint32_t* sv, const uint32_t* shift, int32_t bits, int antithetic,
+                                         olmc_stats* out) {
+    return run_heston_qmc_scenarios(sc, k, construction, point_offset, n_points, n_steps, sv, shift, bits, antithetic, out);
+}
+
+// The 7 / 8 / 11 / 14 contracts of compute_greeks_unified under the model, sigma -> v0 = sigma^2 (HestonAdapter, unified_greeks.py:74-104),
+// as ONE scenario launch: GreeksSet as it stands (bumps, call order, finish), four recursions.
+extern "C" int olmc_heston_greeks_fd(double S, double K, double T, double r, double sigma, double q, int is_call, double kappa, double theta,
+                                     double sigma_v, double rho, int64_t n_paths, int32_t n_steps, uint64_t seed, int antithetic,
+                                     int second_order, double* out9, olmc_stats* evals) {
+    if (!out9) return fail(OLMC_ERR_ARG, "null pointer");
+    if (!(T > 0.0)) return fail(OLMC_ERR_ARG, "T must be > 0");
+    const GreeksSet gs(S, K, T, r, sigma, q, is_call, second_order);
+    olmc_heston_scenario sc[OLMC_MAX_BATCH];
+    heston_greeks_scenarios(gs, kappa, theta, sigma_v, rho, sc);
+    olmc_stats st[OLMC_MAX_BATCH];
+    const int rc = run_heston_scenarios(sc, gs.k, 0, n_paths, n_steps, seed, antithetic, st);
+    if (rc) return rc;
+    gs.finish(st, T, out9, evals);
+    return OLMC_OK;
+}
+
+extern "C" int olmc_heston_qmc_greeks_fd(double S, double K, double T, double r, double sigma, double q, int is_call, double kappa,
+                                         double theta, double sigma_v, double rho, int construction, int64_t n_points, int32_t n_steps,
+                                         const uint32_t* sv, const uint32_t* shift, int32_t bits, int antithetic, int second_order,
+                                         double* out9, olmc_stats* evals) {
+    if (!out9) return fail(OLMC_ERR_ARG, "null pointer");
+    if (!(T > 0.0)) return fail(OLMC_ERR_ARG, "T must be > 0");
+    const GreeksSet gs(S, K, T, r, sigma, q, is_call, second_order);
+    olmc_heston_scenario sc[OLMC_MAX_BATCH];
+    heston_greeks_scenarios(gs, kappa, theta, sigma_v, rho, sc);
+    olmc_stats st[OLMC_MAX_BATCH];
+    const int rc = run_heston_qmc_scenarios(sc, gs.k, construction, 0, n_points, n_steps, sv, shift, bits, antithetic, st);
+    if (rc) return rc;
+    gs.finish(st, T, out9, evals);
+    return OLMC_OK;
+}
+
 // ====================================================== Heston, quadratic-exponential scheme ====
 // olmc_heston_surface / olmc_heston_paths and their Sobol forms with Andersen's QE step in place of the Euler one (include/olmc.h
 // "Heston, quadratic-exponential scheme"): the same checks, ranges, cells and read-out (HestonQe), one launch of the heston_qe_* kernels.

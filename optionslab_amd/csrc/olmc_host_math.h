@@ -452,6 +452,108 @@ inline const char* asian_greeks_layout(const GreeksSet& gs, int32_t n_steps, boo
     return nullptr;
 }
 
+// ------------------------------------------------------ Heston scenario sets ----
+// k <= 16 European contracts under k parameter sets on ONE set of Heston draws (olmc.h "Heston scenario sets and finite-difference
+// Greeks"; heston_scenarios_kernel).  A recursion is HestonStep's six folded constants and a start variance; a contract names its
+// recursion and enters after the step loop through (ln S, (r - q) dt, K, sign).
+constexpr int kHestonRecursions = kAsianGroups;
+static_assert(OLMC_HESTON_MAX_RECURSIONS == kHestonRecursions, "olmc.h's recursion count is the fused Greeks kernels' group count");
+
+struct HestonScenarioSet {
+    // recursion g: the constants HestonStep folds from make_heston's contract, formed by the same products, and heston_start's variance
+    // (v0, or the deterministic first step's for v0 < 0); unused recursions are zeros, never read
+    double step[kHestonRecursions][8];                  // neg_half_dt, one_minus_kdt, kdt_theta, zs, a, b, v_start, 0
+    // kernel slot j: the contracts sorted by recursion, then by log-spot (first appearance); slots [end[g - 1], end[g]) read recursion g
+    double slot[OLMC_MAX_BATCH][4];                     // ln S, (r - q) dt, strike, sign
+    int32_t end[kHestonRecursions];
+    int32_t fresh[OLMC_MAX_BATCH];                      // 1: the slot forms its own spot; 0: it reads the spot of the slot before it
+    int32_t skip0_mask;                                 // bit g: heston_start took step 0 of recursion g (v0 < 0)
+    int32_t n_recursions;
+};
+enum { kScnNegHalfDt, kScnOneMinusKdt, kScnKdtTheta, kScnZs, kScnA, kScnB, kScnVStart };      // HestonScenarioSet::step[g][.]
+enum { kScnLogS, kScnMuDt, kScnStrike, kScnSign };                                            // HestonScenarioSet::slot[j][.]
+
+inline bool same_recursion(const olmc_heston_scenario& x, const olmc_heston_scenario& y) {
+    return same_bits(x.T, y.T) && same_bits(x.kappa, y.kappa) && same_bits(x.theta, y.theta) && same_bits(x.sigma_v, y.sigma_v)
+        && same_bits(x.rho, y.rho) && same_bits(x.v0, y.v0);
+}
+
+// group[i] = the recursion of scenario i, numbered by first appearance.  Returns nullptr, or what is wrong.
+inline const char* heston_scenario_groups(const olmc_heston_scenario* sc, int32_t k, int32_t* n_recursions, int32_t* group) {
+    if (k < 1 || k > OLMC_MAX_BATCH) return "the number of scenarios must be in [1, OLMC_MAX_BATCH]";
+    int32_t first[kHestonRecursions], n = 0;
+    for (int32_t i = 0; i < k; ++i) {
+        int32_t g = 0;
+        while (g < n && !same_recursion(sc[first[g]], sc[i])) ++g;
+        if (g == n) {
+            if (n == kHestonRecursions) return "more than OLMC_HESTON_MAX_RECURSIONS distinct (T, kappa, theta, sigma_v, rho, v0)";
+            first[n++] = i;
+        }
+        group[i] = g;
+    }
+    *n_recursions = n;
+    return nullptr;
+}
+
+// What a scenario answers NaN for (poisoned(), and a NaN in the model).
+inline bool heston_scenario_poisoned(const olmc_heston_scenario& s) {
+    return poisoned(s.S, s.K, s.T, s.r, 0.0, s.q) || std::isnan(s.kappa + s.theta + s.sigma_v + s.rho + s.v0);
+}
+
+// The kernel's argument for k checked scenarios on n_steps steps; slot_of[i] = the kernel slot of scenario i.  `z_unit` as
+// HestonStep's: kZScale for raw Philox normals, 1 for Sobol normals.  Every constant by the products make_heston (olmc.hip) and
+// HestonStep (olmc_kernels.h) form for the one-contract kernels, so a recursion here advances with their bits.
+inline const char* heston_scenario_set(const olmc_heston_scenario* sc, int32_t k, int32_t n_steps, double z_unit, HestonScenarioSet* set,
+                                       int32_t* slot_of) {
+    std::memset(set, 0, sizeof *set);
+    int32_t group[OLMC_MAX_BATCH], spot_of[OLMC_MAX_BATCH], order[OLMC_MAX_BATCH];
+    double log_s[OLMC_MAX_BATCH], mu_dt[OLMC_MAX_BATCH];
+    if (const char* bad = heston_scenario_groups(sc, k, &set->n_recursions, group)) return bad;
+    for (int32_t i = 0; i < k; ++i) {
+        const olmc_heston_scenario& s = sc[i];
+        const double dt = s.T / n_steps, sqrt_dt = std::sqrt(dt), kappa_dt = s.kappa * dt;
+        const int32_t g = group[i];
+        double* const cst = set->step[g];
+        cst[kScnNegHalfDt] = -0.5 * dt;
+        cst[kScnOneMinusKdt] = 1.0 - kappa_dt;
+        cst[kScnKdtTheta] = kappa_dt * s.theta;
+        cst[kScnZs] = z_unit * sqrt_dt;
+        cst[kScnA] = s.sigma_v * s.rho * (z_unit * sqrt_dt);
+        cst[kScnB] = s.sigma_v * std::sqrt(1 - s.rho * s.rho) * (z_unit * sqrt_dt);
+        cst[kScnVStart] = s.v0 >= 0.0 ? s.v0 : std::fmax(s.v0 + kappa_dt * s.theta, 0.0);
+        if (!(s.v0 >= 0.0)) set->skip0_mask |= 1 << g;
+        log_s[i] = std::log(s.S);
+        mu_dt[i] = (s.r - s.q) * dt;
+        spot_of[i] = i;                                  // the first scenario with this recursion and these (ln S, (r - q) dt)
+        for (int32_t j = 0; j < i; ++j)
+            if (group[j] == g && same_bits(log_s[j], log_s[i]) && same_bits(mu_dt[j], mu_dt[i])) { spot_of[i] = spot_of[j]; break; }
+        order[i] = i;
+    }
+    std::stable_sort(order, order + k, [&](int32_t x, int32_t y) {
+        return group[x] != group[y] ? group[x] < group[y] : spot_of[x] < spot_of[y];
+    });
+    for (int32_t j = 0; j < k; ++j) {
+        const int32_t i = order[j];
+        set->slot[j][kScnLogS] = log_s[i];
+        set->slot[j][kScnMuDt] = mu_dt[i];
+        set->slot[j][kScnStrike] = sc[i].K;
+        set->slot[j][kScnSign] = sc[i].is_call ? 1.0 : -1.0;
+        set->fresh[j] = j == 0 || group[order[j - 1]] != group[i] || spot_of[order[j - 1]] != spot_of[i];
+        set->end[group[i]] = j + 1;
+        slot_of[i] = j;
+    }
+    for (int32_t g = set->n_recursions; g < kHestonRecursions; ++g) set->end[g] = k;
+    return nullptr;
+}
+
+// The scenarios of a GreeksSet under the model: sigma -> v0 = sigma^2 (unified_greeks.py:74-104).
+inline void heston_greeks_scenarios(const GreeksSet& gs, double kappa, double theta, double sigma_v, double rho, olmc_heston_scenario* sc) {
+    for (int i = 0; i < gs.k; ++i) {
+        const olmc_option& o = gs.o[i];
+        sc[i] = olmc_heston_scenario{o.S, o.K, o.T, o.r, o.q, kappa, theta, sigma_v, rho, o.sigma * o.sigma, o.is_call, 0};
+    }
+}
+
 // Contiguous global path ranges of a P-rank call: rank d owns [d N / P, (d + 1) N / P)  (SURVEY §8e).  N < 2^53 / P in practice
 // (N <= 2^40 paths, P <= 16), so the products cannot overflow int64.
 inline void shard_range(int64_t n_paths, int rank, int n_ranks, int64_t* lo, int64_t* count) {

@@ -2248,6 +2248,9 @@ struct HestonStep {
     __device__ __forceinline__ explicit HestonStep(const HestonContract& c, double z_unit = kZScale)
         : neg_half_dt(-0.5 * c.dt), one_minus_kdt(1.0 - c.kappa_dt), kdt_theta(c.kappa_dt * c.theta),
           zs(z_unit * c.sqrt_dt), a(c.sigma_v * c.rho * (z_unit * c.sqrt_dt)), b(c.sigma_v * c.rho_c * (z_unit * c.sqrt_dt)) {}
+    // the constants as the host folded them by the same products (olmc_host_math.h: heston_scenario_set)
+    __device__ __forceinline__ HestonStep(double neg_half_dt_, double one_minus_kdt_, double kdt_theta_, double zs_, double a_, double b_)
+        : neg_half_dt(neg_half_dt_), one_minus_kdt(one_minus_kdt_), kdt_theta(kdt_theta_), zs(zs_), a(a_), b(b_) {}
     // SIGN = +1 / -1: the antithetic leg flips both normals (free source modifiers)
     template <int SIGN>
     __device__ __forceinline__ void advance(double u, double w, double& ls, double& v) const {
@@ -4113,6 +4116,176 @@ __global__ __launch_bounds__(kBlock) void heston_qmc_surface_kernel(QmcRange qr,
             heston_qmc_draws<true>(sv, shift, cells.last, lane, lp, step);
         }
     }
+    rows.reduce(ws);
+}
+
+// ------------------------------------------------- Heston scenario sets and fused Greeks ----
+// European payoffs under up to 16 parameter sets on ONE walk over the draws of a path or point (include/olmc.h "Heston scenario sets
+// and finite-difference Greeks"): HestonStep's folded recursion knows (dt, kappa, theta, sigma_v, rho, v0) alone, so a lane carries up
+// to kHestonRecursions (ln S - drift, v) states -- each with its own constants and its own heston_start -- and advances every one of
+// them with HestonStep::legs on the step's one pair of normals (the draws are in units of standard normals: another dt only scales
+// them differently).  ls is carried WITHOUT ln S and without the (r - q) dt terms, as heston_surface_kernel carries it without the
+// latter; the epilogue forms a contract's log-spot as that kernel's read-out does, fma(n, (r - q) dt, ln S + ls), one exponential per
+// leg and per distinct (recursion, ln S, (r - q) dt) -- the host sorts the contracts by recursion and then by log-spot and flags the
+// slots that open a new one (HestonScenarioSet::fresh), so calls and puts and strikes of one spot share its exponential.
+// THE CONSTANTS live in LDS, where HestonSurfaceCells keeps its cells: 6 recursions x 7 doubles would be 84 scalar registers beside
+// the 20 of the round keys and the kernel's own, more than the 102 a wave has, and templating on the recursion count would make six
+// code objects of every one of the six instantiations for what is, per step and recursion, a few broadcast ds_reads under a chain of
+// ~25 dependent fp64 operations.  The set is the kernel's FIRST argument, so the kernarg segment begins with it, and every thread
+// copies one dword of it from there to LDS with a vector load (the same words through the by-value argument would pass through 240
+// scalar registers at once, and a runtime index into the argument itself would move it to scratch); only n_recursions and skip0_mask
+// are read as the scalars they are.  The step loop reads the constants through an offset the optimiser cannot see through
+// (opaque_zero, once per step), or it hoists all 42 values out of the loop into vector registers.  A recursion slot is skipped by a
+// scalar branch when it is not in use (n_recursions is launch-uniform); the state arrays are indexed statically (the slot loop is
+// unrolled), so nothing goes to scratch.  A slot's arithmetic does not depend on its number or on how many are in use.
+// NO per-thread accumulators: as in SurfaceRows a contract's (x, x^2) are folded over the wave as soon as they exist (wave_sum: fixed
+// order) and lane 0 adds them into the wave's LDS row, 2 x 16 doubles wide whatever k; the workgroup row is the four waves' rows added
+// in wave order, then grid_reduce_workgroup<2 * 16>.  The path loops are WAVE-uniform: a lane outside the range runs the recursions
+// of a defined path (path 0 / the Sobol point of its index) with its payoffs masked to 0.
+static_assert(sizeof(HestonScenarioSet) % 4 == 0 && sizeof(HestonScenarioSet) / 4 <= kBlock, "one dword of the set per thread");
+static_assert(kSurfaceCells == OLMC_MAX_BATCH, "a scenario launch's row is OLMC_MAX_BATCH pairs wide");
+
+struct ScenarioRows {
+    double (*stage)[2 * kSurfaceCells];          // LDS [kWavesPerBlock][2 kSurfaceCells]
+    HestonScenarioSet* lds;                      // LDS: the launch's set
+    int lane, wave;
+    // Call first in the kernel, whose first argument is the set.
+    __device__ __forceinline__ void clear() const {
+        if (lane < 2 * kSurfaceCells) stage[wave][lane] = 0.0;
+        const uint32_t* arg = (const uint32_t*)__builtin_amdgcn_kernarg_segment_ptr();
+        if (threadIdx.x < sizeof(HestonScenarioSet) / 4) reinterpret_cast<uint32_t*>(lds)[threadIdx.x] = arg[threadIdx.x];
+        __syncthreads();
+    }
+    template <bool ANTI>
+    __device__ __forceinline__ void start(double (&ls)[kHestonRecursions][2], double (&v)[kHestonRecursions][2]) const {
+#pragma unroll
+        for (int g = 0; g < kHestonRecursions; ++g) {
+            ls[g][0] = ls[g][1] = 0.0;
+            v[g][0] = v[g][1] = lds->step[g][kScnVStart];
+        }
+    }
+    // Step t of every recursion in use from the step's two normals (in the unit the constants were folded for).
+    template <bool ANTI>
+    __device__ __forceinline__ void advance(const HestonScenarioSet& set, int32_t t, double z1, double z2, double (&ls)[kHestonRecursions][2],
+                                            double (&v)[kHestonRecursions][2]) const {
+        const double (*cst)[8] = lds->step + opaque_zero();
+#pragma unroll
+        for (int g = 0; g < kHestonRecursions; ++g) {
+            if (g < set.n_recursions && !(t == 0 && ((set.skip0_mask >> g) & 1))) {
+                const HestonStep hs(cst[g][kScnNegHalfDt], cst[g][kScnOneMinusKdt], cst[g][kScnKdtTheta], cst[g][kScnZs], cst[g][kScnA], cst[g][kScnB]);
+                hs.legs<ANTI>(z1, z2, ls[g], v[g]);
+            }
+        }
+    }
+    // The contracts of a block of 64 paths whose n steps are done.  Call with all 64 lanes.
+    template <int LEGS>
+    __device__ __forceinline__ void read_out(double n, const double (&ls)[kHestonRecursions][2], bool live) const {
+        int32_t j = 0;
+#pragma unroll
+        for (int g = 0; g < kHestonRecursions; ++g) {
+            const int32_t end = __builtin_amdgcn_readfirstlane(lds->end[g]);
+            double s[LEGS] = {};
+            for (; j < end; j = __builtin_amdgcn_readfirstlane(j + 1)) {
+                const double strike = lds->slot[j][kScnStrike], sign = lds->slot[j][kScnSign];
+                if (__builtin_amdgcn_readfirstlane(lds->fresh[j])) {
+                    const double log_s = lds->slot[j][kScnLogS], mu_dt = lds->slot[j][kScnMuDt];
+#pragma unroll
+                    for (int leg = 0; leg < LEGS; ++leg) s[leg] = exp(__builtin_fma(n, mu_dt, log_s + ls[g][leg]));
+                }
+                double sum = 0.0, sumsq = 0.0;
+#pragma unroll
+                for (int leg = 0; leg < LEGS; ++leg) {
+                    const double x = live ? fmax(sign * (s[leg] - strike), 0.0) : 0.0;
+                    sum += x;
+                    sumsq += x * x;
+                }
+                const double wave_total = wave_sum(sum), wave_total_sq = wave_sum(sumsq);       // valid in lane 0
+                if (lane == 0) { stage[wave][2 * j] += wave_total; stage[wave][2 * j + 1] += wave_total_sq; }
+            }
+        }
+    }
+    // The workgroup's row into the grid reduction (all waves).
+    __device__ __forceinline__ void reduce(const ReduceWs& ws) const {
+        __syncthreads();
+        double row = 0.0;
+        if (threadIdx.x < 2 * kSurfaceCells) {
+            row = stage[0][threadIdx.x];
+#pragma unroll
+            for (int k = 1; k < kWavesPerBlock; ++k) row += stage[k][threadIdx.x];
+        }
+        grid_reduce_workgroup<2 * kSurfaceCells>(row, ws);
+    }
+};
+
+// Philox: lane per path, heston_kernel's stream (tag kTagHeston, one block for two steps, raw_normals4_pinned).
+// Resources (tools/kernel_meta.sh, gfx950; no scratch, no spills; LDS 4.0 KiB: the wave rows, the set and the workgroup reduction),
+// VGPRs plain / antithetic: 114 / 110 (heston_kernel: 96 / 76): both allocate within 128, four waves per SIMD against heston_kernel's
+// five and six -- six (ln S, v) pairs per leg live beside the Philox block, where heston_kernel keeps one.
+template <bool ANTI>
+__global__ __launch_bounds__(kBlock) void heston_scenarios_kernel(HestonScenarioSet set, PathRange pr, ReduceWs ws) {
+    constexpr int LEGS = ANTI ? 2 : 1;
+    __shared__ double stage[kWavesPerBlock][2 * kSurfaceCells];
+    __shared__ HestonScenarioSet lds;
+    const ScenarioRows rows{stage, &lds, static_cast<int>(threadIdx.x) & (kWave - 1),
+                            __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) / kWave)};
+    rows.clear();
+    const RoundKeys rk = pin_round_keys(pr.key0, pr.key1);
+    const int32_t blocks = (pr.n_steps + 1) >> 1;
+    const int64_t stride = static_cast<int64_t>(gridDim.x) * kBlock;
+    for (int64_t w0 = static_cast<int64_t>(blockIdx.x) * kBlock + rows.wave * kWave; w0 < pr.count; w0 += stride) {      // wave-uniform
+        const int64_t i = w0 + rows.lane;
+        const bool live = i < pr.count;
+        const PathWords pw = path_words(pr, live ? i : 0);
+        double ls[kHestonRecursions][2], v[kHestonRecursions][2];
+        rows.start<ANTI>(ls, v);
+        for (int32_t b = 0; b < blocks; ++b) {
+            float z[4];
+            raw_normals4_pinned(pw.lo, pw.hi, static_cast<uint32_t>(b), kTagHeston, rk, z);
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int32_t t = 2 * b + h;
+                if (t < pr.n_steps) rows.advance<ANTI>(set, t, static_cast<double>(z[2 * h]), static_cast<double>(z[2 * h + 1]), ls, v);
+            }
+        }
+        rows.read_out<LEGS>(static_cast<double>(pr.n_steps), ls, live);
+    }
+    rows.reduce(ws);
+}
+
+// Sobol: heston_qmc_kernel's skeleton unchanged (heston_point_blocks' aligned blocks, heston_qmc_draws, the bridge's fill and sweep on
+// the library's slabs): ONE fill of the two bridges serves every recursion.  Every lane fills and sweeps its own column of the wave's
+// slab, inside the shard or not, as in heston_qmc_surface_kernel.
+// Resources (tools/kernel_meta.sh, gfx950; no scratch, no spills; LDS 4.0 KiB), VGPRs plain / antithetic: 94 / 100 (sequential), 119 / 129
+// (bridge) (heston_qmc_kernel: 88 / 78 and 117 / 109): sequential plain allocates 96 (five waves per SIMD, heston_qmc_kernel's row),
+// antithetic 104 (four); the bridge forms allocate 120 and 136 (four and three), above the two waves per SIMD the bridge launch holds
+// (olmc.hip: kHestonBridgeBlocksPerCu).  Like heston_qmc_kernel the Sobol forms keep part of their scalar state in lanes of a vector
+// register (the 106 scalar registers are all in use); nothing of it is touched inside the step loop's recursions.
+template <bool BRIDGE, bool ANTI>
+__global__ __launch_bounds__(kBlock) void heston_qmc_scenarios_kernel(HestonScenarioSet set, QmcRange qr, const uint32_t* __restrict__ sv,
+                                                                      const uint32_t* __restrict__ shift, QmcBridgePlan plan, double* slabs,
+                                                                      ReduceWs ws) {
+    constexpr int LEGS = ANTI ? 2 : 1;
+    __shared__ double stage[kWavesPerBlock][2 * kSurfaceCells];
+    __shared__ HestonScenarioSet lds;
+    const ScenarioRows rows{stage, &lds, static_cast<int>(threadIdx.x) & (kWave - 1),
+                            __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) / kWave)};
+    rows.clear();
+    const int32_t n = qr.dims;                                               // steps: the tables hold 2 n dimensions
+    heston_point_blocks(qr, [&](int64_t slot, int lane, uint64_t, bool live, const QmcLanePoint& lp) {
+        double ls[kHestonRecursions][2], v[kHestonRecursions][2];
+        rows.start<ANTI>(ls, v);
+        auto step = [&](int32_t t, double z1, double z2) { rows.advance<ANTI>(set, t, z1, z2, ls, v); };
+        if constexpr (BRIDGE) {
+            double* w1 = slabs + static_cast<size_t>(slot) * (2 * static_cast<size_t>(n) * kWave);
+            double* w2 = w1 + static_cast<size_t>(n) * kWave;
+            auto at = [&](int32_t j) { return static_cast<size_t>(j - 1) * kWave + lane; };
+            heston_qmc_bridge_fill(sv, shift, plan, n, lane, lp, true, w1, w2, at);
+            heston_qmc_bridge_sweep(n, w1, w2, at, step);
+        } else {
+            heston_qmc_draws<true>(sv, shift, n, lane, lp, step);
+        }
+        rows.read_out<LEGS>(static_cast<double>(n), ls, live);
+    });
     rows.reduce(ws);
 }
 

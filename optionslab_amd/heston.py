@@ -13,7 +13,10 @@ scheme (include/olmc.h "Heston, quadratic-exponential scheme") in `price_monte_c
 """
 from __future__ import annotations
 
+import copy
+import struct
 import warnings
+from collections import OrderedDict
 from dataclasses import dataclass
 from typing import Tuple, Literal, Optional
 
@@ -22,6 +25,7 @@ import numpy as np
 from . import _hip
 
 _SURFACE_CELLS = 16          # cells of one launch (OLMC_MAX_BATCH)
+_SCENARIO_KEYS = ("kappa", "theta", "sigma_v", "rho", "v0")
 _STEPS_PER_YEAR = {"euler": 64, "qe": 16}      # calibrate_heston's grid when n_steps is None
 
 
@@ -40,6 +44,34 @@ def _check_scheme(scheme: str, method: str, path_construction: str) -> bool:
         raise ValueError("scheme='qe' with method='qmc' takes path_construction='sequential': pass path_construction='sequential' "
                          "(QE's variance draw is a uniform, not a Brownian increment, so there is nothing for a bridge to build)")
     return scheme == "qe"
+
+
+def _check_euler_only(scheme: str, what: str) -> None:
+    if scheme not in ("euler", "qe"):
+        raise ValueError("scheme must be 'euler' or 'qe'")
+    if scheme == "qe":
+        raise ValueError(f"{what} runs the Euler scheme only: the fused scenario kernels have no quadratic-exponential form yet")
+
+
+def _recursion_key(T, kappa, theta, sigma_v, rho, v0) -> bytes:
+    """What two scenarios must share to share a recursion: the six doubles, compared bit for bit (0.04 and 0.2**2 differ)."""
+    return struct.pack("<6d", T, kappa, theta, sigma_v, rho, v0)
+
+
+def _scenario_launches(keys, max_scenarios: int = _SURFACE_CELLS, max_recursions: int = _hip.HESTON_MAX_RECURSIONS):
+    """A list of scenarios, given by their recursion keys, cut greedily and in the caller's order into launches of at most 16 scenarios
+    and at most 6 distinct recursions: lists of indices, every index once.  A launch ends where the next scenario would be its 17th or
+    would bring a seventh recursion."""
+    launches, current, seen = [], [], set()
+    for i, key in enumerate(keys):
+        if current and (len(current) == max_scenarios or (key not in seen and len(seen) == max_recursions)):
+            launches.append(current)
+            current, seen = [], set()
+        current.append(i)
+        seen.add(key)
+    if current:
+        launches.append(current)
+    return launches
 
 
 def _surface_steps(maturities, n_steps: int) -> Tuple[float, list]:
@@ -236,6 +268,64 @@ class HestonPricer:
                 prices[i, j], errors[i, j] = st.price, st.std_error
         return (prices, errors) if return_error else prices
 
+    def _scenario_tuples(self, scenarios):
+        """price_scenarios' mappings as _hip's tuples (S, K, T, r, q, is_call, kappa, theta, sigma_v, rho, v0), checked."""
+        scenarios = list(scenarios)
+        if not scenarios:
+            raise ValueError("scenarios must not be empty")
+        out = []
+        for i, sc in enumerate(scenarios):
+            missing = [key for key in ("S", "K", "T", "r") if key not in sc]
+            if missing:
+                raise ValueError(f"scenario {i} lacks {missing}")
+            unknown = sorted(set(sc) - {"S", "K", "T", "r", "q", "option_type", *_SCENARIO_KEYS})
+            if unknown:
+                raise ValueError(f"scenario {i} has unknown keys {unknown}")
+            T = float(sc["T"])
+            if T <= 0.0:
+                raise ValueError(f"scenario {i}: T must be > 0")
+            model = [float(sc.get(key, getattr(self, key))) for key in _SCENARIO_KEYS]
+            if not -1.0 <= model[3] <= 1.0:
+                raise ValueError(f"scenario {i}: rho must be in [-1, 1]")
+            out.append((float(sc["S"]), float(sc["K"]), T, float(sc["r"]), float(sc.get("q", 0.0)), sc.get("option_type", "call") == "call", *model))
+        return out
+
+    def price_scenarios(self, scenarios, n_paths: int = 100000, n_steps: int = 252, seed: Optional[int] = None, antithetic: bool = False,
+                        return_error: bool = False, *, method: Literal["pseudo", "qmc"] = "pseudo",
+                        path_construction: Literal["bridge", "sequential"] = "bridge", scheme: Literal["euler", "qe"] = "euler"):
+        """European prices under a list of what-if scenarios on COMMON random numbers: a float64 array (len(scenarios),), with
+        return_error (prices, std_errors).  A scenario is a mapping with the keys S, K, T, r and optionally q (0), option_type
+        ("call"; anything else prices as a put) and kappa, theta, sigma_v, rho, v0 (this pricer's own): spot, strike, maturity, rates
+        and the model may all differ.  Scenario i is price_monte_carlo(S, K, T, r, q, option_type, n_paths, n_steps, seed, antithetic,
+        method=..., path_construction=...) of a pricer with its model -- the same draws, the sums to rounding -- but the scenarios of a
+        launch share ONE walk over the Philox blocks or Sobol points (and one fill of the two bridges): scenarios whose (T, kappa,
+        theta, sigma_v, rho, v0) are equal as doubles share a path recursion, the others take one of their own on the same normals.
+        The list is cut greedily, in the caller's order, into launches of at most 16 scenarios and at most 6 recursions; a scenario's
+        bits depend neither on the cut nor on its neighbours nor on its place.  seed=None draws ONE seed for all launches.
+        A scenario's v0 is not validated as HestonPricer's is: v0 < 0 means what it means at the C ABI (a deterministic first step).
+        The scenarios run the Euler scheme; QE scenarios and Greeks are out of scope here.
+        Refused (ValueError, before the device is touched): what price_monte_carlo refuses, an empty list, a scenario without S, K, T
+        or r, with an unknown key, with T <= 0 or rho outside [-1, 1], and scheme="qe"."""
+        if n_paths < 1 or n_steps < 1:
+            raise ValueError("n_paths and n_steps must be >= 1")
+        _check_euler_only(scheme, "price_scenarios")
+        tuples = self._scenario_tuples(scenarios)
+        qmc = _qmc_tables(method, path_construction, n_paths, n_steps, seed)
+        if qmc is None:
+            s = seed if seed is not None else int(np.random.default_rng().integers(0, 2**31))
+        prices = np.empty(len(tuples), dtype=np.float64)
+        errors = np.empty_like(prices)
+        for launch in _scenario_launches([_recursion_key(t[2], *t[6:]) for t in tuples]):
+            part = [tuples[i] for i in launch]
+            if qmc is not None:
+                sv, shift, bridge = qmc
+                sts = _hip.heston_qmc_scenarios(part, n_paths, sv, shift, bridge, antithetic)
+            else:
+                sts = _hip.heston_scenarios(part, n_paths, n_steps, s, antithetic)
+            for i, st in zip(launch, sts):
+                prices[i], errors[i] = st.price, st.std_error
+        return (prices, errors) if return_error else prices
+
     def simulate_paths(self, S: float, T: float, r: float, q: float = 0.0, n_paths: int = 1000, n_steps: int = 252,
                        seed: Optional[int] = None, *, method: Literal["pseudo", "qmc"] = "pseudo",
                        path_construction: Literal["bridge", "sequential"] = "bridge",
@@ -401,6 +491,61 @@ def greeks_heston(heston_pricer, S: float, K: float, T: float, r: float, sigma: 
     from .greeks import compute_greeks_unified
 
     return compute_greeks_unified(HestonAdapter(heston_pricer), S, K, T, r, sigma, option_type, q)
+
+
+class HestonMCAdapter:
+    """HestonAdapter's convention (sigma -> v0 = sigma^2, unified_greeks.py:74-104) over the device's own Monte Carlo price:
+    ``price`` is price_monte_carlo of a COPY of the model with v0 = sigma^2 at the adapter's n_paths, n_steps, seed, antithetic, method
+    and path_construction -- the wrapped pricer is never mutated -- so compute_greeks_unified(adapter, ...) differentiates the price
+    price_monte_carlo gives.  seed=None draws one seed at construction: every bump sees the same random numbers, as
+    MonteCarloPricer's do.  The adapter carries _fused_greeks, so compute_greeks_unified prices the 7 / 8 / 11 / 14 bumped contracts
+    as ONE scenario launch of four recursions (olmc_heston_greeks_fd / olmc_heston_qmc_greeks_fd); fused=False goes the one launch
+    per evaluation way and gives the same numbers to rounding.  Euler scheme only: QE Greeks are out of scope here.
+    Refused (ValueError, before the device is touched): what price_monte_carlo refuses, and scheme="qe"."""
+
+    def __init__(self, pricer: HestonPricer, n_paths: int = 100000, n_steps: int = 252, seed: Optional[int] = None, antithetic: bool = False, *,
+                 method: Literal["pseudo", "qmc"] = "pseudo", path_construction: Literal["bridge", "sequential"] = "bridge",
+                 scheme: Literal["euler", "qe"] = "euler"):
+        if n_paths < 1 or n_steps < 1:
+            raise ValueError("n_paths and n_steps must be >= 1")
+        _check_euler_only(scheme, "HestonMCAdapter")
+        self.heston = pricer
+        self.n_paths, self.n_steps, self.antithetic = int(n_paths), int(n_steps), bool(antithetic)
+        self.method, self.path_construction = method, path_construction
+        self.seed = int(seed) if seed is not None else int(np.random.default_rng().integers(0, 2**31))
+        self._qmc = _qmc_tables(method, path_construction, self.n_paths, self.n_steps, self.seed)      # the refusals, and the tables once
+
+    def price(self, S, K, T, r, sigma, option_type, q=0.0, **kwargs) -> float:
+        model = copy.copy(self.heston)
+        model.v0 = sigma**2
+        return model.price_monte_carlo(S, K, T, r, q, option_type, self.n_paths, self.n_steps, self.seed, self.antithetic,
+                                       method=self.method, path_construction=self.path_construction, **kwargs)
+
+    def _can_fuse(self, pricer_kwargs) -> bool:
+        return not pricer_kwargs
+
+    def _fused_greeks(self, S, K, T, r, sigma, option_type, q, include_second_order, seed=None):
+        h = self.heston
+        if self._qmc is not None:
+            sv, shift, bridge = self._qmc
+            vals, _ = _hip.heston_qmc_greeks_fd(S, K, T, r, sigma, q, option_type == "call", h.kappa, h.theta, h.sigma_v, h.rho, self.n_paths,
+                                                sv, shift, bridge, self.antithetic, include_second_order, want_evals=False)
+        else:
+            vals, _ = _hip.heston_greeks_fd(S, K, T, r, sigma, q, option_type == "call", h.kappa, h.theta, h.sigma_v, h.rho, self.n_paths,
+                                            self.n_steps, self.seed, self.antithetic, include_second_order, want_evals=False)
+        keys = ("price", "delta", "gamma", "vega", "theta", "rho", "vanna", "charm", "vomma")
+        return OrderedDict((k, np.float64(v)) for k, v in zip(keys if include_second_order else keys[:6], vals))
+
+
+def greeks_heston_monte_carlo(heston_pricer, S: float, K: float, T: float, r: float, sigma: Optional[float] = None,
+                              option_type: str = "call", q: float = 0.0, include_second_order: bool = True, **adapter_kwargs):
+    """compute_greeks_unified over HestonMCAdapter(heston_pricer, **adapter_kwargs): the finite-difference Greeks of the Monte Carlo
+    price in one launch.  sigma=None differentiates at the model's own start, sigma = sqrt(v0).  Euler scheme only."""
+    from .greeks import compute_greeks_unified
+
+    if sigma is None:
+        sigma = float(np.sqrt(heston_pricer.v0))
+    return compute_greeks_unified(HestonMCAdapter(heston_pricer, **adapter_kwargs), S, K, T, r, sigma, option_type, q, include_second_order)
 
 
 def calibration_objective(market_data: dict, *, n_paths: int = 1 << 14, n_steps: Optional[int] = None, seed: int = 0,
