@@ -787,7 +787,20 @@ int olmc_normals(uint64_t seed, int64_t path_offset, int64_t n_paths, int32_t n_
  * timed.  olmc_kernel_time returns the number of launches timed and their total milliseconds since the last reset. */
 int olmc_profile_enable(int on);
 /* Tuning knob for A/B measurements (results never change, only the launch shape):
- *   OLMC_TUNE_GRID_CAP   max workgroups per launch, 0 = default (larger jobs grid-stride)
+ *   OLMC_TUNE_GRID_CAP   max workgroups of a launch whose kernel strides over its work, 0 = default (2^18 workgroups of 256 paths, 4,096
+ *                        below 129 steps; 8,192 workgroups of four waves for the Sobol path kernels).  It reaches every Philox
+ *                        pricing launch (European prices, batches, control variate and terminal array -- a capped European launch has
+ *                        no split tail and no Philox table --, the exotic, structured, jump and Heston kernels, surfaces, scenario
+ *                        sets and products), the path matrices and the American chain's path launch, the one-point and eight-point
+ *                        European Sobol kernels, and every Sobol path launch: a wave per point (Asian, barrier, lookback,
+ *                        autocallable, cliquet and their fused Greeks) or per block of 64 points (the path matrices, every Heston
+ *                        Sobol kernel -- the bridge then reuses each wave's slab over several blocks).
+ *                        It does NOT reach the fused Philox Greeks (olmc_european_greeks_fd, olmc_asian_greeks_fd,
+ *                        olmc_extrema_greeks_fd) nor the fused Sobol batch (olmc_european_qmc_batch / _qmc_greeks_fd): they keep their
+ *                        grid, which for all but the first must cover every path.  Nor the split Sobol workgroups (64 points each,
+ *                        no stride; beyond 2^24 points, where OLMC_TUNE_QMC_BLOCK = 2 would ask for more than 2^18 of them, the launch
+ *                        takes one point per thread), and olmc_european_multi.  The American chain's step kernels run one workgroup per CU at
+ *                        most and stride already; a cap below the CU count lowers them too.  The smallest value, 1, makes one workgroup walk the whole launch
  *   OLMC_TUNE_QMC_BLOCK  Sobol kernels: 0 = by size (default): from 16 dimensions on a workgroup takes 64 points and each of its four waves
  *                        a quarter of the dimensions -- where the point offset is a multiple of 64 and there are 32 dimensions or more,
  *                        with the high Gray-code bits' direction numbers folded once per wave and dimension --; from 2^22 points on (2^21

@@ -57,7 +57,6 @@ int fail(int code, const std::string& msg) {
 
 constexpr int kMaxDevices = 16;
 constexpr int kMaxNV = 2 * OLMC_MAX_BATCH;       // values per workgroup row
-constexpr int32_t kMaxGrid = 1 << 18;            // workgroups per launch; larger jobs grid-stride
 constexpr int32_t kMaxGroups = kMaxGrid / kGroupBlocks + 1;
 static_assert(kMaxGroups * kMaxNV == kGroupRowsCapacity, "device-side guard must match the group_rows allocation");
 
@@ -384,7 +383,7 @@ int copy_to_host(DeviceCtx* c, void* dst, const void* d_src, size_t bytes) {
 
 // Tuning knob (olmc_tune): 0 = automatic.
 int g_multi_launch = 0;      // OLMC_TUNE_MULTI_LAUNCH: 0 = multi-GPU calls queue their ranks from one launcher thread per device (default), -1 = serial
-int g_grid_cap = 0;          // OLMC_TUNE_GRID_CAP: max workgroups per launch (0 = kMaxGrid)
+int g_grid_cap = 0;          // OLMC_TUNE_GRID_CAP: max workgroups of a launch whose kernel strides (0 = kMaxGrid, kQmcPathMaxGrid)
 int g_qmc_block = 0;         // OLMC_TUNE_QMC_BLOCK: 0 = by size, 1 = always eight points per thread, -1 = never (and never split), 2 = always split
 int g_poll = 0;              // OLMC_TUNE_POLL: 0 = blocking calls poll a host-mapped flag for completion (default), -1 = hipStreamSynchronize
 int g_split_tail = 0;        // OLMC_TUNE_SPLIT_TAIL: 0 = split workgroups for the remainder of a European launch (default), -1 = never
@@ -401,18 +400,8 @@ std::atomic<int> g_expect_table_misses{0};   // ... and this counts the launches
 
 // Launch geometry: one workgroup per 256 paths, handed out by the hardware dispatcher
 // (measured faster than a fixed 8-workgroups-per-CU grid-stride); beyond kMaxGrid
-// workgroups the kernels grid-stride.
-// Short paths (n_steps <= 128, the reference's default is ONE step) are bounded by per-workgroup costs
-// (dispatch, row store, ticket), not by the step loop: there 16 workgroups per CU that grid-stride beat
-// one workgroup per 256 paths (8M x 4: 63 -> 43 us, 8M x 32: 143 -> 125 us; equal from 128 steps on,
-// a one-off probe of round 3, profiles/HISTORY.md).
-constexpr int32_t kShortPathSteps = 128, kShortPathGrid = 4096;
-
-int32_t grid_for(int64_t n_paths, int32_t n_steps = INT32_MAX) {
-    int64_t cap = g_grid_cap > 0 ? std::min<int64_t>(g_grid_cap, kMaxGrid) : kMaxGrid;
-    if (g_grid_cap == 0 && n_steps <= kShortPathSteps) cap = kShortPathGrid;
-    return static_cast<int32_t>(std::min<int64_t>((n_paths + kBlock - 1) / kBlock, cap));
-}
+// workgroups the kernels grid-stride (olmc_host_math.h: path_grid, with the short paths' bound).
+int32_t grid_for(int64_t n_paths, int32_t n_steps = INT32_MAX) { return path_grid(n_paths, n_steps, g_grid_cap); }
 
 // Resident workgroups per compute unit of one kernel instantiation (register / LDS limited), asked of the runtime once.
 template <typename Kernel>
@@ -445,11 +434,13 @@ int resident_workgroups(Kernel kernel) {
 // rather than in rounds (first workgroup of a 7-per-CU launch done after 9 us, last after 48: profiles/r03_phase_stamps.jsonl),
 // and OLMC_TUNE_SPLIT_SAT at 2 / 5 / 7 left the 1M x 252 kernel at 100.35 us +- 0.1 (profiles/r03_ab_kernels.txt).  The knob
 // stays for measurements; the default is off.
-int32_t european_launch_shape(const DeviceCtx* c, PathRange* pr, int occ) {
+// keep_grid: the launch takes the default grid whatever OLMC_TUNE_GRID_CAP says (the fused Greeks, as the exotic fused Greeks do).
+int32_t european_launch_shape(const DeviceCtx* c, PathRange* pr, int occ, bool keep_grid = false) {
     pr->split_from = INT32_MAX;
-    const int32_t grid = grid_for(pr->count, pr->n_steps);
+    const int grid_cap = keep_grid ? 0 : g_grid_cap;
+    const int32_t grid = path_grid(pr->count, pr->n_steps, grid_cap);
     const int64_t wgs = (pr->count + kBlock - 1) / kBlock;
-    if (g_split_tail < 0 || g_grid_cap != 0 || wgs != grid) return grid;           // tuned or grid-striding launches keep their shape
+    if (g_split_tail < 0 || grid_cap != 0 || wgs != grid) return grid;           // tuned or grid-striding launches keep their shape
     if ((pr->n_steps >> 2) / kGroup < 4 || c->cus < 1) return grid;
     int64_t per_cu = (pr->count / kBlock) / c->cus;                                 // whole 256-path workgroups per CU
     if (occ >= 1 && g_split_sat > 0) {
@@ -747,12 +738,13 @@ GbmStep gbm_step(double T, int32_t n_steps, double r, double q, double sigma) {
 int run_batch_device(DeviceCtx* c, hipStream_t s, const olmc_option* opts, int32_t k, int64_t path_offset,
                      int64_t n_local, int32_t n_steps, uint64_t seed, int antithetic, double* d_out, double tail,
                      int* pos /* [k]: slot of contract i in d_out, may be NULL when k == 1 */, bool profiled, bool* sums_only = nullptr
-                     /* in: the caller needs no sums of squares; out: the launch made left ONE sum per slot (d_out[slot]) */) {
+                     /* in: the caller needs no sums of squares; out: the launch made left ONE sum per slot (d_out[slot]) */,
+                     bool keep_grid = false /* european_launch_shape's */) {
     PathRange pr = make_range(path_offset, n_local, n_steps, seed);
     const bool anti = antithetic != 0;
     const int nsets = k == 1 ? 1 : (k <= 8 ? 8 : 16);
     const int occ = nsets == 1 ? european_occupancy<1, kReduce>(anti) : (nsets == 8 ? european_occupancy<8, kReduce>(anti) : european_occupancy<16, kReduce>(anti));
-    const int32_t grid = european_launch_shape(c, &pr, occ);
+    const int32_t grid = european_launch_shape(c, &pr, occ, keep_grid);
     // prices only (finite-difference Greeks without their evaluations' standard errors): the sum-only form of the fused kernels,
     // where the launch covers every path
     const bool lean = sums_only && *sums_only && nsets > 1 && static_cast<int64_t>(grid) * kBlock >= n_local;
@@ -854,7 +846,7 @@ int sync_or_recover(DeviceCtx* c, hipStream_t s) {
 }
 
 int run_batch(const olmc_option* opts, int32_t k, int64_t path_offset, int64_t n_local, int32_t n_steps,
-              uint64_t seed, int antithetic, olmc_stats* out, bool prices_only = false) {
+              uint64_t seed, int antithetic, olmc_stats* out, bool prices_only = false, bool keep_grid = false) {
     if (!opts || !out) return fail(OLMC_ERR_ARG, "null pointer");
     if (k < 1 || k > OLMC_MAX_BATCH) return fail(OLMC_ERR_ARG, "batch size must be in [1, OLMC_MAX_BATCH]");
     int rc = check_paths(path_offset, n_local, n_steps);
@@ -865,7 +857,7 @@ int run_batch(const olmc_option* opts, int32_t k, int64_t path_offset, int64_t n
     DeviceCtx* const c = lease.c;
     int pos[OLMC_MAX_BATCH];
     bool lean = prices_only;
-    rc = run_batch_device(c, c->stream, opts, k, path_offset, n_local, n_steps, seed, antithetic, c->d_result, -1.0, pos, true, &lean);
+    rc = run_batch_device(c, c->stream, opts, k, path_offset, n_local, n_steps, seed, antithetic, c->d_result, -1.0, pos, true, &lean, keep_grid);
     if (rc) return rc;
     finish_set(c->h_result, pos, n_local * (antithetic ? 2 : 1), opts, k, false, lean, out);
     return OLMC_OK;
@@ -1139,7 +1131,7 @@ extern "C" int olmc_european_greeks_fd(double S, double K, double T, double r, d
     if (!(T > 0.0)) return fail(OLMC_ERR_ARG, "T must be > 0 (price() returns intrinsic value without simulating)");
     const GreeksSet gs(S, K, T, r, sigma, q, is_call, second_order);
     olmc_stats st[OLMC_MAX_BATCH];
-    int rc = run_batch(gs.o, gs.k, 0, n_paths, n_steps, seed, 1, st, /*prices_only=*/evals == nullptr);     // no evaluations asked for: no sums of squares
+    int rc = run_batch(gs.o, gs.k, 0, n_paths, n_steps, seed, 1, st, /*prices_only=*/evals == nullptr, /*keep_grid=*/true);     // no evaluations asked for: no sums of squares
     if (rc) return rc;
     gs.finish(st, T, out9, evals);
     return OLMC_OK;
@@ -1932,26 +1924,14 @@ int qmc_check(const uint32_t* sv, const uint32_t* shift, int32_t bits, int32_t d
 // 2^19 x 16: 36 / 32, 2^20 x 16: 65 / 48, 2^19 x 32: 52 / 52, 2^20 x 32: 97 / 82, 2^19 x 48: 68 / 73, 2^20 x 48: 128 / 117, 2^20 x 64:
 // 158 / 171, 2^21 x 64: 310 / 293, 2^20 x 252: 530 / 638, 2^21 x 252: 1050 / 1107, 2^22 x 252: 2106 / 2074.  OLMC_TUNE_QMC_BLOCK:
 // 1 = always eight points per thread, 2 = always split, -1 = never eight and never split (one point per thread).
-struct QmcShape {
-    bool blocks, split, aligned, aligned8;
-    int64_t units;       // threads' worth of work: blocks of eight, or points
-    int32_t grid;
-};
+// A split grid that one launch cannot hold falls back to one point per thread.  The arithmetic is olmc_host_math.h's qmc_launch_shape.
 QmcShape qmc_shape(int64_t point_offset, int64_t n_paths, int32_t dims) {
-    QmcShape sh;
-    // split workgroups whose 64 lanes are a 64-ALIGNED block of points fold the high Gray bits' direction numbers once per wave and
+    // QmcShape::aligned: split workgroups whose 64 lanes are a 64-ALIGNED block of points fold the high Gray bits' direction numbers once per wave and
     // dimension and keep the inverse normal's coefficients in registers (olmc_kernels.h qmc_point_sum<true>).  The coefficients'
     // load and the fold's prologue are a fixed cost per wave: it pays from 32 dimensions on (8 per wave; 2^17 x 32: 21.5 -> 19.9 us,
     // 2^18 x 48: 44.6 -> 38.4, 2^14 x 32: even; 16 dimensions: 8.6 -> 8.9, 12.0 -> 12.3).  The one-point form is left to launches of
     // fewer than 16 dimensions and to the knob
-    sh.aligned = (point_offset & 63) == 0 && dims >= 32;
-    sh.aligned8 = (point_offset & 511) == 0;        // eight points per thread: a wave's 64 blocks start at a multiple of 512 points
-    const int blocks_from_log2 = dims < 32 ? 19 : dims < 64 ? 20 : dims < 128 ? 21 : 22;      // fewer dimensions: less for a split wave to spread its fixed costs over
-    sh.blocks = g_qmc_block == 1 ? true : (g_qmc_block != 0 ? false : n_paths >= (int64_t(1) << blocks_from_log2));
-    sh.split = !sh.blocks && (g_qmc_block == 0 || g_qmc_block == 2) && dims >= 16;
-    sh.units = sh.blocks ? (point_offset + n_paths + kQmcBlock - 1) / kQmcBlock - point_offset / kQmcBlock : n_paths;
-    sh.grid = sh.split ? static_cast<int32_t>((n_paths + kWave - 1) / kWave) : grid_for(sh.units);
-    return sh;
+    return qmc_launch_shape(point_offset, n_paths, dims, g_qmc_block, g_grid_cap);
 }
 
 // The Sobol shape ladder of the European kernels (qmc_shape), MODE kReduce / kControlVariate / kTerminal.
@@ -2132,8 +2112,8 @@ void launch_qmc_path_greeks(bool bridge, bool anti, int nsets, int32_t grid, hip
     });
 }
 
-// Workgroups of a QMC path launch: four points in flight per workgroup, grid-striding beyond kQmcPathMaxGrid.
-constexpr int64_t kQmcPathMaxGrid = 8192;
+// Workgroups of a QMC path launch: four points in flight per workgroup, grid-striding beyond kQmcPathMaxGrid (olmc_host_math.h:
+// qmc_point_grid) -- every kernel launched on QmcPathLaunch::grid strides, the fused path Greeks included.
 
 // The argument checks of a Sobol path call, before any context is leased.  A step takes dims_per_step dimensions of the table (1: the GBM
 // paths, 2: Heston's two factors).
@@ -2176,7 +2156,7 @@ int qmc_path_setup(DeviceCtx* c, int construction, int64_t point_offset, int64_t
     pl->qr.count = n_points;
     pl->qr.dims = n_steps;
     pl->qr.mirror = antithetic ? 1 : 0;
-    pl->grid = static_cast<int32_t>(std::min<int64_t>((n_points + kWavesPerBlock - 1) / kWavesPerBlock, kQmcPathMaxGrid));
+    pl->grid = qmc_point_grid(n_points, g_grid_cap);
     pl->anti = antithetic != 0;
     pl->inv_steps = 1.0 / n_steps;
     return OLMC_OK;
@@ -2362,9 +2342,7 @@ int qmc_matrix_prologue(int construction, int64_t n_points, int32_t n_steps, con
 }
 
 // Workgroups of a lanes-over-points launch: one wave per aligned block of 64 points, grid-striding beyond kQmcPathMaxGrid.
-int32_t qmc_block_grid(int64_t blocks) {
-    return static_cast<int32_t>(std::min<int64_t>((blocks + kWavesPerBlock - 1) / kWavesPerBlock, kQmcPathMaxGrid));
-}
+int32_t qmc_block_grid(int64_t blocks) { return qmc_blocks_grid(blocks, g_grid_cap); }
 
 // Sobol points [0, n_points) as the path matrix d_paths (lsm_qmc_paths_kernel), queued on c's stream behind the tables and the plan.
 int qmc_matrix(DeviceCtx* c, int construction, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift, const LsmContract& lc,
@@ -2455,13 +2433,11 @@ namespace {
 // three or four) and strides over the blocks beyond, and
 // the slabs of a launch stay under kHestonSlabCap (the grid shrinks further): the buffer follows the device and n, not the number of
 // points -- 0.5 GiB at 252 steps and 1 GiB from 504 steps on with 256 CUs, kept with the context.
-constexpr size_t kHestonSlabCap = size_t(1) << 30;
-constexpr int32_t kHestonBridgeBlocksPerCu = 2;
+// The sizes are olmc_host_math.h's heston_slab_shape.
 int heston_slabs(DeviceCtx* c, int32_t n_steps, int32_t* grid) {
-    const size_t slab = 2 * static_cast<size_t>(n_steps) * kWave * sizeof(double);          // <= 1 MiB (n <= 1024)
-    const int32_t fit = static_cast<int32_t>(std::max<size_t>(kHestonSlabCap / (slab * kWavesPerBlock), 1));
-    *grid = std::min(*grid, std::min(fit, std::max(c->cus, 1) * kHestonBridgeBlocksPerCu));
-    const size_t bytes = slab * kWavesPerBlock * static_cast<size_t>(*grid);
+    const HestonSlabs hs = heston_slab_shape(n_steps, *grid, c->cus);
+    *grid = hs.grid;
+    const size_t bytes = hs.bytes;
     if (bytes <= c->heston_w_bytes) return OLMC_OK;
     if (c->d_heston_w) {
         HIP_TRY(hipStreamSynchronize(c->stream));                // a launch may still walk the old slabs

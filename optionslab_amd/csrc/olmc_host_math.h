@@ -3,6 +3,7 @@
 // olmc.hip includes for the product and tests/test_host_math_sanitizers.py compiles on its own with
 // `g++ -fsanitize=address,undefined` (tests/host_math_harness.cpp) -- the 8 / 14-contract layouts, the finite-difference formulas
 // and the moment combiners are the code that feeds every fused and every multi-GPU call, and none of it needs a GPU to be checked.
+// The launch geometry (how many workgroups a launch of a given size gets under the tuning knobs) lives here for the same reason.
 //
 // Reference arithmetic restated here (paths relative to the reference repository root):
 //   make_contract        src/simulation/gbm_numpy.py:35-39
@@ -574,6 +575,79 @@ inline void qmc_shard_range(int64_t n_points, int rank, int n_ranks, int64_t* lo
     const int64_t b = rank + 1 == n_ranks ? n_points : n_points * (rank + 1) / n_ranks / kQmcShardAlign * kQmcShardAlign;
     *lo = a;
     *count = b - a;
+}
+
+// ------------------------------------------------------------ launch geometry ----
+// How many workgroups a launch gets, as functions of its size, the tuning knobs (olmc.h: olmc_tune) and the device's CU count.
+// olmc.hip passes its knobs and the context's CUs; tests/host_math_harness.cpp sweeps them.  grid_cap = OLMC_TUNE_GRID_CAP (0 = none):
+// it only ever lowers a grid whose kernel strides over the work beyond it, so no result depends on it.
+constexpr int kBlock = 256;          // 4 wavefronts of 64
+constexpr int kWave = 64;
+constexpr int kWavesPerBlock = kBlock / kWave;
+constexpr int kQmcBlock = 8;         // points per thread of the eight-points form of the European Sobol kernels
+constexpr int32_t kMaxGrid = 1 << 18;            // workgroups per launch; larger jobs grid-stride
+// Short paths (n_steps <= 128, the reference's default is ONE step) are bounded by per-workgroup costs (dispatch, row store, ticket), not
+// by the step loop: there 16 workgroups per CU that grid-stride beat one workgroup per 256 paths (8M x 4: 63 -> 43 us, 8M x 32:
+// 143 -> 125 us; equal from 128 steps on, a one-off probe of round 3, profiles/HISTORY.md).
+constexpr int32_t kShortPathSteps = 128, kShortPathGrid = 4096;
+constexpr int64_t kQmcPathMaxGrid = 8192;        // workgroups of a Sobol path launch: four waves, a point or a block of 64 points each
+constexpr size_t kHestonSlabCap = size_t(1) << 30;
+constexpr int32_t kHestonBridgeBlocksPerCu = 2;
+
+// One workgroup per 256 paths (n_paths >= 1), handed out by the hardware dispatcher; beyond the bound the kernels grid-stride.
+inline int32_t path_grid(int64_t n_paths, int32_t n_steps, int grid_cap) {
+    int64_t cap = grid_cap > 0 ? std::min<int64_t>(grid_cap, kMaxGrid) : kMaxGrid;
+    if (grid_cap == 0 && n_steps <= kShortPathSteps) cap = kShortPathGrid;
+    return static_cast<int32_t>(std::min<int64_t>((n_paths + kBlock - 1) / kBlock, cap));
+}
+
+// A Sobol path launch whose waves take one unit at a time -- a point (lanes over dates), or an aligned block of 64 points (lanes over
+// points) -- and stride over the units beyond the grid: four units in flight per workgroup.
+inline int32_t qmc_wave_grid(int64_t units, int grid_cap) {
+    const int64_t cap = grid_cap > 0 ? std::min<int64_t>(grid_cap, kQmcPathMaxGrid) : kQmcPathMaxGrid;
+    return static_cast<int32_t>(std::min<int64_t>((units + kWavesPerBlock - 1) / kWavesPerBlock, cap));
+}
+inline int32_t qmc_point_grid(int64_t n_points, int grid_cap) { return qmc_wave_grid(n_points, grid_cap); }
+inline int32_t qmc_blocks_grid(int64_t blocks, int grid_cap) { return qmc_wave_grid(blocks, grid_cap); }
+
+// Launch shape of a European Sobol kernel (olmc.hip: qmc_shape tells what was measured).  qmc_block = OLMC_TUNE_QMC_BLOCK.  A split
+// workgroup takes 64 points and has no stride loop: its grid covers every point, whatever grid_cap says, so a split grid that one
+// launch cannot hold (more than kMaxGrid workgroups: beyond 2^24 points, which only qmc_block = 2 asks for) falls back to one point
+// per thread, which strides.
+struct QmcShape {
+    bool blocks, split, aligned, aligned8;
+    int64_t units;       // threads' worth of work: blocks of eight, or points
+    int32_t grid;
+};
+inline QmcShape qmc_launch_shape(int64_t point_offset, int64_t n_paths, int32_t dims, int qmc_block, int grid_cap) {
+    QmcShape sh;
+    sh.aligned = (point_offset & 63) == 0 && dims >= 32;
+    sh.aligned8 = (point_offset & 511) == 0;        // eight points per thread: a wave's 64 blocks start at a multiple of 512 points
+    const int blocks_from_log2 = dims < 32 ? 19 : dims < 64 ? 20 : dims < 128 ? 21 : 22;      // fewer dimensions: less for a split wave to spread its fixed costs over
+    sh.blocks = qmc_block == 1 ? true : (qmc_block != 0 ? false : n_paths >= (int64_t(1) << blocks_from_log2));
+    const int64_t split_grid = (n_paths + kWave - 1) / kWave;
+    sh.split = !sh.blocks && (qmc_block == 0 || qmc_block == 2) && dims >= 16 && split_grid <= kMaxGrid;
+    sh.units = sh.blocks ? (point_offset + n_paths + kQmcBlock - 1) / kQmcBlock - point_offset / kQmcBlock : n_paths;
+    sh.grid = sh.split ? static_cast<int32_t>(split_grid) : path_grid(sh.units, INT32_MAX, grid_cap);
+    return sh;
+}
+
+// The bridge slabs of the Heston Sobol kernels: one [2 n][64] slab of doubles per wave of the grid.  The grid the launch starts from is
+// cut to the workgroups the device holds at once (kHestonBridgeBlocksPerCu per CU) and to what keeps the slabs under kHestonSlabCap;
+// the waves stride over the blocks beyond, each reusing its slab.
+struct HestonSlabs {
+    size_t slab;         // bytes of one wave's slab: <= 1 MiB (n <= 1024)
+    int32_t fit;         // workgroups whose slabs stay under the cap (at least one)
+    int32_t grid;
+    size_t bytes;        // of the whole launch's slabs
+};
+inline HestonSlabs heston_slab_shape(int32_t n_steps, int32_t grid, int cus) {
+    HestonSlabs s;
+    s.slab = 2 * static_cast<size_t>(n_steps) * kWave * sizeof(double);
+    s.fit = static_cast<int32_t>(std::max<size_t>(kHestonSlabCap / (s.slab * kWavesPerBlock), 1));
+    s.grid = std::min(grid, std::min(s.fit, std::max(cus, 1) * kHestonBridgeBlocksPerCu));
+    s.bytes = s.slab * kWavesPerBlock * static_cast<size_t>(s.grid);
+    return s;
 }
 
 }  // namespace olmc

@@ -17,9 +17,7 @@
 
 namespace olmc {
 
-constexpr int kBlock = 256;          // 4 wavefronts of 64
-constexpr int kWave = 64;
-constexpr int kWavesPerBlock = kBlock / kWave;
+// kBlock (256 = 4 wavefronts of kWave = 64), kWavesPerBlock: olmc_host_math.h (the host sizes every grid from them)
 
 // ---------------------------------------------------------------- Philox ----
 // kPhiloxM0, kPhiloxM1, kPhiloxW0, kPhiloxW1: olmc_host_math.h (the host builds the prefix table of a launch from them)
@@ -2879,8 +2877,7 @@ __global__ __launch_bounds__(kBlock) void european_qmc_kernel(QmcRange qr, Contr
 // consecutive points differ in one direction number, and inside an aligned block of eight those are sv[t][0], [1], [0], [2],
 // [0], [1], [0] -- the same for every lane, i.e. scalar operands: 28 + 7 v_bitop3 / v_xor per dimension for eight points
 // instead of 8 x 30, and eight independent inverse normals in flight per thread.  Same points, same uniforms, same z as
-// the one-point kernel; only the order in which a workgroup's payoffs are added differs (1e-16).
-constexpr int kQmcBlock = 8;
+// the one-point kernel; only the order in which a workgroup's payoffs are added differs (1e-16).  kQmcBlock = 8: olmc_host_math.h.
 
 // Sums of the inverse normals of the eight points of an aligned block over all dimensions, in the canonical association (quarters,
 // see qmc_quarter_begin), left in LDS: zs[p][threadIdx.x].  mask[b], b >= B0 = 2, are the Gray-code masks of the block's first point

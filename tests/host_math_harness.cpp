@@ -1,5 +1,6 @@
 // CPU-only harness over optionslab_amd/csrc/olmc_host_math.h -- the pure-host arithmetic that feeds every fused and every multi-GPU
-// call of libolmc.so (contract layouts, the 8 / 14 evaluations of compute_greeks_unified, moment combiners, shard ranges).  Built by
+// call of libolmc.so (contract layouts, the 8 / 14 evaluations of compute_greeks_unified, moment combiners, shard ranges, launch
+// geometry).  Built by
 // tests/test_host_math_sanitizers.py with g++ -fsanitize=address,undefined; no HIP, no device.
 //
 //   harness self                                  property checks over a parameter sweep; prints "ok <count>" or aborts
@@ -239,6 +240,82 @@ static void check_shards() {
         }
 }
 
+// Launch geometry (path_grid, the Sobol path grids, qmc_launch_shape, heston_slab_shape) over sizes, knobs, caps and CU counts: every
+// grid is at least one workgroup and at most its bound, a split grid never exceeds kMaxGrid, an uncapped grid is the formula restated
+// here, and the Heston slabs are grid x 4 waves x 2 n x 64 doubles under kHestonSlabCap.
+static void check_geometry() {
+    const int64_t two24 = int64_t(1) << 24, two26 = int64_t(1) << 26;
+    std::vector<int64_t> counts = {1, 2, 3, 4, 5, 63, 64, 65, 255, 256, 257, 511, 512, 513, 769, 1000, 2000, 32767, 32768, 32769, 131072,
+                                   (int64_t(1) << 19) - 1, int64_t(1) << 19, int64_t(1) << 20, int64_t(1) << 21, (int64_t(1) << 22) - 1,
+                                   int64_t(1) << 22, two26 - 1, two26, two26 + 1, (int64_t(1) << 30) - 1, int64_t(1) << 30};
+    for (int64_t d = -64; d <= 64; ++d) counts.push_back(two24 + d);
+    const int caps[] = {0, 1, 3, 4096, (1 << 18) + 1};
+    const int32_t dims[] = {1, 15, 16, 31, 32, 63, 64, 127, 128, 252, 1024, 21201};
+    const int32_t steps[] = {1, 2, 5, 13, 67, 127, 128, 129, 130, 252, 257, 504, 1023, 1024};
+    const int cus[] = {1, 104, 256};
+    auto ceil_div = [](int64_t a, int64_t b) { return (a + b - 1) / b; };
+    for (int64_t n : counts)
+        for (int cap : caps) {
+            // Philox paths: one workgroup per 256 paths up to the bound
+            for (int32_t m : steps) {
+                for (int32_t mm : {m, INT32_MAX}) {
+                    const int32_t grid = path_grid(n, mm, cap);
+                    const int64_t limit = cap > 0 ? std::min<int64_t>(cap, kMaxGrid) : kMaxGrid;
+                    REQUIRE(grid >= 1 && grid <= limit && grid <= ceil_div(n, 256));
+                    if (cap == 0) REQUIRE(grid == std::min<int64_t>(ceil_div(n, 256), mm <= 128 ? 4096 : 262144));
+                    else REQUIRE(grid == std::min<int64_t>(ceil_div(n, 256), limit));
+                    ++g_checks;
+                }
+            }
+            // Sobol paths: a wave per point, or per block of 64 points
+            const int64_t blocks = ceil_div(n, 64);
+            for (int form = 0; form < 2; ++form) {
+                const int64_t units = form ? blocks : n;
+                const int32_t grid = form ? qmc_blocks_grid(units, cap) : qmc_point_grid(units, cap);
+                const int64_t limit = cap > 0 ? std::min<int64_t>(cap, kQmcPathMaxGrid) : kQmcPathMaxGrid;
+                REQUIRE(grid >= 1 && grid <= limit && grid <= ceil_div(units, 4));
+                REQUIRE(grid == std::min<int64_t>(ceil_div(units, 4), cap == 0 ? 8192 : limit));
+                ++g_checks;
+            }
+            // the Heston bridge slabs behind the block grid
+            for (int32_t m : steps)
+                for (int cu : cus) {
+                    const int32_t start = qmc_blocks_grid(blocks, cap);
+                    const HestonSlabs hs = heston_slab_shape(m, start, cu);
+                    REQUIRE(hs.grid >= 1 && hs.grid <= start && hs.fit >= 1);
+                    REQUIRE(hs.slab == size_t(2) * m * 64 * 8);
+                    REQUIRE(hs.bytes == size_t(hs.grid) * 4 * 2 * m * 64 * 8);
+                    REQUIRE(hs.bytes <= kHestonSlabCap);
+                    const int64_t fit = std::max<int64_t>((int64_t(1) << 30) / (int64_t(4096) * m), 1);
+                    REQUIRE(hs.fit == fit && hs.grid == std::min<int64_t>(start, std::min<int64_t>(fit, 2 * cu)));
+                    ++g_checks;
+                }
+            // the European Sobol shapes under every value of the shape knob
+            for (int32_t d : dims)
+                for (int knob = -1; knob <= 2; ++knob)
+                    for (int64_t first : {int64_t(0), int64_t(1), int64_t(64), int64_t(512), int64_t(4321)}) {
+                        if (first + n > (int64_t(1) << 30)) continue;                 // the entry points refuse points beyond 2^30
+                        const QmcShape sh = qmc_launch_shape(first, n, d, knob, cap);
+                        // the ladder as the library had it before the split grid learnt its bound
+                        const int from = d < 32 ? 19 : d < 64 ? 20 : d < 128 ? 21 : 22;
+                        const bool blocks8 = knob == 1 || (knob == 0 && n >= (int64_t(1) << from));
+                        const bool split_asked = !blocks8 && (knob == 0 || knob == 2) && d >= 16;
+                        const int64_t split_grid = ceil_div(n, 64);
+                        const bool split = split_asked && split_grid <= kMaxGrid;
+                        const int64_t units = blocks8 ? ceil_div(first + n, 8) - first / 8 : n;
+                        REQUIRE(sh.blocks == blocks8 && sh.split == split && sh.units == units);
+                        REQUIRE(sh.aligned == ((first % 64) == 0 && d >= 32) && sh.aligned8 == ((first % 512) == 0));
+                        REQUIRE(sh.grid >= 1 && sh.grid <= kMaxGrid);
+                        if (split_asked && !split) REQUIRE(knob == 2 && n > two24 && sh.grid == path_grid(n, INT32_MAX, cap));      // the fallback: one point per thread
+                        if (sh.split) REQUIRE(sh.grid == split_grid && int64_t(sh.grid) * 64 >= n);                   // covers every point, cap or no cap
+                        else REQUIRE(sh.grid == path_grid(units, INT32_MAX, cap) && (cap == 0 || sh.grid <= cap));
+                        if (cap == 0 && !sh.split) REQUIRE(sh.grid == std::min<int64_t>(ceil_div(units, 256), 262144));
+                        REQUIRE(int64_t(sh.grid) * 256 < (int64_t(1) << 32));
+                        ++g_checks;
+                    }
+        }
+}
+
 // "qmc-shards n p": the P ranges, one per line (the Python mirror is compared with them)
 static int print_qmc_shards(int64_t n, int p) {
     for (int d = 0; d < p; ++d) {
@@ -280,6 +357,7 @@ static int self_test() {
     }
     check_combiners();
     check_shards();
+    check_geometry();
     REQUIRE(poisoned(-1, 1, 1, 0, 0.2, 0) && poisoned(1, 1, -1, 0, 0.2, 0) && poisoned(1, std::nan(""), 1, 0, 0.2, 0) && !poisoned(1, 1, 1, -0.1, 0.2, 0));
     REQUIRE(log_level(0.0) == -INFINITY && log_level(-5.0) == -INFINITY && std::isnan(log_level(std::nan(""))) && log_level(1.0) == 0.0);
     olmc_stats st{};
