@@ -786,7 +786,12 @@ int olmc_normals(uint64_t seed, int64_t path_offset, int64_t n_paths, int32_t n_
  * more than 65535 contracts) are bracketed as a whole.  The ranks' launches of the multi-GPU entry points are not
  * timed.  olmc_kernel_time returns the number of launches timed and their total milliseconds since the last reset. */
 int olmc_profile_enable(int on);
-/* Tuning knob for A/B measurements (results never change, only the launch shape):
+/* Tuning knob for A/B measurements.  Only the launch shape changes: every path, point, payoff and exported array keeps its bits.
+ * OLMC_TUNE_POLL, _STAGED_COPY, _PHILOX_TABLE and _MULTI_LAUNCH also keep the bits of every reduced sum.  The knobs that regroup the
+ * samples over threads and workgroups -- OLMC_TUNE_GRID_CAP, _SPLIT_TAIL, _SPLIT_SAT and, for the European Sobol sums, _QMC_BLOCK (a
+ * thread that carries eight points adds its eight payoffs first) -- add the same payoffs in another association: sum and sumsq may move
+ * in their last bits.  A knob is process-wide and outlives olmc_shutdown; a call's bits depend on the knobs' values, never on the calls
+ * that ran before it (tests/test_gpu_call_history.py).
  *   OLMC_TUNE_GRID_CAP   max workgroups of a launch whose kernel strides over its work, 0 = default (2^18 workgroups of 256 paths, 4,096
  *                        below 129 steps; 8,192 workgroups of four waves for the Sobol path kernels).  It reaches every Philox
  *                        pricing launch (European prices, batches, control variate and terminal array -- a capped European launch has
@@ -806,7 +811,8 @@ int olmc_profile_enable(int on);
  *                        with the high Gray-code bits' direction numbers folded once per wave and dimension --; from 2^22 points on (2^21
  *                        below 128 dimensions, 2^20 below 64, 2^19 below 32) a thread takes eight consecutive points.  1 = always eight points per thread, 2 = always
  *                        split workgroups, -1 = always one point per thread.  Every shape returns the same terminal prices bit for bit
- *                        (one association of a point's normal sum)
+ *                        (one association of a point's normal sum); the sums of the payoffs over the points are associated by the
+ *                        shape (the eight-point shape differs from the other two in the last bit at 5 dimensions x 100 points)
  *   OLMC_TUNE_POLL       blocking calls: 0 = wait by polling the host-mapped flag the kernel raises behind its results
  *                        (default), -1 = hipStreamSynchronize
  *   OLMC_TUNE_SPLIT_TAIL European launches: 0 = the paths beyond a whole number of workgroups per compute unit go to split
