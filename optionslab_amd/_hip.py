@@ -51,6 +51,12 @@ class DevInfo(C.Structure):
                 ("clock_mhz", C.c_int32), ("wavefront", C.c_int32), ("device", C.c_int32), ("hbm_bytes", C.c_int64)]
 
 
+class LvSurface(C.Structure):
+    """ollv_surface (include/olmc_local_vol.h): a host table of local volatilities over (tau, x = ln(S_t / S))."""
+    _fields_ = [("vol", C.POINTER(C.c_double)), ("n_x", C.c_int32), ("n_t", C.c_int32), ("x_lo", C.c_double), ("x_hi", C.c_double),
+                ("t_hi", C.c_double)]
+
+
 _D, _I, _I32, _I64, _U64T, _P = C.c_double, C.c_int, C.c_int32, C.c_int64, C.c_uint64, C.c_void_p
 _byref = C.byref
 _Out9 = C.c_double * 9
@@ -147,6 +153,15 @@ PROTOTYPES = {
     "olmc_kernel_time": (_I, [C.POINTER(_I64), C.POINTER(_D)]),
 }
 
+# the same for include/olmc_local_vol.h (its own header and prefix: olmc.h and PROTOTYPES stay as they are)
+LV_EUROPEAN = 8
+LV_PROTOTYPES = {
+    "ollv_price": (_I, [_D] * 5 + [_I, C.POINTER(LvSurface), _I, _D, _I64, _I64, _I32, _U64T, _I, C.POINTER(Stats)]),
+    "ollv_paths": (_I, [_D] * 4 + [C.POINTER(LvSurface), _I64, _I32, _U64T, _I, C.POINTER(_D)]),
+    "ollv_surface_prices": (_I, [_D] * 4 + [_I, C.POINTER(LvSurface), C.POINTER(_D), C.POINTER(_I32), _I32, _I64, _I64, _I32, _U64T, _I,
+                                         C.POINTER(Stats)]),
+}
+
 _lock = threading.Lock()
 _lib: Optional[C.CDLL] = None
 _initialised = False
@@ -189,7 +204,7 @@ def load_library() -> C.CDLL:
                 lib = C.CDLL(LIBRARY_PATH)
             except OSError as e:
                 raise AccelerationError(f"cannot load {LIBRARY_PATH}: {e}", backend="hip") from e
-            for name, (res, args) in PROTOTYPES.items():
+            for name, (res, args) in list(PROTOTYPES.items()) + list(LV_PROTOTYPES.items()):
                 try:
                     fn = getattr(lib, name)
                 except AttributeError:
@@ -752,6 +767,47 @@ def heston_qmc_surface(S, T, r, q, is_call: bool, kappa, theta, sigma_v, rho, v0
 
 
 HESTON_MAX_RECURSIONS = 6          # OLMC_HESTON_MAX_RECURSIONS
+
+
+def lv_surface(vol, x_lo: float, x_hi: float, t_hi: float = 1.0):
+    """(LvSurface, the float64 array it points into -- keep it alive as long as the struct) for a table vol[n_t][n_x] (a 1-D table is one
+    row).  Shapes and values are checked by the library."""
+    vol = np.ascontiguousarray(vol, dtype=np.float64)
+    if vol.ndim == 1:
+        vol = vol[None, :]
+    if vol.ndim != 2:
+        raise ValueError("the local-volatility table must be [n_t][n_x]")
+    return LvSurface(vol.ctypes.data_as(C.POINTER(C.c_double)), vol.shape[1], vol.shape[0], float(x_lo), float(x_hi), float(t_hi)), vol
+
+
+def lv_price(S, K, T, r, q, is_call: bool, table, payoff: int, barrier: float, n_paths: int, n_steps: int, seed: int, antithetic: bool = False,
+             path_offset: int = 0) -> Stats:
+    """One payoff (BARRIER_KINDS value, LOOKBACK_*, PATH_ASIAN_* or LV_EUROPEAN) on local-volatility paths, one launch (ollv_price);
+    `table` = (vol[n_t][n_x], x_lo, x_hi, t_hi)."""
+    surf, _keep = lv_surface(*table)
+    out = Stats()
+    _check(lib().ollv_price(S, K, T, r, q, int(is_call), C.byref(surf), int(payoff), float(barrier), int(path_offset), int(n_paths), int(n_steps),
+                            seed64(seed), int(antithetic), C.byref(out)))
+    return out
+
+
+def lv_paths(S, T, r, q, table, n_paths: int, n_steps: int, seed: int, path_major: bool = False) -> np.ndarray:
+    """The spot matrix of lv_price's paths (ollv_paths), in gbm_paths' layouts."""
+    surf, _keep = lv_surface(*table)
+    out = _path_matrix(n_paths, n_steps, path_major)
+    _check(lib().ollv_paths(S, T, r, q, C.byref(surf), int(n_paths), int(n_steps), seed64(seed), int(path_major),
+                            out.ctypes.data_as(C.POINTER(C.c_double))))
+    return out
+
+
+def lv_surface_prices(S, T, r, q, is_call: bool, table, strikes, steps, n_paths: int, n_steps: int, seed: int, antithetic: bool = False,
+                      path_offset: int = 0) -> List[Stats]:
+    """European options at the cells (strikes[i], steps[i]) on lv_price's paths, one launch (ollv_surface_prices): at most 16 cells."""
+    surf, _keep = lv_surface(*table)
+    strikes, steps, pk, ps, out = _surface_cells(strikes, steps)
+    _check(lib().ollv_surface_prices(S, T, r, q, int(is_call), C.byref(surf), pk, ps, len(strikes), int(path_offset), int(n_paths), int(n_steps),
+                                     seed64(seed), int(antithetic), out))
+    return list(out)[:len(strikes)]
 
 
 def _scenarios(scenarios):

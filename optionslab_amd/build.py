@@ -8,7 +8,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 SOURCES = [os.path.join(PKG, "csrc", "olmc.hip")]
 HEADERS = [os.path.join(PKG, "csrc", "olmc_kernels.h"), os.path.join(PKG, "csrc", "olmc_host_math.h"), os.path.join(PKG, "csrc", "olmc_job_board.h"),
-           os.path.join(ROOT, "include", "olmc.h")]
+           os.path.join(PKG, "csrc", "olmc_local_vol_kernels.h"), os.path.join(ROOT, "include", "olmc.h"), os.path.join(ROOT, "include", "olmc_local_vol.h")]
 LIBRARY = os.path.join(PKG, "libolmc.so")
 # the instrumented build (include/olmc_probe.h): the same translation unit with its test seams compiled in + the measurement kernels.
 # Test / measurement infrastructure: lives under tools/, loaded by tests, tools and bench.py's calibration, never by the package.
@@ -33,9 +33,9 @@ def is_stale() -> bool:
     return any(os.path.getmtime(p) > built for p in SOURCES + HEADERS)
 
 
-def _compile(sources, output, extra_includes=(), verbose=False):
+def _compile(sources, output, extra_includes=(), verbose=False, defines=()):
     cmd = [_hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-shared", "-fPIC", "-ffp-contract=off",
-           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(PKG, "csrc"), *["-I" + d for d in extra_includes],
+           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(PKG, "csrc"), *["-I" + d for d in extra_includes], *["-D" + d for d in defines],
            "-o", output, *sources, "-ldl"]
     if verbose:
         print(" ".join(cmd))
@@ -56,6 +56,13 @@ def build_probe_library(force: bool = False, verbose: bool = False) -> str:
     if force or probe_is_stale():
         _compile(PROBE_SOURCES, PROBE_LIBRARY, extra_includes=(PROBE_DIR,), verbose=verbose)
     return PROBE_LIBRARY
+
+
+def build_variant(output: str, defines=(), extra_includes=(), verbose: bool = False) -> str:
+    """An A/B build of the product's translation unit with extra -D switches (measurement tools load it through $OLMC_LIBRARY)."""
+    os.makedirs(os.path.dirname(output), exist_ok=True)
+    _compile(SOURCES, output, extra_includes=extra_includes, verbose=verbose, defines=defines)
+    return output
 
 
 def build_library(force: bool = False, verbose: bool = False) -> str:

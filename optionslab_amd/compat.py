@@ -24,6 +24,7 @@ from . import exotic as _exotic
 from . import greeks as _greeks
 from . import heston as _heston
 from . import jump_diffusion as _jump
+from . import local_vol as _lv
 from . import monte_carlo as _mc
 from . import monte_carlo_unified as _uni
 from . import simulation as _sim
@@ -80,6 +81,9 @@ def _targets() -> dict:
         "src.pricing_models.iv_solver": _module("src.pricing_models.iv_solver", implied_volatility=_implied_volatility),
         "src.pricing_models.jump_diffusion": _module("src.pricing_models.jump_diffusion", MertonJumpDiffusion=_jump.MertonJumpDiffusion,
                                                      KouJumpDiffusion=_jump.KouJumpDiffusion),
+        # not re-exported by src/pricing_models/__init__.py: reached by its module path only, as in the reference
+        "src.pricing_models.local_vol": _module("src.pricing_models.local_vol", DupireLocalVol=_lv.DupireLocalVol, LocalVolSurface=_lv.LocalVolSurface,
+                                                create_sample_iv_surface=_lv.create_sample_iv_surface),
         "src.simulation": sim,
         "src.greeks.unified_greeks": _module("src.greeks.unified_greeks", compute_greeks_unified=_greeks.compute_greeks_unified,
                                              PricerProtocol=_greeks.PricerProtocol, ExoticAdapter=_greeks.ExoticAdapter,

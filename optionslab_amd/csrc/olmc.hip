@@ -6,7 +6,9 @@
 //   device: ONE path kernel (its last workgroup writes the reduced sums) -> 8*NV bytes D2H
 // and fails loudly when no HIP device is usable -- there is no CPU fallback.
 #include "olmc.h"
+#include "olmc_local_vol.h"
 #include "olmc_kernels.h"
+#include "olmc_local_vol_kernels.h"
 #include "olmc_job_board.h"
 
 #include <dlfcn.h>
@@ -121,6 +123,9 @@ struct DeviceCtx {
     // the bridge slabs of heston_qmc_kernel: [waves of the grid][2 n][64] doubles, grown on demand (heston_slabs)
     double* d_heston_w = nullptr;
     size_t heston_w_bytes = 0;
+    // the local-volatility table of the call in flight (olmc_local_vol.h), uploaded by every call: nothing reads it after the lease ends
+    float* d_lv = nullptr;              // [kLvMaxNt * kLvMaxNx] fp32 nodes, allocated by the first local-volatility call
+    std::vector<float> lv_host;         // the nodes as uploaded (kept alive for the asynchronous copy)
     bool busy = false;                  // leased (guarded by the pool's mutex)
     // profiling
     std::vector<EventPair> ev_free, ev_pending;
@@ -180,6 +185,7 @@ void ctx_release(DeviceCtx* c) {
     if (c->d_sobol) (void)hipFree(c->d_sobol);
     if (c->d_bridge) (void)hipFree(c->d_bridge);
     if (c->d_heston_w) (void)hipFree(c->d_heston_w);
+    if (c->d_lv) (void)hipFree(c->d_lv);
     for (auto& sl : c->slots) {
         if (sl.block_rows) (void)hipFree(sl.block_rows);
         if (sl.group_rows) (void)hipFree(sl.group_rows);
@@ -2754,6 +2760,158 @@ extern "C" int olmc_heston_qmc_surface(double S, double T, double r, double q, i
                                        int32_t bits, int antithetic, olmc_stats* out) {
     return run_heston_qmc_surface<HestonEuler>(S, T, r, q, is_call, {kappa, theta, sigma_v, rho, v0}, strikes, steps, k, construction, point_offset,
                                                n_points, n_steps, sv, shift, bits, antithetic, out);
+}
+
+// ====================================================== Dupire local volatility ====
+// include/olmc_local_vol.h: the payoffs of olmc_heston_path_payoff, a path matrix and a surface of Europeans on GBM-stream paths whose
+// volatility is a bilinear lookup in the caller's table (olmc_local_vol_kernels.h).  Every check comes before the lease; the table goes
+// to the device on the context's stream with every call and is read by that call's one launch only.
+namespace {
+int lv_surface_check(const ollv_surface* s) {
+    if (!s || !s->vol) return fail(OLMC_ERR_ARG, "null pointer");
+    if (s->n_x < 2 || s->n_x > kLvMaxNx) return fail(OLMC_ERR_ARG, "n_x must be in [2, 256]");
+    if (s->n_t < 1 || s->n_t > kLvMaxNt) return fail(OLMC_ERR_ARG, "n_t must be in [1, 64]");
+    if (!(s->x_hi > s->x_lo)) return fail(OLMC_ERR_ARG, "x_hi must be > x_lo");
+    if (s->n_t > 1 && !(s->t_hi > 0.0)) return fail(OLMC_ERR_ARG, "t_hi must be > 0");
+    const int32_t nodes = s->n_t * s->n_x;
+    for (int32_t k = 0; k < nodes; ++k) {
+        const float a = static_cast<float>(s->vol[k]);          // the value the kernels read
+        if (!(std::isfinite(a) && a > 0.0f)) return fail(OLMC_ERR_ARG, "local volatilities must be finite and > 0");
+    }
+    return OLMC_OK;
+}
+
+int lv_payoff_check(int payoff, double barrier) {
+    if (payoff < OLMC_BARRIER_UP_OUT || payoff > OLLV_EUROPEAN) return fail(OLMC_ERR_ARG, "bad payoff");
+    if (heston_path_is_barrier(payoff) && barrier <= 0.0) return fail(OLMC_ERR_ARG, "Barrier must be positive");
+    return OLMC_OK;
+}
+
+bool lv_poisoned(double S, double K, double T, double r, double q, const ollv_surface* s) {
+    return poisoned(S, K, T, r, 0.0, q) || std::isnan(s->x_lo + s->x_hi) || (s->n_t > 1 && std::isnan(s->t_hi));
+}
+
+// The checked table rounded to fp32 onto context c (on its stream, ahead of the launch that reads it) and the model of n_steps steps.
+int lv_upload(DeviceCtx* c, const ollv_surface* s, double S, double T, double r, double q, int32_t n_steps, LvModel* m) {
+    if (!c->d_lv) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_lv), sizeof(float) * kLvMaxNt * kLvMaxNx));
+    const size_t nodes = static_cast<size_t>(s->n_t) * s->n_x;
+    c->lv_host.resize(nodes);
+    for (size_t k = 0; k < nodes; ++k) c->lv_host[k] = static_cast<float>(s->vol[k]);
+    HIP_TRY(hipMemcpyAsync(c->d_lv, c->lv_host.data(), sizeof(float) * nodes, hipMemcpyHostToDevice, c->stream));
+    const double dt = T / n_steps;
+    m->nodes = c->d_lv;
+    m->n_x = s->n_x;
+    m->n_t = s->n_t;
+    m->x_lo = s->x_lo;
+    m->x_scale = (s->n_x - 1) / (s->x_hi - s->x_lo);
+    m->t_scale = s->n_t > 1 ? (s->n_t - 1) / s->t_hi : 0.0;
+    m->dt = dt;
+    m->rq_dt = (r - q) * dt;
+    m->half_dt = 0.5 * dt;
+    m->vol_unit = std::sqrt(dt) * kZScale;
+    m->s0 = S;
+    m->log_s0 = std::log(S);
+    return OLMC_OK;
+}
+
+// launch_timed with the table's dynamic LDS (lv_lds; none for the A/B form of lv_price_kernel, which keeps a row of its own).  Beyond 48 KiB the kernel is told so first (a no-op where the runtime has no such limit).
+template <typename Kernel, typename... Args>
+void lv_launch(Kernel kernel, const LvModel& m, bool table_in_lds, int32_t grid, hipStream_t s, const EventPair* timed, const Args&... args) {
+    const uint32_t lds = table_in_lds ? static_cast<uint32_t>(sizeof(float)) * m.n_t * m.n_x : 0u;
+    if (lds > 48u * 1024u) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
+        (void)hipGetLastError();
+    }
+    if (timed) hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, s, timed->start, timed->stop, 0, args...);
+    else hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, s, args...);
+}
+
+// f(integral_constant<int, family>) for the family of a checked payoff code, OLLV_EUROPEAN included.
+template <typename F>
+void with_lv_family(int payoff, F&& f) {
+    if (payoff == OLLV_EUROPEAN) f(std::integral_constant<int, kLvEuropean>{});
+    else with_heston_path_family(payoff, f);
+}
+}  // namespace
+
+extern "C" int ollv_price(double S, double K, double T, double r, double q, int is_call, const ollv_surface* surf, int payoff, double barrier,
+                          int64_t path_offset, int64_t n_local, int32_t n_steps, uint64_t seed, int antithetic, olmc_stats* out) {
+    if (!out) return fail(OLMC_ERR_ARG, "null pointer");
+    int rc = lv_surface_check(surf);
+    if (rc) return rc;
+    rc = lv_payoff_check(payoff, barrier);
+    if (rc) return rc;
+    rc = check_paths(path_offset, n_local, n_steps);
+    if (rc) return rc;
+    const ExtremaContract ec = heston_path_contract(S, K, is_call, payoff == OLLV_EUROPEAN ? OLMC_PATH_ASIAN_ARITHMETIC : payoff, barrier);
+    const bool bad = lv_poisoned(S, K, T, r, q, surf) || (heston_path_is_barrier(payoff) && std::isnan(barrier));
+    const double inv_steps = 1.0 / n_steps;
+    CtxLease lease;
+    rc = ctx_lease(&lease);
+    if (rc) return rc;
+    DeviceCtx* const c = lease.c;
+    LvModel m;
+    rc = lv_upload(c, surf, S, T, r, q, n_steps, &m);
+    if (rc) return rc;
+    const PathRange pr = make_range(path_offset, n_local, n_steps, seed);
+    rc = launch_reduce(c, c->stream, c->d_result, -1.0, 2, grid_for(n_local),
+                       [&](int32_t grid, hipStream_t st, const EventPair* timed, const ReduceWs& ws) {
+                           with_lv_family(payoff, [&](auto f) {
+                               with_bool(antithetic != 0, [&](auto a) { lv_launch(lv_price_kernel<f, a>, m, !OLMC_LV_ROW_LDS, grid, st, timed, pr, m, ec, inv_steps, ws); });
+                           });
+                       });
+    if (rc) return rc;
+    finish_one(c->h_result, n_local * (antithetic ? 2 : 1), r, T, bad, out);
+    return OLMC_OK;
+}
+
+extern "C" int ollv_paths(double S, double T, double r, double q, const ollv_surface* surf, int64_t n_paths, int32_t n_steps, uint64_t seed,
+                          int path_major, double* out_host) {
+    if (!out_host) return fail(OLMC_ERR_ARG, "null pointer");
+    int rc = lv_surface_check(surf);
+    if (rc) return rc;
+    const double bytes = 8.0 * static_cast<double>(n_paths) * (n_steps + 1.0);
+    CtxLease lease;
+    rc = matrix_prologue(n_paths, n_steps, bytes, "path matrix would exceed 64 GB", &lease);
+    if (rc) return rc;
+    DeviceCtx* const c = lease.c;
+    LvModel m;
+    rc = lv_upload(c, surf, S, T, r, q, n_steps, &m);
+    if (rc) return rc;
+    const PathRange pr = make_range(0, n_paths, n_steps, seed);
+    with_bool(path_major != 0, [&](auto pm) { lv_launch(lv_paths_kernel<pm>, m, true, grid_for(n_paths), c->stream, nullptr, pr, m, static_cast<double*>(c->d_bulk)); });
+    HIP_TRY(hipGetLastError());
+    return copy_to_host(c, out_host, c->d_bulk, static_cast<size_t>(bytes));
+}
+
+extern "C" int ollv_surface_prices(double S, double T, double r, double q, int is_call, const ollv_surface* surf, const double* strikes,
+                                   const int32_t* steps, int32_t k, int64_t path_offset, int64_t n_local, int32_t n_steps, uint64_t seed,
+                                   int antithetic, olmc_stats* out) {
+    if (!strikes || !steps || !out) return fail(OLMC_ERR_ARG, "null pointer");
+    int rc = lv_surface_check(surf);
+    if (rc) return rc;
+    rc = check_paths(path_offset, n_local, n_steps);
+    if (rc) return rc;
+    SurfaceOrder so;
+    rc = surface_cells(strikes, steps, k, n_steps, &so);
+    if (rc) return rc;
+    const bool bad = lv_poisoned(S, 0.0, T, r, q, surf);
+    CtxLease lease;
+    rc = ctx_lease(&lease);
+    if (rc) return rc;
+    DeviceCtx* const c = lease.c;
+    LvModel m;
+    rc = lv_upload(c, surf, S, T, r, q, n_steps, &m);
+    if (rc) return rc;
+    const PathRange pr = make_range(path_offset, n_local, n_steps, seed);
+    const double sign = is_call ? 1.0 : -1.0;
+    rc = launch_reduce(c, c->stream, c->d_result, -1.0, 2 * kSurfaceCells, grid_for(n_local),
+                       [&](int32_t grid, hipStream_t st, const EventPair* timed, const ReduceWs& ws) {
+                           with_bool(antithetic != 0, [&](auto a) { lv_launch(lv_surface_kernel<a>, m, true, grid, st, timed, pr, m, sign, so.cells, ws); });
+                       });
+    if (rc) return rc;
+    surface_finish(c->h_result, so, strikes, steps, k, n_local * (antithetic ? 2 : 1), r, T / n_steps, bad, out);
+    return OLMC_OK;
 }
 
 // ====================================================== Heston scenario sets and fused Greeks ====

@@ -1,0 +1,73 @@
+// olmc_local_vol_row_kernel.h -- the A/B form of lv_price_kernel (optionslab_amd/csrc/olmc_local_vol_kernels.h includes this file in
+// its place under -DOLMC_LV_ROW_LDS=1).  Measurement code: built by `python tools/local_vol_timing.py --build-row` into
+// tools/ab/libolmc_lv_row.so, loaded through $OLMC_LIBRARY, never part of the product library.
+#pragma once
+// (included inside namespace olmc, after LvModel and the lookup helpers)
+
+// The other shape, for A/B: only the current date's TIME-BLENDED row in LDS (fp64, two buffers of n_x doubles), re-blended from the table
+// in global memory as the date advances; a lookup is two ds_read_b64 and one interpolation.  Every wave of a workgroup must be at the
+// same date: one workgroup barrier per date, a workgroup-uniform trip count, lanes beyond the range walking path 0 with no payoff.
+// The row is blended in time first and interpolated in x second: the header's bilinear form in the other order, equal to rounding.
+template <int FAMILY, bool ANTI>
+__global__ __launch_bounds__(kBlock) void lv_price_kernel(PathRange pr, LvModel m, ExtremaContract ec, double inv_steps, ReduceWs ws) {
+    constexpr int LEGS = ANTI ? 2 : 1;
+    constexpr double kLog2e = 1.4426950408889634;
+    __shared__ double row[2][kLvMaxNx];
+    const RoundKeys rk = pin_round_keys(pr.key0, pr.key1);
+    double acc[2] = {0.0, 0.0};
+    const int32_t blocks = (pr.n_steps + 3) >> 2;
+    const int32_t col = static_cast<int32_t>(threadIdx.x);
+    auto blend = [&](int32_t t) {                                // the row of date t into row[t & 1], a thread per column
+        if (col < m.n_x) {
+            const double v = fmin(fmax(static_cast<double>(t) * m.dt * m.t_scale, 0.0), static_cast<double>(m.n_t - 1));
+            const int32_t i = max(min(static_cast<int32_t>(v), m.n_t - 2), 0), i1 = min(i + 1, m.n_t - 1);
+            const double a0 = static_cast<double>(m.nodes[i * m.n_x + col]), a1 = static_cast<double>(m.nodes[i1 * m.n_x + col]);
+            row[t & 1][col] = a0 + (v - static_cast<double>(i)) * (a1 - a0);
+        }
+    };
+    const int64_t stride = static_cast<int64_t>(gridDim.x) * kBlock;
+    for (int64_t base = static_cast<int64_t>(blockIdx.x) * kBlock; base < pr.count; base += stride) {       // workgroup-uniform
+        const int64_t i = base + threadIdx.x;
+        const bool live = i < pr.count;
+        const PathWords pw = path_words(pr, live ? i : 0);
+        double x[2] = {0.0, 0.0};
+        QmcLeg leg[2];
+        __syncthreads();                                         // the previous trip's last reads are done
+        blend(0);
+        for (int32_t b = 0; b < blocks; ++b) {
+            float z[4];
+            raw_normals4_pinned(pw.lo, pw.hi, static_cast<uint32_t>(b), 0u, rk, z);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int32_t t = 4 * b + j;
+                if (t < pr.n_steps) {                            // launch-uniform: every thread meets every barrier
+                    __syncthreads();                             // row[t & 1] is written; nobody reads row[(t + 1) & 1] any more
+                    if (t + 1 < pr.n_steps) blend(t + 1);
+                    const double* r = row[t & 1];
+                    const double zj = static_cast<double>(z[j]);
+#pragma unroll
+                    for (int l = 0; l < LEGS; ++l) {
+                        const double u = fmin(fmax((x[l] - m.x_lo) * m.x_scale, 0.0), static_cast<double>(m.n_x - 1));
+                        const int32_t c = min(static_cast<int32_t>(u), m.n_x - 2);
+                        const double r0 = r[c], r1 = r[c + 1];
+                        const double sigma = r0 + (u - static_cast<double>(c)) * (r1 - r0);
+                        x[l] += __builtin_fma(sigma * m.vol_unit, l ? -zj : zj, __builtin_fma(-(sigma * sigma), m.half_dt, m.rq_dt));
+                        if constexpr (FAMILY == kQmcAsianArithmetic) qmc_leg_add<FAMILY>(leg[l], x[l] * kLog2e);
+                        else if constexpr (FAMILY != kLvEuropean) qmc_leg_add<FAMILY>(leg[l], x[l]);
+                    }
+                }
+            }
+        }
+        if (live) {
+#pragma unroll
+            for (int l = 0; l < LEGS; ++l) {
+                double p;
+                if constexpr (FAMILY == kLvEuropean) p = fmax(ec.sign * (ec.s0 * exp(x[l]) - ec.strike), 0.0);
+                else p = qmc_payoff<FAMILY>(ec, inv_steps, leg[l].a, leg[l].mx, leg[l].mn, x[l]);
+                acc[0] += p; acc[1] += p * p;
+            }
+        }
+    }
+    block_then_grid_reduce<2>(acc, ws);
+}
+
