@@ -10,6 +10,7 @@
 #include "olmc_kernels.h"
 #include "olmc_local_vol_kernels.h"
 #include "olmc_job_board.h"
+#include "olmc_device_mem.h"
 
 #include <dlfcn.h>
 #include <sched.h>
@@ -61,6 +62,9 @@ constexpr int kMaxDevices = 16;
 constexpr int kMaxNV = 2 * OLMC_MAX_BATCH;       // values per workgroup row
 constexpr int32_t kMaxGroups = kMaxGrid / kGroupBlocks + 1;
 static_assert(kMaxGroups * kMaxNV == kGroupRowsCapacity, "device-side guard must match the group_rows allocation");
+constexpr size_t kCounterBytes = sizeof(uint32_t) * (kMaxGroups + 1) * kCounterStride;      // a workspace slot's counters
+
+using Mem = HipMem;
 
 struct EventPair {
     hipEvent_t start, stop;
@@ -78,10 +82,9 @@ struct DeviceCtx {
     // launch finds the workspace free by construction -- and a blocking call is spared the two barrier packets
     // (hipStreamWaitEvent in front of the kernel, hipEventRecord behind it): ~1 us per call, measured.
     struct WsSlot {
-        double* block_rows = nullptr;  // [cap] doubles, grown on demand (grid x NV)
-        size_t cap = 0;
-        double* group_rows = nullptr;  // [kMaxGroups][kMaxNV]
-        uint32_t* counters = nullptr;  // [(kMaxGroups + 1) * kCounterStride], zero between launches (self-resetting)
+        DeviceBlock<Mem> block_rows;   // doubles, grown on demand (grid x NV, at least 2^16)
+        DeviceBlock<Mem> group_rows;   // [kMaxGroups][kMaxNV] doubles
+        DeviceBlock<Mem> counters;     // [(kMaxGroups + 1) * kCounterStride] words, zero between launches (self-resetting)
         hipEvent_t done = nullptr;     // recorded after the slot's latest launch (shared slots only)
         bool used = false;
         bool claimed = false;          // `owner` (which may be the NULL stream) is the ONE caller stream that has used this slot so far:
@@ -98,34 +101,26 @@ struct DeviceCtx {
     uint64_t* d_flag = nullptr;      // device alias
     uint64_t seq = 0;                // last sequence number handed out
     uint64_t armed = 0;              // != 0: the launch just made raises h_flag to this value
-    double* h_result = nullptr;      // pinned + mapped [kMaxNV + 1 (+ flag)]: the last workgroup writes the sums straight to the host
-    double* d_result = nullptr;      // device alias of h_result (zero-copy: no D2H copy node, only a stream sync)
-    void* d_bulk = nullptr;          // terminal prices / validation taps
-    size_t bulk_bytes = 0;
+    PinnedBlock<Mem> result;         // pinned + mapped [kMaxNV + 1 (+ flag)]: the last workgroup writes the sums straight to the host
+    double* h_result = nullptr;      // view of `result`
+    double* d_result = nullptr;      // its device alias (zero-copy: no D2H copy node, only a stream sync)
+    DeviceBlock<Mem> bulk;           // terminal prices / path matrices / validation taps (bulk_reserve)
     // large results on their way home (copy_to_host): two pinned staging buffers, an event per buffer (allocated by the first large copy)
-    void* h_stage[2] = {nullptr, nullptr};
+    PinnedBlock<Mem> stage[2];
     hipEvent_t stage_landed[2] = {nullptr, nullptr};
-    // independent-contract batches (european_multi_kernel)
-    void* d_multi = nullptr;         // device [ticket counters | done counter | contracts | rows], see olmc_european_multi
-    void* h_multi = nullptr;         // pinned + mapped [contracts | sums]
-    void* d_h_multi = nullptr;       // device alias of h_multi
-    int64_t multi_cap = 0;           // capacity in contracts
-    size_t multi_bpo = 0;            // workgroups per contract the rows are sized for
-    size_t multi_off_done = 0, multi_off_opts = 0, multi_off_rows = 0, multi_hoff_out = 0;
-    // scrambled-Sobol tables of the last QMC call, kept on the device: FD Greeks and repeated pricings reuse one table
-    uint32_t* d_sobol = nullptr;     // [dims x 30 direction numbers | dims shifts]
-    size_t sobol_words = 0;          // capacity
-    std::vector<uint32_t> sobol_host;   // what d_sobol holds (compared word for word with the caller's table)
-    // the Brownian-bridge plan of the last bridge-constructed QMC path call (qmc_bridge_plan): it depends on n_steps alone
-    void* d_bridge = nullptr;        // [n uint32 a | b << 16][3 x n doubles ca, cb, sd]
-    int32_t bridge_n = 0;            // n of the plan d_bridge holds (0: none)
-    std::vector<unsigned char> bridge_host;   // the plan as uploaded (kept alive for the asynchronous copy)
-    // the bridge slabs of heston_qmc_kernel: [waves of the grid][2 n][64] doubles, grown on demand (heston_slabs)
-    double* d_heston_w = nullptr;
-    size_t heston_w_bytes = 0;
-    // the local-volatility table of the call in flight (olmc_local_vol.h), uploaded by every call: nothing reads it after the lease ends
-    float* d_lv = nullptr;              // [kLvMaxNt * kLvMaxNx] fp32 nodes, allocated by the first local-volatility call
-    std::vector<float> lv_host;         // the nodes as uploaded (kept alive for the asynchronous copy)
+    BatchWorkspace<Mem, MultiOption, kMultiCounterStride> multi;      // independent-contract batches (olmc_european_multi)
+    // the scrambled-Sobol table of the last QMC call, [dims x 30 direction numbers | dims shifts], keyed by its content: FD Greeks
+    // and repeated pricings reuse one upload (qmc_table)
+    CachedUpload<Mem> sobol;
+    // the Brownian-bridge plan of the last bridge-constructed QMC path call, [n uint32 a | b << 16][3 x n doubles ca, cb, sd], keyed
+    // by n: it depends on n_steps alone (qmc_bridge_plan)
+    CachedUpload<Mem> bridge;
+    DeviceBlock<Mem> heston_w;       // the bridge slabs of heston_qmc_kernel: [waves of the grid][2 n][64] doubles (heston_slabs)
+    // the local-volatility table of the call in flight (olmc_local_vol.h), fp32 nodes, uploaded by every call: nothing reads it
+    // after the lease ends (lv_upload)
+    CachedUpload<Mem> lv;
+    // "let the old users finish" for everything above but a shared workspace slot: they are all used on the context's own stream
+    int drain() const { return Mem::wait(stream); }
     bool busy = false;                  // leased (guarded by the pool's mutex)
     // profiling
     std::vector<EventPair> ev_free, ev_pending;
@@ -154,45 +149,36 @@ std::atomic<DevicePool*> g_pool[kMaxDevices] = {};      // readers (every call's
 std::atomic<int> g_default_device{-1};                  // device) take no lock
 bool g_profile = false;
 
+int no_users() { return 0; }            // the quiesce of a block allocated once, before anything can use it
+
 int ctx_allocate(DeviceCtx* c) {
     HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     for (auto& sl : c->slots) {
-        HIP_TRY(hipMalloc(&sl.group_rows, sizeof(double) * kMaxNV * kMaxGroups));
-        HIP_TRY(hipMalloc(&sl.counters, sizeof(uint32_t) * (kMaxGroups + 1) * kCounterStride));
-        HIP_TRY(hipMemset(sl.counters, 0, sizeof(uint32_t) * (kMaxGroups + 1) * kCounterStride));
+        int rc = sl.group_rows.reserve(sizeof(double) * kMaxNV * kMaxGroups, no_users);
+        if (!rc) rc = sl.counters.reserve(kCounterBytes, no_users);
+        if (rc) return rc;
+        HIP_TRY(hipMemset(sl.counters.get(), 0, kCounterBytes));
         HIP_TRY(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
     }
-    HIP_TRY(hipHostMalloc(&c->h_result, sizeof(double) * (kMaxNV + 1 + 15), hipHostMallocMapped));
-    HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&c->d_result), c->h_result, 0));
+    const int rc = c->result.reserve(sizeof(double) * (kMaxNV + 1 + 15), no_users, 0, 0, /*mapped=*/true);
+    if (rc) return rc;
+    c->h_result = c->result.as<double>();
+    c->d_result = c->result.alias<double>();
     c->h_flag = reinterpret_cast<uint64_t*>(c->h_result + kMaxNV + 8);      // a cache line of its own
     c->d_flag = reinterpret_cast<uint64_t*>(c->d_result + kMaxNV + 8);
     *c->h_flag = 0;
     return OLMC_OK;
 }
 
-// Frees whatever a context owns (tolerates partially built contexts) and deletes it.
+// Lets a context's work finish, destroys its events and stream (tolerates partially built contexts) and deletes it: its blocks free themselves.
 void ctx_release(DeviceCtx* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     for (auto& ep : c->ev_pending) { (void)hipEventDestroy(ep.start); (void)hipEventDestroy(ep.stop); }
     for (auto& ep : c->ev_free) { (void)hipEventDestroy(ep.start); (void)hipEventDestroy(ep.stop); }
-    if (c->d_bulk) (void)hipFree(c->d_bulk);
-    for (int i = 0; i < 2; ++i) {
-        if (c->h_stage[i]) (void)hipHostFree(c->h_stage[i]);
-        if (c->stage_landed[i]) (void)hipEventDestroy(c->stage_landed[i]);
-    }
-    if (c->d_multi) (void)hipFree(c->d_multi);
-    if (c->h_multi) (void)hipHostFree(c->h_multi);
-    if (c->d_sobol) (void)hipFree(c->d_sobol);
-    if (c->d_bridge) (void)hipFree(c->d_bridge);
-    if (c->d_heston_w) (void)hipFree(c->d_heston_w);
-    if (c->d_lv) (void)hipFree(c->d_lv);
-    for (auto& sl : c->slots) {
-        if (sl.block_rows) (void)hipFree(sl.block_rows);
-        if (sl.group_rows) (void)hipFree(sl.group_rows);
-        if (sl.counters) (void)hipFree(sl.counters);
+    for (hipEvent_t ev : c->stage_landed)
+        if (ev) (void)hipEventDestroy(ev);
+    for (auto& sl : c->slots)
         if (sl.done) (void)hipEventDestroy(sl.done);
-    }
-    if (c->h_result) (void)hipHostFree(c->h_result);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -278,14 +264,11 @@ int ctx_lease(CtxLease* out) {
     return ctx_lease_on(dev, out);
 }
 
-int bulk_reserve(DeviceCtx* c, size_t bytes) {
-    if (bytes <= c->bulk_bytes) return OLMC_OK;
-    if (c->d_bulk) HIP_TRY(hipFree(c->d_bulk));
-    c->d_bulk = nullptr;
-    c->bulk_bytes = 0;
-    HIP_TRY(hipMalloc(&c->d_bulk, bytes));
-    c->bulk_bytes = bytes;
-    return OLMC_OK;
+// The context's bulk buffer with room for `bytes`; a call that keeps several arrays there cuts them from `spans`, in order.
+int bulk_reserve(DeviceCtx* c, size_t bytes, Carver* spans = nullptr) {
+    const int rc = c->bulk.reserve(bytes, [c] { return c->drain(); });
+    if (spans) *spans = c->bulk.carve();
+    return rc;
 }
 
 // A large result (a path matrix: 100k x 252 doubles = 202 MB; a terminal array of 64M paths = 1 GB) on its way to the CALLER's buffer,
@@ -306,7 +289,8 @@ int copy_to_host(DeviceCtx* c, void* dst, const void* d_src, size_t bytes) {
         return OLMC_OK;
     }
     for (int i = 0; i < 2; ++i) {
-        if (!c->h_stage[i]) HIP_TRY(hipHostMalloc(&c->h_stage[i], kStageBytes, hipHostMallocDefault));
+        const int rc = c->stage[i].reserve(kStageBytes, no_users);
+        if (rc) return rc;
         if (!c->stage_landed[i]) HIP_TRY(hipEventCreateWithFlags(&c->stage_landed[i], hipEventDisableTiming));
     }
     cpu_set_t cpus;
@@ -326,7 +310,7 @@ int copy_to_host(DeviceCtx* c, void* dst, const void* d_src, size_t bytes) {
             }
             const size_t len = chunk_len(i), per = (len / n_threads + 4095) & ~size_t(4095);      // page-sized slices: each page of dst has one toucher
             const size_t lo = std::min(len, per * w), hi = std::min(len, lo + per);
-            if (hi > lo) std::memcpy(static_cast<char*>(dst) + static_cast<size_t>(i) * kStageBytes + lo, static_cast<const char*>(c->h_stage[i & 1]) + lo, hi - lo);
+            if (hi > lo) std::memcpy(static_cast<char*>(dst) + static_cast<size_t>(i) * kStageBytes + lo, static_cast<const char*>(c->stage[i & 1].get()) + lo, hi - lo);
             copied[i & 1].fetch_add(1, std::memory_order_release);
         }
     };
@@ -357,7 +341,7 @@ int copy_to_host(DeviceCtx* c, void* dst, const void* d_src, size_t bytes) {
             copied[slot].store(0, std::memory_order_relaxed);
             us_workers += us_since(t);
         }
-        err = hipMemcpyAsync(c->h_stage[slot], static_cast<const char*>(d_src) + static_cast<size_t>(i) * kStageBytes, chunk_len(i), hipMemcpyDeviceToHost, c->stream);
+        err = hipMemcpyAsync(c->stage[slot].get(), static_cast<const char*>(d_src) + static_cast<size_t>(i) * kStageBytes, chunk_len(i), hipMemcpyDeviceToHost, c->stream);
         if (err == hipSuccess) err = hipEventRecord(c->stage_landed[slot], c->stream);
         if (err == hipSuccess && i >= 1) {
             const auto t = clock::now();
@@ -500,23 +484,19 @@ int make_ws(DeviceCtx* c, hipStream_t stream, int32_t grid, int nv, double* d_ou
     c->cur_slot = idx;
     const bool guarded = !own && sl.shared;
     const size_t need = static_cast<size_t>(grid) * nv;
-    if (need > sl.cap) {
+    int rc = sl.block_rows.reserve(sizeof(double) * need, [&] {      // the slot's launches so far: its one stream's, or the event's
         if (!guarded) HIP_TRY(hipStreamSynchronize(stream));
         else if (sl.used) HIP_TRY(hipEventSynchronize(sl.done));
-        if (sl.block_rows) HIP_TRY(hipFree(sl.block_rows));
-        sl.block_rows = nullptr;
-        sl.cap = 0;
-        const size_t cap = std::max<size_t>(need, size_t(1) << 16);
-        HIP_TRY(hipMalloc(&sl.block_rows, sizeof(double) * cap));
-        sl.cap = cap;
-    }
+        return static_cast<int>(OLMC_OK);
+    }, sizeof(double) << 16);
+    if (rc) return rc;
     if (guarded && sl.used) HIP_TRY(hipStreamWaitEvent(stream, sl.done, 0));   // previous user of this shared slot, whatever its stream
-    ws->block_rows = sl.block_rows;
-    ws->group_rows = sl.group_rows;
-    ws->counters = sl.counters;
+    ws->block_rows = sl.block_rows.as<double>();
+    ws->group_rows = sl.group_rows.as<double>();
+    ws->counters = sl.counters.as<uint32_t>();
     ws->out = d_out;
     ws->tail = tail;
-    ws->row_capacity = sl.cap;
+    ws->row_capacity = sl.block_rows.capacity() / sizeof(double);
 #ifdef OLMC_WITH_PROBES
     if (g_force_nv > 0) ws->row_capacity = static_cast<uint64_t>(grid) * g_force_nv;        // the knob UNDER-reports (test of the guard)
 #endif
@@ -536,7 +516,7 @@ void ws_recover(DeviceCtx* c) {
     c->armed = 0;
     (void)hipDeviceSynchronize();
     (void)hipGetLastError();
-    for (auto& sl : c->slots) (void)hipMemset(sl.counters, 0, sizeof(uint32_t) * (kMaxGroups + 1) * kCounterStride);
+    for (auto& sl : c->slots) (void)hipMemset(sl.counters.get(), 0, kCounterBytes);
 }
 
 // The same for the batch workspace (self-resetting ticket counters and the batch's done counter).
@@ -544,7 +524,7 @@ void multi_recover(DeviceCtx* c) {
     c->armed = 0;
     (void)hipDeviceSynchronize();
     (void)hipGetLastError();
-    if (c->d_multi) (void)hipMemset(c->d_multi, 0, c->multi_off_opts);
+    if (c->multi.counters()) (void)hipMemset(c->multi.counters(), 0, c->multi.counter_bytes());
 }
 
 // Call right after launching a kernel that uses the workspace handed out by make_ws.
@@ -873,6 +853,8 @@ int run_batch(const olmc_option* opts, int32_t k, int64_t path_offset, int64_t n
 
 namespace { void multi_gpu_release(); }      // the multi-GPU engine's streams, buffers and communicators (defined with it)
 
+int olmc::device_mem_fail(hipError_t e, const char* call) { return fail(OLMC_ERR_HIP, std::string(call) + ": " + hipGetErrorString(e)); }
+
 // =============================================================== lifetime ====
 extern "C" int olmc_abi_version(void) { return OLMC_ABI_VERSION; }
 
@@ -1036,47 +1018,21 @@ extern "C" int olmc_european_multi(const olmc_option* opts, const uint32_t* tags
     if (rc) return rc;
     DeviceCtx* const c = lease.c;
     const int32_t bpo = static_cast<int32_t>(std::min<int64_t>((n_paths + kBlock - 1) / kBlock, 1024));   // workgroups per contract
-    auto align = [](size_t b) { return (b + 255) / 256 * 256; };
-    // Device workspace [counters | done counter | contracts | rows]: the ticket counters sit FIRST and are sized by the capacity in
-    // contracts, so their place does not move with the batch size and they are zeroed once per (re)allocation -- every finisher
-    // re-zeroes the counter it consumed.  Pinned host staging [contracts | sums]: contracts go up by one asynchronous DMA from
-    // pinned memory, the sums are written into pinned memory by the kernel itself, completion is the polled word of the context.
-    if (n_options > c->multi_cap || static_cast<size_t>(bpo) > c->multi_bpo) {
-        // the two capacities grow independently: more contracts doubles the contract capacity, more workgroups per contract (a
-        // larger n_paths on the same batch) only widens the rows -- a convergence sweep over n_paths must not double `cap` each time
-        const int64_t cap = n_options > c->multi_cap ? std::max<int64_t>(n_options, std::max<int64_t>(2 * c->multi_cap, 64)) : c->multi_cap;
-        const size_t bpo_cap = std::max<size_t>(bpo, c->multi_bpo);
-        const size_t b_cnt = align(sizeof(uint32_t) * cap * kMultiCounterStride), b_done = 256, b_opts = align(sizeof(MultiOption) * cap);
-        const size_t b_rows = align(sizeof(double) * 2 * bpo_cap * cap);
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (c->d_multi) HIP_TRY(hipFree(c->d_multi));
-        if (c->h_multi) HIP_TRY(hipHostFree(c->h_multi));
-        c->d_multi = nullptr; c->h_multi = nullptr; c->multi_cap = 0; c->multi_bpo = 0;
-        HIP_TRY(hipMalloc(&c->d_multi, b_cnt + b_done + b_opts + b_rows));
-        HIP_TRY(hipMemsetAsync(c->d_multi, 0, b_cnt + b_done, c->stream));
-        HIP_TRY(hipHostMalloc(&c->h_multi, b_opts + align(sizeof(double) * 2 * cap), hipHostMallocMapped));
-        HIP_TRY(hipHostGetDevicePointer(&c->d_h_multi, c->h_multi, 0));
-        c->multi_cap = cap;
-        c->multi_bpo = bpo_cap;
-        c->multi_off_done = b_cnt; c->multi_off_opts = b_cnt + b_done; c->multi_off_rows = b_cnt + b_done + b_opts; c->multi_hoff_out = b_opts;
-    }
-    char* base = static_cast<char*>(c->d_multi);
-    uint32_t* d_cnt = reinterpret_cast<uint32_t*>(base);
-    uint32_t* d_done = reinterpret_cast<uint32_t*>(base + c->multi_off_done);
-    MultiOption* d_opts = reinterpret_cast<MultiOption*>(base + c->multi_off_opts);
-    double* d_rows = reinterpret_cast<double*>(base + c->multi_off_rows);
-    MultiOption* h = reinterpret_cast<MultiOption*>(c->h_multi);
-    const double* h_out = reinterpret_cast<const double*>(static_cast<char*>(c->h_multi) + c->multi_hoff_out);
-    double* d_out = reinterpret_cast<double*>(static_cast<char*>(c->d_h_multi) + c->multi_hoff_out);
+    // the batch workspace (BatchWorkspace): contracts go up by one asynchronous DMA from pinned memory, the sums are written into
+    // pinned memory by the kernel itself, completion is the polled word of the context
+    decltype(c->multi)::Views v;
+    rc = c->multi.reserve(static_cast<size_t>(n_options), static_cast<size_t>(bpo), c->stream, &v);
+    if (rc) return rc;
+    MultiOption* const h = v.h_opts;
     for (int64_t j = 0; j < n_options; ++j) {
         const Contract ct = make_contract(opts[j], n_steps);
         h[j].a = ct.a; h[j].vol = ct.vol; h[j].strike = ct.strike; h[j].sign = ct.sign;
         h[j].tag = tags ? tags[j] : static_cast<uint32_t>(j);
         h[j].pad = 0;
     }
-    HIP_TRY(hipMemcpyAsync(d_opts, h, sizeof(MultiOption) * n_options, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(v.d_opts, h, sizeof(MultiOption) * n_options, hipMemcpyHostToDevice, c->stream));
     MultiDone md;
-    md.done_count = d_done;
+    md.done_count = v.d_done;
     md.n_total = static_cast<uint32_t>(n_options);
     md.done_flag = nullptr;
     md.done_value = 0;
@@ -1091,7 +1047,7 @@ extern "C" int olmc_european_multi(const olmc_option* opts, const uint32_t* tags
     if (g_profile) { rc = prof_begin(c, c->stream, &ep); if (rc) return rc; }
     for (int64_t base_opt = 0; base_opt < n_options; base_opt += 65535) {
         const unsigned ny = static_cast<unsigned>(std::min<int64_t>(65535, n_options - base_opt));
-        with_bool(antithetic != 0, [&](auto a) { launch_timed(european_multi_kernel<a>, dim3(bpo, ny), dim3(kBlock), c->stream, nullptr, pr, d_opts, base_opt, d_rows, d_cnt, d_out, md); });
+        with_bool(antithetic != 0, [&](auto a) { launch_timed(european_multi_kernel<a>, dim3(bpo, ny), dim3(kBlock), c->stream, nullptr, pr, v.d_opts, base_opt, v.d_rows, v.d_cnt, v.d_out, md); });
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) {
             multi_recover(c);
@@ -1101,7 +1057,7 @@ extern "C" int olmc_european_multi(const olmc_option* opts, const uint32_t* tags
     if (g_profile) { rc = prof_end(c, c->stream, ep); if (rc) { multi_recover(c); return rc; } }
     rc = wait_armed(c, c->stream);
     if (rc) { multi_recover(c); return rc; }
-    finish_set(h_out, nullptr, n_paths * (antithetic ? 2 : 1), opts, n_options, false, false, out);
+    finish_set(v.h_out, nullptr, n_paths * (antithetic ? 2 : 1), opts, n_options, false, false, out);
     return OLMC_OK;
 }
 
@@ -1122,8 +1078,8 @@ extern "C" int olmc_multi_capacity(int64_t* out2) {
     int rc = ctx_lease(&lease);
     if (rc) return rc;
     DeviceCtx* const c = lease.c;
-    out2[0] = c->multi_cap;
-    out2[1] = static_cast<int64_t>(c->multi_bpo);
+    out2[0] = static_cast<int64_t>(c->multi.capacity());
+    out2[1] = static_cast<int64_t>(c->multi.rows_per_contract());
     return OLMC_OK;
 }
 
@@ -1162,9 +1118,9 @@ extern "C" int olmc_european_terminal(double S, double T, double r, double sigma
     cs.c[0] = make_contract(make_option(S, 0.0, T, r, sigma, q, 1), n_steps);
     cs.base_mask = 1u; cs.upper_continues_slot0 = 0;
     ReduceWs ws{};   // unused in kTerminal mode
-    launch_european<1, kTerminal>(antithetic != 0, grid, c->stream, pr, cs, ws, static_cast<double*>(c->d_bulk));
+    launch_european<1, kTerminal>(antithetic != 0, grid, c->stream, pr, cs, ws, c->bulk.as<double>());
     HIP_TRY(hipGetLastError());
-    return copy_to_host(c, out_host, c->d_bulk, bytes);
+    return copy_to_host(c, out_host, c->bulk.get(), bytes);
 }
 
 // =========================================================== control variate ====
@@ -1490,10 +1446,10 @@ extern "C" int olmc_gbm_paths(double S, double T, double r, double sigma, double
     lc.n_steps = n_steps;
     const PathRange pr = make_range(0, n_paths, n_steps, seed);
     with_bool(path_major != 0, [&](auto pm) {
-        launch_timed(lsm_paths_kernel<pm>, dim3(grid_for(n_paths)), dim3(kBlock), c->stream, nullptr, pr, lc, static_cast<double*>(c->d_bulk));
+        launch_timed(lsm_paths_kernel<pm>, dim3(grid_for(n_paths)), dim3(kBlock), c->stream, nullptr, pr, lc, c->bulk.as<double>());
     });
     HIP_TRY(hipGetLastError());
-    return copy_to_host(c, out_host, c->d_bulk, static_cast<size_t>(bytes));
+    return copy_to_host(c, out_host, c->bulk.get(), static_cast<size_t>(bytes));
 }
 
 extern "C" int olmc_exercise_boundary(double S, double K, double T, double r, double sigma, double q, int is_call,
@@ -1506,10 +1462,11 @@ extern "C" int olmc_exercise_boundary(double S, double K, double T, double r, do
     DeviceCtx* const c = lease.c;
     const size_t rows = static_cast<size_t>(n_steps) + 1;
     const size_t path_bytes = (static_cast<size_t>(bytes) + 255) / 256 * 256;
-    rc = bulk_reserve(c, path_bytes + rows * sizeof(double));
+    Carver bulk;
+    rc = bulk_reserve(c, path_bytes + rows * sizeof(double), &bulk);
     if (rc) return rc;
-    double* d_paths = static_cast<double*>(c->d_bulk);
-    double* d_boundary = reinterpret_cast<double*>(static_cast<char*>(c->d_bulk) + path_bytes);
+    double* d_paths = bulk.take<double>(path_bytes / sizeof(double));
+    double* d_boundary = bulk.take<double>(rows);
     LsmContract lc{};
     const GbmStep g = gbm_step(T, n_steps, r, q, sigma);          // exotic_options.py:54-56
     lc.log_s0 = std::log(S);
@@ -1573,12 +1530,12 @@ LsmContract lsm_contract(double S, double K, double T, double r, double sigma, d
 double lsm_bytes(int64_t n_paths, int32_t n_steps) { return 8.0 * static_cast<double>(n_paths) * (n_steps + 2.0) + 8.0 * 2 * 1024 * kLsmNV; }
 
 // The step chain of an LSM pricing over the time-major path matrix d_paths [n_steps + 1][n_paths] that a launch queued before it on
-// c's stream writes; d_cash [n_paths] and d_rows [2][1024][kLsmNV] follow it in c's bulk buffer.  Leaves the moments of the time-0
+// c's stream writes; d_cash [n_paths] and d_rows [2][1024][kLsmNV] are the next the caller's `bulk` hands out.  Leaves the moments of the time-0
 // cash flows in c->h_result once the host has waited for them.
 int lsm_chain(DeviceCtx* c, double S, double K, double T, double r, double sigma, double q, int is_call, const LsmContract& lc,
-              int64_t n_paths, int32_t n_steps, double* d_paths) {
-    double* d_cash = d_paths + static_cast<size_t>(n_steps + 1) * n_paths;              // [n_paths]
-    double* d_rows = d_cash + n_paths;                                                  // [2][grid][kLsmNV]: the regression sums a date hands to the next launch
+              int64_t n_paths, int32_t n_steps, double* d_paths, Carver* bulk) {
+    double* d_cash = bulk->take<double>(static_cast<size_t>(n_paths));                  // [n_paths]
+    double* d_rows = bulk->take<double>(size_t(2) * 1024 * kLsmNV);                     // [2][grid][kLsmNV]: the regression sums a date hands to the next launch
     const double dt = T / n_steps;
     // The per-date launches move 32 bytes per path and hand 16 sums per workgroup to the next launch, EVERY workgroup of which sums all
     // the rows: at most ONE workgroup per compute unit (<= 256 rows: one round trip), each thread taking its paths U at a time with all
@@ -1629,14 +1586,15 @@ extern "C" int olmc_american_lsm(double S, double K, double T, double r, double 
     int rc = matrix_prologue(n_paths, n_steps, lsm_bytes(n_paths, n_steps), "path matrix would exceed 64 GB: lower n_paths or n_steps", &lease);
     if (rc) return rc;
     DeviceCtx* const c = lease.c;
-    double* d_paths = static_cast<double*>(c->d_bulk);                                  // [n_steps + 1][n_paths]
+    Carver bulk = c->bulk.carve();
+    double* d_paths = bulk.take<double>((static_cast<size_t>(n_steps) + 1) * n_paths);   // [n_steps + 1][n_paths]
     const LsmContract lc = lsm_contract(S, K, T, r, sigma, q, is_call, n_steps, poly_degree);
     const PathRange pr = make_range(0, n_paths, n_steps, seed);
     EventPair ep{};
     if (g_profile) { rc = prof_begin(c, c->stream, &ep); if (rc) return rc; }
     hipLaunchKernelGGL((lsm_paths_kernel<false>), dim3(grid_for(n_paths)), dim3(kBlock), 0, c->stream, pr, lc, d_paths);
     HIP_TRY(hipGetLastError());
-    rc = lsm_chain(c, S, K, T, r, sigma, q, is_call, lc, n_paths, n_steps, d_paths);
+    rc = lsm_chain(c, S, K, T, r, sigma, q, is_call, lc, n_paths, n_steps, d_paths, &bulk);
     if (rc) return rc;
     if (g_profile) { rc = prof_end(c, c->stream, ep); if (rc) return rc; }
     // the time-0 cash flows are already discounted step by step (:302-304): no outer factor
@@ -1756,8 +1714,9 @@ int heston_qmc_scheme_check(const HestonModel& m, int construction) {
 template <typename Launch>
 int heston_path_matrices(DeviceCtx* c, int64_t n_paths, int32_t n_steps, double* spot_host, double* var_host, Launch&& launch) {
     const size_t bytes = sizeof(double) * static_cast<size_t>(n_paths) * (static_cast<size_t>(n_steps) + 1);
-    double* d_spot = static_cast<double*>(c->d_bulk);
-    double* d_var = d_spot + static_cast<size_t>(n_paths) * (n_steps + 1);
+    Carver bulk = c->bulk.carve();
+    double* d_spot = bulk.take<double>(bytes / sizeof(double));
+    double* d_var = bulk.take<double>(bytes / sizeof(double));
     EventPair ep{};
     const EventPair* timed = nullptr;                  // profiling on: the path kernel counts in olmc_kernel_time
     int rc = prof_pair(c, &ep, &timed);
@@ -1877,10 +1836,10 @@ extern "C" int olmc_jump_paths(double S, double T, double r, double sigma, doubl
     DeviceCtx* const c = lease.c;
     const PathRange pr = make_range(0, n_paths, n_steps, seed);
     with_bool(path_major != 0, [&](auto pm) {
-        launch_timed(jump_paths_kernel<pm>, dim3(grid_for(n_paths)), dim3(kBlock), c->stream, nullptr, pr, jc, S, static_cast<double*>(c->d_bulk));
+        launch_timed(jump_paths_kernel<pm>, dim3(grid_for(n_paths)), dim3(kBlock), c->stream, nullptr, pr, jc, S, c->bulk.as<double>());
     });
     HIP_TRY(hipGetLastError());
-    return copy_to_host(c, out_host, c->d_bulk, static_cast<size_t>(bytes));
+    return copy_to_host(c, out_host, c->bulk.get(), static_cast<size_t>(bytes));
 }
 
 // ======================================================================= QMC ====
@@ -1890,24 +1849,12 @@ namespace {
 // travels only when it differs from the one already there (compared word for word: 31 KB at 252 dims, ~1 us, against two pageable
 // uploads): the 8 / 14 pricings of literal FD Greeks and every repeated pricing share one upload.  The caller owns c (a lease, or
 // a multi-GPU rank's own context).
-int qmc_table(DeviceCtx* c, const uint32_t* sv, const uint32_t* shift, int32_t dims) {
-    const size_t sv_words = static_cast<size_t>(dims) * kSobolBits, table_words = sv_words + dims;
-    const bool same = c->sobol_host.size() == table_words && std::memcmp(c->sobol_host.data(), sv, sizeof(uint32_t) * sv_words) == 0 &&
-                      std::memcmp(c->sobol_host.data() + sv_words, shift, sizeof(uint32_t) * dims) == 0;
-    if (same) return OLMC_OK;
-    c->sobol_host.clear();                       // whatever happens below, the device copy is no longer described by it
-    if (table_words > c->sobol_words) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (c->d_sobol) HIP_TRY(hipFree(c->d_sobol));
-        c->d_sobol = nullptr;
-        c->sobol_words = 0;
-        HIP_TRY(hipMalloc(&c->d_sobol, sizeof(uint32_t) * table_words));
-        c->sobol_words = table_words;
-    }
-    HIP_TRY(hipMemcpyAsync(c->d_sobol, sv, sizeof(uint32_t) * sv_words, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->d_sobol + sv_words, shift, sizeof(uint32_t) * dims, hipMemcpyHostToDevice, c->stream));
-    c->sobol_host.assign(sv, sv + sv_words);
-    c->sobol_host.insert(c->sobol_host.end(), shift, shift + dims);
+int qmc_table(DeviceCtx* c, const uint32_t* sv, const uint32_t* shift, int32_t dims, const uint32_t** d_sv, const uint32_t** d_shift) {
+    const size_t sv_words = static_cast<size_t>(dims) * kSobolBits;
+    const int rc = c->sobol.put(sv, sizeof(uint32_t) * sv_words, shift, sizeof(uint32_t) * dims, c->stream, [c] { return c->drain(); });
+    if (rc) return rc;
+    *d_sv = c->sobol.device<uint32_t>();
+    *d_shift = *d_sv + sv_words;
     return OLMC_OK;
 }
 
@@ -1984,10 +1931,9 @@ Contract qmc_contract(double S, double K, double T, double r, double sigma, doub
 // c->d_result).
 int qmc_device(DeviceCtx* c, const Contract& ct, int64_t point_offset, int64_t n_paths, int32_t dims, const uint32_t* sv,
                const uint32_t* shift, bool five, double* d_out, double tail, bool profiled) {
-    int rc = qmc_table(c, sv, shift, dims);
+    const uint32_t *d_sv, *d_shift;
+    int rc = qmc_table(c, sv, shift, dims, &d_sv, &d_shift);
     if (rc) return rc;
-    const uint32_t* d_sv = c->d_sobol;
-    const uint32_t* d_shift = d_sv + static_cast<size_t>(dims) * kSobolBits;
     const QmcRange qr{static_cast<uint64_t>(point_offset), n_paths, dims, 0};
     const QmcShape sh = qmc_shape(point_offset, n_paths, dims);
     return launch_reduce(c, c->stream, d_out, tail, five ? 5 : 2, sh.grid, [&](int32_t grid, hipStream_t s, const EventPair* timed, const ReduceWs& ws) {
@@ -2018,16 +1964,17 @@ int run_qmc(double S, double K, double T, double r, double sigma, double q, int 
         return OLMC_OK;
     }
     const size_t term_bytes = sizeof(double) * static_cast<size_t>(n_paths) * (mirror ? 2 : 1);
-    rc = bulk_reserve(c, term_bytes);
+    Carver bulk;
+    rc = bulk_reserve(c, term_bytes, &bulk);
     if (rc) return rc;
-    rc = qmc_table(c, sv, shift, dims);
+    const uint32_t *d_sv, *d_shift;
+    rc = qmc_table(c, sv, shift, dims, &d_sv, &d_shift);
     if (rc) return rc;
-    double* d_term = static_cast<double*>(c->d_bulk);
+    double* d_term = bulk.take<double>(term_bytes / sizeof(double));
     const QmcShape sh = qmc_shape(point_offset, n_paths, dims);
     const QmcRange qr{static_cast<uint64_t>(point_offset), n_paths, dims, mirror ? 1 : 0};
     // no reduction workspace is handed out: only the launch status matters
-    launch_qmc_european<kTerminal>(sh, sh.grid, c->stream, nullptr, qr, ct, c->d_sobol, c->d_sobol + static_cast<size_t>(dims) * kSobolBits,
-                                   ReduceWs{}, d_term);
+    launch_qmc_european<kTerminal>(sh, sh.grid, c->stream, nullptr, qr, ct, d_sv, d_shift, ReduceWs{}, d_term);
     HIP_TRY(hipGetLastError());
     c->armed = 0;
     return copy_to_host(c, terminal_host, d_term, term_bytes);
@@ -2062,10 +2009,9 @@ namespace {
 // the context's device; the kernel reads node k from lane k of a trip (qmc_path_kernel).
 int qmc_bridge_plan(DeviceCtx* c, int32_t n, QmcBridgePlan* plan) {
     const size_t ab_bytes = (sizeof(uint32_t) * static_cast<size_t>(n) + 7) & ~size_t(7), bytes = ab_bytes + sizeof(double) * 3 * n;
-    if (c->bridge_n != n) {
-        std::vector<unsigned char> host(bytes, 0);
-        uint32_t* ab = reinterpret_cast<uint32_t*>(host.data());
-        double* coef = reinterpret_cast<double*>(host.data() + ab_bytes);
+    const int rc = c->bridge.ensure(n, bytes, c->stream, [c] { return c->drain(); }, [&](unsigned char* host) {
+        uint32_t* ab = reinterpret_cast<uint32_t*>(host);
+        double* coef = reinterpret_cast<double*>(host + ab_bytes);
         std::vector<std::pair<int32_t, int32_t>> queue{{0, n}};
         int32_t k = 1;
         for (size_t head = 0; head < queue.size(); ++head) {
@@ -2082,19 +2028,11 @@ int qmc_bridge_plan(DeviceCtx* c, int32_t n, QmcBridgePlan* plan) {
             queue.emplace_back(m, b);
         }
         if (k != n) return fail(OLMC_ERR_ARG, "bridge plan is incomplete");
-        c->bridge_n = 0;
-        if (c->d_bridge) {
-            HIP_TRY(hipStreamSynchronize(c->stream));            // a launch of the previous plan may still read it
-            HIP_TRY(hipFree(c->d_bridge));
-            c->d_bridge = nullptr;
-        }
-        HIP_TRY(hipMalloc(&c->d_bridge, bytes));
-        c->bridge_host.swap(host);
-        HIP_TRY(hipMemcpyAsync(c->d_bridge, c->bridge_host.data(), bytes, hipMemcpyHostToDevice, c->stream));
-        c->bridge_n = n;
-    }
-    plan->ab = static_cast<const uint32_t*>(c->d_bridge);
-    plan->coef = reinterpret_cast<const double*>(static_cast<const unsigned char*>(c->d_bridge) + ab_bytes);
+        return static_cast<int>(OLMC_OK);
+    });
+    if (rc) return rc;
+    plan->ab = c->bridge.device<uint32_t>();
+    plan->coef = reinterpret_cast<const double*>(c->bridge.device<unsigned char>() + ab_bytes);
     return OLMC_OK;
 }
 
@@ -2148,10 +2086,8 @@ struct QmcPathLaunch {
 int qmc_path_setup(DeviceCtx* c, int construction, int64_t point_offset, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift,
                    int antithetic, QmcPathLaunch* pl, int32_t dims_per_step = 1) {
     const int32_t dims = n_steps * dims_per_step;                        // the table's; the plan and qr.dims count steps
-    int rc = qmc_table(c, sv, shift, dims);
+    int rc = qmc_table(c, sv, shift, dims, &pl->d_sv, &pl->d_shift);
     if (rc) return rc;
-    pl->d_sv = c->d_sobol;
-    pl->d_shift = pl->d_sv + static_cast<size_t>(dims) * kSobolBits;
     pl->plan = QmcBridgePlan{nullptr, nullptr};
     pl->bridge = construction == OLMC_QMC_BRIDGE;
     if (pl->bridge) {
@@ -2376,13 +2312,14 @@ extern "C" int olmc_american_lsm_qmc(double S, double K, double T, double r, dou
     int rc = qmc_matrix_prologue(construction, n_points, n_steps, sv, shift, bits, lsm_bytes(n_points, n_steps), &lease);
     if (rc) return rc;
     DeviceCtx* const c = lease.c;
-    double* d_paths = static_cast<double*>(c->d_bulk);                                  // [n_steps + 1][n_points], then olmc_american_lsm's buffers
+    Carver bulk = c->bulk.carve();
+    double* d_paths = bulk.take<double>((static_cast<size_t>(n_steps) + 1) * n_points);  // [n_steps + 1][n_points], then olmc_american_lsm's buffers
     const LsmContract lc = lsm_contract(S, K, T, r, sigma, q, is_call, n_steps, poly_degree);
     EventPair ep{};
     if (g_profile) { rc = prof_begin(c, c->stream, &ep); if (rc) return rc; }
     rc = qmc_matrix(c, construction, n_points, n_steps, sv, shift, lc, false, d_paths);
     if (rc) return rc;
-    rc = lsm_chain(c, S, K, T, r, sigma, q, is_call, lc, n_points, n_steps, d_paths);
+    rc = lsm_chain(c, S, K, T, r, sigma, q, is_call, lc, n_points, n_steps, d_paths, &bulk);
     if (rc) return rc;
     if (g_profile) { rc = prof_end(c, c->stream, ep); if (rc) return rc; }
     finish_one(c->h_result, n_points, 0.0, T, poisoned(S, K, T, r, sigma, q), out);
@@ -2400,10 +2337,11 @@ extern "C" int olmc_exercise_boundary_qmc(double S, double K, double T, double r
     if (rc) return rc;
     DeviceCtx* const c = lease.c;
     const size_t path_bytes = (static_cast<size_t>(bytes) + 255) / 256 * 256;
-    rc = bulk_reserve(c, path_bytes + rows * sizeof(double));
+    Carver bulk;
+    rc = bulk_reserve(c, path_bytes + rows * sizeof(double), &bulk);
     if (rc) return rc;
-    double* d_paths = static_cast<double*>(c->d_bulk);
-    double* d_boundary = reinterpret_cast<double*>(static_cast<char*>(c->d_bulk) + path_bytes);
+    double* d_paths = bulk.take<double>(path_bytes / sizeof(double));
+    double* d_boundary = bulk.take<double>(rows);
     rc = qmc_matrix(c, construction, n_points, n_steps, sv, shift, lsm_contract(S, K, T, r, sigma, q, is_call, n_steps, 1), false, d_paths);
     if (rc) return rc;
     // as olmc_exercise_boundary: np.percentile(x, 10) for a put, 90 for a call (exotic_options.py:337-341)
@@ -2425,9 +2363,9 @@ extern "C" int olmc_gbm_qmc_paths(double S, double T, double r, double sigma, do
     DeviceCtx* const c = lease.c;
     LsmContract lc = lsm_contract(S, S, T, r, sigma, q, 0, n_steps, 1);            // no strike: only the path fields are read
     lc.s_first = S;                                                     // the export's column 0 is S itself, as olmc_gbm_paths'
-    rc = qmc_matrix(c, construction, n_points, n_steps, sv, shift, lc, path_major != 0, static_cast<double*>(c->d_bulk));
+    rc = qmc_matrix(c, construction, n_points, n_steps, sv, shift, lc, path_major != 0, c->bulk.as<double>());
     if (rc) return rc;
-    return copy_to_host(c, out_host, c->d_bulk, static_cast<size_t>(bytes));
+    return copy_to_host(c, out_host, c->bulk.get(), static_cast<size_t>(bytes));
 }
 
 // ================================================================ Heston on Sobol paths ====
@@ -2443,17 +2381,7 @@ namespace {
 int heston_slabs(DeviceCtx* c, int32_t n_steps, int32_t* grid) {
     const HestonSlabs hs = heston_slab_shape(n_steps, *grid, c->cus);
     *grid = hs.grid;
-    const size_t bytes = hs.bytes;
-    if (bytes <= c->heston_w_bytes) return OLMC_OK;
-    if (c->d_heston_w) {
-        HIP_TRY(hipStreamSynchronize(c->stream));                // a launch may still walk the old slabs
-        HIP_TRY(hipFree(c->d_heston_w));
-        c->d_heston_w = nullptr;
-        c->heston_w_bytes = 0;
-    }
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_heston_w), bytes));
-    c->heston_w_bytes = bytes;
-    return OLMC_OK;
+    return c->heston_w.reserve(hs.bytes, [c] { return c->drain(); });      // a launch may still walk the old slabs
 }
 
 // run_qmc_payoff's shape of a Heston price launch (heston_qmc_kernel, heston_qmc_path_kernel): the grid over the blocks of 64 points,
@@ -2465,7 +2393,7 @@ auto heston_qmc_shape(int64_t point_offset, int64_t n_points, int32_t n_steps) {
         pl->slabs = nullptr;
         if (!pl->bridge) return static_cast<int>(OLMC_OK);
         const int rc2 = heston_slabs(c, n_steps, &pl->grid);
-        pl->slabs = c->d_heston_w;
+        pl->slabs = c->heston_w.as<double>();
         return rc2;
     };
 }
@@ -2793,13 +2721,15 @@ bool lv_poisoned(double S, double K, double T, double r, double q, const ollv_su
 
 // The checked table rounded to fp32 onto context c (on its stream, ahead of the launch that reads it) and the model of n_steps steps.
 int lv_upload(DeviceCtx* c, const ollv_surface* s, double S, double T, double r, double q, int32_t n_steps, LvModel* m) {
-    if (!c->d_lv) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->d_lv), sizeof(float) * kLvMaxNt * kLvMaxNx));
     const size_t nodes = static_cast<size_t>(s->n_t) * s->n_x;
-    c->lv_host.resize(nodes);
-    for (size_t k = 0; k < nodes; ++k) c->lv_host[k] = static_cast<float>(s->vol[k]);
-    HIP_TRY(hipMemcpyAsync(c->d_lv, c->lv_host.data(), sizeof(float) * nodes, hipMemcpyHostToDevice, c->stream));
+    const int rc = c->lv.upload(sizeof(float) * nodes, c->stream, [c] { return c->drain(); }, [&](unsigned char* host) {
+        float* f = reinterpret_cast<float*>(host);
+        for (size_t k = 0; k < nodes; ++k) f[k] = static_cast<float>(s->vol[k]);
+        return 0;
+    }, sizeof(float) * kLvMaxNt * kLvMaxNx);                // the block is sized for the largest table by the first call
+    if (rc) return rc;
     const double dt = T / n_steps;
-    m->nodes = c->d_lv;
+    m->nodes = c->lv.device<float>();
     m->n_x = s->n_x;
     m->n_t = s->n_t;
     m->x_lo = s->x_lo;
@@ -2879,9 +2809,9 @@ extern "C" int ollv_paths(double S, double T, double r, double q, const ollv_sur
     rc = lv_upload(c, surf, S, T, r, q, n_steps, &m);
     if (rc) return rc;
     const PathRange pr = make_range(0, n_paths, n_steps, seed);
-    with_bool(path_major != 0, [&](auto pm) { lv_launch(lv_paths_kernel<pm>, m, true, grid_for(n_paths), c->stream, nullptr, pr, m, static_cast<double*>(c->d_bulk)); });
+    with_bool(path_major != 0, [&](auto pm) { lv_launch(lv_paths_kernel<pm>, m, true, grid_for(n_paths), c->stream, nullptr, pr, m, c->bulk.as<double>()); });
     HIP_TRY(hipGetLastError());
-    return copy_to_host(c, out_host, c->d_bulk, static_cast<size_t>(bytes));
+    return copy_to_host(c, out_host, c->bulk.get(), static_cast<size_t>(bytes));
 }
 
 extern "C" int ollv_surface_prices(double S, double T, double r, double q, int is_call, const ollv_surface* surf, const double* strikes,
@@ -3225,10 +3155,9 @@ int qmc_batch_device(DeviceCtx* c, const olmc_option* opts, int32_t k, int64_t p
     const QmcShape sh = qmc_shape(point_offset, n_paths, dims);
     if (k < 2 || (sh.units + kBlock - 1) / kBlock > kMaxGrid)
         return fail(OLMC_ERR_ARG, "a shard of fused Sobol contracts needs 2 .. 16 contracts and points one grid covers");
-    int rc = qmc_table(c, sv, shift, dims);
+    const uint32_t *d_sv, *d_shift;
+    int rc = qmc_table(c, sv, shift, dims, &d_sv, &d_shift);
     if (rc) return rc;
-    const uint32_t* d_sv = c->d_sobol;
-    const uint32_t* d_shift = d_sv + static_cast<size_t>(dims) * kSobolBits;
     const QmcRange qr{static_cast<uint64_t>(point_offset), n_paths, dims, 0};
     const int32_t grid = sh.split ? sh.grid : static_cast<int32_t>((sh.units + kBlock - 1) / kBlock);     // the grid covers every point / block
     const int nsets = k <= 8 ? 8 : 16;
@@ -3362,6 +3291,7 @@ struct MultiEngine;
 struct MultiRank {
     int device = -1;
     DeviceCtx* ctx = nullptr;                       // the rank's own: its stream is the rank stream
+    DeviceBlock<Mem> buffers;                       // d_send and d_recv
     double* d_send = nullptr;                       // [kMultiValues] this rank's sums (written by its path kernel's last workgroup)
     double* d_recv = nullptr;                       // [kMultiValues] the reduced sums
     hipEvent_t queued = nullptr;                    // rehearsal only: the rank's path kernel is queued behind this
@@ -3419,7 +3349,7 @@ void engine_destroy(MultiEngine* e) {
     for (MultiRank& rk : e->ranks) {
         if (rk.device < 0 || hipSetDevice(rk.device) != hipSuccess) continue;
         if (rk.ctx) ctx_release(rk.ctx);
-        if (rk.d_send) (void)hipFree(rk.d_send);
+        (void)rk.buffers.reset();
         if (rk.queued) (void)hipEventDestroy(rk.queued);
     }
     (void)hipGetLastError();
@@ -3450,8 +3380,10 @@ int engine_build(const std::vector<int>& devs, bool rehearsal, MultiEngine** out
         rk.device = devs[d];
         constexpr int kStride = 64;                  // doubles: the receive buffer starts on its own 512-byte boundary (the collective's vector accesses)
         static_assert(kStride >= kMultiValues, "rank buffers hold the widest payload");
-        hipError_t err = hipMalloc(&rk.d_send, sizeof(double) * 2 * kStride);
-        if (err == hipSuccess) { rk.d_recv = rk.d_send + kStride; err = hipEventCreateWithFlags(&rk.queued, hipEventDisableTiming); }
+        if (rk.buffers.reserve(sizeof(double) * 2 * kStride, no_users)) return bail(fail(OLMC_ERR_HIP, "multi-GPU engine, rank " + std::to_string(d) + ": " + t_error));
+        rk.d_send = rk.buffers.as<double>();
+        rk.d_recv = rk.d_send + kStride;
+        const hipError_t err = hipEventCreateWithFlags(&rk.queued, hipEventDisableTiming);
         if (err != hipSuccess) return bail(fail(OLMC_ERR_HIP, std::string("multi-GPU engine, rank ") + std::to_string(d) + ": " + hipGetErrorString(err)));
     }
     if (!rehearsal) {
@@ -3837,15 +3769,16 @@ extern "C" int olmc_philox_words(uint64_t seed, int64_t path_offset, int64_t n_p
     if (rc) return rc;
     DeviceCtx* const c = lease.c;
     const size_t bytes = sizeof(uint32_t) * 4 * static_cast<size_t>(n_paths) * n_blocks;
-    rc = bulk_reserve(c, bytes);
+    Carver bulk;
+    rc = bulk_reserve(c, bytes, &bulk);
     if (rc) return rc;
+    uint32_t* d_words = bulk.take<uint32_t>(bytes / sizeof(uint32_t));
     const int64_t total = n_paths * n_blocks;
     const int grid = static_cast<int>(std::min<int64_t>((total + 255) / 256, 4096));
     hipLaunchKernelGGL(philox_words_kernel, dim3(grid), dim3(256), 0, c->stream, static_cast<uint64_t>(path_offset), n_paths,
-                       block0, n_blocks, stream_tag, static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32),
-                       static_cast<uint32_t*>(c->d_bulk));
+                       block0, n_blocks, stream_tag, static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32), d_words);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out_host, c->d_bulk, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(out_host, d_words, bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return OLMC_OK;
 }
@@ -3857,15 +3790,16 @@ extern "C" int olmc_normals(uint64_t seed, int64_t path_offset, int64_t n_paths,
     if (rc) return rc;
     DeviceCtx* const c = lease.c;
     const size_t bytes = sizeof(float) * static_cast<size_t>(n_paths) * n_steps;
-    rc = bulk_reserve(c, bytes);
+    Carver bulk;
+    rc = bulk_reserve(c, bytes, &bulk);
     if (rc) return rc;
+    float* d_z = bulk.take<float>(bytes / sizeof(float));
     const int64_t total = n_paths * ((n_steps + 3) / 4);
     const int grid = static_cast<int>(std::min<int64_t>((total + 255) / 256, 4096));
     hipLaunchKernelGGL(normals_kernel, dim3(grid), dim3(256), 0, c->stream, static_cast<uint64_t>(path_offset), n_paths,
-                       n_steps, static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32),
-                       static_cast<float*>(c->d_bulk));
+                       n_steps, static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32), d_z);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out_host, c->d_bulk, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(out_host, d_z, bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return OLMC_OK;
 }

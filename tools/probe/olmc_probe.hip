@@ -19,10 +19,11 @@ extern "C" int olmc_exp2_probe_form(const double* x_host, int64_t n, double* y_h
     if (rc) return rc;
     DeviceCtx* const c = lease.c;
     const size_t bytes = sizeof(double) * static_cast<size_t>(n);
-    rc = bulk_reserve(c, 2 * bytes);
+    Carver bulk;
+    rc = bulk_reserve(c, 2 * bytes, &bulk);
     if (rc) return rc;
-    double* d_x = static_cast<double*>(c->d_bulk);
-    double* d_y = d_x + n;
+    double* d_x = bulk.take<double>(n);
+    double* d_y = bulk.take<double>(n);
     HIP_TRY(hipMemcpyAsync(d_x, x_host, bytes, hipMemcpyHostToDevice, c->stream));
     const int grid = static_cast<int>(std::min<int64_t>((n + 255) / 256, 4096));
     hipLaunchKernelGGL(exp2_probe_kernel, dim3(grid), dim3(256), 0, c->stream, d_x, n, d_y, form);
@@ -47,10 +48,11 @@ extern "C" int olmc_ndtri_probe(const double* p_host, int64_t n, double* z_host,
     if (rc) return rc;
     DeviceCtx* const c = lease.c;
     const size_t bytes = sizeof(double) * static_cast<size_t>(n);
-    rc = bulk_reserve(c, 2 * bytes);
+    Carver bulk;
+    rc = bulk_reserve(c, 2 * bytes, &bulk);
     if (rc) return rc;
-    double* d_p = static_cast<double*>(c->d_bulk);
-    double* d_z = d_p + n;
+    double* d_p = bulk.take<double>(n);
+    double* d_z = bulk.take<double>(n);
     HIP_TRY(hipMemcpyAsync(d_p, p_host, bytes, hipMemcpyHostToDevice, c->stream));
     const int grid = static_cast<int>(std::min<int64_t>((n + 255) / 256, 4096));
     hipLaunchKernelGGL(ndtri_probe_kernel, dim3(grid), dim3(256), 0, c->stream, d_p, n, d_z, form);
@@ -70,13 +72,14 @@ extern "C" int olmc_box_muller_probe(const uint32_t* xa_host, const uint32_t* xb
     DeviceCtx* const c = lease.c;
     const size_t bytes = sizeof(uint32_t) * static_cast<size_t>(n);
     static_assert(sizeof(uint32_t) == sizeof(float), "one stride for words and normals");
-    rc = bulk_reserve(c, 5 * bytes);
+    Carver bulk;
+    rc = bulk_reserve(c, 5 * bytes, &bulk);
     if (rc) return rc;
-    uint32_t* d_xa = static_cast<uint32_t*>(c->d_bulk);
-    uint32_t* d_xb = d_xa + n;
-    float* d_cos = reinterpret_cast<float*>(d_xb + n);
-    float* d_sin = d_cos + n;
-    float* d_pair = d_sin + n;
+    uint32_t* d_xa = bulk.take<uint32_t>(n);
+    uint32_t* d_xb = bulk.take<uint32_t>(n);
+    float* d_cos = bulk.take<float>(n);
+    float* d_sin = bulk.take<float>(n);
+    float* d_pair = bulk.take<float>(n);
     HIP_TRY(hipMemcpyAsync(d_xa, xa_host, bytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(d_xb, xb_host, bytes, hipMemcpyHostToDevice, c->stream));
     const int grid = static_cast<int>(std::min<int64_t>((n + 255) / 256, 4096));
@@ -98,10 +101,11 @@ extern "C" int olmc_sqrt_nonneg_probe(const double* x_host, int64_t n, double* y
     if (rc) return rc;
     DeviceCtx* const c = lease.c;
     const size_t bytes = sizeof(double) * static_cast<size_t>(n);
-    rc = bulk_reserve(c, 2 * bytes);
+    Carver bulk;
+    rc = bulk_reserve(c, 2 * bytes, &bulk);
     if (rc) return rc;
-    double* d_x = static_cast<double*>(c->d_bulk);
-    double* d_y = d_x + n;
+    double* d_x = bulk.take<double>(n);
+    double* d_y = bulk.take<double>(n);
     HIP_TRY(hipMemcpyAsync(d_x, x_host, bytes, hipMemcpyHostToDevice, c->stream));
     const int grid = static_cast<int>(std::min<int64_t>((n + 255) / 256, 4096));
     hipLaunchKernelGGL(sqrt_nonneg_probe_kernel, dim3(grid), dim3(256), 0, c->stream, d_x, n, d_y);
@@ -178,7 +182,7 @@ extern "C" int olmc_reduce_probe(int nv, int form, int values, int blocking, int
     const size_t bytes = sizeof(double) * static_cast<size_t>(launches) * row;
     rc = bulk_reserve(c, bytes);
     if (rc) return rc;
-    double* const d_out = static_cast<double*>(c->d_bulk);
+    double* const d_out = c->bulk.as<double>();
     ReduceWs widest;                                         // the workspace grows (and waits for the stream) here, not between the launches
     rc = make_ws(c, c->stream, grid_of(most), nv, d_out, -1.0, &widest);
     if (rc) return rc;
@@ -206,10 +210,11 @@ extern "C" int olmc_rows_sum_probe(int nv, int whole_workgroup, const double* ro
     if (rc) return rc;
     DeviceCtx* const c = lease.c;
     const size_t count = static_cast<size_t>(rows) * nv;
-    rc = bulk_reserve(c, sizeof(double) * (count + nv));
+    Carver bulk;
+    rc = bulk_reserve(c, sizeof(double) * (count + nv), &bulk);
     if (rc) return rc;
-    double* d_rows = static_cast<double*>(c->d_bulk);
-    double* d_out = d_rows + count;
+    double* d_rows = bulk.take<double>(count);
+    double* d_out = bulk.take<double>(nv);
     HIP_TRY(hipMemcpyAsync(d_rows, rows_host, sizeof(double) * count, hipMemcpyHostToDevice, c->stream));
     with_reduce_width(nv, [&](auto width) {
         if (whole_workgroup) {
@@ -235,10 +240,11 @@ extern "C" int olmc_wave_reduce_probe(int p, int op, const double* v_host, doubl
     if (rc) return rc;
     DeviceCtx* const c = lease.c;
     const size_t count = static_cast<size_t>(kWave) * p;
-    rc = bulk_reserve(c, sizeof(double) * (count + kWave));
+    Carver bulk;
+    rc = bulk_reserve(c, sizeof(double) * (count + kWave), &bulk);
     if (rc) return rc;
-    double* d_v = static_cast<double*>(c->d_bulk);
-    double* d_out = d_v + count;
+    double* d_v = bulk.take<double>(count);
+    double* d_out = bulk.take<double>(kWave);
     HIP_TRY(hipMemcpyAsync(d_v, v_host, sizeof(double) * count, hipMemcpyHostToDevice, c->stream));
     auto with_p = [&](auto f) {
         switch (p) {
@@ -282,10 +288,11 @@ extern "C" int olmc_clock_probe(int64_t n_paths, int32_t n_steps, uint64_t seed,
     DeviceCtx* const c = lease.c;
     const int32_t grid = static_cast<int32_t>(std::min<int64_t>((n_paths + kBlock - 1) / kBlock, kMaxGrid));
     const size_t bytes = sizeof(uint64_t) * 2 * static_cast<size_t>(grid) + 256;
-    rc = bulk_reserve(c, bytes);
+    Carver bulk;
+    rc = bulk_reserve(c, bytes, &bulk);
     if (rc) return rc;
-    uint64_t* d_stamps = static_cast<uint64_t*>(c->d_bulk);
-    double* d_sink = reinterpret_cast<double*>(d_stamps + 2 * static_cast<size_t>(grid));
+    uint64_t* d_stamps = bulk.take<uint64_t>(2 * static_cast<size_t>(grid));
+    double* d_sink = bulk.take<double>(256 / sizeof(double));
     const PathRange pr = make_range(0, static_cast<int64_t>(grid) * kBlock, n_steps, seed);
     hipLaunchKernelGGL(clock_probe_kernel, dim3(grid), dim3(kBlock), 0, c->stream, pr, d_stamps, d_sink);
     HIP_TRY(hipGetLastError());
@@ -329,7 +336,8 @@ extern "C" int olmc_phase_stamps(int64_t n_paths, int32_t n_steps, uint64_t seed
     if (capacity < words) return fail(OLMC_ERR_ARG, "stamp buffer too small: need 5 * workgroups + 1 words");
     rc = bulk_reserve(c, sizeof(uint64_t) * static_cast<size_t>(words));
     if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(c->d_bulk, 0, sizeof(uint64_t) * static_cast<size_t>(words), c->stream));
+    uint64_t* const d_stamps = c->bulk.as<uint64_t>();
+    HIP_TRY(hipMemsetAsync(d_stamps, 0, sizeof(uint64_t) * static_cast<size_t>(words), c->stream));
     ContractSet<1> cs;
     cs.c[0] = make_contract(make_option(100.0, 100.0, 1.0, 0.05, 0.2, 0.0, 1), n_steps);
     cs.base_mask = 1u; cs.upper_continues_slot0 = 0;
@@ -349,16 +357,16 @@ extern "C" int olmc_phase_stamps(int64_t n_paths, int32_t n_steps, uint64_t seed
     ReduceWs quiet = ws;
     quiet.done_flag = nullptr;
     for (int32_t k = 0; k < lead_launches; ++k) {
-        hipLaunchKernelGGL(european_stamp_kernel, dim3(grid), dim3(kBlock), 0, c->stream, pr, cs, quiet, static_cast<uint64_t*>(c->d_bulk));
+        hipLaunchKernelGGL(european_stamp_kernel, dim3(grid), dim3(kBlock), 0, c->stream, pr, cs, quiet, d_stamps);
         rc = after_launch(c, c->stream);             // a failed launch leaves the self-resetting counters to ws_recover()
         if (rc) return rc;
     }
-    hipExtLaunchKernelGGL(european_stamp_kernel, dim3(grid), dim3(kBlock), 0, c->stream, ep.start, ep.stop, 0, pr, cs, ws, static_cast<uint64_t*>(c->d_bulk));
+    hipExtLaunchKernelGGL(european_stamp_kernel, dim3(grid), dim3(kBlock), 0, c->stream, ep.start, ep.stop, 0, pr, cs, ws, d_stamps);
     rc = after_launch(c, c->stream);
     if (rc) return rc;
     rc = sync_or_recover(c, c->stream);
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(stamps_host, c->d_bulk, sizeof(uint64_t) * static_cast<size_t>(words), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(stamps_host, d_stamps, sizeof(uint64_t) * static_cast<size_t>(words), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     float ms = 0.f;
     HIP_TRY(hipEventElapsedTime(&ms, ep.start, ep.stop));
@@ -393,7 +401,7 @@ extern "C" int olmc_issue_probe(int op, int waves_per_simd, double* ns_per_instr
     rc = prof_acquire(c, &ep);
     if (rc) return rc;
     for (int rep = 0; rep < 2; ++rep) {          // first launch warms the instruction cache
-        hipExtLaunchKernelGGL(table[op], grid, block, 0, c->stream, ep.start, ep.stop, 0, static_cast<uint32_t*>(c->d_bulk), 1u, 0xD2511F53u);
+        hipExtLaunchKernelGGL(table[op], grid, block, 0, c->stream, ep.start, ep.stop, 0, c->bulk.as<uint32_t>(), 1u, 0xD2511F53u);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
