@@ -162,6 +162,15 @@ LV_PROTOTYPES = {
                                          C.POINTER(Stats)]),
 }
 
+# and for include/olmc_local_vol_qmc.h (prefix olvq_: the two dicts above stay as they are)
+_U32P = C.POINTER(C.c_uint32)
+LVQ_PROTOTYPES = {
+    "olvq_price": (_I, [_D] * 5 + [_I, C.POINTER(LvSurface), _I, _D, _I, _I64, _I64, _I32, _U32P, _U32P, _I32, _I, C.POINTER(Stats)]),
+    "olvq_paths": (_I, [_D] * 4 + [C.POINTER(LvSurface), _I, _I64, _I32, _U32P, _U32P, _I32, _I, C.POINTER(_D)]),
+    "olvq_surface_prices": (_I, [_D] * 4 + [_I, C.POINTER(LvSurface), C.POINTER(_D), C.POINTER(_I32), _I32, _I, _I64, _I64, _I32, _U32P, _U32P,
+                                         _I32, _I, C.POINTER(Stats)]),
+}
+
 _lock = threading.Lock()
 _lib: Optional[C.CDLL] = None
 _initialised = False
@@ -204,7 +213,7 @@ def load_library() -> C.CDLL:
                 lib = C.CDLL(LIBRARY_PATH)
             except OSError as e:
                 raise AccelerationError(f"cannot load {LIBRARY_PATH}: {e}", backend="hip") from e
-            for name, (res, args) in list(PROTOTYPES.items()) + list(LV_PROTOTYPES.items()):
+            for name, (res, args) in list(PROTOTYPES.items()) + list(LV_PROTOTYPES.items()) + list(LVQ_PROTOTYPES.items()):
                 try:
                     fn = getattr(lib, name)
                 except AttributeError:
@@ -807,6 +816,38 @@ def lv_surface_prices(S, T, r, q, is_call: bool, table, strikes, steps, n_paths:
     strikes, steps, pk, ps, out = _surface_cells(strikes, steps)
     _check(lib().ollv_surface_prices(S, T, r, q, int(is_call), C.byref(surf), pk, ps, len(strikes), int(path_offset), int(n_paths), int(n_steps),
                                      seed64(seed), int(antithetic), out))
+    return list(out)[:len(strikes)]
+
+
+def lvq_price(S, K, T, r, q, is_call: bool, table, payoff: int, barrier: float, n_points: int, sv: np.ndarray, shift: np.ndarray,
+              bridge: bool = True, antithetic: bool = False, point_offset: int = 0) -> Stats:
+    """lv_price on scrambled-Sobol paths (olvq_price): n_steps = sv.shape[0] dimensions, one per step; sv / shift as extrema_qmc."""
+    sv, psv, shift, psh = _sobol_args(sv, shift, point_offset, n_points)
+    surf, _keep = lv_surface(*table)
+    out = Stats()
+    _check(lib().olvq_price(S, K, T, r, q, int(is_call), C.byref(surf), int(payoff), float(barrier), QMC_BRIDGE if bridge else QMC_SEQUENTIAL,
+                            int(point_offset), int(n_points), int(sv.shape[0]), psv, psh, int(sv.shape[1]), int(antithetic), C.byref(out)))
+    return out
+
+
+def lvq_paths(S, T, r, q, table, n_points: int, sv: np.ndarray, shift: np.ndarray, bridge: bool = True, path_major: bool = False) -> np.ndarray:
+    """The spot matrix of lvq_price's points [0, n_points) (olvq_paths; the non-mirrored leg), in gbm_paths' layouts."""
+    sv, psv, shift, psh = _sobol_args(sv, shift, 0, n_points)
+    surf, _keep = lv_surface(*table)
+    out = _path_matrix(n_points, int(sv.shape[0]), path_major)
+    _check(lib().olvq_paths(S, T, r, q, C.byref(surf), QMC_BRIDGE if bridge else QMC_SEQUENTIAL, int(n_points), int(sv.shape[0]), psv, psh,
+                            int(sv.shape[1]), int(path_major), out.ctypes.data_as(C.POINTER(C.c_double))))
+    return out
+
+
+def lvq_surface_prices(S, T, r, q, is_call: bool, table, strikes, steps, n_points: int, sv: np.ndarray, shift: np.ndarray, bridge: bool = True,
+                       antithetic: bool = False, point_offset: int = 0) -> List[Stats]:
+    """lv_surface_prices on lvq_price's points (olvq_surface_prices): sv.shape[0] steps to T, at most 16 cells."""
+    sv, psv, shift, psh = _sobol_args(sv, shift, point_offset, n_points)
+    surf, _keep = lv_surface(*table)
+    strikes, steps, pk, ps, out = _surface_cells(strikes, steps)
+    _check(lib().olvq_surface_prices(S, T, r, q, int(is_call), C.byref(surf), pk, ps, len(strikes), QMC_BRIDGE if bridge else QMC_SEQUENTIAL,
+                                     int(point_offset), int(n_points), int(sv.shape[0]), psv, psh, int(sv.shape[1]), int(antithetic), out))
     return list(out)[:len(strikes)]
 
 

@@ -7,8 +7,10 @@
 // and fails loudly when no HIP device is usable -- there is no CPU fallback.
 #include "olmc.h"
 #include "olmc_local_vol.h"
+#include "olmc_local_vol_qmc.h"
 #include "olmc_kernels.h"
 #include "olmc_local_vol_kernels.h"
+#include "olmc_local_vol_qmc_kernels.h"
 #include "olmc_job_board.h"
 #include "olmc_device_mem.h"
 
@@ -115,7 +117,7 @@ struct DeviceCtx {
     // the Brownian-bridge plan of the last bridge-constructed QMC path call, [n uint32 a | b << 16][3 x n doubles ca, cb, sd], keyed
     // by n: it depends on n_steps alone (qmc_bridge_plan)
     CachedUpload<Mem> bridge;
-    DeviceBlock<Mem> heston_w;       // the bridge slabs of heston_qmc_kernel: [waves of the grid][2 n][64] doubles (heston_slabs)
+    DeviceBlock<Mem> heston_w;       // the bridge slabs of heston_qmc_kernel: [waves of the grid][2 n][64] doubles (heston_slabs); lv_qmc_price_kernel's [n][64]
     // the local-volatility table of the call in flight (olmc_local_vol.h), fp32 nodes, uploaded by every call: nothing reads it
     // after the lease ends (lv_upload)
     CachedUpload<Mem> lv;
@@ -2378,8 +2380,8 @@ namespace {
 // the slabs of a launch stay under kHestonSlabCap (the grid shrinks further): the buffer follows the device and n, not the number of
 // points -- 0.5 GiB at 252 steps and 1 GiB from 504 steps on with 256 CUs, kept with the context.
 // The sizes are olmc_host_math.h's heston_slab_shape.
-int heston_slabs(DeviceCtx* c, int32_t n_steps, int32_t* grid) {
-    const HestonSlabs hs = heston_slab_shape(n_steps, *grid, c->cus);
+int heston_slabs(DeviceCtx* c, int32_t n_steps, int32_t* grid, int32_t factors = 2) {
+    const HestonSlabs hs = heston_slab_shape(n_steps, *grid, c->cus, factors);
     *grid = hs.grid;
     return c->heston_w.reserve(hs.bytes, [c] { return c->drain(); });      // a launch may still walk the old slabs
 }
@@ -2720,7 +2722,8 @@ bool lv_poisoned(double S, double K, double T, double r, double q, const ollv_su
 }
 
 // The checked table rounded to fp32 onto context c (on its stream, ahead of the launch that reads it) and the model of n_steps steps.
-int lv_upload(DeviceCtx* c, const ollv_surface* s, double S, double T, double r, double q, int32_t n_steps, LvModel* m) {
+// z_unit: what one unit of the kernel's normals is worth (kZScale: the Philox stream's raw normals; 1: the Sobol kernels' true ones).
+int lv_upload(DeviceCtx* c, const ollv_surface* s, double S, double T, double r, double q, int32_t n_steps, LvModel* m, double z_unit = kZScale) {
     const size_t nodes = static_cast<size_t>(s->n_t) * s->n_x;
     const int rc = c->lv.upload(sizeof(float) * nodes, c->stream, [c] { return c->drain(); }, [&](unsigned char* host) {
         float* f = reinterpret_cast<float*>(host);
@@ -2738,7 +2741,7 @@ int lv_upload(DeviceCtx* c, const ollv_surface* s, double S, double T, double r,
     m->dt = dt;
     m->rq_dt = (r - q) * dt;
     m->half_dt = 0.5 * dt;
-    m->vol_unit = std::sqrt(dt) * kZScale;
+    m->vol_unit = std::sqrt(dt) * z_unit;
     m->s0 = S;
     m->log_s0 = std::log(S);
     return OLMC_OK;
@@ -2841,6 +2844,126 @@ extern "C" int ollv_surface_prices(double S, double T, double r, double q, int i
                        });
     if (rc) return rc;
     surface_finish(c->h_result, so, strikes, steps, k, n_local * (antithetic ? 2 : 1), r, T / n_steps, bad, out);
+    return OLMC_OK;
+}
+
+// ====================================================== Dupire local volatility on Sobol paths ====
+// include/olmc_local_vol_qmc.h: the three entry points above on scrambled-Sobol points (olmc_local_vol_qmc_kernels.h).  The checks are
+// those of both sides, from their helpers: the table, payoff and cells as above, the construction, tables and points as the other
+// Sobol path calls (one dimension per step), all before the lease.
+namespace {
+// The shape of a local-volatility Sobol launch (lv_qmc_price_kernel, lv_qmc_surface_kernel): heston_qmc_shape's grid over the aligned
+// blocks of 64 points, for the bridge one [n][64] slab per wave of the grid in the Heston kernels' block (heston_slabs), then the table
+// and the model in units of true normals.
+auto lv_qmc_shape(const ollv_surface* surf, double S, double T, double r, double q, int64_t point_offset, int64_t n_points, int32_t n_steps,
+                  LvModel* m) {
+    return [=](DeviceCtx* c, QmcPathLaunch* pl) {
+        const int64_t first_block = point_offset / kWave, last_block = (point_offset + n_points - 1) / kWave;
+        pl->grid = qmc_block_grid(last_block - first_block + 1);
+        pl->slabs = nullptr;
+        if (pl->bridge) {
+            const int rc = heston_slabs(c, n_steps, &pl->grid, 1);
+            if (rc) return rc;
+            pl->slabs = c->heston_w.as<double>();
+        }
+        return lv_upload(c, surf, S, T, r, q, n_steps, m, 1.0);
+    };
+}
+}  // namespace
+
+extern "C" int olvq_price(double S, double K, double T, double r, double q, int is_call, const ollv_surface* surf, int payoff, double barrier,
+                          int construction, int64_t point_offset, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift,
+                          int32_t bits, int antithetic, olmc_stats* out) {
+    if (!out) return fail(OLMC_ERR_ARG, "null pointer");
+    int rc = lv_surface_check(surf);
+    if (rc) return rc;
+    rc = lv_payoff_check(payoff, barrier);
+    if (rc) return rc;
+    rc = qmc_path_check(construction, point_offset, n_points, n_steps, sv, shift, bits);
+    if (rc) return rc;
+    const ExtremaContract ec = heston_path_contract(S, K, is_call, payoff == OLLV_EUROPEAN ? OLMC_PATH_ASIAN_ARITHMETIC : payoff, barrier);
+    const bool bad = lv_poisoned(S, K, T, r, q, surf) || (heston_path_is_barrier(payoff) && std::isnan(barrier));
+    LvModel m;
+    return run_qmc_payoff(construction, point_offset, n_points, n_steps, sv, shift, antithetic, r, T, bad, out,
+                          [&](int32_t g, hipStream_t s, const EventPair* timed, const QmcPathLaunch& pl, const ReduceWs& ws) {
+                              with_lv_family(payoff, [&](auto f) {
+                                  with_bool(pl.bridge, [&](auto b) {
+                                      with_bool(pl.anti, [&](auto a) {
+                                          lv_launch(lv_qmc_price_kernel<f, b, a>, m, true, g, s, timed, pl.qr, m, ec, pl.inv_steps, pl.d_sv, pl.d_shift,
+                                                    pl.plan, pl.slabs, ws);
+                                      });
+                                  });
+                              });
+                          },
+                          1, lv_qmc_shape(surf, S, T, r, q, point_offset, n_points, n_steps, &m));
+}
+
+extern "C" int olvq_paths(double S, double T, double r, double q, const ollv_surface* surf, int construction, int64_t n_points, int32_t n_steps,
+                          const uint32_t* sv, const uint32_t* shift, int32_t bits, int path_major, double* out_host) {
+    if (!out_host) return fail(OLMC_ERR_ARG, "null pointer");
+    int rc = lv_surface_check(surf);
+    if (rc) return rc;
+    rc = qmc_path_check(construction, 0, n_points, n_steps, sv, shift, bits);
+    if (rc) return rc;
+    const double bytes = 8.0 * static_cast<double>(n_points) * (n_steps + 1.0);
+    CtxLease lease;
+    rc = matrix_prologue(n_points, n_steps, bytes, "path matrix would exceed 64 GB", &lease);
+    if (rc) return rc;
+    DeviceCtx* const c = lease.c;
+    QmcPathLaunch pl;
+    rc = qmc_path_setup(c, construction, 0, n_points, n_steps, sv, shift, 0, &pl);
+    if (rc) return rc;
+    LvModel m;
+    rc = lv_upload(c, surf, S, T, r, q, n_steps, &m, 1.0);
+    if (rc) return rc;
+    const int32_t grid = qmc_block_grid((n_points + kWave - 1) / kWave);
+    EventPair ep{};
+    const EventPair* timed = nullptr;                  // profiling on: the path kernel counts in olmc_kernel_time
+    rc = prof_pair(c, &ep, &timed);
+    if (rc) return rc;
+    with_bool(pl.bridge, [&](auto b) {
+        with_bool(path_major != 0, [&](auto pm) {
+            lv_launch(lv_qmc_paths_kernel<b, pm>, m, true, grid, c->stream, timed, pl.qr, m, pl.d_sv, pl.d_shift, pl.plan, c->bulk.as<double>());
+        });
+    });
+    HIP_TRY(hipGetLastError());
+    return copy_to_host(c, out_host, c->bulk.get(), static_cast<size_t>(bytes));
+}
+
+extern "C" int olvq_surface_prices(double S, double T, double r, double q, int is_call, const ollv_surface* surf, const double* strikes,
+                                   const int32_t* steps, int32_t k, int construction, int64_t point_offset, int64_t n_points, int32_t n_steps,
+                                   const uint32_t* sv, const uint32_t* shift, int32_t bits, int antithetic, olmc_stats* out) {
+    if (!strikes || !steps || !out) return fail(OLMC_ERR_ARG, "null pointer");
+    int rc = lv_surface_check(surf);
+    if (rc) return rc;
+    rc = qmc_path_check(construction, point_offset, n_points, n_steps, sv, shift, bits);
+    if (rc) return rc;
+    SurfaceOrder so;
+    rc = surface_cells(strikes, steps, k, n_steps, &so);
+    if (rc) return rc;
+    const bool bad = lv_poisoned(S, 0.0, T, r, q, surf);
+    CtxLease lease;
+    rc = ctx_lease(&lease);
+    if (rc) return rc;
+    DeviceCtx* const c = lease.c;
+    QmcPathLaunch pl;
+    rc = qmc_path_setup(c, construction, point_offset, n_points, n_steps, sv, shift, antithetic, &pl);
+    if (rc) return rc;
+    LvModel m;
+    rc = lv_qmc_shape(surf, S, T, r, q, point_offset, n_points, n_steps, &m)(c, &pl);
+    if (rc) return rc;
+    const double sign = is_call ? 1.0 : -1.0;
+    rc = launch_reduce(c, c->stream, c->d_result, -1.0, 2 * kSurfaceCells, pl.grid,
+                       [&](int32_t g, hipStream_t s, const EventPair* timed, const ReduceWs& ws) {
+                           with_bool(pl.bridge, [&](auto b) {
+                               with_bool(pl.anti, [&](auto a) {
+                                   lv_launch(lv_qmc_surface_kernel<b, a>, m, true, g, s, timed, pl.qr, m, sign, so.cells, pl.d_sv, pl.d_shift, pl.plan,
+                                             pl.slabs, ws);
+                               });
+                           });
+                       });
+    if (rc) return rc;
+    surface_finish(c->h_result, so, strikes, steps, k, n_points * (pl.anti ? 2 : 1), r, T / n_steps, bad, out);
     return OLMC_OK;
 }
 

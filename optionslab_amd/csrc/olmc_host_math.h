@@ -632,7 +632,8 @@ inline QmcShape qmc_launch_shape(int64_t point_offset, int64_t n_paths, int32_t 
     return sh;
 }
 
-// The bridge slabs of the Heston Sobol kernels: one [2 n][64] slab of doubles per wave of the grid.  The grid the launch starts from is
+// The bridge slabs of the Heston Sobol kernels: one [2 n][64] slab of doubles per wave of the grid ([factors n][64]: the local-volatility
+// Sobol kernels have one factor).  The grid the launch starts from is
 // cut to the workgroups the device holds at once (kHestonBridgeBlocksPerCu per CU) and to what keeps the slabs under kHestonSlabCap;
 // the waves stride over the blocks beyond, each reusing its slab.
 struct HestonSlabs {
@@ -641,9 +642,9 @@ struct HestonSlabs {
     int32_t grid;
     size_t bytes;        // of the whole launch's slabs
 };
-inline HestonSlabs heston_slab_shape(int32_t n_steps, int32_t grid, int cus) {
+inline HestonSlabs heston_slab_shape(int32_t n_steps, int32_t grid, int cus, int32_t factors = 2) {
     HestonSlabs s;
-    s.slab = 2 * static_cast<size_t>(n_steps) * kWave * sizeof(double);
+    s.slab = static_cast<size_t>(factors) * static_cast<size_t>(n_steps) * kWave * sizeof(double);
     s.fit = static_cast<int32_t>(std::max<size_t>(kHestonSlabCap / (s.slab * kWavesPerBlock), 1));
     s.grid = std::min(grid, std::min(s.fit, std::max(cus, 1) * kHestonBridgeBlocksPerCu));
     s.bytes = s.slab * kWavesPerBlock * static_cast<size_t>(s.grid);

@@ -6,6 +6,7 @@ Calibration follows the reference's rules in code of this package's own: `dupire
 uniform table over (tau, x = ln(S_t / S)) (`local_vol_table`) and Monte Carlo paths walk it on the GPU (include/olmc_local_vol.h):
 Europeans, Asians, barriers, lookbacks and a strike x maturity surface, each in one launch, on the GBM Philox stream.
 `price_fdm` itself is not restated (INTEGRATION.md "Local volatility").
+Additive: `DupireLocalVolQMC` (`model.qmc()`) runs the same methods on scrambled-Sobol points (include/olmc_local_vol_qmc.h).
 """
 from __future__ import annotations
 
@@ -148,9 +149,19 @@ class DupireLocalVol:
         seed = self.seed if seed is None else seed
         return n_paths, n_steps, seed if seed is not None else int(np.random.default_rng().integers(0, 2**31))
 
+    # The three device calls, each on a table of local_vol_table and the sizes and seed _sizes settled: what DupireLocalVolQMC overrides.
+    def _device_price(self, S, K, T, r, q, is_call, table, payoff, barrier, n_paths, n_steps, seed, antithetic):
+        return _hip.lv_price(S, K, T, r, q, is_call, table, payoff, barrier, n_paths, n_steps, seed, antithetic)
+
+    def _device_paths(self, S, T, r, q, table, n_paths, n_steps, seed):
+        return _hip.lv_paths(S, T, r, q, table, n_paths, n_steps, seed, path_major=True)
+
+    def _device_surface(self, S, T, r, q, is_call, table, strikes, steps, n_paths, n_steps, seed, antithetic):
+        return _hip.lv_surface_prices(S, T, r, q, is_call, table, strikes, steps, n_paths, n_steps, seed, antithetic)
+
     def _price_payoff(self, payoff, barrier, S, K, T, r, q, option_type, n_paths, n_steps, seed, antithetic, return_error):
         n_paths, n_steps, s = self._sizes(n_paths, n_steps, seed)
-        st = _hip.lv_price(S, K, T, r, q, option_type == "call", self.local_vol_table(S, T), payoff, barrier, n_paths, n_steps, s, antithetic)
+        st = self._device_price(S, K, T, r, q, option_type == "call", self.local_vol_table(S, T), payoff, barrier, n_paths, n_steps, s, antithetic)
         return (np.float64(st.price), float(st.std_error)) if return_error else np.float64(st.price)
 
     def price_monte_carlo(self, S: float, K: float, T: float, r: float, q: float = 0.0, option_type: Literal["call", "put"] = "call",
@@ -166,7 +177,7 @@ class DupireLocalVol:
                        seed: Optional[int] = None) -> np.ndarray:
         """The spot matrix (n_paths, n_steps + 1) of price_monte_carlo's recursion for the same seed; column 0 is S itself."""
         n_paths, n_steps, s = self._sizes(n_paths, n_steps, seed)
-        return _hip.lv_paths(S, T, r, q, self.local_vol_table(S, T), n_paths, n_steps, s, path_major=True)
+        return self._device_paths(S, T, r, q, self.local_vol_table(S, T), n_paths, n_steps, s)
 
     def price_asian(self, S: float, K: float, T: float, r: float, q: float = 0.0, option_type: Literal["call", "put"] = "call",
                     avg_type: Literal["arithmetic", "geometric"] = "arithmetic", n_paths: Optional[int] = None, n_steps: Optional[int] = None,
@@ -216,7 +227,7 @@ class DupireLocalVol:
         errors = np.empty_like(prices)
         for launch in _surface_launches(steps, len(ks)):
             cell_k, cell_m = [ks[i] for i, _j in launch], [steps[j] for _i, j in launch]
-            sts = _hip.lv_surface_prices(S, T, r, q, option_type == "call", table, cell_k, cell_m, n_paths, n_steps, s, antithetic)
+            sts = self._device_surface(S, T, r, q, option_type == "call", table, cell_k, cell_m, n_paths, n_steps, s, antithetic)
             for (i, j), st in zip(launch, sts):
                 prices[i, j], errors[i, j] = st.price, st.std_error
         return (prices, errors) if return_error else prices
@@ -228,6 +239,48 @@ class DupireLocalVol:
         self.r = r
         self.q = q
         return float(self.price_monte_carlo(S, K, T, r, q, option_type))
+
+    def qmc(self, path_construction: Literal["bridge", "sequential"] = "bridge") -> "DupireLocalVolQMC":
+        """This model on scrambled-Sobol points: a view that shares the calibrated surface and spline objects and takes r, q, n_paths,
+        n_steps and seed as they are now."""
+        view = DupireLocalVolQMC(self.r, self.q, n_paths=self.n_paths, n_steps=self.n_steps, seed=self.seed, path_construction=path_construction)
+        view._calibrated, view._spline = self._calibrated, self._spline
+        return view
+
+
+class DupireLocalVolQMC(DupireLocalVol):
+    """DupireLocalVol on scrambled-Sobol paths (include/olmc_local_vol_qmc.h): every pricing method, simulate_paths, price_surface and
+    price keep their signatures and meanings; n_paths counts Sobol points and path i is point i of scipy.stats.qmc.Sobol(d = n_steps,
+    scramble=True, seed), one dimension per step.  path_construction="bridge" (the default, at most 1024 steps) builds the Brownian
+    path by the breadth-first bridge and steps on its increments, "sequential" gives step t dimension t (at most 21201 steps).  The
+    refusals are exotic._qmc_tables', ValueErrors raised before the device is touched.  return_error's figure is the naive standard
+    error of the payoffs: for Sobol points it overstates the error.  With seed=None every call draws a scramble of its own; with a
+    fixed seed compute_greeks_unified(model.qmc(), ...) differentiates on the same points, one launch per bump."""
+
+    def __init__(self, r: float = 0.05, q: float = 0.0, *, n_paths: int = 1 << 14, n_steps: int = 252, seed: Optional[int] = None,
+                 path_construction: Literal["bridge", "sequential"] = "bridge"):
+        if path_construction not in ("bridge", "sequential"):
+            raise ValueError("path_construction must be 'bridge' or 'sequential'")
+        super().__init__(r, q, n_paths=n_paths, n_steps=n_steps, seed=seed)
+        self.path_construction = path_construction
+
+    def _sobol(self, n_paths, n_steps, seed):
+        """(sv, shift, bridge) of Sobol(d = n_steps, seed); sobol_tables caches them, so price_surface's launches share one pair."""
+        from .exotic import _qmc_tables
+
+        return _qmc_tables("qmc", self.path_construction, n_paths, n_steps, seed)
+
+    def _device_price(self, S, K, T, r, q, is_call, table, payoff, barrier, n_paths, n_steps, seed, antithetic):
+        sv, shift, bridge = self._sobol(n_paths, n_steps, seed)
+        return _hip.lvq_price(S, K, T, r, q, is_call, table, payoff, barrier, n_paths, sv, shift, bridge, antithetic)
+
+    def _device_paths(self, S, T, r, q, table, n_paths, n_steps, seed):
+        sv, shift, bridge = self._sobol(n_paths, n_steps, seed)
+        return _hip.lvq_paths(S, T, r, q, table, n_paths, sv, shift, bridge, path_major=True)
+
+    def _device_surface(self, S, T, r, q, is_call, table, strikes, steps, n_paths, n_steps, seed, antithetic):
+        sv, shift, bridge = self._sobol(n_paths, n_steps, seed)
+        return _hip.lvq_surface_prices(S, T, r, q, is_call, table, strikes, steps, n_paths, sv, shift, bridge, antithetic)
 
 
 def create_sample_iv_surface(spot: float = 100, n_strikes: int = 20, n_expiries: int = 5) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
