@@ -32,6 +32,7 @@
 #include <functional>
 #include <limits>
 #include <mutex>
+#include <optional>
 #include <string>
 #include <system_error>
 #include <thread>
@@ -1846,27 +1847,80 @@ extern "C" int olmc_jump_paths(double S, double T, double r, double sigma, doubl
 
 // ======================================================================= QMC ====
 namespace {
+// The Sobol arguments of an entry point as its caller passed them, unchecked: SobolCall::make is their only reader.  Braces refuse a
+// 64-bit count where a 32-bit one belongs.  The European family has no construction (it passes OLMC_QMC_SEQUENTIAL) and calls its
+// steps `dims`.
+struct SobolArgs {
+    int construction;
+    int64_t point_offset, n_points;
+    int32_t n_steps;
+    const uint32_t* sv;
+    const uint32_t* shift;
+    int32_t bits;
+    int antithetic;
+};
+
+// The Sobol points and tables of one call.  One exists only if make() passed it: every refusal of the construction, the tables and
+// the point range has been made, with the dimensions a step takes (1: the GBM and local-volatility paths and the European sums, 2:
+// Heston's two factors), before anything below an entry point -- the lease, the upload, a launch -- can ask for them.
+class SobolCall {
+public:
+    const bool bridge;
+    const int64_t first, count;              // points [first, first + count) of the one sequence
+    const int32_t n_steps, dims_per_step;
+    const uint32_t* const sv;
+    const uint32_t* const shift;
+    const int32_t bits;
+    const bool anti;
+
+    // The argument checks of a Sobol call, before any context is leased; *rc and olmc_last_error() say why there is no call.
+    static std::optional<SobolCall> make(const SobolArgs& a, int32_t dims_per_step, int* rc) {
+        *rc = check(a, dims_per_step);
+        if (*rc) return std::nullopt;
+        return SobolCall(a.construction == OLMC_QMC_BRIDGE, a.point_offset, a.n_points, a.n_steps, dims_per_step, a.sv, a.shift, a.bits, a.antithetic != 0);
+    }
+    // The same call over points [lo, lo + n) inside its own: a multi-GPU rank's share.
+    SobolCall over(int64_t lo, int64_t n) const { return SobolCall(bridge, lo, n, n_steps, dims_per_step, sv, shift, bits, anti); }
+
+    int32_t dims() const { return n_steps * dims_per_step; }                 // the table's; a plan and a QmcRange count steps
+    int64_t samples() const { return count * (anti ? 2 : 1); }
+    QmcRange range() const { return QmcRange{static_cast<uint64_t>(first), count, n_steps, anti ? 1 : 0}; }
+
+private:
+    SobolCall(bool bridge_, int64_t first_, int64_t count_, int32_t n_steps_, int32_t dims_per_step_, const uint32_t* sv_, const uint32_t* shift_,
+              int32_t bits_, bool anti_)
+        : bridge(bridge_), first(first_), count(count_), n_steps(n_steps_), dims_per_step(dims_per_step_), sv(sv_), shift(shift_), bits(bits_),
+          anti(anti_) {}
+
+    static int check(const SobolArgs& a, int32_t dims_per_step) {
+        if (a.construction != OLMC_QMC_SEQUENTIAL && a.construction != OLMC_QMC_BRIDGE) return fail(OLMC_ERR_ARG, "bad construction");
+        if (a.construction == OLMC_QMC_BRIDGE && a.n_steps > OLMC_QMC_BRIDGE_MAX_STEPS)
+            return fail(OLMC_ERR_ARG, "the Brownian-bridge construction takes at most OLMC_QMC_BRIDGE_MAX_STEPS (1024) dates");
+        static_assert(OLMC_QMC_BRIDGE_MAX_STEPS == kQmcBridgeMaxSteps, "the header's cap is the kernel's LDS size");
+        if (dims_per_step == 2 && (a.n_steps < 1 || a.n_steps > 10600))
+            return fail(OLMC_ERR_ARG, "n_steps must be in [1, 10600]: a step takes two of the 21201 Sobol dimensions");
+        const int32_t dims = a.n_steps * dims_per_step;
+        if (!a.sv || !a.shift) return fail(OLMC_ERR_ARG, "null pointer");
+        if (a.bits != kSobolBits) return fail(OLMC_ERR_ARG, "only 30-bit Sobol tables (SciPy's default) are supported");
+        if (dims < 1 || dims > 21201) return fail(OLMC_ERR_ARG, "dims must be in [1, 21201]");
+        const int rc = check_paths(a.point_offset, a.n_points, dims);
+        if (rc) return rc;
+        if (a.point_offset + a.n_points > (int64_t(1) << kSobolBits)) return fail(OLMC_ERR_ARG, "at most 2**30 Sobol points");
+        return OLMC_OK;
+    }
+};
+
 // The scrambled direction matrix and digital shift on the device: [dims x 30 | dims] words, uploaded on c's own stream -- the stream
 // every launch that reads them is queued on, so no launch sees a table half travelled or one another caller put there.  The table
 // travels only when it differs from the one already there (compared word for word: 31 KB at 252 dims, ~1 us, against two pageable
 // uploads): the 8 / 14 pricings of literal FD Greeks and every repeated pricing share one upload.  The caller owns c (a lease, or
 // a multi-GPU rank's own context).
-int qmc_table(DeviceCtx* c, const uint32_t* sv, const uint32_t* shift, int32_t dims, const uint32_t** d_sv, const uint32_t** d_shift) {
-    const size_t sv_words = static_cast<size_t>(dims) * kSobolBits;
-    const int rc = c->sobol.put(sv, sizeof(uint32_t) * sv_words, shift, sizeof(uint32_t) * dims, c->stream, [c] { return c->drain(); });
+int qmc_table(DeviceCtx* c, const SobolCall& q, const uint32_t** d_sv, const uint32_t** d_shift) {
+    const size_t sv_words = static_cast<size_t>(q.dims()) * kSobolBits;
+    const int rc = c->sobol.put(q.sv, sizeof(uint32_t) * sv_words, q.shift, sizeof(uint32_t) * q.dims(), c->stream, [c] { return c->drain(); });
     if (rc) return rc;
     *d_sv = c->sobol.device<uint32_t>();
     *d_shift = *d_sv + sv_words;
-    return OLMC_OK;
-}
-
-int qmc_check(const uint32_t* sv, const uint32_t* shift, int32_t bits, int32_t dims, int64_t point_offset, int64_t n_paths) {
-    if (!sv || !shift) return fail(OLMC_ERR_ARG, "null pointer");
-    if (bits != kSobolBits) return fail(OLMC_ERR_ARG, "only 30-bit Sobol tables (SciPy's default) are supported");
-    if (dims < 1 || dims > 21201) return fail(OLMC_ERR_ARG, "dims must be in [1, 21201]");
-    int rc = check_paths(point_offset, n_paths, dims);
-    if (rc) return rc;
-    if (point_offset + n_paths > (int64_t(1) << kSobolBits)) return fail(OLMC_ERR_ARG, "at most 2**30 Sobol points");
     return OLMC_OK;
 }
 
@@ -1880,13 +1934,13 @@ int qmc_check(const uint32_t* sv, const uint32_t* shift, int32_t bits, int32_t d
 // 158 / 171, 2^21 x 64: 310 / 293, 2^20 x 252: 530 / 638, 2^21 x 252: 1050 / 1107, 2^22 x 252: 2106 / 2074.  OLMC_TUNE_QMC_BLOCK:
 // 1 = always eight points per thread, 2 = always split, -1 = never eight and never split (one point per thread).
 // A split grid that one launch cannot hold falls back to one point per thread.  The arithmetic is olmc_host_math.h's qmc_launch_shape.
-QmcShape qmc_shape(int64_t point_offset, int64_t n_paths, int32_t dims) {
+QmcShape qmc_shape(const SobolCall& q) {
     // QmcShape::aligned: split workgroups whose 64 lanes are a 64-ALIGNED block of points fold the high Gray bits' direction numbers once per wave and
     // dimension and keep the inverse normal's coefficients in registers (olmc_kernels.h qmc_point_sum<true>).  The coefficients'
     // load and the fold's prologue are a fixed cost per wave: it pays from 32 dimensions on (8 per wave; 2^17 x 32: 21.5 -> 19.9 us,
     // 2^18 x 48: 44.6 -> 38.4, 2^14 x 32: even; 16 dimensions: 8.6 -> 8.9, 12.0 -> 12.3).  The one-point form is left to launches of
     // fewer than 16 dimensions and to the knob
-    return qmc_launch_shape(point_offset, n_paths, dims, g_qmc_block, g_grid_cap);
+    return qmc_launch_shape(q.first, q.count, q.dims(), g_qmc_block, g_grid_cap);
 }
 
 // The Sobol shape ladder of the European kernels (qmc_shape), MODE kReduce / kControlVariate / kTerminal.
@@ -1928,58 +1982,60 @@ Contract qmc_contract(double S, double K, double T, double r, double sigma, doub
     return ct;
 }
 
-// ONE reducing Sobol launch of contract ct over points [point_offset, point_offset + n_paths), queued on c's own stream behind the
-// table: {sum, sumsq} -- the five control-variate moments when `five` -- then `tail` at d_out (launch_reduce: blocks when d_out is
-// c->d_result).
-int qmc_device(DeviceCtx* c, const Contract& ct, int64_t point_offset, int64_t n_paths, int32_t dims, const uint32_t* sv,
-               const uint32_t* shift, bool five, double* d_out, double tail, bool profiled) {
+// ONE reducing Sobol launch of contract ct over the points of q, queued on c's own stream behind the table: {sum, sumsq} -- the five
+// control-variate moments when `five` -- then `tail` at d_out (launch_reduce: blocks when d_out is c->d_result).
+int qmc_device(DeviceCtx* c, const Contract& ct, const SobolCall& q, bool five, double* d_out, double tail, bool profiled) {
     const uint32_t *d_sv, *d_shift;
-    int rc = qmc_table(c, sv, shift, dims, &d_sv, &d_shift);
+    int rc = qmc_table(c, q, &d_sv, &d_shift);
     if (rc) return rc;
-    const QmcRange qr{static_cast<uint64_t>(point_offset), n_paths, dims, 0};
-    const QmcShape sh = qmc_shape(point_offset, n_paths, dims);
+    const QmcRange qr = q.range();
+    const QmcShape sh = qmc_shape(q);
     return launch_reduce(c, c->stream, d_out, tail, five ? 5 : 2, sh.grid, [&](int32_t grid, hipStream_t s, const EventPair* timed, const ReduceWs& ws) {
         if (five) launch_qmc_european<kControlVariate>(sh, grid, s, timed, qr, ct, d_sv, d_shift, ws, nullptr);
         else launch_qmc_european<kReduce>(sh, grid, s, timed, qr, ct, d_sv, d_shift, ws, nullptr);
     }, profiled);
 }
 
-int run_qmc(double S, double K, double T, double r, double sigma, double q, int is_call, int64_t point_offset,
-            int64_t n_paths, int32_t dims, const uint32_t* sv, const uint32_t* shift, int32_t bits,
-            olmc_stats* out, double* terminal_host, int mirror = 0, olmc_cv_moments* cv = nullptr) {
-    int rc = qmc_check(sv, shift, bits, dims, point_offset, n_paths);
-    if (rc) return rc;
+// One European call on the points of q (its antithetic flag: the terminal values' mirror half): stats at out, the control variate's
+// moments at cv, or the terminal values at terminal_host.
+int run_qmc(const olmc_option& o, const SobolCall& q, olmc_stats* out, double* terminal_host, olmc_cv_moments* cv = nullptr) {
     CtxLease lease;
-    rc = ctx_lease(&lease);
+    int rc = ctx_lease(&lease);
     if (rc) return rc;
     DeviceCtx* const c = lease.c;
-    const Contract ct = qmc_contract(S, K, T, r, sigma, q, is_call, dims, mirror != 0);
+    const Contract ct = qmc_contract(o.S, o.K, o.T, o.r, o.sigma, o.q, o.is_call, q.dims(), q.anti);
     if (!terminal_host) {
-        rc = qmc_device(c, ct, point_offset, n_paths, dims, sv, shift, cv != nullptr, c->d_result, -1.0, true);
+        rc = qmc_device(c, ct, q, cv != nullptr, c->d_result, -1.0, true);
         if (rc) return rc;
         if (cv) {       // device moments are of the UNdiscounted payoff x; d = disc * x (monte_carlo.py:175)
-            cv_from_device(c->h_result, n_paths, S, T, r, q, cv);
-            if (poisoned(S, K, T, r, sigma, q)) cv->value = std::nan("");
+            cv_from_device(c->h_result, q.count, o.S, o.T, o.r, o.q, cv);
+            if (poisoned(o.S, o.K, o.T, o.r, o.sigma, o.q)) cv->value = std::nan("");
             return OLMC_OK;
         }
-        finish_one(c->h_result, n_paths, r, T, poisoned(S, K, T, r, sigma, q), out);
+        finish_one(c->h_result, q.count, o.r, o.T, poisoned(o.S, o.K, o.T, o.r, o.sigma, o.q), out);
         return OLMC_OK;
     }
-    const size_t term_bytes = sizeof(double) * static_cast<size_t>(n_paths) * (mirror ? 2 : 1);
+    const size_t term_bytes = sizeof(double) * static_cast<size_t>(q.samples());
     Carver bulk;
     rc = bulk_reserve(c, term_bytes, &bulk);
     if (rc) return rc;
     const uint32_t *d_sv, *d_shift;
-    rc = qmc_table(c, sv, shift, dims, &d_sv, &d_shift);
+    rc = qmc_table(c, q, &d_sv, &d_shift);
     if (rc) return rc;
     double* d_term = bulk.take<double>(term_bytes / sizeof(double));
-    const QmcShape sh = qmc_shape(point_offset, n_paths, dims);
-    const QmcRange qr{static_cast<uint64_t>(point_offset), n_paths, dims, mirror ? 1 : 0};
+    const QmcShape sh = qmc_shape(q);
     // no reduction workspace is handed out: only the launch status matters
-    launch_qmc_european<kTerminal>(sh, sh.grid, c->stream, nullptr, qr, ct, d_sv, d_shift, ReduceWs{}, d_term);
+    launch_qmc_european<kTerminal>(sh, sh.grid, c->stream, nullptr, q.range(), ct, d_sv, d_shift, ReduceWs{}, d_term);
     HIP_TRY(hipGetLastError());
     c->armed = 0;
     return copy_to_host(c, terminal_host, d_term, term_bytes);
+}
+
+// The European family's Sobol call: no construction, `dims` one-dimension steps; then run_qmc.
+int run_qmc_checked(const olmc_option& o, const SobolArgs& a, olmc_stats* out, double* terminal_host, olmc_cv_moments* cv = nullptr) {
+    int rc;
+    const auto q = SobolCall::make(a, 1, &rc);
+    return q ? run_qmc(o, *q, out, terminal_host, cv) : rc;
 }
 }  // namespace
 
@@ -1987,21 +2043,24 @@ extern "C" int olmc_european_qmc_cv(double S, double K, double T, double r, doub
                                     int64_t point_offset, int64_t n_paths, int32_t dims, const uint32_t* sv,
                                     const uint32_t* shift, int32_t bits, olmc_cv_moments* out) {
     if (!out) return fail(OLMC_ERR_ARG, "null pointer");
-    return run_qmc(S, K, T, r, sigma, q, is_call, point_offset, n_paths, dims, sv, shift, bits, nullptr, nullptr, 0, out);
+    return run_qmc_checked(make_option(S, K, T, r, sigma, q, is_call), {OLMC_QMC_SEQUENTIAL, point_offset, n_paths, dims, sv, shift, bits, 0}, nullptr,
+                           nullptr, out);
 }
 
 extern "C" int olmc_european_qmc(double S, double K, double T, double r, double sigma, double q, int is_call,
                                  int64_t point_offset, int64_t n_paths, int32_t dims, const uint32_t* sv,
                                  const uint32_t* shift, int32_t bits, olmc_stats* out) {
     if (!out) return fail(OLMC_ERR_ARG, "null pointer");
-    return run_qmc(S, K, T, r, sigma, q, is_call, point_offset, n_paths, dims, sv, shift, bits, out, nullptr);
+    return run_qmc_checked(make_option(S, K, T, r, sigma, q, is_call), {OLMC_QMC_SEQUENTIAL, point_offset, n_paths, dims, sv, shift, bits, 0}, out,
+                           nullptr);
 }
 
 extern "C" int olmc_european_qmc_terminal(double S, double T, double r, double sigma, double q, int64_t point_offset,
                                           int64_t n_paths, int32_t dims, const uint32_t* sv, const uint32_t* shift,
                                           int32_t bits, int antithetic, double* out_host) {
     if (!out_host) return fail(OLMC_ERR_ARG, "null pointer");
-    return run_qmc(S, 0.0, T, r, sigma, q, 1, point_offset, n_paths, dims, sv, shift, bits, nullptr, out_host, antithetic);
+    return run_qmc_checked(make_option(S, 0.0, T, r, sigma, q, 1), {OLMC_QMC_SEQUENTIAL, point_offset, n_paths, dims, sv, shift, bits, antithetic},
+                           nullptr, out_host);
 }
 
 // ============================================================ QMC path payoffs ====
@@ -2038,42 +2097,6 @@ int qmc_bridge_plan(DeviceCtx* c, int32_t n, QmcBridgePlan* plan) {
     return OLMC_OK;
 }
 
-template <int FAMILY>
-void launch_qmc_path(bool bridge, bool anti, int32_t grid, hipStream_t s, const EventPair* timed, const QmcRange& qr, const ExtremaContract& ec,
-                     double inv_steps, const uint32_t* d_sv, const uint32_t* d_shift, const QmcBridgePlan& plan, const ReduceWs& ws) {
-    with_bool(bridge, [&](auto b) {
-        with_bool(anti, [&](auto a) { launch_timed(qmc_path_kernel<FAMILY, b, a>, dim3(grid), dim3(kBlock), s, timed, qr, ec, inv_steps, d_sv, d_shift, plan, ws); });
-    });
-}
-
-// The same for the fused Greeks kernel (8 or 16 contract slots).
-template <int FAMILY>
-void launch_qmc_path_greeks(bool bridge, bool anti, int nsets, int32_t grid, hipStream_t s, const EventPair* timed, const QmcRange& qr,
-                            const ExtremaGreeksSet& es, double inv_steps, const uint32_t* d_sv, const uint32_t* d_shift, const QmcBridgePlan& plan,
-                            const ReduceWs& ws) {
-    with_bool(bridge, [&](auto b) {
-        with_set_anti(nsets, anti, [&](auto width, auto a) {
-            launch_timed(qmc_path_greeks_kernel<FAMILY, b, a, width>, dim3(grid), dim3(kBlock), s, timed, qr, es, inv_steps, d_sv, d_shift, plan, ws);
-        });
-    });
-}
-
-// Workgroups of a QMC path launch: four points in flight per workgroup, grid-striding beyond kQmcPathMaxGrid (olmc_host_math.h:
-// qmc_point_grid) -- every kernel launched on QmcPathLaunch::grid strides, the fused path Greeks included.
-
-// The argument checks of a Sobol path call, before any context is leased.  A step takes dims_per_step dimensions of the table (1: the GBM
-// paths, 2: Heston's two factors).
-int qmc_path_check(int construction, int64_t point_offset, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift, int32_t bits,
-                   int32_t dims_per_step = 1) {
-    if (construction != OLMC_QMC_SEQUENTIAL && construction != OLMC_QMC_BRIDGE) return fail(OLMC_ERR_ARG, "bad construction");
-    if (construction == OLMC_QMC_BRIDGE && n_steps > OLMC_QMC_BRIDGE_MAX_STEPS)
-        return fail(OLMC_ERR_ARG, "the Brownian-bridge construction takes at most OLMC_QMC_BRIDGE_MAX_STEPS (1024) dates");
-    static_assert(OLMC_QMC_BRIDGE_MAX_STEPS == kQmcBridgeMaxSteps, "the header's cap is the kernel's LDS size");
-    if (dims_per_step == 2 && (n_steps < 1 || n_steps > 10600))
-        return fail(OLMC_ERR_ARG, "n_steps must be in [1, 10600]: a step takes two of the 21201 Sobol dimensions");
-    return qmc_check(sv, shift, bits, n_steps * dims_per_step, point_offset, n_points);
-}
-
 // A Sobol path launch on a context the caller holds: the tables (and the bridge plan) on its device, the points, the grid.
 struct QmcPathLaunch {
     const uint32_t* d_sv;
@@ -2083,108 +2106,112 @@ struct QmcPathLaunch {
     int32_t grid;
     bool bridge, anti;
     double inv_steps;
-    double* slabs = nullptr;     // heston_qmc_kernel's bridge slabs (heston_slabs)
+    double* slabs = nullptr;     // the bridge slabs of the Heston and local-volatility kernels (heston_slabs)
 };
-int qmc_path_setup(DeviceCtx* c, int construction, int64_t point_offset, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift,
-                   int antithetic, QmcPathLaunch* pl, int32_t dims_per_step = 1) {
-    const int32_t dims = n_steps * dims_per_step;                        // the table's; the plan and qr.dims count steps
-    int rc = qmc_table(c, sv, shift, dims, &pl->d_sv, &pl->d_shift);
+int qmc_path_setup(DeviceCtx* c, const SobolCall& q, QmcPathLaunch* pl) {
+    int rc = qmc_table(c, q, &pl->d_sv, &pl->d_shift);
     if (rc) return rc;
     pl->plan = QmcBridgePlan{nullptr, nullptr};
-    pl->bridge = construction == OLMC_QMC_BRIDGE;
+    pl->bridge = q.bridge;
     if (pl->bridge) {
-        rc = qmc_bridge_plan(c, n_steps, &pl->plan);
+        rc = qmc_bridge_plan(c, q.n_steps, &pl->plan);
         if (rc) return rc;
     }
-    pl->qr.first = static_cast<uint64_t>(point_offset);
-    pl->qr.count = n_points;
-    pl->qr.dims = n_steps;
-    pl->qr.mirror = antithetic ? 1 : 0;
-    pl->grid = qmc_point_grid(n_points, g_grid_cap);
-    pl->anti = antithetic != 0;
-    pl->inv_steps = 1.0 / n_steps;
+    pl->qr = q.range();
+    // Workgroups of a QMC path launch: four points in flight per workgroup, grid-striding beyond kQmcPathMaxGrid (olmc_host_math.h:
+    // qmc_point_grid) -- every kernel launched on QmcPathLaunch::grid strides, the fused path Greeks included.
+    pl->grid = qmc_point_grid(q.count, g_grid_cap);
+    pl->anti = q.anti;
+    pl->inv_steps = 1.0 / q.n_steps;
     return OLMC_OK;
 }
 
-// One Sobol path pricing once its arguments are checked: the lease, the tables (and the plan), launch(grid, stream, timed, pl, ws) -- the
-// payoff's kernel -- under the grid reduction, the statistics; r_for_discount as run_structured.  shape(c, &pl) may give the launch a
-// grid of its own and reserve what it needs on the context.
-template <typename Launch, typename Shape>
-int run_qmc_payoff(int construction, int64_t point_offset, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift,
-                   int antithetic, double r_for_discount, double T, bool poisoned_inputs, olmc_stats* out, Launch launch, int32_t dims_per_step,
-                   Shape shape) {
+// f(bool_constant<bridge>, bool_constant<anti>) for a launch's construction and antithetic flag.
+template <typename F>
+void with_bridge_anti(const QmcPathLaunch& pl, F&& f) {
+    with_bool(pl.bridge, [&](auto b) { with_bool(pl.anti, [&](auto a) { f(b, a); }); });
+}
+
+// f(integral_constant<int, family>) for kQmcAsianArithmetic, kQmcAsianGeometric or (anything else) kQmcExtrema.
+template <typename F>
+void with_qmc_path_family(int family, F&& f) {
+    if (family == kQmcAsianArithmetic) f(std::integral_constant<int, kQmcAsianArithmetic>{});
+    else if (family == kQmcAsianGeometric) f(std::integral_constant<int, kQmcAsianGeometric>{});
+    else f(std::integral_constant<int, kQmcExtrema>{});
+}
+
+// One reducing Sobol path launch of a checked call: the lease, the tables (and the plan), shape(c, q, &pl) -- which may give the launch a
+// grid of its own and reserve what it needs on the context --, launch(grid, stream, timed, pl, ws) under the grid reduction with rows
+// of nv values, then finish(sums, samples) on the host's copy of the row.
+template <typename Shape, typename Launch, typename Finish>
+int run_qmc_reduce(const SobolCall& q, int nv, Shape shape, Launch launch, Finish finish) {
     CtxLease lease;
     int rc = ctx_lease(&lease);
     if (rc) return rc;
     DeviceCtx* const c = lease.c;
     QmcPathLaunch pl;
-    rc = qmc_path_setup(c, construction, point_offset, n_points, n_steps, sv, shift, antithetic, &pl, dims_per_step);
+    rc = qmc_path_setup(c, q, &pl);
     if (rc) return rc;
-    rc = shape(c, &pl);
+    rc = shape(c, q, &pl);
     if (rc) return rc;
-    rc = launch_reduce(c, c->stream, c->d_result, -1.0, 2, pl.grid,
+    rc = launch_reduce(c, c->stream, c->d_result, -1.0, nv, pl.grid,
                        [&](int32_t g, hipStream_t s, const EventPair* timed, const ReduceWs& ws) { launch(g, s, timed, pl, ws); });
     if (rc) return rc;
-    finish_one(c->h_result, n_points * (pl.anti ? 2 : 1), r_for_discount, T, poisoned_inputs, out);
+    finish(c->h_result, q.samples());
     return OLMC_OK;
 }
-template <typename Launch>
-int run_qmc_payoff(int construction, int64_t point_offset, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift,
-                   int antithetic, double r_for_discount, double T, bool poisoned_inputs, olmc_stats* out, Launch launch) {
-    return run_qmc_payoff(construction, point_offset, n_points, n_steps, sv, shift, antithetic, r_for_discount, T, poisoned_inputs, out, launch, 1,
-                          [](DeviceCtx*, QmcPathLaunch*) { return OLMC_OK; });
+// The shape of the GBM path kernels: qmc_path_setup's grid, nothing reserved.
+inline int qmc_point_shape(DeviceCtx*, const SobolCall&, QmcPathLaunch*) { return OLMC_OK; }
+// The finish of one pricing: the statistics of {sum, sumsq}; r_for_discount as run_structured.
+auto qmc_stats(double r_for_discount, double T, bool poisoned_inputs, olmc_stats* out) {
+    return [=](const double* h, int64_t n) { finish_one(h, n, r_for_discount, T, poisoned_inputs, out); };
 }
 
 // family: kQmcAsianArithmetic / kQmcAsianGeometric (payoff ignored) or kQmcExtrema (payoff = kBarrier* / kLookback*, `barrier` its level).
-int run_qmc_path(int family, int payoff, double S, double K, double T, double r, double sigma, double q, int is_call, double barrier,
-                 int construction, int64_t point_offset, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift,
-                 int32_t bits, int antithetic, olmc_stats* out) {
+int run_qmc_path(int family, int payoff, const olmc_option& o, double barrier, const SobolArgs& args, olmc_stats* out) {
     if (!out) return fail(OLMC_ERR_ARG, "null pointer");
-    const int rc = qmc_path_check(construction, point_offset, n_points, n_steps, sv, shift, bits);
-    if (rc) return rc;
-    const ExtremaContract ec = make_extrema(S, K, T, r, sigma, q, is_call, family == kQmcExtrema ? payoff : 0, barrier, n_steps);
-    const bool bad = poisoned(S, K, T, r, sigma, q) || std::isnan(barrier);
-    return run_qmc_payoff(construction, point_offset, n_points, n_steps, sv, shift, antithetic, r, T, bad, out,
-                          [&](int32_t g, hipStream_t s, const EventPair* timed, const QmcPathLaunch& pl, const ReduceWs& ws) {
-        if (family == kQmcAsianArithmetic) launch_qmc_path<kQmcAsianArithmetic>(pl.bridge, pl.anti, g, s, timed, pl.qr, ec, pl.inv_steps, pl.d_sv, pl.d_shift, pl.plan, ws);
-        else if (family == kQmcAsianGeometric) launch_qmc_path<kQmcAsianGeometric>(pl.bridge, pl.anti, g, s, timed, pl.qr, ec, pl.inv_steps, pl.d_sv, pl.d_shift, pl.plan, ws);
-        else launch_qmc_path<kQmcExtrema>(pl.bridge, pl.anti, g, s, timed, pl.qr, ec, pl.inv_steps, pl.d_sv, pl.d_shift, pl.plan, ws);
-    });
+    int rc;
+    const auto q = SobolCall::make(args, 1, &rc);
+    if (!q) return rc;
+    const ExtremaContract ec = make_extrema(o.S, o.K, o.T, o.r, o.sigma, o.q, o.is_call, family == kQmcExtrema ? payoff : 0, barrier, q->n_steps);
+    const bool bad = poisoned(o.S, o.K, o.T, o.r, o.sigma, o.q) || std::isnan(barrier);
+    return run_qmc_reduce(*q, 2, qmc_point_shape, [&](int32_t g, hipStream_t s, const EventPair* timed, const QmcPathLaunch& pl, const ReduceWs& ws) {
+        with_qmc_path_family(family, [&](auto f) {
+            with_bridge_anti(pl, [&](auto b, auto a) {
+                launch_timed(qmc_path_kernel<f, b, a>, dim3(g), dim3(kBlock), s, timed, pl.qr, ec, pl.inv_steps, pl.d_sv, pl.d_shift, pl.plan, ws);
+            });
+        });
+    }, qmc_stats(o.r, o.T, bad, out));
 }
 
 // The 8 / 14 contracts of compute_greeks_unified over a Sobol-path option (ExoticAdapter, method="qmc") on points [0, n_points), ONE
 // launch of qmc_path_greeks_kernel.  Every family is grouped by extrema_greeks_layout in the Sobol normal's unit (1); the Asian
 // families have no level (payoff 0, barrier 0: log_barrier_rel 0, unread).
-int run_qmc_path_greeks(int family, int payoff, double S, double K, double T, double r, double sigma, double q, int is_call, double barrier,
-                        int construction, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift, int32_t bits,
-                        int antithetic, int second_order, double* out9, olmc_stats* evals) {
+int run_qmc_path_greeks(int family, int payoff, const olmc_option& o, double barrier, const SobolArgs& args, int second_order, double* out9,
+                        olmc_stats* evals) {
     if (!out9) return fail(OLMC_ERR_ARG, "null pointer");
-    if (!(T > 0.0)) return fail(OLMC_ERR_ARG, "T must be > 0");
-    int rc = qmc_path_check(construction, 0, n_points, n_steps, sv, shift, bits);
-    if (rc) return rc;
-    const GreeksSet gs(S, K, T, r, sigma, q, is_call, second_order);
+    if (!(o.T > 0.0)) return fail(OLMC_ERR_ARG, "T must be > 0");
+    int rc;
+    const auto q = SobolCall::make(args, 1, &rc);
+    if (!q) return rc;
+    const GreeksSet gs(o.S, o.K, o.T, o.r, o.sigma, o.q, o.is_call, second_order);
     ExtremaGreeksSet es;
-    if (const char* bad = extrema_greeks_layout(gs, n_steps, payoff, barrier, K, is_call, &es, 1.0)) return fail(OLMC_ERR_STATE, bad);
-    CtxLease lease;
-    rc = ctx_lease(&lease);
-    if (rc) return rc;
-    DeviceCtx* const c = lease.c;
-    QmcPathLaunch pl;
-    rc = qmc_path_setup(c, construction, 0, n_points, n_steps, sv, shift, antithetic, &pl);
-    if (rc) return rc;
+    if (const char* bad = extrema_greeks_layout(gs, q->n_steps, payoff, barrier, o.K, o.is_call, &es, 1.0)) return fail(OLMC_ERR_STATE, bad);
     const int nsets = gs.nsets();
-    rc = launch_reduce(c, c->stream, c->d_result, -1.0, 2 * nsets, pl.grid, [&](int32_t g, hipStream_t s, const EventPair* timed, const ReduceWs& ws) {
-        if (family == kQmcAsianArithmetic)
-            launch_qmc_path_greeks<kQmcAsianArithmetic>(pl.bridge, pl.anti, nsets, g, s, timed, pl.qr, es, pl.inv_steps, pl.d_sv, pl.d_shift, pl.plan, ws);
-        else if (family == kQmcAsianGeometric)
-            launch_qmc_path_greeks<kQmcAsianGeometric>(pl.bridge, pl.anti, nsets, g, s, timed, pl.qr, es, pl.inv_steps, pl.d_sv, pl.d_shift, pl.plan, ws);
-        else launch_qmc_path_greeks<kQmcExtrema>(pl.bridge, pl.anti, nsets, g, s, timed, pl.qr, es, pl.inv_steps, pl.d_sv, pl.d_shift, pl.plan, ws);
+    return run_qmc_reduce(*q, 2 * nsets, qmc_point_shape, [&](int32_t g, hipStream_t s, const EventPair* timed, const QmcPathLaunch& pl, const ReduceWs& ws) {
+        with_qmc_path_family(family, [&](auto f) {
+            with_bool(pl.bridge, [&](auto b) {
+                with_set_anti(nsets, pl.anti, [&](auto width, auto a) {
+                    launch_timed(qmc_path_greeks_kernel<f, b, a, width>, dim3(g), dim3(kBlock), s, timed, pl.qr, es, pl.inv_steps, pl.d_sv, pl.d_shift,
+                                 pl.plan, ws);
+                });
+            });
+        });
+    }, [&](const double* h, int64_t n) {
+        olmc_stats st[OLMC_MAX_BATCH];
+        finish_set(h, nullptr, n, gs.o, gs.k, false, false, st);
+        gs.finish(st, o.T, out9, evals);
     });
-    if (rc) return rc;
-    olmc_stats st[OLMC_MAX_BATCH];
-    finish_set(c->h_result, nullptr, n_points * (pl.anti ? 2 : 1), gs.o, gs.k, false, false, st);
-    gs.finish(st, T, out9, evals);
-    return OLMC_OK;
 }
 }  // namespace
 
@@ -2192,8 +2219,8 @@ extern "C" int olmc_asian_qmc(double S, double K, double T, double r, double sig
                               int64_t point_offset, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift, int32_t bits,
                               int antithetic, olmc_stats* out) {
     if (avg_kind != OLMC_AVG_ARITHMETIC && avg_kind != OLMC_AVG_GEOMETRIC) return fail(OLMC_ERR_ARG, "bad avg_kind (arithmetic or geometric)");
-    return run_qmc_path(avg_kind == OLMC_AVG_GEOMETRIC ? kQmcAsianGeometric : kQmcAsianArithmetic, 0, S, K, T, r, sigma, q, is_call, 0.0,
-                        construction, point_offset, n_points, n_steps, sv, shift, bits, antithetic, out);
+    return run_qmc_path(avg_kind == OLMC_AVG_GEOMETRIC ? kQmcAsianGeometric : kQmcAsianArithmetic, 0, make_option(S, K, T, r, sigma, q, is_call), 0.0,
+                        {construction, point_offset, n_points, n_steps, sv, shift, bits, antithetic}, out);
 }
 
 extern "C" int olmc_extrema_qmc(double S, double K, double T, double r, double sigma, double q, int is_call, int payoff, double barrier,
@@ -2201,8 +2228,8 @@ extern "C" int olmc_extrema_qmc(double S, double K, double T, double r, double s
                                 const uint32_t* shift, int32_t bits, int antithetic, olmc_stats* out) {
     if (payoff < OLMC_BARRIER_UP_OUT || payoff > OLMC_LOOKBACK_FIXED) return fail(OLMC_ERR_ARG, "bad payoff");
     if (payoff <= OLMC_BARRIER_DOWN_IN && !(barrier > 0.0)) return fail(OLMC_ERR_ARG, "Barrier must be positive");
-    return run_qmc_path(kQmcExtrema, payoff, S, K, T, r, sigma, q, is_call, payoff <= OLMC_BARRIER_DOWN_IN ? barrier : 0.0, construction,
-                        point_offset, n_points, n_steps, sv, shift, bits, antithetic, out);
+    return run_qmc_path(kQmcExtrema, payoff, make_option(S, K, T, r, sigma, q, is_call), payoff <= OLMC_BARRIER_DOWN_IN ? barrier : 0.0,
+                        {construction, point_offset, n_points, n_steps, sv, shift, bits, antithetic}, out);
 }
 
 extern "C" int olmc_asian_qmc_greeks_fd(double S, double K, double T, double r, double sigma, double q, int is_call, int avg_kind,
@@ -2210,8 +2237,8 @@ extern "C" int olmc_asian_qmc_greeks_fd(double S, double K, double T, double r, 
                                         int32_t bits, int antithetic, int second_order, double* out9, olmc_stats* evals) {
     if (avg_kind != OLMC_AVG_ARITHMETIC && avg_kind != OLMC_AVG_GEOMETRIC)
         return fail(OLMC_ERR_ARG, "bad avg_kind (arithmetic or geometric: the fp32-exponent form has no Sobol path)");
-    return run_qmc_path_greeks(avg_kind == OLMC_AVG_GEOMETRIC ? kQmcAsianGeometric : kQmcAsianArithmetic, 0, S, K, T, r, sigma, q, is_call, 0.0,
-                               construction, n_points, n_steps, sv, shift, bits, antithetic, second_order, out9, evals);
+    return run_qmc_path_greeks(avg_kind == OLMC_AVG_GEOMETRIC ? kQmcAsianGeometric : kQmcAsianArithmetic, 0, make_option(S, K, T, r, sigma, q, is_call),
+                               0.0, {construction, 0, n_points, n_steps, sv, shift, bits, antithetic}, second_order, out9, evals);
 }
 
 extern "C" int olmc_extrema_qmc_greeks_fd(double S, double K, double T, double r, double sigma, double q, int is_call, int payoff, double barrier,
@@ -2219,8 +2246,8 @@ extern "C" int olmc_extrema_qmc_greeks_fd(double S, double K, double T, double r
                                           int32_t bits, int antithetic, int second_order, double* out9, olmc_stats* evals) {
     if (payoff < OLMC_BARRIER_UP_OUT || payoff > OLMC_LOOKBACK_FIXED) return fail(OLMC_ERR_ARG, "bad payoff");
     if (payoff <= OLMC_BARRIER_DOWN_IN && !(barrier > 0.0)) return fail(OLMC_ERR_ARG, "Barrier must be positive");
-    return run_qmc_path_greeks(kQmcExtrema, payoff, S, K, T, r, sigma, q, is_call, payoff <= OLMC_BARRIER_DOWN_IN ? barrier : 0.0, construction,
-                               n_points, n_steps, sv, shift, bits, antithetic, second_order, out9, evals);
+    return run_qmc_path_greeks(kQmcExtrema, payoff, make_option(S, K, T, r, sigma, q, is_call), payoff <= OLMC_BARRIER_DOWN_IN ? barrier : 0.0,
+                               {construction, 0, n_points, n_steps, sv, shift, bits, antithetic}, second_order, out9, evals);
 }
 
 // The autocallable and the cliquet on the Sobol paths of run_qmc_path (include/olmc.h "quasi-Monte Carlo structured products"): the
@@ -2235,69 +2262,67 @@ extern "C" int olmc_autocallable_qmc(double S, double T, double r, double sigma,
                                      int64_t point_offset, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift,
                                      int32_t bits, int antithetic, olmc_stats* out) {
     if (!out) return fail(OLMC_ERR_ARG, "null pointer");
-    int rc = qmc_path_check(construction, point_offset, n_points, n_steps, sv, shift, bits);
-    if (rc) return rc;
+    int rc;
+    const auto call = SobolCall::make({construction, point_offset, n_points, n_steps, sv, shift, bits, antithetic}, 1, &rc);
+    if (!call) return rc;
     rc = autocall_check(observation_freq, n_steps);
     if (rc) return rc;
     const AutocallSetup a = make_autocall(S, T, r, sigma, q, autocall_barrier, coupon_barrier, coupon_rate, ki_barrier, observation_freq, n_steps);
     const uint32_t magic = qmc_date_magic(observation_freq);
     // payoffs are already discounted path by path, as olmc_autocallable's: no outer discount
-    return run_qmc_payoff(construction, point_offset, n_points, n_steps, sv, shift, antithetic, 0.0, T, a.bad, out,
-                          [&](int32_t g, hipStream_t s, const EventPair* timed, const QmcPathLaunch& pl, const ReduceWs& ws) {
-                              with_bool(pl.bridge, [&](auto b) {
-                                  with_bool(pl.anti, [&](auto m) {
-                                      launch_timed(qmc_autocall_kernel<b, m>, dim3(g), dim3(kBlock), s, timed, pl.qr, a.ac, a.obs_rate, magic, pl.d_sv,
-                                                   pl.d_shift, pl.plan, ws);
-                                  });
-                              });
-                          });
+    return run_qmc_reduce(*call, 2, qmc_point_shape, [&](int32_t g, hipStream_t s, const EventPair* timed, const QmcPathLaunch& pl, const ReduceWs& ws) {
+        with_bridge_anti(pl, [&](auto b, auto m) {
+            launch_timed(qmc_autocall_kernel<b, m>, dim3(g), dim3(kBlock), s, timed, pl.qr, a.ac, a.obs_rate, magic, pl.d_sv, pl.d_shift, pl.plan, ws);
+        });
+    }, qmc_stats(0.0, T, a.bad, out));
 }
 
 extern "C" int olmc_cliquet_qmc(double S, double T, double r, double sigma, double q, double local_cap, double local_floor, double global_cap,
                                 double global_floor, int32_t n_periods, int construction, int64_t point_offset, int64_t n_points,
                                 int32_t n_steps, const uint32_t* sv, const uint32_t* shift, int32_t bits, int antithetic, olmc_stats* out) {
     if (!out) return fail(OLMC_ERR_ARG, "null pointer");
-    int rc = qmc_path_check(construction, point_offset, n_points, n_steps, sv, shift, bits);
-    if (rc) return rc;
+    int rc;
+    const auto call = SobolCall::make({construction, point_offset, n_points, n_steps, sv, shift, bits, antithetic}, 1, &rc);
+    if (!call) return rc;
     rc = cliquet_check(n_periods, n_steps);
     if (rc) return rc;
     const CliquetContract cc = make_cliquet(S, T, r, sigma, q, local_cap, local_floor, global_cap, global_floor, n_periods, n_steps);
     const uint32_t magic = qmc_date_magic(cc.steps_per_period);
     const bool bad = cliquet_poisoned(S, T, r, sigma, q, local_cap, local_floor, global_cap, global_floor);
-    return run_qmc_payoff(construction, point_offset, n_points, n_steps, sv, shift, antithetic, r, T, bad, out,
-                          [&](int32_t g, hipStream_t s, const EventPair* timed, const QmcPathLaunch& pl, const ReduceWs& ws) {
-                              with_bool(pl.bridge, [&](auto b) {
-                                  with_bool(pl.anti, [&](auto m) {
-                                      launch_timed(qmc_cliquet_kernel<b, m>, dim3(g), dim3(kBlock), s, timed, pl.qr, cc, magic, pl.d_sv, pl.d_shift,
-                                                   pl.plan, ws);
-                                  });
-                              });
-                          });
+    return run_qmc_reduce(*call, 2, qmc_point_shape, [&](int32_t g, hipStream_t s, const EventPair* timed, const QmcPathLaunch& pl, const ReduceWs& ws) {
+        with_bridge_anti(pl, [&](auto b, auto m) {
+            launch_timed(qmc_cliquet_kernel<b, m>, dim3(g), dim3(kBlock), s, timed, pl.qr, cc, magic, pl.d_sv, pl.d_shift, pl.plan, ws);
+        });
+    }, qmc_stats(r, T, bad, out));
 }
 
 // ================================================================ QMC path matrix ====
 namespace {
-// The argument checks and the lease of a Sobol path-matrix call: qmc_path_check, then matrix_prologue with the call's `bytes` (reserved
-// when `reserve`) -- every refusal before any device work.
-int qmc_matrix_prologue(int construction, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift, int32_t bits,
-                        double bytes, CtxLease* lease, bool reserve = true, int32_t dims_per_step = 1) {
-    const int rc = qmc_path_check(construction, 0, n_points, n_steps, sv, shift, bits, dims_per_step);
-    return rc ? rc : matrix_prologue(n_points, n_steps, bytes, "path matrix would exceed 64 GB: lower n_paths or n_steps", lease, reserve);
+// The lease of a Sobol path-matrix call, after its Sobol checks: matrix_prologue with the call's `bytes` (reserved when `reserve`) --
+// every refusal before any device work.
+int qmc_matrix_prologue(const SobolCall& q, double bytes, CtxLease* lease, bool reserve = true) {
+    return matrix_prologue(q.count, q.n_steps, bytes, "path matrix would exceed 64 GB: lower n_paths or n_steps", lease, reserve);
 }
 
-// Workgroups of a lanes-over-points launch: one wave per aligned block of 64 points, grid-striding beyond kQmcPathMaxGrid.
-int32_t qmc_block_grid(int64_t blocks) { return qmc_blocks_grid(blocks, g_grid_cap); }
+// Workgroups of a lanes-over-points launch: one wave per block of 64 points that the call touches, aligned in the absolute point
+// index, grid-striding beyond kQmcPathMaxGrid.
+int32_t qmc_block_grid(const SobolCall& q) { return qmc_blocks_grid((q.first + q.count - 1) / kWave - q.first / kWave + 1, g_grid_cap); }
 
-// Sobol points [0, n_points) as the path matrix d_paths (lsm_qmc_paths_kernel), queued on c's stream behind the tables and the plan.
-int qmc_matrix(DeviceCtx* c, int construction, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift, const LsmContract& lc,
-               bool path_major, double* d_paths) {
+// The set-up of a path-matrix launch: the tables, the plan and the range of qmc_path_setup, the grid over the blocks of 64 points.
+int qmc_matrix_setup(DeviceCtx* c, const SobolCall& q, QmcPathLaunch* pl) {
+    const int rc = qmc_path_setup(c, q, pl);
+    pl->grid = qmc_block_grid(q);
+    return rc;
+}
+
+// The points of q as the path matrix d_paths (lsm_qmc_paths_kernel), queued on c's stream behind the tables and the plan.
+int qmc_matrix(DeviceCtx* c, const SobolCall& q, const LsmContract& lc, bool path_major, double* d_paths) {
     QmcPathLaunch pl;
-    const int rc = qmc_path_setup(c, construction, 0, n_points, n_steps, sv, shift, 0, &pl);
+    const int rc = qmc_matrix_setup(c, q, &pl);
     if (rc) return rc;
-    const int32_t grid = qmc_block_grid((n_points + kWave - 1) / kWave);
     with_bool(pl.bridge, [&](auto b) {
         with_bool(path_major, [&](auto pm) {
-            launch_timed(lsm_qmc_paths_kernel<b, pm>, dim3(grid), dim3(kBlock), c->stream, nullptr, pl.qr, lc, pl.d_sv, pl.d_shift, pl.plan, d_paths);
+            launch_timed(lsm_qmc_paths_kernel<b, pm>, dim3(pl.grid), dim3(kBlock), c->stream, nullptr, pl.qr, lc, pl.d_sv, pl.d_shift, pl.plan, d_paths);
         });
     });
     HIP_TRY(hipGetLastError());
@@ -2310,8 +2335,11 @@ extern "C" int olmc_american_lsm_qmc(double S, double K, double T, double r, dou
                                      int32_t poly_degree, olmc_stats* out) {
     if (!out) return fail(OLMC_ERR_ARG, "null pointer");
     if (poly_degree < 1 || poly_degree > kLsmMaxDegree) return fail(OLMC_ERR_ARG, "poly_degree must be in [1, 4]");
+    int rc;
+    const auto call = SobolCall::make({construction, 0, n_points, n_steps, sv, shift, bits, 0}, 1, &rc);
+    if (!call) return rc;
     CtxLease lease;
-    int rc = qmc_matrix_prologue(construction, n_points, n_steps, sv, shift, bits, lsm_bytes(n_points, n_steps), &lease);
+    rc = qmc_matrix_prologue(*call, lsm_bytes(n_points, n_steps), &lease);
     if (rc) return rc;
     DeviceCtx* const c = lease.c;
     Carver bulk = c->bulk.carve();
@@ -2319,7 +2347,7 @@ extern "C" int olmc_american_lsm_qmc(double S, double K, double T, double r, dou
     const LsmContract lc = lsm_contract(S, K, T, r, sigma, q, is_call, n_steps, poly_degree);
     EventPair ep{};
     if (g_profile) { rc = prof_begin(c, c->stream, &ep); if (rc) return rc; }
-    rc = qmc_matrix(c, construction, n_points, n_steps, sv, shift, lc, false, d_paths);
+    rc = qmc_matrix(c, *call, lc, false, d_paths);
     if (rc) return rc;
     rc = lsm_chain(c, S, K, T, r, sigma, q, is_call, lc, n_points, n_steps, d_paths, &bulk);
     if (rc) return rc;
@@ -2334,8 +2362,11 @@ extern "C" int olmc_exercise_boundary_qmc(double S, double K, double T, double r
     if (!boundary_host) return fail(OLMC_ERR_ARG, "null pointer");
     const size_t rows = static_cast<size_t>(n_steps) + 1;
     const double bytes = 8.0 * static_cast<double>(n_points) * (n_steps + 1.0);
+    int rc;
+    const auto call = SobolCall::make({construction, 0, n_points, n_steps, sv, shift, bits, 0}, 1, &rc);
+    if (!call) return rc;
     CtxLease lease;
-    int rc = qmc_matrix_prologue(construction, n_points, n_steps, sv, shift, bits, bytes, &lease, false);
+    rc = qmc_matrix_prologue(*call, bytes, &lease, false);
     if (rc) return rc;
     DeviceCtx* const c = lease.c;
     const size_t path_bytes = (static_cast<size_t>(bytes) + 255) / 256 * 256;
@@ -2344,7 +2375,7 @@ extern "C" int olmc_exercise_boundary_qmc(double S, double K, double T, double r
     if (rc) return rc;
     double* d_paths = bulk.take<double>(path_bytes / sizeof(double));
     double* d_boundary = bulk.take<double>(rows);
-    rc = qmc_matrix(c, construction, n_points, n_steps, sv, shift, lsm_contract(S, K, T, r, sigma, q, is_call, n_steps, 1), false, d_paths);
+    rc = qmc_matrix(c, *call, lsm_contract(S, K, T, r, sigma, q, is_call, n_steps, 1), false, d_paths);
     if (rc) return rc;
     // as olmc_exercise_boundary: np.percentile(x, 10) for a put, 90 for a call (exotic_options.py:337-341)
     hipLaunchKernelGGL(exercise_boundary_kernel, dim3(static_cast<uint32_t>(rows)), dim3(kBoundaryThreads), 0, c->stream, d_paths, n_points, K,
@@ -2359,13 +2390,16 @@ extern "C" int olmc_gbm_qmc_paths(double S, double T, double r, double sigma, do
                                   const uint32_t* sv, const uint32_t* shift, int32_t bits, int path_major, double* out_host) {
     if (!out_host) return fail(OLMC_ERR_ARG, "null pointer");
     const double bytes = 8.0 * static_cast<double>(n_points) * (n_steps + 1.0);
+    int rc;
+    const auto call = SobolCall::make({construction, 0, n_points, n_steps, sv, shift, bits, 0}, 1, &rc);
+    if (!call) return rc;
     CtxLease lease;
-    int rc = qmc_matrix_prologue(construction, n_points, n_steps, sv, shift, bits, bytes, &lease);
+    rc = qmc_matrix_prologue(*call, bytes, &lease);
     if (rc) return rc;
     DeviceCtx* const c = lease.c;
     LsmContract lc = lsm_contract(S, S, T, r, sigma, q, 0, n_steps, 1);            // no strike: only the path fields are read
     lc.s_first = S;                                                     // the export's column 0 is S itself, as olmc_gbm_paths'
-    rc = qmc_matrix(c, construction, n_points, n_steps, sv, shift, lc, path_major != 0, c->bulk.as<double>());
+    rc = qmc_matrix(c, *call, lc, path_major != 0, c->bulk.as<double>());
     if (rc) return rc;
     return copy_to_host(c, out_host, c->bulk.get(), static_cast<size_t>(bytes));
 }
@@ -2386,46 +2420,44 @@ int heston_slabs(DeviceCtx* c, int32_t n_steps, int32_t* grid, int32_t factors =
     return c->heston_w.reserve(hs.bytes, [c] { return c->drain(); });      // a launch may still walk the old slabs
 }
 
-// run_qmc_payoff's shape of a Heston price launch (heston_qmc_kernel, heston_qmc_path_kernel): the grid over the blocks of 64 points,
+// run_qmc_reduce's shape of a Heston price launch (heston_qmc_kernel, heston_qmc_path_kernel): the grid over the blocks of 64 points,
 // aligned in the absolute point index, and for the bridge its slabs.
-auto heston_qmc_shape(int64_t point_offset, int64_t n_points, int32_t n_steps) {
-    return [=](DeviceCtx* c, QmcPathLaunch* pl) {
-        const int64_t first_block = point_offset / kWave, last_block = (point_offset + n_points - 1) / kWave;
-        pl->grid = qmc_block_grid(last_block - first_block + 1);
-        pl->slabs = nullptr;
-        if (!pl->bridge) return static_cast<int>(OLMC_OK);
-        const int rc2 = heston_slabs(c, n_steps, &pl->grid);
-        pl->slabs = c->heston_w.as<double>();
-        return rc2;
-    };
+int heston_qmc_shape(DeviceCtx* c, const SobolCall& q, QmcPathLaunch* pl) {
+    pl->grid = qmc_block_grid(q);
+    pl->slabs = nullptr;
+    if (!pl->bridge) return OLMC_OK;
+    const int rc = heston_slabs(c, q.n_steps, &pl->grid, q.dims_per_step);
+    pl->slabs = c->heston_w.as<double>();
+    return rc;
 }
 
 // Sobol: every (S, v) state of points [0, n_points) of the scheme's construction.
 template <typename Scheme>
-int run_heston_qmc_paths(double S, double T, double r, double q, const HestonModel& m, int construction, int64_t n_points, int32_t n_steps,
-                         const uint32_t* sv, const uint32_t* shift, int32_t bits, int path_major, double* spot_host, double* var_host) {
+int run_heston_qmc_paths(double S, double T, double r, double q, const HestonModel& m, const SobolArgs& args, int path_major, double* spot_host,
+                         double* var_host) {
     if (!spot_host || !var_host) return fail(OLMC_ERR_ARG, "null pointer");
-    int rc = heston_qmc_scheme_check<Scheme>(m, construction);
+    int rc = heston_qmc_scheme_check<Scheme>(m, args.construction);
     if (rc) return rc;
-    const double bytes = 8.0 * static_cast<double>(n_points) * (n_steps + 1.0);
+    const auto call = SobolCall::make(args, 2, &rc);
+    if (!call) return rc;
+    const double bytes = 8.0 * static_cast<double>(call->count) * (call->n_steps + 1.0);
     CtxLease lease;
-    rc = qmc_matrix_prologue(construction, n_points, n_steps, sv, shift, bits, 2 * bytes, &lease, true, 2);
+    rc = qmc_matrix_prologue(*call, 2 * bytes, &lease);
     if (rc) return rc;
     DeviceCtx* const c = lease.c;
-    const auto hc = Scheme::make(S, T, r, q, 1, m, n_steps);
+    const auto hc = Scheme::make(S, T, r, q, 1, m, call->n_steps);
     QmcPathLaunch pl;
-    rc = qmc_path_setup(c, construction, 0, n_points, n_steps, sv, shift, 0, &pl, 2);
+    rc = qmc_matrix_setup(c, *call, &pl);
     if (rc) return rc;
-    const int32_t grid = qmc_block_grid((n_points + kWave - 1) / kWave);
-    return heston_path_matrices(c, n_points, n_steps, spot_host, var_host, [&](const EventPair* timed, double* d_spot, double* d_var) {
+    return heston_path_matrices(c, call->count, call->n_steps, spot_host, var_host, [&](const EventPair* timed, double* d_spot, double* d_var) {
         with_bool(path_major != 0, [&](auto pm) {
             if constexpr (Scheme::kBridge) {
                 with_bool(pl.bridge, [&](auto b) {
-                    launch_timed(heston_qmc_paths_kernel<b, pm>, dim3(grid), dim3(kBlock), c->stream, timed, pl.qr, hc, S, pl.d_sv, pl.d_shift, pl.plan,
+                    launch_timed(heston_qmc_paths_kernel<b, pm>, dim3(pl.grid), dim3(kBlock), c->stream, timed, pl.qr, hc, S, pl.d_sv, pl.d_shift, pl.plan,
                                  d_spot, d_var);
                 });
             } else {
-                launch_timed(heston_qe_qmc_paths_kernel<pm>, dim3(grid), dim3(kBlock), c->stream, timed, pl.qr, hc, S, pl.d_sv, pl.d_shift, d_spot, d_var);
+                launch_timed(heston_qe_qmc_paths_kernel<pm>, dim3(pl.grid), dim3(kBlock), c->stream, timed, pl.qr, hc, S, pl.d_sv, pl.d_shift, d_spot, d_var);
             }
         });
     });
@@ -2439,27 +2471,22 @@ extern "C" int olmc_heston_qmc(double S, double K, double T, double r, double q,
     const HestonModel hm{kappa, theta, sigma_v, rho, v0};
     int rc = heston_check(hm);
     if (rc) return rc;
-    rc = qmc_path_check(construction, point_offset, n_points, n_steps, sv, shift, bits, 2);
-    if (rc) return rc;
+    const auto call = SobolCall::make({construction, point_offset, n_points, n_steps, sv, shift, bits, antithetic}, 2, &rc);
+    if (!call) return rc;
     const HestonContract hc = make_heston(S, K, T, r, q, is_call, hm, n_steps);
     const bool bad = heston_poisoned(S, K, T, r, q, hm);
-    return run_qmc_payoff(construction, point_offset, n_points, n_steps, sv, shift, antithetic, r, T, bad, out,
-                          [&](int32_t g, hipStream_t s, const EventPair* timed, const QmcPathLaunch& pl, const ReduceWs& ws) {
-                              with_bool(pl.bridge, [&](auto b) {
-                                  with_bool(pl.anti, [&](auto m) {
-                                      launch_timed(heston_qmc_kernel<b, m>, dim3(g), dim3(kBlock), s, timed, pl.qr, hc, pl.d_sv, pl.d_shift, pl.plan,
-                                                   pl.slabs, ws);
-                                  });
-                              });
-                          },
-                          2, heston_qmc_shape(point_offset, n_points, n_steps));
+    return run_qmc_reduce(*call, 2, heston_qmc_shape, [&](int32_t g, hipStream_t s, const EventPair* timed, const QmcPathLaunch& pl, const ReduceWs& ws) {
+        with_bridge_anti(pl, [&](auto b, auto m) {
+            launch_timed(heston_qmc_kernel<b, m>, dim3(g), dim3(kBlock), s, timed, pl.qr, hc, pl.d_sv, pl.d_shift, pl.plan, pl.slabs, ws);
+        });
+    }, qmc_stats(r, T, bad, out));
 }
 
 extern "C" int olmc_heston_qmc_paths(double S, double T, double r, double q, double kappa, double theta, double sigma_v, double rho, double v0,
                                      int construction, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift,
                                      int32_t bits, int path_major, double* spot_host, double* var_host) {
-    return run_heston_qmc_paths<HestonEuler>(S, T, r, q, {kappa, theta, sigma_v, rho, v0}, construction, n_points, n_steps, sv, shift, bits, path_major,
-                                             spot_host, var_host);
+    return run_heston_qmc_paths<HestonEuler>(S, T, r, q, {kappa, theta, sigma_v, rho, v0}, {construction, 0, n_points, n_steps, sv, shift, bits, 0},
+                                             path_major, spot_host, var_host);
 }
 
 // ============================================================ path payoffs under Heston ====
@@ -2503,10 +2530,7 @@ ExtremaContract heston_path_contract(double S, double K, int is_call, int payoff
 // f(integral_constant<int, family>) for the family of a checked payoff code.
 template <typename F>
 void with_heston_path_family(int payoff, F&& f) {
-    const int family = heston_path_family(payoff);
-    if (family == kQmcAsianArithmetic) f(std::integral_constant<int, kQmcAsianArithmetic>{});
-    else if (family == kQmcAsianGeometric) f(std::integral_constant<int, kQmcAsianGeometric>{});
-    else f(std::integral_constant<int, kQmcExtrema>{});
+    with_qmc_path_family(heston_path_family(payoff), f);
 }
 }  // namespace
 
@@ -2543,23 +2567,19 @@ extern "C" int olmc_heston_qmc_path_payoff(double S, double K, double T, double 
     if (rc) return rc;
     rc = heston_path_check(payoff, barrier);
     if (rc) return rc;
-    rc = qmc_path_check(construction, point_offset, n_points, n_steps, sv, shift, bits, 2);
-    if (rc) return rc;
+    const auto call = SobolCall::make({construction, point_offset, n_points, n_steps, sv, shift, bits, antithetic}, 2, &rc);
+    if (!call) return rc;
     const HestonContract hc = make_heston(S, K, T, r, q, is_call, hm, n_steps);
     const ExtremaContract ec = heston_path_contract(S, K, is_call, payoff, barrier);
     const bool bad = heston_poisoned(S, K, T, r, q, hm) || (heston_path_is_barrier(payoff) && std::isnan(barrier));
-    return run_qmc_payoff(construction, point_offset, n_points, n_steps, sv, shift, antithetic, r, T, bad, out,
-                          [&](int32_t g, hipStream_t s, const EventPair* timed, const QmcPathLaunch& pl, const ReduceWs& ws) {
-                              with_heston_path_family(payoff, [&](auto f) {
-                                  with_bool(pl.bridge, [&](auto b) {
-                                      with_bool(pl.anti, [&](auto m) {
-                                          launch_timed(heston_qmc_path_kernel<f, b, m>, dim3(g), dim3(kBlock), s, timed, pl.qr, hc, ec, pl.inv_steps,
-                                                       pl.d_sv, pl.d_shift, pl.plan, pl.slabs, ws);
-                                      });
-                                  });
-                              });
-                          },
-                          2, heston_qmc_shape(point_offset, n_points, n_steps));
+    return run_qmc_reduce(*call, 2, heston_qmc_shape, [&](int32_t g, hipStream_t s, const EventPair* timed, const QmcPathLaunch& pl, const ReduceWs& ws) {
+        with_heston_path_family(payoff, [&](auto f) {
+            with_bridge_anti(pl, [&](auto b, auto m) {
+                launch_timed(heston_qmc_path_kernel<f, b, m>, dim3(g), dim3(kBlock), s, timed, pl.qr, hc, ec, pl.inv_steps, pl.d_sv, pl.d_shift, pl.plan,
+                             pl.slabs, ws);
+            });
+        });
+    }, qmc_stats(r, T, bad, out));
 }
 
 // ====================================================== a Heston option surface ====
@@ -2636,44 +2656,31 @@ int run_heston_surface(double S, double T, double r, double q, int is_call, cons
 // (without the bridge: the grid over the aligned blocks, no slabs).
 template <typename Scheme>
 int run_heston_qmc_surface(double S, double T, double r, double q, int is_call, const HestonModel& m, const double* strikes, const int32_t* steps,
-                           int32_t k, int construction, int64_t point_offset, int64_t n_points, int32_t n_steps, const uint32_t* sv,
-                           const uint32_t* shift, int32_t bits, int antithetic, olmc_stats* out) {
+                           int32_t k, const SobolArgs& args, olmc_stats* out) {
     if (!strikes || !steps || !out) return fail(OLMC_ERR_ARG, "null pointer");
-    int rc = heston_qmc_scheme_check<Scheme>(m, construction);
+    int rc = heston_qmc_scheme_check<Scheme>(m, args.construction);
     if (rc) return rc;
-    rc = qmc_path_check(construction, point_offset, n_points, n_steps, sv, shift, bits, 2);
-    if (rc) return rc;
+    const auto call = SobolCall::make(args, 2, &rc);
+    if (!call) return rc;
+    const int32_t n_steps = call->n_steps;
     SurfaceOrder so;
     rc = surface_cells(strikes, steps, k, n_steps, &so);
     if (rc) return rc;
     const auto hc = Scheme::make(S, T, r, q, is_call, m, n_steps);
     const bool bad = heston_poisoned(S, 0.0, T, r, q, m);
-    CtxLease lease;
-    rc = ctx_lease(&lease);
-    if (rc) return rc;
-    DeviceCtx* const c = lease.c;
-    QmcPathLaunch pl;
-    rc = qmc_path_setup(c, construction, point_offset, n_points, n_steps, sv, shift, antithetic, &pl, 2);
-    if (rc) return rc;
-    rc = heston_qmc_shape(point_offset, n_points, n_steps)(c, &pl);
-    if (rc) return rc;
-    rc = launch_reduce(c, c->stream, c->d_result, -1.0, 2 * kSurfaceCells, pl.grid,
-                       [&](int32_t g, hipStream_t s, const EventPair* timed, const ReduceWs& ws) {
-                           with_bool(pl.anti, [&](auto a) {
-                               if constexpr (Scheme::kBridge) {
-                                   with_bool(pl.bridge, [&](auto b) {
-                                       launch_timed(heston_qmc_surface_kernel<b, a>, dim3(g), dim3(kBlock), s, timed, pl.qr, hc, so.cells, pl.d_sv,
-                                                    pl.d_shift, pl.plan, pl.slabs, ws);
-                                   });
-                               } else {
-                                   launch_timed(heston_qe_qmc_surface_kernel<a>, dim3(g), dim3(kBlock), s, timed, pl.qr, hc, so.cells, pl.d_sv, pl.d_shift,
-                                                ws);
-                               }
-                           });
-                       });
-    if (rc) return rc;
-    surface_finish(c->h_result, so, strikes, steps, k, n_points * (pl.anti ? 2 : 1), r, T / n_steps, bad, out);
-    return OLMC_OK;
+    return run_qmc_reduce(*call, 2 * kSurfaceCells, heston_qmc_shape,
+                          [&](int32_t g, hipStream_t s, const EventPair* timed, const QmcPathLaunch& pl, const ReduceWs& ws) {
+        with_bool(pl.anti, [&](auto a) {
+            if constexpr (Scheme::kBridge) {
+                with_bool(pl.bridge, [&](auto b) {
+                    launch_timed(heston_qmc_surface_kernel<b, a>, dim3(g), dim3(kBlock), s, timed, pl.qr, hc, so.cells, pl.d_sv, pl.d_shift, pl.plan,
+                                 pl.slabs, ws);
+                });
+            } else {
+                launch_timed(heston_qe_qmc_surface_kernel<a>, dim3(g), dim3(kBlock), s, timed, pl.qr, hc, so.cells, pl.d_sv, pl.d_shift, ws);
+            }
+        });
+    }, [&](const double* h, int64_t n) { surface_finish(h, so, strikes, steps, k, n, r, T / n_steps, bad, out); });
 }
 }  // namespace
 
@@ -2688,8 +2695,8 @@ extern "C" int olmc_heston_qmc_surface(double S, double T, double r, double q, i
                                        double rho, double v0, const double* strikes, const int32_t* steps, int32_t k, int construction,
                                        int64_t point_offset, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift,
                                        int32_t bits, int antithetic, olmc_stats* out) {
-    return run_heston_qmc_surface<HestonEuler>(S, T, r, q, is_call, {kappa, theta, sigma_v, rho, v0}, strikes, steps, k, construction, point_offset,
-                                               n_points, n_steps, sv, shift, bits, antithetic, out);
+    return run_heston_qmc_surface<HestonEuler>(S, T, r, q, is_call, {kappa, theta, sigma_v, rho, v0}, strikes, steps, k,
+                                               {construction, point_offset, n_points, n_steps, sv, shift, bits, antithetic}, out);
 }
 
 // ====================================================== Dupire local volatility ====
@@ -2855,18 +2862,10 @@ namespace {
 // The shape of a local-volatility Sobol launch (lv_qmc_price_kernel, lv_qmc_surface_kernel): heston_qmc_shape's grid over the aligned
 // blocks of 64 points, for the bridge one [n][64] slab per wave of the grid in the Heston kernels' block (heston_slabs), then the table
 // and the model in units of true normals.
-auto lv_qmc_shape(const ollv_surface* surf, double S, double T, double r, double q, int64_t point_offset, int64_t n_points, int32_t n_steps,
-                  LvModel* m) {
-    return [=](DeviceCtx* c, QmcPathLaunch* pl) {
-        const int64_t first_block = point_offset / kWave, last_block = (point_offset + n_points - 1) / kWave;
-        pl->grid = qmc_block_grid(last_block - first_block + 1);
-        pl->slabs = nullptr;
-        if (pl->bridge) {
-            const int rc = heston_slabs(c, n_steps, &pl->grid, 1);
-            if (rc) return rc;
-            pl->slabs = c->heston_w.as<double>();
-        }
-        return lv_upload(c, surf, S, T, r, q, n_steps, m, 1.0);
+auto lv_qmc_shape(const ollv_surface* surf, double S, double T, double r, double q, LvModel* m) {
+    return [=](DeviceCtx* c, const SobolCall& call, QmcPathLaunch* pl) {
+        const int rc = heston_qmc_shape(c, call, pl);
+        return rc ? rc : lv_upload(c, surf, S, T, r, q, call.n_steps, m, 1.0);
     };
 }
 }  // namespace
@@ -2879,23 +2878,19 @@ extern "C" int olvq_price(double S, double K, double T, double r, double q, int 
     if (rc) return rc;
     rc = lv_payoff_check(payoff, barrier);
     if (rc) return rc;
-    rc = qmc_path_check(construction, point_offset, n_points, n_steps, sv, shift, bits);
-    if (rc) return rc;
+    const auto call = SobolCall::make({construction, point_offset, n_points, n_steps, sv, shift, bits, antithetic}, 1, &rc);
+    if (!call) return rc;
     const ExtremaContract ec = heston_path_contract(S, K, is_call, payoff == OLLV_EUROPEAN ? OLMC_PATH_ASIAN_ARITHMETIC : payoff, barrier);
     const bool bad = lv_poisoned(S, K, T, r, q, surf) || (heston_path_is_barrier(payoff) && std::isnan(barrier));
     LvModel m;
-    return run_qmc_payoff(construction, point_offset, n_points, n_steps, sv, shift, antithetic, r, T, bad, out,
+    return run_qmc_reduce(*call, 2, lv_qmc_shape(surf, S, T, r, q, &m),
                           [&](int32_t g, hipStream_t s, const EventPair* timed, const QmcPathLaunch& pl, const ReduceWs& ws) {
-                              with_lv_family(payoff, [&](auto f) {
-                                  with_bool(pl.bridge, [&](auto b) {
-                                      with_bool(pl.anti, [&](auto a) {
-                                          lv_launch(lv_qmc_price_kernel<f, b, a>, m, true, g, s, timed, pl.qr, m, ec, pl.inv_steps, pl.d_sv, pl.d_shift,
-                                                    pl.plan, pl.slabs, ws);
-                                      });
-                                  });
-                              });
-                          },
-                          1, lv_qmc_shape(surf, S, T, r, q, point_offset, n_points, n_steps, &m));
+        with_lv_family(payoff, [&](auto f) {
+            with_bridge_anti(pl, [&](auto b, auto a) {
+                lv_launch(lv_qmc_price_kernel<f, b, a>, m, true, g, s, timed, pl.qr, m, ec, pl.inv_steps, pl.d_sv, pl.d_shift, pl.plan, pl.slabs, ws);
+            });
+        });
+    }, qmc_stats(r, T, bad, out));
 }
 
 extern "C" int olvq_paths(double S, double T, double r, double q, const ollv_surface* surf, int construction, int64_t n_points, int32_t n_steps,
@@ -2903,27 +2898,26 @@ extern "C" int olvq_paths(double S, double T, double r, double q, const ollv_sur
     if (!out_host) return fail(OLMC_ERR_ARG, "null pointer");
     int rc = lv_surface_check(surf);
     if (rc) return rc;
-    rc = qmc_path_check(construction, 0, n_points, n_steps, sv, shift, bits);
-    if (rc) return rc;
+    const auto call = SobolCall::make({construction, 0, n_points, n_steps, sv, shift, bits, 0}, 1, &rc);
+    if (!call) return rc;
     const double bytes = 8.0 * static_cast<double>(n_points) * (n_steps + 1.0);
     CtxLease lease;
     rc = matrix_prologue(n_points, n_steps, bytes, "path matrix would exceed 64 GB", &lease);
     if (rc) return rc;
     DeviceCtx* const c = lease.c;
     QmcPathLaunch pl;
-    rc = qmc_path_setup(c, construction, 0, n_points, n_steps, sv, shift, 0, &pl);
+    rc = qmc_matrix_setup(c, *call, &pl);
     if (rc) return rc;
     LvModel m;
     rc = lv_upload(c, surf, S, T, r, q, n_steps, &m, 1.0);
     if (rc) return rc;
-    const int32_t grid = qmc_block_grid((n_points + kWave - 1) / kWave);
     EventPair ep{};
     const EventPair* timed = nullptr;                  // profiling on: the path kernel counts in olmc_kernel_time
     rc = prof_pair(c, &ep, &timed);
     if (rc) return rc;
     with_bool(pl.bridge, [&](auto b) {
         with_bool(path_major != 0, [&](auto pm) {
-            lv_launch(lv_qmc_paths_kernel<b, pm>, m, true, grid, c->stream, timed, pl.qr, m, pl.d_sv, pl.d_shift, pl.plan, c->bulk.as<double>());
+            lv_launch(lv_qmc_paths_kernel<b, pm>, m, true, pl.grid, c->stream, timed, pl.qr, m, pl.d_sv, pl.d_shift, pl.plan, c->bulk.as<double>());
         });
     });
     HIP_TRY(hipGetLastError());
@@ -2936,35 +2930,20 @@ extern "C" int olvq_surface_prices(double S, double T, double r, double q, int i
     if (!strikes || !steps || !out) return fail(OLMC_ERR_ARG, "null pointer");
     int rc = lv_surface_check(surf);
     if (rc) return rc;
-    rc = qmc_path_check(construction, point_offset, n_points, n_steps, sv, shift, bits);
-    if (rc) return rc;
+    const auto call = SobolCall::make({construction, point_offset, n_points, n_steps, sv, shift, bits, antithetic}, 1, &rc);
+    if (!call) return rc;
     SurfaceOrder so;
     rc = surface_cells(strikes, steps, k, n_steps, &so);
     if (rc) return rc;
     const bool bad = lv_poisoned(S, 0.0, T, r, q, surf);
-    CtxLease lease;
-    rc = ctx_lease(&lease);
-    if (rc) return rc;
-    DeviceCtx* const c = lease.c;
-    QmcPathLaunch pl;
-    rc = qmc_path_setup(c, construction, point_offset, n_points, n_steps, sv, shift, antithetic, &pl);
-    if (rc) return rc;
     LvModel m;
-    rc = lv_qmc_shape(surf, S, T, r, q, point_offset, n_points, n_steps, &m)(c, &pl);
-    if (rc) return rc;
     const double sign = is_call ? 1.0 : -1.0;
-    rc = launch_reduce(c, c->stream, c->d_result, -1.0, 2 * kSurfaceCells, pl.grid,
-                       [&](int32_t g, hipStream_t s, const EventPair* timed, const ReduceWs& ws) {
-                           with_bool(pl.bridge, [&](auto b) {
-                               with_bool(pl.anti, [&](auto a) {
-                                   lv_launch(lv_qmc_surface_kernel<b, a>, m, true, g, s, timed, pl.qr, m, sign, so.cells, pl.d_sv, pl.d_shift, pl.plan,
-                                             pl.slabs, ws);
-                               });
-                           });
-                       });
-    if (rc) return rc;
-    surface_finish(c->h_result, so, strikes, steps, k, n_points * (pl.anti ? 2 : 1), r, T / n_steps, bad, out);
-    return OLMC_OK;
+    return run_qmc_reduce(*call, 2 * kSurfaceCells, lv_qmc_shape(surf, S, T, r, q, &m),
+                          [&](int32_t g, hipStream_t s, const EventPair* timed, const QmcPathLaunch& pl, const ReduceWs& ws) {
+        with_bridge_anti(pl, [&](auto b, auto a) {
+            lv_launch(lv_qmc_surface_kernel<b, a>, m, true, g, s, timed, pl.qr, m, sign, so.cells, pl.d_sv, pl.d_shift, pl.plan, pl.slabs, ws);
+        });
+    }, [&](const double* h, int64_t n) { surface_finish(h, so, strikes, steps, k, n, r, T / n_steps, bad, out); });
 }
 
 // ====================================================== Heston scenario sets and fused Greeks ====
@@ -3024,36 +3003,22 @@ int run_heston_scenarios(const olmc_heston_scenario* sc, int32_t k, int64_t path
 }
 
 // Sobol: the scenarios on points [point_offset, point_offset + n_points) of olmc_heston_qmc's construction; the shape of a Heston price launch.
-int run_heston_qmc_scenarios(const olmc_heston_scenario* sc, int32_t k, int construction, int64_t point_offset, int64_t n_points, int32_t n_steps,
-                             const uint32_t* sv, const uint32_t* shift, int32_t bits, int antithetic, olmc_stats* out) {
+int run_heston_qmc_scenarios(const olmc_heston_scenario* sc, int32_t k, const SobolArgs& args, olmc_stats* out) {
     int rc = scenario_check(sc, k, out);
     if (rc) return rc;
-    rc = qmc_path_check(construction, point_offset, n_points, n_steps, sv, shift, bits, 2);
-    if (rc) return rc;
+    const auto call = SobolCall::make(args, 2, &rc);
+    if (!call) return rc;
     HestonScenarioSet set;
     int32_t slot_of[OLMC_MAX_BATCH];
-    if (const char* bad = heston_scenario_set(sc, k, n_steps, 1.0, &set, slot_of)) return fail(OLMC_ERR_ARG, bad);
-    CtxLease lease;
-    rc = ctx_lease(&lease);
-    if (rc) return rc;
-    DeviceCtx* const c = lease.c;
-    QmcPathLaunch pl;
-    rc = qmc_path_setup(c, construction, point_offset, n_points, n_steps, sv, shift, antithetic, &pl, 2);
-    if (rc) return rc;
-    rc = heston_qmc_shape(point_offset, n_points, n_steps)(c, &pl);
-    if (rc) return rc;
-    rc = launch_reduce(c, c->stream, c->d_result, -1.0, 2 * kSurfaceCells, pl.grid,
-                       [&](int32_t g, hipStream_t s, const EventPair* timed, const ReduceWs& ws) {
-                           with_bool(pl.anti, [&](auto a) {
-                               with_bool(pl.bridge, [&](auto b) {
-                                   launch_timed(heston_qmc_scenarios_kernel<b, a>, dim3(g), dim3(kBlock), s, timed, set, pl.qr, pl.d_sv, pl.d_shift,
-                                                pl.plan, pl.slabs, ws);
-                               });
-                           });
-                       });
-    if (rc) return rc;
-    scenario_finish(c->h_result, slot_of, sc, k, n_points * (pl.anti ? 2 : 1), out);
-    return OLMC_OK;
+    if (const char* bad = heston_scenario_set(sc, k, call->n_steps, 1.0, &set, slot_of)) return fail(OLMC_ERR_ARG, bad);
+    return run_qmc_reduce(*call, 2 * kSurfaceCells, heston_qmc_shape,
+                          [&](int32_t g, hipStream_t s, const EventPair* timed, const QmcPathLaunch& pl, const ReduceWs& ws) {
+        with_bool(pl.anti, [&](auto a) {           // the surface's nest, not with_bridge_anti's: the kernels keep their order in the code object
+            with_bool(pl.bridge, [&](auto b) {
+                launch_timed(heston_qmc_scenarios_kernel<b, a>, dim3(g), dim3(kBlock), s, timed, set, pl.qr, pl.d_sv, pl.d_shift, pl.plan, pl.slabs, ws);
+            });
+        });
+    }, [&](const double* h, int64_t n) { scenario_finish(h, slot_of, sc, k, n, out); });
 }
 }  // namespace
 
@@ -3072,7 +3037,7 @@ extern "C" int olmc_heston_scenarios(const olmc_heston_scenario* sc, int32_t k, 
 extern "C" int olmc_heston_qmc_scenarios(const olmc_heston_scenario* sc, int32_t k, int construction, int64_t point_offset, int64_t n_points,
                                          int32_t n_steps, const uint32_t* sv, const uint32_t* shift, int32_t bits, int antithetic,
                                          olmc_stats* out) {
-    return run_heston_qmc_scenarios(sc, k, construction, point_offset, n_points, n_steps, sv, shift, bits, antithetic, out);
+    return run_heston_qmc_scenarios(sc, k, {construction, point_offset, n_points, n_steps, sv, shift, bits, antithetic}, out);
 }
 
 // The 7 / 8 / 11 / 14 contracts of compute_greeks_unified under the model, sigma -> v0 = sigma^2 (HestonAdapter, unified_greeks.py:74-104),
@@ -3102,7 +3067,7 @@ extern "C" int olmc_heston_qmc_greeks_fd(double S, double K, double T, double r,
     olmc_heston_scenario sc[OLMC_MAX_BATCH];
     heston_greeks_scenarios(gs, kappa, theta, sigma_v, rho, sc);
     olmc_stats st[OLMC_MAX_BATCH];
-    const int rc = run_heston_qmc_scenarios(sc, gs.k, construction, 0, n_points, n_steps, sv, shift, bits, antithetic, st);
+    const int rc = run_heston_qmc_scenarios(sc, gs.k, {construction, 0, n_points, n_steps, sv, shift, bits, antithetic}, st);
     if (rc) return rc;
     gs.finish(st, T, out9, evals);
     return OLMC_OK;
@@ -3123,8 +3088,8 @@ extern "C" int olmc_heston_qe_qmc_surface(double S, double T, double r, double q
                                           double rho, double v0, const double* strikes, const int32_t* steps, int32_t k, int construction,
                                           int64_t point_offset, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift,
                                           int32_t bits, int antithetic, olmc_stats* out) {
-    return run_heston_qmc_surface<HestonQe>(S, T, r, q, is_call, {kappa, theta, sigma_v, rho, v0}, strikes, steps, k, construction, point_offset,
-                                            n_points, n_steps, sv, shift, bits, antithetic, out);
+    return run_heston_qmc_surface<HestonQe>(S, T, r, q, is_call, {kappa, theta, sigma_v, rho, v0}, strikes, steps, k,
+                                            {construction, point_offset, n_points, n_steps, sv, shift, bits, antithetic}, out);
 }
 
 extern "C" int olmc_heston_qe_paths(double S, double T, double r, double q, double kappa, double theta, double sigma_v, double rho, double v0,
@@ -3135,8 +3100,8 @@ extern "C" int olmc_heston_qe_paths(double S, double T, double r, double q, doub
 extern "C" int olmc_heston_qe_qmc_paths(double S, double T, double r, double q, double kappa, double theta, double sigma_v, double rho, double v0,
                                         int construction, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift,
                                         int32_t bits, int path_major, double* spot_host, double* var_host) {
-    return run_heston_qmc_paths<HestonQe>(S, T, r, q, {kappa, theta, sigma_v, rho, v0}, construction, n_points, n_steps, sv, shift, bits, path_major,
-                                          spot_host, var_host);
+    return run_heston_qmc_paths<HestonQe>(S, T, r, q, {kappa, theta, sigma_v, rho, v0}, {construction, 0, n_points, n_steps, sv, shift, bits, 0},
+                                          path_major, spot_host, var_host);
 }
 
 // ====================================================== structured products under Heston ====
@@ -3168,42 +3133,34 @@ int run_heston_product(double S, double T, double r, double q, const HestonModel
     });
 }
 
-// The checks of a Sobol call that do not depend on the product, in the order of olmc_heston_qe_qmc_surface.
-int heston_qmc_product_check(int scheme, const HestonModel& m, int construction, int64_t point_offset, int64_t n_points, int32_t n_steps,
-                             const uint32_t* sv, const uint32_t* shift, int32_t bits) {
-    int rc = heston_scheme_check(scheme, m);
-    if (rc) return rc;
-    if (scheme == OLMC_HESTON_QE) {
-        rc = heston_qe_sequential(construction);
-        if (rc) return rc;
-    }
-    return qmc_path_check(construction, point_offset, n_points, n_steps, sv, shift, bits, 2);
+// The checks of a Sobol call that do not depend on the product, in the order of olmc_heston_qe_qmc_surface, and the call they pass.
+std::optional<SobolCall> heston_qmc_product_call(int scheme, const HestonModel& m, const SobolArgs& args, int* rc) {
+    *rc = heston_scheme_check(scheme, m);
+    if (!*rc && scheme == OLMC_HESTON_QE) *rc = heston_qe_sequential(args.construction);
+    if (*rc) return std::nullopt;
+    return SobolCall::make(args, 2, rc);
 }
 
-// Sobol: points [point_offset, point_offset + n_points) of olmc_heston_qmc's construction (Euler) / olmc_heston_qe_qmc_surface's (QE:
-// sequential, the grid over the aligned blocks, no slabs).
+// Sobol: the points of olmc_heston_qmc's construction (Euler) / olmc_heston_qe_qmc_surface's (QE: sequential, the grid over the aligned
+// blocks, no slabs).
 template <template <bool> class Product>
 int run_heston_qmc_product(double S, double T, double r, double q, const HestonModel& m, int scheme, const typename Product<false>::Contract& pc,
-                           double r_for_discount, bool bad, int construction, int64_t point_offset, int64_t n_points, int32_t n_steps,
-                           const uint32_t* sv, const uint32_t* shift, int antithetic, olmc_stats* out) {
+                           double r_for_discount, bool bad, const SobolCall& call, olmc_stats* out) {
     return with_heston_scheme(scheme, [&](auto s) {
         using Scheme = decltype(s);
-        const auto hc = Scheme::make(S, T, r, q, 1, m, n_steps);
-        return run_qmc_payoff(construction, point_offset, n_points, n_steps, sv, shift, antithetic, r_for_discount, T, bad, out,
-                              [&](int32_t g, hipStream_t st, const EventPair* timed, const QmcPathLaunch& pl, const ReduceWs& ws) {
-                                  with_bool(pl.anti, [&](auto a) {
-                                      if constexpr (Scheme::kBridge) {
-                                          with_bool(pl.bridge, [&](auto b) {
-                                              launch_timed(heston_qmc_product_kernel<Product, b, a>, dim3(g), dim3(kBlock), st, timed, pl.qr, hc, pc,
-                                                           pl.d_sv, pl.d_shift, pl.plan, pl.slabs, ws);
-                                          });
-                                      } else {
-                                          launch_timed(heston_qe_qmc_product_kernel<Product, a>, dim3(g), dim3(kBlock), st, timed, pl.qr, hc, pc, pl.d_sv,
-                                                       pl.d_shift, ws);
-                                      }
-                                  });
-                              },
-                              2, heston_qmc_shape(point_offset, n_points, n_steps));
+        const auto hc = Scheme::make(S, T, r, q, 1, m, call.n_steps);
+        return run_qmc_reduce(call, 2, heston_qmc_shape, [&](int32_t g, hipStream_t st, const EventPair* timed, const QmcPathLaunch& pl, const ReduceWs& ws) {
+            with_bool(pl.anti, [&](auto a) {
+                if constexpr (Scheme::kBridge) {
+                    with_bool(pl.bridge, [&](auto b) {
+                        launch_timed(heston_qmc_product_kernel<Product, b, a>, dim3(g), dim3(kBlock), st, timed, pl.qr, hc, pc, pl.d_sv, pl.d_shift,
+                                     pl.plan, pl.slabs, ws);
+                    });
+                } else {
+                    launch_timed(heston_qe_qmc_product_kernel<Product, a>, dim3(g), dim3(kBlock), st, timed, pl.qr, hc, pc, pl.d_sv, pl.d_shift, ws);
+                }
+            });
+        }, qmc_stats(r_for_discount, T, bad, out));
     });
 }
 }  // namespace
@@ -3230,13 +3187,13 @@ extern "C" int olmc_heston_autocallable_qmc(double S, double T, double r, double
                                             olmc_stats* out) {
     if (!out) return fail(OLMC_ERR_ARG, "null pointer");
     const HestonModel m{kappa, theta, sigma_v, rho, v0};
-    int rc = heston_qmc_product_check(scheme, m, construction, point_offset, n_points, n_steps, sv, shift, bits);
-    if (rc) return rc;
+    int rc;
+    const auto call = heston_qmc_product_call(scheme, m, {construction, point_offset, n_points, n_steps, sv, shift, bits, antithetic}, &rc);
+    if (!call) return rc;
     rc = autocall_check(observation_freq, n_steps);
     if (rc) return rc;
     const AutocallSetup a = make_autocall(S, T, r, 0.0, q, autocall_barrier, coupon_barrier, coupon_rate, ki_barrier, observation_freq, n_steps);
-    return run_heston_qmc_product<HestonAutocall>(S, T, r, q, m, scheme, a.ac, 0.0, a.bad || m.nan(), construction, point_offset, n_points, n_steps,
-                                                  sv, shift, antithetic, out);
+    return run_heston_qmc_product<HestonAutocall>(S, T, r, q, m, scheme, a.ac, 0.0, a.bad || m.nan(), *call, out);
 }
 
 extern "C" int olmc_heston_cliquet(double S, double T, double r, double q, double kappa, double theta, double sigma_v, double rho, double v0,
@@ -3259,29 +3216,29 @@ extern "C" int olmc_heston_cliquet_qmc(double S, double T, double r, double q, d
                                        const uint32_t* sv, const uint32_t* shift, int32_t bits, int antithetic, olmc_stats* out) {
     if (!out) return fail(OLMC_ERR_ARG, "null pointer");
     const HestonModel m{kappa, theta, sigma_v, rho, v0};
-    int rc = heston_qmc_product_check(scheme, m, construction, point_offset, n_points, n_steps, sv, shift, bits);
-    if (rc) return rc;
+    int rc;
+    const auto call = heston_qmc_product_call(scheme, m, {construction, point_offset, n_points, n_steps, sv, shift, bits, antithetic}, &rc);
+    if (!call) return rc;
     rc = cliquet_check(n_periods, n_steps);
     if (rc) return rc;
     const CliquetContract cc = make_cliquet(S, T, r, 0.0, q, local_cap, local_floor, global_cap, global_floor, n_periods, n_steps);
     const bool bad = cliquet_poisoned(S, T, r, 0.0, q, local_cap, local_floor, global_cap, global_floor) || m.nan();
-    return run_heston_qmc_product<HestonCliquet>(S, T, r, q, m, scheme, cc, r, bad, construction, point_offset, n_points, n_steps, sv, shift,
-                                                 antithetic, out);
+    return run_heston_qmc_product<HestonCliquet>(S, T, r, q, m, scheme, cc, r, bad, *call, out);
 }
 
 namespace {
-// k (2 .. 16) contracts on points [point_offset, point_offset + n_paths), ONE launch (european_qmc_batch_kernel) whose grid covers
-// them all, queued on c's own stream behind the table: the 2 nsets sums then `tail` at d_out, contract i's pair at slot pos[i]
-// (launch_reduce: blocks when d_out is c->d_result).
-int qmc_batch_device(DeviceCtx* c, const olmc_option* opts, int32_t k, int64_t point_offset, int64_t n_paths, int32_t dims,
-                     const uint32_t* sv, const uint32_t* shift, double* d_out, double tail, int* pos, bool profiled) {
-    const QmcShape sh = qmc_shape(point_offset, n_paths, dims);
+// k (2 .. 16) contracts on the points of q, ONE launch (european_qmc_batch_kernel) whose grid covers them all, queued on c's own
+// stream behind the table: the 2 nsets sums then `tail` at d_out, contract i's pair at slot pos[i] (launch_reduce: blocks when d_out
+// is c->d_result).
+int qmc_batch_device(DeviceCtx* c, const olmc_option* opts, int32_t k, const SobolCall& q, double* d_out, double tail, int* pos, bool profiled) {
+    const QmcShape sh = qmc_shape(q);
     if (k < 2 || (sh.units + kBlock - 1) / kBlock > kMaxGrid)
         return fail(OLMC_ERR_ARG, "a shard of fused Sobol contracts needs 2 .. 16 contracts and points one grid covers");
     const uint32_t *d_sv, *d_shift;
-    int rc = qmc_table(c, sv, shift, dims, &d_sv, &d_shift);
+    int rc = qmc_table(c, q, &d_sv, &d_shift);
     if (rc) return rc;
-    const QmcRange qr{static_cast<uint64_t>(point_offset), n_paths, dims, 0};
+    const QmcRange qr = q.range();
+    const int32_t dims = q.dims();
     const int32_t grid = sh.split ? sh.grid : static_cast<int32_t>((sh.units + kBlock - 1) / kBlock);     // the grid covers every point / block
     const int nsets = k <= 8 ? 8 : 16;
     return launch_reduce(c, c->stream, d_out, tail, 2 * nsets, grid, [&](int32_t g, hipStream_t s, const EventPair* timed, const ReduceWs& ws) {
@@ -3300,17 +3257,16 @@ int qmc_batch_device(DeviceCtx* c, const olmc_option* opts, int32_t k, int64_t p
 
 // k contracts on the same Sobol points, ONE launch (qmc_batch_device); falls back to k launches beyond the size one grid covers.
 // out[i] = stats of opts[i].
-int run_qmc_batch(const olmc_option* opts, int32_t k, int64_t point_offset, int64_t n_paths, int32_t dims, const uint32_t* sv,
-                  const uint32_t* shift, int32_t bits, olmc_stats* out) {
+int run_qmc_batch(const olmc_option* opts, int32_t k, const SobolArgs& args, olmc_stats* out) {
     if (!opts || !out) return fail(OLMC_ERR_ARG, "null pointer");
     if (k < 1 || k > OLMC_MAX_BATCH) return fail(OLMC_ERR_ARG, "batch size must be in [1, OLMC_MAX_BATCH]");
-    int rc = qmc_check(sv, shift, bits, dims, point_offset, n_paths);
-    if (rc) return rc;
-    const int64_t units = qmc_shape(point_offset, n_paths, dims).units;
+    int rc;
+    const auto q = SobolCall::make(args, 1, &rc);
+    if (!q) return rc;
+    const int64_t units = qmc_shape(*q).units;
     if (k == 1 || (units + kBlock - 1) / kBlock > kMaxGrid) {             // one contract, or more points than a grid covers: literal launches
         for (int i = 0; i < k; ++i) {
-            rc = run_qmc(opts[i].S, opts[i].K, opts[i].T, opts[i].r, opts[i].sigma, opts[i].q, opts[i].is_call, point_offset, n_paths, dims, sv, shift,
-                         bits, &out[i], nullptr);
+            rc = run_qmc(opts[i], *q, &out[i], nullptr);
             if (rc) return rc;
         }
         return OLMC_OK;
@@ -3320,16 +3276,16 @@ int run_qmc_batch(const olmc_option* opts, int32_t k, int64_t point_offset, int6
     if (rc) return rc;
     DeviceCtx* const c = lease.c;
     int pos[OLMC_MAX_BATCH];
-    rc = qmc_batch_device(c, opts, k, point_offset, n_paths, dims, sv, shift, c->d_result, -1.0, pos, true);
+    rc = qmc_batch_device(c, opts, k, *q, c->d_result, -1.0, pos, true);
     if (rc) return rc;
-    finish_set(c->h_result, pos, n_paths, opts, k, false, false, out);
+    finish_set(c->h_result, pos, q->count, opts, k, false, false, out);
     return OLMC_OK;
 }
 }  // namespace
 
 extern "C" int olmc_european_qmc_batch(const olmc_option* opts, int32_t k, int64_t point_offset, int64_t n_paths, int32_t dims,
                                        const uint32_t* sv, const uint32_t* shift, int32_t bits, olmc_stats* out) {
-    return run_qmc_batch(opts, k, point_offset, n_paths, dims, sv, shift, bits, out);
+    return run_qmc_batch(opts, k, {OLMC_QMC_SEQUENTIAL, point_offset, n_paths, dims, sv, shift, bits, 0}, out);
 }
 
 extern "C" int olmc_european_qmc_greeks_fd(double S, double K, double T, double r, double sigma, double q, int is_call, int64_t n_paths,
@@ -3339,7 +3295,7 @@ extern "C" int olmc_european_qmc_greeks_fd(double S, double K, double T, double 
     if (!(T > 0.0)) return fail(OLMC_ERR_ARG, "T must be > 0 (price() returns intrinsic value without simulating)");
     const GreeksSet gs(S, K, T, r, sigma, q, is_call, second_order);
     olmc_stats st[OLMC_MAX_BATCH];
-    int rc = run_qmc_batch(gs.o, gs.k, 0, n_paths, dims, sv, shift, bits, st);
+    int rc = run_qmc_batch(gs.o, gs.k, {OLMC_QMC_SEQUENTIAL, 0, n_paths, dims, sv, shift, bits, 0}, st);
     if (rc) return rc;
     gs.finish(st, T, out9, evals);
     return OLMC_OK;
@@ -3818,12 +3774,13 @@ extern "C" int olmc_multi_gpu_european_qmc(double S, double K, double T, double 
                                            int64_t n_paths, int32_t dims, const uint32_t* sv, const uint32_t* shift, int32_t bits,
                                            int n_gpus, olmc_stats* out) {
     if (!out) return fail(OLMC_ERR_ARG, "null pointer");
-    int rc = qmc_check(sv, shift, bits, dims, 0, n_paths);
-    if (rc) return rc;
+    int rc;
+    const auto call = SobolCall::make({OLMC_QMC_SEQUENTIAL, 0, n_paths, dims, sv, shift, bits, 0}, 1, &rc);
+    if (!call) return rc;
     const Contract ct = qmc_contract(S, K, T, r, sigma, q, is_call, dims, false);
     double host[3] = {0, 0, 0};
     rc = multi_gpu_run(n_gpus, n_paths, dims, 3, [&](int, int64_t lo, int64_t n_local, DeviceCtx* c, double* d_send) {
-        return qmc_device(c, ct, lo, n_local, dims, sv, shift, false, d_send, static_cast<double>(n_local), false);
+        return qmc_device(c, ct, call->over(lo, n_local), false, d_send, static_cast<double>(n_local), false);
     }, host, true);
     if (rc) return rc;
     finish_one(host, static_cast<int64_t>(host[2]), r, T, poisoned(S, K, T, r, sigma, q), out);
@@ -3838,15 +3795,16 @@ extern "C" int olmc_multi_gpu_european_qmc_greeks_fd(double S, double K, double 
                                                      int32_t bits, int second_order, int n_gpus, double* out9, olmc_stats* evals) {
     if (!out9) return fail(OLMC_ERR_ARG, "null pointer");
     if (!(T > 0.0)) return fail(OLMC_ERR_ARG, "T must be > 0 (price() returns intrinsic value without simulating)");
-    int rc = qmc_check(sv, shift, bits, dims, 0, n_paths);
-    if (rc) return rc;
+    int rc;
+    const auto call = SobolCall::make({OLMC_QMC_SEQUENTIAL, 0, n_paths, dims, sv, shift, bits, 0}, 1, &rc);
+    if (!call) return rc;
     const GreeksSet gs(S, K, T, r, sigma, q, is_call, second_order);
     const int nsets = gs.k <= 8 ? 8 : 16;
     int pos[OLMC_MAX_BATCH] = {};
     double host[kMultiValues] = {};
     rc = multi_gpu_run(n_gpus, n_paths, dims, 2 * nsets + 1, [&](int rank, int64_t lo, int64_t n_local, DeviceCtx* c, double* d_send) {
         int other[OLMC_MAX_BATCH];                                                               // every rank lays the set out alike: rank 0's
-        return qmc_batch_device(c, gs.o, gs.k, lo, n_local, dims, sv, shift, d_send, static_cast<double>(n_local), rank == 0 ? pos : other, false);
+        return qmc_batch_device(c, gs.o, gs.k, call->over(lo, n_local), d_send, static_cast<double>(n_local), rank == 0 ? pos : other, false);
     }, host, true);
     if (rc) return rc;
     olmc_stats st[OLMC_MAX_BATCH];
@@ -3861,12 +3819,13 @@ extern "C" int olmc_multi_gpu_european_qmc_cv(double S, double K, double T, doub
                                               int64_t n_paths, int32_t dims, const uint32_t* sv, const uint32_t* shift, int32_t bits,
                                               int n_gpus, olmc_cv_moments* out) {
     if (!out) return fail(OLMC_ERR_ARG, "null pointer");
-    int rc = qmc_check(sv, shift, bits, dims, 0, n_paths);
-    if (rc) return rc;
+    int rc;
+    const auto call = SobolCall::make({OLMC_QMC_SEQUENTIAL, 0, n_paths, dims, sv, shift, bits, 0}, 1, &rc);
+    if (!call) return rc;
     const Contract ct = qmc_contract(S, K, T, r, sigma, q, is_call, dims, false);
     double host[6] = {};
     rc = multi_gpu_run(n_gpus, n_paths, dims, 6, [&](int, int64_t lo, int64_t n_local, DeviceCtx* c, double* d_send) {
-        return qmc_device(c, ct, lo, n_local, dims, sv, shift, true, d_send, static_cast<double>(n_local), false);
+        return qmc_device(c, ct, call->over(lo, n_local), true, d_send, static_cast<double>(n_local), false);
     }, host, true);
     if (rc) return rc;
     cv_from_device(host, static_cast<int64_t>(host[5]), S, T, r, q, out);

@@ -325,6 +325,25 @@ _REFUSALS = [
      "T must be > 0 (price() returns intrinsic value without simulating)"),
     ("olmc_multi_gpu_european_qmc_greeks_fd", lambda: (*_G, 64, 4, *_sobol(4), 30, 0, 0, _out9(), None), "n_gpus out of range"),
     ("olmc_multi_gpu_european_qmc_cv", lambda: (*_G, 64, 0, *_sobol(1), 30, 1, _CV()), "dims must be in [1, 21201]"),
+    # two faults at once: the refusal is the one of the check that comes first (the entry point's own, then the Sobol call's:
+    # construction, bridge cap, tables, bits, dims, points; then the matrix size)
+    ("olmc_asian_qmc", lambda: (*_G, 2, 2, 0, 64, 4, *_sobol(4), 30, 0, _ST()), "bad avg_kind (arithmetic or geometric)"),
+    ("olmc_asian_qmc", lambda: (*_G, 0, 2, 0, 64, 4, *_sobol(4), 32, 0, _ST()), "bad construction"),
+    ("olmc_asian_qmc", lambda: (*_G, 0, 0, 0, 64, 4, *_sobol(4), 32, 0, None), "null pointer"),
+    ("olmc_extrema_qmc", lambda: (*_G, 6, 120.0, 0, 0, 64, 4, *_sobol(4), 32, 0, _ST()), "bad payoff"),
+    ("olmc_extrema_qmc", lambda: (*_G, 5, 0.0, 0, 0, 0, 4, *_sobol(4), 32, 0, _ST()), "only 30-bit Sobol tables (SciPy's default) are supported"),
+    ("olmc_european_qmc", lambda: (*_G, 0, 0, 0, *_sobol(1), 32, _ST()), "only 30-bit Sobol tables (SciPy's default) are supported"),
+    ("olmc_european_qmc_greeks_fd", lambda: (*_GT0, 64, 4, *_sobol(4), 32, 0, _out9(), None),
+     "T must be > 0 (price() returns intrinsic value without simulating)"),
+    ("olmc_european_qmc_batch", lambda: (_opts(2), 0, 0, 64, 4, *_sobol(4), 32, (_hip.Stats * 16)()), "batch size must be in [1, OLMC_MAX_BATCH]"),
+    ("olmc_american_lsm_qmc", lambda: (*_G, 2, 64, 4, *_sobol(4), 30, 5, _ST()), "poly_degree must be in [1, 4]"),
+    ("olmc_american_lsm_qmc", lambda: (*_G, 2, 10 ** 9, 10, *_sobol(10), 30, 2, _ST()), "bad construction"),
+    ("olmc_gbm_qmc_paths", lambda: (*_MKT, 2, 10 ** 9, 10, *_sobol(10), 30, 0, (C.c_double * 4)()), "bad construction"),
+    ("olmc_gbm_qmc_paths", lambda: (*_MKT, 0, 10 ** 9, 10, *_sobol(10), 32, 0, (C.c_double * 4)()),
+     "only 30-bit Sobol tables (SciPy's default) are supported"),
+    ("olmc_exercise_boundary_qmc", lambda: (*_G, 0, 10 ** 9, 10, *_sobol(10), 31, (C.c_double * 4)()),
+     "only 30-bit Sobol tables (SciPy's default) are supported"),
+    ("olmc_multi_gpu_european_qmc", lambda: (*_G, 64, 4, *_sobol(4), 16, 0, _ST()), "only 30-bit Sobol tables (SciPy's default) are supported"),
 ]
 
 

@@ -98,6 +98,11 @@ _REFUSALS = [
     (_Q, lambda: (*_PRICE, 6, 0.0, 1, 0, 64, 8, *_sobol(16), 30, 0, None), "null pointer"),
     (_Q, lambda: (*_PRICE, 7, 0.0, 0, 0, 0, 8, *_sobol(16), 30, 0, _ST()), "n_paths must be >= 1"),
     (_Q, lambda: (*_PRICE, 7, 0.0, 0, 1, 1 << 30, 8, *_sobol(16), 30, 0, _ST()), "at most 2**30 Sobol points"),
+    # two faults at once: the model, the payoff, then the Sobol call
+    (_Q, lambda: (*_BAD_RHO, 8, 0.0, 2, 0, 64, 8, *_sobol(16), 30, 0, _ST()), "rho must be in [-1, 1]"),
+    (_Q, lambda: (*_PRICE, 8, 0.0, 2, 0, 64, 8, *_sobol(16), 30, 0, _ST()), "bad payoff"),
+    (_Q, lambda: (*_PRICE, 2, 0.0, 1, 0, 64, 1025, *_sobol(2), 30, 0, _ST()), "Barrier must be positive"),
+    (_Q, lambda: (*_PRICE, 6, 0.0, 2, 0, 64, 8, *_sobol(16), 29, 0, _ST()), "bad construction"),
 ]
 
 

@@ -213,6 +213,13 @@ _REFUSALS = [
      "path matrix would exceed 64 GB: lower n_paths or n_steps"),
     ("olmc_heston_qmc_paths", lambda: (S, T, R, Q, 2.0, 0.04, 0.3, 1.01, 0.04, 0, 4, 8, *_sobol(16), 30, 1, _out(4, 8), _out(4, 8)),
      "rho must be in [-1, 1]"),
+    # two faults at once: the model before the Sobol call, and inside it construction, bridge cap, steps, tables, bits, points, matrix
+    ("olmc_heston_qmc", lambda: (*_BAD_RHO, 2, 0, 64, 8, *_sobol(16), 30, 0, _ST()), "rho must be in [-1, 1]"),
+    ("olmc_heston_qmc", lambda: (*_PRICE, 0, 0, 64, 10601, *_sobol(2), 32, 0, _ST()), _STEPS),
+    ("olmc_heston_qmc", lambda: (*_PRICE, 2, 0, 64, 10601, *_sobol(2), 30, 0, _ST()), "bad construction"),
+    ("olmc_heston_qmc", lambda: (*_PRICE, 0, 0, 0, 8, *_sobol(16), 32, 0, _ST()), _BITS),
+    ("olmc_heston_qmc_paths", lambda: (*_PATHS, 2, 1 << 30, 10600, *_sobol(2), 30, 1, _out(1, 1), _out(1, 1)), "bad construction"),
+    ("olmc_heston_qmc_paths", lambda: (*_PATHS, 0, 1 << 30, 10600, *_sobol(2), 29, 1, _out(1, 1), _out(1, 1)), _BITS),
 ]
 
 

@@ -231,6 +231,13 @@ _REFUSALS = [
     ("olmc_heston_qmc_greeks_fd", lambda: (*_GREEKS, 1.5, 0, 64, 4, *_sobol(8), 30, 0, 1, (C.c_double * 9)(), None), "rho must be in [-1, 1]"),
     ("olmc_heston_qmc_greeks_fd", lambda: (*_GREEKS, -0.7, 1, 64, 1025, *_sobol(1), 30, 0, 1, (C.c_double * 9)(), None),
      "the Brownian-bridge construction takes at most OLMC_QMC_BRIDGE_MAX_STEPS (1024) dates"),
+    # two faults at once: the scenario list before the Sobol call
+    ("olmc_heston_qmc_scenarios", lambda: (*_sc(scenario(rho=-1.5)), 2, 0, 64, 4, *_sobol(8), 30, 0, _out()), "rho must be in [-1, 1]"),
+    ("olmc_heston_qmc_scenarios", lambda: (*_sc(*_SEVEN), 2, 0, 64, 4, *_sobol(8), 32, 0, _out()),
+     "more than OLMC_HESTON_MAX_RECURSIONS distinct (T, kappa, theta, sigma_v, rho, v0)"),
+    ("olmc_heston_qmc_scenarios", lambda: (*_sc(), 2, 0, 64, 4, *_sobol(8), 32, 0, _out()), "bad construction"),
+    ("olmc_heston_qmc_greeks_fd", lambda: (S, K, 0.0, R, 0.2, Q, 1, 2.0, 0.04, 0.3, -0.7, 3, 64, 4, *_sobol(8), 30, 0, 1, (C.c_double * 9)(), None),
+     "T must be > 0"),
 ]
 
 

@@ -262,6 +262,14 @@ for _product, _names in (("autocallable", NAMES[:2]), ("cliquet", NAMES[2:])):
          "the Brownian-bridge construction takes at most OLMC_QMC_BRIDGE_MAX_STEPS (1024) dates"),
         (_names[1], _qmc(_product, n_steps=10601, tables=False), "n_steps must be in [1, 10600]: a step takes two of the 21201 Sobol dimensions"),
     ]
+# two or three faults at once: the scheme and its model, QE's construction, the Sobol call, then the product's count
+for _product, _names in (("autocallable", NAMES[:2]), ("cliquet", NAMES[2:])):
+    _REFUSALS += [
+        (_names[1], _qmc(_product, scheme=1, construction=1, bits=32), _BRIDGE),
+        (_names[1], _qmc(_product, scheme=2, construction=2), _SCHEME),
+        (_names[1], _qmc(_product, construction=2, count=0), "bad construction"),
+        (_names[1], _qmc(_product, bits=32, count=13), "only 30-bit Sobol tables (SciPy's default) are supported"),
+    ]
 
 
 @pytest.mark.parametrize("name,args,message", _REFUSALS, ids=[f"{n}-{i}" for i, (n, _a, _m) in enumerate(_REFUSALS)])

@@ -272,6 +272,11 @@ _REFUSALS = [
      "the number of cells must be in [1, OLMC_MAX_BATCH]"),
     ("olmc_heston_qmc_surface", lambda: (*_HEAD, -0.7, 0.04, *_cells(steps=(5, 1)), 1, 0, 64, 4, *_sobol(8), 30, 0, _out()),
      "a cell's step must be in [1, n_steps]"),
+    # two faults at once: the model, then the Sobol call, then the cells
+    ("olmc_heston_qmc_surface", lambda: (*_HEAD, -0.7, 0.04, *_cells()[:2], 0, 2, 0, 64, 4, *_sobol(8), 30, 0, _out()), "bad construction"),
+    ("olmc_heston_qmc_surface", lambda: (*_HEAD, -1.5, 0.04, *_cells()[:2], 0, 2, 0, 64, 4, *_sobol(8), 30, 0, _out()), "rho must be in [-1, 1]"),
+    ("olmc_heston_qmc_surface", lambda: (*_HEAD, -0.7, 0.04, *_cells()[:2], 17, 0, 0, 64, 4, *_sobol(8), 32, 0, _out()),
+     "only 30-bit Sobol tables (SciPy's default) are supported"),
 ]
 
 

@@ -130,6 +130,21 @@ def test_every_refusal_answers_its_message_before_any_device_work(library, entry
                                                              sts), "a cell's step must be in [1, n_steps]")
     if entry == "olvq_paths":
         refused(library, call(n=1 << 30, steps=8), "path matrix would exceed 64 GB")
+    # two faults at once: the table, the payoff, the Sobol call (construction, bridge cap, tables, bits, points), the cells, the matrix
+    one_node, keep_one = surface(n_x=1)
+    refused(library, call(s=C.byref(one_node), construction=2), "n_x must be in [2, 256]")
+    refused(library, call(construction=2, bits=32), "bad construction")
+    refused(library, call(bits=32, n=0), "only 30-bit Sobol tables (SciPy's default) are supported")
+    if entry == "olvq_price":
+        refused(library, call(payoff=9, construction=2), "bad payoff")
+        refused(library, call(s=C.byref(one_node), payoff=9), "n_x must be in [2, 256]")
+    if entry == "olvq_surface_prices":
+        refused(library, call(bits=32, k=17), "only 30-bit Sobol tables (SciPy's default) are supported")
+        refused(library, call(construction=2, k=0), "bad construction")
+    if entry == "olvq_paths":
+        refused(library, call(construction=2, n=1 << 30, steps=8), "bad construction")
+        refused(library, call(bits=32, n=1 << 30, steps=8), "only 30-bit Sobol tables (SciPy's default) are supported")
+    assert keep_one is not None
     assert keep is not None and keep_bad is not None
 
 

@@ -163,6 +163,11 @@ _REFUSALS = [
     ("olmc_cliquet_qmc", lambda: (*_CLIQ, 4, 0, 0, 64, 8, *_sobol(8), 30, 0, None), "null pointer"),
     ("olmc_cliquet_qmc", lambda: (*_CLIQ, 4, -1, 0, 64, 8, *_sobol(8), 30, 0, _ST()), "bad construction"),
     ("olmc_cliquet_qmc", lambda: (*_CLIQ, 4, 0, 0, 64, 0, *_sobol(1), 30, 0, _ST()), "dims must be in [1, 21201]"),
+    # two faults at once: the Sobol call's checks come before the product's count
+    ("olmc_autocallable_qmc", lambda: (*_AUTO, 0, 2, 0, 64, 8, *_sobol(8), 30, 0, _ST()), "bad construction"),
+    ("olmc_autocallable_qmc", lambda: (*_AUTO, 9, 0, 0, 64, 8, *_sobol(8), 32, 0, _ST()), _BITS),
+    ("olmc_cliquet_qmc", lambda: (*_CLIQ, 0, 0, 0, 0, 8, *_sobol(8), 30, 0, _ST()), "n_paths must be >= 1"),
+    ("olmc_cliquet_qmc", lambda: (*_CLIQ, 9, 3, 0, 64, 8, *_sobol(8), 30, 0, None), "null pointer"),
 ]
 
 
