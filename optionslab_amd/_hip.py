@@ -57,6 +57,11 @@ class LvSurface(C.Structure):
                 ("t_hi", C.c_double)]
 
 
+class JdModel(C.Structure):
+    """oljd_model (include/olmc_jump.h): Merton (a1, a2) = (mu_j, sigma_j), Kou (a1, a2, a3) = (p, eta1, eta2)."""
+    _fields_ = [("model", C.c_int32), ("pad", C.c_int32), ("lambda_j", C.c_double), ("a1", C.c_double), ("a2", C.c_double), ("a3", C.c_double)]
+
+
 _D, _I, _I32, _I64, _U64T, _P = C.c_double, C.c_int, C.c_int32, C.c_int64, C.c_uint64, C.c_void_p
 _byref = C.byref
 _Out9 = C.c_double * 9
@@ -171,6 +176,18 @@ LVQ_PROTOTYPES = {
                                          _I32, _I, C.POINTER(Stats)]),
 }
 
+# and for include/olmc_jump.h (prefix oljd_)
+JD_EUROPEAN = 8
+_JDM = C.POINTER(JdModel)
+_JD_RANGE = [_I64, _I64, _I32, _U64T, _I, C.POINTER(Stats)]          # path_offset, n_local, n_steps, seed, antithetic, out
+JD_PROTOTYPES = {
+    "oljd_price": (_I, _SIX + [_I, _JDM, _I, _D] + _JD_RANGE),
+    "oljd_surface_prices": (_I, [_D] * 5 + [_I, _JDM, C.POINTER(_D), C.POINTER(_I32), _I32] + _JD_RANGE),
+    "oljd_autocallable": (_I, [_D] * 5 + [_JDM] + [_D] * 4 + [_I32] + _JD_RANGE),
+    "oljd_cliquet": (_I, [_D] * 5 + [_JDM] + [_D] * 4 + [_I32] + _JD_RANGE),
+    "oljd_paths": (_I, [_D] * 5 + [_JDM, _I64, _I32, _U64T, _I, _I, C.POINTER(_D)]),
+}
+
 _lock = threading.Lock()
 _lib: Optional[C.CDLL] = None
 _initialised = False
@@ -213,7 +230,8 @@ def load_library() -> C.CDLL:
                 lib = C.CDLL(LIBRARY_PATH)
             except OSError as e:
                 raise AccelerationError(f"cannot load {LIBRARY_PATH}: {e}", backend="hip") from e
-            for name, (res, args) in list(PROTOTYPES.items()) + list(LV_PROTOTYPES.items()) + list(LVQ_PROTOTYPES.items()):
+            for name, (res, args) in (list(PROTOTYPES.items()) + list(LV_PROTOTYPES.items()) + list(LVQ_PROTOTYPES.items())
+                                      + list(JD_PROTOTYPES.items())):
                 try:
                     fn = getattr(lib, name)
                 except AttributeError:
@@ -849,6 +867,60 @@ def lvq_surface_prices(S, T, r, q, is_call: bool, table, strikes, steps, n_point
     _check(lib().olvq_surface_prices(S, T, r, q, int(is_call), C.byref(surf), pk, ps, len(strikes), QMC_BRIDGE if bridge else QMC_SEQUENTIAL,
                                      int(point_offset), int(n_points), int(sv.shape[0]), psv, psh, int(sv.shape[1]), int(antithetic), out))
     return list(out)[:len(strikes)]
+
+
+def jd_model(kou: bool, lambda_j, a1, a2, a3=0.0) -> JdModel:
+    return JdModel(int(bool(kou)), 0, float(lambda_j), float(a1), float(a2), float(a3))
+
+
+def jd_price(S, K, T, r, sigma, q, is_call: bool, model, payoff: int, barrier: float, n_paths: int, n_steps: int, seed: int,
+             antithetic: bool = False, path_offset: int = 0) -> Stats:
+    """One payoff (BARRIER_KINDS value, LOOKBACK_*, PATH_ASIAN_* or JD_EUROPEAN) on jump_paths' paths, one launch (oljd_price);
+    `model` = (kou, lambda_j, a1, a2, a3) as jump_diffusion takes them."""
+    m = jd_model(*model)
+    out = Stats()
+    _check(lib().oljd_price(S, K, T, r, sigma, q, int(is_call), C.byref(m), int(payoff), float(barrier), int(path_offset), int(n_paths),
+                            int(n_steps), seed64(seed), int(antithetic), C.byref(out)))
+    return out
+
+
+def jd_surface_prices(S, T, r, sigma, q, is_call: bool, model, strikes, steps, n_paths: int, n_steps: int, seed: int, antithetic: bool = False,
+                      path_offset: int = 0) -> List[Stats]:
+    """European options at the cells (strikes[i], steps[i]) on jd_price's paths, one launch (oljd_surface_prices): at most 16 cells."""
+    m = jd_model(*model)
+    strikes, steps, pk, ps, out = _surface_cells(strikes, steps)
+    _check(lib().oljd_surface_prices(S, T, r, sigma, q, int(is_call), C.byref(m), pk, ps, len(strikes), int(path_offset), int(n_paths),
+                                     int(n_steps), seed64(seed), int(antithetic), out))
+    return list(out)[:len(strikes)]
+
+
+def jd_autocallable(S, T, r, sigma, q, model, autocall_barrier, coupon_barrier, coupon_rate, ki_barrier, observation_freq: int, n_paths: int,
+                    n_steps: int, seed: int, antithetic: bool = False, path_offset: int = 0) -> Stats:
+    """autocallable()'s contract on jd_price's paths, one launch (oljd_autocallable)."""
+    m = jd_model(*model)
+    out = Stats()
+    _check(lib().oljd_autocallable(S, T, r, sigma, q, C.byref(m), autocall_barrier, coupon_barrier, coupon_rate, ki_barrier, int(observation_freq),
+                                   int(path_offset), int(n_paths), int(n_steps), seed64(seed), int(antithetic), C.byref(out)))
+    return out
+
+
+def jd_cliquet(S, T, r, sigma, q, model, local_cap, local_floor, global_cap, global_floor, n_periods: int, n_paths: int, n_steps: int, seed: int,
+               antithetic: bool = False, path_offset: int = 0) -> Stats:
+    """cliquet()'s contract on jd_price's paths, one launch (oljd_cliquet)."""
+    m = jd_model(*model)
+    out = Stats()
+    _check(lib().oljd_cliquet(S, T, r, sigma, q, C.byref(m), local_cap, local_floor, global_cap, global_floor, int(n_periods), int(path_offset),
+                              int(n_paths), int(n_steps), seed64(seed), int(antithetic), C.byref(out)))
+    return out
+
+
+def jd_paths(S, T, r, sigma, q, model, n_paths: int, n_steps: int, seed: int, mirror: bool = False, path_major: bool = False) -> np.ndarray:
+    """The spot matrix of one leg of jd_price's paths (oljd_paths), in gbm_paths' layouts: mirror=False is jump_paths' matrix."""
+    m = jd_model(*model)
+    out = _path_matrix(n_paths, n_steps, path_major)
+    _check(lib().oljd_paths(S, T, r, sigma, q, C.byref(m), int(n_paths), int(n_steps), seed64(seed), int(bool(mirror)), int(path_major),
+                            out.ctypes.data_as(C.POINTER(C.c_double))))
+    return out
 
 
 def _scenarios(scenarios):

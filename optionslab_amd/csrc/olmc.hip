@@ -8,9 +8,11 @@
 #include "olmc.h"
 #include "olmc_local_vol.h"
 #include "olmc_local_vol_qmc.h"
+#include "olmc_jump.h"
 #include "olmc_kernels.h"
 #include "olmc_local_vol_kernels.h"
 #include "olmc_local_vol_qmc_kernels.h"
+#include "olmc_jump_kernels.h"
 #include "olmc_job_board.h"
 #include "olmc_device_mem.h"
 
@@ -3224,6 +3226,146 @@ extern "C" int olmc_heston_cliquet_qmc(double S, double T, double r, double q, d
     const CliquetContract cc = make_cliquet(S, T, r, 0.0, q, local_cap, local_floor, global_cap, global_floor, n_periods, n_steps);
     const bool bad = cliquet_poisoned(S, T, r, 0.0, q, local_cap, local_floor, global_cap, global_floor) || m.nan();
     return run_heston_qmc_product<HestonCliquet>(S, T, r, q, m, scheme, cc, r, bad, *call, out);
+}
+
+// ====================================================== path-dependent payoffs under jump diffusion ====
+// include/olmc_jump.h: the payoffs of olmc_heston_path_payoff, a surface of Europeans, the autocallable and the cliquet on
+// olmc_jump_paths' paths (olmc_jump_kernels.h).  The model's checks are make_jump's, the contracts' those of the Heston entry points of
+// the same payoffs; every check comes before the lease.
+namespace {
+// The checked model as the kernels' contract (K and is_call are read by the surface kernel's sign only).
+int jd_contract(double S, double T, double r, double sigma, double q, int is_call, const oljd_model* m, int32_t n_steps, JumpContract* jc) {
+    if (!m) return fail(OLMC_ERR_ARG, "null pointer");
+    // a NaN intensity is a NaN input (jd_poisoned: NaN results), not a negative one: make_jump's sign check sees 0 in its place
+    return make_jump(S, 0.0, T, r, sigma, q, is_call, m->model, std::isnan(m->lambda_j) ? 0.0 : m->lambda_j, m->a1, m->a2, m->a3, n_steps, jc);
+}
+
+bool jd_poisoned(double S, double K, double T, double r, double sigma, double q, const oljd_model* m) {
+    return poisoned(S, K, T, r, sigma, q) || std::isnan(m->lambda_j + m->a1 + m->a2 + m->a3);
+}
+
+int jd_payoff_check(int payoff, double barrier) {
+    if (payoff < OLMC_BARRIER_UP_OUT || payoff > OLJD_EUROPEAN) return fail(OLMC_ERR_ARG, "bad payoff");
+    if (heston_path_is_barrier(payoff) && barrier <= 0.0) return fail(OLMC_ERR_ARG, "Barrier must be positive");
+    return OLMC_OK;
+}
+
+// f(integral_constant<int, family>) for the family of a checked payoff code, OLJD_EUROPEAN included.
+template <typename F>
+void with_jd_family(int payoff, F&& f) {
+    if (payoff == OLJD_EUROPEAN) f(std::integral_constant<int, kJumpEuropean>{});
+    else with_heston_path_family(payoff, f);
+}
+
+template <template <bool> class Product>
+int run_jd_product(const JumpContract& jc, const typename Product<false>::Contract& pc, double r_for_discount, double T, bool bad, int64_t path_offset,
+                   int64_t n_local, int32_t n_steps, uint64_t seed, int antithetic, olmc_stats* out) {
+    return run_structured(path_offset, n_local, n_steps, seed, antithetic, r_for_discount, T, bad, out,
+                          [&](int32_t grid, hipStream_t st, const EventPair* timed, const PathRange& pr, const ReduceWs& ws) {
+                              with_bool(antithetic != 0, [&](auto a) {
+                                  launch_timed(jump_product_kernel<Product, decltype(a)::value>, dim3(grid), dim3(kBlock), st, timed, pr, jc, pc, ws);
+                              });
+                          });
+}
+}  // namespace
+
+extern "C" int oljd_price(double S, double K, double T, double r, double sigma, double q, int is_call, const oljd_model* model, int payoff,
+                          double barrier, int64_t path_offset, int64_t n_local, int32_t n_steps, uint64_t seed, int antithetic, olmc_stats* out) {
+    if (!out) return fail(OLMC_ERR_ARG, "null pointer");
+    JumpContract jc;
+    int rc = jd_contract(S, T, r, sigma, q, is_call, model, n_steps, &jc);
+    if (rc) return rc;
+    rc = jd_payoff_check(payoff, barrier);
+    if (rc) return rc;
+    const ExtremaContract ec = heston_path_contract(S, K, is_call, payoff == OLJD_EUROPEAN ? OLMC_PATH_ASIAN_ARITHMETIC : payoff, barrier);
+    const bool bad = jd_poisoned(S, K, T, r, sigma, q, model) || (heston_path_is_barrier(payoff) && std::isnan(barrier));
+    const double inv_steps = 1.0 / n_steps;                  // n_steps < 1 was refused by make_jump
+    return run_structured(path_offset, n_local, n_steps, seed, antithetic, r, T, bad, out,
+                          [&](int32_t grid, hipStream_t st, const EventPair* timed, const PathRange& pr, const ReduceWs& ws) {
+                              with_jd_family(payoff, [&](auto f) {
+                                  with_bool(antithetic != 0, [&](auto a) {
+                                      launch_timed(jump_path_kernel<f, a>, dim3(grid), dim3(kBlock), st, timed, pr, jc, ec, inv_steps, ws);
+                                  });
+                              });
+                          });
+}
+
+extern "C" int oljd_surface_prices(double S, double T, double r, double sigma, double q, int is_call, const oljd_model* model, const double* strikes,
+                                   const int32_t* steps, int32_t k, int64_t path_offset, int64_t n_local, int32_t n_steps, uint64_t seed,
+                                   int antithetic, olmc_stats* out) {
+    if (!strikes || !steps || !out) return fail(OLMC_ERR_ARG, "null pointer");
+    JumpContract jc;
+    int rc = jd_contract(S, T, r, sigma, q, is_call, model, n_steps, &jc);
+    if (rc) return rc;
+    rc = check_paths(path_offset, n_local, n_steps);
+    if (rc) return rc;
+    SurfaceOrder so;
+    rc = surface_cells(strikes, steps, k, n_steps, &so);
+    if (rc) return rc;
+    const bool bad = jd_poisoned(S, 0.0, T, r, sigma, q, model);
+    CtxLease lease;
+    rc = ctx_lease(&lease);
+    if (rc) return rc;
+    DeviceCtx* const c = lease.c;
+    const PathRange pr = make_range(path_offset, n_local, n_steps, seed);
+    rc = launch_reduce(c, c->stream, c->d_result, -1.0, 2 * kSurfaceCells, grid_for(n_local),
+                       [&](int32_t grid, hipStream_t st, const EventPair* timed, const ReduceWs& ws) {
+                           with_bool(antithetic != 0, [&](auto a) {
+                               launch_timed(jump_surface_kernel<a>, dim3(grid), dim3(kBlock), st, timed, pr, jc, so.cells, ws);
+                           });
+                       });
+    if (rc) return rc;
+    surface_finish(c->h_result, so, strikes, steps, k, n_local * (antithetic ? 2 : 1), r, T / n_steps, bad, out);
+    return OLMC_OK;
+}
+
+extern "C" int oljd_autocallable(double S, double T, double r, double sigma, double q, const oljd_model* model, double autocall_barrier,
+                                 double coupon_barrier, double coupon_rate, double ki_barrier, int32_t observation_freq, int64_t path_offset,
+                                 int64_t n_local, int32_t n_steps, uint64_t seed, int antithetic, olmc_stats* out) {
+    if (!out) return fail(OLMC_ERR_ARG, "null pointer");
+    JumpContract jc;
+    int rc = jd_contract(S, T, r, sigma, q, 1, model, n_steps, &jc);
+    if (rc) return rc;
+    rc = autocall_check(observation_freq, n_steps);
+    if (rc) return rc;
+    const AutocallSetup a = make_autocall(S, T, r, 0.0, q, autocall_barrier, coupon_barrier, coupon_rate, ki_barrier, observation_freq, n_steps);
+    // payoffs are already discounted path by path, as olmc_autocallable's: no outer discount
+    return run_jd_product<HestonAutocall>(jc, a.ac, 0.0, T, a.bad || jd_poisoned(S, 1.0, T, r, sigma, q, model), path_offset, n_local, n_steps, seed,
+                                          antithetic, out);
+}
+
+extern "C" int oljd_cliquet(double S, double T, double r, double sigma, double q, const oljd_model* model, double local_cap, double local_floor,
+                            double global_cap, double global_floor, int32_t n_periods, int64_t path_offset, int64_t n_local, int32_t n_steps,
+                            uint64_t seed, int antithetic, olmc_stats* out) {
+    if (!out) return fail(OLMC_ERR_ARG, "null pointer");
+    JumpContract jc;
+    int rc = jd_contract(S, T, r, sigma, q, 1, model, n_steps, &jc);
+    if (rc) return rc;
+    rc = cliquet_check(n_periods, n_steps);
+    if (rc) return rc;
+    const CliquetContract cc = make_cliquet(S, T, r, 0.0, q, local_cap, local_floor, global_cap, global_floor, n_periods, n_steps);
+    const bool bad = cliquet_poisoned(S, T, r, sigma, q, local_cap, local_floor, global_cap, global_floor) || jd_poisoned(S, 1.0, T, r, sigma, q, model);
+    return run_jd_product<HestonCliquet>(jc, cc, r, T, bad, path_offset, n_local, n_steps, seed, antithetic, out);
+}
+
+extern "C" int oljd_paths(double S, double T, double r, double sigma, double q, const oljd_model* model, int64_t n_paths, int32_t n_steps,
+                          uint64_t seed, int mirror, int path_major, double* out_host) {
+    if (!out_host) return fail(OLMC_ERR_ARG, "null pointer");
+    JumpContract jc;
+    int rc = jd_contract(S, T, r, sigma, q, 1, model, n_steps, &jc);
+    if (rc) return rc;
+    const double bytes = 8.0 * static_cast<double>(n_paths) * (n_steps + 1.0);
+    CtxLease lease;
+    rc = matrix_prologue(n_paths, n_steps, bytes, "path matrix would exceed 64 GB", &lease);
+    if (rc) return rc;
+    DeviceCtx* const c = lease.c;
+    const PathRange pr = make_range(0, n_paths, n_steps, seed);
+    with_bool(path_major != 0, [&](auto pm) {
+        launch_timed(jump_legs_paths_kernel<pm>, dim3(grid_for(n_paths)), dim3(kBlock), c->stream, nullptr, pr, jc, S, static_cast<int32_t>(mirror != 0),
+                     c->bulk.as<double>());
+    });
+    HIP_TRY(hipGetLastError());
+    return copy_to_host(c, out_host, c->bulk.get(), static_cast<size_t>(bytes));
 }
 
 namespace {

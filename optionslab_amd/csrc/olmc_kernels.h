@@ -2382,9 +2382,10 @@ struct JumpContract {
 
 __device__ __forceinline__ double unit_open64(uint32_t x) { return (static_cast<double>(x) + 0.5) * 2.3283064365386963e-10; }
 
-// The jump part of step t of one path, given its Poisson uniform: the count by inversion, then the sizes.
-__device__ __forceinline__ void jump_sizes(const PathRange& pr, const JumpContract& c, uint32_t g_lo, uint32_t g_hi, int32_t t,
-                                           double u, double& ls) {
+// The jump part of step t of one path for LEGS legs, given its Poisson uniform: the count by inversion, then the size terms, each drawn
+// ONCE and added to every leg, leg 0 first (olmc_jump_kernels.h "the mirror leg").  words(block, tag) is the path's Philox block.
+template <int LEGS, typename Words>
+__device__ __forceinline__ void jump_sizes(const JumpContract& c, Words words, int32_t t, double u, double (&ls)[2]) {
     if (u < c.p0) return;                              // no jump (almost always)
     int32_t n = 1;
     double pk = c.p0 * c.lam_dt, cdf = c.p0 + pk;
@@ -2394,45 +2395,53 @@ __device__ __forceinline__ void jump_sizes(const PathRange& pr, const JumpContra
         cdf += pk;
     }
     if (!c.kou) {
-        const Words4 k = philox4x32_10(g_lo, g_hi, static_cast<uint32_t>(t), kTagJumpSize, pr.key0, pr.key1);
+        const Words4 k = words(static_cast<uint32_t>(t), kTagJumpSize);
         float z_jump, unused;
         box_muller_raw(k.x0, k.x1, z_jump, unused);
-        ls += n * c.mu_j + c.sigma_j * sqrt(static_cast<double>(n)) * (kZScale * static_cast<double>(z_jump));
+        const double term = n * c.mu_j + c.sigma_j * sqrt(static_cast<double>(n)) * (kZScale * static_cast<double>(z_jump));
+#pragma unroll
+        for (int l = 0; l < LEGS; ++l) ls[l] += term;
     } else {
         for (int32_t j = 0; j < n; ++j) {
-            const Words4 k = philox4x32_10(g_lo, g_hi, static_cast<uint32_t>(t), kTagJumpSize + static_cast<uint32_t>(j >> 1),
-                                           pr.key0, pr.key1);
+            const Words4 k = words(static_cast<uint32_t>(t), kTagJumpSize + static_cast<uint32_t>(j >> 1));
             const double ud = unit_open64((j & 1) ? k.x2 : k.x0), um = unit_open64((j & 1) ? k.x3 : k.x1);
-            ls += ud < c.kou_p ? -log(um) * c.inv_eta1 : log(um) * c.inv_eta2;
+            const double term = ud < c.kou_p ? -log(um) * c.inv_eta1 : log(um) * c.inv_eta2;
+#pragma unroll
+            for (int l = 0; l < LEGS; ++l) ls[l] += term;
         }
     }
 }
 
-// Steps 2b and 2b+1 of one path (the second only if it exists); `after(t, ls)` sees ln S after each step.
-template <typename After>
-__device__ __forceinline__ void jump_block(const PathRange& pr, const JumpContract& c, double vol, uint32_t g_lo, uint32_t g_hi,
-                                           int32_t b, double& ls, After after) {
-    const Words4 w = philox4x32_10(g_lo, g_hi, static_cast<uint32_t>(b), kTagJump, pr.key0, pr.key1);
-    float z0, z1;
-    box_muller_raw(w.x0, w.x1, z0, z1);
-    ls += __builtin_fma(vol, static_cast<double>(z0), c.drift);
-    jump_sizes(pr, c, g_lo, g_hi, 2 * b, unit_open64(w.x2), ls);
-    after(2 * b, ls);
-    if (2 * b + 1 < pr.n_steps) {
-        ls += __builtin_fma(vol, static_cast<double>(z1), c.drift);
-        jump_sizes(pr, c, g_lo, g_hi, 2 * b + 1, unit_open64(w.x3), ls);
-        after(2 * b + 1, ls);
+// Steps 0 .. last - 1 of one path for LEGS legs (leg 1 takes -z: vol is in units of RAW normals); `after(t)` sees ls after step t.
+template <int LEGS, typename Words, typename After>
+__device__ __forceinline__ void jump_walk(const JumpContract& c, Words words, double vol, int32_t last, double (&ls)[2], After after) {
+    const int32_t blocks = (last + 1) >> 1;
+    for (int32_t b = 0; b < blocks; ++b) {
+        const Words4 w = words(static_cast<uint32_t>(b), kTagJump);
+        float z[2];
+        box_muller_raw(w.x0, w.x1, z[0], z[1]);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int32_t t = 2 * b + h;
+            if (t < last) {
+                const double zd = static_cast<double>(z[h]);
+                ls[0] += __builtin_fma(vol, zd, c.drift);
+                if constexpr (LEGS == 2) ls[1] += __builtin_fma(-vol, zd, c.drift);
+                jump_sizes<LEGS>(c, words, t, unit_open64(h ? w.x3 : w.x2), ls);
+                after(t);
+            }
+        }
     }
 }
 
 __global__ __launch_bounds__(kBlock) void jump_kernel(PathRange pr, JumpContract c, ReduceWs ws) {
     double acc[2] = {0.0, 0.0};
     const double vol = c.vol * kZScale;
-    const int32_t blocks = (pr.n_steps + 1) >> 1;
     for_each_path(pr, [&](int64_t, uint32_t g_lo, uint32_t g_hi) {
-        double ls = c.log_s0;
-        for (int32_t b = 0; b < blocks; ++b) jump_block(pr, c, vol, g_lo, g_hi, b, ls, [](int32_t, double) {});
-        const double x = fmax(c.sign * (exp(ls) - c.strike), 0.0);
+        double ls[2] = {c.log_s0, 0.0};
+        jump_walk<1>(c, [&](uint32_t block, uint32_t tag) { return philox4x32_10(g_lo, g_hi, block, tag, pr.key0, pr.key1); }, vol, pr.n_steps, ls,
+                     [](int32_t) {});
+        const double x = fmax(c.sign * (exp(ls[0]) - c.strike), 0.0);
         acc[0] += x; acc[1] += x * x;
     });
     block_then_grid_reduce<2>(acc, ws);
@@ -2443,13 +2452,11 @@ __global__ __launch_bounds__(kBlock) void jump_kernel(PathRange pr, JumpContract
 template <bool PATH_MAJOR>
 __global__ __launch_bounds__(kBlock) void jump_paths_kernel(PathRange pr, JumpContract c, double s_first, double* __restrict__ out) {
     const double vol = c.vol * kZScale;
-    const int32_t blocks = (pr.n_steps + 1) >> 1;
     for_each_path(pr, [&](int64_t i, uint32_t g_lo, uint32_t g_hi) {
-        double ls = c.log_s0;
+        double ls[2] = {c.log_s0, 0.0};
         out[path_at<PATH_MAJOR>(i, 0, pr.count, pr.n_steps)] = s_first;
-        for (int32_t b = 0; b < blocks; ++b)
-            jump_block(pr, c, vol, g_lo, g_hi, b, ls,
-                       [&](int32_t t, double l) { out[path_at<PATH_MAJOR>(i, t + 1, pr.count, pr.n_steps)] = exp(l); });
+        jump_walk<1>(c, [&](uint32_t block, uint32_t tag) { return philox4x32_10(g_lo, g_hi, block, tag, pr.key0, pr.key1); }, vol, pr.n_steps, ls,
+                     [&](int32_t t) { out[path_at<PATH_MAJOR>(i, t + 1, pr.count, pr.n_steps)] = exp(ls[0]); });
     });
 }
 
