@@ -1432,29 +1432,43 @@ int matrix_prologue(int64_t n_paths, int32_t n_steps, double bytes, const char* 
     if (rc || !reserve) return rc;
     return bulk_reserve(lease->c, static_cast<size_t>(bytes));
 }
+
+// A family without per-context state to set up between the lease and the launch.
+int no_setup(DeviceCtx*) { return OLMC_OK; }
+
+// One (n_steps + 1) x n_paths matrix of Philox paths [0, n_paths) to the host, after the caller's null and model checks: the prologue,
+// `setup(c)` (the family's per-context hook: the local-volatility table), launch(c, grid, range, the matrix on the device), the copy.
+template <typename Setup, typename Launch>
+int run_philox_matrix(int64_t n_paths, int32_t n_steps, uint64_t seed, double* out_host, Setup setup, Launch launch) {
+    const double bytes = 8.0 * static_cast<double>(n_paths) * (n_steps + 1.0);
+    CtxLease lease;
+    int rc = matrix_prologue(n_paths, n_steps, bytes, "path matrix would exceed 64 GB", &lease);
+    if (rc) return rc;
+    DeviceCtx* const c = lease.c;
+    rc = setup(c);
+    if (rc) return rc;
+    launch(c, grid_for(n_paths), make_range(0, n_paths, n_steps, seed), c->bulk.as<double>());
+    HIP_TRY(hipGetLastError());
+    return copy_to_host(c, out_host, c->bulk.get(), static_cast<size_t>(bytes));
+}
 }  // namespace
 
 extern "C" int olmc_gbm_paths(double S, double T, double r, double sigma, double q, int64_t n_paths, int32_t n_steps,
                               uint64_t seed, int path_major, double* out_host) {
     if (!out_host) return fail(OLMC_ERR_ARG, "null pointer");
-    const double bytes = 8.0 * static_cast<double>(n_paths) * (n_steps + 1.0);
-    CtxLease lease;
-    const int rc = matrix_prologue(n_paths, n_steps, bytes, "path matrix would exceed 64 GB", &lease);
-    if (rc) return rc;
-    DeviceCtx* const c = lease.c;
-    LsmContract lc{};
-    const GbmStep g = gbm_step(T, n_steps, r, q, sigma);          // gbm_numpy.py:106-108
-    lc.log_s0 = std::log(S);
-    lc.s_first = S;
-    lc.drift = g.drift;
-    lc.vol = g.vol;
-    lc.n_steps = n_steps;
-    const PathRange pr = make_range(0, n_paths, n_steps, seed);
-    with_bool(path_major != 0, [&](auto pm) {
-        launch_timed(lsm_paths_kernel<pm>, dim3(grid_for(n_paths)), dim3(kBlock), c->stream, nullptr, pr, lc, c->bulk.as<double>());
+    return run_philox_matrix(n_paths, n_steps, seed, out_host, no_setup,
+                             [&](DeviceCtx* c, int32_t grid, const PathRange& pr, double* d_paths) {
+        LsmContract lc{};
+        const GbmStep g = gbm_step(T, n_steps, r, q, sigma);          // gbm_numpy.py:106-108
+        lc.log_s0 = std::log(S);
+        lc.s_first = S;
+        lc.drift = g.drift;
+        lc.vol = g.vol;
+        lc.n_steps = n_steps;
+        with_bool(path_major != 0, [&](auto pm) {
+            launch_timed(lsm_paths_kernel<pm>, dim3(grid), dim3(kBlock), c->stream, nullptr, pr, lc, d_paths);
+        });
     });
-    HIP_TRY(hipGetLastError());
-    return copy_to_host(c, out_host, c->bulk.get(), static_cast<size_t>(bytes));
 }
 
 extern "C" int olmc_exercise_boundary(double S, double K, double T, double r, double sigma, double q, int is_call,
@@ -1832,19 +1846,14 @@ extern "C" int olmc_jump_paths(double S, double T, double r, double sigma, doubl
                                double* out_host) {
     if (!out_host) return fail(OLMC_ERR_ARG, "null pointer");
     JumpContract jc;
-    int rc = make_jump(S, 0.0, T, r, sigma, q, 1, model, lambda_j, a1, a2, a3, n_steps, &jc);
+    const int rc = make_jump(S, 0.0, T, r, sigma, q, 1, model, lambda_j, a1, a2, a3, n_steps, &jc);
     if (rc) return rc;
-    const double bytes = 8.0 * static_cast<double>(n_paths) * (n_steps + 1.0);
-    CtxLease lease;
-    rc = matrix_prologue(n_paths, n_steps, bytes, "path matrix would exceed 64 GB", &lease);
-    if (rc) return rc;
-    DeviceCtx* const c = lease.c;
-    const PathRange pr = make_range(0, n_paths, n_steps, seed);
-    with_bool(path_major != 0, [&](auto pm) {
-        launch_timed(jump_paths_kernel<pm>, dim3(grid_for(n_paths)), dim3(kBlock), c->stream, nullptr, pr, jc, S, c->bulk.as<double>());
+    return run_philox_matrix(n_paths, n_steps, seed, out_host, no_setup,
+                             [&](DeviceCtx* c, int32_t grid, const PathRange& pr, double* d_paths) {
+        with_bool(path_major != 0, [&](auto pm) {
+            launch_timed(jump_paths_kernel<pm>, dim3(grid), dim3(kBlock), c->stream, nullptr, pr, jc, S, d_paths);
+        });
     });
-    HIP_TRY(hipGetLastError());
-    return copy_to_host(c, out_host, c->bulk.get(), static_cast<size_t>(bytes));
 }
 
 // ======================================================================= QMC ====
@@ -2496,8 +2505,10 @@ extern "C" int olmc_heston_qmc_paths(double S, double T, double r, double q, dou
 // contract, model and range checks, one launch of heston_path_kernel / heston_qmc_path_kernel.
 namespace {
 bool heston_path_is_barrier(int payoff) { return payoff <= OLMC_BARRIER_DOWN_IN; }
-int heston_path_check(int payoff, double barrier) {
-    if (payoff < OLMC_BARRIER_UP_OUT || payoff > OLMC_PATH_ASIAN_GEOMETRIC) return fail(OLMC_ERR_ARG, "bad payoff");
+// The payoff codes of a family end at last_code: OLMC_PATH_ASIAN_GEOMETRIC here, the family's own European (OLLV_EUROPEAN, OLJD_EUROPEAN)
+// where it has one.
+int path_payoff_check(int payoff, double barrier, int last_code) {
+    if (payoff < OLMC_BARRIER_UP_OUT || payoff > last_code) return fail(OLMC_ERR_ARG, "bad payoff");
     if (heston_path_is_barrier(payoff) && barrier <= 0.0) return fail(OLMC_ERR_ARG, "Barrier must be positive");
     return OLMC_OK;
 }
@@ -2529,10 +2540,28 @@ ExtremaContract heston_path_contract(double S, double K, int is_call, int payoff
     return ec;
 }
 
+// The kernels' contract of a checked payoff code and whether a NaN barrier poisons the result.  A code beyond the Heston payoffs is a
+// family's European: like the arithmetic Asian it reads no level and no payoff code.
+struct PathPayoff {
+    ExtremaContract ec;
+    bool nan_barrier;
+};
+PathPayoff path_payoff(double S, double K, int is_call, int payoff, double barrier) {
+    return {heston_path_contract(S, K, is_call, payoff > OLMC_PATH_ASIAN_GEOMETRIC ? OLMC_PATH_ASIAN_ARITHMETIC : payoff, barrier),
+            heston_path_is_barrier(payoff) && std::isnan(barrier)};
+}
+
 // f(integral_constant<int, family>) for the family of a checked payoff code.
 template <typename F>
 void with_heston_path_family(int payoff, F&& f) {
     with_qmc_path_family(heston_path_family(payoff), f);
+}
+
+// The same for a family that has a European at european_code (kPathEuropean).
+template <typename F>
+void with_path_family(int payoff, int european_code, F&& f) {
+    if (payoff == european_code) f(std::integral_constant<int, kPathEuropean>{});
+    else with_heston_path_family(payoff, f);
 }
 }  // namespace
 
@@ -2543,17 +2572,17 @@ extern "C" int olmc_heston_path_payoff(double S, double K, double T, double r, d
     const HestonModel hm{kappa, theta, sigma_v, rho, v0};
     int rc = heston_check(hm);
     if (rc) return rc;
-    rc = heston_path_check(payoff, barrier);
+    rc = path_payoff_check(payoff, barrier, OLMC_PATH_ASIAN_GEOMETRIC);
     if (rc) return rc;
     const HestonContract hc = make_heston(S, K, T, r, q, is_call, hm, n_steps);
-    const ExtremaContract ec = heston_path_contract(S, K, is_call, payoff, barrier);
-    const bool bad = heston_poisoned(S, K, T, r, q, hm) || (heston_path_is_barrier(payoff) && std::isnan(barrier));
+    const PathPayoff pp = path_payoff(S, K, is_call, payoff, barrier);
+    const bool bad = heston_poisoned(S, K, T, r, q, hm) || pp.nan_barrier;
     const double inv_steps = 1.0 / n_steps;                  // n_steps < 1 is refused by run_structured before any launch
     return run_structured(path_offset, n_local, n_steps, seed, antithetic, r, T, bad, out,
                           [&](int32_t grid, hipStream_t st, const EventPair* timed, const PathRange& pr, const ReduceWs& ws) {
                               with_heston_path_family(payoff, [&](auto f) {
                                   with_bool(antithetic != 0, [&](auto a) {
-                                      launch_timed(heston_path_kernel<f, a>, dim3(grid), dim3(kBlock), st, timed, pr, hc, ec, inv_steps, ws);
+                                      launch_timed(heston_path_kernel<f, a>, dim3(grid), dim3(kBlock), st, timed, pr, hc, pp.ec, inv_steps, ws);
                                   });
                               });
                           });
@@ -2567,17 +2596,17 @@ extern "C" int olmc_heston_qmc_path_payoff(double S, double K, double T, double 
     const HestonModel hm{kappa, theta, sigma_v, rho, v0};
     int rc = heston_check(hm);
     if (rc) return rc;
-    rc = heston_path_check(payoff, barrier);
+    rc = path_payoff_check(payoff, barrier, OLMC_PATH_ASIAN_GEOMETRIC);
     if (rc) return rc;
     const auto call = SobolCall::make({construction, point_offset, n_points, n_steps, sv, shift, bits, antithetic}, 2, &rc);
     if (!call) return rc;
     const HestonContract hc = make_heston(S, K, T, r, q, is_call, hm, n_steps);
-    const ExtremaContract ec = heston_path_contract(S, K, is_call, payoff, barrier);
-    const bool bad = heston_poisoned(S, K, T, r, q, hm) || (heston_path_is_barrier(payoff) && std::isnan(barrier));
+    const PathPayoff pp = path_payoff(S, K, is_call, payoff, barrier);
+    const bool bad = heston_poisoned(S, K, T, r, q, hm) || pp.nan_barrier;
     return run_qmc_reduce(*call, 2, heston_qmc_shape, [&](int32_t g, hipStream_t s, const EventPair* timed, const QmcPathLaunch& pl, const ReduceWs& ws) {
         with_heston_path_family(payoff, [&](auto f) {
             with_bridge_anti(pl, [&](auto b, auto m) {
-                launch_timed(heston_qmc_path_kernel<f, b, m>, dim3(g), dim3(kBlock), s, timed, pl.qr, hc, ec, pl.inv_steps, pl.d_sv, pl.d_shift, pl.plan,
+                launch_timed(heston_qmc_path_kernel<f, b, m>, dim3(g), dim3(kBlock), s, timed, pl.qr, hc, pp.ec, pl.inv_steps, pl.d_sv, pl.d_shift, pl.plan,
                              pl.slabs, ws);
             });
         });
@@ -2624,34 +2653,53 @@ void surface_finish(const double* h, const SurfaceOrder& so, const double* strik
     }
 }
 
-// Philox: the cells on paths [path_offset, path_offset + n_local) of the scheme's stream, one launch of its surface kernel.
-template <typename Scheme>
-int run_heston_surface(double S, double T, double r, double q, int is_call, const HestonModel& m, const double* strikes, const int32_t* steps,
-                       int32_t k, int64_t path_offset, int64_t n_local, int32_t n_steps, uint64_t seed, int antithetic, olmc_stats* out) {
-    if (!strikes || !steps || !out) return fail(OLMC_ERR_ARG, "null pointer");
-    int rc = Scheme::check(m);
-    if (rc) return rc;
-    rc = check_paths(path_offset, n_local, n_steps);
+// Philox: the cells on paths [path_offset, path_offset + n_local) of a family's stream, after the caller's null and model checks: the
+// range, the cells, the lease, `setup(c)` (the family's per-context hook: the local-volatility table), one launch of the family's
+// surface kernel -- launch(grid, stream, timed, range, cells, ws) --, the cells' stats.
+struct PhiloxShard {
+    int64_t path_offset, n_local;
+    int32_t n_steps;
+    uint64_t seed;
+    int antithetic;
+};
+template <typename Setup, typename Launch>
+int run_philox_surface(const double* strikes, const int32_t* steps, int32_t k, const PhiloxShard& sh, double r, double T, bool bad, olmc_stats* out,
+                       Setup setup, Launch launch) {
+    int rc = check_paths(sh.path_offset, sh.n_local, sh.n_steps);
     if (rc) return rc;
     SurfaceOrder so;
-    rc = surface_cells(strikes, steps, k, n_steps, &so);
+    rc = surface_cells(strikes, steps, k, sh.n_steps, &so);
     if (rc) return rc;
-    const auto hc = Scheme::make(S, T, r, q, is_call, m, n_steps);
-    const bool bad = heston_poisoned(S, 0.0, T, r, q, m);
     CtxLease lease;
     rc = ctx_lease(&lease);
     if (rc) return rc;
     DeviceCtx* const c = lease.c;
-    const PathRange pr = make_range(path_offset, n_local, n_steps, seed);
-    rc = launch_reduce(c, c->stream, c->d_result, -1.0, 2 * kSurfaceCells, grid_for(n_local),
+    rc = setup(c);
+    if (rc) return rc;
+    const PathRange pr = make_range(sh.path_offset, sh.n_local, sh.n_steps, sh.seed);
+    rc = launch_reduce(c, c->stream, c->d_result, -1.0, 2 * kSurfaceCells, grid_for(sh.n_local),
                        [&](int32_t grid, hipStream_t st, const EventPair* timed, const ReduceWs& ws) {
-                           with_bool(antithetic != 0, [&](auto a) {
-                               launch_timed(Scheme::template surface_kernel<decltype(a)::value>(), dim3(grid), dim3(kBlock), st, timed, pr, hc, so.cells, ws);
-                           });
+                           launch(grid, st, timed, pr, so.cells, ws);
                        });
     if (rc) return rc;
-    surface_finish(c->h_result, so, strikes, steps, k, n_local * (antithetic ? 2 : 1), r, T / n_steps, bad, out);
+    surface_finish(c->h_result, so, strikes, steps, k, sh.n_local * (sh.antithetic ? 2 : 1), r, T / sh.n_steps, bad, out);
     return OLMC_OK;
+}
+
+template <typename Scheme>
+int run_heston_surface(double S, double T, double r, double q, int is_call, const HestonModel& m, const double* strikes, const int32_t* steps,
+                       int32_t k, const PhiloxShard& sh, olmc_stats* out) {
+    if (!strikes || !steps || !out) return fail(OLMC_ERR_ARG, "null pointer");
+    const int rc = Scheme::check(m);
+    if (rc) return rc;
+    return run_philox_surface(strikes, steps, k, sh, r, T, heston_poisoned(S, 0.0, T, r, q, m), out, no_setup,
+                              [&](int32_t grid, hipStream_t st, const EventPair* timed, const PathRange& pr, const HestonSurfaceCells& cells,
+                                  const ReduceWs& ws) {
+        const auto hc = Scheme::make(S, T, r, q, is_call, m, sh.n_steps);
+        with_bool(sh.antithetic != 0, [&](auto a) {
+            launch_timed(Scheme::template surface_kernel<decltype(a)::value>(), dim3(grid), dim3(kBlock), st, timed, pr, hc, cells, ws);
+        });
+    });
 }
 
 // Sobol: the cells on points [point_offset, point_offset + n_points) of the scheme's construction; the shape of a Heston price launch
@@ -2689,8 +2737,8 @@ int run_heston_qmc_surface(double S, double T, double r, double q, int is_call, 
 extern "C" int olmc_heston_surface(double S, double T, double r, double q, int is_call, double kappa, double theta, double sigma_v, double rho,
                                    double v0, const double* strikes, const int32_t* steps, int32_t k, int64_t path_offset, int64_t n_local,
                                    int32_t n_steps, uint64_t seed, int antithetic, olmc_stats* out) {
-    return run_heston_surface<HestonEuler>(S, T, r, q, is_call, {kappa, theta, sigma_v, rho, v0}, strikes, steps, k, path_offset, n_local, n_steps,
-                                           seed, antithetic, out);
+    return run_heston_surface<HestonEuler>(S, T, r, q, is_call, {kappa, theta, sigma_v, rho, v0}, strikes, steps, k,
+                                           {path_offset, n_local, n_steps, seed, antithetic}, out);
 }
 
 extern "C" int olmc_heston_qmc_surface(double S, double T, double r, double q, int is_call, double kappa, double theta, double sigma_v,
@@ -2717,12 +2765,6 @@ int lv_surface_check(const ollv_surface* s) {
         const float a = static_cast<float>(s->vol[k]);          // the value the kernels read
         if (!(std::isfinite(a) && a > 0.0f)) return fail(OLMC_ERR_ARG, "local volatilities must be finite and > 0");
     }
-    return OLMC_OK;
-}
-
-int lv_payoff_check(int payoff, double barrier) {
-    if (payoff < OLMC_BARRIER_UP_OUT || payoff > OLLV_EUROPEAN) return fail(OLMC_ERR_ARG, "bad payoff");
-    if (heston_path_is_barrier(payoff) && barrier <= 0.0) return fail(OLMC_ERR_ARG, "Barrier must be positive");
     return OLMC_OK;
 }
 
@@ -2767,13 +2809,6 @@ void lv_launch(Kernel kernel, const LvModel& m, bool table_in_lds, int32_t grid,
     if (timed) hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, s, timed->start, timed->stop, 0, args...);
     else hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, s, args...);
 }
-
-// f(integral_constant<int, family>) for the family of a checked payoff code, OLLV_EUROPEAN included.
-template <typename F>
-void with_lv_family(int payoff, F&& f) {
-    if (payoff == OLLV_EUROPEAN) f(std::integral_constant<int, kLvEuropean>{});
-    else with_heston_path_family(payoff, f);
-}
 }  // namespace
 
 extern "C" int ollv_price(double S, double K, double T, double r, double q, int is_call, const ollv_surface* surf, int payoff, double barrier,
@@ -2781,12 +2816,12 @@ extern "C" int ollv_price(double S, double K, double T, double r, double q, int 
     if (!out) return fail(OLMC_ERR_ARG, "null pointer");
     int rc = lv_surface_check(surf);
     if (rc) return rc;
-    rc = lv_payoff_check(payoff, barrier);
+    rc = path_payoff_check(payoff, barrier, OLLV_EUROPEAN);
     if (rc) return rc;
     rc = check_paths(path_offset, n_local, n_steps);
     if (rc) return rc;
-    const ExtremaContract ec = heston_path_contract(S, K, is_call, payoff == OLLV_EUROPEAN ? OLMC_PATH_ASIAN_ARITHMETIC : payoff, barrier);
-    const bool bad = lv_poisoned(S, K, T, r, q, surf) || (heston_path_is_barrier(payoff) && std::isnan(barrier));
+    const PathPayoff pp = path_payoff(S, K, is_call, payoff, barrier);
+    const bool bad = lv_poisoned(S, K, T, r, q, surf) || pp.nan_barrier;
     const double inv_steps = 1.0 / n_steps;
     CtxLease lease;
     rc = ctx_lease(&lease);
@@ -2798,8 +2833,8 @@ extern "C" int ollv_price(double S, double K, double T, double r, double q, int 
     const PathRange pr = make_range(path_offset, n_local, n_steps, seed);
     rc = launch_reduce(c, c->stream, c->d_result, -1.0, 2, grid_for(n_local),
                        [&](int32_t grid, hipStream_t st, const EventPair* timed, const ReduceWs& ws) {
-                           with_lv_family(payoff, [&](auto f) {
-                               with_bool(antithetic != 0, [&](auto a) { lv_launch(lv_price_kernel<f, a>, m, !OLMC_LV_ROW_LDS, grid, st, timed, pr, m, ec, inv_steps, ws); });
+                           with_path_family(payoff, OLLV_EUROPEAN, [&](auto f) {
+                               with_bool(antithetic != 0, [&](auto a) { lv_launch(lv_price_kernel<f, a>, m, !OLMC_LV_ROW_LDS, grid, st, timed, pr, m, pp.ec, inv_steps, ws); });
                            });
                        });
     if (rc) return rc;
@@ -2810,50 +2845,29 @@ extern "C" int ollv_price(double S, double K, double T, double r, double q, int 
 extern "C" int ollv_paths(double S, double T, double r, double q, const ollv_surface* surf, int64_t n_paths, int32_t n_steps, uint64_t seed,
                           int path_major, double* out_host) {
     if (!out_host) return fail(OLMC_ERR_ARG, "null pointer");
-    int rc = lv_surface_check(surf);
+    const int rc = lv_surface_check(surf);
     if (rc) return rc;
-    const double bytes = 8.0 * static_cast<double>(n_paths) * (n_steps + 1.0);
-    CtxLease lease;
-    rc = matrix_prologue(n_paths, n_steps, bytes, "path matrix would exceed 64 GB", &lease);
-    if (rc) return rc;
-    DeviceCtx* const c = lease.c;
     LvModel m;
-    rc = lv_upload(c, surf, S, T, r, q, n_steps, &m);
-    if (rc) return rc;
-    const PathRange pr = make_range(0, n_paths, n_steps, seed);
-    with_bool(path_major != 0, [&](auto pm) { lv_launch(lv_paths_kernel<pm>, m, true, grid_for(n_paths), c->stream, nullptr, pr, m, c->bulk.as<double>()); });
-    HIP_TRY(hipGetLastError());
-    return copy_to_host(c, out_host, c->bulk.get(), static_cast<size_t>(bytes));
+    return run_philox_matrix(n_paths, n_steps, seed, out_host, [&](DeviceCtx* c) { return lv_upload(c, surf, S, T, r, q, n_steps, &m); },
+                             [&](DeviceCtx* c, int32_t grid, const PathRange& pr, double* d_paths) {
+        with_bool(path_major != 0, [&](auto pm) { lv_launch(lv_paths_kernel<pm>, m, true, grid, c->stream, nullptr, pr, m, d_paths); });
+    });
 }
 
 extern "C" int ollv_surface_prices(double S, double T, double r, double q, int is_call, const ollv_surface* surf, const double* strikes,
                                    const int32_t* steps, int32_t k, int64_t path_offset, int64_t n_local, int32_t n_steps, uint64_t seed,
                                    int antithetic, olmc_stats* out) {
     if (!strikes || !steps || !out) return fail(OLMC_ERR_ARG, "null pointer");
-    int rc = lv_surface_check(surf);
+    const int rc = lv_surface_check(surf);
     if (rc) return rc;
-    rc = check_paths(path_offset, n_local, n_steps);
-    if (rc) return rc;
-    SurfaceOrder so;
-    rc = surface_cells(strikes, steps, k, n_steps, &so);
-    if (rc) return rc;
-    const bool bad = lv_poisoned(S, 0.0, T, r, q, surf);
-    CtxLease lease;
-    rc = ctx_lease(&lease);
-    if (rc) return rc;
-    DeviceCtx* const c = lease.c;
     LvModel m;
-    rc = lv_upload(c, surf, S, T, r, q, n_steps, &m);
-    if (rc) return rc;
-    const PathRange pr = make_range(path_offset, n_local, n_steps, seed);
     const double sign = is_call ? 1.0 : -1.0;
-    rc = launch_reduce(c, c->stream, c->d_result, -1.0, 2 * kSurfaceCells, grid_for(n_local),
-                       [&](int32_t grid, hipStream_t st, const EventPair* timed, const ReduceWs& ws) {
-                           with_bool(antithetic != 0, [&](auto a) { lv_launch(lv_surface_kernel<a>, m, true, grid, st, timed, pr, m, sign, so.cells, ws); });
-                       });
-    if (rc) return rc;
-    surface_finish(c->h_result, so, strikes, steps, k, n_local * (antithetic ? 2 : 1), r, T / n_steps, bad, out);
-    return OLMC_OK;
+    return run_philox_surface(strikes, steps, k, {path_offset, n_local, n_steps, seed, antithetic}, r, T, lv_poisoned(S, 0.0, T, r, q, surf), out,
+                              [&](DeviceCtx* c) { return lv_upload(c, surf, S, T, r, q, n_steps, &m); },
+                              [&](int32_t grid, hipStream_t st, const EventPair* timed, const PathRange& pr, const HestonSurfaceCells& cells,
+                                  const ReduceWs& ws) {
+        with_bool(antithetic != 0, [&](auto a) { lv_launch(lv_surface_kernel<a>, m, true, grid, st, timed, pr, m, sign, cells, ws); });
+    });
 }
 
 // ====================================================== Dupire local volatility on Sobol paths ====
@@ -2878,18 +2892,18 @@ extern "C" int olvq_price(double S, double K, double T, double r, double q, int 
     if (!out) return fail(OLMC_ERR_ARG, "null pointer");
     int rc = lv_surface_check(surf);
     if (rc) return rc;
-    rc = lv_payoff_check(payoff, barrier);
+    rc = path_payoff_check(payoff, barrier, OLLV_EUROPEAN);
     if (rc) return rc;
     const auto call = SobolCall::make({construction, point_offset, n_points, n_steps, sv, shift, bits, antithetic}, 1, &rc);
     if (!call) return rc;
-    const ExtremaContract ec = heston_path_contract(S, K, is_call, payoff == OLLV_EUROPEAN ? OLMC_PATH_ASIAN_ARITHMETIC : payoff, barrier);
-    const bool bad = lv_poisoned(S, K, T, r, q, surf) || (heston_path_is_barrier(payoff) && std::isnan(barrier));
+    const PathPayoff pp = path_payoff(S, K, is_call, payoff, barrier);
+    const bool bad = lv_poisoned(S, K, T, r, q, surf) || pp.nan_barrier;
     LvModel m;
     return run_qmc_reduce(*call, 2, lv_qmc_shape(surf, S, T, r, q, &m),
                           [&](int32_t g, hipStream_t s, const EventPair* timed, const QmcPathLaunch& pl, const ReduceWs& ws) {
-        with_lv_family(payoff, [&](auto f) {
+        with_path_family(payoff, OLLV_EUROPEAN, [&](auto f) {
             with_bridge_anti(pl, [&](auto b, auto a) {
-                lv_launch(lv_qmc_price_kernel<f, b, a>, m, true, g, s, timed, pl.qr, m, ec, pl.inv_steps, pl.d_sv, pl.d_shift, pl.plan, pl.slabs, ws);
+                lv_launch(lv_qmc_price_kernel<f, b, a>, m, true, g, s, timed, pl.qr, m, pp.ec, pl.inv_steps, pl.d_sv, pl.d_shift, pl.plan, pl.slabs, ws);
             });
         });
     }, qmc_stats(r, T, bad, out));
@@ -3082,8 +3096,8 @@ extern "C" int olmc_heston_qmc_greeks_fd(double S, double K, double T, double r,
 extern "C" int olmc_heston_qe_surface(double S, double T, double r, double q, int is_call, double kappa, double theta, double sigma_v, double rho,
                                       double v0, const double* strikes, const int32_t* steps, int32_t k, int64_t path_offset, int64_t n_local,
                                       int32_t n_steps, uint64_t seed, int antithetic, olmc_stats* out) {
-    return run_heston_surface<HestonQe>(S, T, r, q, is_call, {kappa, theta, sigma_v, rho, v0}, strikes, steps, k, path_offset, n_local, n_steps, seed,
-                                        antithetic, out);
+    return run_heston_surface<HestonQe>(S, T, r, q, is_call, {kappa, theta, sigma_v, rho, v0}, strikes, steps, k,
+                                        {path_offset, n_local, n_steps, seed, antithetic}, out);
 }
 
 extern "C" int olmc_heston_qe_qmc_surface(double S, double T, double r, double q, int is_call, double kappa, double theta, double sigma_v,
@@ -3244,19 +3258,6 @@ bool jd_poisoned(double S, double K, double T, double r, double sigma, double q,
     return poisoned(S, K, T, r, sigma, q) || std::isnan(m->lambda_j + m->a1 + m->a2 + m->a3);
 }
 
-int jd_payoff_check(int payoff, double barrier) {
-    if (payoff < OLMC_BARRIER_UP_OUT || payoff > OLJD_EUROPEAN) return fail(OLMC_ERR_ARG, "bad payoff");
-    if (heston_path_is_barrier(payoff) && barrier <= 0.0) return fail(OLMC_ERR_ARG, "Barrier must be positive");
-    return OLMC_OK;
-}
-
-// f(integral_constant<int, family>) for the family of a checked payoff code, OLJD_EUROPEAN included.
-template <typename F>
-void with_jd_family(int payoff, F&& f) {
-    if (payoff == OLJD_EUROPEAN) f(std::integral_constant<int, kJumpEuropean>{});
-    else with_heston_path_family(payoff, f);
-}
-
 template <template <bool> class Product>
 int run_jd_product(const JumpContract& jc, const typename Product<false>::Contract& pc, double r_for_discount, double T, bool bad, int64_t path_offset,
                    int64_t n_local, int32_t n_steps, uint64_t seed, int antithetic, olmc_stats* out) {
@@ -3275,16 +3276,16 @@ extern "C" int oljd_price(double S, double K, double T, double r, double sigma, 
     JumpContract jc;
     int rc = jd_contract(S, T, r, sigma, q, is_call, model, n_steps, &jc);
     if (rc) return rc;
-    rc = jd_payoff_check(payoff, barrier);
+    rc = path_payoff_check(payoff, barrier, OLJD_EUROPEAN);
     if (rc) return rc;
-    const ExtremaContract ec = heston_path_contract(S, K, is_call, payoff == OLJD_EUROPEAN ? OLMC_PATH_ASIAN_ARITHMETIC : payoff, barrier);
-    const bool bad = jd_poisoned(S, K, T, r, sigma, q, model) || (heston_path_is_barrier(payoff) && std::isnan(barrier));
+    const PathPayoff pp = path_payoff(S, K, is_call, payoff, barrier);
+    const bool bad = jd_poisoned(S, K, T, r, sigma, q, model) || pp.nan_barrier;
     const double inv_steps = 1.0 / n_steps;                  // n_steps < 1 was refused by make_jump
     return run_structured(path_offset, n_local, n_steps, seed, antithetic, r, T, bad, out,
                           [&](int32_t grid, hipStream_t st, const EventPair* timed, const PathRange& pr, const ReduceWs& ws) {
-                              with_jd_family(payoff, [&](auto f) {
+                              with_path_family(payoff, OLJD_EUROPEAN, [&](auto f) {
                                   with_bool(antithetic != 0, [&](auto a) {
-                                      launch_timed(jump_path_kernel<f, a>, dim3(grid), dim3(kBlock), st, timed, pr, jc, ec, inv_steps, ws);
+                                      launch_timed(jump_path_kernel<f, a>, dim3(grid), dim3(kBlock), st, timed, pr, jc, pp.ec, inv_steps, ws);
                                   });
                               });
                           });
@@ -3295,28 +3296,16 @@ extern "C" int oljd_surface_prices(double S, double T, double r, double sigma, d
                                    int antithetic, olmc_stats* out) {
     if (!strikes || !steps || !out) return fail(OLMC_ERR_ARG, "null pointer");
     JumpContract jc;
-    int rc = jd_contract(S, T, r, sigma, q, is_call, model, n_steps, &jc);
+    const int rc = jd_contract(S, T, r, sigma, q, is_call, model, n_steps, &jc);
     if (rc) return rc;
-    rc = check_paths(path_offset, n_local, n_steps);
-    if (rc) return rc;
-    SurfaceOrder so;
-    rc = surface_cells(strikes, steps, k, n_steps, &so);
-    if (rc) return rc;
-    const bool bad = jd_poisoned(S, 0.0, T, r, sigma, q, model);
-    CtxLease lease;
-    rc = ctx_lease(&lease);
-    if (rc) return rc;
-    DeviceCtx* const c = lease.c;
-    const PathRange pr = make_range(path_offset, n_local, n_steps, seed);
-    rc = launch_reduce(c, c->stream, c->d_result, -1.0, 2 * kSurfaceCells, grid_for(n_local),
-                       [&](int32_t grid, hipStream_t st, const EventPair* timed, const ReduceWs& ws) {
-                           with_bool(antithetic != 0, [&](auto a) {
-                               launch_timed(jump_surface_kernel<a>, dim3(grid), dim3(kBlock), st, timed, pr, jc, so.cells, ws);
-                           });
-                       });
-    if (rc) return rc;
-    surface_finish(c->h_result, so, strikes, steps, k, n_local * (antithetic ? 2 : 1), r, T / n_steps, bad, out);
-    return OLMC_OK;
+    return run_philox_surface(strikes, steps, k, {path_offset, n_local, n_steps, seed, antithetic}, r, T,
+                              jd_poisoned(S, 0.0, T, r, sigma, q, model), out, no_setup,
+                              [&](int32_t grid, hipStream_t st, const EventPair* timed, const PathRange& pr, const HestonSurfaceCells& cells,
+                                  const ReduceWs& ws) {
+        with_bool(antithetic != 0, [&](auto a) {
+            launch_timed(jump_surface_kernel<a>, dim3(grid), dim3(kBlock), st, timed, pr, jc, cells, ws);
+        });
+    });
 }
 
 extern "C" int oljd_autocallable(double S, double T, double r, double sigma, double q, const oljd_model* model, double autocall_barrier,
@@ -3352,20 +3341,14 @@ extern "C" int oljd_paths(double S, double T, double r, double sigma, double q, 
                           uint64_t seed, int mirror, int path_major, double* out_host) {
     if (!out_host) return fail(OLMC_ERR_ARG, "null pointer");
     JumpContract jc;
-    int rc = jd_contract(S, T, r, sigma, q, 1, model, n_steps, &jc);
+    const int rc = jd_contract(S, T, r, sigma, q, 1, model, n_steps, &jc);
     if (rc) return rc;
-    const double bytes = 8.0 * static_cast<double>(n_paths) * (n_steps + 1.0);
-    CtxLease lease;
-    rc = matrix_prologue(n_paths, n_steps, bytes, "path matrix would exceed 64 GB", &lease);
-    if (rc) return rc;
-    DeviceCtx* const c = lease.c;
-    const PathRange pr = make_range(0, n_paths, n_steps, seed);
-    with_bool(path_major != 0, [&](auto pm) {
-        launch_timed(jump_legs_paths_kernel<pm>, dim3(grid_for(n_paths)), dim3(kBlock), c->stream, nullptr, pr, jc, S, static_cast<int32_t>(mirror != 0),
-                     c->bulk.as<double>());
+    return run_philox_matrix(n_paths, n_steps, seed, out_host, no_setup,
+                             [&](DeviceCtx* c, int32_t grid, const PathRange& pr, double* d_paths) {
+        with_bool(path_major != 0, [&](auto pm) {
+            launch_timed(jump_legs_paths_kernel<pm>, dim3(grid), dim3(kBlock), c->stream, nullptr, pr, jc, S, static_cast<int32_t>(mirror != 0), d_paths);
+        });
     });
-    HIP_TRY(hipGetLastError());
-    return copy_to_host(c, out_host, c->bulk.get(), static_cast<size_t>(bytes));
 }
 
 namespace {

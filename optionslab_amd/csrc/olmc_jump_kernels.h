@@ -28,8 +28,6 @@
 
 namespace olmc {
 
-enum JumpFamily { kJumpEuropean = 3 };            // continues QmcPathFamily (0 .. 2)
-
 // The path's Philox blocks with the launch's round keys pinned in VGPRs (pin_round_keys), as the other path kernels draw theirs: the words
 // jump_kernel draws from the scalar keys.
 struct JumpWords {
@@ -40,7 +38,7 @@ struct JumpWords {
 
 // oljd_price: the payoffs, dates and log-space level decisions of heston_path_kernel / lv_price_kernel (QmcLeg over x_t = ln(S_t / S),
 // extrema over dates 0 .. n, the Asian mean over dates 1 .. n with one fp64 exponential per date and leg for the arithmetic one, the
-// date-0 barrier decision made on the host: heston_path_contract); kJumpEuropean adds max(+-(S_n - K), 0).
+// date-0 barrier decision made on the host: heston_path_contract); kPathEuropean adds max(+-(S_n - K), 0).
 // Resources (tools/kernel_meta.sh, gfx950; no scratch, no spills; LDS 64 B, the reduction), VGPRs plain / antithetic:
 // arithmetic 110 / 97, geometric 108 / 97, extrema 111 / 117, European 106 / 92 (jump_kernel: 86, with its keys in scalar registers; the
 // twenty pinned round keys are the difference).  No instantiation passes 128: by registers (granule 8, 512 per lane) every one admits
@@ -52,6 +50,7 @@ __global__ __launch_bounds__(kBlock) void jump_path_kernel(PathRange pr, JumpCon
     const RoundKeys rk = pin_round_keys(pr.key0, pr.key1);
     const double vol = c.vol * kZScale;
     double acc[2] = {0.0, 0.0};
+    // The legs written out per family: held in one shared struct the antithetic Asian forms took 96 VGPRs for 97 and left their row.
     for_each_path(pr, [&](int64_t, uint32_t g_lo, uint32_t g_hi) {
         double x[2] = {0.0, 0.0};
         QmcLeg leg[2];
@@ -59,13 +58,13 @@ __global__ __launch_bounds__(kBlock) void jump_path_kernel(PathRange pr, JumpCon
 #pragma unroll
             for (int l = 0; l < LEGS; ++l) {
                 if constexpr (FAMILY == kQmcAsianArithmetic) qmc_leg_add<FAMILY>(leg[l], x[l] * kLog2e);
-                else if constexpr (FAMILY != kJumpEuropean) qmc_leg_add<FAMILY>(leg[l], x[l]);
+                else if constexpr (FAMILY != kPathEuropean) qmc_leg_add<FAMILY>(leg[l], x[l]);
             }
         });
 #pragma unroll
         for (int l = 0; l < LEGS; ++l) {
             double p;
-            if constexpr (FAMILY == kJumpEuropean) p = fmax(ec.sign * (ec.s0 * exp(x[l]) - ec.strike), 0.0);
+            if constexpr (FAMILY == kPathEuropean) p = fmax(ec.sign * (ec.s0 * exp(x[l]) - ec.strike), 0.0);
             else p = qmc_payoff<FAMILY>(ec, inv_steps, leg[l].a, leg[l].mx, leg[l].mn, x[l]);
             acc[0] += p; acc[1] += p * p;
         }
@@ -73,33 +72,25 @@ __global__ __launch_bounds__(kBlock) void jump_path_kernel(PathRange pr, JumpCon
     block_then_grid_reduce<2>(acc, ws);
 }
 
-// oljd_surface_prices: lv_surface_kernel's skeleton, cell rows and read-out (SurfaceRows) on these paths; the walk ends at the last
-// cell's step.  The read-out forms a date's spot as exp(ln S + x) (its mu_dt term is 0 here).  The path loop is wave-uniform as there: a
-// lane outside the range walks path 0 with its payoff masked to 0.
+// oljd_surface_prices: heston_surface_kernel's prologue, wave-uniform path loop, cell rows and read-out (surface_rows,
+// for_each_wave_path, SurfaceRows) on these paths; the walk ends at the last cell's step.  The read-out forms a date's spot as
+// exp(ln S + x) (its mu_dt term is 0 here).
 // Resources (tools/kernel_meta.sh, gfx950; no scratch, no spills; LDS 3.2 KiB), VGPRs plain / antithetic: 101 / 88
 // (lv_surface_kernel's skeleton; heston_surface_kernel: 92 / 82).
 template <bool ANTI>
 __global__ __launch_bounds__(kBlock) void jump_surface_kernel(PathRange pr, JumpContract c, HestonSurfaceCells cells, ReduceWs ws) {
     constexpr int LEGS = ANTI ? 2 : 1;
-    __shared__ double stage[kWavesPerBlock][2 * kSurfaceCells], cell_strike[kSurfaceCells];
-    __shared__ int32_t cell_step[kSurfaceCells];
-    const SurfaceRows rows{stage, cell_strike, cell_step, static_cast<int>(threadIdx.x) & (kWave - 1),
-                           __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) / kWave)};
-    rows.clear(cells);
+    const SurfaceRows rows = surface_rows(cells);
     const RoundKeys rk = pin_round_keys(pr.key0, pr.key1);
     const double vol = c.vol * kZScale;
-    const int64_t stride = static_cast<int64_t>(gridDim.x) * kBlock;
-    for (int64_t w0 = static_cast<int64_t>(blockIdx.x) * kBlock + rows.wave * kWave; w0 < pr.count; w0 += stride) {      // wave-uniform
-        const int64_t i = w0 + rows.lane;
-        const bool live = i < pr.count;
-        const PathWords pw = path_words(pr, live ? i : 0);
+    for_each_wave_path(pr, [&](bool live, PathWords pw) {
         double x[2] = {0.0, 0.0};
         int32_t next = 0, pending = cells.step[0];
         jump_walk<LEGS>(c, JumpWords{pw.lo, pw.hi, rk}, vol, cells.last, x, [&](int32_t t) {
             const double ls[2] = {c.log_s0 + x[0], c.log_s0 + x[1]};
             rows.read_out<LEGS>(next, pending, t + 1, 0.0, c.sign, ls, live);
         });
-    }
+    });
     rows.reduce(ws);
 }
 

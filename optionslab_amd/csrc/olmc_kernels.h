@@ -837,6 +837,19 @@ __device__ __forceinline__ void for_each_path(const PathRange& pr, Body body) {
     }
 }
 
+// The same loop WAVE-uniform, for kernels that fold over the wave inside it: body(live, PathWords) runs with all 64 lanes of every
+// wave that owns a path; a lane outside the range gets path 0 and live = false (it walks a defined path, its payoff is masked to 0).
+template <typename Body>
+__device__ __forceinline__ void for_each_wave_path(const PathRange& pr, Body body) {
+    const int lane = static_cast<int>(threadIdx.x) & (kWave - 1), wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) / kWave);
+    const int64_t stride = static_cast<int64_t>(gridDim.x) * kBlock;
+    for (int64_t w0 = static_cast<int64_t>(blockIdx.x) * kBlock + wave * kWave; w0 < pr.count; w0 += stride) {
+        const int64_t i = w0 + lane;
+        const bool live = i < pr.count;
+        body(live, path_words(pr, live ? i : 0));
+    }
+}
+
 // A path's dates as Philox blocks of four: `full` whole blocks, then one block of which the first `rem` dates are used.
 // Launch-uniform: computed once per kernel, before the path loop.
 struct BlockWalk {
@@ -3130,7 +3143,8 @@ __global__ void publish_kernel(const double* __restrict__ src, int32_t n, double
 // units as asian_exp64_kernel does); geometric = S exp(mean_j ln(S_j / S)); barrier / lookback = extrema_payoff on the running max
 // / min of ln(S_j / S), t = 0 included.  The per-point payoffs meet in block_then_grid_reduce: index order, equal inputs, equal bits.
 constexpr int kQmcBridgeMaxSteps = 1024;
-enum QmcPathFamily { kQmcAsianArithmetic = 0, kQmcAsianGeometric = 1, kQmcExtrema = 2 };
+enum QmcPathFamily { kQmcAsianArithmetic = 0, kQmcAsianGeometric = 1, kQmcExtrema = 2,
+                     kPathEuropean = 3 };      // max(+-(S_n - K), 0) on the same walk: the local-volatility and jump price kernels only
 
 struct QmcBridgePlan {
     const uint32_t* ab;      // [n]: node k's a | b << 16 (node 0: unused -- W_n = sqrt(n) z_0)
@@ -4031,6 +4045,17 @@ struct SurfaceRows {
     }
 };
 
+// The prologue of a surface kernel: the launch's rows and cells in LDS (owned here: one set per kernel), the rows cleared, the cells
+// copied, every wave past the barrier.
+__device__ __forceinline__ SurfaceRows surface_rows(const HestonSurfaceCells& cells) {
+    __shared__ double stage[kWavesPerBlock][2 * kSurfaceCells], cell_strike[kSurfaceCells];
+    __shared__ int32_t cell_step[kSurfaceCells];
+    const SurfaceRows rows{stage, cell_strike, cell_step, static_cast<int>(threadIdx.x) & (kWave - 1),
+                           __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) / kWave)};
+    rows.clear(cells);
+    return rows;
+}
+
 // Philox: lane per path, heston_kernel's stream (tag kTagHeston, one block for two steps: a cell's date may fall inside a block).
 // Resources (tools/kernel_meta.sh, gfx950; no scratch, no spills; LDS 3.2 KiB: the wave rows, the cells and the workgroup
 // reduction), VGPRs plain / antithetic: 92 / 82 (heston_kernel: 96 / 76).  Plain stays in heston_kernel's row (96 allocated, five waves
@@ -4039,17 +4064,14 @@ struct SurfaceRows {
 template <bool ANTI>
 __global__ __launch_bounds__(kBlock) void heston_surface_kernel(PathRange pr, HestonContract c, HestonSurfaceCells cells, ReduceWs ws) {
     constexpr int LEGS = ANTI ? 2 : 1;
-    __shared__ double stage[kWavesPerBlock][2 * kSurfaceCells], cell_strike[kSurfaceCells];
-    __shared__ int32_t cell_step[kSurfaceCells];
-    const SurfaceRows rows{stage, cell_strike, cell_step, static_cast<int>(threadIdx.x) & (kWave - 1),
-                           __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) / kWave)};
-    rows.clear(cells);
+    const SurfaceRows rows = surface_rows(cells);
     const RoundKeys rk = pin_round_keys(pr.key0, pr.key1);
     const HestonStep hs(c);
     double v_start;
     const bool skip0 = heston_start(c, v_start);
     const int32_t blocks = (cells.last + 1) >> 1;
     const int64_t stride = static_cast<int64_t>(gridDim.x) * kBlock;
+    // The loop written out, not for_each_wave_path: with it the plain form measured 4.7 % slower than the parent's (profiles/r24_shared_path_pieces.jsonl).
     for (int64_t w0 = static_cast<int64_t>(blockIdx.x) * kBlock + rows.wave * kWave; w0 < pr.count; w0 += stride) {      // wave-uniform
         const int64_t i = w0 + rows.lane;
         const bool live = i < pr.count;
@@ -4085,11 +4107,7 @@ __global__ __launch_bounds__(kBlock) void heston_qmc_surface_kernel(QmcRange qr,
                                                                     const uint32_t* __restrict__ sv, const uint32_t* __restrict__ shift,
                                                                     QmcBridgePlan plan, double* slabs, ReduceWs ws) {
     constexpr int LEGS = ANTI ? 2 : 1;
-    __shared__ double stage[kWavesPerBlock][2 * kSurfaceCells], cell_strike[kSurfaceCells];
-    __shared__ int32_t cell_step[kSurfaceCells];
-    const SurfaceRows rows{stage, cell_strike, cell_step, static_cast<int>(threadIdx.x) & (kWave - 1),
-                           __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) / kWave)};
-    rows.clear(cells);
+    const SurfaceRows rows = surface_rows(cells);
     const int lane = rows.lane;
     const int32_t n = qr.dims;                                               // steps of the grid: the tables hold 2 n dimensions
     const HestonStep hs(c, 1.0);
@@ -4221,6 +4239,17 @@ struct ScenarioRows {
     }
 };
 
+// The prologue of a scenario kernel (surface_rows without the cell arrays): the rows and the set in LDS, cleared and copied.  Call
+// first in the kernel, whose first argument is the set.
+__device__ __forceinline__ ScenarioRows scenario_rows() {
+    __shared__ double stage[kWavesPerBlock][2 * kSurfaceCells];
+    __shared__ HestonScenarioSet lds;
+    const ScenarioRows rows{stage, &lds, static_cast<int>(threadIdx.x) & (kWave - 1),
+                            __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) / kWave)};
+    rows.clear();
+    return rows;
+}
+
 // Philox: lane per path, heston_kernel's stream (tag kTagHeston, one block for two steps, raw_normals4_pinned).
 // Resources (tools/kernel_meta.sh, gfx950; no scratch, no spills; LDS 4.0 KiB: the wave rows, the set and the workgroup reduction),
 // VGPRs plain / antithetic: 114 / 110 (heston_kernel: 96 / 76): both allocate within 128, four waves per SIMD against heston_kernel's
@@ -4228,14 +4257,11 @@ struct ScenarioRows {
 template <bool ANTI>
 __global__ __launch_bounds__(kBlock) void heston_scenarios_kernel(HestonScenarioSet set, PathRange pr, ReduceWs ws) {
     constexpr int LEGS = ANTI ? 2 : 1;
-    __shared__ double stage[kWavesPerBlock][2 * kSurfaceCells];
-    __shared__ HestonScenarioSet lds;
-    const ScenarioRows rows{stage, &lds, static_cast<int>(threadIdx.x) & (kWave - 1),
-                            __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) / kWave)};
-    rows.clear();
+    const ScenarioRows rows = scenario_rows();
     const RoundKeys rk = pin_round_keys(pr.key0, pr.key1);
     const int32_t blocks = (pr.n_steps + 1) >> 1;
     const int64_t stride = static_cast<int64_t>(gridDim.x) * kBlock;
+    // The loop written out, not for_each_wave_path: with it the plain form takes 104 VGPRs for 114 and leaves its allocation row.
     for (int64_t w0 = static_cast<int64_t>(blockIdx.x) * kBlock + rows.wave * kWave; w0 < pr.count; w0 += stride) {      // wave-uniform
         const int64_t i = w0 + rows.lane;
         const bool live = i < pr.count;
@@ -4269,11 +4295,7 @@ __global__ __launch_bounds__(kBlock) void heston_qmc_scenarios_kernel(HestonScen
                                                                       const uint32_t* __restrict__ shift, QmcBridgePlan plan, double* slabs,
                                                                       ReduceWs ws) {
     constexpr int LEGS = ANTI ? 2 : 1;
-    __shared__ double stage[kWavesPerBlock][2 * kSurfaceCells];
-    __shared__ HestonScenarioSet lds;
-    const ScenarioRows rows{stage, &lds, static_cast<int>(threadIdx.x) & (kWave - 1),
-                            __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) / kWave)};
-    rows.clear();
+    const ScenarioRows rows = scenario_rows();
     const int32_t n = qr.dims;                                               // steps: the tables hold 2 n dimensions
     heston_point_blocks(qr, [&](int64_t slot, int lane, uint64_t, bool live, const QmcLanePoint& lp) {
         double ls[kHestonRecursions][2], v[kHestonRecursions][2];
@@ -4418,18 +4440,10 @@ __device__ __forceinline__ QeWordUniform heston_qe_philox_draw(uint32_t g_lo, ui
 template <bool ANTI>
 __global__ __launch_bounds__(kBlock) void heston_qe_surface_kernel(PathRange pr, HestonQeContract c, HestonSurfaceCells cells, ReduceWs ws) {
     constexpr int LEGS = ANTI ? 2 : 1;
-    __shared__ double stage[kWavesPerBlock][2 * kSurfaceCells], cell_strike[kSurfaceCells];
-    __shared__ int32_t cell_step[kSurfaceCells];
-    const SurfaceRows rows{stage, cell_strike, cell_step, static_cast<int>(threadIdx.x) & (kWave - 1),
-                           __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) / kWave)};
-    rows.clear(cells);
+    const SurfaceRows rows = surface_rows(cells);
     const RoundKeys rk = pin_round_keys(pr.key0, pr.key1);
     const HestonQeStep hs(c, kZScale);
-    const int64_t stride = static_cast<int64_t>(gridDim.x) * kBlock;
-    for (int64_t w0 = static_cast<int64_t>(blockIdx.x) * kBlock + rows.wave * kWave; w0 < pr.count; w0 += stride) {      // wave-uniform
-        const int64_t i = w0 + rows.lane;
-        const bool live = i < pr.count;
-        const PathWords pw = path_words(pr, live ? i : 0);
+    for_each_wave_path(pr, [&](bool live, PathWords pw) {
         double ls[2] = {c.log_s0, c.log_s0}, v[2] = {c.v0, c.v0};             // ls WITHOUT the drift_dt terms: added per read-out
         int32_t next = 0, pending = cells.step[0];
         for (int32_t t = 0; t < cells.last; ++t) {
@@ -4438,7 +4452,7 @@ __global__ __launch_bounds__(kBlock) void heston_qe_surface_kernel(PathRange pr,
             hs.legs<ANTI>(draw, z_v, z_s, ls, v);
             rows.read_out<LEGS>(next, pending, t + 1, c.drift_dt, c.sign, ls, live);
         }
-    }
+    });
     rows.reduce(ws);
 }
 
@@ -4516,11 +4530,7 @@ __global__ __launch_bounds__(kBlock) void heston_qe_qmc_surface_kernel(QmcRange 
                                                                        const uint32_t* __restrict__ sv, const uint32_t* __restrict__ shift,
                                                                        ReduceWs ws) {
     constexpr int LEGS = ANTI ? 2 : 1;
-    __shared__ double stage[kWavesPerBlock][2 * kSurfaceCells], cell_strike[kSurfaceCells];
-    __shared__ int32_t cell_step[kSurfaceCells];
-    const SurfaceRows rows{stage, cell_strike, cell_step, static_cast<int>(threadIdx.x) & (kWave - 1),
-                           __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) / kWave)};
-    rows.clear(cells);
+    const SurfaceRows rows = surface_rows(cells);
     const HestonQeStep hs(c, 1.0);
     heston_point_blocks(qr, [&](int64_t, int lane, uint64_t, bool live, const QmcLanePoint& lp) {
         double ls[2] = {c.log_s0, c.log_s0}, v[2] = {c.v0, c.v0};             // ls WITHOUT the drift_dt terms

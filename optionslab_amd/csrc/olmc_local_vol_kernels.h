@@ -17,7 +17,6 @@
 namespace olmc {
 
 constexpr int kLvMaxNx = 256, kLvMaxNt = 64;      // ollv_surface's caps (olmc.hip refuses anything beyond before a launch)
-enum LvFamily { kLvEuropean = 3 };                // continues QmcPathFamily (0 .. 2)
 
 struct LvModel {
     const float* nodes;          // device [n_t][n_x], row-major
@@ -68,6 +67,28 @@ __device__ __forceinline__ double lv_step(const LvModel& m, const LvRows& rw, do
     return x + __builtin_fma(sigma * m.vol_unit, z_raw, __builtin_fma(-(sigma * sigma), m.half_dt, m.rq_dt));
 }
 
+// Steps 0 .. last - 1 of one path for LEGS legs, in jump_walk's shape: normals(b, z) fills the four RAW normals of Philox block b (steps
+// 4 b .. 4 b + 3), leg 1 takes -z and walks its own sigma path; `after(t)` sees x after step t.
+template <int LEGS, typename Normals, typename After>
+__device__ __forceinline__ void lv_walk(const LvModel& m, Normals normals, int32_t last, double (&x)[2], After after) {
+    const int32_t blocks = (last + 3) >> 2;
+    for (int32_t b = 0; b < blocks; ++b) {
+        float z[4];
+        normals(b, z);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int32_t t = 4 * b + j;
+            if (t < last) {
+                const LvRows rw = lv_rows(m, t);
+                const double zj = static_cast<double>(z[j]);
+#pragma unroll
+                for (int l = 0; l < LEGS; ++l) x[l] = lv_step(m, rw, x[l], l ? -zj : zj);
+                after(t);
+            }
+        }
+    }
+}
+
 #ifndef OLMC_LV_ROW_LDS
 #define OLMC_LV_ROW_LDS 0           // 1 (python tools/local_vol_timing.py --build-row; never the product) swaps lv_price_kernel for the A/B form
 #endif
@@ -77,7 +98,7 @@ __device__ __forceinline__ double lv_step(const LvModel& m, const LvRows& rw, do
 
 // ollv_price: one launch, no path stored.  The payoffs, dates and log-space level decisions are heston_path_kernel's (QmcLeg over
 // ln(S_t / S), extrema over dates 0 .. n, the Asian mean over dates 1 .. n, the date-0 barrier decision made on the host:
-// heston_path_contract); kLvEuropean adds max(+-(S_n - K), 0).  The antithetic leg takes -z and walks its own sigma path.
+// heston_path_contract); kPathEuropean adds max(+-(S_n - K), 0).  The antithetic leg takes -z and walks its own sigma path.
 #if !OLMC_LV_ROW_LDS
 template <int FAMILY, bool ANTI>
 __global__ __launch_bounds__(kBlock) void lv_price_kernel(PathRange pr, LvModel m, ExtremaContract ec, double inv_steps, ReduceWs ws) {
@@ -87,6 +108,8 @@ __global__ __launch_bounds__(kBlock) void lv_price_kernel(PathRange pr, LvModel 
     const RoundKeys rk = pin_round_keys(pr.key0, pr.key1);
     double acc[2] = {0.0, 0.0};
     const BlockWalk w = block_walk(pr.n_steps);
+    // walk_blocks and the legs written out: under lv_walk's per-date `t < last` every instantiation leaves its register row (93 -> 82,
+    // 90 -> 72 VGPRs, ...), and with the legs in one shared struct the plain extrema form left its scalar one (106 -> 95 SGPRs).
     for_each_path(pr, [&](int64_t, uint32_t g_lo, uint32_t g_hi) {
         double x[2] = {0.0, 0.0};
         QmcLeg leg[2];
@@ -100,7 +123,7 @@ __global__ __launch_bounds__(kBlock) void lv_price_kernel(PathRange pr, LvModel 
                 for (int l = 0; l < LEGS; ++l) {
                     x[l] = lv_step(m, rw, x[l], l ? -zj : zj);
                     if constexpr (FAMILY == kQmcAsianArithmetic) qmc_leg_add<FAMILY>(leg[l], x[l] * kLog2e);
-                    else if constexpr (FAMILY != kLvEuropean) qmc_leg_add<FAMILY>(leg[l], x[l]);
+                    else if constexpr (FAMILY != kPathEuropean) qmc_leg_add<FAMILY>(leg[l], x[l]);
                 }
                 ++t;
             }
@@ -109,7 +132,7 @@ __global__ __launch_bounds__(kBlock) void lv_price_kernel(PathRange pr, LvModel 
 #pragma unroll
         for (int l = 0; l < LEGS; ++l) {
             double p;
-            if constexpr (FAMILY == kLvEuropean) p = fmax(ec.sign * (ec.s0 * exp(x[l]) - ec.strike), 0.0);
+            if constexpr (FAMILY == kPathEuropean) p = fmax(ec.sign * (ec.s0 * exp(x[l]) - ec.strike), 0.0);
             else p = qmc_payoff<FAMILY>(ec, inv_steps, leg[l].a, leg[l].mx, leg[l].mn, x[l]);
             acc[0] += p; acc[1] += p * p;
         }
@@ -119,67 +142,36 @@ __global__ __launch_bounds__(kBlock) void lv_price_kernel(PathRange pr, LvModel 
 
 #endif
 
-// ollv_paths: the matrix S exp(x_t), t = 0 .. n, in lsm_paths_kernel's layouts; date 0 is S itself.
+// ollv_paths: the matrix S exp(x_t), t = 0 .. n, in lsm_paths_kernel's layouts; date 0 is S itself.  The draws come from the scalar keys.
 template <bool PATH_MAJOR>
 __global__ __launch_bounds__(kBlock) void lv_paths_kernel(PathRange pr, LvModel m, double* __restrict__ paths) {
     lv_table_to_lds(m);
     for_each_path(pr, [&](int64_t i, uint32_t g_lo, uint32_t g_hi) {
-        double x = 0.0;
+        double x[2] = {0.0, 0.0};
         paths[path_at<PATH_MAJOR>(i, 0, pr.count, pr.n_steps)] = m.s0;
-        const int32_t blocks = (pr.n_steps + 3) >> 2;
-        for (int32_t b = 0; b < blocks; ++b) {
-            float z[4];
-            raw_normals4(g_lo, g_hi, static_cast<uint32_t>(b), 0u, pr.key0, pr.key1, z);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int32_t t = 4 * b + j;
-                if (t < pr.n_steps) {
-                    x = lv_step(m, lv_rows(m, t), x, static_cast<double>(z[j]));
-                    paths[path_at<PATH_MAJOR>(i, t + 1, pr.count, pr.n_steps)] = m.s0 * exp(x);
-                }
-            }
-        }
+        lv_walk<1>(m, [&](int32_t b, float (&z)[4]) { raw_normals4(g_lo, g_hi, static_cast<uint32_t>(b), 0u, pr.key0, pr.key1, z); }, pr.n_steps, x,
+                   [&](int32_t t) { paths[path_at<PATH_MAJOR>(i, t + 1, pr.count, pr.n_steps)] = m.s0 * exp(x[0]); });
     });
 }
 
-// ollv_surface_prices: heston_surface_kernel's skeleton, cell rows and read-out (SurfaceRows) on these paths.  The read-out forms a
-// date's spot as exp(ln S + x) (its mu_dt term is 0 here).  The path loop is wave-uniform as there: a lane outside the range walks
-// path 0 with its payoff masked to 0.
+// ollv_surface_prices: heston_surface_kernel's prologue, wave-uniform path loop, cell rows and read-out (surface_rows,
+// for_each_wave_path, SurfaceRows) on these paths; the walk ends at the last cell's step.  The read-out forms a date's spot as
+// exp(ln S + x) (its mu_dt term is 0 here).
 template <bool ANTI>
 __global__ __launch_bounds__(kBlock) void lv_surface_kernel(PathRange pr, LvModel m, double sign, HestonSurfaceCells cells, ReduceWs ws) {
     constexpr int LEGS = ANTI ? 2 : 1;
-    __shared__ double stage[kWavesPerBlock][2 * kSurfaceCells], cell_strike[kSurfaceCells];
-    __shared__ int32_t cell_step[kSurfaceCells];
-    const SurfaceRows rows{stage, cell_strike, cell_step, static_cast<int>(threadIdx.x) & (kWave - 1),
-                           __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) / kWave)};
     lv_table_to_lds(m);
-    rows.clear(cells);
+    const SurfaceRows rows = surface_rows(cells);
     const RoundKeys rk = pin_round_keys(pr.key0, pr.key1);
-    const int32_t blocks = (cells.last + 3) >> 2;
-    const int64_t stride = static_cast<int64_t>(gridDim.x) * kBlock;
-    for (int64_t w0 = static_cast<int64_t>(blockIdx.x) * kBlock + rows.wave * kWave; w0 < pr.count; w0 += stride) {      // wave-uniform
-        const int64_t i = w0 + rows.lane;
-        const bool live = i < pr.count;
-        const PathWords pw = path_words(pr, live ? i : 0);
+    for_each_wave_path(pr, [&](bool live, PathWords pw) {
         double x[2] = {0.0, 0.0};
         int32_t next = 0, pending = cells.step[0];
-        for (int32_t b = 0; b < blocks; ++b) {
-            float z[4];
-            raw_normals4_pinned(pw.lo, pw.hi, static_cast<uint32_t>(b), 0u, rk, z);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int32_t t = 4 * b + j;
-                if (t < cells.last) {
-                    const LvRows rw = lv_rows(m, t);
-                    const double zj = static_cast<double>(z[j]);
-#pragma unroll
-                    for (int l = 0; l < LEGS; ++l) x[l] = lv_step(m, rw, x[l], l ? -zj : zj);
-                    const double ls[2] = {m.log_s0 + x[0], m.log_s0 + x[1]};
-                    rows.read_out<LEGS>(next, pending, t + 1, 0.0, sign, ls, live);
-                }
-            }
-        }
-    }
+        lv_walk<LEGS>(m, [&](int32_t b, float (&z)[4]) { raw_normals4_pinned(pw.lo, pw.hi, static_cast<uint32_t>(b), 0u, rk, z); }, cells.last, x,
+                      [&](int32_t t) {
+                          const double ls[2] = {m.log_s0 + x[0], m.log_s0 + x[1]};
+                          rows.read_out<LEGS>(next, pending, t + 1, 0.0, sign, ls, live);
+                      });
+    });
     rows.reduce(ws);
 }
 

@@ -107,6 +107,7 @@ __global__ __launch_bounds__(kBlock) void lv_qmc_price_kernel(QmcRange qr, LvMod
     lv_table_to_lds(m);
     const int32_t n = qr.dims;
     double acc[2] = {0.0, 0.0};
+    // The legs written out, as in lv_price_kernel: in one shared struct the plain extrema bridge form measured 1.5 % slower (profiles/r24_shared_path_pieces.jsonl).
     heston_point_blocks(qr, [&](int64_t slot, int lane, uint64_t, bool live, const QmcLanePoint& lp) {
         double x[2] = {0.0, 0.0};
         QmcLeg leg[2];
@@ -116,7 +117,7 @@ __global__ __launch_bounds__(kBlock) void lv_qmc_price_kernel(QmcRange qr, LvMod
             for (int l = 0; l < LEGS; ++l) {
                 x[l] = lv_step(m, rw, x[l], l ? -z : z);
                 if constexpr (FAMILY == kQmcAsianArithmetic) qmc_leg_add<FAMILY>(leg[l], x[l] * kLog2e);
-                else if constexpr (FAMILY != kLvEuropean) qmc_leg_add<FAMILY>(leg[l], x[l]);
+                else if constexpr (FAMILY != kPathEuropean) qmc_leg_add<FAMILY>(leg[l], x[l]);
             }
         };
         if constexpr (BRIDGE) {
@@ -131,7 +132,7 @@ __global__ __launch_bounds__(kBlock) void lv_qmc_price_kernel(QmcRange qr, LvMod
 #pragma unroll
             for (int l = 0; l < LEGS; ++l) {
                 double p;
-                if constexpr (FAMILY == kLvEuropean) p = fmax(ec.sign * (ec.s0 * exp(x[l]) - ec.strike), 0.0);
+                if constexpr (FAMILY == kPathEuropean) p = fmax(ec.sign * (ec.s0 * exp(x[l]) - ec.strike), 0.0);
                 else p = qmc_payoff<FAMILY>(ec, inv_steps, leg[l].a, leg[l].mx, leg[l].mn, x[l]);
                 acc[0] += p; acc[1] += p * p;
             }
@@ -184,12 +185,8 @@ __global__ __launch_bounds__(kBlock) void lv_qmc_surface_kernel(QmcRange qr, LvM
                                                                 const uint32_t* __restrict__ sv, const uint32_t* __restrict__ shift,
                                                                 QmcBridgePlan plan, double* slabs, ReduceWs ws) {
     constexpr int LEGS = ANTI ? 2 : 1;
-    __shared__ double stage[kWavesPerBlock][2 * kSurfaceCells], cell_strike[kSurfaceCells];
-    __shared__ int32_t cell_step[kSurfaceCells];
-    const SurfaceRows rows{stage, cell_strike, cell_step, static_cast<int>(threadIdx.x) & (kWave - 1),
-                           __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) / kWave)};
     lv_table_to_lds(m);
-    rows.clear(cells);
+    const SurfaceRows rows = surface_rows(cells);
     const int32_t n = qr.dims;
     heston_point_blocks(qr, [&](int64_t slot, int lane, uint64_t, bool live, const QmcLanePoint& lp) {      // wave-uniform
         double x[2] = {0.0, 0.0};

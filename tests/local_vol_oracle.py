@@ -38,6 +38,13 @@ class Table:
         return a0 + w_tau * (a1 - a0)
 
 
+def smile_table(n_t, n_x, x_lo, x_hi, t_hi):
+    """The tests' smile: a skew and a term structure, 0.22 - 0.25 x + 0.4 x^2 + 0.05 tau / t_hi on the uniform grid."""
+    x = np.linspace(x_lo, x_hi, n_x)[None, :]
+    tau = (np.arange(n_t)[:, None] / max(n_t - 1, 1))
+    return Table(0.22 - 0.25 * x + 0.4 * x * x + 0.05 * tau, x_lo, x_hi, t_hi)
+
+
 def log_paths(z, table, T, r, q):
     """x[m, n + 1] from the normals z[m, n]."""
     z = np.asarray(z, dtype=np.float64)

@@ -344,6 +344,12 @@ _REFUSALS = [
     ("olmc_exercise_boundary_qmc", lambda: (*_G, 0, 10 ** 9, 10, *_sobol(10), 31, (C.c_double * 4)()),
      "only 30-bit Sobol tables (SciPy's default) are supported"),
     ("olmc_multi_gpu_european_qmc", lambda: (*_G, 64, 4, *_sobol(4), 16, 0, _ST()), "only 30-bit Sobol tables (SciPy's default) are supported"),
+    # the path matrices: the model (with its step count) before the path count, the path count before the size
+    ("olmc_jump_paths", lambda: (*_MKT, 0, 1.0, -0.1, 0.2, 0.0, 0, 0, 1, 0, (C.c_double * 4)()), "n_steps must be >= 1"),
+    ("olmc_jump_paths", lambda: (*_MKT, 2, 1.0, -0.1, 0.2, 0.0, 0, 4, 1, 0, (C.c_double * 4)()), "bad jump model"),
+    ("olmc_jump_paths", lambda: (*_MKT, 0, 1.0, -0.1, 0.2, 0.0, 0, 4, 1, 0, (C.c_double * 4)()), "n_paths must be >= 1"),
+    ("olmc_gbm_paths", lambda: (*_MKT, 0, 0, 1, 0, (C.c_double * 4)()), "n_paths must be >= 1"),
+    ("olmc_gbm_paths", lambda: (*_MKT, 10 ** 9, 0, 1, 0, (C.c_double * 4)()), "n_steps must be >= 1"),
 ]
 
 

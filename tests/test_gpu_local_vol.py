@@ -45,12 +45,11 @@ EUROPEAN = _hip.LV_EUROPEAN
 
 def smile(n_t, n_x, x_lo, x_hi, t_hi):
     """Distinct nodes with a skew and a term structure: 0.22 - 0.25 x + 0.4 x^2 + 0.05 tau / t_hi, all within [0.15, 0.55]."""
-    x = np.linspace(x_lo, x_hi, n_x)[None, :]
-    tau = (np.arange(n_t)[:, None] / max(n_t - 1, 1))
-    vol = 0.22 - 0.25 * x + 0.4 * x * x + 0.05 * tau
+    table = lvo.smile_table(n_t, n_x, x_lo, x_hi, t_hi)
+    vol = table.vol
     a = vol.astype(np.float32)                                # what the kernels read: every node differs from its neighbours
     assert len(np.unique(vol)) == vol.size and np.all(np.diff(a, axis=1) != 0) and np.all(np.diff(a, axis=0) != 0) and vol.min() > 0.15
-    return lvo.Table(vol, x_lo, x_hi, t_hi)
+    return table
 
 
 TABLES = {

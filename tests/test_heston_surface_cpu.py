@@ -277,6 +277,10 @@ _REFUSALS = [
     ("olmc_heston_qmc_surface", lambda: (*_HEAD, -1.5, 0.04, *_cells()[:2], 0, 2, 0, 64, 4, *_sobol(8), 30, 0, _out()), "rho must be in [-1, 1]"),
     ("olmc_heston_qmc_surface", lambda: (*_HEAD, -0.7, 0.04, *_cells()[:2], 17, 0, 0, 64, 4, *_sobol(8), 32, 0, _out()),
      "only 30-bit Sobol tables (SciPy's default) are supported"),
+    # Philox: the model, then the range (count, steps, offset), then the cells
+    ("olmc_heston_surface", lambda: (*_HEAD, -0.7, 0.04, *_cells(steps=(2, 5)), 0, 0, 4, 1, 0, _out()), "n_paths must be >= 1"),
+    ("olmc_heston_surface", lambda: (*_HEAD, -0.7, 0.04, *_cells()[:2], 17, 0, 100, 0, 1, 0, _out()), "n_steps must be >= 1"),
+    ("olmc_heston_surface", lambda: (*_HEAD, 1.5, 0.04, *_cells(steps=(2, 5)), 0, 0, 4, 1, 0, _out()), "rho must be in [-1, 1]"),
 ]
 
 

@@ -135,6 +135,13 @@ def test_every_refusal_answers_its_message_before_any_device_work(library):
     # two faults at once: the model comes first
     refused(library, entries(C.byref(_hip.JdModel(2, 0, 0.5, -0.1, 0.2, 0.0)), payoff=9)["oljd_price"], "bad jump model")
     refused(library, entries(C.byref(good), payoff=9, count=0)["oljd_price"], "bad payoff")
+    # the model's checks hold the step count (make_jump), so it comes before the payoff; the path count before the cells
+    refused(library, entries(C.byref(good), payoff=9, n_steps=0)["oljd_price"], "n_steps must be >= 1")
+    two = (C.c_int32 * 2)(n, n + 1)
+    refused(library, lambda: library.oljd_surface_prices(S, T, R, SIGMA, Q, 1, C.byref(good), strikes, two, 2, 0, 0, n, 1, 0, cells), "n_paths must be >= 1")
+    refused(library, entries(C.byref(good), k=17, count=0)["oljd_surface_prices"], "n_paths must be >= 1")
+    refused(library, entries(C.byref(good), n_steps=0, count=0)["oljd_paths"], "n_steps must be >= 1")
+    refused(library, entries(C.byref(good), count=0, n_steps=1 << 30)["oljd_paths"], "n_paths must be >= 1")
 
 
 def models():

@@ -284,6 +284,17 @@ def test_every_refusal_answers_its_message_before_any_device_work(library, entry
                 "a cell's step must be in [1, n_steps]")
     if entry == "ollv_paths":
         refused(library, call(n=1 << 33, steps=1), "path matrix would exceed 64 GB")
+    # two faults at once: the payoff before the range, inside the range the count before the steps, the range before the cells and the size
+    if entry == "ollv_price":
+        refused(library, call(payoff=9, steps=0), "bad payoff")
+        refused(library, call(payoff=0, barrier=0.0, n=0), "Barrier must be positive")
+    if entry == "ollv_surface_prices":
+        refused(library, lambda: library.ollv_surface_prices(100.0, 1.0, 0.05, 0.0, 1, C.byref(good), strikes, steps, 2, 0, 0, 4, 7, 0, sts),
+                "n_paths must be >= 1")
+        refused(library, call(k=17, steps=0), "n_steps must be >= 1")
+    if entry == "ollv_paths":
+        refused(library, call(n=0, steps=0), "n_paths must be >= 1")
+        refused(library, call(n=1 << 33, steps=0), "n_steps must be >= 1")
     assert keep is not None and keep_bad is not None and keep_row is not None
 
 

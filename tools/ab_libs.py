@@ -2,7 +2,7 @@
 """Interleaved A/B of whole libolmc builds: one subprocess per (library, round), each timing the
 European path kernel with HIP events (olmc_kernel_time).  --case takes one name or a comma-separated list (measured one after the other in the
 same subprocess, which is ended after --timeout seconds); --out appends one JSON line per (case, library).  Usage (GPU box):
-    python tools/ab_libs.py libA.so libB.so ... [--n 1000000] [--m 252] [--rounds 7] [--timeout 300] [--out FILE.jsonl] [--case european|heston_*|greeks8|greeks14|greeks8_lean|greeks14_lean|asian|asian_fast|asian_fast_anti|asian_anti|asian_geo|barrier|heston|merton|kou|autocall[_anti]|cliquet[_anti]|american|{barrier,lookback}_greeks{8,14}[_anti]|asian_greeks8|asian_greeks14[_rho]|qmc|qmc_cv|qmc_greeks8|qmc_greeks14]"""
+    python tools/ab_libs.py libA.so libB.so ... [--n 1000000] [--m 252] [--rounds 7] [--timeout 300] [--out FILE.jsonl] [--case european|heston_*|greeks8|greeks14|greeks8_lean|greeks14_lean|asian|asian_fast|asian_fast_anti|asian_anti|asian_geo|barrier|heston|merton|kou|autocall[_anti]|cliquet[_anti]|american|{barrier,lookback}_greeks{8,14}[_anti]|asian_greeks8|asian_greeks14[_rho]|qmc|qmc_cv|qmc_greeks8|qmc_greeks14|lv_{european,asian,asian_geo,lookback,barrier,surface}[_anti]|lvq_{...}_{seq,bridge}[_anti]|jd_surface_{merton,kou}[_anti]]"""
 import argparse
 import json
 import os
@@ -88,6 +88,31 @@ if "heston_" in sys.argv[3]:
     for _pm, _sp in ((False, ""), (True, "_pm")):          # the path matrices: N x (M + 1) doubles twice to the host per call
         CASES["heston_paths" + _sp] = lambda s, pm=_pm: head(_hip.heston_paths(100.0, 1.0, 0.05, 0.0, *HM, N, M, s, pm))
         CASES["heston_qe_paths" + _sp] = lambda s, pm=_pm: head(_hip.heston_qe_paths(100.0, 1.0, 0.05, 0.0, *HQ, N, M, s, pm))
+# local volatility (lv_*, lvq_*: the 33 x 128 tables of tools/local_vol_timing.py and tools/local_vol_qmc_timing.py, Sobol seed 42) and the
+# jump surfaces (jd_surface_*: the models and the 12 cells of tools/jump_payoff_timing.py); payoff codes 8, 6, 7, 4, 0
+if any(p in sys.argv[3] for p in ("lv_", "lvq_", "jd_")):
+    import numpy as np
+    LQ, LUP = 0.01, 120.0
+    def _smile(base, t_hi):
+        x = np.linspace(-0.5, 0.45, 128)[None, :]
+        return base - 0.25 * x + 0.4 * x * x + 0.05 * (np.arange(33)[:, None] / 32), -0.5, 0.45, t_hi
+    LVT, LVQT = _smile(0.22, 1.0), _smile(0.22, 0.8)
+    CELLS = ([90.0, 100.0, 110.0] * 4, [M // 4] * 3 + [M // 2] * 3 + [3 * M // 4] * 3 + [M] * 3)
+    one = lambda cells: type("R", (), dict(price=cells[0].price, sum=cells[0].sum))()
+    if "lvq_" in sys.argv[3]:
+        from optionslab_amd.monte_carlo import sobol_tables
+        LSV, LSH = sobol_tables(M, 42, N)
+    for _a, _sa in ((False, ""), (True, "_anti")):
+        CASES["lv_surface" + _sa] = lambda s, a=_a: one(_hip.lv_surface_prices(100.0, 1.0, 0.05, LQ, True, LVT, *CELLS, N, M, s, a))
+        for _m, _model in (("merton", (False, 0.5, -0.1, 0.2, 0.0)), ("kou", (True, 1.0, 0.4, 10.0, 5.0))):
+            CASES["jd_surface_" + _m + _sa] = lambda s, a=_a, m=_model: one(_hip.jd_surface_prices(100.0, 1.0, 0.05, 0.2, LQ, True, m, *CELLS, N, M, s, a))
+        for _f, _code, _level in (("european", 8, 0.0), ("asian", 6, 0.0), ("asian_geo", 7, 0.0), ("lookback", 4, 0.0), ("barrier", 0, LUP)):
+            CASES["lv_" + _f + _sa] = lambda s, a=_a, c=_code, l=_level: _hip.lv_price(100.0, 100.0, 1.0, 0.05, LQ, True, LVT, c, l, N, M, s, a)
+            for _b, _sb in ((False, "_seq"), (True, "_bridge")):
+                CASES["lvq_" + _f + _sb + _sa] = (lambda s, a=_a, c=_code, l=_level, b=_b:
+                                                  _hip.lvq_price(100.0, 100.0, 1.0, 0.05, LQ, True, LVQT, c, l, N, LSV, LSH, b, a))
+        for _b, _sb in ((False, "_seq"), (True, "_bridge")):
+            CASES["lvq_surface" + _sb + _sa] = lambda s, a=_a, b=_b: one(_hip.lvq_surface_prices(100.0, 1.0, 0.05, LQ, True, LVQT, *CELLS, N, LSV, LSH, b, a))
 import os, time
 if os.environ.get("OLMC_AB_TUNE"):                      # "knob=value,knob=value" applied before anything runs
     for kv in os.environ["OLMC_AB_TUNE"].split(","):

@@ -53,7 +53,7 @@ __global__ __launch_bounds__(kBlock) void lv_price_kernel(PathRange pr, LvModel 
                         const double sigma = r0 + (u - static_cast<double>(c)) * (r1 - r0);
                         x[l] += __builtin_fma(sigma * m.vol_unit, l ? -zj : zj, __builtin_fma(-(sigma * sigma), m.half_dt, m.rq_dt));
                         if constexpr (FAMILY == kQmcAsianArithmetic) qmc_leg_add<FAMILY>(leg[l], x[l] * kLog2e);
-                        else if constexpr (FAMILY != kLvEuropean) qmc_leg_add<FAMILY>(leg[l], x[l]);
+                        else if constexpr (FAMILY != kPathEuropean) qmc_leg_add<FAMILY>(leg[l], x[l]);
                     }
                 }
             }
@@ -62,7 +62,7 @@ __global__ __launch_bounds__(kBlock) void lv_price_kernel(PathRange pr, LvModel 
 #pragma unroll
             for (int l = 0; l < LEGS; ++l) {
                 double p;
-                if constexpr (FAMILY == kLvEuropean) p = fmax(ec.sign * (ec.s0 * exp(x[l]) - ec.strike), 0.0);
+                if constexpr (FAMILY == kPathEuropean) p = fmax(ec.sign * (ec.s0 * exp(x[l]) - ec.strike), 0.0);
                 else p = qmc_payoff<FAMILY>(ec, inv_steps, leg[l].a, leg[l].mx, leg[l].mn, x[l]);
                 acc[0] += p; acc[1] += p * p;
             }
