@@ -63,9 +63,18 @@ class JdModel(C.Structure):
 
 
 _D, _I, _I32, _I64, _U64T, _P = C.c_double, C.c_int, C.c_int32, C.c_int64, C.c_uint64, C.c_void_p
+_DP, _U32P, _I32P = C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_int32)
+_STATS, _CV, _OPTIONS, _SCENARIOS = C.POINTER(Stats), C.POINTER(CvMoments), C.POINTER(Option), C.POINTER(HestonScenario)
 _byref = C.byref
 _Out9 = C.c_double * 9
-_SIX = [_D] * 6
+# the runs of arguments the entry points share, in the headers' order
+_SIX = [_D] * 6                                      # S, K, T, r, sigma, q
+_HESTON = [_D] * 5                                   # kappa, theta, sigma_v, rho, v0
+_RANGE = [_I64, _I64, _I32, _U64T, _I, _STATS]       # path_offset, n_local, n_steps, seed, antithetic, out
+_SOBOL = [_I32, _U32P, _U32P, _I32]                  # n_dims (under Heston: n_steps, of two dimensions each), sv, shift, bits
+_POINTS = [_I64, _I64] + _SOBOL                      # point_offset, n_points, then the tables
+_CELLS = [_DP, _I32P, _I32]                          # strikes, steps, n_cells
+_GREEKS = [_DP, _STATS]                              # out9, the 14 evaluations (or NULL)
 
 # name -> (restype, argtypes); must list every symbol include/olmc.h declares
 PROTOTYPES = {
@@ -74,118 +83,107 @@ PROTOTYPES = {
     "olmc_shutdown": (_I, []),
     "olmc_last_error": (C.c_char_p, []),
     "olmc_device_info": (_I, [C.POINTER(DevInfo)]),
-    "olmc_european": (_I, _SIX + [_I, _I64, _I32, _U64T, _I, C.POINTER(Stats)]),
-    "olmc_european_shard": (_I, _SIX + [_I, _I64, _I64, _I32, _U64T, _I, C.POINTER(Stats)]),
+    "olmc_european": (_I, _SIX + [_I, _I64, _I32, _U64T, _I, _STATS]),
+    "olmc_european_shard": (_I, _SIX + [_I] + _RANGE),
     "olmc_european_shard_dev": (_I, _SIX + [_I, _I64, _I64, _I32, _U64T, _I, _P, _P]),
-    "olmc_fetch_dev": (_I, [_P, _I32, _P, C.POINTER(_D)]),
-    "olmc_european_batch": (_I, [C.POINTER(Option), _I32, _I64, _I64, _I32, _U64T, _I, C.POINTER(Stats)]),
-    "olmc_european_multi": (_I, [C.POINTER(Option), C.POINTER(C.c_uint32), _I64, _I64, _I32, _U64T, _I, C.POINTER(Stats)]),
+    "olmc_fetch_dev": (_I, [_P, _I32, _P, _DP]),
+    "olmc_european_batch": (_I, [_OPTIONS, _I32] + _RANGE),
+    "olmc_european_multi": (_I, [_OPTIONS, _U32P, _I64, _I64, _I32, _U64T, _I, _STATS]),
     "olmc_multi_capacity": (_I, [C.POINTER(_I64)]),
-    "olmc_contract_layout": (_I, [C.POINTER(Option), _I32, _I32, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(C.c_uint32), C.POINTER(_I32), C.POINTER(_D)]),
-    "olmc_european_greeks_fd": (_I, _SIX + [_I, _I64, _I32, _U64T, _I, C.POINTER(_D), C.POINTER(Stats)]),
-    "olmc_european_terminal": (_I, [_D] * 5 + [_I64, _I32, _U64T, _I, C.POINTER(_D)]),
-    "olmc_gbm_paths": (_I, [_D] * 5 + [_I64, _I32, _U64T, _I, C.POINTER(_D)]),
-    "olmc_european_cv": (_I, _SIX + [_I, _I64, _I32, _U64T, _I, C.POINTER(CvMoments)]),
-    "olmc_european_cv_shard": (_I, _SIX + [_I, _I64, _I64, _I32, _U64T, _I, C.POINTER(CvMoments)]),
-    "olmc_combine_cv": (_I, [C.POINTER(CvMoments), _I32, _D, _D, _D, _D, C.POINTER(CvMoments)]),
-    "olmc_european_qmc": (_I, _SIX + [_I, _I64, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, C.POINTER(Stats)]),
-    "olmc_european_qmc_cv": (_I, _SIX + [_I, _I64, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, C.POINTER(CvMoments)]),
-    "olmc_european_qmc_batch": (_I, [C.POINTER(Option), _I32, _I64, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, C.POINTER(Stats)]),
-    "olmc_european_qmc_greeks_fd": (_I, _SIX + [_I, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, _I, C.POINTER(_D), C.POINTER(Stats)]),
-    "olmc_european_qmc_terminal": (_I, [_D] * 5 + [_I64, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, _I, C.POINTER(_D)]),
-    "olmc_asian": (_I, _SIX + [_I, _I, _I64, _I64, _I32, _U64T, _I, C.POINTER(Stats)]),
-    "olmc_asian_qmc": (_I, _SIX + [_I, _I, _I, _I64, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, _I, C.POINTER(Stats)]),
-    "olmc_extrema_qmc": (_I, _SIX + [_I, _I, _D, _I, _I64, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, _I, C.POINTER(Stats)]),
-    "olmc_asian_qmc_greeks_fd": (_I, _SIX + [_I, _I, _I, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, _I, _I, C.POINTER(_D), C.POINTER(Stats)]),
-    "olmc_extrema_qmc_greeks_fd": (_I, _SIX + [_I, _I, _D, _I, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, _I, _I, C.POINTER(_D),
-                                              C.POINTER(Stats)]),
-    "olmc_asian_greeks_fd": (_I, _SIX + [_I, _I, _I64, _I32, _U64T, _I, _I, C.POINTER(_D), C.POINTER(Stats)]),
-    "olmc_extrema_greeks_fd": (_I, _SIX + [_I, _I, _D, _I64, _I32, _U64T, _I, _I, C.POINTER(_D), C.POINTER(Stats)]),
-    "olmc_barrier": (_I, _SIX + [_I, _D, _I, _I64, _I64, _I32, _U64T, _I, C.POINTER(Stats)]),
-    "olmc_lookback": (_I, _SIX + [_I, _I, _I64, _I64, _I32, _U64T, _I, C.POINTER(Stats)]),
-    "olmc_autocallable": (_I, [_D] * 9 + [_I32, _I64, _I64, _I32, _U64T, _I, C.POINTER(Stats)]),
-    "olmc_cliquet": (_I, [_D] * 9 + [_I32, _I64, _I64, _I32, _U64T, _I, C.POINTER(Stats)]),
-    "olmc_exercise_boundary": (_I, _SIX + [_I, _I64, _I32, _U64T, C.POINTER(_D)]),
-    "olmc_heston_paths": (_I, [_D] * 9 + [_I64, _I32, _U64T, _I, C.POINTER(_D), C.POINTER(_D)]),
-    "olmc_jump_paths": (_I, [_D] * 5 + [_I, _D, _D, _D, _D, _I64, _I32, _U64T, _I, C.POINTER(_D)]),
-    "olmc_american_lsm": (_I, _SIX + [_I, _I64, _I32, _I32, _U64T, C.POINTER(Stats)]),
-    "olmc_autocallable_qmc": (_I, [_D] * 9 + [_I32, _I, _I64, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, _I, C.POINTER(Stats)]),
-    "olmc_cliquet_qmc": (_I, [_D] * 9 + [_I32, _I, _I64, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, _I, C.POINTER(Stats)]),
-    "olmc_american_lsm_qmc": (_I, _SIX + [_I, _I, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, _I32, C.POINTER(Stats)]),
-    "olmc_exercise_boundary_qmc": (_I, _SIX + [_I, _I, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, C.POINTER(_D)]),
-    "olmc_gbm_qmc_paths": (_I, [_D] * 5 + [_I, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, _I, C.POINTER(_D)]),
-    "olmc_jump_diffusion": (_I, _SIX + [_I, _I, _D, _D, _D, _D, _I64, _I64, _I32, _U64T, C.POINTER(Stats)]),
-    "olmc_heston": (_I, [_D] * 5 + [_I] + [_D] * 5 + [_I64, _I64, _I32, _U64T, _I, C.POINTER(Stats)]),
-    "olmc_heston_qmc": (_I, [_D] * 5 + [_I] + [_D] * 5 + [_I, _I64, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, _I, C.POINTER(Stats)]),
-    "olmc_heston_qmc_paths": (_I, [_D] * 9 + [_I, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, _I, C.POINTER(_D), C.POINTER(_D)]),
-    "olmc_heston_path_payoff": (_I, [_D] * 5 + [_I] + [_D] * 5 + [_I, _D, _I64, _I64, _I32, _U64T, _I, C.POINTER(Stats)]),
-    "olmc_heston_qmc_path_payoff": (_I, [_D] * 5 + [_I] + [_D] * 5 + [_I, _D, _I, _I64, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, _I,
-                                         C.POINTER(Stats)]),
-    "olmc_heston_surface": (_I, [_D] * 4 + [_I] + [_D] * 5 + [C.POINTER(_D), C.POINTER(_I32), _I32, _I64, _I64, _I32, _U64T, _I, C.POINTER(Stats)]),
-    "olmc_heston_qmc_surface": (_I, [_D] * 4 + [_I] + [_D] * 5 + [C.POINTER(_D), C.POINTER(_I32), _I32, _I, _I64, _I64, _I32, C.POINTER(C.c_uint32),
-                                     C.POINTER(C.c_uint32), _I32, _I, C.POINTER(Stats)]),
-    "olmc_heston_scenario_layout": (_I, [C.POINTER(HestonScenario), _I32, C.POINTER(_I32), C.POINTER(_I32)]),
-    "olmc_heston_scenarios": (_I, [C.POINTER(HestonScenario), _I32, _I64, _I64, _I32, _U64T, _I, C.POINTER(Stats)]),
-    "olmc_heston_qmc_scenarios": (_I, [C.POINTER(HestonScenario), _I32, _I, _I64, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, _I,
-                                       C.POINTER(Stats)]),
-    "olmc_heston_greeks_fd": (_I, _SIX + [_I] + [_D] * 4 + [_I64, _I32, _U64T, _I, _I, C.POINTER(_D), C.POINTER(Stats)]),
-    "olmc_heston_qmc_greeks_fd": (_I, _SIX + [_I] + [_D] * 4 + [_I, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, _I, _I, C.POINTER(_D),
-                                                             C.POINTER(Stats)]),
-    "olmc_heston_qe_surface": (_I, [_D] * 4 + [_I] + [_D] * 5 + [C.POINTER(_D), C.POINTER(_I32), _I32, _I64, _I64, _I32, _U64T, _I, C.POINTER(Stats)]),
-    "olmc_heston_qe_qmc_surface": (_I, [_D] * 4 + [_I] + [_D] * 5 + [C.POINTER(_D), C.POINTER(_I32), _I32, _I, _I64, _I64, _I32, C.POINTER(C.c_uint32),
-                                        C.POINTER(C.c_uint32), _I32, _I, C.POINTER(Stats)]),
-    "olmc_heston_qe_paths": (_I, [_D] * 9 + [_I64, _I32, _U64T, _I, C.POINTER(_D), C.POINTER(_D)]),
-    "olmc_heston_qe_qmc_paths": (_I, [_D] * 9 + [_I, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, _I, C.POINTER(_D), C.POINTER(_D)]),
-    "olmc_heston_autocallable": (_I, [_D] * 13 + [_I32, _I, _I64, _I64, _I32, _U64T, _I, C.POINTER(Stats)]),
-    "olmc_heston_autocallable_qmc": (_I, [_D] * 13 + [_I32, _I, _I, _I64, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, _I,
-                                          C.POINTER(Stats)]),
-    "olmc_heston_cliquet": (_I, [_D] * 13 + [_I32, _I, _I64, _I64, _I32, _U64T, _I, C.POINTER(Stats)]),
-    "olmc_heston_cliquet_qmc": (_I, [_D] * 13 + [_I32, _I, _I, _I64, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, _I,
-                                     C.POINTER(Stats)]),
-    "olmc_multi_gpu_european":(_I, _SIX + [_I, _I64, _I32, _U64T, _I, _I, C.POINTER(Stats)]),
-    "olmc_multi_gpu_greeks_fd": (_I, _SIX + [_I, _I64, _I32, _U64T, _I, _I, C.POINTER(_D), C.POINTER(Stats)]),
-    "olmc_multi_gpu_european_cv": (_I, _SIX + [_I, _I64, _I32, _U64T, _I, _I, C.POINTER(CvMoments)]),
-    "olmc_multi_gpu_european_qmc": (_I, _SIX + [_I, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, _I, C.POINTER(Stats)]),
-    "olmc_multi_gpu_european_qmc_greeks_fd": (_I, _SIX + [_I, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, _I, _I, C.POINTER(_D), C.POINTER(Stats)]),
-    "olmc_multi_gpu_european_qmc_cv": (_I, _SIX + [_I, _I64, _I32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _I32, _I, C.POINTER(CvMoments)]),
-    "olmc_multi_gpu_spans": (_I, [C.POINTER(_D)]),
-    "olmc_combine_stats": (_I, [C.POINTER(Stats), _I32, _D, _D, C.POINTER(Stats)]),
-    "olmc_philox_words": (_I, [_U64T, _I64, _I64, _I32, _I32, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "olmc_contract_layout": (_I, [_OPTIONS, _I32, _I32, _I32P, _I32P, _U32P, _I32P, _DP]),
+    "olmc_european_greeks_fd": (_I, _SIX + [_I, _I64, _I32, _U64T, _I] + _GREEKS),
+    "olmc_european_terminal": (_I, [_D] * 5 + [_I64, _I32, _U64T, _I, _DP]),
+    "olmc_gbm_paths": (_I, [_D] * 5 + [_I64, _I32, _U64T, _I, _DP]),
+    "olmc_european_cv": (_I, _SIX + [_I, _I64, _I32, _U64T, _I, _CV]),
+    "olmc_european_cv_shard": (_I, _SIX + [_I, _I64, _I64, _I32, _U64T, _I, _CV]),
+    "olmc_combine_cv": (_I, [_CV, _I32, _D, _D, _D, _D, _CV]),
+    "olmc_european_qmc": (_I, _SIX + [_I] + _POINTS + [_STATS]),
+    "olmc_european_qmc_cv": (_I, _SIX + [_I] + _POINTS + [_CV]),
+    "olmc_european_qmc_batch": (_I, [_OPTIONS, _I32] + _POINTS + [_STATS]),
+    "olmc_european_qmc_greeks_fd": (_I, _SIX + [_I, _I64] + _SOBOL + [_I] + _GREEKS),
+    "olmc_european_qmc_terminal": (_I, [_D] * 5 + _POINTS + [_I, _DP]),
+    "olmc_asian": (_I, _SIX + [_I, _I] + _RANGE),
+    "olmc_asian_qmc": (_I, _SIX + [_I, _I, _I] + _POINTS + [_I, _STATS]),
+    "olmc_extrema_qmc": (_I, _SIX + [_I, _I, _D, _I] + _POINTS + [_I, _STATS]),
+    "olmc_asian_qmc_greeks_fd": (_I, _SIX + [_I, _I, _I, _I64] + _SOBOL + [_I, _I] + _GREEKS),
+    "olmc_extrema_qmc_greeks_fd": (_I, _SIX + [_I, _I, _D, _I, _I64] + _SOBOL + [_I, _I] + _GREEKS),
+    "olmc_asian_greeks_fd": (_I, _SIX + [_I, _I, _I64, _I32, _U64T, _I, _I] + _GREEKS),
+    "olmc_extrema_greeks_fd": (_I, _SIX + [_I, _I, _D, _I64, _I32, _U64T, _I, _I] + _GREEKS),
+    "olmc_barrier": (_I, _SIX + [_I, _D, _I] + _RANGE),
+    "olmc_lookback": (_I, _SIX + [_I, _I] + _RANGE),
+    "olmc_autocallable": (_I, [_D] * 9 + [_I32] + _RANGE),
+    "olmc_cliquet": (_I, [_D] * 9 + [_I32] + _RANGE),
+    "olmc_exercise_boundary": (_I, _SIX + [_I, _I64, _I32, _U64T, _DP]),
+    "olmc_heston_paths": (_I, [_D] * 4 + _HESTON + [_I64, _I32, _U64T, _I, _DP, _DP]),
+    "olmc_jump_paths": (_I, [_D] * 5 + [_I, _D, _D, _D, _D, _I64, _I32, _U64T, _I, _DP]),
+    "olmc_american_lsm": (_I, _SIX + [_I, _I64, _I32, _I32, _U64T, _STATS]),
+    "olmc_autocallable_qmc": (_I, [_D] * 9 + [_I32, _I] + _POINTS + [_I, _STATS]),
+    "olmc_cliquet_qmc": (_I, [_D] * 9 + [_I32, _I] + _POINTS + [_I, _STATS]),
+    "olmc_american_lsm_qmc": (_I, _SIX + [_I, _I, _I64] + _SOBOL + [_I32, _STATS]),
+    "olmc_exercise_boundary_qmc": (_I, _SIX + [_I, _I, _I64] + _SOBOL + [_DP]),
+    "olmc_gbm_qmc_paths": (_I, [_D] * 5 + [_I, _I64] + _SOBOL + [_I, _DP]),
+    "olmc_jump_diffusion": (_I, _SIX + [_I, _I, _D, _D, _D, _D, _I64, _I64, _I32, _U64T, _STATS]),
+    "olmc_heston": (_I, [_D] * 5 + [_I] + _HESTON + _RANGE),
+    "olmc_heston_qmc": (_I, [_D] * 5 + [_I] + _HESTON + [_I] + _POINTS + [_I, _STATS]),
+    "olmc_heston_qmc_paths": (_I, [_D] * 4 + _HESTON + [_I, _I64] + _SOBOL + [_I, _DP, _DP]),
+    "olmc_heston_path_payoff": (_I, [_D] * 5 + [_I] + _HESTON + [_I, _D] + _RANGE),
+    "olmc_heston_qmc_path_payoff": (_I, [_D] * 5 + [_I] + _HESTON + [_I, _D, _I] + _POINTS + [_I, _STATS]),
+    "olmc_heston_surface": (_I, [_D] * 4 + [_I] + _HESTON + _CELLS + _RANGE),
+    "olmc_heston_qmc_surface": (_I, [_D] * 4 + [_I] + _HESTON + _CELLS + [_I] + _POINTS + [_I, _STATS]),
+    "olmc_heston_scenario_layout": (_I, [_SCENARIOS, _I32, _I32P, _I32P]),
+    "olmc_heston_scenarios": (_I, [_SCENARIOS, _I32] + _RANGE),
+    "olmc_heston_qmc_scenarios": (_I, [_SCENARIOS, _I32, _I] + _POINTS + [_I, _STATS]),
+    "olmc_heston_greeks_fd": (_I, _SIX + [_I] + [_D] * 4 + [_I64, _I32, _U64T, _I, _I] + _GREEKS),
+    "olmc_heston_qmc_greeks_fd": (_I, _SIX + [_I] + [_D] * 4 + [_I, _I64] + _SOBOL + [_I, _I] + _GREEKS),
+    "olmc_heston_qe_surface": (_I, [_D] * 4 + [_I] + _HESTON + _CELLS + _RANGE),
+    "olmc_heston_qe_qmc_surface": (_I, [_D] * 4 + [_I] + _HESTON + _CELLS + [_I] + _POINTS + [_I, _STATS]),
+    "olmc_heston_qe_paths": (_I, [_D] * 4 + _HESTON + [_I64, _I32, _U64T, _I, _DP, _DP]),
+    "olmc_heston_qe_qmc_paths": (_I, [_D] * 4 + _HESTON + [_I, _I64] + _SOBOL + [_I, _DP, _DP]),
+    "olmc_heston_autocallable": (_I, [_D] * 4 + _HESTON + [_D] * 4 + [_I32, _I] + _RANGE),
+    "olmc_heston_autocallable_qmc": (_I, [_D] * 4 + _HESTON + [_D] * 4 + [_I32, _I, _I] + _POINTS + [_I, _STATS]),
+    "olmc_heston_cliquet": (_I, [_D] * 4 + _HESTON + [_D] * 4 + [_I32, _I] + _RANGE),
+    "olmc_heston_cliquet_qmc": (_I, [_D] * 4 + _HESTON + [_D] * 4 + [_I32, _I, _I] + _POINTS + [_I, _STATS]),
+    "olmc_multi_gpu_european": (_I, _SIX + [_I, _I64, _I32, _U64T, _I, _I, _STATS]),
+    "olmc_multi_gpu_greeks_fd": (_I, _SIX + [_I, _I64, _I32, _U64T, _I, _I] + _GREEKS),
+    "olmc_multi_gpu_european_cv": (_I, _SIX + [_I, _I64, _I32, _U64T, _I, _I, _CV]),
+    "olmc_multi_gpu_european_qmc": (_I, _SIX + [_I, _I64] + _SOBOL + [_I, _STATS]),
+    "olmc_multi_gpu_european_qmc_greeks_fd": (_I, _SIX + [_I, _I64] + _SOBOL + [_I, _I] + _GREEKS),
+    "olmc_multi_gpu_european_qmc_cv": (_I, _SIX + [_I, _I64] + _SOBOL + [_I, _CV]),
+    "olmc_multi_gpu_spans": (_I, [_DP]),
+    "olmc_combine_stats": (_I, [_STATS, _I32, _D, _D, _STATS]),
+    "olmc_philox_words": (_I, [_U64T, _I64, _I64, _I32, _I32, C.c_uint32, _U32P]),
     "olmc_normals": (_I, [_U64T, _I64, _I64, _I32, C.POINTER(C.c_float)]),
     "olmc_profile_enable": (_I, [_I]),
     "olmc_tune": (_I, [_I, _I]),
     "olmc_profile_reset": (_I, []),
-    "olmc_kernel_time": (_I, [C.POINTER(_I64), C.POINTER(_D)]),
+    "olmc_kernel_time": (_I, [C.POINTER(_I64), _DP]),
 }
 
 # the same for include/olmc_local_vol.h (its own header and prefix: olmc.h and PROTOTYPES stay as they are)
 LV_EUROPEAN = 8
+_LVS = C.POINTER(LvSurface)
 LV_PROTOTYPES = {
-    "ollv_price": (_I, [_D] * 5 + [_I, C.POINTER(LvSurface), _I, _D, _I64, _I64, _I32, _U64T, _I, C.POINTER(Stats)]),
-    "ollv_paths": (_I, [_D] * 4 + [C.POINTER(LvSurface), _I64, _I32, _U64T, _I, C.POINTER(_D)]),
-    "ollv_surface_prices": (_I, [_D] * 4 + [_I, C.POINTER(LvSurface), C.POINTER(_D), C.POINTER(_I32), _I32, _I64, _I64, _I32, _U64T, _I,
-                                         C.POINTER(Stats)]),
+    "ollv_price": (_I, [_D] * 5 + [_I, _LVS, _I, _D] + _RANGE),
+    "ollv_paths": (_I, [_D] * 4 + [_LVS, _I64, _I32, _U64T, _I, _DP]),
+    "ollv_surface_prices": (_I, [_D] * 4 + [_I, _LVS] + _CELLS + _RANGE),
 }
 
 # and for include/olmc_local_vol_qmc.h (prefix olvq_: the two dicts above stay as they are)
-_U32P = C.POINTER(C.c_uint32)
 LVQ_PROTOTYPES = {
-    "olvq_price": (_I, [_D] * 5 + [_I, C.POINTER(LvSurface), _I, _D, _I, _I64, _I64, _I32, _U32P, _U32P, _I32, _I, C.POINTER(Stats)]),
-    "olvq_paths": (_I, [_D] * 4 + [C.POINTER(LvSurface), _I, _I64, _I32, _U32P, _U32P, _I32, _I, C.POINTER(_D)]),
-    "olvq_surface_prices": (_I, [_D] * 4 + [_I, C.POINTER(LvSurface), C.POINTER(_D), C.POINTER(_I32), _I32, _I, _I64, _I64, _I32, _U32P, _U32P,
-                                         _I32, _I, C.POINTER(Stats)]),
+    "olvq_price": (_I, [_D] * 5 + [_I, _LVS, _I, _D, _I] + _POINTS + [_I, _STATS]),
+    "olvq_paths": (_I, [_D] * 4 + [_LVS, _I, _I64] + _SOBOL + [_I, _DP]),
+    "olvq_surface_prices": (_I, [_D] * 4 + [_I, _LVS] + _CELLS + [_I] + _POINTS + [_I, _STATS]),
 }
 
 # and for include/olmc_jump.h (prefix oljd_)
 JD_EUROPEAN = 8
 _JDM = C.POINTER(JdModel)
-_JD_RANGE = [_I64, _I64, _I32, _U64T, _I, C.POINTER(Stats)]          # path_offset, n_local, n_steps, seed, antithetic, out
 JD_PROTOTYPES = {
-    "oljd_price": (_I, _SIX + [_I, _JDM, _I, _D] + _JD_RANGE),
-    "oljd_surface_prices": (_I, [_D] * 5 + [_I, _JDM, C.POINTER(_D), C.POINTER(_I32), _I32] + _JD_RANGE),
-    "oljd_autocallable": (_I, [_D] * 5 + [_JDM] + [_D] * 4 + [_I32] + _JD_RANGE),
-    "oljd_cliquet": (_I, [_D] * 5 + [_JDM] + [_D] * 4 + [_I32] + _JD_RANGE),
-    "oljd_paths": (_I, [_D] * 5 + [_JDM, _I64, _I32, _U64T, _I, _I, C.POINTER(_D)]),
+    "oljd_price": (_I, _SIX + [_I, _JDM, _I, _D] + _RANGE),
+    "oljd_surface_prices": (_I, [_D] * 5 + [_I, _JDM] + _CELLS + _RANGE),
+    "oljd_autocallable": (_I, [_D] * 5 + [_JDM] + [_D] * 4 + [_I32] + _RANGE),
+    "oljd_cliquet": (_I, [_D] * 5 + [_JDM] + [_D] * 4 + [_I32] + _RANGE),
+    "oljd_paths": (_I, [_D] * 5 + [_JDM, _I64, _I32, _U64T, _I, _I, _DP]),
 }
 
 _lock = threading.Lock()
@@ -287,6 +285,43 @@ def device_info() -> dict:
                 clock_mhz=info.clock_mhz, wavefront=info.wavefront, device=info.device, hbm_bytes=info.hbm_bytes)
 
 
+# ---- the marshalling every wrapper below shares: one spelling per kind of argument and per kind of answer.  european(), the
+# want_evals=False branch of european_greeks_fd() and european_multi() do not use it: they are the latency paths bench.py times and are
+# written flat on purpose (their comments say what each spares).
+def _answer(rc: int, out):
+    """Check a call's return code and hand back what the call filled.  `return _answer(entry(..., _byref(out := Stats())), out)` is the
+    whole of a wrapper that allocates a Stats or a CvMoments, calls, checks and returns it: one frame, as the written-out form had."""
+    if rc:
+        _check(rc)
+    return out
+
+
+def _greeks(want_evals: bool, entry, *args) -> Tuple[List[float], List[Stats]]:
+    """Call a fused-Greeks entry point, whose last two arguments are the nine values and the fourteen evaluations (NULL unless wanted)."""
+    out9 = _Out9()
+    evals = (Stats * 14)() if want_evals else None
+    _check(entry(*args, out9, evals))
+    return list(out9), (list(evals) if want_evals else [])
+
+
+def _pointer(a: np.ndarray, kind):
+    """A POINTER(kind) at the array's first element that keeps the array alive, as ndarray.ctypes.data_as does, without the cast that
+    data_as makes of it: a Sobol or surface call asks for two (profiles/r25_binding_marshalling.jsonl, the `pointer` rows)."""
+    p = C.POINTER(kind)(kind.from_address(a.ctypes.data))
+    p._arr = a
+    return p
+
+
+def _dp(a: np.ndarray):
+    return _pointer(a, _D)
+
+
+def _options(options):
+    """(the olmc_option array, k) of contracts (S, K, T, r, sigma, q, is_call)."""
+    k = len(options)
+    return (Option * k)(*[Option(S, K, T, r, v, q, int(c), 0) for (S, K, T, r, v, q, c) in options]), k
+
+
 def european(S, K, T, r, sigma, q, is_call: bool, n_paths: int, n_steps: int, seed: int, antithetic: bool = True,
              path_offset: int = 0) -> Stats:
     out = Stats()
@@ -313,8 +348,7 @@ def fetch_dev(d_src_ptr: int, n: int, stream_ptr: int = 0) -> List[float]:
 
 def european_batch(options: Sequence[Tuple[float, float, float, float, float, float, bool]], n_paths: int, n_steps: int,
                    seed: int, antithetic: bool = True, path_offset: int = 0) -> List[Stats]:
-    k = len(options)
-    arr = (Option * k)(*[Option(S, K, T, r, v, q, int(c), 0) for (S, K, T, r, v, q, c) in options])
+    arr, k = _options(options)
     out = (Stats * k)()
     _check(lib().olmc_european_batch(arr, k, int(path_offset), int(n_paths), int(n_steps), seed64(seed), int(antithetic), out))
     return list(out)
@@ -351,8 +385,7 @@ def european_multi(S, K, T, r, sigma, q, is_call, n_paths: int, n_steps: int, se
 def contract_layout(options: Sequence[Tuple[float, float, float, float, float, float, bool]], n_steps: int):
     """(nsets, pos[k], base_mask, upper_continues_slot0, scale[nsets]) of a set of contracts for the fused kernels (olmc_contract_layout;
     pure host function: loads the library, not the GPU)."""
-    k = len(options)
-    arr = (Option * k)(*[Option(S, K, T, r, v, q, int(c), 0) for (S, K, T, r, v, q, c) in options])
+    arr, k = _options(options)
     nsets, pos, mask, cont, scale = C.c_int32(0), (C.c_int32 * k)(), C.c_uint32(0), C.c_int32(0), (C.c_double * 16)()
     _check(load_library().olmc_contract_layout(arr, k, int(n_steps), C.byref(nsets), pos, C.byref(mask), C.byref(cont), scale))
     return nsets.value, list(pos), mask.value, bool(cont.value), list(scale)[:nsets.value]
@@ -370,12 +403,10 @@ def european_greeks_fd(S, K, T, r, sigma, q, is_call: bool, n_paths: int, n_step
     """(price, delta, gamma, vega, theta, rho, vanna, charm, vomma) and -- unless want_evals is False, which spares a blocking
     Greeks call the marshalling of fourteen structs AND lets the library launch its prices-only kernel -- the statistics of the
     bumped contracts in the reference's call order."""
-    out9 = _Out9()
     if want_evals:
-        evals = (Stats * 14)()
-        _check(lib().olmc_european_greeks_fd(S, K, T, r, sigma, q, int(is_call), int(n_paths), int(n_steps), seed64(seed),
-                                             int(second_order), out9, evals))
-        return list(out9), list(evals)
+        return _greeks(True, lib().olmc_european_greeks_fd, S, K, T, r, sigma, q, int(is_call), int(n_paths), int(n_steps), seed64(seed),
+                       int(second_order))
+    out9 = _Out9()
     rc = lib().olmc_european_greeks_fd(S, K, T, r, sigma, q, bool(is_call), int(n_paths), int(n_steps), int(seed) & _U64, bool(second_order), out9, None)
     if rc:                              # the hot blocking call of greeks(): no helper frames on the success path
         _check(rc)
@@ -384,8 +415,7 @@ def european_greeks_fd(S, K, T, r, sigma, q, is_call: bool, n_paths: int, n_step
 
 def european_terminal(S, T, r, sigma, q, n_paths: int, n_steps: int, seed: int, antithetic: bool = True) -> np.ndarray:
     out = np.empty(int(n_paths) * (2 if antithetic else 1), dtype=np.float64)
-    _check(lib().olmc_european_terminal(S, T, r, sigma, q, int(n_paths), int(n_steps), seed64(seed), int(antithetic),
-                                        out.ctypes.data_as(C.POINTER(C.c_double))))
+    _check(lib().olmc_european_terminal(S, T, r, sigma, q, int(n_paths), int(n_steps), seed64(seed), int(antithetic), _dp(out)))
     return out
 
 
@@ -397,18 +427,22 @@ def gbm_paths(S, T, r, sigma, q, n_paths: int, n_steps: int, seed: int, path_maj
     """Prices at dates 0 .. n_steps (date 0 = spot): (n_steps + 1, n_paths) time-major, or with path_major
     the reference's (n_paths, n_steps + 1) C-order array, written in that layout by the kernel."""
     out = _path_matrix(n_paths, n_steps, path_major)
-    _check(lib().olmc_gbm_paths(S, T, r, sigma, q, int(n_paths), int(n_steps), seed64(seed), int(path_major),
-                                out.ctypes.data_as(C.POINTER(C.c_double))))
+    _check(lib().olmc_gbm_paths(S, T, r, sigma, q, int(n_paths), int(n_steps), seed64(seed), int(path_major), _dp(out)))
     return out
+
+
+def _spot_and_variance(entry, n_paths: int, n_steps: int, path_major: bool, *args):
+    """Call a Heston path-matrix entry point, whose last three arguments are path_major and the two matrices; layouts as gbm_paths."""
+    spot = _path_matrix(n_paths, n_steps, path_major)
+    var = np.empty_like(spot)
+    _check(entry(*args, int(path_major), _dp(spot), _dp(var)))
+    return spot, var
 
 
 def heston_paths(S, T, r, q, kappa, theta, sigma_v, rho, v0, n_paths: int, n_steps: int, seed: int, path_major: bool = False):
     """Spot and variance at dates 0 .. n_steps (date 0 = (S, v0)); layouts as gbm_paths."""
-    spot = _path_matrix(n_paths, n_steps, path_major)
-    var = np.empty_like(spot)
-    _check(lib().olmc_heston_paths(S, T, r, q, kappa, theta, sigma_v, rho, v0, int(n_paths), int(n_steps), seed64(seed), int(path_major),
-                                   spot.ctypes.data_as(C.POINTER(C.c_double)), var.ctypes.data_as(C.POINTER(C.c_double))))
-    return spot, var
+    return _spot_and_variance(lib().olmc_heston_paths, n_paths, n_steps, path_major, S, T, r, q, kappa, theta, sigma_v, rho, v0, int(n_paths),
+                              int(n_steps), seed64(seed))
 
 
 def jump_paths(S, T, r, sigma, q, kou: bool, lambda_j, a1, a2, a3, n_paths: int, n_steps: int, seed: int,
@@ -416,127 +450,123 @@ def jump_paths(S, T, r, sigma, q, kou: bool, lambda_j, a1, a2, a3, n_paths: int,
     """Prices of the jump-diffusion recursion at dates 0 .. n_steps (date 0 = spot); layouts as gbm_paths."""
     out = _path_matrix(n_paths, n_steps, path_major)
     _check(lib().olmc_jump_paths(S, T, r, sigma, q, int(bool(kou)), lambda_j, a1, a2, a3, int(n_paths), int(n_steps), seed64(seed),
-                                 int(path_major), out.ctypes.data_as(C.POINTER(C.c_double))))
+                                 int(path_major), _dp(out)))
     return out
 
 
 def exercise_boundary(S, K, T, r, sigma, q, is_call: bool, n_paths: int, n_steps: int, seed: int) -> np.ndarray:
     out = np.empty(int(n_steps) + 1, dtype=np.float64)
-    _check(lib().olmc_exercise_boundary(S, K, T, r, sigma, q, int(is_call), int(n_paths), int(n_steps), seed64(seed),
-                                        out.ctypes.data_as(C.POINTER(C.c_double))))
+    _check(lib().olmc_exercise_boundary(S, K, T, r, sigma, q, int(is_call), int(n_paths), int(n_steps), seed64(seed), _dp(out)))
     return out
 
 
 def european_cv(S, K, T, r, sigma, q, is_call: bool, n_paths: int, n_steps: int, seed: int,
                 antithetic: bool = True) -> CvMoments:
-    out = CvMoments()
-    _check(lib().olmc_european_cv(S, K, T, r, sigma, q, int(is_call), int(n_paths), int(n_steps), seed64(seed),
-                                  int(antithetic), C.byref(out)))
-    return out
+    return _answer(lib().olmc_european_cv(S, K, T, r, sigma, q, int(is_call), int(n_paths), int(n_steps),
+                                          seed64(seed), int(antithetic), _byref(out := CvMoments())), out)
 
 
 def european_cv_shard(S, K, T, r, sigma, q, is_call: bool, path_offset: int, n_local: int, n_steps: int, seed: int,
                       antithetic: bool = True) -> CvMoments:
-    out = CvMoments()
-    _check(lib().olmc_european_cv_shard(S, K, T, r, sigma, q, int(is_call), int(path_offset), int(n_local), int(n_steps), seed64(seed),
-                                        int(antithetic), C.byref(out)))
-    return out
+    return _answer(lib().olmc_european_cv_shard(S, K, T, r, sigma, q, int(is_call), int(path_offset), int(n_local), int(n_steps),
+                                                seed64(seed), int(antithetic), _byref(out := CvMoments())), out)
 
 
 def combine_cv(parts, S, T, r, q) -> CvMoments:
     """Control-variate estimate from per-shard moments (pure host function; loads the library, not the GPU)."""
     arr = (CvMoments * len(parts))(*parts)
-    out = CvMoments()
-    _check(load_library().olmc_combine_cv(arr, len(parts), S, T, r, q, C.byref(out)))
-    return out
+    return _answer(load_library().olmc_combine_cv(arr, len(parts), S, T, r, q, _byref(out := CvMoments())), out)
 
 
 def _u32(a: np.ndarray):
     a = np.ascontiguousarray(a, dtype=np.uint32)
-    return a, a.ctypes.data_as(C.POINTER(C.c_uint32))
+    return a, _pointer(a, C.c_uint32)
 
 
-def _sobol_args(sv, shift, point_offset: int, n_paths: int):
+class _SobolTables:
+    """A Sobol call's tables as one value, as the C host carries them: it keeps sv and shift alive for the call and holds `steps`
+    (dims / dims_per_step) and `run`, the (steps, sv, shift, bits) run of arguments every Sobol entry point takes."""
+    __slots__ = ("sv", "shift", "steps", "run")
+
+    def __init__(self, sv, shift, dims_per_step: int):
+        self.sv, psv = _u32(sv)
+        self.shift, psh = _u32(shift)
+        dims = int(self.sv.shape[0])
+        if dims % dims_per_step:
+            raise ValueError("Heston takes two Sobol dimensions per step: the tables must hold an even number of dimensions" if dims_per_step == 2
+                             else f"the tables must hold a multiple of {dims_per_step} Sobol dimensions")
+        self.steps = dims // dims_per_step
+        self.run = (self.steps, psv, psh, int(self.sv.shape[1]))
+
+
+def _sobol_args(sv, shift, point_offset: int, n_paths: int, dims_per_step: int = 1) -> _SobolTables:
     """The tables as C pointers -- after checking that the point range lies inside the columns the table KNOWS: tables derived from
     the engine's public behaviour (monte_carlo.SobolDirections.valid_bits < 30) hold zeros beyond, and a point index there would
-    silently repeat earlier points.  Plain arrays count as complete (30 bits)."""
+    silently repeat earlier points.  Plain arrays count as complete (30 bits).  dims_per_step: the dimensions one step takes (2 under
+    Heston, whose entry points take the number of steps where the others take the number of dimensions)."""
     bits = int(getattr(sv, "valid_bits", 30))
     if int(point_offset) + int(n_paths) > (1 << bits):
         raise ValueError(f"Sobol points [{int(point_offset)}, {int(point_offset) + int(n_paths)}) reach beyond the 2**{bits} points these tables were "
                          f"derived for: ask sobol_tables(n_steps, seed, n_points=point_offset + n_paths)")
-    sv, psv = _u32(sv)
-    shift, psh = _u32(shift)
-    return sv, psv, shift, psh
+    return _SobolTables(sv, shift, dims_per_step)
 
 
 def european_qmc(S, K, T, r, sigma, q, is_call: bool, n_paths: int, sv: np.ndarray, shift: np.ndarray,
                  point_offset: int = 0) -> Stats:
     """sv: (dims, 30) uint32 scrambled direction matrix, shift: (dims,) uint32 (see olmc.h)."""
-    sv, psv, shift, psh = _sobol_args(sv, shift, point_offset, n_paths)
-    out = Stats()
-    _check(lib().olmc_european_qmc(S, K, T, r, sigma, q, int(is_call), int(point_offset), int(n_paths), int(sv.shape[0]),
-                                   psv, psh, int(sv.shape[1]), C.byref(out)))
-    return out
+    sobol = _sobol_args(sv, shift, point_offset, n_paths)
+    return _answer(lib().olmc_european_qmc(S, K, T, r, sigma, q, int(is_call), int(point_offset), int(n_paths), *sobol.run, _byref(out := Stats())), out)
 
 
 def european_qmc_cv(S, K, T, r, sigma, q, is_call: bool, n_paths: int, sv: np.ndarray, shift: np.ndarray, point_offset: int = 0) -> CvMoments:
-    sv, psv, shift, psh = _sobol_args(sv, shift, point_offset, n_paths)
-    out = CvMoments()
-    _check(lib().olmc_european_qmc_cv(S, K, T, r, sigma, q, int(is_call), int(point_offset), int(n_paths), int(sv.shape[0]), psv, psh,
-                                      int(sv.shape[1]), C.byref(out)))
-    return out
+    sobol = _sobol_args(sv, shift, point_offset, n_paths)
+    return _answer(lib().olmc_european_qmc_cv(S, K, T, r, sigma, q, int(is_call), int(point_offset),
+                                              int(n_paths), *sobol.run, _byref(out := CvMoments())), out)
 
 
 def european_qmc_batch(options: Sequence[Tuple[float, float, float, float, float, float, bool]], n_paths: int, sv: np.ndarray, shift: np.ndarray,
                        point_offset: int = 0) -> List[Stats]:
     """k <= 16 contracts (S, K, T, r, sigma, q, is_call) on the same Sobol points, one launch (olmc_european_qmc_batch)."""
-    sv, psv, shift, psh = _sobol_args(sv, shift, point_offset, n_paths)
-    k = len(options)
-    arr = (Option * k)(*[Option(S, K, T, r, v, q, int(c), 0) for (S, K, T, r, v, q, c) in options])
+    sobol = _sobol_args(sv, shift, point_offset, n_paths)
+    arr, k = _options(options)
     out = (Stats * k)()
-    _check(lib().olmc_european_qmc_batch(arr, k, int(point_offset), int(n_paths), int(sv.shape[0]), psv, psh, int(sv.shape[1]), out))
+    _check(lib().olmc_european_qmc_batch(arr, k, int(point_offset), int(n_paths), *sobol.run, out))
     return list(out)
 
 
 def european_qmc_greeks_fd(S, K, T, r, sigma, q, is_call: bool, n_paths: int, sv: np.ndarray, shift: np.ndarray, second_order: bool,
                            want_evals: bool = True) -> Tuple[List[float], List[Stats]]:
     """As european_greeks_fd, on the Sobol points of a MCMethod.QMC pricer: the 8 / 14 bumped contracts in ONE launch."""
-    sv, psv, shift, psh = _sobol_args(sv, shift, 0, n_paths)
-    out9 = (C.c_double * 9)()
-    evals = (Stats * 14)() if want_evals else None
-    _check(lib().olmc_european_qmc_greeks_fd(S, K, T, r, sigma, q, int(is_call), int(n_paths), int(sv.shape[0]), psv, psh, int(sv.shape[1]),
-                                             int(second_order), out9, evals))
-    return list(out9), (list(evals) if want_evals else [])
+    sobol = _sobol_args(sv, shift, 0, n_paths)
+    return _greeks(want_evals, lib().olmc_european_qmc_greeks_fd, S, K, T, r, sigma, q, int(is_call), int(n_paths), *sobol.run, int(second_order))
 
 
 def european_qmc_terminal(S, T, r, sigma, q, n_paths: int, sv: np.ndarray, shift: np.ndarray,
                           point_offset: int = 0, antithetic: bool = False) -> np.ndarray:
-    sv, psv, shift, psh = _sobol_args(sv, shift, point_offset, n_paths)
+    sobol = _sobol_args(sv, shift, point_offset, n_paths)
     out = np.empty(int(n_paths) * (2 if antithetic else 1), dtype=np.float64)
-    _check(lib().olmc_european_qmc_terminal(S, T, r, sigma, q, int(point_offset), int(n_paths), int(sv.shape[0]), psv, psh,
-                                            int(sv.shape[1]), int(antithetic), out.ctypes.data_as(C.POINTER(C.c_double))))
+    _check(lib().olmc_european_qmc_terminal(S, T, r, sigma, q, int(point_offset), int(n_paths), *sobol.run, int(antithetic), _dp(out)))
     return out
 
 
 def asian(S, K, T, r, sigma, q, is_call: bool, geometric: bool, n_paths: int, n_steps: int, seed: int,
           antithetic: bool = False, path_offset: int = 0, fast: bool = False) -> Stats:
     """fast=True (arithmetic only): the fp32-exponent kernel (OLMC_AVG_ARITHMETIC_FAST); default = reference precision."""
-    out = Stats()
     kind = AVG_GEOMETRIC if geometric else (AVG_ARITHMETIC_FAST if fast else AVG_ARITHMETIC)
-    _check(lib().olmc_asian(S, K, T, r, sigma, q, int(is_call), kind,
-                            int(path_offset), int(n_paths), int(n_steps), seed64(seed), int(antithetic), C.byref(out)))
-    return out
+    return _answer(lib().olmc_asian(S, K, T, r, sigma, q, int(is_call), kind, int(path_offset), int(n_paths), int(n_steps),
+                                    seed64(seed), int(antithetic), _byref(out := Stats())), out)
+
+
+def _average(geometric: bool) -> int:
+    return AVG_GEOMETRIC if geometric else AVG_ARITHMETIC
 
 
 def asian_greeks_fd(S, K, T, r, sigma, q, is_call: bool, n_paths: int, n_steps: int, seed: int, antithetic: bool, second_order: bool,
                     want_evals: bool = True, geometric: bool = False) -> Tuple[List[float], List[Stats]]:
     """As european_greeks_fd for the Asian option (arithmetic at the reference's precision, or geometric): the 8 / 14 bumped contracts in
     ONE launch."""
-    out9 = (C.c_double * 9)()
-    evals = (Stats * 14)() if want_evals else None
-    _check(lib().olmc_asian_greeks_fd(S, K, T, r, sigma, q, int(is_call), AVG_GEOMETRIC if geometric else AVG_ARITHMETIC, int(n_paths), int(n_steps),
-                                      seed64(seed), int(antithetic), int(second_order), out9, evals))
-    return list(out9), (list(evals) if want_evals else [])
+    return _greeks(want_evals, lib().olmc_asian_greeks_fd, S, K, T, r, sigma, q, int(is_call), _average(geometric), int(n_paths), int(n_steps),
+                   seed64(seed), int(antithetic), int(second_order))
 
 
 LOOKBACK_FLOATING, LOOKBACK_FIXED = 4, 5
@@ -545,61 +575,48 @@ QMC_SEQUENTIAL, QMC_BRIDGE = 0, 1
 QMC_BRIDGE_MAX_STEPS = 1024          # OLMC_QMC_BRIDGE_MAX_STEPS
 
 
+def _construction(bridge: bool) -> int:
+    return QMC_BRIDGE if bridge else QMC_SEQUENTIAL
+
+
 def asian_qmc(S, K, T, r, sigma, q, is_call: bool, geometric: bool, n_points: int, sv: np.ndarray, shift: np.ndarray, bridge: bool = True,
               antithetic: bool = False, point_offset: int = 0) -> Stats:
     """The Asian option on scrambled-Sobol paths (olmc_asian_qmc): n_steps = sv.shape[0] dates, bridge or sequential construction."""
-    sv, psv, shift, psh = _sobol_args(sv, shift, point_offset, n_points)
-    out = Stats()
-    _check(lib().olmc_asian_qmc(S, K, T, r, sigma, q, int(is_call), AVG_GEOMETRIC if geometric else AVG_ARITHMETIC,
-                                QMC_BRIDGE if bridge else QMC_SEQUENTIAL, int(point_offset), int(n_points), int(sv.shape[0]), psv, psh,
-                                int(sv.shape[1]), int(antithetic), C.byref(out)))
-    return out
+    sobol = _sobol_args(sv, shift, point_offset, n_points)
+    return _answer(lib().olmc_asian_qmc(S, K, T, r, sigma, q, int(is_call), _average(geometric), _construction(bridge), int(point_offset), int(n_points),
+                                        *sobol.run, int(antithetic), _byref(out := Stats())), out)
 
 
 def extrema_qmc(S, K, T, r, sigma, q, is_call: bool, payoff: int, level: float, n_points: int, sv: np.ndarray, shift: np.ndarray,
                 bridge: bool = True, antithetic: bool = False, point_offset: int = 0) -> Stats:
     """A barrier (payoff = BARRIER_KINDS value, `level` from reference_barrier_level) or lookback (LOOKBACK_FLOATING / LOOKBACK_FIXED)
     option on scrambled-Sobol paths (olmc_extrema_qmc)."""
-    sv, psv, shift, psh = _sobol_args(sv, shift, point_offset, n_points)
-    out = Stats()
-    _check(lib().olmc_extrema_qmc(S, K, T, r, sigma, q, int(is_call), int(payoff), float(level), QMC_BRIDGE if bridge else QMC_SEQUENTIAL,
-                                  int(point_offset), int(n_points), int(sv.shape[0]), psv, psh, int(sv.shape[1]), int(antithetic),
-                                  C.byref(out)))
-    return out
+    sobol = _sobol_args(sv, shift, point_offset, n_points)
+    return _answer(lib().olmc_extrema_qmc(S, K, T, r, sigma, q, int(is_call), int(payoff), float(level), _construction(bridge), int(point_offset),
+                                          int(n_points), *sobol.run, int(antithetic), _byref(out := Stats())), out)
 
 
 def asian_qmc_greeks_fd(S, K, T, r, sigma, q, is_call: bool, geometric: bool, n_points: int, sv: np.ndarray, shift: np.ndarray, bridge: bool,
                         antithetic: bool, second_order: bool, want_evals: bool = True) -> Tuple[List[float], List[Stats]]:
     """As asian_greeks_fd on the Sobol points of asian_qmc: the 8 / 14 bumped contracts in ONE launch (olmc_asian_qmc_greeks_fd)."""
-    sv, psv, shift, psh = _sobol_args(sv, shift, 0, n_points)
-    out9 = (C.c_double * 9)()
-    evals = (Stats * 14)() if want_evals else None
-    _check(lib().olmc_asian_qmc_greeks_fd(S, K, T, r, sigma, q, int(is_call), AVG_GEOMETRIC if geometric else AVG_ARITHMETIC,
-                                          QMC_BRIDGE if bridge else QMC_SEQUENTIAL, int(n_points), int(sv.shape[0]), psv, psh, int(sv.shape[1]),
-                                          int(antithetic), int(second_order), out9, evals))
-    return list(out9), (list(evals) if want_evals else [])
+    sobol = _sobol_args(sv, shift, 0, n_points)
+    return _greeks(want_evals, lib().olmc_asian_qmc_greeks_fd, S, K, T, r, sigma, q, int(is_call), _average(geometric), _construction(bridge),
+                   int(n_points), *sobol.run, int(antithetic), int(second_order))
 
 
 def extrema_qmc_greeks_fd(S, K, T, r, sigma, q, is_call: bool, payoff: int, level: float, n_points: int, sv: np.ndarray, shift: np.ndarray,
                           bridge: bool, antithetic: bool, second_order: bool, want_evals: bool = True) -> Tuple[List[float], List[Stats]]:
     """As extrema_greeks_fd on the Sobol points of extrema_qmc: ONE launch (olmc_extrema_qmc_greeks_fd); `level` is every contract's."""
-    sv, psv, shift, psh = _sobol_args(sv, shift, 0, n_points)
-    out9 = (C.c_double * 9)()
-    evals = (Stats * 14)() if want_evals else None
-    _check(lib().olmc_extrema_qmc_greeks_fd(S, K, T, r, sigma, q, int(is_call), int(payoff), float(level), QMC_BRIDGE if bridge else QMC_SEQUENTIAL,
-                                            int(n_points), int(sv.shape[0]), psv, psh, int(sv.shape[1]), int(antithetic), int(second_order),
-                                            out9, evals))
-    return list(out9), (list(evals) if want_evals else [])
+    sobol = _sobol_args(sv, shift, 0, n_points)
+    return _greeks(want_evals, lib().olmc_extrema_qmc_greeks_fd, S, K, T, r, sigma, q, int(is_call), int(payoff), float(level), _construction(bridge),
+                   int(n_points), *sobol.run, int(antithetic), int(second_order))
 
 
 def extrema_greeks_fd(S, K, T, r, sigma, q, is_call: bool, payoff: int, barrier: float, n_paths: int, n_steps: int, seed: int, antithetic: bool,
                       second_order: bool, want_evals: bool = True) -> Tuple[List[float], List[Stats]]:
     """As european_greeks_fd for a barrier (payoff = BARRIER_KINDS value) or lookback (LOOKBACK_FLOATING / LOOKBACK_FIXED) option: ONE launch."""
-    out9 = (C.c_double * 9)()
-    evals = (Stats * 14)() if want_evals else None
-    _check(lib().olmc_extrema_greeks_fd(S, K, T, r, sigma, q, int(is_call), int(payoff), float(barrier), int(n_paths), int(n_steps), seed64(seed),
-                                        int(antithetic), int(second_order), out9, evals))
-    return list(out9), (list(evals) if want_evals else [])
+    return _greeks(want_evals, lib().olmc_extrema_greeks_fd, S, K, T, r, sigma, q, int(is_call), int(payoff), float(barrier), int(n_paths),
+                   int(n_steps), seed64(seed), int(antithetic), int(second_order))
 
 
 BARRIER_KINDS = {"up-and-out": 0, "up-and-in": 1, "down-and-out": 2, "down-and-in": 3}
@@ -607,190 +624,155 @@ BARRIER_KINDS = {"up-and-out": 0, "up-and-in": 1, "down-and-out": 2, "down-and-i
 
 def barrier(S, K, T, r, sigma, q, is_call: bool, level: float, kind: int, n_paths: int, n_steps: int, seed: int,
             antithetic: bool = False, path_offset: int = 0) -> Stats:
-    out = Stats()
-    _check(lib().olmc_barrier(S, K, T, r, sigma, q, int(is_call), float(level), int(kind), int(path_offset), int(n_paths),
-                              int(n_steps), seed64(seed), int(antithetic), C.byref(out)))
-    return out
+    return _answer(lib().olmc_barrier(S, K, T, r, sigma, q, int(is_call), float(level), int(kind), int(path_offset), int(n_paths), int(n_steps),
+                                      seed64(seed), int(antithetic), _byref(out := Stats())), out)
 
 
 def lookback(S, K, T, r, sigma, q, is_call: bool, fixed_strike: bool, n_paths: int, n_steps: int, seed: int,
              antithetic: bool = False, path_offset: int = 0) -> Stats:
-    out = Stats()
-    _check(lib().olmc_lookback(S, K, T, r, sigma, q, int(is_call), int(fixed_strike), int(path_offset), int(n_paths),
-                               int(n_steps), seed64(seed), int(antithetic), C.byref(out)))
-    return out
+    return _answer(lib().olmc_lookback(S, K, T, r, sigma, q, int(is_call), int(fixed_strike), int(path_offset), int(n_paths), int(n_steps),
+                                       seed64(seed), int(antithetic), _byref(out := Stats())), out)
 
 
 def autocallable(S, T, r, sigma, q, autocall_barrier, coupon_barrier, coupon_rate, ki_barrier, observation_freq: int,
                  n_paths: int, n_steps: int, seed: int, antithetic: bool = False, path_offset: int = 0) -> Stats:
-    out = Stats()
-    _check(lib().olmc_autocallable(S, T, r, sigma, q, autocall_barrier, coupon_barrier, coupon_rate, ki_barrier,
-                                   int(observation_freq), int(path_offset), int(n_paths), int(n_steps), seed64(seed),
-                                   int(antithetic), C.byref(out)))
-    return out
+    return _answer(lib().olmc_autocallable(S, T, r, sigma, q, autocall_barrier, coupon_barrier, coupon_rate, ki_barrier, int(observation_freq),
+                                           int(path_offset), int(n_paths), int(n_steps), seed64(seed), int(antithetic), _byref(out := Stats())), out)
 
 
 def cliquet(S, T, r, sigma, q, local_cap, local_floor, global_cap, global_floor, n_periods: int, n_paths: int, n_steps: int,
             seed: int, antithetic: bool = False, path_offset: int = 0) -> Stats:
-    out = Stats()
-    _check(lib().olmc_cliquet(S, T, r, sigma, q, local_cap, local_floor, global_cap, global_floor, int(n_periods),
-                              int(path_offset), int(n_paths), int(n_steps), seed64(seed), int(antithetic), C.byref(out)))
-    return out
+    return _answer(lib().olmc_cliquet(S, T, r, sigma, q, local_cap, local_floor, global_cap, global_floor, int(n_periods), int(path_offset), int(n_paths),
+                                      int(n_steps), seed64(seed), int(antithetic), _byref(out := Stats())), out)
 
 
 def autocallable_qmc(S, T, r, sigma, q, autocall_barrier, coupon_barrier, coupon_rate, ki_barrier, observation_freq: int, n_points: int,
                      sv: np.ndarray, shift: np.ndarray, bridge: bool = True, antithetic: bool = False, point_offset: int = 0) -> Stats:
     """The autocallable on scrambled-Sobol paths (olmc_autocallable_qmc): n_steps = sv.shape[0] dates, bridge or sequential construction."""
-    sv, psv, shift, psh = _sobol_args(sv, shift, point_offset, n_points)
-    out = Stats()
-    _check(lib().olmc_autocallable_qmc(S, T, r, sigma, q, autocall_barrier, coupon_barrier, coupon_rate, ki_barrier, int(observation_freq),
-                                       QMC_BRIDGE if bridge else QMC_SEQUENTIAL, int(point_offset), int(n_points), int(sv.shape[0]), psv, psh,
-                                       int(sv.shape[1]), int(antithetic), C.byref(out)))
-    return out
+    sobol = _sobol_args(sv, shift, point_offset, n_points)
+    return _answer(lib().olmc_autocallable_qmc(S, T, r, sigma, q, autocall_barrier, coupon_barrier, coupon_rate, ki_barrier, int(observation_freq),
+                                               _construction(bridge), int(point_offset), int(n_points),
+                                               *sobol.run, int(antithetic), _byref(out := Stats())), out)
 
 
 def cliquet_qmc(S, T, r, sigma, q, local_cap, local_floor, global_cap, global_floor, n_periods: int, n_points: int, sv: np.ndarray,
                 shift: np.ndarray, bridge: bool = True, antithetic: bool = False, point_offset: int = 0) -> Stats:
     """The cliquet on scrambled-Sobol paths (olmc_cliquet_qmc): n_steps = sv.shape[0] dates, bridge or sequential construction."""
-    sv, psv, shift, psh = _sobol_args(sv, shift, point_offset, n_points)
-    out = Stats()
-    _check(lib().olmc_cliquet_qmc(S, T, r, sigma, q, local_cap, local_floor, global_cap, global_floor, int(n_periods),
-                                  QMC_BRIDGE if bridge else QMC_SEQUENTIAL, int(point_offset), int(n_points), int(sv.shape[0]), psv, psh,
-                                  int(sv.shape[1]), int(antithetic), C.byref(out)))
-    return out
+    sobol = _sobol_args(sv, shift, point_offset, n_points)
+    return _answer(lib().olmc_cliquet_qmc(S, T, r, sigma, q, local_cap, local_floor, global_cap, global_floor, int(n_periods), _construction(bridge),
+                                          int(point_offset), int(n_points), *sobol.run, int(antithetic), _byref(out := Stats())), out)
 
 
 def american_lsm(S, K, T, r, sigma, q, is_call: bool, n_paths: int, n_steps: int, poly_degree: int, seed: int) -> Stats:
-    out = Stats()
-    _check(lib().olmc_american_lsm(S, K, T, r, sigma, q, int(is_call), int(n_paths), int(n_steps), int(poly_degree),
-                                   seed64(seed), C.byref(out)))
-    return out
+    return _answer(lib().olmc_american_lsm(S, K, T, r, sigma, q, int(is_call), int(n_paths), int(n_steps),
+                                           int(poly_degree), seed64(seed), _byref(out := Stats())), out)
 
 
 def american_lsm_qmc(S, K, T, r, sigma, q, is_call: bool, n_points: int, sv: np.ndarray, shift: np.ndarray, bridge: bool, poly_degree: int) -> Stats:
     """The American option (LSM) on scrambled-Sobol paths (olmc_american_lsm_qmc): n_steps = sv.shape[0] dates, points [0, n_points)."""
-    sv, psv, shift, psh = _sobol_args(sv, shift, 0, n_points)
-    out = Stats()
-    _check(lib().olmc_american_lsm_qmc(S, K, T, r, sigma, q, int(is_call), QMC_BRIDGE if bridge else QMC_SEQUENTIAL, int(n_points), int(sv.shape[0]),
-                                       psv, psh, int(sv.shape[1]), int(poly_degree), C.byref(out)))
-    return out
+    sobol = _sobol_args(sv, shift, 0, n_points)
+    return _answer(lib().olmc_american_lsm_qmc(S, K, T, r, sigma, q, int(is_call), _construction(bridge), int(n_points),
+                                               *sobol.run, int(poly_degree), _byref(out := Stats())), out)
 
 
 def exercise_boundary_qmc(S, K, T, r, sigma, q, is_call: bool, n_points: int, sv: np.ndarray, shift: np.ndarray, bridge: bool) -> np.ndarray:
     """exercise_boundary on the Sobol matrix of american_lsm_qmc (olmc_exercise_boundary_qmc)."""
-    sv, psv, shift, psh = _sobol_args(sv, shift, 0, n_points)
-    out = np.empty(int(sv.shape[0]) + 1, dtype=np.float64)
-    _check(lib().olmc_exercise_boundary_qmc(S, K, T, r, sigma, q, int(is_call), QMC_BRIDGE if bridge else QMC_SEQUENTIAL, int(n_points),
-                                            int(sv.shape[0]), psv, psh, int(sv.shape[1]), out.ctypes.data_as(C.POINTER(C.c_double))))
+    sobol = _sobol_args(sv, shift, 0, n_points)
+    out = np.empty(sobol.steps + 1, dtype=np.float64)
+    _check(lib().olmc_exercise_boundary_qmc(S, K, T, r, sigma, q, int(is_call), _construction(bridge), int(n_points), *sobol.run, _dp(out)))
     return out
 
 
 def gbm_qmc_paths(S, T, r, sigma, q, n_points: int, sv: np.ndarray, shift: np.ndarray, bridge: bool = True, path_major: bool = False) -> np.ndarray:
     """Sobol-path prices at dates 0 .. n_steps = sv.shape[0] (date 0 = spot), layouts as gbm_paths (olmc_gbm_qmc_paths)."""
-    sv, psv, shift, psh = _sobol_args(sv, shift, 0, n_points)
-    out = _path_matrix(n_points, sv.shape[0], path_major)
-    _check(lib().olmc_gbm_qmc_paths(S, T, r, sigma, q, QMC_BRIDGE if bridge else QMC_SEQUENTIAL, int(n_points), int(sv.shape[0]), psv, psh,
-                                    int(sv.shape[1]), int(path_major), out.ctypes.data_as(C.POINTER(C.c_double))))
+    sobol = _sobol_args(sv, shift, 0, n_points)
+    out = _path_matrix(n_points, sobol.steps, path_major)
+    _check(lib().olmc_gbm_qmc_paths(S, T, r, sigma, q, _construction(bridge), int(n_points), *sobol.run, int(path_major), _dp(out)))
     return out
 
 
 def jump_diffusion(S, K, T, r, sigma, q, is_call: bool, kou: bool, lambda_j, a1, a2, a3, n_paths: int, n_steps: int, seed: int,
                    path_offset: int = 0) -> Stats:
     """Merton: (a1, a2) = (mu_j, sigma_j), a3 ignored; Kou: (a1, a2, a3) = (p, eta1, eta2)."""
-    out = Stats()
-    _check(lib().olmc_jump_diffusion(S, K, T, r, sigma, q, int(is_call), int(kou), lambda_j, a1, a2, a3, int(path_offset),
-                                     int(n_paths), int(n_steps), seed64(seed), C.byref(out)))
-    return out
+    return _answer(lib().olmc_jump_diffusion(S, K, T, r, sigma, q, int(is_call), int(kou), lambda_j, a1, a2, a3, int(path_offset), int(n_paths),
+                                             int(n_steps), seed64(seed), _byref(out := Stats())), out)
 
 
 def heston(S, K, T, r, q, is_call: bool, kappa, theta, sigma_v, rho, v0, n_paths: int, n_steps: int, seed: int,
            antithetic: bool = False, path_offset: int = 0) -> Stats:
-    out = Stats()
-    _check(lib().olmc_heston(S, K, T, r, q, int(is_call), kappa, theta, sigma_v, rho, v0, int(path_offset), int(n_paths),
-                             int(n_steps), seed64(seed), int(antithetic), C.byref(out)))
-    return out
-
-
-def _heston_steps(sv) -> int:
-    if sv.shape[0] % 2:
-        raise ValueError("Heston takes two Sobol dimensions per step: the tables must hold an even number of dimensions")
-    return int(sv.shape[0]) // 2
+    return _answer(lib().olmc_heston(S, K, T, r, q, int(is_call), kappa, theta, sigma_v, rho, v0, int(path_offset), int(n_paths), int(n_steps),
+                                     seed64(seed), int(antithetic), _byref(out := Stats())), out)
 
 
 def heston_qmc(S, K, T, r, q, is_call: bool, kappa, theta, sigma_v, rho, v0, n_points: int, sv: np.ndarray, shift: np.ndarray,
                bridge: bool = True, antithetic: bool = False, point_offset: int = 0) -> Stats:
     """Heston on scrambled-Sobol paths (olmc_heston_qmc): n_steps = sv.shape[0] / 2 steps, bridge or sequential construction."""
-    sv, psv, shift, psh = _sobol_args(sv, shift, point_offset, n_points)
-    n_steps = _heston_steps(sv)
-    out = Stats()
-    _check(lib().olmc_heston_qmc(S, K, T, r, q, int(is_call), kappa, theta, sigma_v, rho, v0, QMC_BRIDGE if bridge else QMC_SEQUENTIAL,
-                                 int(point_offset), int(n_points), n_steps, psv, psh, int(sv.shape[1]), int(antithetic), C.byref(out)))
-    return out
+    sobol = _sobol_args(sv, shift, point_offset, n_points, 2)
+    return _answer(lib().olmc_heston_qmc(S, K, T, r, q, int(is_call), kappa, theta, sigma_v, rho, v0, _construction(bridge), int(point_offset), int(n_points),
+                                         *sobol.run, int(antithetic), _byref(out := Stats())), out)
 
 
 def heston_qmc_paths(S, T, r, q, kappa, theta, sigma_v, rho, v0, n_points: int, sv: np.ndarray, shift: np.ndarray, bridge: bool = True,
                      path_major: bool = False):
     """Spot and variance of the Sobol paths at dates 0 .. n_steps = sv.shape[0] / 2, layouts as heston_paths (olmc_heston_qmc_paths)."""
-    sv, psv, shift, psh = _sobol_args(sv, shift, 0, n_points)
-    n_steps = _heston_steps(sv)
-    spot = _path_matrix(n_points, n_steps, path_major)
-    var = np.empty_like(spot)
-    _check(lib().olmc_heston_qmc_paths(S, T, r, q, kappa, theta, sigma_v, rho, v0, QMC_BRIDGE if bridge else QMC_SEQUENTIAL, int(n_points),
-                                       n_steps, psv, psh, int(sv.shape[1]), int(path_major), spot.ctypes.data_as(C.POINTER(C.c_double)),
-                                       var.ctypes.data_as(C.POINTER(C.c_double))))
-    return spot, var
+    sobol = _sobol_args(sv, shift, 0, n_points, 2)
+    return _spot_and_variance(lib().olmc_heston_qmc_paths, n_points, sobol.steps, path_major, S, T, r, q, kappa, theta, sigma_v, rho, v0,
+                              _construction(bridge), int(n_points), *sobol.run)
 
 
 def heston_path_payoff(S, K, T, r, q, is_call: bool, kappa, theta, sigma_v, rho, v0, payoff: int, barrier: float, n_paths: int, n_steps: int,
                        seed: int, antithetic: bool = False, path_offset: int = 0) -> Stats:
     """An Asian (PATH_ASIAN_*), barrier (BARRIER_KINDS value, `barrier` = the level) or lookback (LOOKBACK_*) option on heston()'s paths, one
     launch (olmc_heston_path_payoff); `barrier` is ignored by the other payoffs."""
-    out = Stats()
-    _check(lib().olmc_heston_path_payoff(S, K, T, r, q, int(is_call), kappa, theta, sigma_v, rho, v0, int(payoff), float(barrier),
-                                         int(path_offset), int(n_paths), int(n_steps), seed64(seed), int(antithetic), C.byref(out)))
-    return out
+    return _answer(lib().olmc_heston_path_payoff(S, K, T, r, q, int(is_call), kappa, theta, sigma_v, rho, v0, int(payoff), float(barrier), int(path_offset),
+                                                 int(n_paths), int(n_steps), seed64(seed), int(antithetic), _byref(out := Stats())), out)
 
 
 def heston_qmc_path_payoff(S, K, T, r, q, is_call: bool, kappa, theta, sigma_v, rho, v0, payoff: int, barrier: float, n_points: int,
                            sv: np.ndarray, shift: np.ndarray, bridge: bool = True, antithetic: bool = False, point_offset: int = 0) -> Stats:
     """heston_path_payoff on heston_qmc()'s scrambled-Sobol paths (olmc_heston_qmc_path_payoff): n_steps = sv.shape[0] / 2."""
-    sv, psv, shift, psh = _sobol_args(sv, shift, point_offset, n_points)
-    n_steps = _heston_steps(sv)
-    out = Stats()
-    _check(lib().olmc_heston_qmc_path_payoff(S, K, T, r, q, int(is_call), kappa, theta, sigma_v, rho, v0, int(payoff), float(barrier),
-                                             QMC_BRIDGE if bridge else QMC_SEQUENTIAL, int(point_offset), int(n_points), n_steps, psv, psh,
-                                             int(sv.shape[1]), int(antithetic), C.byref(out)))
-    return out
+    sobol = _sobol_args(sv, shift, point_offset, n_points, 2)
+    return _answer(lib().olmc_heston_qmc_path_payoff(S, K, T, r, q, int(is_call), kappa, theta, sigma_v, rho, v0, int(payoff), float(barrier),
+                                                     _construction(bridge), int(point_offset), int(n_points),
+                                                     *sobol.run, int(antithetic), _byref(out := Stats())), out)
 
 
-def _surface_cells(strikes, steps):
-    strikes = np.ascontiguousarray(strikes, dtype=np.float64)
-    steps = np.ascontiguousarray(steps, dtype=np.int32)
-    if strikes.ndim != 1 or strikes.shape != steps.shape:
-        raise ValueError("strikes and steps must be two lists of one length: cell i is (strikes[i], steps[i])")
-    return strikes, steps, strikes.ctypes.data_as(C.POINTER(C.c_double)), steps.ctypes.data_as(C.POINTER(C.c_int32)), (Stats * max(len(strikes), 1))()
+class _SurfaceCells:
+    """The cells of a surface call as one value: it keeps the strikes and steps alive and holds `run`, the (strikes, steps, n_cells) run
+    of arguments, and `out`, the cells' Stats."""
+    __slots__ = ("strikes", "steps", "run", "out")
+
+    def __init__(self, strikes, steps):
+        self.strikes = np.ascontiguousarray(strikes, dtype=np.float64)
+        self.steps = np.ascontiguousarray(steps, dtype=np.int32)
+        if self.strikes.ndim != 1 or self.strikes.shape != self.steps.shape:
+            raise ValueError("strikes and steps must be two lists of one length: cell i is (strikes[i], steps[i])")
+        self.run = (_dp(self.strikes), _pointer(self.steps, _I32), len(self.strikes))
+        self.out = (Stats * max(len(self.strikes), 1))()
+
+    def answer(self, rc: int) -> List[Stats]:
+        """Check the return code of a surface call that was given `out`, and return one Stats per cell."""
+        if rc:
+            _check(rc)
+        return list(self.out)[:len(self.strikes)]
 
 
 def heston_surface(S, T, r, q, is_call: bool, kappa, theta, sigma_v, rho, v0, strikes, steps, n_paths: int, n_steps: int, seed: int,
                    antithetic: bool = False, path_offset: int = 0) -> List[Stats]:
     """European options at the cells (strikes[i], steps[i]) of the time grid dt = T / n_steps on heston()'s paths, one launch
     (olmc_heston_surface): at most 16 cells, in any order; the answers come in the same order."""
-    strikes, steps, pk, ps, out = _surface_cells(strikes, steps)
-    _check(lib().olmc_heston_surface(S, T, r, q, int(is_call), kappa, theta, sigma_v, rho, v0, pk, ps, len(strikes), int(path_offset),
-                                     int(n_paths), int(n_steps), seed64(seed), int(antithetic), out))
-    return list(out)[:len(strikes)]
+    cells = _SurfaceCells(strikes, steps)
+    return cells.answer(lib().olmc_heston_surface(S, T, r, q, int(is_call), kappa, theta, sigma_v, rho, v0, *cells.run, int(path_offset), int(n_paths),
+                                                  int(n_steps), seed64(seed), int(antithetic), cells.out))
 
 
 def heston_qmc_surface(S, T, r, q, is_call: bool, kappa, theta, sigma_v, rho, v0, strikes, steps, n_points: int, sv: np.ndarray,
                        shift: np.ndarray, bridge: bool = True, antithetic: bool = False, point_offset: int = 0) -> List[Stats]:
     """heston_surface on heston_qmc()'s scrambled-Sobol paths (olmc_heston_qmc_surface): n_steps = sv.shape[0] / 2 steps to T."""
-    sv, psv, shift, psh = _sobol_args(sv, shift, point_offset, n_points)
-    n_steps = _heston_steps(sv)
-    strikes, steps, pk, ps, out = _surface_cells(strikes, steps)
-    _check(lib().olmc_heston_qmc_surface(S, T, r, q, int(is_call), kappa, theta, sigma_v, rho, v0, pk, ps, len(strikes),
-                                         QMC_BRIDGE if bridge else QMC_SEQUENTIAL, int(point_offset), int(n_points), n_steps, psv, psh,
-                                         int(sv.shape[1]), int(antithetic), out))
-    return list(out)[:len(strikes)]
+    sobol = _sobol_args(sv, shift, point_offset, n_points, 2)
+    cells = _SurfaceCells(strikes, steps)
+    return cells.answer(lib().olmc_heston_qmc_surface(S, T, r, q, int(is_call), kappa, theta, sigma_v, rho, v0, *cells.run, _construction(bridge),
+                                                      int(point_offset), int(n_points), *sobol.run, int(antithetic), cells.out))
 
 
 HESTON_MAX_RECURSIONS = 6          # OLMC_HESTON_MAX_RECURSIONS
@@ -804,7 +786,7 @@ def lv_surface(vol, x_lo: float, x_hi: float, t_hi: float = 1.0):
         vol = vol[None, :]
     if vol.ndim != 2:
         raise ValueError("the local-volatility table must be [n_t][n_x]")
-    return LvSurface(vol.ctypes.data_as(C.POINTER(C.c_double)), vol.shape[1], vol.shape[0], float(x_lo), float(x_hi), float(t_hi)), vol
+    return LvSurface(_dp(vol), vol.shape[1], vol.shape[0], float(x_lo), float(x_hi), float(t_hi)), vol
 
 
 def lv_price(S, K, T, r, q, is_call: bool, table, payoff: int, barrier: float, n_paths: int, n_steps: int, seed: int, antithetic: bool = False,
@@ -812,18 +794,15 @@ def lv_price(S, K, T, r, q, is_call: bool, table, payoff: int, barrier: float, n
     """One payoff (BARRIER_KINDS value, LOOKBACK_*, PATH_ASIAN_* or LV_EUROPEAN) on local-volatility paths, one launch (ollv_price);
     `table` = (vol[n_t][n_x], x_lo, x_hi, t_hi)."""
     surf, _keep = lv_surface(*table)
-    out = Stats()
-    _check(lib().ollv_price(S, K, T, r, q, int(is_call), C.byref(surf), int(payoff), float(barrier), int(path_offset), int(n_paths), int(n_steps),
-                            seed64(seed), int(antithetic), C.byref(out)))
-    return out
+    return _answer(lib().ollv_price(S, K, T, r, q, int(is_call), _byref(surf), int(payoff), float(barrier), int(path_offset), int(n_paths), int(n_steps),
+                                    seed64(seed), int(antithetic), _byref(out := Stats())), out)
 
 
 def lv_paths(S, T, r, q, table, n_paths: int, n_steps: int, seed: int, path_major: bool = False) -> np.ndarray:
     """The spot matrix of lv_price's paths (ollv_paths), in gbm_paths' layouts."""
     surf, _keep = lv_surface(*table)
     out = _path_matrix(n_paths, n_steps, path_major)
-    _check(lib().ollv_paths(S, T, r, q, C.byref(surf), int(n_paths), int(n_steps), seed64(seed), int(path_major),
-                            out.ctypes.data_as(C.POINTER(C.c_double))))
+    _check(lib().ollv_paths(S, T, r, q, _byref(surf), int(n_paths), int(n_steps), seed64(seed), int(path_major), _dp(out)))
     return out
 
 
@@ -831,42 +810,37 @@ def lv_surface_prices(S, T, r, q, is_call: bool, table, strikes, steps, n_paths:
                       path_offset: int = 0) -> List[Stats]:
     """European options at the cells (strikes[i], steps[i]) on lv_price's paths, one launch (ollv_surface_prices): at most 16 cells."""
     surf, _keep = lv_surface(*table)
-    strikes, steps, pk, ps, out = _surface_cells(strikes, steps)
-    _check(lib().ollv_surface_prices(S, T, r, q, int(is_call), C.byref(surf), pk, ps, len(strikes), int(path_offset), int(n_paths), int(n_steps),
-                                     seed64(seed), int(antithetic), out))
-    return list(out)[:len(strikes)]
+    cells = _SurfaceCells(strikes, steps)
+    return cells.answer(lib().ollv_surface_prices(S, T, r, q, int(is_call), _byref(surf), *cells.run, int(path_offset), int(n_paths), int(n_steps),
+                                                  seed64(seed), int(antithetic), cells.out))
 
 
 def lvq_price(S, K, T, r, q, is_call: bool, table, payoff: int, barrier: float, n_points: int, sv: np.ndarray, shift: np.ndarray,
               bridge: bool = True, antithetic: bool = False, point_offset: int = 0) -> Stats:
     """lv_price on scrambled-Sobol paths (olvq_price): n_steps = sv.shape[0] dimensions, one per step; sv / shift as extrema_qmc."""
-    sv, psv, shift, psh = _sobol_args(sv, shift, point_offset, n_points)
+    sobol = _sobol_args(sv, shift, point_offset, n_points)
     surf, _keep = lv_surface(*table)
-    out = Stats()
-    _check(lib().olvq_price(S, K, T, r, q, int(is_call), C.byref(surf), int(payoff), float(barrier), QMC_BRIDGE if bridge else QMC_SEQUENTIAL,
-                            int(point_offset), int(n_points), int(sv.shape[0]), psv, psh, int(sv.shape[1]), int(antithetic), C.byref(out)))
-    return out
+    return _answer(lib().olvq_price(S, K, T, r, q, int(is_call), _byref(surf), int(payoff), float(barrier), _construction(bridge), int(point_offset),
+                                    int(n_points), *sobol.run, int(antithetic), _byref(out := Stats())), out)
 
 
 def lvq_paths(S, T, r, q, table, n_points: int, sv: np.ndarray, shift: np.ndarray, bridge: bool = True, path_major: bool = False) -> np.ndarray:
     """The spot matrix of lvq_price's points [0, n_points) (olvq_paths; the non-mirrored leg), in gbm_paths' layouts."""
-    sv, psv, shift, psh = _sobol_args(sv, shift, 0, n_points)
+    sobol = _sobol_args(sv, shift, 0, n_points)
     surf, _keep = lv_surface(*table)
-    out = _path_matrix(n_points, int(sv.shape[0]), path_major)
-    _check(lib().olvq_paths(S, T, r, q, C.byref(surf), QMC_BRIDGE if bridge else QMC_SEQUENTIAL, int(n_points), int(sv.shape[0]), psv, psh,
-                            int(sv.shape[1]), int(path_major), out.ctypes.data_as(C.POINTER(C.c_double))))
+    out = _path_matrix(n_points, sobol.steps, path_major)
+    _check(lib().olvq_paths(S, T, r, q, _byref(surf), _construction(bridge), int(n_points), *sobol.run, int(path_major), _dp(out)))
     return out
 
 
 def lvq_surface_prices(S, T, r, q, is_call: bool, table, strikes, steps, n_points: int, sv: np.ndarray, shift: np.ndarray, bridge: bool = True,
                        antithetic: bool = False, point_offset: int = 0) -> List[Stats]:
     """lv_surface_prices on lvq_price's points (olvq_surface_prices): sv.shape[0] steps to T, at most 16 cells."""
-    sv, psv, shift, psh = _sobol_args(sv, shift, point_offset, n_points)
+    sobol = _sobol_args(sv, shift, point_offset, n_points)
     surf, _keep = lv_surface(*table)
-    strikes, steps, pk, ps, out = _surface_cells(strikes, steps)
-    _check(lib().olvq_surface_prices(S, T, r, q, int(is_call), C.byref(surf), pk, ps, len(strikes), QMC_BRIDGE if bridge else QMC_SEQUENTIAL,
-                                     int(point_offset), int(n_points), int(sv.shape[0]), psv, psh, int(sv.shape[1]), int(antithetic), out))
-    return list(out)[:len(strikes)]
+    cells = _SurfaceCells(strikes, steps)
+    return cells.answer(lib().olvq_surface_prices(S, T, r, q, int(is_call), _byref(surf), *cells.run, _construction(bridge), int(point_offset), int(n_points),
+                                                  *sobol.run, int(antithetic), cells.out))
 
 
 def jd_model(kou: bool, lambda_j, a1, a2, a3=0.0) -> JdModel:
@@ -878,48 +852,40 @@ def jd_price(S, K, T, r, sigma, q, is_call: bool, model, payoff: int, barrier: f
     """One payoff (BARRIER_KINDS value, LOOKBACK_*, PATH_ASIAN_* or JD_EUROPEAN) on jump_paths' paths, one launch (oljd_price);
     `model` = (kou, lambda_j, a1, a2, a3) as jump_diffusion takes them."""
     m = jd_model(*model)
-    out = Stats()
-    _check(lib().oljd_price(S, K, T, r, sigma, q, int(is_call), C.byref(m), int(payoff), float(barrier), int(path_offset), int(n_paths),
-                            int(n_steps), seed64(seed), int(antithetic), C.byref(out)))
-    return out
+    return _answer(lib().oljd_price(S, K, T, r, sigma, q, int(is_call), _byref(m), int(payoff), float(barrier), int(path_offset), int(n_paths), int(n_steps),
+                                    seed64(seed), int(antithetic), _byref(out := Stats())), out)
 
 
 def jd_surface_prices(S, T, r, sigma, q, is_call: bool, model, strikes, steps, n_paths: int, n_steps: int, seed: int, antithetic: bool = False,
                       path_offset: int = 0) -> List[Stats]:
     """European options at the cells (strikes[i], steps[i]) on jd_price's paths, one launch (oljd_surface_prices): at most 16 cells."""
     m = jd_model(*model)
-    strikes, steps, pk, ps, out = _surface_cells(strikes, steps)
-    _check(lib().oljd_surface_prices(S, T, r, sigma, q, int(is_call), C.byref(m), pk, ps, len(strikes), int(path_offset), int(n_paths),
-                                     int(n_steps), seed64(seed), int(antithetic), out))
-    return list(out)[:len(strikes)]
+    cells = _SurfaceCells(strikes, steps)
+    return cells.answer(lib().oljd_surface_prices(S, T, r, sigma, q, int(is_call), _byref(m), *cells.run, int(path_offset), int(n_paths), int(n_steps),
+                                                  seed64(seed), int(antithetic), cells.out))
 
 
 def jd_autocallable(S, T, r, sigma, q, model, autocall_barrier, coupon_barrier, coupon_rate, ki_barrier, observation_freq: int, n_paths: int,
                     n_steps: int, seed: int, antithetic: bool = False, path_offset: int = 0) -> Stats:
     """autocallable()'s contract on jd_price's paths, one launch (oljd_autocallable)."""
     m = jd_model(*model)
-    out = Stats()
-    _check(lib().oljd_autocallable(S, T, r, sigma, q, C.byref(m), autocall_barrier, coupon_barrier, coupon_rate, ki_barrier, int(observation_freq),
-                                   int(path_offset), int(n_paths), int(n_steps), seed64(seed), int(antithetic), C.byref(out)))
-    return out
+    return _answer(lib().oljd_autocallable(S, T, r, sigma, q, _byref(m), autocall_barrier, coupon_barrier, coupon_rate, ki_barrier, int(observation_freq),
+                                           int(path_offset), int(n_paths), int(n_steps), seed64(seed), int(antithetic), _byref(out := Stats())), out)
 
 
 def jd_cliquet(S, T, r, sigma, q, model, local_cap, local_floor, global_cap, global_floor, n_periods: int, n_paths: int, n_steps: int, seed: int,
                antithetic: bool = False, path_offset: int = 0) -> Stats:
     """cliquet()'s contract on jd_price's paths, one launch (oljd_cliquet)."""
     m = jd_model(*model)
-    out = Stats()
-    _check(lib().oljd_cliquet(S, T, r, sigma, q, C.byref(m), local_cap, local_floor, global_cap, global_floor, int(n_periods), int(path_offset),
-                              int(n_paths), int(n_steps), seed64(seed), int(antithetic), C.byref(out)))
-    return out
+    return _answer(lib().oljd_cliquet(S, T, r, sigma, q, _byref(m), local_cap, local_floor, global_cap, global_floor, int(n_periods), int(path_offset),
+                                      int(n_paths), int(n_steps), seed64(seed), int(antithetic), _byref(out := Stats())), out)
 
 
 def jd_paths(S, T, r, sigma, q, model, n_paths: int, n_steps: int, seed: int, mirror: bool = False, path_major: bool = False) -> np.ndarray:
     """The spot matrix of one leg of jd_price's paths (oljd_paths), in gbm_paths' layouts: mirror=False is jump_paths' matrix."""
     m = jd_model(*model)
     out = _path_matrix(n_paths, n_steps, path_major)
-    _check(lib().oljd_paths(S, T, r, sigma, q, C.byref(m), int(n_paths), int(n_steps), seed64(seed), int(bool(mirror)), int(path_major),
-                            out.ctypes.data_as(C.POINTER(C.c_double))))
+    _check(lib().oljd_paths(S, T, r, sigma, q, _byref(m), int(n_paths), int(n_steps), seed64(seed), int(bool(mirror)), int(path_major), _dp(out)))
     return out
 
 
@@ -953,12 +919,10 @@ def heston_qmc_scenarios(scenarios, n_points: int, sv: np.ndarray, shift: np.nda
                          point_offset: int = 0) -> List[Stats]:
     """heston_scenarios on heston_qmc()'s scrambled-Sobol points (olmc_heston_qmc_scenarios): n_steps = sv.shape[0] / 2; one fill of the
     two bridges serves every recursion."""
-    sv, psv, shift, psh = _sobol_args(sv, shift, point_offset, n_points)
-    n_steps = _heston_steps(sv)
+    sobol = _sobol_args(sv, shift, point_offset, n_points, 2)
     arr, k = _scenarios(scenarios)
     out = (Stats * max(k, 1))()
-    _check(lib().olmc_heston_qmc_scenarios(arr, k, QMC_BRIDGE if bridge else QMC_SEQUENTIAL, int(point_offset), int(n_points), n_steps, psv, psh,
-                                           int(sv.shape[1]), int(antithetic), out))
+    _check(lib().olmc_heston_qmc_scenarios(arr, k, _construction(bridge), int(point_offset), int(n_points), *sobol.run, int(antithetic), out))
     return list(out)[:k]
 
 
@@ -966,23 +930,16 @@ def heston_greeks_fd(S, K, T, r, sigma, q, is_call: bool, kappa, theta, sigma_v,
                      second_order: bool, want_evals: bool = True) -> Tuple[List[float], List[Stats]]:
     """As european_greeks_fd under the Heston model with sigma -> v0 = sigma^2: the 7 / 8 / 11 / 14 bumped contracts as ONE scenario launch
     of four recursions (olmc_heston_greeks_fd)."""
-    out9 = (C.c_double * 9)()
-    evals = (Stats * 14)() if want_evals else None
-    _check(lib().olmc_heston_greeks_fd(S, K, T, r, sigma, q, int(is_call), kappa, theta, sigma_v, rho, int(n_paths), int(n_steps), seed64(seed),
-                                       int(antithetic), int(second_order), out9, evals))
-    return list(out9), (list(evals) if want_evals else [])
+    return _greeks(want_evals, lib().olmc_heston_greeks_fd, S, K, T, r, sigma, q, int(is_call), kappa, theta, sigma_v, rho, int(n_paths),
+                   int(n_steps), seed64(seed), int(antithetic), int(second_order))
 
 
 def heston_qmc_greeks_fd(S, K, T, r, sigma, q, is_call: bool, kappa, theta, sigma_v, rho, n_points: int, sv: np.ndarray, shift: np.ndarray,
                          bridge: bool, antithetic: bool, second_order: bool, want_evals: bool = True) -> Tuple[List[float], List[Stats]]:
     """heston_greeks_fd on the Sobol points of heston_qmc (olmc_heston_qmc_greeks_fd)."""
-    sv, psv, shift, psh = _sobol_args(sv, shift, 0, n_points)
-    n_steps = _heston_steps(sv)
-    out9 = (C.c_double * 9)()
-    evals = (Stats * 14)() if want_evals else None
-    _check(lib().olmc_heston_qmc_greeks_fd(S, K, T, r, sigma, q, int(is_call), kappa, theta, sigma_v, rho, QMC_BRIDGE if bridge else QMC_SEQUENTIAL,
-                                           int(n_points), n_steps, psv, psh, int(sv.shape[1]), int(antithetic), int(second_order), out9, evals))
-    return list(out9), (list(evals) if want_evals else [])
+    sobol = _sobol_args(sv, shift, 0, n_points, 2)
+    return _greeks(want_evals, lib().olmc_heston_qmc_greeks_fd, S, K, T, r, sigma, q, int(is_call), kappa, theta, sigma_v, rho,
+                   _construction(bridge), int(n_points), *sobol.run, int(antithetic), int(second_order))
 
 
 STREAM_HESTON_QE = 0x48514500      # OLMC_STREAM_HESTON_QE: counter word 3 of the QE scheme's Philox blocks
@@ -991,152 +948,117 @@ STREAM_HESTON_QE = 0x48514500      # OLMC_STREAM_HESTON_QE: counter word 3 of th
 def heston_qe_surface(S, T, r, q, is_call: bool, kappa, theta, sigma_v, rho, v0, strikes, steps, n_paths: int, n_steps: int, seed: int,
                       antithetic: bool = False, path_offset: int = 0) -> List[Stats]:
     """heston_surface by the quadratic-exponential scheme (olmc_heston_qe_surface): one Philox block per step, at most 16 cells."""
-    strikes, steps, pk, ps, out = _surface_cells(strikes, steps)
-    _check(lib().olmc_heston_qe_surface(S, T, r, q, int(is_call), kappa, theta, sigma_v, rho, v0, pk, ps, len(strikes), int(path_offset),
-                                        int(n_paths), int(n_steps), seed64(seed), int(antithetic), out))
-    return list(out)[:len(strikes)]
+    cells = _SurfaceCells(strikes, steps)
+    return cells.answer(lib().olmc_heston_qe_surface(S, T, r, q, int(is_call), kappa, theta, sigma_v, rho, v0, *cells.run, int(path_offset), int(n_paths),
+                                                     int(n_steps), seed64(seed), int(antithetic), cells.out))
 
 
 def heston_qe_qmc_surface(S, T, r, q, is_call: bool, kappa, theta, sigma_v, rho, v0, strikes, steps, n_points: int, sv: np.ndarray,
                           shift: np.ndarray, bridge: bool = False, antithetic: bool = False, point_offset: int = 0) -> List[Stats]:
     """heston_qe_surface on scrambled-Sobol points (olmc_heston_qe_qmc_surface): n_steps = sv.shape[0] / 2, sequential construction only
     (bridge=True is passed on and refused by the library)."""
-    sv, psv, shift, psh = _sobol_args(sv, shift, point_offset, n_points)
-    n_steps = _heston_steps(sv)
-    strikes, steps, pk, ps, out = _surface_cells(strikes, steps)
-    _check(lib().olmc_heston_qe_qmc_surface(S, T, r, q, int(is_call), kappa, theta, sigma_v, rho, v0, pk, ps, len(strikes),
-                                            QMC_BRIDGE if bridge else QMC_SEQUENTIAL, int(point_offset), int(n_points), n_steps, psv, psh,
-                                            int(sv.shape[1]), int(antithetic), out))
-    return list(out)[:len(strikes)]
+    sobol = _sobol_args(sv, shift, point_offset, n_points, 2)
+    cells = _SurfaceCells(strikes, steps)
+    return cells.answer(lib().olmc_heston_qe_qmc_surface(S, T, r, q, int(is_call), kappa, theta, sigma_v, rho, v0, *cells.run, _construction(bridge),
+                                                         int(point_offset), int(n_points), *sobol.run, int(antithetic), cells.out))
 
 
 HESTON_EULER, HESTON_QE = 0, 1      # olmc.h: OLMC_HESTON_EULER / OLMC_HESTON_QE
+
+
+def _scheme(qe: bool) -> int:
+    return HESTON_QE if qe else HESTON_EULER
 
 
 def heston_autocallable(S, T, r, q, kappa, theta, sigma_v, rho, v0, autocall_barrier, coupon_barrier, coupon_rate, ki_barrier,
                         observation_freq: int, n_paths: int, n_steps: int, seed: int, antithetic: bool = False, path_offset: int = 0,
                         qe: bool = False) -> Stats:
     """The autocallable on heston()'s paths (qe: on heston_qe_surface()'s), one launch (olmc_heston_autocallable)."""
-    out = Stats()
-    _check(lib().olmc_heston_autocallable(S, T, r, q, kappa, theta, sigma_v, rho, v0, autocall_barrier, coupon_barrier, coupon_rate, ki_barrier,
-                                          int(observation_freq), HESTON_QE if qe else HESTON_EULER, int(path_offset), int(n_paths), int(n_steps),
-                                          seed64(seed), int(antithetic), C.byref(out)))
-    return out
+    return _answer(lib().olmc_heston_autocallable(S, T, r, q, kappa, theta, sigma_v, rho, v0, autocall_barrier, coupon_barrier, coupon_rate, ki_barrier,
+                                                  int(observation_freq), _scheme(qe), int(path_offset), int(n_paths), int(n_steps),
+                                                  seed64(seed), int(antithetic), _byref(out := Stats())), out)
 
 
 def heston_autocallable_qmc(S, T, r, q, kappa, theta, sigma_v, rho, v0, autocall_barrier, coupon_barrier, coupon_rate, ki_barrier,
                             observation_freq: int, n_points: int, sv: np.ndarray, shift: np.ndarray, bridge: bool = True,
                             antithetic: bool = False, point_offset: int = 0, qe: bool = False) -> Stats:
     """heston_autocallable on scrambled-Sobol points (olmc_heston_autocallable_qmc): n_steps = sv.shape[0] / 2; qe takes bridge=False only."""
-    sv, psv, shift, psh = _sobol_args(sv, shift, point_offset, n_points)
-    n_steps = _heston_steps(sv)
-    out = Stats()
-    _check(lib().olmc_heston_autocallable_qmc(S, T, r, q, kappa, theta, sigma_v, rho, v0, autocall_barrier, coupon_barrier, coupon_rate,
-                                              ki_barrier, int(observation_freq), HESTON_QE if qe else HESTON_EULER,
-                                              QMC_BRIDGE if bridge else QMC_SEQUENTIAL, int(point_offset), int(n_points), n_steps, psv, psh,
-                                              int(sv.shape[1]), int(antithetic), C.byref(out)))
-    return out
+    sobol = _sobol_args(sv, shift, point_offset, n_points, 2)
+    return _answer(lib().olmc_heston_autocallable_qmc(S, T, r, q, kappa, theta, sigma_v, rho, v0, autocall_barrier, coupon_barrier, coupon_rate, ki_barrier,
+                                                      int(observation_freq), _scheme(qe), _construction(bridge), int(point_offset), int(n_points),
+                                                      *sobol.run, int(antithetic), _byref(out := Stats())), out)
 
 
 def heston_cliquet(S, T, r, q, kappa, theta, sigma_v, rho, v0, local_cap, local_floor, global_cap, global_floor, n_periods: int,
                    n_paths: int, n_steps: int, seed: int, antithetic: bool = False, path_offset: int = 0, qe: bool = False) -> Stats:
     """The cliquet on heston()'s paths (qe: on heston_qe_surface()'s), one launch (olmc_heston_cliquet)."""
-    out = Stats()
-    _check(lib().olmc_heston_cliquet(S, T, r, q, kappa, theta, sigma_v, rho, v0, local_cap, local_floor, global_cap, global_floor,
-                                     int(n_periods), HESTON_QE if qe else HESTON_EULER, int(path_offset), int(n_paths), int(n_steps),
-                                     seed64(seed), int(antithetic), C.byref(out)))
-    return out
+    return _answer(lib().olmc_heston_cliquet(S, T, r, q, kappa, theta, sigma_v, rho, v0, local_cap, local_floor, global_cap, global_floor, int(n_periods),
+                                             _scheme(qe), int(path_offset), int(n_paths), int(n_steps),
+                                             seed64(seed), int(antithetic), _byref(out := Stats())), out)
 
 
 def heston_cliquet_qmc(S, T, r, q, kappa, theta, sigma_v, rho, v0, local_cap, local_floor, global_cap, global_floor, n_periods: int,
                        n_points: int, sv: np.ndarray, shift: np.ndarray, bridge: bool = True, antithetic: bool = False,
                        point_offset: int = 0, qe: bool = False) -> Stats:
     """heston_cliquet on scrambled-Sobol points (olmc_heston_cliquet_qmc): n_steps = sv.shape[0] / 2; qe takes bridge=False only."""
-    sv, psv, shift, psh = _sobol_args(sv, shift, point_offset, n_points)
-    n_steps = _heston_steps(sv)
-    out = Stats()
-    _check(lib().olmc_heston_cliquet_qmc(S, T, r, q, kappa, theta, sigma_v, rho, v0, local_cap, local_floor, global_cap, global_floor,
-                                         int(n_periods), HESTON_QE if qe else HESTON_EULER, QMC_BRIDGE if bridge else QMC_SEQUENTIAL,
-                                         int(point_offset), int(n_points), n_steps, psv, psh, int(sv.shape[1]), int(antithetic),
-                                         C.byref(out)))
-    return out
+    sobol = _sobol_args(sv, shift, point_offset, n_points, 2)
+    return _answer(lib().olmc_heston_cliquet_qmc(S, T, r, q, kappa, theta, sigma_v, rho, v0, local_cap, local_floor, global_cap, global_floor, int(n_periods),
+                                                 _scheme(qe), _construction(bridge), int(point_offset), int(n_points),
+                                                 *sobol.run, int(antithetic), _byref(out := Stats())), out)
 
 
 def heston_qe_paths(S, T, r, q, kappa, theta, sigma_v, rho, v0, n_paths: int, n_steps: int, seed: int, path_major: bool = False):
     """Spot and variance of heston_qe_surface's paths at dates 0 .. n_steps (date 0 = (S, v0)); layouts as gbm_paths."""
-    spot = _path_matrix(n_paths, n_steps, path_major)
-    var = np.empty_like(spot)
-    _check(lib().olmc_heston_qe_paths(S, T, r, q, kappa, theta, sigma_v, rho, v0, int(n_paths), int(n_steps), seed64(seed), int(path_major),
-                                      spot.ctypes.data_as(C.POINTER(C.c_double)), var.ctypes.data_as(C.POINTER(C.c_double))))
-    return spot, var
+    return _spot_and_variance(lib().olmc_heston_qe_paths, n_paths, n_steps, path_major, S, T, r, q, kappa, theta, sigma_v, rho, v0,
+                              int(n_paths), int(n_steps), seed64(seed))
 
 
 def heston_qe_qmc_paths(S, T, r, q, kappa, theta, sigma_v, rho, v0, n_points: int, sv: np.ndarray, shift: np.ndarray, bridge: bool = False,
                         path_major: bool = False):
     """Spot and variance of heston_qe_qmc_surface's paths at dates 0 .. n_steps = sv.shape[0] / 2 (olmc_heston_qe_qmc_paths)."""
-    sv, psv, shift, psh = _sobol_args(sv, shift, 0, n_points)
-    n_steps = _heston_steps(sv)
-    spot = _path_matrix(n_points, n_steps, path_major)
-    var = np.empty_like(spot)
-    _check(lib().olmc_heston_qe_qmc_paths(S, T, r, q, kappa, theta, sigma_v, rho, v0, QMC_BRIDGE if bridge else QMC_SEQUENTIAL, int(n_points),
-                                          n_steps, psv, psh, int(sv.shape[1]), int(path_major), spot.ctypes.data_as(C.POINTER(C.c_double)),
-                                          var.ctypes.data_as(C.POINTER(C.c_double))))
-    return spot, var
+    sobol = _sobol_args(sv, shift, 0, n_points, 2)
+    return _spot_and_variance(lib().olmc_heston_qe_qmc_paths, n_points, sobol.steps, path_major, S, T, r, q, kappa, theta, sigma_v, rho, v0,
+                              _construction(bridge), int(n_points), *sobol.run)
 
 
 def multi_gpu_european(S, K, T, r, sigma, q, is_call: bool, n_paths: int, n_steps: int, seed: int, antithetic: bool,
                        n_gpus: int) -> Stats:
-    out = Stats()
-    _check(lib().olmc_multi_gpu_european(S, K, T, r, sigma, q, int(is_call), int(n_paths), int(n_steps), seed64(seed),
-                                         int(antithetic), int(n_gpus), C.byref(out)))
-    return out
+    return _answer(lib().olmc_multi_gpu_european(S, K, T, r, sigma, q, int(is_call), int(n_paths), int(n_steps), seed64(seed),
+                                                 int(antithetic), int(n_gpus), _byref(out := Stats())), out)
 
 
 def multi_gpu_greeks_fd(S, K, T, r, sigma, q, is_call: bool, n_paths: int, n_steps: int, seed: int, second_order: bool, n_gpus: int,
                         want_evals: bool = True) -> Tuple[List[float], List[Stats]]:
     """As european_greeks_fd over n_gpus devices of this process: one launch per rank, ONE all-reduce of the 2 nsets + 1 sums."""
-    out9 = (C.c_double * 9)()
-    evals = (Stats * 14)() if want_evals else None
-    _check(lib().olmc_multi_gpu_greeks_fd(S, K, T, r, sigma, q, int(is_call), int(n_paths), int(n_steps), seed64(seed), int(second_order),
-                                          int(n_gpus), out9, evals))
-    return list(out9), (list(evals) if want_evals else [])
+    return _greeks(want_evals, lib().olmc_multi_gpu_greeks_fd, S, K, T, r, sigma, q, int(is_call), int(n_paths), int(n_steps), seed64(seed),
+                   int(second_order), int(n_gpus))
 
 
 def multi_gpu_european_cv(S, K, T, r, sigma, q, is_call: bool, n_paths: int, n_steps: int, seed: int, antithetic: bool, n_gpus: int) -> CvMoments:
-    out = CvMoments()
-    _check(lib().olmc_multi_gpu_european_cv(S, K, T, r, sigma, q, int(is_call), int(n_paths), int(n_steps), seed64(seed), int(antithetic),
-                                            int(n_gpus), C.byref(out)))
-    return out
+    return _answer(lib().olmc_multi_gpu_european_cv(S, K, T, r, sigma, q, int(is_call), int(n_paths), int(n_steps), seed64(seed),
+                                                    int(antithetic), int(n_gpus), _byref(out := CvMoments())), out)
 
 
 def multi_gpu_european_qmc(S, K, T, r, sigma, q, is_call: bool, n_paths: int, sv: np.ndarray, shift: np.ndarray, n_gpus: int) -> Stats:
     """As european_qmc over n_gpus devices of this process: rank d prices points [d N / P, (d + 1) N / P), one all-reduce of 3 sums."""
-    sv, psv, shift, psh = _sobol_args(sv, shift, 0, n_paths)
-    out = Stats()
-    _check(lib().olmc_multi_gpu_european_qmc(S, K, T, r, sigma, q, int(is_call), int(n_paths), int(sv.shape[0]), psv, psh, int(sv.shape[1]),
-                                             int(n_gpus), C.byref(out)))
-    return out
+    sobol = _sobol_args(sv, shift, 0, n_paths)
+    return _answer(lib().olmc_multi_gpu_european_qmc(S, K, T, r, sigma, q, int(is_call), int(n_paths), *sobol.run, int(n_gpus), _byref(out := Stats())), out)
 
 
 def multi_gpu_european_qmc_greeks_fd(S, K, T, r, sigma, q, is_call: bool, n_paths: int, sv: np.ndarray, shift: np.ndarray, second_order: bool,
                                      n_gpus: int, want_evals: bool = True) -> Tuple[List[float], List[Stats]]:
     """As european_qmc_greeks_fd over n_gpus devices of this process: every rank prices the 8 / 14 contracts on its block of the
     Sobol points in one launch, one all-reduce of 17 / 33 sums."""
-    sv, psv, shift, psh = _sobol_args(sv, shift, 0, n_paths)
-    out9 = (C.c_double * 9)()
-    evals = (Stats * 14)() if want_evals else None
-    _check(lib().olmc_multi_gpu_european_qmc_greeks_fd(S, K, T, r, sigma, q, int(is_call), int(n_paths), int(sv.shape[0]), psv, psh,
-                                                       int(sv.shape[1]), int(second_order), int(n_gpus), out9, evals))
-    return list(out9), (list(evals) if want_evals else [])
+    sobol = _sobol_args(sv, shift, 0, n_paths)
+    return _greeks(want_evals, lib().olmc_multi_gpu_european_qmc_greeks_fd, S, K, T, r, sigma, q, int(is_call), int(n_paths), *sobol.run,
+                   int(second_order), int(n_gpus))
 
 
 def multi_gpu_european_qmc_cv(S, K, T, r, sigma, q, is_call: bool, n_paths: int, sv: np.ndarray, shift: np.ndarray, n_gpus: int) -> CvMoments:
     """As european_qmc_cv over n_gpus devices of this process: one all-reduce of the five moments and n."""
-    sv, psv, shift, psh = _sobol_args(sv, shift, 0, n_paths)
-    out = CvMoments()
-    _check(lib().olmc_multi_gpu_european_qmc_cv(S, K, T, r, sigma, q, int(is_call), int(n_paths), int(sv.shape[0]), psv, psh, int(sv.shape[1]),
-                                                int(n_gpus), C.byref(out)))
-    return out
+    sobol = _sobol_args(sv, shift, 0, n_paths)
+    return _answer(lib().olmc_multi_gpu_european_qmc_cv(S, K, T, r, sigma, q, int(is_call), int(n_paths),
+                                                        *sobol.run, int(n_gpus), _byref(out := CvMoments())), out)
 
 
 def multi_gpu_spans() -> dict:
@@ -1150,22 +1072,19 @@ def combine_stats(parts: Sequence[Tuple[float, float, int]], r: float, T: float)
     """Pure host function: needs the library but no device."""
     k = len(parts)
     arr = (Stats * k)(*[Stats(s, ss, int(n), 0.0, 0.0) for (s, ss, n) in parts])
-    out = Stats()
-    _check(load_library().olmc_combine_stats(arr, k, r, T, C.byref(out)))
-    return out
+    return _answer(load_library().olmc_combine_stats(arr, k, r, T, _byref(out := Stats())), out)
 
 
 def philox_words(seed: int, path_offset: int, n_paths: int, block0: int, n_blocks: int, tag: int = 0) -> np.ndarray:
     out = np.empty((int(n_paths), int(n_blocks), 4), dtype=np.uint32)
     _check(lib().olmc_philox_words(seed64(seed), int(path_offset), int(n_paths), int(block0), int(n_blocks), int(tag),
-                                   out.ctypes.data_as(C.POINTER(C.c_uint32))))
+                                   _pointer(out, C.c_uint32)))
     return out
 
 
 def normals(seed: int, path_offset: int, n_paths: int, n_steps: int) -> np.ndarray:
     out = np.empty((int(n_paths), int(n_steps)), dtype=np.float32)
-    _check(lib().olmc_normals(seed64(seed), int(path_offset), int(n_paths), int(n_steps),
-                              out.ctypes.data_as(C.POINTER(C.c_float))))
+    _check(lib().olmc_normals(seed64(seed), int(path_offset), int(n_paths), int(n_steps), _pointer(out, C.c_float)))
     return out
 
 

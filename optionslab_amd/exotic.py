@@ -19,6 +19,7 @@ from typing import Literal, Optional
 import numpy as np
 
 from . import _hip
+from ._paths import _barrier_kind, _check_barrier, _check_sizes, _result, _seed
 from .black_scholes import _ncdf
 
 
@@ -47,9 +48,18 @@ def _qmc_tables(method: str, path_construction: str, n_paths: int, n_steps: int,
         raise ValueError(f"path_construction='bridge' takes at most {_hip.QMC_BRIDGE_MAX_STEPS} steps; use 'sequential'")
     if n_paths > 1 << 30:
         raise ValueError("method='qmc' takes at most 2**30 paths (Sobol points)")
-    seed = seed if seed is not None else int(np.random.default_rng().integers(0, 2**31))
-    sv, shift = sobol_tables(n_steps * dims_per_step, seed, n_paths)
+    sv, shift = sobol_tables(n_steps * dims_per_step, _seed(seed), n_paths)
     return sv, shift, bridge
+
+
+def _draws(method: str, path_construction: str, n_paths: int, n_steps: int, seed: Optional[int], dims_per_step: int = 1):
+    """(sobol, run): the arguments a binding takes between its contract and its antithetic or layout flag -- on Sobol points
+    (True, (n_paths, sv, shift, bridge)), else (False, (n_paths, n_steps, seed)).  The refusals are _qmc_tables'; seed=None draws one
+    seed here, so a caller that asks once launches every cut of a surface or scenario set on the same draws."""
+    qmc = _qmc_tables(method, path_construction, n_paths, n_steps, seed, dims_per_step)
+    if qmc is not None:
+        return True, (n_paths, *qmc)
+    return False, (n_paths, n_steps, _seed(seed))
 
 
 @dataclass
@@ -80,24 +90,14 @@ class AsianOption:
         one: for Sobol points it is not a confidence interval (it overstates the error).
         Refused (ValueError, before the device is touched): an unknown method or path_construction, method="qmc" with
         precision="fp32", n_steps > 21201 with method="qmc", n_steps > 1024 with the bridge."""
-        if n_paths < 1 or n_steps < 1:
-            raise ValueError("n_paths and n_steps must be >= 1")
+        _check_sizes(n_paths, n_steps)
         if precision not in ("fp64", "fp32"):
             raise ValueError("precision must be 'fp64' or 'fp32'")
         _qmc_precision(method, precision)
-        qmc = _qmc_tables(method, path_construction, n_paths, n_steps, self.seed)
-        if qmc is not None:
-            sv, shift, bridge = qmc
-            st = _hip.asian_qmc(self.S, self.K, self.T, self.r, self.sigma, self.q, option_type == "call", avg_type != "arithmetic",
-                                n_paths, sv, shift, bridge, antithetic)
-            return (np.float64(st.price), float(st.std_error)) if return_error else np.float64(st.price)
-        # seed=None: the reference leaves the global RandomState unseeded (:51-52) => fresh draw
-        seed = self.seed if self.seed is not None else int(np.random.default_rng().integers(0, 2**31))
-        st = _hip.asian(self.S, self.K, self.T, self.r, self.sigma, self.q, option_type == "call",
-                        avg_type != "arithmetic", n_paths, n_steps, seed, antithetic, fast=precision == "fp32")
-        if return_error:
-            return np.float64(st.price), float(st.std_error)
-        return np.float64(st.price)
+        sobol, run = _draws(method, path_construction, n_paths, n_steps, self.seed)      # seed=None: a fresh draw, as the reference's unseeded RandomState (:51-52)
+        contract = (self.S, self.K, self.T, self.r, self.sigma, self.q, option_type == "call", avg_type != "arithmetic")
+        st = _hip.asian_qmc(*contract, *run, antithetic) if sobol else _hip.asian(*contract, *run, antithetic, fast=precision == "fp32")
+        return _result(st, return_error)
 
     def price_geometric_closed_form(self, option_type: Literal["call", "put"] = "call") -> float:
         """exotic_options.py:133-160"""
@@ -153,23 +153,14 @@ class BarrierOption:
               option_type: Literal["call", "put"] = "call", antithetic: bool = False, return_error: bool = False,
               method: Literal["pseudo", "qmc"] = "pseudo", path_construction: Literal["bridge", "sequential"] = "bridge"):
         """method, path_construction (additive): scrambled-Sobol paths, as AsianOption.price."""
-        if self.barrier <= 0:                       # :195-196
-            raise ValueError("Barrier must be positive")
-        if n_paths < 1 or n_steps < 1:
-            raise ValueError("n_paths and n_steps must be >= 1")
-        # the reference dispatches on startswith("up") / endswith("out") (:201-212)
-        kind = (0 if barrier_type.startswith("up") else 2) + (0 if barrier_type.endswith("out") else 1)
-        qmc = _qmc_tables(method, path_construction, n_paths, n_steps, self.seed)
+        _check_barrier(self.barrier)
+        _check_sizes(n_paths, n_steps)
+        kind = _barrier_kind(barrier_type)
+        sobol, run = _draws(method, path_construction, n_paths, n_steps, self.seed)
         level = reference_barrier_level(self.S, self.barrier, barrier_type)
-        if qmc is not None:
-            sv, shift, bridge = qmc
-            st = _hip.extrema_qmc(self.S, self.K, self.T, self.r, self.sigma, self.q, option_type == "call", kind, level, n_paths, sv, shift,
-                                  bridge, antithetic)
-            return (np.float64(st.price), float(st.std_error)) if return_error else np.float64(st.price)
-        seed = self.seed if self.seed is not None else int(np.random.default_rng().integers(0, 2**31))
-        st = _hip.barrier(self.S, self.K, self.T, self.r, self.sigma, self.q, option_type == "call", level, kind,
-                          n_paths, n_steps, seed, antithetic)
-        return (np.float64(st.price), float(st.std_error)) if return_error else np.float64(st.price)
+        contract = (self.S, self.K, self.T, self.r, self.sigma, self.q, option_type == "call")
+        st = _hip.extrema_qmc(*contract, kind, level, *run, antithetic) if sobol else _hip.barrier(*contract, level, kind, *run, antithetic)
+        return _result(st, return_error)
 
 
 @dataclass
@@ -188,19 +179,15 @@ class LookbackOption:
               option_type: Literal["call", "put"] = "call", antithetic: bool = False, return_error: bool = False,
               method: Literal["pseudo", "qmc"] = "pseudo", path_construction: Literal["bridge", "sequential"] = "bridge"):
         """method, path_construction (additive): scrambled-Sobol paths, as AsianOption.price."""
-        if n_paths < 1 or n_steps < 1:
-            raise ValueError("n_paths and n_steps must be >= 1")
-        qmc = _qmc_tables(method, path_construction, n_paths, n_steps, self.seed)
-        if qmc is not None:
-            sv, shift, bridge = qmc
-            st = _hip.extrema_qmc(self.S, self.K, self.T, self.r, self.sigma, self.q, option_type == "call",
-                                  _hip.LOOKBACK_FIXED if lookback_type != "floating" else _hip.LOOKBACK_FLOATING, 0.0, n_paths, sv, shift,
-                                  bridge, antithetic)
-            return (np.float64(st.price), float(st.std_error)) if return_error else np.float64(st.price)
-        seed = self.seed if self.seed is not None else int(np.random.default_rng().integers(0, 2**31))
-        st = _hip.lookback(self.S, self.K, self.T, self.r, self.sigma, self.q, option_type == "call",
-                           lookback_type != "floating", n_paths, n_steps, seed, antithetic)
-        return (np.float64(st.price), float(st.std_error)) if return_error else np.float64(st.price)
+        _check_sizes(n_paths, n_steps)
+        sobol, run = _draws(method, path_construction, n_paths, n_steps, self.seed)
+        contract = (self.S, self.K, self.T, self.r, self.sigma, self.q, option_type == "call")
+        fixed = lookback_type != "floating"                 # anything but "floating" is the fixed strike, as the reference's else branch
+        if sobol:
+            st = _hip.extrema_qmc(*contract, _hip.LOOKBACK_FIXED if fixed else _hip.LOOKBACK_FLOATING, 0.0, *run, antithetic)
+        else:
+            st = _hip.lookback(*contract, fixed, *run, antithetic)
+        return _result(st, return_error)
 
 
 @dataclass
@@ -221,34 +208,24 @@ class AmericanOption:
         """method, path_construction (additive): "qmc" prices on scrambled-Sobol paths, as AsianOption.price (the seed is the scramble
         seed; the standard error is the naive per-path one), with the same regression as the Philox paths (include/olmc.h "quasi-Monte
         Carlo path matrix").  Refused (ValueError, before the device is touched) as there."""
-        if n_paths < 1 or n_steps < 1:
-            raise ValueError("n_paths and n_steps must be >= 1")
-        qmc = _qmc_tables(method, path_construction, n_paths, n_steps, self.seed)
-        if qmc is not None:
-            sv, shift, bridge = qmc
-            st = _hip.american_lsm_qmc(self.S, self.K, self.T, self.r, self.sigma, self.q, option_type == "call", n_paths, sv, shift, bridge,
-                                       poly_degree)
-            return (np.float64(st.price), float(st.std_error)) if return_error else np.float64(st.price)
-        seed = self.seed if self.seed is not None else int(np.random.default_rng().integers(0, 2**31))
-        st = _hip.american_lsm(self.S, self.K, self.T, self.r, self.sigma, self.q, option_type == "call", n_paths, n_steps,
-                               poly_degree, seed)
-        return (np.float64(st.price), float(st.std_error)) if return_error else np.float64(st.price)
+        _check_sizes(n_paths, n_steps)
+        sobol, run = _draws(method, path_construction, n_paths, n_steps, self.seed)
+        contract = (self.S, self.K, self.T, self.r, self.sigma, self.q, option_type == "call")
+        if sobol:
+            st = _hip.american_lsm_qmc(*contract, *run, poly_degree)
+        else:
+            st = _hip.american_lsm(*contract, n_paths, n_steps, poly_degree, run[2])         # the seed comes last there
+        return _result(st, return_error)
 
     def early_exercise_boundary(self, n_paths: int = 10000, n_steps: int = 50, option_type: Literal["call", "put"] = "put",
                                 method: Literal["pseudo", "qmc"] = "pseudo", path_construction: Literal["bridge", "sequential"] = "bridge"):
         """exotic_options.py:309-345: (times, boundary): per date the 10th (put) / 90th (call) percentile of the
         in-the-money simulated prices, NaN where none is; selected on the device from the LSM path set.
         method, path_construction (additive): the Sobol path set of price(method="qmc")."""
-        if n_paths < 1 or n_steps < 1:
-            raise ValueError("n_paths and n_steps must be >= 1")
-        qmc = _qmc_tables(method, path_construction, n_paths, n_steps, self.seed)
-        if qmc is not None:
-            sv, shift, bridge = qmc
-            boundary = _hip.exercise_boundary_qmc(self.S, self.K, self.T, self.r, self.sigma, self.q, option_type == "call", n_paths, sv, shift,
-                                                  bridge)
-            return np.linspace(0, self.T, n_steps + 1), boundary
-        seed = self.seed if self.seed is not None else int(np.random.default_rng().integers(0, 2**31))
-        boundary = _hip.exercise_boundary(self.S, self.K, self.T, self.r, self.sigma, self.q, option_type == "call", n_paths, n_steps, seed)
+        _check_sizes(n_paths, n_steps)
+        sobol, run = _draws(method, path_construction, n_paths, n_steps, self.seed)
+        boundary = (_hip.exercise_boundary_qmc if sobol else _hip.exercise_boundary)(self.S, self.K, self.T, self.r, self.sigma, self.q,
+                                                                                    option_type == "call", *run)
         return np.linspace(0, self.T, n_steps + 1), boundary
 
 
@@ -283,21 +260,14 @@ class AutocallableOption:
               path_construction: Literal["bridge", "sequential"] = "bridge", **kwargs):
         """method, path_construction (additive): scrambled-Sobol paths, as AsianOption.price (the seed is the scramble seed, the
         standard error the naive per-path one; refusals as there).  **kwargs: the ExoticAdapter's option_type, unread."""
-        if n_paths < 1 or n_steps < 1:
-            raise ValueError("n_paths and n_steps must be >= 1")
-        qmc = _qmc_tables(method, path_construction, n_paths, n_steps, self.seed)
+        _check_sizes(n_paths, n_steps)
+        sobol, run = _draws(method, path_construction, n_paths, n_steps, self.seed)
         autocall_barrier = self.autocall_barrier
         if observation_freq > n_steps:                  # no observation date: nothing redeems early (exotic_options.py:442, 448)
             observation_freq, autocall_barrier = n_steps, math.inf
-        if qmc is not None:
-            sv, shift, bridge = qmc
-            st = _hip.autocallable_qmc(self.S, self.T, self.r, self.sigma, self.q, autocall_barrier, self.coupon_barrier, self.coupon_rate,
-                                       self.ki_barrier, observation_freq, n_paths, sv, shift, bridge, antithetic)
-            return (np.float64(st.price), float(st.std_error)) if return_error else np.float64(st.price)
-        seed = self.seed if self.seed is not None else int(np.random.default_rng().integers(0, 2**31))
-        st = _hip.autocallable(self.S, self.T, self.r, self.sigma, self.q, autocall_barrier, self.coupon_barrier,
-                               self.coupon_rate, self.ki_barrier, observation_freq, n_paths, n_steps, seed, antithetic)
-        return (np.float64(st.price), float(st.std_error)) if return_error else np.float64(st.price)
+        st = (_hip.autocallable_qmc if sobol else _hip.autocallable)(self.S, self.T, self.r, self.sigma, self.q, autocall_barrier, self.coupon_barrier,
+                                                                     self.coupon_rate, self.ki_barrier, observation_freq, *run, antithetic)
+        return _result(st, return_error)
 
 
 @dataclass
@@ -321,18 +291,11 @@ class CliquetOption:
               path_construction: Literal["bridge", "sequential"] = "bridge", **kwargs):
         """method, path_construction (additive): scrambled-Sobol paths, as AsianOption.price (the seed is the scramble seed, the
         standard error the naive per-path one; refusals as there).  **kwargs: the ExoticAdapter's option_type, unread."""
-        if n_paths < 1 or n_steps < 1:
-            raise ValueError("n_paths and n_steps must be >= 1")
-        qmc = _qmc_tables(method, path_construction, n_paths, n_steps, self.seed)
-        if qmc is not None:
-            sv, shift, bridge = qmc
-            st = _hip.cliquet_qmc(self.S, self.T, self.r, self.sigma, self.q, self.local_cap, self.local_floor, self.global_cap,
-                                  self.global_floor, n_periods, n_paths, sv, shift, bridge, antithetic)
-            return (np.float64(st.price), float(st.std_error)) if return_error else np.float64(st.price)
-        seed = self.seed if self.seed is not None else int(np.random.default_rng().integers(0, 2**31))
-        st = _hip.cliquet(self.S, self.T, self.r, self.sigma, self.q, self.local_cap, self.local_floor, self.global_cap,
-                          self.global_floor, n_periods, n_paths, n_steps, seed, antithetic)
-        return (np.float64(st.price), float(st.std_error)) if return_error else np.float64(st.price)
+        _check_sizes(n_paths, n_steps)
+        sobol, run = _draws(method, path_construction, n_paths, n_steps, self.seed)
+        st = (_hip.cliquet_qmc if sobol else _hip.cliquet)(self.S, self.T, self.r, self.sigma, self.q, self.local_cap, self.local_floor,
+                                                           self.global_cap, self.global_floor, n_periods, *run, antithetic)
+        return _result(st, return_error)
 
 
 def price_barrier(S: float, K: float, T: float, r: float, sigma: float, barrier: float, barrier_type: str = "up-and-out",

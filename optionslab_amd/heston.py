@@ -23,8 +23,9 @@ from typing import Tuple, Literal, Optional
 import numpy as np
 
 from . import _hip
+from ._paths import _SURFACE_CELLS, _asian_payoff, _barrier_kind, _check_barrier, _check_sizes, _fill_surface, _lookback_payoff, _result, _seed, _strike_list
+from ._paths import _grid_steps, _surface_launches, _surface_steps      # noqa: F401 -- the surface grid moved there; its names stay importable from here
 
-_SURFACE_CELLS = 16          # cells of one launch (OLMC_MAX_BATCH)
 _SCENARIO_KEYS = ("kappa", "theta", "sigma_v", "rho", "v0")
 _STEPS_PER_YEAR = {"euler": 64, "qe": 16}      # calibrate_heston's grid when n_steps is None
 
@@ -34,6 +35,32 @@ def _qmc_tables(method: str, path_construction: str, n_paths: int, n_steps: int,
     from .exotic import _qmc_tables as tables
 
     return tables(method, path_construction, n_paths, n_steps, seed, dims_per_step=2)
+
+
+def _draws(method: str, path_construction: str, n_paths: int, n_steps: int, seed: Optional[int]):
+    """exotic._draws with two Sobol dimensions per step: on Sobol points (True, (n_paths, sv, shift, bridge)), else (False, (n_paths,
+    n_steps, seed)) -- what every Heston binding takes between its contract and its antithetic or layout flag."""
+    from .exotic import _draws as draws
+
+    return draws(method, path_construction, n_paths, n_steps, seed, dims_per_step=2)
+
+
+# what -> _hip's wrapper by (qe, sobol): Euler or QE, on Philox draws or Sobol points.  The scenario kernels, the path payoffs and the
+# plain price have no QE form (scheme="qe" prices through the one-cell surface).
+_BINDINGS = {
+    "price": {(False, False): "heston", (False, True): "heston_qmc"},
+    "path_payoff": {(False, False): "heston_path_payoff", (False, True): "heston_qmc_path_payoff"},
+    "scenarios": {(False, False): "heston_scenarios", (False, True): "heston_qmc_scenarios"},
+    "surface": {(False, False): "heston_surface", (False, True): "heston_qmc_surface",
+                (True, False): "heston_qe_surface", (True, True): "heston_qe_qmc_surface"},
+    "paths": {(False, False): "heston_paths", (False, True): "heston_qmc_paths",
+              (True, False): "heston_qe_paths", (True, True): "heston_qe_qmc_paths"},
+}
+
+
+def _binding(what: str, sobol: bool, qe: bool = False):
+    """The four-way choice, written once (looked up in _hip at the call, as a plain _hip.name would be)."""
+    return getattr(_hip, _BINDINGS[what][qe, sobol])
 
 
 def _check_scheme(scheme: str, method: str, path_construction: str) -> bool:
@@ -74,50 +101,6 @@ def _scenario_launches(keys, max_scenarios: int = _SURFACE_CELLS, max_recursions
     return launches
 
 
-def _surface_steps(maturities, n_steps: int) -> Tuple[float, list]:
-    """(T, the grid step of every maturity): T = max(maturities), dt = T / n_steps, maturity T_j sits at step m = round(T_j / dt) and
-    must lie on the grid (m >= 1, |m dt - T_j| <= 1e-9 T).  ValueError names the maturity that does not."""
-    mats = [float(t) for t in np.asarray(maturities, dtype=np.float64).ravel()]
-    if not mats:
-        raise ValueError("maturities must not be empty")
-    for t in mats:
-        if not t > 0.0:                                   # NaN included
-            raise ValueError(f"maturity {t!r} must be > 0")
-    if n_steps < 1:
-        raise ValueError("n_paths and n_steps must be >= 1")
-    T = max(mats)
-    dt = T / n_steps
-    steps = []
-    for t in mats:
-        m = int(round(t / dt))
-        if m < 1 or m > n_steps or abs(m * dt - t) > 1e-9 * T:
-            raise ValueError(f"maturity {t!r} is not on the grid of {n_steps} steps to T = {T!r} (dt = {dt!r})")
-        steps.append(m)
-    return T, steps
-
-
-def _surface_launches(steps, n_strikes: int):
-    """The cells (i, j) = (strike index, maturity index) of a surface cut into launches: sorted by step (then maturity index, then
-    strike index), at most 16 cells each -- every cell once; a launch's step loop ends at its own last step."""
-    cells = sorted(((steps[j], j, i) for j in range(len(steps)) for i in range(n_strikes)))
-    return [[(i, j) for _m, j, i in cells[a:a + _SURFACE_CELLS]] for a in range(0, len(cells), _SURFACE_CELLS)]
-
-
-def _grid_steps(maturities, per_year: int = 64, cap: int = 1024) -> int:
-    """The smallest n_steps <= cap with at least per_year steps per year to the longest maturity on whose grid every maturity lies."""
-    mats = [float(t) for t in np.asarray(maturities, dtype=np.float64).ravel()]
-    if not mats or not all(t > 0.0 for t in mats):
-        raise ValueError("maturities must be a non-empty list of positive times")
-    T = max(mats)
-    for n in range(max(1, int(np.ceil(per_year * T - 1e-9))), cap + 1):
-        try:
-            _surface_steps(mats, n)
-        except ValueError:
-            continue
-        return n
-    raise ValueError(f"no grid of at most {cap} steps to T = {T!r} holds every maturity of {mats!r}: pass n_steps, or move the maturities")
-
-
 @dataclass
 class HestonPricer:
     kappa: float
@@ -141,6 +124,9 @@ class HestonPricer:
         if feller < 0:
             warnings.warn(f"Feller condition not satisfied (2κθ - σᵥ² = {feller:.4f} < 0). "
                           "Variance may hit zero in simulations.")
+
+    def _model(self):
+        return self.kappa, self.theta, self.sigma_v, self.rho, self.v0
 
     def _characteristic_function(self, u, S, K, T, r, q):       # :80-129
         kappa, theta, sigma_v, rho, v0 = self.kappa, self.theta, self.sigma_v, self.rho, self.v0
@@ -195,23 +181,13 @@ class HestonPricer:
         step, its own tag) and its Sobol draws (dimension 2t = the variance's uniform, 2t + 1 = the spot's normal) are not Euler's, so
         equal seeds give other paths.  With method="qmc" it takes path_construction="sequential" only: the default "bridge" is refused
         (ValueError, before the device is touched), as is an unknown scheme."""
-        if n_paths < 1 or n_steps < 1:
-            raise ValueError("n_paths and n_steps must be >= 1")
+        _check_sizes(n_paths, n_steps)
         if _check_scheme(scheme, method, path_construction):
             prices, errors = self.price_surface(S, [K], [T], r, q, option_type, n_paths, n_steps, seed, antithetic, return_error=True,
                                                 method=method, path_construction=path_construction, scheme="qe")
             return (np.float64(prices[0, 0]), float(errors[0, 0])) if return_error else np.float64(prices[0, 0])
-        qmc = _qmc_tables(method, path_construction, n_paths, n_steps, seed)
-        if qmc is not None:
-            sv, shift, bridge = qmc
-            st = _hip.heston_qmc(S, K, T, r, q, option_type == "call", self.kappa, self.theta, self.sigma_v, self.rho, self.v0, n_paths,
-                                 sv, shift, bridge, antithetic)
-            return (np.float64(st.price), float(st.std_error)) if return_error else np.float64(st.price)
-        s = seed if seed is not None else int(np.random.default_rng().integers(0, 2**31))
-        st = _hip.heston(S, K, T, r, q, option_type == "call", self.kappa, self.theta, self.sigma_v, self.rho, self.v0,
-                         n_paths, n_steps, s, antithetic)
-        return (np.float64(st.price), float(st.std_error)) if return_error else np.float64(st.price)
-
+        sobol, run = _draws(method, path_construction, n_paths, n_steps, seed)
+        return _result(_binding("price", sobol)(S, K, T, r, q, option_type == "call", *self._model(), *run, antithetic), return_error)
 
     def price_surface(self, S: float, strikes, maturities, r: float, q: float = 0.0, option_type: Literal["call", "put"] = "call",
                       n_paths: int = 100000, n_steps: int = 252, seed: Optional[int] = None, antithetic: bool = False,
@@ -240,33 +216,13 @@ class HestonPricer:
         scheme as price_monte_carlo: with "qe" the cells are read-outs of simulate_paths(..., scheme="qe")'s columns in the same way
         (the launches, the ties to the matrix, the independence of the cells and the shards' sums all hold as above)."""
         qe = _check_scheme(scheme, method, path_construction)
-        ks = [float(k) for k in np.asarray(strikes, dtype=np.float64).ravel()]
-        if not ks:
-            raise ValueError("strikes must not be empty")
-        if n_paths < 1 or n_steps < 1:
-            raise ValueError("n_paths and n_steps must be >= 1")
+        ks = _strike_list(strikes)
+        _check_sizes(n_paths, n_steps)
         T, steps = _surface_steps(maturities, n_steps)
-        qmc = _qmc_tables(method, path_construction, n_paths, n_steps, seed)
-        model = (self.kappa, self.theta, self.sigma_v, self.rho, self.v0)
-        if qmc is None:
-            s = seed if seed is not None else int(np.random.default_rng().integers(0, 2**31))
-        prices = np.empty((len(ks), len(steps)), dtype=np.float64)
-        errors = np.empty_like(prices)
-        for launch in _surface_launches(steps, len(ks)):
-            cell_k, cell_m = [ks[i] for i, _j in launch], [steps[j] for _i, j in launch]
-            if qe and qmc is not None:
-                sv, shift, _bridge = qmc
-                sts = _hip.heston_qe_qmc_surface(S, T, r, q, option_type == "call", *model, cell_k, cell_m, n_paths, sv, shift, False, antithetic)
-            elif qe:
-                sts = _hip.heston_qe_surface(S, T, r, q, option_type == "call", *model, cell_k, cell_m, n_paths, n_steps, s, antithetic)
-            elif qmc is not None:
-                sv, shift, bridge = qmc
-                sts = _hip.heston_qmc_surface(S, T, r, q, option_type == "call", *model, cell_k, cell_m, n_paths, sv, shift, bridge, antithetic)
-            else:
-                sts = _hip.heston_surface(S, T, r, q, option_type == "call", *model, cell_k, cell_m, n_paths, n_steps, s, antithetic)
-            for (i, j), st in zip(launch, sts):
-                prices[i, j], errors[i, j] = st.price, st.std_error
-        return (prices, errors) if return_error else prices
+        sobol, run = _draws(method, path_construction, n_paths, n_steps, seed)
+        cells = _binding("surface", sobol, qe)
+        return _fill_surface(ks, steps, lambda cell_k, cell_m: cells(S, T, r, q, option_type == "call", *self._model(), cell_k, cell_m, *run,
+                                                                    antithetic), return_error)
 
     def _scenario_tuples(self, scenarios):
         """price_scenarios' mappings as _hip's tuples (S, K, T, r, q, is_call, kappa, theta, sigma_v, rho, v0), checked."""
@@ -306,22 +262,14 @@ class HestonPricer:
         The scenarios run the Euler scheme; QE scenarios and Greeks are out of scope here.
         Refused (ValueError, before the device is touched): what price_monte_carlo refuses, an empty list, a scenario without S, K, T
         or r, with an unknown key, with T <= 0 or rho outside [-1, 1], and scheme="qe"."""
-        if n_paths < 1 or n_steps < 1:
-            raise ValueError("n_paths and n_steps must be >= 1")
+        _check_sizes(n_paths, n_steps)
         _check_euler_only(scheme, "price_scenarios")
         tuples = self._scenario_tuples(scenarios)
-        qmc = _qmc_tables(method, path_construction, n_paths, n_steps, seed)
-        if qmc is None:
-            s = seed if seed is not None else int(np.random.default_rng().integers(0, 2**31))
+        sobol, run = _draws(method, path_construction, n_paths, n_steps, seed)
         prices = np.empty(len(tuples), dtype=np.float64)
         errors = np.empty_like(prices)
         for launch in _scenario_launches([_recursion_key(t[2], *t[6:]) for t in tuples]):
-            part = [tuples[i] for i in launch]
-            if qmc is not None:
-                sv, shift, bridge = qmc
-                sts = _hip.heston_qmc_scenarios(part, n_paths, sv, shift, bridge, antithetic)
-            else:
-                sts = _hip.heston_scenarios(part, n_paths, n_steps, s, antithetic)
+            sts = _binding("scenarios", sobol)([tuples[i] for i in launch], *run, antithetic)
             for i, st in zip(launch, sts):
                 prices[i], errors[i] = st.price, st.std_error
         return (prices, errors) if return_error else prices
@@ -332,38 +280,18 @@ class HestonPricer:
                        scheme: Literal["euler", "qe"] = "euler") -> Tuple[np.ndarray, np.ndarray]:
         """heston.py:257-305: (spot_paths, variance_paths), each (n_paths, n_steps + 1), column 0 = (S, v0).
         The states of price_monte_carlo's recursion for the same seed, method, path_construction and scheme (additive, as there)."""
-        if n_paths < 1 or n_steps < 1:
-            raise ValueError("n_paths and n_steps must be >= 1")
+        _check_sizes(n_paths, n_steps)
         qe = _check_scheme(scheme, method, path_construction)
-        qmc = _qmc_tables(method, path_construction, n_paths, n_steps, seed)
-        model = (self.kappa, self.theta, self.sigma_v, self.rho, self.v0)
-        if qe and qmc is not None:
-            sv, shift, _bridge = qmc
-            return _hip.heston_qe_qmc_paths(S, T, r, q, *model, n_paths, sv, shift, False, path_major=True)
-        if qe:
-            s = seed if seed is not None else int(np.random.default_rng().integers(0, 2**31))
-            return _hip.heston_qe_paths(S, T, r, q, *model, n_paths, n_steps, s, path_major=True)
-        if qmc is not None:
-            sv, shift, bridge = qmc
-            return _hip.heston_qmc_paths(S, T, r, q, self.kappa, self.theta, self.sigma_v, self.rho, self.v0, n_paths, sv, shift, bridge,
-                                         path_major=True)
-        s = seed if seed is not None else int(np.random.default_rng().integers(0, 2**31))
-        return _hip.heston_paths(S, T, r, q, self.kappa, self.theta, self.sigma_v, self.rho, self.v0, n_paths, n_steps, s, path_major=True)
+        sobol, run = _draws(method, path_construction, n_paths, n_steps, seed)
+        return _binding("paths", sobol, qe)(S, T, r, q, *self._model(), *run, path_major=True)
 
     def _price_path_payoff(self, payoff: int, barrier: float, S, K, T, r, q, option_type, n_paths, n_steps, seed, antithetic, return_error,
                            method, path_construction):
         """One launch of the path-payoff kernels (include/olmc.h "path payoffs under Heston") under price_monte_carlo's conventions."""
-        if n_paths < 1 or n_steps < 1:
-            raise ValueError("n_paths and n_steps must be >= 1")
-        model = (self.kappa, self.theta, self.sigma_v, self.rho, self.v0)
-        qmc = _qmc_tables(method, path_construction, n_paths, n_steps, seed)
-        if qmc is not None:
-            sv, shift, bridge = qmc
-            st = _hip.heston_qmc_path_payoff(S, K, T, r, q, option_type == "call", *model, payoff, barrier, n_paths, sv, shift, bridge, antithetic)
-        else:
-            s = seed if seed is not None else int(np.random.default_rng().integers(0, 2**31))
-            st = _hip.heston_path_payoff(S, K, T, r, q, option_type == "call", *model, payoff, barrier, n_paths, n_steps, s, antithetic)
-        return (np.float64(st.price), float(st.std_error)) if return_error else np.float64(st.price)
+        _check_sizes(n_paths, n_steps)
+        sobol, run = _draws(method, path_construction, n_paths, n_steps, seed)
+        st = _binding("path_payoff", sobol)(S, K, T, r, q, option_type == "call", *self._model(), payoff, barrier, *run, antithetic)
+        return _result(st, return_error)
 
     def price_asian(self, S: float, K: float, T: float, r: float, q: float = 0.0, option_type: Literal["call", "put"] = "call",
                     avg_type: Literal["arithmetic", "geometric"] = "arithmetic", n_paths: int = 100000, n_steps: int = 252,
@@ -374,10 +302,7 @@ class HestonPricer:
         path_construction, in one launch that stores no path.  seed, antithetic, return_error, method and path_construction as
         price_monte_carlo: with method="qmc" the standard error is the naive per-path one, not a confidence interval (it overstates the
         error).  Refused (ValueError, before the device is touched): an unknown avg_type, and what price_monte_carlo refuses."""
-        if avg_type not in ("arithmetic", "geometric"):
-            raise ValueError("avg_type must be 'arithmetic' or 'geometric'")
-        payoff = _hip.PATH_ASIAN_GEOMETRIC if avg_type == "geometric" else _hip.PATH_ASIAN_ARITHMETIC
-        return self._price_path_payoff(payoff, 0.0, S, K, T, r, q, option_type, n_paths, n_steps, seed, antithetic, return_error, method,
+        return self._price_path_payoff(_asian_payoff(avg_type), 0.0, S, K, T, r, q, option_type, n_paths, n_steps, seed, antithetic, return_error, method,
                                        path_construction)
 
     def price_barrier(self, S: float, K: float, T: float, r: float, barrier: float, q: float = 0.0,
@@ -391,10 +316,8 @@ class HestonPricer:
         as the reference's class reads it: startswith("up") and endswith("out").  After date 0 the kernel decides in log space, ln(S_t / S)
         against ln(barrier / S), where the matrix route compares exp(ln S_t) with the barrier: the two agree except for a path within
         rounding (about 1e-16 relative) of the level, which can decide differently.  The rest as price_asian; also refused: barrier <= 0."""
-        if barrier <= 0:
-            raise ValueError("Barrier must be positive")
-        kind = ("up" if barrier_type.startswith("up") else "down") + ("-and-out" if barrier_type.endswith("out") else "-and-in")
-        return self._price_path_payoff(_hip.BARRIER_KINDS[kind], barrier, S, K, T, r, q, option_type, n_paths, n_steps, seed, antithetic,
+        _check_barrier(barrier)
+        return self._price_path_payoff(_barrier_kind(barrier_type), barrier, S, K, T, r, q, option_type, n_paths, n_steps, seed, antithetic,
                                        return_error, method, path_construction)
 
     def price_lookback(self, S: float, K: float, T: float, r: float, q: float = 0.0, option_type: Literal["call", "put"] = "call",
@@ -404,10 +327,7 @@ class HestonPricer:
         """The lookback option under this model on the extrema of simulate_paths' spot matrix over dates 0 .. n_steps: floating call S_n -
         S_min, floating put S_max - S_n, fixed call max(S_max - K, 0), fixed put max(K - S_min, 0) (LookbackOption.price,
         exotic_options.py:347-401), in one launch that stores no path.  The rest as price_asian; also refused: an unknown lookback_type."""
-        if lookback_type not in ("floating", "fixed"):
-            raise ValueError("lookback_type must be 'floating' or 'fixed'")
-        payoff = _hip.LOOKBACK_FIXED if lookback_type == "fixed" else _hip.LOOKBACK_FLOATING
-        return self._price_path_payoff(payoff, 0.0, S, K, T, r, q, option_type, n_paths, n_steps, seed, antithetic, return_error, method,
+        return self._price_path_payoff(_lookback_payoff(lookback_type), 0.0, S, K, T, r, q, option_type, n_paths, n_steps, seed, antithetic, return_error, method,
                                        path_construction)
 
     def _price_structured(self, philox, sobol, contract, S, T, r, q, n_paths, n_steps, seed, antithetic, return_error, method,
@@ -415,15 +335,9 @@ class HestonPricer:
         """One launch of the structured-product kernels (include/olmc.h "structured products under Heston") under price_monte_carlo's
         conventions: `philox` / `sobol` are the product's two bindings, `contract` its arguments between the model and the counts."""
         qe = _check_scheme(scheme, method, path_construction)
-        model = (self.kappa, self.theta, self.sigma_v, self.rho, self.v0)
-        qmc = _qmc_tables(method, path_construction, n_paths, n_steps, seed)
-        if qmc is not None:
-            sv, shift, bridge = qmc
-            st = sobol(S, T, r, q, *model, *contract, n_paths, sv, shift, bridge, antithetic, qe=qe)
-        else:
-            s = seed if seed is not None else int(np.random.default_rng().integers(0, 2**31))
-            st = philox(S, T, r, q, *model, *contract, n_paths, n_steps, s, antithetic, qe=qe)
-        return (np.float64(st.price), float(st.std_error)) if return_error else np.float64(st.price)
+        on_sobol, run = _draws(method, path_construction, n_paths, n_steps, seed)
+        st = (sobol if on_sobol else philox)(S, T, r, q, *self._model(), *contract, *run, antithetic, qe=qe)
+        return _result(st, return_error)
 
     def price_autocallable(self, S: float, T: float, r: float, q: float = 0.0, autocall_barrier: float = 1.0, coupon_barrier: float = 0.8,
                            coupon_rate: float = 0.10, ki_barrier: float = 0.6, observation_freq: int = 21, n_paths: int = 100000,
@@ -442,8 +356,7 @@ class HestonPricer:
         quarterly observations) is where "qe" matters: Euler on such a grid is biased by tens of standard errors (DESIGN.md "Structured
         products under Heston").  Refused (ValueError, before the device is touched): what price_monte_carlo refuses, and
         observation_freq < 1."""
-        if n_paths < 1 or n_steps < 1:
-            raise ValueError("n_paths and n_steps must be >= 1")
+        _check_sizes(n_paths, n_steps)
         if observation_freq < 1:
             raise ValueError("observation_freq must be >= 1")
         if observation_freq > n_steps:                  # no observation date: nothing redeems early (exotic_options.py:442, 448)
@@ -462,8 +375,7 @@ class HestonPricer:
         CliquetOption.price (exotic_options.py:526-554) computes from simulate_paths' spot matrix for the same seed, method,
         path_construction and scheme, in one launch that stores no path.  The rest as price_autocallable; also refused: n_periods outside
         [1, n_steps]."""
-        if n_paths < 1 or n_steps < 1:
-            raise ValueError("n_paths and n_steps must be >= 1")
+        _check_sizes(n_paths, n_steps)
         if n_periods < 1 or n_periods > n_steps:
             raise ValueError("n_periods must be in [1, n_steps]")
         contract = (local_cap, local_floor, global_cap, global_floor, n_periods)
@@ -506,13 +418,12 @@ class HestonMCAdapter:
     def __init__(self, pricer: HestonPricer, n_paths: int = 100000, n_steps: int = 252, seed: Optional[int] = None, antithetic: bool = False, *,
                  method: Literal["pseudo", "qmc"] = "pseudo", path_construction: Literal["bridge", "sequential"] = "bridge",
                  scheme: Literal["euler", "qe"] = "euler"):
-        if n_paths < 1 or n_steps < 1:
-            raise ValueError("n_paths and n_steps must be >= 1")
+        _check_sizes(n_paths, n_steps)
         _check_euler_only(scheme, "HestonMCAdapter")
         self.heston = pricer
         self.n_paths, self.n_steps, self.antithetic = int(n_paths), int(n_steps), bool(antithetic)
         self.method, self.path_construction = method, path_construction
-        self.seed = int(seed) if seed is not None else int(np.random.default_rng().integers(0, 2**31))
+        self.seed = int(_seed(seed))
         self._qmc = _qmc_tables(method, path_construction, self.n_paths, self.n_steps, self.seed)      # the refusals, and the tables once
 
     def price(self, S, K, T, r, sigma, option_type, q=0.0, **kwargs) -> float:

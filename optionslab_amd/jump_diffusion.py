@@ -16,21 +16,14 @@ from typing import Literal, Optional
 import numpy as np
 
 from . import _hip
+from ._paths import _asian_payoff, _barrier_kind, _check_barrier, _check_sizes, _fill_surface, _lookback_payoff, _result, _seed, _strike_list, _surface_steps
 from .black_scholes import _ncdf
 
 
-def _seed(seed):
-    return seed if seed is not None else int(np.random.default_rng().integers(0, 2**31))
-
-
-def _result(st, return_error):
-    return (np.float64(st.price), float(st.std_error)) if return_error else np.float64(st.price)
-
-
 class _JumpPathPayoffs:
-    """The path-dependent pricers both models share (include/olmc_jump.h): each is ONE launch on simulate_paths' paths that stores no path.
-    Parameter names, defaults, return conventions and refusals are HestonPricer's methods of the same names, without method= / scheme=;
-    sigma stands where price_monte_carlo has it.  antithetic=True also prices the mirror leg of every path (simulate_paths(mirror=True)):
+    """What both models share, written once over `_jd()`: price_monte_carlo, simulate_paths and the path-dependent pricers
+    (include/olmc_jump.h), each of which is ONE launch on simulate_paths' paths that stores no path.  Their parameter names, defaults,
+    return conventions and refusals are HestonPricer's methods of the same names, without method= / scheme=; sigma stands where price_monte_carlo has it.  antithetic=True also prices the mirror leg of every path (simulate_paths(mirror=True)):
     the diffusion normals negated, the jump counts and sizes shared; the price is then the mean over 2 n_paths samples and the standard
     error the plain one over those samples."""
 
@@ -38,9 +31,29 @@ class _JumpPathPayoffs:
         """(kou, lambda_j, a1, a2, a3) of the C ABI."""
         raise NotImplementedError
 
+    def price_monte_carlo(self, S, K, T, r, sigma, option_type: Literal["call", "put"] = "call", q: float = 0.0,
+                          n_paths: int = 100000, n_steps: int = 252, seed: Optional[int] = None, return_error: bool = False, *,
+                          antithetic: bool = False):
+        """antithetic=False is olmc_jump_diffusion's launch; True prices the path and its mirror leg (oljd_price, OLJD_EUROPEAN)."""
+        _check_sizes(n_paths, n_steps)
+        if antithetic:
+            st = _hip.jd_price(S, K, T, r, sigma, q, option_type == "call", self._jd(), _hip.JD_EUROPEAN, 0.0, n_paths, n_steps, _seed(seed), True)
+        else:
+            st = _hip.jump_diffusion(S, K, T, r, sigma, q, option_type == "call", *self._jd(), n_paths, n_steps, _seed(seed))
+        return _result(st, return_error)
+
+    def simulate_paths(self, S, T, r, sigma, q: float = 0.0, n_paths: int = 1, n_steps: int = 252,
+                       seed: Optional[int] = None, *, mirror: bool = False) -> np.ndarray:
+        """(n_paths, n_steps + 1) price paths of price_monte_carlo's recursion for the same seed, column 0 = S (additive for Kou: the
+        reference has them for Merton only); mirror=True: the mirror leg of the same paths (the diffusion normals negated, the jumps
+        shared)."""
+        _check_sizes(n_paths, n_steps)
+        if mirror:
+            return _hip.jd_paths(S, T, r, sigma, q, self._jd(), n_paths, n_steps, _seed(seed), mirror=True, path_major=True)
+        return _hip.jump_paths(S, T, r, sigma, q, *self._jd(), n_paths, n_steps, _seed(seed), path_major=True)
+
     def _price_path_payoff(self, payoff, barrier, S, K, T, r, sigma, q, option_type, n_paths, n_steps, seed, antithetic, return_error):
-        if n_paths < 1 or n_steps < 1:
-            raise ValueError("n_paths and n_steps must be >= 1")
+        _check_sizes(n_paths, n_steps)
         st = _hip.jd_price(S, K, T, r, sigma, q, option_type == "call", self._jd(), payoff, barrier, n_paths, n_steps, _seed(seed), antithetic)
         return _result(st, return_error)
 
@@ -50,10 +63,7 @@ class _JumpPathPayoffs:
                     return_error: bool = False):
         """max(+-(A - K), 0), A the arithmetic or geometric mean of the spot over dates 1 .. n_steps: what AsianOption.price computes from
         simulate_paths' matrix for the same seed.  Refused (ValueError, before the device is touched): an unknown avg_type, bad counts."""
-        if avg_type not in ("arithmetic", "geometric"):
-            raise ValueError("avg_type must be 'arithmetic' or 'geometric'")
-        payoff = _hip.PATH_ASIAN_GEOMETRIC if avg_type == "geometric" else _hip.PATH_ASIAN_ARITHMETIC
-        return self._price_path_payoff(payoff, 0.0, S, K, T, r, sigma, q, option_type, n_paths, n_steps, seed, antithetic, return_error)
+        return self._price_path_payoff(_asian_payoff(avg_type), 0.0, S, K, T, r, sigma, q, option_type, n_paths, n_steps, seed, antithetic, return_error)
 
     def price_barrier(self, S: float, K: float, T: float, r: float, sigma: float, barrier: float, q: float = 0.0,
                       option_type: Literal["call", "put"] = "call",
@@ -63,10 +73,8 @@ class _JumpPathPayoffs:
         active: what BarrierOption.price computes from that matrix.  barrier_type is read as the reference's class reads it:
         startswith("up") and endswith("out").  After date 0 the kernel decides in log space, so a path within rounding (about 1e-16
         relative) of the level can decide differently from the matrix route.  Also refused: barrier <= 0."""
-        if barrier <= 0:
-            raise ValueError("Barrier must be positive")
-        kind = ("up" if barrier_type.startswith("up") else "down") + ("-and-out" if barrier_type.endswith("out") else "-and-in")
-        return self._price_path_payoff(_hip.BARRIER_KINDS[kind], barrier, S, K, T, r, sigma, q, option_type, n_paths, n_steps, seed, antithetic,
+        _check_barrier(barrier)
+        return self._price_path_payoff(_barrier_kind(barrier_type), barrier, S, K, T, r, sigma, q, option_type, n_paths, n_steps, seed, antithetic,
                                        return_error)
 
     def price_lookback(self, S: float, K: float, T: float, r: float, sigma: float, q: float = 0.0,
@@ -76,10 +84,7 @@ class _JumpPathPayoffs:
         """The lookback option on the extrema of simulate_paths' matrix over dates 0 .. n_steps (LookbackOption.price): floating call S_n -
         S_min, floating put S_max - S_n, fixed call max(S_max - K, 0), fixed put max(K - S_min, 0).  Also refused: an unknown
         lookback_type."""
-        if lookback_type not in ("floating", "fixed"):
-            raise ValueError("lookback_type must be 'floating' or 'fixed'")
-        payoff = _hip.LOOKBACK_FIXED if lookback_type == "fixed" else _hip.LOOKBACK_FLOATING
-        return self._price_path_payoff(payoff, 0.0, S, K, T, r, sigma, q, option_type, n_paths, n_steps, seed, antithetic, return_error)
+        return self._price_path_payoff(_lookback_payoff(lookback_type), 0.0, S, K, T, r, sigma, q, option_type, n_paths, n_steps, seed, antithetic, return_error)
 
     def price_surface(self, S: float, strikes, maturities, r: float, sigma: float, q: float = 0.0,
                       option_type: Literal["call", "put"] = "call", n_paths: int = 100000, n_steps: int = 252, seed: Optional[int] = None,
@@ -89,23 +94,12 @@ class _JumpPathPayoffs:
         must lie on that grid, as HestonPricer.price_surface requires (same ValueErrors).  Cell (K, T_j) is exp(-r T_j) mean(max(+-(spot[:,
         m_j] - K), 0)) over column m_j of simulate_paths(S, T, r, sigma, q, n_paths, n_steps, seed); more than 16 cells are cut into
         launches of at most 16, and a cell's bits do not depend on the cells it shares a launch with."""
-        from .heston import _surface_launches, _surface_steps
-
-        ks = [float(k) for k in np.asarray(strikes, dtype=np.float64).ravel()]
-        if not ks:
-            raise ValueError("strikes must not be empty")
-        if n_paths < 1 or n_steps < 1:
-            raise ValueError("n_paths and n_steps must be >= 1")
+        ks = _strike_list(strikes)
+        _check_sizes(n_paths, n_steps)
         T, steps = _surface_steps(maturities, n_steps)
         s = _seed(seed)
-        prices = np.empty((len(ks), len(steps)), dtype=np.float64)
-        errors = np.empty_like(prices)
-        for launch in _surface_launches(steps, len(ks)):
-            cell_k, cell_m = [ks[i] for i, _j in launch], [steps[j] for _i, j in launch]
-            sts = _hip.jd_surface_prices(S, T, r, sigma, q, option_type == "call", self._jd(), cell_k, cell_m, n_paths, n_steps, s, antithetic)
-            for (i, j), st in zip(launch, sts):
-                prices[i, j], errors[i, j] = st.price, st.std_error
-        return (prices, errors) if return_error else prices
+        return _fill_surface(ks, steps, lambda cell_k, cell_m: _hip.jd_surface_prices(S, T, r, sigma, q, option_type == "call", self._jd(), cell_k,
+                                                                                      cell_m, n_paths, n_steps, s, antithetic), return_error)
 
     def price_autocallable(self, S: float, T: float, r: float, sigma: float, q: float = 0.0, autocall_barrier: float = 1.0,
                            coupon_barrier: float = 0.8, coupon_rate: float = 0.10, ki_barrier: float = 0.6, observation_freq: int = 21,
@@ -115,8 +109,7 @@ class _JumpPathPayoffs:
         relative to S; observation dates are observation_freq, 2 observation_freq, ... <= n_steps; a payoff is discounted at its own date;
         the knock-in minimum includes date 0.  observation_freq > n_steps is priced as HestonPricer.price_autocallable prices it (one
         observation on the last step at a level no path reaches).  Also refused: observation_freq < 1."""
-        if n_paths < 1 or n_steps < 1:
-            raise ValueError("n_paths and n_steps must be >= 1")
+        _check_sizes(n_paths, n_steps)
         if observation_freq < 1:
             raise ValueError("observation_freq must be >= 1")
         if observation_freq > n_steps:                  # no observation date: nothing redeems early
@@ -131,8 +124,7 @@ class _JumpPathPayoffs:
         """exp(-r T) mean(max(clip(sum of clip(period return, local_floor, local_cap), global_floor, global_cap), 0) S) over n_periods
         periods of n_steps // n_periods steps from date 0 (CliquetOption.price on simulate_paths' matrix); trailing dates never enter a
         period and are not drawn.  Also refused: n_periods outside [1, n_steps]."""
-        if n_paths < 1 or n_steps < 1:
-            raise ValueError("n_paths and n_steps must be >= 1")
+        _check_sizes(n_paths, n_steps)
         if n_periods < 1 or n_periods > n_steps:
             raise ValueError("n_periods must be in [1, n_steps]")
         st = _hip.jd_cliquet(S, T, r, sigma, q, self._jd(), local_cap, local_floor, global_cap, global_floor, n_periods, n_paths, n_steps,
@@ -187,31 +179,6 @@ class MertonJumpDiffusion(_JumpPathPayoffs):
             return fwd * _ncdf(d1) - strike * _ncdf(d2)
         return strike * _ncdf(-d2) - fwd * _ncdf(-d1)
 
-    def price_monte_carlo(self, S, K, T, r, sigma, option_type: Literal["call", "put"] = "call", q: float = 0.0,
-                          n_paths: int = 100000, n_steps: int = 252, seed: Optional[int] = None, return_error: bool = False, *,
-                          antithetic: bool = False):
-        """antithetic=False is olmc_jump_diffusion's launch; True prices the path and its mirror leg (oljd_price, OLJD_EUROPEAN)."""
-        if n_paths < 1 or n_steps < 1:
-            raise ValueError("n_paths and n_steps must be >= 1")
-        if antithetic:
-            return _result(_hip.jd_price(S, K, T, r, sigma, q, option_type == "call", self._jd(), _hip.JD_EUROPEAN, 0.0, n_paths, n_steps,
-                                         _seed(seed), True), return_error)
-        st = _hip.jump_diffusion(S, K, T, r, sigma, q, option_type == "call", False, self.lambda_j, self.mu_j, self.sigma_j, 0.0,
-                                 n_paths, n_steps, _seed(seed))
-        return (np.float64(st.price), float(st.std_error)) if return_error else np.float64(st.price)
-
-
-    def simulate_paths(self, S, T, r, sigma, q: float = 0.0, n_paths: int = 1, n_steps: int = 252,
-                       seed: Optional[int] = None, *, mirror: bool = False) -> np.ndarray:
-        """(n_paths, n_steps + 1) price paths of price_monte_carlo's recursion for the same seed, column 0 = S; mirror=True: the mirror
-        leg of the same paths (the diffusion normals negated, the jumps shared)."""
-        if n_paths < 1 or n_steps < 1:
-            raise ValueError("n_paths and n_steps must be >= 1")
-        if mirror:
-            return _hip.jd_paths(S, T, r, sigma, q, self._jd(), n_paths, n_steps, _seed(seed), mirror=True, path_major=True)
-        return _hip.jump_paths(S, T, r, sigma, q, False, self.lambda_j, self.mu_j, self.sigma_j, 0.0, n_paths, n_steps, _seed(seed),
-                               path_major=True)
-
     def simulate_path(self, S, T, r, sigma, q: float = 0.0, n_steps: int = 252, seed: Optional[int] = None) -> np.ndarray:
         """jump_diffusion.py:227-272: one path with jumps, shape (n_steps + 1,)."""
         return self.simulate_paths(S, T, r, sigma, q, 1, n_steps, seed)[0]
@@ -238,30 +205,6 @@ class KouJumpDiffusion(_JumpPathPayoffs):
     @property
     def kappa(self) -> float:           # :293-299
         return self.p * self.eta1 / (self.eta1 - 1) + (1 - self.p) * self.eta2 / (self.eta2 + 1) - 1
-
-    def price_monte_carlo(self, S, K, T, r, sigma, option_type: Literal["call", "put"] = "call", q: float = 0.0,
-                          n_paths: int = 100000, n_steps: int = 252, seed: Optional[int] = None, return_error: bool = False, *,
-                          antithetic: bool = False):
-        """antithetic=False is olmc_jump_diffusion's launch; True prices the path and its mirror leg (oljd_price, OLJD_EUROPEAN)."""
-        if n_paths < 1 or n_steps < 1:
-            raise ValueError("n_paths and n_steps must be >= 1")
-        if antithetic:
-            return _result(_hip.jd_price(S, K, T, r, sigma, q, option_type == "call", self._jd(), _hip.JD_EUROPEAN, 0.0, n_paths, n_steps,
-                                         _seed(seed), True), return_error)
-        st = _hip.jump_diffusion(S, K, T, r, sigma, q, option_type == "call", True, self.lambda_j, self.p, self.eta1, self.eta2,
-                                 n_paths, n_steps, _seed(seed))
-        return (np.float64(st.price), float(st.std_error)) if return_error else np.float64(st.price)
-
-    def simulate_paths(self, S, T, r, sigma, q: float = 0.0, n_paths: int = 1, n_steps: int = 252,
-                       seed: Optional[int] = None, *, mirror: bool = False) -> np.ndarray:
-        """(n_paths, n_steps + 1) price paths of price_monte_carlo's recursion (additive: the reference has none for Kou); mirror=True:
-        the mirror leg of the same paths (the diffusion normals negated, the jumps shared)."""
-        if n_paths < 1 or n_steps < 1:
-            raise ValueError("n_paths and n_steps must be >= 1")
-        if mirror:
-            return _hip.jd_paths(S, T, r, sigma, q, self._jd(), n_paths, n_steps, _seed(seed), mirror=True, path_major=True)
-        return _hip.jump_paths(S, T, r, sigma, q, True, self.lambda_j, self.p, self.eta1, self.eta2, n_paths, n_steps, _seed(seed),
-                               path_major=True)
 
 
 class JumpDiffusionAdapter:

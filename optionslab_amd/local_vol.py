@@ -16,7 +16,7 @@ from typing import Callable, Literal, Optional, Tuple
 import numpy as np
 
 from . import _hip
-from .heston import _surface_launches, _surface_steps
+from ._paths import _asian_payoff, _barrier_kind, _check_barrier, _check_sizes, _fill_surface, _lookback_payoff, _result, _seed, _strike_list, _surface_steps
 
 _VOL_CLIP = (0.05, 2.0)          # local_vol.py:238
 _SAMPLE_EXPIRIES = (0.1, 0.25, 0.5, 0.75, 1.0)
@@ -144,10 +144,8 @@ class DupireLocalVol:
     def _sizes(self, n_paths, n_steps, seed):
         n_paths = self.n_paths if n_paths is None else n_paths
         n_steps = self.n_steps if n_steps is None else n_steps
-        if n_paths < 1 or n_steps < 1:
-            raise ValueError("n_paths and n_steps must be >= 1")
-        seed = self.seed if seed is None else seed
-        return n_paths, n_steps, seed if seed is not None else int(np.random.default_rng().integers(0, 2**31))
+        _check_sizes(n_paths, n_steps)
+        return n_paths, n_steps, _seed(self.seed if seed is None else seed)
 
     # The three device calls, each on a table of local_vol_table and the sizes and seed _sizes settled: what DupireLocalVolQMC overrides.
     def _device_price(self, S, K, T, r, q, is_call, table, payoff, barrier, n_paths, n_steps, seed, antithetic):
@@ -162,7 +160,7 @@ class DupireLocalVol:
     def _price_payoff(self, payoff, barrier, S, K, T, r, q, option_type, n_paths, n_steps, seed, antithetic, return_error):
         n_paths, n_steps, s = self._sizes(n_paths, n_steps, seed)
         st = self._device_price(S, K, T, r, q, option_type == "call", self.local_vol_table(S, T), payoff, barrier, n_paths, n_steps, s, antithetic)
-        return (np.float64(st.price), float(st.std_error)) if return_error else np.float64(st.price)
+        return _result(st, return_error)
 
     def price_monte_carlo(self, S: float, K: float, T: float, r: float, q: float = 0.0, option_type: Literal["call", "put"] = "call",
                           n_paths: Optional[int] = None, n_steps: Optional[int] = None, seed: Optional[int] = None, antithetic: bool = False,
@@ -184,10 +182,7 @@ class DupireLocalVol:
                     seed: Optional[int] = None, antithetic: bool = False, return_error: bool = False):
         """max(+-(A - K), 0), A the arithmetic or geometric mean of simulate_paths' spot over dates 1 .. n_steps (HestonPricer.price_asian's
         payoff), on local-volatility paths."""
-        if avg_type not in ("arithmetic", "geometric"):
-            raise ValueError("avg_type must be 'arithmetic' or 'geometric'")
-        payoff = _hip.PATH_ASIAN_GEOMETRIC if avg_type == "geometric" else _hip.PATH_ASIAN_ARITHMETIC
-        return self._price_payoff(payoff, 0.0, S, K, T, r, q, option_type, n_paths, n_steps, seed, antithetic, return_error)
+        return self._price_payoff(_asian_payoff(avg_type), 0.0, S, K, T, r, q, option_type, n_paths, n_steps, seed, antithetic, return_error)
 
     def price_barrier(self, S: float, K: float, T: float, r: float, barrier: float, q: float = 0.0,
                       option_type: Literal["call", "put"] = "call",
@@ -196,19 +191,14 @@ class DupireLocalVol:
                       return_error: bool = False):
         """The barrier option monitored at dates 0 .. n_steps of simulate_paths' matrix, with HestonPricer.price_barrier's reading of
         barrier_type, its date-0 decision and its log-space comparison after date 0.  Refused: barrier <= 0."""
-        if barrier <= 0:
-            raise ValueError("Barrier must be positive")
-        kind = ("up" if barrier_type.startswith("up") else "down") + ("-and-out" if barrier_type.endswith("out") else "-and-in")
-        return self._price_payoff(_hip.BARRIER_KINDS[kind], barrier, S, K, T, r, q, option_type, n_paths, n_steps, seed, antithetic, return_error)
+        _check_barrier(barrier)
+        return self._price_payoff(_barrier_kind(barrier_type), barrier, S, K, T, r, q, option_type, n_paths, n_steps, seed, antithetic, return_error)
 
     def price_lookback(self, S: float, K: float, T: float, r: float, q: float = 0.0, option_type: Literal["call", "put"] = "call",
                        lookback_type: Literal["floating", "fixed"] = "floating", n_paths: Optional[int] = None, n_steps: Optional[int] = None,
                        seed: Optional[int] = None, antithetic: bool = False, return_error: bool = False):
         """The lookback option on the extrema of simulate_paths' matrix over dates 0 .. n_steps (HestonPricer.price_lookback's payoffs)."""
-        if lookback_type not in ("floating", "fixed"):
-            raise ValueError("lookback_type must be 'floating' or 'fixed'")
-        payoff = _hip.LOOKBACK_FIXED if lookback_type == "fixed" else _hip.LOOKBACK_FLOATING
-        return self._price_payoff(payoff, 0.0, S, K, T, r, q, option_type, n_paths, n_steps, seed, antithetic, return_error)
+        return self._price_payoff(_lookback_payoff(lookback_type), 0.0, S, K, T, r, q, option_type, n_paths, n_steps, seed, antithetic, return_error)
 
     def price_surface(self, S: float, strikes, maturities, r: float, q: float = 0.0, option_type: Literal["call", "put"] = "call",
                       n_paths: Optional[int] = None, n_steps: Optional[int] = None, seed: Optional[int] = None, antithetic: bool = False,
@@ -217,20 +207,12 @@ class DupireLocalVol:
         (prices, std_errors).  The grid, its refusals and the launches of at most 16 cells are HestonPricer.price_surface's: n_steps steps
         to the longest maturity, every maturity on that grid; cell (K, T_j) is the discounted payoff of column m_j of simulate_paths'
         matrix.  This is the call that reprices a whole smile."""
-        ks = [float(k) for k in np.asarray(strikes, dtype=np.float64).ravel()]
-        if not ks:
-            raise ValueError("strikes must not be empty")
+        ks = _strike_list(strikes)
         n_paths, n_steps, s = self._sizes(n_paths, n_steps, seed)
         T, steps = _surface_steps(maturities, n_steps)
         table = self.local_vol_table(S, T)
-        prices = np.empty((len(ks), len(steps)), dtype=np.float64)
-        errors = np.empty_like(prices)
-        for launch in _surface_launches(steps, len(ks)):
-            cell_k, cell_m = [ks[i] for i, _j in launch], [steps[j] for _i, j in launch]
-            sts = self._device_surface(S, T, r, q, option_type == "call", table, cell_k, cell_m, n_paths, n_steps, s, antithetic)
-            for (i, j), st in zip(launch, sts):
-                prices[i, j], errors[i, j] = st.price, st.std_error
-        return (prices, errors) if return_error else prices
+        return _fill_surface(ks, steps, lambda cell_k, cell_m: self._device_surface(S, T, r, q, option_type == "call", table, cell_k, cell_m, n_paths,
+                                                                                   n_steps, s, antithetic), return_error)
 
     def price(self, S: float, K: float, T: float, r: float, sigma: float, option_type: str, q: float = 0.0) -> float:
         """PricerProtocol (local_vol.py:264-277): sigma is ignored, the calibrated surface prices; r and q are kept, as the reference keeps

@@ -17,6 +17,7 @@ from typing import Literal, Optional, Union
 import numpy as np
 
 from . import _hip
+from ._paths import _seed
 from .exceptions import AccelerationError
 
 SOBOL_MAX_DIM = 21201            # src/simulation/gbm_qmc.py:29-30
@@ -221,7 +222,7 @@ class MonteCarloPricer:
         self.num_steps = num_steps
         # one 31-bit draw at construction, then fixed: repeated price() calls and
         # all FD bumps share the normals (monte_carlo.py:68-70)
-        self.seed = seed if seed is not None else int(np.random.default_rng().integers(0, 2**31))
+        self.seed = _seed(seed)
         self.method = method
         self._use_numba = False
 

@@ -18,6 +18,7 @@ from typing import Literal, Optional, Tuple, Union
 import numpy as np
 
 from . import _hip
+from ._paths import _seed
 
 NUMBA_AVAILABLE = False
 GPU_AVAILABLE = True       # this class always runs on the HIP device (or raises)
@@ -40,7 +41,7 @@ class MonteCarloPricerUni:
             raise InputValidationError("num_simulations and num_steps must be positive integers")
         self.num_simulations = num_simulations
         self.num_steps = num_steps
-        self.seed = seed if seed is not None else int(np.random.default_rng().integers(0, 2**31))
+        self.seed = _seed(seed)
         self.rng = np.random.default_rng(seed)          # :287 (feeds delta_gamma's seed draw)
         self.use_numba = False
         self.use_gpu = True

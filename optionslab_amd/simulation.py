@@ -5,6 +5,7 @@
 import numpy as np
 
 from . import _hip
+from ._paths import _check_sizes
 
 __all__ = ["simulate_gbm_hip", "simulate_gbm_hip_fast", "simulate_gbm_paths_hip", "simulate_gbm_qmc_hip",
            "simulate_gbm_qmc_antithetic_hip", "simulate_gbm_qmc_paths_hip", "hip_available"]
@@ -31,8 +32,7 @@ def simulate_gbm_paths_hip(S: float, T: float, r: float, sigma: float, q: float,
     """Full paths, shape (n_paths, n_steps + 1), column 0 = S (counterpart of simulate_gbm_paths,
     gbm_numpy.py:86-118).  The kernel writes the reference's C-order (n_paths, n_steps + 1) layout
     itself, so the array arrives in one device-to-host copy with no host-side transpose."""
-    if n_paths < 1 or n_steps < 1:
-        raise ValueError("n_paths and n_steps must be >= 1")
+    _check_sizes(n_paths, n_steps)
     return _hip.gbm_paths(S, T, r, sigma, q, n_paths, n_steps, seed, path_major=True)
 
 
@@ -61,7 +61,6 @@ def simulate_gbm_qmc_paths_hip(S: float, T: float, r: float, sigma: float, q: fl
     Refused (ValueError, before the device is touched) as AsianOption.price(method="qmc")."""
     from .exotic import _qmc_tables
 
-    if n_paths < 1 or n_steps < 1:
-        raise ValueError("n_paths and n_steps must be >= 1")
+    _check_sizes(n_paths, n_steps)
     sv, shift, bridge = _qmc_tables("qmc", path_construction, n_paths, n_steps, seed)
     return _hip.gbm_qmc_paths(S, T, r, sigma, q, n_paths, sv, shift, bridge, path_major=True)
