@@ -10,8 +10,9 @@ import subprocess
 import pytest
 
 from optionslab_amd import _hip
-from optionslab_amd.build import LIBRARY, build_library
+from optionslab_amd.build import LIBRARY
 from optionslab_amd.exceptions import AccelerationError
+from tests.abi_support import _CV, _ST, _opts, _out9, library, refused, sobol as _sobol
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "olmc.h")
@@ -26,12 +27,6 @@ def declared_symbols(header=HEADER):
 def exported_symbols(path):
     out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
     return set(re.findall(r"\bT (olmc_[a-z0-9_]+)", out))
-
-
-@pytest.fixture(scope="module")
-def library():
-    build_library()
-    return _hip.load_library()
 
 
 def test_header_declares_the_expected_surface():
@@ -190,30 +185,10 @@ def test_the_kernels_refuse_a_finite_math_build():
 
 # One row per argument refusal of the pricing entry points that happens before a device is touched: (entry point, arguments,
 # exact olmc_last_error() message).  Every row returns OLMC_ERR_ARG with or without a GPU.
-def _ST():
-    return C.byref(_hip.Stats())
-
-
-def _CV():
-    return C.byref(_hip.CvMoments())
-
-
 _G = (100.0, 100.0, 1.0, 0.05, 0.2, 0.0, 1)                       # S K T r sigma q is_call
 _GT0 = (100.0, 100.0, 0.0, 0.05, 0.2, 0.0, 1)                     # T = 0
 _MKT = (100.0, 1.0, 0.05, 0.2, 0.0)                               # S T r sigma q
 _HES = (0.05, 0.0, 2.0, 0.04, 0.3)                                # r q kappa theta sigma_v (rho, v0 follow)
-
-
-def _opts(k):
-    return (_hip.Option * 16)(*[_hip.Option(100.0, 90.0 + i, 1.0, 0.05, 0.2, 0.0, 1, 0) for i in range(k)])
-
-
-def _sobol(dims):
-    return (C.c_uint32 * (30 * max(dims, 1)))(*range(1, 30 * max(dims, 1) + 1)), (C.c_uint32 * max(dims, 1))()
-
-
-def _out9():
-    return (C.c_double * 9)()
 
 
 _REFUSALS = [
@@ -356,6 +331,4 @@ _REFUSALS = [
 @pytest.mark.parametrize("name,args,message", _REFUSALS, ids=[f"{n}-{i}" for i, (n, _a, _m) in enumerate(_REFUSALS)])
 def test_entry_points_refuse_bad_arguments_before_touching_a_device(library, name, args, message):
     """Each refusal answers OLMC_ERR_ARG (1) with its exact message, ahead of any device work (no device is initialised here)."""
-    rc = getattr(library, name)(*args())
-    assert rc == 1
-    assert library.olmc_last_error().decode() == message
+    refused(library, getattr(library, name)(*args()), message)

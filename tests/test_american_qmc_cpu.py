@@ -11,19 +11,13 @@ import pytest
 import optionslab_amd as ol
 from optionslab_amd import _hip
 from oracle import numpy_reference as orc
+from tests.abi_support import no_device
 
 S, K, T, R, SIG = 100.0, 100.0, 1.0, 0.05, 0.2
 NEW_ENTRY_POINTS = ("olmc_american_lsm_qmc", "olmc_exercise_boundary_qmc", "olmc_gbm_qmc_paths")
 
 
-@pytest.fixture
-def no_device(monkeypatch):
-    """Any attempt to reach the library (hence the device) fails the test."""
-    def touched(*a, **k):
-        raise AssertionError("the device was touched")
-
-    for name in ("lib", "american_lsm", "american_lsm_qmc", "exercise_boundary", "exercise_boundary_qmc", "gbm_qmc_paths"):
-        monkeypatch.setattr(_hip, name, touched)
+_BINDINGS = ("lib", "american_lsm", "american_lsm_qmc", "exercise_boundary", "exercise_boundary_qmc", "gbm_qmc_paths")
 
 
 REFUSALS = [

@@ -10,6 +10,7 @@ import pytest
 import optionslab_amd as ol
 from optionslab_amd import _hip
 from optionslab_amd.exceptions import AccelerationError
+from tests.abi_support import no_device
 
 S, K, T, R, SIG = 100.0, 100.0, 1.0, 0.05, 0.2
 
@@ -22,14 +23,7 @@ def _options():
     ]
 
 
-@pytest.fixture
-def no_device(monkeypatch):
-    """Any attempt to reach the library (hence the device) fails the test."""
-    def touched(*a, **k):
-        raise AssertionError("the device was touched")
-
-    for name in ("lib", "asian_qmc", "extrema_qmc", "asian", "barrier", "lookback"):
-        monkeypatch.setattr(_hip, name, touched)
+_BINDINGS = ("lib", "asian_qmc", "extrema_qmc", "asian", "barrier", "lookback")
 
 
 @pytest.mark.parametrize("kwargs,match", [

@@ -1,35 +1,20 @@
 """Fused finite-difference Greeks on Sobol paths (olmc_asian_qmc_greeks_fd / olmc_extrema_qmc_greeks_fd) without a device: the ABI
 exports and binds them, every refusal comes before any device work, and ExoticAdapter picks the fused plan for a seeded method="qmc"
 option only."""
-import ctypes as C
 
 import pytest
 
 import optionslab_amd as ol
 from optionslab_amd import _hip
-from optionslab_amd.build import build_library
 from optionslab_amd.exceptions import GreeksError
 from optionslab_amd.greeks import ExoticAdapter, compute_greeks_unified
+from tests.abi_support import library, _out9, refused, sobol as _sobol
 
 NAMES = ("olmc_asian_qmc_greeks_fd", "olmc_extrema_qmc_greeks_fd")
 S, K, T, R, SIG = 100.0, 100.0, 1.0, 0.05, 0.2
 
 _G = (S, K, T, R, SIG, 0.0, 1)                  # S K T r sigma q is_call
 _GT0 = (S, K, 0.0, R, SIG, 0.0, 1)              # T = 0
-
-
-def _sobol(dims):
-    return (C.c_uint32 * (30 * dims))(*range(1, 30 * dims + 1)), (C.c_uint32 * dims)()
-
-
-def _out9():
-    return (C.c_double * 9)()
-
-
-@pytest.fixture(scope="module")
-def library():
-    build_library()
-    return _hip.load_library()
 
 
 def test_the_library_exports_and_binds_both_entry_points(library):
@@ -71,9 +56,7 @@ _REFUSALS = [
 
 @pytest.mark.parametrize("name,args,message", _REFUSALS, ids=[f"{n}-{i}" for i, (n, _a, _m) in enumerate(_REFUSALS)])
 def test_refusals_answer_err_arg_before_any_device_work(library, name, args, message):
-    rc = getattr(library, name)(*args())
-    assert rc == 1
-    assert library.olmc_last_error().decode() == message
+    refused(library, getattr(library, name)(*args()), message)
 
 
 # ------------------------------------------------------------------------------------------------- the adapter's plan ----

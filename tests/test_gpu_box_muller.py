@@ -26,6 +26,7 @@ import pytest
 import optionslab_amd as ol
 from optionslab_amd import _hip
 from tests import box_muller_reference as bm
+from tests.gpu_support import device_fixture
 from tools.probe import binding as probe
 
 pytestmark = pytest.mark.gpu
@@ -36,11 +37,7 @@ ENTRY_IDS = [f"{e['kind']}-seed{e['seed']}-path{e['path']}-x{e['slot']}" for e i
 S, K, T, R, SIGMA = 100.0, 1.0, 1.0, 0.05, 0.2          # a deep in-the-money call: no payoff clips to zero
 
 
-@pytest.fixture(scope="module", autouse=True)
-def _device():
-    assert hip.device_info()["arch"].startswith("gfx950")
-    yield
-    hip.shutdown()
+_device = device_fixture(hip)
 
 
 def _assert_gate(measured):

@@ -20,7 +20,6 @@ touching the device again.
 """
 import contextlib
 import random
-import time
 
 import numpy as np
 import pytest
@@ -28,6 +27,7 @@ import pytest
 import optionslab_amd as ol
 from optionslab_amd import _hip
 from tests import call_catalogue as cc
+from tests.history import Device, baseline_fixture, first_difference
 
 pytestmark = [pytest.mark.gpu, pytest.mark.filterwarnings("ignore:The balance properties of Sobol")]
 
@@ -35,7 +35,7 @@ ENTRIES = cc.catalogue()
 BY_NAME = {e.name: e for e in ENTRIES}
 DEFAULT_KNOBS = ((_hip.TUNE_GRID_CAP, 0), (_hip.TUNE_QMC_BLOCK, 0), (_hip.TUNE_SPLIT_TAIL, 0), (_hip.TUNE_POLL, 0), (_hip.TUNE_SPLIT_SAT, 0),
                  (_hip.TUNE_MULTI_LAUNCH, 0), (_hip.TUNE_STAGED_COPY, 0), (_hip.TUNE_PHILOX_TABLE, 1))
-_dead = []            # the message of a call that failed unexpectedly: nothing more is started on the device
+DEVICE = Device()
 
 
 def set_defaults():
@@ -44,36 +44,12 @@ def set_defaults():
     _hip.profile_enable(False)
 
 
-def invoke(entry) -> np.ndarray:
-    if _dead:
-        pytest.fail(f"an earlier call failed, nothing more is run on the device: {_dead[0]}")
-    try:
-        return cc.words(entry.call())
-    except BaseException as exc:
-        _dead.append(f"{entry.name}: {type(exc).__name__}: {exc}")
-        raise
-
-
-def fresh(entry) -> np.ndarray:
-    """The call as the first one of a newly initialised library."""
-    _hip.shutdown()
-    return invoke(entry)
-
-
-def first_difference(got, want) -> str:
-    if got.shape != want.shape:
-        return f"{got.size} words instead of {want.size}"
-    i = int(np.flatnonzero(got != want)[0])
-    return (f"word {i} of {want.size}: got 0x{int(got[i]):016x} ({got[i:i + 1].view(np.float64)[0]!r}), "
-            f"fresh library 0x{int(want[i]):016x} ({want[i:i + 1].view(np.float64)[0]!r}); {int(np.count_nonzero(got != want))} words differ")
-
-
 def run_history(sequence, expected, label):
     """Runs the entries one after the other on the library as it stands; every result against expected[name].  Returns the failures as
     (position in the sequence, report)."""
     failures, ran = [], []
     for pos, e in enumerate(sequence):
-        got = invoke(e)
+        got = DEVICE.invoke(e.name, e.call)
         if not np.array_equal(got, expected[e.name]):
             failures.append((pos, f"[{label}] {e.name} (call {pos + 1} of {len(sequence)}) differs from the fresh library: "
                                   f"{first_difference(got, expected[e.name])}\n    ran before it: {', '.join(ran) if ran else 'nothing'}"))
@@ -86,18 +62,8 @@ def report(failures, checks):
         pytest.fail(f"{len(failures)} of {checks} checks failed\n" + "\n".join(text for _, text in failures[:12]), pytrace=False)
 
 
-@pytest.fixture(scope="module")
-def baseline():
-    """name -> words of the call on a fresh library; taken once.  Knobs at their defaults before, and again after the module."""
-    if not _hip.hip_available():
-        pytest.fail("no HIP device")
-    set_defaults()
-    t0 = time.perf_counter()
-    base = {e.name: fresh(e) for e in ENTRIES}
-    print(f"\nBASELINE {len(ENTRIES)} fresh libraries in {time.perf_counter() - t0:.2f} s")
-    yield base
-    if not _dead:
-        set_defaults()
+# name -> words of the call on a fresh library; taken once.  Knobs at their defaults before, and again after the module.
+baseline = baseline_fixture(DEVICE, lambda: {e.name: e.call for e in ENTRIES}, defaults=set_defaults)
 
 
 def test_the_baseline_is_stable(baseline):
@@ -106,7 +72,7 @@ def test_the_baseline_is_stable(baseline):
              "fetch-dev-N100-n64"]
     failures = []
     for name in names:
-        got = fresh(BY_NAME[name])
+        got = DEVICE.fresh(name, BY_NAME[name].call)
         if not np.array_equal(got, baseline[name]):
             failures.append((0, f"{name} differs between two fresh libraries: {first_difference(got, baseline[name])}"))
     report(failures, len(names))
@@ -130,8 +96,8 @@ def test_whole_catalogue_on_one_library(baseline, order):
     if failures and failures[0][0] > 0:                       # ONE replay: does the immediate predecessor alone reproduce the first failure?
         pos, text = failures[0]
         before, e = seq[pos - 1], seq[pos]
-        fresh(before)
-        again = invoke(e)
+        DEVICE.fresh(before.name, before.call)
+        again = DEVICE.invoke(e.name, e.call)
         alone = not np.array_equal(again, baseline[e.name])
         failures[0] = (pos, text + f"\n    replay shutdown -> {before.name} -> {e.name}: the predecessor alone "
                                    + ("REPRODUCES it: " + first_difference(again, baseline[e.name]) if alone else "does NOT reproduce it"))
@@ -214,33 +180,17 @@ def test_american_chains_on_a_bulk_buffer_the_largest_matrix_filled(baseline):
 
 
 # -------------------------------------------------------------------------------------- 4. after a call that returned early ----
-def _guarded(label, call):
-    """Runs an early-return call; anything but the outcome its history expects ends the device work of this file."""
-    if _dead:
-        pytest.fail(f"an earlier call failed, nothing more is run on the device: {_dead[0]}")
-    try:
-        return call()
-    except ol.AccelerationError as exc:
-        if "libolmc error 1:" in str(exc):                    # OLMC_ERR_ARG: refused before any device work
-            return exc
-        _dead.append(f"{label}: {exc}")
-        raise
-    except BaseException as exc:
-        _dead.append(f"{label}: {type(exc).__name__}: {exc}")
-        raise
-
-
 def _refused(call):
     """The call must be refused with OLMC_ERR_ARG."""
     def run(label):
-        assert isinstance(_guarded(label, call), ol.AccelerationError), f"{label}: was not refused"
+        assert isinstance(DEVICE.guarded(label, call), ol.AccelerationError), f"{label}: was not refused"
     return run
 
 
 def _nan(call):
     """A NaN input: the call succeeds and every price is NaN."""
     def run(label):
-        got = _guarded(label, call)
+        got = DEVICE.guarded(label, call)
         got = got if isinstance(got, list) else [got]
         assert all(isinstance(st, _hip.Stats) and np.isnan(st.price) for st in got), (label, got)
     return run
@@ -346,7 +296,7 @@ def test_sobol_block_shapes(baseline, shape):
               "olmc_multi_gpu_european_qmc_greeks_fd", "olmc_multi_gpu_european_qmc_cv"}
     failures = []
     with knob(_hip.TUNE_QMC_BLOCK, shape, 0):
-        expected = {e.name: fresh(e) if shaped & set(e.entry_points) else baseline[e.name] for e in seq}
+        expected = {e.name: DEVICE.fresh(e.name, e.call) if shaped & set(e.entry_points) else baseline[e.name] for e in seq}
         _hip.shutdown()
         failures += run_history(seq, expected, f"Sobol block shape {shape}")
         failures += run_history(seq[::-1], expected, f"Sobol block shape {shape}, reversed")
@@ -382,7 +332,7 @@ def test_switches_that_change_the_association(baseline, switch):
     seq = picks()
     failures = []
     with knob(which, value, default):
-        switched = {e.name: fresh(e) for e in seq}
+        switched = {e.name: DEVICE.fresh(e.name, e.call) for e in seq}
         _hip.shutdown()
         failures += run_history(seq, switched, f"{switch} set")
         failures += run_history(seq[::-1], switched, f"{switch} set, reversed")

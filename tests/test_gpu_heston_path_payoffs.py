@@ -16,18 +16,19 @@ Barriers are discontinuous, so every tie first asserts that no path of its oracl
 relative of the barrier (on the CPU the closest approach over N <= 4096, n <= 1024 was 9e-8; rounding differences are 1e-13).  No path
 is left out: a seed that breaks the precondition is to be changed, not the rule.
 """
+import functools
 import json
 import math
 import os
-import warnings
 
 import numpy as np
 import pytest
 
-import optionslab_amd as ol
 from optionslab_amd import _hip
 from optionslab_amd.monte_carlo import sobol_tables
 from tests import heston_path_oracle as hpo
+from tests import gpu_support
+from tests.gpu_support import heston_pricer as pricer
 from tests.heston_path_oracle import CALM, FELLER_VIOLATING, K, PAYOFFS, Q, R, S, T, USUAL
 
 pytestmark = pytest.mark.gpu
@@ -35,12 +36,6 @@ pytestmark = pytest.mark.gpu
 TIE = dict(rel=1e-10, abs=1e-12)
 STEPS = (1, 2, 13, 64, 252)
 OPTION_TYPES = ("call", "put")
-
-
-def pricer(model):
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore", UserWarning)                               # Feller
-        return ol.HestonPricer(*model)
 
 
 def assert_clear_of_the_barriers(spot, label):
@@ -61,12 +56,7 @@ def sobol_stats(model, family, kind, option_type, N, n, seed, construction, anti
                                        antithetic, point_offset)
 
 
-def check_sums(st, x, label):
-    want, want2 = float(np.sum(x)), float(np.sum(x * x))
-    print(label, "sum", st.sum, "oracle", want, "sumsq", st.sumsq, "oracle", want2)
-    assert st.n == len(x), label
-    assert st.sum == pytest.approx(want, **TIE), label
-    assert st.sumsq == pytest.approx(want2, **TIE), label
+check_sums = functools.partial(gpu_support.check_sums, tie=TIE)
 
 
 # ------------------------------------------------------------------------------ 1. Philox: tie to the device's own matrix ----

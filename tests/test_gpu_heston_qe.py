@@ -15,12 +15,10 @@ step whose psi lies within 1e-9 of 1.5 may take the other branch on the device a
 """
 import functools
 import math
-import warnings
 
 import numpy as np
 import pytest
 
-import optionslab_amd as ol
 from optionslab_amd import _hip
 from optionslab_amd.black_scholes import implied_volatility
 from optionslab_amd.exceptions import AccelerationError
@@ -28,6 +26,7 @@ from optionslab_amd.heston import calibration_objective
 from optionslab_amd.monte_carlo import sobol_tables
 from oracle import philox_oracle
 from tests import heston_qe_reference as qe
+from tests.gpu_support import heston_pricer as pricer
 
 pytestmark = pytest.mark.gpu
 
@@ -37,12 +36,6 @@ MODEL_NAMES = ("feller_violated", "steep", "usual")
 SEQUENTIAL = dict(method="qmc", path_construction="sequential", scheme="qe")
 PHILOX_SEED = 3
 WORST = {}                                              # the worst deviations seen, printed by every tie
-
-
-def pricer(model):
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore", UserWarning)                               # Feller
-        return ol.HestonPricer(*model)
 
 
 @functools.lru_cache(maxsize=None)

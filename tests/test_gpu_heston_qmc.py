@@ -11,14 +11,13 @@ of the recursion differ by at most 1.1e-13 in ln S and 5e-14 in v over these mod
 """
 import collections
 import math
-import warnings
 
 import numpy as np
 import pytest
 
-import optionslab_amd as ol
 from optionslab_amd import _hip
 from optionslab_amd.monte_carlo import sobol_tables
+from tests.gpu_support import heston_pricer as pricer
 from tests.sobol_reference import bridge_walk, normal_chunks
 
 pytestmark = pytest.mark.gpu
@@ -34,12 +33,6 @@ STEPS = (1, 2, 13, 64, 252, 1000, 1024, 4096)                                   
 
 def constructions(n):
     return ("bridge", "sequential") if n <= 1024 else ("sequential",)
-
-
-def pricer(model):
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore", UserWarning)                               # Feller
-        return ol.HestonPricer(*model)
 
 
 # ----------------------------------------------------------------------------------------------------------- oracle ----

@@ -18,7 +18,6 @@ import copy
 import json
 import math
 import os
-import warnings
 
 import numpy as np
 import pytest
@@ -28,6 +27,7 @@ from optionslab_amd import _hip
 from optionslab_amd.greeks import compute_greeks_unified, fd_steps
 from optionslab_amd.monte_carlo import sobol_tables
 from tests import heston_scenario_oracle as hso
+from tests.gpu_support import heston_pricer as pricer
 from tests.heston_path_oracle import CALM, FELLER_VIOLATING, USUAL
 
 pytestmark = pytest.mark.gpu
@@ -37,12 +37,6 @@ S, K, T, R, Q = 100.0, 100.0, 1.0, 0.05, 0.02
 MODELS = (USUAL, FELLER_VIOLATING)
 KINDS = ("pseudo", "bridge", "sequential")
 GREEK_NAMES = ("price", "delta", "gamma", "vega", "theta", "rho", "vanna", "charm", "vomma")
-
-
-def pricer(model):
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore", UserWarning)                               # Feller
-        return ol.HestonPricer(*model)
 
 
 def scenario(S_=S, K_=K, T_=T, r_=R, q_=Q, call=True, model=USUAL):

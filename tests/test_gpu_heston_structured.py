@@ -20,12 +20,10 @@ import functools
 import json
 import math
 import os
-import warnings
 
 import numpy as np
 import pytest
 
-import optionslab_amd as ol
 from optionslab_amd import _hip
 from optionslab_amd.exceptions import AccelerationError
 from optionslab_amd.monte_carlo import sobol_tables
@@ -33,6 +31,8 @@ from oracle import numpy_reference as orc
 from oracle import philox_oracle
 from tests import heston_path_oracle as hpo
 from tests import heston_qe_reference as qe
+from tests import gpu_support
+from tests.gpu_support import heston_pricer as pricer
 
 pytestmark = pytest.mark.gpu
 
@@ -47,12 +47,6 @@ COUNTS = (1, 63, 65, 1000, 4097)
 SHAPE_IDS = [f"n{n}-f{f}-p{p}" for n, f, p in SHAPES]
 EULER_MODELS = (hpo.USUAL, hpo.FELLER_VIOLATING)
 QE_MODELS = (qe.FELLER_VIOLATED, qe.STEEP, qe.USUAL)
-
-
-def pricer(model):
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore", UserWarning)                               # Feller
-        return ol.HestonPricer(*model)
 
 
 def autocall_payoffs(spot, f, contract=AUTOCALL):
@@ -92,12 +86,7 @@ def branch_mix(spot, f):
     return float(early.mean()), float(coupon.mean()), float(loss.mean())
 
 
-def check_sums(st, x, label):
-    want, want2 = float(np.sum(x)), float(np.sum(x * x))
-    print(label, "sum", st.sum, "oracle", want, "sumsq", st.sumsq, "oracle", want2)
-    assert st.n == len(x), label
-    assert st.sum == pytest.approx(want, **TIE), label
-    assert st.sumsq == pytest.approx(want2, **TIE), label
+check_sums = functools.partial(gpu_support.check_sums, tie=TIE)
 
 
 def philox_autocall(model, f, N, n, seed, qe_scheme, antithetic=False, path_offset=0, contract=AUTOCALL):

@@ -12,10 +12,10 @@ must add up, four combined standard errors against the reference's fixture (test
 6. The reference at workload level.
 7. Calibration: the deterministic conditions only.
 """
+import functools
 import json
 import math
 import os
-import warnings
 
 import numpy as np
 import pytest
@@ -26,6 +26,8 @@ from optionslab_amd.black_scholes import implied_volatility
 from optionslab_amd.heston import calibrate_heston, calibration_objective
 from optionslab_amd.monte_carlo import sobol_tables
 from tests import heston_path_oracle as hpo
+from tests import gpu_support
+from tests.gpu_support import heston_pricer as pricer
 from tests.heston_path_oracle import CALM, FELLER_VIOLATING, Q, R, S, T, USUAL
 
 pytestmark = pytest.mark.gpu
@@ -33,12 +35,6 @@ pytestmark = pytest.mark.gpu
 TIE = dict(rel=1e-10, abs=1e-12)
 STRIKES = (80.0, 100.0, 120.0)
 OPTION_TYPES = ("call", "put")
-
-
-def pricer(model):
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore", UserWarning)                               # Feller
-        return ol.HestonPricer(*model)
 
 
 def cells_for(n):
@@ -65,12 +61,7 @@ def payoff(spot, strike, step, option_type):
     return np.maximum((1.0 if option_type == "call" else -1.0) * (spot[:, step] - strike), 0)
 
 
-def check_sums(st, x, label):
-    want, want2 = float(np.sum(x)), float(np.sum(x * x))
-    print(label, "sum", st.sum, "oracle", want, "sumsq", st.sumsq, "oracle", want2)
-    assert st.n == len(x), label
-    assert st.sum == pytest.approx(want, **TIE), label
-    assert st.sumsq == pytest.approx(want2, **TIE), label
+check_sums = functools.partial(gpu_support.check_sums, tie=TIE)
 
 
 def check_cells(stats, spot_legs, cells, option_type, label):

@@ -15,6 +15,7 @@ import pytest
 
 import optionslab_amd as ol
 from optionslab_amd import _hip
+from tests.gpu_support import device_fixture
 from tools.probe import binding as probe
 
 pytestmark = pytest.mark.gpu
@@ -23,13 +24,12 @@ ATM = (100.0, 100.0, 1.0, 0.05, 0.2)
 hip = probe.hip
 
 
-@pytest.fixture(scope="module", autouse=True)
-def _device():
-    assert hip.device_info()["arch"].startswith("gfx950")
-    yield
+def _knobs_off():
     for knob in (probe.TUNE_FAULT_SHARD, probe.TUNE_FORCE_NV, probe.TUNE_MULTI_REHEARSAL):
         probe.tune(knob, 0)
-    hip.shutdown()
+
+
+_device = device_fixture(hip, after=_knobs_off)
 
 
 @pytest.fixture

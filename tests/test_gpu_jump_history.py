@@ -8,13 +8,13 @@ on the device.  Each of the five entry points (257 x 13, Merton M0) runs after
   (c) olmc_jump_diffusion (the kernel whose stream these share);
   (d) a refused oljd_price (an argument error, made before any device work).
 """
-import numpy as np
 import pytest
 
 from optionslab_amd import _hip
 from optionslab_amd.exceptions import AccelerationError
 from tests import call_catalogue as cc
 from tests import heston_path_oracle as hpo
+from tests.history import Device, baseline_fixture, check_fresh_bits_after
 
 pytestmark = [pytest.mark.gpu, pytest.mark.filterwarnings("ignore:The balance properties of Sobol")]
 
@@ -23,7 +23,7 @@ N, STEPS = 257, 13
 M0, K1 = (False, 0.5, -0.1, 0.2, 0.0), (True, 60.0, 0.6, 25.0, 20.0)
 AUTOCALL, CLIQUET = (1.0, 0.9, 0.10, 0.8), (0.05, -0.05, 0.30, 0.0)
 ENTRIES = ["oljd_price", "oljd_surface_prices", "oljd_autocallable", "oljd_cliquet", "oljd_paths"]
-_dead = []            # the message of a call that failed unexpectedly: nothing more is started on the device
+DEVICE = Device()
 
 
 def calls(model=M0, n=STEPS, seed=cc.SEED_A):
@@ -47,26 +47,7 @@ def refused_price():
     return 0
 
 
-def invoke(call) -> np.ndarray:
-    if _dead:
-        pytest.fail(f"an earlier call failed, nothing more is run on the device: {_dead[0]}")
-    try:
-        return cc.words(call())
-    except BaseException as exc:
-        _dead.append(f"{type(exc).__name__}: {exc}")
-        raise
-
-
-def fresh(call) -> np.ndarray:
-    _hip.shutdown()
-    return invoke(call)
-
-
-@pytest.fixture(scope="module")
-def baseline():
-    if not _hip.hip_available():
-        pytest.fail("no HIP device")
-    return {entry: fresh(call) for entry, call in calls().items()}
+baseline = baseline_fixture(DEVICE, lambda: calls())
 
 
 HISTORIES = {
@@ -80,11 +61,4 @@ HISTORIES = {
 @pytest.mark.parametrize("history", list(HISTORIES))
 @pytest.mark.parametrize("entry", ENTRIES)
 def test_entry_point_gives_the_fresh_library_s_bits_after(baseline, entry, history):
-    _hip.shutdown()
-    for before in HISTORIES[history](entry):
-        invoke(before)
-    got, want = invoke(calls()[entry]), baseline[entry]
-    assert got.shape == want.shape
-    assert np.array_equal(got, want), f"{entry} after {history}: {int(np.count_nonzero(got != want))} of {want.size} words differ"
-    again = invoke(calls()[entry])                              # and once more on the used library
-    assert np.array_equal(again, want)
+    check_fresh_bits_after(DEVICE, baseline, entry, calls()[entry], history, HISTORIES[history](entry))

@@ -7,6 +7,7 @@ sums against per-path payoffs, rel 1e-12 for shards, 3.5 standard errors against
 two Monte Carlo prices.  Every tie first asserts that no path comes within 1e-9 (relative) of a level it could cross: the kernels
 decide in log space, the matrix route after an exponential.
 """
+import functools
 import hashlib
 import json
 import math
@@ -19,6 +20,7 @@ import optionslab_amd as ol
 from optionslab_amd import _hip
 from optionslab_amd.exceptions import AccelerationError
 from tests import heston_path_oracle as hpo
+from tests import gpu_support
 from tests.test_gpu_heston_structured import (AUTOCALL, CLIQUET, COUNTS, SHAPES, assert_clear_of_the_levels, autocall_payoffs, branch_mix,
                                                cliquet_payoffs)
 
@@ -67,12 +69,7 @@ def assert_clear_of_the_barriers(spot, label):
     assert gap > 1e-9, (label, gap)
 
 
-def check_sums(st, x, label):
-    want, want2 = float(np.sum(x)), float(np.sum(x * x))
-    print(label, "sum", st.sum, "oracle", want, "sumsq", st.sumsq, "oracle", want2)
-    assert st.n == len(x), label
-    assert st.sum == pytest.approx(want, **TIE), label
-    assert st.sumsq == pytest.approx(want2, **TIE), label
+check_sums = functools.partial(gpu_support.check_sums, tie=TIE)
 
 
 def check_every_payoff(label, spots, model, N, n, seed, antithetic):

@@ -11,19 +11,19 @@ runs after
   (c) a Philox ollv_price (the table uploaded in units of the raw normals);
   (d) a refused olvq_price (an argument error, made before any device work).
 """
-import numpy as np
 import pytest
 
 from optionslab_amd import _hip
 from optionslab_amd.exceptions import AccelerationError
 from tests import call_catalogue as cc
 from tests import test_gpu_local_vol as lv
+from tests.history import Device, baseline_fixture, check_fresh_bits_after
 
 pytestmark = [pytest.mark.gpu, pytest.mark.filterwarnings("ignore:The balance properties of Sobol")]
 
 N, STEPS = 257, 13
 ENTRIES = ["olvq_price", "olvq_paths", "olvq_surface_prices"]
-_dead = []            # the message of a call that failed unexpectedly: nothing more is started on the device
+DEVICE = Device()
 
 
 def cells(n):
@@ -52,26 +52,7 @@ def refused_price():
     return 0
 
 
-def invoke(call) -> np.ndarray:
-    if _dead:
-        pytest.fail(f"an earlier call failed, nothing more is run on the device: {_dead[0]}")
-    try:
-        return cc.words(call())
-    except BaseException as exc:
-        _dead.append(f"{type(exc).__name__}: {exc}")
-        raise
-
-
-def fresh(call) -> np.ndarray:
-    _hip.shutdown()
-    return invoke(call)
-
-
-@pytest.fixture(scope="module")
-def baseline():
-    if not _hip.hip_available():
-        pytest.fail("no HIP device")
-    return {entry: fresh(call) for entry, call in calls("33x128").items()}
+baseline = baseline_fixture(DEVICE, lambda: calls("33x128"))
 
 
 HISTORIES = {
@@ -86,11 +67,4 @@ HISTORIES = {
 @pytest.mark.parametrize("history", list(HISTORIES))
 @pytest.mark.parametrize("entry", ENTRIES)
 def test_entry_point_gives_the_fresh_library_s_bits_after(baseline, entry, history):
-    _hip.shutdown()
-    for before in HISTORIES[history](entry):
-        invoke(before)
-    got, want = invoke(calls("33x128")[entry]), baseline[entry]
-    assert got.shape == want.shape
-    assert np.array_equal(got, want), f"{entry} after {history}: {int(np.count_nonzero(got != want))} of {want.size} words differ"
-    again = invoke(calls("33x128")[entry])                      # and once more on the used library
-    assert np.array_equal(again, want)
+    check_fresh_bits_after(DEVICE, baseline, entry, calls("33x128")[entry], history, HISTORIES[history](entry))

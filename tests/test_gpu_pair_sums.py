@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from optionslab_amd import _hip
+from tests.gpu_support import device_fixture
 
 pytestmark = pytest.mark.gpu
 
@@ -20,12 +21,7 @@ N = 4096
 REL = 2e-6        # fp32 partial sums and hardware transcendentals on the normal sum, times vol <= 0.2
 
 
-@pytest.fixture(scope="module", autouse=True)
-def _device():
-    info = _hip.device_info()
-    assert info["arch"].startswith("gfx950"), info
-    yield
-    _hip.shutdown()
+_device = device_fixture()
 
 
 @pytest.mark.parametrize("M", [1, 2, 3, 4, 5, 7, 8, 15, 16, 17, 63, 64, 252, 253])

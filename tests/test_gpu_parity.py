@@ -19,6 +19,7 @@ import optionslab_amd as ol
 from optionslab_amd import _hip
 from oracle import numpy_reference as orc
 from oracle import philox_oracle as po
+from tests.gpu_support import device_fixture
 
 pytestmark = pytest.mark.gpu
 
@@ -28,12 +29,7 @@ Z_ABS_TOL = 2e-5        # |z_gpu - z_checker| per normal (fp32 normals, hardware
 REL_STREAM_TOL = 2e-6   # price vs the same-stream C checker
 
 
-@pytest.fixture(scope="module", autouse=True)
-def _device():
-    info = _hip.device_info()
-    assert info["arch"].startswith("gfx950"), info
-    yield
-    _hip.shutdown()
+_device = device_fixture()
 
 
 # ------------------------------------------------------------------ RNG stream

@@ -14,11 +14,12 @@ import pytest
 
 from optionslab_amd import _hip
 from tests import path_kernels_calls as pk
+from tests.history import Device
 
 pytestmark = [pytest.mark.gpu, pytest.mark.filterwarnings("ignore:The balance properties of Sobol")]
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "path_kernels_parent_bits.json")
-_dead = []            # the message of a call that failed unexpectedly: nothing more is started on the device
+DEVICE = Device(record=lambda words: words)             # pk.record takes the label: the calls below record themselves
 
 
 @pytest.fixture(scope="module")
@@ -30,16 +31,6 @@ def golden():
     return doc["shapes"]
 
 
-def invoke(label, call):
-    if _dead:
-        pytest.fail(f"an earlier call failed, nothing more is run on the device: {_dead[0]}")
-    try:
-        return pk.record(label, call())
-    except BaseException as exc:
-        _dead.append(f"{label}: {type(exc).__name__}: {exc}")
-        raise
-
-
 @pytest.mark.parametrize("group", pk.GROUPS)
 @pytest.mark.parametrize("shape", list(pk.SHAPES))
 def test_every_call_gives_the_parent_commit_s_words(golden, shape, group):
@@ -49,7 +40,7 @@ def test_every_call_gives_the_parent_commit_s_words(golden, shape, group):
     assert set(calls) == set(want) and len(calls) > 0
     _hip.tune(_hip.TUNE_GRID_CAP, cap)
     try:
-        got = {label: invoke(label, call) for label, call in calls.items()}
+        got = {label: DEVICE.invoke(label, lambda: pk.record(label, call())) for label, call in calls.items()}
     finally:
         _hip.tune(_hip.TUNE_GRID_CAP, 0)                        # the knob is process-global: 0 again whatever happens
     differ = [label for label in calls if got[label] != want[label]]

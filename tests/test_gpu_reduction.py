@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 from tests import reduction_reference as ref
+from tests.gpu_support import device_fixture
 from tools.probe import binding as probe
 
 pytestmark = pytest.mark.gpu
@@ -24,12 +25,7 @@ ATM = (100.0, 100.0, 1.0, 0.05, 0.2)
 hip = probe.hip
 
 
-@pytest.fixture(scope="module", autouse=True)
-def _device():
-    assert hip.device_info()["arch"].startswith("gfx950")
-    yield
-    probe.tune(probe.TUNE_FORCE_NV, 0)
-    hip.shutdown()
+_device = device_fixture(hip, after=lambda: probe.tune(probe.TUNE_FORCE_NV, 0))
 
 
 @functools.lru_cache(maxsize=None)

@@ -1,7 +1,6 @@
 """HestonPricer.price_asian / price_barrier / price_lookback without a device: the ABI declares, binds and exports the two entry points,
 they refuse bad arguments with exact messages before any device work, the Python refusals come before the library is loaded, the
 methods reach the bindings with the payoff codes of the header, and the reference fixture is whole."""
-import ctypes as C
 import json
 import math
 import os
@@ -13,7 +12,8 @@ import pytest
 
 import optionslab_amd as ol
 from optionslab_amd import _hip
-from optionslab_amd.build import LIBRARY, PROBE_LIBRARY, build_library, build_probe_library
+from optionslab_amd.build import LIBRARY, PROBE_LIBRARY, build_probe_library
+from tests.abi_support import library, no_library, refused, sobol as _sobol, _ST
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 S, K, T, R, Q = 100.0, 100.0, 1.0, 0.05, 0.01
@@ -32,12 +32,6 @@ def _calls(p):
 
 
 # ------------------------------------------------------------------------------------------------------------ the ABI ----
-@pytest.fixture(scope="module")
-def library():
-    build_library()
-    return _hip.load_library()
-
-
 def _exported(path):
     out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
     return set(re.findall(r"\bT (olmc_[a-z0-9_]+)", out))
@@ -55,14 +49,6 @@ def test_the_header_declares_the_bindings_bind_and_both_libraries_export_the_ent
     assert (_hip.PATH_ASIAN_ARITHMETIC, _hip.PATH_ASIAN_GEOMETRIC) == (6, 7)
     assert "#define OLMC_ABI_VERSION 6 " in header
     assert library.olmc_abi_version() == 6
-
-
-def _ST():
-    return C.byref(_hip.Stats())
-
-
-def _sobol(dims):
-    return (C.c_uint32 * (30 * dims))(*range(1, 30 * dims + 1)), (C.c_uint32 * dims)()
 
 
 _PRICE = (S, K, T, R, Q, 1, *MODEL)                               # S K T r q is_call kappa theta sigma_v rho v0
@@ -109,21 +95,10 @@ _REFUSALS = [
 @pytest.mark.parametrize("name,args,message", _REFUSALS, ids=[f"{n}-{i}" for i, (n, _a, _m) in enumerate(_REFUSALS)])
 def test_entry_points_refuse_bad_arguments_before_touching_a_device(library, name, args, message):
     """Each refusal answers OLMC_ERR_ARG (1) with its exact message, ahead of any device work (no device is initialised here)."""
-    rc = getattr(library, name)(*args())
-    assert rc == 1
-    assert library.olmc_last_error().decode() == message
+    refused(library, getattr(library, name)(*args()), message)
 
 
 # --------------------------------------------------------------------------------------------------------- the methods ----
-@pytest.fixture
-def no_library(monkeypatch):
-    """Any attempt to load the library (hence to reach the device) fails the test."""
-    def touched(*a, **k):
-        raise AssertionError("the library was loaded")
-
-    monkeypatch.setattr(_hip, "lib", touched)
-
-
 @pytest.mark.parametrize("kwargs,match", [
     (dict(method="sobol"), "method"),
     (dict(method="qmc", path_construction="pca"), "path_construction"),

@@ -10,7 +10,6 @@ tests/test_gpu_heston_qe.py ties the device to) and the host logic of the `schem
 import ctypes as C
 import inspect
 import math
-import warnings
 
 import numpy as np
 import pytest
@@ -20,24 +19,11 @@ import optionslab_amd as ol
 from optionslab_amd import _hip
 from optionslab_amd import heston as hes
 from tests import heston_qe_reference as qe
+from tests.abi_support import library, no_library, refused, sobol as _sobol
+from tests.gpu_support import heston_pricer as pricer
 
 S, R, Q, T = 100.0, 0.05, 0.0, 1.0
 QE_NAMES = ("olmc_heston_qe_surface", "olmc_heston_qe_qmc_surface", "olmc_heston_qe_paths", "olmc_heston_qe_qmc_paths")
-
-
-def pricer(model):
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore", UserWarning)                               # Feller
-        return ol.HestonPricer(*model)
-
-
-@pytest.fixture
-def no_library(monkeypatch):
-    """Any attempt to load the library (hence to reach the device) fails the test."""
-    def touched(*a, **k):
-        raise AssertionError("the library was loaded")
-
-    monkeypatch.setattr(_hip, "lib", touched)
 
 
 # ---------------------------------------------------------------------------------------------------- 1. the moments ----
@@ -273,14 +259,6 @@ def test_the_default_grid_of_a_qe_calibration_has_16_steps_a_year(recorded):
 
 
 # ---------------------------------------------------------------------------------------------------- 5. the C ABI ----
-@pytest.fixture(scope="module")
-def library():
-    from optionslab_amd.build import build_library
-
-    build_library()
-    return _hip.load_library()
-
-
 def test_the_entry_points_are_declared_bound_and_exported(library):
     from tests.test_abi_cpu import declared_symbols
 
@@ -296,10 +274,6 @@ def _st(k=16):
 
 def _cells(k=1, step=4):
     return (C.c_double * max(k, 1))(*[100.0] * k), (C.c_int32 * max(k, 1))(*[step] * k)
-
-
-def _sobol(dims):
-    return (C.c_uint32 * (30 * dims))(*range(1, 30 * dims + 1)), (C.c_uint32 * dims)()
 
 
 def _mats():
@@ -366,6 +340,4 @@ _REFUSALS += [
 
 @pytest.mark.parametrize("name,args,message", _REFUSALS, ids=[f"{n}-{i}" for i, (n, _a, _m) in enumerate(_REFUSALS)])
 def test_the_entry_points_refuse_bad_arguments_before_touching_a_device(library, name, args, message):
-    rc = getattr(library, name)(*args())
-    assert rc == 1
-    assert library.olmc_last_error().decode() == message
+    refused(library, getattr(library, name)(*args()), message)

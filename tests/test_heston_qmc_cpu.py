@@ -1,7 +1,6 @@
 """method="qmc" on HestonPricer without a device: every refusal comes before the device is touched, "qmc" reaches the Sobol bindings
 with tables of 2 n dimensions, "pseudo" and the default reach the Philox ones with the arguments they always got, a missing GPU is
 loud, and the C entry points refuse bad arguments before any device work."""
-import ctypes as C
 import os
 
 import numpy as np
@@ -9,8 +8,8 @@ import pytest
 
 import optionslab_amd as ol
 from optionslab_amd import _hip
-from optionslab_amd.build import build_library
 from optionslab_amd.exceptions import AccelerationError
+from tests.abi_support import library, no_device, _out, refused, sobol as _sobol, _ST
 
 S, K, T, R, Q = 100.0, 100.0, 1.0, 0.05, 0.01
 MODEL = (2.0, 0.04, 0.3, -0.7, 0.04)                      # kappa theta sigma_v rho v0
@@ -24,16 +23,6 @@ def _pricer():
 def _calls(pricer):
     """The two public calls as functions of their keywords (n_paths, n_steps and the rest)."""
     return [lambda **kw: pricer.price_monte_carlo(S, K, T, R, Q, "call", **kw), lambda **kw: pricer.simulate_paths(S, T, R, Q, **kw)]
-
-
-@pytest.fixture
-def no_device(monkeypatch):
-    """Any attempt to reach the library (hence the device) fails the test."""
-    def touched(*a, **k):
-        raise AssertionError("the device was touched")
-
-    for name in _BINDINGS:
-        monkeypatch.setattr(_hip, name, touched, raising=False)
 
 
 @pytest.mark.parametrize("kwargs,match", [
@@ -162,24 +151,6 @@ def test_the_bindings_refuse_tables_with_an_odd_number_of_dimensions(monkeypatch
 
 
 # ------------------------------------------------------------------------------------------------- the C entry points ----
-@pytest.fixture(scope="module")
-def library():
-    build_library()
-    return _hip.load_library()
-
-
-def _ST():
-    return C.byref(_hip.Stats())
-
-
-def _sobol(dims):
-    return (C.c_uint32 * (30 * dims))(*range(1, 30 * dims + 1)), (C.c_uint32 * dims)()
-
-
-def _out(n_points, n_steps):
-    return (C.c_double * (n_points * (n_steps + 1)))()
-
-
 _PRICE = (S, K, T, R, Q, 1, *MODEL)                               # S K T r q is_call kappa theta sigma_v rho v0
 _PATHS = (S, T, R, Q, *MODEL)
 _BAD_RHO = (S, K, T, R, Q, 1, 2.0, 0.04, 0.3, -1.5, 0.04)
@@ -226,16 +197,11 @@ _REFUSALS = [
 @pytest.mark.parametrize("name,args,message", _REFUSALS, ids=[f"{n}-{i}" for i, (n, _a, _m) in enumerate(_REFUSALS)])
 def test_entry_points_refuse_bad_arguments_before_touching_a_device(library, name, args, message):
     """Each refusal answers OLMC_ERR_ARG (1) with its exact message, ahead of any device work (no device is initialised here)."""
-    rc = getattr(library, name)(*args())
-    assert rc == 1
-    assert library.olmc_last_error().decode() == message
+    refused(library, getattr(library, name)(*args()), message)
 
 
 def test_the_philox_heston_entry_points_still_refuse_as_before(library):
-    assert library.olmc_heston(*_BAD_RHO, 0, 64, 8, 1, 0, _ST()) == 1
-    assert library.olmc_last_error().decode() == "rho must be in [-1, 1]"
-    assert library.olmc_heston(*_PRICE, 0, 64, 8, 1, 0, None) == 1
-    assert library.olmc_last_error().decode() == "null pointer"
-    assert library.olmc_heston_paths(S, T, R, Q, 2.0, 0.04, 0.3, -1.5, 0.04, 4, 8, 1, 1, _out(4, 8), _out(4, 8)) == 1
-    assert library.olmc_last_error().decode() == "rho must be in [-1, 1]"
+    refused(library, library.olmc_heston(*_BAD_RHO, 0, 64, 8, 1, 0, _ST()), "rho must be in [-1, 1]")
+    refused(library, library.olmc_heston(*_PRICE, 0, 64, 8, 1, 0, None), "null pointer")
+    refused(library, library.olmc_heston_paths(S, T, R, Q, 2.0, 0.04, 0.3, -1.5, 0.04, 4, 8, 1, 1, _out(4, 8), _out(4, 8)), "rho must be in [-1, 1]")
     assert library.olmc_abi_version() == 6

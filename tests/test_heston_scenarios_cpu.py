@@ -9,26 +9,11 @@ import pytest
 import optionslab_amd as ol
 from optionslab_amd import _hip
 from optionslab_amd import heston as hes
-from optionslab_amd.build import build_library
 from optionslab_amd.greeks import fd_steps
+from tests.abi_support import library, no_library, _out17 as _out, refused, sobol as _sobol
 
 S, K, T, R, Q = 100.0, 100.0, 1.0, 0.05, 0.02
 MODEL = (2.0, 0.04, 0.3, -0.7, 0.04)                      # kappa theta sigma_v rho v0
-
-
-@pytest.fixture(scope="module")
-def library():
-    build_library()
-    return _hip.load_library()
-
-
-@pytest.fixture
-def no_library(monkeypatch):
-    """Any attempt to reach the device fails the test."""
-    def touched(*a, **k):
-        raise AssertionError("the device was touched")
-
-    monkeypatch.setattr(_hip, "lib", touched)
 
 
 def scenario(S_=S, K_=K, T_=T, r_=R, q_=Q, call=True, model=MODEL, **over):
@@ -181,14 +166,6 @@ def _sc(*scenarios):
     return _hip._scenarios(list(scenarios) or [scenario()])
 
 
-def _sobol(dims):
-    return (C.c_uint32 * (30 * max(dims, 1)))(*range(1, 30 * max(dims, 1) + 1)), (C.c_uint32 * max(dims, 1))()
-
-
-def _out():
-    return (_hip.Stats * 17)()
-
-
 _SEVEN = [scenario(v0=0.01 * (i + 1)) for i in range(7)]
 _GREEKS = (S, K, T, R, 0.2, Q, 1, 2.0, 0.04, 0.3)                                   # ... rho follows
 _REFUSALS = [
@@ -244,9 +221,7 @@ _REFUSALS = [
 @pytest.mark.parametrize("name,args,message", _REFUSALS, ids=[f"{n}-{i}" for i, (n, _a, _m) in enumerate(_REFUSALS)])
 def test_entry_points_refuse_bad_arguments_before_touching_a_device(library, name, args, message):
     """Each refusal answers OLMC_ERR_ARG (1) with its exact message, ahead of any device work (no device is initialised here)."""
-    rc = getattr(library, name)(*args())
-    assert rc == 1
-    assert library.olmc_last_error().decode() == message
+    refused(library, getattr(library, name)(*args()), message)
 
 
 def test_the_bindings_check_the_tables(no_library):

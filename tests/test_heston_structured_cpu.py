@@ -8,7 +8,6 @@ import inspect
 import json
 import math
 import os
-import warnings
 
 import numpy as np
 import pytest
@@ -16,27 +15,14 @@ import pytest
 import optionslab_amd as ol
 from optionslab_amd import _hip
 from tests import heston_qe_reference as qe
+from tests.abi_support import library, no_library, refused, sobol as _sobol
+from tests.gpu_support import heston_pricer as pricer
 
 S, R, Q, T = 100.0, 0.05, 0.01, 1.0
 NAMES = ("olmc_heston_autocallable", "olmc_heston_autocallable_qmc", "olmc_heston_cliquet", "olmc_heston_cliquet_qmc")
 BINDINGS = ("heston_autocallable", "heston_autocallable_qmc", "heston_cliquet", "heston_cliquet_qmc")
 AUTOCALL = (1.0, 0.9, 0.10, 0.8)          # autocall, coupon, rate, knock-in
 CLIQUET = (0.05, -0.05, 0.30, 0.0)
-
-
-def pricer(model):
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore", UserWarning)                               # Feller
-        return ol.HestonPricer(*model)
-
-
-@pytest.fixture
-def no_library(monkeypatch):
-    """Any attempt to load the library (hence to reach the device) fails the test."""
-    def touched(*a, **k):
-        raise AssertionError("the library was loaded")
-
-    monkeypatch.setattr(_hip, "lib", touched)
 
 
 # ---------------------------------------------------------------------------------------------------- the signatures ----
@@ -171,14 +157,6 @@ def test_an_observation_frequency_beyond_the_steps_is_one_unreachable_observatio
 
 
 # ---------------------------------------------------------------------------------------------------------- the C ABI ----
-@pytest.fixture(scope="module")
-def library():
-    from optionslab_amd.build import build_library
-
-    build_library()
-    return _hip.load_library()
-
-
 def test_the_entry_points_are_declared_bound_and_exported(library):
     from tests.test_abi_cpu import declared_symbols, exported_symbols
 
@@ -194,10 +172,6 @@ def test_the_entry_points_are_declared_bound_and_exported(library):
 
 def _st():
     return _hip.Stats()
-
-
-def _sobol(dims):
-    return (C.c_uint32 * (30 * dims))(*range(1, 30 * dims + 1)), (C.c_uint32 * dims)()
 
 
 _M = (2.0, 0.04, 0.3, -0.7, 0.04)
@@ -274,17 +248,13 @@ for _product, _names in (("autocallable", NAMES[:2]), ("cliquet", NAMES[2:])):
 
 @pytest.mark.parametrize("name,args,message", _REFUSALS, ids=[f"{n}-{i}" for i, (n, _a, _m) in enumerate(_REFUSALS)])
 def test_the_entry_points_refuse_bad_arguments_before_touching_a_device(library, name, args, message):
-    rc = getattr(library, name)(*args())
-    assert rc == 1
-    assert library.olmc_last_error().decode() == message
+    refused(library, getattr(library, name)(*args()), message)
 
 
 def test_a_negative_start_variance_is_eulers_to_take_and_qes_to_refuse(library):
     """v0 < 0 means under Euler what it means in olmc_heston: it passes the argument checks (the next refusal shows it did)."""
-    rc = library.olmc_heston_autocallable(*_philox("autocallable", _model(v0=-0.01), n_local=0)())
-    assert rc == 1 and library.olmc_last_error().decode() == "n_paths must be >= 1"
-    rc = library.olmc_heston_cliquet(*_philox("cliquet", _model(v0=-0.01), scheme=1, n_local=0)())
-    assert rc == 1 and library.olmc_last_error().decode() == "v0 must be non-negative for the QE scheme"
+    refused(library, library.olmc_heston_autocallable(*_philox("autocallable", _model(v0=-0.01), n_local=0)()), "n_paths must be >= 1")
+    refused(library, library.olmc_heston_cliquet(*_philox("cliquet", _model(v0=-0.01), scheme=1, n_local=0)()), "v0 must be non-negative for the QE scheme")
 
 
 # ------------------------------------------------------------------------------------------------- the golden file ----

@@ -17,21 +17,13 @@ import optionslab_amd as ol
 from optionslab_amd import _hip
 from optionslab_amd import heston as hes
 from optionslab_amd.black_scholes import black_scholes, implied_volatility
-from optionslab_amd.build import LIBRARY, PROBE_LIBRARY, build_library, build_probe_library
+from optionslab_amd.build import LIBRARY, PROBE_LIBRARY, build_probe_library
+from tests.abi_support import library, no_library, _out17 as _out, refused, sobol as _sobol
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 S, R, Q = 100.0, 0.05, 0.01
 MODEL = (2.0, 0.04, 0.3, -0.7, 0.04)                      # kappa theta sigma_v rho v0
 NAMES = ("olmc_heston_surface", "olmc_heston_qmc_surface")
-
-
-@pytest.fixture
-def no_library(monkeypatch):
-    """Any attempt to load the library (hence to reach the device) fails the test."""
-    def touched(*a, **k):
-        raise AssertionError("the library was loaded")
-
-    monkeypatch.setattr(_hip, "lib", touched)
 
 
 def _market(**over):
@@ -207,12 +199,6 @@ def test_the_references_import_lines_resolve_under_compat():
 
 
 # ------------------------------------------------------------------------------------------------------------ the ABI ----
-@pytest.fixture(scope="module")
-def library():
-    build_library()
-    return _hip.load_library()
-
-
 def _exported(path):
     out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
     return set(re.findall(r"\bT (olmc_[a-z0-9_]+)", out))
@@ -232,14 +218,6 @@ def test_the_header_declares_the_bindings_bind_and_both_libraries_export_the_ent
 
 def _cells(strikes=(90.0, 100.0), steps=(2, 4)):
     return (C.c_double * len(strikes))(*strikes), (C.c_int32 * len(steps))(*steps), len(strikes)
-
-
-def _sobol(dims):
-    return (C.c_uint32 * (30 * max(dims, 1)))(*range(1, 30 * max(dims, 1) + 1)), (C.c_uint32 * max(dims, 1))()
-
-
-def _out():
-    return (_hip.Stats * 17)()
 
 
 _HEAD = (100.0, 1.0, 0.05, 0.01, 1, 2.0, 0.04, 0.3)                                  # S T r q is_call kappa theta sigma_v (rho, v0 follow)
@@ -287,9 +265,7 @@ _REFUSALS = [
 @pytest.mark.parametrize("name,args,message", _REFUSALS, ids=[f"{n}-{i}" for i, (n, _a, _m) in enumerate(_REFUSALS)])
 def test_entry_points_refuse_bad_arguments_before_touching_a_device(library, name, args, message):
     """Each refusal answers OLMC_ERR_ARG (1) with its exact message, ahead of any device work (no device is initialised here)."""
-    rc = getattr(library, name)(*args())
-    assert rc == 1
-    assert library.olmc_last_error().decode() == message
+    refused(library, getattr(library, name)(*args()), message)
 
 
 def test_the_bindings_check_the_cell_lists(no_library):

@@ -8,27 +8,18 @@
 import ctypes as C
 import inspect
 import os
-import re
 import shutil
 import subprocess
 import sys
 
-import pytest
-
 import optionslab_amd as ol
 from optionslab_amd import _hip
-from optionslab_amd.build import LIBRARY, build_library
+from tests.abi_support import assert_header_matches, library, refused
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "olmc_jump.h")
 NAMES = ["oljd_autocallable", "oljd_cliquet", "oljd_paths", "oljd_price", "oljd_surface_prices"]
 METHODS = ("price_asian", "price_barrier", "price_lookback", "price_surface", "price_autocallable", "price_cliquet")
-
-
-@pytest.fixture(scope="module")
-def library():
-    build_library()
-    return _hip.load_library()
 
 
 def c_compiler():
@@ -48,16 +39,7 @@ def test_header_compiles_as_c(tmp_path):
 
 
 def test_header_exports_and_prototypes_agree(library):
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    declared = sorted(set(re.findall(r"\b(oljd_[a-z0-9_]+)\s*\(", text)))
-    out = subprocess.run(["nm", "-D", "--defined-only", LIBRARY], capture_output=True, text=True, check=True).stdout
-    exported = sorted(set(re.findall(r"\bT (oljd_[a-z0-9_]+)", out)))
-    assert declared == exported == sorted(_hip.JD_PROTOTYPES) == NAMES
-    for name, (res, args) in _hip.JD_PROTOTYPES.items():
-        fn = getattr(library, name)
-        assert fn.restype is res and list(fn.argtypes) == list(args)
-    assert not set(_hip.JD_PROTOTYPES) & (set(_hip.PROTOTYPES) | set(_hip.LV_PROTOTYPES) | set(_hip.LVQ_PROTOTYPES))
-    assert library.olmc_abi_version() == 6
+    assert_header_matches(library, HEADER, "oljd_", _hip.JD_PROTOTYPES, NAMES)
     assert _hip.JD_EUROPEAN == 8 == _hip.LV_EUROPEAN
 
 
@@ -77,10 +59,6 @@ def test_the_model_struct_has_the_headers_layout(tmp_path):
     m = _hip.jd_model(True, 1.5, 0.4, 10.0, 5.0)
     assert (m.model, m.pad, m.lambda_j, m.a1, m.a2, m.a3) == (1, 0, 1.5, 0.4, 10.0, 5.0)
     assert _hip.jd_model(False, 0.5, -0.1, 0.2).a3 == 0.0
-
-
-def refused(library, call, message):
-    assert call() == 1 and library.olmc_last_error().decode() == message, (library.olmc_last_error().decode(), message)
 
 
 def test_every_refusal_answers_its_message_before_any_device_work(library):
@@ -103,12 +81,12 @@ def test_every_refusal_answers_its_message_before_any_device_work(library):
     def every(message, skip=(), **kw):
         for name, call in entries(**kw).items():
             if name not in skip:
-                refused(library, call, message)
+                refused(library, call(), message)
 
     every("null pointer", m=None)
     every("null pointer", m=C.byref(good), st=False)
-    refused(library, lambda: library.oljd_surface_prices(S, T, R, SIGMA, Q, 1, C.byref(good), None, steps, 1, 0, N, n, 1, 0, cells), "null pointer")
-    refused(library, lambda: library.oljd_surface_prices(S, T, R, SIGMA, Q, 1, C.byref(good), strikes, None, 1, 0, N, n, 1, 0, cells), "null pointer")
+    refused(library, library.oljd_surface_prices(S, T, R, SIGMA, Q, 1, C.byref(good), None, steps, 1, 0, N, n, 1, 0, cells), "null pointer")
+    refused(library, library.oljd_surface_prices(S, T, R, SIGMA, Q, 1, C.byref(good), strikes, None, 1, 0, N, n, 1, 0, cells), "null pointer")
     for code in (2, -1):
         every("bad jump model", m=C.byref(_hip.JdModel(code, 0, 0.5, -0.1, 0.2, 0.0)))
     every("lambda_j must be non-negative", m=C.byref(_hip.jd_model(False, -0.5, -0.1, 0.2)))
@@ -117,31 +95,31 @@ def test_every_refusal_answers_its_message_before_any_device_work(library):
     every("n_paths must be >= 1", m=C.byref(good), count=0)
     every("path_offset must be >= 0", m=C.byref(good), offset=-1, skip=("oljd_paths",))
     for payoff in (-1, 9):
-        refused(library, entries(C.byref(good), payoff=payoff)["oljd_price"], "bad payoff")
+        refused(library, entries(C.byref(good), payoff=payoff)["oljd_price"](), "bad payoff")
     for kind in range(4):
         for level in (0.0, -5.0):
-            refused(library, entries(C.byref(good), payoff=kind, barrier=level)["oljd_price"], "Barrier must be positive")
+            refused(library, entries(C.byref(good), payoff=kind, barrier=level)["oljd_price"](), "Barrier must be positive")
     for k in (0, 17):
-        refused(library, entries(C.byref(good), k=k)["oljd_surface_prices"], "the number of cells must be in [1, OLMC_MAX_BATCH]")
+        refused(library, entries(C.byref(good), k=k)["oljd_surface_prices"](), "the number of cells must be in [1, OLMC_MAX_BATCH]")
     for bad_step in (0, n + 1):
         two = (C.c_int32 * 2)(n, bad_step)
-        refused(library, lambda: library.oljd_surface_prices(S, T, R, SIGMA, Q, 1, C.byref(good), strikes, two, 2, 0, N, n, 1, 0, cells),
+        refused(library, library.oljd_surface_prices(S, T, R, SIGMA, Q, 1, C.byref(good), strikes, two, 2, 0, N, n, 1, 0, cells),
                 "a cell's step must be in [1, n_steps]")
-    refused(library, entries(C.byref(good), freq=0)["oljd_autocallable"], "observation_freq must be >= 1")
-    refused(library, entries(C.byref(good), freq=n + 1)["oljd_autocallable"], "no observation date: observation_freq > n_steps")
+    refused(library, entries(C.byref(good), freq=0)["oljd_autocallable"](), "observation_freq must be >= 1")
+    refused(library, entries(C.byref(good), freq=n + 1)["oljd_autocallable"](), "no observation date: observation_freq > n_steps")
     for periods in (0, n + 1):
-        refused(library, entries(C.byref(good), periods=periods)["oljd_cliquet"], "n_periods must be in [1, n_steps]")
-    refused(library, entries(C.byref(good), count=1 << 27, n_steps=252)["oljd_paths"], "path matrix would exceed 64 GB")
+        refused(library, entries(C.byref(good), periods=periods)["oljd_cliquet"](), "n_periods must be in [1, n_steps]")
+    refused(library, entries(C.byref(good), count=1 << 27, n_steps=252)["oljd_paths"](), "path matrix would exceed 64 GB")
     # two faults at once: the model comes first
-    refused(library, entries(C.byref(_hip.JdModel(2, 0, 0.5, -0.1, 0.2, 0.0)), payoff=9)["oljd_price"], "bad jump model")
-    refused(library, entries(C.byref(good), payoff=9, count=0)["oljd_price"], "bad payoff")
+    refused(library, entries(C.byref(_hip.JdModel(2, 0, 0.5, -0.1, 0.2, 0.0)), payoff=9)["oljd_price"](), "bad jump model")
+    refused(library, entries(C.byref(good), payoff=9, count=0)["oljd_price"](), "bad payoff")
     # the model's checks hold the step count (make_jump), so it comes before the payoff; the path count before the cells
-    refused(library, entries(C.byref(good), payoff=9, n_steps=0)["oljd_price"], "n_steps must be >= 1")
+    refused(library, entries(C.byref(good), payoff=9, n_steps=0)["oljd_price"](), "n_steps must be >= 1")
     two = (C.c_int32 * 2)(n, n + 1)
-    refused(library, lambda: library.oljd_surface_prices(S, T, R, SIGMA, Q, 1, C.byref(good), strikes, two, 2, 0, 0, n, 1, 0, cells), "n_paths must be >= 1")
-    refused(library, entries(C.byref(good), k=17, count=0)["oljd_surface_prices"], "n_paths must be >= 1")
-    refused(library, entries(C.byref(good), n_steps=0, count=0)["oljd_paths"], "n_steps must be >= 1")
-    refused(library, entries(C.byref(good), count=0, n_steps=1 << 30)["oljd_paths"], "n_paths must be >= 1")
+    refused(library, library.oljd_surface_prices(S, T, R, SIGMA, Q, 1, C.byref(good), strikes, two, 2, 0, 0, n, 1, 0, cells), "n_paths must be >= 1")
+    refused(library, entries(C.byref(good), k=17, count=0)["oljd_surface_prices"](), "n_paths must be >= 1")
+    refused(library, entries(C.byref(good), n_steps=0, count=0)["oljd_paths"](), "n_steps must be >= 1")
+    refused(library, entries(C.byref(good), count=0, n_steps=1 << 30)["oljd_paths"](), "n_paths must be >= 1")
 
 
 def models():

@@ -12,7 +12,6 @@ import ctypes as C
 import inspect
 import json
 import os
-import re
 import shutil
 import subprocess
 
@@ -21,8 +20,8 @@ import pytest
 
 import optionslab_amd as ol
 from optionslab_amd import _hip
-from optionslab_amd.build import LIBRARY, build_library
 from tests import local_vol_oracle as lvo
+from tests.abi_support import assert_header_matches, library, refused
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "olmc_local_vol.h")
@@ -173,26 +172,8 @@ def test_oracle_payoffs_by_hand():
 
 
 # --------------------------------------------------------------------------------------------------------------- ABI ----
-def declared():
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(ollv_[a-z0-9_]+)\s*\(", text)))
-
-
-@pytest.fixture(scope="module")
-def library():
-    build_library()
-    return _hip.load_library()
-
-
 def test_header_exports_and_prototypes_agree(library):
-    out = subprocess.run(["nm", "-D", "--defined-only", LIBRARY], capture_output=True, text=True, check=True).stdout
-    exported = sorted(set(re.findall(r"\bT (ollv_[a-z0-9_]+)", out)))
-    assert declared() == exported == sorted(_hip.LV_PROTOTYPES) == ["ollv_paths", "ollv_price", "ollv_surface_prices"]
-    for name, (res, args) in _hip.LV_PROTOTYPES.items():
-        fn = getattr(library, name)
-        assert fn.restype is res and list(fn.argtypes) == list(args)
-    assert not set(_hip.LV_PROTOTYPES) & set(_hip.PROTOTYPES)
-    assert library.olmc_abi_version() == 6
+    assert_header_matches(library, HEADER, "ollv_", _hip.LV_PROTOTYPES, ["ollv_paths", "ollv_price", "ollv_surface_prices"])
 
 
 def test_header_is_c99_and_the_struct_is_forty_bytes(tmp_path):
@@ -231,7 +212,7 @@ BAD_SURFACES = [
 
 
 def entry_calls(library, s, *, payoff=8, barrier=0.0, offset=0, n=100, steps=4, k=2, out=True, cells=True, matrix=True):
-    """The three entry points on the surface pointer s, as (name, rc) thunks."""
+    """The three entry points on the surface pointer s, as thunks that give the return code."""
     st = _hip.Stats()
     sts = (_hip.Stats * 16)()
     strikes, cell_steps = (C.c_double * 16)(*([100.0] * 16)), (C.c_int32 * 16)(*([1] * 16))
@@ -244,16 +225,11 @@ def entry_calls(library, s, *, payoff=8, barrier=0.0, offset=0, n=100, steps=4, 
     }
 
 
-def refused(library, thunk, message):
-    rc = thunk()
-    assert rc == 1 and library.olmc_last_error().decode() == message, (rc, library.olmc_last_error())
-
-
 @pytest.mark.parametrize("entry", sorted(_hip.LV_PROTOTYPES))
 def test_every_refusal_answers_its_message_before_any_device_work(library, entry):
     """rc 1 (OLMC_ERR_ARG) and the exact words, on a machine with or without a device: none of these calls initialises one."""
     good, keep = surface()
-    call = lambda s=C.byref(good), **kw: entry_calls(library, s, **kw)[entry]
+    call = lambda s=C.byref(good), **kw: entry_calls(library, s, **kw)[entry]()
     refused(library, call(s=None), "null pointer")
     null_vol = _hip.LvSurface(None, 2, 2, -0.5, 0.5, 1.0)
     refused(library, call(s=C.byref(null_vol)), "null pointer")
@@ -280,7 +256,7 @@ def test_every_refusal_answers_its_message_before_any_device_work(library, entry
         refused(library, call(k=17), "the number of cells must be in [1, OLMC_MAX_BATCH]")
         sts = (_hip.Stats * 2)()
         strikes, steps = (C.c_double * 2)(100.0, 100.0), (C.c_int32 * 2)(1, 5)
-        refused(library, lambda: library.ollv_surface_prices(100.0, 1.0, 0.05, 0.0, 1, C.byref(good), strikes, steps, 2, 0, 100, 4, 7, 0, sts),
+        refused(library, library.ollv_surface_prices(100.0, 1.0, 0.05, 0.0, 1, C.byref(good), strikes, steps, 2, 0, 100, 4, 7, 0, sts),
                 "a cell's step must be in [1, n_steps]")
     if entry == "ollv_paths":
         refused(library, call(n=1 << 33, steps=1), "path matrix would exceed 64 GB")
@@ -289,7 +265,7 @@ def test_every_refusal_answers_its_message_before_any_device_work(library, entry
         refused(library, call(payoff=9, steps=0), "bad payoff")
         refused(library, call(payoff=0, barrier=0.0, n=0), "Barrier must be positive")
     if entry == "ollv_surface_prices":
-        refused(library, lambda: library.ollv_surface_prices(100.0, 1.0, 0.05, 0.0, 1, C.byref(good), strikes, steps, 2, 0, 0, 4, 7, 0, sts),
+        refused(library, library.ollv_surface_prices(100.0, 1.0, 0.05, 0.0, 1, C.byref(good), strikes, steps, 2, 0, 0, 4, 7, 0, sts),
                 "n_paths must be >= 1")
         refused(library, call(k=17, steps=0), "n_steps must be >= 1")
     if entry == "ollv_paths":

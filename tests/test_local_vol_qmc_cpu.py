@@ -13,7 +13,6 @@
 import ctypes as C
 import inspect
 import os
-import re
 import shutil
 import subprocess
 
@@ -22,11 +21,11 @@ import pytest
 
 import optionslab_amd as ol
 from optionslab_amd import _hip
-from optionslab_amd.build import LIBRARY, build_library
 from tests import local_vol_oracle as lvo
 from tests import sobol_reference as sr
 from tests import test_gpu_local_vol_qmc as g
-from tests.test_local_vol_cpu import BAD_SURFACES, refused, surface
+from tests.abi_support import assert_header_matches, library, refused
+from tests.test_local_vol_cpu import BAD_SURFACES, surface
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "olmc_local_vol_qmc.h")
@@ -35,24 +34,9 @@ NAMES = ["olvq_paths", "olvq_price", "olvq_surface_prices"]
 pytestmark = pytest.mark.filterwarnings("ignore:The balance properties of Sobol")
 
 
-@pytest.fixture(scope="module")
-def library():
-    build_library()
-    return _hip.load_library()
-
-
 # --------------------------------------------------------------------------------------------------------------- ABI ----
 def test_header_exports_and_prototypes_agree(library):
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    declared = sorted(set(re.findall(r"\b(olvq_[a-z0-9_]+)\s*\(", text)))
-    out = subprocess.run(["nm", "-D", "--defined-only", LIBRARY], capture_output=True, text=True, check=True).stdout
-    exported = sorted(set(re.findall(r"\bT (olvq_[a-z0-9_]+)", out)))
-    assert declared == exported == sorted(_hip.LVQ_PROTOTYPES) == NAMES
-    for name, (res, args) in _hip.LVQ_PROTOTYPES.items():
-        fn = getattr(library, name)
-        assert fn.restype is res and list(fn.argtypes) == list(args)
-    assert not set(_hip.LVQ_PROTOTYPES) & (set(_hip.PROTOTYPES) | set(_hip.LV_PROTOTYPES))
-    assert library.olmc_abi_version() == 6
+    assert_header_matches(library, HEADER, "olvq_", _hip.LVQ_PROTOTYPES, NAMES)
 
 
 def test_header_is_c99(tmp_path):
@@ -70,7 +54,7 @@ def test_header_is_c99(tmp_path):
 
 def entry_calls(library, s, *, payoff=8, barrier=0.0, construction=1, offset=0, n=100, steps=4, k=2, bits=30, out=True, cells=True, matrix=True,
                 sv=True, shift=True):
-    """The three entry points on the surface pointer s, as thunks."""
+    """The three entry points on the surface pointer s, as thunks that give the return code."""
     st = _hip.Stats()
     sts = (_hip.Stats * 16)()
     strikes, cell_steps = (C.c_double * 16)(*([100.0] * 16)), (C.c_int32 * 16)(*([1] * 16))
@@ -90,7 +74,7 @@ def entry_calls(library, s, *, payoff=8, barrier=0.0, construction=1, offset=0, 
 def test_every_refusal_answers_its_message_before_any_device_work(library, entry):
     """rc 1 (OLMC_ERR_ARG) and the exact words, on a machine with or without a device: none of these calls initialises one."""
     good, keep = surface()
-    call = lambda s=C.byref(good), **kw: entry_calls(library, s, **kw)[entry]
+    call = lambda s=C.byref(good), **kw: entry_calls(library, s, **kw)[entry]()
     # the table, the payoff, the cells and the matrix: ollv_*'s refusals
     refused(library, call(s=None), "null pointer")
     refused(library, call(s=C.byref(_hip.LvSurface(None, 2, 2, -0.5, 0.5, 1.0))), "null pointer")
@@ -126,7 +110,7 @@ def test_every_refusal_answers_its_message_before_any_device_work(library, entry
         sts = (_hip.Stats * 2)()
         tables = (C.c_uint32 * 64)()
         strikes, steps = (C.c_double * 2)(100.0, 100.0), (C.c_int32 * 2)(1, 5)
-        refused(library, lambda: library.olvq_surface_prices(100.0, 1.0, 0.05, 0.0, 1, C.byref(good), strikes, steps, 2, 1, 0, 100, 4, tables, tables, 30, 0,
+        refused(library, library.olvq_surface_prices(100.0, 1.0, 0.05, 0.0, 1, C.byref(good), strikes, steps, 2, 1, 0, 100, 4, tables, tables, 30, 0,
                                                              sts), "a cell's step must be in [1, n_steps]")
     if entry == "olvq_paths":
         refused(library, call(n=1 << 30, steps=8), "path matrix would exceed 64 GB")

@@ -1,7 +1,6 @@
 """method="qmc" on the autocallable and the cliquet without a device: every refusal comes before the device is touched, "qmc" reaches
 the Sobol bindings and "pseudo" the Philox ones with the arguments they always got, a missing GPU is loud, and the C entry points
 refuse bad arguments before any device work."""
-import ctypes as C
 import math
 import os
 
@@ -10,8 +9,8 @@ import pytest
 
 import optionslab_amd as ol
 from optionslab_amd import _hip
-from optionslab_amd.build import build_library
 from optionslab_amd.exceptions import AccelerationError
+from tests.abi_support import library, no_device, refused, sobol as _sobol, _ST
 
 S, K, T, R, SIG, Q = 100.0, 100.0, 1.0, 0.05, 0.2, 0.0
 _BINDINGS = ("lib", "autocallable", "cliquet", "autocallable_qmc", "cliquet_qmc")
@@ -19,16 +18,6 @@ _BINDINGS = ("lib", "autocallable", "cliquet", "autocallable_qmc", "cliquet_qmc"
 
 def _options():
     return [ol.AutocallableOption(S, K, T, R, SIG, seed=3), ol.CliquetOption(S, K, T, R, SIG, seed=3)]
-
-
-@pytest.fixture
-def no_device(monkeypatch):
-    """Any attempt to reach the library (hence the device) fails the test."""
-    def touched(*a, **k):
-        raise AssertionError("the device was touched")
-
-    for name in _BINDINGS:
-        monkeypatch.setattr(_hip, name, touched, raising=False)
 
 
 @pytest.mark.parametrize("kwargs,match", [
@@ -125,20 +114,6 @@ def test_the_abi_declares_the_structured_qmc_entry_points():
 
 
 # ------------------------------------------------------------------------------------------------- the C entry points ----
-@pytest.fixture(scope="module")
-def library():
-    build_library()
-    return _hip.load_library()
-
-
-def _ST():
-    return C.byref(_hip.Stats())
-
-
-def _sobol(dims):
-    return (C.c_uint32 * (30 * dims))(*range(1, 30 * dims + 1)), (C.c_uint32 * dims)()
-
-
 _MKT = (100.0, 1.0, 0.05, 0.2, 0.0)                               # S T r sigma q
 _AUTO = (*_MKT, 1.0, 0.8, 0.10, 0.6)                              # + autocall, coupon level, coupon rate, knock-in
 _CLIQ = (*_MKT, 0.05, -0.05, 0.30, 0.0)                           # + local cap, local floor, global cap, global floor
@@ -174,9 +149,7 @@ _REFUSALS = [
 @pytest.mark.parametrize("name,args,message", _REFUSALS, ids=[f"{n}-{i}" for i, (n, _a, _m) in enumerate(_REFUSALS)])
 def test_entry_points_refuse_bad_arguments_before_touching_a_device(library, name, args, message):
     """Each refusal answers OLMC_ERR_ARG (1) with its exact message, ahead of any device work (no device is initialised here)."""
-    rc = getattr(library, name)(*args())
-    assert rc == 1
-    assert library.olmc_last_error().decode() == message
+    refused(library, getattr(library, name)(*args()), message)
 
 
 def test_the_refactored_philox_entry_points_still_refuse_as_before(library):
@@ -185,5 +158,4 @@ def test_the_refactored_philox_entry_points_still_refuse_as_before(library):
         ("olmc_autocallable", (*_AUTO, 9, 0, 64, 8, 1, 0, _ST()), "no observation date: observation_freq > n_steps"),
         ("olmc_cliquet", (*_CLIQ, 9, 0, 64, 8, 1, 0, _ST()), "n_periods must be in [1, n_steps]"),
     ]:
-        assert getattr(library, name)(*args) == 1
-        assert library.olmc_last_error().decode() == message
+        refused(library, getattr(library, name)(*args), message)
