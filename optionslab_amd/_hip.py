@@ -62,6 +62,12 @@ class JdModel(C.Structure):
     _fields_ = [("model", C.c_int32), ("pad", C.c_int32), ("lambda_j", C.c_double), ("a1", C.c_double), ("a2", C.c_double), ("a3", C.c_double)]
 
 
+class JsScenario(C.Structure):
+    """oljs_scenario (include/olmc_jump_scenarios.h): a contract and its jump model, (a1, a2, a3) as JdModel's."""
+    _fields_ = [("S", C.c_double), ("K", C.c_double), ("T", C.c_double), ("r", C.c_double), ("sigma", C.c_double), ("q", C.c_double),
+                ("is_call", C.c_int32), ("model", C.c_int32), ("lambda_j", C.c_double), ("a1", C.c_double), ("a2", C.c_double), ("a3", C.c_double)]
+
+
 _D, _I, _I32, _I64, _U64T, _P = C.c_double, C.c_int, C.c_int32, C.c_int64, C.c_uint64, C.c_void_p
 _DP, _U32P, _I32P = C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_int32)
 _STATS, _CV, _OPTIONS, _SCENARIOS = C.POINTER(Stats), C.POINTER(CvMoments), C.POINTER(Option), C.POINTER(HestonScenario)
@@ -186,6 +192,14 @@ JD_PROTOTYPES = {
     "oljd_paths": (_I, [_D] * 5 + [_JDM, _I64, _I32, _U64T, _I, _I, _DP]),
 }
 
+# and for include/olmc_jump_scenarios.h (prefix oljs_)
+_JSS = C.POINTER(JsScenario)
+JS_PROTOTYPES = {
+    "oljs_layout": (_I, [_JSS, _I32, _I32P, _I32P]),
+    "oljs_scenarios": (_I, [_JSS, _I32] + _RANGE),
+    "oljs_greeks_fd": (_I, _SIX + [_I, _JDM, _I64, _I32, _U64T, _I, _I] + _GREEKS),
+}
+
 _lock = threading.Lock()
 _lib: Optional[C.CDLL] = None
 _initialised = False
@@ -229,7 +243,7 @@ def load_library() -> C.CDLL:
             except OSError as e:
                 raise AccelerationError(f"cannot load {LIBRARY_PATH}: {e}", backend="hip") from e
             for name, (res, args) in (list(PROTOTYPES.items()) + list(LV_PROTOTYPES.items()) + list(LVQ_PROTOTYPES.items())
-                                      + list(JD_PROTOTYPES.items())):
+                                      + list(JD_PROTOTYPES.items()) + list(JS_PROTOTYPES.items())):
                 try:
                     fn = getattr(lib, name)
                 except AttributeError:
@@ -887,6 +901,41 @@ def jd_paths(S, T, r, sigma, q, model, n_paths: int, n_steps: int, seed: int, mi
     out = _path_matrix(n_paths, n_steps, path_major)
     _check(lib().oljd_paths(S, T, r, sigma, q, _byref(m), int(n_paths), int(n_steps), seed64(seed), int(bool(mirror)), int(path_major), _dp(out)))
     return out
+
+
+def _jd_scenarios(scenarios):
+    """(S, K, T, r, sigma, q, is_call, kou, lambda_j, a1, a2, a3) tuples as the C array."""
+    k = len(scenarios)
+    return (JsScenario * max(k, 1))(*[JsScenario(S, K, T, r, sigma, q, int(bool(c)), int(bool(kou)), lam, a1, a2, a3)
+                                      for (S, K, T, r, sigma, q, c, kou, lam, a1, a2, a3) in scenarios]), k
+
+
+def jd_scenario_layout(scenarios) -> Tuple[int, List[int]]:
+    """(n_groups, group[k]) of a list of scenarios (S, K, T, r, sigma, q, is_call, kou, lambda_j, a1, a2, a3): two share a jump group
+    exactly when their (kou, lambda_j, T, a1, a2, a3) are equal as doubles (Merton's unread a3 apart), numbered by first appearance
+    (oljs_layout; pure host function: loads the library, not the GPU)."""
+    arr, k = _jd_scenarios(scenarios)
+    n_groups, group = C.c_int32(0), (C.c_int32 * max(k, 1))()
+    _check(load_library().oljs_layout(arr, k, C.byref(n_groups), group))
+    return n_groups.value, list(group)[:k]
+
+
+def jd_scenarios(scenarios, n_paths: int, n_steps: int, seed: int, antithetic: bool = False, path_offset: int = 0) -> List[Stats]:
+    """European options under k <= 16 scenarios (S, K, T, r, sigma, q, is_call, kou, lambda_j, a1, a2, a3) on ONE walk over
+    jump_diffusion()'s draws, one launch (oljs_scenarios); the answers come in the caller's order."""
+    arr, k = _jd_scenarios(scenarios)
+    out = (Stats * max(k, 1))()
+    _check(lib().oljs_scenarios(arr, k, int(path_offset), int(n_paths), int(n_steps), seed64(seed), int(antithetic), out))
+    return list(out)[:k]
+
+
+def jd_greeks_fd(S, K, T, r, sigma, q, is_call: bool, model, n_paths: int, n_steps: int, seed: int, antithetic: bool, second_order: bool,
+                 want_evals: bool = True) -> Tuple[List[float], List[Stats]]:
+    """As european_greeks_fd under the jump model (kou, lambda_j, a1, a2, a3): the 7 / 8 / 11 / 14 bumped contracts as ONE scenario launch
+    of two jump groups (oljs_greeks_fd)."""
+    m = jd_model(*model)
+    return _greeks(want_evals, lib().oljs_greeks_fd, S, K, T, r, sigma, q, int(is_call), _byref(m), int(n_paths), int(n_steps), seed64(seed),
+                   int(antithetic), int(second_order))
 
 
 def _scenarios(scenarios):

@@ -13,6 +13,7 @@
 #include "olmc_local_vol_kernels.h"
 #include "olmc_local_vol_qmc_kernels.h"
 #include "olmc_jump_kernels.h"
+#include "olmc_jump_scenario_kernels.h"
 #include "olmc_job_board.h"
 #include "olmc_device_mem.h"
 
@@ -3349,6 +3350,98 @@ extern "C" int oljd_paths(double S, double T, double r, double sigma, double q, 
             launch_timed(jump_legs_paths_kernel<pm>, dim3(grid), dim3(kBlock), c->stream, nullptr, pr, jc, S, static_cast<int32_t>(mirror != 0), d_paths);
         });
     });
+}
+
+// ====================================================== jump-diffusion scenario sets and fused Greeks ====
+// include/olmc_jump_scenarios.h: k scenarios on one walk over olmc_jump_paths' draws.  The grouping and the kernel's argument are host
+// arithmetic (olmc_host_math.h: jump_scenario_set), the launch is the Heston scenario sets' -- the same range, grid and rows, one launch
+// of jump_scenarios_kernel at the smallest instantiated group bound that holds the launch's groups.
+namespace {
+static_assert(sizeof(JumpScenarioSet) <= 2048, "the scenario set travels by value in the kernel arguments");
+constexpr int kJumpGroupBounds[] = {2, 4, 16};
+
+// The checks of a scenario list that need no device, in the order olmc_jump_scenarios.h lists them: the model's are make_jump's.
+int jump_scenario_check(const oljs_scenario* sc, int32_t k, int32_t n_steps, const olmc_stats* out) {
+    if (!sc || !out) return fail(OLMC_ERR_ARG, "null pointer");
+    if (k < 1 || k > OLMC_MAX_BATCH) return fail(OLMC_ERR_ARG, "the number of scenarios must be in [1, OLMC_MAX_BATCH]");
+    if (n_steps < 1) return fail(OLMC_ERR_ARG, "n_steps must be >= 1");
+    for (int32_t i = 0; i < k; ++i) {
+        const oljs_scenario& s = sc[i];
+        if (s.T <= 0.0) return fail(OLMC_ERR_ARG, "T must be > 0 in every scenario");
+        JumpContract unused;      // a NaN intensity is a NaN input, not a negative one (jd_contract)
+        const int rc = make_jump(s.S, s.K, s.T, s.r, s.sigma, s.q, s.is_call, s.model, std::isnan(s.lambda_j) ? 0.0 : s.lambda_j, s.a1, s.a2, s.a3,
+                                 n_steps, &unused);
+        if (rc) return rc;
+    }
+    return OLMC_OK;
+}
+
+template <int B = 0>
+void launch_jump_scenarios(int32_t n_groups, bool anti, int32_t grid, hipStream_t st, const EventPair* timed, const JumpScenarioSet& set,
+                           const PathRange& pr, const ReduceWs& ws) {
+    constexpr int bound = kJumpGroupBounds[B];
+    if constexpr (B + 1 < static_cast<int>(sizeof kJumpGroupBounds / sizeof *kJumpGroupBounds)) {
+        if (n_groups > bound) return launch_jump_scenarios<B + 1>(n_groups, anti, grid, st, timed, set, pr, ws);
+    }
+    with_bool(anti, [&](auto a) { launch_timed(jump_scenarios_kernel<bound, decltype(a)::value>, dim3(grid), dim3(kBlock), st, timed, set, pr, ws); });
+}
+
+int run_jump_scenarios(const oljs_scenario* sc, int32_t k, int64_t path_offset, int64_t n_local, int32_t n_steps, uint64_t seed, int antithetic,
+                       olmc_stats* out) {
+    int rc = jump_scenario_check(sc, k, n_steps, out);
+    if (rc) return rc;
+    rc = check_paths(path_offset, n_local, n_steps);
+    if (rc) return rc;
+    JumpScenarioSet set;
+    int32_t slot_of[OLMC_MAX_BATCH];
+    if (const char* bad = jump_scenario_set(sc, k, n_steps, &set, slot_of)) return fail(OLMC_ERR_ARG, bad);
+    CtxLease lease;
+    rc = ctx_lease(&lease);
+    if (rc) return rc;
+    DeviceCtx* const c = lease.c;
+    const PathRange pr = make_range(path_offset, n_local, n_steps, seed);
+    rc = launch_reduce(c, c->stream, c->d_result, -1.0, 2 * kSurfaceCells, grid_for(n_local),
+                       [&](int32_t grid, hipStream_t st, const EventPair* timed, const ReduceWs& ws) {
+                           launch_jump_scenarios(set.n_groups, antithetic != 0, grid, st, timed, set, pr, ws);
+                       });
+    if (rc) return rc;
+    const int64_t n = n_local * (antithetic ? 2 : 1);
+    for (int32_t i = 0; i < k; ++i) {
+        const int32_t j = slot_of[i];
+        if (jump_scenario_poisoned(sc[i])) nan_stats(n, &out[i]);
+        else finish_stats(c->h_result[2 * j], c->h_result[2 * j + 1], n, sc[i].r, sc[i].T, &out[i]);
+    }
+    return OLMC_OK;
+}
+}  // namespace
+
+// The grouping of a scenario list (pure host arithmetic: needs no device).
+extern "C" int oljs_layout(const oljs_scenario* sc, int32_t k, int32_t* n_groups, int32_t* group) {
+    if (!sc || !n_groups || !group) return fail(OLMC_ERR_ARG, "null pointer");
+    if (const char* bad = jump_scenario_groups(sc, k, n_groups, group)) return fail(OLMC_ERR_ARG, bad);
+    return OLMC_OK;
+}
+
+extern "C" int oljs_scenarios(const oljs_scenario* sc, int32_t k, int64_t path_offset, int64_t n_local, int32_t n_steps, uint64_t seed,
+                              int antithetic, olmc_stats* out) {
+    return run_jump_scenarios(sc, k, path_offset, n_local, n_steps, seed, antithetic, out);
+}
+
+// The 7 / 8 / 11 / 14 contracts of compute_greeks_unified under the model as ONE scenario launch: GreeksSet as it stands (bumps, call
+// order, finish), two jump groups (T and T - h_T).
+extern "C" int oljs_greeks_fd(double S, double K, double T, double r, double sigma, double q, int is_call, const oljd_model* model,
+                              int64_t n_paths, int32_t n_steps, uint64_t seed, int antithetic, int second_order, double* out9,
+                              olmc_stats* evals) {
+    if (!out9 || !model) return fail(OLMC_ERR_ARG, "null pointer");
+    if (!(T > 0.0)) return fail(OLMC_ERR_ARG, "T must be > 0");
+    const GreeksSet gs(S, K, T, r, sigma, q, is_call, second_order);
+    oljs_scenario sc[OLMC_MAX_BATCH];
+    jump_greeks_scenarios(gs, *model, sc);
+    olmc_stats st[OLMC_MAX_BATCH];
+    const int rc = run_jump_scenarios(sc, gs.k, 0, n_paths, n_steps, seed, antithetic, st);
+    if (rc) return rc;
+    gs.finish(st, T, out9, evals);
+    return OLMC_OK;
 }
 
 namespace {

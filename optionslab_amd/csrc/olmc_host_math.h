@@ -15,6 +15,7 @@
 #define OLMC_HOST_MATH_H
 
 #include "olmc.h"
+#include "olmc_jump_scenarios.h"
 
 #include <algorithm>
 #include <cmath>
@@ -552,6 +553,112 @@ inline void heston_greeks_scenarios(const GreeksSet& gs, double kappa, double th
     for (int i = 0; i < gs.k; ++i) {
         const olmc_option& o = gs.o[i];
         sc[i] = olmc_heston_scenario{o.S, o.K, o.T, o.r, o.q, kappa, theta, sigma_v, rho, o.sigma * o.sigma, o.is_call, 0};
+    }
+}
+
+// ------------------------------------------------------ jump-diffusion scenario sets ----
+// k <= 16 European contracts under k parameter sets on ONE walk over olmc_jump_paths' draws (olmc_jump_scenarios.h;
+// jump_scenarios_kernel).  A lane carries Z = the sum of the path's raw normals and one jump sum J per JUMP GROUP -- the scenarios whose
+// (model, lambda_j, T, a1, a2, a3) are equal as doubles -- and a contract enters after the step loop through (ln S, vol, n drift, K,
+// sign): x = fma(vol, +-Z, n drift) + J.  A launch of k scenarios has at most k groups.
+constexpr int kJumpGroups = OLMC_MAX_BATCH;
+
+struct JumpScenarioSet {
+    // group g: what jump_sizes reads of make_jump's contract, formed by the same products; unused groups are zeros, never read
+    double grp[kJumpGroups][6];                         // p0, lambda dt, then Merton (mu_j, sigma_j, 0) | Kou (p, 1 / eta1, 1 / eta2), 0
+    // kernel slot j: the contracts sorted by group, then by (ln S, vol, n drift) (first appearance); slots [end[g - 1], end[g]) read group g
+    double slot[OLMC_MAX_BATCH][6];                     // ln S, vol (in raw normals), n drift, strike, sign, 0
+    int32_t end[kJumpGroups];
+    int32_t fresh[OLMC_MAX_BATCH];                      // 1: the slot forms its own spot; 0: it reads the spot of the slot before it
+    int32_t kou_mask;                                   // bit g: group g is Kou's
+    int32_t n_groups;
+    double p0_floor;                                    // the smallest p0 of the groups in use (0 if one is NaN): below it no group jumps
+};
+enum { kJsP0, kJsLamDt, kJsC1, kJsC2, kJsC3 };                                                // JumpScenarioSet::grp[g][.]
+enum { kJsLogS, kJsVol, kJsNDrift, kJsStrike, kJsSign };                                      // JumpScenarioSet::slot[j][.]
+
+inline bool same_jump_group(const oljs_scenario& x, const oljs_scenario& y) {
+    return x.model == y.model && same_bits(x.lambda_j, y.lambda_j) && same_bits(x.T, y.T) && same_bits(x.a1, y.a1) && same_bits(x.a2, y.a2)
+        && (x.model == OLMC_JUMP_MERTON || same_bits(x.a3, y.a3));            // Merton does not read a3
+}
+
+// group[i] = the jump group of scenario i, numbered by first appearance.  Returns nullptr, or what is wrong.
+inline const char* jump_scenario_groups(const oljs_scenario* sc, int32_t k, int32_t* n_groups, int32_t* group) {
+    if (k < 1 || k > OLMC_MAX_BATCH) return "the number of scenarios must be in [1, OLMC_MAX_BATCH]";
+    int32_t first[kJumpGroups], n = 0;
+    for (int32_t i = 0; i < k; ++i) {
+        int32_t g = 0;
+        while (g < n && !same_jump_group(sc[first[g]], sc[i])) ++g;
+        if (g == n) first[n++] = i;
+        group[i] = g;
+    }
+    *n_groups = n;
+    return nullptr;
+}
+
+// What a scenario answers NaN for: olmc_jump_diffusion's rule (poisoned(), and a NaN in the model, Merton's unread a3 included).
+inline bool jump_scenario_poisoned(const oljs_scenario& s) {
+    return poisoned(s.S, s.K, s.T, s.r, s.sigma, s.q) || std::isnan(s.lambda_j + s.a1 + s.a2 + s.a3);
+}
+
+// E[e^Y - 1] of a jump size Y (jump_diffusion.py:64-67 Merton, :293-299 Kou), as make_jump (olmc.hip) forms it.
+inline double jump_kappa(int model, double a1, double a2, double a3) {
+    return model == OLMC_JUMP_MERTON ? std::exp(a1 + 0.5 * a2 * a2) - 1 : a1 * a2 / (a2 - 1) + (1 - a1) * a3 / (a3 + 1) - 1;
+}
+
+// The kernel's argument for k scenarios on n_steps >= 1 steps; slot_of[i] = the kernel slot of scenario i.  Every constant by the
+// products make_jump (olmc.hip) and the one-contract kernels (vol * kZScale) form, so a term here has their bits.
+inline const char* jump_scenario_set(const oljs_scenario* sc, int32_t k, int32_t n_steps, JumpScenarioSet* set, int32_t* slot_of) {
+    std::memset(set, 0, sizeof *set);
+    int32_t group[OLMC_MAX_BATCH], spot_of[OLMC_MAX_BATCH], order[OLMC_MAX_BATCH];
+    double log_s[OLMC_MAX_BATCH], vol[OLMC_MAX_BATCH], n_drift[OLMC_MAX_BATCH];
+    if (const char* bad = jump_scenario_groups(sc, k, &set->n_groups, group)) return bad;
+    set->p0_floor = 1.0;
+    for (int32_t i = 0; i < k; ++i) {
+        const oljs_scenario& s = sc[i];
+        const double dt = s.T / n_steps;
+        const int32_t g = group[i];
+        const bool kou = s.model != OLMC_JUMP_MERTON;
+        double* const cst = set->grp[g];
+        cst[kJsLamDt] = s.lambda_j * dt;
+        cst[kJsP0] = std::exp(-cst[kJsLamDt]);
+        cst[kJsC1] = s.a1;
+        cst[kJsC2] = kou ? 1.0 / s.a2 : s.a2;
+        cst[kJsC3] = kou ? 1.0 / s.a3 : 0.0;
+        if (kou) set->kou_mask |= 1 << g;
+        set->p0_floor = cst[kJsP0] < set->p0_floor ? cst[kJsP0] : (std::isnan(cst[kJsP0]) ? 0.0 : set->p0_floor);
+        const double drift = (s.r - s.q - s.lambda_j * jump_kappa(s.model, s.a1, s.a2, s.a3) - 0.5 * s.sigma * s.sigma) * dt;
+        log_s[i] = std::log(s.S);
+        vol[i] = s.sigma * std::sqrt(dt) * kZScale;
+        n_drift[i] = static_cast<double>(n_steps) * drift;
+        spot_of[i] = i;                                  // the first scenario with this group and these (ln S, vol, n drift)
+        for (int32_t j = 0; j < i; ++j)
+            if (group[j] == g && same_bits(log_s[j], log_s[i]) && same_bits(vol[j], vol[i]) && same_bits(n_drift[j], n_drift[i])) { spot_of[i] = spot_of[j]; break; }
+        order[i] = i;
+    }
+    std::stable_sort(order, order + k, [&](int32_t x, int32_t y) {
+        return group[x] != group[y] ? group[x] < group[y] : spot_of[x] < spot_of[y];
+    });
+    for (int32_t j = 0; j < k; ++j) {
+        const int32_t i = order[j];
+        set->slot[j][kJsLogS] = log_s[i];
+        set->slot[j][kJsVol] = vol[i];
+        set->slot[j][kJsNDrift] = n_drift[i];
+        set->slot[j][kJsStrike] = sc[i].K;
+        set->slot[j][kJsSign] = sc[i].is_call ? 1.0 : -1.0;
+        set->fresh[j] = j == 0 || group[order[j - 1]] != group[i] || spot_of[order[j - 1]] != spot_of[i];
+        set->end[group[i]] = j + 1;
+        slot_of[i] = j;
+    }
+    for (int32_t g = set->n_groups; g < kJumpGroups; ++g) set->end[g] = k;
+    return nullptr;
+}
+
+// The scenarios of a GreeksSet under the model.
+inline void jump_greeks_scenarios(const GreeksSet& gs, const oljd_model& m, oljs_scenario* sc) {
+    for (int i = 0; i < gs.k; ++i) {
+        const olmc_option& o = gs.o[i];
+        sc[i] = oljs_scenario{o.S, o.K, o.T, o.r, o.sigma, o.q, o.is_call, m.model, m.lambda_j, m.a1, m.a2, m.a3};
     }
 }
 

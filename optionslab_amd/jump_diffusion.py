@@ -5,18 +5,21 @@ src/pricing_models/jump_diffusion.py:38-372).
 uniform, jump draws).  `MertonJumpDiffusion.price` is the reference's Poisson-weighted
 Black-Scholes series (:69-132) -- scalar host arithmetic, the accuracy anchor of the MC.
 Additive: Asians, barriers, lookbacks, a strike x maturity surface, the autocallable and the
-cliquet on the same paths, one launch each (include/olmc_jump.h; `_JumpPathPayoffs`).
+cliquet on the same paths, one launch each (include/olmc_jump.h; `_JumpPathPayoffs`); what-if scenario sets and the fused
+finite-difference Greeks of the Monte Carlo price (include/olmc_jump_scenarios.h; `price_scenarios`, `JumpMCAdapter`).
 """
 from __future__ import annotations
 
+import dataclasses
 import math
+from collections import OrderedDict
 from dataclasses import dataclass
 from typing import Literal, Optional
 
 import numpy as np
 
 from . import _hip
-from ._paths import _asian_payoff, _barrier_kind, _check_barrier, _check_sizes, _fill_surface, _lookback_payoff, _result, _seed, _strike_list, _surface_steps
+from ._paths import _SURFACE_CELLS, _asian_payoff, _barrier_kind, _check_barrier, _check_sizes, _fill_surface, _lookback_payoff, _result, _seed, _strike_list, _surface_steps
 from .black_scholes import _ncdf
 
 
@@ -131,6 +134,54 @@ class _JumpPathPayoffs:
                              _seed(seed), antithetic)
         return _result(st, return_error)
 
+    def _scenario_tuples(self, scenarios):
+        """price_scenarios' mappings as _hip's tuples (S, K, T, r, sigma, q, is_call, kou, lambda_j, a1, a2, a3), checked."""
+        scenarios = list(scenarios)
+        if not scenarios:
+            raise ValueError("scenarios must not be empty")
+        own = [f.name for f in dataclasses.fields(self)]
+        out = []
+        for i, sc in enumerate(scenarios):
+            missing = [key for key in ("S", "K", "T", "r", "sigma") if key not in sc]
+            if missing:
+                raise ValueError(f"scenario {i} lacks {missing}")
+            unknown = sorted(set(sc) - {"S", "K", "T", "r", "sigma", "q", "option_type", *own})
+            if unknown:
+                raise ValueError(f"scenario {i} has unknown keys {unknown}")
+            T = float(sc["T"])
+            if T <= 0.0:
+                raise ValueError(f"scenario {i}: T must be > 0")
+            try:
+                model = dataclasses.replace(self, **{key: float(sc[key]) for key in own if key in sc})      # __post_init__'s checks
+            except ValueError as e:
+                raise ValueError(f"scenario {i}: {e}") from None
+            out.append((float(sc["S"]), float(sc["K"]), T, float(sc["r"]), float(sc["sigma"]), float(sc.get("q", 0.0)),
+                        sc.get("option_type", "call") == "call", *model._jd()))
+        return out
+
+    def price_scenarios(self, scenarios, n_paths: int = 100000, n_steps: int = 252, seed: Optional[int] = None, antithetic: bool = False,
+                        return_error: bool = False):
+        """European prices under a list of what-if scenarios on COMMON random numbers: a float64 array (len(scenarios),), with
+        return_error (prices, std_errors).  A scenario is a mapping with the keys S, K, T, r, sigma and optionally q (0), option_type
+        ("call"; anything else prices as a put) and the model's own fields (this instance's where absent): spot, strike, maturity,
+        rates, volatility and the jump law may all differ.  Scenario i is price_monte_carlo(S, K, T, r, sigma, option_type, q, n_paths,
+        n_steps, seed, antithetic=antithetic) of a model with its fields -- the same draws, the sums to rounding -- but the scenarios
+        of a launch share ONE walk over the Philox blocks: the diffusion enters through one sum of normals per path, and scenarios
+        whose (lambda_j, T and jump-size parameters) are equal as doubles share a jump sum, the others take one of their own on the
+        same Poisson uniforms and size draws.  The list is cut in the caller's order into launches of at most 16 scenarios; a
+        scenario's bits depend neither on the cut nor on its neighbours nor on its place.  seed=None draws ONE seed for all launches.
+        Refused (ValueError, before the device is touched): bad counts, an empty list, a scenario without S, K, T, r or sigma, with an
+        unknown key, with T <= 0, or with model fields the model's own constructor refuses."""
+        _check_sizes(n_paths, n_steps)
+        tuples = self._scenario_tuples(scenarios)
+        s = _seed(seed)
+        prices = np.empty(len(tuples), dtype=np.float64)
+        errors = np.empty_like(prices)
+        for a in range(0, len(tuples), _SURFACE_CELLS):
+            for i, st in enumerate(_hip.jd_scenarios(tuples[a:a + _SURFACE_CELLS], n_paths, n_steps, s, antithetic), a):
+                prices[i], errors[i] = st.price, st.std_error
+        return (prices, errors) if return_error else prices
+
 
 @dataclass
 class MertonJumpDiffusion(_JumpPathPayoffs):
@@ -215,3 +266,39 @@ class JumpDiffusionAdapter:
 
     def price(self, S, K, T, r, sigma, option_type, q=0.0, **kwargs) -> float:
         return self.jd.price(S, K, T, r, sigma, option_type, q)
+
+
+class JumpMCAdapter:
+    """PricerProtocol over a jump-diffusion model's device Monte Carlo price: ``price`` is the model's price_monte_carlo at the adapter's
+    n_paths, n_steps, seed and antithetic, so compute_greeks_unified(adapter, ...) differentiates the price price_monte_carlo gives --
+    for Kou as for Merton, where JumpDiffusionAdapter differentiates Merton's series.  seed=None draws one seed at construction: every
+    bump sees the same random numbers.  The adapter carries _fused_greeks, so compute_greeks_unified prices the 7 / 8 / 11 / 14 bumped
+    contracts as ONE scenario launch of two jump groups (oljs_greeks_fd); fused=False goes the one launch per evaluation way and gives
+    the same numbers to rounding.  Refused (ValueError, before the device is touched): bad counts."""
+
+    def __init__(self, model, n_paths: int = 100000, n_steps: int = 252, seed: Optional[int] = None, antithetic: bool = False):
+        _check_sizes(n_paths, n_steps)
+        self.jd = model
+        self.n_paths, self.n_steps, self.antithetic = int(n_paths), int(n_steps), bool(antithetic)
+        self.seed = int(_seed(seed))
+
+    def price(self, S, K, T, r, sigma, option_type, q=0.0, **kwargs) -> float:
+        return self.jd.price_monte_carlo(S, K, T, r, sigma, option_type, q, self.n_paths, self.n_steps, self.seed, antithetic=self.antithetic, **kwargs)
+
+    def _can_fuse(self, pricer_kwargs) -> bool:
+        return not pricer_kwargs
+
+    def _fused_greeks(self, S, K, T, r, sigma, option_type, q, include_second_order, seed=None):
+        vals, _ = _hip.jd_greeks_fd(S, K, T, r, sigma, q, option_type == "call", self.jd._jd(), self.n_paths, self.n_steps, self.seed,
+                                    self.antithetic, include_second_order, want_evals=False)
+        keys = ("price", "delta", "gamma", "vega", "theta", "rho", "vanna", "charm", "vomma")
+        return OrderedDict((k, np.float64(v)) for k, v in zip(keys if include_second_order else keys[:6], vals))
+
+
+def greeks_jump_monte_carlo(model, S: float, K: float, T: float, r: float, sigma: float, option_type: str = "call", q: float = 0.0,
+                            include_second_order: bool = True, **adapter_kwargs):
+    """compute_greeks_unified over JumpMCAdapter(model, **adapter_kwargs): the finite-difference Greeks of the Monte Carlo price in one
+    launch."""
+    from .greeks import compute_greeks_unified
+
+    return compute_greeks_unified(JumpMCAdapter(model, **adapter_kwargs), S, K, T, r, sigma, option_type, q, include_second_order)
