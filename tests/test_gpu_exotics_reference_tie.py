@@ -10,7 +10,9 @@ convention that is off moves these by far more than the tolerances, which follow
          exponential's last bits and the order of the final sums differ;
   REL    fp32 partial sums of the normals or of the log-prices (geometric and fast arithmetic Asian, cliquet): the checker's 2e-6.
 The reference has no antithetic mirror: for antithetic=True the mirrored leg is rebuilt on the host from the device paths'
-log-increments as 2 drift - increment, and the two legs are tied together."""
+log-increments as 2 drift - increment, and the two legs are tied together.
+The device's own matrix is itself pinned in tests/test_gpu_path_matrices_exact.py: to a long-double recursion on the stream's draws,
+within (t + 8) M 2^-52 on ln S."""
 import math
 
 import numpy as np

@@ -6,6 +6,8 @@ and at sigma = 0: their difference isolates the jump sums), and the antithetic s
 sums against per-path payoffs, rel 1e-12 for shards, 3.5 standard errors against a closed form and 4 combined standard errors between
 two Monte Carlo prices.  Every tie first asserts that no path comes within 1e-9 (relative) of a level it could cross: the kernels
 decide in log space, the matrix route after an exponential.
+The device's own matrix (olmc_jump_paths, and oljd_paths with both legs) is pinned in tests/test_gpu_path_matrices_exact.py: to a
+long-double recursion on the stream's draws, the jump counts to SciPy's Poisson quantile.
 """
 import functools
 import hashlib

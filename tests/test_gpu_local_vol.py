@@ -21,6 +21,9 @@ Sizes: N in {100, 257, 4133} paths (less than a workgroup, one thread past a wor
   8  S = NaN gives a NaN price, and the next call is right.
 
 Every tie prints its worst deviation as a `DEVIATION {json}` line.
+
+The device's own GBM matrix, which 1 compares with and whose normals 2 recovers (an error of its fp64 part would go into them unseen),
+is pinned in tests/test_gpu_path_matrices_exact.py to a long-double recursion on the stream's draws.
 """
 import contextlib
 import json
