@@ -20,6 +20,10 @@ The mapping of words to steps is the kernels' comments (olmc_kernels.h):
           Merton's size normal of step t is cos(x0, x1) of block t, tag 3; Kou's jump j of step t takes (u_d, u_m) from words 2 (j % 2),
           2 (j % 2) + 1 of block t, tag 3 + j // 2.
 
+These matrices add every normal in fp64.  The kernels that first sum a path's normals in fp32 chains (the European family, the cliquet's
+period sums, the geometric Asian's prefix sums) are pinned in tests/normal_sum_oracle.py, which replays those chains bit for bit on the
+same words and the same tap.
+
 The cases of tests/test_gpu_path_matrices_exact.py are fixed here, so that tests/test_path_draw_oracle_cpu.py can hold the conditions
 on their Poisson uniforms (no uniform within 1e-12 of a step of the CDF, no count at the cap of 64) without a device.
 """

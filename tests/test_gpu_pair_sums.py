@@ -4,7 +4,11 @@ european_path_kernel sums a path's normals in pair-sum units (olmc_kernels.h, "P
 in the partial block a first pair the same way and an odd leftover normal times 1 / sqrt(2), and the path's sum scaled by
 2 sqrt(ln 2).  olmc_normals still returns every normal on its own (rad * cos, rad * sin).  Rebuilding the terminal prices in fp64
 from those normals on the same seed checks the bookkeeping of every n_steps % 4 and of an odd leftover: a unit that is off by
-sqrt(2) on one normal moves a price by ~1e-2 relative, far above what fp32 rounding and the hardware sine leave (~1e-7)."""
+sqrt(2) on one normal moves a price by ~1e-2 relative, far above what fp32 rounding and the hardware sine leave (~1e-7).
+
+This is the bookkeeping only: REL lets through anything a hundred times the chain's rounding.  The chain itself -- every fma, the
+association of the groups and quarters, the constants -- is pinned bit for bit by tests/normal_sum_oracle.py, against which
+tests/test_gpu_normal_sums_exact.py holds the same kernels at fp64's own scale."""
 import math
 
 import numpy as np
