@@ -200,6 +200,14 @@ JS_PROTOTYPES = {
     "oljs_greeks_fd": (_I, _SIX + [_I, _JDM, _I64, _I32, _U64T, _I, _I] + _GREEKS),
 }
 
+# and for include/olha.h (prefix olha_)
+HA_BASIS_SPOT_VARIANCE, HA_BASIS_SPOT = 0, 1
+HA_PROTOTYPES = {
+    "olha_american_lsm": (_I, [_D] * 5 + [_I] + _HESTON + [_I, _I, _I32, _I64, _I32, _U64T, _STATS]),
+    "olha_american_lsm_qmc": (_I, [_D] * 5 + [_I] + _HESTON + [_I, _I, _I32, _I, _I64, _U32P, _U32P, _I32, _I32, _STATS]),
+    "olha_regressor_scales": (_I, [_D] * 5 + [_I] + [_D] * 4 + [_I32] + [_DP] * 4),
+}
+
 _lock = threading.Lock()
 _lib: Optional[C.CDLL] = None
 _initialised = False
@@ -243,7 +251,7 @@ def load_library() -> C.CDLL:
             except OSError as e:
                 raise AccelerationError(f"cannot load {LIBRARY_PATH}: {e}", backend="hip") from e
             for name, (res, args) in (list(PROTOTYPES.items()) + list(LV_PROTOTYPES.items()) + list(LVQ_PROTOTYPES.items())
-                                      + list(JD_PROTOTYPES.items()) + list(JS_PROTOTYPES.items())):
+                                      + list(JD_PROTOTYPES.items()) + list(JS_PROTOTYPES.items()) + list(HA_PROTOTYPES.items())):
                 try:
                     fn = getattr(lib, name)
                 except AttributeError:
@@ -1068,6 +1076,36 @@ def heston_qe_qmc_paths(S, T, r, q, kappa, theta, sigma_v, rho, v0, n_points: in
     sobol = _sobol_args(sv, shift, 0, n_points, 2)
     return _spot_and_variance(lib().olmc_heston_qe_qmc_paths, n_points, sobol.steps, path_major, S, T, r, q, kappa, theta, sigma_v, rho, v0,
                               _construction(bridge), int(n_points), *sobol.run)
+
+
+def _basis(spot_basis: bool) -> int:
+    return HA_BASIS_SPOT if spot_basis else HA_BASIS_SPOT_VARIANCE
+
+
+def heston_american_lsm(S, K, T, r, q, is_call: bool, kappa, theta, sigma_v, rho, v0, n_paths: int, n_steps: int, seed: int, poly_degree: int = 2,
+                        spot_basis: bool = False, qe: bool = False) -> Stats:
+    """The American option (LSM on the state (S_t, v_t); spot_basis: on S_t alone) on heston_paths' matrices (qe: heston_qe_paths'),
+    one chain of per-date launches (olha_american_lsm)."""
+    return _answer(lib().olha_american_lsm(S, K, T, r, q, int(is_call), kappa, theta, sigma_v, rho, v0, _scheme(qe), _basis(spot_basis), int(poly_degree),
+                                           int(n_paths), int(n_steps), seed64(seed), _byref(out := Stats())), out)
+
+
+def heston_american_lsm_qmc(S, K, T, r, q, is_call: bool, kappa, theta, sigma_v, rho, v0, n_points: int, sv: np.ndarray, shift: np.ndarray,
+                            bridge: bool = True, poly_degree: int = 2, spot_basis: bool = False, qe: bool = False) -> Stats:
+    """heston_american_lsm on heston_qmc_paths' matrices (qe: heston_qe_qmc_paths', bridge=False only): n_steps = sv.shape[0] / 2
+    (olha_american_lsm_qmc, which takes the tables' dimensions after the tables)."""
+    steps, psv, psh, bits = _sobol_args(sv, shift, 0, n_points, 2).run
+    return _answer(lib().olha_american_lsm_qmc(S, K, T, r, q, int(is_call), kappa, theta, sigma_v, rho, v0, _scheme(qe), _basis(spot_basis), int(poly_degree),
+                                               _construction(bridge), int(n_points), psv, psh, 2 * steps, bits, _byref(out := Stats())), out)
+
+
+def heston_american_scales(S, K, T, r, q, is_call: bool, kappa, theta, sigma_v, v0, n_steps: int):
+    """(x_centre, x_width, y_centre, y_width), each (n_steps + 1,): the pairs that standardise heston_american_lsm's regressors
+    x = (S_t / K - centre) / width and y = (v_t - centre) / width per date (olha_regressor_scales; pure host function: loads the library,
+    not the GPU)."""
+    out = [np.empty(int(n_steps) + 1 if n_steps >= 1 else 1, dtype=np.float64) for _ in range(4)]
+    _check(load_library().olha_regressor_scales(S, K, T, r, q, int(is_call), kappa, theta, sigma_v, v0, int(n_steps), *[_dp(a) for a in out]))
+    return tuple(out)
 
 
 def multi_gpu_european(S, K, T, r, sigma, q, is_call: bool, n_paths: int, n_steps: int, seed: int, antithetic: bool,

@@ -9,11 +9,13 @@
 #include "olmc_local_vol.h"
 #include "olmc_local_vol_qmc.h"
 #include "olmc_jump.h"
+#include "olha.h"
 #include "olmc_kernels.h"
 #include "olmc_local_vol_kernels.h"
 #include "olmc_local_vol_qmc_kernels.h"
 #include "olmc_jump_kernels.h"
 #include "olmc_jump_scenario_kernels.h"
+#include "olmc_heston_american_kernels.h"
 #include "olmc_job_board.h"
 #include "olmc_device_mem.h"
 
@@ -1551,12 +1553,11 @@ double lsm_bytes(int64_t n_paths, int32_t n_steps) { return 8.0 * static_cast<do
 
 // The step chain of an LSM pricing over the time-major path matrix d_paths [n_steps + 1][n_paths] that a launch queued before it on
 // c's stream writes; d_cash [n_paths] and d_rows [2][1024][kLsmNV] are the next the caller's `bulk` hands out.  Leaves the moments of the time-0
-// cash flows in c->h_result once the host has waited for them.
-int lsm_chain(DeviceCtx* c, double S, double K, double T, double r, double sigma, double q, int is_call, const LsmContract& lc,
-              int64_t n_paths, int32_t n_steps, double* d_paths, Carver* bulk) {
+// cash flows in c->h_result once the host has waited for them.  scale(t, &centre, &inv_width) gives the regressor's pair of date t.
+template <typename Scale>
+int lsm_chain_scaled(DeviceCtx* c, const LsmContract& lc, int64_t n_paths, int32_t n_steps, double* d_paths, Carver* bulk, Scale&& scale) {
     double* d_cash = bulk->take<double>(static_cast<size_t>(n_paths));                  // [n_paths]
     double* d_rows = bulk->take<double>(size_t(2) * 1024 * kLsmNV);                     // [2][grid][kLsmNV]: the regression sums a date hands to the next launch
-    const double dt = T / n_steps;
     // The per-date launches move 32 bytes per path and hand 16 sums per workgroup to the next launch, EVERY workgroup of which sums all
     // the rows: at most ONE workgroup per compute unit (<= 256 rows: one round trip), each thread taking its paths U at a time with all
     // 3 U loads in flight.  With one wave per SIMD the register count buys nothing, so U follows the paths a thread has (1, 2, 4, 8:
@@ -1573,7 +1574,7 @@ int lsm_chain(DeviceCtx* c, double S, double K, double T, double r, double sigma
     int rc = make_ws(c, c->stream, grid, kLsmNV, c->d_result, -1.0, &ws);          // arms the completion word for the launch that writes d_result
     if (rc) return rc;
     std::vector<double> centre(static_cast<size_t>(n_steps) + 1, 1.0), inv_width(static_cast<size_t>(n_steps) + 1, 1.0);   // while the path kernel runs
-    for (int32_t t = 1; t < n_steps; ++t) lsm_regressor_scale(S, K, r, q, sigma, dt, t, is_call != 0, &centre[t], &inv_width[t]);
+    for (int32_t t = 1; t < n_steps; ++t) scale(t, &centre[t], &inv_width[t]);
     int32_t init = 1;
     for (int32_t t_fit = n_steps - 1; t_fit >= 0; --t_fit) {
         const bool first = init != 0, final_date = t_fit == 0;
@@ -1595,6 +1596,15 @@ int lsm_chain(DeviceCtx* c, double S, double K, double T, double r, double sigma
         init = 0;
     }
     return sync_or_recover(c, c->stream);
+}
+
+// The chain under constant volatility: lsm_regressor_scale's pair with the contract's sigma at every date.
+int lsm_chain(DeviceCtx* c, double S, double K, double T, double r, double sigma, double q, int is_call, const LsmContract& lc,
+              int64_t n_paths, int32_t n_steps, double* d_paths, Carver* bulk) {
+    const double dt = T / n_steps;
+    return lsm_chain_scaled(c, lc, n_paths, n_steps, d_paths, bulk, [&](int32_t t, double* centre, double* inv_width) {
+        lsm_regressor_scale(S, K, r, q, sigma, dt, t, is_call != 0, centre, inv_width);
+    });
 }
 }  // namespace
 
@@ -3119,6 +3129,214 @@ extern "C" int olmc_heston_qe_qmc_paths(double S, double T, double r, double q, 
                                         int32_t bits, int path_major, double* spot_host, double* var_host) {
     return run_heston_qmc_paths<HestonQe>(S, T, r, q, {kappa, theta, sigma_v, rho, v0}, {construction, 0, n_points, n_steps, sv, shift, bits, 0},
                                           path_major, spot_host, var_host);
+}
+
+// ====================================================== American options under Heston ====
+// include/olha.h: the path kernels of olmc_heston_paths / olmc_heston_qe_paths and their Sobol forms, time-major, queued on the
+// context's stream ahead of a step chain -- heston_lsm_step_kernel on (S_t, v_t), or lsm_step_kernel on the spot matrix alone.
+namespace {
+static_assert(OLHA_EULER == OLMC_HESTON_EULER && OLHA_QE == OLMC_HESTON_QE, "with_heston_scheme reads olha.h's scheme codes");
+
+struct HaDateScale {                 // a date's regressors: x = (S_t / K - cx) iwx, y = (v_t - cy) iwy
+    double cx = 1.0, iwx = 1.0, cy = 0.0, iwy = 1.0;
+};
+
+// The model's expected average variance over [0, t], theta + (v0 - theta)(1 - e^(-kappa t)) / (kappa t): the sigma^2 of the lognormal
+// law behind a date's (cx, wx).
+double heston_average_variance(const HestonModel& m, double t) {
+    const double a = m.kappa * t;
+    return m.theta + (m.v0 - m.theta) * (a == 0.0 ? 1.0 : -std::expm1(-a) / a);
+}
+
+// lsm_regressor_scale's pair for S_t / K with the date's own sigma, and the conditional mean and standard deviation of the CIR variance
+// v_t given v0 for v_t; the width of v_t is clamped below at 1e-6 max(mean, theta) and at 1e-12, so that sigma_v = 0 leaves y finite
+// (exactly 0 where v_t is the mean).  A closed form that is not finite leaves the pair at (1, 1) / (0, 1).
+HaDateScale heston_lsm_scale(double S, double K, double r, double q, bool is_call, const HestonModel& m, double dt, int32_t t) {
+    HaDateScale s;
+    const double years = dt * t;
+    lsm_regressor_scale(S, K, r, q, std::sqrt(std::max(heston_average_variance(m, years), 0.0)), dt, t, is_call, &s.cx, &s.iwx);
+    const double a = m.kappa * years, e = std::exp(-a);
+    const double tg = years * (a == 0.0 ? 1.0 : -std::expm1(-a) / a);              // (1 - e^(-kappa t)) / kappa
+    const double mean = m.theta + (m.v0 - m.theta) * e;
+    const double var = m.sigma_v * m.sigma_v * (m.v0 * e * tg + 0.5 * m.theta * m.kappa * tg * tg);
+    const double width = std::max({std::sqrt(std::max(var, 0.0)), 1e-6 * std::max(mean, m.theta), 1e-12});
+    if (std::isfinite(mean) && std::isfinite(width)) {
+        s.cy = mean;
+        s.iwy = 1.0 / width;
+    }
+    return s;
+}
+
+// Bytes of a pricing's device buffers: the two matrices and the cash flows, + two buffers of <= 1024 workgroup rows of nv sums.
+double ha_bytes(int64_t n_paths, int32_t n_steps, int nv) {
+    return 8.0 * static_cast<double>(n_paths) * (2.0 * (n_steps + 1.0) + 1.0) + 8.0 * 2 * 1024 * nv;
+}
+int ha_row_width(int basis, int32_t poly_degree) {
+    if (basis == OLHA_BASIS_SPOT) return kLsmNV;
+    return poly_degree == 1 ? HaBasis<1>::NV : poly_degree == 2 ? HaBasis<2>::NV : HaBasis<3>::NV;
+}
+
+// The checks of both entry points that need neither the model nor the counts.
+int ha_check(int scheme, int basis, int32_t poly_degree, const olmc_stats* out) {
+    if (!out) return fail(OLMC_ERR_ARG, "null pointer");
+    if (scheme != OLHA_EULER && scheme != OLHA_QE) return fail(OLMC_ERR_ARG, "bad scheme (OLHA_EULER or OLHA_QE)");
+    if (basis != OLHA_BASIS_SPOT_VARIANCE && basis != OLHA_BASIS_SPOT) return fail(OLMC_ERR_ARG, "bad basis (OLHA_BASIS_SPOT_VARIANCE or OLHA_BASIS_SPOT)");
+    if (basis == OLHA_BASIS_SPOT_VARIANCE && (poly_degree < 1 || poly_degree > kHaMaxDegree))
+        return fail(OLMC_ERR_ARG, "poly_degree must be in [1, 3] for OLHA_BASIS_SPOT_VARIANCE");
+    if (basis == OLHA_BASIS_SPOT && (poly_degree < 1 || poly_degree > kLsmMaxDegree))
+        return fail(OLMC_ERR_ARG, "poly_degree must be in [1, 4] for OLHA_BASIS_SPOT");
+    return OLMC_OK;
+}
+
+// lsm_chain's launches with the bivariate step kernel of total degree D over the two time-major matrices; d_cash [n_paths] and d_rows
+// [2][1024][NV] are the next the caller's `bulk` hands out.  The grid and U are lsm_chain's: at most one workgroup per CU (every
+// workgroup of a launch re-reads every row of the launch before it), U from the paths a thread has.  Leaves {sum, sumsq} of the time-0
+// cash flows in c->h_result once the host has waited for them.
+template <int D>
+int heston_lsm_chain(DeviceCtx* c, const LsmContract& lc, const std::vector<HaDateScale>& scale, int64_t n_paths, int32_t n_steps,
+                     const double* d_spot, const double* d_var, Carver* bulk) {
+    constexpr int NV = HaBasis<D>::NV;
+    double* d_cash = bulk->take<double>(static_cast<size_t>(n_paths));
+    double* d_rows = bulk->take<double>(size_t(2) * 1024 * NV);
+    const int32_t grid = std::min<int32_t>(grid_for(n_paths), std::min<int32_t>(c->cus, 1024));
+    const int64_t per_thread = (n_paths + static_cast<int64_t>(grid) * kBlock - 1) / (static_cast<int64_t>(grid) * kBlock);
+    const int unroll = per_thread <= 1 ? 1 : per_thread <= 2 ? 2 : per_thread <= 4 ? 4 : 8;
+    ReduceWs ws;
+    int rc = make_ws(c, c->stream, grid, 2, c->d_result, -1.0, &ws);               // arms the completion word for the launch that writes d_result
+    if (rc) return rc;
+    bool first = true;
+    for (int32_t t_fit = n_steps - 1; t_fit >= 0; --t_fit) {
+        const bool final_date = t_fit == 0;
+        const HaDateScale &f = scale[t_fit], &p = scale[t_fit + 1];
+        const HaScale sc{f.cx, f.iwx, f.cy, f.iwy, p.cx, p.iwx, p.cy, p.iwy};
+        auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), 0, c->stream, n_paths, lc, sc, d_rows, t_fit, d_spot, d_var, d_cash, ws); };
+        auto pick = [&](auto u) {
+            constexpr int U = decltype(u)::value;
+            if (first && final_date) go(heston_lsm_step_kernel<D, U, true, true>);
+            else if (first) go(heston_lsm_step_kernel<D, U, true, false>);
+            else if (final_date) go(heston_lsm_step_kernel<D, U, false, true>);
+            else go(heston_lsm_step_kernel<D, U, false, false>);
+        };
+        if (unroll == 1) pick(std::integral_constant<int, 1>{});
+        else if (unroll == 2) pick(std::integral_constant<int, 2>{});
+        else if (unroll == 4) pick(std::integral_constant<int, 4>{});
+        else pick(std::integral_constant<int, 8>{});
+        rc = after_launch(c, c->stream);
+        if (rc) return rc;
+        first = false;
+    }
+    return sync_or_recover(c, c->stream);
+}
+
+// One pricing on c, whose bulk buffer holds ha_bytes: `paths(d_spot, d_var)` queues the scheme's time-major path kernel on c's
+// stream, the chain of the basis follows it, out answers from the time-0 cash flows (already discounted step by step: no outer factor).
+template <typename Paths>
+int heston_american(DeviceCtx* c, double S, double K, double T, double r, double q, int is_call, const HestonModel& m, int basis, int32_t poly_degree,
+                    int64_t n_paths, int32_t n_steps, Paths&& paths, olmc_stats* out) {
+    const size_t cells = (static_cast<size_t>(n_steps) + 1) * static_cast<size_t>(n_paths);
+    Carver bulk = c->bulk.carve();
+    double* d_spot = bulk.take<double>(cells);          // [n_steps + 1][n_paths] each, then the chain's buffers
+    double* d_var = bulk.take<double>(cells);
+    EventPair ep{};
+    int rc;
+    if (g_profile) { rc = prof_begin(c, c->stream, &ep); if (rc) return rc; }
+    paths(d_spot, d_var);
+    HIP_TRY(hipGetLastError());
+    const LsmContract lc = lsm_contract(S, K, T, r, 0.0, q, is_call, n_steps, poly_degree);        // the chains read strike, sign, discount, degree, n_steps
+    const double dt = T / n_steps;
+    std::vector<HaDateScale> scale(static_cast<size_t>(n_steps) + 1);                             // while the path kernel runs
+    for (int32_t t = 1; t < n_steps; ++t) scale[t] = heston_lsm_scale(S, K, r, q, is_call != 0, m, dt, t);
+    if (basis == OLHA_BASIS_SPOT) {
+        rc = lsm_chain_scaled(c, lc, n_paths, n_steps, d_spot, &bulk, [&](int32_t t, double* centre, double* inv_width) {
+            *centre = scale[t].cx;
+            *inv_width = scale[t].iwx;
+        });
+    } else if (poly_degree == 1) {
+        rc = heston_lsm_chain<1>(c, lc, scale, n_paths, n_steps, d_spot, d_var, &bulk);
+    } else if (poly_degree == 2) {
+        rc = heston_lsm_chain<2>(c, lc, scale, n_paths, n_steps, d_spot, d_var, &bulk);
+    } else {
+        rc = heston_lsm_chain<3>(c, lc, scale, n_paths, n_steps, d_spot, d_var, &bulk);
+    }
+    if (rc) return rc;
+    if (g_profile) { rc = prof_end(c, c->stream, ep); if (rc) return rc; }
+    finish_one(c->h_result, n_paths, 0.0, T, heston_poisoned(S, K, T, r, q, m), out);
+    return OLMC_OK;
+}
+constexpr const char* kHaTooBig = "path matrices would exceed 64 GB: lower n_paths or n_steps";
+}  // namespace
+
+extern "C" int olha_american_lsm(double S, double K, double T, double r, double q, int is_call, double kappa, double theta, double sigma_v,
+                                 double rho, double v0, int scheme, int basis, int32_t poly_degree, int64_t n_paths, int32_t n_steps,
+                                 uint64_t seed, olmc_stats* out) {
+    int rc = ha_check(scheme, basis, poly_degree, out);
+    if (rc) return rc;
+    const HestonModel m{kappa, theta, sigma_v, rho, v0};
+    return with_heston_scheme(scheme, [&](auto s) -> int {
+        using Scheme = decltype(s);
+        rc = Scheme::check(m);
+        if (rc) return rc;
+        CtxLease lease;
+        rc = matrix_prologue(n_paths, n_steps, ha_bytes(n_paths, n_steps, ha_row_width(basis, poly_degree)), kHaTooBig, &lease);
+        if (rc) return rc;
+        DeviceCtx* const c = lease.c;
+        const auto hc = Scheme::make(S, T, r, q, 1, m, n_steps);                   // as run_heston_paths makes it: the same matrices
+        const PathRange pr = make_range(0, n_paths, n_steps, seed);
+        return heston_american(c, S, K, T, r, q, is_call, m, basis, poly_degree, n_paths, n_steps, [&](double* d_spot, double* d_var) {
+            hipLaunchKernelGGL(Scheme::template paths_kernel<false>(), dim3(grid_for(n_paths)), dim3(kBlock), 0, c->stream, pr, hc, S, d_spot, d_var);
+        }, out);
+    });
+}
+
+extern "C" int olha_american_lsm_qmc(double S, double K, double T, double r, double q, int is_call, double kappa, double theta, double sigma_v,
+                                     double rho, double v0, int scheme, int basis, int32_t poly_degree, int construction, int64_t n_points,
+                                     const uint32_t* sv, const uint32_t* shift, int32_t dims, int32_t bits, olmc_stats* out) {
+    int rc = ha_check(scheme, basis, poly_degree, out);
+    if (rc) return rc;
+    if (dims % 2) return fail(OLMC_ERR_ARG, "dims must be even: a step takes two Sobol dimensions");
+    const HestonModel m{kappa, theta, sigma_v, rho, v0};
+    return with_heston_scheme(scheme, [&](auto s) -> int {
+        using Scheme = decltype(s);
+        rc = heston_qmc_scheme_check<Scheme>(m, construction);
+        if (rc) return rc;
+        const auto call = SobolCall::make({construction, 0, n_points, dims / 2, sv, shift, bits, 0}, 2, &rc);
+        if (!call) return rc;
+        const int32_t n_steps = call->n_steps;
+        CtxLease lease;
+        rc = matrix_prologue(n_points, n_steps, ha_bytes(n_points, n_steps, ha_row_width(basis, poly_degree)), kHaTooBig, &lease);
+        if (rc) return rc;
+        DeviceCtx* const c = lease.c;
+        const auto hc = Scheme::make(S, T, r, q, 1, m, n_steps);                   // as run_heston_qmc_paths makes it: the same matrices
+        QmcPathLaunch pl;
+        rc = qmc_matrix_setup(c, *call, &pl);
+        if (rc) return rc;
+        return heston_american(c, S, K, T, r, q, is_call, m, basis, poly_degree, n_points, n_steps, [&](double* d_spot, double* d_var) {
+            if constexpr (Scheme::kBridge) {
+                with_bool(pl.bridge, [&](auto b) {
+                    hipLaunchKernelGGL((heston_qmc_paths_kernel<decltype(b)::value, false>), dim3(pl.grid), dim3(kBlock), 0, c->stream, pl.qr, hc, S, pl.d_sv,
+                                       pl.d_shift, pl.plan, d_spot, d_var);
+                });
+            } else {
+                hipLaunchKernelGGL((heston_qe_qmc_paths_kernel<false>), dim3(pl.grid), dim3(kBlock), 0, c->stream, pl.qr, hc, S, pl.d_sv, pl.d_shift, d_spot, d_var);
+            }
+        }, out);
+    });
+}
+
+extern "C" int olha_regressor_scales(double S, double K, double T, double r, double q, int is_call, double kappa, double theta, double sigma_v,
+                                     double v0, int32_t n_steps, double* x_centre, double* x_width, double* y_centre, double* y_width) {
+    if (!x_centre || !x_width || !y_centre || !y_width) return fail(OLMC_ERR_ARG, "null pointer");
+    if (n_steps < 1) return fail(OLMC_ERR_ARG, "n_steps must be >= 1");
+    const HestonModel m{kappa, theta, sigma_v, 0.0, v0};
+    const double dt = T / n_steps;
+    for (int32_t t = 0; t <= n_steps; ++t) {
+        const HaDateScale s = t >= 1 && t < n_steps ? heston_lsm_scale(S, K, r, q, is_call != 0, m, dt, t) : HaDateScale{};
+        x_centre[t] = s.cx;
+        x_width[t] = 1.0 / s.iwx;
+        y_centre[t] = s.cy;
+        y_width[t] = 1.0 / s.iwy;
+    }
+    return OLMC_OK;
 }
 
 // ====================================================== structured products under Heston ====

@@ -451,7 +451,8 @@ __device__ __forceinline__ void grid_reduce(double v, const ReduceWs& ws, Epilog
 // of the workgroup; `v` is this workgroup's sum of component threadIdx.x (wave 0, lanes < NV).
 template <int NV>
 __device__ __forceinline__ double workgroup_rows_sum(const double* src, int32_t rows, double* part /* LDS [kBlock] */) {
-    constexpr int NVP = NV <= 8 ? 8 : NV <= 16 ? 16 : 32;
+    constexpr int NVP = NV <= 8 ? 8 : NV <= 16 ? 16 : NV <= 32 ? 32 : 64;        // 64: the 39 sums of the Heston American fit of degree 3
+    static_assert(NV <= 64, "a row is summed by the threads of one wave's width");
     constexpr int SUBS = kBlock / NVP;
     const int c = threadIdx.x % NVP, sub = threadIdx.x / NVP;
     double v = 0.0;

@@ -10,6 +10,8 @@ Additive: ``method="qmc"`` runs `price_monte_carlo` and `simulate_paths` on scra
 Additive: ``scheme="qe"`` (keyword-only; "euler" is the default and today's code path) discretises with Andersen's quadratic-exponential
 scheme (include/olmc.h "Heston, quadratic-exponential scheme") in `price_monte_carlo`, `simulate_paths`, `price_surface`,
 `calibration_objective` and `calibrate_heston`; the path payoffs (`price_asian`, `price_barrier`, `price_lookback`) stay on Euler.
+Additive: `price_american` prices the American option by least-squares Monte Carlo on `simulate_paths`' matrices, regressing on the
+state (S_t, v_t) (include/olha.h), with either scheme and either method.
 """
 from __future__ import annotations
 
@@ -329,6 +331,38 @@ class HestonPricer:
         exotic_options.py:347-401), in one launch that stores no path.  The rest as price_asian; also refused: an unknown lookback_type."""
         return self._price_path_payoff(_lookback_payoff(lookback_type), 0.0, S, K, T, r, q, option_type, n_paths, n_steps, seed, antithetic, return_error, method,
                                        path_construction)
+
+    def price_american(self, S: float, K: float, T: float, r: float, q: float = 0.0, option_type: Literal["call", "put"] = "put",
+                       n_paths: int = 50000, n_steps: int = 50, poly_degree: int = 2, seed: Optional[int] = None, return_error: bool = False, *,
+                       basis: Literal["spot_variance", "spot"] = "spot_variance", scheme: Literal["euler", "qe"] = "euler",
+                       method: Literal["pseudo", "qmc"] = "pseudo", path_construction: Literal["bridge", "sequential"] = "bridge"):
+        """The American option under this model by Longstaff-Schwartz least-squares Monte Carlo (include/olha.h): AmericanOption.price's
+        algorithm (exotic_options.py:259-306) on the matrices of simulate_paths(S, T, r, q, n_paths, n_steps, seed, method=...,
+        path_construction=..., scheme=...), regressing at every exercise date 1 .. n_steps - 1 the discounted cash flows of the paths in
+        the money on the date's state.  There is no antithetic mirror: the regression runs over the whole path set.
+        basis: "spot_variance" (default) = all monomials x^a y^b, a + b <= poly_degree in [1, 3], of the standardised spot x and
+        variance y (3, 6 or 10 unknowns) -- under stochastic volatility the continuation value depends on (S_t, v_t); "spot" = 1, x, ..,
+        x^poly_degree, poly_degree in [1, 4], AmericanOption's one-factor fit on the Heston spot: a valid but lower price.  A date is
+        fitted when more paths are in the money than the fit has unknowns; otherwise nobody exercises there.
+        seed=None, return_error, method, path_construction and scheme as price_monte_carlo: with method="qmc" the standard error is the
+        naive per-path one, and scheme="qe" takes path_construction="sequential" only.  T <= 0 returns the intrinsic value (error 0)
+        without simulating.  Refused (ValueError, before the device is touched): an option_type other than "call" / "put", an unknown
+        basis or scheme, poly_degree outside the basis's range, n_paths or n_steps < 1, and what price_monte_carlo refuses."""
+        if option_type not in ("call", "put"):
+            raise ValueError("option_type must be 'call' or 'put'")
+        if basis not in ("spot_variance", "spot"):
+            raise ValueError("basis must be 'spot_variance' or 'spot'")
+        qe = _check_scheme(scheme, method, path_construction)
+        top = 4 if basis == "spot" else 3
+        if not 1 <= poly_degree <= top:
+            raise ValueError(f"poly_degree must be in [1, {top}] for basis={basis!r}")
+        _check_sizes(n_paths, n_steps)
+        if T <= 0:
+            intrinsic = max(S - K, 0) if option_type == "call" else max(K - S, 0)
+            return (np.float64(intrinsic), 0.0) if return_error else np.float64(intrinsic)
+        sobol, run = _draws(method, path_construction, n_paths, n_steps, seed)
+        entry = _hip.heston_american_lsm_qmc if sobol else _hip.heston_american_lsm
+        return _result(entry(S, K, T, r, q, option_type == "call", *self._model(), *run, poly_degree, basis == "spot", qe), return_error)
 
     def _price_structured(self, philox, sobol, contract, S, T, r, q, n_paths, n_steps, seed, antithetic, return_error, method,
                           path_construction, scheme):
