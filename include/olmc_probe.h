@@ -5,7 +5,8 @@
  * can price through it), with contexts of its own.  libolmc.so exports NONE of the symbols declared here and contains no
  * fault-injection branch.  Same conventions as olmc.h: int status, 0 = ok, olmc_last_error() of the SAME library for the text.
  * Who loads it: tests/ (device-guard, failing-shard, multi-rank rehearsal, exp2, inverse-normal, Box-Muller, square-root and moment taps, and the three taps of the
- * fused grid reduction: olmc_reduce_probe, olmc_rows_sum_probe, olmc_wave_reduce_probe), tools/ (phase stamps, issue
+ * fused grid reduction: olmc_reduce_probe, olmc_rows_sum_probe, olmc_wave_reduce_probe, and the two taps of the LSM chains' in-wave
+ * solvers: olmc_ha_fit_probe, olmc_lsm_fit_probe), tools/ (phase stamps, issue
  * probes), bench.py (clock and issue-cost calibration of the roofline) -- through tools/probe/binding.py. */
 #ifndef OLMC_PROBE_H
 #define OLMC_PROBE_H
@@ -43,21 +44,38 @@ int olmc_normal_moments(uint64_t seed, int64_t path_offset, int64_t n_paths, int
  * workspace; thread t of workgroup b contributes H(b, c, salt[j]) + K(t, c, salt[j]) to component c when 256 b + t < n_threads[j],
  * else 0.0 -- H a 24-bit, K a 16-bit odd integer hash (written out in tools/probe/olmc_probe_kernels.h and restated by
  * tests/reduction_reference.py), so every partial sum is exact in fp64 and the totals must EQUAL integers.  values 0 = those
- * integers, 1 = double(H + K) / 3.0 (sums round).  nv in {2, 5, 8, 16, 32}.  form 0 = block_then_grid_reduce<nv>, 1 =
- * block_then_grid_reduce_from<nv, 1> with the first exchange made by the producer (nv 8, 16, 32 only), 2 = block_row_sum<nv> then
+ * integers, 1 = double(H + K) / 3.0 (sums round).  nv in {2, 5, 8, 10, 16, 22, 32}.  form 0 = block_then_grid_reduce<nv>, 1 =
+ * block_then_grid_reduce_from<nv, 1> with the first exchange made by the producer (nv >= 8 only), 2 = block_row_sum<nv> then
  * grid_reduce<nv> (nv = 2) / grid_reduce_workgroup<nv> called directly.  blocking 1 = each launch writes the context's pinned result
  * and completes through the polled flag; 0 = all launches queued back to back on one stream with no host wait between them, each into
  * its own slot of a device buffer, one synchronise and one copy at the end.  out[launches][nv + 1] (host): the nv totals, then the
  * workspace's tail (= n_threads[j]).  Where a launch refuses to store (the device-side row-capacity guard) the totals are NaN and the
- * tail is -1 (blocking) or NaN. */
+ * tail is -1 (blocking) or NaN.
+ * form 3 = the hand-over of the LSM chains (lsm_step_kernel, heston_lsm_step_kernel), nv in {10, 16, 22, 39} (HaBasis<D>::NV and
+ * kLsmNV; 39 exists in this form only, a workspace row of the grid reduction holds 32 values): ONE pair of launches on one stream with
+ * nothing between them.  The first, on ceil(n_threads[0] / 256) <= 1024 workgroups with salt[0], has every workgroup store
+ * block_row_sum<nv> of its values as a plain row; in the second, `launches` workgroups (the argument counts workgroups here) each run
+ * workgroup_rows_sum<nv> over all those rows and store their totals: out[launches][nv], no tail.  `blocking` is not read. */
 int olmc_reduce_probe(int nv, int form, int values, int blocking, int32_t launches, const int64_t* n_threads, const uint64_t* salt,
                       double* out);
 /* The row summers on a host matrix rows_host[rows][nv] (rows in [1, 2^20]): out_nv[c] = sum of column c by wave_rows_sum<nv>
- * (whole_workgroup 0: one wave, nv 2 or 5) or workgroup_rows_sum<nv> (whole_workgroup 1: 256 threads, nv 5, 8, 16 or 32). */
+ * (whole_workgroup 0: one wave, nv 2 or 5) or workgroup_rows_sum<nv> (whole_workgroup 1: 256 threads, nv 5, 8, 10, 16, 22, 32 or 39). */
 int olmc_rows_sum_probe(int nv, int whole_workgroup, const double* rows_host, int32_t rows, double* out_nv);
-/* wave_transpose_reduce<p, 32, op> on one wave, p in {1, 2, 4, 8, 16, 32}, op 0 = sum, 1 = max, 2 = min: lane l starts from
+/* wave_transpose_reduce<p, 32, op> on one wave, p in {1, 2, 4, 8, 16, 32, 64}, op 0 = sum, 1 = max, 2 = min: lane l starts from
  * v_host[l][0 .. p); out[l] = its v[0] afterwards, the result of value index l >> (6 - log2 p). */
 int olmc_wave_reduce_probe(int p, int op, const double* v_host, double* out);
+/* The in-wave solvers of the LSM chains on CHOSEN totals: what the `fit` lambda of heston_lsm_step_kernel (olmc_ha_fit_probe: ha_fit<D>,
+ * degree 1..3) and of lsm_step_kernel (olmc_lsm_fit_probe: LsmFit, degree 1..4) does, in that order -- workgroup_rows_sum over the
+ * set's single row, the solve in the first wave, the barrier, a copy of the coefficients out of LDS -- one workgroup of 256 threads per
+ * set, n_sets in [1, 4096]; thread 255, in the last wave, writes the set's coefficients and `valid`.
+ * olmc_ha_fit_probe: totals_host[n_sets][NV], NV = 10, 22, 39: the moments sum x^a y^b at ha_index(a, b) = s (s + 1) / 2 + b, s = a + b
+ * <= 2 degree (NM = 6, 15, 28 of them), the right-hand sides sum x^a y^b cf at NM + ha_index(a, b), a + b <= degree (NU = 3, 6, 10), the
+ * in-the-money count last; beta_host[n_sets][NU].
+ * olmc_lsm_fit_probe: totals_host[n_sets][16]: sum z^m at m = 0..8, sum z^k cf at 9 + k, k = 0..4, the count at 14; beta_host[n_sets][5]
+ * (unknowns beyond `degree` are 0).
+ * The totals need not be moments of anything: the operation is totals -> coefficients. */
+int olmc_ha_fit_probe(int degree, const double* totals_host, int32_t n_sets, double* beta_host, int32_t* valid_host);
+int olmc_lsm_fit_probe(int degree, const double* totals_host, int32_t n_sets, double* beta_host, int32_t* valid_host);
 
 /* ---- where a launch spends its time --------------------------------------- */
 /* One launch of the headline kernel (European call, antithetic, n_paths x n_steps, production launch shape): wave 0 of every

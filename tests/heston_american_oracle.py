@@ -32,13 +32,21 @@ def lstsq_fit(A, cf):
     return np.linalg.lstsq(A, cf, rcond=None)[0]
 
 
-def normal_equations_fit(A, cf):
-    """A^T A beta = A^T cf by elimination in the natural order; a pivot not above 1e-11 of its own diagonal moment pins that unknown."""
+def normal_equations_fit(A, cf, report=None):
+    """A^T A beta = A^T cf by elimination in the natural order; a pivot not above 1e-11 of its own diagonal moment pins that unknown.
+    `report` (a list) receives per pivot (its ratio to its diagonal moment, the smallest ratio among the pivots of this solve that were
+    divided by before it, 1.0 when none): what a caller needs to say how far a pin decision was from depending on rounding."""
     n = A.shape[1]
     aug = np.column_stack([A.T @ A, A.T @ cf])
     diag = np.diag(aug).copy()
+    floor = 1.0
     for k in range(n):
-        if not abs(aug[k, k]) > 1e-11 * abs(diag[k]):
+        pinned = not abs(aug[k, k]) > 1e-11 * abs(diag[k])
+        if report is not None:
+            ratio = abs(aug[k, k]) / abs(diag[k]) if diag[k] else 0.0
+            report.append((ratio, floor))
+            floor = floor if pinned else min(floor, ratio)
+        if pinned:
             aug[k, :] = 0.0
             aug[:, k] = 0.0
             aug[k, k] = 1.0

@@ -117,7 +117,9 @@ def rounded_reference(nv: int, n_threads: int, salt: int):
 
 
 # ---- the launch shapes of tests/test_gpu_reduction.py (the CPU test checks that every total they lead to stays exact)
-NV_FORMS = [(nv, form) for nv in (2, 5, 8, 16, 32) for form in (0, 1, 2) if form != 1 or nv >= 8]
+# 10 and 22 are HaBasis<1>::NV and HaBasis<2>::NV (the Heston American fit); HaBasis<3>::NV = 39 is wider than a workspace row of the grid
+# reduction (32 values) and exists in the hand-over form alone (below)
+NV_FORMS = [(nv, form) for nv in (2, 5, 8, 10, 16, 22, 32) for form in (0, 1, 2) if form != 1 or nv >= 8]
 # one group; a group of exactly 256; a second group of one workgroup; the SUBS and SUBS * kBatch boundaries of every padded width
 SWEEP_G = (1, 2, 31, 32, 33, 63, 64, 65, 255, 256, 257, 511, 512, 513, 1000)
 BIG_G = (65_537, 1 << 18)               # 257 groups (second trip of the level-2 row sum); the largest grid (1,024 groups)
@@ -147,3 +149,39 @@ def big_launches():
     """(n_threads, salts) of the launches past 65,536 workgroups: each BIG_G full, and with one thread in its last workgroup."""
     n = [x for g in BIG_G for x in (BLOCK * g, BLOCK * g - (BLOCK - 1))]
     return n, [0x5_0000_0000 + j for j in range(len(n))]
+
+
+# ---- form 3, the hand-over of the LSM chains: G1 workgroups store block_row_sum<nv> rows, G2 workgroups each sum all of them by
+# workgroup_rows_sum<nv>.  The widths are kLsmNV and HaBasis<D>::NV; the chains launch at most 1,024 workgroups.
+HAND_OVER_NV = (16, 10, 22, 39)
+HAND_OVER_G1 = (1, 2, 255, 256, 257, 1024)
+HAND_OVER_G2 = (1, 3, 256)
+
+
+def padded_width(nv: int, whole_workgroup: bool) -> int:
+    """NVP of workgroup_rows_sum<nv> (8, 16, 32, 64: the 39 sums of degree 3 take a whole wave's width) / wave_rows_sum<nv> (2, 8, 16, 32)."""
+    if whole_workgroup:
+        return 8 if nv <= 8 else 16 if nv <= 16 else 32 if nv <= 32 else 64
+    return 2 if nv <= 2 else 8 if nv <= 8 else 16 if nv <= 16 else 32
+
+
+def subs_batch(nv: int, whole_workgroup: bool):
+    """(SUBS, kBatch): row subsets per column and loads in flight per lane; NVP = 64 gives (4, 16)."""
+    nvp = padded_width(nv, whole_workgroup)
+    if whole_workgroup:
+        return BLOCK // nvp, 16 if nvp >= 16 else 8
+    return 64 // nvp, 8
+
+
+def transpose_width(nv: int) -> int:
+    """P of block_row_sum<nv>: nv padded to a power of two (39 -> 64: SHIFT = 0, a value index per lane)."""
+    p = 1
+    while p < nv:
+        p *= 2
+    return p
+
+
+def hand_over_launches(nv: int):
+    """(n_threads, salts) of form 3's first launches: every G1 full, with one thread in the last workgroup, and with one thread missing."""
+    n = [x for g in HAND_OVER_G1 for x in (BLOCK * g, BLOCK * g - (BLOCK - 1), BLOCK * g - 1)]
+    return n, [(nv << 44) ^ (0xC2B2AE3D27D4EB4F * (j + 1) & 0xFFFFFFFFFFF) for j in range(len(n))]

@@ -51,14 +51,17 @@ def test_measurement_code_is_not_in_the_product_library():
     build_probe_library()
     product, instrumented = exported_symbols(LIBRARY), exported_symbols(PROBE_LIBRARY)
     only_probe = set(declared_symbols(PROBE_HEADER))
-    assert only_probe == set(probe.PROBE_PROTOTYPES) and len(only_probe) == 15
+    assert only_probe == set(probe.PROBE_PROTOTYPES) and len(only_probe) == 17
     assert not (only_probe & product)
     assert not [n for n in product if any(w in n for w in ("probe", "stamp", "clock", "moments"))]
     assert instrumented == product | only_probe
     blob = open(LIBRARY, "rb").read()
-    for word in (b"probe_mad_u64_u32", b"european_stamp_kernel", b"clock_probe_kernel", b"normal_moments_kernel", b"FAULT_SHARD", b"injected shard failure"):
+    for word in (b"probe_mad_u64_u32", b"european_stamp_kernel", b"clock_probe_kernel", b"normal_moments_kernel", b"ha_fit_probe_kernel",
+                 b"lsm_fit_probe_kernel", b"rows_store_probe_kernel", b"rows_total_probe_kernel", b"FAULT_SHARD", b"injected shard failure"):
         assert word not in blob, word
-    assert b"european_stamp_kernel" in open(PROBE_LIBRARY, "rb").read()
+    probe_blob = open(PROBE_LIBRARY, "rb").read()
+    for word in (b"european_stamp_kernel", b"ha_fit_probe_kernel", b"lsm_fit_probe_kernel", b"rows_store_probe_kernel", b"rows_total_probe_kernel"):
+        assert word in probe_blob, word
     lib = probe.hip.load_library()
     for name in only_probe:
         assert hasattr(lib, name)

@@ -11,6 +11,7 @@ degrees 1 .. 3, the cash flows of the lstsq run at every date) is 2.95e-9 (sigma
 4.2e5), times 100.  A case whose margin falls under the guard is given another seed when this file is written; with seed 7 none of
 the cases below does (the smallest margin is 1.5e-6).
 """
+import functools
 import math
 
 import numpy as np
@@ -169,6 +170,44 @@ def test_a_constant_variance_pins_every_y_monomial(degree):
     assert_tied(st, want, x, AMERICAN_TIE)
 
 
+def library_regressors(S, K, q, call, model, n_steps):
+    """regressors(t, S_t, v_t) -> (x, y) in the library's own standardisation (olha_regressor_scales: host arithmetic)."""
+    kappa, theta, sigma_v, _rho, v0 = model
+    cx, wx, cy, wy = _hip.heston_american_scales(S, K, T, R, q, call, kappa, theta, sigma_v, v0, n_steps)
+    return lambda t, s, v: ((s / K - cx[t]) / wx[t], (v - cy[t]) / wy[t])
+
+
+@pytest.mark.parametrize("degree", [1, 2, 3])
+def test_a_constant_variance_off_its_mean_pins_every_y_monomial_during_elimination(degree):
+    """sigma_v = 0 with v0 = 0.09, not theta: v_t is the same on every path but it is the Euler recursion's value, not the conditional
+    mean the regressor is centred on, and the width is at its clamp -- y is a constant in the thousands.  No y column is zero from
+    the start: the pivot of y becomes zero only once the constant has been eliminated, x y only after x, and so on, each a cancellation of
+    sums of order y^2 .. y^6 down to rounding.  Every monomial with a power of y must pin, and what is left is the one-factor fit.
+    First, in NumPy on the same matrices: the restated rule (normal equations in the library's regressors, the pin rule) makes the
+    one-factor decisions, none of them within GUARD of its threshold."""
+    model = (2.0, 0.04, 0.0, -0.7, 0.09)
+    S, K, q, call = PUT
+    n_paths, n_steps = 20_001, 25
+    spot, var = matrices(EULER, model, S, q, n_paths, n_steps, 7)
+    assert np.all(var == var[0]) and np.all(var[0, 1:] != 0.04) and np.all(np.diff(var[0]) < 0)
+    regressors = library_regressors(S, K, q, call, model, n_steps)
+    y = np.array([regressors(t, spot[:1, t], var[:1, t])[1][0] for t in range(1, n_steps)])
+    assert np.all(np.abs(y) > 1.0), y
+    report = []
+    _price, _cf, _margin, restated = hao.american_from_state(spot, var, K, T, R, model[1], "put", degree, regressors=regressors,
+                                                             fit=functools.partial(hao.normal_equations_fit, report=report), return_decisions=True)
+    _price, _cf, margin, one_factor = hao.american_from_state(spot, var, K, T, R, model[1], "put", degree, with_variance=False, return_decisions=True)
+    unknowns = (degree + 1) * (degree + 2) // 2
+    pinned = [sorted(k for k in range(unknowns) if not report[d + k][0] > 1e-11) for d in range(0, len(report), unknowns)]
+    print("degree", degree, "margin", margin, "largest pinned ratio", max(r for r, _ in report if not r > 1e-11), "smallest fitted", min(r for r, _ in report if r > 1e-11))
+    assert len(pinned) == n_steps - 1 and all(p == [k for k, (a, b) in enumerate((s - b, b) for s in range(degree + 1) for b in range(s + 1)) if b] for p in pinned)
+    assert one_factor.any() and np.array_equal(restated, one_factor)
+    assert margin > GUARD
+    st = price(EULER, model, S, K, q, call, n_paths, n_steps, 7, degree)
+    want, x = orc.american_from_paths(spot, K, T, R, "put", degree, return_payoffs=True)
+    assert_tied(st, want, x, AMERICAN_TIE)
+
+
 # -------------------------------------------------------------------- 4. too few paths in the money to regress ----
 @pytest.mark.parametrize("draw", [EULER, SOBOL_BRIDGE], ids=["euler", "sobol-bridge"])
 def test_five_paths_never_exercise_early(draw):
@@ -182,6 +221,53 @@ def test_five_paths_never_exercise_early(draw):
     assert np.any(x > 0)
     assert_tied(st, np.mean(x), x, 1e-13)
     assert hao.american_from_state(spot, var, K, T, R, USUAL[1], "put", 2)[2] == math.inf      # the oracle fitted no date either
+
+
+FEW_N, FEW_SEEDS, FEW_STEPS, FEW_STRIKE = (7, 8, 11, 12, 16, 40), range(12), 6, 110.0
+FEW_LEFT_OUT = 0.25
+
+
+def few_paths_checker(spot, var, degree, regressors):
+    """(cash flows, robust) of the restated device algorithm (normal equations, pin rule, the library's regressors) on the matrices.
+    ROBUST says that no decision of the run can depend on rounding, by two figures the checker reports about itself:
+      pivots   a pivot that follows divisions by pivots of ratio >= rho carries an error of about n^2 u / rho of its diagonal moment (n
+               unknowns, u = 2^-53: each entry of the Schur complement has taken at most n updates whose multipliers are known to u / rho, and
+               the moments themselves are sums of <= 40 terms in another order); every pivot ratio must lie at least 100 such errors away
+               from 1e-11, on either side;
+      margin   a backward stable solve errs in the continuation value by about n^2 u K / rho_min (the scaled moment matrix's condition
+               number is 1 / rho_min up to a factor n); the smallest |intrinsic - continuation| must be above 100 times that."""
+    n, u, report = (degree + 1) * (degree + 2) // 2, 2.0 ** -53, []
+    _price, cf, margin = hao.american_from_state(spot, var, FEW_STRIKE, T, R, USUAL[1], "put", degree, regressors=regressors,
+                                                 fit=functools.partial(hao.normal_equations_fit, report=report))
+    distance = min((abs(ratio - 1e-11) / (n * n * u / floor) for ratio, floor in report), default=math.inf)
+    rho_min = min((ratio for ratio, _ in report if ratio > 1e-11), default=1.0)
+    return cf, distance >= 100.0 and margin > 100.0 * n * n * u * FEW_STRIKE / rho_min, len(report) // n
+
+
+@pytest.mark.parametrize("degree", [1, 2, 3])
+def test_a_few_paths_where_the_moment_matrix_is_all_but_singular(degree):
+    """The two-factor counterpart of test_gpu_exotics' test_american_where_the_moment_matrix_is_singular: 7 .. 40 paths, six dates, a put
+    ten in the money, so that dates have exactly NU, NU + 1 or a few more paths in the money (3, 6, 10 unknowns) and the fit all but
+    interpolates.  Every price is finite and within [0, K], n ==; wherever the checker's own figures say its decisions are robust the
+    device's sum is the checker's at rel 1e-5 (one flipped decision moves it by more).  At most a quarter of the (N, seed) cases may be
+    left out that way (counted on the device's matrices when this was written: none of the 72 per degree, 339 / 251 / 120 dates fitted)."""
+    S, q, call = 100.0, 0.0, False
+    regressors = library_regressors(S, FEW_STRIKE, q, call, USUAL, FEW_STEPS)
+    compared = fitted_dates = 0
+    for n_paths in FEW_N:
+        for seed in FEW_SEEDS:
+            st = price(EULER, USUAL, S, FEW_STRIKE, q, call, n_paths, FEW_STEPS, seed, degree)
+            spot, var = matrices(EULER, USUAL, S, q, n_paths, FEW_STEPS, seed)
+            cf, robust, fitted = few_paths_checker(spot, var, degree, regressors)
+            assert st.n == n_paths and math.isfinite(st.price) and 0.0 <= st.price <= FEW_STRIKE, (n_paths, degree, seed, st.price)
+            fitted_dates += fitted
+            if robust:
+                compared += 1
+                assert st.sum == pytest.approx(float(np.sum(cf)), rel=1e-5, abs=1e-9), (n_paths, degree, seed, st.sum, float(np.sum(cf)))
+    total = len(FEW_N) * len(FEW_SEEDS)
+    print("degree", degree, "compared", compared, "of", total, "dates fitted", fitted_dates)
+    assert total - compared <= FEW_LEFT_OUT * total
+    assert fitted_dates > 0 or degree == 3 and max(FEW_N) <= 10
 
 
 # ------------------------------------------------------------------------------------------- 5. the statistics ----

@@ -5,8 +5,9 @@ grid_reduce_workgroup, wave_rows_sum, workgroup_rows_sum) pinned to EXACT sums t
 Every price, Greek and moment of the library leaves the device through this code, and a pricing test cannot see it fail: one lost
 lane in a million paths is 1e-6 of a sum the same-stream ties compare at 2e-6.  A reduction has an exact answer, though.  The taps
 feed it integers whose every partial sum fits in 53 bits (tests/reduction_reference.py), so the fp64 result is exact in any order
-and must EQUAL a Python integer: a dropped, doubled, stale or misrouted value fails `==`, at every row width (NV 2, 5, 8, 16, 32),
-entry form, group count and ragged tail the product reaches.  No tolerance anywhere except in the one test of rounded sums, whose
+and must EQUAL a Python integer: a dropped, doubled, stale or misrouted value fails `==`, at every row width (NV 2, 5, 8, 16, 32, and
+the Heston American fit's 10, 22 and 39 with their P = 64 transpose and NVP = 64 row sum), entry form -- the LSM chains' two-launch
+hand-over among them -- group count and ragged tail the product reaches.  No tolerance anywhere except in the one test of rounded sums, whose
 bound is the textbook one for recursive summation in any order."""
 import functools
 import math
@@ -122,26 +123,23 @@ def test_back_to_back_launches_are_exact_under_load(nv):
 
 # ------------------------------------------------------------------ row summers
 def _subs_batch(nv, whole_workgroup):
-    """(SUBS, kBatch) of wave_rows_sum<nv> / workgroup_rows_sum<nv>: row subsets per column and loads in flight per lane."""
-    if whole_workgroup:
-        nvp = 8 if nv <= 8 else 16 if nv <= 16 else 32
-        return 256 // nvp, 16 if nvp >= 16 else 8
-    nvp = 2 if nv <= 2 else 8 if nv <= 8 else 16 if nv <= 16 else 32
-    return 64 // nvp, 8
+    """(SUBS, kBatch) of wave_rows_sum<nv> / workgroup_rows_sum<nv>: row subsets per column and loads in flight per lane (NVP = 64, the 39
+    sums of degree 3: 4 subsets of 16 loads)."""
+    return ref.subs_batch(nv, whole_workgroup)
 
 
-ROW_SUMMERS = [(2, False), (5, False), (5, True), (8, True), (16, True), (32, True)]
+ROW_SUMMERS = [(2, False), (5, False), (5, True), (8, True), (10, True), (16, True), (22, True), (32, True), (39, True)]
 
 
 @functools.lru_cache(maxsize=None)
 def _integer_rows():
-    m = np.random.default_rng(7).integers(1, 2 ** 30, size=(1 << 18, 32), dtype=np.int64)
+    m = np.random.default_rng(7).integers(1, 2 ** 30, size=(1 << 18, 39), dtype=np.int64)
     return m, m.astype(np.float64)
 
 
 def _row_counts(nv, whole_workgroup):
     s, b = _subs_batch(nv, whole_workgroup)
-    return sorted({1, s - 1, s, s + 1, s * b - 1, s * b, s * b + 1, 2 * s * b + 3, 1024, 1025, 65_537, 1 << 18})
+    return sorted({1, s - 1, s, s + 1, s * b - 1, s * b, s * b + 1, 2 * s * b - 1, 2 * s * b, 2 * s * b + 3, 3 * s * b + 1, 1024, 1025, 65_537, 1 << 18} - {0})
 
 
 @pytest.mark.parametrize("nv,whole_workgroup", ROW_SUMMERS, ids=[f"{'workgroup' if w else 'wave'}-{nv}" for nv, w in ROW_SUMMERS])
@@ -186,7 +184,7 @@ def _placed(per_value, p):
 
 
 @pytest.mark.parametrize("op", ["sum", "max", "min"])
-@pytest.mark.parametrize("p", [1, 2, 4, 8, 16, 32])
+@pytest.mark.parametrize("p", [1, 2, 4, 8, 16, 32, 64])
 def test_wave_transpose_reduce_places_every_value_index_on_its_lanes(p, op):
     rng = np.random.default_rng(100 * p + len(op))
     # integers: exact whatever the order of the exchanges
@@ -257,6 +255,41 @@ def test_a_rounded_sum_keeps_its_bits_between_neighbours_that_change(nv, blockin
     assert len({out[j, :nv].tobytes() for j in range(0, 400, 2)}) == 1
     assert len({out[j, :nv].tobytes() for j in range(1, 400, 2)}) > 100        # the neighbours did change
     assert [int(x) for x in out[:, nv]] == n
+
+
+# ------------------------------------------------------------------ the LSM chains' hand-over
+@pytest.mark.parametrize("nv", ref.HAND_OVER_NV)
+def test_the_lsm_chains_hand_over_sums_exactly_in_every_workgroup(nv):
+    """Form 3, what lsm_step_kernel and heston_lsm_step_kernel do between two dates: G1 workgroups store block_row_sum<nv> as plain rows,
+    every one of G2 workgroups of the next launch sums all the rows by workgroup_rows_sum<nv>.  G1 = 1, 2, 255, 256, 257, 1024 (the
+    chains' cap), each full, with one live thread in the last workgroup and with one thread missing; G2 = 1, 3, 256: EVERY workgroup's
+    totals equal the integers."""
+    n, salts = ref.hand_over_launches(nv)
+    for g2 in ref.HAND_OVER_G2:
+        for x, salt in zip(n, salts):
+            out = probe.hand_over_probe(nv, x, salt, g2)
+            want = expected(nv, x, salt)
+            assert out.shape == (g2, nv) and np.isfinite(out).all(), (nv, g2, x)
+            assert np.array_equal(out, np.floor(out)), (nv, g2, x, "a total that is not an integer")
+            wrong = [(w, c, int(out[w, c]) - want[c]) for w in range(g2) for c in range(nv) if int(out[w, c]) != want[c]]
+            assert not wrong, (nv, g2, f"n_threads {x} ({ref.workgroups(x)} workgroups), salt {salt:#x}", wrong[:4])
+
+
+@pytest.mark.parametrize("nv", ref.HAND_OVER_NV)
+def test_the_hand_over_s_rounded_totals_are_one_set_of_bits(nv):
+    """values = 1 (sums round): all G2 workgroups hold the same bits, whatever G2 -- the rows are summed in index order by every
+    workgroup -- and they lie within the bound of recursive summation of the correctly rounded sum (as the test above)."""
+    n, salt = 256 * 257 - 3, 0xB_0000_0000 + nv
+    fs, sabs, count = ref.rounded_reference(nv, n, salt)
+    seen = set()
+    for g2 in ref.HAND_OVER_G2:
+        out = probe.hand_over_probe(nv, n, salt, g2, values=1)
+        assert out.shape == (g2, nv) and np.isfinite(out).all()
+        seen |= {out[w].tobytes() for w in range(g2)}
+        for c in range(nv):
+            assert abs(out[0, c] - fs[c]) <= count * 2.0 ** -53 * sabs[c], (nv, g2, c, out[0, c], fs[c])
+    assert len(seen) == 1, (nv, len(seen))
+    assert any(out[0, c] != math.floor(out[0, c]) for c in range(nv))            # the sums did round
 
 
 # ------------------------------------------------------------------ tail and guard

@@ -43,6 +43,8 @@ def _second_binding():
         "olmc_reduce_probe": (_I, [_I, _I, _I, _I, _I32, C.POINTER(_I64), C.POINTER(_U64T), C.POINTER(_D)]),
         "olmc_rows_sum_probe": (_I, [_I, _I, C.POINTER(_D), _I32, C.POINTER(_D)]),
         "olmc_wave_reduce_probe": (_I, [_I, _I, C.POINTER(_D), C.POINTER(_D)]),
+        "olmc_ha_fit_probe": (_I, [_I, C.POINTER(_D), _I32, C.POINTER(_D), C.POINTER(_I32)]),
+        "olmc_lsm_fit_probe": (_I, [_I, C.POINTER(_D), _I32, C.POINTER(_D), C.POINTER(_I32)]),
         "olmc_phase_stamps": (_I, [_I64, _I32, _U64T, _I32, C.POINTER(C.c_uint64), _I64, C.POINTER(_I64)]),
         "olmc_clock_probe": (_I, [_I64, _I32, _U64T, C.POINTER(_D)]),
         "olmc_issue_probe": (_I, [_I, _I, C.POINTER(_D)]),
@@ -55,7 +57,7 @@ def _second_binding():
 
 hip = _second_binding()
 PROBE_PROTOTYPES = ("olmc_exp2_probe", "olmc_exp2_probe_form", "olmc_ndtri_probe", "olmc_box_muller_probe", "olmc_sqrt_nonneg_probe",
-                    "olmc_normal_moments", "olmc_reduce_probe", "olmc_rows_sum_probe", "olmc_wave_reduce_probe", "olmc_phase_stamps", "olmc_clock_probe", "olmc_issue_probe", "olmc_probe_tune",
+                    "olmc_normal_moments", "olmc_reduce_probe", "olmc_rows_sum_probe", "olmc_wave_reduce_probe", "olmc_ha_fit_probe", "olmc_lsm_fit_probe", "olmc_phase_stamps", "olmc_clock_probe", "olmc_issue_probe", "olmc_probe_tune",
                     "olmc_european_f64_normals", "olmc_launch_gap_probe")
 _check, lib, seed64 = hip._check, hip.lib, hip.seed64
 
@@ -122,7 +124,8 @@ def normal_moments(seed: int, n_paths: int, n_steps: int, path_offset: int = 0):
 def reduce_probe(nv: int, form: int, n_threads, salts, values: int = 0, blocking: bool = True) -> np.ndarray:
     """out[launches, nv + 1] of olmc_reduce_probe: the fused grid reduction (form 0 block_then_grid_reduce, 1 the folded first
     exchange, 2 block_row_sum + grid_reduce[_workgroup]) on the synthetic values of tests/reduction_reference.py, one launch per entry
-    of n_threads / salts; the last column is the workspace's tail (= n_threads).  blocking=False queues every launch back to back."""
+    of n_threads / salts; the last column is the workspace's tail (= n_threads).  blocking=False queues every launch back to back.
+    form 3 is hand_over_probe's."""
     n = np.ascontiguousarray(n_threads, dtype=np.int64).ravel()
     s = np.ascontiguousarray(salts, dtype=np.uint64).ravel()
     if n.size != s.size:
@@ -131,6 +134,39 @@ def reduce_probe(nv: int, form: int, n_threads, salts, values: int = 0, blocking
     _check(lib().olmc_reduce_probe(int(nv), int(form), int(values), int(bool(blocking)), n.size, n.ctypes.data_as(C.POINTER(C.c_int64)),
                                    s.ctypes.data_as(C.POINTER(C.c_uint64)), out.ctypes.data_as(C.POINTER(C.c_double))))
     return out
+
+
+def hand_over_probe(nv: int, n_threads: int, salt: int, g2: int, values: int = 0) -> np.ndarray:
+    """out[g2, nv] of olmc_reduce_probe's form 3, the LSM chains' hand-over: ceil(n_threads / 256) workgroups store block_row_sum<nv> of
+    the synthetic values as plain rows, then g2 workgroups each sum all the rows by workgroup_rows_sum<nv>."""
+    n, s = (C.c_int64 * 1)(int(n_threads)), (C.c_uint64 * 1)(int(salt))
+    out = np.full((int(g2), int(nv)), np.nan, dtype=np.float64)
+    _check(lib().olmc_reduce_probe(int(nv), 3, int(values), 0, int(g2), n, s, out.ctypes.data_as(C.POINTER(C.c_double))))
+    return out
+
+
+def _fit_probe(entry, degree: int, totals: np.ndarray, nu: int):
+    totals = np.ascontiguousarray(totals, dtype=np.float64)
+    beta = np.full((totals.shape[0], nu), np.nan, dtype=np.float64)
+    valid = np.full(totals.shape[0], -1, dtype=np.int32)
+    _check(entry(int(degree), totals.ctypes.data_as(C.POINTER(C.c_double)), totals.shape[0], beta.ctypes.data_as(C.POINTER(C.c_double)),
+                 valid.ctypes.data_as(C.POINTER(C.c_int32))))
+    return beta, valid
+
+
+def ha_fit_probe(degree: int, totals: np.ndarray):
+    """(beta[n_sets, NU], valid[n_sets]) of ha_fit<degree> (the Heston American option's in-wave solver) on totals[n_sets, NV]."""
+    nu = (degree + 1) * (degree + 2) // 2
+    if np.ndim(totals) != 2 or np.shape(totals)[1] != (2 * degree + 1) * (degree + 1) + nu + 1:
+        raise ValueError("totals must be [n_sets, NV]")
+    return _fit_probe(lib().olmc_ha_fit_probe, degree, totals, nu)
+
+
+def lsm_fit_probe(degree: int, totals: np.ndarray):
+    """(beta[n_sets, 5], valid[n_sets]) of LsmFit (the one-factor American option's in-wave solver) on totals[n_sets, 16]."""
+    if np.ndim(totals) != 2 or np.shape(totals)[1] != 16:
+        raise ValueError("totals must be [n_sets, 16]")
+    return _fit_probe(lib().olmc_lsm_fit_probe, degree, totals, 5)
 
 
 def rows_sum_probe(rows: np.ndarray, whole_workgroup: bool) -> np.ndarray:

@@ -124,17 +124,53 @@ void launch_reduce_probe(int form, int32_t grid, hipStream_t st, const EventPair
     else if constexpr (NV >= 8) launch_timed(reduce_probe_kernel<NV, 1>, dim3(grid), dim3(kBlock), st, timed, n, salt, values, ws);
 }
 
-// f(integral_constant<int, NV>) for the row widths the product instantiates; false for any other nv.
+// f(integral_constant<int, NV>) for the row widths the product instantiates (10, 22, 39 = HaBasis<D>::NV); false for any other nv.
 template <typename F>
 bool with_reduce_width(int nv, F&& f) {
     switch (nv) {
         case 2: f(std::integral_constant<int, 2>{}); return true;
         case 5: f(std::integral_constant<int, 5>{}); return true;
         case 8: f(std::integral_constant<int, 8>{}); return true;
+        case 10: f(std::integral_constant<int, 10>{}); return true;
         case 16: f(std::integral_constant<int, 16>{}); return true;
+        case 22: f(std::integral_constant<int, 22>{}); return true;
         case 32: f(std::integral_constant<int, 32>{}); return true;
+        case 39: f(std::integral_constant<int, 39>{}); return true;
         default: return false;
     }
+}
+static_assert(HaBasis<1>::NV == 10 && HaBasis<2>::NV == 22 && HaBasis<3>::NV == 39 && kLsmNV == 16, "the widths of the LSM chains' rows");
+
+constexpr int32_t kLsmChainRows = 1024;                      // the chains launch at most this many workgroups (lsm_chain, heston_lsm_chain)
+
+// Form 3: launch 1 = ceil(n / 256) workgroups store their block_row_sum<nv> rows, launch 2 = g2 workgroups each sum all of them
+// (workgroup_rows_sum<nv>), same stream, nothing between them.  Bulk buffer = [rows | out[g2][nv]].
+int reduce_probe_hand_over(int nv, int values, int32_t g2, int64_t n, uint64_t salt, double* out) {
+    if (nv != 10 && nv != 16 && nv != 22 && nv != 39) return fail(OLMC_ERR_ARG, "form 3 (the LSM chains' hand-over) exists for nv 10, 16, 22 and 39");
+    if (n < 1) return fail(OLMC_ERR_ARG, "n_threads must be >= 1");
+    if (n > static_cast<int64_t>(kLsmChainRows) * kBlock) return fail(OLMC_ERR_ARG, "form 3 takes at most 1024 workgroups in its first launch");
+    CtxLease lease;
+    int rc = ctx_lease(&lease);
+    if (rc) return rc;
+    DeviceCtx* const c = lease.c;
+    const int32_t g1 = static_cast<int32_t>((n + kBlock - 1) / kBlock);
+    const size_t n_rows = static_cast<size_t>(g1) * nv, n_out = static_cast<size_t>(g2) * nv;
+    Carver bulk;
+    rc = bulk_reserve(c, sizeof(double) * (n_rows + n_out), &bulk);
+    if (rc) return rc;
+    double* d_rows = bulk.take<double>(n_rows);
+    double* d_out = bulk.take<double>(n_out);
+    HIP_TRY(hipMemsetAsync(d_rows, 0xFF, sizeof(double) * (n_rows + n_out), c->stream));     // NaN wherever a launch writes nothing
+    with_reduce_width(nv, [&](auto width) {
+        if constexpr (width >= 10) {
+            hipLaunchKernelGGL(rows_store_probe_kernel<width>, dim3(g1), dim3(kBlock), 0, c->stream, n, salt, values, d_rows);
+            hipLaunchKernelGGL(rows_total_probe_kernel<width>, dim3(g2), dim3(kBlock), 0, c->stream, d_rows, g1, d_out);
+        }
+    });
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, d_out, sizeof(double) * n_out, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return OLMC_OK;
 }
 }  // namespace
 
@@ -145,11 +181,13 @@ bool with_reduce_width(int nv, F&& f) {
 extern "C" int olmc_reduce_probe(int nv, int form, int values, int blocking, int32_t launches, const int64_t* n_threads, const uint64_t* salt,
                                  double* out) {
     if (!n_threads || !salt || !out) return fail(OLMC_ERR_ARG, "null pointer");
-    if (nv != 2 && nv != 5 && nv != 8 && nv != 16 && nv != 32) return fail(OLMC_ERR_ARG, "nv must be 2, 5, 8, 16 or 32");
-    if (form < 0 || form > 2) return fail(OLMC_ERR_ARG, "form must be 0, 1 or 2");
-    if (form == 1 && nv < 8) return fail(OLMC_ERR_ARG, "form 1 (the folded first exchange) exists for nv 8, 16 and 32");
+    if (form < 0 || form > 3) return fail(OLMC_ERR_ARG, "form must be 0, 1, 2 or 3");
     if ((values != 0 && values != 1) || (blocking != 0 && blocking != 1)) return fail(OLMC_ERR_ARG, "values and blocking must be 0 or 1");
     if (launches < 1 || launches > 4096) return fail(OLMC_ERR_ARG, "launches must be in [1, 4096]");
+    if (form == 3) return reduce_probe_hand_over(nv, values, launches, n_threads[0], salt[0], out);
+    if (nv != 2 && nv != 5 && nv != 8 && nv != 10 && nv != 16 && nv != 22 && nv != 32)
+        return fail(OLMC_ERR_ARG, "nv must be 2, 5, 8, 10, 16, 22 or 32 (39: form 3 only, a workspace row holds 32 values)");
+    if (form == 1 && nv < 8) return fail(OLMC_ERR_ARG, "form 1 (the folded first exchange) exists for nv 8 and wider");
     int64_t most = 0;
     for (int32_t j = 0; j < launches; ++j) {
         if (n_threads[j] < 1) return fail(OLMC_ERR_ARG, "n_threads must be >= 1");
@@ -167,7 +205,9 @@ extern "C" int olmc_reduce_probe(int nv, int form, int values, int blocking, int
         const uint64_t s = salt[j];
         return launch_reduce(c, c->stream, d_out, static_cast<double>(n), nv, grid_of(n),
                              [&](int32_t grid, hipStream_t st, const EventPair* timed, const ReduceWs& ws) {
-                                 with_reduce_width(nv, [&](auto width) { launch_reduce_probe<width>(form, grid, st, timed, n, s, values, ws); });
+                                 with_reduce_width(nv, [&](auto width) {
+                                     if constexpr (width <= kMaxNV) launch_reduce_probe<width>(form, grid, st, timed, n, s, values, ws);
+                                 });
                              });
     };
     if (blocking) {
@@ -197,13 +237,13 @@ extern "C" int olmc_reduce_probe(int nv, int form, int values, int blocking, int
     return OLMC_OK;
 }
 
-// wave_rows_sum<nv> (whole_workgroup = 0: nv 2 or 5, one wave) or workgroup_rows_sum<nv> (1: nv 5, 8, 16 or 32, 256 threads) on a host
+// wave_rows_sum<nv> (whole_workgroup = 0: nv 2 or 5, one wave) or workgroup_rows_sum<nv> (1: nv 5, 8, 10, 16, 22, 32 or 39, 256 threads) on a host
 // matrix [rows][nv]: out_nv[c] = the sum of column c.  Bulk buffer = [matrix | out].
 extern "C" int olmc_rows_sum_probe(int nv, int whole_workgroup, const double* rows_host, int32_t rows, double* out_nv) {
     if (!rows_host || !out_nv) return fail(OLMC_ERR_ARG, "null pointer");
     if (whole_workgroup != 0 && whole_workgroup != 1) return fail(OLMC_ERR_ARG, "whole_workgroup must be 0 or 1");
-    if (whole_workgroup ? (nv != 5 && nv != 8 && nv != 16 && nv != 32) : (nv != 2 && nv != 5))
-        return fail(OLMC_ERR_ARG, "nv must be 2 or 5 for one wave, 5, 8, 16 or 32 for the whole workgroup");
+    if (whole_workgroup ? (nv != 5 && nv != 8 && nv != 10 && nv != 16 && nv != 22 && nv != 32 && nv != 39) : (nv != 2 && nv != 5))
+        return fail(OLMC_ERR_ARG, "nv must be 2 or 5 for one wave, 5, 8, 10, 16, 22, 32 or 39 for the whole workgroup");
     if (rows < 1 || rows > (1 << 20)) return fail(OLMC_ERR_ARG, "rows must be in [1, 2^20]");
     CtxLease lease;
     int rc = ctx_lease(&lease);
@@ -233,7 +273,7 @@ extern "C" int olmc_rows_sum_probe(int nv, int whole_workgroup, const double* ro
 // v[0] afterwards.  Bulk buffer = [v | out].
 extern "C" int olmc_wave_reduce_probe(int p, int op, const double* v_host, double* out) {
     if (!v_host || !out) return fail(OLMC_ERR_ARG, "null pointer");
-    if (p != 1 && p != 2 && p != 4 && p != 8 && p != 16 && p != 32) return fail(OLMC_ERR_ARG, "p must be 1, 2, 4, 8, 16 or 32");
+    if (p != 1 && p != 2 && p != 4 && p != 8 && p != 16 && p != 32 && p != 64) return fail(OLMC_ERR_ARG, "p must be 1, 2, 4, 8, 16, 32 or 64");
     if (op < 0 || op > 2) return fail(OLMC_ERR_ARG, "op must be 0 (sum), 1 (max) or 2 (min)");
     CtxLease lease;
     int rc = ctx_lease(&lease);
@@ -253,7 +293,8 @@ extern "C" int olmc_wave_reduce_probe(int p, int op, const double* v_host, doubl
             case 4: f(std::integral_constant<int, 4>{}); break;
             case 8: f(std::integral_constant<int, 8>{}); break;
             case 16: f(std::integral_constant<int, 16>{}); break;
-            default: f(std::integral_constant<int, 32>{}); break;
+            case 32: f(std::integral_constant<int, 32>{}); break;
+            default: f(std::integral_constant<int, 64>{}); break;     // block_row_sum<39>: SHIFT = 0, every lane ends with a value of its own
         }
     };
     with_p([&](auto width) {
@@ -265,6 +306,52 @@ extern "C" int olmc_wave_reduce_probe(int p, int op, const double* v_host, doubl
     HIP_TRY(hipMemcpyAsync(out, d_out, sizeof(double) * kWave, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return OLMC_OK;
+}
+
+// ---- the in-wave solvers of the LSM chains on chosen totals (ha_fit_probe_kernel, lsm_fit_probe_kernel) ----
+namespace {
+// One workgroup per set: totals_host[n_sets][nv] in, beta_host[n_sets][nu] and valid_host[n_sets] out.  Bulk buffer = [totals | beta | valid].
+template <typename Launch>
+int fit_probe(const double* totals_host, int32_t n_sets, int nv, int nu, double* beta_host, int32_t* valid_host, Launch&& launch) {
+    if (!totals_host || !beta_host || !valid_host) return fail(OLMC_ERR_ARG, "null pointer");
+    if (n_sets < 1 || n_sets > 4096) return fail(OLMC_ERR_ARG, "n_sets must be in [1, 4096]");
+    CtxLease lease;
+    int rc = ctx_lease(&lease);
+    if (rc) return rc;
+    DeviceCtx* const c = lease.c;
+    const size_t n_totals = static_cast<size_t>(n_sets) * nv, n_beta = static_cast<size_t>(n_sets) * nu;
+    Carver bulk;
+    rc = bulk_reserve(c, sizeof(double) * (n_totals + n_beta) + sizeof(int32_t) * static_cast<size_t>(n_sets), &bulk);
+    if (rc) return rc;
+    double* d_totals = bulk.take<double>(n_totals);
+    double* d_beta = bulk.take<double>(n_beta);
+    int32_t* d_valid = bulk.take<int32_t>(n_sets);
+    HIP_TRY(hipMemcpyAsync(d_totals, totals_host, sizeof(double) * n_totals, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(d_beta, 0xFF, sizeof(double) * n_beta + sizeof(int32_t) * static_cast<size_t>(n_sets), c->stream));   // NaN / -1 where nothing is written
+    launch(c->stream, d_totals, d_beta, d_valid);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(beta_host, d_beta, sizeof(double) * n_beta, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(valid_host, d_valid, sizeof(int32_t) * static_cast<size_t>(n_sets), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return OLMC_OK;
+}
+}  // namespace
+
+extern "C" int olmc_ha_fit_probe(int degree, const double* totals_host, int32_t n_sets, double* beta_host, int32_t* valid_host) {
+    if (degree < 1 || degree > kHaMaxDegree) return fail(OLMC_ERR_ARG, "degree must be in [1, 3]");
+    const int nu = (degree + 1) * (degree + 2) / 2, nv = (2 * degree + 1) * (2 * degree + 2) / 2 + nu + 1;
+    return fit_probe(totals_host, n_sets, nv, nu, beta_host, valid_host, [&](hipStream_t st, const double* t, double* b, int32_t* v) {
+        if (degree == 1) hipLaunchKernelGGL(ha_fit_probe_kernel<1>, dim3(n_sets), dim3(kBlock), 0, st, t, b, v);
+        else if (degree == 2) hipLaunchKernelGGL(ha_fit_probe_kernel<2>, dim3(n_sets), dim3(kBlock), 0, st, t, b, v);
+        else hipLaunchKernelGGL(ha_fit_probe_kernel<3>, dim3(n_sets), dim3(kBlock), 0, st, t, b, v);
+    });
+}
+
+extern "C" int olmc_lsm_fit_probe(int degree, const double* totals_host, int32_t n_sets, double* beta_host, int32_t* valid_host) {
+    if (degree < 1 || degree > kLsmMaxDegree) return fail(OLMC_ERR_ARG, "degree must be in [1, 4]");
+    return fit_probe(totals_host, n_sets, kLsmNV, kLsmMaxDegree + 1, beta_host, valid_host, [&](hipStream_t st, const double* t, double* b, int32_t* v) {
+        hipLaunchKernelGGL(lsm_fit_probe_kernel, dim3(n_sets), dim3(kBlock), 0, st, static_cast<int32_t>(degree), t, b, v);
+    });
 }
 
 extern "C" int olmc_normal_moments(uint64_t seed, int64_t path_offset, int64_t n_paths, int32_t n_steps, double* out4) {

@@ -2,6 +2,7 @@
 // into libolmc.so.  They use the product's own device functions (olmc_kernels.h), so what they measure is the product's code.
 #pragma once
 #include "olmc_kernels.h"
+#include "olmc_heston_american_kernels.h"
 
 namespace olmc {
 
@@ -389,6 +390,64 @@ __global__ __launch_bounds__(kWave) void wave_reduce_probe_kernel(const double* 
     for (int k = 0; k < P; ++k) v[k] = v_in[threadIdx.x * P + k];
     wave_transpose_reduce<P, kWave / 2, Op>(v);
     out[threadIdx.x] = v[0];
+}
+
+// FORM 3 of olmc_reduce_probe, the hand-over of the LSM chains (lsm_step_kernel, heston_lsm_step_kernel) in two launches on one stream:
+// every workgroup of the first stores block_row_sum<NV> of the synthetic values as a plain row (the kernel boundary publishes it), every
+// workgroup of the second sums all the rows by workgroup_rows_sum<NV> and stores its totals, out[blockIdx.x][NV].
+template <int NV>
+__global__ __launch_bounds__(kBlock) void rows_store_probe_kernel(int64_t n_threads, uint64_t salt, int values, double* __restrict__ rows) {
+    const uint32_t seed = probe_seed(salt);
+    const bool live = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x < n_threads;
+    double acc[NV];
+#pragma unroll
+    for (int k = 0; k < NV; ++k) acc[k] = reduce_probe_value(seed, blockIdx.x, threadIdx.x, static_cast<uint32_t>(k), live, values);
+    const double s = block_row_sum<NV>(acc);
+    if (threadIdx.x < NV) rows[static_cast<size_t>(blockIdx.x) * NV + threadIdx.x] = s;
+}
+
+template <int NV>
+__global__ __launch_bounds__(kBlock) void rows_total_probe_kernel(const double* __restrict__ rows, int32_t n_rows, double* __restrict__ out) {
+    __shared__ double part[kBlock];
+    const double total = workgroup_rows_sum<NV>(rows, n_rows, part);
+    if (threadIdx.x < NV) out[static_cast<size_t>(blockIdx.x) * NV + threadIdx.x] = total;
+}
+
+// ---------------------------------------------------------------- the in-wave solvers of the LSM chains ----
+// What the `fit` lambda of heston_lsm_step_kernel / lsm_step_kernel does, in that order, on totals the host chose: workgroup blockIdx.x
+// sums the ONE row of its set by workgroup_rows_sum, solves in its first wave (ha_fit<D> / LsmFit), meets the barrier and copies the
+// coefficients out of LDS; thread kBlock - 1 -- in the LAST wave, so the LDS hand-over to another wave is part of what is observed --
+// writes them and `valid`.
+template <int D>
+__global__ __launch_bounds__(kBlock) void ha_fit_probe_kernel(const double* __restrict__ totals /* [gridDim.x][NV] */, double* __restrict__ beta /* [gridDim.x][NU] */,
+                                                              int32_t* __restrict__ valid) {
+    using B = HaBasis<D>;
+    __shared__ double part[kBlock];
+    __shared__ HaCoeffs<D> shared_fit;
+    const double total = workgroup_rows_sum<B::NV>(totals + static_cast<size_t>(blockIdx.x) * B::NV, 1, part);
+    if (threadIdx.x < kWave) ha_fit<D>(&shared_fit, total);
+    __syncthreads();
+    const HaCoeffs<D> f = shared_fit;
+    if (threadIdx.x == kBlock - 1) {
+#pragma unroll
+        for (int k = 0; k < B::NU; ++k) beta[static_cast<size_t>(blockIdx.x) * B::NU + k] = f.beta[k];
+        valid[blockIdx.x] = f.valid;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void lsm_fit_probe_kernel(int32_t degree, const double* __restrict__ totals /* [gridDim.x][kLsmNV] */,
+                                                               double* __restrict__ beta /* [gridDim.x][kLsmMaxDegree + 1] */, int32_t* __restrict__ valid) {
+    __shared__ double part[kBlock];
+    __shared__ LsmCoeffs shared_fit;
+    const double total = workgroup_rows_sum<kLsmNV>(totals + static_cast<size_t>(blockIdx.x) * kLsmNV, 1, part);
+    if (threadIdx.x < kWave) LsmFit{&shared_fit, degree}(total);
+    __syncthreads();
+    const LsmCoeffs f = shared_fit;
+    if (threadIdx.x == kBlock - 1) {
+#pragma unroll
+        for (int k = 0; k <= kLsmMaxDegree; ++k) beta[static_cast<size_t>(blockIdx.x) * (kLsmMaxDegree + 1) + k] = f.beta[k];
+        valid[blockIdx.x] = f.valid;
+    }
 }
 
 // ---------------------------------------------------------------- the price of the reference's own width (round 4) ----
