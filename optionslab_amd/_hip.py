@@ -57,6 +57,11 @@ class LvSurface(C.Structure):
                 ("t_hi", C.c_double)]
 
 
+class SabrModel(C.Structure):
+    """olsb_model (include/olmc_sabr.h): alpha = sigma_0, beta the CEV exponent, rho the correlation, nu the volatility of volatility."""
+    _fields_ = [("alpha", C.c_double), ("beta", C.c_double), ("rho", C.c_double), ("nu", C.c_double)]
+
+
 class JdModel(C.Structure):
     """oljd_model (include/olmc_jump.h): Merton (a1, a2) = (mu_j, sigma_j), Kou (a1, a2, a3) = (p, eta1, eta2)."""
     _fields_ = [("model", C.c_int32), ("pad", C.c_int32), ("lambda_j", C.c_double), ("a1", C.c_double), ("a2", C.c_double), ("a3", C.c_double)]
@@ -200,6 +205,16 @@ JS_PROTOTYPES = {
     "oljs_greeks_fd": (_I, _SIX + [_I, _JDM, _I64, _I32, _U64T, _I, _I] + _GREEKS),
 }
 
+# and for include/olmc_sabr.h (prefix olsb_)
+SABR_EUROPEAN = 8
+STREAM_SABR = 0x53414252           # OLMC_STREAM_SABR: counter word 3 of the SABR paths' Philox blocks
+_SBM = C.POINTER(SabrModel)
+SABR_PROTOTYPES = {
+    "olsb_price": (_I, [_D] * 4 + [_I, _SBM, _I, _D] + _RANGE),
+    "olsb_paths": (_I, [_D] * 2 + [_SBM, _I64, _I32, _U64T, _I, _I, _DP, _DP]),
+    "olsb_surface_prices": (_I, [_D] * 3 + [_I, _SBM] + _CELLS + _RANGE),
+}
+
 # and for include/olha.h (prefix olha_)
 HA_BASIS_SPOT_VARIANCE, HA_BASIS_SPOT = 0, 1
 HA_PROTOTYPES = {
@@ -251,7 +266,8 @@ def load_library() -> C.CDLL:
             except OSError as e:
                 raise AccelerationError(f"cannot load {LIBRARY_PATH}: {e}", backend="hip") from e
             for name, (res, args) in (list(PROTOTYPES.items()) + list(LV_PROTOTYPES.items()) + list(LVQ_PROTOTYPES.items())
-                                      + list(JD_PROTOTYPES.items()) + list(JS_PROTOTYPES.items()) + list(HA_PROTOTYPES.items())):
+                                      + list(JD_PROTOTYPES.items()) + list(JS_PROTOTYPES.items()) + list(HA_PROTOTYPES.items())
+                                      + list(SABR_PROTOTYPES.items())):
                 try:
                     fn = getattr(lib, name)
                 except AttributeError:
@@ -909,6 +925,36 @@ def jd_paths(S, T, r, sigma, q, model, n_paths: int, n_steps: int, seed: int, mi
     out = _path_matrix(n_paths, n_steps, path_major)
     _check(lib().oljd_paths(S, T, r, sigma, q, _byref(m), int(n_paths), int(n_steps), seed64(seed), int(bool(mirror)), int(path_major), _dp(out)))
     return out
+
+
+def sabr_model(alpha, beta, rho, nu) -> SabrModel:
+    return SabrModel(float(alpha), float(beta), float(rho), float(nu))
+
+
+def sabr_price(F, K, T, r, is_call: bool, model, payoff: int, barrier: float, n_paths: int, n_steps: int, seed: int, antithetic: bool = False,
+               path_offset: int = 0) -> Stats:
+    """One payoff (BARRIER_KINDS value, LOOKBACK_*, PATH_ASIAN_* or SABR_EUROPEAN) on SABR paths of the forward, one launch (olsb_price);
+    `model` = (alpha, beta, rho, nu)."""
+    m = sabr_model(*model)
+    return _answer(lib().olsb_price(F, K, T, r, int(is_call), _byref(m), int(payoff), float(barrier), int(path_offset), int(n_paths), int(n_steps),
+                                    seed64(seed), int(antithetic), _byref(out := Stats())), out)
+
+
+def sabr_paths(F, T, model, n_paths: int, n_steps: int, seed: int, mirror: bool = False, path_major: bool = False):
+    """Forward and volatility at dates 0 .. n_steps of one leg of sabr_price's paths (olsb_paths; date 0 = (F, alpha)); layouts as
+    gbm_paths."""
+    m = sabr_model(*model)
+    return _spot_and_variance(lib().olsb_paths, n_paths, n_steps, path_major, F, T, _byref(m), int(n_paths), int(n_steps), seed64(seed),
+                              int(bool(mirror)))
+
+
+def sabr_surface_prices(F, T, r, is_call: bool, model, strikes, steps, n_paths: int, n_steps: int, seed: int, antithetic: bool = False,
+                        path_offset: int = 0) -> List[Stats]:
+    """European options at the cells (strikes[i], steps[i]) on sabr_price's paths, one launch (olsb_surface_prices): at most 16 cells."""
+    m = sabr_model(*model)
+    cells = _SurfaceCells(strikes, steps)
+    return cells.answer(lib().olsb_surface_prices(F, T, r, int(is_call), _byref(m), *cells.run, int(path_offset), int(n_paths), int(n_steps),
+                                                  seed64(seed), int(antithetic), cells.out))
 
 
 def _jd_scenarios(scenarios):

@@ -26,6 +26,7 @@ from . import heston as _heston
 from . import jump_diffusion as _jump
 from . import local_vol as _lv
 from . import monte_carlo as _mc
+from . import sabr as _sabr
 from . import monte_carlo_unified as _uni
 from . import simulation as _sim
 
@@ -38,7 +39,7 @@ _MISSING = object()
 _PACKAGE_EXPORTS = {
     "src.pricing_models": ["src.pricing_models.monte_carlo", "src.pricing_models.monte_carlo_unified", "src.pricing_models.black_scholes",
                            "src.pricing_models.exotic_options", "src.pricing_models.heston", "src.pricing_models.jump_diffusion",
-                           "src.pricing_models.iv_solver"],
+                           "src.pricing_models.iv_solver", "src.pricing_models.sabr"],
     "src.greeks": ["src.greeks.unified_greeks"],
     "src.exceptions": ["src.exceptions.montecarlo_exceptions", "src.exceptions.greek_exceptions"],
 }
@@ -81,6 +82,7 @@ def _targets() -> dict:
         "src.pricing_models.iv_solver": _module("src.pricing_models.iv_solver", implied_volatility=_implied_volatility),
         "src.pricing_models.jump_diffusion": _module("src.pricing_models.jump_diffusion", MertonJumpDiffusion=_jump.MertonJumpDiffusion,
                                                      KouJumpDiffusion=_jump.KouJumpDiffusion),
+        "src.pricing_models.sabr": _module("src.pricing_models.sabr", SABRModel=_sabr.SABRModel, calibrate_sabr=_sabr.calibrate_sabr),
         # not re-exported by src/pricing_models/__init__.py: reached by its module path only, as in the reference
         "src.pricing_models.local_vol": _module("src.pricing_models.local_vol", DupireLocalVol=_lv.DupireLocalVol, LocalVolSurface=_lv.LocalVolSurface,
                                                 create_sample_iv_surface=_lv.create_sample_iv_surface),
@@ -88,7 +90,7 @@ def _targets() -> dict:
         "src.greeks.unified_greeks": _module("src.greeks.unified_greeks", compute_greeks_unified=_greeks.compute_greeks_unified,
                                              PricerProtocol=_greeks.PricerProtocol, ExoticAdapter=_greeks.ExoticAdapter,
                                              HestonAdapter=_heston.HestonAdapter, JumpDiffusionAdapter=_jump.JumpDiffusionAdapter,
-                                             greeks_heston=_heston.greeks_heston),
+                                             greeks_heston=_heston.greeks_heston, SABRAdapter=_sabr.SABRAdapter, greeks_sabr=_sabr.greeks_sabr),
         "src.exceptions.montecarlo_exceptions": _module("src.exceptions.montecarlo_exceptions", MonteCarloError=_exc.MonteCarloError,
                                                         InputValidationError=_exc.InputValidationError, ConvergenceError=_exc.ConvergenceError,
                                                         AccelerationError=_exc.AccelerationError),

@@ -9,11 +9,13 @@
 #include "olmc_local_vol.h"
 #include "olmc_local_vol_qmc.h"
 #include "olmc_jump.h"
+#include "olmc_sabr.h"
 #include "olha.h"
 #include "olmc_kernels.h"
 #include "olmc_local_vol_kernels.h"
 #include "olmc_local_vol_qmc_kernels.h"
 #include "olmc_jump_kernels.h"
+#include "olmc_sabr_kernels.h"
 #include "olmc_jump_scenario_kernels.h"
 #include "olmc_heston_american_kernels.h"
 #include "olmc_job_board.h"
@@ -2878,6 +2880,116 @@ extern "C" int ollv_surface_prices(double S, double T, double r, double q, int i
                               [&](int32_t grid, hipStream_t st, const EventPair* timed, const PathRange& pr, const HestonSurfaceCells& cells,
                                   const ReduceWs& ws) {
         with_bool(antithetic != 0, [&](auto a) { lv_launch(lv_surface_kernel<a>, m, true, grid, st, timed, pr, m, sign, cells, ws); });
+    });
+}
+
+// ====================================================== SABR ====
+// include/olmc_sabr.h: the payoffs of olmc_heston_path_payoff, the two path matrices and a surface of Europeans on paths of the SABR
+// process (olmc_sabr_kernels.h).  Every check comes before the lease; the kernel is picked by beta's kind.
+namespace {
+static_assert(kTagSabr == OLMC_STREAM_SABR, "the kernels' tag is the header's");
+
+int sabr_check(const olsb_model* m, double F) {
+    if (!m) return fail(OLMC_ERR_ARG, "null pointer");
+    if (m->alpha <= 0.0) return fail(OLMC_ERR_ARG, "alpha must be positive");
+    if (!(m->beta >= 0.0 && m->beta <= 1.0)) return fail(OLMC_ERR_ARG, "beta must be in [0, 1]");
+    if (!(m->rho >= -1.0 && m->rho <= 1.0)) return fail(OLMC_ERR_ARG, "rho must be in [-1, 1]");
+    if (m->nu < 0.0) return fail(OLMC_ERR_ARG, "nu must be non-negative");
+    if (F <= 0.0) return fail(OLMC_ERR_ARG, "F must be positive");
+    return OLMC_OK;
+}
+
+bool sabr_poisoned(double F, double K, double T, double r, const olsb_model* m) {
+    return poisoned(F, K, T, r, 0.0, 0.0) || std::isnan(m->alpha + m->beta + m->rho + m->nu);
+}
+
+SabrModel make_sabr(double F, double T, const olsb_model* m, int32_t n_steps) {
+    const double dt = T / n_steps, unit = std::sqrt(dt) * kZScale;
+    SabrModel sm;
+    sm.f0 = F;
+    sm.log_f0 = std::log(F);
+    sm.alpha = m->alpha;
+    sm.beta = m->beta;
+    sm.half_dt = 0.5 * dt;
+    sm.vol_unit = unit;
+    sm.a = m->nu * m->rho * unit;
+    sm.b = m->nu * std::sqrt(1.0 - m->rho * m->rho) * unit;
+    sm.c = -0.5 * m->nu * m->nu * dt;
+    return sm;
+}
+
+// f(integral_constant<int, kind>) for the kernel of beta: the three special exponents by exact equality, otherwise the general one.
+template <typename F>
+void with_sabr_kind(double beta, F&& f) {
+    if (beta == 1.0) f(std::integral_constant<int, kSabrLognormal>{});
+    else if (beta == 0.5) f(std::integral_constant<int, kSabrHalf>{});
+    else if (beta == 0.0) f(std::integral_constant<int, kSabrNormal>{});
+    else f(std::integral_constant<int, kSabrGeneral>{});
+}
+}  // namespace
+
+extern "C" int olsb_price(double F, double K, double T, double r, int is_call, const olsb_model* m, int payoff, double barrier, int64_t path_offset,
+                          int64_t n_local, int32_t n_steps, uint64_t seed, int antithetic, olmc_stats* out) {
+    if (!out) return fail(OLMC_ERR_ARG, "null pointer");
+    int rc = sabr_check(m, F);
+    if (rc) return rc;
+    rc = path_payoff_check(payoff, barrier, OLSB_EUROPEAN);
+    if (rc) return rc;
+    rc = check_paths(path_offset, n_local, n_steps);
+    if (rc) return rc;
+    const SabrModel sm = make_sabr(F, T, m, n_steps);
+    const PathPayoff pp = path_payoff(F, K, is_call, payoff, barrier);
+    const bool bad = sabr_poisoned(F, K, T, r, m) || pp.nan_barrier;
+    const double inv_steps = 1.0 / n_steps;
+    return run_structured(path_offset, n_local, n_steps, seed, antithetic, r, T, bad, out,
+                          [&](int32_t grid, hipStream_t st, const EventPair* timed, const PathRange& pr, const ReduceWs& ws) {
+                              with_path_family(payoff, OLSB_EUROPEAN, [&](auto f) {
+                                  with_sabr_kind(m->beta, [&](auto b) {
+                                      with_bool(antithetic != 0, [&](auto a) {
+                                          launch_timed(sabr_price_kernel<f, b, a>, dim3(grid), dim3(kBlock), st, timed, pr, sm, pp.ec, inv_steps, ws);
+                                      });
+                                  });
+                              });
+                          });
+}
+
+extern "C" int olsb_paths(double F, double T, const olsb_model* m, int64_t n_paths, int32_t n_steps, uint64_t seed, int mirror, int path_major,
+                          double* forward_host, double* vol_host) {
+    if (!forward_host || !vol_host) return fail(OLMC_ERR_ARG, "null pointer");
+    int rc = sabr_check(m, F);
+    if (rc) return rc;
+    const double bytes = 8.0 * static_cast<double>(n_paths) * (n_steps + 1.0);
+    CtxLease lease;
+    rc = matrix_prologue(n_paths, n_steps, 2 * bytes, "path matrices would exceed 64 GB", &lease);
+    if (rc) return rc;
+    DeviceCtx* const c = lease.c;
+    const SabrModel sm = make_sabr(F, T, m, n_steps);
+    const PathRange pr = make_range(0, n_paths, n_steps, seed);
+    const double flip = mirror ? -1.0 : 1.0;
+    return heston_path_matrices(c, n_paths, n_steps, forward_host, vol_host, [&](const EventPair* timed, double* d_forward, double* d_vol) {
+        with_sabr_kind(m->beta, [&](auto b) {
+            with_bool(path_major != 0, [&](auto pm) {
+                launch_timed(sabr_paths_kernel<b, pm>, dim3(grid_for(n_paths)), dim3(kBlock), c->stream, timed, pr, sm, flip, d_forward, d_vol);
+            });
+        });
+    });
+}
+
+extern "C" int olsb_surface_prices(double F, double T, double r, int is_call, const olsb_model* m, const double* strikes, const int32_t* steps,
+                                   int32_t k, int64_t path_offset, int64_t n_local, int32_t n_steps, uint64_t seed, int antithetic, olmc_stats* out) {
+    if (!strikes || !steps || !out) return fail(OLMC_ERR_ARG, "null pointer");
+    const int rc = sabr_check(m, F);
+    if (rc) return rc;
+    const double sign = is_call ? 1.0 : -1.0;
+    return run_philox_surface(strikes, steps, k, {path_offset, n_local, n_steps, seed, antithetic}, r, T, sabr_poisoned(F, 0.0, T, r, m), out, no_setup,
+                              [&](int32_t grid, hipStream_t st, const EventPair* timed, const PathRange& pr, const HestonSurfaceCells& cells,
+                                  const ReduceWs& ws) {
+        const SabrModel sm = make_sabr(F, T, m, n_steps);
+        with_sabr_kind(m->beta, [&](auto b) {
+            with_bool(antithetic != 0, [&](auto a) {
+                launch_timed(sabr_surface_kernel<b, a>, dim3(grid), dim3(kBlock), st, timed, pr, sm, sign, cells, ws);
+            });
+        });
     });
 }
 

@@ -2301,13 +2301,13 @@ __device__ __forceinline__ Words4 heston_words(uint32_t g_lo, uint32_t g_hi, int
     return philox4x32_10(g_lo, g_hi, static_cast<uint32_t>(block), tag, k.k0, k.k1);
 }
 
-// Steps t = 0 .. last - 1 of a path on the Euler stream, one block for two steps: body(t, z1, z2, advance) with the step's RAW
-// normals; advance = false where heston_start took the step.
-template <typename Keys, typename Body>
+// Steps t = 0 .. last - 1 of a path on a stream that spends one block on two steps (TAG = kTagHeston: the Euler stream; kTagSabr:
+// olmc_sabr_kernels.h): body(t, z1, z2, advance) with the step's RAW normals; advance = false where heston_start took the step.
+template <uint32_t TAG, typename Keys, typename Body>
 __device__ __forceinline__ void heston_philox_walk(uint32_t g_lo, uint32_t g_hi, const Keys& keys, int32_t last, bool skip0, Body body) {
     const int32_t blocks = (last + 1) >> 1;
     for (int32_t b = 0; b < blocks; ++b) {
-        const Words4 w = heston_words(g_lo, g_hi, b, kTagHeston, keys);
+        const Words4 w = heston_words(g_lo, g_hi, b, TAG, keys);
         float z[4];
         box_muller_raw(w.x0, w.x1, z[0], z[1]);
         box_muller_raw(w.x2, w.x3, z[2], z[3]);
@@ -2363,7 +2363,7 @@ __global__ __launch_bounds__(kBlock) void heston_paths_kernel(PathRange pr, Hest
         double ls[2] = {c.log_s0, c.log_s0}, v[2] = {v_start, v_start};       // leg 0 only; ls WITHOUT the (r - q) dt terms: added per date below
         spot[path_at<PATH_MAJOR>(i, 0, pr.count, pr.n_steps)] = s_first;
         var[path_at<PATH_MAJOR>(i, 0, pr.count, pr.n_steps)] = c.v0;
-        heston_philox_walk(g_lo, g_hi, LaunchKeys{pr.key0, pr.key1}, pr.n_steps, skip0, [&](int32_t t, double z1, double z2, bool advance) {
+        heston_philox_walk<kTagHeston>(g_lo, g_hi, LaunchKeys{pr.key0, pr.key1}, pr.n_steps, skip0, [&](int32_t t, double z1, double z2, bool advance) {
             if (advance) hs.legs<false>(z1, z2, ls, v);
             const size_t at = path_at<PATH_MAJOR>(i, t + 1, pr.count, pr.n_steps);
             spot[at] = exp(__builtin_fma(static_cast<double>(t + 1), c.mu_dt, ls[0]));
@@ -4016,6 +4016,20 @@ struct SurfaceRows {
         double s[LEGS];
 #pragma unroll
         for (int leg = 0; leg < LEGS; ++leg) s[leg] = exp(__builtin_fma(static_cast<double>(date), mu_dt, ls[leg]));
+        read_out_cells<LEGS>(next, pending, date, sign, s, live);
+    }
+    // The same for a kernel whose state is the price itself (SABR with beta < 1: olmc_sabr_kernels.h): the date's spots as they stand.
+    template <int LEGS>
+    __device__ __forceinline__ void read_out_linear(int32_t& next, int32_t& pending, int32_t date, double sign, const double (&f)[2], bool live) const {
+        if (date != pending) return;
+        double s[LEGS];
+#pragma unroll
+        for (int leg = 0; leg < LEGS; ++leg) s[leg] = f[leg];
+        read_out_cells<LEGS>(next, pending, date, sign, s, live);
+    }
+    // Every cell pending at `date` takes max(sign (s - strike), 0) per leg of the date's spots s.
+    template <int LEGS>
+    __device__ __forceinline__ void read_out_cells(int32_t& next, int32_t& pending, int32_t date, double sign, const double (&s)[LEGS], bool live) const {
         int32_t nx = __builtin_amdgcn_readfirstlane(next);
         do {
             const double strike_nx = strike[nx];
@@ -4751,7 +4765,7 @@ __global__ __launch_bounds__(kBlock) void heston_product_kernel(PathRange pr, He
     const int32_t last = Product<ANTI>::last(pc, pr.n_steps);
     for_each_path(pr, [&](int64_t, uint32_t g_lo, uint32_t g_hi) {
         p.start(pc, v_start);
-        heston_philox_walk(g_lo, g_hi, rk, last, skip0, [&](int32_t t, double z1, double z2, bool advance) {
+        heston_philox_walk<kTagHeston>(g_lo, g_hi, rk, last, skip0, [&](int32_t t, double z1, double z2, bool advance) {
             if (advance) hs.legs<ANTI>(z1, z2, p.ls, p.v);
             p.date(pc, t);
         });
