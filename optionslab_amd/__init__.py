@@ -12,7 +12,7 @@ from .greeks import ExoticAdapter, PricerProtocol, compute_greeks_unified
 from .heston import HestonAdapter, HestonMCAdapter, HestonPricer, calibrate_heston, greeks_heston, greeks_heston_monte_carlo
 from .local_vol import DupireLocalVol, DupireLocalVolQMC, LocalVolSurface, create_sample_iv_surface
 from .jump_diffusion import JumpDiffusionAdapter, JumpMCAdapter, KouJumpDiffusion, MertonJumpDiffusion, greeks_jump_monte_carlo
-from .sabr import SABRAdapter, SABRMCAdapter, SABRModel, calibrate_sabr, greeks_sabr
+from .sabr import SABRAdapter, SABRMCAdapter, SABRModel, SABRModelQMC, calibrate_sabr, greeks_sabr
 from .monte_carlo import NUMBA_AVAILABLE, MCMethod, MCResult, MonteCarloPricer
 from .monte_carlo_unified import MonteCarloPricerUni
 from .simulation import (hip_available, simulate_gbm_hip, simulate_gbm_hip_fast, simulate_gbm_paths_hip,
@@ -25,7 +25,7 @@ __all__ = [
     "MonteCarloPricer", "MonteCarloPricerUni", "MCMethod", "MCResult", "NUMBA_AVAILABLE", "compute_greeks_unified", "PricerProtocol",
     "ExoticAdapter", "HestonPricer", "HestonAdapter", "HestonMCAdapter", "greeks_heston", "greeks_heston_monte_carlo", "calibrate_heston", "implied_volatility", "MertonJumpDiffusion", "KouJumpDiffusion", "JumpDiffusionAdapter", "JumpMCAdapter", "greeks_jump_monte_carlo", "AsianOption", "BarrierOption", "LookbackOption", "AmericanOption", "price_american", "AutocallableOption", "CliquetOption", "price_asian", "price_barrier", "black_scholes", "simulate_gbm_hip", "simulate_gbm_hip_fast", "simulate_gbm_paths_hip", "simulate_gbm_qmc_hip", "simulate_gbm_qmc_antithetic_hip", "simulate_gbm_qmc_paths_hip",
     "DupireLocalVol", "DupireLocalVolQMC", "LocalVolSurface", "create_sample_iv_surface",
-    "SABRModel", "calibrate_sabr", "SABRAdapter", "SABRMCAdapter", "greeks_sabr",
+    "SABRModel", "SABRModelQMC", "calibrate_sabr", "SABRAdapter", "SABRMCAdapter", "greeks_sabr",
     "hip_available", "MonteCarloError", "InputValidationError", "ConvergenceError", "AccelerationError", "GreeksError",
 ]
 

@@ -215,6 +215,13 @@ SABR_PROTOTYPES = {
     "olsb_surface_prices": (_I, [_D] * 3 + [_I, _SBM] + _CELLS + _RANGE),
 }
 
+# and for include/olmc_sabr_qmc.h (prefix olsq_: SABR_PROTOTYPES stays as it is)
+SABRQ_PROTOTYPES = {
+    "olsq_price": (_I, [_D] * 4 + [_I, _SBM, _I, _D, _I] + _POINTS + [_I, _STATS]),
+    "olsq_paths": (_I, [_D] * 2 + [_SBM, _I, _I64] + _SOBOL + [_I, _I, _DP, _DP]),
+    "olsq_surface_prices": (_I, [_D] * 3 + [_I, _SBM] + _CELLS + [_I] + _POINTS + [_I, _STATS]),
+}
+
 # and for include/olha.h (prefix olha_)
 HA_BASIS_SPOT_VARIANCE, HA_BASIS_SPOT = 0, 1
 HA_PROTOTYPES = {
@@ -267,7 +274,7 @@ def load_library() -> C.CDLL:
                 raise AccelerationError(f"cannot load {LIBRARY_PATH}: {e}", backend="hip") from e
             for name, (res, args) in (list(PROTOTYPES.items()) + list(LV_PROTOTYPES.items()) + list(LVQ_PROTOTYPES.items())
                                       + list(JD_PROTOTYPES.items()) + list(JS_PROTOTYPES.items()) + list(HA_PROTOTYPES.items())
-                                      + list(SABR_PROTOTYPES.items())):
+                                      + list(SABR_PROTOTYPES.items()) + list(SABRQ_PROTOTYPES.items())):
                 try:
                     fn = getattr(lib, name)
                 except AttributeError:
@@ -955,6 +962,35 @@ def sabr_surface_prices(F, T, r, is_call: bool, model, strikes, steps, n_paths: 
     cells = _SurfaceCells(strikes, steps)
     return cells.answer(lib().olsb_surface_prices(F, T, r, int(is_call), _byref(m), *cells.run, int(path_offset), int(n_paths), int(n_steps),
                                                   seed64(seed), int(antithetic), cells.out))
+
+
+def sabrq_price(F, K, T, r, is_call: bool, model, payoff: int, barrier: float, n_points: int, sv: np.ndarray, shift: np.ndarray,
+                bridge: bool = True, antithetic: bool = False, point_offset: int = 0) -> Stats:
+    """sabr_price on scrambled-Sobol paths (olsq_price): n_steps = sv.shape[0] / 2 steps, two dimensions each; sv / shift as heston_qmc."""
+    sobol = _sobol_args(sv, shift, point_offset, n_points, 2)
+    m = sabr_model(*model)
+    return _answer(lib().olsq_price(F, K, T, r, int(is_call), _byref(m), int(payoff), float(barrier), _construction(bridge), int(point_offset),
+                                    int(n_points), *sobol.run, int(antithetic), _byref(out := Stats())), out)
+
+
+def sabrq_paths(F, T, model, n_points: int, sv: np.ndarray, shift: np.ndarray, bridge: bool = True, mirror: bool = False,
+                path_major: bool = False):
+    """Forward and volatility at dates 0 .. n_steps = sv.shape[0] / 2 of one leg of sabrq_price's points [0, n_points) (olsq_paths; date
+    0 = (F, alpha)); layouts as gbm_paths."""
+    sobol = _sobol_args(sv, shift, 0, n_points, 2)
+    m = sabr_model(*model)
+    return _spot_and_variance(lib().olsq_paths, n_points, sobol.steps, path_major, F, T, _byref(m), _construction(bridge), int(n_points), *sobol.run,
+                              int(bool(mirror)))
+
+
+def sabrq_surface_prices(F, T, r, is_call: bool, model, strikes, steps, n_points: int, sv: np.ndarray, shift: np.ndarray, bridge: bool = True,
+                         antithetic: bool = False, point_offset: int = 0) -> List[Stats]:
+    """sabr_surface_prices on sabrq_price's points (olsq_surface_prices): sv.shape[0] / 2 steps to T, at most 16 cells."""
+    sobol = _sobol_args(sv, shift, point_offset, n_points, 2)
+    m = sabr_model(*model)
+    cells = _SurfaceCells(strikes, steps)
+    return cells.answer(lib().olsq_surface_prices(F, T, r, int(is_call), _byref(m), *cells.run, _construction(bridge), int(point_offset), int(n_points),
+                                                  *sobol.run, int(antithetic), cells.out))
 
 
 def _jd_scenarios(scenarios):

@@ -12,6 +12,7 @@ HEADERS = [os.path.join(PKG, "csrc", "olmc_kernels.h"), os.path.join(PKG, "csrc"
            os.path.join(PKG, "csrc", "olmc_local_vol_kernels.h"), os.path.join(PKG, "csrc", "olmc_local_vol_qmc_kernels.h"),
            os.path.join(PKG, "csrc", "olmc_jump_kernels.h"), os.path.join(ROOT, "include", "olmc_jump.h"),
            os.path.join(PKG, "csrc", "olmc_sabr_kernels.h"), os.path.join(ROOT, "include", "olmc_sabr.h"),
+           os.path.join(PKG, "csrc", "olmc_sabr_qmc_kernels.h"), os.path.join(ROOT, "include", "olmc_sabr_qmc.h"),
            os.path.join(PKG, "csrc", "olmc_jump_scenario_kernels.h"), os.path.join(ROOT, "include", "olmc_jump_scenarios.h"),
            os.path.join(PKG, "csrc", "olmc_heston_american_kernels.h"), os.path.join(ROOT, "include", "olha.h"),
            os.path.join(ROOT, "include", "olmc.h"), os.path.join(ROOT, "include", "olmc_local_vol.h"), os.path.join(ROOT, "include", "olmc_local_vol_qmc.h")]

@@ -10,6 +10,7 @@
 #include "olmc_local_vol_qmc.h"
 #include "olmc_jump.h"
 #include "olmc_sabr.h"
+#include "olmc_sabr_qmc.h"
 #include "olha.h"
 #include "olmc_kernels.h"
 #include "olmc_local_vol_kernels.h"
@@ -18,6 +19,7 @@
 #include "olmc_sabr_kernels.h"
 #include "olmc_jump_scenario_kernels.h"
 #include "olmc_heston_american_kernels.h"
+#include "olmc_sabr_qmc_kernels.h"
 #include "olmc_job_board.h"
 #include "olmc_device_mem.h"
 
@@ -2903,8 +2905,9 @@ bool sabr_poisoned(double F, double K, double T, double r, const olsb_model* m) 
     return poisoned(F, K, T, r, 0.0, 0.0) || std::isnan(m->alpha + m->beta + m->rho + m->nu);
 }
 
-SabrModel make_sabr(double F, double T, const olsb_model* m, int32_t n_steps) {
-    const double dt = T / n_steps, unit = std::sqrt(dt) * kZScale;
+// z_unit: what one unit of the kernel's normals is worth -- kZScale for the Philox kernels' RAW normals, 1 for the Sobol kernels' true ones.
+SabrModel make_sabr(double F, double T, const olsb_model* m, int32_t n_steps, double z_unit) {
+    const double dt = T / n_steps, unit = std::sqrt(dt) * z_unit;
     SabrModel sm;
     sm.f0 = F;
     sm.log_f0 = std::log(F);
@@ -2937,7 +2940,7 @@ extern "C" int olsb_price(double F, double K, double T, double r, int is_call, c
     if (rc) return rc;
     rc = check_paths(path_offset, n_local, n_steps);
     if (rc) return rc;
-    const SabrModel sm = make_sabr(F, T, m, n_steps);
+    const SabrModel sm = make_sabr(F, T, m, n_steps, kZScale);
     const PathPayoff pp = path_payoff(F, K, is_call, payoff, barrier);
     const bool bad = sabr_poisoned(F, K, T, r, m) || pp.nan_barrier;
     const double inv_steps = 1.0 / n_steps;
@@ -2963,7 +2966,7 @@ extern "C" int olsb_paths(double F, double T, const olsb_model* m, int64_t n_pat
     rc = matrix_prologue(n_paths, n_steps, 2 * bytes, "path matrices would exceed 64 GB", &lease);
     if (rc) return rc;
     DeviceCtx* const c = lease.c;
-    const SabrModel sm = make_sabr(F, T, m, n_steps);
+    const SabrModel sm = make_sabr(F, T, m, n_steps, kZScale);
     const PathRange pr = make_range(0, n_paths, n_steps, seed);
     const double flip = mirror ? -1.0 : 1.0;
     return heston_path_matrices(c, n_paths, n_steps, forward_host, vol_host, [&](const EventPair* timed, double* d_forward, double* d_vol) {
@@ -2984,13 +2987,97 @@ extern "C" int olsb_surface_prices(double F, double T, double r, int is_call, co
     return run_philox_surface(strikes, steps, k, {path_offset, n_local, n_steps, seed, antithetic}, r, T, sabr_poisoned(F, 0.0, T, r, m), out, no_setup,
                               [&](int32_t grid, hipStream_t st, const EventPair* timed, const PathRange& pr, const HestonSurfaceCells& cells,
                                   const ReduceWs& ws) {
-        const SabrModel sm = make_sabr(F, T, m, n_steps);
+        const SabrModel sm = make_sabr(F, T, m, n_steps, kZScale);
         with_sabr_kind(m->beta, [&](auto b) {
             with_bool(antithetic != 0, [&](auto a) {
                 launch_timed(sabr_surface_kernel<b, a>, dim3(grid), dim3(kBlock), st, timed, pr, sm, sign, cells, ws);
             });
         });
     });
+}
+
+// ====================================================== SABR on Sobol paths ====
+// include/olmc_sabr_qmc.h: the three entry points above on scrambled-Sobol points (olmc_sabr_qmc_kernels.h).  The checks are those of
+// both sides, from their helpers, in the header's order: pointers, the model and F, the payoff, then the construction, tables and
+// points as olmc_heston_qmc (two dimensions per step), then the cells -- all before the lease.  The launches take the shape of a
+// Heston price launch (heston_qmc_shape: the bridge's [2 n][64] slabs) and the model in units of true normals.
+extern "C" int olsq_price(double F, double K, double T, double r, int is_call, const olsb_model* m, int payoff, double barrier, int construction,
+                          int64_t point_offset, int64_t n_points, int32_t n_steps, const uint32_t* sv, const uint32_t* shift, int32_t bits,
+                          int antithetic, olmc_stats* out) {
+    if (!out) return fail(OLMC_ERR_ARG, "null pointer");
+    int rc = sabr_check(m, F);
+    if (rc) return rc;
+    rc = path_payoff_check(payoff, barrier, OLSB_EUROPEAN);
+    if (rc) return rc;
+    const auto call = SobolCall::make({construction, point_offset, n_points, n_steps, sv, shift, bits, antithetic}, 2, &rc);
+    if (!call) return rc;
+    const SabrModel sm = make_sabr(F, T, m, n_steps, 1.0);
+    const PathPayoff pp = path_payoff(F, K, is_call, payoff, barrier);
+    const bool bad = sabr_poisoned(F, K, T, r, m) || pp.nan_barrier;
+    return run_qmc_reduce(*call, 2, heston_qmc_shape, [&](int32_t g, hipStream_t s, const EventPair* timed, const QmcPathLaunch& pl, const ReduceWs& ws) {
+        with_path_family(payoff, OLSB_EUROPEAN, [&](auto f) {
+            with_bridge_anti(pl, [&](auto b, auto a) {
+                with_sabr_kind(m->beta, [&](auto kind) {
+                    launch_timed(sabr_qmc_price_kernel<f, kind, b, a>, dim3(g), dim3(kBlock), s, timed, pl.qr, sm, pp.ec, pl.inv_steps, pl.d_sv, pl.d_shift,
+                                 pl.plan, pl.slabs, ws);
+                });
+            });
+        });
+    }, qmc_stats(r, T, bad, out));
+}
+
+extern "C" int olsq_paths(double F, double T, const olsb_model* m, int construction, int64_t n_points, int32_t n_steps, const uint32_t* sv,
+                          const uint32_t* shift, int32_t bits, int mirror, int path_major, double* forward_host, double* vol_host) {
+    if (!forward_host || !vol_host) return fail(OLMC_ERR_ARG, "null pointer");
+    int rc = sabr_check(m, F);
+    if (rc) return rc;
+    const auto call = SobolCall::make({construction, 0, n_points, n_steps, sv, shift, bits, 0}, 2, &rc);
+    if (!call) return rc;
+    const double bytes = 8.0 * static_cast<double>(n_points) * (n_steps + 1.0);
+    CtxLease lease;
+    rc = qmc_matrix_prologue(*call, 2 * bytes, &lease);
+    if (rc) return rc;
+    DeviceCtx* const c = lease.c;
+    const SabrModel sm = make_sabr(F, T, m, n_steps, 1.0);
+    QmcPathLaunch pl;
+    rc = qmc_matrix_setup(c, *call, &pl);
+    if (rc) return rc;
+    const double flip = mirror ? -1.0 : 1.0;
+    return heston_path_matrices(c, n_points, n_steps, forward_host, vol_host, [&](const EventPair* timed, double* d_forward, double* d_vol) {
+        with_sabr_kind(m->beta, [&](auto kind) {
+            with_bool(pl.bridge, [&](auto b) {
+                with_bool(path_major != 0, [&](auto pm) {
+                    launch_timed(sabr_qmc_paths_kernel<kind, b, pm>, dim3(pl.grid), dim3(kBlock), c->stream, timed, pl.qr, sm, flip, pl.d_sv, pl.d_shift,
+                                 pl.plan, d_forward, d_vol);
+                });
+            });
+        });
+    });
+}
+
+extern "C" int olsq_surface_prices(double F, double T, double r, int is_call, const olsb_model* m, const double* strikes, const int32_t* steps,
+                                   int32_t k, int construction, int64_t point_offset, int64_t n_points, int32_t n_steps, const uint32_t* sv,
+                                   const uint32_t* shift, int32_t bits, int antithetic, olmc_stats* out) {
+    if (!strikes || !steps || !out) return fail(OLMC_ERR_ARG, "null pointer");
+    int rc = sabr_check(m, F);
+    if (rc) return rc;
+    const auto call = SobolCall::make({construction, point_offset, n_points, n_steps, sv, shift, bits, antithetic}, 2, &rc);
+    if (!call) return rc;
+    SurfaceOrder so;
+    rc = surface_cells(strikes, steps, k, n_steps, &so);
+    if (rc) return rc;
+    const SabrModel sm = make_sabr(F, T, m, n_steps, 1.0);
+    const bool bad = sabr_poisoned(F, 0.0, T, r, m);
+    const double sign = is_call ? 1.0 : -1.0;
+    return run_qmc_reduce(*call, 2 * kSurfaceCells, heston_qmc_shape,
+                          [&](int32_t g, hipStream_t s, const EventPair* timed, const QmcPathLaunch& pl, const ReduceWs& ws) {
+        with_bridge_anti(pl, [&](auto b, auto a) {
+            with_sabr_kind(m->beta, [&](auto kind) {
+                launch_timed(sabr_qmc_surface_kernel<kind, b, a>, dim3(g), dim3(kBlock), s, timed, pl.qr, sm, sign, so.cells, pl.d_sv, pl.d_shift, pl.plan,
+                             pl.slabs, ws);
+            });
+        });
+    }, [&](const double* h, int64_t n) { surface_finish(h, so, strikes, steps, k, n, r, T / n_steps, bad, out); });
 }
 
 // ====================================================== Dupire local volatility on Sobol paths ====

@@ -7,7 +7,8 @@ Both are restated here in this package's own code and tied to the reference by t
 Additive: Monte Carlo paths of the process itself (include/olmc_sabr.h) -- dF = sigma F^beta dW1, dsigma = nu sigma dW2, absorbed at 0
 for beta < 1 -- where the expansion degrades (large nu, rho towards -1, the wings) and for the payoffs it does not cover: Europeans,
 Asians, barriers, lookbacks and a strike x maturity surface, each in one launch, and the Monte Carlo smile.  The methods take the
-forward F where DupireLocalVol's take S, and no q.
+forward F where DupireLocalVol's take S, and no q.  `SABRModelQMC` (`model.qmc()`) runs the same methods on scrambled-Sobol points
+(include/olmc_sabr_qmc.h).
 """
 from __future__ import annotations
 
@@ -115,9 +116,19 @@ class SABRModel:
         _check_sizes(n_paths, n_steps)
         return n_paths, n_steps, _seed(seed)
 
+    # The three device calls, each on the sizes and seed _sizes settled: what SABRModelQMC overrides.
+    def _device_price(self, F, K, T, r, is_call, payoff, barrier, n_paths, n_steps, seed, antithetic):
+        return _hip.sabr_price(F, K, T, r, is_call, self._model(), payoff, barrier, n_paths, n_steps, seed, antithetic)
+
+    def _device_paths(self, F, T, n_paths, n_steps, seed, mirror):
+        return _hip.sabr_paths(F, T, self._model(), n_paths, n_steps, seed, mirror=mirror, path_major=True)
+
+    def _device_surface(self, F, T, r, is_call, strikes, steps, n_paths, n_steps, seed, antithetic):
+        return _hip.sabr_surface_prices(F, T, r, is_call, self._model(), strikes, steps, n_paths, n_steps, seed, antithetic)
+
     def _price_payoff(self, payoff, barrier, F, K, T, r, option_type, n_paths, n_steps, seed, antithetic, return_error):
         n_paths, n_steps, s = self._sizes(F, n_paths, n_steps, seed)
-        return _result(_hip.sabr_price(F, K, T, r, option_type == "call", self._model(), payoff, barrier, n_paths, n_steps, s, antithetic), return_error)
+        return _result(self._device_price(F, K, T, r, option_type == "call", payoff, barrier, n_paths, n_steps, s, antithetic), return_error)
 
     def price_monte_carlo(self, F: float, K: float, T: float, r: float, option_type: Literal["call", "put"] = "call",
                           n_paths: Optional[int] = None, n_steps: Optional[int] = None, seed: Optional[int] = None, antithetic: bool = False,
@@ -132,7 +143,7 @@ class SABRModel:
         """The forward and volatility matrices, each (n_paths, n_steps + 1), of price_monte_carlo's recursion for the same seed; column
         0 is (F, alpha) as given.  mirror=True gives the antithetic leg."""
         n_paths, n_steps, s = self._sizes(F, n_paths, n_steps, seed)
-        return _hip.sabr_paths(F, T, self._model(), n_paths, n_steps, s, mirror=mirror, path_major=True)
+        return self._device_paths(F, T, n_paths, n_steps, s, mirror)
 
     def price_asian(self, F: float, K: float, T: float, r: float, option_type: Literal["call", "put"] = "call",
                     avg_type: Literal["arithmetic", "geometric"] = "arithmetic", n_paths: Optional[int] = None, n_steps: Optional[int] = None,
@@ -164,8 +175,8 @@ class SABRModel:
         ks = _strike_list(strikes)
         n_paths, n_steps, s = self._sizes(F, n_paths, n_steps, seed)
         T, steps = _surface_steps(maturities, n_steps)
-        return _fill_surface(ks, steps, lambda cell_k, cell_m: _hip.sabr_surface_prices(F, T, r, option_type == "call", self._model(), cell_k, cell_m,
-                                                                                         n_paths, n_steps, s, antithetic), return_error)
+        return _fill_surface(ks, steps, lambda cell_k, cell_m: self._device_surface(F, T, r, option_type == "call", cell_k, cell_m, n_paths, n_steps, s,
+                                                                                   antithetic), return_error)
 
     def smile_monte_carlo(self, F: float, T: float, strikes, n_paths: Optional[int] = None, n_steps: Optional[int] = None,
                           seed: Optional[int] = None, antithetic: bool = False) -> np.ndarray:
@@ -181,13 +192,54 @@ class SABRModel:
                 idx = [i for i in chunk if (ks[i] >= F) == is_call]
                 if not idx:
                     continue
-                sts = _hip.sabr_surface_prices(F, T, 0.0, is_call, self._model(), [ks[i] for i in idx], [n_steps] * len(idx), n_paths, n_steps, s, antithetic)
+                sts = self._device_surface(F, T, 0.0, is_call, [ks[i] for i in idx], [n_steps] * len(idx), n_paths, n_steps, s, antithetic)
                 for i, st in zip(idx, sts):
                     try:
                         vols[i] = implied_volatility(st.price, F, ks[i], T, 0.0, "call" if is_call else "put", 0.0)
                     except ValueError:
                         pass
         return vols
+
+    def qmc(self, path_construction: Literal["bridge", "sequential"] = "bridge") -> "SABRModelQMC":
+        """This model on scrambled-Sobol points: a view with the same four parameters."""
+        return SABRModelQMC(self.alpha, self.beta, self.rho, self.nu, path_construction=path_construction)
+
+
+@dataclass
+class SABRModelQMC(SABRModel):
+    """SABRModel on scrambled-Sobol paths (include/olmc_sabr_qmc.h): every Monte Carlo method keeps its signature and meaning,
+    simulate_paths(mirror=), price_surface, smile_monte_carlo and antithetic included; n_paths counts Sobol points and path i is point i
+    of scipy.stats.qmc.Sobol(d = 2 n_steps, scramble=True, seed), two dimensions per step.  path_construction="bridge" (the default, at
+    most 1024 steps) builds the two Brownian paths by the breadth-first bridge and steps on their increments, "sequential" gives step t
+    dimensions 2t and 2t + 1 (at most 10600 steps).  The table refusals are heston._qmc_tables', ValueErrors raised before the device is
+    touched.  return_error's figure is the naive standard error of the payoffs: for Sobol points it overstates the error.  With
+    seed=None every call draws a scramble of its own; SABRMCAdapter(model.qmc(), ...) differentiates on the same points at its fixed
+    seed, one launch per bump."""
+
+    path_construction: str = "bridge"
+
+    def __post_init__(self):
+        super().__post_init__()
+        if self.path_construction not in ("bridge", "sequential"):
+            raise ValueError("path_construction must be 'bridge' or 'sequential'")
+
+    def _sobol(self, n_paths, n_steps, seed):
+        """(sv, shift, bridge) of Sobol(d = 2 n_steps, seed); sobol_tables caches them, so price_surface's launches share one pair."""
+        from .heston import _qmc_tables
+
+        return _qmc_tables("qmc", self.path_construction, n_paths, n_steps, seed)
+
+    def _device_price(self, F, K, T, r, is_call, payoff, barrier, n_paths, n_steps, seed, antithetic):
+        sv, shift, bridge = self._sobol(n_paths, n_steps, seed)
+        return _hip.sabrq_price(F, K, T, r, is_call, self._model(), payoff, barrier, n_paths, sv, shift, bridge, antithetic)
+
+    def _device_paths(self, F, T, n_paths, n_steps, seed, mirror):
+        sv, shift, bridge = self._sobol(n_paths, n_steps, seed)
+        return _hip.sabrq_paths(F, T, self._model(), n_paths, sv, shift, bridge, mirror=mirror, path_major=True)
+
+    def _device_surface(self, F, T, r, is_call, strikes, steps, n_paths, n_steps, seed, antithetic):
+        sv, shift, bridge = self._sobol(n_paths, n_steps, seed)
+        return _hip.sabrq_surface_prices(F, T, r, is_call, self._model(), strikes, steps, n_paths, sv, shift, bridge, antithetic)
 
 
 def calibrate_sabr(F: float, T: float, strikes: np.ndarray, market_vols: np.ndarray, beta: float = 0.5,
